@@ -14,8 +14,14 @@ Default scaling is WEAK -- the path partitions into independent images with no d
 configuration's 256 images (at N = 1 that IS BASELINE config 3; at N = 8 it is 2 048 images, 256 per GPU);
 `--scaling strong` is config 3 read literally: 256 images in total, 32 per GPU at N = 8.  Rank 0 prints one JSON line.
 
-At N = 1 the line also carries `extra`: BASELINE configs 2, 4 and 5 measured the same way (HIP events on the
-launch stream, inputs resident in HBM), each with its own roofline figures, parity flag and CPU baseline.
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.  `--full` adds
+everything else: the parity spot check against the CPU oracle, the copy / access-pattern / recommended-pitch
+calibrations of the roofline, the CPU baseline and, at N = 1, `configs` (BASELINE configs 2, 4 and 5 measured the
+same way -- HIP events on the launch stream, inputs resident in HBM -- each with its own roofline figures, parity
+flag and CPU baseline).
+
+`--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of rank 0's BGRA output and
+per-row channel sums of its images) as float .npy files, for output-for-output comparisons of two builds.
 
 PyTorch is plumbing here: device memory, the stream handle and torch.distributed for process bootstrap.
 The compute goes through the C ABI of ffpic_amd/libffpic_hip.so.
@@ -1099,6 +1105,36 @@ def compact_configs(extra):
     return out
 
 
+DUMP_SEED = 20261016
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_sample(n, H):
+    """The fixed, seeded selection --dump-outputs writes for a batch of n images of H rows: up to 8 images (the first and the
+    last among them) x up to 64 rows for the pixels, up to 256 images for the per-row sums."""
+    rng = np.random.default_rng(DUMP_SEED)
+    images = np.unique(np.concatenate([[0, n - 1], rng.choice(n, min(n, 6), replace=False)]))
+    rows = np.sort(rng.choice(H, min(H, 64), replace=False))
+    sum_images = np.arange(n) if n <= 256 else np.sort(rng.choice(n, 256, replace=False))
+    return images, rows, sum_images
+
+
+def dump_outputs(path, out, n, H, W, stride):
+    """What the caller of the timed path receives -- n BGRA images of H x W at `stride` bytes in `out` -- as float .npy files:
+    bgra_sample.npy   float32 [images, rows, W, 4]: the sampled rows of the sampled images, every pixel of them
+    bgra_row_sums.npy float64 [sum_images, H, 4]: each row's B, G, R, A sums (exact in float64), i.e. every pixel of those images"""
+    images, rows, sum_images = dump_sample(n, H)
+    view = out[:n * stride].view(n, stride)[:, :H * W * 4].view(n, H, W, 4)
+    arrays = {"bgra_sample": view[torch.as_tensor(images, device=out.device)][:, torch.as_tensor(rows, device=out.device)].float(),
+              "bgra_row_sums": torch.stack([view[int(i)].to(torch.int32).sum(dim=1) for i in sum_images]).double()}
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1108,11 +1144,17 @@ def main():
     ap.add_argument("--images", type=int, default=0, help="override the number of images (per batch if strong, per GPU if weak)")
     ap.add_argument("--scaling", default="weak", choices=["strong", "weak"],
                     help="weak (default): the configuration's batch per GPU (independent images, no data-path collective); strong: that batch shared out over the GPUs (BASELINE config 3 read literally: 256 images in total)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C4 / C5 measurements of `extra`")
-    ap.add_argument("--extras", default="", help="comma-separated subset of c2,jpeg_layouts,c4,c5,f1,stage_kernels to measure (default: all)")
-    ap.add_argument("--extra-file", default="", help="also write the result line WITH the verbose `extra` object (every stage, roofline and sample description) to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (a seeded sample, float .npy, at most 64 MB) to DIR")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check against the CPU oracle, the roofline calibrations, the CPU baseline and (N = 1) the other configurations")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline legs of --full (a plain run has none)")
+    ap.add_argument("--no-extra", action="store_true", help="skip the C2 / C4 / C5 measurements of --full's `extra` (a plain run has none)")
+    ap.add_argument("--extras", default="", help="with --full: comma-separated subset of c2,jpeg_layouts,c4,c5,f1,stage_kernels to measure (default: all)")
+    ap.add_argument("--extra-file", default="", help="with --full: also write the result line WITH the verbose `extra` object (every stage, roofline and sample description) to this file")
     a = ap.parse_args()
+    if not a.full and (a.extras or a.extra_file):
+        ap.error("--extras and --extra-file select parts of --full: add --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1160,8 +1202,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # parity spot check on this rank's first AND last image, before warmup (outside the timed region;
-    # the CPU-side check idles the GPU, so it must not sit between warmup and timing), and the per-image
+    # --full: parity spot check on this rank's first AND last image, before warmup (outside the timed region;
+    # the CPU-side check idles the GPU, so it must not sit between warmup and timing); always: the per-image
     # checksums the rank vouches for its output with in the batch close
     parity = None
     step()
@@ -1169,7 +1211,7 @@ def main():
     capi.check(L.ffhip_bgra_checksum(out.data_ptr(), pitch, stride, W, H, n, sums.data_ptr(), stream), "ffhip_bgra_checksum")
     torch.cuda.synchronize()
     checksum = int(sums[:n].sum().item()) & 0xFFFFFFFFFFFFFFFF
-    if rank == 0:
+    if rank == 0 and a.full:
         O = oracle_lib()
         mcus = cols * rows
         parity = True
@@ -1202,10 +1244,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     complete = shard.batch_complete(records, total_images)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, n, H, W, stride)
 
-    # copy-kernel calibration of the achievable HBM rate, same process, same buffers
+    # --full: copy-kernel calibration of the achievable HBM rate, same process, same buffers
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and a.full:
         nbytes = min(out.numel(), 4 << 30) // 2 // 16 * 16
         src, dst = out[:nbytes], out[nbytes:2 * nbytes]
         for _ in range(2):
@@ -1220,7 +1264,7 @@ def main():
     # the same launch into a buffer of the pitch the library recommends to callers that own their output (ffhip_bgra_layout: + 1 KiB per row);
     # reported next to the headline, which stays at the reference's pitch
     rec_pitch = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         try:
             rp, rs = C.c_int64(), C.c_int64()
             capi.check(L.ffhip_bgra_layout(C.byref(geom), C.byref(rp), C.byref(rs)), "ffhip_bgra_layout")
@@ -1244,7 +1288,7 @@ def main():
     # the fused kernel's own access pattern with the arithmetic taken out (ffhip_jpeg_pattern_calibrate: same grid, loads, store addresses) on the
     # HEADLINE's buffers -- the ceiling this placement of them allows; `out` holds meaningless bytes afterwards (nothing below reads it)
     pattern_gbs = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         try:
             cal = lambda: capi.check(L.ffhip_jpeg_pattern_calibrate(C.byref(geom), n, t_y.data_ptr(), t_u.data_ptr(), t_v.data_ptr(), t_q.data_ptr(), 0,
                                                                       out.data_ptr(), pitch, stride, stream), "ffhip_jpeg_pattern_calibrate")
@@ -1290,9 +1334,9 @@ def main():
         }
         if rehearse:
             line["config"]["rehearsal"] = "all ranks on one GPU over gloo: exercises the N > 1 control path only, the value is meaningless"
-        if not a.no_cpu and world == 1:   # the CPU leg is timed on rank 0 at N = 1 only
+        if a.full and not a.no_cpu and world == 1:   # the CPU leg is timed on rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline(cols, rows, t_y, t_u, t_v, q)
-        if world == 1 and not a.no_extra:
+        if a.full and world == 1 and not a.no_extra:
             del t_y, t_u, t_v, out
             torch.cuda.empty_cache()
             T = Timer(L, stream)

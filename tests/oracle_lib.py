@@ -5,6 +5,7 @@ TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py.  The product (ffpic_amd) never imports this.
 """
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -100,6 +101,85 @@ def ffo():
 
 def have_ref():
     return os.path.exists(REF_SO) or os.path.isdir("/root/reference")
+
+
+REF_OUTPUTS = os.path.join(ROOT, "tests", "golden", "ref_outputs.npz")
+# FFPIC_RECORD_REF=1, with the reference present: write ref_outputs.npz anew from the tests that run in the session
+# (tests/test_oracle_vs_ref.py and tests/test_entropy.py::test_bmp_bytes_equal_reference_writer, together)
+RECORD_REF = os.environ.get("FFPIC_RECORD_REF") == "1"
+_stored = None
+
+
+def _ref_store(update=None):
+    global _stored
+    if _stored is None:
+        _stored = dict(np.load(REF_OUTPUTS)) if os.path.exists(REF_OUTPUTS) and not RECORD_REF else {}
+    if update:
+        _stored.update(update)
+        np.savez_compressed(REF_OUTPUTS, **_stored)
+    return _stored
+
+
+def _as_tuple(a):
+    return tuple(np.asarray(x) for x in a) if isinstance(a, tuple) else (np.asarray(a),)
+
+
+def ref_digest(arrays):
+    """SHA-256 over the dtype, shape and bytes of each array, in order"""
+    h = hashlib.sha256()
+    for a in _as_tuple(arrays):
+        h.update(f"{a.dtype.str}{a.shape}".encode())
+        h.update(np.ascontiguousarray(a).tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def ref_inputs(key, compute):
+    """Reference outputs a test hands to the oracle as INPUTS (an array or a tuple of arrays, kept whole in
+    tests/golden/ref_outputs.npz): compute() through the compiled reference where it can be had -- and then equal to the
+    stored copy -- else the stored copy."""
+    store = _ref_store()
+    if not have_ref():
+        if key in store:
+            return store[key]
+        parts = []
+        while f"{key}/{len(parts)}" in store:
+            parts.append(store[f"{key}/{len(parts)}"])
+        if not parts:
+            raise KeyError(f"{key}: not in {REF_OUTPUTS}")
+        return tuple(parts)
+    got = compute()
+    arrays = {f"{key}/{i}": a for i, a in enumerate(got)} if isinstance(got, tuple) else {key: np.asarray(got)}
+    if RECORD_REF:
+        _ref_store(arrays)
+    else:
+        for k, a in arrays.items():
+            s = store.get(k)
+            assert s is not None and s.dtype == a.dtype and np.array_equal(s, a), f"{k}: the stored copy is not what the reference computes"
+    return got
+
+
+def check_ref(key, got, compute):
+    """`got` (an array or a tuple of arrays, what the oracle computed) must be what the reference computes from the same
+    inputs.  Where the compiled reference can be had, compute() runs it: element-for-element comparison, and the SHA-256
+    digest stored in tests/golden/ref_outputs.npz must be that of its outputs.  Elsewhere the digest of `got` must equal
+    the stored one."""
+    got = _as_tuple(got)
+    if not have_ref():
+        want = _ref_store().get("sha256:" + key)
+        assert want is not None, f"{key}: no digest in {REF_OUTPUTS}"
+        assert np.array_equal(ref_digest(got), want), f"{key}: not what the reference computes (stored digest)"
+        return
+    exp = _as_tuple(compute())
+    assert len(got) == len(exp), key
+    for i, (g, e) in enumerate(zip(got, exp)):
+        assert g.dtype == e.dtype and g.shape == e.shape, (key, i, g.dtype, g.shape, e.dtype, e.shape)
+        bad = np.argwhere(g != e)
+        assert bad.size == 0, f"{key}[{i}]: first difference at {tuple(int(x) for x in bad[0])}"
+    if RECORD_REF:
+        _ref_store({"sha256:" + key: ref_digest(exp)})
+    else:
+        want = _ref_store().get("sha256:" + key)
+        assert want is not None and np.array_equal(ref_digest(exp), want), f"{key}: the stored digest is not that of the reference's outputs"
 
 
 def ref():

@@ -21,12 +21,46 @@ def _line(out):
 
 
 def test_one_gpu_line_small():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--images", "5", "--no-cpu", "--no-extra"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--images", "5", "--full", "--no-cpu", "--no-extra"],
                          capture_output=True, text=True, cwd=ROOT, timeout=600)
     rec = _line(out)
     assert rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["scaling"] == "weak"
     assert rec["config"]["batch_complete"] is True and rec["config"]["parity_vs_oracle_first_and_last_image"] is True
     assert rec["config"]["images_total"] == 5 and rec["roofline"]["bound"] == "hbm" and rec["roofline"]["frac"] > 0
+
+
+def test_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times the K steps and nothing else; --dump-outputs writes the last step's BGRA sample and row sums,
+    which must be the oracle's pixels for the inputs the bench generates from its seed."""
+    import numpy as np
+    import torch
+    import bench
+    import oracle_lib as O
+    from ffpic_amd import capi
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--workload", "c2", "--images", "5",
+                          "--dump-outputs", str(d)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    rec = _line(out)
+    assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["config"]["batch_complete"] is True
+    assert rec["config"]["parity_vs_oracle_first_and_last_image"] is None and rec["roofline"]["copy_kernel_GBps"] is None
+    assert "cpu_baseline" not in rec and "configs" not in rec
+    files = sorted(os.listdir(d))
+    assert files == ["bgra_row_sums.npy", "bgra_sample.npy"]
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    sample, sums = np.load(d / "bgra_sample.npy"), np.load(d / "bgra_row_sums.npy")
+    assert sample.dtype == np.float32 and sums.dtype == np.float64
+    cols, rows, _, _ = bench.WORKLOADS["c2"]
+    capi.require_device(0)
+    t_y, t_u, t_v, q = bench.gen_batch_on_device(torch.device("cuda", 0), cols, rows, 5, seed=0)
+    images, sample_rows, sum_images = bench.dump_sample(5, rows * 16)
+    mcus = cols * rows
+    assert sample.shape == (len(images), len(sample_rows), cols * 16, 4) and sums.shape == (len(sum_images), rows * 16, 4)
+    for k, i in enumerate(sum_images):
+        exp = O.oracle_jpeg_recon(O.make_geom(cols, rows), t_y[i * mcus * 256:(i + 1) * mcus * 256].cpu().numpy(),
+                                  t_u[i * mcus * 64:(i + 1) * mcus * 64].cpu().numpy(), t_v[i * mcus * 64:(i + 1) * mcus * 64].cpu().numpy(), q)[0]
+        assert np.array_equal(sums[k], exp.astype(np.int64).sum(axis=1)), i
+        if i in images:
+            assert np.array_equal(sample[list(images).index(i)], exp[sample_rows]), i
 
 
 @pytest.mark.parametrize("scaling,total,launcher", [("strong", 7, "self"), ("weak", 6, "torchrun")])
@@ -41,7 +75,7 @@ def test_two_rank_rehearsal(scaling, total, launcher):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["FFHIP_BENCH_REHEARSE"] = "1"
     images = 7 if scaling == "strong" else 3
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--images", str(images), "--scaling", scaling, "--no-cpu"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--images", str(images), "--scaling", scaling, "--full", "--no-cpu"]
     head = [sys.executable] if launcher == "self" else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                                         "--master-port", str(port)]
     out = subprocess.run(head + tail, capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)

@@ -126,30 +126,30 @@ def test_failed_picture_does_not_keep_stale_planes():
         assert np.array_equal(cy[:yb], cy[2 * yb:]) and cy[:yb].any()
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="needs oracle/_ref for the reference's bmpwriter")
 def test_bmp_bytes_equal_reference_writer(tmp_path):
-    R = O.ref()
-
-    class Display(C.Structure):   # display/display.h:10-19
-        _fields_ = [("name", C.c_char_p), ("width", C.c_int), ("height", C.c_int), ("private", C.c_void_p),
-                    ("init", C.CFUNCTYPE(C.c_int, C.c_char_p, C.c_int, C.c_int)), ("uninit", C.CFUNCTYPE(C.c_int)),
-                    ("draw_pixels", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int))]
-    bw = Display.in_dll(R, "bmp_writer")
     rng = np.random.default_rng(1)
     w, h = 40, 24
     px = rng.integers(0, 256, size=(h, w, 4)).astype(np.uint8)
-    title = str(tmp_path / "ref")
-    bw.init(title.encode(), w, h)
-    bw.draw_pixels(px.ctypes.data, 0, 0, w, h, 32, w * 4, 0)
-    bw.uninit()
+
+    def ref():
+        class Display(C.Structure):   # display/display.h:10-19
+            _fields_ = [("name", C.c_char_p), ("width", C.c_int), ("height", C.c_int), ("private", C.c_void_p),
+                        ("init", C.CFUNCTYPE(C.c_int, C.c_char_p, C.c_int, C.c_int)), ("uninit", C.CFUNCTYPE(C.c_int)),
+                        ("draw_pixels", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int))]
+        bw = Display.in_dll(O.ref(), "bmp_writer")
+        title = str(tmp_path / "ref")
+        bw.init(title.encode(), w, h)
+        bw.draw_pixels(px.ctypes.data, 0, 0, w, h, 32, w * 4, 0)
+        bw.uninit()
+        return np.fromfile(title + ".bmp", np.uint8)
     mine = str(tmp_path / "mine.bmp")
     capi.check(capi.lib().ffhip_bmp_write(mine.encode(), px.ctypes.data, w, h, w * 4))
-    assert open(mine, "rb").read() == open(title + ".bmp", "rb").read()
+    O.check_ref("bmp_writer_40x24", np.fromfile(mine, np.uint8), ref)
     # a padded pitch writes the same file
     padded = np.zeros((h, w + 8, 4), np.uint8)
     padded[:, :w] = px
     capi.check(capi.lib().ffhip_bmp_write(mine.encode(), padded.ctypes.data, w, h, (w + 8) * 4))
-    assert open(mine, "rb").read() == open(title + ".bmp", "rb").read()
+    O.check_ref("bmp_writer_40x24", np.fromfile(mine, np.uint8), ref)
 
 
 def test_front_end_under_sanitizers(tmp_path):

@@ -13,7 +13,7 @@ prof() { # name, program args...
   find /tmp/rp_$name -name "*kernel_stats.csv" -exec cp {} $O/${name}_kernel_stats.csv \;
   echo "done $name"
 }
-prof bench $R/bench.py
+prof bench $R/bench.py --full
 grep '^{' $O/bench.stdout | tail -1 > $O/bench.json
 prof jpeg_geoms $R/tests/tools/bench_jpeg_geoms.py
 prof hevc_residual $R/tests/tools/bench_hevc_residual.py

@@ -23,7 +23,7 @@ pmc() { # name, kernel filter, counters..., then "--", program args
   python3 $R/tests/tools/pmc_summary.py /tmp/rp_$name --kernel $kern >> $O/$name.txt
   echo "done $name"
 }
-prof bench $R/bench.py --extra-file $O/bench_full.json
+prof bench $R/bench.py --full --extra-file $O/bench_full.json
 grep '^{' $O/bench.stdout | tail -1 > $O/bench.json
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/rp_pmc_$c

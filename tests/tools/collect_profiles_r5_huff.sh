@@ -29,6 +29,6 @@ for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR S
   echo "done pmc set"
 done
 cd $R
-python3 bench.py --extras f1 --extra-file $O/bench_f1_full.json > $O/bench_f1.json 2> /dev/null
+python3 bench.py --full --extras f1 --extra-file $O/bench_f1_full.json > $O/bench_f1.json 2> /dev/null
 echo "done bench f1"
 ls -la $O
