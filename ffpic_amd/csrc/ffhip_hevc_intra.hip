@@ -30,10 +30,7 @@
 #include <cstring>
 #include <thread>
 #include <vector>
-#include <map>
-#include <memory>
 #include <mutex>
-#include <new>
 
 #ifndef FFHIP_HEVC_INTRA_WAVES
 #define FFHIP_HEVC_INTRA_WAVES 256 /* waves of the grouped form's one launch: enough for the widest wavefront of an 8K picture (~200 groups)
@@ -1601,9 +1598,6 @@ extern "C" int ffhip_debug_hevc_plan_result(uint32_t out[8])
     return FFHIP_OK;
 }
 
-
-#define SCRATCH_HEVC_INTRA 3
-
 extern "C" size_t ffhip_hevc_plan_gpu_words(long long n_tus, const int pw[3], const int ph[3], const int wl[3]);
 extern "C" int ffhip_hevc_plan_gpu(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3],
                                    uint32_t *scratch, hipStream_t st, const u32x4 **sched, const u32x4 **groups, const uint32_t **wait_idx,
@@ -2394,45 +2388,22 @@ extern "C" int ffhip_hevc_intra_recon(const ffhip_hevc_tu *h_tus, const ffhip_he
  * eight-picture call's span when it ran in front of the one grouped kernel) runs on streams of the library's own while chunk k reconstructs, and
  * the chunks' grouped kernels run on two streams in turn so that one chunk's start fills the other's tail.  What makes that legal is the
  * caller's word that tiles never reference each other; the results are those of ffhip_hevc_intra_recon on the whole list. */
-#define SCRATCH_HEVC_TILES_JT 20
-#define SCRATCH_HEVC_TILES_CHUNK 21 /* .. + 3 */
-#define SCRATCH_HEVC_TILES_ONE 25   /* .. + 1 */
-/* Who used a one-chunk scratch last: the scratch belongs to (kind, CALLER's stream), so its guard does too -- the parity of the call, and per scratch an
- * event recorded on the caller's stream behind the call's grouped kernel.  (Kept per calling thread until round 6: a thread that alternated between two
- * streams, or two threads on one stream, could let a pre-pass rewrite a schedule the grouped kernel of another call was still reading.)  Calls that
- * share a stream take turns for the length of their enqueue: they share the scratch. */
-namespace {
-struct TileGuard {
-    std::mutex mu;
-    unsigned parity = 0;
-    bool recorded[2] = {false, false};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-};
-std::mutex g_tile_guard_mu;
-std::map<void *, std::unique_ptr<TileGuard>> g_tile_guards;
-TileGuard *tile_guard_for(void *stream)
+/* Who used a one-chunk scratch last: the scratch belongs to (kind, device, CALLER's stream), so its guard does too (FfhipTileGuard, in the stream's
+ * entry of the library's registry).  (Kept per calling thread until round 6: a thread that alternated between two streams, or two threads on one
+ * stream, could let a pre-pass rewrite a schedule the grouped kernel of another call was still reading.)  NULL when its events could not be made. */
+static FfhipTileGuard *tile_guard_for(void *stream)
 {
-    std::lock_guard<std::mutex> l(g_tile_guard_mu);
-    std::unique_ptr<TileGuard> &g = g_tile_guards[stream];
-    if (!g) {
-        std::unique_ptr<TileGuard> n(new (std::nothrow) TileGuard);
-        if (!n) return nullptr;
-        if (hipEventCreateWithFlags(&n->ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&n->ev[1], hipEventDisableTiming) != hipSuccess) {
+    std::lock_guard<std::mutex> l(g_ffhip_state_mu);
+    FfhipTileGuard &g = ffhip_stream_state(stream)->tiles;
+    if (!g.ev[0]) {
+        if (hipEventCreateWithFlags(&g.ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&g.ev[1], hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
-            if (n->ev[0]) (void)hipEventDestroy(n->ev[0]);
-            return nullptr; /* (the map keeps an empty slot: the next call tries again) */
+            if (g.ev[0]) (void)hipEventDestroy(g.ev[0]);
+            g.ev[0] = g.ev[1] = nullptr; /* the next call tries again */
+            return nullptr;
         }
-        g = std::move(n);
     }
-    return g.get();
-}
-} // namespace
-extern "C" void ffhip_hevc_tiles_release(void) /* ffhip_release_caches: nothing of the library's is in flight, the scratches go as well */
-{
-    std::lock_guard<std::mutex> l(g_tile_guard_mu);
-    for (auto &e : g_tile_guards)
-        if (e.second) { (void)hipEventDestroy(e.second->ev[0]); (void)hipEventDestroy(e.second->ev[1]); }
-    g_tile_guards.clear();
+    return &g;
 }
 extern "C" int ffhip_hevc_intra_recon_tiles(const ffhip_hevc_tu *h_tus, const ffhip_hevc_tu *d_tus, long long n_tus, const long long *tile_first, int n_tiles,
                                             const int16_t *d_residual, int16_t *d_y, int16_t *d_cb, int16_t *d_cr, int width_y, int height_y, int y_stride,
@@ -2472,9 +2443,9 @@ extern "C" int ffhip_hevc_intra_recon_tiles(const ffhip_hevc_tu *h_tus, const ff
      * alternates between TWO scratches, so the pre-pass of call n + 1 only waits for call n - 1 and runs next to the tail of call n's grouped kernel
      * (whose waves leave as the wavefront narrows), the colour conversion behind it and the next residual batches. */
     if (chunks == 1) {
-        TileGuard *const guard = tile_guard_for(stream);
+        FfhipTileGuard *const guard = tile_guard_for(stream);
         if (!guard) return FFHIP_EIO;
-        std::lock_guard<std::mutex> turn(guard->mu);
+        std::lock_guard<std::mutex> turn(guard->turn);
         /* ONE chunk -- the default: cutting the list does not pay (below) --, but the pre-pass does not wait for `stream`: it reads the TU list alone,
          * so it runs while the stream is still busy with what the caller enqueued in front of this call -- the residual batches of this picture, the
          * colour conversion of the picture before.  (d_tus must be COMPLETE when the call is made: see the header.) */

@@ -233,9 +233,6 @@ __global__ __launch_bounds__(256) void k_jpeg_huff(HuffArgs a)
     if (bad) a.status[w.x] = FFHIP_EINVAL;
 }
 
-#define SCRATCH_HUFF 4
-#define SCRATCH_HUFF_SYNC 30
-
 namespace {
 /* One pass over a picture's entropy-coded segment: the bytes without their stuffing (FF 00 -> FF) into dst, every
  * restart interval 4-byte aligned and followed by at least 4 zero bytes, seg[k] = offset of interval k in that clean
@@ -369,7 +366,6 @@ extern "C" int ffhip_jpeg_lut_test(const uint8_t *file, size_t len, int which, u
  * and the Huffman kernel's own time by HIP events on the call's stream */
 static thread_local double g_huff_times[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define SYNC_PARTS FFHIP_HUFF_PARTS
-thread_local FfhipHuffThen g_ffhip_huff_then = {0, nullptr, 0, 0};
 /* (the upload stream, the second kernel stream and the events of a call are the thread's and the device's: ffhip_huff_streams_get) */
 /* bits of a subsequence, unless FFHIP_JPEG_SYNC_BITS sets them: by the bits an MCU takes (huff_sync_enqueue has the measurements) */
 static uint32_t sync_sub_bits(unsigned long long bits, unsigned long long mcus)
@@ -410,22 +406,11 @@ struct SyncJob {
 static int huff_sync_enqueue(SyncJob &job, void *stream, uint32_t **h_cnt);
 static int huff_sync_finish(SyncJob &job, void *stream, uint32_t *h_cnt, int *status);
 
-/* the header records of a batch, kept by the thread between calls (84 MB of fresh pages for 4 096 files, and their return, are milliseconds);
- * ffhip_release_caches lets the calling thread's go */
-static thread_local std::unique_ptr<struct jpeg_hdr[]> hdr_keep;
-static thread_local size_t hdr_cap = 0;
-extern "C" void ffhip_huff_release_thread(void)
+/* then: reconstruct the pictures into then->bgra behind each part of the batch as it is decoded (ffhip_jpeg_decode_files_device) */
+int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
+                                int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant, int *status, void *stream,
+                                const FfhipHuffThen *then)
 {
-    hdr_keep.reset();
-    hdr_cap = 0;
-}
-
-extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
-                                            const ffhip_jpeg_geom *geom, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v,
-                                            uint16_t *d_quant, int *status, void *stream)
-{
-    const FfhipHuffThen then = g_ffhip_huff_then;
-    g_ffhip_huff_then.on = 0;
     if (n < 0 || !geom || (n > 0 && (!files || !lens || !d_coef_y || !d_quant || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
     if (geom->ncomp == 3 && (!d_coef_u || !d_coef_v)) return FFHIP_EINVAL;
@@ -437,14 +422,8 @@ extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const s
     const bool times = FFHIP_ENV("FFHIP_HUFF_TIMES") != nullptr; /* host phases on stderr */
     const auto T0 = std::chrono::steady_clock::now();
     /* ---- host, pictures over threads: headers, tables, restart-interval starts ---- */
-    /* (not a std::vector: that would zero 20 KB a file on this thread before the parsing threads start -- 84 MB and 10 ms for 4 096 thumbnails -- and
-     * ffhip_jpeg_parse clears its record itself) */
-    if ((size_t)n > hdr_cap) {
-        hdr_keep.reset(new (std::nothrow) struct jpeg_hdr[(size_t)n + (size_t)n / 4]);
-        hdr_cap = hdr_keep ? (size_t)n + (size_t)n / 4 : 0;
-        if (!hdr_keep) return FFHIP_ENOMEM;
-    }
-    struct jpeg_hdr *const hdr = hdr_keep.get();
+    struct jpeg_hdr *const hdr = ffhip_huff_hdr_records((size_t)n); /* the calling thread's, kept between calls */
+    if (!hdr) return FFHIP_ENOMEM;
     std::vector<std::vector<uint32_t>> segs((size_t)n);
     std::vector<std::vector<uint32_t>> raws((size_t)n); /* per picture: its intervals' own lengths */
     parallel_for(n, n_threads, [&](int i) {
@@ -667,9 +646,9 @@ extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const s
                 job.plane[1] = d_coef_u ? d_coef_u + (size_t)p_lo * mcus * images[0].nb[1] * 64 : nullptr;
                 job.plane[2] = d_coef_v ? d_coef_v + (size_t)p_lo * mcus * images[0].nb[2] * 64 : nullptr;
                 rc = huff_sync_enqueue(job, pstream, &h_cnt[part]);
-                if (!rc && then.on) /* the part's pictures: coefficients -> BGRA while the next part's bytes come up */
+                if (!rc && then) /* the part's pictures: coefficients -> BGRA while the next part's bytes come up */
                     rc = ffhip_jpeg_recon_batch(geom, p_hi - p_lo, job.plane[0], job.plane[1], job.plane[2], d_quant + (size_t)p_lo * 256, 256,
-                                                then.bgra + (int64_t)p_lo * then.image_stride, then.pitch, then.image_stride, nullptr, 0, pstream);
+                                                then->bgra + (int64_t)p_lo * then->image_stride, then->pitch, then->image_stride, nullptr, 0, pstream);
             }
             if (rc) return fail(rc); /* nothing of this call may be in flight when its buffers are handed back */
         }
@@ -713,8 +692,8 @@ extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const s
     }
     HUFF_CHECK(hipGetLastError());
     (void)hipEventRecord(g_huff_ev[1], st);
-    if (!use_sync && then.on) {
-        const int rc = ffhip_jpeg_recon_batch(geom, n, d_coef_y, d_coef_u, d_coef_v, d_quant, 256, then.bgra, then.pitch, then.image_stride, nullptr, 0, stream);
+    if (!use_sync && then) {
+        const int rc = ffhip_jpeg_recon_batch(geom, n, d_coef_y, d_coef_u, d_coef_v, d_quant, 256, then->bgra, then->pitch, then->image_stride, nullptr, 0, stream);
         if (rc) return fail(rc);
     }
     /* per-picture verdicts come back with the stream (tiny); the staging buffer is free again after this sync */
@@ -736,9 +715,9 @@ extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const s
             SyncJob &job = jobs[part];
             const int p_lo = (int)((job.o_status - o_status) / 4);
             int rc = huff_sync_finish(job, job.stream, h_cnt[part], status + p_lo);
-            if (!rc && job.reran && then.on) { /* the part's passes ran only now: so must its reconstruction (and the caller's stream be behind it) */
+            if (!rc && job.reran && then) { /* the part's passes ran only now: so must its reconstruction (and the caller's stream be behind it) */
                 rc = ffhip_jpeg_recon_batch(geom, job.n, job.plane[0], job.plane[1], job.plane[2], d_quant + (size_t)p_lo * 256, 256,
-                                            then.bgra + (int64_t)p_lo * then.image_stride, then.pitch, then.image_stride, nullptr, 0, job.stream);
+                                            then->bgra + (int64_t)p_lo * then->image_stride, then->pitch, then->image_stride, nullptr, 0, job.stream);
                 if (!rc && job.stream != stream && hipStreamSynchronize((hipStream_t)job.stream) != hipSuccess) rc = FFHIP_EIO;
             }
             if (rc) return fail(rc);
@@ -748,6 +727,12 @@ extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const s
         if (status[i]) return status[i];
     return FFHIP_OK;
 #undef HUFF_CHECK
+}
+extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
+                                            const ffhip_jpeg_geom *geom, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v,
+                                            uint16_t *d_quant, int *status, void *stream)
+{
+    return jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, geom, d_coef_y, d_coef_u, d_coef_v, d_quant, status, stream, nullptr);
 }
 
 /* =====================================================================================================================

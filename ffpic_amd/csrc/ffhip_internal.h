@@ -5,6 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
+#include <vector>
+
 #include "ffpic_hip.h"
 
 #define FFHIP_CHECK(expr, code)                    \
@@ -21,9 +25,11 @@ extern "C" {
 #endif
 void ffhip_note_hip_error(int hip_error, const char *what);
 int ffhip_have_device(void); /* 1 once ffhip_init succeeded on a gfx950 device */
-uint32_t *ffhip_scratch(int kind, void *stream, size_t words);
-uint8_t *ffhip_pinned_scratch(int kind, void *stream, size_t bytes); /* per (kind, stream) pinned host staging, NULL on failure */ /* per (kind, stream) device scratch, NULL on failure */
+uint32_t *ffhip_scratch(int kind, void *stream, size_t words); /* per (kind, device, stream) device scratch, NULL on failure */
+uint8_t *ffhip_pinned_scratch(int kind, void *stream, size_t bytes); /* per (kind, device, stream) pinned host staging, NULL on failure */
 int *ffhip_async_err_word(void); /* pinned word kernels report an in-launch abort through; see ffhip_stream_sync */
+void ffhip_release_caches(void); /* frees what the library keeps between calls, every thread's (ffhip_state_release): no call of any thread may be
+                                    in flight, its host part included */
 /* The FFHIP_* switches (A/B knobs of the tools, diagnostics) are read from the environment ONCE per process, at a call
  * site's first use, and kept; ffhip_reload_env() (public, include/ffpic_hip.h) makes every site read its switch again. */
 /* `val` points into storage the library keeps for the life of the process (values are interned, whatever their length:
@@ -71,32 +77,97 @@ __device__ __forceinline__ int ffhip_load_s16_sc1(__amdgpu_buffer_rsrc_t r, int 
 }
 #endif
 
+/* Kinds of ffhip_scratch / ffhip_pinned_scratch: a (kind, device, stream) owns its buffer.  ".. + n": the kind's sub-slots go up to kind + n. */
+enum FfhipScratchKind {
+    SCRATCH_VP8_PRED = 1,
+    SCRATCH_VP8_LF = 2,
+    SCRATCH_HEVC_INTRA = 3,
+    SCRATCH_HUFF = 4,
+    SCRATCH_FILES_DEV = 5,
+    SCRATCH_JPEG_HOST = 6,
+    SCRATCH_VP8_RETRY = 8,
+    SCRATCH_VP8_FRAMES = 9,        /* .. + 1 */
+    SCRATCH_HEVC_TILES_JT = 20,
+    SCRATCH_HEVC_TILES_CHUNK = 21, /* .. + 3 */
+    SCRATCH_HEVC_TILES_ONE = 25,   /* .. + 1 */
+    SCRATCH_HUFF_SYNC = 30,        /* .. + FFHIP_HUFF_PARTS - 1 */
+};
 
-/* ffhip_vp8_predict_loopfilter: the two row kernels of one call side by side (ffhip_vp8_lf.hip).  While `active`, the
- * prediction entry records `fork` behind its counter reset and publishes where its per-row counters live, and the loop-filter
- * entry launches on `side` behind `fork`, polling those counters. */
-struct FfhipVp8Fusion {
-    int active;
-    const uint32_t *pred_progress;
-    void *side;  /* hipStream_t */
-    void *fork;  /* hipEvent_t  */
-    int pred_split; /* the prediction runs luma and chroma rows apart: its chroma counters (behind the luma ones) count too */
-    int pshift; /* a row's progress counter is word (image * mbrows + row) << pshift */
+/* ffhip_vp8_decode_frames (row form) -> ffhip_vp8_predict_loopfilter: the colour conversion the caller enqueues behind the call belongs to
+ * it -- a retry has to run it again, behind the filter */
+struct FfhipVp8Then { uint8_t *bgra; int pitch; int64_t image_stride; };
+
+/* ffhip_vp8_predict_loopfilter: the two row kernels of one call side by side (ffhip_vp8_lf.hip).  The prediction records `fork` behind its
+ * counter reset and fills in the rest; the loop filter launches on `side` behind `fork`, polling the prediction's counters. */
+struct Vp8SideBySide {
+    hipStream_t side;
+    hipEvent_t fork;
     int *err_word; /* where the two kernels of THIS call report a bounded wait that ran out: the call's own pinned word (its retry record's), so that
                       nobody else's abort can set off the retry; NULL = the process-wide word */
+    const uint32_t *pred_progress; /* set by the prediction: its per-row counters (NULL: it did not launch the row kernel) */
+    int pshift;     /* set by the prediction: a row's progress counter is word (image * mbrows + row) << pshift */
+    int pred_split; /* set by the prediction: it runs luma and chroma rows apart, its chroma counters (behind the luma ones) count too */
 };
-extern thread_local FfhipVp8Fusion g_ffhip_vp8_fusion;
-/* ffhip_vp8_decode_frames (row form) -> ffhip_vp8_predict_loopfilter: the colour conversion the caller enqueues behind the call belongs to it -- a
- * retry has to run it again, behind the filter (consumed, i.e. switched off, by the callee) */
-struct FfhipVp8Then { int on; uint8_t *bgra; int pitch; int64_t image_stride; };
-extern thread_local FfhipVp8Then g_ffhip_vp8_then;
+/* the entry points with their hand-offs as an argument (the public entries pass NULL) */
+int vp8_predict_recon_impl(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
+                           int64_t residual_stride, const int32_t *d_resmap, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y,
+                           int64_t plane_stride_uv, void *stream, Vp8SideBySide *sbs);
+int vp8_loopfilter_impl(int mbcols, int mbrows, int n_images, int filter_type, const uint8_t *d_modes, const uint8_t *d_filters, uint8_t *d_y,
+                        uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const Vp8SideBySide *sbs);
+int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
+                                int64_t residual_stride, const int32_t *d_resmap, int filter_type, const uint8_t *d_filters, uint8_t *d_y,
+                                uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const FfhipVp8Then *then);
 
-/* ffhip_jpeg_decode_files_device -> ffhip_jpeg_entropy_batch_gpu: the reconstruction of the pictures, enqueued by the entropy call itself behind each
- * part of the batch it has decoded (consumed, i.e. switched off, by the callee) */
-struct FfhipHuffThen { int on; uint8_t *bgra; int64_t pitch, image_stride; };
-extern thread_local FfhipHuffThen g_ffhip_huff_then;
+/* ffhip_jpeg_decode_files_device -> ffhip_jpeg_entropy_batch_gpu: the reconstruction of the pictures, enqueued by the entropy call itself behind
+ * each part of the batch it has decoded */
+struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; };
+int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
+                                int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant, int *status, void *stream,
+                                const FfhipHuffThen *then);
 
-/* the calling thread's side stream with its fork / join events (ffhip_vp8_lf.hip: one set per thread and device, released by ffhip_shutdown) */
+/* ---- what the library keeps between calls (ffhip_state.hip) ---- */
+/* The record of a stream's last side-by-side VP8 call, for its repeat by ffhip_stream_sync (ffhip_vp8_lf.hip); `armed` says whether it
+ * describes a call.  The mode copy's storage and the pinned word are reused call after call. */
+struct FfhipVp8Retry {
+    bool armed = false;
+    int mbcols = 0, mbrows = 0, n_images = 0, filter_type = 0;
+    std::vector<uint8_t> h_modes;
+    const uint8_t *d_modes = nullptr, *d_filters = nullptr;
+    const int16_t *d_residual = nullptr;
+    int64_t residual_stride = 0, plane_y = 0, plane_uv = 0;
+    const int32_t *d_resmap = nullptr;
+    uint8_t *y = nullptr, *u = nullptr, *v = nullptr, *keep = nullptr;
+    FfhipVp8Then then = {nullptr, 0, 0}; /* bgra NULL: none */
+    int *err = nullptr; /* pinned, device-visible: the call's own abort word */
+    unsigned long long seq = 0; /* the stream's vp8_seq behind the call */
+};
+/* Who used a one-chunk scratch of ffhip_hevc_intra_recon_tiles last (ffhip_hevc_intra.hip): the parity of the call, and per scratch an event
+ * recorded on the stream behind the call's grouped kernel.  Calls that share a stream take turns (`turn`) for the length of their enqueue. */
+struct FfhipTileGuard {
+    std::mutex turn;
+    unsigned parity = 0;
+    bool recorded[2] = {false, false};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+struct FfhipBuf { void *p = nullptr; size_t cap = 0; };
+/* One per (device, stream), made on first use.  A stream of ffhip_stream_create's loses its entries in ffhip_stream_destroy, any other stream
+ * in ffhip_release_caches / ffhip_shutdown. */
+struct FfhipStreamState {
+    std::map<int, FfhipBuf> scratch, pinned; /* by kind; cap in words / bytes */
+    FfhipVp8Retry retry;
+    unsigned long long vp8_seq = 0; /* VP8 prediction / filter calls enqueued so far: a retry record is only good while its call is the LAST of them */
+    FfhipTileGuard tiles;
+};
+/* the entry of (current device, stream), made when missing unless !make; hold g_ffhip_state_mu while touching it (the tile guard's `turn` aside) */
+extern std::mutex g_ffhip_state_mu;
+FfhipStreamState *ffhip_stream_state(void *stream, bool make = true);
+void ffhip_state_release(void); /* no call of any thread in flight: empties both registries and the pipeline's slots */
+void ffhip_pipeline_release(void); /* ffhip_pipeline.hip: its two slots of pinned + device buffers */
+int ffhip_vp8_side_by_side_retry(void *stream); /* ffhip_vp8_lf.hip, for ffhip_stream_sync: 0 nothing reported by a side-by-side call of this
+                                                   stream, FFHIP_RETRIED repeated, FFHIP_EIO */
+struct jpeg_hdr *ffhip_huff_hdr_records(size_t n); /* the calling thread's header records, room for at least n, kept between calls; NULL: no memory */
+
+/* the calling thread's side stream with its fork / join events (ffhip_state.hip: one set per thread and device) */
 struct FfhipSide { void *stream, *fork, *join, *mid, *aux; }; /* mid: a second point of the main stream the side stream may wait for; aux: a second
                                                                 point of the side stream the main stream may wait for */
 extern "C" int ffhip_side_stream_get(FfhipSide *out);
@@ -107,8 +178,7 @@ struct FfhipPipe { void *plan, *groups2, *ev[FFHIP_PIPE_EVENTS]; };
 extern "C" int ffhip_pipe_streams_get(FfhipPipe *out);
 
 /* ... and the device Huffman decoder's (ffhip_jpeg_entropy_batch_gpu): the copy stream its parts' bytes go up on, the second kernel stream, the
- * parts' events, fork / join, two timing events; all made together (none is published unless all exist), keyed by the thread's device like
- * the side stream and released with it */
+ * parts' events, fork / join, two timing events; all made together (none is published unless all exist); same owner and lifetime */
 #define FFHIP_HUFF_PARTS 8
 struct FfhipHuffStreams { void *up, *c2, *part_ev[FFHIP_HUFF_PARTS], *fork, *join, *time_ev[2]; };
 extern "C" int ffhip_huff_streams_get(FfhipHuffStreams *out);

@@ -952,14 +952,13 @@ static bool strip_two(const ffhip_jpeg_geom *g)
      * strip, loses 1-4 % with two (the pattern of 128 x 8-pixel strips is that much slower than that of 64 x 8: profiles/r6_strips_ab*.jsonl) */
     return FFHIP_JPEG_STRIPS_DEFAULT == 2 && g->ncomp == 3;
 }
-static void launch_strip(const ffhip_jpeg_geom *g, const JpegBatch &q_in, int n_images, hipStream_t st)
+static void launch_strip(const ffhip_jpeg_geom *g, const JpegBatch &q_in, int n_images, bool two, hipStream_t st)
 {
     JpegBatch q = q_in;
     q.xcd_remap = jpeg_remap_mode();
     q.wgs_per_image = (q.quads_per_image + WAVES_PER_WG - 1) / WAVES_PER_WG;
     q.wpi_magic = q.wgs_per_image == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)q.wgs_per_image) + 1u;
     const dim3 grid((unsigned)((long long)q.wgs_per_image * n_images), 1, 1);
-    const bool two = strip_two(g);
 #define STRIP_LAUNCH(H_, V_, NC_) do { \
         if (q.pattern_only) { /* the arithmetic-free twins: same grids, loads and stores */ \
             if (two) hipLaunchKernelGGL((k_jpeg_fused_strip<H_, V_, NC_, 3, true, 1>), grid, dim3(WG_THREADS), 0, st, q); \
@@ -1065,7 +1064,8 @@ static int jpeg_recon_batch_impl(const ffhip_jpeg_geom *g, int n_images, const i
     }
 
     if (is_fused_strip(g)) {
-        const int mps = ((g->ncomp == 1 || g->h * g->v == 1) ? 8 : 4) * (strip_two(g) ? 2 : 1), bpm = g->ncomp == 1 ? 1 : g->h * g->v;
+        const bool two = strip_two(g); /* once per call: the grid and the kernel must agree whatever ffhip_reload_env does meanwhile */
+        const int mps = ((g->ncomp == 1 || g->h * g->v == 1) ? 8 : 4) * (two ? 2 : 1), bpm = g->ncomp == 1 ? 1 : g->h * g->v;
         JpegBatch p = {};
         p.pattern_only = pattern_only ? 1 : 0;
         p.coef_y = d_coef_y; p.coef_u = d_coef_u; p.coef_v = d_coef_v;
@@ -1089,7 +1089,7 @@ static int jpeg_recon_batch_impl(const ffhip_jpeg_geom *g, int n_images, const i
             q.quant += (long long)first * quant_stride;
             q.bgra += (long long)first * image_stride;
             q.n_images = cnt;
-            launch_strip(g, q, cnt, st);
+            launch_strip(g, q, cnt, two, st);
             FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
         }
         return FFHIP_OK;
@@ -1143,7 +1143,6 @@ extern "C" int ffhip_jpeg_pattern_calibrate(const ffhip_jpeg_geom *g, int n_imag
     return jpeg_recon_batch_impl(g, n_images, d_coef_y, d_coef_u, d_coef_v, d_quant, quant_stride, d_bgra, pitch, image_stride, nullptr, 0, stream, true);
 }
 
-#define SCRATCH_JPEG_HOST 6
 extern "C" int ffhip_jpeg_recon_batch_host(const ffhip_jpeg_geom *g, int n_images, const int16_t *coef_y,
                                            const int16_t *coef_u, const int16_t *coef_v,
                                            const uint16_t *quant, int64_t quant_stride, uint8_t *bgra,

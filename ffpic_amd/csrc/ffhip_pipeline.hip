@@ -94,7 +94,7 @@ void copy_out(uint8_t *bgra, int64_t pitch, int64_t image_stride, const uint8_t 
 }
 } // namespace
 
-extern "C" void ffhip_pipeline_release(void)
+void ffhip_pipeline_release(void)
 {
     std::lock_guard<std::mutex> lock(g_pipe_mu);
     for (int s = 0; s < 2; s++) {
@@ -227,7 +227,6 @@ extern "C" int ffhip_jpeg_decode_files(const uint8_t *const *files, const size_t
 
 /* Files in, pixels out ON THE DEVICE: for consumers that live on the GPU (a resize, an inference pre-processing
  * stage) nothing but the compressed bytes crosses PCIe.  Coefficient planes are library scratch (kept per stream). */
-#define SCRATCH_FILES_DEV 5
 extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
                                               ffhip_jpeg_geom *geom_out, uint8_t *d_bgra, int64_t pitch, int64_t image_stride,
                                               int *status, void *stream)
@@ -254,9 +253,8 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
         int16_t *dy = (int16_t *)base, *du = cb ? dy + (size_t)n * yb : nullptr, *dv = cb ? du + (size_t)n * cb : nullptr;
         uint16_t *dq = (uint16_t *)(base + (((size_t)n * (yb + 2 * cb) * 2 + 15) & ~(size_t)15));
         /* (the reconstruction is enqueued by the entropy call itself, behind each part of the batch as it is decoded) */
-        g_ffhip_huff_then.on = 1; g_ffhip_huff_then.bgra = d_bgra; g_ffhip_huff_then.pitch = pitch; g_ffhip_huff_then.image_stride = image_stride;
-        rc = ffhip_jpeg_entropy_batch_gpu(files, lens, n, n_threads, &g, dy, du, dv, dq, status, stream);
-        g_ffhip_huff_then.on = 0;
+        const FfhipHuffThen then = {d_bgra, pitch, image_stride};
+        rc = jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, &g, dy, du, dv, dq, status, stream, &then);
         if (rc == FFHIP_OK) return FFHIP_OK;
         if (rc != FFHIP_EINVAL) return rc;
     }

@@ -122,17 +122,12 @@ extern "C" int ffhip_init(int device)
     return FFHIP_OK;
 }
 
-extern "C" void ffhip_release_caches(void); /* below: scratch kept per (stage, stream) */
-extern "C" void ffhip_pipeline_release(void); /* ffhip_pipeline.hip: its two slots of pinned + device buffers */
-extern "C" void ffhip_vp8_release_side_streams(void); /* ffhip_vp8_lf.hip: the side stream + events of ffhip_vp8_predict_loopfilter */
-/* Nothing of the library's may be in flight.  Frees what the library keeps between calls (device scratch, pinned
- * staging, the pipeline's buffers); the next compute call binds the device again. */
+/* Nothing of the library's may be in flight.  Frees what the library keeps between calls (ffhip_state.hip); the next compute call binds
+ * the device again. */
 extern "C" void ffhip_shutdown(void)
 {
     if (g_ready) {
         (void)hipDeviceSynchronize();
-        ffhip_pipeline_release();
-        ffhip_vp8_release_side_streams();
         ffhip_release_caches();
     }
     g_ready = 0;
@@ -152,68 +147,10 @@ extern "C" int *ffhip_async_err_word(void)
 
 extern "C" const char *ffhip_arch_name(void) { return g_arch; }
 
-/* Device scratch owned by (kind, stream), grown on demand and kept: the dependency-scheduled stages
- * put their schedules / counters there.  Everything a call enqueues is ordered on its stream, so
- * the same stream may reuse its buffer call after call without waiting, and calls on different
- * streams (or threads) never share one.  Growing waits for the stream first: the old buffer may
- * still be read by what that stream has queued. */
-#include <utility>
-struct ScratchEntry { uint32_t *dev; size_t words; };
-static std::map<std::pair<int, void *>, ScratchEntry> g_scratch;
-static std::mutex g_scratch_mu;
-/* the same for PINNED host memory (staging for uploads): owned by (kind, stream), kept, grown on demand.  The caller
- * must not refill it before what it enqueued from it on that stream has run (a stream sync, as a rule). */
-static std::map<std::pair<int, void *>, std::pair<uint8_t *, size_t>> g_pinned;
-extern "C" uint8_t *ffhip_pinned_scratch(int kind, void *stream, size_t bytes)
-{
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    auto &e = g_pinned[std::make_pair(kind, stream)];
-    if (bytes > e.second) {
-        if (e.first) {
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return nullptr;
-            (void)hipHostFree(e.first);
-        }
-        e.first = nullptr;
-        e.second = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        if (hipHostMalloc((void **)&e.first, want, hipHostMallocDefault) != hipSuccess) { e.first = nullptr; return nullptr; }
-        e.second = want;
-    }
-    return e.first;
-}
-
-extern "C" void ffhip_huff_release_thread(void); /* ffhip_huff_gpu.hip: the calling thread's header records */
-extern "C" void ffhip_hevc_tiles_release(void); /* ffhip_hevc_intra.hip: the per-stream guards of the tile call's two scratch sets */
 extern "C" void ffhip_release_caches(void)
 {
-    ffhip_huff_release_thread();
-    ffhip_hevc_tiles_release();
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    for (auto &e : g_scratch)
-        if (e.second.dev) (void)hipFree(e.second.dev);
-    g_scratch.clear();
-    for (auto &e : g_pinned)
-        if (e.second.first) (void)hipHostFree(e.second.first);
-    g_pinned.clear();
+    ffhip_state_release();
     if (g_async_err) { (void)hipHostFree(g_async_err); g_async_err = nullptr; }
-}
-
-extern "C" uint32_t *ffhip_scratch(int kind, void *stream, size_t words)
-{
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    ScratchEntry &e = g_scratch[std::make_pair(kind, stream)];
-    if (words > e.words) {
-        if (e.dev) {
-            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return nullptr;
-            (void)hipFree(e.dev);
-        }
-        e.dev = nullptr;
-        e.words = 0;
-        const size_t want = words + words / 4 + 1024; /* some headroom: lists of nearly equal size do not reallocate */
-        if (hipMalloc((void **)&e.dev, want * sizeof(uint32_t)) != hipSuccess) { e.dev = nullptr; return nullptr; }
-        e.words = want;
-    }
-    return e.dev;
 }
 
 extern "C" const char *ffhip_strerror(int code)
@@ -260,9 +197,6 @@ extern "C" void *ffhip_stream_create(void)
     if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
     return (void *)s;
 }
-extern "C" void ffhip_stream_destroy(void *s) { if (s) (void)hipStreamDestroy((hipStream_t)s); }
-extern "C" int ffhip_vp8_side_by_side_retry(void *stream); /* ffhip_vp8_lf.hip: 0 nothing reported by a side-by-side call of this stream, FFHIP_RETRIED repeated, FFHIP_EIO */
-extern "C" void ffhip_vp8_retry_forget(void *stream);
 extern "C" int ffhip_stream_sync(void *s)
 {
     FFHIP_CHECK(hipStreamSynchronize((hipStream_t)s), FFHIP_EIO);
@@ -283,7 +217,10 @@ extern "C" int ffhip_stream_sync(void *s)
         *(volatile int *)g_async_err = 0;
         return code == FFHIP_ASYNC_BAD_INPUT ? FFHIP_EINVAL : FFHIP_EIO;
     }
-    ffhip_vp8_retry_forget(s);
+    {
+        std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
+        if (FfhipStreamState *e = ffhip_stream_state(s, false)) e->retry.armed = false; /* clean: whatever was enqueued there has run */
+    }
     return retried;
 }
 extern "C" void *ffhip_event_create(void)

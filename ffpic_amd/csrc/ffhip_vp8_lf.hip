@@ -19,7 +19,6 @@
 #include "ffhip_internal.h"
 
 #include <algorithm>
-#include <map>
 #include <mutex>
 #include <stdlib.h>
 #include <string.h>
@@ -381,19 +380,17 @@ __global__ __launch_bounds__(64) void k_vp8_loopfilter_rows(Vp8LfArgs a)
     }
 }
 
-#define SCRATCH_VP8_LF 2
-
-thread_local FfhipVp8Fusion g_ffhip_vp8_fusion = {0, nullptr, nullptr, nullptr, 0};
-extern "C" void ffhip_vp8_note_enqueue(void *stream); /* below: the self-healing record of a side-by-side call is good while that call is the stream's last */
-
-extern "C" int ffhip_vp8_loopfilter(int mbcols, int mbrows, int n_images, int filter_type, const uint8_t *d_modes,
-                                    const uint8_t *d_filters, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v,
-                                    int64_t plane_stride_y, int64_t plane_stride_uv, void *stream)
+/* sbs: next to the prediction of the same call (ffhip_vp8_predict_loopfilter), on its side stream */
+int vp8_loopfilter_impl(int mbcols, int mbrows, int n_images, int filter_type, const uint8_t *d_modes, const uint8_t *d_filters, uint8_t *d_y,
+                        uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const Vp8SideBySide *sbs)
 {
     if (mbcols <= 0 || mbrows <= 0 || n_images < 0 || filter_type < 0 || filter_type > 2) return FFHIP_EINVAL;
     if (n_images == 0 || filter_type == 0) return FFHIP_OK; /* WEBP_FILTER_NONE (webp.c:1852-1856) */
     if (!d_modes || !d_filters || !d_y || !d_u || !d_v) return FFHIP_EINVAL;
-    ffhip_vp8_note_enqueue(stream);
+    { /* (the self-healing record of a side-by-side call is good while that call is the stream's last: below) */
+        std::lock_guard<std::mutex> l(g_ffhip_state_mu);
+        ffhip_stream_state(stream)->vp8_seq++;
+    }
     const long long n_mb = (long long)mbcols * mbrows;
     if (n_mb * n_images > 0x3fffffffLL) return FFHIP_EINVAL;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
@@ -401,7 +398,7 @@ extern "C" int ffhip_vp8_loopfilter(int mbcols, int mbrows, int n_images, int fi
     /* row form (default): one launch, no host-side scheduling */
     const char *mode_env = FFHIP_ENV("FFHIP_VP8_LF_MODE");
     int *async_err = (mode_env && !strcmp(mode_env, "levels")) ? nullptr : ffhip_async_err_word();
-    if (async_err && g_ffhip_vp8_fusion.active && g_ffhip_vp8_fusion.err_word) async_err = g_ffhip_vp8_fusion.err_word; /* the side-by-side call's own word */
+    if (async_err && sbs && sbs->err_word) async_err = sbs->err_word; /* the side-by-side call's own word */
     if (async_err && !((uintptr_t)d_modes & 3) && !(((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v | (uintptr_t)plane_stride_y | (uintptr_t)plane_stride_uv) & 3) &&
         n_mb < (1LL << 23)) {
         const int pshift = []{ const char *e = FFHIP_ENV("FFHIP_VP8_PROGRESS_SHIFT"); return e ? std::min(5, std::max(0, atoi(e))) : 5; }();
@@ -409,15 +406,15 @@ extern "C" int ffhip_vp8_loopfilter(int mbcols, int mbrows, int n_images, int fi
         uint32_t *g_work = ffhip_scratch(SCRATCH_VP8_LF, stream, words);
         if (!g_work) return FFHIP_ENOMEM;
         const uint32_t *pred_progress = nullptr;
-        if (g_ffhip_vp8_fusion.active && g_ffhip_vp8_fusion.pred_progress) { /* next to the prediction kernel, behind its counter reset */
-            pred_progress = g_ffhip_vp8_fusion.pred_progress;
-            st = (hipStream_t)g_ffhip_vp8_fusion.side;
-            FFHIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)g_ffhip_vp8_fusion.fork, 0), FFHIP_EIO);
+        if (sbs && sbs->pred_progress) { /* next to the prediction kernel, behind its counter reset */
+            pred_progress = sbs->pred_progress;
+            st = sbs->side;
+            FFHIP_CHECK(hipStreamWaitEvent(st, sbs->fork, 0), FFHIP_EIO);
         }
         FFHIP_CHECK(hipMemsetAsync(g_work, 0, words * sizeof(uint32_t), st), FFHIP_EIO);
         Vp8LfArgs a = {};
-        a.pred_progress = pred_progress; a.pshift = pshift; a.pred_pshift = g_ffhip_vp8_fusion.pshift;
-        a.pred_split = pred_progress ? g_ffhip_vp8_fusion.pred_split : 0;
+        a.pred_progress = pred_progress; a.pshift = pshift; a.pred_pshift = pred_progress ? sbs->pshift : 0;
+        a.pred_split = pred_progress ? sbs->pred_split : 0;
         a.modes = d_modes; a.filters = d_filters; a.y = d_y; a.u = d_u; a.v = d_v;
         a.plane_y = plane_stride_y; a.plane_uv = plane_stride_uv;
         a.mbcols = mbcols; a.mbrows = mbrows; a.filter_type = filter_type;
@@ -473,6 +470,13 @@ extern "C" int ffhip_vp8_loopfilter(int mbcols, int mbrows, int n_images, int fi
     return FFHIP_OK;
 }
 
+extern "C" int ffhip_vp8_loopfilter(int mbcols, int mbrows, int n_images, int filter_type, const uint8_t *d_modes,
+                                    const uint8_t *d_filters, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v,
+                                    int64_t plane_stride_y, int64_t plane_stride_uv, void *stream)
+{
+    return vp8_loopfilter_impl(mbcols, mbrows, n_images, filter_type, d_modes, d_filters, d_y, d_u, d_v, plane_stride_y, plane_stride_uv, stream, nullptr);
+}
+
 /* calculate_filter_control_parameter (format/webp.c:1756-1803) for the four segments and both macroblock kinds, as
  * WEBP_read_frame calls it (webp.c:1905-1915: once per DCT partition index, not per segment).  Host arithmetic, no device.  A level of 0 only clears sub_limit
  * (webp.c:1799); the other two fields keep what the decoder's zero-initialised state held. */
@@ -508,142 +512,6 @@ extern "C" int ffhip_vp8_filter_params(const ffhip_vp8_filter_header *h, uint8_t
     return FFHIP_OK;
 }
 
-/* The side stream and the two events of ffhip_vp8_predict_loopfilter: one set per calling thread and device, made on first
- * use, recreated when the thread's current device has changed, released by ffhip_shutdown (ffhip_vp8_release_side_streams)
- * or when the thread ends. */
-namespace {
-struct SideStream {
-    int device = -1;
-    hipStream_t side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr, mid = nullptr, aux = nullptr;
-    /* ffhip_hevc_intra_recon_tiles' pipeline (made on first use): a stream for the chunks' pre-passes, a second stream for grouped kernels, events */
-    hipStream_t plan = nullptr, groups2 = nullptr;
-    hipEvent_t pev[FFHIP_PIPE_EVENTS] = {};
-    /* ffhip_jpeg_entropy_batch_gpu's (made on first use, all or none) */
-    hipStream_t huff_up = nullptr, huff_c2 = nullptr;
-    hipEvent_t huff_ev[FFHIP_HUFF_PARTS + 4] = {};
-};
-std::mutex g_side_mu;
-std::vector<SideStream *> g_sides;
-void side_release(SideStream *s)
-{
-    if (s->side) (void)hipStreamDestroy(s->side);
-    if (s->fork) (void)hipEventDestroy(s->fork);
-    if (s->join) (void)hipEventDestroy(s->join);
-    if (s->mid) (void)hipEventDestroy(s->mid);
-    if (s->aux) (void)hipEventDestroy(s->aux);
-    if (s->plan) (void)hipStreamDestroy(s->plan);
-    if (s->groups2) (void)hipStreamDestroy(s->groups2);
-    for (auto &e : s->pev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    if (s->huff_up) (void)hipStreamDestroy(s->huff_up);
-    if (s->huff_c2) (void)hipStreamDestroy(s->huff_c2);
-    for (auto &e : s->huff_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    s->huff_up = s->huff_c2 = nullptr;
-    s->plan = s->groups2 = nullptr;
-    s->side = nullptr; s->fork = s->join = s->mid = s->aux = nullptr; s->device = -1;
-}
-struct SideHolder {
-    SideStream s;
-    SideHolder() { std::lock_guard<std::mutex> l(g_side_mu); g_sides.push_back(&s); }
-    ~SideHolder()
-    {
-        std::lock_guard<std::mutex> l(g_side_mu);
-        g_sides.erase(std::remove(g_sides.begin(), g_sides.end(), &s), g_sides.end());
-        side_release(&s);
-    }
-};
-SideStream *side_stream_for_this_thread()
-{
-    static thread_local SideHolder h;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> l(g_side_mu);
-    if (h.s.side && h.s.device != dev) side_release(&h.s);
-    if (!h.s.side) {
-        /* the highest priority the device has: what runs here is the SHORT chain next to a large kernel of the caller's stream (the HEVC planner's
-         * ticket kernels next to the per-pixel programs: a few workgroups each, which otherwise queue behind thousands), or, in the VP8
-         * side-by-side call, a kernel whose share of the residency is its own (FFHIP_SIDE_PRIORITY=0: the default priority) */
-        int least = 0, greatest = 0;
-        const bool high = !FFHIP_ENV("FFHIP_SIDE_PRIORITY") || atoi(FFHIP_ENV("FFHIP_SIDE_PRIORITY")) != 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = greatest = 0; }
-        if (hipStreamCreateWithPriority(&h.s.side, hipStreamNonBlocking, high ? greatest : 0) != hipSuccess || hipEventCreateWithFlags(&h.s.fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h.s.join, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h.s.mid, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h.s.aux, hipEventDisableTiming) != hipSuccess) {
-            side_release(&h.s);
-            return nullptr;
-        }
-        h.s.device = dev;
-    }
-    return &h.s;
-}
-} // namespace
-/* the same side stream for other stages of the library that have two independent chains in one call (ffhip_hevc_intra_recon: the
- * substitution table next to the planner's kernels); 0 on success */
-extern "C" int ffhip_side_stream_get(FfhipSide *out)
-{
-    SideStream *ss = side_stream_for_this_thread();
-    if (!ss) return FFHIP_EIO;
-    out->stream = ss->side; out->fork = ss->fork; out->join = ss->join; out->mid = ss->mid; out->aux = ss->aux;
-    return FFHIP_OK;
-}
-/* ... and the streams and events of a pipelined call (ffhip_hevc_intra_recon_tiles), next to the thread's side stream and released with it */
-extern "C" int ffhip_pipe_streams_get(FfhipPipe *out)
-{
-    SideStream *ss = side_stream_for_this_thread();
-    if (!ss) return FFHIP_EIO;
-    std::lock_guard<std::mutex> l(g_side_mu);
-    if (!ss->plan) {
-        bool ok = hipStreamCreateWithFlags(&ss->plan, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&ss->groups2, hipStreamNonBlocking) == hipSuccess;
-        for (int k = 0; ok && k < FFHIP_PIPE_EVENTS; k++) ok = hipEventCreateWithFlags(&ss->pev[k], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            if (ss->plan) (void)hipStreamDestroy(ss->plan);
-            if (ss->groups2) (void)hipStreamDestroy(ss->groups2);
-            for (auto &e : ss->pev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-            ss->plan = ss->groups2 = nullptr;
-            return FFHIP_EIO;
-        }
-    }
-    out->plan = ss->plan; out->groups2 = ss->groups2;
-    for (int k = 0; k < FFHIP_PIPE_EVENTS; k++) out->ev[k] = ss->pev[k];
-    return FFHIP_OK;
-}
-extern "C" int ffhip_huff_streams_get(FfhipHuffStreams *out)
-{
-    SideStream *ss = side_stream_for_this_thread(); /* (recreated, and these with it, when the thread's current device has changed) */
-    if (!ss) return FFHIP_EIO;
-    std::lock_guard<std::mutex> l(g_side_mu);
-    if (!ss->huff_up) {
-        hipStream_t up = nullptr, c2 = nullptr;
-        hipEvent_t ev[FFHIP_HUFF_PARTS + 4] = {};
-        bool ok = hipStreamCreateWithFlags(&up, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&c2, hipStreamNonBlocking) == hipSuccess;
-        for (int k = 0; ok && k < FFHIP_HUFF_PARTS + 2; k++) ok = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) == hipSuccess;
-        for (int k = FFHIP_HUFF_PARTS + 2; ok && k < FFHIP_HUFF_PARTS + 4; k++) ok = hipEventCreate(&ev[k]) == hipSuccess;
-        if (!ok) { /* nothing half-made is kept: the next call tries again from nothing */
-            (void)hipGetLastError();
-            if (up) (void)hipStreamDestroy(up);
-            if (c2) (void)hipStreamDestroy(c2);
-            for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-            return FFHIP_EIO;
-        }
-        for (int k = 0; k < FFHIP_HUFF_PARTS + 4; k++) ss->huff_ev[k] = ev[k];
-        ss->huff_c2 = c2;
-        ss->huff_up = up; /* last */
-    }
-    out->up = ss->huff_up; out->c2 = ss->huff_c2;
-    for (int k = 0; k < FFHIP_HUFF_PARTS; k++) out->part_ev[k] = ss->huff_ev[k];
-    out->fork = ss->huff_ev[FFHIP_HUFF_PARTS]; out->join = ss->huff_ev[FFHIP_HUFF_PARTS + 1];
-    out->time_ev[0] = ss->huff_ev[FFHIP_HUFF_PARTS + 2]; out->time_ev[1] = ss->huff_ev[FFHIP_HUFF_PARTS + 3];
-    return FFHIP_OK;
-}
-extern "C" void ffhip_vp8_retry_release(void);
-extern "C" void ffhip_vp8_release_side_streams(void) /* ffhip_shutdown: nothing of the library's is in flight */
-{
-    ffhip_vp8_retry_release();
-    std::lock_guard<std::mutex> l(g_side_mu);
-    for (SideStream *s : g_sides) side_release(s);
-}
-
 /* ---- the side-by-side call is repeated by ffhip_stream_sync when it could not finish ----
  * What the prediction reads of the planes' FORMER contents is one column: the reference's wrapped 16x16 H_PRED at x = 0 reads the sample left
  * of a row's first pixel, i.e. the plane's last column a line further up (predict.c:346-353).  The one-call form keeps a copy of that column
@@ -653,7 +521,6 @@ extern "C" void ffhip_vp8_release_side_streams(void) /* ffhip_shutdown: nothing 
  * ffhip_vp8_decode_frames' row form), one after the other -- everything else the stages read is their inputs, which are intact.  The sync
  * then says FFHIP_RETRIED, not FFHIP_OK: the planes hold the bytes of an undisturbed call, but what the CALLER enqueued behind the call has
  * consumed the aborted run's (round 4 said FFHIP_OK, and converted the aborted planes to BGRA in ffhip_vp8_decode_frames' row form). */
-#define SCRATCH_VP8_RETRY 8
 __global__ __launch_bounds__(256) void k_vp8_last_column(uint8_t *y, long long plane_y, int ys, int rows, int n_images, uint8_t *keep, int restore)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -663,69 +530,31 @@ __global__ __launch_bounds__(256) void k_vp8_last_column(uint8_t *y, long long p
     if (restore) *p = keep[i];
     else keep[i] = *p;
 }
-thread_local FfhipVp8Then g_ffhip_vp8_then = {0, nullptr, 0, 0};
-namespace {
-struct Vp8Retry { /* one per stream, kept (the mode copy's storage and the pinned word are reused call after call); `armed` says whether it describes a call */
-    bool armed = false;
-    int mbcols = 0, mbrows = 0, n_images = 0, filter_type = 0;
-    std::vector<uint8_t> h_modes;
-    const uint8_t *d_modes = nullptr, *d_filters = nullptr;
-    const int16_t *d_residual = nullptr;
-    int64_t residual_stride = 0, plane_y = 0, plane_uv = 0;
-    const int32_t *d_resmap = nullptr;
-    uint8_t *y = nullptr, *u = nullptr, *v = nullptr, *keep = nullptr;
-    FfhipVp8Then then = {0, nullptr, 0, 0};
-    int *err = nullptr; /* pinned, device-visible: the call's own abort word */
-    unsigned long long seq = 0;
-};
-std::mutex g_retry_mu;
-std::map<void *, Vp8Retry> g_retry; /* by stream: the last side-by-side call enqueued there */
-std::map<void *, unsigned long long> g_vp8_seq; /* by stream: VP8 prediction / filter calls enqueued so far -- a record is only good while its call is the LAST of them */
-} // namespace
-extern "C" void ffhip_vp8_note_enqueue(void *stream)
-{
-    std::lock_guard<std::mutex> l(g_retry_mu);
-    g_vp8_seq[stream]++;
-}
-extern "C" void ffhip_vp8_retry_forget(void *stream) /* a clean ffhip_stream_sync: whatever was enqueued there has run */
-{
-    std::lock_guard<std::mutex> l(g_retry_mu);
-    auto it = g_retry.find(stream);
-    if (it != g_retry.end()) it->second.armed = false;
-}
-extern "C" void ffhip_vp8_retry_release(void) /* ffhip_shutdown */
-{
-    std::lock_guard<std::mutex> l(g_retry_mu);
-    for (auto &e : g_retry)
-        if (e.second.err) (void)hipHostFree(e.second.err);
-    g_retry.clear();
-    g_vp8_seq.clear();
-}
 /* ffhip_stream_sync(stream), the stream having drained: 0 = no side-by-side call of this stream reported anything; FFHIP_RETRIED = one had
  * run into a bounded wait, was repeated stage by stage and is done; FFHIP_EIO = it had, and could not be repeated (no longer the stream's
- * last VP8 call) or the repeat failed */
-extern "C" int ffhip_vp8_side_by_side_retry(void *stream)
+ * last VP8 call) or the repeat failed.  (The record is the stream's entry of the library's registry: ffhip_state.hip.) */
+int ffhip_vp8_side_by_side_retry(void *stream)
 {
-    Vp8Retry r;
+    FfhipVp8Retry r;
     {
-        std::lock_guard<std::mutex> l(g_retry_mu);
-        auto it = g_retry.find(stream);
-        if (it == g_retry.end() || !it->second.armed || !it->second.err) return 0;
-        const int code = *(volatile int *)it->second.err;
+        std::lock_guard<std::mutex> l(g_ffhip_state_mu);
+        FfhipStreamState *e = ffhip_stream_state(stream, false);
+        if (!e || !e->retry.armed || !e->retry.err) return 0;
+        const int code = *(volatile int *)e->retry.err;
         if (!code) return 0;
-        *(volatile int *)it->second.err = 0;
-        it->second.armed = false;
-        if (it->second.seq != g_vp8_seq[stream]) return FFHIP_EIO; /* other VP8 calls went onto the stream behind it: their order cannot be restored */
-        r = it->second;
+        *(volatile int *)e->retry.err = 0;
+        e->retry.armed = false;
+        if (e->retry.seq != e->vp8_seq) return FFHIP_EIO; /* other VP8 calls went onto the stream behind it: their order cannot be restored */
+        r = e->retry;
     }
     hipStream_t st = (hipStream_t)stream;
     const long long lines = (long long)16 * r.mbrows * r.n_images;
     hipLaunchKernelGGL(k_vp8_last_column, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, r.y, (long long)r.plane_y, 16 * r.mbcols, 16 * r.mbrows, r.n_images, r.keep, 1);
     if (hipGetLastError() != hipSuccess) return FFHIP_EIO;
-    int rc = ffhip_vp8_predict_recon(r.mbcols, r.mbrows, r.n_images, r.h_modes.data(), r.d_modes, r.d_residual, r.residual_stride, r.d_resmap, r.y, r.u, r.v,
-                                     r.plane_y, r.plane_uv, stream);
-    if (rc == FFHIP_OK) rc = ffhip_vp8_loopfilter(r.mbcols, r.mbrows, r.n_images, r.filter_type, r.d_modes, r.d_filters, r.y, r.u, r.v, r.plane_y, r.plane_uv, stream);
-    if (rc == FFHIP_OK && r.then.on)
+    int rc = vp8_predict_recon_impl(r.mbcols, r.mbrows, r.n_images, r.h_modes.data(), r.d_modes, r.d_residual, r.residual_stride, r.d_resmap, r.y, r.u, r.v,
+                                    r.plane_y, r.plane_uv, stream, nullptr);
+    if (rc == FFHIP_OK) rc = vp8_loopfilter_impl(r.mbcols, r.mbrows, r.n_images, r.filter_type, r.d_modes, r.d_filters, r.y, r.u, r.v, r.plane_y, r.plane_uv, stream, nullptr);
+    if (rc == FFHIP_OK && r.then.bgra)
         rc = ffhip_yuv420_to_bgra(r.then.bgra, r.then.pitch, r.y, r.u, r.v, 16 * r.mbcols, 8 * r.mbcols, r.mbrows, r.mbcols, r.n_images, r.plane_y, r.plane_uv,
                                   r.then.image_stride, stream);
     if (rc != FFHIP_OK) return FFHIP_EIO;
@@ -737,36 +566,29 @@ extern "C" int ffhip_vp8_side_by_side_retry(void *stream)
  * side by side (the filter on a stream of the library's own, forked behind the prediction's counter reset and joined back
  * into `stream`), the filter's rows following the prediction's through its per-row counters.  Same arguments and the same
  * bytes as ffhip_vp8_predict_recon followed by ffhip_vp8_loopfilter; the two chains overlap instead of adding up. */
-extern "C" int ffhip_vp8_predict_recon(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes,
-                                       const int16_t *d_residual, int64_t residual_stride, const int32_t *d_resmap, uint8_t *d_y,
-                                       uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream);
-extern "C" int ffhip_vp8_predict_loopfilter(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes,
-                                            const int16_t *d_residual, int64_t residual_stride, const int32_t *d_resmap,
-                                            int filter_type, const uint8_t *d_filters, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v,
-                                            int64_t plane_stride_y, int64_t plane_stride_uv, void *stream)
+int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
+                                int64_t residual_stride, const int32_t *d_resmap, int filter_type, const uint8_t *d_filters, uint8_t *d_y,
+                                uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const FfhipVp8Then *then)
 {
-    /* taken and cleared before anything can return: an early return must not leave the record armed for the thread's next direct call */
-    const FfhipVp8Then then = g_ffhip_vp8_then;
-    g_ffhip_vp8_then.on = 0;
     if (filter_type < 0 || filter_type > 2) return FFHIP_EINVAL;
     if (filter_type != 0 && !d_filters) return FFHIP_EINVAL;
     const char *off = FFHIP_ENV("FFHIP_VP8_FUSE"); /* =0: one after the other on `stream` (A/B knob) */
     const bool fuse = filter_type != 0 && n_images > 0 && !(off && off[0] == '0') && ffhip_have_device();
-    hipStream_t side = nullptr;
-    hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+    Vp8SideBySide sbs = {};
+    hipEvent_t join_ev = nullptr;
     if (fuse) {
-        SideStream *ss = side_stream_for_this_thread();
-        if (!ss) return FFHIP_EIO;
-        side = ss->side; fork_ev = ss->fork; join_ev = ss->join;
+        FfhipSide side;
+        if (ffhip_side_stream_get(&side) != FFHIP_OK) return FFHIP_EIO;
+        sbs.side = (hipStream_t)side.stream; sbs.fork = (hipEvent_t)side.fork; join_ev = (hipEvent_t)side.join;
     }
     /* for the repeat: the last luma column as it is now, and who to call again (small batches only: the record holds a copy of the
      * host's mode bytes, which the row form checks on the host; a chip-filling batch leaves no room for the second kernel to be kept out) */
-    uint8_t *keep = nullptr;
     const bool heal = fuse && h_modes && d_y && (long long)mbcols * mbrows * n_images <= (1LL << 17) && !FFHIP_ENV("FFHIP_VP8_NO_RETRY");
-    int *err_word = nullptr;
+    const long long lines = (long long)16 * mbrows * n_images;
+    uint8_t *keep = heal ? (uint8_t *)ffhip_scratch(SCRATCH_VP8_RETRY, stream, (size_t)(lines + 3) / 4) : nullptr;
     {
-        std::lock_guard<std::mutex> l(g_retry_mu);
-        Vp8Retry &r = g_retry[stream];
+        std::lock_guard<std::mutex> l(g_ffhip_state_mu);
+        FfhipVp8Retry &r = ffhip_stream_state(stream)->retry;
         if (r.err && *(volatile int *)r.err) { /* an earlier call's abort nobody collected (the caller never came back with ffhip_stream_sync): not lost */
             int *g = ffhip_async_err_word();
             if (g) *(volatile int *)g = *(volatile int *)r.err;
@@ -774,8 +596,6 @@ extern "C" int ffhip_vp8_predict_loopfilter(int mbcols, int mbrows, int n_images
         }
         r.armed = false;
         if (heal) {
-            const long long lines = (long long)16 * mbrows * n_images;
-            keep = (uint8_t *)ffhip_scratch(SCRATCH_VP8_RETRY, stream, (size_t)(lines + 3) / 4);
             if (!r.err && hipHostMalloc((void **)&r.err, 64, hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); r.err = nullptr; }
             if (keep && r.err) {
                 *(volatile int *)r.err = 0;
@@ -785,36 +605,38 @@ extern "C" int ffhip_vp8_predict_loopfilter(int mbcols, int mbrows, int n_images
                     r.mbcols = mbcols; r.mbrows = mbrows; r.n_images = n_images; r.filter_type = filter_type;
                     r.h_modes.assign(h_modes, h_modes + (size_t)mbcols * mbrows * n_images * 20); /* (the vector keeps its storage between calls) */
                     r.d_modes = d_modes; r.d_filters = d_filters; r.d_residual = d_residual; r.residual_stride = residual_stride; r.d_resmap = d_resmap;
-                    r.plane_y = plane_stride_y; r.plane_uv = plane_stride_uv; r.y = d_y; r.u = d_u; r.v = d_v; r.keep = keep; r.then = then;
+                    r.plane_y = plane_stride_y; r.plane_uv = plane_stride_uv; r.y = d_y; r.u = d_u; r.v = d_v; r.keep = keep;
+                    r.then = then ? *then : FfhipVp8Then{nullptr, 0, 0};
                     r.armed = true;
-                    err_word = r.err;
+                    sbs.err_word = r.err;
                 }
             }
         }
     }
-    g_ffhip_vp8_fusion.err_word = err_word;
-    g_ffhip_vp8_fusion.active = fuse ? 1 : 0;
-    g_ffhip_vp8_fusion.pred_progress = nullptr;
-    g_ffhip_vp8_fusion.side = side;
-    g_ffhip_vp8_fusion.fork = fork_ev;
-    int rc = ffhip_vp8_predict_recon(mbcols, mbrows, n_images, h_modes, d_modes, d_residual, residual_stride, d_resmap, d_y, d_u, d_v,
-                                     plane_stride_y, plane_stride_uv, stream);
-    const bool forked = fuse && g_ffhip_vp8_fusion.pred_progress != nullptr;
+    int rc = vp8_predict_recon_impl(mbcols, mbrows, n_images, h_modes, d_modes, d_residual, residual_stride, d_resmap, d_y, d_u, d_v,
+                                    plane_stride_y, plane_stride_uv, stream, fuse ? &sbs : nullptr);
+    const bool forked = sbs.pred_progress != nullptr;
     if (rc == FFHIP_OK && filter_type != 0)
-        rc = ffhip_vp8_loopfilter(mbcols, mbrows, n_images, filter_type, d_modes, d_filters, d_y, d_u, d_v, plane_stride_y, plane_stride_uv, stream);
-    g_ffhip_vp8_fusion.active = 0;
-    g_ffhip_vp8_fusion.pred_progress = nullptr;
-    g_ffhip_vp8_fusion.err_word = nullptr;
+        rc = vp8_loopfilter_impl(mbcols, mbrows, n_images, filter_type, d_modes, d_filters, d_y, d_u, d_v, plane_stride_y, plane_stride_uv, stream,
+                                 fuse ? &sbs : nullptr);
     {
-        std::lock_guard<std::mutex> l(g_retry_mu);
-        auto it = g_retry.find(stream);
-        if (it != g_retry.end() && it->second.armed) {
-            if (rc == FFHIP_OK && forked) it->second.seq = g_vp8_seq[stream];
-            else it->second.armed = false; /* nothing ran side by side: nothing to repeat */
+        std::lock_guard<std::mutex> l(g_ffhip_state_mu);
+        FfhipStreamState *e = ffhip_stream_state(stream);
+        if (e->retry.armed) {
+            if (rc == FFHIP_OK && forked) e->retry.seq = e->vp8_seq;
+            else e->retry.armed = false; /* nothing ran side by side: nothing to repeat */
         }
     }
     if (forked) { /* whatever happened to the filter's launch: `stream` continues behind the side stream */
-        if (hipEventRecord(join_ev, side) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, join_ev, 0) != hipSuccess) return FFHIP_EIO;
+        if (hipEventRecord(join_ev, sbs.side) != hipSuccess || hipStreamWaitEvent((hipStream_t)stream, join_ev, 0) != hipSuccess) return FFHIP_EIO;
     }
     return rc;
+}
+extern "C" int ffhip_vp8_predict_loopfilter(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes,
+                                            const int16_t *d_residual, int64_t residual_stride, const int32_t *d_resmap,
+                                            int filter_type, const uint8_t *d_filters, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v,
+                                            int64_t plane_stride_y, int64_t plane_stride_uv, void *stream)
+{
+    return vp8_predict_loopfilter_impl(mbcols, mbrows, n_images, h_modes, d_modes, d_residual, residual_stride, d_resmap, filter_type, d_filters, d_y, d_u,
+                                       d_v, plane_stride_y, plane_stride_uv, stream, nullptr);
 }

@@ -46,7 +46,7 @@ int ffhip_device_count(void);
 /* Bind the calling thread's library state to `device` (hipSetDevice) and create
  * the small internal staging buffers used by the per-block entry points. */
 int ffhip_init(int device);
-void ffhip_shutdown(void); /* with nothing in flight: frees the scratch, staging and pipeline buffers the library keeps
+void ffhip_shutdown(void); /* with no call of any thread in flight: frees the scratch, staging and pipeline buffers the library keeps
                               between calls; a later compute call binds the device again */
 const char *ffhip_strerror(int code);
 /* The FFHIP_* environment switches (A/B knobs of tests/tools, diagnostics; none is needed in production) are read ONCE per
@@ -66,7 +66,8 @@ int ffhip_memcpy_h2d(void *dst, const void *src, size_t bytes, void *stream);
 int ffhip_memcpy_d2h(void *dst, const void *src, size_t bytes, void *stream);
 int ffhip_memset(void *dst, int value, size_t bytes, void *stream);
 void *ffhip_stream_create(void);
-void ffhip_stream_destroy(void *stream);
+void ffhip_stream_destroy(void *stream); /* waits for what `stream` holds, then frees the library's state of it (scratch, staging, VP8
+                                            retry record, HEVC tile guard) with it */
 int ffhip_stream_sync(void *stream); /* NULL = the default stream; FFHIP_EIO also if a dependency-scheduled
                                          kernel (VP8 predict / loop filter, HEVC intra) reported an abort;
                                          FFHIP_RETRIED (> 0) when a side-by-side VP8 call was repeated, see there */

@@ -183,3 +183,177 @@ def test_decode_frames_row_form_repeats_its_colour_conversion(monkeypatch, plane
     for i in range(n):
         assert np.array_equal(bgra[i], exp[i]), i
     monkeypatch.delenv("FFHIP_DEBUG_VP8_LF_GIVEUP"); monkeypatch.delenv("FFHIP_VP8_FRAMES"); capi.reload_env()
+
+
+class _Calls:
+    """An HEVC tile call, a side-by-side VP8 call and (huff=True) a device Huffman batch, with their inputs and outputs in device memory of
+    `device` and what each must produce.  Every method binds `device` first, and no ops helper is used: they bind device 0."""
+
+    def __init__(self, device=0, huff=True, hevc_size=(512, 256)):
+        from test_oracle_golden import FILES
+        from test_vp8_lf_gpu import oracle_lf
+        self.L, self.dev, self.ptrs = capi.require_device(device), device, []
+        self.w, self.h = hevc_size
+        tus, res = synth.hevc_intra_tus(self.w, self.h, seed=41, tu_mix="c5")
+        self.tus, self.tf = np.ascontiguousarray(tus), np.zeros(1, np.int64)
+        self.d_tus, self.d_res = self._up(self.tus), self._up(res)
+        self.hevc_exp = O.oracle_hevc_intra(tus, res, self.w, self.h, True, 8, 8)
+        self.hevc_out = [self._alloc(self.w * self.h * 2), self._alloc(self.w * self.h // 2), self._alloc(self.w * self.h // 2)]
+        self.c, self.r, self.n = 21, 13, 2
+        c, r, n = self.c, self.r, self.n
+        self.modes = np.ascontiguousarray(np.stack([synth.vp8_modes(c, r, seed=1400 + i) for i in range(n)]))
+        self.modes.reshape(n, r, c, 20)[:, 1::2, 0, 0] = 3
+        resid = np.stack([synth.vp8_residual(c * r, seed=1410 + i) for i in range(n)])
+        flt = synth.vp8_filters(seed=33)
+        self.vp8_exp = [oracle_lf(c, r, 2, self.modes[i], flt, O.oracle_vp8_frame(c, r, self.modes[i], resid[i])) for i in range(n)]
+        self.d_modes, self.d_resid, self.d_flt = self._up(self.modes), self._up(np.ascontiguousarray(resid)), self._up(np.ascontiguousarray(flt))
+        self.ysz, self.csz = 256 * c * r, 64 * c * r
+        self.vp8_out = [self._alloc(n * self.ysz), self._alloc(n * self.csz), self._alloc(n * self.csz)]
+        self.huff = huff
+        if huff:
+            import ctypes as C
+            import os
+            data = open(os.path.join(os.path.dirname(__file__), "golden", FILES["q85_420_dri"]), "rb").read()
+            files = [data] * 3
+            self.g, cy, cu, cv, _ = ops.jpeg_entropy_batch(files, n_threads=2)
+            self.huff_exp = (cy, cu, cv)
+            self.bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+            self.fptrs = (C.c_void_p * len(files))(*[b.ctypes.data for b in self.bufs])
+            self.lens = (C.c_size_t * len(files))(*[b.size for b in self.bufs])
+            self.status = (C.c_int * len(files))()
+            nf, g = len(files), self.g
+            self.huff_out = [self._alloc(nf * g.y_blocks * 128), self._alloc(nf * g.c_blocks * 128), self._alloc(nf * g.c_blocks * 128), self._alloc(nf * 512)]
+        capi.check(self.L.ffhip_stream_sync(None))
+
+    def _bind(self):
+        capi.check(self.L.ffhip_init(self.dev))
+
+    def _alloc(self, nbytes):
+        p = self.L.ffhip_malloc(max(nbytes, 16))
+        assert p
+        self.ptrs.append(p)
+        return p
+
+    def _up(self, a):
+        p = self._alloc(a.nbytes)
+        capi.check(self.L.ffhip_memcpy_h2d(p, a.ctypes.data, a.nbytes, None))
+        return p
+
+    def _down(self, p, shape, dtype):
+        out = np.empty(shape, dtype)
+        capi.check(self.L.ffhip_memcpy_d2h(out.ctypes.data, p, out.nbytes, None))
+        capi.check(self.L.ffhip_stream_sync(None))
+        return out
+
+    def enqueue(self, s):
+        import ctypes as C
+        self._bind()
+        L, w, h, c, r, n = self.L, self.w, self.h, self.c, self.r, self.n
+        for p, nbytes in zip(self.hevc_out + self.vp8_out, (w * h * 2, w * h // 2, w * h // 2, n * self.ysz, n * self.csz, n * self.csz)):
+            capi.check(L.ffhip_memset(p, 0, nbytes, s))
+        y, u, v = self.hevc_out
+        capi.check(L.ffhip_hevc_intra_recon_tiles(self.tus.ctypes.data, self.d_tus, len(self.tus), self.tf.ctypes.data, 1, self.d_res, y, u, v, w, h, w, w // 2,
+                                                  h // 2, w // 2, 8, 8, s))
+        y, u, v = self.vp8_out
+        capi.check(L.ffhip_vp8_predict_loopfilter(c, r, n, self.modes.ctypes.data, self.d_modes, self.d_resid, c * r * 384, None, 2, self.d_flt, y, u, v,
+                                                  self.ysz, self.csz, s))
+        if self.huff:
+            dy, du, dv, dq = self.huff_out
+            capi.check(L.ffhip_jpeg_entropy_batch_gpu(self.fptrs, self.lens, len(self.bufs), 2, C.byref(self.g), dy, du, dv, dq, self.status, s))
+
+    def check(self, tag):
+        self._bind()
+        w, h, c, r, n = self.w, self.h, self.c, self.r, self.n
+        got = [self._down(p, sh, np.int16) for p, sh in zip(self.hevc_out, ((h, w), (h // 2, w // 2), (h // 2, w // 2)))]
+        for a, b, name in zip(got, self.hevc_exp, "YUV"):
+            assert np.array_equal(a, b), (tag, "hevc", name)
+        got = [self._down(p, sh, np.uint8) for p, sh in zip(self.vp8_out, ((n, 16 * r, 16 * c), (n, 8 * r, 8 * c), (n, 8 * r, 8 * c)))]
+        for i in range(n):
+            for a, b, name in zip(got, self.vp8_exp[i], "YUV"):
+                assert np.array_equal(a[i], b), (tag, "vp8", i, name)
+        if self.huff:
+            assert list(self.status) == [0] * len(self.bufs), tag
+            for p, e, name in zip(self.huff_out, self.huff_exp, "YUV"):
+                assert np.array_equal(self._down(p, e.shape, np.int16), e), (tag, "huff", name)
+
+    def close(self):
+        self._bind()
+        for p in self.ptrs:
+            self.L.ffhip_free(p)
+        self.ptrs = []
+
+
+def test_stream_churn_frees_what_each_stream_held():
+    """16 rounds of: create a stream, an HEVC tile call, a side-by-side VP8 call and a device Huffman batch on it, sync, destroy.  Every output is the
+    oracle's, and free device memory after the last round is within one round's scratch of what it was after the first: ffhip_stream_destroy frees
+    the stream's entries (scratch, retry record, tile guard) -- a new stream that gets the same handle starts from nothing.  One round's scratch is
+    measured on a live stream and must be large (the 2048x1024 tile call's per-pixel programs alone are 8 bytes a sample, 25 MB): a library that
+    kept each destroyed stream's scratch would lose 15 of them."""
+    torch = pytest.importorskip("torch")
+    calls = _Calls(hevc_size=(2048, 1024))
+    L = calls.L
+    s = L.ffhip_stream_create()                    # the thread's own streams and events are made here, not in the rounds
+    calls.enqueue(s)
+    assert capi.sync(s) == 0
+    L.ffhip_stream_destroy(s)
+    before = torch.cuda.mem_get_info(0)[0]
+    s = L.ffhip_stream_create()
+    calls.enqueue(s)
+    assert capi.sync(s) == 0
+    one_round = before - torch.cuda.mem_get_info(0)[0]   # the scratch of one live stream
+    assert one_round >= 16 << 20, one_round
+    L.ffhip_stream_destroy(s)
+    free = []
+    for rnd in range(16):
+        s = L.ffhip_stream_create()
+        assert s
+        calls.enqueue(s)
+        assert capi.sync(s) == 0, rnd
+        calls.check(rnd)
+        L.ffhip_stream_destroy(s)
+        free.append(torch.cuda.mem_get_info(0)[0])
+    assert free[-1] >= free[0] - one_round, (one_round, free)
+    calls.close()
+
+
+def test_stream_destroy_waits_for_queued_work():
+    """ffhip_stream_destroy on a stream with work still queued (an HEVC tile call and a side-by-side VP8 call behind large copies; the Huffman batch
+    is left out: it waits for its stream before it returns) returns once that work has run: an event recorded behind the work is pending when
+    destroy is called and complete when it returns, and the outputs are complete.  A stream created next decodes bit for bit."""
+    torch = pytest.importorskip("torch")
+    calls = _Calls(huff=False)
+    L = calls.L
+    a, b = ops.DeviceBuffer(nbytes=256 << 20), ops.DeviceBuffer(nbytes=256 << 20)
+    s = L.ffhip_stream_create()
+    for _ in range(64):
+        capi.check(L.ffhip_copy_calibrate(b.ptr, a.ptr, 256 << 20, s))
+    calls.enqueue(s)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.ExternalStream(s))
+    assert not done.query()                        # the work is still queued ...
+    L.ffhip_stream_destroy(s)                      # (no sync in front of it)
+    assert done.query()                            # ... and has run when destroy returns
+    calls.check("destroyed")
+    s = L.ffhip_stream_create()
+    calls.enqueue(s)
+    assert capi.sync(s) == 0
+    calls.check("next")
+    L.ffhip_stream_destroy(s)
+    calls.close()
+
+
+def test_null_stream_calls_alternating_between_two_devices():
+    """One thread, null-stream HEVC tile and side-by-side VP8 calls on device 0, then 1, then 0 ...: the library's state of the null stream is per
+    device (scratch, retry record, tile guard), and so is the thread's side stream -- every output is the oracle's."""
+    L = capi.lib()
+    if L.ffhip_device_count() < 2:
+        pytest.skip("needs two devices")
+    calls = [_Calls(d, huff=False) for d in (0, 1)]
+    for rnd in range(6):
+        k = calls[rnd & 1]
+        k.enqueue(None)
+        assert capi.sync(None) == 0, rnd
+        k.check(rnd)
+    for k in calls:
+        k.close()
+    capi.require_device(0)
