@@ -25,6 +25,7 @@ EXPORTS = [
     "ffhip_heif_grid_parse", "ffhip_heif_grid_compose", "ffhip_hevc_picture_layout", "ffhip_jpeg_decode_files", "ffhip_jpeg_decode_files_device", "ffhip_jpeg_entropy_batch_gpu", "ffhip_jpeg_stage_scan_test", "ffhip_jpeg_stage_scan_raw_test", "ffhip_jpeg_lut_test", "ffhip_host_malloc", "ffhip_host_free",
     "ffhip_shard_range", "ffhip_comm_unique_id", "ffhip_comm_init_rank", "ffhip_comm_destroy", "ffhip_batch_close", "ffhip_batch_complete",
     "ffhip_bgra_checksum", "ffhip_vp8_filter_params", "ffhip_vp8_predict_loopfilter", "ffhip_reload_env", "ffhip_env_value_test", "ffhip_vp8_decode_frames", "ffhip_bgra_layout",
+    "ffhip_jpeg_recon_items", "ffhip_jpeg_decode_files_mixed_device",
 ]
 
 
@@ -80,6 +81,12 @@ class JpegGeom(C.Structure):
     @property
     def c_blocks(self):
         return self.mcu_cols * self.mcu_rows
+
+
+class JpegItem(C.Structure):
+    """ffhip_jpeg_item: one picture of an ffhip_jpeg_recon_items call (device pointers)"""
+    _fields_ = [("geom", JpegGeom), ("d_coef_y", C.c_void_p), ("d_coef_u", C.c_void_p), ("d_coef_v", C.c_void_p),
+                ("d_quant", C.c_void_p), ("d_bgra", C.c_void_p), ("pitch", C.c_int64)]
 
 
 def jpeg_geom(mcu_cols, mcu_rows, ncomp=3, h=2, v=2, qt_id=(0, 1, 1)):
@@ -184,6 +191,8 @@ def lib():
     L.ffhip_jpeg_entropy_batch_gpu.argtypes = [vp, vp, ci, ci, C.POINTER(JpegGeom), vp, vp, vp, vp, vp, vp]
     L.ffhip_jpeg_decode_files_device.argtypes = [vp, vp, ci, ci, C.POINTER(JpegGeom), vp, i64, i64, vp, vp]
     L.ffhip_jpeg_decode_files.argtypes = [vp, vp, ci, ci, ci, C.POINTER(JpegGeom), vp, i64, i64, vp]
+    L.ffhip_jpeg_recon_items.argtypes = [C.POINTER(JpegItem), ci, vp]
+    L.ffhip_jpeg_decode_files_mixed_device.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(JpegGeom), vp, vp]
     L.ffhip_hevc_picture_layout.argtypes = [ci, ci, ci, C.POINTER(HevcLayout)]
     L.ffhip_heif_grid_parse.argtypes = [vp, sz, C.POINTER(HeifGrid)]
     L.ffhip_heif_grid_compose.argtypes = [vp, i64, ci, ci, vp, i64, i64, ci, ci, ci, ci, vp]

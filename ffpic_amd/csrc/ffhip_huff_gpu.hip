@@ -36,6 +36,7 @@ struct HuffImage {
     uint32_t seg_base, n_seg;    /* its restart intervals inside `seg` (offsets relative to scan_off): n_seg starts and,
                                   * as entry n_seg, the length of the clean stream = the end of the last interval */
     uint32_t restart, mcus;
+    uint32_t mcu_base;           /* MCUs of the call's pictures before this one: where its blocks start in the planes */
     uint32_t ncomp, nb[3];       /* blocks per MCU and component */
     uint32_t tab_dc[3], tab_ac[3]; /* indices into `tabs` */
 };
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(256) void k_jpeg_huff(HuffArgs a)
     uint32_t nbt = 0;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const unsigned long long pb = a.plane[c] ? (unsigned long long)(uintptr_t)(a.plane[c] + (size_t)w.x * im.mcus * im.nb[c] * 64) : 0ull;
+        const unsigned long long pb = a.plane[c] ? (unsigned long long)(uintptr_t)(a.plane[c] + (size_t)im.mcu_base * im.nb[c] * 64) : 0ull;
         planeb[wv][c][lane] = pb;
         predv[wv][c][lane] = 0;
         for (uint32_t kb0 = 0; kb0 < im.nb[c] && nbt < 8; kb0++)
@@ -408,8 +409,8 @@ static int huff_sync_finish(SyncJob &job, void *stream, uint32_t *h_cnt, int *st
 
 /* then: reconstruct the pictures into then->bgra behind each part of the batch as it is decoded (ffhip_jpeg_decode_files_device) */
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
-                                int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant, int *status, void *stream,
-                                const FfhipHuffThen *then)
+                                const ffhip_jpeg_geom *geoms, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant,
+                                int *status, void *stream, const FfhipHuffThen *then)
 {
     if (n < 0 || !geom || (n > 0 && (!files || !lens || !d_coef_y || !d_quant || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
@@ -418,7 +419,21 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
     if (n_threads > 64) n_threads = 64;
     if (geom->mcu_cols <= 0 || geom->mcu_rows <= 0 || geom->h < 1 || geom->v < 1 || geom->h * geom->v > 4 ||
         (geom->ncomp != 1 && geom->ncomp != 3)) return FFHIP_EINVAL;
-    const size_t mcus = (size_t)geom->mcu_cols * geom->mcu_rows;
+    /* per picture its MCUs and where its blocks start: one geometry (geoms NULL) or pictures of one layout class that differ in size */
+    std::vector<uint32_t> pic_mcus((size_t)n), mcu_base((size_t)n + 1);
+    {
+        size_t sum = 0;
+        for (int i = 0; i < n; i++) {
+            const ffhip_jpeg_geom *gi = geoms ? &geoms[i] : geom;
+            if (geoms && (gi->ncomp != geom->ncomp || gi->h != geom->h || gi->v != geom->v || gi->mcu_cols <= 0 || gi->mcu_rows <= 0)) return FFHIP_EINVAL;
+            pic_mcus[(size_t)i] = (uint32_t)((size_t)gi->mcu_cols * gi->mcu_rows);
+            mcu_base[(size_t)i] = (uint32_t)sum;
+            sum += pic_mcus[(size_t)i];
+            if (sum > 0xffffffffu) return FFHIP_EINVAL;
+        }
+        mcu_base[(size_t)n] = (uint32_t)sum;
+    }
+    const size_t total_mcus = mcu_base[(size_t)n];
     const bool times = FFHIP_ENV("FFHIP_HUFF_TIMES") != nullptr; /* host phases on stderr */
     const auto T0 = std::chrono::steady_clock::now();
     /* ---- host, pictures over threads: headers, tables, restart-interval starts ---- */
@@ -431,7 +446,9 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
         status[i] = ffhip_jpeg_parse(files[i], lens[i], &j);
         if (status[i]) return;
         const int mc = (j.width + 8 * j.h[0] - 1) / (8 * j.h[0]), mr = (j.height + 8 * j.v[0] - 1) / (8 * j.v[0]);
-        if (mc != geom->mcu_cols || mr != geom->mcu_rows || j.ncomp != geom->ncomp || j.h[0] != geom->h || j.v[0] != geom->v ||
+        const ffhip_jpeg_geom *gi = geoms ? &geoms[i] : geom;
+        const size_t mcus = pic_mcus[(size_t)i];
+        if (mc != gi->mcu_cols || mr != gi->mcu_rows || j.ncomp != gi->ncomp || j.h[0] != gi->h || j.v[0] != gi->v ||
             j.scan_len > 0x7fffffffu) {
             status[i] = FFHIP_EINVAL; /* another geometry */
             return;
@@ -450,7 +467,7 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
     /* the subsequences' length is worked out ONCE, from the batch's scan bytes: the choice of kernel below and every part's passes go by the same figure */
     unsigned long long batch_bits = 0;
     for (int i = 0; i < n; i++) batch_bits += 8ull * hdr[(size_t)i].scan_len;
-    const uint32_t sub_bits = sync_sub_bits(batch_bits, (unsigned long long)n * mcus);
+    const uint32_t sub_bits = sync_sub_bits(batch_bits, (unsigned long long)total_mcus);
     if (use_sync && !(sy && sy[0] == '1')) {
         /* restart intervals of a subsequence or two (a DRI of one or a few MCUs: 32 400 intervals in a 4K picture) are lanes enough as they are, every
          * one starting from the truth: three passes, a 60-byte record per interval and rounds that have nothing to settle are the wrong tool; the kernel
@@ -477,7 +494,8 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
         im.scan_off = (uint32_t)scan_total;
         im.scan_len = (uint32_t)j.scan_len;
         im.restart = (uint32_t)j.restart;
-        im.mcus = (uint32_t)mcus;
+        im.mcus = pic_mcus[(size_t)i];
+        im.mcu_base = mcu_base[(size_t)i];
         im.ncomp = (uint32_t)j.ncomp;
         im.seg_base = (uint32_t)seg_total;
         im.n_seg = (uint32_t)segs[(size_t)i].size() - 1;
@@ -511,11 +529,11 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
     /* the kernel stores the non-zero coefficients only: the planes are cleared first -- enqueued here, so that the
      * clears (4.8 GB for 256 4K pictures) run while the host is still staging */
     {
-        const size_t yb = mcus * geom->h * geom->v * 64;
-        FFHIP_CHECK(hipMemsetAsync(d_coef_y, 0, (size_t)n * yb * 2, st), FFHIP_EIO);
+        const size_t yb = total_mcus * geom->h * geom->v * 64;
+        FFHIP_CHECK(hipMemsetAsync(d_coef_y, 0, yb * 2, st), FFHIP_EIO);
         if (geom->ncomp == 3) {
-            FFHIP_CHECK(hipMemsetAsync(d_coef_u, 0, (size_t)n * mcus * 128, st), FFHIP_EIO);
-            FFHIP_CHECK(hipMemsetAsync(d_coef_v, 0, (size_t)n * mcus * 128, st), FFHIP_EIO);
+            FFHIP_CHECK(hipMemsetAsync(d_coef_u, 0, total_mcus * 128, st), FFHIP_EIO);
+            FFHIP_CHECK(hipMemsetAsync(d_coef_v, 0, total_mcus * 128, st), FFHIP_EIO);
         }
     }
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
@@ -552,6 +570,27 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
         return code;
     };
 #define HUFF_CHECK(call) do { if ((call) != hipSuccess) return fail(FFHIP_EIO); } while (0)
+    /* pictures [lo, hi) from their planes to then's BGRA on `on`: one geometry, one ffhip_jpeg_recon_batch; items, one ffhip_jpeg_recon_items (scratch
+     * slot `part`: the parts' calls are in flight side by side) */
+    std::vector<ffhip_jpeg_item> then_items;
+    auto recon_then = [&](int lo, int hi, void *on, int part) -> int {
+        if (!then->items) {
+            const size_t mcus = pic_mcus[0];
+            return ffhip_jpeg_recon_batch(geom, hi - lo, d_coef_y + (size_t)lo * mcus * geom->h * geom->v * 64, d_coef_u ? d_coef_u + (size_t)lo * mcus * 64 : nullptr,
+                                          d_coef_v ? d_coef_v + (size_t)lo * mcus * 64 : nullptr, d_quant + (size_t)lo * 256, 256,
+                                          then->bgra + (int64_t)lo * then->image_stride, then->pitch, then->image_stride, nullptr, 0, on);
+        }
+        then_items.assign(then->items + lo, then->items + hi);
+        for (int i = lo; i < hi; i++) {
+            ffhip_jpeg_item &it = then_items[(size_t)(i - lo)];
+            const size_t b = mcu_base[(size_t)i];
+            it.d_coef_y = d_coef_y + b * geom->h * geom->v * 64;
+            it.d_coef_u = d_coef_u ? d_coef_u + b * 64 : nullptr;
+            it.d_coef_v = d_coef_v ? d_coef_v + b * 64 : nullptr;
+            it.d_quant = d_quant + (size_t)i * 256;
+        }
+        return jpeg_recon_items_impl(then_items.data(), hi - lo, on, part);
+    };
     int n_parts = n >= 32 ? 4 : 1;
     if (use_sync) {
         /* parts of about 140 MB of scan bytes, a hundred 4K files -- a round over fewer subsequences fills the chip badly, and what is left to wait for
@@ -633,8 +672,8 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
                         sg.scan_off = im.scan_off + sgv[k];
                         sg.clean_len = sgv[k + 1] - sgv[k];
                         sg.raw_len = raws[(size_t)i][k];
-                        sg.mcu0 = (uint32_t)((size_t)(i - p_lo) * mcus + (size_t)k * im.restart);
-                        const size_t left = mcus - (size_t)k * im.restart;
+                        sg.mcu0 = (uint32_t)((size_t)(mcu_base[(size_t)i] - mcu_base[(size_t)p_lo]) + (size_t)k * im.restart);
+                        const size_t left = im.mcus - (size_t)k * im.restart;
                         sg.mcus = (uint32_t)(left < im.restart ? left : im.restart);
                         part_segs[part].push_back(sg);
                     }
@@ -642,13 +681,13 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
                 job.segs = part_segs[part].data();
                 job.n_segs = part_segs[part].size();
                 if (rc) return fail(rc);
-                job.plane[0] = d_coef_y + (size_t)p_lo * mcus * images[0].nb[0] * 64;
-                job.plane[1] = d_coef_u ? d_coef_u + (size_t)p_lo * mcus * images[0].nb[1] * 64 : nullptr;
-                job.plane[2] = d_coef_v ? d_coef_v + (size_t)p_lo * mcus * images[0].nb[2] * 64 : nullptr;
+                const size_t base = mcu_base[(size_t)p_lo];
+                job.plane[0] = d_coef_y + base * images[0].nb[0] * 64;
+                job.plane[1] = d_coef_u ? d_coef_u + base * images[0].nb[1] * 64 : nullptr;
+                job.plane[2] = d_coef_v ? d_coef_v + base * images[0].nb[2] * 64 : nullptr;
                 rc = huff_sync_enqueue(job, pstream, &h_cnt[part]);
                 if (!rc && then) /* the part's pictures: coefficients -> BGRA while the next part's bytes come up */
-                    rc = ffhip_jpeg_recon_batch(geom, p_hi - p_lo, job.plane[0], job.plane[1], job.plane[2], d_quant + (size_t)p_lo * 256, 256,
-                                                then->bgra + (int64_t)p_lo * then->image_stride, then->pitch, then->image_stride, nullptr, 0, pstream);
+                    rc = recon_then(p_lo, p_hi, pstream, part);
             }
             if (rc) return fail(rc); /* nothing of this call may be in flight when its buffers are handed back */
         }
@@ -693,7 +732,7 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
     HUFF_CHECK(hipGetLastError());
     (void)hipEventRecord(g_huff_ev[1], st);
     if (!use_sync && then) {
-        const int rc = ffhip_jpeg_recon_batch(geom, n, d_coef_y, d_coef_u, d_coef_v, d_quant, 256, then->bgra, then->pitch, then->image_stride, nullptr, 0, stream);
+        const int rc = recon_then(0, n, stream, 0);
         if (rc) return fail(rc);
     }
     /* per-picture verdicts come back with the stream (tiny); the staging buffer is free again after this sync */
@@ -716,8 +755,7 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
             const int p_lo = (int)((job.o_status - o_status) / 4);
             int rc = huff_sync_finish(job, job.stream, h_cnt[part], status + p_lo);
             if (!rc && job.reran && then) { /* the part's passes ran only now: so must its reconstruction (and the caller's stream be behind it) */
-                rc = ffhip_jpeg_recon_batch(geom, job.n, job.plane[0], job.plane[1], job.plane[2], d_quant + (size_t)p_lo * 256, 256,
-                                            then->bgra + (int64_t)p_lo * then->image_stride, then->pitch, then->image_stride, nullptr, 0, job.stream);
+                rc = recon_then(p_lo, p_lo + job.n, job.stream, part);
                 if (!rc && job.stream != stream && hipStreamSynchronize((hipStream_t)job.stream) != hipSuccess) rc = FFHIP_EIO;
             }
             if (rc) return fail(rc);
@@ -732,7 +770,7 @@ extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const s
                                             const ffhip_jpeg_geom *geom, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v,
                                             uint16_t *d_quant, int *status, void *stream)
 {
-    return jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, geom, d_coef_y, d_coef_u, d_coef_v, d_quant, status, stream, nullptr);
+    return jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, geom, nullptr, d_coef_y, d_coef_u, d_coef_v, d_quant, status, stream, nullptr);
 }
 
 /* =====================================================================================================================

@@ -27,6 +27,10 @@ void ffhip_note_hip_error(int hip_error, const char *what);
 int ffhip_have_device(void); /* 1 once ffhip_init succeeded on a gfx950 device */
 uint32_t *ffhip_scratch(int kind, void *stream, size_t words); /* per (kind, device, stream) device scratch, NULL on failure */
 uint8_t *ffhip_pinned_scratch(int kind, void *stream, size_t bytes); /* per (kind, device, stream) pinned host staging, NULL on failure */
+/* the same staging for a call that only enqueues: waits for the copy out of it that the stream's previous call of this kind recorded with
+ * ffhip_pinned_staged (not for the whole stream), so that the buffer may be refilled */
+uint8_t *ffhip_pinned_staging(int kind, void *stream, size_t bytes);
+int ffhip_pinned_staged(int kind, void *stream); /* behind the copy just enqueued out of the kind's staging on `stream` */
 int *ffhip_async_err_word(void); /* pinned word kernels report an in-launch abort through; see ffhip_stream_sync */
 void ffhip_release_caches(void); /* frees what the library keeps between calls, every thread's (ffhip_state_release): no call of any thread may be
                                     in flight, its host part included */
@@ -91,6 +95,8 @@ enum FfhipScratchKind {
     SCRATCH_HEVC_TILES_CHUNK = 21, /* .. + 3 */
     SCRATCH_HEVC_TILES_ONE = 25,   /* .. + 1 */
     SCRATCH_HUFF_SYNC = 30,        /* .. + FFHIP_HUFF_PARTS - 1 */
+    SCRATCH_FILES_MIXED = 7,       /* ffhip_jpeg_decode_files_mixed_device: a class's planes and quantiser tables, the host decoder's pinned planes */
+    SCRATCH_JPEG_ITEMS = 40,       /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items' records and per-workgroup table, pinned records */
 };
 
 /* ffhip_vp8_decode_frames (row form) -> ffhip_vp8_predict_loopfilter: the colour conversion the caller enqueues behind the call belongs to
@@ -120,10 +126,17 @@ int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint
 
 /* ffhip_jpeg_decode_files_device -> ffhip_jpeg_entropy_batch_gpu: the reconstruction of the pictures, enqueued by the entropy call itself behind
  * each part of the batch it has decoded */
-struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; };
+/* items (mixed batches, ffhip_jpeg_decode_files_mixed_device): per picture its geometry, output and pitch; the call fills in the plane and
+ * quantiser pointers and reconstructs with ffhip_jpeg_recon_items instead (bgra, pitch and image_stride unused) */
+struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_jpeg_item *items; };
+/* geoms: NULL = every picture has *geom; else picture i has geoms[i], all of *geom's layout class (ncomp, h, v): the planes hold the
+ * pictures one behind the other, picture i at the sum of the MCUs of the pictures before it */
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
-                                int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant, int *status, void *stream,
-                                const FfhipHuffThen *then);
+                                const ffhip_jpeg_geom *geoms, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant,
+                                int *status, void *stream, const FfhipHuffThen *then);
+int jpeg_item_class(const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch); /* the layout class 0..6 of a picture ffhip_jpeg_recon_items takes
+                                                                                        with this output and pitch, -1 if it refuses it */
+int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot); /* ffhip_jpeg_recon_items with scratch slot 0..FFHIP_HUFF_PARTS-1 */
 
 /* ---- what the library keeps between calls (ffhip_state.hip) ---- */
 /* The record of a stream's last side-by-side VP8 call, for its repeat by ffhip_stream_sync (ffhip_vp8_lf.hip); `armed` says whether it
@@ -154,6 +167,7 @@ struct FfhipBuf { void *p = nullptr; size_t cap = 0; };
  * in ffhip_release_caches / ffhip_shutdown. */
 struct FfhipStreamState {
     std::map<int, FfhipBuf> scratch, pinned; /* by kind; cap in words / bytes */
+    std::map<int, hipEvent_t> staged;        /* by kind: behind the last copy out of its pinned staging (ffhip_pinned_staged) */
     FfhipVp8Retry retry;
     unsigned long long vp8_seq = 0; /* VP8 prediction / filter calls enqueued so far: a retry record is only good while its call is the LAST of them */
     FfhipTileGuard tiles;

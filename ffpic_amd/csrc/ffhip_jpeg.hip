@@ -38,7 +38,9 @@
 
 #include <errno.h>
 #include <stdlib.h>
+#include <string.h>
 #include <mutex>
+#include <vector>
 
 #ifndef WAVES_PER_WG
 #define WAVES_PER_WG 4
@@ -268,6 +270,56 @@ __device__ __forceinline__ u32 xcd_remap_wg(int mode)
 }
 
 /* ------------------------------------------------------------------------
+ * Mixed batches (ffhip_jpeg_recon_items): items of one layout class that differ in size, planes, quantiser tables, output
+ * and pitch, in one launch.  The host lays the items' workgroups end to end (first_wg: a prefix sum of what each needs) and
+ * k_jpeg_items_table writes every item's index over its range of a per-workgroup table; a workgroup of an items kernel
+ * then reads its item with one wave-uniform load after the XCD remap -- no search -- and the item's record with a few
+ * more, builds the batch of one the uniform body runs on, and runs it.  Loads only: nothing per item is written back.
+ * ---------------------------------------------------------------------- */
+struct JpegItemDesc { /* 96 bytes, 16-byte aligned: scalar loads */
+    const int16_t *coef_y, *coef_u, *coef_v;
+    const uint16_t *quant;
+    uint8_t *bgra;
+    long long pitch;
+    int mcu_cols, mcu_rows, quads_per_row, quads_per_image;
+    u32 qpr_magic;
+    int qt_y, qt_u, qt_v;
+    u32 first_wg, n_wgs; /* the item's range of the per-workgroup table */
+    u32 pad[2];
+};
+static_assert(sizeof(JpegItemDesc) == 96, "JpegItemDesc layout");
+struct JpegItems {
+    const JpegItemDesc *desc;
+    const u32 *wg_item; /* per workgroup of the call: its item */
+    u32 wg_base;        /* this launch's first workgroup (a class's launches, split below 2^31 workgroups) */
+    int xcd_remap;
+};
+
+/* one workgroup per item: the item's index over its range of the per-workgroup table */
+__global__ __launch_bounds__(256) void k_jpeg_items_table(const JpegItemDesc *desc, u32 *wg_item)
+{
+    const u32 item = blockIdx.x, first = desc[item].first_wg, n = desc[item].n_wgs;
+    for (u32 k = threadIdx.x; k < n; k += 256) wg_item[first + k] = item;
+}
+
+/* the batch of one the workgroup belongs to (img = 0, pointers the item's own); returns the workgroup's index inside it */
+__device__ __forceinline__ int jpeg_item_batch(const JpegItems &t, JpegBatch &p)
+{
+    const u32 wg = t.wg_base + xcd_remap_wg(t.xcd_remap);
+    const u32 item = __builtin_amdgcn_readfirstlane(t.wg_item[wg]);
+    const JpegItemDesc &d = t.desc[item];
+    p.coef_y = d.coef_y; p.coef_u = d.coef_u; p.coef_v = d.coef_v;
+    p.quant = d.quant; p.quant_stride = 0;
+    p.bgra = d.bgra; p.pitch = d.pitch; p.image_stride = 0;
+    p.mcu_cols = d.mcu_cols; p.mcu_rows = d.mcu_rows; p.quads_per_row = d.quads_per_row; p.n_images = 1;
+    p.qt_y = d.qt_y; p.qt_u = d.qt_u; p.qt_v = d.qt_v;
+    p.quads_per_image = d.quads_per_image; p.qpr_magic = d.qpr_magic;
+    p.wgs_per_image = (int)d.n_wgs; p.wpi_magic = 0;
+    p.xcd_remap = t.xcd_remap; p.pattern_only = 0;
+    return (int)(wg - d.first_wg);
+}
+
+/* ------------------------------------------------------------------------
  * Fused kernel, 3 components, h = v = 2.
  * ---------------------------------------------------------------------- */
 
@@ -471,54 +523,17 @@ __device__ __forceinline__ void quad_pattern(const JpegBatch &p, const LaneRoles
 template <int QPW, int NT, bool PATTERN = false>
 __global__ __launch_bounds__(WG_THREADS) void k_jpeg420_fused(JpegBatch p)
 {
-    __shared__ __attribute__((aligned(16))) char lds_all[WAVES_PER_WG * LDS_WAVE_BYTES];
-    const u32 lane = threadIdx.x & 63;
-    /* wave-uniform values are forced into SGPRs: hipcc cannot prove that anything
-     * derived from threadIdx is uniform and would run all the index math per lane */
-    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    /* 1-D grid over (image, slot group); a slot is QPW consecutive quads of the image's row-major
-     * quad sequence.  Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one), so
-     * the linear id is remapped to give every XCD one contiguous chunk of the sequence: the
-     * pieces of an output row then come from one XCD back to back instead of from eight at
-     * different times (+6 % on the memory-only pattern, tests/tools/membench_jpeg.hip).
-     * Speed only: any placement computes the same bytes. */
-    u32 wg;
-    {
-        wg = xcd_remap_wg(p.xcd_remap);
-    }
-    int img = (int)__umulhi(wg, p.wpi_magic), wgi = (int)wg - img * p.wgs_per_image; /* scalar */
-    if (wgi < 0) { img--; wgi += p.wgs_per_image; }
-    if (wgi >= p.wgs_per_image) { img++; wgi -= p.wgs_per_image; }
-    const int qidx0 = (int)((u32)wgi * WAVES_PER_WG + wave) * QPW;
-    if (qidx0 >= p.quads_per_image) return; /* wave-uniform; no barriers anywhere in this kernel */
+#include "ffhip_jpeg420_body.inc"
+}
 
-    WaveCtx c;
-    wave_ctx_init(c, lds_all + wave * LDS_WAVE_BYTES, lane);
-    LaneRoles r;
-    lane_roles_init(r, c, lane, (u32)p.pitch);
-
-    int mrow[QPW], qcol[QPW];
-    QuadLoads ld[QPW];
-#pragma unroll
-    for (int i = 0; i < QPW; i++) {
-        int qi = qidx0 + i;
-        qi = qi < p.quads_per_image ? qi : p.quads_per_image - 1; /* duplicate load, never stored */
-        int mr = (int)__umulhi((u32)qi, p.qpr_magic), qc = qi - mr * p.quads_per_row; /* scalar */
-        if (qc < 0) { mr--; qc += p.quads_per_row; }
-        if (qc >= p.quads_per_row) { mr++; qc -= p.quads_per_row; } /* quads_per_row == 1: magic saturates */
-        mrow[i] = mr;
-        qcol[i] = qc;
-        ld[i] = quad_load<NT & 1>(p, r, lane, img, mr, qc * 4);
-    }
-    const uint16_t *qt = p.quant + (long long)img * p.quant_stride;
-    const u32x4 q_y = *(const u32x4 *)(qt + p.qt_y * 64 + r.row * 8);
-    const u32x4 q_c = *(const u32x4 *)(qt + (lane < 32 ? p.qt_u : p.qt_v) * 64 + r.row * 8);
-#pragma unroll
-    for (int i = 0; i < QPW; i++)
-        if (qidx0 + i < p.quads_per_image) {
-            if (PATTERN) quad_pattern<NT>(p, r, ld[i], img, mrow[i], qcol[i] * 4);
-            else quad_recon<NT>(p, c, r, lane, ld[i], q_y, q_c, img, mrow[i], qcol[i] * 4);
-        }
+/* the same over the items of ffhip_jpeg_recon_items, one workgroup's item from the per-workgroup table */
+template <int QPW, int NT>
+__global__ __launch_bounds__(WG_THREADS) void k_jpeg420_fused_items(JpegItems items)
+{
+    constexpr bool PATTERN = false;
+#define FFHIP_JPEG_ITEMS 1
+#include "ffhip_jpeg420_body.inc"
+#undef FFHIP_JPEG_ITEMS
 }
 
 /* ------------------------------------------------------------------------
@@ -545,254 +560,16 @@ __global__ __launch_bounds__(WG_THREADS) void k_jpeg420_fused(JpegBatch p)
 template <int H, int V, int NC, int NT, bool PATTERN = false, int TWO = 0> /* PATTERN: the loads and the stores only (ffhip_jpeg_pattern_calibrate) */
 __global__ __launch_bounds__(WG_THREADS) void k_jpeg_fused_strip(JpegBatch p)
 {
-    constexpr int BPM = H * V;                            /* luma blocks per MCU          */
-    constexpr int MPS = ((NC == 1 || BPM == 1) ? 8 : 4) * ((TWO && BPM < 4) ? 2 : 1); /* MCUs per strip (of a wave) */
-    constexpr int LR = MPS * BPM / 8;                    /* luma rounds: 4:1:1 and its transpose take TWO strips' worth of luma per wave (1 024 pixels), so that
-                                                            their one chroma round (4 U + 4 V blocks) has no idle block -- 1.5 rounds per 512 pixels where the
-                                                            single strip took 2 -- and the transpose's rows are runs of 128 bytes, not 64 */
-    constexpr int PASSES = 2 * LR;                       /* colour passes of 256 pixels */
-    constexpr int SW = MPS * 8 * H, SH = 8 * V;          /* strip size in pixels (512; h * v = 4 or TWO: 1024) */
-    constexpr int CW = MPS * 8;                          /* chroma samples per strip row */
-    constexpr int GPR = SW / 4;                          /* 4-pixel groups per pixel row */
-    constexpr int RPP = 64 / GPR;                        /* lane rows per pass */
-    static_assert((LR == 1 || LR == 2) && SW * SH == 512 * LR && BPM <= 4 && BPM != 3 && (H == 1 || V == 1), "strip geometry");
-    /* the sample planes in the wave's LDS behind the 1 KB work tile: luma SW x SH, then U and V (8 rows of CW) */
-    constexpr int CPB = CW * 8 * 2;                      /* bytes of a chroma plane */
-    constexpr int YP = SM_YP, UP = YP + SW * SH * 2, VP = UP + ((LR == 1 && CPB < 1024) ? 1024 : CPB);
-    constexpr int WAVE_LDS = NC == 3 ? VP + CPB : UP;
-    constexpr int WAVE_BYTES = WAVE_LDS <= SM_WAVE_BYTES ? SM_WAVE_BYTES : (WAVE_LDS + 1023) / 1024 * 1024; /* 4 KB as ever; TWO: 4:4:4 7 KB, 4:2:2 / 4:4:0 5 KB */
-    static_assert(UP == SM_UP || LR == 2, "plane offsets");
-    __shared__ __attribute__((aligned(16))) char lds_all[WAVES_PER_WG * WAVE_BYTES];
-    const u32 lane = threadIdx.x & 63;
-    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    u32 wg;
-    {
-        wg = xcd_remap_wg(p.xcd_remap);
-    }
-    int img = (int)__umulhi(wg, p.wpi_magic), wgi = (int)wg - img * p.wgs_per_image; /* scalar */
-    if (wgi < 0) { img--; wgi += p.wgs_per_image; }
-    if (wgi >= p.wgs_per_image) { img++; wgi -= p.wgs_per_image; }
-    const int sidx = (int)((u32)wgi * WAVES_PER_WG + wave);
-    if (sidx >= p.quads_per_image) return; /* wave-uniform; no barriers in this kernel */
-    int mrow = (int)__umulhi((u32)sidx, p.qpr_magic), scol = sidx - mrow * p.quads_per_row;
-    if (scol < 0) { mrow--; scol += p.quads_per_row; }
-    if (scol >= p.quads_per_row) { mrow++; scol -= p.quads_per_row; }
-    const int mcu0 = scol * MPS, last = p.mcu_cols - 1;
-    const int rem = last - mcu0 < MPS - 1 ? last - mcu0 : MPS - 1; /* MCUs of this strip that exist, minus one */
+#include "ffhip_jpeg_strip_body.inc"
+}
 
-    WaveCtx c;
-    wave_ctx_init(c, lds_all + wave * WAVE_BYTES, lane);
-    const u32 row = lane & 7, lblk = lane >> 3;
-    const long long mcu_base = ((long long)img * p.mcu_rows + mrow) * p.mcu_cols + mcu0; /* scalar */
-    const uint16_t *qt = p.quant + (long long)img * p.quant_stride;
-
-    /* ---- all loads up front: ragged strips re-read their last MCU, its pixels are never stored ---- */
-    u32x4 ly[LR], lc0, lc1, lc2, lc3; /* (lc2, lc3: the second halves of U and V where a wave has sixteen MCUs of 4:4:4) */
-#pragma unroll
-    for (int lr = 0; lr < LR; lr++) {
-        int m = ((int)lblk + 8 * lr) / BPM;
-        m = m > rem ? rem : m;
-        ly[lr] = load16<NT & 1>((const char *)(p.coef_y + (mcu_base + m) * (64 * BPM) + (((int)lblk + 8 * lr) % BPM) * 64 + row * 8));
-    }
-    const u32x4 q_y = *(const u32x4 *)(qt + p.qt_y * 64 + row * 8);
-    u32x4 q_c0 = q_y, q_c1 = q_y;
-    if (NC == 3) {
-        if (MPS >= 8) { /* rounds of 8 blocks: U, then V (sixteen MCUs: two of each) */
-            const int m = (int)lblk > rem ? rem : (int)lblk;
-            lc0 = load16<NT & 1>((const char *)(p.coef_u + (mcu_base + m) * 64 + row * 8));
-            lc1 = load16<NT & 1>((const char *)(p.coef_v + (mcu_base + m) * 64 + row * 8));
-            if (MPS == 16) {
-                const int m2 = (int)lblk + 8 > rem ? rem : (int)lblk + 8;
-                lc2 = load16<NT & 1>((const char *)(p.coef_u + (mcu_base + m2) * 64 + row * 8));
-                lc3 = load16<NT & 1>((const char *)(p.coef_v + (mcu_base + m2) * 64 + row * 8));
-            }
-            q_c0 = *(const u32x4 *)(qt + p.qt_u * 64 + row * 8);
-            q_c1 = *(const u32x4 *)(qt + p.qt_v * 64 + row * 8);
-        } else {        /* one round: blocks 0-3 = U of MCU 0-3, blocks 4-7 = V */
-            int m = (int)(lblk & 3);
-            m = m > rem ? rem : m;
-            lc0 = load16<NT & 1>((const char *)((lane < 32 ? p.coef_u : p.coef_v) + (mcu_base + m) * 64 + row * 8));
-            q_c0 = *(const u32x4 *)(qt + (lane < 32 ? p.qt_u : p.qt_v) * 64 + row * 8);
-        }
-    }
-
-    /* ---- IDCT rounds -> sample planes in LDS: luma SH rows x SW, chroma 8 rows x CW (int16).  The 16-byte chunks of a
-     * plane row are XOR-swizzled by the row (sw_off) so that the block-row writes here (lanes of one block are 8 rows
-     * apart at the same chunk) and the row-segment reads of the colour passes both touch every bank once: laid out
-     * plainly, the writes were 4-way bank conflicts (175 M conflict cycles per launch at 4:4:4, profiles/r1_jpeg_geoms_pmc.txt) ---- */
-    /* v = 2: the colour passes take rows 2j (pass 0) and 2j + 1 (pass 1) on the same lane, so that the chroma terms the
-     * two rows share are computed once; the luma plane keeps the even rows first, then the odd ones, which keeps the
-     * four rows a pass reads at once in four different bank quarters */
-    auto yrow_pos = [](u32 r) -> u32 { return (r >> 1) + 8 * (r & 1u); };
-    auto sw_off = [](u32 row, u32 col, u32 row_samples) -> u32 { /* byte offset of sample (row, col) in a swizzled plane */
-        const u32 key = row_samples >= 64 ? (row & 7u) : ((row >> 2) & 3u);
-        return row * row_samples * 2 + ((((col >> 3) ^ key) & (row_samples / 8 - 1)) << 4) + (col & 7u) * 2;
-    };
-    u32x4 pat = {0u, 0u, 0u, 0u}; /* PATTERN: what gets stored -- an XOR of everything the wave loaded */
-    if (PATTERN) {
-#pragma unroll
-        for (int lr = 0; lr < LR; lr++) pat = pat ^ ly[lr];
-        if (NC == 3) pat = pat ^ lc0;
-        if (NC == 3 && MPS >= 8) pat = pat ^ lc1;
-        if (NC == 3 && MPS == 16) pat = pat ^ lc2 ^ lc3;
-    }
-#pragma unroll
-    for (int lr = 0; lr < LR && !PATTERN; lr++) {
-        const u32x4 pk = idct8x8_round(c, ly[lr], q_y);
-        const u32 gb = c.blk + 8 * lr, m = gb / BPM, sub = gb % BPM;
-        const u32 pcol = (m * H + (H > 1 ? sub : 0)) * 8, prow = (V > 1 ? sub : 0) * 8 + c.idx;
-        *(u32x4 *)(c.lds + YP + sw_off(V == 2 ? yrow_pos(prow) : prow, pcol, SW)) = pk;
-    }
-    if (NC == 3 && !PATTERN) {
-        if (MPS >= 8) {
-            const u32x4 pu = idct8x8_round(c, lc0, q_c0);
-            *(u32x4 *)(c.lds + UP + sw_off(c.idx, c.blk * 8, CW)) = pu;
-            const u32x4 pv = idct8x8_round(c, lc1, q_c1);
-            *(u32x4 *)(c.lds + VP + sw_off(c.idx, c.blk * 8, CW)) = pv;
-            if (MPS == 16) {
-                const u32x4 pu2 = idct8x8_round(c, lc2, q_c0);
-                *(u32x4 *)(c.lds + UP + sw_off(c.idx, (c.blk + 8) * 8, CW)) = pu2;
-                const u32x4 pv2 = idct8x8_round(c, lc3, q_c1);
-                *(u32x4 *)(c.lds + VP + sw_off(c.idx, (c.blk + 8) * 8, CW)) = pv2;
-            }
-        } else {
-            const u32x4 pc = idct8x8_round(c, lc0, q_c0);
-            if (MPS == 4 || (c.blk & 3) < MPS) /* h*v = 4: blocks 2, 3, 6, 7 of the round are repeats of the strip's last MCU */
-                *(u32x4 *)(c.lds + (c.blk < 4 ? UP : VP) + sw_off(c.idx, (c.blk & 3) * 8, CW)) = pc;
-        }
-    }
-
-    /* ---- colour: 2 passes x 4 pixels per lane; 4/H chroma samples serve them.  Same packed form as the 4:2:0 kernel:
-     * per pixel PAIR three 16-bit adds, three saturating packs and three byte permutes ---- */
-    uint8_t *const obase = p.bgra + (long long)img * p.image_stride + (long long)mrow * SH * p.pitch + (long long)mcu0 * (32 * H);
-    TermBits grey_t = {};
-    if (NC == 1) grey_t = chroma_term_bits(0u, 0u); /* U = V = 0 planes (jpg.c:501,552-554): uu = vv = -128, never "sensitive" */
-    u32 tr2[2], tg2[2], tb2[2], us[2] = {0, 0}, vs[2] = {0, 0}, sens = 0;
-    /* per-lane LDS offsets of the two passes, computed once: pass 1 reads 64 / GPR rows (v = 2: 8 row positions) further
-     * on, which flips one bit of the swizzle key -- an XOR and an add instead of a second address computation */
-    const u32 row0 = V >= 2 ? 2 * (lane / GPR) : lane / GPR, pc0 = (lane % GPR) * 4;
-    const u32 y_off0 = sw_off(V == 2 ? yrow_pos(row0) : row0, pc0, SW);
-    /* v = 4: rows 2j and 2j + 1 share (row >> 2), i.e. the swizzle key: the next plane row, 32 bytes on */
-    const u32 y_off1 = SW == 64 ? (y_off0 ^ 0x40u) + 4 * 128 : (SW == 32 ? (y_off0 ^ 0x20u) + 8 * 64 : y_off0 + 32);
-    static_assert((SW == 64 && 64 / GPR == 4 && V == 1) || (SW == 32 && V == 2) || LR == 2, "pass-1 offset identities");
-    /* the pixel row of pass `it`.  v = 1: RPP lane rows a pass, one below the other (128 x 8 pixels: two rows a pass, four passes).  v >= 2: a lane takes rows
-     * 2j and 2j + 1 in two passes running (they share their chroma row), RPP such pairs a pass pair -- the transpose of 4:1:1 (32 x 32): the upper half, then the
-     * lower half; two strips of 4:4:0 (64 x 16): rows 0-7, then 8-15 */
-    auto pass_row = [&](int it) -> u32 {
-        return V >= 2 ? row0 + (u32)(it & 1) + (u32)(2 * RPP * (it >> 1)) : row0 + (u32)(it * RPP);
-    };
-    u32 y_offs[PASSES], c_offs[PASSES];
-#pragma unroll
-    for (int it = 0; it < PASSES; it++) {
-        y_offs[it] = LR == 2 ? sw_off(V == 2 ? yrow_pos(pass_row(it)) : pass_row(it), pc0, SW) : (it ? y_off1 : y_off0); /* (four passes: worked out pass by pass) */
-        c_offs[it] = 0;
-    }
-    const u32 c_off0 = NC == 3 ? sw_off(row0 / V, pc0 / H, CW) : 0;
-    /* v = 1: pass 1 is four rows down -- one bit of the key flips and four chroma rows (CW samples each) are skipped */
-    const u32 c_off1 = V >= 2 ? c_off0 : (CW == 64 ? (c_off0 ^ 0x40u) + 4 * 128 : (c_off0 ^ 0x10u) + 4 * CW * 2);
-#pragma unroll
-    for (int it = 0; it < PASSES; it++) c_offs[it] = (LR == 2 && NC == 3) ? sw_off(pass_row(it) / V, pc0 / H, CW) : (it ? c_off1 : c_off0);
-#pragma unroll
-    for (int it = 0; it < PASSES; it++) {
-        const u32 prow = pass_row(it);
-        if (PATTERN) { /* the pass's store, at its address and under its mask */
-            if (mcu0 + (int)(pc0 / (8 * H)) <= last) {
-                u32x4 *dst = (u32x4 *)(obase + (long long)prow * p.pitch + pc0 * 4);
-                if (NT & 2) __builtin_nontemporal_store(pat + (u32)it, dst);
-                else *dst = pat + (u32)it;
-            }
-            continue;
-        }
-        const u32x2 yy = *(const u32x2 *)(c.lds + YP + y_offs[it]);
-        if (V >= 2 && (it & 1)) {
-            /* the terms of pass 0 serve this row too */
-        } else if (NC == 1) {
-            tr2[0] = tr2[1] = __builtin_amdgcn_perm(grey_t.r, grey_t.r, 0x01000100u);
-            tg2[0] = tg2[1] = __builtin_amdgcn_perm(grey_t.g, grey_t.g, 0x01000100u);
-            tb2[0] = tb2[1] = __builtin_amdgcn_perm(grey_t.b, grey_t.b, 0x01000100u);
-        } else {
-            const u32 c_off = c_offs[it];
-            if (H == 1) {
-                const u32x2 a = *(const u32x2 *)(c.lds + UP + c_off), b = *(const u32x2 *)(c.lds + VP + c_off);
-                us[0] = a[0]; us[1] = a[1]; vs[0] = b[0]; vs[1] = b[1];
-            } else if (H == 2) {
-                us[0] = *(const u32 *)(c.lds + UP + c_off);
-                vs[0] = *(const u32 *)(c.lds + VP + c_off);
-                us[1] = vs[1] = 0;
-            } else { /* h = 4: the lane's four pixels share one chroma sample */
-                us[0] = *(const uint16_t *)(c.lds + UP + c_off);
-                vs[0] = *(const uint16_t *)(c.lds + VP + c_off);
-                us[1] = vs[1] = 0;
-            }
-            sens = 0;
-            if (H == 4) {
-                const TermBits t = chroma_term_bits(us[0], vs[0]);
-                sens = t.sens ? 1u : 0u;
-                tr2[0] = tr2[1] = __builtin_amdgcn_perm(t.r, t.r, 0x01000100u);
-                tg2[0] = tg2[1] = __builtin_amdgcn_perm(t.g, t.g, 0x01000100u);
-                tb2[0] = tb2[1] = __builtin_amdgcn_perm(t.b, t.b, 0x01000100u);
-            } else {
-                constexpr int NP = H == 1 ? 2 : 1; /* sample pairs: two at h = 1, one at h = 2 */
-                TermBits2 t[NP];
-#pragma unroll
-                for (int k = 0; k < NP; k++) t[k] = chroma_term_bits2(us[k], vs[k]);
-                float any;
-                if (H == 1) {
-                    const f32x2 m = t[0].rem * t[NP - 1].rem;
-                    any = m.x * m.y;
-#pragma unroll
-                    for (int h2 = 0; h2 < 2; h2++) { /* one chroma sample per pixel */
-                        tr2[h2] = t[h2 % NP].r;
-                        tg2[h2] = t[h2 % NP].g;
-                        tb2[h2] = t[h2 % NP].b;
-                    }
-                } else {
-                    any = t[0].rem.x * t[0].rem.y;
-                    tr2[0] = __builtin_amdgcn_perm(t[0].r, t[0].r, 0x01000100u); /* a pixel pair shares its chroma sample */
-                    tr2[1] = __builtin_amdgcn_perm(t[0].r, t[0].r, 0x03020302u);
-                    tg2[0] = __builtin_amdgcn_perm(t[0].g, t[0].g, 0x01000100u);
-                    tg2[1] = __builtin_amdgcn_perm(t[0].g, t[0].g, 0x03020302u);
-                    tb2[0] = __builtin_amdgcn_perm(t[0].b, t[0].b, 0x01000100u);
-                    tb2[1] = __builtin_amdgcn_perm(t[0].b, t[0].b, 0x03020302u);
-                }
-                if (any == 0.0f) { /* rare: some sample's G sum is a multiple of 1000 (zero included) */
-#pragma unroll
-                    for (int k = 0; k < 2 * NP; k++) {
-                        const float rem = (k & 1) ? t[k >> 1].rem.y : t[k >> 1].rem.x, sf = (k & 1) ? t[k >> 1].sf.y : t[k >> 1].sf.x;
-                        sens |= (rem == 0.0f && sf != 76288.0f) ? 1u << k : 0u;
-                    }
-                }
-            }
-        }
-        u32x4 px;
-#pragma unroll
-        for (int h2 = 0; h2 < 2; h2++) {
-            const u32 y2 = yy[h2];
-            const u32 r2 = sat_pk_u8_i16(pk_add16(y2, tr2[h2]));
-            const u32 g2 = sat_pk_u8_i16(pk_add16(y2, tg2[h2]));
-            const u32 b2 = sat_pk_u8_i16(pk_add16(y2, tb2[h2]));
-            const u32 bg = __builtin_amdgcn_perm(g2, b2, 0x05010400u); /* b0 g0 b1 g1 */
-            px[2 * h2] = __builtin_amdgcn_perm(r2, bg, 0x0d040100u);     /* b0 g0 r0 ff */
-            px[2 * h2 + 1] = __builtin_amdgcn_perm(r2, bg, 0x0d050302u); /* b1 g1 r1 ff */
-        }
-        if (NC == 3 && sens) { /* rare: exact-integer G decided by the fp64 roundings */
-#pragma unroll
-            for (int d = 0; d < 4; d++) {
-                const int k = d / H;
-                if (sens & (1u << k)) {
-                    const int y1 = (int)((d & 1) ? (yy[d >> 1] >> 16) : (yy[d >> 1] & 0xffffu));
-                    const u32 ua = (k & 1) ? (us[k >> 1] >> 16) : (us[k >> 1] & 0xffffu); /* raw samples: uu = u - 128 (colorspace.c:149) */
-                    const u32 va = (k & 1) ? (vs[k >> 1] >> 16) : (vs[k >> 1] & 0xffffu);
-                    px[d] = (px[d] & 0xffff00ffu) | (green_fp64(y1, (int)ua - 128, (int)va - 128) << 8);
-                }
-            }
-        }
-        if (mcu0 + (int)(pc0 / (8 * H)) <= last) {
-            u32x4 *dst = (u32x4 *)(obase + (long long)prow * p.pitch + pc0 * 4);
-            if (NT & 2) __builtin_nontemporal_store(px, dst);
-            else *dst = px;
-        }
-    }
+template <int H, int V, int NC, int NT, int TWO>
+__global__ __launch_bounds__(WG_THREADS) void k_jpeg_fused_strip_items(JpegItems items)
+{
+    constexpr bool PATTERN = false;
+#define FFHIP_JPEG_ITEMS 1
+#include "ffhip_jpeg_strip_body.inc"
+#undef FFHIP_JPEG_ITEMS
 }
 
 /* ------------------------------------------------------------------------
@@ -1124,6 +901,173 @@ static int jpeg_recon_batch_impl(const ffhip_jpeg_geom *g, int n_images, const i
     hipLaunchKernelGGL(k_jpeg_color_generic, dim3(grid), dim3(256), 0, st, cg);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
     return FFHIP_OK;
+}
+
+/* ---- mixed batches: ffhip_jpeg_recon_items ---- */
+
+/* the layout classes of the fused kernels: 4:2:0, 4:4:4, 4:2:2, 4:4:0, h4v1, h1v4, grey; -1 for the two-pass layouts */
+static int jpeg_layout_class(const ffhip_jpeg_geom *g)
+{
+    if (g->ncomp == 1) return g->h == 1 && g->v == 1 ? 6 : -1;
+    if (g->h == 2 && g->v == 2) return 0;
+    if (g->h == 1 && g->v == 1) return 1;
+    if (g->h == 2 && g->v == 1) return 2;
+    if (g->h == 1 && g->v == 2) return 3;
+    if (g->h == 4 && g->v == 1) return 4;
+    if (g->h == 1 && g->v == 4) return 5;
+    return -1;
+}
+#define JPEG_CLASSES 7
+static const int kClassH[JPEG_CLASSES] = {2, 1, 2, 1, 4, 1, 1}, kClassV[JPEG_CLASSES] = {2, 1, 1, 2, 1, 4, 1};
+static bool class_two(int c)
+{
+    const ffhip_jpeg_geom g = {1, 1, c == 6 ? 1 : 3, kClassH[c], kClassV[c], {0, 1, 1}};
+    return c != 0 && strip_two(&g);
+}
+/* MCUs of a quad (4:2:0) or of a strip (the others) */
+static int class_mps(int c, bool two) { return c == 0 ? 4 : ((c == 6 || c == 1) ? 8 : 4) * (two ? 2 : 1); }
+/* the class of a picture with this geometry, output and pitch, or -1: the limits jpeg_recon_batch_impl puts on a batch of one */
+static int item_class(const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch, const int mps[JPEG_CLASSES])
+{
+    if (!geom_ok(g)) return -1;
+    const int c = jpeg_layout_class(g);
+    if (c < 0) return -1; /* the two-pass layouts are not part of the mixed path */
+    if (!d_bgra || ((uintptr_t)d_bgra & 15)) return -1;
+    const int64_t width = (int64_t)g->mcu_cols * 8 * g->h;
+    if (pitch < width * 4 || (pitch & 15) || pitch * 16 > 0x7fffffffLL) return -1;
+    const long long qpr = (g->mcu_cols + mps[c] - 1) / mps[c];
+    if (qpr > 4096 || qpr * g->mcu_rows > (1 << 20)) return -1;
+    return c;
+}
+int jpeg_item_class(const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch)
+{
+    int mps[JPEG_CLASSES];
+    for (int c = 0; c < JPEG_CLASSES; c++) mps[c] = class_mps(c, class_two(c));
+    return g ? item_class(g, d_bgra, pitch, mps) : -1;
+}
+
+static void launch_strip_items(int cls, bool two, dim3 grid, const JpegItems &t, hipStream_t st)
+{
+#define STRIP_ITEMS(H_, V_, NC_) do { \
+        if (two) hipLaunchKernelGGL((k_jpeg_fused_strip_items<H_, V_, NC_, 3, 1>), grid, dim3(WG_THREADS), 0, st, t); \
+        else hipLaunchKernelGGL((k_jpeg_fused_strip_items<H_, V_, NC_, 3, 0>), grid, dim3(WG_THREADS), 0, st, t); \
+    } while (0)
+    switch (cls) {
+    case 1: STRIP_ITEMS(1, 1, 3); break;
+    case 2: STRIP_ITEMS(2, 1, 3); break;
+    case 3: STRIP_ITEMS(1, 2, 3); break;
+    case 4: STRIP_ITEMS(4, 1, 3); break;
+    case 5: STRIP_ITEMS(1, 4, 3); break;
+    default: STRIP_ITEMS(1, 1, 1); break;
+    }
+#undef STRIP_ITEMS
+}
+static void launch_420_items(int variant, dim3 grid, const JpegItems &t, hipStream_t st)
+{
+#define ITEMS_420(Q, N) hipLaunchKernelGGL((k_jpeg420_fused_items<Q, N>), grid, dim3(WG_THREADS), 0, st, t)
+    switch (variant) {
+    case 10: ITEMS_420(1, 0); break;
+    case 11: ITEMS_420(1, 1); break;
+    case 12: ITEMS_420(1, 2); break;
+    case 13: ITEMS_420(1, 3); break;
+    case 20: ITEMS_420(2, 0); break;
+    case 21: ITEMS_420(2, 1); break;
+    case 22: ITEMS_420(2, 2); break;
+    default: ITEMS_420(2, 3); break;
+    }
+#undef ITEMS_420
+}
+
+/* `slot` (0 .. FFHIP_HUFF_PARTS - 1) picks the scratch: the device entropy decoder enqueues one call per part of its batch, each with its own */
+int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot)
+{
+    if (n < 0 || (n > 0 && !items) || slot < 0 || slot >= FFHIP_HUFF_PARTS) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    /* choices fixed once per call: the 4:2:0 variant as launch_fused reads it, strips per wave per class as launch_strip's callers do */
+    const char *e = FFHIP_ENV("FFHIP_JPEG_VARIANT");
+    const int variant = (e && e[0] >= '1' && e[0] <= '2' && e[1] >= '0' && e[1] <= '3') ? (e[0] - '0') * 10 + (e[1] - '0') : FFHIP_JPEG_DEFAULT_VARIANT;
+    bool two[JPEG_CLASSES];
+    int mps[JPEG_CLASSES], per_wave[JPEG_CLASSES]; /* MCUs of a quad / strip; quads or strips per wave */
+    for (int c = 0; c < JPEG_CLASSES; c++) {
+        two[c] = class_two(c);
+        mps[c] = class_mps(c, two[c]);
+        per_wave[c] = c == 0 ? variant / 10 : 1;
+    }
+    /* every item checked as jpeg_recon_batch_impl checks a batch of one */
+    std::vector<int> cls((size_t)n);
+    int count[JPEG_CLASSES] = {};
+    for (int i = 0; i < n; i++) {
+        const ffhip_jpeg_item &it = items[i];
+        const int c = item_class(&it.geom, it.d_bgra, it.pitch, mps);
+        if (c < 0) return FFHIP_EINVAL;
+        if (!it.d_coef_y || !it.d_quant || (it.geom.ncomp == 3 && (!it.d_coef_u || !it.d_coef_v))) return FFHIP_EINVAL;
+        if (((uintptr_t)it.d_coef_y & 15) || ((uintptr_t)it.d_coef_u & 15) || ((uintptr_t)it.d_coef_v & 15) || ((uintptr_t)it.d_quant & 15))
+            return FFHIP_EINVAL;
+        cls[(size_t)i] = c;
+        count[c]++;
+    }
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    hipStream_t st = (hipStream_t)stream;
+    /* records in class order, every item's workgroups behind those of the items before it */
+    std::vector<JpegItemDesc> desc((size_t)n);
+    int at[JPEG_CLASSES];
+    unsigned long long wg_first[JPEG_CLASSES + 1];
+    for (int c = 0, k = 0; c < JPEG_CLASSES; c++) { at[c] = k; k += count[c]; }
+    for (int i = 0; i < n; i++) {
+        const ffhip_jpeg_item &it = items[i];
+        const ffhip_jpeg_geom *g = &it.geom;
+        const int c = cls[(size_t)i];
+        JpegItemDesc &d = desc[(size_t)at[c]++];
+        d = JpegItemDesc();
+        d.coef_y = it.d_coef_y; d.coef_u = it.d_coef_u; d.coef_v = it.d_coef_v;
+        d.quant = it.d_quant; d.bgra = it.d_bgra; d.pitch = it.pitch;
+        d.mcu_cols = g->mcu_cols; d.mcu_rows = g->mcu_rows;
+        d.quads_per_row = (g->mcu_cols + mps[c] - 1) / mps[c];
+        d.quads_per_image = d.quads_per_row * g->mcu_rows;
+        d.qpr_magic = d.quads_per_row == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)d.quads_per_row) + 1u;
+        d.qt_y = g->qt_id[0]; d.qt_u = g->qt_id[1]; d.qt_v = g->qt_id[2];
+        const int slots = (d.quads_per_image + per_wave[c] - 1) / per_wave[c];
+        d.n_wgs = (u32)((slots + WAVES_PER_WG - 1) / WAVES_PER_WG);
+    }
+    unsigned long long total = 0;
+    for (int c = 0, k = 0; c < JPEG_CLASSES; c++) {
+        wg_first[c] = total;
+        for (int j = 0; j < count[c]; j++, k++) {
+            desc[(size_t)k].first_wg = (u32)total;
+            total += desc[(size_t)k].n_wgs;
+        }
+    }
+    wg_first[JPEG_CLASSES] = total;
+    if (total > 0xffffffffULL) return FFHIP_EINVAL; /* the table's entries are 32-bit workgroup indices */
+    /* device scratch: the records, then the per-workgroup table; pinned staging for the records.  Both per (stream, slot) */
+    const size_t desc_bytes = (size_t)n * sizeof(JpegItemDesc);
+    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_JPEG_ITEMS + slot, stream, desc_bytes / 4 + (size_t)total + 16);
+    if (!dev) return FFHIP_ENOMEM;
+    uint8_t *pin = ffhip_pinned_staging(SCRATCH_JPEG_ITEMS + slot, stream, desc_bytes);
+    if (!pin) return FFHIP_ENOMEM;
+    memcpy(pin, desc.data(), desc_bytes);
+    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
+    if (ffhip_pinned_staged(SCRATCH_JPEG_ITEMS + slot, stream) != FFHIP_OK) return FFHIP_EIO;
+    const JpegItemDesc *d_desc = (const JpegItemDesc *)dev;
+    u32 *d_table = (u32 *)(dev + desc_bytes);
+    hipLaunchKernelGGL(k_jpeg_items_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_table);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    const int remap = jpeg_remap_mode();
+    for (int c = 0; c < JPEG_CLASSES; c++)
+        for (unsigned long long b = wg_first[c]; b < wg_first[c + 1]; b += 0x7fffffffULL) { /* a launch below 2^31 workgroups, as the uniform path splits */
+            const unsigned long long left = wg_first[c + 1] - b;
+            const dim3 grid((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL), 1, 1);
+            JpegItems t;
+            t.desc = d_desc; t.wg_item = d_table; t.wg_base = (u32)b; t.xcd_remap = remap;
+            if (c == 0) launch_420_items(variant, grid, t, st);
+            else launch_strip_items(c, two[c], grid, t, st);
+            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+        }
+    return FFHIP_OK;
+}
+extern "C" int ffhip_jpeg_recon_items(const ffhip_jpeg_item *items, int n, void *stream)
+{
+    return jpeg_recon_items_impl(items, n, stream, 0);
 }
 
 extern "C" int ffhip_jpeg_recon_batch(const ffhip_jpeg_geom *g, int n_images, const int16_t *d_coef_y,

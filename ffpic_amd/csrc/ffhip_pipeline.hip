@@ -253,8 +253,8 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
         int16_t *dy = (int16_t *)base, *du = cb ? dy + (size_t)n * yb : nullptr, *dv = cb ? du + (size_t)n * cb : nullptr;
         uint16_t *dq = (uint16_t *)(base + (((size_t)n * (yb + 2 * cb) * 2 + 15) & ~(size_t)15));
         /* (the reconstruction is enqueued by the entropy call itself, behind each part of the batch as it is decoded) */
-        const FfhipHuffThen then = {d_bgra, pitch, image_stride};
-        rc = jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, &g, dy, du, dv, dq, status, stream, &then);
+        const FfhipHuffThen then = {d_bgra, pitch, image_stride, nullptr};
+        rc = jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, &g, nullptr, dy, du, dv, dq, status, stream, &then);
         if (rc == FFHIP_OK) return FFHIP_OK;
         if (rc != FFHIP_EINVAL) return rc;
     }
@@ -290,4 +290,115 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
     for (int s = 0; s < 2; s++)
         if (hipStreamSynchronize(slot[s].st) != hipSuccess && rc == FFHIP_OK) rc = FFHIP_EIO;
     return rc ? rc : result;
+}
+
+/* Files of any baseline geometry, pixels on the device, one call: headers on host threads, the files grouped by layout class (the items
+ * kernels take one class a launch, the device entropy decoder one MCU block record a call), and per class the device entropy decoder
+ * over pictures of different sizes with one ffhip_jpeg_recon_items launch behind each part of its write pass; a class it refuses goes to
+ * host threads.  A class's planes are library scratch of the stream, reused by the next class: every class's work has run when its
+ * turn ends (the entropy call synchronises the stream). */
+extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
+                                                    uint8_t *const *d_bgra, const int64_t *pitch, ffhip_jpeg_geom *geom_out,
+                                                    int *status, void *stream)
+{
+    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 64) n_threads = 64;
+    auto pool_for = [](int count, int nt, auto f) { /* f(i) for i < count over nt host threads */
+        if (nt > count) nt = count;
+        if (nt <= 1) { for (int i = 0; i < count; i++) f(i); return; }
+        std::vector<std::thread> pool;
+        auto part = [&](int t) { for (int i = t; i < count; i += nt) f(i); };
+        for (int t = 1; t < nt; t++) pool.emplace_back(part, t);
+        part(0);
+        for (auto &th : pool) th.join();
+    };
+    /* ---- headers: each file's geometry and class; a file the mixed path cannot take (progressive, 12-bit, a two-pass layout, an output
+     * or pitch ffhip_jpeg_recon_items refuses) has its code now and takes no further part ---- */
+    std::vector<ffhip_jpeg_geom> geoms((size_t)n);
+    std::vector<int> cls((size_t)n, -1);
+    pool_for(n, n_threads, [&](int i) {
+        int w = 0, h = 0;
+        ffhip_jpeg_geom &g = geoms[(size_t)i];
+        memset(&g, 0, sizeof(g));
+        status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
+        if (geom_out) geom_out[i] = g;
+        if (status[i]) return;
+        cls[(size_t)i] = jpeg_item_class(&g, d_bgra[i], pitch[i]);
+        if (cls[(size_t)i] < 0) status[i] = FFHIP_EINVAL;
+    });
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    hipStream_t st = (hipStream_t)stream;
+    const char *ge = FFHIP_ENV("FFHIP_JPEG_GPU_ENTROPY");
+    const char *sy = FFHIP_ENV("FFHIP_JPEG_SYNC"); /* =0: files without restart markers are one lane each on the device, worth it from a thousand files only */
+    int rc = FFHIP_OK;
+    for (int c = 0; c < 7 && rc == FFHIP_OK; c++) {
+        std::vector<int> idx;
+        for (int i = 0; i < n; i++)
+            if (cls[(size_t)i] == c) idx.push_back(i);
+        const int nc = (int)idx.size();
+        if (!nc) continue;
+        std::vector<const uint8_t *> cf((size_t)nc);
+        std::vector<size_t> cl((size_t)nc);
+        std::vector<ffhip_jpeg_geom> cg((size_t)nc);
+        std::vector<ffhip_jpeg_item> items((size_t)nc);
+        std::vector<int> cs((size_t)nc, 0);
+        std::vector<size_t> base((size_t)nc + 1); /* MCUs of the class's pictures before picture k */
+        for (int k = 0; k < nc; k++) {
+            const int i = idx[(size_t)k];
+            cf[(size_t)k] = files[i]; cl[(size_t)k] = lens[i]; cg[(size_t)k] = geoms[(size_t)i];
+            ffhip_jpeg_item &it = items[(size_t)k];
+            memset(&it, 0, sizeof(it));
+            it.geom = geoms[(size_t)i]; it.d_bgra = d_bgra[i]; it.pitch = pitch[i];
+            base[(size_t)k + 1] = base[(size_t)k] + (size_t)it.geom.mcu_cols * it.geom.mcu_rows;
+        }
+        const ffhip_jpeg_geom &g0 = cg[0];
+        const size_t mcus = base[(size_t)nc], yb = mcus * g0.h * g0.v * 64, cb = g0.ncomp == 3 ? mcus * 64 : 0; /* int16 elements of the class */
+        const size_t q_off = ((yb + 2 * cb) * 2 + 15) & ~(size_t)15, bytes = q_off + (size_t)nc * 512;
+        uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_FILES_MIXED, stream, bytes / 4 + 16);
+        if (!dev) { rc = FFHIP_ENOMEM; break; }
+        int16_t *dy = (int16_t *)dev, *du = cb ? dy + yb : nullptr, *dv = cb ? du + cb : nullptr;
+        uint16_t *dq = (uint16_t *)(dev + q_off);
+        bool done = false;
+        if (!(ge && ge[0] == '0') && ((ge && ge[0] == '1') || !(sy && sy[0] == '0') || ffhip_jpeg_probe_restart(cf[0], cl[0]) > 0 || nc >= 1024)) {
+            const FfhipHuffThen then = {nullptr, 0, 0, items.data()};
+            const int grc = jpeg_entropy_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), dy, du, dv, dq, cs.data(), stream, &then);
+            if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
+            done = grc == FFHIP_OK;
+        }
+        if (!done) {
+            /* host threads: each picture at its own offsets of the pinned planes, one upload, the good pictures reconstructed */
+            if (hipStreamSynchronize(st) != hipSuccess) { rc = FFHIP_EIO; break; } /* the scratch may still be read by what `stream` holds */
+            uint8_t *pin = ffhip_pinned_scratch(SCRATCH_FILES_MIXED, stream, bytes);
+            if (!pin) { rc = FFHIP_ENOMEM; break; }
+            int16_t *hy = (int16_t *)pin, *hu = cb ? hy + yb : nullptr, *hv = cb ? hu + cb : nullptr;
+            uint16_t *hq = (uint16_t *)(pin + q_off);
+            pool_for(nc, n_threads, [&](int k) {
+                const ffhip_jpeg_geom &g = cg[(size_t)k];
+                const size_t b = base[(size_t)k];
+                cs[(size_t)k] = ffhip_jpeg_entropy_decode(cf[(size_t)k], cl[(size_t)k], &g, hy + b * g.h * g.v * 64, hu ? hu + b * 64 : nullptr,
+                                                          hv ? hv + b * 64 : nullptr, hq + (size_t)k * 256);
+            });
+            if (hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { rc = FFHIP_EIO; break; }
+            std::vector<ffhip_jpeg_item> good;
+            for (int k = 0; k < nc; k++) {
+                if (cs[(size_t)k]) continue;
+                ffhip_jpeg_item it = items[(size_t)k];
+                const size_t b = base[(size_t)k];
+                it.d_coef_y = dy + b * it.geom.h * it.geom.v * 64;
+                it.d_coef_u = du ? du + b * 64 : nullptr;
+                it.d_coef_v = dv ? dv + b * 64 : nullptr;
+                it.d_quant = dq + (size_t)k * 256;
+                good.push_back(it);
+            }
+            rc = jpeg_recon_items_impl(good.data(), (int)good.size(), stream, 0);
+            if (hipStreamSynchronize(st) != hipSuccess && rc == FFHIP_OK) rc = FFHIP_EIO;
+        }
+        for (int k = 0; k < nc; k++) status[idx[(size_t)k]] = cs[(size_t)k];
+    }
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return FFHIP_OK;
 }

@@ -41,6 +41,7 @@ void release(FfhipStreamState &s)
 {
     for (auto &e : s.scratch) (void)hipFree(e.second.p);
     for (auto &e : s.pinned) (void)hipHostFree(e.second.p);
+    for (auto &e : s.staged) (void)hipEventDestroy(e.second);
     if (s.retry.err) (void)hipHostFree(s.retry.err);
     for (hipEvent_t e : s.tiles.ev)
         if (e) (void)hipEventDestroy(e);
@@ -67,6 +68,26 @@ extern "C" uint8_t *ffhip_pinned_scratch(int kind, void *stream, size_t bytes)
 {
     std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
     return (uint8_t *)grow(ffhip_stream_state(stream)->pinned[kind], bytes, 1, 4096, true, stream);
+}
+
+extern "C" uint8_t *ffhip_pinned_staging(int kind, void *stream, size_t bytes)
+{
+    hipEvent_t ev = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
+        auto &m = ffhip_stream_state(stream)->staged;
+        auto it = m.find(kind);
+        if (it != m.end()) ev = it->second;
+    }
+    if (ev && hipEventSynchronize(ev) != hipSuccess) return nullptr; /* (outside the lock: other streams' calls go on meanwhile) */
+    return ffhip_pinned_scratch(kind, stream, bytes);
+}
+extern "C" int ffhip_pinned_staged(int kind, void *stream)
+{
+    std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
+    hipEvent_t &ev = ffhip_stream_state(stream)->staged[kind];
+    if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { ev = nullptr; return FFHIP_EIO; }
+    return hipEventRecord(ev, (hipStream_t)stream) == hipSuccess ? FFHIP_OK : FFHIP_EIO;
 }
 
 /* Waits for what `s` holds, then frees its entries with the stream: a stream made next with the same handle starts from nothing.  (A handle

@@ -441,3 +441,59 @@ def jpeg_decode_files_device(files, n_threads=8):
     capi.check(L.ffhip_jpeg_decode_files_device(ptrs, lens, n, n_threads, C.byref(g2), dout.ptr, g.width * 4, g.width * 4 * g.height,
                                                 status, None), "ffhip_jpeg_decode_files_device")
     return g2, dout.to_host((n, g.height, g.width, 4), np.uint8), dout
+
+
+def jpeg_recon_items(items, stream=None):
+    """ffhip_jpeg_recon_items: `items` a list of capi.JpegItem (device pointers); pictures of any fused layout and size in
+    one call, one launch per layout class.  Only enqueues on `stream`."""
+    L = capi.lib()
+    n = len(items)
+    arr = (capi.JpegItem * max(n, 1))(*items)
+    capi.check(L.ffhip_jpeg_recon_items(arr, n, stream), "ffhip_jpeg_recon_items")
+
+
+def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True, crop=True):
+    """ffhip_jpeg_decode_files_mixed_device: baseline JPEG files of any geometry (list of bytes) in one call.  Every picture
+    gets its place in ONE device allocation, at a 16-byte-aligned offset with the pitch 4 x its coded width.  Returns
+    (geoms, [host BGRA [h][w][4] cropped to each file's display size (crop=False: the coded size)], device buffer); with
+    strict=False a failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows."""
+    L = capi.require_device()
+    n = len(files)
+    offs, pitches, total = [], [], 0
+    sizes = []
+    for f in files:
+        try:
+            g, w, h = jpeg_probe(f)
+            pitch, rows = g.width * 4, g.height
+        except capi.FfhipError:
+            w = h = pitch = rows = 0
+        offs.append(total)
+        pitches.append(pitch)
+        sizes.append((w, h, rows))
+        total += (pitch * rows + 15) & ~15
+    dout = DeviceBuffer(nbytes=max(total, 16))
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
+    pitch_arr = (C.c_int64 * n)(*pitches)
+    geoms = (capi.JpegGeom * n)()
+    status = (C.c_int * n)()
+    rc = L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n, n_threads, outs, pitch_arr, geoms, status, stream)
+    if strict:
+        capi.check(rc, "ffhip_jpeg_decode_files_mixed_device")
+    elif rc not in (0, capi.FFHIP_EINVAL):
+        capi.check(rc, "ffhip_jpeg_decode_files_mixed_device")
+    flat = dout.to_host((max(total, 16),), np.uint8)
+    images = []
+    for i in range(n):
+        w, h, rows = sizes[i]
+        if status[i] or not pitches[i]:
+            images.append(None)
+            continue
+        pic = flat[offs[i]:offs[i] + pitches[i] * rows].reshape(rows, pitches[i] // 4, 4)
+        images.append(pic[:h, :w].copy() if crop else pic.copy())
+    geoms = list(geoms)
+    if strict:
+        return geoms, images, dout
+    return geoms, images, dout, list(status)

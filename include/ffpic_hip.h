@@ -167,6 +167,24 @@ int ffhip_jpeg_recon_batch(const ffhip_jpeg_geom *geom, int n_images, const int1
                            int64_t pitch, int64_t image_stride, void *d_workspace,
                            size_t workspace_bytes, void *stream);
 size_t ffhip_jpeg_workspace_bytes(const ffhip_jpeg_geom *geom, int n_images);
+/* Mixed batches: pictures that differ in size, planes, quantiser tables, output and pitch, and in layout, in one call.
+ * One launch per layout class present (4:2:0, 4:4:4, 4:2:2, 4:4:0, h4v1, h1v4, grey), each picture reconstructed
+ * by the same fused kernel body as ffhip_jpeg_recon_batch with n = 1 -- byte for byte the same output.  Per item:
+ *   geom          its geometry; the two-pass layouts (grey with h*v > 1, h or v = 3) are refused
+ *   d_coef_*      its MCU-order planes (layout as ffhip_jpeg_recon_batch, n = 1; d_coef_u / _v NULL for grey)
+ *   d_quant       uint16 [4][64] natural order
+ *   d_bgra        its coded-size BGRA picture; pitch >= 4 x coded width, a multiple of 16, pitch x 16 < 2^31
+ * Every device pointer 16-byte aligned.  `items` is a HOST array; every check is made before anything is enqueued
+ * (FFHIP_EINVAL, on a machine without a device too; FFHIP_ENODEV there for good arguments).  Only enqueues on `stream`;
+ * the records and the per-workgroup table are library scratch of the stream. */
+typedef struct ffhip_jpeg_item {
+    ffhip_jpeg_geom geom;
+    const int16_t *d_coef_y, *d_coef_u, *d_coef_v;
+    const uint16_t *d_quant;
+    uint8_t *d_bgra;
+    int64_t pitch;
+} ffhip_jpeg_item;
+int ffhip_jpeg_recon_items(const ffhip_jpeg_item *items, int n, void *stream);
 /* The BGRA layout this library recommends to a caller that owns its output buffer: *pitch = the reference's row pitch
  * (4 bytes x the coded width, format/jpg.c:484-486) + 1024 bytes, *image_stride = pitch x coded height.  The fused kernels
  * write 16 rows of a macroblock row at once, and with rows exactly 15 360 bytes apart (a 3840-pixel row) the rate depends on
@@ -566,6 +584,17 @@ int ffhip_debug_huff_times(double out[8]);
 int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
                                    ffhip_jpeg_geom *geom_out, uint8_t *d_bgra, int64_t pitch, int64_t image_stride,
                                    int *status, void *stream);
+/* Files of ANY baseline geometry in one call, pixels on the device: picture i at d_bgra[i] with pitch[i] (its coded size, as
+ * ffhip_jpeg_probe reports it: the caller probes, then allocates; 16-byte aligned, pitch as for ffhip_jpeg_recon_items).  Headers
+ * are parsed on n_threads host threads, the files grouped by layout class, and per class the device entropy decoder runs over
+ * pictures of different sizes, with one ffhip_jpeg_recon_items launch behind each part of its write pass; a class the device
+ * decoder refuses (or all of them, FFHIP_JPEG_GPU_ENTROPY=0) is decoded by host threads into pinned memory and uploaded.
+ * geom_out[i] (may be NULL) receives each file's geometry, status[i] its code: a damaged, truncated, progressive, 12-bit or
+ * two-pass-layout file gets a non-zero code and no promised output bytes, and every other file is still decoded.  Returns the
+ * first failure.  Synchronises `stream` like ffhip_jpeg_decode_files_device. */
+int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
+                                         uint8_t *const *d_bgra, const int64_t *pitch, ffhip_jpeg_geom *geom_out,
+                                         int *status, void *stream);
 void *ffhip_host_malloc(size_t bytes); /* pinned host memory */
 void ffhip_host_free(void *p);
 int ffhip_jpeg_decode_files(const uint8_t *const *files, const size_t *lens, int n, int n_threads, int chunk,
