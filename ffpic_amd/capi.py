@@ -25,7 +25,7 @@ EXPORTS = [
     "ffhip_heif_grid_parse", "ffhip_heif_grid_compose", "ffhip_hevc_picture_layout", "ffhip_jpeg_decode_files", "ffhip_jpeg_decode_files_device", "ffhip_jpeg_entropy_batch_gpu", "ffhip_jpeg_stage_scan_test", "ffhip_jpeg_stage_scan_raw_test", "ffhip_jpeg_lut_test", "ffhip_host_malloc", "ffhip_host_free",
     "ffhip_shard_range", "ffhip_comm_unique_id", "ffhip_comm_init_rank", "ffhip_comm_destroy", "ffhip_batch_close", "ffhip_batch_complete",
     "ffhip_bgra_checksum", "ffhip_vp8_filter_params", "ffhip_vp8_predict_loopfilter", "ffhip_reload_env", "ffhip_env_value_test", "ffhip_vp8_decode_frames", "ffhip_bgra_layout",
-    "ffhip_jpeg_recon_items", "ffhip_jpeg_decode_files_mixed_device",
+    "ffhip_jpeg_recon_items", "ffhip_jpeg_decode_files_mixed_device", "ffhip_vp8_decode_items",
 ]
 
 
@@ -87,6 +87,14 @@ class JpegItem(C.Structure):
     """ffhip_jpeg_item: one picture of an ffhip_jpeg_recon_items call (device pointers)"""
     _fields_ = [("geom", JpegGeom), ("d_coef_y", C.c_void_p), ("d_coef_u", C.c_void_p), ("d_coef_v", C.c_void_p),
                 ("d_quant", C.c_void_p), ("d_bgra", C.c_void_p), ("pitch", C.c_int64)]
+
+
+class Vp8Item(C.Structure):
+    """ffhip_vp8_item: one key frame of an ffhip_vp8_decode_items call (device pointers; h_modes, quant and filters on the host)"""
+    _fields_ = [("mbcols", C.c_int32), ("mbrows", C.c_int32), ("h_modes", C.c_void_p), ("d_modes", C.c_void_p),
+                ("d_levels", C.c_void_p), ("d_mbinfo", C.c_void_p), ("quant", (C.c_uint16 * 8) * 4), ("d_residual", C.c_void_p),
+                ("d_resmap", C.c_void_p), ("filter_type", C.c_int32), ("filters", C.c_uint8 * 24), ("d_bgra", C.c_void_p),
+                ("pitch", C.c_int64)]
 
 
 def jpeg_geom(mcu_cols, mcu_rows, ncomp=3, h=2, v=2, qt_id=(0, 1, 1)):
@@ -192,6 +200,7 @@ def lib():
     L.ffhip_jpeg_decode_files_device.argtypes = [vp, vp, ci, ci, C.POINTER(JpegGeom), vp, i64, i64, vp, vp]
     L.ffhip_jpeg_decode_files.argtypes = [vp, vp, ci, ci, ci, C.POINTER(JpegGeom), vp, i64, i64, vp]
     L.ffhip_jpeg_recon_items.argtypes = [C.POINTER(JpegItem), ci, vp]
+    L.ffhip_vp8_decode_items.argtypes = [C.POINTER(Vp8Item), ci, vp]
     L.ffhip_jpeg_decode_files_mixed_device.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(JpegGeom), vp, vp]
     L.ffhip_hevc_picture_layout.argtypes = [ci, ci, ci, C.POINTER(HevcLayout)]
     L.ffhip_heif_grid_parse.argtypes = [vp, sz, C.POINTER(HeifGrid)]

@@ -97,7 +97,21 @@ enum FfhipScratchKind {
     SCRATCH_HUFF_SYNC = 30,        /* .. + FFHIP_HUFF_PARTS - 1 */
     SCRATCH_FILES_MIXED = 7,       /* ffhip_jpeg_decode_files_mixed_device: a class's planes and quantiser tables, the host decoder's pinned planes */
     SCRATCH_JPEG_ITEMS = 40,       /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items' records and per-workgroup table, pinned records */
+    SCRATCH_VP8_ITEMS = 50,        /* .. + 2: ffhip_vp8_decode_items' tables (and their pinned copy), the levels items' residual, the line slots */
 };
+
+/* ffhip_vp8_decode_items (ffhip_vp8_frame.hip): its levels items' residual stage (ffhip_vp8.hip) and its device mode check
+ * (ffhip_vp8_pred.hip).  Both tables end in a sentinel whose `first` is the total. */
+struct Vp8ResItem {
+    const int16_t *levels; /* [n_mb][25][16] */
+    const uint8_t *info;   /* [n_mb][32] */
+    int16_t *out;          /* [n_mb][384]: the call's residual scratch at `first` */
+    long long first;       /* its first macroblock among the call's levels items */
+    uint16_t quant[32];    /* [4][8] as Vp8ResArgs::quant */
+};
+struct Vp8CheckItem { const uint8_t *modes; long long first; /* its first record among the items checked on the device */ };
+int vp8_residual_items_enqueue(const Vp8ResItem *d_items, int n, long long n_mb, uint32_t *d_wg_item, void *stream);
+int vp8_check_modes_items_enqueue(const Vp8CheckItem *d_items, int n, long long n_records, uint32_t *ctrl, int *async_err, void *stream);
 
 /* ffhip_vp8_decode_frames (row form) -> ffhip_vp8_predict_loopfilter: the colour conversion the caller enqueues behind the call belongs to
  * it -- a retry has to run it again, behind the filter */

@@ -107,87 +107,55 @@ __global__ __launch_bounds__(256) void k_vp8_residual(Vp8ResArgs a)
     const int t = threadIdx.x & 31, slot = threadIdx.x >> 5;
     const long long mb = (long long)blockIdx.x * 8 + slot;
     if (mb >= a.n_mb) return; /* whole 32-lane slots: the lane pairs below are never split */
-    const bool even = (t & 1) == 0;
-    const int blk = even ? t >> 1 : 16 + (t >> 1); /* the block this lane computes; >= 25: none (odd lanes 19..31) */
-    const bool works = blk < 25;
-    const int kb = works ? blk : 0;
-    /* the macroblock's 32 info bytes as two aligned dwords per lane (the one holding nz[blk], and bytes 24-27: nz of the
-     * Y2 block, has_y2, segment) and the quantiser pair as one dword */
-    const u32 *info = (const u32 *)(a.info + mb * 32);
-    const u32 iw = info[kb >> 2], ic = info[6];
-    const int nz = (int)((iw >> (8 * (kb & 3))) & 0xffu), nz24 = (int)(ic & 0xffu), has_y2 = ((ic >> 8) & 0xffu) != 0, seg = (int)((ic >> 16) & 3u);
-    const int qsel = kb < 16 ? 0 : (kb < 24 ? 4 : 2);
-    const u32 qpair = *(const u32 *)(a.quant + seg * 8 + qsel); /* (dc, ac) of this lane's block kind */
-    const u32 qdc = qpair & 0xffffu, qac = qpair >> 16;
-    const u32x4 *src = (const u32x4 *)(a.levels + mb * 400);
-    const u32x4 c1 = __builtin_nontemporal_load(src + t);
-    u32x4 c2 = {0u, 0u, 0u, 0u};
-    if (t < 18) c2 = __builtin_nontemporal_load(src + 32 + t);
-    if (PATTERN) { /* (info and quantiser words are loaded as ever: iw, ic, qpair feed the stored words so that nothing is dropped) */
-        u32x4 *dstp = (u32x4 *)(a.out + mb * 384);
-        const u32 k = iw ^ ic ^ qpair;
-        __builtin_nontemporal_store(c1 + k, dstp + t);
-        if (t < 16) __builtin_nontemporal_store(c2 + k, dstp + 32 + t);
-        return;
+#include "ffhip_vp8_residual_body.inc"
+}
+
+/* ffhip_vp8_decode_items: the macroblocks of all its levels items end to end, each 32-lane slot with its own item's buffers and
+ * quantisers.  The body is k_vp8_residual's as included text (a forceinline function changed the JPEG kernels' register allocation).
+ * A workgroup reads the item of its first macroblock from the per-workgroup table; a slot's item is that one or a later one (items
+ * of fewer than eight macroblocks end inside a workgroup), found by walking the items' prefix. */
+__global__ __launch_bounds__(256) void k_vp8_residual_items(const Vp8ResItem *items, const u32 *wg_item, long long n_mb_all)
+{
+    constexpr bool PATTERN = false;
+    __shared__ __attribute__((aligned(16))) short y2in[8][16];
+    __shared__ __attribute__((aligned(16))) int y2t[8][16];
+    const int t = threadIdx.x & 31, slot = threadIdx.x >> 5;
+    const long long gmb = (long long)blockIdx.x * 8 + slot;
+    if (gmb >= n_mb_all) return;
+    typedef __attribute__((address_space(4))) const Vp8ResItem cres;
+    typedef __attribute__((address_space(4))) const u32 cu32;
+    const int it0 = (int)((cu32 *)wg_item)[blockIdx.x];
+    if ((long long)blockIdx.x * 8 + 7 < ((cres *)items)[it0 + 1].first) {
+        /* the whole workgroup in one item (every workgroup but those at an item's end): its record by scalar loads -- a chain of
+         * vector loads in front of the levels made this short-lived kernel 7 % slower than k_vp8_residual */
+        cres *const d = (cres *)items + it0;
+        const Vp8ResArgs a = {d->levels, d->info, items[it0].quant, d->out, 0};
+        const long long mb = gmb - d->first;
+#include "ffhip_vp8_residual_body.inc"
+    } else {
+        int it = it0;
+        while (gmb >= items[it + 1].first) it++; /* (the sentinel behind the last item holds the total) */
+        const Vp8ResItem &d = items[it];
+        const Vp8ResArgs a = {d.levels, d.info, d.quant, d.out, 0};
+        const long long mb = gmb - d.first;
+#include "ffhip_vp8_residual_body.inc"
     }
-    /* block assembly inside the lane pair */
-    const unsigned long long even_lanes = 0x5555555555555555ull;
-    const u32x4 l0 = pair_pick<false>(c2, c1, even_lanes);  /* even: my first chunk; odd: my even neighbour's second load */
-    const u32x4 l1 = pair_pick<true>(c1, c2, ~even_lanes);  /* even: my odd neighbour's first chunk; odd: my second load */
-    const u32 lv[8] = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-    u32 pk[8]; /* pk[2r + h] = (c[4r + 2h], c[4r + 2h + 1]) */
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        /* low 16 bits of level*q == the int16 store of webp.c:1061 */
-        const u32 f = i == 0 ? (qdc | (qac << 16)) : (qac | (qac << 16));
-        using u16x2 = unsigned short __attribute__((ext_vector_type(2)));
-        const u32 lvi = lv[i];
-        pk[i] = __builtin_bit_cast(u32, (u16x2)(__builtin_bit_cast(u16x2, lvi) * __builtin_bit_cast(u16x2, f)));
-    }
-    /* Y2 -> luma DCs, ACROSS the sixteen luma lanes of the macroblock (webp.c:1067-1106).  Done by the Y2 lane
-     * alone the inverse WHT is ~100 instructions that the whole wave pays for one or two working lanes (a third
-     * of this VALU-bound kernel).  Instead the Y2 lane parks its 16 dequantised coefficients in LDS and the lane of luma
-     * block 4r + i computes t[4r + i] of the column pass from column i, parks that, and computes w[4r + i] of the
-     * row pass from row r: each is one of four +- combinations picked by r (then i), and w[blk] is exactly the DC
-     * that block needs.  Writers and readers never sit on two sides of one branch (divergent sides have no defined
-     * order): stores are predicated blocks followed by a wave-level fence; LDS serves a wave in program order. */
-    if (blk == 24 && has_y2) {
-        *(u32x4 *)&y2in[slot][0] = u32x4{pk[0], pk[1], pk[2], pk[3]};
-        *(u32x4 *)&y2in[slot][8] = u32x4{pk[4], pk[5], pk[6], pk[7]};
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool luma = even; /* blk < 16 */
-    const int r4 = (blk >> 2) & 3, i4 = blk & 3;
-    int tv = 0;
-    if (luma && has_y2) {
-        const int v0 = y2in[slot][i4], v1 = y2in[slot][4 + i4], v2 = y2in[slot][8 + i4], v3 = y2in[slot][12 + i4];
-        const int a4 = v0 + v3, b4 = v1 + v2, e4 = v1 - v2, f4 = v0 - v3;
-        const int p4 = (r4 & 1) ? f4 : a4, q4 = (r4 & 1) ? e4 : b4;
-        tv = (r4 & 2) ? p4 - q4 : p4 + q4; /* rows: a+b, f+e, a-b, f-e */
-        y2t[slot][blk] = tv;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (luma && has_y2) {
-        const u32x4 row = *(const u32x4 *)&y2t[slot][4 * r4];
-        const int t0 = (int)row[0], t1 = (int)row[1], t2 = (int)row[2], t3 = (int)row[3];
-        const int a4 = t0 + t3, b4 = t1 + t2, e4 = t1 - t2, f4 = t0 - t3;
-        const int p4 = (i4 & 1) ? f4 : a4, q4 = (i4 & 1) ? e4 : b4;
-        const int full = (short)((((i4 & 2) ? p4 - q4 : p4 + q4) + 3) >> 3);
-        const int fast = (short)((y2in[slot][0] + 3) >> 3); /* IWHT_fast, webp.c:1098-1106 */
-        pk[0] = __builtin_amdgcn_perm(pk[0], (u32)(nz24 > 1 ? full : fast), 0x07060100u);
-    }
-    if (works && blk != 24 && (nz > 1 || (pk[0] & 0xffffu) != 0)) vp8_idct4x4(pk);
-    /* back to chunks: chunk t = even ? my lower half : my even neighbour's upper half; chunk 32 + t (t < 16) = even ? my odd
-     * neighbour's lower half : my upper half */
-    const u32x4 o0 = {pk[0], pk[1], pk[2], pk[3]}, o1 = {pk[4], pk[5], pk[6], pk[7]};
-    const u32x4 s1 = pair_pick<false>(o1, o0, even_lanes), s2 = pair_pick<true>(o0, o1, ~even_lanes);
-    u32x4 *dst = (u32x4 *)(a.out + mb * 384);
-    __builtin_nontemporal_store(s1, dst + t);
-    if (t < 16) __builtin_nontemporal_store(s2, dst + 32 + t);
+}
+
+/* one workgroup per item: its index over the workgroups whose first macroblock is its own (as k_jpeg_items_table) */
+__global__ __launch_bounds__(256) void k_vp8_residual_items_table(const Vp8ResItem *items, u32 *wg_item)
+{
+    const long long b0 = (items[blockIdx.x].first + 7) / 8, b1 = (items[blockIdx.x + 1].first + 7) / 8;
+    for (long long b = b0 + threadIdx.x; b < b1; b += 256) wg_item[b] = blockIdx.x;
+}
+
+int vp8_residual_items_enqueue(const Vp8ResItem *d_items, int n, long long n_mb, uint32_t *d_wg_item, void *stream)
+{
+    hipLaunchKernelGGL(k_vp8_residual_items_table, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, d_items, d_wg_item);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    hipLaunchKernelGGL(k_vp8_residual_items, dim3((unsigned)((n_mb + 7) / 8)), dim3(256), 0, (hipStream_t)stream, d_items, d_wg_item, n_mb);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
 }
 
 extern "C" int ffhip_vp8_residual_batch(long long n_mb, const int16_t *d_levels, const uint8_t *d_mbinfo,

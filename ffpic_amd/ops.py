@@ -452,6 +452,15 @@ def jpeg_recon_items(items, stream=None):
     capi.check(L.ffhip_jpeg_recon_items(arr, n, stream), "ffhip_jpeg_recon_items")
 
 
+def vp8_decode_items(items, stream=None):
+    """ffhip_vp8_decode_items: `items` a list of capi.Vp8Item; key frames of any size, quantisers and loop filter in one call
+    (one launch per filter type and residual-map form).  Only enqueues on `stream`."""
+    L = capi.lib()
+    n = len(items)
+    arr = (capi.Vp8Item * max(n, 1))(*items)
+    capi.check(L.ffhip_vp8_decode_items(arr, n, stream), "ffhip_vp8_decode_items")
+
+
 def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True, crop=True):
     """ffhip_jpeg_decode_files_mixed_device: baseline JPEG files of any geometry (list of bytes) in one call.  Every picture
     gets its place in ONE device allocation, at a 16-byte-aligned offset with the pitch 4 x its coded width.  Returns

@@ -407,6 +407,42 @@ int ffhip_vp8_decode_frames(int mbcols, int mbrows, int n_images, const uint8_t 
                             const int16_t *d_residual, int64_t residual_stride, const int32_t *d_resmap, int filter_type,
                             const uint8_t *d_filters, uint8_t *d_bgra, int pitch, int64_t image_stride, uint8_t *d_y,
                             uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream);
+/* Mixed batches: key frames that differ in size, quantisers, loop filter, output and pitch, in one call.  Each item gets the
+ * BGRA bytes of ffhip_vp8_residual_batch (levels form only) followed by ffhip_vp8_decode_frames(n_images = 1) on that item
+ * alone.  Per item:
+ *   mbcols, mbrows   its size in macroblocks (fewer than 2^23 of them)
+ *   h_modes          host copy of its [n_mb][20] mode records (checked here), or NULL: checked by ONE kernel in front of the
+ *                    decode for all such items; a bad record then gives FFHIP_EINVAL from the next ffhip_stream_sync and no
+ *                    item's output is written
+ *   d_modes          device [n_mb][20], format as ffhip_vp8_predict_recon, 4-byte aligned
+ *   the residual     EITHER d_levels (16-byte aligned) + d_mbinfo (4-byte aligned) + quant (HOST values, as d_quant of
+ *                    ffhip_vp8_residual_batch): the call runs the residual stage with this item's quantisers into library
+ *                    scratch (768 B per macroblock) -- OR d_residual ([rows][384], 4-byte aligned; d_levels NULL)
+ *   d_resmap         [n_mb] residual row of each macroblock (below n_mb), or NULL for the identity; as ffhip_vp8_predict_recon
+ *   filter_type      0 none, 1 simple, 2 normal; filters: HOST values, as ffhip_vp8_filter_params leaves them
+ *   d_bgra, pitch    16*mbrows rows of 16*mbcols pixels, `pitch` bytes apart: 16-byte aligned, pitch >= 64*mbcols, a
+ *                    multiple of 16, pitch*16*mbrows < 2^31.  Only those pixels are written, not the pitch's padding
+ * `items` is a HOST array; fewer than 2^30 macroblocks in all.  Every check is made before anything is enqueued (FFHIP_EINVAL,
+ * on a machine without a device too; FFHIP_ENODEV there for good arguments).  Only enqueues on `stream`.  Always the one-kernel
+ * frame form of ffhip_vp8_decode_frames (one launch per filter type and residual-map form present, frames dealt to workgroups
+ * largest first): there is no row form and no FFHIP_RETRIED, so one or two frames decode with the frame kernel's latency, not
+ * the row kernels'.  BGRA only (no planes).  Residual scratch, descriptor tables and line slots are library scratch of the
+ * stream. */
+typedef struct ffhip_vp8_item {
+    int mbcols, mbrows;
+    const uint8_t *h_modes;
+    const uint8_t *d_modes;
+    const int16_t *d_levels;
+    const uint8_t *d_mbinfo;
+    uint16_t quant[4][8];
+    const int16_t *d_residual;
+    const int32_t *d_resmap;
+    int filter_type;
+    uint8_t filters[4][2][3];
+    uint8_t *d_bgra;
+    int64_t pitch;
+} ffhip_vp8_item;
+int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *stream);
 
 /* ---- HEVC intra prediction + reconstruction for a list of transform units ----
  * decode_intra_block steps 5-10 (coding/hevc.c:4730-4790) for every TU of a picture:
