@@ -1598,21 +1598,96 @@ extern "C" int ffhip_debug_hevc_plan_result(uint32_t out[8])
     return FFHIP_OK;
 }
 
-extern "C" size_t ffhip_hevc_plan_gpu_words(long long n_tus, const int pw[3], const int ph[3], const int wl[3]);
-extern "C" int ffhip_hevc_plan_gpu(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3],
-                                   uint32_t *scratch, hipStream_t st, const u32x4 **sched, const u32x4 **groups, const uint32_t **wait_idx,
-                                   int *n_groups, const uint32_t **d_result, uint32_t *wait_cap_out);
-
-extern "C" int ffhip_hevc_plan_gpu_checked(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3],
-                                           uint32_t *scratch, hipStream_t st, const u32x4 **sched, const u32x4 **groups, const uint32_t **wait_idx,
-                                           int *n_groups, const uint32_t **d_result, uint32_t *wait_cap_out, const int *check, int *async_err,
-                                           const FfhipPlanHooks *hooks, uint32_t *also_zero, size_t also_zero_words);
+/* log2 of the chroma planes' subsampling against luma, horizontally (4:2:0 / 4:2:2: 1) */
+static int chroma_shift(const int pw[3]) { return (pw[1] > 0 && pw[1] * 2 <= pw[0] + 1) ? 1 : 0; }
 
 struct GroupPlan {
     std::vector<u32x4> sched;  /* 3 per slot */
     std::vector<u32x4> groups;
     std::vector<uint32_t> wait;
 };
+
+struct PlanMeta { uint32_t group, wait_begin, slot; uint8_t wait_count, signal, tile_ok; }; /* plan_groups: per TU */
+/* fn(0 .. n_threads - 1), each on a thread of its own but the first */
+template <class F>
+static void on_threads(int n_threads, F &fn)
+{
+    if (n_threads == 1) { fn(0); return; }
+    std::vector<std::thread> pool;
+    for (int th = 1; th < n_threads; th++) pool.emplace_back(fn, th);
+    fn(0);
+    for (auto &th : pool) th.join();
+}
+/* plan_groups' pass 3: the threads' wait lists (TU ranges in order) as one, wait_begin made absolute, and the dependency depth of every group */
+static void merge_waits(long long n_tus, const std::vector<std::vector<uint32_t>> &waits, PlanMeta *meta, size_t n_groups, std::vector<uint32_t> &gdepth,
+                        GroupPlan &out)
+{
+    const int n_threads = (int)waits.size();
+    size_t total_wait = 0;
+    for (auto &w : waits) total_wait += w.size();
+    out.wait.resize(std::max<size_t>(total_wait, 1));
+    out.wait[0] = 0;
+    gdepth.assign(n_groups, 0);
+    size_t base = 0;
+    for (int th = 0; th < n_threads; th++) {
+        const long long lo = n_tus * th / n_threads, hi = n_tus * (th + 1) / n_threads;
+        const std::vector<uint32_t> &w = waits[(size_t)th];
+        if (!w.empty()) memcpy(out.wait.data() + base, w.data(), w.size() * sizeof(uint32_t));
+        for (long long i = lo; i < hi; i++) {
+            PlanMeta &m = meta[(size_t)i];
+            uint32_t depth = gdepth[m.group];
+            for (unsigned q = 0; q < m.wait_count; q++) depth = std::max(depth, gdepth[meta[w[m.wait_begin + q]].group] + 1);
+            gdepth[m.group] = depth;
+            m.wait_begin += (uint32_t)base;
+        }
+        base += w.size();
+    }
+}
+/* plan_groups' last step: the tickets' order (by_depth: dependency depth, ties in decode order; else decode order), the group records, the slots */
+static void order_and_emit(const ffhip_hevc_tu *tus, long long n_tus, const int win_log2[3], const int bw[3], const uint32_t jt_boff[3], const bool by_depth,
+                           const PlanMeta *mp, const std::vector<uint32_t> &gcount, const std::vector<uint32_t> &gfirst, const std::vector<uint32_t> &gdepth,
+                           int n_threads, GroupPlan &out)
+{
+    static thread_local std::vector<uint32_t> order, gbase;
+    /* Tickets go out in dependency-depth order (ties: decode order), so the waves that hold tickets
+     * are the ones near the ready front rather than thousands of groups ahead of it, polling.
+     * Every group a group waits for has a smaller depth, hence a smaller ticket.  (Depths are only
+     * trusted for contiguous groups; otherwise decode order, which pass 2 checked is valid.) */
+    const size_t ng = gcount.size();
+    order.resize(ng);
+    for (size_t g = 0; g < ng; g++) order[g] = (uint32_t)g;
+    if (by_depth) std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return gdepth[x] < gdepth[y]; });
+    gbase.resize(ng);
+    out.groups.resize(ng);
+    uint32_t run = 0;
+    for (size_t k = 0; k < ng; k++) {
+        const uint32_t g = order[k];
+        gbase[g] = run;
+        u32x4 rec;
+        rec.x = run;
+        rec.y = gcount[g];
+        rec.z = (uint32_t)win_log2[tus[gfirst[g]].cidx];
+        rec.w = 0;
+        out.groups[k] = rec;
+        run += gcount[g];
+    }
+    out.sched.resize((size_t)n_tus * 3);
+    static_assert(sizeof(ffhip_hevc_tu) == 32, "slot layout");
+    const uint32_t *const gbasep = gbase.data();
+    auto emit = [&](int th) {
+        const long long lo = n_tus * th / n_threads, hi = n_tus * (th + 1) / n_threads;
+        for (long long i = lo; i < hi; i++) {
+            const PlanMeta &m = mp[(size_t)i];
+            u32x4 *q = &out.sched[(size_t)(gbasep[m.group] + m.slot) * 3];
+            memcpy(q, &tus[i], 32);
+            q[2].x = m.wait_begin;
+            q[2].y = (uint32_t)m.wait_count | ((uint32_t)m.signal << 8) | ((uint32_t)m.tile_ok << 9);
+            q[2].z = (uint32_t)i;
+            q[2].w = (jt_boff[tus[i].cidx] + (uint32_t)(tus[i].y >> 2) * (uint32_t)bw[tus[i].cidx] + (uint32_t)(tus[i].x >> 2)) * JT_STRIDE;
+        }
+    };
+    on_threads(n_threads, emit);
+}
 
 /* Cut the (validated) list into window-tile groups in order of first appearance and collect, per
  * TU, the TUs of OTHER groups it reads, whether some other group reads it, and whether all its
@@ -1625,9 +1700,8 @@ static bool plan_groups(const ffhip_hevc_tu *tus, long long n_tus, const int pw[
 {
     /* scratch kept between calls: a picture's worth of maps is reallocated and refilled otherwise */
     static thread_local std::vector<int32_t> owner[3], gid_of[3];
-    struct Meta { uint32_t group, wait_begin, slot; uint8_t wait_count, signal, tile_ok; };
-    static thread_local std::vector<Meta> meta;
-    static thread_local std::vector<uint32_t> gcount, gdepth, gfirst, order, gbase;
+    static thread_local std::vector<PlanMeta> meta;
+    static thread_local std::vector<uint32_t> gcount, gdepth, gfirst;
     int bw[3], gw[3];
     for (int c = 0; c < 3; c++) {
         bw[c] = (pw[c] + 3) / 4;
@@ -1656,7 +1730,7 @@ static bool plan_groups(const ffhip_hevc_tu *tus, long long n_tus, const int pw[
             contiguous = false;
         }
         cur_group = (uint32_t)gslot;
-        Meta &m = meta[(size_t)i];
+        PlanMeta &m = meta[(size_t)i];
         m.group = cur_group; m.signal = 0; m.tile_ok = 1;
         m.slot = gcount[cur_group]++;
         int32_t *orow = owner[c].data() + (size_t)(t.y >> 2) * bw[c] + (t.x >> 2);
@@ -1668,7 +1742,7 @@ static bool plan_groups(const ffhip_hevc_tu *tus, long long n_tus, const int pw[
      * depends on TUs before it in the list (a block whose owner comes later held older content when
      * the sequential decoder looked at it) ---- */
     /* the scratch vectors are thread_local: worker threads must go through pointers taken here */
-    Meta *const mp = meta.data();
+    PlanMeta *const mp = meta.data();
     const int32_t *const ownp[3] = {owner[0].data(), owner[1].data(), owner[2].data()};
     const char *pt = FFHIP_ENV("FFHIP_PLAN_THREADS");
     /* one thread unless asked: on the 16-core share of an MI355X box 2-8 threads were no faster
@@ -1683,7 +1757,7 @@ static bool plan_groups(const ffhip_hevc_tu *tus, long long n_tus, const int pw[
         for (long long i = lo; i < hi; i++) {
             const ffhip_hevc_tu &t = tus[i];
             const int c = t.cidx, n = 1 << t.log2_size, wl = win_log2[c];
-            Meta &m = mp[(size_t)i];
+            PlanMeta &m = mp[(size_t)i];
             const uint32_t g = m.group;
             int32_t deps[72];
             int nd = 0;
@@ -1711,90 +1785,20 @@ static bool plan_groups(const ffhip_hevc_tu *tus, long long n_tus, const int pw[
             m.wait_count = (uint8_t)nd;
             m.wait_begin = (uint32_t)w.size(); /* relative to this thread's list until pass 3 */
             for (int q = 0; q < nd; q++) {
-                Meta &mj = mp[(size_t)deps[q]];
+                PlanMeta &mj = mp[(size_t)deps[q]];
                 if (mj.group > g) { bad = true; return; }
                 __atomic_store_n(&mj.signal, (uint8_t)1, __ATOMIC_RELAXED);
                 w.push_back((uint32_t)deps[q]);
             }
         }
     };
-    if (n_threads == 1) scan(0);
-    else {
-        std::vector<std::thread> pool;
-        for (int th = 1; th < n_threads; th++) pool.emplace_back(scan, th);
-        scan(0);
-        for (auto &th : pool) th.join();
-    }
+    on_threads(n_threads, scan);
     if (bad) return false;
     const auto T2 = std::chrono::steady_clock::now();
     /* ---- pass 3 (sequential, light): one wait list, dependency depth per group ---- */
-    size_t total_wait = 0;
-    for (auto &w : waits) total_wait += w.size();
-    out.wait.resize(std::max<size_t>(total_wait, 1));
-    out.wait[0] = 0;
-    gdepth.assign(gcount.size(), 0);
-    {
-        size_t base = 0;
-        for (int th = 0; th < n_threads; th++) {
-            const long long lo = n_tus * th / n_threads, hi = n_tus * (th + 1) / n_threads;
-            const std::vector<uint32_t> &w = waits[(size_t)th];
-            if (!w.empty()) memcpy(out.wait.data() + base, w.data(), w.size() * sizeof(uint32_t));
-            for (long long i = lo; i < hi; i++) {
-                Meta &m = meta[(size_t)i];
-                uint32_t depth = gdepth[m.group];
-                for (unsigned q = 0; q < m.wait_count; q++) depth = std::max(depth, gdepth[meta[w[m.wait_begin + q]].group] + 1);
-                gdepth[m.group] = depth;
-                m.wait_begin += (uint32_t)base;
-            }
-            base += w.size();
-        }
-    }
+    merge_waits(n_tus, waits, mp, gcount.size(), gdepth, out);
     const auto T3 = std::chrono::steady_clock::now();
-    /* Tickets go out in dependency-depth order (ties: decode order), so the waves that hold tickets
-     * are the ones near the ready front rather than thousands of groups ahead of it, polling.
-     * Every group a group waits for has a smaller depth, hence a smaller ticket.  (Depths are only
-     * trusted for contiguous groups; otherwise decode order, which pass 2 checked is valid.) */
-    const size_t ng = gcount.size();
-    order.resize(ng);
-    for (size_t g = 0; g < ng; g++) order[g] = (uint32_t)g;
-    if (contiguous && !FFHIP_ENV("FFHIP_HEVC_INTRA_DECODE_ORDER"))
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return gdepth[x] < gdepth[y]; });
-    gbase.resize(ng);
-    out.groups.resize(ng);
-    uint32_t run = 0;
-    for (size_t k = 0; k < ng; k++) {
-        const uint32_t g = order[k];
-        gbase[g] = run;
-        u32x4 rec;
-        rec.x = run;
-        rec.y = gcount[g];
-        rec.z = (uint32_t)win_log2[tus[gfirst[g]].cidx];
-        rec.w = 0;
-        out.groups[k] = rec;
-        run += gcount[g];
-    }
-    out.sched.resize((size_t)n_tus * 3);
-    static_assert(sizeof(ffhip_hevc_tu) == 32, "slot layout");
-    const uint32_t *const gbasep = gbase.data();
-    auto emit = [&](int th) {
-        const long long lo = n_tus * th / n_threads, hi = n_tus * (th + 1) / n_threads;
-        for (long long i = lo; i < hi; i++) {
-            const Meta &m = mp[(size_t)i];
-            u32x4 *q = &out.sched[(size_t)(gbasep[m.group] + m.slot) * 3];
-            memcpy(q, &tus[i], 32);
-            q[2].x = m.wait_begin;
-            q[2].y = (uint32_t)m.wait_count | ((uint32_t)m.signal << 8) | ((uint32_t)m.tile_ok << 9);
-            q[2].z = (uint32_t)i;
-            q[2].w = (jt_boff[tus[i].cidx] + (uint32_t)(tus[i].y >> 2) * (uint32_t)bw[tus[i].cidx] + (uint32_t)(tus[i].x >> 2)) * JT_STRIDE;
-        }
-    };
-    if (n_threads == 1) emit(0);
-    else {
-        std::vector<std::thread> pool;
-        for (int th = 1; th < n_threads; th++) pool.emplace_back(emit, th);
-        emit(0);
-        for (auto &th : pool) th.join();
-    }
+    order_and_emit(tus, n_tus, win_log2, bw, jt_boff, contiguous && !FFHIP_ENV("FFHIP_HEVC_INTRA_DECODE_ORDER"), mp, gcount, gfirst, gdepth, n_threads, out);
     if (FFHIP_ENV("FFHIP_PLAN_TIMES")) {
         const auto T4 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
@@ -1912,7 +1916,7 @@ static int pick_window(const ffhip_hevc_tu *tus, long long n_tus, const int pw[3
 {
     const char *bp = FFHIP_ENV("FFHIP_HEVC_BY_PLANE");
     const int force = bp ? atoi(bp) : -1;
-    const int cs = (pw[1] > 0 && pw[1] * 2 <= pw[0] + 1) ? 1 : 0;
+    const int cs = chroma_shift(pw);
     wl = wl < 3 ? 3 : (wl > 6 ? 6 : wl);
     for (; wl >= 3; wl--) {
         const int win[3] = {wl, wl - cs, wl - cs};
@@ -1932,7 +1936,7 @@ static bool plan_with_window_search(const ffhip_hevc_tu *tus, long long n_tus, c
                                     GroupPlan &plan, int *used_wl, const uint32_t jt_boff[3])
 {
     wl = wl < 3 ? 3 : (wl > 6 ? 6 : wl);
-    const int cs = (pw[1] > 0 && pw[1] * 2 <= pw[0] + 1) ? 1 : 0;
+    const int cs = chroma_shift(pw);
     for (; wl >= 3; wl--) {
         const int win[3] = {wl, wl - cs, wl - cs};
         if (plan_groups(tus, n_tus, pw, ph, win, plan, jt_boff)) {
@@ -1976,48 +1980,78 @@ extern "C" int ffhip_hevc_intra_plan(const ffhip_hevc_tu *h_tus, long long n_tus
     return FFHIP_OK;
 }
 
-/* ffhip_hevc_intra_recon_tiles runs a call's chunks as a pipeline: a chunk's pre-pass (validation, planner, substitution table, programs) on
- * `plan` -- a stream of the library's own, one pre-pass behind the other -- and its grouped kernel on `groups` (the caller's stream and a second
- * library stream in turn), behind `plan_done`.  Scratch of its own per chunk (`scratch_kind`); the substitution table and the per-pixel words,
- * which are indexed by position in the planes, are shared (`jt_desc`: the chunks cover different areas). */
-struct IntraRoles {
-    hipStream_t plan, groups;
-    hipEvent_t plan_done;
+/* One call of ffhip_hevc_intra_recon -- or the early pre-pass of ffhip_hevc_intra_recon_tiles --: what its validation and its three paths
+ * share.  `st` takes everything in front of the grouped kernel: the caller's stream, or a stream of the library's own, behind which the
+ * caller's (`gst`) waits through `plan_done`. */
+struct IntraCall {
+    const ffhip_hevc_tu *h_tus, *d_tus;
+    long long n_tus;
+    const int16_t *d_residual;
+    int pw[3], ph[3];
+    int pwc[3];                /* the planes in use: the chroma widths are 0 without both chroma planes */
+    bool chroma;               /* both chroma planes given */
+    bool chroma_ok;            /* ... and uv_stride >= width_c */
+    bool big_list;             /* the host validates a sample, the device every record (k_hevc_check_tus) */
+    bool fully_validated, has_res;
+    HevcIntraArgs a;
+    JTabArgs ja;
+    ProgArgs pa;
+    size_t jt_blocks, desc_px, w_jt, w_desc; /* the substitution table and the per-pixel program words: entries, 32-bit words */
+    const ffhip_hevc_tu *list; /* the records the schedule's TU indices refer to: the caller's, or a copy sorted by plane (pick_window) */
+    void *stream;              /* the caller's: owns the scratch */
+    hipStream_t st, gst;
+    hipEvent_t plan_done;      /* NULL: st is the caller's stream */
     int scratch_kind;
-    uint32_t *jt_desc;
-    bool big_call; /* the call this chunk is cut from is a large list (2^17 records and more): the host samples, the device validates, as for the whole list */
+    int *async_err;            /* the grouped form's: NULL for the levels form */
+    std::chrono::steady_clock::time_point th[3]; /* FFHIP_PLAN_TIMES: validation, window choice, enqueue */
 };
-static int intra_recon_impl(const ffhip_hevc_tu *h_tus, const ffhip_hevc_tu *d_tus, long long n_tus,
-                            const int16_t *d_residual, int16_t *d_y, int16_t *d_cb, int16_t *d_cr,
-                            int width_y, int height_y, int y_stride, int width_c, int height_c,
-                            int uv_stride, int bitdepth_y, int bitdepth_c, void *stream, const IntraRoles *roles)
+
+/* The substitution table (JT_STRIDE bytes per 4x4 block) and the per-pixel program words (8 bytes per sample) of the planes in use, as the
+ * kernels index them */
+static void lay_out_tables(IntraCall &c)
 {
-    if (n_tus < 0 || n_tus > 0x7fffffffLL) return FFHIP_EINVAL;
-    if (n_tus == 0) return FFHIP_OK;
-    if (!h_tus || !d_tus || !d_y || width_y <= 0 || height_y <= 0 || y_stride < width_y) return FFHIP_EINVAL;
-    if (bitdepth_y < 8 || bitdepth_y > 15 || bitdepth_c < 8 || bitdepth_c > 15) return FFHIP_EINVAL;
-    if (!ffhip_have_device()) return FFHIP_ENODEV;
-    const int pw[3] = {width_y, width_c, width_c}, ph[3] = {height_y, height_c, height_c};
-    /* validation: field ranges, the block inside its plane, and no availability bit pointing outside the plane */
-    /* lists of 2^17 TUs and more: the host looks at a sample (a bad record there is refused here, at once), every record is checked by a
-     * kernel in front of the planner (k_hevc_check_tus), which refuses the call through the stream -- or by a full host pass below, should the
-     * call not take the device planner */
-    const bool big_list = (n_tus >= (1LL << 17) || (roles && roles->big_call)) && !FFHIP_ENV("FFHIP_HEVC_HOST_CHECK");
+    for (int k = 0; k < 3; k++) {
+        c.ja.bw[k] = (c.pwc[k] + 3) / 4;
+        c.ja.boff[k] = (uint32_t)c.jt_blocks;
+        if (c.pwc[k] > 0) c.jt_blocks += (size_t)c.ja.bw[k] * (size_t)((c.ph[k] + 3) / 4);
+        c.a.jt_bw[k] = c.ja.bw[k];
+        c.a.jt_boff[k] = c.ja.boff[k];
+        c.pa.desc_w[k] = c.pwc[k];
+        c.pa.desc_off[k] = (uint32_t)c.desc_px;
+        if (c.pwc[k] > 0) c.desc_px += (size_t)c.pwc[k] * (size_t)c.ph[k];
+        c.a.desc_w[k] = c.pa.desc_w[k];
+        c.a.desc_off[k] = c.pa.desc_off[k];
+    }
+    c.w_jt = (c.jt_blocks * JT_STRIDE + 256 + 3) / 4; /* padded: the kernel fetches 64 / 192 entries per TU whatever its size */
+    c.w_desc = c.desc_px * 2 + 2;
+}
+/* the grouped kernel's control block: CTRL_HDR words, then one done flag per TU; the ticket counters and the abort word start 128-byte lines */
+static void set_ctrl(HevcIntraArgs &a, uint32_t *ctrl)
+{
+    a.ctrl = ctrl;
+    a.ctrl_ticket = (uint32_t)((32 - (((uintptr_t)ctrl >> 2) & 31)) & 31);
+    a.ctrl_abort = a.ctrl_ticket + 32 * 9;
+}
+
+/* validation: field ranges, the block inside its plane, and no availability bit pointing outside the plane; sampled: only the records
+ * SAMPLED_OUT leaves.  Sets has_res: some record asks for a residual. */
+static bool validate(IntraCall &c, const bool sampled)
+{
+    const long long n_tus = c.n_tus;
     std::atomic<bool> bad{false}, any_res{false};
-    auto validate = [&](const bool sampled) {
     host_parallel_for(sampled ? 1 : n_tus, [&](long long b, long long e) {
         if (sampled) e = n_tus;
         bool res = false, ok = true;
         for (long long i = b; i < e && ok; i++) {
             if (sampled && SAMPLED_OUT(i)) { i |= 4095; continue; }
-            const ffhip_hevc_tu &t = h_tus[i];
-            const int c = t.cidx, n = 1 << t.log2_size;
-            if (c > 2 || t.log2_size < 2 || t.log2_size > 5 || t.pred_mode > 34) { ok = false; break; }
-            if (c > 0 && (!d_cb || !d_cr || uv_stride < width_c)) { ok = false; break; }
-            if (t.x + n > pw[c] || t.y + n > ph[c]) { ok = false; break; }
+            const ffhip_hevc_tu &t = c.h_tus[i];
+            const int k = t.cidx, n = 1 << t.log2_size;
+            if (k > 2 || t.log2_size < 2 || t.log2_size > 5 || t.pred_mode > 34) { ok = false; break; }
+            if (k > 0 && !c.chroma_ok) { ok = false; break; }
+            if (t.x + n > c.pw[k] || t.y + n > c.ph[k]) { ok = false; break; }
             const unsigned long long span = n == 32 ? ~0ull : (1ull << (2 * n)) - 1;
             const unsigned long long top = t.avail_top & span, left = t.avail_left & span;
-            const int room_x = pw[c] - t.x, room_y = ph[c] - t.y; /* samples that exist right of x0 / below y0 */
+            const int room_x = c.pw[k] - t.x, room_y = c.ph[k] - t.y; /* samples that exist right of x0 / below y0 */
             if ((top || (t.flags & 1)) && t.y == 0) ok = false;
             if ((left || (t.flags & 1)) && t.x == 0) ok = false;
             if (room_x < 64 && (top >> room_x)) ok = false;
@@ -2027,50 +2061,286 @@ static int intra_recon_impl(const ffhip_hevc_tu *h_tus, const ffhip_hevc_tu *d_t
         if (!ok) bad.store(true, std::memory_order_relaxed);
         if (res) any_res.store(true, std::memory_order_relaxed);
     });
-    };
-    const bool host_times = FFHIP_ENV("FFHIP_PLAN_TIMES") != nullptr;
-    const auto TH0 = std::chrono::steady_clock::now();
-    validate(big_list);
-    const auto TH1 = std::chrono::steady_clock::now();
-    if (bad.load()) return FFHIP_EINVAL;
-    bool has_res = any_res.load();
-    bool fully_validated = !big_list;
-    auto validate_fully = [&]() -> bool { /* before anything on the host walks the whole list */
-        if (!fully_validated) { validate(false); fully_validated = true; has_res = any_res.load(); }
-        return !bad.load() && !(has_res && !d_residual);
-    };
-    /* wavefront levels at 4x4-block granularity, per plane: only the level-synchronous form needs them */
+    c.has_res = any_res.load();
+    return !bad.load();
+}
+/* before anything on the host walks the whole list */
+static bool validate_fully(IntraCall &c)
+{
+    if (!c.fully_validated) {
+        if (!validate(c, false)) return false;
+        c.fully_validated = true;
+    }
+    return !(c.has_res && !c.d_residual);
+}
+
+/* The substitution table on `s`.  It depends on the TU list alone, so its records may be the caller's whatever order the schedule has. */
+static void enqueue_jtable(IntraCall &c, uint32_t *words, hipStream_t s)
+{
+    c.ja.tus = c.d_tus; c.ja.n = (uint32_t)c.n_tus; c.ja.jt = (uint8_t *)words;
+    c.a.jt = c.ja.jt;
+    hipLaunchKernelGGL(k_hevc_intra_jtable, dim3((unsigned)((c.n_tus + 255) / 256)), dim3(256), 0, s, c.ja);
+}
+/* The per-pixel programs on `s`, into `words`; c.a's schedule, table and planner words are in place */
+static void enqueue_programs(IntraCall &c, uint32_t *words, const int win[3], hipStream_t s)
+{
+    ProgArgs &pa = c.pa;
+    pa.sched = (u32x4 *)c.a.sched; pa.n_slots = (uint32_t)c.n_tus; pa.jt = c.a.jt;
+    pa.records = c.list;
+    pa.desc = (uint2 *)(((uintptr_t)words + 7) & ~(uintptr_t)7);
+    for (int k = 0; k < 3; k++) { pa.wl[k] = win[k]; pa.stride[k] = c.a.stride[k]; pa.jt_bw[k] = c.ja.bw[k]; pa.jt_boff[k] = c.ja.boff[k]; }
+    pa.plan_result = c.a.plan_result; pa.wait_cap = c.a.wait_cap;
+    c.a.desc = pa.desc;
+    hipLaunchKernelGGL(k_hevc_intra_program, dim3((unsigned)((c.n_tus + 255) / 256)), dim3(256), 0, s, pa);
+}
+/* waves of a grouped launch: FFHIP_HEVC_INTRA_WAVES, else -- for `kernel` -- as many as can be resident, else the flat cap */
+static size_t intra_waves(const void *kernel)
+{
+    const char *wv = FFHIP_ENV("FFHIP_HEVC_INTRA_WAVES");
+    if (wv) return (size_t)std::max(1, atoi(wv));
+    return kernel ? (size_t)std::max(FFHIP_HEVC_INTRA_WAVES, ffhip_resident_waves(kernel, 64)) : (size_t)FFHIP_HEVC_INTRA_WAVES;
+}
+
+/* The device-planned path.  NOTHING here waits for the device: the schedule is enqueued, the grouped kernel is enqueued behind it and reads
+ * the planner's verdict itself (a refused list takes its serial path).  For large lists the work that does not depend on the schedule runs
+ * on the calling thread's side stream, NEXT TO the planner's kernels (chains of dependent loads with the chip mostly idle):
+ *   - the substitution table, behind the list's validation (a bad record's position would send its stores anywhere);
+ *   - the depth sweep of the planner's cells, behind k_plan_owner, next to k_plan_count: three workgroups that walk diagonals for 50 - 130 us;
+ *   - behind k_plan_count, the ticket kernels and k_plan_emit.
+ * The per-pixel programs, the one large kernel of that stretch, follow k_plan_count on `st` itself, from what that kernel left (TU record, flag
+ * byte, wait count: the slots' other quarters are being written next door).  (Until late in round 4 the programs were the side stream's and
+ * the sweep ran next to them on `st`: 360 us instead of 130, the long pole of the pre-pass.  Started right behind the validation instead, from
+ * the TU records alone, with k_plan_emit settling the slot words afterwards, they ran next to k_plan_owner and k_plan_count, which then took 341
+ * and 383 us instead of 135 and 223: the eight-picture grid's pre-pass 1.14 ms instead of 1.00.)  The grouped kernel waits for both streams. */
+static int recon_device_planned(IntraCall &c, const int wl, const bool by_plane)
+{
+    HevcIntraArgs &a = c.a;
+    const long long n_tus = c.n_tus;
+    const hipStream_t st = c.st;
+    const int cs = chroma_shift(c.pw);
+    const int win[3] = {wl, wl - cs, wl - cs};
+    const size_t w_plan = ffhip_hevc_plan_gpu_words(n_tus, c.pwc, c.ph, win), w_ctrl = CTRL_HDR + (size_t)n_tus;
+    uint32_t *g_work = ffhip_scratch(c.scratch_kind, c.stream, w_plan + w_ctrl + 16 + c.w_jt + c.w_desc);
+    if (!g_work) return FFHIP_ENOMEM;
+    uint32_t *const ctrl = g_work + ((w_plan + 3) & ~(size_t)3), *const jt_words = ctrl + ((w_ctrl + 3) & ~(size_t)3);
+    FfhipHevcPlan plan;
+    const int check[2] = {c.chroma_ok ? 1 : 0, c.d_residual ? 1 : 0};
+    plan.begin(c.d_tus, n_tus, c.pwc, c.ph, win, g_work, st, ctrl, w_ctrl /* the ticket counter and the done flags */, c.big_list ? check : nullptr,
+               c.async_err);
+    a.sched = plan.a.sched; a.groups = plan.a.groups; a.wait_idx = plan.a.wait_idx; a.plan_result = plan.a.result; a.wait_cap = plan.a.wait_cap;
+
+    FfhipSide side = {nullptr, nullptr, nullptr, nullptr};
+    const bool forked = n_tus >= (1 << 15) && !FFHIP_ENV("FFHIP_HEVC_JT_INLINE") && ffhip_side_stream_get(&side) == FFHIP_OK;
+    const hipStream_t ss = (hipStream_t)side.stream;
+    const hipEvent_t fork = (hipEvent_t)side.fork, join = (hipEvent_t)side.join, mid = (hipEvent_t)side.mid;
+    c.ja.refused = plan.refused();
+    if (forked) { /* (fork: behind whatever of an earlier call still reads the table's memory) */
+        FFHIP_CHECK(hipEventRecord(fork, st), FFHIP_EIO);
+        FFHIP_CHECK(hipStreamWaitEvent(ss, fork, 0), FFHIP_EIO);
+        enqueue_jtable(c, jt_words, ss);
+        FFHIP_CHECK(hipEventRecord(join, ss), FFHIP_EIO);
+    } else {
+        enqueue_jtable(c, jt_words, st);
+    }
+    if (by_plane) plan.partition();
+    c.list = plan.a.tus;
+    plan.owner();
+    bool tickets_aside = forked && !FFHIP_ENV("FFHIP_HEVC_SWEEP_INLINE") && !FFHIP_ENV("FFHIP_HEVC_PROGRAMS_INLINE");
+    if (tickets_aside && (hipEventRecord(fork, st) != hipSuccess || hipStreamWaitEvent(ss, fork, 0) != hipSuccess)) {
+        (void)hipGetLastError();
+        tickets_aside = false;
+    }
+    if (tickets_aside) plan.sweep(ss);
+    plan.count();
+    const bool programs_early = forked && !FFHIP_ENV("FFHIP_HEVC_PROGRAMS_INLINE");
+    if (programs_early) { /* behind k_plan_count: its flags and wait counts are all they need of the schedule */
+        c.pa.tus = c.list; c.pa.flags = plan.a.flags; c.pa.wcount = plan.a.wcount;
+        FFHIP_CHECK(hipEventRecord(mid, st), FFHIP_EIO);
+        if (tickets_aside) {
+            enqueue_programs(c, jt_words + c.w_jt, win, st);
+        } else { /* the sweep and the ticket kernels stay on `st`: the programs go next to them */
+            FFHIP_CHECK(hipStreamWaitEvent(ss, mid, 0), FFHIP_EIO);
+            enqueue_programs(c, jt_words + c.w_jt, win, ss);
+            FFHIP_CHECK(hipEventRecord(join, ss), FFHIP_EIO);
+        }
+    }
+    if (tickets_aside) FFHIP_CHECK(hipStreamWaitEvent(ss, mid, 0), FFHIP_EIO);
+    else plan.sweep(st);
+    plan.tickets(tickets_aside ? ss : st);
+    if (tickets_aside) FFHIP_CHECK(hipEventRecord(join, ss), FFHIP_EIO);
+    const hipError_t launched = hipGetLastError();
+    /* the side stream's last record: behind the programs when they went there.  (`st` must not run ahead of its read of the caller's list,
+     * whatever happened.) */
+    if (forked) FFHIP_CHECK(hipStreamWaitEvent(st, join, 0), FFHIP_EIO);
+    if (launched != hipSuccess) {
+        ffhip_note_hip_error((int)launched, "hipGetLastError()");
+        return FFHIP_EIO;
+    }
+    set_ctrl(a, ctrl);
+    a.async_err = c.async_err;
+    a.n_groups = 0;
+    a.n_tus = n_tus;
+    a.tus = c.list;
+    if (!programs_early) enqueue_programs(c, jt_words + c.w_jt, win, st);
+#ifdef FFHIP_INTRA_TRACE
+    a.trace = g_intra_trace;
+#endif
+    if (c.plan_done) {
+        FFHIP_CHECK(hipEventRecord(c.plan_done, st), FFHIP_EIO);
+        FFHIP_CHECK(hipStreamWaitEvent(c.gst, c.plan_done, 0), FFHIP_EIO);
+    }
+    /* as many waves as can be resident: they trim themselves to the planner's wavefront width.  The throughput instance (three waves per SIMD,
+     * 168 VGPRs) takes plans whose widest wavefront is 3 000 groups and more -- grids of several pictures: four / eight pictures 1.86 / 3.58 ms
+     * against 1.98 / 3.85 with the latency instance; one picture's 135 tiles (width 1 652) are indifferent (0.78 / 0.77).  While every ticket
+     * was an atomic on ONE word in a cache line that waiting waves polled, the extra waves bought nothing (4.28 against 4.29 ms at eight
+     * pictures) and the instance was off.  (An instance with four waves per SIMD's worth of registers -- 128, 27 of them spilled -- would be
+     * thirteen waves per CU by LDS: measured, 3.46 against 3.18 ms at eight pictures.) */
+    const size_t rw = std::max<size_t>(64, intra_waves((const void *)k_hevc_intra_groups<2, 64>));
+    const size_t rw_tp = std::max<size_t>(64, intra_waves((const void *)k_hevc_intra_groups<3, 16>));
+    hipLaunchKernelGGL((k_hevc_intra_groups<2, 64>), dim3((unsigned)std::min<size_t>((size_t)n_tus, rw)), dim3(64), 0, c.gst, a);
+    if (a.tp_width) hipLaunchKernelGGL((k_hevc_intra_groups<3, 16>), dim3((unsigned)std::min<size_t>((size_t)n_tus, rw_tp)), dim3(64), 0, c.gst, a);
+    hipLaunchKernelGGL(k_hevc_intra_serial, dim3(1), dim3(64), 0, c.gst, a); /* does something only for a list the planner refused */
+    g_last_plan_result = a.plan_result; g_last_plan_stream = c.gst;
+    if (FFHIP_ENV("FFHIP_PLAN_TIMES")) {
+        const auto th3 = std::chrono::steady_clock::now();
+        auto us = [](auto x, auto y) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(y - x).count(); };
+        fprintf(stderr, "intra_recon host: validate %ld us, window %ld us, enqueue %ld us (%lld TUs)\n", us(c.th[0], c.th[1]), us(c.th[1], c.th[2]),
+                us(c.th[2], th3), n_tus);
+    }
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
+}
+
+/* The host-planned path: plan_groups with its window search (from `want_wl` down), the schedule uploaded.  1 when no window gives a
+ * deadlock-free plan: the caller takes the levels form. */
+static int recon_host_planned(IntraCall &c, const int want_wl, bool by_plane)
+{
+    HevcIntraArgs &a = c.a;
+    const long long n_tus = c.n_tus;
+    GroupPlan plan;
+    int host_wl = 0;
+    /* the host planner works on the list sorted by plane where the device planner would (pick_window): its slots' TU indices then refer to
+     * the sorted records, which are uploaded next to the schedule */
+    std::vector<ffhip_hevc_tu> h_sorted;
+    if (c.big_list) (void)pick_window(c.h_tus, n_tus, c.pw, c.ph, want_wl, false, &by_plane); /* (the first answer came from a sample) */
+    if (by_plane) sort_by_plane(c.h_tus, n_tus, h_sorted, nullptr);
+    if (!plan_with_window_search(by_plane ? h_sorted.data() : c.h_tus, n_tus, c.pw, c.ph, want_wl, plan, &host_wl, c.ja.boff)) return 1;
+    /* device image: sched | groups | wait | ctrl[CTRL_HDR] + one done flag per TU */
+    const size_t w_sched = plan.sched.size() * 4, w_groups = plan.groups.size() * 4, w_wait = plan.wait.size();
+    const size_t w_ctrl = CTRL_HDR + (size_t)n_tus;
+    const size_t o_groups = w_sched, o_wait = o_groups + w_groups, o_ctrl = (o_wait + w_wait + 3) & ~(size_t)3;
+    const size_t w_sorted = by_plane ? 8 * (size_t)n_tus + 16 : 0;
+    FFHIP_CHECK(hipStreamSynchronize(c.st), FFHIP_EIO); /* the work buffer may still be in use by an earlier call */
+    uint32_t *g_work = ffhip_scratch(c.scratch_kind, c.stream, o_ctrl + w_ctrl + 4 + c.w_jt + c.w_desc + w_sorted);
+    if (!g_work) return FFHIP_ENOMEM;
+    uint32_t *const jt_words = g_work + ((o_ctrl + w_ctrl + 3) & ~(size_t)3);
+    if (by_plane) {
+        uint32_t *ps = jt_words + c.w_jt + c.w_desc + 4;
+        ps += (8 - (((uintptr_t)ps >> 2) & 7)) & 7;
+        FFHIP_CHECK(hipMemcpy(ps, h_sorted.data(), (size_t)n_tus * sizeof(ffhip_hevc_tu), hipMemcpyHostToDevice), FFHIP_EIO);
+        c.list = (const ffhip_hevc_tu *)ps;
+        a.tus = c.list;
+    }
+    enqueue_jtable(c, jt_words, c.st);
+    FFHIP_CHECK(hipMemcpy(g_work, plan.sched.data(), w_sched * 4, hipMemcpyHostToDevice), FFHIP_EIO);
+    FFHIP_CHECK(hipMemcpy(g_work + o_groups, plan.groups.data(), w_groups * 4, hipMemcpyHostToDevice), FFHIP_EIO);
+    FFHIP_CHECK(hipMemcpy(g_work + o_wait, plan.wait.data(), w_wait * 4, hipMemcpyHostToDevice), FFHIP_EIO);
+    FFHIP_CHECK(hipMemsetAsync(g_work + o_ctrl, 0, w_ctrl * 4, c.st), FFHIP_EIO);
+    a.sched = (const u32x4 *)g_work;
+    a.groups = (const u32x4 *)(g_work + o_groups);
+    a.wait_idx = g_work + o_wait;
+    set_ctrl(a, g_work + o_ctrl);
+    g_last_plan_result = nullptr;
+    a.async_err = c.async_err;
+    a.n_groups = (int)plan.groups.size();
+    const int cs = chroma_shift(c.pw);
+    const int win[3] = {host_wl, host_wl - cs, host_wl - cs};
+    enqueue_programs(c, jt_words + c.w_jt, win, c.st);
+    const unsigned wgs = (unsigned)std::min<size_t>(plan.groups.size(), intra_waves(nullptr)); /* one wave each; waves loop over tickets */
+    a.tp_width = 0;
+    hipLaunchKernelGGL((k_hevc_intra_groups<2, 64>), dim3(wgs), dim3(64), 0, c.st, a);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
+}
+
+/* The level-synchronous form: wavefront levels at 4x4-block granularity, per plane, one launch per level */
+static int recon_levels(IntraCall &c)
+{
     std::vector<std::vector<uint32_t>> lists;
-    auto build_levels = [&]() {
+    {
         std::vector<int> lvl[3];
         int bw[3];
-        for (int c = 0; c < 3; c++) {
-            bw[c] = (pw[c] + 3) / 4;
-            lvl[c].assign((size_t)(c == 0 || (d_cb && d_cr) ? bw[c] * ((ph[c] + 3) / 4) : 0), -1);
+        for (int k = 0; k < 3; k++) {
+            bw[k] = (c.pw[k] + 3) / 4;
+            lvl[k].assign((size_t)(k == 0 || c.chroma ? bw[k] * ((c.ph[k] + 3) / 4) : 0), -1);
         }
-        for (long long i = 0; i < n_tus; i++) {
-            const ffhip_hevc_tu &t = h_tus[i];
-            const int c = t.cidx, n = 1 << t.log2_size;
+        for (long long i = 0; i < c.n_tus; i++) {
+            const ffhip_hevc_tu &t = c.h_tus[i];
+            const int k = t.cidx, n = 1 << t.log2_size;
             int lv = 0;
-            auto dep = [&](int px, int py) { lv = std::max(lv, lvl[c][(size_t)(py / 4) * bw[c] + px / 4] + 1); };
+            auto dep = [&](int px, int py) { lv = std::max(lv, lvl[k][(size_t)(py / 4) * bw[k] + px / 4] + 1); };
             if (t.flags & 1) dep(t.x - 1, t.y - 1);
-            for (int k = 0; k < 2 * n; k++) {
-                if ((t.avail_top >> k) & 1) dep(t.x + k, t.y - 1);
-                if ((t.avail_left >> k) & 1) dep(t.x - 1, t.y + k);
+            for (int j = 0; j < 2 * n; j++) {
+                if ((t.avail_top >> j) & 1) dep(t.x + j, t.y - 1);
+                if ((t.avail_left >> j) & 1) dep(t.x - 1, t.y + j);
             }
             for (int by = t.y / 4; by < (t.y + n) / 4; by++)
-                for (int bx = t.x / 4; bx < (t.x + n) / 4; bx++) lvl[c][(size_t)by * bw[c] + bx] = lv;
+                for (int bx = t.x / 4; bx < (t.x + n) / 4; bx++) lvl[k][(size_t)by * bw[k] + bx] = lv;
             if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
             lists[(size_t)lv].push_back((uint32_t)i);
         }
-    };
-    if (has_res && !d_residual) return FFHIP_EINVAL;
-    hipStream_t st = roles ? roles->plan : (hipStream_t)stream; /* everything in front of the grouped kernel */
-    const int scratch_kind = roles ? roles->scratch_kind : SCRATCH_HEVC_INTRA;
-    HevcIntraArgs a = {};
-    /* the records the schedule's TU indices refer to: the caller's, or -- for a list that interleaves the planes inside a scheduling window --
-     * a copy sorted by plane in the call's scratch (pick_window) */
-    const ffhip_hevc_tu *list = d_tus;
+    }
+    std::vector<uint32_t> flat;
+    flat.reserve((size_t)c.n_tus);
+    for (auto &l : lists) flat.insert(flat.end(), l.begin(), l.end());
+    FFHIP_CHECK(hipStreamSynchronize(c.st), FFHIP_EIO);
+    uint32_t *g_work = ffhip_scratch(c.scratch_kind, c.stream, (size_t)c.n_tus);
+    if (!g_work) return FFHIP_ENOMEM;
+    FFHIP_CHECK(hipMemcpy(g_work, flat.data(), flat.size() * sizeof(uint32_t), hipMemcpyHostToDevice), FFHIP_EIO);
+    size_t off = 0;
+    for (auto &l : lists) {
+        c.a.work = g_work + off;
+        c.a.count = (int)l.size();
+        hipLaunchKernelGGL(k_hevc_intra, dim3((unsigned)((c.a.count + 3) / 4)), dim3(256), 0, c.st, c.a);
+        off += l.size();
+    }
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
+}
+
+/* pre: the stream of everything in front of the grouped kernel (the caller's, or the early pre-pass's), plan_done (NULL, or the event the
+ * caller's stream waits for behind the pre-pass), scratch_kind: whose scratch the call takes */
+static int intra_recon_impl(const ffhip_hevc_tu *h_tus, const ffhip_hevc_tu *d_tus, long long n_tus,
+                            const int16_t *d_residual, int16_t *d_y, int16_t *d_cb, int16_t *d_cr,
+                            int width_y, int height_y, int y_stride, int width_c, int height_c,
+                            int uv_stride, int bitdepth_y, int bitdepth_c, void *stream, hipStream_t pre, hipEvent_t plan_done, int scratch_kind)
+{
+    if (n_tus < 0 || n_tus > 0x7fffffffLL) return FFHIP_EINVAL;
+    if (n_tus == 0) return FFHIP_OK;
+    if (!h_tus || !d_tus || !d_y || width_y <= 0 || height_y <= 0 || y_stride < width_y) return FFHIP_EINVAL;
+    if (bitdepth_y < 8 || bitdepth_y > 15 || bitdepth_c < 8 || bitdepth_c > 15) return FFHIP_EINVAL;
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    IntraCall c{};
+    c.h_tus = h_tus; c.d_tus = d_tus; c.n_tus = n_tus; c.d_residual = d_residual;
+    c.chroma = d_cb && d_cr;
+    c.chroma_ok = c.chroma && uv_stride >= width_c;
+    for (int k = 0; k < 3; k++) {
+        c.pw[k] = k ? width_c : width_y;
+        c.ph[k] = k ? height_c : height_y;
+        c.pwc[k] = k == 0 || c.chroma ? c.pw[k] : 0;
+    }
+    c.list = d_tus;
+    c.stream = stream; c.st = pre; c.gst = (hipStream_t)stream; c.plan_done = plan_done; c.scratch_kind = scratch_kind;
+    /* lists of 2^17 TUs and more: the host looks at a sample (a bad record there is refused here, at once), every record is checked by a
+     * kernel in front of the planner (k_hevc_check_tus), which refuses the call through the stream -- or by a full host pass, should the
+     * call not take the device planner */
+    c.big_list = n_tus >= (1LL << 17) && !FFHIP_ENV("FFHIP_HEVC_HOST_CHECK");
+    c.fully_validated = !c.big_list;
+    c.th[0] = std::chrono::steady_clock::now();
+    const bool ok = validate(c, c.big_list);
+    c.th[1] = std::chrono::steady_clock::now();
+    if (!ok || (c.has_res && !d_residual)) return FFHIP_EINVAL;
+    HevcIntraArgs &a = c.a;
     a.tus = d_tus; a.residual = d_residual;
     a.plane[0] = d_y; a.plane[1] = d_cb; a.plane[2] = d_cr;
     a.stride[0] = y_stride; a.stride[1] = uv_stride; a.stride[2] = uv_stride;
@@ -2079,299 +2349,53 @@ static int intra_recon_impl(const ffhip_hevc_tu *h_tus, const ffhip_hevc_tu *d_t
         const char *dw = FFHIP_ENV("FFHIP_DEBUG_WITHHOLD_TU");
         a.debug_withhold = dw ? atoi(dw) : -1;
     }
+    lay_out_tables(c);
 
     /* grouped single-launch form unless FFHIP_HEVC_INTRA_MODE=levels (diagnostics) or no window works */
     const char *mode_env = FFHIP_ENV("FFHIP_HEVC_INTRA_MODE");
     const bool want_groups = !(mode_env && !strcmp(mode_env, "levels"));
-    int *async_err = want_groups ? ffhip_async_err_word() : nullptr;
+    c.async_err = want_groups ? ffhip_async_err_word() : nullptr;
     const bool offsets_fit = (long long)y_stride * height_y < (1LL << 30) && (long long)uv_stride * (height_c > 0 ? height_c : 1) < (1LL << 30);
-    /* geometry of the substitution table (and of the device planner's owner map): 4x4 blocks of the planes in use */
-    const int pwc[3] = {pw[0], (d_cb && d_cr) ? pw[1] : 0, (d_cb && d_cr) ? pw[2] : 0};
-    size_t jt_blocks = 0;
-    JTabArgs ja = {};
-    for (int c = 0; c < 3; c++) {
-        ja.bw[c] = (pwc[c] + 3) / 4;
-        ja.boff[c] = (uint32_t)jt_blocks;
-        if (pwc[c] > 0) jt_blocks += (size_t)ja.bw[c] * (size_t)((ph[c] + 3) / 4);
-        a.jt_bw[c] = ja.bw[c];
-        a.jt_boff[c] = ja.boff[c];
-    }
-    const size_t w_jt = (jt_blocks * JT_STRIDE + 256 + 3) / 4; /* padded: the kernel fetches 64 / 192 entries per TU whatever its size */
-    /* the per-pixel programs: 8 bytes per sample of the planes in use */
-    ProgArgs pa = {};
-    size_t desc_px = 0;
-    for (int c = 0; c < 3; c++) {
-        pa.desc_w[c] = pwc[c];
-        pa.desc_off[c] = (uint32_t)desc_px;
-        if (pwc[c] > 0) desc_px += (size_t)pwc[c] * (size_t)ph[c];
-        a.desc_w[c] = pa.desc_w[c];
-        a.desc_off[c] = pa.desc_off[c];
-    }
-    const size_t w_desc = desc_px * 2 + 2;
-    auto enqueue_programs = [&](uint32_t *words, const int win[3], size_t n_slots, hipStream_t ps) {
-        pa.sched = (u32x4 *)a.sched; pa.n_slots = (uint32_t)n_slots; pa.jt = a.jt;
-        pa.records = list;
-        pa.desc = (uint2 *)(((uintptr_t)words + 7) & ~(uintptr_t)7);
-        for (int c = 0; c < 3; c++) { pa.wl[c] = win[c]; pa.stride[c] = a.stride[c]; pa.jt_bw[c] = ja.bw[c]; pa.jt_boff[c] = ja.boff[c]; }
-        pa.plan_result = a.plan_result; pa.wait_cap = a.wait_cap;
-        a.desc = pa.desc;
-        hipLaunchKernelGGL(k_hevc_intra_program, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, ps, pa);
-    };
-    /* The substitution table depends on the TU list alone: for large lists it is built on the calling thread's side stream, NEXT TO the planner's
-     * kernels (which are chains of dependent loads with the chip mostly idle), and joined in front of the first kernel that reads it. */
-    bool jt_forked = false;
-    FfhipSide side = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto enqueue_jtable = [&](uint32_t *words, bool may_fork) -> int {
-        ja.tus = d_tus; ja.n = (uint32_t)n_tus; ja.jt = (uint8_t *)words;
-        a.jt = ja.jt;
-        hipStream_t js = st;
-        if (may_fork && n_tus >= (1 << 15) && !FFHIP_ENV("FFHIP_HEVC_JT_INLINE") && ffhip_side_stream_get(&side) == FFHIP_OK) {
-            FFHIP_CHECK(hipEventRecord((hipEvent_t)side.fork, st), FFHIP_EIO); /* behind whatever of an earlier call still reads the table's memory */
-            FFHIP_CHECK(hipStreamWaitEvent((hipStream_t)side.stream, (hipEvent_t)side.fork, 0), FFHIP_EIO);
-            js = (hipStream_t)side.stream;
-            jt_forked = true;
-        }
-        hipLaunchKernelGGL(k_hevc_intra_jtable, dim3((unsigned)((n_tus + 255) / 256)), dim3(256), 0, js, ja);
-        if (jt_forked) FFHIP_CHECK(hipEventRecord((hipEvent_t)side.join, js), FFHIP_EIO);
-        return FFHIP_OK;
-    };
-    auto join_jtable = [&]() -> int { /* in front of the first kernel on `st` that reads the table */
-        if (jt_forked) FFHIP_CHECK(hipStreamWaitEvent(st, (hipEvent_t)side.join, 0), FFHIP_EIO);
-        jt_forked = false;
-        return FFHIP_OK;
-    };
-    if (want_groups && async_err && offsets_fit && jt_blocks * JT_STRIDE < (1ull << 32) && desc_px < (1ull << 29) /* 32-bit byte offsets into a plane, the table and the pixel words */) {
+    /* (32-bit byte offsets into a plane, the table and the pixel words) */
+    const bool grouped = want_groups && c.async_err && offsets_fit && c.jt_blocks * JT_STRIDE < (1ull << 32) && c.desc_px < (1ull << 29);
+    int host_wl = 0;
+    bool by_plane = false;
+    if (grouped) {
         const char *we = FFHIP_ENV("FFHIP_HEVC_INTRA_WINDOW");
-        const char *wv = FFHIP_ENV("FFHIP_HEVC_INTRA_WAVES");
-        /* device-planned launches start as many waves as can be resident and trim themselves to the planner's wavefront width
-         * (k_hevc_intra_groups); host-planned ones keep the flat cap */
-        const size_t max_waves = wv ? (size_t)std::max(1, atoi(wv)) : FFHIP_HEVC_INTRA_WAVES;
-        const size_t resident_waves = wv ? max_waves : (size_t)std::max(FFHIP_HEVC_INTRA_WAVES, ffhip_resident_waves((const void *)k_hevc_intra_groups<2, 64>, 64));
-        const size_t resident_waves_tp = wv ? max_waves : (size_t)std::max(FFHIP_HEVC_INTRA_WAVES, ffhip_resident_waves((const void *)k_hevc_intra_groups<3, 16>, 64));
-        /* The throughput instance (three waves per SIMD, 168 VGPRs) takes plans whose widest wavefront is 3 000 groups and more -- grids of several
-         * pictures: four / eight pictures 1.86 / 3.58 ms against 1.98 / 3.85 with the latency instance; one picture's 135 tiles (width 1 652) are
-         * indifferent (0.78 / 0.77).  While every ticket was an atomic on ONE word in a cache line that waiting waves polled, the extra waves bought
-         * nothing (4.28 against 4.29 ms at eight pictures) and the instance was off.  FFHIP_HEVC_INTRA_TP_WIDTH=<width> moves the threshold, 0 = never. */
+        /* FFHIP_HEVC_INTRA_TP_WIDTH=<width>: the widest wavefront from which the throughput instance runs, 0 = never (recon_device_planned) */
         { const char *tw = FFHIP_ENV("FFHIP_HEVC_INTRA_TP_WIDTH"); a.tp_width = tw ? (uint32_t)std::max(0, atoi(tw)) : 3000u; }
         { const char *pr = FFHIP_ENV("FFHIP_HEVC_INTRA_POLL_REPS"); a.poll_reps = pr ? (uint32_t)std::max(1, atoi(pr)) : 1u; }
         { const char *tsx = FFHIP_ENV("FFHIP_HEVC_TICKET_SHARDS"); a.ticket_shards = tsx ? (uint32_t)std::min(8, std::max(1, atoi(tsx))) : 4u; }
         { const char *wp = FFHIP_ENV("FFHIP_HEVC_INTRA_WIDTH_PCT"); a.width_pct = wp ? (uint32_t)std::max(1, atoi(wp)) : 128u; }
-        /* the schedule: built on the device (ffhip_hevc_plan_gpu.hip) unless FFHIP_HEVC_PLAN=host; lists whose groups are
-         * not contiguous runs of the decode order come back from there and take the host planner with its window search */
+        /* the schedule: built on the device (ffhip_hevc_plan_gpu.hip) unless FFHIP_HEVC_PLAN=host.  A list whose groups are not contiguous runs
+         * of the decode order even at the smallest window would be refused by the device planner and decoded by ONE wave (k_hevc_intra_serial:
+         * exact, seconds for an 8K list): such a list takes the host planner with its window search -- or the levels form -- right away; the
+         * serial kernel stays for what only the device can find (more than 64 TUs to wait for, an order its ticket rule cannot serve).  The
+         * window is chosen here, on the host, from the list alone: the largest one (up to the requested) whose groups are contiguous runs of
+         * the decode order -- a 16x16 coding tree block stream needs 16, and finding that out on the device would cost a round trip.  Default:
+         * 64x64, one group per coding tree block.  A group start costs a chain of dependent loads (ticket, group record, slots, wait list,
+         * flags: ~3 us) and every window edge makes halo TUs; with the small TUs running as per-pixel programs the longer serial walk through
+         * a 64x64 block costs less than that (8K random quadtree: 14.8 ms against 17.3 with 32x32; the config-5 mix 8.1 against 12.0; 1080p and
+         * smaller pictures are indifferent -- tests/tools/bench_intra_c5.py, bench_intra_sizes.py) */
         const char *pe = FFHIP_ENV("FFHIP_HEVC_PLAN");
-        /* a list whose groups are not contiguous runs of the decode order even at the smallest window would be refused by the device
-         * planner and decoded by ONE wave (k_hevc_intra_serial: exact, seconds for an 8K list): such a list takes the host planner
-         * with its window search -- or the levels form -- right away; the serial kernel stays for what only the device can find
-         * (more than 64 TUs to wait for, an order its ticket rule cannot serve) */
-        bool by_plane = false;
-        const int dev_cs = (pw[1] > 0 && pw[1] * 2 <= pw[0] + 1) ? 1 : 0;
-        int dev_wl = pick_window(h_tus, n_tus, pw, ph, we ? atoi(we) : 6, big_list, &by_plane);
+        int dev_wl = pick_window(h_tus, n_tus, c.pw, c.ph, we ? atoi(we) : 6, c.big_list, &by_plane);
         bool dev_ok = dev_wl != 0;
         if (!dev_ok) dev_wl = 3;
-        const auto TH2 = std::chrono::steady_clock::now();
+        c.th[2] = std::chrono::steady_clock::now();
         if (pe && !strcmp(pe, "device")) dev_ok = true; /* tests: force the device planner (and with it the serial path of a list it refuses) */
-        if (!(pe && !strcmp(pe, "host")) && dev_ok) {
-            /* NOTHING below waits for the device: the schedule is enqueued, the grouped kernel is enqueued behind it and
-             * reads the planner's verdict itself (a refused list takes its serial path).  The window is chosen here, on
-             * the host, from the list alone: the largest one (up to the requested) whose groups are contiguous runs of
-             * the decode order -- a 16x16 coding tree block stream needs 16, and finding that out on the device would
-             * cost a round trip. */
-            /* default window: 64x64, one group per coding tree block.  A group start costs a chain of dependent loads
-             * (ticket, group record, slots, wait list, flags: ~3 us) and every window edge makes halo TUs; with the small
-             * TUs running as per-pixel programs the longer serial walk through a 64x64 block costs less than that
-             * (8K random quadtree: 14.8 ms against 17.3 with 32x32; the config-5 mix 8.1 against 12.0; 1080p and smaller
-             * pictures are indifferent -- tests/tools/bench_intra_c5.py, bench_intra_sizes.py) */
-            const int wl = dev_wl, cs = dev_cs;
-            const int win[3] = {wl, wl - cs, wl - cs};
-            const size_t w_plan = ffhip_hevc_plan_gpu_words(n_tus, pwc, ph, win), w_ctrl = CTRL_HDR + (size_t)n_tus;
-            const bool shared_jt = roles && roles->jt_desc;
-            uint32_t *g_work = ffhip_scratch(scratch_kind, stream, w_plan + w_ctrl + 16 + (shared_jt ? 0 : w_jt + w_desc));
-            if (!g_work) return FFHIP_ENOMEM;
-            uint32_t *const jt_words = shared_jt ? roles->jt_desc : g_work + ((w_plan + 3) & ~(size_t)3) + ((w_ctrl + 3) & ~(size_t)3);
-            int n_groups = 0;
-            /* the substitution table starts (on the side stream) behind the list's validation: a bad record's position would send its stores anywhere */
-            /* ... and the per-pixel programs follow it there, behind k_plan_count (whose flags and wait counts are all they need of the schedule),
-             * next to the ticket kernels and k_plan_emit on `stream`; the grouped kernel waits for both.  (Started right behind the validation
-             * instead, from the TU records alone, with k_plan_emit settling the slot words afterwards -- the programs read no table any more --
-             * they ran next to k_plan_owner and k_plan_count, which then took 341 and 383 us instead of 135 and 223: the eight-picture grid's
-             * pre-pass 1.14 ms instead of 1.00.) */
-            /* The side stream takes, behind the table: the depth sweep of the planner's cells (behind k_plan_owner, NEXT TO k_plan_count: three
-             * workgroups that walk diagonals for 50 - 130 us), then -- behind k_plan_count -- the ticket kernels and k_plan_emit.  The per-pixel
-             * programs, the one large kernel of that stretch, follow k_plan_count on `stream` itself, from what that kernel left (TU record,
-             * flag byte, wait count: the slots' other quarters are being written next door).  (Until late in round 4 the programs were the side
-             * stream's and the sweep ran next to them on `stream`: 360 us instead of 130, the long pole of the pre-pass.) */
-            bool programs_forked = false, tickets_aside = false;
-            auto ticket_stream = [&]() -> void * {
-                if (!jt_forked || FFHIP_ENV("FFHIP_HEVC_SWEEP_INLINE") || FFHIP_ENV("FFHIP_HEVC_PROGRAMS_INLINE")) return nullptr;
-                if (hipEventRecord((hipEvent_t)side.fork, st) != hipSuccess || hipStreamWaitEvent((hipStream_t)side.stream, (hipEvent_t)side.fork, 0) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return nullptr;
-                }
-                tickets_aside = true;
-                return side.stream;
-            };
-            auto programs_early = [&](const uint8_t *flags, const uint32_t *wcount, const uint32_t *result) -> int {
-                if (!jt_forked) return FFHIP_OK; /* a small list: everything on `stream`, in order */
-                pa.tus = list; pa.flags = flags; pa.wcount = wcount; pa.refused = nullptr;
-                a.sched = (const u32x4 *)g_work; /* where the planner puts the slots (ffhip_hevc_plan_gpu's layout starts with them) */
-                a.plan_result = result; a.wait_cap = (uint32_t)(8 * (size_t)n_tus);
-                if (tickets_aside) { /* on `stream`, right behind k_plan_count -- and behind the point the ticket kernels wait for */
-                    FFHIP_CHECK(hipEventRecord((hipEvent_t)side.mid, st), FFHIP_EIO);
-                    enqueue_programs(jt_words + w_jt, win, (size_t)n_tus, st);
-                } else { /* the sweep and the ticket kernels stay on `stream`: the programs go next to them */
-                    FFHIP_CHECK(hipEventRecord((hipEvent_t)side.mid, st), FFHIP_EIO);
-                    FFHIP_CHECK(hipStreamWaitEvent((hipStream_t)side.stream, (hipEvent_t)side.mid, 0), FFHIP_EIO);
-                    enqueue_programs(jt_words + w_jt, win, (size_t)n_tus, (hipStream_t)side.stream);
-                    FFHIP_CHECK(hipEventRecord((hipEvent_t)side.join, (hipStream_t)side.stream), FFHIP_EIO);
-                }
-                programs_forked = true;
-                return FFHIP_OK;
-            };
-            auto tickets_wait = [&]() -> int {
-                FFHIP_CHECK(hipStreamWaitEvent((hipStream_t)side.stream, (hipEvent_t)side.mid, 0), FFHIP_EIO); /* recorded behind k_plan_count, in front of the programs */
-                return FFHIP_OK;
-            };
-            auto tickets_enqueued = [&]() -> int {
-                FFHIP_CHECK(hipEventRecord((hipEvent_t)side.join, (hipStream_t)side.stream), FFHIP_EIO);
-                return FFHIP_OK;
-            };
-            struct Hook { decltype(enqueue_jtable) *fn; decltype(programs_early) *pe; uint32_t *words; JTabArgs *ja; decltype(ticket_stream) *ts; decltype(tickets_wait) *tw;
-                          decltype(tickets_enqueued) *te; } hook = {&enqueue_jtable, &programs_early, jt_words, &ja, &ticket_stream, &tickets_wait, &tickets_enqueued};
-            FfhipPlanHooks hooks = {};
-            hooks.ctx = &hook;
-            hooks.by_plane = by_plane ? 1 : 0;
-            hooks.tus_used = &list;
-            hooks.after_check = [](void *ctx, const unsigned *refused) -> int {
-                Hook *h = (Hook *)ctx;
-                h->ja->refused = refused;
-                return (*h->fn)(h->words, true);
-            };
-            hooks.ticket_stream = [](void *ctx) -> void * { return (*((Hook *)ctx)->ts)(); };
-            hooks.tickets_wait = [](void *ctx) -> int { return (*((Hook *)ctx)->tw)(); };
-            hooks.tickets_enqueued = [](void *ctx) -> int { return (*((Hook *)ctx)->te)(); };
-            if (!FFHIP_ENV("FFHIP_HEVC_PROGRAMS_INLINE"))
-                hooks.after_count = [](void *ctx, const unsigned char *flags, const unsigned *wcount, const unsigned *result) -> int {
-                    return (*((Hook *)ctx)->pe)(flags, wcount, result);
-                };
-            const int check[2] = {(d_cb && d_cr && uv_stride >= width_c) ? 1 : 0, d_residual ? 1 : 0};
-            const int prc = ffhip_hevc_plan_gpu_checked(d_tus, n_tus, pwc, ph, win, g_work, st, &a.sched, &a.groups, &a.wait_idx, &n_groups, &a.plan_result, &a.wait_cap,
-                                                        big_list ? check : nullptr, async_err, &hooks,
-                                                        g_work + ((w_plan + 3) & ~(size_t)3), w_ctrl /* the ticket counter and the done flags: cleared by the planner's first launch */);
-            if (prc < 0) { (void)join_jtable(); return prc; } /* (`stream` must not run ahead of the side stream's read of the caller's list) */
-            a.ctrl = g_work + ((w_plan + 3) & ~(size_t)3);
-            a.ctrl_ticket = (uint32_t)((32 - (((uintptr_t)a.ctrl >> 2) & 31)) & 31); a.ctrl_abort = a.ctrl_ticket + 32 * 9;
-            a.async_err = async_err;
-            a.n_groups = 0;
-            a.n_tus = n_tus;
-            a.tus = list;
-            { const int jrc = join_jtable(); if (jrc) return jrc; } /* (the side stream's last record: behind the programs when they went there) */
-            if (!programs_forked) { pa.tus = nullptr; pa.flags = nullptr; pa.wcount = nullptr; pa.refused = nullptr; enqueue_programs(jt_words + w_jt, win, (size_t)n_tus, st); }
-#ifdef FFHIP_INTRA_TRACE
-            a.trace = g_intra_trace;
-#endif
-            hipStream_t gst = st;
-            if (roles) { /* a chunk of a pipelined call: the grouped kernel runs elsewhere, behind this pre-pass */
-                FFHIP_CHECK(hipEventRecord(roles->plan_done, st), FFHIP_EIO);
-                FFHIP_CHECK(hipStreamWaitEvent(roles->groups, roles->plan_done, 0), FFHIP_EIO);
-                gst = roles->groups;
-            }
-            /* a chunk of a pipelined call leaves a share of the wave slots free: its waves hold ALL of their SIMD's registers (3 x 168), so with the
-             * chip full of them the next chunk's pre-pass did not start before they left (its first kernel: 8 us alone, 550 us there), and no two
-             * chunks' grouped kernels ever overlapped.  Tickets, not residency, are what a launch of any size is safe by. */
-            size_t share = 100;
-            if (roles && roles->jt_desc) { const char *sp = FFHIP_ENV("FFHIP_HEVC_TILE_WAVES_PCT"); share = sp ? (size_t)std::max(10, std::min(100, atoi(sp))) : 67; }
-            const size_t rw = std::max<size_t>(64, resident_waves * share / 100), rw_tp = std::max<size_t>(64, resident_waves_tp * share / 100);
-            hipLaunchKernelGGL((k_hevc_intra_groups<2, 64>), dim3((unsigned)std::min<size_t>((size_t)n_tus, rw)), dim3(64), 0, gst, a);
-            /* (an instance with four waves per SIMD's worth of registers -- 128, 27 of them spilled -- would be thirteen waves per CU by LDS: measured,
-             * 3.46 against 3.18 ms at eight pictures) */
-            if (a.tp_width) hipLaunchKernelGGL((k_hevc_intra_groups<3, 16>), dim3((unsigned)std::min<size_t>((size_t)n_tus, rw_tp)), dim3(64), 0, gst, a);
-            hipLaunchKernelGGL(k_hevc_intra_serial, dim3(1), dim3(64), 0, gst, a); /* does something only for a list the planner refused */
-            g_last_plan_result = a.plan_result; g_last_plan_stream = gst;
-            if (host_times) {
-                const auto TH3 = std::chrono::steady_clock::now();
-                auto us = [](auto x, auto y) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(y - x).count(); };
-                fprintf(stderr, "intra_recon host: validate %ld us, window %ld us, enqueue %ld us (%lld TUs)\n", us(TH0, TH1), us(TH1, TH2), us(TH2, TH3), n_tus);
-            }
-            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-            return FFHIP_OK;
-        }
-        if (!validate_fully()) return FFHIP_EINVAL; /* the host planner walks every record */
-        if (roles) { /* (a chunk of a pipelined call that does not take the device planner: in line on its groups stream, which has the inputs) */
-            FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-            st = roles->groups;
-        }
-        GroupPlan plan;
-        int host_wl = 0;
-        /* the host planner works on the list sorted by plane where the device planner would (pick_window): its slots' TU indices then refer to
-         * the sorted records, which are uploaded next to the schedule */
-        std::vector<ffhip_hevc_tu> h_sorted;
-        if (big_list) (void)pick_window(h_tus, n_tus, pw, ph, we ? atoi(we) : FFHIP_HEVC_INTRA_WINDOW_LOG2, false, &by_plane); /* (the first answer came from a sample) */
-        if (by_plane) sort_by_plane(h_tus, n_tus, h_sorted, nullptr);
-        if (plan_with_window_search(by_plane ? h_sorted.data() : h_tus, n_tus, pw, ph, we ? atoi(we) : FFHIP_HEVC_INTRA_WINDOW_LOG2, plan, &host_wl, ja.boff)) {
-            /* device image: sched | groups | wait | ctrl[CTRL_HDR] + one done flag per TU */
-            const size_t w_sched = plan.sched.size() * 4, w_groups = plan.groups.size() * 4, w_wait = plan.wait.size();
-            const size_t w_ctrl = CTRL_HDR + (size_t)n_tus;
-            const size_t o_groups = w_sched, o_wait = o_groups + w_groups, o_ctrl = (o_wait + w_wait + 3) & ~(size_t)3;
-            const size_t w_sorted = by_plane ? 8 * (size_t)n_tus + 16 : 0;
-            FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO); /* the work buffer may still be in use by an earlier call */
-            uint32_t *g_work = ffhip_scratch(scratch_kind, stream, o_ctrl + w_ctrl + 4 + w_jt + w_desc + w_sorted);
-            if (!g_work) return FFHIP_ENOMEM;
-            uint32_t *const jt_words = g_work + ((o_ctrl + w_ctrl + 3) & ~(size_t)3);
-            if (by_plane) {
-                uint32_t *ps = jt_words + w_jt + w_desc + 4;
-                ps += (8 - (((uintptr_t)ps >> 2) & 7)) & 7;
-                FFHIP_CHECK(hipMemcpy(ps, h_sorted.data(), (size_t)n_tus * sizeof(ffhip_hevc_tu), hipMemcpyHostToDevice), FFHIP_EIO);
-                list = (const ffhip_hevc_tu *)ps;
-                a.tus = list;
-            }
-            { const int jrc = enqueue_jtable(jt_words, false); if (jrc) return jrc; }
-            FFHIP_CHECK(hipMemcpy(g_work, plan.sched.data(), w_sched * 4, hipMemcpyHostToDevice), FFHIP_EIO);
-            FFHIP_CHECK(hipMemcpy(g_work + o_groups, plan.groups.data(), w_groups * 4, hipMemcpyHostToDevice), FFHIP_EIO);
-            FFHIP_CHECK(hipMemcpy(g_work + o_wait, plan.wait.data(), w_wait * 4, hipMemcpyHostToDevice), FFHIP_EIO);
-            FFHIP_CHECK(hipMemsetAsync(g_work + o_ctrl, 0, w_ctrl * 4, st), FFHIP_EIO);
-            a.sched = (const u32x4 *)g_work;
-            a.groups = (const u32x4 *)(g_work + o_groups);
-            a.wait_idx = g_work + o_wait;
-            a.ctrl = g_work + o_ctrl;
-            g_last_plan_result = nullptr;
-            a.ctrl_ticket = (uint32_t)((32 - (((uintptr_t)a.ctrl >> 2) & 31)) & 31); a.ctrl_abort = a.ctrl_ticket + 32 * 9;
-            a.async_err = async_err;
-            a.n_groups = (int)plan.groups.size();
-            {
-                const int cs = (pw[1] > 0 && pw[1] * 2 <= pw[0] + 1) ? 1 : 0;
-                const int win[3] = {host_wl, host_wl - cs, host_wl - cs};
-                enqueue_programs(jt_words + w_jt, win, (size_t)n_tus, st);
-            }
-            const unsigned wgs = (unsigned)std::min<size_t>(plan.groups.size(), max_waves); /* one wave each; waves loop over tickets */
-            a.tp_width = 0;
-            hipLaunchKernelGGL((k_hevc_intra_groups<2, 64>), dim3(wgs), dim3(64), 0, st, a);
-            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-            return FFHIP_OK;
-        }
+        if (!(pe && !strcmp(pe, "host")) && dev_ok) return recon_device_planned(c, dev_wl, by_plane);
+        host_wl = we ? atoi(we) : FFHIP_HEVC_INTRA_WINDOW_LOG2;
     }
-
-    if (!validate_fully()) return FFHIP_EINVAL;
-    if (roles && st == roles->plan) {
-        FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-        st = roles->groups;
+    if (!validate_fully(c)) return FFHIP_EINVAL; /* the host planner and the levels form walk every record */
+    if (c.st != c.gst) { /* ... and run in line on the caller's stream */
+        FFHIP_CHECK(hipStreamSynchronize(c.st), FFHIP_EIO);
+        c.st = c.gst;
     }
-    build_levels();
-    std::vector<uint32_t> flat;
-    flat.reserve((size_t)n_tus);
-    for (auto &l : lists) flat.insert(flat.end(), l.begin(), l.end());
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-    uint32_t *g_work = ffhip_scratch(scratch_kind, stream, (size_t)n_tus);
-    if (!g_work) return FFHIP_ENOMEM;
-    FFHIP_CHECK(hipMemcpy(g_work, flat.data(), flat.size() * sizeof(uint32_t), hipMemcpyHostToDevice), FFHIP_EIO);
-    size_t off = 0;
-    for (auto &l : lists) {
-        a.work = g_work + off;
-        a.count = (int)l.size();
-        hipLaunchKernelGGL(k_hevc_intra, dim3((unsigned)((a.count + 3) / 4)), dim3(256), 0, st, a);
-        off += l.size();
+    if (grouped) {
+        const int hrc = recon_host_planned(c, host_wl, by_plane);
+        if (hrc != 1) return hrc;
     }
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    return FFHIP_OK;
+    return recon_levels(c);
 }
 
 extern "C" int ffhip_hevc_intra_recon(const ffhip_hevc_tu *h_tus, const ffhip_hevc_tu *d_tus, long long n_tus,
@@ -2379,15 +2403,15 @@ extern "C" int ffhip_hevc_intra_recon(const ffhip_hevc_tu *h_tus, const ffhip_he
                                       int width_y, int height_y, int y_stride, int width_c, int height_c,
                                       int uv_stride, int bitdepth_y, int bitdepth_c, void *stream)
 {
-    return intra_recon_impl(h_tus, d_tus, n_tus, d_residual, d_y, d_cb, d_cr, width_y, height_y, y_stride, width_c, height_c, uv_stride, bitdepth_y, bitdepth_c, stream, nullptr);
+    return intra_recon_impl(h_tus, d_tus, n_tus, d_residual, d_y, d_cb, d_cr, width_y, height_y, y_stride, width_c, height_c, uv_stride, bitdepth_y, bitdepth_c, stream,
+                            (hipStream_t)stream, nullptr, SCRATCH_HEVC_INTRA);
 }
 
 /* The tile loop of a HEIF grid (format/heif.c:297-309: decode one tile after the other, no dependency between tiles) as ONE call over the
- * concatenated lists of independent pictures that share one plane set -- and as a PIPELINE: the list is cut at tile boundaries into up to four
- * chunks of about equal size; the pre-pass of chunk k + 1 (validation, planner, substitution table, per-pixel programs: a third of an
- * eight-picture call's span when it ran in front of the one grouped kernel) runs on streams of the library's own while chunk k reconstructs, and
- * the chunks' grouped kernels run on two streams in turn so that one chunk's start fills the other's tail.  What makes that legal is the
- * caller's word that tiles never reference each other; the results are those of ffhip_hevc_intra_recon on the whole list. */
+ * concatenated lists of independent pictures that share one plane set, with the pre-pass (validation, planner, substitution table, per-pixel
+ * programs) on a stream of the library's own, next to what the caller's stream still holds.  The results are those of ffhip_hevc_intra_recon
+ * on the whole list.  (Cutting the list at tile boundaries into chunks whose pre-passes and grouped kernels overlapped was built and measured
+ * slower: DESIGN.md 4.7 "Round 5".) */
 /* Who used a one-chunk scratch last: the scratch belongs to (kind, device, CALLER's stream), so its guard does too (FfhipTileGuard, in the stream's
  * entry of the library's registry).  (Kept per calling thread until round 6: a thread that alternated between two streams, or two threads on one
  * stream, could let a pre-pass rewrite a schedule the grouped kernel of another call was still reading.)  NULL when its events could not be made. */
@@ -2414,92 +2438,30 @@ extern "C" int ffhip_hevc_intra_recon_tiles(const ffhip_hevc_tu *h_tus, const ff
     for (int k = 0; k < n_tiles; k++)
         if (tile_first[k] < (k ? tile_first[k - 1] : 0) || tile_first[k] > n_tus) return FFHIP_EINVAL;
     if (n_tiles > 0 && tile_first[0] != 0) return FFHIP_EINVAL;
-    /* chunks (FFHIP_HEVC_TILE_CHUNKS=2..4; default 1: see below), cut at the tile boundaries nearest to equal shares */
-    const char *ce = FFHIP_ENV("FFHIP_HEVC_TILE_CHUNKS");
-    int want = ce ? std::max(1, std::min(4, atoi(ce))) : 1;
-    long long cut[5] = {0, n_tus, n_tus, n_tus, n_tus};
-    int chunks = 1;
-    if (n_tiles > 1 && want > 1) {
-        int ti = 1;
-        for (int c = 1; c < want; c++) {
-            const long long target = n_tus * c / want;
-            while (ti < n_tiles && tile_first[ti] < target) ti++;
-            if (ti >= n_tiles) break;
-            /* the boundary at or behind the target, or the one in front of it when that is nearer */
-            long long at = tile_first[ti];
-            if (ti > 1 && target - tile_first[ti - 1] < at - target && tile_first[ti - 1] > cut[chunks - 1]) at = tile_first[ti - 1];
-            if (at <= cut[chunks - 1] || at >= n_tus) continue;
-            cut[chunks++] = at;
-        }
-        cut[chunks] = n_tus;
-    }
     FfhipPipe pipe;
     const char *early_e = FFHIP_ENV("FFHIP_HEVC_TILE_EARLY");
     const bool early = !(early_e && early_e[0] == '0');
-    if ((chunks == 1 && !early) || !ffhip_have_device() || ffhip_pipe_streams_get(&pipe) != FFHIP_OK)
-        return intra_recon_impl(h_tus, d_tus, n_tus, d_residual, d_y, d_cb, d_cr, width_y, height_y, y_stride, width_c, height_c, uv_stride, bitdepth_y, bitdepth_c, stream, nullptr);
-    /* The library's pre-pass stream may not touch a pipeline scratch (schedule, tables) before the grouped kernel of the call that used it last has
-     * finished with it: an event recorded behind every call, waited for in front of the next call that takes the same scratch.  The one-chunk form
-     * alternates between TWO scratches, so the pre-pass of call n + 1 only waits for call n - 1 and runs next to the tail of call n's grouped kernel
-     * (whose waves leave as the wavefront narrows), the colour conversion behind it and the next residual batches. */
-    if (chunks == 1) {
-        FfhipTileGuard *const guard = tile_guard_for(stream);
-        if (!guard) return FFHIP_EIO;
-        std::lock_guard<std::mutex> turn(guard->turn);
-        /* ONE chunk -- the default: cutting the list does not pay (below) --, but the pre-pass does not wait for `stream`: it reads the TU list alone,
-         * so it runs while the stream is still busy with what the caller enqueued in front of this call -- the residual batches of this picture, the
-         * colour conversion of the picture before.  (d_tus must be COMPLETE when the call is made: see the header.) */
-        const char *db = FFHIP_ENV("FFHIP_HEVC_TILE_SCRATCHES");
-        const unsigned par = (db && db[0] == '1') ? 0u : (guard->parity++ & 1u);
-        IntraRoles roles;
-        roles.plan = (hipStream_t)pipe.plan; roles.groups = (hipStream_t)stream; roles.plan_done = (hipEvent_t)pipe.ev[2];
-        roles.scratch_kind = SCRATCH_HEVC_TILES_ONE + (int)par; roles.jt_desc = nullptr; roles.big_call = n_tus >= (1LL << 17);
-        /* (with one scratch: the stream's call before; with two: the one before that) */
-        if (guard->recorded[par]) FFHIP_CHECK(hipStreamWaitEvent(roles.plan, guard->ev[par], 0), FFHIP_EIO);
-        const int rc1 = intra_recon_impl(h_tus, d_tus, n_tus, d_residual, d_y, d_cb, d_cr, width_y, height_y, y_stride, width_c, height_c, uv_stride, bitdepth_y, bitdepth_c, stream,
-                                         &roles);
-        if (hipEventRecord(guard->ev[par], (hipStream_t)stream) == hipSuccess) guard->recorded[par] = true;
-        else { (void)hipGetLastError(); (void)hipStreamSynchronize((hipStream_t)stream); guard->recorded[par] = false; }
-        return rc1;
-    }
-    if (!h_tus || !d_tus || !d_y || width_y <= 0 || height_y <= 0) return FFHIP_EINVAL;
-    /* the tables indexed by position in the planes, shared by the chunks: the substitution table (JT_STRIDE bytes per 4x4 block) and the per-pixel
-     * program words (8 bytes per sample) -- laid out as intra_recon_impl lays them out behind its own scratch */
-    const bool chroma = d_cb && d_cr;
-    size_t jt_blocks = 0, desc_px = 0;
-    for (int c = 0; c < 3; c++) {
-        const int w = c == 0 ? width_y : (chroma ? width_c : 0), h = c == 0 ? height_y : height_c;
-        if (w > 0) { jt_blocks += (size_t)((w + 3) / 4) * (size_t)((h + 3) / 4); desc_px += (size_t)w * (size_t)h; }
-    }
-    const size_t w_jt = (jt_blocks * JT_STRIDE + 256 + 3) / 4, w_desc = desc_px * 2 + 2;
-    uint32_t *jt_desc = ffhip_scratch(SCRATCH_HEVC_TILES_JT, stream, w_jt + w_desc + 16);
-    if (!jt_desc) return FFHIP_ENOMEM;
-    hipStream_t st = (hipStream_t)stream, s_plan = (hipStream_t)pipe.plan, s_g2 = (hipStream_t)pipe.groups2;
-    hipEvent_t ev_in = (hipEvent_t)pipe.ev[0], ev_g2 = (hipEvent_t)pipe.ev[1];
-    /* (measured on the eight-picture grid, profiles/r5_hevc_tiles_timeline_8x4.txt: a quarter of the tiles is a grouped kernel of 0.6 ms -- the length
-     * of a tile's dependency chain -- where the whole list's is 1.73, and the grouped kernel's waves hold all of their SIMDs' registers, so the next
-     * chunk's pre-pass does not start before they leave: 3.5 ms against 2.6 for the one launch; with two chunks, or with a third or half of the wave
-     * slots left free, 2.65 - 3.8.  The cut stays as a tested switch; the default is one chunk.) */
-    /* the library's streams start behind what the caller's holds (the residuals) */
-    FFHIP_CHECK(hipEventRecord(ev_in, st), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamWaitEvent(s_plan, ev_in, 0), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamWaitEvent(s_g2, ev_in, 0), FFHIP_EIO);
-    int rc = FFHIP_OK;
-    for (int k = 0; k < chunks && rc == FFHIP_OK; k++) {
-        IntraRoles roles;
-        roles.plan = s_plan;
-        roles.groups = (k & 1) ? s_g2 : st;
-        roles.plan_done = (hipEvent_t)pipe.ev[2 + k];
-        roles.scratch_kind = SCRATCH_HEVC_TILES_CHUNK + k;
-        roles.jt_desc = jt_desc;
-        roles.big_call = n_tus >= (1LL << 17);
-        rc = intra_recon_impl(h_tus + cut[k], d_tus + cut[k], cut[k + 1] - cut[k], d_residual, d_y, d_cb, d_cr, width_y, height_y, y_stride, width_c, height_c, uv_stride,
-                              bitdepth_y, bitdepth_c, stream, &roles);
-    }
-    /* the caller's stream continues behind everything, whatever happened */
-    if (hipEventRecord(ev_g2, s_g2) != hipSuccess || hipStreamWaitEvent(st, ev_g2, 0) != hipSuccess) return FFHIP_EIO;
-    if (hipEventRecord(ev_in, s_plan) != hipSuccess || hipStreamWaitEvent(st, ev_in, 0) != hipSuccess) return FFHIP_EIO;
-    /* (the chunked form's streams start behind `stream`, which the call before has joined everything into) */
+    if (!early || !ffhip_have_device() || ffhip_pipe_streams_get(&pipe) != FFHIP_OK)
+        return ffhip_hevc_intra_recon(h_tus, d_tus, n_tus, d_residual, d_y, d_cb, d_cr, width_y, height_y, y_stride, width_c, height_c, uv_stride, bitdepth_y, bitdepth_c, stream);
+    /* The library's pre-pass stream may not touch a scratch (schedule, tables) before the grouped kernel of the call that used it last has finished
+     * with it: an event recorded behind every call, waited for in front of the next call that takes the same scratch.  Calls alternate between TWO
+     * scratches, so the pre-pass of call n + 1 only waits for call n - 1 and runs next to the tail of call n's grouped kernel (whose waves leave as
+     * the wavefront narrows), the colour conversion behind it and the next residual batches. */
+    FfhipTileGuard *const guard = tile_guard_for(stream);
+    if (!guard) return FFHIP_EIO;
+    std::lock_guard<std::mutex> turn(guard->turn);
+    /* The pre-pass does not wait for `stream`: it reads the TU list alone, so it runs while the stream is still busy with what the caller enqueued
+     * in front of this call -- the residual batches of this picture, the colour conversion of the picture before.  (d_tus must be COMPLETE when
+     * the call is made: see the header.) */
+    const char *db = FFHIP_ENV("FFHIP_HEVC_TILE_SCRATCHES");
+    const unsigned par = (db && db[0] == '1') ? 0u : (guard->parity++ & 1u);
+    const hipStream_t pre = (hipStream_t)pipe.plan;
+    /* (with one scratch: the stream's call before; with two: the one before that) */
+    if (guard->recorded[par]) FFHIP_CHECK(hipStreamWaitEvent(pre, guard->ev[par], 0), FFHIP_EIO);
+    const int rc = intra_recon_impl(h_tus, d_tus, n_tus, d_residual, d_y, d_cb, d_cr, width_y, height_y, y_stride, width_c, height_c, uv_stride, bitdepth_y, bitdepth_c, stream,
+                                    pre, (hipEvent_t)pipe.plan_done, SCRATCH_HEVC_TILES_ONE + (int)par);
+    if (hipEventRecord(guard->ev[par], (hipStream_t)stream) == hipSuccess) guard->recorded[par] = true;
+    else { (void)hipGetLastError(); (void)hipStreamSynchronize((hipStream_t)stream); guard->recorded[par] = false; }
     return rc;
 }
 

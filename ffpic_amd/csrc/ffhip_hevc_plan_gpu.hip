@@ -31,53 +31,6 @@
  */
 #include "ffhip_internal.h"
 
-struct PlanArgs {
-    const ffhip_hevc_tu *tus;
-    uint32_t n;
-    int pw[3], ph[3], bw[3], gw[3], wl[3];
-    uint32_t owner_off[3], win_off[3]; /* per plane: start inside owner[] / win_run[] */
-    int32_t *owner;        /* TU index per 4x4 block, -1 = none                     */
-    uint32_t *win_run;     /* run that claimed a window, ~0 = none                  */
-    uint32_t *start;       /* 1 where a run starts; after the scan: runs before me  */
-    uint32_t *runid;       /* inclusive scan of start, minus one                    */
-    uint32_t *wcount;      /* wait entries per TU; after the scan: first entry      */
-    uint32_t *wbegin;
-    uint8_t *flags;        /* bit 0 signal, bit 1 tile_ok                           */
-    uint32_t *gstart;      /* TU index where run r starts; [n_runs] = n             */
-    uint32_t *wait_idx;
-    u32x4 *sched, *groups;
-    uint32_t *result;      /* [0] fail, [1] number of runs, [2] wait entries, [3] no wavefront keys, [4] the widest wavefront:
-                              the largest number of runs that share a dependency depth, [5] log2 of the luma window, [6] a record failed
-                              k_hevc_check_tus, [7] the list was sorted by plane (k_part_*) */
-    uint32_t wait_cap;     /* words reserved for wait_idx                           */
-    uint32_t wsub_n;       /* slices in use: a power of two, at most PLAN_WSUB, never more than blocks of 256 TUs */
-    uint32_t *wsub;        /* PLAN_WSUB counters, one per 128-byte line: wait entries handed out of slice r of wait_idx */
-    uint32_t *cell_claim;  /* per 64x64-luma cell and plane: TU that opened it, ~0 = none (is the CTB 64?) */
-    uint32_t *cell_edges;  /* bit 0 left, 1 above, 2 above-left, 3 above-right: cells this cell's TUs read */
-    uint32_t *cell_depth;  /* longest chain of such edges ending here: the wavefront index of the cell     */
-    uint32_t n_cells, cgh[3];
-    uint32_t cell_off[3], cgw[3];
-    int cshift[3];         /* log2 of the cell size in samples of the plane          */
-    uint32_t *rank_of;     /* ticket of a run                                          */
-    uint32_t *blk_tot;     /* per block of 256 TUs: run starts                                        */
-    uint32_t *blk_pre;     /* its exclusive scan: starts in the blocks before                         */
-    uint32_t *cell_nruns;  /* runs per cell                                            */
-    uint32_t *cell_base;   /* first ticket of the cell's runs                          */
-    uint32_t *hist;        /* [depths][shards] runs per (depth, shard)                 */
-    uint32_t *hist_pre;    /* its exclusive scan: first ticket of the pair             */
-    uint32_t *fill;        /* [depths][shards] tickets of the pair handed out so far   */
-    uint32_t depths;       /* a bound on the depths: a chain ending at cell (x, y) has at most x + 2y edges */
-    float stripe_scale[3]; /* 2^shard_log2 / cells of the plane */
-    uint32_t shard_log2;   /* the counters of one depth are spread over 2^shard_log2 words, picked by the cell's block: a grid of tiles has
-                              two dozen distinct depths for its 200 000 cells, and that many atomic adds on two dozen words took 0.4 ms */
-    /* the list sorted by plane (k_part_*): the caller's records, the copy the planner and everything behind it work on, and per
-     * (plane, block of 256 records) the records of that plane in the block / in front of it in the sorted list */
-    const ffhip_hevc_tu *raw;
-    ffhip_hevc_tu *sorted;
-    uint32_t *part_tot, *part_pre;
-    uint32_t part_nb;
-};
-
 /* ---- scans: a shuffle scan inside the wave, the waves' totals through LDS ---- */
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, const int lane)
 {
@@ -892,11 +845,6 @@ __global__ __launch_bounds__(256) void k_hevc_check_tus(const ffhip_hevc_tu *tus
 /* Layout of the device scratch the caller provides (32-bit words).  sched / groups / wait_idx sit where the grouped
  * kernel expects to be told they are; everything else is planner-private.  ONE function lays the scratch out, for the size
  * query (base = NULL: only the word count matters) and for the launch. */
-struct PlanLayout {
-    size_t words, blocks, wins, cells, n_blocks, wait_cap;
-    uint32_t *zero_cells; /* cell_edges | cell_nruns | hist | fill, adjacent: cleared together */
-    size_t zero_cells_words;
-};
 static PlanLayout plan_layout(PlanArgs &a, uint32_t *base, const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3])
 {
     PlanLayout L = {};
@@ -969,135 +917,86 @@ static PlanLayout plan_layout(PlanArgs &a, uint32_t *base, const ffhip_hevc_tu *
     L.words = (size_t)(p - base) + 16;
     return L;
 }
-extern "C" size_t ffhip_hevc_plan_gpu_words(long long n_tus, const int pw[3], const int ph[3], const int wl[3])
+size_t ffhip_hevc_plan_gpu_words(long long n_tus, const int pw[3], const int ph[3], const int wl[3])
 {
     PlanArgs a;
     return plan_layout(a, nullptr, nullptr, n_tus, pw, ph, wl).words;
 }
 
-/* Returns 0 when the plan is in place (n_groups, n_wait filled), 1 when the list needs the host planner.
- * With d_result != NULL nothing is waited for: the plan is only ENQUEUED, *d_result points at the device words
- * {refused, number of groups, wait entries} the grouped kernel reads for itself (with *wait_cap, the reservation the
- * wait entries must fit), *n_groups is left alone and the return value is 0. */
-extern "C" int ffhip_hevc_plan_gpu_checked(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3],
-                                           uint32_t *scratch, hipStream_t st, const u32x4 **sched, const u32x4 **groups, const uint32_t **wait_idx,
-                                           int *n_groups, const uint32_t **d_result, uint32_t *wait_cap_out, const int *check /* NULL, or {chroma_ok,
-                                           have_residual} */, int *async_err, const FfhipPlanHooks *hooks, uint32_t *also_zero, size_t also_zero_words);
-extern "C" int ffhip_hevc_plan_gpu(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3],
-                                   uint32_t *scratch, hipStream_t st, const u32x4 **sched, const u32x4 **groups, const uint32_t **wait_idx,
-                                   int *n_groups, const uint32_t **d_result, uint32_t *wait_cap_out)
+/* The stages of FfhipHevcPlan (ffhip_internal.h).  owner = -1, win_run = ~0 (adjacent); flags, result = 0 (adjacent); cell_claim = ~0;
+ * cell_edges, cell_nruns, hist, fill = 0 (adjacent: OR-ed and added into; every cell's depth is written by the sweep): ONE launch for the four
+ * regions and the caller's -- as four memsets they were four more kernel boundaries in front of a chain of small kernels */
+void FfhipHevcPlan::begin(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3], uint32_t *scratch, hipStream_t stream,
+                          uint32_t *also_zero, size_t also_zero_words, const int *check, int *async_err)
 {
-    return ffhip_hevc_plan_gpu_checked(d_tus, n_tus, pw, ph, wl, scratch, st, sched, groups, wait_idx, n_groups, d_result, wait_cap_out, nullptr, nullptr,
-                                       nullptr, nullptr, 0);
-}
-/* ... with the list's validation as the first kernel behind the scratch's reset (check != NULL), a hook that runs once that kernel is
- * enqueued: what the caller starts from there (the substitution table on a side stream) may rely on result[6], handed to the hook; and a
- * second hook behind k_plan_count, when the per-TU flags (who publishes, who may use the LDS tile) and wait counts are final: the per-pixel
- * programs need nothing else of the schedule and can be built next to the ticket kernels (flags, wait counts, result words) */
-extern "C" int ffhip_hevc_plan_gpu_checked(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3],
-                                           uint32_t *scratch, hipStream_t st, const u32x4 **sched, const u32x4 **groups, const uint32_t **wait_idx,
-                                           int *n_groups, const uint32_t **d_result, uint32_t *wait_cap_out, const int *check, int *async_err,
-                                           const FfhipPlanHooks *hooks, uint32_t *also_zero /* a region of the
-                                           caller's (the grouped kernel's ticket counter and done flags), cleared by the same launch */, size_t also_zero_words)
-{
-    PlanArgs a;
-    const PlanLayout Lo = plan_layout(a, scratch, d_tus, n_tus, pw, ph, wl);
-    const size_t n = (size_t)n_tus, blocks = Lo.blocks, wins = Lo.wins, cells = Lo.cells, wait_cap = Lo.wait_cap;
-    /* owner = -1, win_run = ~0 (adjacent); flags, result = 0 (adjacent); cell_claim = ~0; cell_edges, cell_nruns, hist, fill = 0 (adjacent:
-     * OR-ed and added into; every cell's depth is written by the sweep): ONE launch for the four regions -- as four memsets they were four
-     * more kernel boundaries in front of a chain of small kernels */
+    st = stream;
+    L = plan_layout(a, scratch, d_tus, n_tus, pw, ph, wl);
+    const size_t n = (size_t)n_tus;
     {
         PlanInit in;
-        in.p[0] = (uint32_t *)a.owner; in.words[0] = blocks + wins; in.value[0] = ~0u;
+        in.p[0] = (uint32_t *)a.owner; in.words[0] = L.blocks + L.wins; in.value[0] = ~0u;
         in.p[1] = (uint32_t *)a.flags; in.words[1] = (n + 3) / 4 + 4 + 16 + 32 * PLAN_WSUB + 32; in.value[1] = 0u;
-        in.p[2] = a.cell_claim; in.words[2] = cells; in.value[2] = ~0u;
-        in.p[3] = Lo.zero_cells; in.words[3] = Lo.zero_cells_words; in.value[3] = 0u;
+        in.p[2] = a.cell_claim; in.words[2] = L.cells; in.value[2] = ~0u;
+        in.p[3] = L.zero_cells; in.words[3] = L.zero_cells_words; in.value[3] = 0u;
         in.p[4] = also_zero; in.words[4] = also_zero ? also_zero_words : 0; in.value[4] = 0u;
         size_t most = 0;
         for (int r = 0; r < 5; r++) most = in.words[r] > most ? in.words[r] : most;
         const size_t wg = (most / 4 + 255) / 256 + 1;
         hipLaunchKernelGGL(k_plan_init, dim3((unsigned)(wg > 4096 ? 4096 : wg), also_zero ? 5 : 4), dim3(256), 0, st, in);
     }
-    const unsigned grid = (unsigned)Lo.n_blocks;
     if (check && async_err) {
+        const unsigned grid = (unsigned)L.n_blocks;
         PlanCheck k;
         for (int c = 0; c < 3; c++) { k.pw[c] = pw[c]; k.ph[c] = ph[c]; }
         k.chroma_ok = check[0]; k.have_residual = check[1]; k.async_err = async_err;
         hipLaunchKernelGGL(k_hevc_check_tus, dim3(grid > 2048 ? 2048u : grid), dim3(256), 0, st, d_tus, (uint32_t)n, k, a.result);
     }
-    if (hooks && hooks->after_check) {
-        const int hrc = hooks->after_check(hooks->ctx, a.result + 6);
-        if (hrc) return hrc;
-    }
-    if (hooks && hooks->by_plane) { /* the list sorted by plane (k_part_*): from here on `a.tus` is the sorted copy */
-        hipLaunchKernelGGL(k_part_count, dim3(grid), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_plan_scan, dim3((unsigned)((3 * Lo.n_blocks + 4095) / 4096)), dim3(256), 0, st, (const uint32_t *)a.part_tot, a.part_pre, (uint32_t)(3 * Lo.n_blocks),
-                           (uint32_t *)nullptr, 0u, (const uint32_t *)(a.result + 6));
-        hipLaunchKernelGGL(k_part_scatter, dim3(grid), dim3(256), 0, st, a);
-        a.tus = a.sorted;
-    }
-    if (hooks && hooks->tus_used) *hooks->tus_used = a.tus;
-    hipLaunchKernelGGL(k_plan_owner, dim3(grid), dim3(256), 0, st, a);
-    /* the depth sweep needs the cells' edges, which k_plan_owner has just left: three workgroups walking diagonals for 50 - 130 us -- next to
-     * k_plan_count on a stream of the caller's where there is one, in front of the ticket kernels otherwise */
-    auto enqueue_sweep = [&](hipStream_t ss) {
-        uint32_t max_gh = 0;
-        for (int c = 0; c < 3; c++) max_gh = a.cgh[c] > max_gh ? a.cgh[c] : max_gh;
-        const unsigned threads = max_gh >= 1024 ? 1024u : (unsigned)((max_gh + 63) / 64 * 64);
-        bool fast = max_gh <= DEPTH_ROWS;
-        for (int c = 0; c < 3; c++) fast = fast && (size_t)a.cgw[c] * a.cgh[c] <= CELLS_LDS;
-        uint32_t max_gw = 0;
-        for (int c = 0; c < 3; c++) max_gw = a.cgw[c] > max_gw ? a.cgw[c] : max_gw;
-        if (max_gw <= 1024 && fast && !FFHIP_ENV("FFHIP_HEVC_DEPTH_DIAGONALS")) /* row by row: planes of up to 65 536 samples a line whose edge bits fit the LDS */
-            hipLaunchKernelGGL(k_plan_cell_depth_rows, dim3(3), dim3(1024), 0, ss, a); /* (1024 threads fetch the edge bits; the waves without columns leave then) */
-        else if (fast) hipLaunchKernelGGL(k_plan_cell_depth<true>, dim3(3), dim3(1024), 0, ss, a);
-        else hipLaunchKernelGGL(k_plan_cell_depth<false>, dim3(3), dim3(threads ? threads : 64u), 0, ss, a);
-    };
-    hipStream_t ts = st; /* the stream of the sweep, the ticket kernels and k_plan_emit */
-    if (hooks && hooks->ticket_stream) {
-        void *ss = hooks->ticket_stream(hooks->ctx);
-        if (ss) {
-            ts = (hipStream_t)ss;
-            enqueue_sweep(ts);
-        }
-    }
-    hipLaunchKernelGGL(k_plan_scan, dim3((unsigned)((Lo.n_blocks + 4095) / 4096)), dim3(256), 0, st, (const uint32_t *)a.blk_tot, a.blk_pre, (uint32_t)Lo.n_blocks, (uint32_t *)nullptr, 0u,
+}
+void FfhipHevcPlan::partition()
+{
+    const unsigned grid = (unsigned)L.n_blocks;
+    hipLaunchKernelGGL(k_part_count, dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_plan_scan, dim3((unsigned)((3 * L.n_blocks + 4095) / 4096)), dim3(256), 0, st, (const uint32_t *)a.part_tot, a.part_pre, (uint32_t)(3 * L.n_blocks),
+                       (uint32_t *)nullptr, 0u, (const uint32_t *)(a.result + 6));
+    hipLaunchKernelGGL(k_part_scatter, dim3(grid), dim3(256), 0, st, a);
+    a.tus = a.sorted;
+}
+void FfhipHevcPlan::owner() const
+{
+    hipLaunchKernelGGL(k_plan_owner, dim3((unsigned)L.n_blocks), dim3(256), 0, st, a);
+}
+/* three workgroups walking diagonals for 50 - 130 us */
+void FfhipHevcPlan::sweep(hipStream_t s) const
+{
+    uint32_t max_gh = 0;
+    for (int c = 0; c < 3; c++) max_gh = a.cgh[c] > max_gh ? a.cgh[c] : max_gh;
+    const unsigned threads = max_gh >= 1024 ? 1024u : (unsigned)((max_gh + 63) / 64 * 64);
+    bool fast = max_gh <= DEPTH_ROWS;
+    for (int c = 0; c < 3; c++) fast = fast && (size_t)a.cgw[c] * a.cgh[c] <= CELLS_LDS;
+    uint32_t max_gw = 0;
+    for (int c = 0; c < 3; c++) max_gw = a.cgw[c] > max_gw ? a.cgw[c] : max_gw;
+    if (max_gw <= 1024 && fast && !FFHIP_ENV("FFHIP_HEVC_DEPTH_DIAGONALS")) /* row by row: planes of up to 65 536 samples a line whose edge bits fit the LDS */
+        hipLaunchKernelGGL(k_plan_cell_depth_rows, dim3(3), dim3(1024), 0, s, a); /* (1024 threads fetch the edge bits; the waves without columns leave then) */
+    else if (fast) hipLaunchKernelGGL(k_plan_cell_depth<true>, dim3(3), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL(k_plan_cell_depth<false>, dim3(3), dim3(threads ? threads : 64u), 0, s, a);
+}
+void FfhipHevcPlan::count() const
+{
+    const unsigned grid = (unsigned)L.n_blocks;
+    hipLaunchKernelGGL(k_plan_scan, dim3((unsigned)((L.n_blocks + 4095) / 4096)), dim3(256), 0, st, (const uint32_t *)a.blk_tot, a.blk_pre, (uint32_t)L.n_blocks, (uint32_t *)nullptr, 0u,
                        (const uint32_t *)(a.result + 6));
     hipLaunchKernelGGL(k_plan_runid, dim3(grid), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_plan_count, dim3(grid), dim3(256), 0, st, a);
-    if (hooks && hooks->after_count) {
-        const int hrc = hooks->after_count(hooks->ctx, a.flags, a.wcount, a.result);
-        if (hrc) return hrc;
-    }
-    /* tickets: runs by (wavefront index of their cell, decode order).  The sweep: one diagonal per step, at most one cell per row of cells, a
-     * lane per row (k_plan_cell_depth) */
-    if (ts == st) enqueue_sweep(st);
-    else if (hooks->tickets_wait) { const int hrc = hooks->tickets_wait(hooks->ctx); if (hrc) return hrc; }
-    const size_t m = n < wins ? n : wins; /* runs <= windows, or the plan is refused (k_plan_count: a window with two runs) */
-    const unsigned cgrid = (unsigned)((cells + 255) / 256);
-    hipLaunchKernelGGL(k_plan_cell_hist, dim3(cgrid), dim3(256), 0, ts, a);
-    hipLaunchKernelGGL(k_plan_scan, dim3((unsigned)((((size_t)a.depths << a.shard_log2) + 4095) / 4096)), dim3(256), 0, ts, (const uint32_t *)a.hist, a.hist_pre,
+}
+/* runs by (wavefront index of their cell, decode order) */
+void FfhipHevcPlan::tickets(hipStream_t s) const
+{
+    const size_t m = (size_t)a.n < L.wins ? (size_t)a.n : L.wins; /* runs <= windows, or the plan is refused (k_plan_count: a window with two runs) */
+    const unsigned cgrid = (unsigned)((L.cells + 255) / 256);
+    hipLaunchKernelGGL(k_plan_cell_hist, dim3(cgrid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_plan_scan, dim3((unsigned)((((size_t)a.depths << a.shard_log2) + 4095) / 4096)), dim3(256), 0, s, (const uint32_t *)a.hist, a.hist_pre,
                        (uint32_t)(a.depths << a.shard_log2), a.result + 4, a.shard_log2, (const uint32_t *)(a.result + 3));
-    hipLaunchKernelGGL(k_plan_cell_base, dim3(cgrid), dim3(256), 0, ts, a);
-    hipLaunchKernelGGL(k_plan_rank, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ts, a, (uint32_t)m);
-    hipLaunchKernelGGL(k_plan_emit, dim3(grid), dim3(256), 0, ts, a, (uint32_t)m);
-    if (ts != st && hooks->tickets_enqueued) { const int hrc = hooks->tickets_enqueued(hooks->ctx); if (hrc) return hrc; }
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    if (d_result) {
-        *sched = a.sched;
-        *groups = a.groups;
-        *wait_idx = a.wait_idx;
-        *d_result = a.result;
-        if (wait_cap_out) *wait_cap_out = (uint32_t)wait_cap;
-        return 0;
-    }
-    uint32_t res[3] = {1, 0, 0};
-    FFHIP_CHECK(hipMemcpyAsync(res, a.result, sizeof res, hipMemcpyDeviceToHost, st), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-    if (res[0] || res[2] > wait_cap) return 1; /* not contiguous, too many pollers, or more wait entries than reserved */
-    *sched = a.sched;
-    *groups = a.groups;
-    *wait_idx = a.wait_idx;
-    *n_groups = (int)res[1];
-    return 0;
+    hipLaunchKernelGGL(k_plan_cell_base, dim3(cgrid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_plan_rank, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, a, (uint32_t)m);
+    hipLaunchKernelGGL(k_plan_emit, dim3((unsigned)L.n_blocks), dim3(256), 0, s, a, (uint32_t)m);
 }

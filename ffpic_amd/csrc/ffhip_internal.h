@@ -91,8 +91,6 @@ enum FfhipScratchKind {
     SCRATCH_JPEG_HOST = 6,
     SCRATCH_VP8_RETRY = 8,
     SCRATCH_VP8_FRAMES = 9,        /* .. + 1 */
-    SCRATCH_HEVC_TILES_JT = 20,
-    SCRATCH_HEVC_TILES_CHUNK = 21, /* .. + 3 */
     SCRATCH_HEVC_TILES_ONE = 25,   /* .. + 1 */
     SCRATCH_HUFF_SYNC = 30,        /* .. + FFHIP_HUFF_PARTS - 1 */
     SCRATCH_FILES_MIXED = 7,       /* ffhip_jpeg_decode_files_mixed_device: a class's planes and quantiser tables, the host decoder's pinned planes */
@@ -196,13 +194,11 @@ int ffhip_vp8_side_by_side_retry(void *stream); /* ffhip_vp8_lf.hip, for ffhip_s
 struct jpeg_hdr *ffhip_huff_hdr_records(size_t n); /* the calling thread's header records, room for at least n, kept between calls; NULL: no memory */
 
 /* the calling thread's side stream with its fork / join events (ffhip_state.hip: one set per thread and device) */
-struct FfhipSide { void *stream, *fork, *join, *mid, *aux; }; /* mid: a second point of the main stream the side stream may wait for; aux: a second
-                                                                point of the side stream the main stream may wait for */
+struct FfhipSide { void *stream, *fork, *join, *mid; }; /* mid: a second point of the main stream the side stream may wait for */
 extern "C" int ffhip_side_stream_get(FfhipSide *out);
-/* the calling thread's streams and events for a pipelined call (ffhip_hevc_intra_recon_tiles): a stream the chunks' pre-passes follow each other
- * on, a second stream for grouped kernels (the caller's is the first), events; same owner and lifetime as the side stream */
-#define FFHIP_PIPE_EVENTS 12
-struct FfhipPipe { void *plan, *groups2, *ev[FFHIP_PIPE_EVENTS]; };
+/* the calling thread's stream and event for the early pre-pass of ffhip_hevc_intra_recon_tiles: the stream the pre-passes follow each other on,
+ * the event the caller's stream waits for in front of the grouped kernel; same owner and lifetime as the side stream */
+struct FfhipPipe { void *plan, *plan_done; };
 extern "C" int ffhip_pipe_streams_get(FfhipPipe *out);
 
 /* ... and the device Huffman decoder's (ffhip_jpeg_entropy_batch_gpu): the copy stream its parts' bytes go up on, the second kernel stream, the
@@ -229,24 +225,79 @@ extern "C" int ffhip_huff_streams_get(FfhipHuffStreams *out);
 #define FFHIP_VP8_LF_CTRL_ABORT 32
 #define FFHIP_VP8_LF_CTRL_HDR 64
 
-/* What ffhip_hevc_intra_recon hangs into the device planner's chain of launches (ffhip_hevc_plan_gpu_checked): everything is optional.
- *   after_check       behind the list's validation kernel: start what depends on the TU list alone (the substitution table, side stream)
- *   ticket_stream     behind k_plan_owner: a stream, already waiting for that kernel, that takes the depth sweep NOW -- next to k_plan_count
- *                     -- and the ticket kernels and k_plan_emit later (NULL: everything in line on the planner's stream)
- *   after_count       behind k_plan_count: flags and wait counts are final (the per-pixel programs)
- *   tickets_wait      (ticket_stream given) make that stream wait for k_plan_count, in front of the ticket kernels
- *   tickets_enqueued  (ticket_stream given) the schedule's last kernel is on that stream: whoever reads the schedule waits for it
- *   by_plane          the list interleaves the planes inside a scheduling window (the reference's own order, coding/hevc.c:5013-5180): plan and
- *                     decode a stable partition of it by plane; *tus_used then points at that copy (in the planner's scratch) */
-struct FfhipPlanHooks {
-    void *ctx;
-    int (*after_check)(void *ctx, const unsigned *refused);
-    void *(*ticket_stream)(void *ctx);
-    int (*after_count)(void *ctx, const unsigned char *flags, const unsigned *wcount, const unsigned *result);
-    int (*tickets_wait)(void *ctx);
-    int (*tickets_enqueued)(void *ctx);
-    int by_plane;                       /* sort the list by plane in front of k_plan_owner (ffhip_hevc_plan_gpu.hip, k_part_*) */
-    const ffhip_hevc_tu **tus_used;     /* out, set before after_count runs: the records the schedule's TU indices refer to (the caller's, or the sorted copy) */
+/* The device planner (ffhip_hevc_plan_gpu.hip): its kernels' argument, where its scratch is (plan_layout) ... */
+struct PlanArgs {
+    const ffhip_hevc_tu *tus;
+    uint32_t n;
+    int pw[3], ph[3], bw[3], gw[3], wl[3];
+    uint32_t owner_off[3], win_off[3]; /* per plane: start inside owner[] / win_run[] */
+    int32_t *owner;        /* TU index per 4x4 block, -1 = none                     */
+    uint32_t *win_run;     /* run that claimed a window, ~0 = none                  */
+    uint32_t *start;       /* 1 where a run starts; after the scan: runs before me  */
+    uint32_t *runid;       /* inclusive scan of start, minus one                    */
+    uint32_t *wcount;      /* wait entries per TU; after the scan: first entry      */
+    uint32_t *wbegin;
+    uint8_t *flags;        /* bit 0 signal, bit 1 tile_ok                           */
+    uint32_t *gstart;      /* TU index where run r starts; [n_runs] = n             */
+    uint32_t *wait_idx;
+    u32x4 *sched, *groups;
+    uint32_t *result;      /* [0] fail, [1] number of runs, [2] wait entries, [3] no wavefront keys, [4] the widest wavefront:
+                              the largest number of runs that share a dependency depth, [5] log2 of the luma window, [6] a record failed
+                              k_hevc_check_tus, [7] the list was sorted by plane (k_part_*) */
+    uint32_t wait_cap;     /* words reserved for wait_idx                           */
+    uint32_t wsub_n;       /* slices in use: a power of two, at most PLAN_WSUB, never more than blocks of 256 TUs */
+    uint32_t *wsub;        /* PLAN_WSUB counters, one per 128-byte line: wait entries handed out of slice r of wait_idx */
+    uint32_t *cell_claim;  /* per 64x64-luma cell and plane: TU that opened it, ~0 = none (is the CTB 64?) */
+    uint32_t *cell_edges;  /* bit 0 left, 1 above, 2 above-left, 3 above-right: cells this cell's TUs read */
+    uint32_t *cell_depth;  /* longest chain of such edges ending here: the wavefront index of the cell     */
+    uint32_t n_cells, cgh[3];
+    uint32_t cell_off[3], cgw[3];
+    int cshift[3];         /* log2 of the cell size in samples of the plane          */
+    uint32_t *rank_of;     /* ticket of a run                                          */
+    uint32_t *blk_tot;     /* per block of 256 TUs: run starts                                        */
+    uint32_t *blk_pre;     /* its exclusive scan: starts in the blocks before                         */
+    uint32_t *cell_nruns;  /* runs per cell                                            */
+    uint32_t *cell_base;   /* first ticket of the cell's runs                          */
+    uint32_t *hist;        /* [depths][shards] runs per (depth, shard)                 */
+    uint32_t *hist_pre;    /* its exclusive scan: first ticket of the pair             */
+    uint32_t *fill;        /* [depths][shards] tickets of the pair handed out so far   */
+    uint32_t depths;       /* a bound on the depths: a chain ending at cell (x, y) has at most x + 2y edges */
+    float stripe_scale[3]; /* 2^shard_log2 / cells of the plane */
+    uint32_t shard_log2;   /* the counters of one depth are spread over 2^shard_log2 words, picked by the cell's block: a grid of tiles has
+                              two dozen distinct depths for its 200 000 cells, and that many atomic adds on two dozen words took 0.4 ms */
+    /* the list sorted by plane (k_part_*): the caller's records, the copy the planner and everything behind it work on, and per
+     * (plane, block of 256 records) the records of that plane in the block / in front of it in the sorted list */
+    const ffhip_hevc_tu *raw;
+    ffhip_hevc_tu *sorted;
+    uint32_t *part_tot, *part_pre;
+    uint32_t part_nb;
 };
+struct PlanLayout {
+    size_t words, blocks, wins, cells, n_blocks, wait_cap;
+    uint32_t *zero_cells; /* cell_edges | cell_nruns | hist | fill, adjacent: cleared together */
+    size_t zero_cells_words;
+};
+/* ... and the stages ffhip_hevc_intra_recon enqueues one after the other, with its own work between them (the substitution table, the
+ * per-pixel programs, the forks and joins of its side stream).  Everything goes to `st`, the stream given to begin(), but the stages that
+ * take a stream.  The schedule is only ENQUEUED: the grouped kernel reads the planner's verdict (a.result) for itself. */
+struct FfhipHevcPlan {
+    PlanArgs a; /* behind begin(): a.sched, a.groups, a.wait_idx, a.result, a.wait_cap (the outputs); behind count(): a.flags, a.wcount are final */
+    PlanLayout L;
+    hipStream_t st;
+    /* k_plan_init, which also clears `also_zero` (the grouped kernel's ticket counter and done flags), then -- check = {chroma_ok,
+     * have_residual} -- the list's validation, k_hevc_check_tus: refused() is set for a bad record */
+    void begin(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3], uint32_t *scratch, hipStream_t stream,
+               uint32_t *also_zero, size_t also_zero_words, const int *check, int *async_err);
+    const uint32_t *refused() const { return a.result + 6; }
+    /* k_part_*: a stable partition of the list by plane (for a list that interleaves the planes inside a scheduling window, the reference's
+     * own order, coding/hevc.c:5013-5180); from here on a.tus is that copy, in the planner's scratch: the records the schedule refers to */
+    void partition();
+    void owner() const;                /* k_plan_owner */
+    void sweep(hipStream_t s) const;   /* the depth sweep of the cells, behind owner() */
+    void count() const;                /* k_plan_scan, k_plan_runid, k_plan_count */
+    void tickets(hipStream_t s) const; /* k_plan_cell_hist, k_plan_scan, k_plan_cell_base, k_plan_rank, k_plan_emit: behind sweep() and count() */
+};
+/* 32-bit words of the scratch FfhipHevcPlan::begin lays out */
+size_t ffhip_hevc_plan_gpu_words(long long n_tus, const int pw[3], const int ph[3], const int wl[3]);
 
 #endif

@@ -141,11 +141,11 @@ template <int NS, int NE> struct Group {
     }
 };
 struct ThreadSet {
-    /* the side stream with fork, join, mid, aux: what runs there is the SHORT chain next to a large kernel of the caller's stream (the HEVC planner's
+    /* the side stream with fork, join, mid: what runs there is the SHORT chain next to a large kernel of the caller's stream (the HEVC planner's
      * ticket kernels next to the per-pixel programs: a few workgroups each, which otherwise queue behind thousands), or, in the VP8 side-by-side
      * call, a kernel whose share of the residency is its own -- hence the top priority */
-    Group<1, 4> side;
-    Group<2, FFHIP_PIPE_EVENTS> pipe;    /* plan, groups2 */
+    Group<1, 3> side;
+    Group<1, 1> pipe;                    /* plan; plan_done */
     Group<2, FFHIP_HUFF_PARTS + 4> huff; /* up, c2; the last two events time */
     void release() { side.release(); pipe.release(); huff.release(); }
 };
@@ -180,17 +180,16 @@ template <class G> G *thread_group(G ThreadSet::*which, bool top, int timed)
  * substitution table next to the planner's kernels) */
 extern "C" int ffhip_side_stream_get(FfhipSide *out)
 {
-    const auto *g = thread_group(&ThreadSet::side, true, 4);
+    const auto *g = thread_group(&ThreadSet::side, true, 3);
     if (!g) return FFHIP_EIO;
-    *out = {g->s[0], g->ev[0], g->ev[1], g->ev[2], g->ev[3]};
+    *out = {g->s[0], g->ev[0], g->ev[1], g->ev[2]};
     return FFHIP_OK;
 }
 extern "C" int ffhip_pipe_streams_get(FfhipPipe *out)
 {
-    const auto *g = thread_group(&ThreadSet::pipe, false, FFHIP_PIPE_EVENTS);
+    const auto *g = thread_group(&ThreadSet::pipe, false, 1);
     if (!g) return FFHIP_EIO;
-    out->plan = g->s[0]; out->groups2 = g->s[1];
-    for (int k = 0; k < FFHIP_PIPE_EVENTS; k++) out->ev[k] = g->ev[k];
+    *out = {g->s[0], g->ev[0]};
     return FFHIP_OK;
 }
 extern "C" int ffhip_huff_streams_get(FfhipHuffStreams *out)

@@ -204,18 +204,17 @@ def test_c5_135_tile_8k_grid(monkeypatch):
                                 envs=({}, {"FFHIP_HEVC_JT_INLINE": "1"}), monkeypatch=monkeypatch, sorted_by_plane=True)
     for a, b in zip(exp, exp_r):
         assert np.array_equal(a, b)
-    # the tile loop as a pipeline (ffhip_hevc_intra_recon_tiles): the list cut at tile boundaries into 1 .. 4 chunks, each chunk's pre-pass next to
-    # the chunk before's grouped kernel -- in both orders of the records
+    # the tile loop with its pre-pass on the library's stream (ffhip_hevc_intra_recon_tiles), with one scratch set and two, and in stream order --
+    # in both orders of the records (the settings pile up: each dict adds to the ones before)
     tile_first = np.arange(K, dtype=np.int64) * len(t0)
-    _intra_full_picture(T * gx, T * gy, tus, np.tile(res0, K), envs=({}, {"FFHIP_HEVC_TILE_EARLY": "0"}, {"FFHIP_HEVC_TILE_SCRATCHES": "1"}, {"FFHIP_HEVC_TILE_CHUNKS": "2", "FFHIP_HEVC_TILE_WAVES_PCT": "50"}, {"FFHIP_HEVC_TILE_CHUNKS": "3"}, {"FFHIP_HEVC_TILE_CHUNKS": "4"},
-                                                                       {"FFHIP_HEVC_TILE_CHUNKS": "4", "FFHIP_HEVC_JT_INLINE": "1"}),
+    _intra_full_picture(T * gx, T * gy, tus, np.tile(res0, K), envs=({}, {"FFHIP_HEVC_TILE_SCRATCHES": "1"}, {"FFHIP_HEVC_TILE_EARLY": "0"}, {"FFHIP_HEVC_JT_INLINE": "1"}),
                         monkeypatch=monkeypatch, tile_first=tile_first, exp=exp)
-    _intra_full_picture(T * gx, T * gy, grid_of(synth.hevc_reference_order(t0, 64, 2, 6)), np.tile(res0, K), envs=({"FFHIP_HEVC_TILE_CHUNKS": "4"},),
+    _intra_full_picture(T * gx, T * gy, grid_of(synth.hevc_reference_order(t0, 64, 2, 6)), np.tile(res0, K), envs=({"FFHIP_HEVC_TILE_EARLY": "1"},),
                         monkeypatch=monkeypatch, tile_first=tile_first, exp=exp, sorted_by_plane=True)
     # ... and with the colour conversion in the same call (ffhip_hevc_decode_tiles)
     from test_color_gpu import oracle_420_16
     bgra_exp = oracle_420_16(exp[0], exp[1], exp[2], T * gy // 2, T * gx // 2, 2)
-    _intra_full_picture(T * gx, T * gy, tus, np.tile(res0, K), envs=({}, {"FFHIP_HEVC_TILE_CHUNKS": "3"}, {"FFHIP_HEVC_TILE_EARLY": "0"}),
+    _intra_full_picture(T * gx, T * gy, tus, np.tile(res0, K), envs=({}, {"FFHIP_HEVC_TILE_EARLY": "0"}),
                         monkeypatch=monkeypatch, tile_first=tile_first, exp=exp, bgra_exp=bgra_exp)
     for i in range(1, K):
         ox, oy = (i % gx) * T, (i // gx) * T
