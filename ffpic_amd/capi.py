@@ -26,10 +26,12 @@ EXPORTS = [
     "ffhip_shard_range", "ffhip_comm_unique_id", "ffhip_comm_init_rank", "ffhip_comm_destroy", "ffhip_batch_close", "ffhip_batch_complete",
     "ffhip_bgra_checksum", "ffhip_vp8_filter_params", "ffhip_vp8_predict_loopfilter", "ffhip_reload_env", "ffhip_env_value_test", "ffhip_vp8_decode_frames", "ffhip_bgra_layout",
     "ffhip_jpeg_recon_items", "ffhip_jpeg_decode_files_mixed_device", "ffhip_vp8_decode_items",
+    "ffhip_vp8_dequant_factors", "ffhip_webp_probe", "ffhip_webp_parse", "ffhip_webp_parse_batch", "ffhip_webp_parse_device", "ffhip_webp_decode_files_device", "ffhip_debug_webp_last_parts",
 ]
 
 
 FFHIP_EINVAL, FFHIP_ENOMEM, FFHIP_ENODEV, FFHIP_EIO = -22, -12, -19, -5     # include/ffpic_hip.h:34-37
+FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1002, -1003
 
 
 class FfhipError(RuntimeError):
@@ -59,6 +61,26 @@ class Vp8FilterHeader(C.Structure):
                 ("segmentation_enabled", C.c_uint8), ("segment_feature_mode", C.c_uint8), ("lf_update_value", C.c_int8 * 4),
                 ("loop_filter_adj_enable", C.c_uint8), ("mode_ref_lf_delta0", C.c_int8), ("mb_mode_delta0", C.c_int8),
                 ("nbr_partitions", C.c_uint8)]
+
+
+class Vp8QuantHeader(C.Structure):
+    """ffhip_vp8_quant_header"""
+    _fields_ = [("y_ac_qi", C.c_uint8), ("y_dc_delta", C.c_int8), ("y2_dc_delta", C.c_int8), ("y2_ac_delta", C.c_int8),
+                ("uv_dc_delta", C.c_int8), ("uv_ac_delta", C.c_int8), ("segmentation_enabled", C.c_uint8),
+                ("update_mb_segmentation_map", C.c_uint8), ("quantizer_update_value", C.c_int8 * 4)]
+
+
+class WebpInfo(C.Structure):
+    """ffhip_webp_info"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("mbcols", C.c_int32), ("mbrows", C.c_int32), ("filter_type", C.c_int32),
+                ("nbr_partitions", C.c_int32), ("quant", (C.c_uint16 * 8) * 4), ("filters", C.c_uint8 * 24),
+                ("quant_header", Vp8QuantHeader), ("filter_header", Vp8FilterHeader)]
+
+
+class WebpParsed(C.Structure):
+    """ffhip_webp_parsed: caller arrays (host) of one file and its header"""
+    _fields_ = [("modes", C.c_void_p), ("levels", C.c_void_p), ("mbinfo", C.c_void_p), ("resmap", C.c_void_p), ("n_mb_cap", C.c_int64),
+                ("info", WebpInfo)]
 
 
 class JpegGeom(C.Structure):
@@ -202,6 +224,13 @@ def lib():
     L.ffhip_jpeg_recon_items.argtypes = [C.POINTER(JpegItem), ci, vp]
     L.ffhip_vp8_decode_items.argtypes = [C.POINTER(Vp8Item), ci, vp]
     L.ffhip_jpeg_decode_files_mixed_device.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_vp8_dequant_factors.argtypes = [C.POINTER(Vp8QuantHeader), vp]
+    L.ffhip_webp_probe.argtypes = [vp, sz, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.ffhip_webp_parse.argtypes = [vp, sz, C.POINTER(WebpParsed)]
+    L.ffhip_webp_parse_batch.argtypes = [vp, vp, ci, ci, C.POINTER(WebpParsed), vp]
+    L.ffhip_webp_parse_device.argtypes = [vp, vp, ci, C.POINTER(WebpParsed), vp, vp]
+    L.ffhip_debug_webp_last_parts.argtypes = [vp]
+    L.ffhip_webp_decode_files_device.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(WebpInfo), vp, vp]
     L.ffhip_hevc_picture_layout.argtypes = [ci, ci, ci, C.POINTER(HevcLayout)]
     L.ffhip_heif_grid_parse.argtypes = [vp, sz, C.POINTER(HeifGrid)]
     L.ffhip_heif_grid_compose.argtypes = [vp, i64, ci, ci, vp, i64, i64, ci, ci, ci, ci, vp]

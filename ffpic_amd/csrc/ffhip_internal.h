@@ -95,6 +95,7 @@ enum FfhipScratchKind {
     SCRATCH_HUFF_SYNC = 30,        /* .. + FFHIP_HUFF_PARTS - 1 */
     SCRATCH_FILES_MIXED = 7,       /* ffhip_jpeg_decode_files_mixed_device: a class's planes and quantiser tables, the host decoder's pinned planes */
     SCRATCH_JPEG_ITEMS = 40,       /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items' records and per-workgroup table, pinned records */
+    SCRATCH_WEBP = 60,             /* .. + 1: ffhip_webp_decode_files_device: a part's arrays, descriptors and file bytes (and their pinned copy); the host threads' pinned arrays */
     SCRATCH_VP8_ITEMS = 50,        /* .. + 2: ffhip_vp8_decode_items' tables (and their pinned copy), the levels items' residual, the line slots */
 };
 

@@ -506,3 +506,143 @@ def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True,
     if strict:
         return geoms, images, dout
     return geoms, images, dout, list(status)
+
+
+def vp8_dequant_factors(y_ac_qi, deltas=(0, 0, 0, 0, 0), segmentation_enabled=0, update_mb_segmentation_map=1, updates=(0, 0, 0, 0)):
+    """ffhip_vp8_dequant_factors (read_dequantization, format/webp.c:458-548): uint16 [4][8].  deltas = y_dc, y2_dc, y2_ac, uv_dc, uv_ac."""
+    L = capi.lib()
+    h = capi.Vp8QuantHeader()
+    h.y_ac_qi = y_ac_qi
+    h.y_dc_delta, h.y2_dc_delta, h.y2_ac_delta, h.uv_dc_delta, h.uv_ac_delta = [int(d) for d in deltas]
+    h.segmentation_enabled, h.update_mb_segmentation_map = segmentation_enabled, update_mb_segmentation_map
+    for i in range(4):
+        h.quantizer_update_value[i] = int(updates[i])
+    out = np.zeros((4, 8), np.uint16)
+    capi.check(L.ffhip_vp8_dequant_factors(C.byref(h), out.ctypes.data), "ffhip_vp8_dequant_factors")
+    return out
+
+
+def webp_probe(data):
+    """ffhip_webp_probe: (width, height, mbcols, mbrows) of a lossy WebP file (bytes); the picture ffhip_webp_decode_files_device
+    writes is 16*mbcols x 16*mbrows, width x height of it is what the reference's loader reports."""
+    L = capi.lib()
+    v = [C.c_int() for _ in range(4)]
+    buf = np.frombuffer(data, dtype=np.uint8)
+    capi.check(L.ffhip_webp_probe(buf.ctypes.data, buf.size, *[C.byref(x) for x in v]), "ffhip_webp_probe")
+    return tuple(x.value for x in v)
+
+
+def _webp_parsed(n_mb):
+    arrs = dict(modes=np.zeros((n_mb, 20), np.uint8), levels=np.zeros((n_mb, 25, 16), np.int16), mbinfo=np.zeros((n_mb, 32), np.uint8),
+                resmap=np.zeros(n_mb, np.int32))
+    p = capi.WebpParsed()
+    p.modes, p.levels, p.mbinfo, p.resmap = [arrs[k].ctypes.data for k in ("modes", "levels", "mbinfo", "resmap")]
+    p.n_mb_cap = n_mb
+    return p, arrs
+
+
+def _webp_result(p, arrs):
+    i = p.info
+    arrs.update(width=i.width, height=i.height, mbcols=i.mbcols, mbrows=i.mbrows, filter_type=i.filter_type, nbr_partitions=i.nbr_partitions,
+                quant=np.ctypeslib.as_array(i.quant).reshape(4, 8).copy(), filters=np.ctypeslib.as_array(i.filters).reshape(4, 2, 3).copy(),
+                info=i)
+    return arrs
+
+
+def webp_parse(data):
+    """ffhip_webp_parse on the host: dict of modes [n_mb][20], levels [n_mb][25][16], mbinfo [n_mb][32], resmap [n_mb], quant [4][8],
+    filters [4][2][3], filter_type, the sizes and the header (`info`, a capi.WebpInfo)."""
+    L = capi.lib()
+    _, _, c, r = webp_probe(data)
+    p, arrs = _webp_parsed(c * r)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    capi.check(L.ffhip_webp_parse(buf.ctypes.data, buf.size, C.byref(p)), "ffhip_webp_parse")
+    return _webp_result(p, arrs)
+
+
+def _webp_batch_args(files):
+    n = len(files)
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    return bufs, ptrs, lens
+
+
+def _webp_parse_many(files, call):
+    n = len(files)
+    bufs, ptrs, lens = _webp_batch_args(files)
+    outs = (capi.WebpParsed * n)()
+    keep = []
+    for i, f in enumerate(files):
+        try:
+            _, _, c, r = webp_probe(f)
+        except capi.FfhipError:
+            c = r = 0
+        p, arrs = _webp_parsed(max(c * r, 1))
+        outs[i] = p
+        keep.append(arrs)
+    status = (C.c_int * n)()
+    rc = call(ptrs, lens, n, outs, status)
+    if rc not in (0, capi.FFHIP_EINVAL) and rc > -1000:
+        capi.check(rc, "webp parse")
+    return [None if status[i] else _webp_result(outs[i], keep[i]) for i in range(n)], list(status)
+
+
+def webp_parse_batch(files, n_threads=4):
+    """ffhip_webp_parse_batch: (list of webp_parse dicts, None for a failing file; status codes)."""
+    L = capi.lib()
+    return _webp_parse_many(files, lambda ptrs, lens, n, outs, status: L.ffhip_webp_parse_batch(ptrs, lens, n, n_threads, outs, status))
+
+
+def webp_parse_device(files, stream=None):
+    """ffhip_webp_parse_device: the same arrays from the two device kernels (no host fall-back), for comparing the halves."""
+    L = capi.require_device()
+    return _webp_parse_many(files, lambda ptrs, lens, n, outs, status: L.ffhip_webp_parse_device(ptrs, lens, n, outs, status, stream))
+
+
+def webp_decode_files_device(files, n_threads=8, stream=None, strict=True, crop=True):
+    """ffhip_webp_decode_files_device: lossy WebP files of any sizes (list of bytes) in one call.  Every picture gets its place in ONE
+    device allocation, at a 16-byte-aligned offset with the pitch 64 x its macroblock columns.  Returns (infos, [host BGRA [h][w][4]
+    cropped to the probe's width x height (crop=False: the decoded 16*mbrows x 16*mbcols)], device buffer); with strict=False a
+    failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows."""
+    L = capi.require_device()
+    n = len(files)
+    offs, pitches, sizes, total = [], [], [], 0
+    for f in files:
+        try:
+            w, h, c, r = webp_probe(f)
+            pitch, rows = 64 * c, 16 * r
+        except capi.FfhipError:
+            w = h = pitch = rows = 0
+        offs.append(total)
+        pitches.append(pitch)
+        sizes.append((w, h, rows))
+        total += (pitch * rows + 15) & ~15
+    dout = DeviceBuffer(nbytes=max(total, 16))
+    bufs, ptrs, lens = _webp_batch_args(files)
+    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
+    pitch_arr = (C.c_int64 * n)(*pitches)
+    infos = (capi.WebpInfo * n)()
+    status = (C.c_int * n)()
+    rc = L.ffhip_webp_decode_files_device(ptrs, lens, n, n_threads, outs, pitch_arr, infos, status, stream)
+    if strict or (rc not in (0, capi.FFHIP_EINVAL) and rc > -1000):
+        capi.check(rc, "ffhip_webp_decode_files_device")
+    flat = dout.to_host((max(total, 16),), np.uint8)
+    images = []
+    for i in range(n):
+        w, h, rows = sizes[i]
+        if status[i] or not pitches[i]:
+            images.append(None)
+            continue
+        pic = flat[offs[i]:offs[i] + pitches[i] * rows].reshape(rows, pitches[i] // 4, 4)
+        images.append(pic[:h, :w].copy() if crop else pic.copy())
+    if strict:
+        return list(infos), images, dout
+    return list(infos), images, dout, list(status)
+
+
+def webp_last_parts():
+    """ffhip_debug_webp_last_parts: (parts the kernels took, parts the host threads took) in this thread's last WebP files call"""
+    out = (C.c_int * 2)()
+    capi.check(capi.lib().ffhip_debug_webp_last_parts(out), "ffhip_debug_webp_last_parts")
+    return out[0], out[1]

@@ -444,6 +444,122 @@ typedef struct ffhip_vp8_item {
 } ffhip_vp8_item;
 int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *stream);
 
+/* ---- lossy WebP files: the VP8 front end (container, frame header, bool decoder) in front of ffhip_vp8_decode_items ----
+ * The contract is the reference's WEBP_load (format/webp.c:2002 on; WEBP_read_frame :1872-1926, read_vp8_ctl_partition :897-935,
+ * vp8_decode_mb_header :1277-1450, vp8_get_coefficients :992-1064, vp8_decode_residual_block / _data :1125-1225,
+ * coding/booldec.c), bit for bit on the BGRA it produces -- not RFC 6386; ffhip_vp8_bool.h lists where the two differ. */
+#define FFHIP_EWEBP_LOSSLESS (-1001)    /* a VP8L chunk: lossless WebP is not decoded (the reference has a stub)      */
+#define FFHIP_EWEBP_ANIMATION (-1002)   /* the VP8X animation flag, or an ANIM / ANMF chunk in front of the frame      */
+#define FFHIP_EWEBP_INTER_FRAME (-1003) /* the frame tag says "not a key frame" (webp.c:1877-1880)                     */
+
+/* The frame-header fields read_dequantization (format/webp.c:458-548) reads, as the reference's header parser leaves them
+ * (format/webp.h:157-197), and the derivation itself on the host: the uint16 [4 segments][8] = y1_dc, y1_ac, y2_dc, y2_ac, uv_dc,
+ * uv_ac, 0, 0 that ffhip_vp8_item.quant and ffhip_vp8_residual_batch's d_quant take.  As the reference HAS it:
+ *   - absolute or delta is switched by update_mb_segmentation_map, not by segment_feature_mode (webp.c:518-522): map updated =
+ *     the update value IS the index, map kept = it is added to y_ac_qi;
+ *   - the index is a uint16_t: a negative one wraps and clamp(., 127) then gives index 127, not 0 (a delta applied to a small
+ *     non-negative index still clamps to 0: that sum is an int);
+ *   - without segmentation only segment 0 is derived, the others stay zero (webp.c:515);
+ *   - y2_dc is doubled and capped at 132, y2_ac is x 155 / 100, floored at 8 (webp.c:527-543). */
+typedef struct ffhip_vp8_quant_header {
+    uint8_t y_ac_qi; /* 0..127 */
+    int8_t y_dc_delta, y2_dc_delta, y2_ac_delta, uv_dc_delta, uv_ac_delta;
+    uint8_t segmentation_enabled;
+    uint8_t update_mb_segmentation_map;
+    int8_t quantizer_update_value[4]; /* segmentation.quant[s].quantizer_update_value */
+} ffhip_vp8_quant_header;
+/* host only */
+int ffhip_vp8_dequant_factors(const ffhip_vp8_quant_header *hdr, uint16_t *quant /* [4][8] */);
+
+/* What the frame header of a file says: the picture, and the per-frame arguments of ffhip_vp8_item. */
+typedef struct ffhip_webp_info {
+    int32_t width, height;   /* what WEBP_load puts into struct pic (webp.c:2069-2076): the VP8X canvas fields when there is such a
+                                chunk (read as stored, without the format's "+ 1"), otherwise the frame's size rounded UP to a
+                                multiple of 4 */
+    int32_t mbcols, mbrows;  /* the decoded picture is 16*mbcols x 16*mbrows */
+    int32_t filter_type;     /* 0 none, 1 simple, 2 normal */
+    int32_t nbr_partitions;  /* 1, 2, 4 or 8 token partitions.  (8 overflow the reference's own p[4] and bt[4] arrays, webp.h:268,
+                                webp.c:1904, so there is no reference output to pin them: such files are decoded by the rule of the
+                                others, and the tests hold host parser, kernels and oracle chain against each other on them.) */
+    uint16_t quant[4][8];    /* ffhip_vp8_dequant_factors of quant_header */
+    uint8_t filters[4][2][3]; /* ffhip_vp8_filter_params of filter_header (nbr_partitions passed through: its kept defect depends on it) */
+    ffhip_vp8_quant_header quant_header;
+    ffhip_vp8_filter_header filter_header;
+} ffhip_webp_info;
+
+/* Host only.  The chunk walk of WEBP_load as it is (webp.c:2016-2066): `VP8X` and `ALPH` are accepted only at the reference's
+ * fixed struct sizes (size fields 10 and 1), unknown chunks are skipped by their size without the padding byte, the first `VP8 `
+ * chunk ends the walk; then the key-frame tag, the start code and the 14-bit sizes.  Any of the four outputs may be NULL.
+ * FFHIP_EWEBP_* for lossless, animated and inter-frame files, FFHIP_EINVAL for anything else that is not a lossy WebP. */
+int ffhip_webp_probe(const uint8_t *file, size_t len, int *width, int *height, int *mbcols, int *mbrows);
+
+/* Host only: one file -> what ffhip_vp8_decode_items takes, into CALLER memory sized from the probe (n_mb = mbcols * mbrows):
+ *   modes   uint8 [n_mb][20]      the mode records ([18] = segment id)
+ *   levels  int16 [n_mb][25][16]  mbinfo uint8 [n_mb][32]   as ffhip_vp8_residual_batch reads them
+ *   resmap  int32 [n_mb]          the residual row each macroblock shows: its own, or for a macroblock with mb_skip_coeff the
+ *                                 last CODED macroblock's in decode order, across row ends too -- the reference leaves the previous
+ *                                 coefficients in place (webp.c:1207-1223, the array lives outside both loops, :1830).  A skipped
+ *                                 macroblock in front of every coded one reads an uninitialised stack array in the reference: it
+ *                                 gets its own (all-zero) row here, and that case is UNPINNED.
+ *   n_mb_cap                      macroblocks the four arrays have room for (FFHIP_EINVAL when the file has more)
+ * info receives the header.  Row y takes its tokens from partition y & (nbr_partitions - 1) (webp.c:1836); the `top` contexts carry
+ * across rows, `left` starts at zero in every row; a skipped macroblock clears contexts 1-8 always and context 0 only when it is
+ * not B_PRED (webp.c:1213-1221).  A partition that is asked for a byte beyond its length is FFHIP_EINVAL ("truncated": the
+ * reference reads one byte of heap there and then exits, utils/bitstream.c:115-120), and no read goes outside [file, file + len).
+ * The last partition ends with the FILE in the reference (webp.c:452-454); here it ends with the `VP8 ` chunk where that is
+ * shorter, so bytes of a chunk behind the frame are never taken for tokens. */
+typedef struct ffhip_webp_parsed {
+    uint8_t *modes;
+    int16_t *levels;
+    uint8_t *mbinfo;
+    int32_t *resmap;
+    int64_t n_mb_cap;
+    ffhip_webp_info info;
+} ffhip_webp_parsed;
+int ffhip_webp_parse(const uint8_t *file, size_t len, ffhip_webp_parsed *out);
+/* n files over n_threads host threads; status[i] = each file's code, returns the first failure */
+int ffhip_webp_parse_batch(const uint8_t *const *files, const size_t *lens, int n, int n_threads, ffhip_webp_parsed *outs, int *status);
+/* The same arrays from the DEVICE front end (kernel A: macroblock headers, kernel B: token partitions), copied back into the
+ * caller's HOST arrays: lets a test say which half differs from ffhip_webp_parse.  No fall-back: a file the kernels refuse gets
+ * their verdict (FFHIP_EINVAL).  Synchronises `stream`. */
+int ffhip_webp_parse_device(const uint8_t *const *files, const size_t *lens, int n, ffhip_webp_parsed *outs, int *status, void *stream);
+
+/* Files in, pixels on the device: n lossy WebP files of any sizes in one call, picture i at d_bgra[i] with pitch[i] -- 16*mbrows
+ * rows of 16*mbcols pixels as ffhip_webp_probe reports them (the caller probes, then allocates; alignment and pitch as for
+ * ffhip_vp8_item).  Host threads parse only the frame header (a few hundred bool decodes, up to prob_skip_false) and derive
+ * quantisers and filters; the file bytes go up through pinned staging; kernel A reads the macroblock headers of the first partition
+ * into mode records, skip flags and the residual map, kernel B the token partitions into levels and token counts, and
+ * ffhip_vp8_decode_items (device-side mode check, no FFHIP_RETRIED) does the rest.  Arithmetic decoding is serial per stream, so a
+ * frame is ONE lane's work in either kernel -- a lone lane issues as fast as a full wave, so every frame gets a wave of its own
+ * until a part of the batch has more frames than the device has wave slots; only then do several frames share a wave.  Frames with
+ * 2, 4 or 8 token partitions are walked row by row by that one lane, which holds all the decoder states: no waits between waves.
+ * The batch is processed in PARTS of at most 2^23 macroblocks with the kernels and 2^19 with the host threads.  A part's arrays
+ * take 856 bytes per macroblock (levels, token counts, records, maps).  Up to 1 GiB they are library scratch of the stream, kept
+ * between calls like every other scratch; a larger part (from some 150 frames of 1080p; 6.7 GiB at the bound) allocates its own and
+ * frees them when it is done, so this call leaves no more than 1 GiB standing.  (ffhip_vp8_decode_items behind it keeps its 768
+ * bytes of residual per macroblock as that call documents.)  The kernels' parts are that large because a part costs what its
+ * LARGEST frame costs one lane, however many frames it holds; the host threads' arrays are mirrored in pinned memory, hence 2^19.
+ * FFHIP_WEBP_GPU_ENTROPY=0: n_threads host threads parse the parts instead (the loops of ffhip_webp_parse) and the arrays are
+ * uploaded; =1: always the kernels; unset: the kernels for a part worth at least 32 x n_threads of its largest frame (macroblocks
+ * of the part / macroblocks of its largest file), the host threads below; FFHIP_WEBP_GPU_MIN_FILES replaces that product.
+ * MEASURED with n_threads = 16 on an MI355X: a lane takes 45 us per macroblock of a photograph, a host thread
+ * 1.7 us -- 1, 16 and 256 copies of a 1080p stream and the mixed fixture set are faster on the host, 512 and 1 024 copies on the
+ * device.  Other thread counts were NOT measured; the threshold scales with n_threads on the assumption that the host threads
+ * scale linearly.  The kernels refuse only what the host parser refuses (a partition asked for a byte beyond its length; same
+ * source, same lengths), so a file they refuse has its code from them and is not parsed a second time.
+ * FFHIP_WEBP_PACK (frames per wave, 1..32) and FFHIP_WEBP_PART_MB (macroblocks per part, both front ends) let tests reach the
+ * packed and the many-part forms with small batches.
+ * info_out[i] (may be NULL) receives each file's header, status[i] its code: a damaged, truncated, lossless, animated or inter-frame
+ * file gets a non-zero code and no promised output bytes, and every other file is still decoded.  Returns the first failure.
+ * Every argument check is made before anything is enqueued (FFHIP_EINVAL, on a machine without a device too; FFHIP_ENODEV there
+ * for good arguments).  Synchronises `stream`. */
+int ffhip_webp_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                   const int64_t *pitch, ffhip_webp_info *info_out, int *status, void *stream);
+
+/* Diagnostics: how many parts of the calling thread's last ffhip_webp_decode_files_device / ffhip_webp_parse_device call went to the
+ * kernels (out[0]) and to the host threads (out[1]). */
+int ffhip_debug_webp_last_parts(int out[2]);
+
 /* ---- HEVC intra prediction + reconstruction for a list of transform units ----
  * decode_intra_block steps 5-10 (coding/hevc.c:4730-4790) for every TU of a picture:
  * intra_sample_prediction (hevc.c:4542-4662: neighbour gathering, reference_sample_substitution
