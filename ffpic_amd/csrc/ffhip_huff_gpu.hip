@@ -24,12 +24,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
-#include <thread>
 #include <vector>
 #include <memory>
 #include <new>
-#include <type_traits>
 
 struct HuffImage {
     uint32_t scan_off, scan_len; /* this picture's entropy-coded bytes inside `scan` */
@@ -322,18 +319,6 @@ void build_lut(const struct huff &h, uint16_t *out)
         for (int i = 0; i < 512 + 128 * groups; i++)
             if (!out[i]) out[i] = LUT_NO_CODE;
 }
-
-template <typename F>
-void parallel_for(int n, int n_threads, F f)
-{
-    if (n_threads > n) n_threads = n;
-    if (n_threads <= 1) { for (int i = 0; i < n; i++) f(i); return; }
-    std::vector<std::thread> pool;
-    auto part = [&](int t) { for (int i = t; i < n; i += n_threads) f(i); };
-    for (int t = 1; t < n_threads; t++) pool.emplace_back(part, t);
-    part(0);
-    for (auto &th : pool) th.join();
-}
 } // namespace
 
 /* Test hook (host only, no device needed): stage_scan on caller memory.  dst must hold len + 8 n_seg + 64 bytes. */
@@ -366,8 +351,6 @@ extern "C" int ffhip_jpeg_lut_test(const uint8_t *file, size_t len, int which, u
 /* what the calling thread's last ffhip_jpeg_entropy_batch_gpu call spent where (bench.py's configs.f1): microseconds of host time per phase,
  * and the Huffman kernel's own time by HIP events on the call's stream */
 static thread_local double g_huff_times[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define SYNC_PARTS FFHIP_HUFF_PARTS
-/* (the upload stream, the second kernel stream and the events of a call are the thread's and the device's: ffhip_huff_streams_get) */
 /* bits of a subsequence, unless FFHIP_JPEG_SYNC_BITS sets them: by the bits an MCU takes (huff_sync_enqueue has the measurements) */
 static uint32_t sync_sub_bits(unsigned long long bits, unsigned long long mcus)
 {
@@ -407,6 +390,409 @@ struct SyncJob {
 static int huff_sync_enqueue(SyncJob &job, void *stream, uint32_t **h_cnt);
 static int huff_sync_finish(SyncJob &job, void *stream, uint32_t *h_cnt, int *status);
 
+namespace {
+typedef std::chrono::steady_clock::time_point HuffTime;
+HuffTime huff_now() { return std::chrono::steady_clock::now(); }
+long us(HuffTime a, HuffTime b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); }
+/* the one upload, pinned stage and device image alike: scan bytes | 16 zero bytes | tables | look-up tables | picture records | interval starts (per
+ * picture one more: the end of its last interval) | work list | status | quantisers */
+struct HuffLayout { size_t o_tabs, o_l12, o_img, o_seg, o_work, o_status, o_quant, total; };
+HuffLayout huff_layout(size_t scan_total, size_t n_tabs, size_t n, size_t seg_total)
+{
+    HuffLayout L;
+    size_t at = scan_total + 16;
+    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
+    L.o_tabs = take(n_tabs * sizeof(struct huff));
+    L.o_l12 = take(n_tabs * LUT_WORDS * 2);
+    L.o_img = take(n * sizeof(HuffImage));
+    L.o_seg = take((seg_total + n) * 4);
+    L.o_work = take(seg_total * 8);
+    L.o_status = take(n * 4);
+    L.o_quant = take(n * 512);
+    L.total = at;
+    return L;
+}
+/* One call of jpeg_entropy_batch_gpu_impl: its arguments and what its stages hand each other. */
+struct HuffCall {
+    const uint8_t *const *files;
+    const size_t *lens;
+    int n, n_threads;
+    const ffhip_jpeg_geom *geom, *geoms;
+    int16_t *d_coef_y, *d_coef_u, *d_coef_v;
+    uint16_t *d_quant;
+    int *status;
+    hipStream_t st;            /* the caller's stream */
+    const FfhipHuffThen *then; /* NULL: coefficients only */
+    std::vector<uint32_t> pic_mcus, mcu_base; /* per picture its MCUs and the MCUs of the pictures before it; mcu_base[n] = all */
+    struct jpeg_hdr *hdr;                     /* the calling thread's header records */
+    std::vector<std::vector<uint32_t>> segs, raws; /* per picture: its intervals' starts in its clean stream (and the end of the last), their own lengths */
+    uint32_t sub_bits;
+    std::vector<HuffImage> images;
+    std::vector<const struct huff *> uniq;    /* the distinct Huffman tables of the batch */
+    size_t scan_total, seg_total;
+    HuffLayout L;
+    uint8_t *stage, *dev;                     /* pinned staging and device image, kept per stream: callers on different streams overlap completely */
+    hipStream_t up, second;                   /* the thread's (ffhip_huff_streams_get): the copy stream the parts' bytes go up on, the second kernel stream */
+    hipEvent_t fork, join, *part_ev, time_ev[2];
+    std::vector<ffhip_jpeg_item> then_items;
+    bool times;                               /* FFHIP_HUFF_TIMES: host phases on stderr */
+    HuffTime T0, T1, T2, T3, T4;              /* start | headers parsed | laid out | staged | tail up */
+    long staging_us, tables_us;               /* unstuffing without, and the tables of huff_tail_up */
+};
+
+#define HUFF_TRY(call) do { if ((call) != hipSuccess) return FFHIP_EIO; } while (0)
+int huff_first_status(const HuffCall &c) { for (int i = 0; i < c.n; i++) if (c.status[i]) return c.status[i]; return FFHIP_OK; }
+/* arguments and geometry; per picture its MCUs and where its blocks start: one geometry (geoms NULL) or pictures of one layout class that differ in size */
+int huff_check(HuffCall &c)
+{
+    const ffhip_jpeg_geom *geom = c.geom;
+    if (geom->ncomp == 3 && (!c.d_coef_u || !c.d_coef_v)) return FFHIP_EINVAL;
+    c.n_threads = c.n_threads < 1 ? 1 : c.n_threads > 64 ? 64 : c.n_threads;
+    if (geom->mcu_cols <= 0 || geom->mcu_rows <= 0 || geom->h < 1 || geom->v < 1 || geom->h * geom->v > 4 ||
+        (geom->ncomp != 1 && geom->ncomp != 3)) return FFHIP_EINVAL;
+    c.pic_mcus.resize((size_t)c.n);
+    c.mcu_base.resize((size_t)c.n + 1);
+    size_t sum = 0;
+    for (int i = 0; i < c.n; i++) {
+        const ffhip_jpeg_geom *gi = c.geoms ? &c.geoms[i] : geom;
+        if (c.geoms && (gi->ncomp != geom->ncomp || gi->h != geom->h || gi->v != geom->v || gi->mcu_cols <= 0 || gi->mcu_rows <= 0)) return FFHIP_EINVAL;
+        c.pic_mcus[(size_t)i] = (uint32_t)((size_t)gi->mcu_cols * gi->mcu_rows);
+        c.mcu_base[(size_t)i] = (uint32_t)sum;
+        sum += c.pic_mcus[(size_t)i];
+        if (sum > 0xffffffffu) return FFHIP_EINVAL;
+    }
+    c.mcu_base[(size_t)c.n] = (uint32_t)sum;
+    return FFHIP_OK;
+}
+/* host, pictures over threads: headers, tables, room for the restart-interval starts.  The first file's code that is not 0, if any */
+int huff_parse_headers(HuffCall &c)
+{
+    c.hdr = ffhip_huff_hdr_records((size_t)c.n); /* kept between calls */
+    if (!c.hdr) return FFHIP_ENOMEM;
+    c.segs.resize((size_t)c.n);
+    c.raws.resize((size_t)c.n);
+    ffhip_parallel_for(c.n, c.n_threads, [&c](int i) {
+        struct jpeg_hdr &j = c.hdr[(size_t)i];
+        c.status[i] = ffhip_jpeg_parse(c.files[i], c.lens[i], &j);
+        if (c.status[i]) return;
+        const int mc = (j.width + 8 * j.h[0] - 1) / (8 * j.h[0]), mr = (j.height + 8 * j.v[0] - 1) / (8 * j.v[0]);
+        const ffhip_jpeg_geom *gi = c.geoms ? &c.geoms[i] : c.geom;
+        const size_t mcus = c.pic_mcus[(size_t)i];
+        if (mc != gi->mcu_cols || mr != gi->mcu_rows || j.ncomp != gi->ncomp || j.h[0] != gi->h || j.v[0] != gi->v ||
+            j.scan_len > 0x7fffffffu) {
+            c.status[i] = FFHIP_EINVAL; /* another geometry */
+            return;
+        }
+        if (!j.restart) j.restart = (int)mcus; /* no DRI: the whole scan is one interval */
+        /* the interval starts are found while the bytes are staged (stage_scan) */
+        c.segs[(size_t)i].assign((size_t)((mcus + j.restart - 1) / j.restart) + 1, 0u); /* (one more: the end of the last) */
+        c.raws[(size_t)i].assign(c.segs[(size_t)i].size(), 0u);
+    });
+    return huff_first_status(c);
+}
+/* Which decoder: true, the subsequence decoder -- a lane per c.sub_bits bits of a restart interval (of the whole scan, in a file without restart
+ * markers), brought into step with each other over rounds; false, k_jpeg_huff, a lane per restart interval -- a file without markers is ONE lane's then */
+bool huff_choose_subsequences(HuffCall &c)
+{
+    const char *sy = FFHIP_ENV("FFHIP_JPEG_SYNC");
+    /* the subsequences' length is worked out ONCE, from the batch's scan bytes: the choice of kernel below and every part's passes go by the same figure */
+    unsigned long long batch_bits = 0, n_int = 0;
+    for (int i = 0; i < c.n; i++) batch_bits += 8ull * c.hdr[(size_t)i].scan_len;
+    c.sub_bits = sync_sub_bits(batch_bits, (unsigned long long)c.mcu_base[(size_t)c.n]);
+    if (sy && (sy[0] == '0' || sy[0] == '1')) return sy[0] == '1';
+    /* restart intervals of a subsequence or two (a DRI of one or a few MCUs: 32 400 intervals in a 4K picture) are lanes enough as they are, every
+     * one starting from the truth: three passes, a 60-byte record per interval and rounds that have nothing to settle are the wrong tool; the
+     * interval kernel takes such batches (FFHIP_JPEG_SYNC=1 keeps the subsequence decoder on them) */
+    for (int i = 0; i < c.n; i++) n_int += c.segs[(size_t)i].size() - 1;
+    return batch_bits > 2ull * c.sub_bits * n_int;
+}
+/* pictures of a batch mostly share their Huffman tables (an encoder's defaults): keep one copy of each distinct table */
+uint32_t huff_table_id(std::vector<const struct huff *> &uniq, const struct huff *t)
+{
+    for (size_t u = uniq.size(); u-- > 0;) /* newest first: the previous picture's are the likely match */
+        if (uniq[u] == t || !memcmp(&uniq[u]->maxcode, &t->maxcode, offsetof(struct huff, fast) - offsetof(struct huff, maxcode))) return (uint32_t)u; /* (look[] and fast[] follow from the rest) */
+    uniq.push_back(t);
+    return (uint32_t)(uniq.size() - 1);
+}
+/* the picture records with their places in the upload, the distinct tables, the layout, the stream's pinned stage and device image */
+int huff_lay_out(HuffCall &c)
+{
+    c.images.resize((size_t)c.n);
+    c.scan_total = c.seg_total = 0;
+    for (int i = 0; i < c.n; i++) {
+        const struct jpeg_hdr &j = c.hdr[(size_t)i];
+        HuffImage &im = c.images[(size_t)i];
+        im.scan_off = (uint32_t)c.scan_total;
+        im.scan_len = (uint32_t)j.scan_len;
+        im.restart = (uint32_t)j.restart;
+        im.mcus = c.pic_mcus[(size_t)i];
+        im.mcu_base = c.mcu_base[(size_t)i];
+        im.ncomp = (uint32_t)j.ncomp;
+        im.seg_base = (uint32_t)c.seg_total;
+        im.n_seg = (uint32_t)c.segs[(size_t)i].size() - 1;
+        for (int k = 0; k < 3; k++) {
+            im.nb[k] = k < j.ncomp ? (uint32_t)(j.h[k] * j.v[k]) : 0;
+            im.tab_dc[k] = huff_table_id(c.uniq, &j.dc[k < j.ncomp ? j.td[k] : j.td[0]]);
+            im.tab_ac[k] = huff_table_id(c.uniq, &j.ac[k < j.ncomp ? j.ta[k] : j.ta[0]]);
+        }
+        c.scan_total += (j.scan_len + 8 * (size_t)im.n_seg + 64 + 15) & ~(size_t)15; /* unstuffed, every interval aligned and padded, slack for the 16-byte stores */
+        c.seg_total += im.n_seg;
+        im.seg_base += (uint32_t)i; /* one more entry per picture: the end of its last interval */
+        if (c.scan_total > 0x7fffffffu) return FFHIP_EINVAL;
+    }
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    if (c.uniq.size() > 4095) return FFHIP_EINVAL; /* table indices travel in 12 bits */
+    c.L = huff_layout(c.scan_total, c.uniq.size(), (size_t)c.n, c.seg_total);
+    c.stage = ffhip_pinned_scratch(SCRATCH_HUFF, c.st, c.L.total + 64);
+    if (!c.stage) return FFHIP_ENOMEM;
+    c.T2 = huff_now();
+    c.dev = (uint8_t *)ffhip_scratch(SCRATCH_HUFF, c.st, (c.L.total + 3) / 4);
+    return c.dev ? FFHIP_OK : FFHIP_ENOMEM;
+}
+/* the kernels store the non-zero coefficients only: the planes are cleared first -- enqueued before the staging, so that the
+ * clears (4.8 GB for 256 4K pictures) run while the host is still staging */
+int huff_clear_planes(HuffCall &c)
+{
+    const size_t total_mcus = c.mcu_base[(size_t)c.n], yb = total_mcus * c.geom->h * c.geom->v * 64;
+    FFHIP_CHECK(hipMemsetAsync(c.d_coef_y, 0, yb * 2, c.st), FFHIP_EIO);
+    if (c.geom->ncomp != 3) return FFHIP_OK;
+    FFHIP_CHECK(hipMemsetAsync(c.d_coef_u, 0, total_mcus * 128, c.st), FFHIP_EIO);
+    FFHIP_CHECK(hipMemsetAsync(c.d_coef_v, 0, total_mcus * 128, c.st), FFHIP_EIO);
+    return FFHIP_OK;
+}
+/* Pictures [lo, hi) over threads: the picture's bytes into the stage, unstuffed, every restart interval 4-byte aligned and followed by >= 4 zero
+ * bytes; a picture whose restart markers do not add up gets FFHIP_EINVAL in status[].  lists: what k_jpeg_huff reads besides -- the interval
+ * starts, a work-list entry per interval -- and the picture's quantisers (the subsequence decoder keeps the interval lists on the host and has
+ * sent the tail of the image already). */
+void huff_stage_pictures(HuffCall &c, int lo, int hi, bool lists)
+{
+    ffhip_parallel_for(hi - lo, c.n_threads, [&c, lo, lists](int i_rel) {
+        const int i = lo + i_rel;
+        const struct jpeg_hdr &j = c.hdr[(size_t)i];
+        const HuffImage &im = c.images[(size_t)i];
+        uint8_t *dst = c.stage + im.scan_off;
+        std::vector<uint32_t> &sgv = c.segs[(size_t)i];
+        size_t off = 0;
+        if (stage_scan(dst, j.scan, j.scan + j.scan_len, sgv.data(), im.n_seg, &off, c.raws[(size_t)i].data()) != im.n_seg) c.status[i] = FFHIP_EINVAL;
+        memset(dst + off, 0, 16);
+        sgv[im.n_seg] = (uint32_t)off;
+        if (!lists) return;
+        uint32_t *sg = (uint32_t *)(c.stage + c.L.o_seg) + im.seg_base;
+        u32x2 *wk = (u32x2 *)(c.stage + c.L.o_work) + (im.seg_base - (uint32_t)i);
+        for (uint32_t k = 0; k < im.n_seg; k++) {
+            sg[k] = sgv[k];
+            wk[k].x = (uint32_t)i;
+            wk[k].y = k;
+        }
+        sg[im.n_seg] = (uint32_t)off;
+        memcpy(c.stage + c.L.o_quant + (size_t)i * 512, j.quant, 512);
+    });
+}
+int huff_part_lo(const HuffCall &c, int n_parts, int part) { return (int)((long long)c.n * part / n_parts); }
+size_t huff_scan_end(const HuffCall &c, int hi) { return hi < c.n ? c.images[(size_t)hi].scan_off : c.scan_total; } /* of the pictures in front of hi */
+
+/* tables, picture records, status, quantiser tables: behind the scan bytes in the image, one copy on the caller's stream, and the quantisers from
+ * there to the caller's d_quant.  (The quantisers are in the stage already.) */
+int huff_tail_up(HuffCall &c)
+{
+    const HuffTime Ta = huff_now();
+    memset(c.stage + c.scan_total, 0, 16);
+    ffhip_parallel_for((int)c.uniq.size(), c.n_threads, [&c](int u) {
+        ((struct huff *)(c.stage + c.L.o_tabs))[u] = *c.uniq[(size_t)u];
+        build_lut(*c.uniq[(size_t)u], (uint16_t *)(c.stage + c.L.o_l12) + (size_t)u * LUT_WORDS);
+    });
+    memcpy(c.stage + c.L.o_img, c.images.data(), c.images.size() * sizeof(HuffImage));
+    memset(c.stage + c.L.o_status, 0, (size_t)c.n * 4);
+    c.tables_us = us(Ta, huff_now());
+    FFHIP_CHECK(hipMemcpyAsync(c.dev + c.scan_total, c.stage + c.scan_total, c.L.total - c.scan_total, hipMemcpyHostToDevice, c.st), FFHIP_EIO);
+    FFHIP_CHECK(hipMemcpyAsync(c.d_quant, c.dev + c.L.o_quant, (size_t)c.n * 512, hipMemcpyDeviceToDevice, c.st), FFHIP_EIO);
+    return FFHIP_OK;
+}
+/* pictures [lo, hi) from their planes to then's BGRA on `on`: one geometry, one ffhip_jpeg_recon_batch; items, one ffhip_jpeg_recon_items (scratch
+ * slot `part`: the parts' calls are in flight side by side) */
+int huff_reconstruct(HuffCall &c, int lo, int hi, void *on, int part)
+{
+    const FfhipHuffThen *then = c.then;
+    if (!then->items) {
+        const size_t mcus = c.pic_mcus[0];
+        return ffhip_jpeg_recon_batch(c.geom, hi - lo, c.d_coef_y + (size_t)lo * mcus * c.geom->h * c.geom->v * 64, c.d_coef_u ? c.d_coef_u + (size_t)lo * mcus * 64 : nullptr,
+                                      c.d_coef_v ? c.d_coef_v + (size_t)lo * mcus * 64 : nullptr, c.d_quant + (size_t)lo * 256, 256,
+                                      then->bgra + (int64_t)lo * then->image_stride, then->pitch, then->image_stride, nullptr, 0, on);
+    }
+    c.then_items.assign(then->items + lo, then->items + hi);
+    for (int i = lo; i < hi; i++) jpeg_item_planes(&c.then_items[(size_t)(i - lo)], c.d_coef_y, c.d_coef_u, c.d_coef_v, c.d_quant, c.mcu_base[(size_t)i], (size_t)i);
+    return jpeg_recon_items_impl(c.then_items.data(), hi - lo, on, part);
+}
+/* The end of either decoder's enqueueing: the per-picture verdicts come back with the stream (tiny), the stream is drained -- the staging buffer is
+ * free again after this sync --, and the call's times are kept (ffhip_debug_huff_times) and, on demand, printed */
+int huff_collect(HuffCall &c)
+{
+    HUFF_TRY(hipMemcpyAsync(c.stage + c.L.o_status, c.dev + c.L.o_status, (size_t)c.n * 4, hipMemcpyDeviceToHost, c.st));
+    const HuffTime T5 = huff_now();
+    HUFF_TRY(hipStreamSynchronize(c.st));
+    const HuffTime T6 = huff_now();
+    if (c.times) {
+        fprintf(stderr, "huff staging: header parse %ld us, layout %ld us, unstuff + markers (uploads enqueued by parts) %ld us, tables %ld us (%d files, %zu bytes, %d threads)\n", us(c.T0, c.T1), us(c.T1, c.T2), c.staging_us, c.tables_us, c.n, c.L.total, c.n_threads);
+        fprintf(stderr, "huff device: enqueue %ld us, wait for uploads + clears + kernel %ld us\n", us(c.T3, T5), us(T5, T6));
+    }
+    float kms = 0.0f;
+    if (hipEventElapsedTime(&kms, c.time_ev[0], c.time_ev[1]) != hipSuccess) { (void)hipGetLastError(); kms = 0.0f; }
+    g_huff_times[0] = (double)us(c.T0, c.T1); g_huff_times[1] = (double)us(c.T1, c.T2); g_huff_times[2] = (double)c.staging_us; g_huff_times[3] = (double)c.tables_us;
+    g_huff_times[4] = (double)us(c.T4, T5); g_huff_times[5] = (double)us(T5, T6); g_huff_times[6] = (double)kms * 1e3; g_huff_times[7] = (double)us(c.T0, T6);
+    memcpy(c.status, c.stage + c.L.o_status, (size_t)c.n * 4);
+    return FFHIP_OK;
+}
+/* ---- k_jpeg_huff, a lane per restart interval.  Everything on the caller's stream: the plane clears are on it already ---- */
+int huff_decode_intervals(HuffCall &c)
+{
+    /* the pictures are staged a quarter of the batch at a time and each quarter's bytes go up while the next is
+     * being unstuffed: the upload (8 ms for 256 4K files) hides behind the staging (7 ms) instead of following it */
+    const int n_parts = c.n >= 32 ? 4 : 1;
+    for (int part = 0; part < n_parts; part++) {
+        const int lo = huff_part_lo(c, n_parts, part), hi = huff_part_lo(c, n_parts, part + 1);
+        const size_t b0 = huff_scan_end(c, lo), b1 = huff_scan_end(c, hi);
+        huff_stage_pictures(c, lo, hi, true);
+        HUFF_TRY(hipMemcpyAsync(c.dev + b0, c.stage + b0, b1 - b0, hipMemcpyHostToDevice, c.st));
+    }
+    if (huff_first_status(c)) return huff_first_status(c); /* a file whose restart markers do not add up: nothing is decoded */
+    c.T3 = huff_now();
+    c.staging_us = us(c.T2, c.T3);
+    const int rc = huff_tail_up(c); /* last: the interval lists were found while staging */
+    if (rc) return rc;
+    c.T4 = huff_now();
+    HuffArgs a;
+    a.scan = c.dev;
+    a.tabs = (const struct huff *)(c.dev + c.L.o_tabs);
+    a.lut = (const uint16_t *)(c.dev + c.L.o_l12);
+    a.images = (const HuffImage *)(c.dev + c.L.o_img);
+    a.seg = (const uint32_t *)(c.dev + c.L.o_seg);
+    a.work = (const u32x2 *)(c.dev + c.L.o_work);
+    a.plane[0] = c.d_coef_y; a.plane[1] = c.d_coef_u; a.plane[2] = c.d_coef_v;
+    a.status = (int *)(c.dev + c.L.o_status);
+    a.n_work = (uint32_t)c.seg_total;
+    (void)hipEventRecord(c.time_ev[0], c.st);
+    {   /* 128-byte rings (two workgroups of four waves per CU) while that holds the whole batch at once; 64-byte rings (three per CU, a refill every 8 symbols instead
+         * of 16) beyond: 256 4K files of 135 intervals 9.9 ms against 10.4, 1 024 files 25.2 against 20.2 */
+        int cus = 256, device = 0;
+        if (hipGetDevice(&device) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        const unsigned wgs = (a.n_work + 255) / 256;
+        const char *fr = FFHIP_ENV("FFHIP_HUFF_RING"); /* =16 / =32 forces either */
+        if (fr ? atoi(fr) == 16 : wgs > 2u * (unsigned)cus) hipLaunchKernelGGL((k_jpeg_huff<16, 8>), dim3(wgs), dim3(256), 0, c.st, a);
+        else hipLaunchKernelGGL((k_jpeg_huff<32, 16>), dim3(wgs), dim3(256), 0, c.st, a);
+    }
+    HUFF_TRY(hipGetLastError());
+    (void)hipEventRecord(c.time_ev[1], c.st);
+    if (c.then) {
+        const int rrc = huff_reconstruct(c, 0, c.n, c.st, 0);
+        if (rrc) return rrc;
+    }
+    return huff_collect(c);
+}
+/* parts of the batch that the subsequence decoder stages, sends and decodes one behind the other */
+int huff_sync_part_count(const HuffCall &c)
+{
+    /* parts of about 140 MB of scan bytes, a hundred 4K files -- a round over fewer subsequences fills the chip badly, and what is left to wait for
+     * behind the last upload are the last part's kernels: 256 4K files 13.7-14.0 ms in three parts, 14.0-14.5 in four, 14.2 in two, 14.4-14.5 in six (and 14.7-14.9 in four of
+     * 1/8, 3/8, 3/8, 1/8 of the files, which looked good on paper) */
+    const int by_bytes = (int)((c.scan_total + (70u << 20)) / (140u << 20)); /* (by bytes, not by files: 4 096 thumbnails are a hundred megabytes) */
+    int n_parts = c.n < 32 || c.scan_total < (16u << 20) ? 1 : by_bytes < 2 ? 2 : by_bytes > FFHIP_HUFF_PARTS ? FFHIP_HUFF_PARTS : by_bytes;
+    const char *e = FFHIP_ENV("FFHIP_JPEG_SYNC_PARTS"); /* (1..8) */
+    if (e && atoi(e) >= 1) n_parts = atoi(e) > FFHIP_HUFF_PARTS ? FFHIP_HUFF_PARTS : atoi(e);
+    return n_parts > c.n ? c.n : n_parts;
+}
+/* the record huff_sync_enqueue takes for pictures [lo, hi), staged: their intervals into `segs`, their planes.  A picture's status that is not 0
+ * (its restart markers do not add up) is returned */
+int huff_sync_job(const HuffCall &c, SyncJob &job, std::vector<SyncSeg> &segs, int part, int lo, int hi)
+{
+    job.sub_bits = c.sub_bits;
+    job.dev = c.dev; job.o_tabs = c.L.o_tabs; job.o_l12 = c.L.o_l12; job.o_status = c.L.o_status + (size_t)lo * 4; job.n = hi - lo; job.part = part;
+    job.images = c.images.data() + lo;
+    segs.clear();
+    for (int i = lo; i < hi; i++) {
+        const HuffImage &im = c.images[(size_t)i];
+        const std::vector<uint32_t> &sgv = c.segs[(size_t)i];
+        if (c.status[i]) return c.status[i];
+        for (uint32_t k = 0; k < im.n_seg; k++) {
+            SyncSeg sg;
+            sg.pic = (uint32_t)(i - lo);
+            sg.scan_off = im.scan_off + sgv[k];
+            sg.clean_len = sgv[k + 1] - sgv[k];
+            sg.raw_len = c.raws[(size_t)i][k];
+            sg.mcu0 = (uint32_t)((size_t)(c.mcu_base[(size_t)i] - c.mcu_base[(size_t)lo]) + (size_t)k * im.restart);
+            const size_t left = im.mcus - (size_t)k * im.restart;
+            sg.mcus = (uint32_t)(left < im.restart ? left : im.restart);
+            segs.push_back(sg);
+        }
+    }
+    job.segs = segs.data();
+    job.n_segs = segs.size();
+    const size_t base = c.mcu_base[(size_t)lo];
+    job.plane[0] = c.d_coef_y + base * c.images[0].nb[0] * 64;
+    job.plane[1] = c.d_coef_u ? c.d_coef_u + base * c.images[0].nb[1] * 64 : nullptr;
+    job.plane[2] = c.d_coef_v ? c.d_coef_v + base * c.images[0].nb[2] * 64 : nullptr;
+    return FFHIP_OK;
+}
+/* ---- the subsequence decoder, the batch in parts: it starts on a part as soon as that part's bytes are up, so the tail of the image goes first ---- */
+int huff_decode_subsequences(HuffCall &c)
+{
+    const int n_parts = huff_sync_part_count(c);
+    SyncJob jobs[FFHIP_HUFF_PARTS];
+    std::vector<SyncSeg> part_segs[FFHIP_HUFF_PARTS];
+    uint32_t *h_cnt[FFHIP_HUFF_PARTS];
+    for (int i = 0; i < c.n; i++) memcpy(c.stage + c.L.o_quant + (size_t)i * 512, c.hdr[(size_t)i].quant, 512);
+    int rc = huff_tail_up(c);
+    if (rc) return rc;
+    (void)hipEventRecord(c.time_ev[0], c.st);
+    /* the parts' kernels alternate between the caller's stream and one of the library's: the list rounds of a part are a handful of sparse kernels
+     * that each take as long as one lane takes for its subsequence, and run under the next part's full rounds instead of in front of them
+     * (FFHIP_JPEG_SYNC_STREAMS=1: all on the caller's) */
+    const char *ss = FFHIP_ENV("FFHIP_JPEG_SYNC_STREAMS");
+    const bool two_streams = n_parts > 1 && !(ss && ss[0] == '1');
+    if (two_streams) { /* behind the plane clears, the tables and the quantiser copy */
+        HUFF_TRY(hipEventRecord(c.fork, c.st));
+        HUFF_TRY(hipStreamWaitEvent(c.second, c.fork, 0));
+    }
+    for (int part = 0; part < n_parts; part++) {
+        const int lo = huff_part_lo(c, n_parts, part), hi = huff_part_lo(c, n_parts, part + 1);
+        SyncJob &job = jobs[part];
+        const size_t b0 = huff_scan_end(c, lo), b1 = huff_scan_end(c, hi);
+        huff_stage_pictures(c, lo, hi, false);
+        /* the part's bytes go up on a stream of their own, the copy engine's, while the rounds of the parts before run: 256 4K files are
+         * 8 ms of PCIe and 11 ms of kernels */
+        job.stream = two_streams && (part & 1) ? (void *)c.second : c.st; /* this part's kernels */
+        HUFF_TRY(hipMemcpyAsync(c.dev + b0, c.stage + b0, b1 - b0, hipMemcpyHostToDevice, c.up));
+        HUFF_TRY(hipEventRecord(c.part_ev[part], c.up));
+        HUFF_TRY(hipStreamWaitEvent((hipStream_t)job.stream, c.part_ev[part], 0));
+        rc = huff_sync_job(c, job, part_segs[part], part, lo, hi);
+        if (!rc) rc = huff_sync_enqueue(job, job.stream, &h_cnt[part]);
+        if (!rc && c.then) rc = huff_reconstruct(c, lo, hi, job.stream, part); /* the part's pictures: coefficients -> BGRA while the next part's bytes come up */
+        if (rc) return rc;
+    }
+    if (two_streams) { /* the caller's stream is behind everything again */
+        HUFF_TRY(hipEventRecord(c.join, c.second));
+        HUFF_TRY(hipStreamWaitEvent(c.st, c.join, 0));
+    }
+    c.T3 = c.T4 = huff_now();
+    c.staging_us = us(c.T2, c.T3) - c.tables_us; /* (the tail went up inside that span) */
+    HUFF_TRY(hipGetLastError()); /* (of a launch that reported none itself) */
+    (void)hipEventRecord(c.time_ev[1], c.st);
+    rc = huff_collect(c);
+    if (rc) return rc;
+    for (int part = 0; part < n_parts; part++) {
+        SyncJob &job = jobs[part];
+        const int lo = huff_part_lo(c, n_parts, part);
+        rc = huff_sync_finish(job, job.stream, h_cnt[part], c.status + lo);
+        if (!rc && job.reran && c.then) { /* the part's passes ran only now: so must its reconstruction (and the caller's stream be behind it) */
+            rc = huff_reconstruct(c, lo, lo + job.n, job.stream, part);
+            if (!rc && job.stream != c.st && hipStreamSynchronize((hipStream_t)job.stream) != hipSuccess) rc = FFHIP_EIO;
+        }
+        if (rc) return rc;
+        if (c.times) fprintf(stderr, "huff sync, part %d: %u subsequences of %u bits, %u rounds\n", part, job.n_tasks, job.sub_bits, job.rounds_used);
+    }
+    return FFHIP_OK;
+}
+} // namespace
+
 /* then: reconstruct the pictures into then->bgra behind each part of the batch as it is decoded (ffhip_jpeg_decode_files_device) */
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
                                 const ffhip_jpeg_geom *geoms, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant,
@@ -414,357 +800,37 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
 {
     if (n < 0 || !geom || (n > 0 && (!files || !lens || !d_coef_y || !d_quant || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    if (geom->ncomp == 3 && (!d_coef_u || !d_coef_v)) return FFHIP_EINVAL;
-    if (n_threads < 1) n_threads = 1;
-    if (n_threads > 64) n_threads = 64;
-    if (geom->mcu_cols <= 0 || geom->mcu_rows <= 0 || geom->h < 1 || geom->v < 1 || geom->h * geom->v > 4 ||
-        (geom->ncomp != 1 && geom->ncomp != 3)) return FFHIP_EINVAL;
-    /* per picture its MCUs and where its blocks start: one geometry (geoms NULL) or pictures of one layout class that differ in size */
-    std::vector<uint32_t> pic_mcus((size_t)n), mcu_base((size_t)n + 1);
-    {
-        size_t sum = 0;
-        for (int i = 0; i < n; i++) {
-            const ffhip_jpeg_geom *gi = geoms ? &geoms[i] : geom;
-            if (geoms && (gi->ncomp != geom->ncomp || gi->h != geom->h || gi->v != geom->v || gi->mcu_cols <= 0 || gi->mcu_rows <= 0)) return FFHIP_EINVAL;
-            pic_mcus[(size_t)i] = (uint32_t)((size_t)gi->mcu_cols * gi->mcu_rows);
-            mcu_base[(size_t)i] = (uint32_t)sum;
-            sum += pic_mcus[(size_t)i];
-            if (sum > 0xffffffffu) return FFHIP_EINVAL;
-        }
-        mcu_base[(size_t)n] = (uint32_t)sum;
-    }
-    const size_t total_mcus = mcu_base[(size_t)n];
-    const bool times = FFHIP_ENV("FFHIP_HUFF_TIMES") != nullptr; /* host phases on stderr */
-    const auto T0 = std::chrono::steady_clock::now();
-    /* ---- host, pictures over threads: headers, tables, restart-interval starts ---- */
-    struct jpeg_hdr *const hdr = ffhip_huff_hdr_records((size_t)n); /* the calling thread's, kept between calls */
-    if (!hdr) return FFHIP_ENOMEM;
-    std::vector<std::vector<uint32_t>> segs((size_t)n);
-    std::vector<std::vector<uint32_t>> raws((size_t)n); /* per picture: its intervals' own lengths */
-    parallel_for(n, n_threads, [&](int i) {
-        struct jpeg_hdr &j = hdr[(size_t)i];
-        status[i] = ffhip_jpeg_parse(files[i], lens[i], &j);
-        if (status[i]) return;
-        const int mc = (j.width + 8 * j.h[0] - 1) / (8 * j.h[0]), mr = (j.height + 8 * j.v[0] - 1) / (8 * j.v[0]);
-        const ffhip_jpeg_geom *gi = geoms ? &geoms[i] : geom;
-        const size_t mcus = pic_mcus[(size_t)i];
-        if (mc != gi->mcu_cols || mr != gi->mcu_rows || j.ncomp != gi->ncomp || j.h[0] != gi->h || j.v[0] != gi->v ||
-            j.scan_len > 0x7fffffffu) {
-            status[i] = FFHIP_EINVAL; /* another geometry */
-            return;
-        }
-        if (!j.restart) j.restart = (int)mcus; /* no DRI: the whole scan is one interval */
-        /* the interval starts are found while the bytes are staged (stage_scan) */
-        segs[(size_t)i].assign((size_t)((mcus + j.restart - 1) / j.restart) + 1, 0u); /* (one more: the end of the last) */
-        raws[(size_t)i].assign(segs[(size_t)i].size(), 0u);
-    });
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    /* the subsequence decoder: a lane per 2048 bits of a restart interval (of the whole scan, in a file without restart markers), brought into step with
-     * each other over rounds.  FFHIP_JPEG_SYNC=0: the kernel above, a lane per restart interval -- a file without markers is ONE lane's then */
-    const char *sy = FFHIP_ENV("FFHIP_JPEG_SYNC");
-    bool use_sync = !(sy && sy[0] == '0');
-    /* the subsequences' length is worked out ONCE, from the batch's scan bytes: the choice of kernel below and every part's passes go by the same figure */
-    unsigned long long batch_bits = 0;
-    for (int i = 0; i < n; i++) batch_bits += 8ull * hdr[(size_t)i].scan_len;
-    const uint32_t sub_bits = sync_sub_bits(batch_bits, (unsigned long long)total_mcus);
-    if (use_sync && !(sy && sy[0] == '1')) {
-        /* restart intervals of a subsequence or two (a DRI of one or a few MCUs: 32 400 intervals in a 4K picture) are lanes enough as they are, every
-         * one starting from the truth: three passes, a 60-byte record per interval and rounds that have nothing to settle are the wrong tool; the kernel
-         * above takes such batches (FFHIP_JPEG_SYNC=1 keeps the subsequence decoder on them) */
-        unsigned long long n_int = 0;
-        for (int i = 0; i < n; i++) n_int += segs[(size_t)i].size() - 1;
-        if (batch_bits <= 2ull * sub_bits * n_int) use_sync = false;
-    }
-    const auto T1 = std::chrono::steady_clock::now();
-    /* ---- layout of the one upload: scan bytes | tables | picture records | interval starts | work list | status ---- */
-    std::vector<HuffImage> images((size_t)n);
-    /* pictures of a batch mostly share their Huffman tables (an encoder's defaults): keep one copy of each distinct table */
-    std::vector<const struct huff *> uniq;
-    auto table_id = [&](const struct huff *t) -> uint32_t {
-        for (size_t u = uniq.size(); u-- > 0;) /* newest first: the previous picture's are the likely match */
-            if (uniq[u] == t || !memcmp(&uniq[u]->maxcode, &t->maxcode, offsetof(struct huff, fast) - offsetof(struct huff, maxcode))) return (uint32_t)u; /* (look[] and fast[] follow from the rest) */
-        uniq.push_back(t);
-        return (uint32_t)(uniq.size() - 1);
-    };
-    size_t scan_total = 0, seg_total = 0;
-    for (int i = 0; i < n; i++) {
-        const struct jpeg_hdr &j = hdr[(size_t)i];
-        HuffImage &im = images[(size_t)i];
-        im.scan_off = (uint32_t)scan_total;
-        im.scan_len = (uint32_t)j.scan_len;
-        im.restart = (uint32_t)j.restart;
-        im.mcus = pic_mcus[(size_t)i];
-        im.mcu_base = mcu_base[(size_t)i];
-        im.ncomp = (uint32_t)j.ncomp;
-        im.seg_base = (uint32_t)seg_total;
-        im.n_seg = (uint32_t)segs[(size_t)i].size() - 1;
-        for (int c = 0; c < 3; c++) {
-            im.nb[c] = c < j.ncomp ? (uint32_t)(j.h[c] * j.v[c]) : 0;
-            im.tab_dc[c] = table_id(&j.dc[c < j.ncomp ? j.td[c] : j.td[0]]);
-            im.tab_ac[c] = table_id(&j.ac[c < j.ncomp ? j.ta[c] : j.ta[0]]);
-        }
-        scan_total += (j.scan_len + 8 * (size_t)im.n_seg + 64 + 15) & ~(size_t)15; /* unstuffed, every interval aligned and padded, slack for the 16-byte stores */
-        seg_total += im.n_seg;
-        im.seg_base += (uint32_t)i; /* one more entry per picture: the end of its last interval */
-        if (scan_total > 0x7fffffffu) return FFHIP_EINVAL;
-    }
-    if (!ffhip_have_device()) return FFHIP_ENODEV;
-    const size_t n_tabs = uniq.size();
-    if (n_tabs > 4095) return FFHIP_EINVAL; /* table indices travel in 12 bits */
-    const size_t o_tabs = scan_total + 16, o_l12 = (o_tabs + n_tabs * sizeof(struct huff) + 15) & ~(size_t)15;
-    const size_t o_img = o_l12 + n_tabs * LUT_WORDS * 2;
-    const size_t o_seg = (o_img + images.size() * sizeof(HuffImage) + 15) & ~(size_t)15, o_work = (o_seg + (seg_total + (size_t)n) * 4 + 15) & ~(size_t)15;
-    const size_t o_status = (o_work + seg_total * 8 + 15) & ~(size_t)15, o_quant = (o_status + (size_t)n * 4 + 15) & ~(size_t)15;
-    const size_t total = o_quant + (size_t)n * 512;
-    /* pinned staging and device image are kept per stream: callers on different streams overlap completely */
-    uint8_t *stage = ffhip_pinned_scratch(SCRATCH_HUFF, stream, total + 64);
-    if (!stage) return FFHIP_ENOMEM;
-    const auto T2 = std::chrono::steady_clock::now();
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_HUFF, stream, (total + 3) / 4);
-    if (!dev) return FFHIP_ENOMEM;
-    /* the pictures are staged a quarter of the batch at a time and each quarter's bytes go up while the next is
-     * being unstuffed: the upload (8 ms for 256 4K files) hides behind the staging (7 ms) instead of following it */
-    /* the kernel stores the non-zero coefficients only: the planes are cleared first -- enqueued here, so that the
-     * clears (4.8 GB for 256 4K pictures) run while the host is still staging */
-    {
-        const size_t yb = total_mcus * geom->h * geom->v * 64;
-        FFHIP_CHECK(hipMemsetAsync(d_coef_y, 0, yb * 2, st), FFHIP_EIO);
-        if (geom->ncomp == 3) {
-            FFHIP_CHECK(hipMemsetAsync(d_coef_u, 0, total_mcus * 128, st), FFHIP_EIO);
-            FFHIP_CHECK(hipMemsetAsync(d_coef_v, 0, total_mcus * 128, st), FFHIP_EIO);
-        }
-    }
-    auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
-    /* tables, picture records, status, quantiser tables: behind the scan bytes in the image.  The files with markers send them last (the interval lists are
-     * found while staging); the subsequence decoder first, because it starts on a part of the batch as soon as that part's bytes are up */
-    long tables_us = 0;
-    auto tail_up = [&]() -> int {
-        const auto Ta = std::chrono::steady_clock::now();
-        memset(stage + scan_total, 0, 16);
-        parallel_for((int)n_tabs, n_threads, [&](int u) {
-            ((struct huff *)(stage + o_tabs))[u] = *uniq[(size_t)u];
-            build_lut(*uniq[(size_t)u], (uint16_t *)(stage + o_l12) + (size_t)u * LUT_WORDS);
-        });
-        memcpy(stage + o_img, images.data(), images.size() * sizeof(HuffImage));
-        memset(stage + o_status, 0, (size_t)n * 4);
-        tables_us = us(Ta, std::chrono::steady_clock::now());
-        FFHIP_CHECK(hipMemcpyAsync(dev + scan_total, stage + scan_total, total - scan_total, hipMemcpyHostToDevice, st), FFHIP_EIO);
-        FFHIP_CHECK(hipMemcpyAsync(d_quant, dev + o_quant, (size_t)n * 512, hipMemcpyDeviceToDevice, st), FFHIP_EIO);
-        return FFHIP_OK;
-    };
+    HuffCall c{files, lens, n, n_threads, geom, geoms, d_coef_y, d_coef_u, d_coef_v, d_quant, status, (hipStream_t)stream, then}; /* (the rest: empty) */
+    int rc = huff_check(c);
+    if (rc) return rc;
+    c.times = FFHIP_ENV("FFHIP_HUFF_TIMES") != nullptr;
+    c.T0 = huff_now();
+    rc = huff_parse_headers(c);
+    if (rc) return rc;
+    const bool subsequences = huff_choose_subsequences(c);
+    c.T1 = huff_now();
+    rc = huff_lay_out(c);
+    if (rc) return rc;
+    rc = huff_clear_planes(c);
+    if (rc) return rc;
     FfhipHuffStreams hs;
     if (ffhip_huff_streams_get(&hs) != FFHIP_OK) return FFHIP_EIO; /* (nothing of this call is enqueued yet but the plane clears, which touch no buffer of the library's) */
-    const hipStream_t g_huff_up = (hipStream_t)hs.up, g_huff_c2 = (hipStream_t)hs.c2;
-    hipEvent_t *const g_huff_part_ev = (hipEvent_t *)hs.part_ev;
-    const hipEvent_t g_huff_fork = (hipEvent_t)hs.fork, g_huff_join = (hipEvent_t)hs.join;
-    const hipEvent_t g_huff_ev[2] = {(hipEvent_t)hs.time_ev[0], (hipEvent_t)hs.time_ev[1]};
-    /* every failure behind this point leaves through `fail`: uploads, part kernels or a `then` reconstruction into the caller's pixels may be in flight,
-     * and the pinned stage, the device image and the parts' scratch are refilled by the thread's next call */
-    auto fail = [&](int code) -> int {
-        (void)hipStreamSynchronize(g_huff_up);
-        (void)hipStreamSynchronize(g_huff_c2);
-        (void)hipStreamSynchronize(st);
+    c.up = (hipStream_t)hs.up; c.second = (hipStream_t)hs.c2;
+    c.part_ev = (hipEvent_t *)hs.part_ev;
+    c.fork = (hipEvent_t)hs.fork; c.join = (hipEvent_t)hs.join;
+    c.time_ev[0] = (hipEvent_t)hs.time_ev[0]; c.time_ev[1] = (hipEvent_t)hs.time_ev[1];
+    rc = subsequences ? huff_decode_subsequences(c) : huff_decode_intervals(c);
+    if (rc) {
+        /* The one exit of every failure of either decoder: uploads, part kernels or a `then` reconstruction into the caller's pixels may be in flight,
+         * and the pinned stage, the device image and the parts' scratch are refilled by the thread's next call.  Nothing of this call may be in flight
+         * when its buffers are handed back. */
+        (void)hipStreamSynchronize(c.up);
+        (void)hipStreamSynchronize(c.second);
+        (void)hipStreamSynchronize(c.st);
         (void)hipGetLastError();
-        return code;
-    };
-#define HUFF_CHECK(call) do { if ((call) != hipSuccess) return fail(FFHIP_EIO); } while (0)
-    /* pictures [lo, hi) from their planes to then's BGRA on `on`: one geometry, one ffhip_jpeg_recon_batch; items, one ffhip_jpeg_recon_items (scratch
-     * slot `part`: the parts' calls are in flight side by side) */
-    std::vector<ffhip_jpeg_item> then_items;
-    auto recon_then = [&](int lo, int hi, void *on, int part) -> int {
-        if (!then->items) {
-            const size_t mcus = pic_mcus[0];
-            return ffhip_jpeg_recon_batch(geom, hi - lo, d_coef_y + (size_t)lo * mcus * geom->h * geom->v * 64, d_coef_u ? d_coef_u + (size_t)lo * mcus * 64 : nullptr,
-                                          d_coef_v ? d_coef_v + (size_t)lo * mcus * 64 : nullptr, d_quant + (size_t)lo * 256, 256,
-                                          then->bgra + (int64_t)lo * then->image_stride, then->pitch, then->image_stride, nullptr, 0, on);
-        }
-        then_items.assign(then->items + lo, then->items + hi);
-        for (int i = lo; i < hi; i++) {
-            ffhip_jpeg_item &it = then_items[(size_t)(i - lo)];
-            const size_t b = mcu_base[(size_t)i];
-            it.d_coef_y = d_coef_y + b * geom->h * geom->v * 64;
-            it.d_coef_u = d_coef_u ? d_coef_u + b * 64 : nullptr;
-            it.d_coef_v = d_coef_v ? d_coef_v + b * 64 : nullptr;
-            it.d_quant = d_quant + (size_t)i * 256;
-        }
-        return jpeg_recon_items_impl(then_items.data(), hi - lo, on, part);
-    };
-    int n_parts = n >= 32 ? 4 : 1;
-    if (use_sync) {
-        /* parts of about 140 MB of scan bytes, a hundred 4K files -- a round over fewer subsequences fills the chip badly, and what is left to wait for
-         * behind the last upload are the last part's kernels: 256 4K files 13.7-14.0 ms in three parts, 14.0-14.5 in four, 14.2 in two, 14.4-14.5 in six (and 14.7-14.9 in four of
-         * 1/8, 3/8, 3/8, 1/8 of the files, which looked good on paper) */
-        const int by_bytes = (int)((scan_total + (70u << 20)) / (140u << 20)); /* (by bytes, not by files: 4 096 thumbnails are a hundred megabytes) */
-        n_parts = n < 32 || scan_total < (16u << 20) ? 1 : by_bytes < 2 ? 2 : by_bytes > SYNC_PARTS ? SYNC_PARTS : by_bytes;
-        const char *e = FFHIP_ENV("FFHIP_JPEG_SYNC_PARTS"); /* parts of the batch that are staged, sent and decoded one behind the other (1..8) */
-        if (e && atoi(e) >= 1) n_parts = atoi(e) > SYNC_PARTS ? SYNC_PARTS : atoi(e);
-        if (n_parts > n) n_parts = n;
+        return rc;
     }
-    SyncJob jobs[SYNC_PARTS];
-    bool two_streams = false;
-    std::vector<SyncSeg> part_segs[SYNC_PARTS];
-    uint32_t *h_cnt[SYNC_PARTS];
-    if (use_sync) {
-        /* the parts' bytes go up on a stream of their own, the copy engine's, while the rounds of the parts before run on the caller's: 256 4K files are
-         * 8 ms of PCIe and 11 ms of kernels */
-        for (int i = 0; i < n; i++) memcpy(stage + o_quant + (size_t)i * 512, hdr[(size_t)i].quant, 512);
-        const int rc = tail_up();
-        if (rc) return fail(rc);
-        (void)hipEventRecord(g_huff_ev[0], st);
-        /* the parts' kernels alternate between the caller's stream and one of the library's: the list rounds of a part are a handful of sparse kernels
-         * that each take as long as one lane takes for its subsequence, and run under the next part's full rounds instead of in front of them
-         * (FFHIP_JPEG_SYNC_STREAMS=1: all on the caller's) */
-        const char *ss = FFHIP_ENV("FFHIP_JPEG_SYNC_STREAMS");
-        two_streams = n_parts > 1 && !(ss && ss[0] == '1');
-        if (two_streams) HUFF_CHECK(hipEventRecord(g_huff_fork, st)); /* behind the plane clears, the tables and the quantiser copy */
-        if (two_streams) HUFF_CHECK(hipStreamWaitEvent(g_huff_c2, g_huff_fork, 0));
-    }
-    auto part_lo = [&](int part) -> int { return (int)((long long)n * part / n_parts); };
-    for (int part = 0; part < n_parts; part++) {
-    const int p_lo = part_lo(part), p_hi = part_lo(part + 1);
-    parallel_for(p_hi - p_lo, n_threads, [&](int i_rel) {
-        const int i = p_lo + i_rel;
-        const struct jpeg_hdr &j = hdr[(size_t)i];
-        const HuffImage &im = images[(size_t)i];
-        /* the picture's bytes, unstuffed, every restart interval 4-byte aligned and followed by >= 4 zero bytes */
-        uint8_t *dst = stage + im.scan_off;
-        std::vector<uint32_t> &sgv = segs[(size_t)i];
-        size_t off = 0;
-        if (stage_scan(dst, j.scan, j.scan + j.scan_len, sgv.data(), im.n_seg, &off, raws[(size_t)i].data()) != im.n_seg) status[i] = FFHIP_EINVAL;
-        memset(dst + off, 0, 16);
-        sgv[im.n_seg] = (uint32_t)off;
-        if (use_sync) return; /* (the interval lists stay on the host; the tail of the image is on its way already) */
-        uint32_t *sg = (uint32_t *)(stage + o_seg) + im.seg_base;
-        u32x2 *wk = (u32x2 *)(stage + o_work) + (im.seg_base - (uint32_t)i);
-        for (uint32_t k = 0; k < im.n_seg; k++) {
-            sg[k] = segs[(size_t)i][k];
-            wk[k].x = (uint32_t)i;
-            wk[k].y = k;
-        }
-        sg[im.n_seg] = (uint32_t)off;
-        memcpy(stage + o_quant + (size_t)i * 512, j.quant, 512);
-    });
-    {
-        const size_t b0 = images[(size_t)p_lo].scan_off, b1 = p_hi < n ? images[(size_t)p_hi].scan_off : scan_total;
-        if (!use_sync) {
-            HUFF_CHECK(hipMemcpyAsync(dev + b0, stage + b0, b1 - b0, hipMemcpyHostToDevice, st));
-        } else {
-            SyncJob &job = jobs[part];
-            int rc = FFHIP_OK;
-            void *const pstream = two_streams && (part & 1) ? (void *)g_huff_c2 : stream; /* this part's kernels */
-            job.stream = pstream;
-            if (hipMemcpyAsync(dev + b0, stage + b0, b1 - b0, hipMemcpyHostToDevice, g_huff_up) != hipSuccess || hipEventRecord(g_huff_part_ev[part], g_huff_up) != hipSuccess ||
-                hipStreamWaitEvent((hipStream_t)pstream, g_huff_part_ev[part], 0) != hipSuccess) rc = FFHIP_EIO;
-            if (!rc) {
-                job.sub_bits = sub_bits;
-                job.dev = dev; job.o_tabs = o_tabs; job.o_l12 = o_l12; job.o_status = o_status + (size_t)p_lo * 4; job.n = p_hi - p_lo; job.part = part;
-                job.images = images.data() + p_lo;
-                part_segs[part].clear();
-                for (int i = p_lo; i < p_hi && !rc; i++) {
-                    const HuffImage &im = images[(size_t)i];
-                    const std::vector<uint32_t> &sgv = segs[(size_t)i];
-                    if (status[i]) { rc = status[i]; break; } /* a file whose restart markers do not add up */
-                    for (uint32_t k = 0; k < im.n_seg; k++) {
-                        SyncSeg sg;
-                        sg.pic = (uint32_t)(i - p_lo);
-                        sg.scan_off = im.scan_off + sgv[k];
-                        sg.clean_len = sgv[k + 1] - sgv[k];
-                        sg.raw_len = raws[(size_t)i][k];
-                        sg.mcu0 = (uint32_t)((size_t)(mcu_base[(size_t)i] - mcu_base[(size_t)p_lo]) + (size_t)k * im.restart);
-                        const size_t left = im.mcus - (size_t)k * im.restart;
-                        sg.mcus = (uint32_t)(left < im.restart ? left : im.restart);
-                        part_segs[part].push_back(sg);
-                    }
-                }
-                job.segs = part_segs[part].data();
-                job.n_segs = part_segs[part].size();
-                if (rc) return fail(rc);
-                const size_t base = mcu_base[(size_t)p_lo];
-                job.plane[0] = d_coef_y + base * images[0].nb[0] * 64;
-                job.plane[1] = d_coef_u ? d_coef_u + base * images[0].nb[1] * 64 : nullptr;
-                job.plane[2] = d_coef_v ? d_coef_v + base * images[0].nb[2] * 64 : nullptr;
-                rc = huff_sync_enqueue(job, pstream, &h_cnt[part]);
-                if (!rc && then) /* the part's pictures: coefficients -> BGRA while the next part's bytes come up */
-                    rc = recon_then(p_lo, p_hi, pstream, part);
-            }
-            if (rc) return fail(rc); /* nothing of this call may be in flight when its buffers are handed back */
-        }
-    }
-    } /* parts */
-    if (two_streams) { /* the caller's stream is behind everything again */
-        HUFF_CHECK(hipEventRecord(g_huff_join, g_huff_c2));
-        HUFF_CHECK(hipStreamWaitEvent(st, g_huff_join, 0));
-    }
-    for (int i = 0; i < n; i++)
-        if (status[i]) return fail(status[i]); /* a file whose restart markers do not add up: nothing is decoded */
-    const auto T3 = std::chrono::steady_clock::now();
-    if (!use_sync) {
-        const int rc = tail_up();
-        if (rc) return fail(rc);
-    }
-    const auto T4 = std::chrono::steady_clock::now();
-    if (times) {
-        fprintf(stderr, "huff staging: header parse %ld us, layout %ld us, unstuff + markers (uploads enqueued by parts) %ld us, tables %ld us (%d files, %zu bytes, %d threads)\n", us(T0, T1), us(T1, T2), us(T2, T3) - (use_sync ? tables_us : 0), tables_us, n, total, n_threads);
-    }
-    HuffArgs a;
-    a.scan = dev;
-    a.tabs = (const struct huff *)(dev + o_tabs);
-    a.lut = (const uint16_t *)(dev + o_l12);
-    a.images = (const HuffImage *)(dev + o_img);
-    a.seg = (const uint32_t *)(dev + o_seg);
-    a.work = (const u32x2 *)(dev + o_work);
-    a.plane[0] = d_coef_y; a.plane[1] = d_coef_u; a.plane[2] = d_coef_v;
-    a.status = (int *)(dev + o_status);
-    a.n_work = (uint32_t)seg_total;
-    if (!use_sync) (void)hipEventRecord(g_huff_ev[0], st);
-    if (!use_sync)
-    {   /* 128-byte rings (two workgroups of four waves per CU) while that holds the whole batch at once; 64-byte rings (three per CU, a refill every 8 symbols instead
-         * of 16) beyond: 256 4K files of 135 intervals 9.9 ms against 10.4, 1 024 files 25.2 against 20.2 */
-        int cus = 256, dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const unsigned wgs = (a.n_work + 255) / 256;
-        const char *fr = FFHIP_ENV("FFHIP_HUFF_RING"); /* =16 / =32 forces either */
-        if (fr ? atoi(fr) == 16 : wgs > 2u * (unsigned)cus) hipLaunchKernelGGL((k_jpeg_huff<16, 8>), dim3(wgs), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_jpeg_huff<32, 16>), dim3(wgs), dim3(256), 0, st, a);
-    }
-    HUFF_CHECK(hipGetLastError());
-    (void)hipEventRecord(g_huff_ev[1], st);
-    if (!use_sync && then) {
-        const int rc = recon_then(0, n, stream, 0);
-        if (rc) return fail(rc);
-    }
-    /* per-picture verdicts come back with the stream (tiny); the staging buffer is free again after this sync */
-    HUFF_CHECK(hipMemcpyAsync(stage + o_status, dev + o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    const auto T5 = std::chrono::steady_clock::now();
-    HUFF_CHECK(hipStreamSynchronize(st));
-    const auto T6 = std::chrono::steady_clock::now();
-    if (times)
-        fprintf(stderr, "huff device: enqueue %ld us, wait for uploads + clears + kernel %ld us\n", us(T3, T5), us(T5, T6));
-    {
-        float kms = 0.0f;
-        if (hipEventElapsedTime(&kms, g_huff_ev[0], g_huff_ev[1]) != hipSuccess) { (void)hipGetLastError(); kms = 0.0f; }
-        g_huff_times[0] = (double)us(T0, T1); g_huff_times[1] = (double)us(T1, T2); g_huff_times[2] = (double)(us(T2, T3) - (use_sync ? tables_us : 0)); g_huff_times[3] = (double)tables_us;
-        g_huff_times[4] = (double)us(T4, T5); g_huff_times[5] = (double)us(T5, T6); g_huff_times[6] = (double)kms * 1e3; g_huff_times[7] = (double)us(T0, T6);
-    }
-    memcpy(status, stage + o_status, (size_t)n * 4);
-    if (use_sync)
-        for (int part = 0; part < n_parts; part++) {
-            SyncJob &job = jobs[part];
-            const int p_lo = (int)((job.o_status - o_status) / 4);
-            int rc = huff_sync_finish(job, job.stream, h_cnt[part], status + p_lo);
-            if (!rc && job.reran && then) { /* the part's passes ran only now: so must its reconstruction (and the caller's stream be behind it) */
-                rc = recon_then(p_lo, p_lo + job.n, job.stream, part);
-                if (!rc && job.stream != stream && hipStreamSynchronize((hipStream_t)job.stream) != hipSuccess) rc = FFHIP_EIO;
-            }
-            if (rc) return fail(rc);
-            if (times) fprintf(stderr, "huff sync, part %d: %u subsequences of %u bits, %u rounds\n", part, job.n_tasks, job.sub_bits, job.rounds_used);
-        }
-    for (int i = 0; i < n; i++)
-        if (status[i]) return status[i];
-    return FFHIP_OK;
-#undef HUFF_CHECK
+    return huff_first_status(c);
 }
 extern "C" int ffhip_jpeg_entropy_batch_gpu(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
                                             const ffhip_jpeg_geom *geom, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v,

@@ -7,6 +7,7 @@
 
 #include <map>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #include "ffpic_hip.h"
@@ -53,6 +54,19 @@ int ffhip_resident_waves(const void *kernel, int block_threads); /* workgroups o
 #ifdef __cplusplus
 #define FFHIP_ENV(NAME) ([]() -> const char * { static struct ffhip_env_site site = {NAME, -1, nullptr}; return ffhip_env_lookup(&site); }())
 #endif
+
+/* f(i) for every i < count over n_threads host threads, strided: thread t takes i = t, t + n_threads, ...; the calling thread is thread 0,
+ * and one thread (or one item) runs inline */
+template <class F> void ffhip_parallel_for(int count, int n_threads, F f)
+{
+    if (n_threads > count) n_threads = count;
+    if (n_threads <= 1) { for (int i = 0; i < count; i++) f(i); return; }
+    std::vector<std::thread> pool;
+    auto part = [&](int t) { for (int i = t; i < count; i += n_threads) f(i); };
+    for (int t = 1; t < n_threads; t++) pool.emplace_back(part, t);
+    part(0);
+    for (auto &th : pool) th.join();
+}
 
 typedef unsigned int u32;
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
@@ -150,6 +164,15 @@ int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens,
 int jpeg_item_class(const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch); /* the layout class 0..6 of a picture ffhip_jpeg_recon_items takes
                                                                                         with this output and pitch, -1 if it refuses it */
 int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot); /* ffhip_jpeg_recon_items with scratch slot 0..FFHIP_HUFF_PARTS-1 */
+/* the plane and quantiser pointers of picture `index` of a call whose planes hold its pictures one behind the other: the picture's blocks start
+ * at MCU `mcu_base` of y / u / v (u, v NULL for grey), its tables are the index-th 256 of q */
+inline void jpeg_item_planes(ffhip_jpeg_item *it, const int16_t *y, const int16_t *u, const int16_t *v, const uint16_t *q, size_t mcu_base, size_t index)
+{
+    it->d_coef_y = y + mcu_base * it->geom.h * it->geom.v * 64;
+    it->d_coef_u = u ? u + mcu_base * 64 : nullptr;
+    it->d_coef_v = v ? v + mcu_base * 64 : nullptr;
+    it->d_quant = q + index * 256;
+}
 
 /* ---- what the library keeps between calls (ffhip_state.hip) ---- */
 /* The record of a stream's last side-by-side VP8 call, for its repeat by ffhip_stream_sync (ffhip_vp8_lf.hip); `armed` says whether it

@@ -16,7 +16,7 @@
 #include <string.h>
 
 #include <mutex>
-#include <thread>
+#include <thread> /* copy_out */
 #include <vector>
 
 namespace {
@@ -92,6 +92,43 @@ void copy_out(uint8_t *bgra, int64_t pitch, int64_t image_stride, const uint8_t 
     part(0, nt);
     for (auto &th : pool) th.join();
 }
+
+/* Does the entropy decode of these files go to the device?  FFHIP_JPEG_GPU_ENTROPY=0 keeps it on the host threads and =1 forces it to the device.
+ * Unset, it goes there: the subsequence decoder takes files whatever their restart markers.  Only with FFHIP_JPEG_SYNC=0 -- the kernel with a lane
+ * per restart interval, to which a file without markers is ONE lane, its latency per batch that of one interval -- it takes a batch whose first
+ * file has markers, or a thousand files or more. */
+bool jpeg_entropy_on_device(const uint8_t *file0, size_t len0, int n)
+{
+    const char *ge = FFHIP_ENV("FFHIP_JPEG_GPU_ENTROPY");
+    if (ge && (ge[0] == '0' || ge[0] == '1')) return ge[0] == '1';
+    const char *sy = FFHIP_ENV("FFHIP_JPEG_SYNC");
+    return !(sy && sy[0] == '0') || ffhip_jpeg_probe_restart(file0, len0) > 0 || n >= 1024;
+}
+
+/* Y | U | V | quantiser tables of a batch in one block, device or pinned: yb and cb are the int16 elements of the luma plane and of each chroma
+ * plane (cb 0: grey, no chroma planes), the n pictures' tables lie on a 16-byte boundary behind the planes */
+struct Planes { int16_t *y, *u, *v; uint16_t *q; };
+struct PlaneBlock {
+    size_t yb, cb, q_off, bytes;
+    PlaneBlock(size_t yb_, size_t cb_, size_t n) : yb(yb_), cb(cb_), q_off(((yb_ + 2 * cb_) * 2 + 15) & ~(size_t)15), bytes(q_off + n * 512) {}
+    Planes at(uint8_t *base) const { int16_t *y = (int16_t *)base; return {y, cb ? y + yb : nullptr, cb ? y + yb + cb : nullptr, (uint16_t *)(base + q_off)}; }
+};
+
+/* Host threads Huffman-decode pictures [first, first + cnt) into the slot's pinned planes (yb, cb: int16 elements per picture), then four H2D
+ * copies on the slot's stream.  The decoder's code goes to *result if that holds none yet: per-picture codes are in status[], bad pictures
+ * still occupy their place. */
+int host_decode_chunk(Slot &sl, const uint8_t *const *files, const size_t *lens, int first, int cnt, int n_threads, const ffhip_jpeg_geom &g,
+                      size_t yb, size_t cb, int *status, int *result)
+{
+    const int erc = ffhip_jpeg_entropy_batch(files + first, lens + first, cnt, n_threads, &g, sl.h_y, cb ? sl.h_u : nullptr, cb ? sl.h_v : nullptr, sl.h_q,
+                                             status + first);
+    if (erc && !*result) *result = erc;
+    hipError_t e = hipMemcpyAsync(sl.d_y, sl.h_y, cnt * yb * 2, hipMemcpyHostToDevice, sl.st);
+    if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_u, sl.h_u, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
+    if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_v, sl.h_v, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(sl.d_q, sl.h_q, (size_t)cnt * 512, hipMemcpyHostToDevice, sl.st);
+    return e == hipSuccess ? FFHIP_OK : FFHIP_EIO;
+}
 } // namespace
 
 void ffhip_pipeline_release(void)
@@ -132,14 +169,7 @@ extern "C" int ffhip_jpeg_decode_files(const uint8_t *const *files, const size_t
     if (g.mcu_cols <= 0 || g.mcu_rows <= 0) return FFHIP_EINVAL; /* workspace_bytes is 0 for a geometry it rejects, too */
     if (ffhip_jpeg_workspace_bytes(&g, 1) != 0) return FFHIP_EINVAL; /* one component with several blocks per MCU: not here */
     if (!ffhip_have_device()) return FFHIP_ENODEV;
-    /* the entropy decode runs on the device (FFHIP_JPEG_GPU_ENTROPY=0 keeps it off): the subsequence decoder, whatever the files' restart markers; with
-     * FFHIP_JPEG_SYNC=0, round 4's kernel -- a lane per restart interval, its latency per batch that of ONE interval --, for files that have markers */
-    const char *ge = FFHIP_ENV("FFHIP_JPEG_GPU_ENTROPY");
-    bool gpu_entropy = !(ge && ge[0] == '0');
-    if (gpu_entropy && !(ge && ge[0] == '1')) { /* "1" forces it; default: always, unless files without restart markers are to be one lane each (FFHIP_JPEG_SYNC=0) */
-        const char *sy = FFHIP_ENV("FFHIP_JPEG_SYNC");
-        gpu_entropy = !(sy && sy[0] == '0') || ffhip_jpeg_probe_restart(files[0], lens[0]) > 0 || n >= 1024;
-    }
+    const bool gpu_entropy = jpeg_entropy_on_device(files[0], lens[0], n);
     if (chunk <= 0) {
         /* a chunk is a device call and a stream sync: 32 pictures of 4K (a gigabyte of BGRA per slot), and as many small pictures as make 256 MB of BGRA
          * -- 1 024 thumbnails of 256x256, not 32 */
@@ -181,9 +211,9 @@ extern "C" int ffhip_jpeg_decode_files(const uint8_t *const *files, const size_t
         rc = drain(sl); /* the slot's previous chunk (k - 2) */
         if (rc) break;
         hipError_t e = hipSuccess;
-        /* entropy decode.  Files with restart markers: on the device, one lane per interval, straight into the
-         * device planes (the host only parses headers and finds the markers).  Otherwise, or if that refuses:
-         * host threads into pinned memory, then H2D.  Either way chunk k - 1 is on the GPU meanwhile. */
+        /* entropy decode.  On the device, straight into the device planes (the host only parses headers and unstuffs the
+         * scan bytes), unless the gate keeps the files on the host or the device call refuses them: then host threads
+         * into pinned memory and H2D.  Either way chunk k - 1 is on the GPU meanwhile. */
         bool on_device = false;
         if (gpu_entropy) {
             const int grc = ffhip_jpeg_entropy_batch_gpu(files + first, lens + first, cnt, n_threads, &g, sl.d_y, cb ? sl.d_u : nullptr,
@@ -192,14 +222,8 @@ extern "C" int ffhip_jpeg_decode_files(const uint8_t *const *files, const size_t
             if (!on_device && grc != FFHIP_EINVAL) { rc = grc; break; }
         }
         if (!on_device) {
-            const int erc = ffhip_jpeg_entropy_batch(files + first, lens + first, cnt, n_threads, &g, sl.h_y, cb ? sl.h_u : nullptr,
-                                                     cb ? sl.h_v : nullptr, sl.h_q, status + first);
-            if (erc && !result) result = erc; /* per-picture codes are in status[]; bad pictures still occupy their place */
-            e = hipMemcpyAsync(sl.d_y, sl.h_y, cnt * yb * 2, hipMemcpyHostToDevice, sl.st);
-            if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_u, sl.h_u, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
-            if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_v, sl.h_v, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
-            if (e == hipSuccess) e = hipMemcpyAsync(sl.d_q, sl.h_q, (size_t)cnt * 512, hipMemcpyHostToDevice, sl.st);
-            if (e != hipSuccess) { rc = FFHIP_EIO; break; }
+            rc = host_decode_chunk(sl, files, lens, first, cnt, n_threads, g, yb, cb, status, &result);
+            if (rc) break;
         }
         rc = ffhip_jpeg_recon_batch(&g, cnt, sl.d_y, cb ? sl.d_u : nullptr, cb ? sl.d_v : nullptr, sl.d_q, 256, sl.d_out, (int64_t)dev_pitch,
                                     (int64_t)out_b, nullptr, 0, sl.st);
@@ -243,22 +267,19 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
     const size_t mcus = (size_t)g.mcu_cols * g.mcu_rows;
     const size_t yb = mcus * g.h * g.v * 64, cb = g.ncomp == 3 ? mcus * 64 : 0; /* int16 elements per picture */
     hipStream_t st = (hipStream_t)stream;
-    const char *ge = FFHIP_ENV("FFHIP_JPEG_GPU_ENTROPY");
-    const char *sy = FFHIP_ENV("FFHIP_JPEG_SYNC"); /* =0: files without restart markers are one lane each on the device, worth it from a thousand files only */
-    if (!(ge && ge[0] == '0') && ((ge && ge[0] == '1') || !(sy && sy[0] == '0') || ffhip_jpeg_probe_restart(files[0], lens[0]) > 0 || n >= 1024)) {
-        /* entropy decode on the device, a lane per restart interval, straight into planes in library scratch; one reconstruction launch behind it */
-        const size_t words = ((size_t)n * (yb + 2 * cb) * 2 + (size_t)n * 512 + 64) / 4 + 16;
-        uint8_t *base = (uint8_t *)ffhip_scratch(SCRATCH_FILES_DEV, stream, words);
+    if (jpeg_entropy_on_device(files[0], lens[0], n)) {
+        /* entropy decode on the device, straight into planes in library scratch; the reconstruction is enqueued by the entropy call itself, behind
+         * each part of the batch as it is decoded */
+        const PlaneBlock blk((size_t)n * yb, (size_t)n * cb, (size_t)n);
+        uint8_t *base = (uint8_t *)ffhip_scratch(SCRATCH_FILES_DEV, stream, blk.bytes / 4 + 16);
         if (!base) return FFHIP_ENOMEM;
-        int16_t *dy = (int16_t *)base, *du = cb ? dy + (size_t)n * yb : nullptr, *dv = cb ? du + (size_t)n * cb : nullptr;
-        uint16_t *dq = (uint16_t *)(base + (((size_t)n * (yb + 2 * cb) * 2 + 15) & ~(size_t)15));
-        /* (the reconstruction is enqueued by the entropy call itself, behind each part of the batch as it is decoded) */
+        const Planes d = blk.at(base);
         const FfhipHuffThen then = {d_bgra, pitch, image_stride, nullptr};
-        rc = jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, &g, nullptr, dy, du, dv, dq, status, stream, &then);
+        rc = jpeg_entropy_batch_gpu_impl(files, lens, n, n_threads, &g, nullptr, d.y, d.u, d.v, d.q, status, stream, &then);
         if (rc == FFHIP_OK) return FFHIP_OK;
         if (rc != FFHIP_EINVAL) return rc;
     }
-    /* Host threads (files without restart markers are one interval each: a lane per FILE only pays from a thousand files on).  A pipeline of
+    /* Host threads (the gate's answer, or the device call refused the files).  A pipeline of
      * chunks over the two slots ffhip_jpeg_decode_files uses: while the host threads decode chunk k + 1 into pinned memory, chunk k is copied
      * to the device and reconstructed on the slot's own stream, straight into the caller's d_bgra.  (Until round 5 this path decoded the whole
      * batch into pageable vectors, then uploaded it: 1.84 s for 256 4K files, most of it page faults and a pageable copy of 9.5 GB.)  Everything
@@ -276,14 +297,8 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
         Slot &sl = slot[k & 1];
         const int cnt = n - first < chunk ? n - first : chunk;
         if (hipStreamSynchronize(sl.st) != hipSuccess) { rc = FFHIP_EIO; break; } /* the slot's previous chunk (k - 2) has left its pinned planes */
-        const int erc = ffhip_jpeg_entropy_batch(files + first, lens + first, cnt, n_threads, &g, sl.h_y, cb ? sl.h_u : nullptr, cb ? sl.h_v : nullptr, sl.h_q,
-                                                 status + first);
-        if (erc && !result) result = erc; /* per-picture codes are in status[]; bad pictures still occupy their place */
-        hipError_t e = hipMemcpyAsync(sl.d_y, sl.h_y, cnt * yb * 2, hipMemcpyHostToDevice, sl.st);
-        if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_u, sl.h_u, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
-        if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_v, sl.h_v, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
-        if (e == hipSuccess) e = hipMemcpyAsync(sl.d_q, sl.h_q, (size_t)cnt * 512, hipMemcpyHostToDevice, sl.st);
-        if (e != hipSuccess) { rc = FFHIP_EIO; break; }
+        rc = host_decode_chunk(sl, files, lens, first, cnt, n_threads, g, yb, cb, status, &result);
+        if (rc) break;
         rc = ffhip_jpeg_recon_batch(&g, cnt, sl.d_y, cb ? sl.d_u : nullptr, cb ? sl.d_v : nullptr, sl.d_q, 256, d_bgra + (int64_t)first * image_stride, pitch, image_stride,
                                     nullptr, 0, sl.st);
     }
@@ -305,20 +320,11 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
     if (n == 0) return FFHIP_OK;
     if (n_threads < 1) n_threads = 1;
     if (n_threads > 64) n_threads = 64;
-    auto pool_for = [](int count, int nt, auto f) { /* f(i) for i < count over nt host threads */
-        if (nt > count) nt = count;
-        if (nt <= 1) { for (int i = 0; i < count; i++) f(i); return; }
-        std::vector<std::thread> pool;
-        auto part = [&](int t) { for (int i = t; i < count; i += nt) f(i); };
-        for (int t = 1; t < nt; t++) pool.emplace_back(part, t);
-        part(0);
-        for (auto &th : pool) th.join();
-    };
     /* ---- headers: each file's geometry and class; a file the mixed path cannot take (progressive, 12-bit, a two-pass layout, an output
      * or pitch ffhip_jpeg_recon_items refuses) has its code now and takes no further part ---- */
     std::vector<ffhip_jpeg_geom> geoms((size_t)n);
     std::vector<int> cls((size_t)n, -1);
-    pool_for(n, n_threads, [&](int i) {
+    ffhip_parallel_for(n, n_threads, [&](int i) {
         int w = 0, h = 0;
         ffhip_jpeg_geom &g = geoms[(size_t)i];
         memset(&g, 0, sizeof(g));
@@ -330,8 +336,6 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
     });
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
-    const char *ge = FFHIP_ENV("FFHIP_JPEG_GPU_ENTROPY");
-    const char *sy = FFHIP_ENV("FFHIP_JPEG_SYNC"); /* =0: files without restart markers are one lane each on the device, worth it from a thousand files only */
     int rc = FFHIP_OK;
     for (int c = 0; c < 7 && rc == FFHIP_OK; c++) {
         std::vector<int> idx;
@@ -355,41 +359,35 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
         }
         const ffhip_jpeg_geom &g0 = cg[0];
         const size_t mcus = base[(size_t)nc], yb = mcus * g0.h * g0.v * 64, cb = g0.ncomp == 3 ? mcus * 64 : 0; /* int16 elements of the class */
-        const size_t q_off = ((yb + 2 * cb) * 2 + 15) & ~(size_t)15, bytes = q_off + (size_t)nc * 512;
-        uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_FILES_MIXED, stream, bytes / 4 + 16);
+        const PlaneBlock blk(yb, cb, (size_t)nc);
+        uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_FILES_MIXED, stream, blk.bytes / 4 + 16);
         if (!dev) { rc = FFHIP_ENOMEM; break; }
-        int16_t *dy = (int16_t *)dev, *du = cb ? dy + yb : nullptr, *dv = cb ? du + cb : nullptr;
-        uint16_t *dq = (uint16_t *)(dev + q_off);
+        const Planes d = blk.at(dev);
         bool done = false;
-        if (!(ge && ge[0] == '0') && ((ge && ge[0] == '1') || !(sy && sy[0] == '0') || ffhip_jpeg_probe_restart(cf[0], cl[0]) > 0 || nc >= 1024)) {
+        if (jpeg_entropy_on_device(cf[0], cl[0], nc)) {
             const FfhipHuffThen then = {nullptr, 0, 0, items.data()};
-            const int grc = jpeg_entropy_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), dy, du, dv, dq, cs.data(), stream, &then);
+            const int grc = jpeg_entropy_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, cs.data(), stream, &then);
             if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
             done = grc == FFHIP_OK;
         }
         if (!done) {
             /* host threads: each picture at its own offsets of the pinned planes, one upload, the good pictures reconstructed */
             if (hipStreamSynchronize(st) != hipSuccess) { rc = FFHIP_EIO; break; } /* the scratch may still be read by what `stream` holds */
-            uint8_t *pin = ffhip_pinned_scratch(SCRATCH_FILES_MIXED, stream, bytes);
+            uint8_t *pin = ffhip_pinned_scratch(SCRATCH_FILES_MIXED, stream, blk.bytes);
             if (!pin) { rc = FFHIP_ENOMEM; break; }
-            int16_t *hy = (int16_t *)pin, *hu = cb ? hy + yb : nullptr, *hv = cb ? hu + cb : nullptr;
-            uint16_t *hq = (uint16_t *)(pin + q_off);
-            pool_for(nc, n_threads, [&](int k) {
+            const Planes h = blk.at(pin);
+            ffhip_parallel_for(nc, n_threads, [&](int k) {
                 const ffhip_jpeg_geom &g = cg[(size_t)k];
                 const size_t b = base[(size_t)k];
-                cs[(size_t)k] = ffhip_jpeg_entropy_decode(cf[(size_t)k], cl[(size_t)k], &g, hy + b * g.h * g.v * 64, hu ? hu + b * 64 : nullptr,
-                                                          hv ? hv + b * 64 : nullptr, hq + (size_t)k * 256);
+                cs[(size_t)k] = ffhip_jpeg_entropy_decode(cf[(size_t)k], cl[(size_t)k], &g, h.y + b * g.h * g.v * 64, h.u ? h.u + b * 64 : nullptr,
+                                                          h.v ? h.v + b * 64 : nullptr, h.q + (size_t)k * 256);
             });
-            if (hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { rc = FFHIP_EIO; break; }
+            if (hipMemcpyAsync(dev, pin, blk.bytes, hipMemcpyHostToDevice, st) != hipSuccess) { rc = FFHIP_EIO; break; }
             std::vector<ffhip_jpeg_item> good;
             for (int k = 0; k < nc; k++) {
                 if (cs[(size_t)k]) continue;
                 ffhip_jpeg_item it = items[(size_t)k];
-                const size_t b = base[(size_t)k];
-                it.d_coef_y = dy + b * it.geom.h * it.geom.v * 64;
-                it.d_coef_u = du ? du + b * 64 : nullptr;
-                it.d_coef_v = dv ? dv + b * 64 : nullptr;
-                it.d_quant = dq + (size_t)k * 256;
+                jpeg_item_planes(&it, d.y, d.u, d.v, d.q, base[(size_t)k], (size_t)k);
                 good.push_back(it);
             }
             rc = jpeg_recon_items_impl(good.data(), (int)good.size(), stream, 0);

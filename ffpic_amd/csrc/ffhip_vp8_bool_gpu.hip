@@ -15,7 +15,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <thread>
 #include <vector>
 
 #include "ffhip_internal.h"
@@ -146,17 +145,6 @@ __global__ __launch_bounds__(64) void k_webp_tokens(const WebpDesc *descs, int n
 
 namespace {
 
-template <class F> void pool_for(int count, int nt, F f)
-{
-    if (nt > count) nt = count;
-    if (nt <= 1) { for (int i = 0; i < count; i++) f(i); return; }
-    std::vector<std::thread> pool;
-    auto part = [&](int t) { for (int i = t; i < count; i += nt) f(i); };
-    for (int t = 1; t < nt; t++) pool.emplace_back(part, t);
-    part(0);
-    for (auto &th : pool) th.join();
-}
-
 size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 /* where a part's arrays lie in its device scratch (and in the pinned mirror of the host path) */
@@ -217,7 +205,7 @@ int run_part(const std::vector<PartFile> &pf, const std::vector<ffhip_webp_frame
         if (!pin) return FFHIP_ENOMEM;
         WebpDesc *hd = (WebpDesc *)pin;
         uint8_t *hbytes = pin + (L.bytes - L.descs);
-        pool_for(nf, n_threads, [&](int k) {
+        ffhip_parallel_for(nf, n_threads, [&](int k) {
             const PartFile &p = pf[(size_t)k];
             const ffhip_webp_frame &f = frames[(size_t)p.idx];
             memcpy(hbytes + p.byte_off, files[p.idx] + f.p0_off, p.byte_len);
@@ -260,7 +248,7 @@ int run_part(const std::vector<PartFile> &pf, const std::vector<ffhip_webp_frame
         FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO); /* the scratch may still be read by what `stream` holds */
         uint8_t *pin = ffhip_pinned_scratch(SCRATCH_WEBP + 1, stream, L.skip);
         if (!pin) return FFHIP_ENOMEM;
-        pool_for(nf, n_threads, [&](int k) {
+        ffhip_parallel_for(nf, n_threads, [&](int k) {
             const PartFile &p = pf[(size_t)k];
             status[p.idx] = ffhip_webp_parse_frame(files[p.idx], &frames[(size_t)p.idx], pin + L.modes + p.first_mb * 20,
                                                    (int16_t *)(pin + L.levels) + p.first_mb * 400, pin + L.mbinfo + p.first_mb * 32,
@@ -314,7 +302,7 @@ int webp_files_impl(const uint8_t *const *files, const size_t *lens, int n, int 
     if (n_threads < 1) n_threads = 1;
     if (n_threads > 64) n_threads = 64;
     std::vector<ffhip_webp_frame> frames((size_t)n);
-    pool_for(n, n_threads, [&](int i) {
+    ffhip_parallel_for(n, n_threads, [&](int i) {
         ffhip_webp_frame &f = frames[(size_t)i];
         status[i] = files[i] && lens[i] ? ffhip_webp_read_header(files[i], lens[i], &f) : FFHIP_EINVAL;
         if (info_out) info_out[i] = f.info;
