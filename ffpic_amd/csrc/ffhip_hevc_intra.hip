@@ -12,15 +12,19 @@
  * Dependency-bound like every intra decoder: a TU reads reconstructed samples of earlier
  * TUs.  Default form: ONE launch, k_hevc_intra_groups (window groups, done flags per TU, see
  * there), scheduled by the device-side planner of ffhip_hevc_plan_gpu.hip or, for lists it
- * hands back, by plan_groups below.  Diagnostic form (FFHIP_HEVC_INTRA_MODE=levels): the host
- * gives each TU a wavefront level (1 + the highest level among the 4x4 blocks its available
- * neighbours lie in) and launches k_hevc_intra once per level, a wave per TU.
- * The TU body is the same in both: the 4n+1 neighbours live in LDS in
+ * hands back, by the host planner of ffhip_hevc_plan_host.hip.  Diagnostic form and fallback
+ * (FFHIP_HEVC_INTRA_MODE=levels): the host gives each TU a wavefront level (1 + the highest
+ * level among the 4x4 blocks its available neighbours lie in) and launches k_hevc_intra once
+ * per level, a wave per TU.
+ * Two TU bodies with the same arithmetic, intra_tu (levels form) and intra_tu_g (grouped form):
+ * the 4n+1 neighbours live in LDS in
  * scan order (left column bottom-up, corner, top row left-to-right): in that order the
  * reference's substitution is "nearest available sample at or before me, else the first
  * available one", and its [1 2 1] smoothing is a 3-tap filter with untouched ends.
+ * This file: the kernels and the call (validation, the three paths, the tile entry points);
+ * ffhip_hevc_plan.h has what the three files share.
  */
-#include "ffhip_internal.h"
+#include "ffhip_hevc_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -28,17 +32,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <vector>
-#include <mutex>
 
 #ifndef FFHIP_HEVC_INTRA_WAVES
 #define FFHIP_HEVC_INTRA_WAVES 256 /* waves of the grouped form's one launch: enough for the widest wavefront of an 8K picture (~200 groups)
                                       and for a grid of 96 tiles; every further wave only holds a ticket far from its turn and polls
                                       (1024 waves: config-5 mix 6.5 ms, quadtree 11.7; 256: 6.0 / 11.4; tests/tools/bench_intra_c5.py) */
-#endif
-#ifndef FFHIP_HEVC_INTRA_WINDOW_LOG2
-#define FFHIP_HEVC_INTRA_WINDOW_LOG2 5 /* luma window of the grouped form: 32x32 (1080p sweep in profiles/r1_stages.json) */
 #endif
 
 #define CTRL_HDR 352 /* words in front of the done flags: room for ten 128-byte lines wherever the block starts (ticket counters, abort) */
@@ -83,7 +82,6 @@ struct HevcIntraArgs {
     unsigned long long *trace;   /* diagnostics build only (make trace): 12 words per TU, then one per ticket */
 #endif
 };
-#define JT_STRIDE 20 /* table bytes per 4x4 block: a TU of size n owns n/4 consecutive blocks of its first block row, 5n >= 4n + 1 bytes */
 #ifdef FFHIP_INTRA_TRACE
 static unsigned long long *g_intra_trace = nullptr;
 extern "C" void ffhip_debug_intra_trace(void *d_buf) { g_intra_trace = (unsigned long long *)d_buf; }
@@ -230,16 +228,13 @@ __device__ __attribute__((noinline)) void rdpcm_accumulate(short *R, const int l
     }
 }
 
-/* One TU by one wave: steps 5-10 of decode_intra_block.  s, s2: NB_MAX ints each; refbase: 140 ints;
- * R: 32*32 shorts -- all private to the wave (LDS).
- * GROUPED: picture samples move with agent-scope accesses, and neighbours inside the group's window
- * (origin wx0, wy0, size 1 << wl) come from / go to the wave's LDS copy `tile` when tile_ok. */
-template <bool GROUPED, int LG> /* LG = log2 of the TU size: every loop below has a compile-time trip count */
+/* One TU by one wave, the levels form's body: steps 5-10 of decode_intra_block.  s, s2: NB_MAX ints each;
+ * refbase: 140 ints; R: 32*32 shorts -- all private to the wave (LDS).  Picture samples are read and written
+ * with plain accesses: a level's TUs only read what earlier launches wrote. */
+template <int LG> /* LG = log2 of the TU size: every loop below has a compile-time trip count */
 __device__ __forceinline__ void intra_tu(const HevcIntraArgs &a, const ffhip_hevc_tu &t, const int lane, int *s, int *s2,
-                                         int *refbase, short *R, const ResPrefetch &rp, short *tile, const int wl,
-                                         const bool tile_ok)
+                                         int *refbase, short *R, const ResPrefetch &rp)
 {
-    const int wx0 = GROUPED ? (t.x >> wl) << wl : 0, wy0 = GROUPED ? (t.y >> wl) << wl : 0, wsz = GROUPED ? 1 << wl : 0;
     constexpr int n = 1 << LG, lg = LG;
     const int cidx = t.cidx, mode = t.pred_mode, flags = t.flags;
     const int bd = cidx == 0 ? a.bitdepth_y : a.bitdepth_c;
@@ -296,13 +291,7 @@ __device__ __forceinline__ void intra_tu(const HevcIntraArgs &a, const ffhip_hev
         int v = 1 << (bd - 1);
         if (n_avail > 0) {
             const int16_t *sp = plane + (long long)py * stride + px;
-            if (GROUPED) {
-                const unsigned tx = (unsigned)(px - wx0), ty = (unsigned)(py - wy0);
-                if (tile_ok && tx < (unsigned)wsz && ty < (unsigned)wsz) v = (int)tile[TILE_ORIGIN + ty * TILE_STRIDE + tx];
-                else v = ffhip_load_s16_sc1(ffhip_rsrc(plane, 0xffffffffu), (py * stride + px) * 2);
-            } else {
-                v = (int)*sp;
-            }
+            v = (int)*sp;
         }
         s[i] = v;
     }
@@ -425,13 +414,7 @@ __device__ __forceinline__ void intra_tu(const HevcIntraArgs &a, const ffhip_hev
         const int rs = has_res ? (int)R[p] : 0;
         int16_t *dp = plane + (long long)(y0 + y) * stride + x0 + x;
         const short rec = (short)clip3i(0, (1 << bd) - 1, pr + rs);
-        if (GROUPED) {
-            __hip_atomic_store(dp, rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned tx = (unsigned)(x0 + x - wx0), ty = (unsigned)(y0 + y - wy0);
-            if (tx < (unsigned)wsz && ty < (unsigned)wsz) tile[TILE_ORIGIN + ty * TILE_STRIDE + tx] = rec;
-        } else {
-            *dp = rec;
-        }
+        *dp = rec;
     }
 #undef LEFT
 #undef TOP
@@ -1114,16 +1097,14 @@ __global__ __launch_bounds__(256) void k_hevc_intra_jtable(JTabArgs a)
     }
 }
 
-template <bool GROUPED>
 __device__ __forceinline__ void intra_tu_any(const HevcIntraArgs &a, const ffhip_hevc_tu &t, const int lane, int *s, int *s2,
-                                             int *refbase, short *R, const ResPrefetch &rp, short *tile, const int wl,
-                                             const bool tile_ok)
+                                             int *refbase, short *R, const ResPrefetch &rp)
 {
     switch (t.log2_size) {
-    case 2: intra_tu<GROUPED, 2>(a, t, lane, s, s2, refbase, R, rp, tile, wl, tile_ok); break;
-    case 3: intra_tu<GROUPED, 3>(a, t, lane, s, s2, refbase, R, rp, tile, wl, tile_ok); break;
-    case 4: intra_tu<GROUPED, 4>(a, t, lane, s, s2, refbase, R, rp, tile, wl, tile_ok); break;
-    default: intra_tu<GROUPED, 5>(a, t, lane, s, s2, refbase, R, rp, tile, wl, tile_ok); break;
+    case 2: intra_tu<2>(a, t, lane, s, s2, refbase, R, rp); break;
+    case 3: intra_tu<3>(a, t, lane, s, s2, refbase, R, rp); break;
+    case 4: intra_tu<4>(a, t, lane, s, s2, refbase, R, rp); break;
+    default: intra_tu<5>(a, t, lane, s, s2, refbase, R, rp); break;
     }
 }
 
@@ -1138,7 +1119,7 @@ __global__ __launch_bounds__(256) void k_hevc_intra(HevcIntraArgs a)
     const ffhip_hevc_tu t = a.tus[a.work[item]];
     ResPrefetch rp;
     fetch_residual(a, t, lane, rp);
-    intra_tu_any<false>(a, t, lane, nbA[w], nbB[w], refs[w], resl[w], rp, nullptr, 0, false);
+    intra_tu_any(a, t, lane, nbA[w], nbB[w], refs[w], resl[w], rp);
 }
 
 /* Grouped form: ONE launch per picture.  The host cuts the TU list into groups -- the TUs whose
@@ -1598,388 +1579,6 @@ extern "C" int ffhip_debug_hevc_plan_result(uint32_t out[8])
     return FFHIP_OK;
 }
 
-/* log2 of the chroma planes' subsampling against luma, horizontally (4:2:0 / 4:2:2: 1) */
-static int chroma_shift(const int pw[3]) { return (pw[1] > 0 && pw[1] * 2 <= pw[0] + 1) ? 1 : 0; }
-
-struct GroupPlan {
-    std::vector<u32x4> sched;  /* 3 per slot */
-    std::vector<u32x4> groups;
-    std::vector<uint32_t> wait;
-};
-
-struct PlanMeta { uint32_t group, wait_begin, slot; uint8_t wait_count, signal, tile_ok; }; /* plan_groups: per TU */
-/* fn(0 .. n_threads - 1), each on a thread of its own but the first */
-template <class F>
-static void on_threads(int n_threads, F &fn)
-{
-    if (n_threads == 1) { fn(0); return; }
-    std::vector<std::thread> pool;
-    for (int th = 1; th < n_threads; th++) pool.emplace_back(fn, th);
-    fn(0);
-    for (auto &th : pool) th.join();
-}
-/* plan_groups' pass 3: the threads' wait lists (TU ranges in order) as one, wait_begin made absolute, and the dependency depth of every group */
-static void merge_waits(long long n_tus, const std::vector<std::vector<uint32_t>> &waits, PlanMeta *meta, size_t n_groups, std::vector<uint32_t> &gdepth,
-                        GroupPlan &out)
-{
-    const int n_threads = (int)waits.size();
-    size_t total_wait = 0;
-    for (auto &w : waits) total_wait += w.size();
-    out.wait.resize(std::max<size_t>(total_wait, 1));
-    out.wait[0] = 0;
-    gdepth.assign(n_groups, 0);
-    size_t base = 0;
-    for (int th = 0; th < n_threads; th++) {
-        const long long lo = n_tus * th / n_threads, hi = n_tus * (th + 1) / n_threads;
-        const std::vector<uint32_t> &w = waits[(size_t)th];
-        if (!w.empty()) memcpy(out.wait.data() + base, w.data(), w.size() * sizeof(uint32_t));
-        for (long long i = lo; i < hi; i++) {
-            PlanMeta &m = meta[(size_t)i];
-            uint32_t depth = gdepth[m.group];
-            for (unsigned q = 0; q < m.wait_count; q++) depth = std::max(depth, gdepth[meta[w[m.wait_begin + q]].group] + 1);
-            gdepth[m.group] = depth;
-            m.wait_begin += (uint32_t)base;
-        }
-        base += w.size();
-    }
-}
-/* plan_groups' last step: the tickets' order (by_depth: dependency depth, ties in decode order; else decode order), the group records, the slots */
-static void order_and_emit(const ffhip_hevc_tu *tus, long long n_tus, const int win_log2[3], const int bw[3], const uint32_t jt_boff[3], const bool by_depth,
-                           const PlanMeta *mp, const std::vector<uint32_t> &gcount, const std::vector<uint32_t> &gfirst, const std::vector<uint32_t> &gdepth,
-                           int n_threads, GroupPlan &out)
-{
-    static thread_local std::vector<uint32_t> order, gbase;
-    /* Tickets go out in dependency-depth order (ties: decode order), so the waves that hold tickets
-     * are the ones near the ready front rather than thousands of groups ahead of it, polling.
-     * Every group a group waits for has a smaller depth, hence a smaller ticket.  (Depths are only
-     * trusted for contiguous groups; otherwise decode order, which pass 2 checked is valid.) */
-    const size_t ng = gcount.size();
-    order.resize(ng);
-    for (size_t g = 0; g < ng; g++) order[g] = (uint32_t)g;
-    if (by_depth) std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return gdepth[x] < gdepth[y]; });
-    gbase.resize(ng);
-    out.groups.resize(ng);
-    uint32_t run = 0;
-    for (size_t k = 0; k < ng; k++) {
-        const uint32_t g = order[k];
-        gbase[g] = run;
-        u32x4 rec;
-        rec.x = run;
-        rec.y = gcount[g];
-        rec.z = (uint32_t)win_log2[tus[gfirst[g]].cidx];
-        rec.w = 0;
-        out.groups[k] = rec;
-        run += gcount[g];
-    }
-    out.sched.resize((size_t)n_tus * 3);
-    static_assert(sizeof(ffhip_hevc_tu) == 32, "slot layout");
-    const uint32_t *const gbasep = gbase.data();
-    auto emit = [&](int th) {
-        const long long lo = n_tus * th / n_threads, hi = n_tus * (th + 1) / n_threads;
-        for (long long i = lo; i < hi; i++) {
-            const PlanMeta &m = mp[(size_t)i];
-            u32x4 *q = &out.sched[(size_t)(gbasep[m.group] + m.slot) * 3];
-            memcpy(q, &tus[i], 32);
-            q[2].x = m.wait_begin;
-            q[2].y = (uint32_t)m.wait_count | ((uint32_t)m.signal << 8) | ((uint32_t)m.tile_ok << 9);
-            q[2].z = (uint32_t)i;
-            q[2].w = (jt_boff[tus[i].cidx] + (uint32_t)(tus[i].y >> 2) * (uint32_t)bw[tus[i].cidx] + (uint32_t)(tus[i].x >> 2)) * JT_STRIDE;
-        }
-    };
-    on_threads(n_threads, emit);
-}
-
-/* Cut the (validated) list into window-tile groups in order of first appearance and collect, per
- * TU, the TUs of OTHER groups it reads, whether some other group reads it, and whether all its
- * available neighbours inside the window were written by its own group (then the kernel may take
- * them from its LDS tile).  Returns false when some TU would wait for a group with a larger
- * ticket (window larger than the coding tree block, or an exotic list): the caller then tries a
- * smaller window or falls back to the level-synchronous form. */
-static bool plan_groups(const ffhip_hevc_tu *tus, long long n_tus, const int pw[3], const int ph[3], const int win_log2[3],
-                        GroupPlan &out, const uint32_t jt_boff[3])
-{
-    /* scratch kept between calls: a picture's worth of maps is reallocated and refilled otherwise */
-    static thread_local std::vector<int32_t> owner[3], gid_of[3];
-    static thread_local std::vector<PlanMeta> meta;
-    static thread_local std::vector<uint32_t> gcount, gdepth, gfirst;
-    int bw[3], gw[3];
-    for (int c = 0; c < 3; c++) {
-        bw[c] = (pw[c] + 3) / 4;
-        gw[c] = pw[c] > 0 ? ((pw[c] - 1) >> win_log2[c]) + 1 : 0;
-        owner[c].assign((size_t)bw[c] * (size_t)((ph[c] + 3) / 4), -1);
-        gid_of[c].assign((size_t)gw[c] * (size_t)(ph[c] > 0 ? ((ph[c] - 1) >> win_log2[c]) + 1 : 0), -1);
-    }
-    const auto T0 = std::chrono::steady_clock::now();
-    meta.resize((size_t)n_tus);
-    gcount.clear();
-    gfirst.clear();
-    /* ---- pass 1 (sequential, light): groups in order of first appearance, slot inside the group, block owners ----
-     * contiguous: every group is one run of the list; then a group is complete before a later one starts,
-     * which is what makes the dependency depths of pass 3 final when they are read */
-    bool contiguous = true;
-    uint32_t cur_group = ~0u;
-    for (long long i = 0; i < n_tus; i++) {
-        const ffhip_hevc_tu &t = tus[i];
-        const int c = t.cidx, n = 1 << t.log2_size, wl = win_log2[c];
-        int32_t &gslot = gid_of[c][(size_t)(t.y >> wl) * gw[c] + (t.x >> wl)];
-        if (gslot < 0) {
-            gslot = (int32_t)gcount.size();
-            gcount.push_back(0);
-            gfirst.push_back((uint32_t)i);
-        } else if ((uint32_t)gslot != cur_group) {
-            contiguous = false;
-        }
-        cur_group = (uint32_t)gslot;
-        PlanMeta &m = meta[(size_t)i];
-        m.group = cur_group; m.signal = 0; m.tile_ok = 1;
-        m.slot = gcount[cur_group]++;
-        int32_t *orow = owner[c].data() + (size_t)(t.y >> 2) * bw[c] + (t.x >> 2);
-        for (int by = 0; by < n / 4; by++, orow += bw[c])
-            for (int bx = 0; bx < n / 4; bx++) orow[bx] = (int32_t)i;
-    }
-    const auto T1 = std::chrono::steady_clock::now();
-    /* ---- pass 2 (parallel over TU ranges): who reads whom.  The owner map is complete; a TU only
-     * depends on TUs before it in the list (a block whose owner comes later held older content when
-     * the sequential decoder looked at it) ---- */
-    /* the scratch vectors are thread_local: worker threads must go through pointers taken here */
-    PlanMeta *const mp = meta.data();
-    const int32_t *const ownp[3] = {owner[0].data(), owner[1].data(), owner[2].data()};
-    const char *pt = FFHIP_ENV("FFHIP_PLAN_THREADS");
-    /* one thread unless asked: on the 16-core share of an MI355X box 2-8 threads were no faster
-     * (2.5-5.0 ms against 2.7 ms for this pass on 172k TUs: thread start-up and the shared maps eat the gain) */
-    const int n_threads = pt ? std::max(1, std::min(16, atoi(pt))) : 1;
-    std::vector<std::vector<uint32_t>> waits((size_t)n_threads);
-    std::atomic<bool> bad(false);
-    auto scan = [&](int th) {
-        const long long lo = n_tus * th / n_threads, hi = n_tus * (th + 1) / n_threads;
-        std::vector<uint32_t> &w = waits[(size_t)th];
-        w.reserve((size_t)(hi - lo) * 2);
-        for (long long i = lo; i < hi; i++) {
-            const ffhip_hevc_tu &t = tus[i];
-            const int c = t.cidx, n = 1 << t.log2_size, wl = win_log2[c];
-            PlanMeta &m = mp[(size_t)i];
-            const uint32_t g = m.group;
-            int32_t deps[72];
-            int nd = 0;
-            bool tile_ok = true;
-            const int wx0 = (t.x >> wl) << wl, wy0 = (t.y >> wl) << wl, wsz = 1 << wl;
-            const int32_t *own = ownp[c];
-            auto dep = [&](int px, int py) {
-                int32_t j = own[(size_t)(py >> 2) * bw[c] + (px >> 2)];
-                if (j >= i) j = -1;
-                const bool mine = j >= 0 && mp[(size_t)j].group == g;
-                if (j >= 0 && !mine) {
-                    bool dup = false;
-                    for (int q = nd - 1; q >= 0 && !dup; q--) dup = deps[q] == j; /* neighbours repeat back to back */
-                    if (!dup && nd < 72) deps[nd++] = j;
-                }
-                if (!mine && px >= wx0 && px < wx0 + wsz && py >= wy0 && py < wy0 + wsz) tile_ok = false; /* not in my LDS copy */
-            };
-            if (t.flags & 1) dep(t.x - 1, t.y - 1);
-            for (int k = 0; k < 2 * n; k += 4) {
-                if ((t.avail_top >> k) & 0xf) dep(t.x + k, t.y - 1);
-                if ((t.avail_left >> k) & 0xf) dep(t.x - 1, t.y + k);
-            }
-            if (nd > 64) { bad = true; return; }
-            m.tile_ok = tile_ok;
-            m.wait_count = (uint8_t)nd;
-            m.wait_begin = (uint32_t)w.size(); /* relative to this thread's list until pass 3 */
-            for (int q = 0; q < nd; q++) {
-                PlanMeta &mj = mp[(size_t)deps[q]];
-                if (mj.group > g) { bad = true; return; }
-                __atomic_store_n(&mj.signal, (uint8_t)1, __ATOMIC_RELAXED);
-                w.push_back((uint32_t)deps[q]);
-            }
-        }
-    };
-    on_threads(n_threads, scan);
-    if (bad) return false;
-    const auto T2 = std::chrono::steady_clock::now();
-    /* ---- pass 3 (sequential, light): one wait list, dependency depth per group ---- */
-    merge_waits(n_tus, waits, mp, gcount.size(), gdepth, out);
-    const auto T3 = std::chrono::steady_clock::now();
-    order_and_emit(tus, n_tus, win_log2, bw, jt_boff, contiguous && !FFHIP_ENV("FFHIP_HEVC_INTRA_DECODE_ORDER"), mp, gcount, gfirst, gdepth, n_threads, out);
-    if (FFHIP_ENV("FFHIP_PLAN_TIMES")) {
-        const auto T4 = std::chrono::steady_clock::now();
-        auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
-        fprintf(stderr, "plan: setup+pass1 %ld us, pass2 %ld us, pass3 %ld us, order+emit %ld us (threads %d)\n", us(T0, T1), us(T1, T2), us(T2, T3), us(T3, T4), n_threads);
-    }
-    return true;
-}
-
-/* Host-side passes over a TU list (validation, the contiguity test) are ~2-4 ns per TU and thread: 7 ms for the 1.8 million TUs of
- * eight 8K grids, more than the device needs for them.  Lists of 2^17 TUs and more are cut into pieces for up to 16 threads
- * (started per call: ~20 us each, they work while the others start). */
-template <class F>
-static void host_parallel_for(long long n, F &&fn)
-{
-    const long long min_piece = 1 << 16;
-    unsigned hw = std::thread::hardware_concurrency();
-    long long nt = n / min_piece;
-    nt = nt > 16 ? 16 : nt;
-    nt = hw && nt > (long long)hw ? (long long)hw : nt;
-    if (nt < 2) { fn(0, n); return; }
-    std::vector<std::thread> th;
-    th.reserve((size_t)nt - 1);
-    const long long piece = (n + nt - 1) / nt;
-    for (long long k = 1; k < nt; k++) th.emplace_back([&fn, k, piece, n]() { fn(k * piece, std::min(n, (k + 1) * piece)); });
-    fn(0, std::min(n, piece));
-    for (auto &t : th) t.join();
-}
-
-/* Are the groups of this window -- the TUs whose top-left corner falls into one window tile of one plane -- contiguous
- * runs of the list?  (Then a group is complete before a later one starts, the condition of the grouped kernel.)  Two rules in one
- * pass, a byte map per plane and rule; scratch kept per thread:
- *   bit 0  runs of the list AS IT IS: a TU opens a run where its window differs from that of the record in front of it
- *   bit 1  runs of every plane's OWN subsequence: ... from that of the previous record of the same plane.  This is the rule the
- *          reference's order needs: it decodes coding unit by coding unit, the unit's luma tree, then Cb, then Cr
- *          (coding/hevc.c:5013-5180 calling decode_intra_block :4665-4805), so a coding tree block with several coding units
- *          switches planes INSIDE every 64x64 area.  The planes do not read each other, so the device planner may work on the
- *          list sorted by plane (ffhip_hevc_plan_gpu.hip, k_part_*), where bit 1 is what bit 0 is here.
- * Bit 0 implies bit 1. */
-/* sampled: only the records of every 64th stretch of 4096 are looked at -- every 256th from a million records on -- (large lists, whose full test runs on the device: a window that
- * is not contiguous there is refused by the planner and the list decoded by the serial kernel -- exact, slow, and only for a list whose
- * coding-tree-block size changes between the sampled stretches) */
-#define SAMPLED_OUT(i) ((((i) >> 12) & (n_tus >= (1LL << 20) ? 255 : 63)) != 0)
-static int groups_contiguous(const ffhip_hevc_tu *tus, long long n_tus, const int pw[3], const int ph[3], const int win_log2[3], const bool sampled = false)
-{
-    static thread_local std::vector<uint8_t> seen[3];
-    int gw[3];
-    size_t cnt[3];
-    for (int c = 0; c < 3; c++) {
-        gw[c] = pw[c] > 0 ? ((pw[c] - 1) >> win_log2[c]) + 1 : 0;
-        cnt[c] = (size_t)gw[c] * (size_t)(ph[c] > 0 ? ((ph[c] - 1) >> win_log2[c]) + 1 : 0);
-        seen[c].assign(2 * cnt[c], 0); /* [0, cnt): the list as it is; [cnt, 2 cnt): the plane's own subsequence */
-    }
-    uint8_t *const map[3] = {seen[0].data(), seen[1].data(), seen[2].data()};
-    std::atomic<bool> twice_raw{false}, twice_plane{false};
-    auto window_of = [&](const ffhip_hevc_tu &t) -> long long { /* -1: an unvalidated record of a sampled list (the device pass refuses it) */
-        const int c = t.cidx;
-        if (c > 2 || t.x >= pw[c] || t.y >= ph[c]) return -1;
-        return (long long)(t.y >> win_log2[c]) * gw[c] + (t.x >> win_log2[c]);
-    };
-    /* a TU opens a run where its window differs from its predecessor's: stateless per TU under the first rule, so the list is cut into
-     * pieces for as many threads as pay (a window entered by two pieces is entered twice all the same: the mark is an atomic exchange);
-     * under the second rule a piece -- and a sampled stretch -- first looks back for the last record of each plane in front of it */
-    host_parallel_for(sampled ? 1 : n_tus, [&](long long b, long long e) { /* (a sample is one thread's work: starting sixteen costs more than the pass) */
-        if (sampled) e = n_tus;
-        long long last[3] = {-2, -2, -2}; /* the window of the plane's previous record; -2 = not looked up yet */
-        auto look_back = [&](long long i) {
-            int missing = 3;
-            last[0] = last[1] = last[2] = -1;
-            for (long long j = i - 1; j >= 0 && j >= i - 4096 && missing; j--) { /* (further back than any coding tree block reaches: a run that old is taken for a new one) */
-                const int c = tus[j].cidx;
-                if (c > 2 || last[c] != -1) continue;
-                const long long w = window_of(tus[j]);
-                if (w < 0) continue;
-                last[c] = w; missing--;
-            }
-        };
-        look_back(b);
-        for (long long i = b; i < e && !twice_plane.load(std::memory_order_relaxed); i++) {
-            if (sampled && SAMPLED_OUT(i)) { i |= 4095; if (i + 1 < e) look_back(i + 1); continue; }
-            const ffhip_hevc_tu &t = tus[i];
-            const long long w = window_of(t);
-            if (w < 0) continue;
-            const int c = t.cidx;
-            if (last[c] != w) {
-                last[c] = w;
-                if (__atomic_exchange_n(map[c] + cnt[c] + w, (uint8_t)1, __ATOMIC_RELAXED)) twice_plane.store(true, std::memory_order_relaxed);
-            }
-            if (i > 0 && tus[i - 1].cidx == c && window_of(tus[i - 1]) == w) continue;
-            if (!twice_raw.load(std::memory_order_relaxed) && __atomic_exchange_n(map[c] + w, (uint8_t)1, __ATOMIC_RELAXED)) twice_raw.store(true, std::memory_order_relaxed);
-        }
-    });
-    const bool plane_ok = !twice_plane.load();
-    return (plane_ok && !twice_raw.load() ? 1 : 0) | (plane_ok ? 2 : 0);
-}
-
-/* The list sorted by plane (stable), on the host: for the host planner and ffhip_hevc_intra_plan, what k_part_* do for the device planner.
- * perm[k] = the caller's index of sorted record k. */
-static void sort_by_plane(const ffhip_hevc_tu *tus, long long n_tus, std::vector<ffhip_hevc_tu> &sorted, std::vector<uint32_t> *perm)
-{
-    size_t cnt[3] = {0, 0, 0};
-    for (long long i = 0; i < n_tus; i++) cnt[tus[i].cidx > 2 ? 2 : tus[i].cidx]++;
-    size_t at[3] = {0, cnt[0], cnt[0] + cnt[1]};
-    sorted.resize((size_t)n_tus);
-    if (perm) perm->resize((size_t)n_tus);
-    for (long long i = 0; i < n_tus; i++) {
-        const size_t k = at[tus[i].cidx > 2 ? 2 : tus[i].cidx]++;
-        sorted[k] = tus[i];
-        if (perm) (*perm)[k] = (uint32_t)i;
-    }
-}
-/* the largest luma window (from `wl` down to 8x8) under which the list's groups are contiguous runs, by the plane's own subsequence; *by_plane:
- * NOT by the list as it is, i.e. the list has to be sorted by plane for that window.  0 when there is none.  FFHIP_HEVC_BY_PLANE=0 keeps to the
- * list as it is (the rule until round 5), =1 sorts whenever the sort alone does not make the window smaller (tests: both forms on every list). */
-static int pick_window(const ffhip_hevc_tu *tus, long long n_tus, const int pw[3], const int ph[3], int wl, const bool sampled, bool *by_plane)
-{
-    const char *bp = FFHIP_ENV("FFHIP_HEVC_BY_PLANE");
-    const int force = bp ? atoi(bp) : -1;
-    const int cs = chroma_shift(pw);
-    wl = wl < 3 ? 3 : (wl > 6 ? 6 : wl);
-    for (; wl >= 3; wl--) {
-        const int win[3] = {wl, wl - cs, wl - cs};
-        const int bits = groups_contiguous(tus, n_tus, pw, ph, win, sampled);
-        if (force == 0 ? (bits & 1) : (bits & 2)) {
-            *by_plane = force == 0 ? false : (force == 1 ? true : !(bits & 1));
-            return wl;
-        }
-    }
-    *by_plane = false;
-    return 0;
-}
-
-/* the window search both entry points share: the requested (or default) luma window, halved until a
- * plan exists; chroma windows cover the same picture area */
-static bool plan_with_window_search(const ffhip_hevc_tu *tus, long long n_tus, const int pw[3], const int ph[3], int wl,
-                                    GroupPlan &plan, int *used_wl, const uint32_t jt_boff[3])
-{
-    wl = wl < 3 ? 3 : (wl > 6 ? 6 : wl);
-    const int cs = chroma_shift(pw);
-    for (; wl >= 3; wl--) {
-        const int win[3] = {wl, wl - cs, wl - cs};
-        if (plan_groups(tus, n_tus, pw, ph, win, plan, jt_boff)) {
-            if (used_wl) *used_wl = wl;
-            return true;
-        }
-    }
-    return false;
-}
-
-/* Host only (no device needed): the schedule ffhip_hevc_intra_recon would build for a VALIDATED list.
- * out_ticket[i] = ticket of TU i's group, out_wait[i] = number of TUs of other groups it waits for
- * (either may be NULL); stats = {groups, luma window log2 used, wait entries, TUs that may use the LDS tile}.
- * Returns FFHIP_EINVAL when no window gives a deadlock-free ticket order (the caller would use levels). */
-extern "C" int ffhip_hevc_intra_plan(const ffhip_hevc_tu *h_tus, long long n_tus, int width_y, int height_y, int width_c,
-                                     int height_c, int window_log2, uint32_t *out_ticket, uint32_t *out_wait, int32_t *stats)
-{
-    if (!h_tus || n_tus <= 0 || width_y <= 0 || height_y <= 0) return FFHIP_EINVAL;
-    const int pw[3] = {width_y, width_c, width_c}, ph[3] = {height_y, height_c, height_c};
-    GroupPlan plan;
-    int wl = 0;
-    const uint32_t no_table[3] = {0, 0, 0};
-    /* as ffhip_hevc_intra_recon does: a list that interleaves the planes inside a window is planned sorted by plane */
-    std::vector<ffhip_hevc_tu> sorted;
-    std::vector<uint32_t> perm;
-    bool by_plane = false;
-    const int want = window_log2 ? window_log2 : FFHIP_HEVC_INTRA_WINDOW_LOG2;
-    (void)pick_window(h_tus, n_tus, pw, ph, want, false, &by_plane);
-    if (by_plane) sort_by_plane(h_tus, n_tus, sorted, &perm);
-    if (!plan_with_window_search(by_plane ? sorted.data() : h_tus, n_tus, pw, ph, want, plan, &wl, no_table)) return FFHIP_EINVAL;
-    int tile_ok = 0;
-    for (size_t g = 0; g < plan.groups.size(); g++)
-        for (uint32_t k = 0; k < plan.groups[g].y; k++) {
-            const u32x4 q = plan.sched[(size_t)(plan.groups[g].x + k) * 3 + 2];
-            const uint32_t i = by_plane ? perm[q.z] : q.z;
-            if (out_ticket) out_ticket[i] = (uint32_t)g;
-            if (out_wait) out_wait[i] = q.y & 0xff;
-            tile_ok += (q.y >> 9) & 1;
-        }
-    if (stats) { stats[0] = (int32_t)plan.groups.size(); stats[1] = wl; stats[2] = (int32_t)plan.wait.size(); stats[3] = tile_ok; }
-    return FFHIP_OK;
-}
-
 /* One call of ffhip_hevc_intra_recon -- or the early pre-pass of ffhip_hevc_intra_recon_tiles --: what its validation and its three paths
  * share.  `st` takes everything in front of the grouped kernel: the caller's stream, or a stream of the library's own, behind which the
  * caller's (`gst`) waits through `plan_done`. */
@@ -2033,8 +1632,7 @@ static void set_ctrl(HevcIntraArgs &a, uint32_t *ctrl)
     a.ctrl_abort = a.ctrl_ticket + 32 * 9;
 }
 
-/* validation: field ranges, the block inside its plane, and no availability bit pointing outside the plane; sampled: only the records
- * SAMPLED_OUT leaves.  Sets has_res: some record asks for a residual. */
+/* validation: every record passes hevc_tu_valid; sampled: only the records sampled_out leaves.  Sets has_res: some record asks for a residual. */
 static bool validate(IntraCall &c, const bool sampled)
 {
     const long long n_tus = c.n_tus;
@@ -2043,19 +1641,9 @@ static bool validate(IntraCall &c, const bool sampled)
         if (sampled) e = n_tus;
         bool res = false, ok = true;
         for (long long i = b; i < e && ok; i++) {
-            if (sampled && SAMPLED_OUT(i)) { i |= 4095; continue; }
+            if (sampled && sampled_out(i, n_tus)) { i |= 4095; continue; }
             const ffhip_hevc_tu &t = c.h_tus[i];
-            const int k = t.cidx, n = 1 << t.log2_size;
-            if (k > 2 || t.log2_size < 2 || t.log2_size > 5 || t.pred_mode > 34) { ok = false; break; }
-            if (k > 0 && !c.chroma_ok) { ok = false; break; }
-            if (t.x + n > c.pw[k] || t.y + n > c.ph[k]) { ok = false; break; }
-            const unsigned long long span = n == 32 ? ~0ull : (1ull << (2 * n)) - 1;
-            const unsigned long long top = t.avail_top & span, left = t.avail_left & span;
-            const int room_x = c.pw[k] - t.x, room_y = c.ph[k] - t.y; /* samples that exist right of x0 / below y0 */
-            if ((top || (t.flags & 1)) && t.y == 0) ok = false;
-            if ((left || (t.flags & 1)) && t.x == 0) ok = false;
-            if (room_x < 64 && (top >> room_x)) ok = false;
-            if (room_y < 64 && (left >> room_y)) ok = false;
+            ok = hevc_tu_valid(t, c.pw, c.ph, c.chroma_ok);
             res |= (t.flags & 2) != 0;
         }
         if (!ok) bad.store(true, std::memory_order_relaxed);
@@ -2266,30 +1854,7 @@ static int recon_host_planned(IntraCall &c, const int want_wl, bool by_plane)
 /* The level-synchronous form: wavefront levels at 4x4-block granularity, per plane, one launch per level */
 static int recon_levels(IntraCall &c)
 {
-    std::vector<std::vector<uint32_t>> lists;
-    {
-        std::vector<int> lvl[3];
-        int bw[3];
-        for (int k = 0; k < 3; k++) {
-            bw[k] = (c.pw[k] + 3) / 4;
-            lvl[k].assign((size_t)(k == 0 || c.chroma ? bw[k] * ((c.ph[k] + 3) / 4) : 0), -1);
-        }
-        for (long long i = 0; i < c.n_tus; i++) {
-            const ffhip_hevc_tu &t = c.h_tus[i];
-            const int k = t.cidx, n = 1 << t.log2_size;
-            int lv = 0;
-            auto dep = [&](int px, int py) { lv = std::max(lv, lvl[k][(size_t)(py / 4) * bw[k] + px / 4] + 1); };
-            if (t.flags & 1) dep(t.x - 1, t.y - 1);
-            for (int j = 0; j < 2 * n; j++) {
-                if ((t.avail_top >> j) & 1) dep(t.x + j, t.y - 1);
-                if ((t.avail_left >> j) & 1) dep(t.x - 1, t.y + j);
-            }
-            for (int by = t.y / 4; by < (t.y + n) / 4; by++)
-                for (int bx = t.x / 4; bx < (t.x + n) / 4; bx++) lvl[k][(size_t)by * bw[k] + bx] = lv;
-            if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
-            lists[(size_t)lv].push_back((uint32_t)i);
-        }
-    }
+    std::vector<std::vector<uint32_t>> lists = intra_levels(c.h_tus, c.n_tus, c.pw, c.ph, c.chroma);
     std::vector<uint32_t> flat;
     flat.reserve((size_t)c.n_tus);
     for (auto &l : lists) flat.insert(flat.end(), l.begin(), l.end());

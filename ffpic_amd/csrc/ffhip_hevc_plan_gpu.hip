@@ -1,7 +1,7 @@
 /*
  * ffhip_hevc_plan_gpu.hip -- the group schedule of ffhip_hevc_intra_recon built ON the device.
  *
- * The host planner (plan_groups in ffhip_hevc_intra.hip) costs ~30 ns per TU on one core: more than the kernel it
+ * The host planner (plan_groups in ffhip_hevc_plan_host.hip) costs ~30 ns per TU on one core: more than the kernel it
  * feeds once a picture has a few hundred thousand TUs (an 8K picture, a HEIF grid).  Everything it derives is a pure
  * function of the TU list, one TU at a time, given the map "which TU owns this 4x4 block":
  *   k_plan_owner   every TU stamps its index on its blocks, says whether it starts a new RUN (a maximal stretch of consecutive TUs whose
@@ -29,7 +29,7 @@
  *                  smaller ticket -- the deadlock-freedom condition of the grouped kernel -- from the wait list as written
  * Same output layout as the host planner.  Nothing here is a library primitive: the scans are a wave shuffle scan + LDS.
  */
-#include "ffhip_internal.h"
+#include "ffhip_hevc_plan.h"
 
 /* ---- scans: a shuffle scan inside the wave, the waves' totals through LDS ---- */
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, const int lane)
@@ -806,8 +806,8 @@ __global__ __launch_bounds__(256) void k_plan_runid(PlanArgs a)
     if (i < a.n) a.runid[i] = before + incl - 1u;
 }
 
-/* Validation of a large TU list ON the device (what ffhip_hevc_intra_recon's host pass checks record by record: field ranges, the block
- * inside its plane, no availability bit pointing outside the plane, a residual buffer where a TU asks for one).  For lists of 2^17 TUs and
+/* Validation of a large TU list ON the device (what ffhip_hevc_intra_recon's host pass checks record by record: hevc_tu_valid of
+ * ffhip_hevc_plan.h, the one rule of both, and a residual buffer where a TU asks for one).  For lists of 2^17 TUs and
  * more the host only looks at a sample (a pass over 1.8 M records was 0.7 ms of an enqueue call next to 4 ms of device work); a bad record
  * found here refuses the call through the stream: result[6] sends every kernel behind this one home, result[0] the grouped kernel, and
  * ffhip_stream_sync reports FFHIP_EINVAL -- nothing is written. */
@@ -822,18 +822,7 @@ __global__ __launch_bounds__(256) void k_hevc_check_tus(const ffhip_hevc_tu *tus
     bool bad = false;
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const ffhip_hevc_tu t = tus[i];
-        const int c = t.cidx;
-        if (c > 2 || t.log2_size < 2 || t.log2_size > 5 || t.pred_mode > 34) { bad = true; continue; }
-        const int sz = 1 << t.log2_size;
-        if (c > 0 && !k.chroma_ok) bad = true;
-        if (t.x + sz > k.pw[c] || t.y + sz > k.ph[c]) { bad = true; continue; }
-        const unsigned long long span = sz == 32 ? ~0ull : (1ull << (2 * sz)) - 1;
-        const unsigned long long top = t.avail_top & span, left = t.avail_left & span;
-        const int room_x = k.pw[c] - t.x, room_y = k.ph[c] - t.y;
-        if ((top || (t.flags & 1)) && t.y == 0) bad = true;
-        if ((left || (t.flags & 1)) && t.x == 0) bad = true;
-        if (room_x < 64 && (top >> room_x)) bad = true;
-        if (room_y < 64 && (left >> room_y)) bad = true;
+        if (!hevc_tu_valid(t, k.pw, k.ph, k.chroma_ok != 0)) bad = true;
         if ((t.flags & 2) && !k.have_residual) bad = true;
     }
     if (__builtin_amdgcn_ballot_w64(bad) && (threadIdx.x & 63) == 0) {
@@ -923,7 +912,7 @@ size_t ffhip_hevc_plan_gpu_words(long long n_tus, const int pw[3], const int ph[
     return plan_layout(a, nullptr, nullptr, n_tus, pw, ph, wl).words;
 }
 
-/* The stages of FfhipHevcPlan (ffhip_internal.h).  owner = -1, win_run = ~0 (adjacent); flags, result = 0 (adjacent); cell_claim = ~0;
+/* The stages of FfhipHevcPlan (ffhip_hevc_plan.h).  owner = -1, win_run = ~0 (adjacent); flags, result = 0 (adjacent); cell_claim = ~0;
  * cell_edges, cell_nruns, hist, fill = 0 (adjacent: OR-ed and added into; every cell's depth is written by the sweep): ONE launch for the four
  * regions and the caller's -- as four memsets they were four more kernel boundaries in front of a chain of small kernels */
 void FfhipHevcPlan::begin(const ffhip_hevc_tu *d_tus, long long n_tus, const int pw[3], const int ph[3], const int wl[3], uint32_t *scratch, hipStream_t stream,
