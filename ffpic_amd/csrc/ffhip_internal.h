@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -147,6 +148,14 @@ int vp8_predict_recon_impl(int mbcols, int mbrows, int n_images, const uint8_t *
                            int64_t plane_stride_uv, void *stream, Vp8SideBySide *sbs);
 int vp8_loopfilter_impl(int mbcols, int mbrows, int n_images, int filter_type, const uint8_t *d_modes, const uint8_t *d_filters, uint8_t *d_y,
                         uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const Vp8SideBySide *sbs);
+/* shared by the two stages' host entries (ffhip_vp8_pred.hip).  The row forms' switches: FFHIP_VP8_PROGRESS_SHIFT, FFHIP_VP8_SLACK, and where the
+ * kernel reports a wait that ran out -- the process-wide pinned word, the side-by-side call's own, or NULL: no row form (`mode` is "levels") */
+struct Vp8RowSwitches { int pshift, slack; int *async_err; };
+Vp8RowSwitches vp8_row_switches(const char *mode, const Vp8SideBySide *sbs);
+/* the levels forms' common end: lists[level] = (image, macroblock) pairs; flattened into scratch `scratch_kind` of the stream (after a
+ * synchronise: an earlier call may still read it), then launch(work, count) for every level that has pairs, in order */
+int vp8_levels_upload_and_launch(int scratch_kind, void *stream, const std::vector<std::vector<uint32_t>> &lists,
+                                 const std::function<void(const uint32_t *work, int count)> &launch);
 int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
                                 int64_t residual_stride, const int32_t *d_resmap, int filter_type, const uint8_t *d_filters, uint8_t *d_y,
                                 uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const FfhipVp8Then *then);

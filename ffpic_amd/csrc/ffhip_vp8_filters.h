@@ -1,12 +1,11 @@
 /* ffhip_vp8_filters.h -- the VP8 loop filter's edge filters (format/webp.c:1480-1553) as device functions shared by the row
- * kernels of ffhip_vp8_lf.hip and the fused frame kernel of ffhip_vp8_frame.hip. */
+ * kernels of ffhip_vp8_lf.hip and the fused frame kernel of ffhip_vp8_frame.hip (clamp255, wave_sync, FLS: ffhip_vp8_device.h). */
 #ifndef FFHIP_VP8_FILTERS_H
 #define FFHIP_VP8_FILTERS_H
-#include "ffhip_internal.h"
+#include "ffhip_vp8_device.h"
 
 __device__ __forceinline__ int sclip1(int v) { return v < -128 ? -128 : (v > 127 ? 127 : v); }
 __device__ __forceinline__ int sclip2(int v) { return v < -16 ? -16 : (v > 15 ? 15 : v); }
-__device__ __forceinline__ int clip255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 __device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 
 /* p[0..7] = p3 p2 p1 p0 q0 q1 q2 q3 across one edge */
@@ -14,28 +13,28 @@ __device__ __forceinline__ void filt2(int *p)
 {
     const int a = 3 * (p[4] - p[3]) + sclip1(p[2] - p[5]);
     const int a1 = sclip2((a + 4) >> 3), a2 = sclip2((a + 3) >> 3);
-    p[3] = clip255(p[3] + a2);
-    p[4] = clip255(p[4] - a1);
+    p[3] = clamp255(p[3] + a2);
+    p[4] = clamp255(p[4] - a1);
 }
 __device__ __forceinline__ void filt4(int *p)
 {
     const int a = 3 * (p[4] - p[3]);
     const int a1 = sclip2((a + 4) >> 3), a2 = sclip2((a + 3) >> 3), a3 = (a1 + 1) >> 1;
-    p[2] = clip255(p[2] + a3);
-    p[3] = clip255(p[3] + a2);
-    p[4] = clip255(p[4] - a1);
-    p[5] = clip255(p[5] - a3);
+    p[2] = clamp255(p[2] + a3);
+    p[3] = clamp255(p[3] + a2);
+    p[4] = clamp255(p[4] - a1);
+    p[5] = clamp255(p[5] - a3);
 }
 __device__ __forceinline__ void filt6(int *p)
 {
     const int a = sclip1(3 * (p[4] - p[3]) + sclip1(p[2] - p[5]));
     const int a1 = (27 * a + 63) >> 7, a2 = (18 * a + 63) >> 7, a3 = (9 * a + 63) >> 7;
-    p[1] = clip255(p[1] + a3);
-    p[2] = clip255(p[2] + a2);
-    p[3] = clip255(p[3] + a1);
-    p[4] = clip255(p[4] - a1);
-    p[5] = clip255(p[5] - a2);
-    p[6] = clip255(p[6] - a3);
+    p[1] = clamp255(p[1] + a3);
+    p[2] = clamp255(p[2] + a2);
+    p[3] = clamp255(p[3] + a1);
+    p[4] = clamp255(p[4] - a1);
+    p[5] = clamp255(p[5] - a2);
+    p[6] = clamp255(p[6] - a3);
 }
 /* one sample position of one edge; s points at p3 of an 8-sample window inside the line */
 __device__ __forceinline__ void edge_simple(int *s, int thresh)
@@ -71,13 +70,6 @@ __device__ __forceinline__ void filter_line(int *line, int type, bool outer, boo
     }
 }
 
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* The row kernel filters the 16 luma lines and the 2 x 8 chroma lines of a macroblock with ONE instruction stream: lanes
  * 0-15 hold a luma line (edges at 0, 4, 8, 12), lanes 16-31 a chroma line (edges at 0 and 4; the normal filter only).
  * As two branches of an if / else the chroma lines ran behind the luma lines: half as much again per phase. */
@@ -95,8 +87,8 @@ __device__ __forceinline__ void edge_simple_bf(int *s, int thresh, bool on)
     const bool apply = on && 4 * absdiff(s[3], s[4]) + absdiff(s[2], s[5]) <= 2 * thresh + 1;
     const int a = apply ? 3 * (s[4] - s[3]) + sclip1(s[2] - s[5]) : 0;
     const int a1 = sclip2((a + 4) >> 3), a2 = sclip2((a + 3) >> 3);
-    s[3] = clip255(s[3] + a2);
-    s[4] = clip255(s[4] - a1);
+    s[3] = clamp255(s[3] + a2);
+    s[4] = clamp255(s[4] - a1);
 }
 template <bool MB_EDGE>
 __device__ __forceinline__ void edge_normal_bf(int *s, int thresh, int ithresh, int hevt, bool on)
@@ -111,19 +103,19 @@ __device__ __forceinline__ void edge_normal_bf(int *s, int thresh, int ithresh, 
         const int a1 = sclip2((a + 4) >> 3), a2 = sclip2((a + 3) >> 3);
         const int b = (apply && !hev) ? sclip1(base + w) : 0;
         const int b1 = (27 * b + 63) >> 7, b2 = (18 * b + 63) >> 7, b3 = (9 * b + 63) >> 7;
-        s[1] = clip255(s[1] + b3);
-        s[2] = clip255(s[2] + b2);
-        s[3] = clip255(s[3] + a2 + b1);
-        s[4] = clip255(s[4] - a1 - b1);
-        s[5] = clip255(s[5] - b2);
-        s[6] = clip255(s[6] - b3);
+        s[1] = clamp255(s[1] + b3);
+        s[2] = clamp255(s[2] + b2);
+        s[3] = clamp255(s[3] + a2 + b1);
+        s[4] = clamp255(s[4] - a1 - b1);
+        s[5] = clamp255(s[5] - b2);
+        s[6] = clamp255(s[6] - b3);
     } else {       /* filt2 where the edge has high variance, filt4 elsewhere */
         const int a = apply ? base + (hev ? w : 0) : 0;
         const int a1 = sclip2((a + 4) >> 3), a2 = sclip2((a + 3) >> 3), a3 = hev ? 0 : (a1 + 1) >> 1;
-        s[2] = clip255(s[2] + a3);
-        s[3] = clip255(s[3] + a2);
-        s[4] = clip255(s[4] - a1);
-        s[5] = clip255(s[5] - a3);
+        s[2] = clamp255(s[2] + a3);
+        s[3] = clamp255(s[3] + a2);
+        s[4] = clamp255(s[4] - a1);
+        s[5] = clamp255(s[5] - a3);
     }
 }
 /* `outer` (the macroblock has a neighbour on that side) and `lum` (the lane holds a luma line: edges at 8 and 12) are
@@ -150,7 +142,7 @@ __device__ __forceinline__ void filter_line_mixed(int *line, bool outer, bool in
         }
     }
 }
-/* STRIDE 1: the line is a pixel row (vertical edges); STRIDE LS (== CS): a pixel column (horizontal edges) */
+/* STRIDE 1: the line is a pixel row (vertical edges); STRIDE FLS: a pixel column (horizontal edges) */
 template <int STRIDE, int TYPE>
 __device__ __forceinline__ void filter_phase(uint8_t *base, const bool active, const bool lum, bool outer, bool inner, int sub, int inter, int hevt)
 {

@@ -59,27 +59,9 @@ struct Vp8FrameArgs {
     unsigned slot_bytes;
 };
 
-/* the directional 4x4 predictors' taps (the table of ffhip_vp8_pred.hip, generated by tests/tools/gen_vp8_pred_table.py):
- * a | b<<4 | c<<8 per (mode-2, pixel); pixel = (e[a] + 2 e[b] + e[c] + 2) >> 2 on e = L K J I X A B C D E F G H */
-__device__ static const unsigned short kFrTaps[8][16] = {
-    {0x654, 0x765, 0x876, 0x987, 0x654, 0x765, 0x876, 0x987, 0x654, 0x765, 0x876, 0x987, 0x654, 0x765, 0x876, 0x987},
-    {0x432, 0x432, 0x432, 0x432, 0x321, 0x321, 0x321, 0x321, 0x210, 0x210, 0x210, 0x210, 0x100, 0x100, 0x100, 0x100},
-    {0x543, 0x654, 0x765, 0x876, 0x432, 0x543, 0x654, 0x765, 0x321, 0x432, 0x543, 0x654, 0x210, 0x321, 0x432, 0x543},
-    {0x545, 0x656, 0x767, 0x878, 0x543, 0x654, 0x765, 0x876, 0x432, 0x545, 0x656, 0x767, 0x321, 0x543, 0x654, 0x765},
-    {0x765, 0x876, 0x987, 0xa98, 0x876, 0x987, 0xa98, 0xba9, 0x987, 0xa98, 0xba9, 0xcba, 0xa98, 0xba9, 0xcba, 0xccb},
-    {0x656, 0x767, 0x878, 0x989, 0x765, 0x876, 0x987, 0xa98, 0x767, 0x878, 0x989, 0xba9, 0x876, 0x987, 0xa98, 0xcba},
-    {0x434, 0x543, 0x654, 0x765, 0x323, 0x432, 0x434, 0x543, 0x212, 0x321, 0x323, 0x432, 0x101, 0x210, 0x212, 0x321},
-    {0x323, 0x321, 0x212, 0x210, 0x212, 0x210, 0x101, 0x100, 0x101, 0x100, 0x000, 0x000, 0x000, 0x000, 0x000, 0x000},
-};
-
 #define FR_SPIN_LIMIT (1 << 22)
-#define PRS 28 /* prediction luma tile: [3] left column, [4..19] pixels, [20..23] above-right; row 0 = the row above */
-#define PCS 16 /* prediction chroma tiles: [3] left column, [4..11] pixels; row 0 = the row above */
-#define FLS 24 /* filter tiles (luma: 6 rows above, 8 columns left; chroma: 4 and 4), one stride for both (filter_phase) */
-#define FBT_C0 480
-#define FBT_C1 624
-#define FBT_DUMP 768
-/* one wave's LDS arena */
+/* one wave's LDS arena (tile strides, tile offsets and lane masks: ffhip_vp8_device.h; the filter tiles here have 6 rows above and 8 columns left
+ * for luma, 4 and 4 for chroma) */
 #define AR_BT 0      /* 784 B: prediction tiles + dump cell                         */
 #define AR_R 800     /* 768 B: the macroblock's residual                            */
 #define AR_TL 1568   /* 22 x 24 B: luma filter tile                                 */
@@ -94,28 +76,10 @@ __device__ static const unsigned short kFrTaps[8][16] = {
 #define SH_BYTES 768
 #define FR_OUT ((int)0x80000000u) /* a buffer offset outside everything: loads return 0, stores are dropped */
 
-#define FM_LUMATOP 0x00000000001fffffull   /* lanes 0..20  */
-#define FM_TOPRIGHT 0x00000000001e0000ull  /* lanes 17..20 */
-#define FM_UTOP 0x000000003fe00000ull      /* lanes 21..29 */
-#define FM_VTOP 0x000001ff00000000ull      /* lanes 32..40 */
-#define FM_LEFT 0xffff000000000000ull      /* lanes 48..63 */
-#define FM_FIRST_LUMA 0x0000000000000001ull
-#define FM_FIRST_CHROMA 0x0000000100200000ull
-
-typedef u32 fr_u32x3 __attribute__((ext_vector_type(3)));
-
-__device__ __forceinline__ int fr_clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-__device__ __forceinline__ int fr_sum4(u32 v) { return (int)__builtin_amdgcn_sad_u8(v, 0u, 0u); }
-/* b where the lane's bit of the (wave-uniform) 64-bit mask is set, else a */
-__device__ __forceinline__ int fr_select(unsigned long long mask, int a, int b)
-{
-    int r; /* (every mask here comes from ballots and wave-uniform conditions: it is in SGPRs already) */
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(mask));
-    return r;
-}
 #define FR_AUX_SC0 1 /* workgroup-scope loads of the lines (they hit the CU's L1 like plain loads: the producer is on this CU) */
 /* a B_PRED sub-block mode as the row reads it: k_vp8_frames takes it as it is (the host's check or k_vp8_check_modes refused the call
- * in front of it); k_vp8_frames_items clamps it (an item's host copy is checked, not its device copy: TT is never indexed beyond mode 9) */
+ * in front of it); k_vp8_frames_items clamps it (an item's host copy is checked, not its device copy: TT is never indexed beyond mode 9).
+ * What a valid record is: vp8_mode_record_valid, ffhip_vp8_device.h */
 #define FR_SUBMODE(m) m
 
 template <int TYPE, bool PLANES, bool MAP> /* MAP: the call has a residual map (d_resmap): its scalar load per macroblock and four scalar registers only there; loop filter of the launch: 0 none, 1 simple, 2 normal; PLANES: the filtered planes are written as well (their three buffer
@@ -130,7 +94,7 @@ __global__ __launch_bounds__(1024) void k_vp8_frames(Vp8FrameArgs a)
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), NW = (int)(blockDim.x >> 6);
     uint8_t *const AR = smem + SH_BYTES + w * AR_BYTES;
-    uint8_t *const BT = AR + AR_BT, *const T = BT, *const C0 = BT + FBT_C0, *const C1 = BT + FBT_C1;
+    uint8_t *const BT = AR + AR_BT, *const T = BT, *const C0 = BT + BT_C0, *const C1 = BT + BT_C1;
     short *const R = (short *)(AR + AR_R);
     uint8_t *const TL = AR + AR_TL;
     typedef __attribute__((address_space(3))) uint8_t lds_u8;
@@ -144,13 +108,15 @@ __global__ __launch_bounds__(1024) void k_vp8_frames(Vp8FrameArgs a)
      * V (rows 4..7), then the unfiltered bottom row of Y, U, V */
     const int off_fu = 6 * ys, off_fv = 6 * ys + 4 * us, off_ul = 6 * ys + 8 * us, off_uu = off_ul + ys, off_uv = off_uu + us;
 
-    /* ---- once per workgroup: the tap table, the filter parameters, the counters ---- */
+    /* ---- once per workgroup: the tap table, the filter parameters, the counters.  (This start of the workgroup is twice in this file, and the tap table's fill a third time in
+     * k_vp8_predict_rows: as one included text or one inlined helper the same values came out of other instructions, and these kernels' code
+     * is pinned.) ---- */
     if (w == 0) {
         if (lane < 16) {
             auto off = [](int k) { return k < 4 ? (3 - k) * PRS - 1 : (k == 4 ? -PRS - 1 : -PRS + (k - 5)); };
 #pragma unroll
             for (int m = 0; m < 8; m++) {
-                const unsigned t = kFrTaps[m][lane];
+                const unsigned t = kVp8Taps[m][lane];
                 TT[(m + 2) * 16 + lane] = (u32)(off((int)(t & 15)) + 64) | ((u32)(off((int)((t >> 4) & 15)) + 64) << 8) | ((u32)(off((int)(t >> 8)) + 64) << 16);
             }
             const int r = lane >> 2, c = lane & 3;
@@ -237,7 +203,7 @@ __global__ __launch_bounds__(1024) void k_vp8_frames_items(Vp8ItemsArgs ia)
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), NW = (int)(blockDim.x >> 6);
     uint8_t *const AR = smem + SH_BYTES + w * AR_BYTES;
     uint8_t *const FT = smem + SH_BYTES + NW * AR_BYTES + 32 * w; /* the wave's frame's filter parameters */
-    uint8_t *const BT = AR + AR_BT, *const T = BT, *const C0 = BT + FBT_C0, *const C1 = BT + FBT_C1;
+    uint8_t *const BT = AR + AR_BT, *const T = BT, *const C0 = BT + BT_C0, *const C1 = BT + BT_C1;
     short *const R = (short *)(AR + AR_R);
     uint8_t *const TL = AR + AR_TL;
     typedef __attribute__((address_space(3))) uint8_t lds_u8;
@@ -250,7 +216,7 @@ __global__ __launch_bounds__(1024) void k_vp8_frames_items(Vp8ItemsArgs ia)
             auto off = [](int k) { return k < 4 ? (3 - k) * PRS - 1 : (k == 4 ? -PRS - 1 : -PRS + (k - 5)); };
 #pragma unroll
             for (int m = 0; m < 8; m++) {
-                const unsigned t = kFrTaps[m][lane];
+                const unsigned t = kVp8Taps[m][lane];
                 TT[(m + 2) * 16 + lane] = (u32)(off((int)(t & 15)) + 64) | ((u32)(off((int)((t >> 4) & 15)) + 64) << 8) | ((u32)(off((int)(t >> 8)) + 64) << 16);
             }
             const int r = lane >> 2, c = lane & 3;
@@ -333,12 +299,39 @@ static int decode_frames_rows(int mbcols, int mbrows, int n_images, const uint8_
                                 image_stride, stream);
 }
 
+static int device_cus() /* of the current device, asked every time */
+{
+    int cus = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+}
+
+/* Waves per workgroup, i.e. per frame at work: 16 while there is at most one frame per CU (four waves per SIMD either way), else 8 and two
+ * frames per CU -- or 4 and four frames:
+ * rows that start with the reference's wrapped 16x16 H_PRED (predict.c:346-353: the sample left of a row's first pixel is the LAST pixel of
+ * the row above) wait for the whole row above: while such a row waits, its frame keeps ONE wave busy.  A stream with many of them -- one
+ * row in seven with uniformly random modes -- is faster with four frames of four waves on a CU than with two of eight: 1 024 random-mode
+ * 1080p frames 12.5 ms against 14.4 (an encoder's stream, which has next to none: 8.85 against 8.41).  Told from a sample of the host's
+ * copies of the modes: the first column of up to 32 frames, `sampler(f)` yielding frame f's (modes NULL: it has no host copy). */
+struct Vp8FirstColumn { const uint8_t *modes; int mbcols, mbrows; };
+template <class Sampler>
+static int frame_waves(int n_frames, int cus, Sampler sampler)
+{
+    if (n_frames < 4LL * cus) return n_frames <= cus ? 16 : 8;
+    long long rows = 0, serial = 0;
+    for (int f = 0, step = n_frames > 32 ? n_frames / 32 : 1; f < n_frames; f += step) {
+        const Vp8FirstColumn c = sampler(f);
+        if (!c.modes) continue;
+        for (int y = 1; y < c.mbrows; y++, rows++) serial += c.modes[(long long)y * c.mbcols * 20] == 3;
+    }
+    return rows > 0 && serial * 16 >= rows ? 4 : 8;
+}
+
 static bool frames_take_fused_form(int n_images)
 {
     /* the frame kernel wants a frame per workgroup and enough workgroups to fill the chip; a handful of frames is
      * faster as rows of any frame on any wave (ffhip_vp8_pred.hip).  FFHIP_VP8_FRAMES=rows|fused forces either. */
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus();
     const char *form = FFHIP_ENV("FFHIP_VP8_FRAMES");
     const char *thr = FFHIP_ENV("FFHIP_VP8_FRAMES_MIN");
     const int min_fused = thr ? atoi(thr) : cus / 2;
@@ -367,8 +360,7 @@ extern "C" int ffhip_vp8_decode_frames(int mbcols, int mbrows, int n_images, con
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
 
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus();
     const bool fused = frames_take_fused_form(n_images);
     if (!fused) {
         if (!h_modes) return FFHIP_EINVAL; /* the row form checks small batches on the host copy */
@@ -383,21 +375,8 @@ extern "C" int ffhip_vp8_decode_frames(int mbcols, int mbrows, int n_images, con
     const bool host_checked = h_modes && recs <= (1LL << 17);
     if (host_checked && !ffhip_vp8_modes_ok_host(h_modes, recs)) return FFHIP_EINVAL;
 
-    /* waves per frame: 16 while there is at most one frame per CU (four waves per SIMD either way), else 8 and two frames per CU */
     const char *nwv = FFHIP_ENV("FFHIP_VP8_FRAME_WAVES");
-    int nw = nwv ? atoi(nwv) : (n_images <= cus ? 16 : 8);
-    if (!nwv && h_modes && n_images >= 4LL * cus) {
-        /* Rows that start with the reference's wrapped 16x16 H_PRED (predict.c:346-353: the sample left of a row's first pixel is the LAST pixel of
-         * the row above) wait for the whole row above: while such a row waits, its frame keeps ONE wave busy.  A stream with many of them -- one
-         * row in seven with uniformly random modes -- is faster with four frames of four waves on a CU than with two of eight: 1 024 random-mode
-         * 1080p frames 12.5 ms against 14.4 (an encoder's stream, which has next to none: 8.85 against 8.41).  Told from a sample of the host's
-         * copy of the modes: the first column of up to 32 frames. */
-        long long rows = 0, serial = 0;
-        const int step = n_images > 32 ? n_images / 32 : 1;
-        for (long long f = 0; f < n_images; f += step)
-            for (int y = 1; y < mbrows; y++, rows++) serial += h_modes[(f * n_mb + (long long)y * mbcols) * 20] == 3;
-        if (rows > 0 && serial * 16 >= rows) nw = 4;
-    }
+    int nw = nwv ? atoi(nwv) : frame_waves(n_images, cus, [&](int f) { return Vp8FirstColumn{h_modes ? h_modes + (long long)f * n_mb * 20 : nullptr, mbcols, mbrows}; });
     nw = std::max(1, std::min(16, nw));
     const size_t lds = SH_BYTES + (size_t)nw * AR_BYTES;
     const bool planes = d_y != nullptr;
@@ -477,8 +456,7 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
     hipStream_t st = (hipStream_t)stream;
     int *async_err = ffhip_async_err_word();
     if (!async_err) return FFHIP_ENOMEM;
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus();
 
     /* one launch per (filter type, residual-map form) present; in each, the frames dealt largest first to the least-loaded workgroup */
     struct Launch {
@@ -500,18 +478,10 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
                 if (items[i].filter_type == ft && (items[i].d_resmap != nullptr) == L.map) L.frames.push_back(i);
             if (L.frames.empty()) continue;
             const int nf = (int)L.frames.size();
-            /* waves per workgroup: ffhip_vp8_decode_frames' choice for a batch of this many frames */
-            int nw = nf <= cus ? 16 : 8;
-            if (nf >= 4LL * cus) {
-                long long rows = 0, serial = 0;
-                const int step = nf > 32 ? nf / 32 : 1;
-                for (int f = 0; f < nf; f += step) {
-                    const ffhip_vp8_item &it = items[L.frames[(size_t)f]];
-                    if (!it.h_modes) continue;
-                    for (int y = 1; y < it.mbrows; y++, rows++) serial += it.h_modes[(long long)y * it.mbcols * 20] == 3;
-                }
-                if (rows > 0 && serial * 16 >= rows) nw = 4;
-            }
+            const int nw = frame_waves(nf, cus, [&](int f) { /* ffhip_vp8_decode_frames' choice for a batch of this many frames */
+                const ffhip_vp8_item &it = items[L.frames[(size_t)f]];
+                return Vp8FirstColumn{it.h_modes, it.mbcols, it.mbrows};
+            });
             L.nw = nw;
             L.lds = SH_BYTES + (size_t)nw * (AR_BYTES + 32);
             int per_cu = 0;

@@ -5,10 +5,10 @@
      * columns -1..7 (21..29, 32..40); lane 48: the sample left of the row's first pixel at x = 0 (the last pixel of the row above) */
     const int pb_off = lane <= 20 ? off_ul + lane - 1 : (lane >= 21 && lane <= 29 ? off_uu + lane - 22 : (lane >= 32 && lane <= 40 ? off_uv + lane - 33 : FR_OUT));
     const int pb_step = lane <= 20 ? 16 : 8;
-    const int dst1 = lane <= 20 ? 3 + lane : (lane <= 29 && lane >= 21 ? FBT_C0 + 3 + (lane - 21) : (lane >= 32 && lane <= 40 ? FBT_C1 + 3 + (lane - 32) :
-                     (lane >= 48 ? (lane - 47) * PRS + 3 : FBT_DUMP)));
-    const int dst2 = lane < 16 ? (lane < 8 ? FBT_C0 : FBT_C1) + ((lane & 7) + 1) * PCS + 3 : FBT_DUMP;
-    const int carry_src = lane >= 48 ? (lane - 47) * PRS + 4 + 15 : (lane < 16 ? (lane < 8 ? FBT_C0 : FBT_C1) + ((lane & 7) + 1) * PCS + 4 + 7 : FBT_DUMP);
+    const int dst1 = lane <= 20 ? 3 + lane : (lane <= 29 && lane >= 21 ? BT_C0 + 3 + (lane - 21) : (lane >= 32 && lane <= 40 ? BT_C1 + 3 + (lane - 32) :
+                     (lane >= 48 ? (lane - 47) * PRS + 3 : BT_DUMP)));
+    const int dst2 = lane < 16 ? (lane < 8 ? BT_C0 : BT_C1) + ((lane & 7) + 1) * PCS + 3 : BT_DUMP;
+    const int carry_src = lane >= 48 ? (lane - 47) * PRS + 4 + 15 : (lane < 16 ? (lane < 8 ? BT_C0 : BT_C1) + ((lane & 7) + 1) * PCS + 4 + 7 : BT_DUMP);
     /* the filter tiles' top rows out of the row above's filtered lines, a dword per lane: luma rows -6..-1 (lanes 0..23: row
      * lane >> 2, dword lane & 3), chroma rows -4..-1 of U (32..39) and V (40..47) */
     const int lt_off = lane < 24 ? (lane >> 2) * ys + 4 * (lane & 3) : (lane >= 32 && lane < 48 ? (lane < 40 ? off_fu : off_fv) + ((lane >> 1) & 3) * us + 4 * (lane & 1) : FR_OUT);
@@ -36,8 +36,8 @@
     } else if (lane >= 56) {
         const int k = lane - 56;
         if (k < 4) { ls_src = bt + (unsigned)(16 * PRS + 4 + 4 * k); ls_dst = off_ul + 4 * k; ls_step = 16; }
-        else if (k < 6) { ls_src = bt + (unsigned)(FBT_C0 + 8 * PCS + 4 + 4 * (k - 4)); ls_dst = off_uu + 4 * (k - 4); ls_step = 8; }
-        else { ls_src = bt + (unsigned)(FBT_C1 + 8 * PCS + 4 + 4 * (k - 6)); ls_dst = off_uv + 4 * (k - 6); ls_step = 8; }
+        else if (k < 6) { ls_src = bt + (unsigned)(BT_C0 + 8 * PCS + 4 + 4 * (k - 4)); ls_dst = off_uu + 4 * (k - 4); ls_step = 8; }
+        else { ls_src = bt + (unsigned)(BT_C1 + 8 * PCS + 4 + 4 * (k - 6)); ls_dst = off_uv + 4 * (k - 6); ls_step = 8; }
         ls_first = true;
     } else { ls_src = dump; ls_dst = FR_OUT; ls_step = 0; ls_first = false; }
     const unsigned long long ls_any = __builtin_amdgcn_ballot_w64(ls_dst != FR_OUT), ls_at0 = __builtin_amdgcn_ballot_w64(ls_first);

@@ -29,6 +29,7 @@
             while (seen < want) {
                 seen = (u32)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&PROG[wp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                 if (seen >= want) break;
+                /* (the row kernels of ffhip_vp8_pred.hip / ffhip_vp8_lf.hip wait the same way on device-coherent counters: another scope, sleep and limit) */
                 /* A wait that runs out cannot happen (the row above belongs to a wave of this workgroup); a hang guard all the same.  It does NOT
                  * leave the kernel: the wave stops waiting -- here and, through the abort word, everywhere in the workgroup -- and goes on to the end
                  * with whatever it finds (the call reports FFHIP_EIO).  An exit from inside the macroblock loop would be one more way round it for
@@ -49,7 +50,7 @@
              * With a branch round them the compiler's wait for the fetched registers -- the minimum over the ways into the loop head -- became a
              * wait for everything in flight, the stores issued behind the fetch included */
             {
-                const fr_u32x3 r3 = __builtin_bit_cast(fr_u32x3, __builtin_amdgcn_raw_buffer_load_b96(rRes, real_row ? lane * 12 : FR_OUT, (int)(rrow * 768), 0));
+                const u32x3 r3 = __builtin_bit_cast(u32x3, __builtin_amdgcn_raw_buffer_load_b96(rRes, real_row ? lane * 12 : FR_OUT, (int)(rrow * 768), 0));
                 f.res[0] = r3[0]; f.res[1] = r3[1]; f.res[2] = r3[2];
                 f.mo = (u32)__builtin_amdgcn_raw_buffer_load_b32(rMo, (lane < 5 ? lane : 4) * 4, x1 * 20, 0);
                 /* the row above's last pixel for the raw H_PRED read at x = 0; the rest of that column is not reconstructed yet and reads 0 */
@@ -88,13 +89,13 @@
                 const bool raw = ymode == 2 || ymode == 3;
                 const int carry = (int)BT[carry_src]; /* the previous macroblock's right column (unfiltered: the filter works on its own tile) */
                 const unsigned long long none = 0ull;
-                *(fr_u32x3 *)((char *)R + lane * 12) = fr_u32x3{f.res[0], f.res[1], f.res[2]};
-                const unsigned long long m127 = (y == 0 ? (FM_UTOP | FM_VTOP | (raw ? none : FM_LUMATOP)) : none) | ((!raw && x == a.mbcols - 1) ? FM_TOPRIGHT : none);
-                const unsigned long long m129 = (x == 0 ? (FM_FIRST_CHROMA | (raw ? none : (FM_FIRST_LUMA | FM_LEFT))) : none) & ~m127;
+                *(u32x3 *)((char *)R + lane * 12) = u32x3{f.res[0], f.res[1], f.res[2]};
+                const unsigned long long m127 = (y == 0 ? (M_UTOP | M_VTOP | (raw ? none : M_LUMATOP)) : none) | ((!raw && x == a.mbcols - 1) ? M_TOPRIGHT : none);
+                const unsigned long long m129 = (x == 0 ? (M_FIRST_CHROMA | (raw ? none : (M_FIRST_LUMA | M_LEFT))) : none) & ~m127;
                 int v = f.pb;
-                v = fr_select(x != 0 ? FM_LEFT : none, v, carry);
-                v = fr_select(m127, v, 127);
-                v = fr_select(m129, v, 129);
+                v = lane_select_smask(x != 0 ? M_LEFT : none, v, carry);
+                v = lane_select_smask(m127, v, 127);
+                v = lane_select_smask(m129, v, 129);
                 BT[dst1] = (uint8_t)v;
                 BT[dst2] = (uint8_t)(x == 0 ? 129 : carry);
             }
@@ -155,17 +156,17 @@
                         uint8_t *S = T + sb;
                         const int va = T[sb - 64 + (int)(to & 0xff)], vb = T[sb - 64 + (int)((to >> 8) & 0xff)], vc = T[sb - 64 + (int)(to >> 16)];
                         const int dir = (va + 2 * vb + vc + 2) >> 2;
-                        const int tm = fr_clamp255(va + vb - vc);
+                        const int tm = clamp255(va + vb - vc);
                         int p = mode == 1 ? tm : dir;
                         /* B_DC_PRED's five LDS reads and the sum only where one of the step's two sub-blocks asks for it (the modes are the
                          * wave's: a scalar test) */
                         if (sub_mode(nA) == 0 || sub_mode(nB) == 0) {
                             const u32 top4 = *(const u32 *)(S - PRS);
                             const int l0 = S[-1], l1 = S[PRS - 1], l2 = S[2 * PRS - 1], l3 = S[3 * PRS - 1];
-                            const int dc = (4 + fr_sum4(top4) + l0 + l1 + l2 + l3) >> 3;
+                            const int dc = (4 + sum4(top4) + l0 + l1 + l2 + l3) >> 3;
                             p = mode == 0 ? dc : p;
                         }
-                        S[r * PRS + c] = (uint8_t)fr_clamp255(p + rv);
+                        S[r * PRS + c] = (uint8_t)clamp255(p + rv);
                         wave_sync();
                     }
                     lumaout = *(const u32 *)(T + (r16 + 1) * PRS + 4 + c16);
@@ -179,7 +180,7 @@
 #pragma unroll
                             for (int k2 = 0; k2 < 16; k2++) dc += T[(k2 + 1) * PRS + 3];
                         }
-                        if (y > 0) dc += fr_sum4(*(const u32 *)(T + 4)) + fr_sum4(*(const u32 *)(T + 8)) + fr_sum4(*(const u32 *)(T + 12)) + fr_sum4(*(const u32 *)(T + 16));
+                        if (y > 0) dc += sum4(*(const u32 *)(T + 4)) + sum4(*(const u32 *)(T + 8)) + sum4(*(const u32 *)(T + 12)) + sum4(*(const u32 *)(T + 16));
                         if (x == 0 && y == 0) dc = 0x80;
                         else if (x == 0 || y == 0) dc = (dc + 8) >> 4;
                         else dc = (dc + 16) >> 5;
@@ -193,11 +194,11 @@
 #pragma unroll
                     for (int k2 = 0; k2 < 4; k2++) {
                         const int tpx = (int)((top4 >> (8 * k2)) & 0xff);
-                        int p = fr_clamp255(tpx + lc);          /* TM_PRED */
-                        p = fr_select(is_h, p, lf);             /* raw dst[-1]   (predict.c:346-353) */
-                        p = fr_select(is_v, p, tpx);            /* raw row above (predict.c:338-344) */
-                        p = fr_select(is_dc, p, dcv);
-                        o |= (u32)fr_clamp255(p + rs[k2]) << (8 * k2);
+                        int p = clamp255(tpx + lc);          /* TM_PRED */
+                        p = lane_select_smask(is_h, p, lf);             /* raw dst[-1]   (predict.c:346-353) */
+                        p = lane_select_smask(is_v, p, tpx);            /* raw row above (predict.c:338-344) */
+                        p = lane_select_smask(is_dc, p, dcv);
+                        o |= (u32)clamp255(p + rs[k2]) << (8 * k2);
                     }
                     wave_sync();
                     *(u32 *)(T + (r16 + 1) * PRS + 4 + c16) = o;
@@ -217,17 +218,17 @@
 #pragma unroll
                                 for (int k2 = 0; k2 < 8; k2++) dc += Cp[(k2 + 1) * PCS + 3];
                             }
-                            if (y > 0) dc += fr_sum4(*(const u32 *)(Cp + 4)) + fr_sum4(*(const u32 *)(Cp + 8));
+                            if (y > 0) dc += sum4(*(const u32 *)(Cp + 4)) + sum4(*(const u32 *)(Cp + 8));
                             if (x == 0 && y == 0) dc = 0x80;
                             else if (x == 0 || y == 0) dc = (dc + 4) >> 3;
                             else dc = (dc + 8) >> 4;
                             p = dc & 0xff;
                         } else {
-                            p = fr_select(__builtin_amdgcn_ballot_w64(uvmode == 1), lf, fr_clamp255(lf + tpx - cor));
-                            p = fr_select(__builtin_amdgcn_ballot_w64(uvmode == 2), p, tpx);
+                            p = lane_select_smask(__builtin_amdgcn_ballot_w64(uvmode == 1), lf, clamp255(lf + tpx - cor));
+                            p = lane_select_smask(__builtin_amdgcn_ballot_w64(uvmode == 2), p, tpx);
                         }
                         const int ri = 256 + 64 * pl + 16 * (2 * (r >> 2) + (c >> 2)) + 4 * (r & 3) + (c & 3);
-                        outc[pl] = fr_clamp255(p + R[ri]);
+                        outc[pl] = clamp255(p + R[ri]);
                     }
                     wave_sync();
                     C0[(r + 1) * PCS + 4 + c] = (uint8_t)outc[0];
@@ -289,18 +290,18 @@
                 }
             /* ---- stores: the lines (real macroblocks only), the BGRA block, the planes for who wants them ---- */
             {
-                const int dst = fr_select(real_mb ? (x > 0 ? ls_any : ls_at0) : 0ull, FR_OUT, ls_dst + x * ls_step); /* (no lines from the emission-only row and column: dropped) */
+                const int dst = lane_select_smask(real_mb ? (x > 0 ? ls_any : ls_at0) : 0ull, FR_OUT, ls_dst + x * ls_step); /* (no lines from the emission-only row and column: dropped) */
                 __builtin_amdgcn_raw_buffer_store_b32(lsv, rL, dst, me_off, 0);
             }
             {
                 const unsigned long long em_ok = em_rows & (x == 0 ? cols_first : (x < a.mbcols ? ~0ull : ~cols_first));
-                const int dst = fr_select(em_ok, FR_OUT, em_dst + y * 16 * a.pitch + x * 64);
+                const int dst = lane_select_smask(em_ok, FR_OUT, em_dst + y * 16 * a.pitch + x * 64);
                 __builtin_amdgcn_raw_buffer_store_b128(px, rOut, dst, 0, 0);
                 if (PLANES) {
-                    const int dsty = fr_select(em_ok, FR_OUT, em_dsty + y * 16 * ys + x * 16);
+                    const int dsty = lane_select_smask(em_ok, FR_OUT, em_dsty + y * 16 * ys + x * 16);
                     __builtin_amdgcn_raw_buffer_store_b32(el, rY, dsty, 0, 0);
                     const unsigned long long pc_ok = pc_rows & (x == 0 ? pcol_first : (x < a.mbcols ? pc_all : pc_all & ~pcol_first));
-                    const int dstc = fr_select(pc_ok, FR_OUT, pc_dst + y * 8 * us + x * 8);
+                    const int dstc = lane_select_smask(pc_ok, FR_OUT, pc_dst + y * 8 * us + x * 8);
                     if (lane < 16) __builtin_amdgcn_raw_buffer_store_b32(pcv, rU, dstc, 0, 0);
                     else __builtin_amdgcn_raw_buffer_store_b32(pcv, rV, dstc, 0, 0);
                 }

@@ -9,14 +9,18 @@
  * including the reference's choice of which macroblocks get their inner edges filtered
  * (`if (skip_sub_filter)` in the normal filter, `if (!skip_sub_filter)` in the simple one).
  *
- * Dependency-bound like the predictor: filtering macroblock (x, y) reads and rewrites up to
- * 4 / 3 pixels of its left and top neighbours, which must already be filtered (and (x+1, y-1)
- * must have rewritten the top neighbour's right columns).  Same wavefront levels x + 2y, one
- * launch per level over the batch, one wave per macroblock.  The macroblock and its 4-pixel
- * borders sit in LDS; the vertical-edge phase keeps one pixel row per lane in registers
- * (left edge, then the three inner edges), the horizontal-edge phase one column per lane.
+ * Dependency-bound like the predictor: filtering macroblock (x, y) reads and rewrites up to 4 / 3 pixels of its left and top
+ * neighbours, which must already be filtered (and (x+1, y-1) must have rewritten the top neighbour's right columns).  Two forms, as in
+ * ffhip_vp8_pred.hip:
+ *   - the ROW form, the default (k_vp8_loopfilter_rows): one launch per batch, a wave per macroblock row, rows by ticket, per-row
+ *     progress counters; in the side-by-side call (ffhip_vp8_predict_loopfilter, below) it runs next to the prediction's row kernel and
+ *     follows that kernel's counters as well.
+ *   - the LEVELS form (k_vp8_loopfilter): wavefront levels x + 2y, one launch per level over the batch, one wave per macroblock; the
+ *     fallback for unaligned planes or records and the A/B form (FFHIP_VP8_LF_MODE=levels).
+ * In both the macroblock and its 4-pixel borders sit in LDS; the vertical-edge phase keeps one pixel row per lane in registers, the
+ * horizontal-edge phase one column per lane.  Also here: ffhip_vp8_filter_params, and the side-by-side call with its retry record.
  */
-#include "ffhip_internal.h"
+#include "ffhip_vp8_filters.h"
 
 #include <algorithm>
 #include <mutex>
@@ -42,15 +46,9 @@ struct Vp8LfArgs {
     int pred_split;                /* that prediction runs its chroma as rows of their own: their counters follow the luma rows' */
 };
 
-#include "ffhip_vp8_filters.h"
-
-
-#define LS 24 /* luma tile row stride (4 + 16, padded)   */
-#define CS 24 /* chroma tile row stride (4 + 8, padded to the luma stride: the row kernel walks luma and chroma columns with the same offsets) */
-
 __global__ __launch_bounds__(256) void k_vp8_loopfilter(Vp8LfArgs a)
 {
-    __shared__ uint8_t tl[4][20 * LS], tc[4][2][12 * CS];
+    __shared__ uint8_t tl[4][20 * FLS], tc[4][2][12 * FLS];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int item = blockIdx.x * 4 + w;
     if (item >= a.count) return;
@@ -72,18 +70,18 @@ __global__ __launch_bounds__(256) void k_vp8_loopfilter(Vp8LfArgs a)
     /* ---- load the macroblock with 4-pixel left/top borders (only what exists) ---- */
     for (int i = lane; i < 20 * 20; i += 64) {
         const int r = i / 20 - 4, c = i % 20 - 4;
-        if ((r >= 0 || y > 0) && (c >= 0 || x > 0)) TL[(r + 4) * LS + c + 4] = Y[(long long)r * ys + c];
+        if ((r >= 0 || y > 0) && (c >= 0 || x > 0)) TL[(r + 4) * FLS + c + 4] = Y[(long long)r * ys + c];
     }
     if (type != 1)
         for (int i = lane; i < 2 * 144; i += 64) {
             const int pl = i / 144, j = i % 144, r = j / 12 - 4, c = j % 12 - 4;
-            if ((r >= 0 || y > 0) && (c >= 0 || x > 0)) tc[w][pl][(r + 4) * CS + c + 4] = C[pl][(long long)r * us + c];
+            if ((r >= 0 || y > 0) && (c >= 0 || x > 0)) tc[w][pl][(r + 4) * FLS + c + 4] = C[pl][(long long)r * us + c];
         }
     wave_sync();
     /* ---- vertical edges: one pixel row per lane (lanes 0-15 luma, 16-23 U, 24-31 V) ---- */
     if (lane < 16) {
         int line[20];
-        uint8_t *row = TL + (lane + 4) * LS;
+        uint8_t *row = TL + (lane + 4) * FLS;
 #pragma unroll
         for (int k = 0; k < 20; k++) line[k] = row[k];
         filter_line<16>(line, type, x > 0, inner, sub, inter, hevt);
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(256) void k_vp8_loopfilter(Vp8LfArgs a)
         for (int k = 1; k < 19; k++) row[k] = (uint8_t)line[k];
     } else if (lane < 32 && type != 1) {
         int line[12];
-        uint8_t *row = tc[w][(lane >> 3) & 1] + ((lane & 7) + 4) * CS;
+        uint8_t *row = tc[w][(lane >> 3) & 1] + ((lane & 7) + 4) * FLS;
 #pragma unroll
         for (int k = 0; k < 12; k++) line[k] = row[k];
         filter_line<8>(line, type, x > 0, inner, sub, inter, hevt);
@@ -104,31 +102,31 @@ __global__ __launch_bounds__(256) void k_vp8_loopfilter(Vp8LfArgs a)
         int line[20];
         uint8_t *col = TL + lane + 4;
 #pragma unroll
-        for (int k = 0; k < 20; k++) line[k] = col[k * LS];
+        for (int k = 0; k < 20; k++) line[k] = col[k * FLS];
         filter_line<16>(line, type, y > 0, inner, sub, inter, hevt);
 #pragma unroll
-        for (int k = 1; k < 19; k++) col[k * LS] = (uint8_t)line[k];
+        for (int k = 1; k < 19; k++) col[k * FLS] = (uint8_t)line[k];
     } else if (lane < 32 && type != 1) {
         int line[12];
         uint8_t *col = tc[w][(lane >> 3) & 1] + (lane & 7) + 4;
 #pragma unroll
-        for (int k = 0; k < 12; k++) line[k] = col[k * CS];
+        for (int k = 0; k < 12; k++) line[k] = col[k * FLS];
         filter_line<8>(line, type, y > 0, inner, sub, inter, hevt);
 #pragma unroll
-        for (int k = 1; k < 11; k++) col[k * CS] = (uint8_t)line[k];
+        for (int k = 1; k < 11; k++) col[k * FLS] = (uint8_t)line[k];
     }
     wave_sync();
     /* ---- write back what this macroblock may have changed: its own pixels and the 3 pixels
      * beyond its left / top edge (never the 4x4 corner above-left, which it did not touch) ---- */
     for (int i = lane; i < 19 * 19; i += 64) {
         const int r = i / 19 - 3, c = i % 19 - 3;
-        if ((r >= 0 || c >= 0) && (r >= 0 || y > 0) && (c >= 0 || x > 0)) Y[(long long)r * ys + c] = TL[(r + 4) * LS + c + 4];
+        if ((r >= 0 || c >= 0) && (r >= 0 || y > 0) && (c >= 0 || x > 0)) Y[(long long)r * ys + c] = TL[(r + 4) * FLS + c + 4];
     }
     if (type != 1)
         for (int i = lane; i < 2 * 121; i += 64) {
             const int pl = i / 121, j = i % 121, r = j / 11 - 3, c = j % 11 - 3;
             if ((r >= 0 || c >= 0) && (r >= 0 || y > 0) && (c >= 0 || x > 0))
-                C[pl][(long long)r * us + c] = tc[w][pl][(r + 4) * CS + c + 4];
+                C[pl][(long long)r * us + c] = tc[w][pl][(r + 4) * FLS + c + 4];
         }
 }
 
@@ -141,13 +139,6 @@ __global__ __launch_bounds__(256) void k_vp8_loopfilter(Vp8LfArgs a)
  * when the in-order completion of the wave's memory operations proves those stores done. */
 #define LF_SPIN_LIMIT (1 << 21)
 
-/* per lane: bit `lane` of a 64-bit mask picks b over a -- one v_cndmask with the mask in an SGPR pair */
-__device__ __forceinline__ int lane_select(unsigned long long mask, int a, int b)
-{
-    int d;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(mask));
-    return d;
-}
 struct LfFetch {
     u32 y0, y1, cu, cv; /* luma items lane and lane + 64 (of 80: 20 rows x 4 dwords), one chroma dword of U and of V (of 24 each: 12 rows x 2) */
     u32 m0, m4;         /* mode bytes 0..3 and 16..19 of the macroblock */
@@ -160,11 +151,10 @@ struct LfFetch {
 template <int TYPE> /* the filter type of the launch (1 simple, 2 normal): a kernel each, no run-time switch in the edges */
 __global__ __launch_bounds__(64) void k_vp8_loopfilter_rows(Vp8LfArgs a)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t TL[20 * LS];
-    __shared__ __attribute__((aligned(16))) uint8_t TC[2][20 * CS]; /* 12 rows in use; 20 so that filter_phase's unused reads of a chroma column stay inside */
+    __shared__ __attribute__((aligned(16))) uint8_t TL[20 * FLS];
+    __shared__ __attribute__((aligned(16))) uint8_t TC[2][20 * FLS]; /* 12 rows in use; 20 so that filter_phase's unused reads of a chroma column stay inside */
     __shared__ uint8_t FT[24];
     __shared__ u32 DUMP[64]; /* where lanes without a role read and write */
-    static_assert(LS == CS, "filter_phase walks luma and chroma tiles with one stride");
     const int lane = threadIdx.x;
     const int n_mb = a.mbcols * a.mbrows;
     const int ys = 16 * a.mbcols, us = 8 * a.mbcols;
@@ -180,20 +170,20 @@ __global__ __launch_bounds__(64) void k_vp8_loopfilter_rows(Vp8LfArgs a)
     const int fy0 = ((lane >> 2) - 4) * ys + 4 * (lane & 3);                       /* item lane: tile row lane >> 2 (picture row - 4) */
     const int fy1 = lane < 16 ? ((lane >> 2) + 12) * ys + 4 * (lane & 3) : LF_OUT; /* item lane + 64                                  */
     const int fc = lane < 24 ? ((lane >> 1) - 4) * us + 4 * (lane & 1) : LF_OUT;   /* chroma item lane of either plane                */
-    const unsigned dy0 = tl + (unsigned)((lane >> 2) * LS + 4 + 4 * (lane & 3));
-    const unsigned dy1 = lane < 16 ? tl + (unsigned)(((lane >> 2) + 16) * LS + 4 + 4 * (lane & 3)) : dump;
-    const unsigned dcu = lane < 24 ? tc0 + (unsigned)((lane >> 1) * CS + 4 + 4 * (lane & 1)) : dump;
-    const unsigned dcv = lane < 24 ? tc1 + (unsigned)((lane >> 1) * CS + 4 + 4 * (lane & 1)) : dump;
+    const unsigned dy0 = tl + (unsigned)((lane >> 2) * FLS + 4 + 4 * (lane & 3));
+    const unsigned dy1 = lane < 16 ? tl + (unsigned)(((lane >> 2) + 16) * FLS + 4 + 4 * (lane & 3)) : dump;
+    const unsigned dcu = lane < 24 ? tc0 + (unsigned)((lane >> 1) * FLS + 4 + 4 * (lane & 1)) : dump;
+    const unsigned dcv = lane < 24 ? tc1 + (unsigned)((lane >> 1) * FLS + 4 + 4 * (lane & 1)) : dump;
     /* the tile's right end becomes the next macroblock's left border: lanes 0-19 a luma row, 32-43 / 44-55 a chroma row */
-    const unsigned keep_src = lane < 20 ? tl + (unsigned)(lane * LS + 16) : (lane >= 32 && lane < 56 && type != 1 ? (lane < 44 ? tc0 : tc1) + (unsigned)(((lane - 32) % 12) * CS + 8) : dump);
-    const unsigned keep_dst = lane < 20 ? tl + (unsigned)(lane * LS) : (lane >= 32 && lane < 56 && type != 1 ? (lane < 44 ? tc0 : tc1) + (unsigned)(((lane - 32) % 12) * CS) : dump);
+    const unsigned keep_src = lane < 20 ? tl + (unsigned)(lane * FLS + 16) : (lane >= 32 && lane < 56 && type != 1 ? (lane < 44 ? tc0 : tc1) + (unsigned)(((lane - 32) % 12) * FLS + 8) : dump);
+    const unsigned keep_dst = lane < 20 ? tl + (unsigned)(lane * FLS) : (lane >= 32 && lane < 56 && type != 1 ? (lane < 44 ? tc0 : tc1) + (unsigned)(((lane - 32) % 12) * FLS) : dump);
     /* write-back: luma items lane and lane + 64 of 100 (20 rows x 5 dwords, the first one the 4 columns left of the
      * macroblock), chroma item lane of 36 (12 rows x 3) of either plane.  An item in tile rows 0-3 exists only below the
      * first macroblock row, one in dword column 0 only right of the first macroblock: as lane masks, picked per macroblock */
     const int wr0 = lane / 5, wd0 = lane % 5, wr1 = (lane + 64) / 5, wd1 = (lane + 64) % 5, wrc = lane / 3, wdc = lane % 3;
     const int wy0 = (wr0 - 4) * ys + 4 * wd0 - 4, wy1 = lane < 36 ? (wr1 - 4) * ys + 4 * wd1 - 4 : LF_OUT, wc = lane < 36 ? (wrc - 4) * us + 4 * wdc - 4 : LF_OUT;
-    const unsigned sy0 = tl + (unsigned)(wr0 * LS + 4 * wd0), sy1 = lane < 36 ? tl + (unsigned)(wr1 * LS + 4 * wd1) : dump;
-    const unsigned scu = lane < 36 ? tc0 + (unsigned)(wrc * CS + 4 * wdc) : dump, scv = lane < 36 ? tc1 + (unsigned)(wrc * CS + 4 * wdc) : dump;
+    const unsigned sy0 = tl + (unsigned)(wr0 * FLS + 4 * wd0), sy1 = lane < 36 ? tl + (unsigned)(wr1 * FLS + 4 * wd1) : dump;
+    const unsigned scu = lane < 36 ? tc0 + (unsigned)(wrc * FLS + 4 * wdc) : dump, scv = lane < 36 ? tc1 + (unsigned)(wrc * FLS + 4 * wdc) : dump;
 
     for (;;) {
         unsigned ticket = 0;
@@ -352,9 +342,9 @@ __global__ __launch_bounds__(64) void k_vp8_loopfilter_rows(Vp8LfArgs a)
                 const bool lum = lane < 16, active = lane < 16 || (lane < 32 && type != 1);
                 uint8_t *const mine = lum ? TL : TC[(lane >> 3) & 1];
                 const int li = lum ? lane : (lane & 7);
-                filter_phase<1, TYPE>(mine + (li + 4) * LS, active, lum, x > 0, inner, sub, inter, hevt);
+                filter_phase<1, TYPE>(mine + (li + 4) * FLS, active, lum, x > 0, inner, sub, inter, hevt);
                 wave_sync();
-                filter_phase<LS, TYPE>(mine + li + 4, active, lum, y > 0, inner, sub, inter, hevt);
+                filter_phase<FLS, TYPE>(mine + li + 4, active, lum, y > 0, inner, sub, inter, hevt);
                 wave_sync();
                 wb0 = LDS32(sy0); wb1 = LDS32(sy1);
                 if (type != 1) { wbu = LDS32(scu); wbv = LDS32(scv); }
@@ -365,10 +355,10 @@ __global__ __launch_bounds__(64) void k_vp8_loopfilter_rows(Vp8LfArgs a)
                 /* ---- write back rows -4..15, columns -4..15 as dwords (the cells this macroblock did not change are
                  * rewritten with the value it read: their owners are finished) -- but nothing outside the picture ---- */
                 const int org = row_org + x * 16, corg = row_corg + x * 8;
-                __builtin_amdgcn_raw_buffer_store_b32(wb0, rY, lane_select(x > 0 ? ok0 : first0, LF_OUT, wy0) + org, 0, FFHIP_AUX_SC1);
-                __builtin_amdgcn_raw_buffer_store_b32(wb1, rY, lane_select(x > 0 ? ok1 : first1, LF_OUT, wy1) + org, 0, FFHIP_AUX_SC1);
+                __builtin_amdgcn_raw_buffer_store_b32(wb0, rY, lane_select_smask(x > 0 ? ok0 : first0, LF_OUT, wy0) + org, 0, FFHIP_AUX_SC1);
+                __builtin_amdgcn_raw_buffer_store_b32(wb1, rY, lane_select_smask(x > 0 ? ok1 : first1, LF_OUT, wy1) + org, 0, FFHIP_AUX_SC1);
                 if (type != 1) {
-                    const int oc = lane_select(x > 0 ? okc : firstc, LF_OUT, wc) + corg; /* added here, not as the scalar offset: the range check looks at this operand alone, and a lane's offset may be negative */
+                    const int oc = lane_select_smask(x > 0 ? okc : firstc, LF_OUT, wc) + corg; /* added here, not as the scalar offset: the range check looks at this operand alone, and a lane's offset may be negative */
                     __builtin_amdgcn_raw_buffer_store_b32(wbu, rU, oc, 0, FFHIP_AUX_SC1);
                     __builtin_amdgcn_raw_buffer_store_b32(wbv, rV, oc, 0, FFHIP_AUX_SC1);
                 }
@@ -378,6 +368,54 @@ __global__ __launch_bounds__(64) void k_vp8_loopfilter_rows(Vp8LfArgs a)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_store(prog_me, (unsigned)a.mbcols, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+/* row form (default): one launch, no host-side scheduling.  `a`: the common fields */
+static int lf_rows_enqueue(Vp8LfArgs a, int n_images, const Vp8RowSwitches &sw, void *stream, const Vp8SideBySide *sbs)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const size_t words = FFHIP_VP8_LF_CTRL_HDR + (((size_t)n_images * (size_t)a.mbrows) << sw.pshift);
+    uint32_t *g_work = ffhip_scratch(SCRATCH_VP8_LF, stream, words);
+    if (!g_work) return FFHIP_ENOMEM;
+    if (sbs && sbs->pred_progress) { /* next to the prediction kernel, behind its counter reset */
+        a.pred_progress = sbs->pred_progress; a.pred_pshift = sbs->pshift; a.pred_split = sbs->pred_split;
+        st = sbs->side;
+        FFHIP_CHECK(hipStreamWaitEvent(st, sbs->fork, 0), FFHIP_EIO);
+    }
+    FFHIP_CHECK(hipMemsetAsync(g_work, 0, words * sizeof(uint32_t), st), FFHIP_EIO);
+    a.ctrl = g_work; a.async_err = sw.async_err; a.n_images = n_images; a.pshift = sw.pshift; a.slack = sw.slack;
+    a.debug_giveup = FFHIP_ENV("FFHIP_DEBUG_VP8_LF_GIVEUP") ? 1 : 0;
+    /* as many waves as can be resident, at most a wavefront's width of rows per image (ffhip_vp8_predict_recon has the
+     * reasoning); next to the prediction kernel of the same call each of the two takes half of its own residency, so
+     * filter waves -- which wait for the prediction's counters -- can never keep the prediction from becoming resident */
+    const char *wv = FFHIP_ENV("FFHIP_VP8_LF_WAVES");
+    /* measured (256 x 1080p): the filter is at its best with two waves per SIMD and loses a factor of two with four (1024 / 2048 /
+     * 3584 waves: 1.95 / 1.86 / 3.4 ms -- its waves mostly wait, and waiting waves poll); next to the prediction one per SIMD does */
+    long long resident = ffhip_resident_waves(a.filter_type == 1 ? (const void *)k_vp8_loopfilter_rows<1> : (const void *)k_vp8_loopfilter_rows<2>, 64);
+    resident = std::max<long long>(1, a.pred_progress ? resident / 4 : resident / 3);
+    const long long wide = std::max<long long>(256, (long long)n_images * (a.mbcols / 8 + 1)); /* measured, 16 x 1080p: 8 / 16 / 24 / 32 rows per image 0.83 / 0.67 / 0.81 / 0.85 ms alone (encoder's stream) */
+    const long long cap = wv ? std::max(1, atoi(wv)) : std::min(resident, wide);
+    const dim3 grid((unsigned)std::min<long long>((long long)n_images * a.mbrows, cap));
+    if (a.filter_type == 1) hipLaunchKernelGGL(k_vp8_loopfilter_rows<1>, grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_vp8_loopfilter_rows<2>, grid, dim3(64), 0, st, a);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
+}
+
+/* levels form (fallback, A/B): levels x + 2y, the same for every image, no mode-dependent edges here */
+static int lf_levels_enqueue(Vp8LfArgs a, int n_images, void *stream)
+{
+    std::vector<std::vector<uint32_t>> lists((size_t)(a.mbcols + 2 * (a.mbrows - 1)));
+    for (int img = 0; img < n_images; img++)
+        for (int y = 0; y < a.mbrows; y++)
+            for (int x = 0; x < a.mbcols; x++) {
+                lists[(size_t)(x + 2 * y)].push_back((uint32_t)img);
+                lists[(size_t)(x + 2 * y)].push_back((uint32_t)(y * a.mbcols + x));
+            }
+    return vp8_levels_upload_and_launch(SCRATCH_VP8_LF, stream, lists, [&](const uint32_t *work, int count) {
+        a.work = work; a.count = count;
+        hipLaunchKernelGGL(k_vp8_loopfilter, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    });
 }
 
 /* sbs: next to the prediction of the same call (ffhip_vp8_predict_loopfilter), on its side stream */
@@ -394,80 +432,15 @@ int vp8_loopfilter_impl(int mbcols, int mbrows, int n_images, int filter_type, c
     const long long n_mb = (long long)mbcols * mbrows;
     if (n_mb * n_images > 0x3fffffffLL) return FFHIP_EINVAL;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
-    hipStream_t st = (hipStream_t)stream;
-    /* row form (default): one launch, no host-side scheduling */
-    const char *mode_env = FFHIP_ENV("FFHIP_VP8_LF_MODE");
-    int *async_err = (mode_env && !strcmp(mode_env, "levels")) ? nullptr : ffhip_async_err_word();
-    if (async_err && sbs && sbs->err_word) async_err = sbs->err_word; /* the side-by-side call's own word */
-    if (async_err && !((uintptr_t)d_modes & 3) && !(((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v | (uintptr_t)plane_stride_y | (uintptr_t)plane_stride_uv) & 3) &&
-        n_mb < (1LL << 23)) {
-        const int pshift = []{ const char *e = FFHIP_ENV("FFHIP_VP8_PROGRESS_SHIFT"); return e ? std::min(5, std::max(0, atoi(e))) : 5; }();
-        const size_t words = FFHIP_VP8_LF_CTRL_HDR + (((size_t)n_images * (size_t)mbrows) << pshift);
-        uint32_t *g_work = ffhip_scratch(SCRATCH_VP8_LF, stream, words);
-        if (!g_work) return FFHIP_ENOMEM;
-        const uint32_t *pred_progress = nullptr;
-        if (sbs && sbs->pred_progress) { /* next to the prediction kernel, behind its counter reset */
-            pred_progress = sbs->pred_progress;
-            st = sbs->side;
-            FFHIP_CHECK(hipStreamWaitEvent(st, sbs->fork, 0), FFHIP_EIO);
-        }
-        FFHIP_CHECK(hipMemsetAsync(g_work, 0, words * sizeof(uint32_t), st), FFHIP_EIO);
-        Vp8LfArgs a = {};
-        a.pred_progress = pred_progress; a.pshift = pshift; a.pred_pshift = pred_progress ? sbs->pshift : 0;
-        a.pred_split = pred_progress ? sbs->pred_split : 0;
-        a.modes = d_modes; a.filters = d_filters; a.y = d_y; a.u = d_u; a.v = d_v;
-        a.plane_y = plane_stride_y; a.plane_uv = plane_stride_uv;
-        a.mbcols = mbcols; a.mbrows = mbrows; a.filter_type = filter_type;
-        a.ctrl = g_work; a.async_err = async_err; a.n_images = n_images;
-        { const char *sl = FFHIP_ENV("FFHIP_VP8_SLACK"); a.slack = sl ? std::max(0, atoi(sl)) : 0; }
-        a.debug_giveup = FFHIP_ENV("FFHIP_DEBUG_VP8_LF_GIVEUP") ? 1 : 0;
-        /* as many waves as can be resident, at most a wavefront's width of rows per image (ffhip_vp8_predict_recon has the
-         * reasoning); next to the prediction kernel of the same call each of the two takes half of its own residency, so
-         * filter waves -- which wait for the prediction's counters -- can never keep the prediction from becoming resident */
-        const char *wv = FFHIP_ENV("FFHIP_VP8_LF_WAVES");
-        /* measured (256 x 1080p): the filter is at its best with two waves per SIMD and loses a factor of two with four (1024 / 2048 /
-         * 3584 waves: 1.95 / 1.86 / 3.4 ms -- its waves mostly wait, and waiting waves poll); next to the prediction one per SIMD does */
-        long long resident = ffhip_resident_waves(filter_type == 1 ? (const void *)k_vp8_loopfilter_rows<1> : (const void *)k_vp8_loopfilter_rows<2>, 64);
-        resident = std::max<long long>(1, pred_progress ? resident / 4 : resident / 3);
-        const long long wide = std::max<long long>(256, (long long)n_images * (mbcols / 8 + 1)); /* measured, 16 x 1080p: 8 / 16 / 24 / 32 rows per image 0.83 / 0.67 / 0.81 / 0.85 ms alone (encoder's stream) */
-        const long long cap = wv ? std::max(1, atoi(wv)) : std::min(resident, wide);
-        const dim3 grid((unsigned)std::min<long long>((long long)n_images * mbrows, cap));
-        if (filter_type == 1) hipLaunchKernelGGL(k_vp8_loopfilter_rows<1>, grid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL(k_vp8_loopfilter_rows<2>, grid, dim3(64), 0, st, a);
-        FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-        return FFHIP_OK;
-    }
-
-    /* levels x + 2y: the same for every image, no mode-dependent edges here */
-    const int n_levels = mbcols + 2 * (mbrows - 1);
-    std::vector<std::vector<uint32_t>> lists((size_t)n_levels);
-    for (int img = 0; img < n_images; img++)
-        for (int y = 0; y < mbrows; y++)
-            for (int x = 0; x < mbcols; x++) {
-                lists[(size_t)(x + 2 * y)].push_back((uint32_t)img);
-                lists[(size_t)(x + 2 * y)].push_back((uint32_t)(y * mbcols + x));
-            }
-    const size_t total = (size_t)(2 * n_mb * n_images);
-    uint32_t *g_work = ffhip_scratch(SCRATCH_VP8_LF, stream, total);
-    if (!g_work) return FFHIP_ENOMEM;
-    std::vector<uint32_t> flat;
-    flat.reserve(total);
-    for (auto &l : lists) flat.insert(flat.end(), l.begin(), l.end());
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-    FFHIP_CHECK(hipMemcpy(g_work, flat.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice), FFHIP_EIO);
-    Vp8LfArgs a = {};
+    Vp8LfArgs a = {}; /* the fields both forms read */
     a.modes = d_modes; a.filters = d_filters; a.y = d_y; a.u = d_u; a.v = d_v;
     a.plane_y = plane_stride_y; a.plane_uv = plane_stride_uv;
     a.mbcols = mbcols; a.mbrows = mbrows; a.filter_type = filter_type;
-    size_t off = 0;
-    for (auto &l : lists) {
-        a.work = g_work + off;
-        a.count = (int)(l.size() / 2);
-        if (a.count) hipLaunchKernelGGL(k_vp8_loopfilter, dim3((unsigned)((a.count + 3) / 4)), dim3(256), 0, st, a);
-        off += l.size();
-    }
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    return FFHIP_OK;
+    const Vp8RowSwitches sw = vp8_row_switches(FFHIP_ENV("FFHIP_VP8_LF_MODE"), sbs);
+    if (sw.async_err && !((uintptr_t)d_modes & 3) && !(((uintptr_t)d_y | (uintptr_t)d_u | (uintptr_t)d_v | (uintptr_t)plane_stride_y | (uintptr_t)plane_stride_uv) & 3) &&
+        n_mb < (1LL << 23))
+        return lf_rows_enqueue(a, n_images, sw, stream, sbs);
+    return lf_levels_enqueue(a, n_images, stream);
 }
 
 extern "C" int ffhip_vp8_loopfilter(int mbcols, int mbrows, int n_images, int filter_type, const uint8_t *d_modes,

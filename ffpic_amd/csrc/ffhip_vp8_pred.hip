@@ -8,14 +8,17 @@
  * rules (129/127 defaults, 127 top-right inside a macroblock, 16x16 V/H predictors that
  * copy raw memory -- predict.c:338-353 -- for which bytes before the plane read as 0).
  *
- * This stage is dependency-bound, not bandwidth-bound: a macroblock needs its left, above,
- * above-left and above-right neighbours reconstructed.  The host assigns every macroblock a
- * wavefront level (x + 2y, plus one extra edge for the reference's wrapped H_PRED read at
- * x = 0) and the library launches one kernel per level over all images of the batch; a
- * wave owns one macroblock, keeps it in LDS while the 16 dependent 4x4 steps of B_PRED run,
- * and writes it out once.  Parallelism comes from the batch and the wavefront width.
+ * This stage is dependency-bound, not bandwidth-bound: a macroblock needs its left, above, above-left and above-right neighbours
+ * reconstructed.  The file holds two forms of it:
+ *   - the ROW form, the default (k_vp8_predict_rows): one launch per batch, a wave owns a macroblock row of one image, rows are handed
+ *     out by ticket and follow the row above through per-row progress counters; no host-side scheduling.  It is also the prediction half
+ *     of the side-by-side call (ffhip_vp8_lf.hip) and the small-batch form of ffhip_vp8_decode_frames (ffhip_vp8_frame.hip).
+ *   - the LEVELS form (k_vp8_predict): the host assigns every macroblock a wavefront level (x + 2y, plus one extra edge for the
+ *     reference's wrapped H_PRED read at x = 0) and there is one launch per level over all images of the batch, a wave per macroblock.
+ *     The fallback for what the row form does not take (unaligned mode records, a plane of 2^23 macroblocks) and the A/B form
+ *     (FFHIP_VP8_PRED_MODE=levels).  Also here: the device check of mode records and what both stages' host entries share.
  */
-#include "ffhip_internal.h"
+#include "ffhip_vp8_device.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -40,30 +43,9 @@ struct Vp8PredArgs {
     unsigned long long *trace; /* diagnostics (ffhip_debug_vp8_trace): per (image, row) EIGHT words: the 100 MHz clock at ticket, first macroblock, middle, last store; then the row's time (same clock) summed per phase: fetch wait + consume, poll + next fetch's issue, luma, chroma */
 };
 
-/* generated by tests/tools/gen_vp8_pred_table.py: taps a | b<<4 | c<<8 per (mode-2, pixel);
- * pixel = (e[a] + 2 e[b] + e[c] + 2) >> 2 on e = L K J I X A B C D E F G H */
-__device__ static const unsigned short kVp8Taps[8][16] = {
-    {0x654, 0x765, 0x876, 0x987, 0x654, 0x765, 0x876, 0x987, 0x654, 0x765, 0x876, 0x987, 0x654, 0x765, 0x876, 0x987},
-    {0x432, 0x432, 0x432, 0x432, 0x321, 0x321, 0x321, 0x321, 0x210, 0x210, 0x210, 0x210, 0x100, 0x100, 0x100, 0x100},
-    {0x543, 0x654, 0x765, 0x876, 0x432, 0x543, 0x654, 0x765, 0x321, 0x432, 0x543, 0x654, 0x210, 0x321, 0x432, 0x543},
-    {0x545, 0x656, 0x767, 0x878, 0x543, 0x654, 0x765, 0x876, 0x432, 0x545, 0x656, 0x767, 0x321, 0x543, 0x654, 0x765},
-    {0x765, 0x876, 0x987, 0xa98, 0x876, 0x987, 0xa98, 0xba9, 0x987, 0xa98, 0xba9, 0xcba, 0xa98, 0xba9, 0xcba, 0xccb},
-    {0x656, 0x767, 0x878, 0x989, 0x765, 0x876, 0x987, 0xa98, 0x767, 0x878, 0x989, 0xba9, 0x876, 0x987, 0xa98, 0xcba},
-    {0x434, 0x543, 0x654, 0x765, 0x323, 0x432, 0x434, 0x543, 0x212, 0x321, 0x323, 0x432, 0x101, 0x210, 0x212, 0x321},
-    {0x323, 0x321, 0x212, 0x210, 0x212, 0x210, 0x101, 0x100, 0x101, 0x100, 0x000, 0x000, 0x000, 0x000, 0x000, 0x000},
-};
-
-__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 __device__ __forceinline__ int px_or0(const uint8_t *plane, long long off) { return off < 0 ? 0 : plane[off]; }
 
 #define TS 24 /* tile row stride: 1 left + 16 + 4 top-right, padded */
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 /* DC / TM / VE / HE value of an NxN block pixel from edge arrays with the reference's rules */
 template <int N>
@@ -264,10 +246,6 @@ __global__ __launch_bounds__(256) void k_vp8_predict(Vp8PredArgs a)
  * 492-517) unless the 16x16 mode is V_PRED/H_PRED, which copy raw memory (predict.c:338-353);
  * after that every predictor is a handful of plain tile reads. */
 #define VP8_SPIN_LIMIT (1 << 21)
-#define RS 28  /* luma tile row stride: [3] left column, [4..19] pixels, [20..23] above-right; row 0 = the row above */
-#define CS 16  /* chroma tile row stride: [3] left column, [4..11] pixels; row 0 = the row above */
-
-typedef u32 u32x3 __attribute__((ext_vector_type(3)));
 struct Vp8Fetch {
     u32 res[3]; /* the part's share of the residual: 12 B per lane (whole macroblock), 8 B (luma) or 4 B (chroma) */
     u32 mo;    /* lanes 0..4: one dword of the 20 mode bytes */
@@ -275,31 +253,6 @@ struct Vp8Fetch {
                     (21..29), V top (32..40), raw luma left at x = 0 (48..63) -- one load per plane, a lane without a role in
                     that plane reads 0; OR-ed when the fetch is CONSUMED (combined at the loads, the OR would wait for them there) */
 };
-
-__device__ __forceinline__ int sum4(u32 v) { return (int)__builtin_amdgcn_sad_u8(v, 0u, 0u); }
-
-/* b where the lane's bit of the 64-bit mask is set, else a: the mask is wave-uniform (which lanes have which role is known
- * at compile time, which rule applies is a property of the macroblock), so the whole edge-rule logic is scalar arithmetic on
- * lane masks and one v_cndmask per rule -- written per lane it was a compare, an exec-mask update and a skipped branch per rule */
-__device__ __forceinline__ int lane_select(unsigned long long mask, int a, int b)
-{
-    int r;
-    /* the mask is wave-uniform but the compiler may have computed it on the vector unit: an "s" operand does not move it back by itself */
-    const unsigned long long m = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(mask >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)mask);
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(m));
-    return r;
-}
-
-#define BT_C0 480  /* U tile inside the border/pixel tile array */
-#define BT_C1 624  /* V tile */
-#define BT_DUMP 768 /* where lanes without a role write */
-#define M_LUMATOP 0x00000000001fffffull   /* lanes 0..20  */
-#define M_TOPRIGHT 0x00000000001e0000ull  /* lanes 17..20: columns 16..19 of the row above */
-#define M_UTOP 0x000000003fe00000ull      /* lanes 21..29 */
-#define M_VTOP 0x000001ff00000000ull      /* lanes 32..40 */
-#define M_LEFT 0xffff000000000000ull      /* lanes 48..63 */
-#define M_FIRST_LUMA 0x0000000000000001ull
-#define M_FIRST_CHROMA 0x0000000100200000ull /* lanes 21 and 32: column -1 of the chroma rows above */
 
 /* what a lane does, by its number: constants of the launch */
 struct Vp8Lane {
@@ -396,7 +349,7 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
             /* the raw left column (lanes 48-63) is read from memory at x = 0 only -- everywhere else it is the previous macroblock's
              * right column, carried over in LDS: pointed outside the plane the sixteen lanes cost no memory request (they were sixteen
              * device-coherent 64-byte requests per macroblock, four fifths of the kernel's uncached reads) */
-            f.a = ffhip_load_u8_sc1(rY, lane_select(x1 != 0 ? M_LEFT : 0ull, L.offY + org, (int)0x80000000u));
+            f.a = ffhip_load_u8_sc1(rY, lane_select_vmask(x1 != 0 ? M_LEFT : 0ull, L.offY + org, (int)0x80000000u));
         }
         if (PART != 1) {
             f.b = ffhip_load_u8_sc1(rU, L.offU + corg);
@@ -467,9 +420,9 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
                                                 ((!raw && x == a.mbcols - 1) ? M_TOPRIGHT : none);
                 const unsigned long long m129 = (x == 0 ? (M_FIRST_CHROMA | (raw ? none : (M_FIRST_LUMA | M_LEFT))) : none) & ~m127;
                 int v = f.a | f.b | f.c;
-                v = lane_select(x != 0 ? M_LEFT : none, v, carry);
-                v = lane_select(m127, v, 127);
-                v = lane_select(m129, v, 129);
+                v = lane_select_vmask(x != 0 ? M_LEFT : none, v, carry);
+                v = lane_select_vmask(m127, v, 127);
+                v = lane_select_vmask(m129, v, 129);
                 BT[L.dst1] = (uint8_t)v;
                 BT[L.dst2] = (uint8_t)(x == 0 ? 129 : carry); /* chroma left columns */
             } else if (PART == 1) {
@@ -477,17 +430,17 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
                 const unsigned long long m127 = (y == 0 && !raw ? M_LUMATOP : none) | ((!raw && x == a.mbcols - 1) ? M_TOPRIGHT : none);
                 const unsigned long long m129 = (x == 0 && !raw ? (M_FIRST_LUMA | M_LEFT) : none) & ~m127;
                 int v = f.a;
-                v = lane_select(x != 0 ? M_LEFT : none, v, carry);
-                v = lane_select(m127, v, 127);
-                v = lane_select(m129, v, 129);
+                v = lane_select_vmask(x != 0 ? M_LEFT : none, v, carry);
+                v = lane_select_vmask(m127, v, 127);
+                v = lane_select_vmask(m129, v, 129);
                 BT[L.dst1] = (uint8_t)v; /* (lanes with a chroma role write into the chroma tiles nobody reads here) */
             } else {
                 *(u32 *)((char *)R + 512 + lane * 4) = f.res[0];
                 const unsigned long long m127 = y == 0 ? (M_UTOP | M_VTOP) : none;
                 const unsigned long long m129 = (x == 0 ? M_FIRST_CHROMA : none) & ~m127;
                 int v = f.b | f.c;
-                v = lane_select(m127, v, 127);
-                v = lane_select(m129, v, 129);
+                v = lane_select_vmask(m127, v, 127);
+                v = lane_select_vmask(m129, v, 129);
                 BT[L.dst1] = (uint8_t)v;
                 BT[L.dst2] = (uint8_t)(x == 0 ? 129 : carry); /* chroma left columns */
             }
@@ -532,7 +485,7 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
                     const int modeA = (int)((mo[(2 + nA) >> 2] >> (8 * ((2 + nA) & 3))) & 0xff), modeB = (int)((mo[(2 + nB) >> 2] >> (8 * ((2 + nB) & 3))) & 0xff);
                     const int mode = second ? modeB : modeA;
                     const u32 to = TT[(mode < 10 ? mode : 2) * 16 + l16]; /* a mode past the table: the first directional row, as before */
-                    const int oA = ((nA >> 2) * 4 + 1) * RS + 4 + (nA & 3) * 4, oB = ((nB >> 2) * 4 + 1) * RS + 4 + (nB & 3) * 4;
+                    const int oA = ((nA >> 2) * 4 + 1) * PRS + 4 + (nA & 3) * 4, oB = ((nB >> 2) * 4 + 1) * PRS + 4 + (nB & 3) * 4;
                     const int sb = second ? oB : oA; /* sub-block origin in the tile */
                     ta[t] = sb - 64 + (int)(to & 0xff); tb[t] = sb - 64 + (int)((to >> 8) & 0xff); tc[t] = sb - 64 + (int)(to >> 16);
                     rv[t] = (int)R[16 * (second ? nB : nA) + l16];
@@ -542,26 +495,26 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
                 for (int t = 0; t < 10; t++) {
                     uint8_t *S = T + so[t];
                     const int va = T[ta[t]], vb = T[tb[t]], vc = T[tc[t]];
-                    const u32 top4 = *(const u32 *)(S - RS);
-                    const int l0 = S[-1], l1 = S[RS - 1], l2 = S[2 * RS - 1], l3 = S[3 * RS - 1];
+                    const u32 top4 = *(const u32 *)(S - PRS);
+                    const int l0 = S[-1], l1 = S[PRS - 1], l2 = S[2 * PRS - 1], l3 = S[3 * PRS - 1];
                     const int dir = (va + 2 * vb + vc + 2) >> 2;
                     const int tm = clamp255(va + vb - vc);
                     const int dc = (4 + sum4(top4) + l0 + l1 + l2 + l3) >> 3;
                     int p = md[t] == 1 ? tm : dir;
                     p = md[t] == 0 ? dc : p;
-                    S[r * RS + c] = (uint8_t)clamp255(p + rv[t]);
+                    S[r * PRS + c] = (uint8_t)clamp255(p + rv[t]);
                     wave_sync();
                 }
-                lumaout = *(const u32 *)(T + (r16 + 1) * RS + 4 + c16);
+                lumaout = *(const u32 *)(T + (r16 + 1) * PRS + 4 + c16);
             } else {
                 const u32 top4 = *(const u32 *)(T + 4 + c16);
-                const int lf = T[(r16 + 1) * RS + 3], cor = T[3];
+                const int lf = T[(r16 + 1) * PRS + 3], cor = T[3];
                 int dcv = 0;
                 if (ymode == 0) { /* DC over the edges that exist (predict.c:34-76) */
                     int dc = 0;
                     if (x > 0) {
 #pragma unroll
-                        for (int k = 0; k < 16; k++) dc += T[(k + 1) * RS + 3];
+                        for (int k = 0; k < 16; k++) dc += T[(k + 1) * PRS + 3];
                     }
                     if (y > 0) dc += sum4(*(const u32 *)(T + 4)) + sum4(*(const u32 *)(T + 8)) + sum4(*(const u32 *)(T + 12)) + sum4(*(const u32 *)(T + 16));
                     if (x == 0 && y == 0) dc = 0x80;
@@ -581,13 +534,13 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
                 for (int k = 0; k < 4; k++) {
                     const int tpx = (int)((top4 >> (8 * k)) & 0xff);
                     int p = clamp255(tpx + lc);                  /* TM_PRED */
-                    p = lane_select(is_h, p, lf);                /* raw dst[-1]   (predict.c:346-353) */
-                    p = lane_select(is_v, p, tpx);               /* raw row above (predict.c:338-344) */
-                    p = lane_select(is_dc, p, dcv);
+                    p = lane_select_vmask(is_h, p, lf);                /* raw dst[-1]   (predict.c:346-353) */
+                    p = lane_select_vmask(is_v, p, tpx);               /* raw row above (predict.c:338-344) */
+                    p = lane_select_vmask(is_dc, p, dcv);
                     o |= (u32)clamp255(p + rs[k]) << (8 * k);
                 }
                 wave_sync(); /* every lane has read its borders */
-                *(u32 *)(T + (r16 + 1) * RS + 4 + c16) = o;
+                *(u32 *)(T + (r16 + 1) * PRS + 4 + c16) = o;
                 lumaout = o;
             }
             if (tr) { const unsigned long long tn = wall_clock64(); ph2 += tn - tp; tp = tn; }
@@ -598,13 +551,13 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
 #pragma unroll
             for (int pl = 0; pl < 2; pl++) {
                 const uint8_t *Cp = pl ? C1 : C0;
-                const int lf = Cp[(r + 1) * CS + 3], tpx = Cp[4 + c], cor = Cp[3];
+                const int lf = Cp[(r + 1) * PCS + 3], tpx = Cp[4 + c], cor = Cp[3];
                 int p;
                 if (uvmode == 0) {
                     int dc = 0;
                     if (x > 0) {
 #pragma unroll
-                        for (int k = 0; k < 8; k++) dc += Cp[(k + 1) * CS + 3];
+                        for (int k = 0; k < 8; k++) dc += Cp[(k + 1) * PCS + 3];
                     }
                     if (y > 0) dc += sum4(*(const u32 *)(Cp + 4)) + sum4(*(const u32 *)(Cp + 8));
                     if (x == 0 && y == 0) dc = 0x80;
@@ -612,15 +565,15 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
                     else dc = (dc + 8) >> 4;
                     p = dc & 0xff;
                 } else {
-                    p = lane_select(__builtin_amdgcn_ballot_w64(uvmode == 1), lf, clamp255(lf + tpx - cor));
-                    p = lane_select(__builtin_amdgcn_ballot_w64(uvmode == 2), p, tpx);
+                    p = lane_select_vmask(__builtin_amdgcn_ballot_w64(uvmode == 1), lf, clamp255(lf + tpx - cor));
+                    p = lane_select_vmask(__builtin_amdgcn_ballot_w64(uvmode == 2), p, tpx);
                 }
                 const int ri = 256 + 64 * pl + 16 * (2 * (r >> 2) + (c >> 2)) + 4 * (r & 3) + (c & 3);
                 outc[pl] = clamp255(p + R[ri]);
             }
             wave_sync(); /* all border reads done before the tiles change */
-            C0[(r + 1) * CS + 4 + c] = (uint8_t)outc[0];
-            C1[(r + 1) * CS + 4 + c] = (uint8_t)outc[1];
+            C0[(r + 1) * PCS + 4 + c] = (uint8_t)outc[0];
+            C1[(r + 1) * PCS + 4 + c] = (uint8_t)outc[1];
         }
         wave_sync();
         if (tr) { const unsigned long long tn = wall_clock64(); ph3 += tn - tp; tp = tn; }
@@ -644,7 +597,7 @@ __device__ __forceinline__ bool vp8_row(const Vp8PredArgs &a, const Vp8Lane &L, 
 template <bool TRACE>
 __global__ __launch_bounds__(64) void k_vp8_predict_rows(Vp8PredArgs a)
 {
-    /* one array for the luma tile T (17 rows of RS), the chroma tiles (9 rows of CS each) and a dump cell, so that a lane's
+    /* one array for the luma tile T (17 rows of PRS), the chroma tiles (9 rows of PCS each) and a dump cell, so that a lane's
      * border byte goes out with ONE store whatever its role */
     __shared__ __attribute__((aligned(16))) uint8_t BT[BT_DUMP + 16];
     __shared__ __attribute__((aligned(16))) short R[384];
@@ -660,7 +613,7 @@ __global__ __launch_bounds__(64) void k_vp8_predict_rows(Vp8PredArgs a)
      * edge e[k] of predict.c's L K J I X A..H sits at (3-k) rows down / one left, the corner, or k-5 along the row above */
     u32 tapoff[8];
     {
-        auto off = [](int k) { return k < 4 ? (3 - k) * RS - 1 : (k == 4 ? -RS - 1 : -RS + (k - 5)); };
+        auto off = [](int k) { return k < 4 ? (3 - k) * PRS - 1 : (k == 4 ? -PRS - 1 : -PRS + (k - 5)); };
 #pragma unroll
         for (int m = 0; m < 8; m++) {
             const unsigned t = kVp8Taps[m][lane & 15];
@@ -668,7 +621,7 @@ __global__ __launch_bounds__(64) void k_vp8_predict_rows(Vp8PredArgs a)
         }
     }
     /* above-right of the sub-blocks in column 3 below the first row: always 127 (predict.c:509-517) */
-    if (lane < 12) T[(4 + 4 * (lane >> 2)) * RS + 20 + (lane & 3)] = 127;
+    if (lane < 12) T[(4 + 4 * (lane >> 2)) * PRS + 20 + (lane & 3)] = 127;
     /* the tap words again as a table in LDS, [directional mode][pixel]: a B_PRED macroblock looks up the words of its
      * sixteen sub-blocks at once, in front of the sixteen dependent steps -- picking them inside each step was seven
      * compares and seven selects on the chain (a lone wave pays ~8 cycles an instruction, profiles/r2_lone_wave.txt) */
@@ -676,7 +629,7 @@ __global__ __launch_bounds__(64) void k_vp8_predict_rows(Vp8PredArgs a)
 #pragma unroll
         for (int m = 0; m < 8; m++) TT[(m + 2) * 16 + lane] = tapoff[m];
         const int r = lane >> 2, c = lane & 3;
-        TT[16 + lane] = (u32)(r * RS - 1 + 64) | ((u32)(-RS + c + 64) << 8) | ((u32)(-RS - 1 + 64) << 16);
+        TT[16 + lane] = (u32)(r * PRS - 1 + 64) | ((u32)(-PRS + c + 64) << 8) | ((u32)(-PRS - 1 + 64) << 16);
         TT[lane] = 64u | (64u << 8) | (64u << 16);
     }
     wave_sync();
@@ -690,15 +643,12 @@ __global__ __launch_bounds__(64) void k_vp8_predict_rows(Vp8PredArgs a)
     L.offU = lane >= 21 && lane <= 29 ? lane - 22 - us : OUT;
     L.offV = lane >= 32 && lane <= 40 ? lane - 33 - us : OUT;
     L.dst1 = lane <= 20 ? 3 + lane : (lane <= 29 && lane >= 21 ? BT_C0 + 3 + (lane - 21) : (lane >= 32 && lane <= 40 ? BT_C1 + 3 + (lane - 32) :
-             (lane >= 48 ? (lane - 47) * RS + 3 : BT_DUMP)));
+             (lane >= 48 ? (lane - 47) * PRS + 3 : BT_DUMP)));
     /* chroma left columns: lanes 0..15 = plane (lane >> 3), row (lane & 7) */
-    L.dst2 = lane < 16 ? (lane < 8 ? BT_C0 : BT_C1) + ((lane & 7) + 1) * CS + 3 : BT_DUMP;
-    L.carry_src = lane >= 48 ? (lane - 47) * RS + 4 + 15 : (lane < 16 ? (lane < 8 ? BT_C0 : BT_C1) + ((lane & 7) + 1) * CS + 4 + 7 : BT_DUMP);
+    L.dst2 = lane < 16 ? (lane < 8 ? BT_C0 : BT_C1) + ((lane & 7) + 1) * PCS + 3 : BT_DUMP;
+    L.carry_src = lane >= 48 ? (lane - 47) * PRS + 4 + 15 : (lane < 16 ? (lane < 8 ? BT_C0 : BT_C1) + ((lane & 7) + 1) * PCS + 4 + 7 : BT_DUMP);
     L.lumaY_lane = (lane >> 2) * ys + (lane & 3) * 4; L.chroma_lane = (lane >> 3) * us + (lane & 7);
 
-    /* Tickets per part: (row index, image), row index major, so whatever a row waits for -- the same part of the row above -- has a
-     * smaller ticket of the same counter and is running or done.  One wave in four starts on the chroma rows (they are a third of
-     * the luma rows' work); a wave that finds its part's tickets gone takes the other part's, so any grid size finishes both. */
     /* Tickets per part: (row index, image), row index major, so whatever a row waits for -- the same part of the row above -- has a
      * smaller ticket of the same counter and is running or done.  Split: two waves in five start on the chroma rows (a third of the luma rows' work, but a chroma
      * row follows the row above at one macroblock, so as many of them are in flight: with one wave in four the chroma finished 0.25 ms
@@ -731,42 +681,36 @@ __global__ __launch_bounds__(64) void k_vp8_predict_rows(Vp8PredArgs a)
 
 /* ------------------------------------------------------------------------ host */
 
-/* Mode bytes out of range (not a VP8 mode: predict.c:426-645 has no such case) for batches too large for a host pass: one thread per
- * macroblock record in FRONT of the row kernel, whose ticket counter a bad record pushes beyond every row.  Checked inside the row kernel's
- * macroblock loop -- one branch that is never taken -- it cost 9 % on 16 frames of random modes. */
+/* Mode records that are not VP8's (vp8_mode_record_valid) for batches too large for a host pass: one thread per record in FRONT of the
+ * kernel that reads them.  Checked inside the row kernel's macroblock loop -- one branch that is never taken -- it cost 9 % on 16 frames
+ * of random modes.  Both kernels write vp8_mode_record_valid's rule out: called as the predicate it compiled to more scalar (32 -> 37) or
+ * vector registers (8 -> 17) in every form tried; tests/test_vp8_items_gpu.py holds the kernels to the predicate record by record. */
+/* Refuse the call through the stream: a ticket counter beyond every row (words 0 and idx_c) sends each wave of the kernel behind home at
+ * once, at no cost to a valid call (a look at the abort word per row cost a 1024-frame call 4 %); the frame kernels read word idx_abort. */
+__device__ __forceinline__ void vp8_refuse_call(uint32_t *ctrl, int *async_err, const uint32_t idx_c, const uint32_t idx_abort)
+{
+    __hip_atomic_store(&ctrl[0], 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&ctrl[idx_c], 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&ctrl[idx_abort], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(async_err, FFHIP_ASYNC_BAD_INPUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+/* the records of one array (20-byte records, 4-byte aligned) */
 __global__ __launch_bounds__(256) void k_vp8_check_modes(const uint8_t *modes, long long n_records, uint32_t *ctrl, int *async_err, uint32_t idx_c, uint32_t idx_abort)
 {
     bool bad = false;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_records; i += (long long)gridDim.x * 256) {
-        const uint32_t *rec = (const uint32_t *)(modes + i * 20); /* 20-byte records, 4-byte aligned */
+        const uint32_t *rec = (const uint32_t *)(modes + i * 20);
         const uint32_t m = rec[0];
         bad |= (m & 0xffu) > 4u || ((m >> 8) & 0xffu) > 3u;
-        if ((m & 0xffu) == 4u) { /* B_PRED: bytes 2..17 index a table of ten predictors (predict.c: PredLuma4[imodes[n]]) */
-            /* a byte above 9 has bit 7, or bits 4-6, set, or is 10..15: (b + 6) carries into bit 4 exactly for 10..15 */
+        if ((m & 0xffu) == 4u) {
             auto over9 = [](uint32_t w) { return ((w | (((w & 0x0f0f0f0fu) + 0x06060606u))) & 0xf0f0f0f0u) != 0u; };
             bad |= over9(m >> 16) || over9(rec[1]) || over9(rec[2]) || over9(rec[3]) || over9(rec[4] & 0xffffu);
         }
     }
-    if (__builtin_amdgcn_ballot_w64(bad) && (threadIdx.x & 63) == 0) {
-        /* the row kernel's waves take their first ticket behind this kernel: a ticket counter beyond every row sends each of them
-         * home at once, at no cost to a valid call (a look at ctrl[1] per row cost a 1024-frame call 4 %) */
-        __hip_atomic_store(&ctrl[0], 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ctrl[idx_c], 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ctrl[idx_abort], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(async_err, FFHIP_ASYNC_BAD_INPUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (__builtin_amdgcn_ballot_w64(bad) && (threadIdx.x & 63) == 0) vp8_refuse_call(ctrl, async_err, idx_c, idx_abort);
 }
-
-/* for the frame kernel of ffhip_vp8_frame.hip: the same two checks */
-extern "C" int ffhip_vp8_check_modes_enqueue(const uint8_t *d_modes, long long n_records, uint32_t *ctrl, int *async_err, void *stream)
-{
-    hipLaunchKernelGGL(k_vp8_check_modes, dim3((unsigned)std::min<long long>((n_records + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, d_modes,
-                       n_records, ctrl, async_err, 2u, 1u); /* the frame kernel's four-word header: nobody polls it */
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    return FFHIP_OK;
-}
-/* the same checks over the records of ffhip_vp8_decode_items' items without a host copy, one launch for all of them: a record's item is
- * found by a search over the items' prefix (the sentinel behind the last one holds the total) */
+/* the records of ffhip_vp8_decode_items' items without a host copy, one launch for all of them: a record's item is found by a search over
+ * the items' prefix (the sentinel behind the last one holds the total); the frame kernels' four-word header */
 __global__ __launch_bounds__(256) void k_vp8_check_modes_items(const Vp8CheckItem *items, int n, long long n_records, uint32_t *ctrl, int *async_err)
 {
     bool bad = false;
@@ -785,35 +729,152 @@ __global__ __launch_bounds__(256) void k_vp8_check_modes_items(const Vp8CheckIte
             bad |= over9(m >> 16) || over9(rec[1]) || over9(rec[2]) || over9(rec[3]) || over9(rec[4] & 0xffffu);
         }
     }
-    if (__builtin_amdgcn_ballot_w64(bad) && (threadIdx.x & 63) == 0) { /* the frame kernels' four-word header, as ffhip_vp8_check_modes_enqueue */
-        __hip_atomic_store(&ctrl[0], 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ctrl[2], 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(async_err, FFHIP_ASYNC_BAD_INPUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (__builtin_amdgcn_ballot_w64(bad) && (threadIdx.x & 63) == 0) vp8_refuse_call(ctrl, async_err, 2u, 1u);
+}
+static unsigned check_modes_grid(long long n_records) { return (unsigned)std::min<long long>((n_records + 255) / 256, 4096); }
+/* for the frame kernel of ffhip_vp8_frame.hip, whose header is four words (0 and 2 unused, 1 the abort word: nobody polls it) */
+extern "C" int ffhip_vp8_check_modes_enqueue(const uint8_t *d_modes, long long n_records, uint32_t *ctrl, int *async_err, void *stream)
+{
+    hipLaunchKernelGGL(k_vp8_check_modes, dim3(check_modes_grid(n_records)), dim3(256), 0, (hipStream_t)stream, d_modes, n_records, ctrl, async_err, 2u, 1u);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
 }
 int vp8_check_modes_items_enqueue(const Vp8CheckItem *d_items, int n, long long n_records, uint32_t *ctrl, int *async_err, void *stream)
 {
-    hipLaunchKernelGGL(k_vp8_check_modes_items, dim3((unsigned)std::min<long long>((n_records + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       d_items, n, n_records, ctrl, async_err);
+    hipLaunchKernelGGL(k_vp8_check_modes_items, dim3(check_modes_grid(n_records)), dim3(256), 0, (hipStream_t)stream, d_items, n, n_records, ctrl, async_err);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
     return FFHIP_OK;
 }
 extern "C" int ffhip_vp8_modes_ok_host(const uint8_t *h_modes, long long n_records)
 {
-    for (long long i = 0; i < n_records; i++) {
-        const uint8_t *rec = h_modes + i * 20;
-        if (rec[0] > 4 || rec[1] > 3) return 0;
-        if (rec[0] == 4)
-            for (int k = 2; k < 18; k++)
-                if (rec[k] > 9) return 0; /* the reference indexes a table of ten predictors with it */
-    }
+    for (long long i = 0; i < n_records; i++)
+        if (!vp8_mode_record_valid(h_modes + i * 20)) return 0;
     return 1;
 }
 
 static unsigned long long *g_vp8_trace = nullptr;
 /* diagnostics: a device buffer of 8 x n_images x mbrows u64 the row kernel stamps (tests/tools/diag_vp8_row_trace.py); NULL = off */
 extern "C" void ffhip_debug_vp8_trace(void *d_buf) { g_vp8_trace = (unsigned long long *)d_buf; }
+
+Vp8RowSwitches vp8_row_switches(const char *mode, const Vp8SideBySide *sbs)
+{
+    Vp8RowSwitches sw;
+    sw.async_err = (mode && !strcmp(mode, "levels")) ? nullptr : ffhip_async_err_word();
+    if (sw.async_err && sbs && sbs->err_word) sw.async_err = sbs->err_word; /* the side-by-side call's own word (ffhip_vp8_lf.hip) */
+    const char *ps = FFHIP_ENV("FFHIP_VP8_PROGRESS_SHIFT"), *sl = FFHIP_ENV("FFHIP_VP8_SLACK");
+    sw.pshift = ps ? std::min(5, std::max(0, atoi(ps))) : 5;
+    sw.slack = sl ? std::max(0, atoi(sl)) : 0;
+    return sw;
+}
+int vp8_levels_upload_and_launch(int scratch_kind, void *stream, const std::vector<std::vector<uint32_t>> &lists,
+                                 const std::function<void(const uint32_t *work, int count)> &launch)
+{
+    size_t total = 0;
+    for (auto &l : lists) total += l.size();
+    uint32_t *g_work = ffhip_scratch(scratch_kind, stream, total);
+    if (!g_work) return FFHIP_ENOMEM;
+    std::vector<uint32_t> flat;
+    flat.reserve(total);
+    for (auto &l : lists) flat.insert(flat.end(), l.begin(), l.end());
+    FFHIP_CHECK(hipStreamSynchronize((hipStream_t)stream), FFHIP_EIO); /* the work buffer may still be in use by an earlier call */
+    FFHIP_CHECK(hipMemcpy(g_work, flat.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice), FFHIP_EIO);
+    size_t off = 0;
+    for (auto &l : lists) {
+        if (!l.empty()) launch(g_work + off, (int)(l.size() / 2));
+        off += l.size();
+    }
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
+}
+
+/* row form (default): no host-side scheduling at all, one launch.  `a`: the common fields */
+static int pred_rows_enqueue(Vp8PredArgs a, int n_images, const uint8_t *h_modes, const Vp8RowSwitches &sw, void *stream, Vp8SideBySide *sbs)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int mbcols = a.mbcols, mbrows = a.mbrows;
+    const long long recs = (long long)mbcols * mbrows * n_images;
+    /* mode bytes out of range: refused here, synchronously, for batches of up to 2^17 macroblocks; beyond that the
+     * host pass would cost more than the launch it guards (8 M records for 1024 frames), and a kernel in front of the row
+     * kernel refuses the call through the stream (k_vp8_check_modes: nothing is written, ffhip_stream_sync returns FFHIP_EINVAL) */
+    const bool host_checked = recs <= (1LL << 17);
+    if (host_checked && !ffhip_vp8_modes_ok_host(h_modes, recs)) return FFHIP_EINVAL;
+    const size_t words = FFHIP_VP8_CTRL_HDR + ((2 * (size_t)n_images * (size_t)mbrows) << sw.pshift); /* tickets, abort; the rows' luma counters, then their chroma counters */
+    uint32_t *g_work = ffhip_scratch(SCRATCH_VP8_PRED, stream, words);
+    if (!g_work) return FFHIP_ENOMEM;
+    FFHIP_CHECK(hipMemsetAsync(g_work, 0, words * sizeof(uint32_t), st), FFHIP_EIO);
+    if (!host_checked) { /* IN FRONT of the fork: enqueued behind it, the side-by-side filter kernel became resident a kernel ahead of the
+                            prediction it waits for, and a 1024-frame call took a third longer (12.1 -> 16.6 ms for the two stages) */
+        hipLaunchKernelGGL(k_vp8_check_modes, dim3(check_modes_grid(recs)), dim3(256), 0, st, a.modes, recs, g_work, sw.async_err, (uint32_t)FFHIP_VP8_CTRL_TICKET_C, (uint32_t)FFHIP_VP8_CTRL_ABORT);
+    }
+    if (sbs) { /* the loop filter of the same call starts behind this point, on its own stream */
+        FFHIP_CHECK(hipEventRecord(sbs->fork, st), FFHIP_EIO);
+        sbs->pred_progress = g_work + FFHIP_VP8_CTRL_HDR;
+        sbs->pshift = sw.pshift;
+    }
+    a.ctrl = g_work; a.async_err = sw.async_err; a.n_images = n_images; a.pshift = sw.pshift; a.slack = sw.slack;
+    a.trace = g_vp8_trace;
+    /* How many waves: as many as can be RESIDENT (occupancy x CUs; half of that next to the loop-filter kernel of the same
+     * call, so that the two always fit side by side whichever the hardware starts first), but never more rows per image
+     * than its wavefront is wide -- a row trails the row above by four macroblocks, so mbcols / 4 + 2 rows of an image can
+     * be at work at once; a wave beyond that holds a ticket far from its turn and only polls (16 x 1080p: 2048 waves
+     * 5.62 / 2.10 ms, 256 waves 5.48 / 1.96 -- tests/tools/bench_stages.py).  One wave per SIMD issues an instruction every
+     * 5-8 cycles (profiles/r2_lone_wave.txt); the co-resident waves of OTHER images fill those slots, which is where the
+     * throughput of a large batch comes from (tests/tools/bench_vp8_batch_sweep.py). */
+    const char *wv = FFHIP_ENV("FFHIP_VP8_PRED_WAVES");
+    /* measured (256 x 1080p, tests/tools/diag_vp8_batch_waves.py, diag_vp8_batch_grid.py): the kernel gains up to three waves per
+     * SIMD and loses beyond (2048 / 3072 / 4096 waves: 2.56 / 2.45 / 2.56 ms); next to the loop filter three quarters of the
+     * residency are the prediction's -- it is the longer chain -- and a quarter of its own the filter's: together they still fit */
+    long long resident = ffhip_resident_waves((const void *)k_vp8_predict_rows<false>, 64);
+    resident = std::max<long long>(1, resident - resident / 4);
+    const long long rows_wide = (long long)n_images * (mbcols / 5 + 1); /* measured, 16 x 1080p of the encoder's stream next to the filter: 16 / 24 / 32 rows per image 1.19 / 1.12 / 1.18 ms */
+    /* Luma and chroma as rows of their own (other waves) take the chroma off the chain a frame hangs on -- one frame 0.93 -> 0.84 ms --
+     * at the price of 14 device-coherent requests per macroblock instead of 10 (modes, poll and counter twice) and of as many
+     * chroma rows in flight as luma rows (a chroma row follows the row above at one macroblock).  Measured, whole chain on the
+     * encoder's stream, split against not: 1 frame 0.84 / 0.92 ms, 16 frames 1.16 / 1.15, 64 frames 2.55 / 1.97, 256 frames 6.7 / 5.4.
+     * So: split while the launch is at its minimum size anyway (a handful of frames), not beyond. */
+    const char *sp = FFHIP_ENV("FFHIP_VP8_PRED_SPLIT");
+    a.split = sp ? (atoi(sp) != 0) : (rows_wide * 5 / 3 <= 256);
+    const long long wide = std::max<long long>(256, a.split ? rows_wide * 5 / 3 : rows_wide);
+    const long long cap = wv ? std::max(1, atoi(wv)) : std::min(resident, wide);
+    const unsigned waves = (unsigned)std::min<long long>((a.split ? 2LL : 1LL) * n_images * mbrows, cap);
+    if (sbs) sbs->pred_split = a.split;
+    if (a.trace) hipLaunchKernelGGL(k_vp8_predict_rows<true>, dim3(waves), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_vp8_predict_rows<false>, dim3(waves), dim3(64), 0, st, a);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    return FFHIP_OK;
+}
+
+/* levels form (fallback, A/B): one launch per wavefront level */
+static int pred_levels_enqueue(Vp8PredArgs a, int n_images, const uint8_t *h_modes, void *stream)
+{
+    const int mbcols = a.mbcols, mbrows = a.mbrows;
+    const long long n_mb = (long long)mbcols * mbrows;
+    /* before anything is enqueued, as the row form's host check: k_vp8_predict indexes kVp8Taps with a B_PRED sub-block mode */
+    if (!ffhip_vp8_modes_ok_host(h_modes, n_mb * n_images)) return FFHIP_EINVAL;
+    /* wavefront levels: left, above, above-left, above-right -- plus the reference's wrapped
+     * read of H_PRED at x = 0, which sees the last pixel of the previous pixel row
+     * (predict.c:346-353), i.e. the last macroblock of the row above */
+    std::vector<int> level((size_t)n_mb);
+    std::vector<std::vector<uint32_t>> lists;
+    for (int img = 0; img < n_images; img++) {
+        const uint8_t *mo = h_modes + (size_t)img * n_mb * 20;
+        for (int y = 0; y < mbrows; y++)
+            for (int x = 0; x < mbcols; x++) {
+                int lv = 0;
+                auto dep = [&](int dx, int dy) { if (dx >= 0 && dx < mbcols && dy >= 0) lv = std::max(lv, level[(size_t)dy * mbcols + dx] + 1); };
+                dep(x - 1, y); dep(x, y - 1); dep(x - 1, y - 1); dep(x + 1, y - 1);
+                if (x == 0 && y > 0 && mo[((size_t)y * mbcols) * 20] == 3) dep(mbcols - 1, y - 1);
+                level[(size_t)y * mbcols + x] = lv;
+                if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
+                lists[(size_t)lv].push_back((uint32_t)img);
+                lists[(size_t)lv].push_back((uint32_t)(y * mbcols + x));
+            }
+    }
+    return vp8_levels_upload_and_launch(SCRATCH_VP8_PRED, stream, lists, [&](const uint32_t *work, int count) {
+        a.work = work; a.count = count;
+        hipLaunchKernelGGL(k_vp8_predict, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    });
+}
 
 /* sbs: next to the loop filter of the same call (ffhip_vp8_predict_loopfilter), which starts behind the counter reset */
 int vp8_predict_recon_impl(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
@@ -831,117 +892,15 @@ int vp8_predict_recon_impl(int mbcols, int mbrows, int n_images, const uint8_t *
         std::lock_guard<std::mutex> l(g_ffhip_state_mu);
         ffhip_stream_state(stream)->vp8_seq++;
     }
-
-    hipStream_t st = (hipStream_t)stream;
-    /* row form (default): no host-side scheduling at all, one launch */
-    const char *mode_env = FFHIP_ENV("FFHIP_VP8_PRED_MODE");
-    int *async_err = (mode_env && !strcmp(mode_env, "levels")) ? nullptr : ffhip_async_err_word();
-    if (async_err && sbs && sbs->err_word) async_err = sbs->err_word; /* the side-by-side call's own word (ffhip_vp8_lf.hip) */
-    if (async_err && !((uintptr_t)d_modes & 3) && n_mb < (1LL << 23) /* 32-bit byte offsets into a plane */) {
-        /* mode bytes out of range: refused here, synchronously, for batches of up to 2^17 macroblocks; beyond that the
-         * host pass would cost more than the launch it guards (8 M records for 1024 frames), and a kernel in front of the row
-         * kernel refuses the call through the stream (k_vp8_check_modes: nothing is written, ffhip_stream_sync returns FFHIP_EINVAL) */
-        const bool host_checked = n_mb * n_images <= (1LL << 17);
-        if (host_checked)
-            if (!ffhip_vp8_modes_ok_host(h_modes, n_mb * n_images)) return FFHIP_EINVAL;
-        const int pshift = []{ const char *e = FFHIP_ENV("FFHIP_VP8_PROGRESS_SHIFT"); return e ? std::min(5, std::max(0, atoi(e))) : 5; }();
-        const size_t words = FFHIP_VP8_CTRL_HDR + ((2 * (size_t)n_images * (size_t)mbrows) << pshift); /* tickets, abort; the rows' luma counters, then their chroma counters */
-        uint32_t *g_work = ffhip_scratch(SCRATCH_VP8_PRED, stream, words);
-        if (!g_work) return FFHIP_ENOMEM;
-        FFHIP_CHECK(hipMemsetAsync(g_work, 0, words * sizeof(uint32_t), st), FFHIP_EIO);
-        if (!host_checked) { /* IN FRONT of the fork: enqueued behind it, the side-by-side filter kernel became resident a kernel ahead of the
-                                prediction it waits for, and a 1024-frame call took a third longer (12.1 -> 16.6 ms for the two stages) */
-            const long long recs = n_mb * n_images;
-            hipLaunchKernelGGL(k_vp8_check_modes, dim3((unsigned)std::min<long long>((recs + 255) / 256, 4096)), dim3(256), 0, st, d_modes, recs, g_work, async_err, (uint32_t)FFHIP_VP8_CTRL_TICKET_C, (uint32_t)FFHIP_VP8_CTRL_ABORT);
-        }
-        if (sbs) { /* the loop filter of the same call starts behind this point, on its own stream */
-            FFHIP_CHECK(hipEventRecord(sbs->fork, st), FFHIP_EIO);
-            sbs->pred_progress = g_work + FFHIP_VP8_CTRL_HDR;
-            sbs->pshift = pshift;
-        }
-        Vp8PredArgs a = {};
-        a.modes = d_modes; a.residual = d_residual; a.resmap = d_resmap;
-        a.y = d_y; a.u = d_u; a.v = d_v;
-        a.plane_y = plane_stride_y; a.plane_uv = plane_stride_uv; a.res_stride = residual_stride;
-        a.mbcols = mbcols; a.mbrows = mbrows;
-        a.ctrl = g_work; a.async_err = async_err; a.n_images = n_images; a.pshift = pshift;
-        a.trace = g_vp8_trace;
-        { const char *sl = FFHIP_ENV("FFHIP_VP8_SLACK"); a.slack = sl ? std::max(0, atoi(sl)) : 0; }
-        /* How many waves: as many as can be RESIDENT (occupancy x CUs; half of that next to the loop-filter kernel of the same
-         * call, so that the two always fit side by side whichever the hardware starts first), but never more rows per image
-         * than its wavefront is wide -- a row trails the row above by four macroblocks, so mbcols / 4 + 2 rows of an image can
-         * be at work at once; a wave beyond that holds a ticket far from its turn and only polls (16 x 1080p: 2048 waves
-         * 5.62 / 2.10 ms, 256 waves 5.48 / 1.96 -- tests/tools/bench_stages.py).  One wave per SIMD issues an instruction every
-         * 5-8 cycles (profiles/r2_lone_wave.txt); the co-resident waves of OTHER images fill those slots, which is where the
-         * throughput of a large batch comes from (tests/tools/bench_vp8_batch_sweep.py). */
-        const char *wv = FFHIP_ENV("FFHIP_VP8_PRED_WAVES");
-        /* measured (256 x 1080p, tests/tools/diag_vp8_batch_waves.py, diag_vp8_batch_grid.py): the kernel gains up to three waves per
-         * SIMD and loses beyond (2048 / 3072 / 4096 waves: 2.56 / 2.45 / 2.56 ms); next to the loop filter three quarters of the
-         * residency are the prediction's -- it is the longer chain -- and a quarter of its own the filter's: together they still fit */
-        long long resident = ffhip_resident_waves((const void *)k_vp8_predict_rows<false>, 64);
-        resident = std::max<long long>(1, resident - resident / 4);
-        const long long rows_wide = (long long)n_images * (mbcols / 5 + 1); /* measured, 16 x 1080p of the encoder's stream next to the filter: 16 / 24 / 32 rows per image 1.19 / 1.12 / 1.18 ms */
-        /* Luma and chroma as rows of their own (other waves) take the chroma off the chain a frame hangs on -- one frame 0.93 -> 0.84 ms --
-         * at the price of 14 device-coherent requests per macroblock instead of 10 (modes, poll and counter twice) and of as many
-         * chroma rows in flight as luma rows (a chroma row follows the row above at one macroblock).  Measured, whole chain on the
-         * encoder's stream, split against not: 1 frame 0.84 / 0.92 ms, 16 frames 1.16 / 1.15, 64 frames 2.55 / 1.97, 256 frames 6.7 / 5.4.
-         * So: split while the launch is at its minimum size anyway (a handful of frames), not beyond. */
-        const char *sp = FFHIP_ENV("FFHIP_VP8_PRED_SPLIT");
-        a.split = sp ? (atoi(sp) != 0) : (rows_wide * 5 / 3 <= 256);
-        const long long wide = std::max<long long>(256, a.split ? rows_wide * 5 / 3 : rows_wide);
-        const long long cap = wv ? std::max(1, atoi(wv)) : std::min(resident, wide);
-        const unsigned waves = (unsigned)std::min<long long>((a.split ? 2LL : 1LL) * n_images * mbrows, cap);
-        if (sbs) sbs->pred_split = a.split;
-        if (a.trace) hipLaunchKernelGGL(k_vp8_predict_rows<true>, dim3(waves), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL(k_vp8_predict_rows<false>, dim3(waves), dim3(64), 0, st, a);
-        FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-        return FFHIP_OK;
-    }
-
-    /* wavefront levels: left, above, above-left, above-right -- plus the reference's wrapped
-     * read of H_PRED at x = 0, which sees the last pixel of the previous pixel row
-     * (predict.c:346-353), i.e. the last macroblock of the row above */
-    std::vector<int> level((size_t)n_mb);
-    std::vector<std::vector<uint32_t>> lists;
-    for (int img = 0; img < n_images; img++) {
-        const uint8_t *mo = h_modes + (size_t)img * n_mb * 20;
-        for (int y = 0; y < mbrows; y++)
-            for (int x = 0; x < mbcols; x++) {
-                int lv = 0;
-                auto dep = [&](int dx, int dy) { if (dx >= 0 && dx < mbcols && dy >= 0) lv = std::max(lv, level[(size_t)dy * mbcols + dx] + 1); };
-                dep(x - 1, y); dep(x, y - 1); dep(x - 1, y - 1); dep(x + 1, y - 1);
-                if (x == 0 && y > 0 && mo[((size_t)y * mbcols) * 20] == 3) dep(mbcols - 1, y - 1);
-                if (mo[((size_t)y * mbcols + x) * 20] > 4 || mo[((size_t)y * mbcols + x) * 20 + 1] > 3) return FFHIP_EINVAL;
-                level[(size_t)y * mbcols + x] = lv;
-                if ((size_t)lv >= lists.size()) lists.resize((size_t)lv + 1);
-                lists[(size_t)lv].push_back((uint32_t)img);
-                lists[(size_t)lv].push_back((uint32_t)(y * mbcols + x));
-            }
-    }
-    size_t total = 0;
-    for (auto &l : lists) total += l.size();
-    uint32_t *g_work = ffhip_scratch(SCRATCH_VP8_PRED, stream, total);
-    if (!g_work) return FFHIP_ENOMEM;
-    std::vector<uint32_t> flat;
-    flat.reserve(total);
-    for (auto &l : lists) flat.insert(flat.end(), l.begin(), l.end());
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO); /* the work buffer may still be in use by an earlier call */
-    FFHIP_CHECK(hipMemcpy(g_work, flat.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice), FFHIP_EIO);
-
-    Vp8PredArgs a;
+    Vp8PredArgs a = {}; /* the fields both forms read */
     a.modes = d_modes; a.residual = d_residual; a.resmap = d_resmap;
     a.y = d_y; a.u = d_u; a.v = d_v;
     a.plane_y = plane_stride_y; a.plane_uv = plane_stride_uv; a.res_stride = residual_stride;
     a.mbcols = mbcols; a.mbrows = mbrows;
-    size_t off = 0;
-    for (auto &l : lists) {
-        a.work = g_work + off;
-        a.count = (int)(l.size() / 2);
-        hipLaunchKernelGGL(k_vp8_predict, dim3((unsigned)((a.count + 3) / 4)), dim3(256), 0, st, a);
-        off += l.size();
-    }
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    return FFHIP_OK;
+    const Vp8RowSwitches sw = vp8_row_switches(FFHIP_ENV("FFHIP_VP8_PRED_MODE"), sbs);
+    if (sw.async_err && !((uintptr_t)d_modes & 3) && n_mb < (1LL << 23) /* 32-bit byte offsets into a plane */)
+        return pred_rows_enqueue(a, n_images, h_modes, sw, stream, sbs);
+    return pred_levels_enqueue(a, n_images, h_modes, stream);
 }
 extern "C" int ffhip_vp8_predict_recon(int mbcols, int mbrows, int n_images, const uint8_t *h_modes,
                                        const uint8_t *d_modes, const int16_t *d_residual, int64_t residual_stride,

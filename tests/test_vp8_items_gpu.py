@@ -218,6 +218,37 @@ def test_bad_device_modes_refuse_at_the_sync_and_write_nothing():
     assert L.ffhip_stream_sync(None) == 0
 
 
+def test_device_check_agrees_with_host_check():
+    """One 1x1-macroblock item per record of a table (positions 0..17; per position the limit, limit + 1, 0x0f, 0x10, 0x7f, 0x80, 0xff; each
+    once in a B_PRED record and once in a DC record), filter_type 0, the residual form: with h_modes the host check refuses a bad record at
+    the call, without it the device check refuses at the next ffhip_stream_sync, which says FFHIP_EINVAL exactly once.  Both are the numpy
+    rule, case by case: the smallest shape at which the shared predicate, the merged check kernel and its refusal stores can go wrong."""
+    L = capi.require_device()
+    bases = [np.array([4, 1] + [(3 * k + 1) % 10 for k in range(16)] + [0, 0], np.uint8), np.array([0, 2] + [(3 * k + 1) % 10 for k in range(16)] + [0, 0], np.uint8)]
+    recs = []
+    for p in range(18):
+        lim = 4 if p == 0 else (3 if p == 1 else 9)
+        for v in (lim, lim + 1, 0x0f, 0x10, 0x7f, 0x80, 0xff):
+            for b in bases:
+                rec = b.copy()
+                rec[p] = v
+                recs.append(rec)
+    recs = np.stack(recs)
+    want = (recs[:, 0] <= 4) & (recs[:, 1] <= 3) & ((recs[:, 0] != 4) | (recs[:, 2:18] <= 9).all(axis=1))
+    assert len(recs) == 252 and want.sum() not in (0, len(want))
+    f = Frame(1, 1, recs[0][None].copy(), 0, None, residual=synth.vp8_residual(1, seed=77))
+    for rec, ok in zip(recs, want):
+        f.modes[0] = rec
+        capi.check(L.ffhip_memcpy_h2d(f.dm.ptr, f.modes.ctypes.data, 20, None))
+        for host in (True, False):
+            f.host_modes = host
+            arr = (capi.Vp8Item * 1)(f.item())
+            rc = L.ffhip_vp8_decode_items(arr, 1, None)
+            first, second = L.ffhip_stream_sync(None), L.ffhip_stream_sync(None)
+            exp = (0, 0, 0) if ok else ((capi.FFHIP_EINVAL, 0, 0) if host else (0, capi.FFHIP_EINVAL, 0))
+            assert (rc, first, second) == exp, (rec, host)
+
+
 def test_bad_host_modes_refuse_the_call_with_nothing_enqueued():
     L = capi.require_device()
     frames = _sweep_frames(6, 6100)

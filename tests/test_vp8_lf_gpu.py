@@ -263,6 +263,40 @@ def test_sub_block_mode_above_9_is_refused(large):
     assert np.array_equal(dy.to_host((n, 16 * r, 16 * c), np.uint8), y_h)
 
 
+def test_sub_block_mode_above_9_is_refused_by_the_levels_form(monkeypatch):
+    """... and by the levels form (FFHIP_VP8_PRED_MODE=levels), which indexes the tap table with that byte: a 2x2-macroblock frame, the call
+    itself returns FFHIP_EINVAL with nothing enqueued, the planes are untouched; the same byte in a record that is not B_PRED passes."""
+    from ffpic_amd import capi
+    L = capi.require_device()
+    c = r = 2
+    modes = np.zeros((1, 4, 20), np.uint8)
+    modes[0, :, 0] = [4, 0, 4, 1]
+    modes[0, :, 2:18] = np.arange(64, dtype=np.uint8).reshape(4, 16) % 10
+    bad = modes.copy()
+    bad[0, 2, 2 + 5] = 10
+    harmless = modes.copy()
+    harmless[0, 3, 2 + 5] = 200
+    dr = ops.DeviceBuffer(synth.vp8_residual(4, seed=43)[None])
+    dy, du, dv = ops.DeviceBuffer(nbytes=1024), ops.DeviceBuffer(nbytes=256), ops.DeviceBuffer(nbytes=256)
+    monkeypatch.setenv("FFHIP_VP8_PRED_MODE", "levels"); capi.reload_env()
+    try:
+        def call(m):
+            dm = ops.DeviceBuffer(m)
+            for d in (dy, du, dv):
+                capi.check(L.ffhip_memset(d.ptr, 0x5a, d.nbytes, None))
+            rc = L.ffhip_vp8_predict_recon(c, r, 1, m.ctypes.data, dm.ptr, dr.ptr, 4 * 384, None, dy.ptr, du.ptr, dv.ptr, 1024, 256, None)
+            return rc, L.ffhip_stream_sync(None)
+        assert call(bad) == (capi.FFHIP_EINVAL, 0)
+        for d, nb in ((dy, 1024), (du, 256), (dv, 256)):
+            assert (d.to_host((nb,), np.uint8) == 0x5a).all()
+        assert call(harmless) == (0, 0)
+        y_h = dy.to_host((1024,), np.uint8)
+        assert call(modes) == (0, 0)
+        assert np.array_equal(dy.to_host((1024,), np.uint8), y_h) and not (y_h == 0x5a).all()
+    finally:
+        monkeypatch.undo(); capi.reload_env()
+
+
 def test_webp_file_1080p_256_frames(golden):
     """A chip-filling batch: 256 copies of the real encoder's 1080p frame in ONE ffhip_vp8_predict_loopfilter call (the frame loop
     of webp.c:1833-1866; the wave caps follow residency at this size, not 16 waves per image).  Every frame's planes equal the
