@@ -170,8 +170,18 @@ struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_j
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
                                 const ffhip_jpeg_geom *geoms, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant,
                                 int *status, void *stream, const FfhipHuffThen *then);
-int jpeg_item_class(const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch); /* the layout class 0..6 of a picture ffhip_jpeg_recon_items takes
-                                                                                        with this output and pitch, -1 if it refuses it */
+/* The layout classes of the fused JPEG kernels (ffhip_jpeg.hip: 4:2:0, 4:4:4, 4:2:2, 4:4:0, h4v1, h1v4, grey) and what one call chooses for its
+ * kernels, read from the FFHIP_JPEG_* switches once, up front */
+#define JPEG_CLASSES 7
+struct JpegChoices {
+    int variant; /* 4:2:0: <quads per wave><nt bits> */
+    int remap;   /* the mode of the workgroup-to-XCD remap */
+    int strips[JPEG_CLASSES], mps[JPEG_CLASSES], per_wave[JPEG_CLASSES]; /* per class: strips' worth per wave (1 / 2), MCUs of a unit (a quad, or
+                                                                            that many strips), units a wave takes */
+};
+JpegChoices jpeg_choices(void);
+/* the layout class 0..6 of a picture ffhip_jpeg_recon_items takes with this output and pitch under these choices, -1 if it refuses it */
+int jpeg_item_class(const JpegChoices &ch, const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch);
 int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot); /* ffhip_jpeg_recon_items with scratch slot 0..FFHIP_HUFF_PARTS-1 */
 /* the plane and quantiser pointers of picture `index` of a call whose planes hold its pictures one behind the other: the picture's blocks start
  * at MCU `mcu_base` of y / u / v (u, v NULL for grey), its tables are the index-th 256 of q */

@@ -40,6 +40,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #ifndef WAVES_PER_WG
@@ -666,90 +667,171 @@ static int geom_ok(const ffhip_jpeg_geom *g)
     return 1;
 }
 
-/* kernel variant: quads per wave and cache policy.  FFHIP_JPEG_VARIANT="<qpw><nt>" (e.g. "21")
- * overrides the default for experiments; every variant computes identical bytes. */
-/* A/B knobs; identical bytes either way.  FFHIP_JPEG_XCD_CHUNK_LOG2=k (2..20): the XCDs take chunks of 2^k workgroups in turn */
-static int jpeg_remap_mode(void)
+/* The layout classes of the fused kernels, in the order jpeg_item_class reports them: 4:2:0 (k_jpeg420_fused, a unit = a quad of 4 MCUs), then
+ * the strip layouts (k_jpeg_fused_strip, a unit = a strip): 4:4:4, 4:2:2, 4:4:0, 4:1:1 (h = 4) and its transpose (v = 4), grey.  Every other
+ * layout the reference's loop admits -- the three-block pairs (h or v = 3), grey with several blocks per MCU; no encoder writes them -- has
+ * no class and takes the two-pass path.  `mcus`: MCUs of a unit of one strip; `can_two`: there is a TWO = 1 kernel, two strips' worth per
+ * wave (h * v = 4 always has 1 024 pixels per wave). */
+struct JpegLayout { int ncomp, h, v, mcus; bool can_two; const char *kernel; };
+static constexpr JpegLayout kLayout[JPEG_CLASSES] = {
+    {3, 2, 2, 4, false, "k_jpeg420_fused"},
+    {3, 1, 1, 8, true, "k_jpeg_fused_strip"},
+    {3, 2, 1, 4, true, "k_jpeg_fused_strip"},
+    {3, 1, 2, 4, true, "k_jpeg_fused_strip"},
+    {3, 4, 1, 4, false, "k_jpeg_fused_strip"},
+    {3, 1, 4, 4, false, "k_jpeg_fused_strip"},
+    {1, 1, 1, 8, true, "k_jpeg_fused_strip"},
+};
+static int jpeg_layout_class(const ffhip_jpeg_geom *g)
 {
-    if (FFHIP_ENV("FFHIP_JPEG_NO_XCD_REMAP")) return 0;
-    const char *e = FFHIP_ENV("FFHIP_JPEG_XCD_CHUNK_LOG2");
-    if (e) { const int k = atoi(e); if (k >= 2 && k <= 20) return k; }
-    return 1;
+    for (int c = 0; c < JPEG_CLASSES; c++)
+        if (g->ncomp == kLayout[c].ncomp && g->h == kLayout[c].h && g->v == kLayout[c].v) return c;
+    return -1;
 }
-static void launch_fused(const JpegBatch &q_in, int n_images, hipStream_t st)
+
+/* What a call chooses for its kernels, fixed up front: the grid and the kernel must agree whatever ffhip_reload_env does meanwhile.
+ * Every choice computes identical bytes. */
+JpegChoices jpeg_choices(void)
 {
+    JpegChoices ch;
+    /* kernel variant of 4:2:0: quads per wave and cache policy.  FFHIP_JPEG_VARIANT="<qpw><nt>" (e.g. "21") overrides the default for experiments */
     const char *e = FFHIP_ENV("FFHIP_JPEG_VARIANT");
-    const int g_variant = (e && e[0] >= '1' && e[0] <= '2' && e[1] >= '0' && e[1] <= '3') ? (e[0] - '0') * 10 + (e[1] - '0') : FFHIP_JPEG_DEFAULT_VARIANT;
-    const int qpw = g_variant / 10;
-    JpegBatch q = q_in;
-    q.xcd_remap = jpeg_remap_mode();
-    const int slots = (q.quads_per_image + qpw - 1) / qpw;
-    q.wgs_per_image = (slots + WAVES_PER_WG - 1) / WAVES_PER_WG;
-    q.wpi_magic = q.wgs_per_image == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)q.wgs_per_image) + 1u;
-    const dim3 grid((unsigned)((long long)q.wgs_per_image * n_images), 1, 1);
-    /* FFHIP_JPEG_LDS_PAD=<bytes>: that much dynamic LDS per workgroup on top of the kernel's own 21 KB, which nobody touches -- fewer workgroups per CU
-     * (7 as shipped; 8192 -> 5, 16384 -> 4, 32768 -> 3, 61440 -> 1): the occupancy experiment of DESIGN.md 5 as a run-time switch */
-    const char *pe = FFHIP_ENV("FFHIP_JPEG_LDS_PAD");
-    const unsigned pad = pe && atoi(pe) > 0 && atoi(pe) <= 120 * 1024 ? (unsigned)atoi(pe) & ~15u : 0u;
-    if (q.pattern_only) { /* the variant's twin (non-temporal loads and stores): same grid, same loads, same stores */
-        if (qpw == 2) hipLaunchKernelGGL((k_jpeg420_fused<2, 3, true>), grid, dim3(WG_THREADS), pad, st, q);
-        else hipLaunchKernelGGL((k_jpeg420_fused<1, 3, true>), grid, dim3(WG_THREADS), pad, st, q);
-        return;
+    ch.variant = (e && e[0] >= '1' && e[0] <= '2' && e[1] >= '0' && e[1] <= '3') ? (e[0] - '0') * 10 + (e[1] - '0') : FFHIP_JPEG_DEFAULT_VARIANT;
+    /* A/B knobs of the workgroup placement.  FFHIP_JPEG_XCD_CHUNK_LOG2=k (2..20): the XCDs take chunks of 2^k workgroups in turn */
+    ch.remap = 1;
+    e = FFHIP_ENV("FFHIP_JPEG_XCD_CHUNK_LOG2");
+    if (e && atoi(e) >= 2 && atoi(e) <= 20) ch.remap = atoi(e);
+    if (FFHIP_ENV("FFHIP_JPEG_NO_XCD_REMAP")) ch.remap = 0;
+    /* two strips' worth per wave where there is a kernel for it.  FFHIP_JPEG_STRIPS=1 / 2 forces either.  4:4:4, 4:2:2, 4:4:0: + 2-3 %, + 4-5 %,
+     * + 3-6 % on the same output buffer, slow and fast placements alike; grey, which runs at its access pattern with one strip, loses 1-4 % with
+     * two (the pattern of 128 x 8-pixel strips is that much slower than that of 64 x 8: profiles/r6_strips_ab*.jsonl) */
+    e = FFHIP_ENV("FFHIP_JPEG_STRIPS");
+    const int forced = e && (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0;
+    for (int c = 0; c < JPEG_CLASSES; c++) {
+        const JpegLayout &l = kLayout[c];
+        ch.strips[c] = !l.can_two ? 1 : (forced ? forced : (l.ncomp == 3 ? FFHIP_JPEG_STRIPS_DEFAULT : 1));
+        ch.mps[c] = l.mcus * ch.strips[c];
+        ch.per_wave[c] = c == 0 ? ch.variant / 10 : 1;
     }
-#define FFHIP_LAUNCH(Q, N) hipLaunchKernelGGL((k_jpeg420_fused<Q, N>), grid, dim3(WG_THREADS), pad, st, q)
-    switch (g_variant) {
-    case 10: FFHIP_LAUNCH(1, 0); break;
-    case 11: FFHIP_LAUNCH(1, 1); break;
-    case 12: FFHIP_LAUNCH(1, 2); break;
-    case 13: FFHIP_LAUNCH(1, 3); break;
-    case 20: FFHIP_LAUNCH(2, 0); break;
-    case 21: FFHIP_LAUNCH(2, 1); break;
-    case 22: FFHIP_LAUNCH(2, 2); break;
-    default: FFHIP_LAUNCH(2, 3); break;
-    }
-#undef FFHIP_LAUNCH
+    return ch;
 }
 
-static int is_fused420(const ffhip_jpeg_geom *g) { return g->ncomp == 3 && g->h == 2 && g->v == 2; }
-/* 4:4:4, 4:2:2, 4:4:0, 4:1:1 (h = 4) and its transpose (v = 4), grey: k_jpeg_fused_strip.  The three-block pairs
- * (h or v = 3) and grey with several blocks per MCU -- layouts the reference's loop admits and no encoder writes --
- * take the two-pass path */
-static int is_fused_strip(const ffhip_jpeg_geom *g)
+/* floor(2^32 / x) + 1: n / x = mulhi(n, magic) for the n the kernels divide (x = 1: n itself) */
+static u32 recip_magic(int x) { return x == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)x) + 1u; }
+
+/* One picture's planes, quantiser tables, output and pitch, as the uniform call (every picture of its batch) and an item give them: first the
+ * rules that need no device ... */
+static bool picture_planes_ok(const ffhip_jpeg_geom *g, const int16_t *y, const int16_t *u, const int16_t *v, const uint16_t *quant)
 {
-    return (g->ncomp == 3 && (g->h * g->v <= 2 || g->h == 4 || g->v == 4)) || (g->ncomp == 1 && g->h == 1 && g->v == 1);
+    if (!y || !quant || (g->ncomp == 3 && (!u || !v))) return false;
+    return !(((uintptr_t)y & 15) || ((uintptr_t)u & 15) || ((uintptr_t)v & 15) || ((uintptr_t)quant & 15));
+}
+static bool picture_out_ok(const ffhip_jpeg_geom *g, const uint8_t *bgra, int64_t pitch)
+{
+    return bgra && !((uintptr_t)bgra & 15) && pitch >= (int64_t)g->mcu_cols * 8 * g->h * 4 && !(pitch & 15);
+}
+/* ... then the limits of the fused kernels' index arithmetic, for units of `mps` MCUs.  The uniform call asks behind its device check, the
+ * items call in front of it */
+static long long units_per_row(const ffhip_jpeg_geom *g, int mps) { return (g->mcu_cols + mps - 1) / mps; }
+static bool picture_limits_ok(const ffhip_jpeg_geom *g, int mps, int64_t pitch)
+{
+    const long long qpr = units_per_row(g, mps);
+    return qpr <= 4096 && qpr * g->mcu_rows <= (1 << 20) && pitch * 16 <= 0x7fffffffLL;
+}
+/* ... and the picture's part of a JpegBatch / JpegItemDesc.  "quad" = unit: a strip for the strip layouts */
+template <class T>
+static void picture_fill(T &p, const ffhip_jpeg_geom *g, int mps, const int16_t *y, const int16_t *u, const int16_t *v, const uint16_t *quant, uint8_t *bgra,
+                         int64_t pitch)
+{
+    p.coef_y = y; p.coef_u = u; p.coef_v = v;
+    p.quant = quant; p.bgra = bgra; p.pitch = pitch;
+    p.mcu_cols = g->mcu_cols; p.mcu_rows = g->mcu_rows;
+    p.quads_per_row = (int)units_per_row(g, mps);
+    p.quads_per_image = p.quads_per_row * g->mcu_rows;
+    p.qpr_magic = recip_magic(p.quads_per_row);
+    p.qt_y = g->qt_id[0]; p.qt_u = g->qt_id[1]; p.qt_v = g->qt_id[2];
+}
+/* workgroups of a picture: `per_wave` units a wave */
+static int picture_wgs(int quads_per_image, int per_wave)
+{
+    const int slots = (quads_per_image + per_wave - 1) / per_wave;
+    return (slots + WAVES_PER_WG - 1) / WAVES_PER_WG;
 }
 
-/* two strips' worth per wave for the layouts with h * v <= 2 and grey (k_jpeg_fused_strip<..., TWO = 1>); h * v = 4 always has.  FFHIP_JPEG_STRIPS=1 / 2 forces either */
-static bool strip_two(const ffhip_jpeg_geom *g)
+/* Run-time values to template arguments, each mapping written once for the uniform and the items launcher.
+ * f(<class>, <TWO>): H, V and NC of the class's kernels are kLayout's; TWO = 1 only where the class has such a kernel */
+template <int N> using Int = std::integral_constant<int, N>;
+template <class F> static void with_class(int c, bool two, F f)
 {
-    if (g->ncomp == 3 && g->h * g->v == 4) return false;
-    const char *e = FFHIP_ENV("FFHIP_JPEG_STRIPS");
-    if (e && (e[0] == '1' || e[0] == '2')) return e[0] == '2';
-    /* 4:4:4, 4:2:2, 4:4:0: + 2-3 %, + 4-5 %, + 3-6 % on the same output buffer, slow and fast placements alike; grey, which runs at its access pattern with one
-     * strip, loses 1-4 % with two (the pattern of 128 x 8-pixel strips is that much slower than that of 64 x 8: profiles/r6_strips_ab*.jsonl) */
-    return FFHIP_JPEG_STRIPS_DEFAULT == 2 && g->ncomp == 3;
+    auto strips = [&](auto C) {
+        if constexpr (kLayout[decltype(C)::value].can_two) { if (two) return f(C, Int<1>()); }
+        f(C, Int<0>());
+    };
+    switch (c) {
+    case 0: strips(Int<0>()); break;
+    case 1: strips(Int<1>()); break;
+    case 2: strips(Int<2>()); break;
+    case 3: strips(Int<3>()); break;
+    case 4: strips(Int<4>()); break;
+    case 5: strips(Int<5>()); break;
+    default: strips(Int<6>()); break;
+    }
 }
-static void launch_strip(const ffhip_jpeg_geom *g, const JpegBatch &q_in, int n_images, bool two, hipStream_t st)
+/* f(<QPW>, <NT>) of a 4:2:0 variant */
+template <class F> static void with_variant(int variant, F f)
 {
-    JpegBatch q = q_in;
-    q.xcd_remap = jpeg_remap_mode();
-    q.wgs_per_image = (q.quads_per_image + WAVES_PER_WG - 1) / WAVES_PER_WG;
-    q.wpi_magic = q.wgs_per_image == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)q.wgs_per_image) + 1u;
-    const dim3 grid((unsigned)((long long)q.wgs_per_image * n_images), 1, 1);
-#define STRIP_LAUNCH(H_, V_, NC_) do { \
-        if (q.pattern_only) { /* the arithmetic-free twins: same grids, loads and stores */ \
-            if (two) hipLaunchKernelGGL((k_jpeg_fused_strip<H_, V_, NC_, 3, true, 1>), grid, dim3(WG_THREADS), 0, st, q); \
-            else hipLaunchKernelGGL((k_jpeg_fused_strip<H_, V_, NC_, 3, true, 0>), grid, dim3(WG_THREADS), 0, st, q); \
-        } else if (two) hipLaunchKernelGGL((k_jpeg_fused_strip<H_, V_, NC_, 3, false, 1>), grid, dim3(WG_THREADS), 0, st, q); \
-        else hipLaunchKernelGGL((k_jpeg_fused_strip<H_, V_, NC_, 3, false, 0>), grid, dim3(WG_THREADS), 0, st, q); \
-    } while (0)
-    if (g->ncomp == 1) STRIP_LAUNCH(1, 1, 1);
-    else if (g->h == 1 && g->v == 1) STRIP_LAUNCH(1, 1, 3);
-    else if (g->h == 2) STRIP_LAUNCH(2, 1, 3);
-    else if (g->v == 2) STRIP_LAUNCH(1, 2, 3);
-    else if (g->h == 4) STRIP_LAUNCH(4, 1, 3);
-    else STRIP_LAUNCH(1, 4, 3);
-#undef STRIP_LAUNCH
+    auto nt = [&](auto Q) {
+        switch (variant % 10) {
+        case 0: f(Q, Int<0>()); break;
+        case 1: f(Q, Int<1>()); break;
+        case 2: f(Q, Int<2>()); break;
+        default: f(Q, Int<3>()); break;
+        }
+    };
+    if (variant / 10 == 1) nt(Int<1>());
+    else nt(Int<2>());
+}
+
+/* the uniform launch of class c: q.n_images pictures of q's geometry */
+static void launch_batch(int c, const JpegChoices &ch, JpegBatch q, hipStream_t st)
+{
+    q.xcd_remap = ch.remap;
+    q.wgs_per_image = picture_wgs(q.quads_per_image, ch.per_wave[c]);
+    q.wpi_magic = recip_magic(q.wgs_per_image);
+    const dim3 grid((unsigned)((long long)q.wgs_per_image * q.n_images), 1, 1);
+    with_class(c, ch.strips[c] == 2, [&](auto C, auto TWO) {
+        constexpr int cls = decltype(C)::value, two = decltype(TWO)::value;
+        constexpr JpegLayout l = kLayout[cls];
+        if constexpr (cls == 0) {
+            /* FFHIP_JPEG_LDS_PAD=<bytes>: that much dynamic LDS per workgroup on top of the kernel's own 21 KB, which nobody touches -- fewer workgroups per CU
+             * (7 as shipped; 8192 -> 5, 16384 -> 4, 32768 -> 3, 61440 -> 1): the occupancy experiment of DESIGN.md 5 as a run-time switch */
+            const char *pe = FFHIP_ENV("FFHIP_JPEG_LDS_PAD");
+            const unsigned pad = pe && atoi(pe) > 0 && atoi(pe) <= 120 * 1024 ? (unsigned)atoi(pe) & ~15u : 0u;
+            with_variant(ch.variant, [&](auto Q, auto N) {
+                constexpr int qpw = decltype(Q)::value, nt = decltype(N)::value;
+                /* the variant's twin (non-temporal loads and stores): same grid, same loads, same stores */
+                if (q.pattern_only) hipLaunchKernelGGL((k_jpeg420_fused<qpw, 3, true>), grid, dim3(WG_THREADS), pad, st, q);
+                else hipLaunchKernelGGL((k_jpeg420_fused<qpw, nt>), grid, dim3(WG_THREADS), pad, st, q);
+            });
+        } else if (q.pattern_only) /* the arithmetic-free twins: same grids, loads and stores */
+            hipLaunchKernelGGL((k_jpeg_fused_strip<l.h, l.v, l.ncomp, 3, true, two>), grid, dim3(WG_THREADS), 0, st, q);
+        else
+            hipLaunchKernelGGL((k_jpeg_fused_strip<l.h, l.v, l.ncomp, 3, false, two>), grid, dim3(WG_THREADS), 0, st, q);
+    });
+}
+/* the items launch of class c: the workgroups of `grid` from t.wg_base on */
+static void launch_items(int c, const JpegChoices &ch, dim3 grid, const JpegItems &t, hipStream_t st)
+{
+    with_class(c, ch.strips[c] == 2, [&](auto C, auto TWO) {
+        constexpr int cls = decltype(C)::value, two = decltype(TWO)::value;
+        constexpr JpegLayout l = kLayout[cls];
+        if constexpr (cls == 0)
+            with_variant(ch.variant, [&](auto Q, auto N) {
+                hipLaunchKernelGGL((k_jpeg420_fused_items<decltype(Q)::value, decltype(N)::value>), grid, dim3(WG_THREADS), 0, st, t);
+            });
+        else
+            hipLaunchKernelGGL((k_jpeg_fused_strip_items<l.h, l.v, l.ncomp, 3, two>), grid, dim3(WG_THREADS), 0, st, t);
+    });
 }
 
 static int grid_for(long long work_items_per_wg_unit)
@@ -772,7 +854,7 @@ extern "C" int ffhip_bgra_layout(const ffhip_jpeg_geom *g, int64_t *pitch, int64
 
 extern "C" size_t ffhip_jpeg_workspace_bytes(const ffhip_jpeg_geom *g, int n_images)
 {
-    if (!geom_ok(g) || n_images <= 0 || is_fused420(g) || is_fused_strip(g)) return 0;
+    if (!geom_ok(g) || n_images <= 0 || jpeg_layout_class(g) >= 0) return 0;
     size_t mcus = (size_t)g->mcu_cols * g->mcu_rows * (size_t)n_images;
     size_t blocks = mcus * (size_t)(g->h * g->v) + (g->ncomp == 3 ? 2 * mcus : 0);
     return blocks * 64 * sizeof(int16_t);
@@ -781,7 +863,8 @@ extern "C" size_t ffhip_jpeg_workspace_bytes(const ffhip_jpeg_geom *g, int n_ima
 extern "C" const char *ffhip_jpeg_kernel_name(const ffhip_jpeg_geom *g)
 {
     if (!geom_ok(g)) return "";
-    return is_fused420(g) ? "k_jpeg420_fused" : (is_fused_strip(g) ? "k_jpeg_fused_strip" : "k_jpeg_idct_planes");
+    const int c = jpeg_layout_class(g);
+    return c >= 0 ? kLayout[c].kernel : "k_jpeg_idct_planes";
 }
 
 static int jpeg_recon_batch_impl(const ffhip_jpeg_geom *g, int n_images, const int16_t *d_coef_y,
@@ -793,84 +876,32 @@ static int jpeg_recon_batch_impl(const ffhip_jpeg_geom *g, int n_images, const i
     if (!geom_ok(g) || n_images < 0) return FFHIP_EINVAL;
     if (n_images == 0) return FFHIP_OK;
     const int64_t width = (int64_t)g->mcu_cols * 8 * g->h, height = (int64_t)g->mcu_rows * 8 * g->v;
-    if (!d_coef_y || !d_quant || !d_bgra) return FFHIP_EINVAL;
-    if (g->ncomp == 3 && (!d_coef_u || !d_coef_v)) return FFHIP_EINVAL;
-    if (pitch < width * 4 || (pitch & 15) || ((uintptr_t)d_bgra & 15) || (image_stride & 15)) return FFHIP_EINVAL;
-    if (n_images > 1 && image_stride < pitch * height) return FFHIP_EINVAL;
-    if (quant_stride != 0 && quant_stride < 256) return FFHIP_EINVAL;
-    if (((uintptr_t)d_coef_y & 15) || ((uintptr_t)d_coef_u & 15) || ((uintptr_t)d_coef_v & 15) ||
-        ((uintptr_t)d_quant & 15) || (quant_stride & 7))
-        return FFHIP_EINVAL;
+    if (!picture_planes_ok(g, d_coef_y, d_coef_u, d_coef_v, d_quant) || !picture_out_ok(g, d_bgra, pitch)) return FFHIP_EINVAL;
+    if ((image_stride & 15) || (n_images > 1 && image_stride < pitch * height)) return FFHIP_EINVAL;
+    if ((quant_stride != 0 && quant_stride < 256) || (quant_stride & 7)) return FFHIP_EINVAL;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
 
-    if (pattern_only && !is_fused420(g) && !is_fused_strip(g)) return FFHIP_EINVAL;
-    if (is_fused420(g)) {
-        JpegBatch p;
-        p.pattern_only = 0;
+    const int c = jpeg_layout_class(g);
+    if (c >= 0) {
+        const JpegChoices ch = jpeg_choices();
+        if (!picture_limits_ok(g, ch.mps[c], pitch)) return FFHIP_EINVAL;
+        JpegBatch p = {};
+        picture_fill(p, g, ch.mps[c], d_coef_y, d_coef_u, d_coef_v, d_quant, d_bgra, pitch);
+        p.quant_stride = quant_stride; p.image_stride = image_stride; p.n_images = n_images;
         if (pattern_only) {
             const char *sl = FFHIP_ENV("FFHIP_JPEG_PATTERN_SLEEP");
             p.pattern_only = 1 + (sl && atoi(sl) > 0 && atoi(sl) < 4096 ? atoi(sl) : 0);
         }
-        p.coef_y = d_coef_y; p.coef_u = d_coef_u; p.coef_v = d_coef_v;
-        p.quant = d_quant; p.quant_stride = quant_stride;
-        p.bgra = d_bgra; p.pitch = pitch; p.image_stride = image_stride;
-        p.mcu_cols = g->mcu_cols; p.mcu_rows = g->mcu_rows;
-        p.quads_per_row = (g->mcu_cols + 3) / 4; p.n_images = n_images;
-        p.quads_per_image = p.quads_per_row * g->mcu_rows;
-        p.qpr_magic = p.quads_per_row == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)p.quads_per_row) + 1u;
-        p.qt_y = g->qt_id[0]; p.qt_u = g->qt_id[1]; p.qt_v = g->qt_id[2];
-        long long quads = (long long)p.quads_per_row * p.mcu_rows * n_images;
-        if (quads > 0x7fffffffLL || pitch * 16 > 0x7fffffffLL || p.quads_per_image > (1 << 20) || p.quads_per_row > 4096)
-            return FFHIP_EINVAL;
-        const int max_imgs = (int)(0x7fffffffLL / ((p.quads_per_image + WAVES_PER_WG - 1) / WAVES_PER_WG));
-        for (int first = 0; first < n_images; first += max_imgs) {
-            const int cnt = n_images - first < max_imgs ? n_images - first : max_imgs;
-            JpegBatch q = p;
-            const long long mcus = (long long)g->mcu_cols * g->mcu_rows;
-            q.coef_y += (long long)first * mcus * 256;
-            q.coef_u += (long long)first * mcus * 64;
-            q.coef_v += (long long)first * mcus * 64;
-            q.quant += (long long)first * quant_stride;
-            q.bgra += (long long)first * image_stride;
-            q.n_images = cnt;
-            launch_fused(q, cnt, st);
-            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-        }
+        /* One launch, below 2^31 workgroups: quads_per_image * n_images <= 0x7fffffff here, hence
+         * n_images <= floor(0x7fffffff / quads_per_image) <= floor(0x7fffffff / ceil(quads_per_image / 4)),
+         * and a picture takes at most ceil(quads_per_image / 4) workgroups. */
+        if ((long long)p.quads_per_image * n_images > 0x7fffffffLL) return FFHIP_EINVAL;
+        launch_batch(c, ch, p, st);
+        FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
         return FFHIP_OK;
     }
-
-    if (is_fused_strip(g)) {
-        const bool two = strip_two(g); /* once per call: the grid and the kernel must agree whatever ffhip_reload_env does meanwhile */
-        const int mps = ((g->ncomp == 1 || g->h * g->v == 1) ? 8 : 4) * (two ? 2 : 1), bpm = g->ncomp == 1 ? 1 : g->h * g->v;
-        JpegBatch p = {};
-        p.pattern_only = pattern_only ? 1 : 0;
-        p.coef_y = d_coef_y; p.coef_u = d_coef_u; p.coef_v = d_coef_v;
-        p.quant = d_quant; p.quant_stride = quant_stride;
-        p.bgra = d_bgra; p.pitch = pitch; p.image_stride = image_stride;
-        p.mcu_cols = g->mcu_cols; p.mcu_rows = g->mcu_rows;
-        p.quads_per_row = (g->mcu_cols + mps - 1) / mps; p.n_images = n_images;   /* "quad" = strip here */
-        p.quads_per_image = p.quads_per_row * g->mcu_rows;
-        p.qpr_magic = p.quads_per_row == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)p.quads_per_row) + 1u;
-        p.qt_y = g->qt_id[0]; p.qt_u = g->qt_id[1]; p.qt_v = g->qt_id[2];
-        const long long strips = (long long)p.quads_per_row * p.mcu_rows * n_images;
-        if (strips > 0x7fffffffLL || pitch * 16 > 0x7fffffffLL || p.quads_per_image > (1 << 20) || p.quads_per_row > 4096)
-            return FFHIP_EINVAL;
-        const int max_imgs = (int)(0x7fffffffLL / ((p.quads_per_image + WAVES_PER_WG - 1) / WAVES_PER_WG));
-        for (int first = 0; first < n_images; first += max_imgs) {
-            const int cnt = n_images - first < max_imgs ? n_images - first : max_imgs;
-            JpegBatch q = p;
-            const long long mcus = (long long)g->mcu_cols * g->mcu_rows;
-            q.coef_y += (long long)first * mcus * 64 * bpm;
-            if (g->ncomp == 3) { q.coef_u += (long long)first * mcus * 64; q.coef_v += (long long)first * mcus * 64; }
-            q.quant += (long long)first * quant_stride;
-            q.bgra += (long long)first * image_stride;
-            q.n_images = cnt;
-            launch_strip(g, q, cnt, two, st);
-            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-        }
-        return FFHIP_OK;
-    }
+    if (pattern_only) return FFHIP_EINVAL;
 
     /* remaining geometries (grey with h*v > 1, h or v = 3): IDCT to sample planes, then colour */
     const size_t need = ffhip_jpeg_workspace_bytes(g, n_images);
@@ -905,77 +936,10 @@ static int jpeg_recon_batch_impl(const ffhip_jpeg_geom *g, int n_images, const i
 
 /* ---- mixed batches: ffhip_jpeg_recon_items ---- */
 
-/* the layout classes of the fused kernels: 4:2:0, 4:4:4, 4:2:2, 4:4:0, h4v1, h1v4, grey; -1 for the two-pass layouts */
-static int jpeg_layout_class(const ffhip_jpeg_geom *g)
+int jpeg_item_class(const JpegChoices &ch, const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch)
 {
-    if (g->ncomp == 1) return g->h == 1 && g->v == 1 ? 6 : -1;
-    if (g->h == 2 && g->v == 2) return 0;
-    if (g->h == 1 && g->v == 1) return 1;
-    if (g->h == 2 && g->v == 1) return 2;
-    if (g->h == 1 && g->v == 2) return 3;
-    if (g->h == 4 && g->v == 1) return 4;
-    if (g->h == 1 && g->v == 4) return 5;
-    return -1;
-}
-#define JPEG_CLASSES 7
-static const int kClassH[JPEG_CLASSES] = {2, 1, 2, 1, 4, 1, 1}, kClassV[JPEG_CLASSES] = {2, 1, 1, 2, 1, 4, 1};
-static bool class_two(int c)
-{
-    const ffhip_jpeg_geom g = {1, 1, c == 6 ? 1 : 3, kClassH[c], kClassV[c], {0, 1, 1}};
-    return c != 0 && strip_two(&g);
-}
-/* MCUs of a quad (4:2:0) or of a strip (the others) */
-static int class_mps(int c, bool two) { return c == 0 ? 4 : ((c == 6 || c == 1) ? 8 : 4) * (two ? 2 : 1); }
-/* the class of a picture with this geometry, output and pitch, or -1: the limits jpeg_recon_batch_impl puts on a batch of one */
-static int item_class(const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch, const int mps[JPEG_CLASSES])
-{
-    if (!geom_ok(g)) return -1;
-    const int c = jpeg_layout_class(g);
-    if (c < 0) return -1; /* the two-pass layouts are not part of the mixed path */
-    if (!d_bgra || ((uintptr_t)d_bgra & 15)) return -1;
-    const int64_t width = (int64_t)g->mcu_cols * 8 * g->h;
-    if (pitch < width * 4 || (pitch & 15) || pitch * 16 > 0x7fffffffLL) return -1;
-    const long long qpr = (g->mcu_cols + mps[c] - 1) / mps[c];
-    if (qpr > 4096 || qpr * g->mcu_rows > (1 << 20)) return -1;
-    return c;
-}
-int jpeg_item_class(const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch)
-{
-    int mps[JPEG_CLASSES];
-    for (int c = 0; c < JPEG_CLASSES; c++) mps[c] = class_mps(c, class_two(c));
-    return g ? item_class(g, d_bgra, pitch, mps) : -1;
-}
-
-static void launch_strip_items(int cls, bool two, dim3 grid, const JpegItems &t, hipStream_t st)
-{
-#define STRIP_ITEMS(H_, V_, NC_) do { \
-        if (two) hipLaunchKernelGGL((k_jpeg_fused_strip_items<H_, V_, NC_, 3, 1>), grid, dim3(WG_THREADS), 0, st, t); \
-        else hipLaunchKernelGGL((k_jpeg_fused_strip_items<H_, V_, NC_, 3, 0>), grid, dim3(WG_THREADS), 0, st, t); \
-    } while (0)
-    switch (cls) {
-    case 1: STRIP_ITEMS(1, 1, 3); break;
-    case 2: STRIP_ITEMS(2, 1, 3); break;
-    case 3: STRIP_ITEMS(1, 2, 3); break;
-    case 4: STRIP_ITEMS(4, 1, 3); break;
-    case 5: STRIP_ITEMS(1, 4, 3); break;
-    default: STRIP_ITEMS(1, 1, 1); break;
-    }
-#undef STRIP_ITEMS
-}
-static void launch_420_items(int variant, dim3 grid, const JpegItems &t, hipStream_t st)
-{
-#define ITEMS_420(Q, N) hipLaunchKernelGGL((k_jpeg420_fused_items<Q, N>), grid, dim3(WG_THREADS), 0, st, t)
-    switch (variant) {
-    case 10: ITEMS_420(1, 0); break;
-    case 11: ITEMS_420(1, 1); break;
-    case 12: ITEMS_420(1, 2); break;
-    case 13: ITEMS_420(1, 3); break;
-    case 20: ITEMS_420(2, 0); break;
-    case 21: ITEMS_420(2, 1); break;
-    case 22: ITEMS_420(2, 2); break;
-    default: ITEMS_420(2, 3); break;
-    }
-#undef ITEMS_420
+    const int c = geom_ok(g) ? jpeg_layout_class(g) : -1; /* the two-pass layouts are not part of the mixed path */
+    return c >= 0 && picture_out_ok(g, d_bgra, pitch) && picture_limits_ok(g, ch.mps[c], pitch) ? c : -1;
 }
 
 /* `slot` (0 .. FFHIP_HUFF_PARTS - 1) picks the scratch: the device entropy decoder enqueues one call per part of its batch, each with its own */
@@ -983,26 +947,14 @@ int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int
 {
     if (n < 0 || (n > 0 && !items) || slot < 0 || slot >= FFHIP_HUFF_PARTS) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    /* choices fixed once per call: the 4:2:0 variant as launch_fused reads it, strips per wave per class as launch_strip's callers do */
-    const char *e = FFHIP_ENV("FFHIP_JPEG_VARIANT");
-    const int variant = (e && e[0] >= '1' && e[0] <= '2' && e[1] >= '0' && e[1] <= '3') ? (e[0] - '0') * 10 + (e[1] - '0') : FFHIP_JPEG_DEFAULT_VARIANT;
-    bool two[JPEG_CLASSES];
-    int mps[JPEG_CLASSES], per_wave[JPEG_CLASSES]; /* MCUs of a quad / strip; quads or strips per wave */
-    for (int c = 0; c < JPEG_CLASSES; c++) {
-        two[c] = class_two(c);
-        mps[c] = class_mps(c, two[c]);
-        per_wave[c] = c == 0 ? variant / 10 : 1;
-    }
-    /* every item checked as jpeg_recon_batch_impl checks a batch of one */
+    const JpegChoices ch = jpeg_choices();
+    /* every item a picture the uniform call would take, of a fused layout */
     std::vector<int> cls((size_t)n);
     int count[JPEG_CLASSES] = {};
     for (int i = 0; i < n; i++) {
         const ffhip_jpeg_item &it = items[i];
-        const int c = item_class(&it.geom, it.d_bgra, it.pitch, mps);
-        if (c < 0) return FFHIP_EINVAL;
-        if (!it.d_coef_y || !it.d_quant || (it.geom.ncomp == 3 && (!it.d_coef_u || !it.d_coef_v))) return FFHIP_EINVAL;
-        if (((uintptr_t)it.d_coef_y & 15) || ((uintptr_t)it.d_coef_u & 15) || ((uintptr_t)it.d_coef_v & 15) || ((uintptr_t)it.d_quant & 15))
-            return FFHIP_EINVAL;
+        const int c = jpeg_item_class(ch, &it.geom, it.d_bgra, it.pitch);
+        if (c < 0 || !picture_planes_ok(&it.geom, it.d_coef_y, it.d_coef_u, it.d_coef_v, it.d_quant)) return FFHIP_EINVAL;
         cls[(size_t)i] = c;
         count[c]++;
     }
@@ -1015,19 +967,11 @@ int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int
     for (int c = 0, k = 0; c < JPEG_CLASSES; c++) { at[c] = k; k += count[c]; }
     for (int i = 0; i < n; i++) {
         const ffhip_jpeg_item &it = items[i];
-        const ffhip_jpeg_geom *g = &it.geom;
         const int c = cls[(size_t)i];
         JpegItemDesc &d = desc[(size_t)at[c]++];
         d = JpegItemDesc();
-        d.coef_y = it.d_coef_y; d.coef_u = it.d_coef_u; d.coef_v = it.d_coef_v;
-        d.quant = it.d_quant; d.bgra = it.d_bgra; d.pitch = it.pitch;
-        d.mcu_cols = g->mcu_cols; d.mcu_rows = g->mcu_rows;
-        d.quads_per_row = (g->mcu_cols + mps[c] - 1) / mps[c];
-        d.quads_per_image = d.quads_per_row * g->mcu_rows;
-        d.qpr_magic = d.quads_per_row == 1 ? 0xffffffffu : (u32)(0x100000000ULL / (unsigned)d.quads_per_row) + 1u;
-        d.qt_y = g->qt_id[0]; d.qt_u = g->qt_id[1]; d.qt_v = g->qt_id[2];
-        const int slots = (d.quads_per_image + per_wave[c] - 1) / per_wave[c];
-        d.n_wgs = (u32)((slots + WAVES_PER_WG - 1) / WAVES_PER_WG);
+        picture_fill(d, &it.geom, ch.mps[c], it.d_coef_y, it.d_coef_u, it.d_coef_v, it.d_quant, it.d_bgra, it.pitch);
+        d.n_wgs = (u32)picture_wgs(d.quads_per_image, ch.per_wave[c]);
     }
     unsigned long long total = 0;
     for (int c = 0, k = 0; c < JPEG_CLASSES; c++) {
@@ -1052,15 +996,13 @@ int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int
     u32 *d_table = (u32 *)(dev + desc_bytes);
     hipLaunchKernelGGL(k_jpeg_items_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_table);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    const int remap = jpeg_remap_mode();
     for (int c = 0; c < JPEG_CLASSES; c++)
-        for (unsigned long long b = wg_first[c]; b < wg_first[c + 1]; b += 0x7fffffffULL) { /* a launch below 2^31 workgroups, as the uniform path splits */
+        for (unsigned long long b = wg_first[c]; b < wg_first[c + 1]; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups; a class's total may not */
             const unsigned long long left = wg_first[c + 1] - b;
             const dim3 grid((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL), 1, 1);
             JpegItems t;
-            t.desc = d_desc; t.wg_item = d_table; t.wg_base = (u32)b; t.xcd_remap = remap;
-            if (c == 0) launch_420_items(variant, grid, t, st);
-            else launch_strip_items(c, two[c], grid, t, st);
+            t.desc = d_desc; t.wg_item = d_table; t.wg_base = (u32)b; t.xcd_remap = ch.remap;
+            launch_items(c, ch, grid, t, st);
             FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
         }
     return FFHIP_OK;

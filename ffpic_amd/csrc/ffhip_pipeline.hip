@@ -324,6 +324,7 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
      * or pitch ffhip_jpeg_recon_items refuses) has its code now and takes no further part ---- */
     std::vector<ffhip_jpeg_geom> geoms((size_t)n);
     std::vector<int> cls((size_t)n, -1);
+    const JpegChoices ch = jpeg_choices();
     ffhip_parallel_for(n, n_threads, [&](int i) {
         int w = 0, h = 0;
         ffhip_jpeg_geom &g = geoms[(size_t)i];
@@ -331,13 +332,13 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
         status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
         if (geom_out) geom_out[i] = g;
         if (status[i]) return;
-        cls[(size_t)i] = jpeg_item_class(&g, d_bgra[i], pitch[i]);
+        cls[(size_t)i] = jpeg_item_class(ch, &g, d_bgra[i], pitch[i]);
         if (cls[(size_t)i] < 0) status[i] = FFHIP_EINVAL;
     });
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
     int rc = FFHIP_OK;
-    for (int c = 0; c < 7 && rc == FFHIP_OK; c++) {
+    for (int c = 0; c < JPEG_CLASSES && rc == FFHIP_OK; c++) {
         std::vector<int> idx;
         for (int i = 0; i < n; i++)
             if (cls[(size_t)i] == c) idx.push_back(i);

@@ -102,6 +102,68 @@ def test_geometry_validation(L):
     assert L.ffhip_jpeg_kernel_name(C.byref(g)) == b"k_jpeg420_fused"
 
 
+A = 1 << 20     # fake, 16-byte-aligned "device" addresses: nothing is dereferenced before the device check
+
+
+def _recon(L, g, fn="ffhip_jpeg_recon_batch", n=1, y=A, u=A + 1024, v=A + 2048, q=A + 3072, qs=256, out=A + 4096, pitch=None, stride=None):
+    pitch = g.width * 4 if pitch is None else pitch
+    stride = pitch * g.height if stride is None else stride
+    args = (C.byref(g), n, y, u if g.ncomp == 3 else None, v if g.ncomp == 3 else None, q, qs, out, pitch, stride)
+    return L.ffhip_jpeg_pattern_calibrate(*args, None) if fn == "pattern" else L.ffhip_jpeg_recon_batch(*args, None, 0, None)
+
+
+# ffhip_jpeg_recon_batch / ffhip_jpeg_pattern_calibrate refuse geometry, NULL, alignment, pitch and stride in front of the device check ...
+UNIFORM_EINVAL = {
+    "luma plane misaligned": dict(y=A + 8),
+    "chroma plane misaligned": dict(v=A + 2048 + 2),
+    "output misaligned": dict(out=A + 4096 + 4),
+    "quantiser misaligned": dict(q=A + 3072 + 8),
+    "quant_stride 255: below one picture's tables": dict(qs=255),
+    "quant_stride 8: below one picture's tables": dict(qs=8),
+    "quant_stride 260: tables off 16 bytes": dict(qs=260),
+    "luma plane NULL": dict(y=None),
+    "chroma plane NULL": dict(u=None),
+    "pitch below 4 x coded width": dict(pitch=5 * 64 - 16),
+    "pitch off 16": dict(pitch=5 * 64 + 4),
+    "stride off 16": dict(n=2, stride=5 * 64 * 48 + 8),
+    "stride below pitch x coded height": dict(n=2, stride=5 * 64 * 48 - 16),
+    "negative count": dict(n=-1),
+}
+# ... and the kernels' unit limits, the pattern call's refusal of two-pass layouts and the workspace behind it
+UNIFORM_BEHIND_DEVICE_CHECK = {
+    "more than 4096 quads per row": dict(g=(4 * 4096 + 1, 1)),
+    "more than 4096 strips per row": dict(g=(16 * 4096 + 1, 1, 3, 1, 1)),
+    "more than 2^20 quads per image": dict(g=(4, (1 << 20) + 1)),
+    "pitch x 16 at 2^31": dict(pitch=1 << 27),
+    "pattern call on a two-pass layout": dict(g=(5, 3, 3, 3, 1), fn="pattern"),
+    "pattern call on grey with four blocks": dict(g=(5, 3, 1, 2, 2), fn="pattern"),
+    "two-pass layout without a workspace": dict(g=(5, 3, 3, 3, 1)),
+    "well-formed 4:2:0": dict(),
+    "well-formed grey": dict(g=(5, 3, 1, 1, 1)),
+    "quant_stride 0: one set of tables": dict(n=2, qs=0),
+}
+
+
+@pytest.mark.parametrize("why", list(UNIFORM_EINVAL))
+def test_uniform_jpeg_call_refusals_in_front_of_the_device_check(L, why):
+    for fn in ("ffhip_jpeg_recon_batch", "pattern"):
+        for geom in ((5, 3), (5, 3, 3, 1, 2)):
+            kw = dict(UNIFORM_EINVAL[why])
+            if "pitch" in kw or "stride" in kw:                       # written for a width of 40 x 8 pixels and 48 rows
+                geom = (5, 3)
+            assert _recon(L, capi.jpeg_geom(*geom), fn=fn, **kw) == capi.FFHIP_EINVAL, (why, fn, geom)
+
+
+@pytest.mark.parametrize("why", list(UNIFORM_BEHIND_DEVICE_CHECK))
+def test_uniform_jpeg_call_reaches_the_device_check_first(L, why):
+    """what the uniform call refuses only BEHIND its device check answers FFHIP_ENODEV on a machine without a GPU, like a well-formed call"""
+    if L.ffhip_device_count() > 0:
+        pytest.skip("a GPU is present; covered by the -m gpu tests")
+    kw = dict(UNIFORM_BEHIND_DEVICE_CHECK[why])
+    g = capi.jpeg_geom(*kw.pop("g", (5, 3)))
+    assert _recon(L, g, **kw) == capi.FFHIP_ENODEV, why
+
+
 def test_product_never_touches_the_oracle():
     """The product tree must not import, link or reference the CPU checker."""
     pkg = os.path.join(ROOT, "ffpic_amd")

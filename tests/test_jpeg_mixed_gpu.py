@@ -112,18 +112,16 @@ def _upload(a):
     return ops.DeviceBuffer(host=np.ascontiguousarray(a))
 
 
-def test_recon_items_share_one_allocation_and_touch_nothing_else():
-    L = capi.require_device()
-    rng = np.random.default_rng(5)
-    q = synth.quant_tables()
-    specs = [("420", 7, 3), ("444", 1, 1), ("422", 9, 2), ("440", 3, 5), ("h4v1", 5, 2), ("h1v4", 2, 2), ("grey", 17, 3),
-             ("420", 1, 1), ("420", 40, 2), ("444", 33, 1), ("grey", 1, 4), ("422", 4, 1), ("420", 5, 4)]
+def build_items(L, specs, rng, q, adversarial=True):
+    """the pictures of specs = [(layout, mcu_cols, mcu_rows)] as items of one call: synthetic planes of their own, one quantiser set, and ONE output
+    allocation filled with 0xA5 that holds every picture at an arbitrary 16-byte offset, with the reference's pitch, a ragged one or the recommended
+    one in turn.  Returns (items, places, dout, total, keep): places[k] = (geom, offset, pitch, (cy, cu, cv)); keep holds the device planes alive"""
     keep, items, places = [], [], []
     total = 0
     for k, (lay, mc, mr) in enumerate(specs):
         ncomp, h, v = LAYOUTS[lay]
         geom = capi.jpeg_geom(mc, mr, ncomp, h, v)
-        if k % 3 == 2:      # full-range adversarial levels
+        if adversarial and k % 3 == 2:      # full-range adversarial levels
             cy = synth.adversarial_blocks(rng, geom.y_blocks).reshape(-1)
             cu = synth.adversarial_blocks(rng, geom.c_blocks).reshape(-1) if ncomp == 3 else None
             cv = synth.adversarial_blocks(rng, geom.c_blocks).reshape(-1) if ncomp == 3 else None
@@ -141,6 +139,7 @@ def test_recon_items_share_one_allocation_and_touch_nothing_else():
     sentinel = np.full(total, 0xA5, np.uint8)
     dout = _upload(sentinel)
     dq = _upload(q)
+    keep.append(dq)
     for geom, off, pitch, (cy, cu, cv) in places:
         by, bu, bv = _upload(cy), _upload(cu) if cu is not None else None, _upload(cv) if cv is not None else None
         keep += [by, bu, bv]
@@ -149,6 +148,16 @@ def test_recon_items_share_one_allocation_and_touch_nothing_else():
         it.d_coef_y, it.d_coef_u, it.d_coef_v = by.ptr, bu.ptr if bu else None, bv.ptr if bv else None
         it.d_quant, it.d_bgra, it.pitch = dq.ptr, dout.ptr + off, pitch
         items.append(it)
+    return items, places, dout, total, keep
+
+
+def test_recon_items_share_one_allocation_and_touch_nothing_else():
+    L = capi.require_device()
+    rng = np.random.default_rng(5)
+    q = synth.quant_tables()
+    specs = [("420", 7, 3), ("444", 1, 1), ("422", 9, 2), ("440", 3, 5), ("h4v1", 5, 2), ("h1v4", 2, 2), ("grey", 17, 3),
+             ("420", 1, 1), ("420", 40, 2), ("444", 33, 1), ("grey", 1, 4), ("422", 4, 1), ("420", 5, 4)]
+    items, places, dout, total, keep = build_items(L, specs, rng, q)
     ops.jpeg_recon_items(items)
     capi.check(L.ffhip_stream_sync(None))
     got = dout.to_host((total,), np.uint8)

@@ -42,6 +42,44 @@ def test_jpeg_launch_shapes(env, switch):
         assert np.array_equal(gpu_recon(geom, n, cy, cu, cv, q), exp), (env, cols, rows, n)
 
 
+def _mcus_per_unit(layout, strips):
+    """MCUs one wave's unit holds: a quad of 4:2:0 is 4 MCUs; a strip is 8 MCUs of 4:4:4 / grey and 4 of 4:2:2 / 4:4:0, and a wave takes two strips' worth
+    of the three colour layouts by default, of grey too with FFHIP_JPEG_STRIPS=2, one with =1; h4v1 / h1v4 always have 4"""
+    if layout in ("420", "h4v1", "h1v4"):
+        return 4
+    two = strips == "2" or (strips is None and layout != "grey")
+    return (8 if layout in ("444", "grey") else 4) * (2 if two else 1)
+
+
+@pytest.mark.parametrize("strips", [None, "1", "2"])
+@pytest.mark.parametrize("variant", [None, "21"])
+def test_jpeg_items_under_the_switches_that_pick_their_kernels(variant, strips, switch):
+    """ffhip_jpeg_recon_items under FFHIP_JPEG_VARIANT / FFHIP_JPEG_STRIPS: one call with, per layout, pictures whose MCU row leaves a unit (m MCUs under the
+    switch) short by one, whole, over by one and two whole plus one, and a single MCU -- one and three MCU rows each.  Every item equals
+    ffhip_jpeg_recon_batch of the picture alone under the same switch, and the oracle"""
+    from test_jpeg_mixed_gpu import LAYOUTS, build_items
+    L = capi.require_device()
+    switch(**{k: v for k, v in (("FFHIP_JPEG_VARIANT", variant), ("FFHIP_JPEG_STRIPS", strips)) if v is not None})
+    specs = []
+    for lay in LAYOUTS:
+        m = _mcus_per_unit(lay, strips)
+        specs += [(lay, mc, mr) for mc in sorted({1, m - 1, m, m + 1, 2 * m + 1} - {0}) for mr in (1, 3)]
+    q = synth.quant_tables()
+    items, places, dout, total, keep = build_items(L, specs, np.random.default_rng(11), q, adversarial=False)
+    ops.jpeg_recon_items(items)
+    capi.check(L.ffhip_stream_sync(None))
+    got = dout.to_host((total,), np.uint8)
+    for spec, it, (geom, off, pitch, (cy, cu, cv)) in zip(specs, items, places):
+        W, H = geom.width, geom.height
+        rows = np.lib.stride_tricks.as_strided(got[off:], shape=(H, W * 4), strides=(pitch, 1))
+        one = ops.DeviceBuffer(nbytes=pitch * H)
+        ops.jpeg_recon_batch(geom, 1, it.d_coef_y, it.d_coef_u, it.d_coef_v, it.d_quant, 0, one.ptr, pitch, pitch * H)
+        capi.check(L.ffhip_stream_sync(None))
+        assert np.array_equal(rows, one.to_host((H, pitch), np.uint8)[:, :W * 4]), (variant, strips, spec, "batch of one")
+        exp = O.oracle_jpeg_recon(O.make_geom(geom.mcu_cols, geom.mcu_rows, geom.ncomp, geom.h, geom.v), cy, cu, cv, q, n_images=1)
+        assert np.array_equal(rows.reshape(H, W, 4), exp.reshape(H, W, 4)), (variant, strips, spec, "oracle")
+
+
 @pytest.mark.parametrize("strips", ["1", "2"])
 @pytest.mark.parametrize("nc,h,v", [(3, 1, 1), (3, 2, 1), (3, 1, 2), (1, 1, 1), (3, 4, 1), (3, 1, 4)])
 def test_jpeg_strips_per_wave(nc, h, v, strips, switch):
