@@ -41,6 +41,7 @@ def _alone(data):
 
 
 def _writer_file(rng, w, h, layout, restart=0, q=None):
+    """-> (the file's bytes, the coefficient planes it was written from)"""
     ncomp, hh, vv = LAYOUTS[layout]
     mc, mr = -(-w // (8 * hh)), -(-h // (8 * vv))
     quant = synth.quant_tables() if q is None else q
@@ -49,7 +50,7 @@ def _writer_file(rng, w, h, layout, restart=0, q=None):
         coef += [synth._blocks(rng, mc * mr, quant[1]), synth._blocks(rng, mc * mr, quant[1])]
     else:
         coef += [None, None]
-    return jpeg_writer.encode(w, h, hh, vv, coef, quant, restart=restart)
+    return jpeg_writer.encode(w, h, hh, vv, coef, quant, restart=restart), coef
 
 
 def _pil_file(rng, w, h, sub=2, mode="RGB", q=85):
@@ -83,9 +84,11 @@ def test_all_fixture_files_in_one_call_equal_the_reference_decode(golden, entrop
 # ---------------------------------------------------------------------------------------------------- 2. seeded random batches
 @pytest.mark.parametrize("seed", [0, 1, 2])
 def test_random_mixed_batches_equal_single_file_decodes(entropy_env, seed):
+    """every picture of the batch equals the same file decoded alone -- and, for the files written here, the oracle's reconstruction of the coefficients
+    they were written from (the library against the answer, not only against itself)"""
     entropy_env(None)
     rng = np.random.default_rng(100 + seed)
-    files = []
+    files, written = [], []
     for k in range(18):
         layout = list(LAYOUTS)[k % len(LAYOUTS)]
         w, h = int(rng.integers(1, 300)), int(rng.integers(1, 200))
@@ -93,18 +96,27 @@ def test_random_mixed_batches_equal_single_file_decodes(entropy_env, seed):
             w, h = int(rng.integers(1, 9)), int(rng.integers(1, 9))           # one MCU
         if k % 6 == 2:
             w = 8 * LAYOUTS[layout][1]                                        # one strip wide
-        files.append(_writer_file(rng, w, h, layout, restart=int(rng.integers(0, 3)) * int(rng.integers(1, 7))))
-    files.append(_writer_file(rng, 4200, 24, "444", restart=0))              # wider than 4 096
-    files.append(_writer_file(rng, 4104, 17, "420", restart=5))
+        written.append(_writer_file(rng, w, h, layout, restart=int(rng.integers(0, 3)) * int(rng.integers(1, 7))))
+    written.append(_writer_file(rng, 4200, 24, "444", restart=0))            # wider than 4 096
+    written.append(_writer_file(rng, 4104, 17, "420", restart=5))
+    files = [d for d, _ in written]
+    coefs = [c for _, c in written]
     files.append(_pil_file(rng, 333, 211, sub=2))
     files.append(_pil_file(rng, 127, 65, sub=0))
     files.append(_pil_file(rng, 250, 99, sub=1))
     files.append(_pil_file(rng, 97, 203, mode="L"))
+    coefs += [None] * 4
     order = rng.permutation(len(files))
     files = [files[i] for i in order]
+    coefs = [coefs[i] for i in order]
     geoms, images, _ = ops.jpeg_decode_files_mixed_device(files, n_threads=4)
-    for d, img in zip(files, images):
+    q = synth.quant_tables()
+    for d, img, coef, g in zip(files, images, coefs, geoms):
         assert np.array_equal(img, _alone(d))
+        if coef is not None:
+            cy, cu, cv = [np.ascontiguousarray(c.reshape(-1)) if c is not None else None for c in coef]
+            exp = O.oracle_jpeg_recon(O.make_geom(g.mcu_cols, g.mcu_rows, g.ncomp, g.h, g.v), cy, cu, cv, q)[0]
+            assert np.array_equal(img, exp[:img.shape[0], :img.shape[1]])
 
 
 # ---------------------------------------------------------------------------------------------------- 3. items on synthetic planes
@@ -184,8 +196,8 @@ def test_recon_items_share_one_allocation_and_touch_nothing_else():
 def test_bad_file_in_the_middle_fails_alone(entropy_env, bad):
     entropy_env(None)
     rng = np.random.default_rng(11)
-    good = [_writer_file(rng, 120, 72, "420", restart=3), _pil_file(rng, 200, 130, sub=2), _writer_file(rng, 64, 40, "444"),
-            _pil_file(rng, 77, 51, mode="L"), _writer_file(rng, 90, 33, "422", restart=2), _pil_file(rng, 310, 180, sub=2)]
+    good = [_writer_file(rng, 120, 72, "420", restart=3)[0], _pil_file(rng, 200, 130, sub=2), _writer_file(rng, 64, 40, "444")[0],
+            _pil_file(rng, 77, 51, mode="L"), _writer_file(rng, 90, 33, "422", restart=2)[0], _pil_file(rng, 310, 180, sub=2)]
     if bad == "truncated":
         d = _pil_file(rng, 300, 200, sub=2)
         b = d[:len(d) // 2]
@@ -246,7 +258,7 @@ def test_4096_thumbnails_of_64_sizes(entropy_env):
     rng = np.random.default_rng(21)
     sizes = [(int(rng.integers(24, 160)), int(rng.integers(24, 160))) for _ in range(64)]
     layouts = ["420", "444", "422", "grey"]
-    protos = [_writer_file(rng, w, h, layouts[k % 4], restart=(k % 3) * 2) for k, (w, h) in enumerate(sizes)]
+    protos = [_writer_file(rng, w, h, layouts[k % 4], restart=(k % 3) * 2)[0] for k, (w, h) in enumerate(sizes)]
     alone = [_alone(p) for p in protos]
     pick = rng.integers(0, 64, 4096)
     files = [protos[int(i)] for i in pick]
@@ -261,7 +273,7 @@ def test_two_threads_on_two_streams():
     rng = np.random.default_rng(31)
     batches = []
     for t in range(2):
-        fs = [_writer_file(rng, int(rng.integers(8, 400)), int(rng.integers(8, 300)), list(LAYOUTS)[(k + t) % 7], restart=k % 4)
+        fs = [_writer_file(rng, int(rng.integers(8, 400)), int(rng.integers(8, 300)), list(LAYOUTS)[(k + t) % 7], restart=k % 4)[0]
               for k in range(24)]
         fs += [_pil_file(rng, 260 + 40 * t, 170, sub=2), _pil_file(rng, 150, 90 + t, mode="L")]
         batches.append(fs)
