@@ -27,6 +27,7 @@ EXPORTS = [
     "ffhip_bgra_checksum", "ffhip_vp8_filter_params", "ffhip_vp8_predict_loopfilter", "ffhip_reload_env", "ffhip_env_value_test", "ffhip_vp8_decode_frames", "ffhip_bgra_layout",
     "ffhip_jpeg_recon_items", "ffhip_jpeg_decode_files_mixed_device", "ffhip_vp8_decode_items",
     "ffhip_vp8_dequant_factors", "ffhip_webp_probe", "ffhip_webp_parse", "ffhip_webp_parse_batch", "ffhip_webp_parse_device", "ffhip_webp_decode_files_device", "ffhip_debug_webp_last_parts",
+    "ffhip_bgra_to_tensor_items", "ffhip_jpeg_decode_files_tensor", "ffhip_webp_decode_files_tensor",
 ]
 
 
@@ -117,6 +118,30 @@ class Vp8Item(C.Structure):
                 ("d_levels", C.c_void_p), ("d_mbinfo", C.c_void_p), ("quant", (C.c_uint16 * 8) * 4), ("d_residual", C.c_void_p),
                 ("d_resmap", C.c_void_p), ("filter_type", C.c_int32), ("filters", C.c_uint8 * 24), ("d_bgra", C.c_void_p),
                 ("pitch", C.c_int64)]
+
+
+FFHIP_TENSOR_U8, FFHIP_TENSOR_F16, FFHIP_TENSOR_F32 = 0, 1, 2
+
+
+class TensorFormat(C.Structure):
+    """ffhip_tensor_format"""
+    _fields_ = [("dtype", C.c_int32), ("bgr", C.c_int32), ("planar", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class TensorItem(C.Structure):
+    """ffhip_tensor_item: one picture of an ffhip_bgra_to_tensor_items call (device pointers; strides in elements)"""
+    _fields_ = [("d_bgra", C.c_void_p), ("pitch", C.c_int64), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("d_out", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64)]
+
+
+class TensorOut(C.Structure):
+    """ffhip_tensor_out"""
+    _fields_ = [("d_out", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64)]
+
+
+class Rect(C.Structure):
+    """ffhip_rect"""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 
 
 def jpeg_geom(mcu_cols, mcu_rows, ncomp=3, h=2, v=2, qt_id=(0, 1, 1)):
@@ -255,6 +280,11 @@ def lib():
     L.ffhip_bgra_checksum.argtypes = [vp, i64, i64, ci, ci, ci, vp, vp]
     L.ffhip_vp8_decode_frames.argtypes = [ci, ci, ci, vp, vp, vp, i64, vp, ci, vp, vp, ci, i64, vp, vp, vp, i64, i64, vp]
     L.ffhip_bgra_layout.argtypes = [C.POINTER(JpegGeom), C.POINTER(i64), C.POINTER(i64)]
+    L.ffhip_bgra_to_tensor_items.argtypes = [C.POINTER(TensorItem), ci, C.POINTER(TensorFormat), vp]
+    L.ffhip_jpeg_decode_files_tensor.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                 C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_webp_decode_files_tensor.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                 C.POINTER(WebpInfo), vp, vp]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

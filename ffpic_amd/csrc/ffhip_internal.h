@@ -112,6 +112,8 @@ enum FfhipScratchKind {
     SCRATCH_JPEG_ITEMS = 40,       /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items' records and per-workgroup table, pinned records */
     SCRATCH_WEBP = 60,             /* .. + 1: ffhip_webp_decode_files_device: a part's arrays, descriptors and file bytes (and their pinned copy); the host threads' pinned arrays */
     SCRATCH_VP8_ITEMS = 50,        /* .. + 2: ffhip_vp8_decode_items' tables (and their pinned copy), the levels items' residual, the line slots */
+    SCRATCH_TENSOR_ITEMS = 70,     /* ffhip_bgra_to_tensor_items' records and per-workgroup table, pinned records */
+    SCRATCH_TENSOR_BGRA = 71,      /* ffhip_*_decode_files_tensor: a part's BGRA pictures */
 };
 
 /* ffhip_vp8_decode_items (ffhip_vp8_frame.hip): its levels items' residual stage (ffhip_vp8.hip) and its device mode check

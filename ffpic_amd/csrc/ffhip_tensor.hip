@@ -1,0 +1,267 @@
+/*
+ * ffhip_tensor.hip -- the last stage between the decoders and a program that reads tensors: BGRA pictures as the decode calls leave
+ * them -> RGB / BGR, CHW / HWC, uint8 / float16 / float32, cropped to a rectangle, in one launch for a whole mixed batch
+ * (ffhip_bgra_to_tensor_items), and the file calls built on it (ffhip_jpeg_decode_files_tensor, ffhip_webp_decode_files_tensor).
+ * The layout of the work is described in ffhip_tensor_body.h.
+ */
+#include "ffhip_internal.h"
+#include "ffhip_tensor_body.h"
+
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+namespace {
+
+struct TensorArgs {
+    const TensorItemDesc *desc;
+    const u32 *wg_item; /* per workgroup of the call: its item */
+    u32 wg_base;        /* the launch's first workgroup */
+    TensorScale s;
+};
+
+/* one workgroup per item: the item's index over its range of the per-workgroup table */
+__global__ __launch_bounds__(256) void k_tensor_items_table(const TensorItemDesc *desc, u32 *wg_item)
+{
+    const u32 item = blockIdx.x, first = desc[item].first_wg, n = desc[item].n_wgs;
+    for (u32 k = threadIdx.x; k < n; k += 256) wg_item[first + k] = item;
+}
+
+/* A workgroup takes FFHIP_TENSOR_WG_UNITS consecutive units of one item, lane l the units l, l + 256, ...: a wave's 64 lanes store 64
+ * consecutive 16-byte blocks of a run (or of the runs that follow each other in a narrow picture). */
+template <int DT, bool PLANAR, bool BGR> __global__ __launch_bounds__(FFHIP_TENSOR_WG_THREADS) void k_bgra_to_tensor(TensorArgs a)
+{
+    const u32 wg = a.wg_base + blockIdx.x;
+    const u32 item = __builtin_amdgcn_readfirstlane(a.wg_item[wg]);
+    const TensorItemDesc d = a.desc[item];
+    const u32 base = (wg - d.first_wg) * FFHIP_TENSOR_WG_UNITS + threadIdx.x;
+#pragma unroll 2
+    for (int i = 0; i < FFHIP_TENSOR_UNITS_PER_LANE; i++) {
+        const u32 t = base + (u32)i * FFHIP_TENSOR_WG_THREADS;
+        if (t >= d.total) break;
+        tensor_unit<DT, PLANAR, BGR>(d, a.s, t);
+    }
+}
+
+typedef void (*TensorKernel)(TensorArgs);
+template <int DT> TensorKernel tensor_kernel_of(bool planar, bool bgr)
+{
+    return planar ? (bgr ? k_bgra_to_tensor<DT, true, true> : k_bgra_to_tensor<DT, true, false>)
+                  : (bgr ? k_bgra_to_tensor<DT, false, true> : k_bgra_to_tensor<DT, false, false>);
+}
+TensorKernel tensor_kernel(const ffhip_tensor_format *f)
+{
+    const bool planar = f->planar != 0, bgr = f->bgr != 0;
+    return f->dtype == FFHIP_TENSOR_U8 ? tensor_kernel_of<FFHIP_TENSOR_U8>(planar, bgr)
+         : f->dtype == FFHIP_TENSOR_F16 ? tensor_kernel_of<FFHIP_TENSOR_F16>(planar, bgr)
+                                        : tensor_kernel_of<FFHIP_TENSOR_F32>(planar, bgr);
+}
+
+int tensor_elem_size(int dtype) { return dtype == FFHIP_TENSOR_U8 ? 1 : (dtype == FFHIP_TENSOR_F16 ? 2 : 4); }
+
+bool tensor_format_ok(const ffhip_tensor_format *f)
+{
+    if (!f || f->dtype < FFHIP_TENSOR_U8 || f->dtype > FFHIP_TENSOR_F32) return false;
+    for (int c = 0; c < 3; c++) {
+        if (!isfinite(f->scale[c]) || !isfinite(f->bias[c])) return false;
+        if (f->dtype == FFHIP_TENSOR_U8 && (f->scale[c] != 1.0f || f->bias[c] != 0.0f)) return false;
+    }
+    return true;
+}
+
+/* an item the call takes under format f; fills its record (first_wg aside) */
+bool tensor_item_desc(const ffhip_tensor_item &it, const ffhip_tensor_format *f, TensorItemDesc *out)
+{
+    const int es = tensor_elem_size(f->dtype);
+    if (it.width < 1 || it.height < 1 || it.x0 < 0 || it.y0 < 0) return false;
+    if (!it.d_bgra || ((uintptr_t)it.d_bgra & 3) || it.pitch < 4 || (it.pitch & 3)) return false;
+    /* source offsets stay within 31 bits, as the decode calls' own pictures do (pitch x rows < 2^31), and the rectangle within the pitch */
+    if (4LL * ((long long)it.x0 + it.width) > it.pitch || ((long long)it.y0 + it.height) * it.pitch > 0x7fffffffLL) return false;
+    if (!it.d_out || ((uintptr_t)it.d_out & (uintptr_t)(es - 1))) return false;
+    const long long run_len = f->planar ? it.width : 3LL * it.width;
+    if (it.row_stride < run_len) return false;
+    __int128 span = (__int128)it.row_stride * (it.height - 1) + run_len; /* elements from the first to behind the last of a plane (HWC: of the tensor) */
+    if (f->planar) {
+        if ((__int128)it.plane_stride < span) return false;
+        span += (__int128)it.plane_stride * 2;
+    }
+    if (span * es > ((__int128)1 << 62)) return false; /* element offsets are 64-bit in the kernel */
+    const long long runs = (f->planar ? 3LL : 1LL) * it.height;
+    const long long units = (run_len * es + 15) / 16 + 1;
+    if (runs * units > 0xffffffffLL) return false; /* a unit's index is 32-bit */
+    memset(out, 0, sizeof(*out));
+    out->src = it.d_bgra + (long long)it.y0 * it.pitch + 4LL * it.x0;
+    out->dst = (uint8_t *)it.d_out;
+    out->pitch = it.pitch;
+    out->row_stride = it.row_stride;
+    out->plane_stride = f->planar ? it.plane_stride : 0;
+    out->width = it.width;
+    out->height = it.height;
+    out->units = (u32)units;
+    out->total = (u32)(runs * units);
+    out->n_wgs = (u32)((runs * units + FFHIP_TENSOR_WG_UNITS - 1) / FFHIP_TENSOR_WG_UNITS);
+    return true;
+}
+
+} // namespace
+
+extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, void *stream)
+{
+    if (n < 0 || (n > 0 && !items) || !tensor_format_ok(fmt)) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    /* the records, every item's workgroups behind those of the items before it */
+    std::vector<TensorItemDesc> desc((size_t)n);
+    unsigned long long total = 0;
+    for (int i = 0; i < n; i++) {
+        if (!tensor_item_desc(items[i], fmt, &desc[(size_t)i])) return FFHIP_EINVAL;
+        desc[(size_t)i].first_wg = (u32)total;
+        total += desc[(size_t)i].n_wgs;
+    }
+    if (total > 0xffffffffULL) return FFHIP_EINVAL; /* the table's entries are 32-bit workgroup indices */
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    hipStream_t st = (hipStream_t)stream;
+    /* device scratch: the records, then the per-workgroup table; pinned staging for the records.  Both per stream */
+    const size_t desc_bytes = (size_t)n * sizeof(TensorItemDesc);
+    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_TENSOR_ITEMS, stream, desc_bytes / 4 + (size_t)total + 16);
+    if (!dev) return FFHIP_ENOMEM;
+    uint8_t *pin = ffhip_pinned_staging(SCRATCH_TENSOR_ITEMS, stream, desc_bytes);
+    if (!pin) return FFHIP_ENOMEM;
+    memcpy(pin, desc.data(), desc_bytes);
+    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
+    if (ffhip_pinned_staged(SCRATCH_TENSOR_ITEMS, stream) != FFHIP_OK) return FFHIP_EIO;
+    const TensorItemDesc *d_desc = (const TensorItemDesc *)dev;
+    u32 *d_table = (u32 *)(dev + desc_bytes);
+    hipLaunchKernelGGL(k_tensor_items_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_table);
+    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    const TensorKernel kernel = tensor_kernel(fmt);
+    for (unsigned long long b = 0; b < total; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups */
+        const unsigned long long left = total - b;
+        TensorArgs a;
+        a.desc = d_desc; a.wg_item = d_table; a.wg_base = (u32)b;
+        for (int c = 0; c < 3; c++) { a.s.scale[c] = fmt->scale[c]; a.s.bias[c] = fmt->bias[c]; }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL)), dim3(FFHIP_TENSOR_WG_THREADS), 0, st, a);
+        FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    }
+    return FFHIP_OK;
+}
+
+/* ---- files in, tensors out ---- */
+namespace {
+
+struct TensorPicture { int coded_w, coded_h, width, height; }; /* what a decode call writes; what the file displays (inside it) */
+/* decodes files [first, first + cnt) into d_bgra[k] with pitch[k]: the call underneath, its per-file codes into status + first */
+typedef std::function<int(int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch)> TensorDecode;
+
+size_t tensor_part_budget()
+{
+    const char *v = FFHIP_ENV("FFHIP_TENSOR_PART_BYTES");
+    const long long b = v ? atoll(v) : 0;
+    return b > 0 ? (size_t)b : (size_t)1 << 30;
+}
+
+/* pic[i] is valid where status[i] == 0 (the probe's verdict) */
+int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs, const ffhip_rect *roi, const std::vector<TensorPicture> &pic,
+                     int *status, void *stream, const TensorDecode &decode)
+{
+    /* the items, with a stand-in for the picture's address: everything about rectangle and output is checked before anything is enqueued */
+    std::vector<ffhip_tensor_item> item((size_t)n);
+    std::vector<int> mine((size_t)n, FFHIP_OK); /* the code this call gives a file the decoder takes */
+    for (int i = 0; i < n; i++) {
+        if (status[i]) continue;
+        const TensorPicture &p = pic[(size_t)i];
+        const ffhip_rect r = roi ? roi[i] : ffhip_rect{0, 0, p.width, p.height};
+        ffhip_tensor_item &it = item[(size_t)i];
+        it.d_bgra = (const uint8_t *)(uintptr_t)256; it.pitch = 4LL * p.coded_w;
+        it.x0 = r.x0; it.y0 = r.y0; it.width = r.width; it.height = r.height;
+        it.d_out = outs[i].d_out; it.row_stride = outs[i].row_stride; it.plane_stride = outs[i].plane_stride;
+        TensorItemDesc d;
+        if (r.x0 < 0 || r.y0 < 0 || r.width < 1 || r.height < 1 || (long long)r.x0 + r.width > p.width || (long long)r.y0 + r.height > p.height ||
+            !tensor_item_desc(it, fmt, &d))
+            mine[(size_t)i] = FFHIP_EINVAL;
+    }
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    const size_t budget = tensor_part_budget();
+    auto bytes_of = [&](int i) { return status[i] ? (size_t)0 : ((size_t)4 * pic[(size_t)i].coded_w * pic[(size_t)i].coded_h + 255) & ~(size_t)255; };
+    for (int first = 0; first < n;) {
+        /* a part: files while their pictures fit the budget; a picture larger than the budget is a part of its own */
+        int cnt = 0;
+        size_t bytes = 0;
+        while (first + cnt < n && (cnt == 0 || bytes + bytes_of(first + cnt) <= budget)) bytes += bytes_of(first + cnt++);
+        uint8_t *base = (uint8_t *)ffhip_scratch(SCRATCH_TENSOR_BGRA, stream, bytes / 4 + 64);
+        if (!base) return FFHIP_ENOMEM;
+        std::vector<uint8_t *> d_bgra((size_t)cnt);
+        std::vector<int64_t> pitch((size_t)cnt);
+        size_t at = 0;
+        for (int k = 0; k < cnt; k++) { /* (a file the probe refused: the decoder refuses it again before it looks at its output) */
+            d_bgra[(size_t)k] = base + at;
+            pitch[(size_t)k] = status[first + k] ? 0 : 4LL * pic[(size_t)(first + k)].coded_w;
+            at += bytes_of(first + k);
+        }
+        const int rc = decode(first, cnt, d_bgra.data(), pitch.data());
+        if (rc) { /* a file's code, or the call's own failure */
+            bool a_files = false;
+            for (int k = 0; k < cnt; k++) a_files = a_files || status[first + k] == rc;
+            if (!a_files) return rc;
+        }
+        std::vector<ffhip_tensor_item> good;
+        for (int k = 0; k < cnt; k++) {
+            const int i = first + k;
+            if (status[i]) continue;
+            if (mine[(size_t)i]) { status[i] = mine[(size_t)i]; continue; }
+            item[(size_t)i].d_bgra = d_bgra[(size_t)k];
+            good.push_back(item[(size_t)i]);
+        }
+        const int src = ffhip_bgra_to_tensor_items(good.data(), (int)good.size(), fmt, stream);
+        if (src) return src;
+        FFHIP_CHECK(hipStreamSynchronize((hipStream_t)stream), FFHIP_EIO); /* the next part decodes into the same scratch */
+        first += cnt;
+    }
+    for (int i = 0; i < n; i++)
+        if (status[i]) return status[i];
+    return FFHIP_OK;
+}
+
+bool tensor_files_args_ok(const uint8_t *const *files, const size_t *lens, int n, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs, const int *status)
+{
+    return n >= 0 && tensor_format_ok(fmt) && (n == 0 || (files && lens && outs && status));
+}
+
+} // namespace
+
+extern "C" int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                              const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+{
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status)) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    std::vector<TensorPicture> pic((size_t)n);
+    ffhip_parallel_for(n, n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads), [&](int i) {
+        ffhip_jpeg_geom g;
+        memset(&g, 0, sizeof(g));
+        int w = 0, h = 0;
+        status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
+        if (geom_out) geom_out[i] = g;
+        pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h};
+    });
+    return tensor_files_run(n, fmt, outs, roi, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+        return ffhip_jpeg_decode_files_mixed_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, geom_out ? geom_out + first : nullptr,
+                                                    status + first, stream);
+    });
+}
+
+extern "C" int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                              const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_webp_info *info_out, int *status, void *stream)
+{
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status)) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    std::vector<TensorPicture> pic((size_t)n);
+    for (int i = 0; i < n; i++) {
+        int w = 0, h = 0, c = 0, r = 0;
+        status[i] = files[i] && lens[i] ? ffhip_webp_probe(files[i], lens[i], &w, &h, &c, &r) : FFHIP_EINVAL;
+        /* the loader's size is the container's word (ffhip_webp_info): what of it the decoded picture holds */
+        pic[(size_t)i] = TensorPicture{16 * c, 16 * r, w < 16 * c ? w : 16 * c, h < 16 * r ? h : 16 * r};
+    }
+    return tensor_files_run(n, fmt, outs, roi, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+        return ffhip_webp_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
+                                              status + first, stream);
+    });
+}

@@ -1,0 +1,149 @@
+"""Decoded pictures as torch tensors on the device (include/ffpic_hip.h, "decoded pictures into tensors"): files in, RGB / BGR,
+CHW / HWC, uint8 / float16 / float32 tensors out, nothing but the compressed bytes crossing PCIe.  torch is imported when a
+function here is called, not with the package: ffpic_amd.ops stays torch-free."""
+import ctypes as C
+
+import numpy as np
+
+from . import capi, ops
+
+_DTYPES = {"uint8": capi.FFHIP_TENSOR_U8, "float16": capi.FFHIP_TENSOR_F16, "float32": capi.FFHIP_TENSOR_F32}
+
+
+def _dtype_name(dtype):
+    name = "uint8" if dtype is None else str(np.dtype(dtype)) if not str(dtype).startswith("torch.") else str(dtype)[6:]
+    name = {"half": "float16", "float": "float32"}.get(name, name)
+    if name not in _DTYPES:
+        raise ValueError(f"dtype {dtype!r}: uint8, float16 or float32")
+    return name
+
+
+def tensor_format(dtype=None, layout="CHW", order="RGB", mean=None, std=None):
+    """capi.TensorFormat.  mean / std: per OUTPUT channel on a 0..1 scale; scale = float32(1 / (255 std)), bias = float32(-mean / std),
+    computed in doubles and rounded once.  With neither, scale 1 and bias 0: a float output holds the byte values."""
+    name = _dtype_name(dtype)
+    if layout not in ("CHW", "HWC") or order not in ("RGB", "BGR"):
+        raise ValueError("layout is 'CHW' or 'HWC', order 'RGB' or 'BGR'")
+    f = capi.TensorFormat()
+    f.dtype, f.bgr, f.planar = _DTYPES[name], int(order == "BGR"), int(layout == "CHW")
+    if mean is None and std is None:
+        scale, bias = [1.0] * 3, [0.0] * 3
+    else:
+        if name == "uint8":
+            raise ValueError("mean / std need a float dtype")
+        mean = [0.0] * 3 if mean is None else [float(m) for m in mean]
+        std = [1.0] * 3 if std is None else [float(s) for s in std]
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("mean and std have one value per channel")
+        scale, bias = [1.0 / (255.0 * s) for s in std], [-m / s for m, s in zip(mean, std)]
+    for c in range(3):
+        f.scale[c], f.bias[c] = scale[c], bias[c]      # ctypes rounds the double to float32, once
+    return f
+
+
+def bgra_to_tensors(items, fmt, stream=None):
+    """ffhip_bgra_to_tensor_items: `items` a list of capi.TensorItem (device pointers, strides in elements), `fmt` a capi.TensorFormat;
+    one launch for the whole batch.  Only enqueues on `stream` (a hipStream_t handle; None: the default stream)."""
+    L = capi.lib()
+    n = len(items)
+    arr = (capi.TensorItem * max(n, 1))(*items)
+    capi.check(L.ffhip_bgra_to_tensor_items(arr, n, C.byref(fmt), stream), "ffhip_bgra_to_tensor_items")
+
+
+def tensor_out(t, layout):
+    """capi.TensorOut of a torch tensor [3][H][W] (layout 'CHW') or [H][W][3] ('HWC') whose innermost dimension(s) are dense: a slice of a
+    batch tensor, a view with padded rows"""
+    if layout == "CHW":
+        ok, rs, ps = t.dim() == 3 and t.shape[0] == 3 and t.stride(2) == 1, t.stride(1), t.stride(0)
+    else:
+        ok, rs, ps = t.dim() == 3 and t.shape[2] == 3 and t.stride(2) == 1 and t.stride(1) == 3, t.stride(0), 0
+    if not ok:
+        raise ValueError(f"a {layout} tensor with dense pixels is needed, got shape {tuple(t.shape)} strides {t.stride()}")
+    return capi.TensorOut(t.data_ptr(), rs, ps)
+
+
+def _rois(roi, n):
+    if roi is None:
+        return None
+    if len(roi) == 4 and not hasattr(roi[0], "__len__"):
+        roi = [roi] * n
+    if len(roi) != n:
+        raise ValueError("roi: one (x0, y0, width, height), or one per file")
+    return [tuple(int(v) for v in r) for r in roi]
+
+
+def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict):
+    import torch
+    fmt = tensor_format(dtype, layout, order, mean, std)
+    tdtype = getattr(torch, _dtype_name(dtype))
+    dev = torch.cuda.current_device()
+    L = capi.require_device(dev)
+    n = len(files)
+    rois = _rois(roi, n)
+    sizes = []                                                    # (height, width) of each file's tensor; None: the probe refused it
+    for i, f in enumerate(files):
+        try:
+            w, h = probe(f)
+        except capi.FfhipError:
+            if strict or stack:
+                raise
+            sizes.append(None)
+            continue
+        sizes.append((rois[i][3], rois[i][2]) if rois else (h, w))
+    shape = (lambda h, w: (3, h, w)) if layout == "CHW" else (lambda h, w: (h, w, 3))
+    device = torch.device("cuda", dev)
+    if stack:
+        if len(set(sizes)) > 1:
+            raise ValueError(f"stack=True needs pictures of one size, got {sorted(set(sizes))}")
+        batch = torch.empty((n,) + (shape(*sizes[0]) if n else shape(0, 0)), dtype=tdtype, device=device)
+        tensors = [batch[i] for i in range(n)]
+    else:
+        tensors = [None if s is None or min(s) < 1 else torch.empty(shape(*s), dtype=tdtype, device=device) for s in sizes]
+    outs = (capi.TensorOut * max(n, 1))(*[capi.TensorOut() if t is None else tensor_out(t, layout) for t in tensors])
+    rects = (capi.Rect * max(n, 1))(*[capi.Rect(*r) for r in rois]) if rois else None
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+    status = (C.c_int * max(n, 1))()
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = call(L)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, None, status, stream)
+    status = list(status)[:n]
+    if strict or stack or (rc != 0 and rc not in status):         # a file's code, or the call's own failure
+        capi.check(rc, what)
+    if stack:
+        return batch
+    tensors = [None if status[i] else tensors[i] for i in range(n)]
+    return tensors if strict else (tensors, status)
+
+
+def _jpeg_size(f):
+    _, w, h = ops.jpeg_probe(f)
+    return w, h
+
+
+def _webp_size(f):
+    w, h, c, r = ops.webp_probe(f)
+    return min(w, 16 * c), min(h, 16 * r)
+
+
+def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
+                           strict=True):
+    """ffhip_jpeg_decode_files_tensor: baseline JPEG files (list of bytes) of any geometry in one call -> torch tensors on the current
+    device, written on torch's current stream (the call synchronises it).
+      dtype    torch.uint8 (None), torch.float16 or torch.float32;  layout 'CHW' / 'HWC';  order 'RGB' / 'BGR'
+      mean/std per channel on a 0..1 scale: out = byte * float32(1 / (255 std)) + float32(-mean / std); with neither, the byte value
+      roi      None: each file's display size; (x0, y0, width, height) for all files, or a list of one per file
+      stack    one [N,3,H,W] / [N,H,W,3] tensor, the files' outputs slices of it; ValueError when the sizes differ, and every file
+               has to decode
+    Returns the list of tensors; with strict=False a failing file does not raise: its entry is None, and the per-file status codes
+    follow as a second element."""
+    return _decode_to_tensors(lambda L: L.ffhip_jpeg_decode_files_tensor, "ffhip_jpeg_decode_files_tensor", _jpeg_size, files, dtype,
+                              layout, order, mean, std, roi, stack, n_threads, strict)
+
+
+def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
+                           strict=True):
+    """ffhip_webp_decode_files_tensor: lossy WebP files; arguments and result as decode_jpeg_to_tensors.  A file's display size is the
+    probe's width x height as far as the decoded picture holds it."""
+    return _decode_to_tensors(lambda L: L.ffhip_webp_decode_files_tensor, "ffhip_webp_decode_files_tensor", _webp_size, files, dtype,
+                              layout, order, mean, std, roi, stack, n_threads, strict)

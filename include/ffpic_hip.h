@@ -763,6 +763,69 @@ int ffhip_copy_calibrate(void *d_dst, const void *d_src, size_t bytes, void *str
 int ffhip_jpeg_pattern_calibrate(const ffhip_jpeg_geom *geom, int n_images, const int16_t *d_coef_y, const int16_t *d_coef_u, const int16_t *d_coef_v,
                                  const uint16_t *d_quant, int64_t quant_stride, uint8_t *d_bgra, int64_t pitch, int64_t image_stride, void *stream);
 
+/* ---- decoded pictures into tensors (ffhip_tensor.hip) ----
+ * The decode calls leave the reference's picture: BGRA with a constant alpha byte, the coded size, a pitch.  A program on the GPU reads
+ * tensors: RGB or BGR, planar or interleaved, bytes or normalised floats, the display size or a region of it.  This is that last stage. */
+#define FFHIP_TENSOR_U8 0
+#define FFHIP_TENSOR_F16 1
+#define FFHIP_TENSOR_F32 2
+typedef struct ffhip_tensor_format {
+    int32_t dtype;  /* FFHIP_TENSOR_*                                                                                     */
+    int32_t bgr;    /* 0: channels R,G,B   non-zero: B,G,R                                                                */
+    int32_t planar; /* non-zero: [3][H][W] (CHW)   0: [H][W][3] (HWC)                                                     */
+    float scale[3]; /* per OUTPUT channel: out = (float)byte * scale[c] + bias[c], the product and the sum each rounded   */
+    float bias[3];  /* to float (the library is built with -ffp-contract=off); F16: that float converted round-to-nearest- */
+                    /* even; U8: the byte itself, scale must be 1 and bias 0.  All six finite                             */
+} ffhip_tensor_format;
+/* One picture of a batch.  All pointers are DEVICE pointers.
+ *   d_bgra, pitch      a picture as the decode calls write it: 4-byte aligned, pitch a multiple of 4
+ *   x0, y0, width,     the rectangle to take (width, height >= 1, x0, y0 >= 0); the caller keeps it inside the picture, the call checks
+ *   height             what it can: 4 (x0 + width) <= pitch, and (y0 + height) pitch < 2^31 -- the bound of the decode calls' own pictures
+ *   d_out              element 0 of the output, aligned to ONE element only (a slice of a larger tensor starts anywhere)
+ *   row_stride,        in elements.  HWC: element (y, x, c) at y row_stride + 3 x + c, row_stride >= 3 width, plane_stride unused.
+ *   plane_stride       CHW: element (c, y, x) at c plane_stride + y row_stride + x, row_stride >= width,
+ *                      plane_stride >= row_stride (height - 1) + width
+ * The alpha byte is ignored.  Only the width x height elements per channel are written: row padding, plane padding and the bytes around the
+ * output stay untouched, whatever the output's alignment (rows are cut along the DESTINATION's 16-byte blocks: whole blocks are stored as
+ * one 16-byte store, the partial block at either end of a row element by element). */
+typedef struct ffhip_tensor_item {
+    const uint8_t *d_bgra;
+    int64_t pitch;
+    int32_t x0, y0, width, height;
+    void *d_out;
+    int64_t row_stride, plane_stride;
+} ffhip_tensor_item;
+/* ONE launch for the whole batch, pictures and outputs of any sizes, all in format *fmt (the twelve combinations of dtype, planar and bgr
+ * are instances of one kernel body, chosen here).  `items` is a HOST array; every check is made before anything is enqueued
+ * (FFHIP_EINVAL -- an unknown dtype, U8 with a scale other than 1 or a bias other than 0, a scale or bias that is not finite, an item
+ * outside what its fields' lines above say --, on a machine without a device too; FFHIP_ENODEV there for good arguments).  n == 0 is
+ * FFHIP_OK.  Only enqueues on `stream`; the records and the per-workgroup table are library scratch of the stream. */
+int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, void *stream);
+
+/* Files in, tensors out.  outs[i] is file i's output (fields as in ffhip_tensor_item); roi[i] the rectangle of its DISPLAY picture to
+ * deliver, roi == NULL the whole of it: width x height as ffhip_jpeg_probe reports them, ffhip_webp_info.width x .height (what of it
+ * the decoded picture holds) for WebP.  The caller probes, then allocates.
+ * The batch is decoded in PARTS by ffhip_jpeg_decode_files_mixed_device / ffhip_webp_decode_files_device into BGRA pictures (coded size,
+ * pitch 4 x the coded width) that are library scratch of the stream, ffhip_bgra_to_tensor_items behind each part.  A part's pictures take at
+ * most 1 GiB (FFHIP_TENSOR_PART_BYTES replaces the figure: lets tests reach the many-part form with small batches); a single picture
+ * larger than that is a part of its own.
+ * Per file the semantics of the calls underneath: status[i] receives each file's code -- a file they refuse or find damaged theirs,
+ * FFHIP_EINVAL for a rectangle that is empty or leaves the display picture and for an output ffhip_bgra_to_tensor_items would refuse --,
+ * nothing of such a file's output is written, every other file is delivered; geom_out / info_out (may be NULL) as underneath.  Returns the
+ * first failure.  FFHIP_EINVAL for NULL files, lens, fmt, outs or status and for a format the items call refuses; every check is made
+ * before anything is enqueued (on a machine without a device too; FFHIP_ENODEV there for good arguments).  Synchronises `stream`. */
+typedef struct ffhip_tensor_out {
+    void *d_out;
+    int64_t row_stride, plane_stride;
+} ffhip_tensor_out;
+typedef struct ffhip_rect {
+    int32_t x0, y0, width, height;
+} ffhip_rect;
+int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                   const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_jpeg_geom *geom_out, int *status, void *stream);
+int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                   const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_webp_info *info_out, int *status, void *stream);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
