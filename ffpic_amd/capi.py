@@ -28,6 +28,7 @@ EXPORTS = [
     "ffhip_jpeg_recon_items", "ffhip_jpeg_decode_files_mixed_device", "ffhip_vp8_decode_items",
     "ffhip_vp8_dequant_factors", "ffhip_webp_probe", "ffhip_webp_parse", "ffhip_webp_parse_batch", "ffhip_webp_parse_device", "ffhip_webp_decode_files_device", "ffhip_debug_webp_last_parts",
     "ffhip_bgra_to_tensor_items", "ffhip_jpeg_decode_files_tensor", "ffhip_webp_decode_files_tensor",
+    "ffhip_resize_axis_taps", "ffhip_bgra_resize_items", "ffhip_jpeg_decode_files_tensor_resized", "ffhip_webp_decode_files_tensor_resized",
 ]
 
 
@@ -142,6 +143,21 @@ class TensorOut(C.Structure):
 class Rect(C.Structure):
     """ffhip_rect"""
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+FFHIP_RESIZE_BILINEAR, FFHIP_RESIZE_ANTIALIAS = 0, 1
+FFHIP_RESIZE_MAX_SIDE = 16384
+
+
+class ResizeItem(C.Structure):
+    """ffhip_resize_item: one picture of an ffhip_bgra_resize_items call (device pointers; pitches in bytes)"""
+    _fields_ = [("d_src", C.c_void_p), ("src_pitch", C.c_int64), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int64), ("out_width", C.c_int32), ("out_height", C.c_int32)]
+
+
+class Size(C.Structure):
+    """ffhip_size"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32)]
 
 
 def jpeg_geom(mcu_cols, mcu_rows, ncomp=3, h=2, v=2, qt_id=(0, 1, 1)):
@@ -285,6 +301,12 @@ def lib():
                                                  C.POINTER(JpegGeom), vp, vp]
     L.ffhip_webp_decode_files_tensor.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
                                                  C.POINTER(WebpInfo), vp, vp]
+    L.ffhip_resize_axis_taps.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_uint16), ci]
+    L.ffhip_bgra_resize_items.argtypes = [C.POINTER(ResizeItem), ci, ci, vp]
+    L.ffhip_jpeg_decode_files_tensor_resized.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                         C.POINTER(Size), ci, C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_webp_decode_files_tensor_resized.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                         C.POINTER(Size), ci, C.POINTER(WebpInfo), vp, vp]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

@@ -114,6 +114,8 @@ enum FfhipScratchKind {
     SCRATCH_VP8_ITEMS = 50,        /* .. + 2: ffhip_vp8_decode_items' tables (and their pinned copy), the levels items' residual, the line slots */
     SCRATCH_TENSOR_ITEMS = 70,     /* ffhip_bgra_to_tensor_items' records and per-workgroup table, pinned records */
     SCRATCH_TENSOR_BGRA = 71,      /* ffhip_*_decode_files_tensor: a part's BGRA pictures */
+    SCRATCH_RESIZE_ITEMS = 72,     /* ffhip_bgra_resize_items' records, per-workgroup table and tap tables, pinned records */
+    SCRATCH_RESIZE_BGRA = 73,      /* ffhip_*_decode_files_tensor_resized: a part's resized BGRA pictures */
 };
 
 /* ffhip_vp8_decode_items (ffhip_vp8_frame.hip): its levels items' residual stage (ffhip_vp8.hip) and its device mode check

@@ -1,7 +1,8 @@
 /*
  * ffhip_tensor.hip -- the last stage between the decoders and a program that reads tensors: BGRA pictures as the decode calls leave
  * them -> RGB / BGR, CHW / HWC, uint8 / float16 / float32, cropped to a rectangle, in one launch for a whole mixed batch
- * (ffhip_bgra_to_tensor_items), and the file calls built on it (ffhip_jpeg_decode_files_tensor, ffhip_webp_decode_files_tensor).
+ * (ffhip_bgra_to_tensor_items), and the file calls built on it (ffhip_jpeg_decode_files_tensor, ffhip_webp_decode_files_tensor, and
+ * their _resized forms with ffhip_bgra_resize_items between the decoder and this stage).
  * The layout of the work is described in ffhip_tensor_body.h.
  */
 #include "ffhip_internal.h"
@@ -159,10 +160,13 @@ size_t tensor_part_budget()
     return b > 0 ? (size_t)b : (size_t)1 << 30;
 }
 
+struct TensorResize { const ffhip_size *out_size; int filter; }; /* out_size == NULL: every file keeps its rectangle's size */
+
 /* pic[i] is valid where status[i] == 0 (the probe's verdict) */
-int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs, const ffhip_rect *roi, const std::vector<TensorPicture> &pic,
-                     int *status, void *stream, const TensorDecode &decode)
+int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs, const ffhip_rect *roi, const TensorResize &rs,
+                     const std::vector<TensorPicture> &pic, int *status, void *stream, const TensorDecode &decode)
 {
+    const ffhip_size *out_size = rs.out_size;
     /* the items, with a stand-in for the picture's address: everything about rectangle and output is checked before anything is enqueued */
     std::vector<ffhip_tensor_item> item((size_t)n);
     std::vector<int> mine((size_t)n, FFHIP_OK); /* the code this call gives a file the decoder takes */
@@ -175,18 +179,28 @@ int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_o
         it.x0 = r.x0; it.y0 = r.y0; it.width = r.width; it.height = r.height;
         it.d_out = outs[i].d_out; it.row_stride = outs[i].row_stride; it.plane_stride = outs[i].plane_stride;
         TensorItemDesc d;
-        if (r.x0 < 0 || r.y0 < 0 || r.width < 1 || r.height < 1 || (long long)r.x0 + r.width > p.width || (long long)r.y0 + r.height > p.height ||
-            !tensor_item_desc(it, fmt, &d))
-            mine[(size_t)i] = FFHIP_EINVAL;
+        bool ok = r.x0 >= 0 && r.y0 >= 0 && r.width >= 1 && r.height >= 1 && (long long)r.x0 + r.width <= p.width && (long long)r.y0 + r.height <= p.height;
+        if (ok && out_size) { /* the rectangle is the resize's source; the sink takes the whole resized picture */
+            const ffhip_size &o = out_size[i];
+            ok = r.width <= FFHIP_RESIZE_MAX_SIDE && r.height <= FFHIP_RESIZE_MAX_SIDE && o.width >= 1 && o.width <= FFHIP_RESIZE_MAX_SIDE &&
+                 o.height >= 1 && o.height <= FFHIP_RESIZE_MAX_SIDE;
+            it.pitch = 4LL * o.width; it.x0 = 0; it.y0 = 0; it.width = o.width; it.height = o.height;
+        }
+        if (!ok || !tensor_item_desc(it, fmt, &d)) mine[(size_t)i] = FFHIP_EINVAL;
     }
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t budget = tensor_part_budget();
     auto bytes_of = [&](int i) { return status[i] ? (size_t)0 : ((size_t)4 * pic[(size_t)i].coded_w * pic[(size_t)i].coded_h + 255) & ~(size_t)255; };
+    /* the resized picture of a file that gets one */
+    auto resized_of = [&](int i) { return !out_size || status[i] || mine[(size_t)i] ? (size_t)0 : ((size_t)4 * out_size[i].width * out_size[i].height + 255) & ~(size_t)255; };
     for (int first = 0; first < n;) {
         /* a part: files while their pictures fit the budget; a picture larger than the budget is a part of its own */
         int cnt = 0;
-        size_t bytes = 0;
-        while (first + cnt < n && (cnt == 0 || bytes + bytes_of(first + cnt) <= budget)) bytes += bytes_of(first + cnt++);
+        size_t bytes = 0, resized = 0;
+        while (first + cnt < n && (cnt == 0 || bytes + resized + bytes_of(first + cnt) + resized_of(first + cnt) <= budget)) {
+            resized += resized_of(first + cnt);
+            bytes += bytes_of(first + cnt++);
+        }
         uint8_t *base = (uint8_t *)ffhip_scratch(SCRATCH_TENSOR_BGRA, stream, bytes / 4 + 64);
         if (!base) return FFHIP_ENOMEM;
         std::vector<uint8_t *> d_bgra((size_t)cnt);
@@ -203,13 +217,32 @@ int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_o
             for (int k = 0; k < cnt; k++) a_files = a_files || status[first + k] == rc;
             if (!a_files) return rc;
         }
+        uint8_t *small = nullptr; /* the part's resized pictures, pitch 4 x out width */
+        if (out_size && !(small = (uint8_t *)ffhip_scratch(SCRATCH_RESIZE_BGRA, stream, resized / 4 + 64))) return FFHIP_ENOMEM;
         std::vector<ffhip_tensor_item> good;
+        std::vector<ffhip_resize_item> shrink;
+        size_t small_at = 0;
         for (int k = 0; k < cnt; k++) {
             const int i = first + k;
             if (status[i]) continue;
             if (mine[(size_t)i]) { status[i] = mine[(size_t)i]; continue; }
             item[(size_t)i].d_bgra = d_bgra[(size_t)k];
+            if (out_size) {
+                const ffhip_rect r = roi ? roi[i] : ffhip_rect{0, 0, pic[(size_t)i].width, pic[(size_t)i].height};
+                ffhip_resize_item s;
+                s.d_src = d_bgra[(size_t)k]; s.src_pitch = pitch[(size_t)k];
+                s.x0 = r.x0; s.y0 = r.y0; s.width = r.width; s.height = r.height;
+                s.d_dst = small + small_at; s.dst_pitch = 4LL * out_size[i].width;
+                s.out_width = out_size[i].width; s.out_height = out_size[i].height;
+                shrink.push_back(s);
+                item[(size_t)i].d_bgra = s.d_dst;
+                small_at += resized_of(i);
+            }
             good.push_back(item[(size_t)i]);
+        }
+        if (out_size) {
+            const int rrc = ffhip_bgra_resize_items(shrink.data(), (int)shrink.size(), rs.filter, stream);
+            if (rrc) return rrc;
         }
         const int src = ffhip_bgra_to_tensor_items(good.data(), (int)good.size(), fmt, stream);
         if (src) return src;
@@ -226,10 +259,14 @@ bool tensor_files_args_ok(const uint8_t *const *files, const size_t *lens, int n
     return n >= 0 && tensor_format_ok(fmt) && (n == 0 || (files && lens && outs && status));
 }
 
-} // namespace
+bool resize_files_args_ok(int n, const ffhip_size *out_size, int filter)
+{
+    return (filter == FFHIP_RESIZE_BILINEAR || filter == FFHIP_RESIZE_ANTIALIAS) && (n <= 0 || out_size);
+}
 
-extern "C" int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
-                                              const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+/* the two families' common bodies: rs.out_size == NULL is the call without a resize */
+int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
+                      const ffhip_rect *roi, const TensorResize &rs, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
     if (!tensor_files_args_ok(files, lens, n, fmt, outs, status)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
@@ -242,14 +279,14 @@ extern "C" int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const
         if (geom_out) geom_out[i] = g;
         pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h};
     });
-    return tensor_files_run(n, fmt, outs, roi, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+    return tensor_files_run(n, fmt, outs, roi, rs, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
         return ffhip_jpeg_decode_files_mixed_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, geom_out ? geom_out + first : nullptr,
                                                     status + first, stream);
     });
 }
 
-extern "C" int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
-                                              const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_webp_info *info_out, int *status, void *stream)
+int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
+                      const ffhip_rect *roi, const TensorResize &rs, ffhip_webp_info *info_out, int *status, void *stream)
 {
     if (!tensor_files_args_ok(files, lens, n, fmt, outs, status)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
@@ -260,8 +297,38 @@ extern "C" int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const
         /* the loader's size is the container's word (ffhip_webp_info): what of it the decoded picture holds */
         pic[(size_t)i] = TensorPicture{16 * c, 16 * r, w < 16 * c ? w : 16 * c, h < 16 * r ? h : 16 * r};
     }
-    return tensor_files_run(n, fmt, outs, roi, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+    return tensor_files_run(n, fmt, outs, roi, rs, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
         return ffhip_webp_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
                                               status + first, stream);
     });
+}
+
+} // namespace
+
+extern "C" int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                              const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+{
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{nullptr, 0}, geom_out, status, stream);
+}
+
+extern "C" int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                              const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_webp_info *info_out, int *status, void *stream)
+{
+    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{nullptr, 0}, info_out, status, stream);
+}
+
+extern "C" int ffhip_jpeg_decode_files_tensor_resized(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                      const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                      ffhip_jpeg_geom *geom_out, int *status, void *stream)
+{
+    if (!resize_files_args_ok(n, out_size, filter)) return FFHIP_EINVAL;
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, geom_out, status, stream);
+}
+
+extern "C" int ffhip_webp_decode_files_tensor_resized(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                      const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                      ffhip_webp_info *info_out, int *status, void *stream)
+{
+    if (!resize_files_args_ok(n, out_size, filter)) return FFHIP_EINVAL;
+    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, info_out, status, stream);
 }

@@ -50,6 +50,36 @@ def bgra_to_tensors(items, fmt, stream=None):
     capi.check(L.ffhip_bgra_to_tensor_items(arr, n, C.byref(fmt), stream), "ffhip_bgra_to_tensor_items")
 
 
+def resize_bgra(items, antialias=True, stream=None):
+    """ffhip_bgra_resize_items: `items` a list of capi.ResizeItem (device pointers, pitches in bytes), BGRA rectangles of any sizes to BGRA
+    pictures of any sizes by the library's integer rule (antialias: the triangle widens with the shrink factor; otherwise two taps), one
+    resize launch for the whole batch.  Only enqueues on `stream` (a hipStream_t handle; None: the default stream)."""
+    L = capi.lib()
+    n = len(items)
+    arr = (capi.ResizeItem * max(n, 1))(*items)
+    capi.check(L.ffhip_bgra_resize_items(arr, n, _filter(antialias), stream), "ffhip_bgra_resize_items")
+
+
+def _filter(antialias):
+    return capi.FFHIP_RESIZE_ANTIALIAS if antialias else capi.FFHIP_RESIZE_BILINEAR
+
+
+def axis_taps(n_in, n_out, antialias=True):
+    """ffhip_resize_axis_taps for every output index of an axis: (first[n_out] as an int array, a list of n_out uint16 weight arrays).
+    Each array sums to 4096.  Needs no device."""
+    L = capi.lib()
+    first, taps = np.zeros(n_out, np.int64), []
+    f = C.c_int()
+    for o in range(n_out):
+        count = L.ffhip_resize_axis_taps(n_in, n_out, _filter(antialias), o, C.byref(f), None, 0)
+        capi.check(min(count, 0), "ffhip_resize_axis_taps")
+        q = np.zeros(count, np.uint16)
+        L.ffhip_resize_axis_taps(n_in, n_out, _filter(antialias), o, C.byref(f), q.ctypes.data_as(C.POINTER(C.c_uint16)), count)
+        first[o] = f.value
+        taps.append(q)
+    return first, taps
+
+
 def tensor_out(t, layout):
     """capi.TensorOut of a torch tensor [3][H][W] (layout 'CHW') or [H][W][3] ('HWC') whose innermost dimension(s) are dense: a slice of a
     batch tensor, a view with padded rows"""
@@ -72,9 +102,25 @@ def _rois(roi, n):
     return [tuple(int(v) for v in r) for r in roi]
 
 
-def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict):
-    import torch
+def _sizes(size, n):
+    """size=(H, W) for all files or a list of one per file -> [(H, W)] * n"""
+    if size is None:
+        return None
+    if len(size) == 2 and not hasattr(size[0], "__len__"):
+        size = [size] * n
+    if len(size) != n:
+        raise ValueError("size: one (height, width), or one per file")
+    size = [tuple(int(v) for v in s) for s in size]
+    for s in size:
+        if len(s) != 2 or min(s) < 1 or max(s) > capi.FFHIP_RESIZE_MAX_SIDE:
+            raise ValueError(f"size {s}: (height, width), each in 1..{capi.FFHIP_RESIZE_MAX_SIDE}")
+    return size
+
+
+def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size=None, antialias=True):
     fmt = tensor_format(dtype, layout, order, mean, std)
+    targets = _sizes(size, len(files))                            # argument errors come before any device use
+    import torch
     tdtype = getattr(torch, _dtype_name(dtype))
     dev = torch.cuda.current_device()
     L = capi.require_device(dev)
@@ -89,7 +135,7 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
                 raise
             sizes.append(None)
             continue
-        sizes.append((rois[i][3], rois[i][2]) if rois else (h, w))
+        sizes.append(targets[i] if targets else (rois[i][3], rois[i][2]) if rois else (h, w))
     shape = (lambda h, w: (3, h, w)) if layout == "CHW" else (lambda h, w: (h, w, 3))
     device = torch.device("cuda", dev)
     if stack:
@@ -106,7 +152,11 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
     lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
     status = (C.c_int * max(n, 1))()
     stream = torch.cuda.current_stream().cuda_stream
-    rc = call(L)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, None, status, stream)
+    if targets:
+        out_size = (capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets])
+        rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias), None, status, stream)
+    else:
+        rc = call(L)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, None, status, stream)
     status = list(status)[:n]
     if strict or stack or (rc != 0 and rc not in status):         # a file's code, or the call's own failure
         capi.check(rc, what)
@@ -127,7 +177,7 @@ def _webp_size(f):
 
 
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                           strict=True):
+                           strict=True, size=None, antialias=True):
     """ffhip_jpeg_decode_files_tensor: baseline JPEG files (list of bytes) of any geometry in one call -> torch tensors on the current
     device, written on torch's current stream (the call synchronises it).
       dtype    torch.uint8 (None), torch.float16 or torch.float32;  layout 'CHW' / 'HWC';  order 'RGB' / 'BGR'
@@ -135,15 +185,20 @@ def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
       roi      None: each file's display size; (x0, y0, width, height) for all files, or a list of one per file
       stack    one [N,3,H,W] / [N,H,W,3] tensor, the files' outputs slices of it; ValueError when the sizes differ, and every file
                has to decode
+      size     None: every tensor has its file's (or roi's) size.  (H, W) for all files, or a list of one per file: each picture (its
+               roi) is resized on the device to that size (ffhip_jpeg_decode_files_tensor_resized; the library's integer rule), so
+               that stack=True takes files of different sizes
+      antialias  with size: True widens the filter with the shrink factor (as PIL, torch antialias=True); False: two taps per axis
     Returns the list of tensors; with strict=False a failing file does not raise: its entry is None, and the per-file status codes
     follow as a second element."""
-    return _decode_to_tensors(lambda L: L.ffhip_jpeg_decode_files_tensor, "ffhip_jpeg_decode_files_tensor", _jpeg_size, files, dtype,
-                              layout, order, mean, std, roi, stack, n_threads, strict)
+    return _decode_to_tensors(lambda L: L.ffhip_jpeg_decode_files_tensor, "ffhip_jpeg_decode_files_tensor" + ("_resized" if size is not None else ""),
+                              _jpeg_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias)
 
 
 def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                           strict=True):
-    """ffhip_webp_decode_files_tensor: lossy WebP files; arguments and result as decode_jpeg_to_tensors.  A file's display size is the
+                           strict=True, size=None, antialias=True):
+    """ffhip_webp_decode_files_tensor (with size: ffhip_webp_decode_files_tensor_resized): lossy WebP files; arguments and result as
+    decode_jpeg_to_tensors.  A file's display size is the
     probe's width x height as far as the decoded picture holds it."""
-    return _decode_to_tensors(lambda L: L.ffhip_webp_decode_files_tensor, "ffhip_webp_decode_files_tensor", _webp_size, files, dtype,
-                              layout, order, mean, std, roi, stack, n_threads, strict)
+    return _decode_to_tensors(lambda L: L.ffhip_webp_decode_files_tensor, "ffhip_webp_decode_files_tensor" + ("_resized" if size is not None else ""),
+                              _webp_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias)

@@ -826,6 +826,68 @@ int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const size_t *le
 int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                    const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_webp_info *info_out, int *status, void *stream);
 
+/* ---- decoded pictures resized on the device (ffhip_resize.hip) ----
+ * The tensor stage above keeps every picture's size; a program that trains or infers wants one [N,3,H,W].  This stage resizes BGRA
+ * rectangles of any sizes to BGRA pictures of any sizes in one call, by a rule that is integers only, so that every
+ * implementation of it gives the same bytes.  Each axis alone, n_in source samples -> n_out output samples:
+ *   S = 2 n_out (FFHIP_RESIZE_BILINEAR: two taps) or 2 max(n_in, n_out) (FFHIP_RESIZE_ANTIALIAS: the triangle widens with the shrink
+ *   factor, as PIL's and torch's antialias=True).  For output o, c = (2 o + 1) n_in; source sample k is a tap iff
+ *   d_k = |(2 k + 1) n_out - c| < S and 0 <= k < n_in (taps outside are dropped, never read; the taps are a run first .. first + count - 1).
+ *   r_k = S - d_k, R their sum, q_k = floor((4096 r_k + floor(R / 2)) / R); 4096 - sum(q) is added to the tap of the largest r (the
+ *   lowest k on a tie): sum(q) == 4096.  Every q is >= 0: where a run of many hundred taps rounds up more often than its largest weight
+ *   can pay for (ANTIALIAS 1080 -> 1: 41 too many, the largest weight 7), that tap becomes 0 and what is still owed is taken from the
+ *   taps that follow in the same order -- falling r, the lowest k on a tie --, each down to 0 at most.  No run of up to 224 taps needs it.
+ * A byte of output pixel (ox, oy) is (sum_y sum_x qy qx v[y][x] + 2^23) >> 24: one rounding, no clamp needed (at most 255 2^24 + 2^23).
+ * All four bytes of a pixel are filtered alike: a constant alpha stays constant, equal sizes on both axes are a copy. */
+#define FFHIP_RESIZE_BILINEAR 0
+#define FFHIP_RESIZE_ANTIALIAS 1
+#define FFHIP_RESIZE_MAX_SIDE 16384 /* of a source rectangle and of an output: (2 k + 1) n_out stays below 2^30 */
+/* The rule for one output index, on the HOST (no device needed; the kernels run the same function): returns the tap count of output `o`,
+ * *first = its first source sample, q[0 .. min(count, cap) - 1] the weights, each in 0..4096 (q may be NULL when cap is 0).  FFHIP_EINVAL for n_in or
+ * n_out outside 1..16384, an unknown filter, o outside 0..n_out-1, first == NULL, cap < 0. */
+int ffhip_resize_axis_taps(int n_in, int n_out, int filter, int o, int *first, uint16_t *q, int cap);
+/* One picture of a batch.  All pointers are DEVICE pointers.
+ *   d_src, src_pitch   a BGRA picture as the decode calls write it: 4-byte aligned, pitch a multiple of 4
+ *   x0, y0, width,     the source rectangle (x0, y0 >= 0; width, height in 1..16384); the caller keeps it inside the picture, the call
+ *   height             checks what it can: 4 (x0 + width) <= src_pitch, and (y0 + height) src_pitch < 2^31
+ *   d_dst, dst_pitch   the output picture: 4-byte aligned, dst_pitch a multiple of 4 and >= 4 out_width
+ *   out_width,         in 1..16384
+ *   out_height
+ * Only the out_width x out_height pixels are written (one dword store each): the row padding of the destination stays untouched.
+ * Source and destination must not overlap. */
+typedef struct ffhip_resize_item {
+    const uint8_t *d_src;
+    int64_t src_pitch;
+    int32_t x0, y0, width, height;
+    uint8_t *d_dst;
+    int64_t dst_pitch;
+    int32_t out_width, out_height;
+} ffhip_resize_item;
+/* The whole batch, rectangles and outputs of any sizes, in ONE resize launch behind one small launch that writes the batch's tap tables
+ * (the rule above, per item and axis) and its per-workgroup table.  `items` is a HOST array; every check is made before anything is
+ * enqueued (FFHIP_EINVAL -- n < 0, NULL items with n > 0, a filter other than the two above, an item outside what its fields' lines above
+ * say --, on a machine without a device too; FFHIP_ENODEV there for good arguments).  n == 0 is FFHIP_OK.  Only enqueues on `stream`; the
+ * records, the per-workgroup table and the tap tables are library scratch of the stream. */
+int ffhip_bgra_resize_items(const ffhip_resize_item *items, int n, int filter, void *stream);
+
+/* Files in, tensors of chosen sizes out: ffhip_*_decode_files_tensor with the resize between the decoder and the tensor stage.  roi[i]
+ * (roi == NULL: the whole display picture) is file i's SOURCE rectangle, out_size[i] the size it is resized to by `filter`, and outs[i]
+ * is laid out for out_size[i].  Per part: the decode call, ffhip_bgra_resize_items into BGRA pictures of the target sizes (pitch
+ * 4 x out width; library scratch of the stream), ffhip_bgra_to_tensor_items; a part's decoded and resized pictures together keep the
+ * part budget of the calls above.  Per file as above, and status[i] = FFHIP_EINVAL also for a rectangle side or an out_size side
+ * outside 1..16384 and for an output ffhip_bgra_to_tensor_items would refuse for out_size[i]: nothing of that file is written, the
+ * others are delivered.  FFHIP_EINVAL for what the calls above refuse, for NULL out_size (n > 0) and for an unknown filter, before
+ * anything is enqueued (on a machine without a device too; FFHIP_ENODEV there for good arguments).  Synchronises `stream`. */
+typedef struct ffhip_size {
+    int32_t width, height;
+} ffhip_size;
+int ffhip_jpeg_decode_files_tensor_resized(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                           const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                           ffhip_jpeg_geom *geom_out, int *status, void *stream);
+int ffhip_webp_decode_files_tensor_resized(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                           const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                           ffhip_webp_info *info_out, int *status, void *stream);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
