@@ -29,6 +29,9 @@ EXPORTS = [
     "ffhip_vp8_dequant_factors", "ffhip_webp_probe", "ffhip_webp_parse", "ffhip_webp_parse_batch", "ffhip_webp_parse_device", "ffhip_webp_decode_files_device", "ffhip_debug_webp_last_parts",
     "ffhip_bgra_to_tensor_items", "ffhip_jpeg_decode_files_tensor", "ffhip_webp_decode_files_tensor",
     "ffhip_resize_axis_taps", "ffhip_bgra_resize_items", "ffhip_jpeg_decode_files_tensor_resized", "ffhip_webp_decode_files_tensor_resized",
+    "ffhip_jpeg_scaled_block", "ffhip_jpeg_scaled_size", "ffhip_jpeg_scaled_rect", "ffhip_jpeg_scale_choose", "ffhip_jpeg_scaled_wg_blocks",
+    "ffhip_jpeg_recon_items_scaled", "ffhip_jpeg_decode_files_mixed_device_scaled", "ffhip_jpeg_decode_files_tensor_scaled",
+    "ffhip_debug_tensor_last_parts",
 ]
 
 
@@ -307,6 +310,14 @@ def lib():
                                                          C.POINTER(Size), ci, C.POINTER(JpegGeom), vp, vp]
     L.ffhip_webp_decode_files_tensor_resized.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
                                                          C.POINTER(Size), ci, C.POINTER(WebpInfo), vp, vp]
+    L.ffhip_jpeg_scaled_block.argtypes = [vp, vp, ci, vp]
+    L.ffhip_jpeg_scaled_size.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]
+    L.ffhip_jpeg_scaled_rect.argtypes = [ci, ci, ci, C.POINTER(Rect), C.POINTER(Rect)]
+    L.ffhip_jpeg_scale_choose.argtypes = [ci, ci, ci, ci]
+    L.ffhip_jpeg_recon_items_scaled.argtypes = [C.POINTER(JpegItem), C.POINTER(ci), ci, vp]
+    L.ffhip_jpeg_decode_files_mixed_device_scaled.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(ci), C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_jpeg_decode_files_tensor_scaled.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                        C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(JpegGeom), vp, vp]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

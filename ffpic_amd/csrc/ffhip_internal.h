@@ -116,6 +116,7 @@ enum FfhipScratchKind {
     SCRATCH_TENSOR_BGRA = 71,      /* ffhip_*_decode_files_tensor: a part's BGRA pictures */
     SCRATCH_RESIZE_ITEMS = 72,     /* ffhip_bgra_resize_items' records, per-workgroup table and tap tables, pinned records */
     SCRATCH_RESIZE_BGRA = 73,      /* ffhip_*_decode_files_tensor_resized: a part's resized BGRA pictures */
+    SCRATCH_JPEG_SCALED = 80,      /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_scaled's records and per-workgroup table, pinned records */
 };
 
 /* ffhip_vp8_decode_items (ffhip_vp8_frame.hip): its levels items' residual stage (ffhip_vp8.hip) and its device mode check
@@ -168,7 +169,8 @@ int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint
  * each part of the batch it has decoded */
 /* items (mixed batches, ffhip_jpeg_decode_files_mixed_device): per picture its geometry, output and pitch; the call fills in the plane and
  * quantiser pointers and reconstructs with ffhip_jpeg_recon_items instead (bgra, pitch and image_stride unused) */
-struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_jpeg_item *items; };
+/* denom (with items only; NULL: every picture at full size): per picture its denominator 1, 2, 4 or 8 -- ffhip_jpeg_recon_items_scaled */
+struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_jpeg_item *items; const int *denom; };
 /* geoms: NULL = every picture has *geom; else picture i has geoms[i], all of *geom's layout class (ncomp, h, v): the planes hold the
  * pictures one behind the other, picture i at the sum of the MCUs of the pictures before it */
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
@@ -187,6 +189,12 @@ JpegChoices jpeg_choices(void);
 /* the layout class 0..6 of a picture ffhip_jpeg_recon_items takes with this output and pitch under these choices, -1 if it refuses it */
 int jpeg_item_class(const JpegChoices &ch, const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch);
 int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot); /* ffhip_jpeg_recon_items with scratch slot 0..FFHIP_HUFF_PARTS-1 */
+int jpeg_geom_class(const ffhip_jpeg_geom *g); /* the layout class 0..6 of a geometry, -1 for a bad one and for the two-pass layouts */
+/* the layout class 0..6 of a picture ffhip_jpeg_recon_items_scaled takes at denominator 2, 4 or 8 with this output and pitch, -1 if it refuses
+ * it: the one statement of what that call asks of geometry and output (ffhip_jpeg_scaled.hip) */
+int jpeg_scaled_item_class(const ffhip_jpeg_geom *g, int denom, const uint8_t *d_bgra, int64_t pitch);
+/* ffhip_jpeg_recon_items_scaled (ffhip_jpeg_scaled.hip) with that scratch slot: item i at 1 / denom[i] of its size, denominator 1 through jpeg_recon_items_impl */
+int jpeg_recon_items_scaled_impl(const ffhip_jpeg_item *items, const int *denom, int n, void *stream, int slot);
 /* the plane and quantiser pointers of picture `index` of a call whose planes hold its pictures one behind the other: the picture's blocks start
  * at MCU `mcu_base` of y / u / v (u, v NULL for grey), its tables are the index-th 256 of q */
 inline void jpeg_item_planes(ffhip_jpeg_item *it, const int16_t *y, const int16_t *u, const int16_t *v, const uint16_t *q, size_t mcu_base, size_t index)

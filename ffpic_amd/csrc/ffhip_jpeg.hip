@@ -936,9 +936,11 @@ static int jpeg_recon_batch_impl(const ffhip_jpeg_geom *g, int n_images, const i
 
 /* ---- mixed batches: ffhip_jpeg_recon_items ---- */
 
+int jpeg_geom_class(const ffhip_jpeg_geom *g) { return geom_ok(g) ? jpeg_layout_class(g) : -1; }
+
 int jpeg_item_class(const JpegChoices &ch, const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch)
 {
-    const int c = geom_ok(g) ? jpeg_layout_class(g) : -1; /* the two-pass layouts are not part of the mixed path */
+    const int c = jpeg_geom_class(g); /* the two-pass layouts are not part of the mixed path */
     return c >= 0 && picture_out_ok(g, d_bgra, pitch) && picture_limits_ok(g, ch.mps[c], pitch) ? c : -1;
 }
 

@@ -11,6 +11,7 @@
  */
 #include "ffhip_internal.h"
 #include "ffhip_entropy_internal.h"
+#include "ffhip_jpeg_scaled_body.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -312,11 +313,15 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
  * over pictures of different sizes with one ffhip_jpeg_recon_items launch behind each part of its write pass; a class it refuses goes to
  * host threads.  A class's planes are library scratch of the stream, reused by the next class: every class's work has run when its
  * turn ends (the entropy call synchronises the stream). */
-extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
-                                                    uint8_t *const *d_bgra, const int64_t *pitch, ffhip_jpeg_geom *geom_out,
-                                                    int *status, void *stream)
+/* denom == NULL: every picture at full size, the call as it was.  Otherwise picture i at 1 / denom[i] of its size (ffhip_jpeg_recon_items_scaled):
+ * its output is checked against the SCALED coded width, and the denominators travel with the items to both reconstruction sites -- behind
+ * the device entropy decoder's parts, and behind the host threads' upload */
+static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
+                                   const int *denom, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
     if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
+    for (int i = 0; denom && i < n; i++)
+        if (!jpeg_denom_ok(denom[i])) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
     if (n_threads < 1) n_threads = 1;
     if (n_threads > 64) n_threads = 64;
@@ -332,7 +337,10 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
         status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
         if (geom_out) geom_out[i] = g;
         if (status[i]) return;
-        cls[(size_t)i] = jpeg_item_class(ch, &g, d_bgra[i], pitch[i]);
+        if (denom && denom[i] > 1) /* the output holds the scaled picture: rows of 8 / denom x h x mcu_cols pixels */
+            cls[(size_t)i] = jpeg_scaled_item_class(&g, denom[i], d_bgra[i], pitch[i]);
+        else
+            cls[(size_t)i] = jpeg_item_class(ch, &g, d_bgra[i], pitch[i]);
         if (cls[(size_t)i] < 0) status[i] = FFHIP_EINVAL;
     });
     if (!ffhip_have_device()) return FFHIP_ENODEV;
@@ -348,10 +356,11 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
         std::vector<size_t> cl((size_t)nc);
         std::vector<ffhip_jpeg_geom> cg((size_t)nc);
         std::vector<ffhip_jpeg_item> items((size_t)nc);
-        std::vector<int> cs((size_t)nc, 0);
+        std::vector<int> cs((size_t)nc, 0), cd((size_t)nc, 1); /* cd: the class's denominators */
         std::vector<size_t> base((size_t)nc + 1); /* MCUs of the class's pictures before picture k */
         for (int k = 0; k < nc; k++) {
             const int i = idx[(size_t)k];
+            if (denom) cd[(size_t)k] = denom[i];
             cf[(size_t)k] = files[i]; cl[(size_t)k] = lens[i]; cg[(size_t)k] = geoms[(size_t)i];
             ffhip_jpeg_item &it = items[(size_t)k];
             memset(&it, 0, sizeof(it));
@@ -366,7 +375,7 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
         const Planes d = blk.at(dev);
         bool done = false;
         if (jpeg_entropy_on_device(cf[0], cl[0], nc)) {
-            const FfhipHuffThen then = {nullptr, 0, 0, items.data()};
+            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom ? cd.data() : nullptr};
             const int grc = jpeg_entropy_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, cs.data(), stream, &then);
             if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
             done = grc == FFHIP_OK;
@@ -385,13 +394,16 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
             });
             if (hipMemcpyAsync(dev, pin, blk.bytes, hipMemcpyHostToDevice, st) != hipSuccess) { rc = FFHIP_EIO; break; }
             std::vector<ffhip_jpeg_item> good;
+            std::vector<int> good_d;
             for (int k = 0; k < nc; k++) {
                 if (cs[(size_t)k]) continue;
                 ffhip_jpeg_item it = items[(size_t)k];
                 jpeg_item_planes(&it, d.y, d.u, d.v, d.q, base[(size_t)k], (size_t)k);
                 good.push_back(it);
+                good_d.push_back(cd[(size_t)k]);
             }
-            rc = jpeg_recon_items_impl(good.data(), (int)good.size(), stream, 0);
+            rc = denom ? jpeg_recon_items_scaled_impl(good.data(), good_d.data(), (int)good.size(), stream, 0)
+                       : jpeg_recon_items_impl(good.data(), (int)good.size(), stream, 0);
             if (hipStreamSynchronize(st) != hipSuccess && rc == FFHIP_OK) rc = FFHIP_EIO;
         }
         for (int k = 0; k < nc; k++) status[idx[(size_t)k]] = cs[(size_t)k];
@@ -400,4 +412,19 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files,
     for (int i = 0; i < n; i++)
         if (status[i]) return status[i];
     return FFHIP_OK;
+}
+
+extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
+                                                    uint8_t *const *d_bgra, const int64_t *pitch, ffhip_jpeg_geom *geom_out,
+                                                    int *status, void *stream)
+{
+    return jpeg_decode_files_mixed(files, lens, n, n_threads, d_bgra, pitch, nullptr, geom_out, status, stream);
+}
+
+extern "C" int ffhip_jpeg_decode_files_mixed_device_scaled(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
+                                                           uint8_t *const *d_bgra, const int64_t *pitch, const int *denom,
+                                                           ffhip_jpeg_geom *geom_out, int *status, void *stream)
+{
+    if (n > 0 && !denom) return FFHIP_EINVAL;
+    return jpeg_decode_files_mixed(files, lens, n, n_threads, d_bgra, pitch, denom, geom_out, status, stream);
 }

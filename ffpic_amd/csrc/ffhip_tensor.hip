@@ -6,6 +6,7 @@
  * The layout of the work is described in ffhip_tensor_body.h.
  */
 #include "ffhip_internal.h"
+#include "ffhip_jpeg_scaled_body.h"
 #include "ffhip_tensor_body.h"
 
 #include <math.h>
@@ -149,7 +150,8 @@ extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n,
 /* ---- files in, tensors out ---- */
 namespace {
 
-struct TensorPicture { int coded_w, coded_h, width, height; }; /* what a decode call writes; what the file displays (inside it) */
+struct TensorPicture { int coded_w, coded_h, width, height; int64_t pitch; }; /* what a decode call writes; what the file displays (inside it); its row bytes */
+thread_local int g_tensor_last_parts = 0; /* ffhip_debug_tensor_last_parts */
 /* decodes files [first, first + cnt) into d_bgra[k] with pitch[k]: the call underneath, its per-file codes into status + first */
 typedef std::function<int(int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch)> TensorDecode;
 
@@ -167,6 +169,7 @@ int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_o
                      const std::vector<TensorPicture> &pic, int *status, void *stream, const TensorDecode &decode)
 {
     const ffhip_size *out_size = rs.out_size;
+    g_tensor_last_parts = 0; /* a call that returns before its first part has taken none */
     /* the items, with a stand-in for the picture's address: everything about rectangle and output is checked before anything is enqueued */
     std::vector<ffhip_tensor_item> item((size_t)n);
     std::vector<int> mine((size_t)n, FFHIP_OK); /* the code this call gives a file the decoder takes */
@@ -175,7 +178,7 @@ int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_o
         const TensorPicture &p = pic[(size_t)i];
         const ffhip_rect r = roi ? roi[i] : ffhip_rect{0, 0, p.width, p.height};
         ffhip_tensor_item &it = item[(size_t)i];
-        it.d_bgra = (const uint8_t *)(uintptr_t)256; it.pitch = 4LL * p.coded_w;
+        it.d_bgra = (const uint8_t *)(uintptr_t)256; it.pitch = p.pitch;
         it.x0 = r.x0; it.y0 = r.y0; it.width = r.width; it.height = r.height;
         it.d_out = outs[i].d_out; it.row_stride = outs[i].row_stride; it.plane_stride = outs[i].plane_stride;
         TensorItemDesc d;
@@ -190,7 +193,7 @@ int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_o
     }
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t budget = tensor_part_budget();
-    auto bytes_of = [&](int i) { return status[i] ? (size_t)0 : ((size_t)4 * pic[(size_t)i].coded_w * pic[(size_t)i].coded_h + 255) & ~(size_t)255; };
+    auto bytes_of = [&](int i) { return status[i] ? (size_t)0 : ((size_t)pic[(size_t)i].pitch * pic[(size_t)i].coded_h + 255) & ~(size_t)255; };
     /* the resized picture of a file that gets one */
     auto resized_of = [&](int i) { return !out_size || status[i] || mine[(size_t)i] ? (size_t)0 : ((size_t)4 * out_size[i].width * out_size[i].height + 255) & ~(size_t)255; };
     for (int first = 0; first < n;) {
@@ -208,9 +211,10 @@ int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_o
         size_t at = 0;
         for (int k = 0; k < cnt; k++) { /* (a file the probe refused: the decoder refuses it again before it looks at its output) */
             d_bgra[(size_t)k] = base + at;
-            pitch[(size_t)k] = status[first + k] ? 0 : 4LL * pic[(size_t)(first + k)].coded_w;
+            pitch[(size_t)k] = status[first + k] ? 0 : pic[(size_t)(first + k)].pitch;
             at += bytes_of(first + k);
         }
+        g_tensor_last_parts++;
         const int rc = decode(first, cnt, d_bgra.data(), pitch.data());
         if (rc) { /* a file's code, or the call's own failure */
             bool a_files = false;
@@ -265,21 +269,48 @@ bool resize_files_args_ok(int n, const ffhip_size *out_size, int filter)
 }
 
 /* the two families' common bodies: rs.out_size == NULL is the call without a resize */
+/* denom == NULL: every file at full size, the calls as they were.  Otherwise file i is decoded at 1 / denom[i] of its size (0: the largest
+ * denominator at which its rectangle still covers out_size[i], ffhip_jpeg_scale_choose): the picture the run below sees is the SCALED one
+ * -- coded and display size, a pitch rounded up to 16 bytes -- and the rectangle is the full-size one mapped onto it */
 int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
-                      const ffhip_rect *roi, const TensorResize &rs, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+                      const ffhip_rect *roi, const TensorResize &rs, const int *denom, int *denom_out, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
     if (!tensor_files_args_ok(files, lens, n, fmt, outs, status)) return FFHIP_EINVAL;
+    for (int i = 0; denom && i < n; i++)
+        if (denom[i] != 0 ? !jpeg_denom_ok(denom[i]) : !rs.out_size) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
     std::vector<TensorPicture> pic((size_t)n);
+    std::vector<int> den(denom ? (size_t)n : 0, 1);
+    std::vector<ffhip_rect> mapped(denom && roi ? (size_t)n : 0);
     ffhip_parallel_for(n, n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads), [&](int i) {
         ffhip_jpeg_geom g;
         memset(&g, 0, sizeof(g));
         int w = 0, h = 0;
         status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
         if (geom_out) geom_out[i] = g;
-        pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h};
+        pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h, 4LL * g.mcu_cols * 8 * g.h};
+        if (!denom) return;
+        if (denom_out) denom_out[i] = 0;
+        if (roi) mapped[(size_t)i] = ffhip_rect{0, 0, 0, 0}; /* an empty rectangle: the run refuses the file */
+        if (status[i]) return;
+        const ffhip_rect r = roi ? roi[i] : ffhip_rect{0, 0, w, h};
+        const bool r_ok = r.x0 >= 0 && r.y0 >= 0 && r.width >= 1 && r.height >= 1 && (long long)r.x0 + r.width <= w && (long long)r.y0 + r.height <= h;
+        int d = denom[i];
+        if (d == 0) {
+            const ffhip_size &o = rs.out_size[i];
+            d = r_ok && o.width >= 1 && o.height >= 1 ? ffhip_jpeg_scale_choose(r.width, r.height, o.width, o.height) : 1;
+        }
+        den[(size_t)i] = d;
+        if (denom_out) denom_out[i] = d;
+        const int N = 8 / d;
+        const int cw = N * g.h * g.mcu_cols, chh = N * g.v * g.mcu_rows;
+        pic[(size_t)i] = TensorPicture{cw, chh, jpeg_scaled_len(w, d), jpeg_scaled_len(h, d), (4LL * cw + 15) & ~15LL};
+        if (roi && r_ok) mapped[(size_t)i] = jpeg_scaled_rect_of(w, h, d, r);
     });
-    return tensor_files_run(n, fmt, outs, roi, rs, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+    return tensor_files_run(n, fmt, outs, denom && roi ? mapped.data() : roi, rs, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+        if (denom)
+            return ffhip_jpeg_decode_files_mixed_device_scaled(files + first, lens + first, cnt, n_threads, d_bgra, pitch, den.data() + first,
+                                                               geom_out ? geom_out + first : nullptr, status + first, stream);
         return ffhip_jpeg_decode_files_mixed_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, geom_out ? geom_out + first : nullptr,
                                                     status + first, stream);
     });
@@ -295,7 +326,7 @@ int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
         int w = 0, h = 0, c = 0, r = 0;
         status[i] = files[i] && lens[i] ? ffhip_webp_probe(files[i], lens[i], &w, &h, &c, &r) : FFHIP_EINVAL;
         /* the loader's size is the container's word (ffhip_webp_info): what of it the decoded picture holds */
-        pic[(size_t)i] = TensorPicture{16 * c, 16 * r, w < 16 * c ? w : 16 * c, h < 16 * r ? h : 16 * r};
+        pic[(size_t)i] = TensorPicture{16 * c, 16 * r, w < 16 * c ? w : 16 * c, h < 16 * r ? h : 16 * r, 64LL * c};
     }
     return tensor_files_run(n, fmt, outs, roi, rs, pic, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
         return ffhip_webp_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
@@ -308,7 +339,7 @@ int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
 extern "C" int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                               const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{nullptr, 0}, geom_out, status, stream);
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{nullptr, 0}, nullptr, nullptr, geom_out, status, stream);
 }
 
 extern "C" int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
@@ -322,7 +353,7 @@ extern "C" int ffhip_jpeg_decode_files_tensor_resized(const uint8_t *const *file
                                                       ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
     if (!resize_files_args_ok(n, out_size, filter)) return FFHIP_EINVAL;
-    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, geom_out, status, stream);
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, nullptr, nullptr, geom_out, status, stream);
 }
 
 extern "C" int ffhip_webp_decode_files_tensor_resized(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
@@ -332,3 +363,14 @@ extern "C" int ffhip_webp_decode_files_tensor_resized(const uint8_t *const *file
     if (!resize_files_args_ok(n, out_size, filter)) return FFHIP_EINVAL;
     return webp_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, info_out, status, stream);
 }
+
+extern "C" int ffhip_jpeg_decode_files_tensor_scaled(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                     const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                     const int *denom, int *denom_out, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+{
+    if (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS) return FFHIP_EINVAL;
+    if (n > 0 && !denom) return FFHIP_EINVAL;
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, denom, denom_out, geom_out, status, stream);
+}
+
+extern "C" int ffhip_debug_tensor_last_parts(void) { return g_tensor_last_parts; }

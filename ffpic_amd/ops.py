@@ -452,6 +452,95 @@ def jpeg_recon_items(items, stream=None):
     capi.check(L.ffhip_jpeg_recon_items(arr, n, stream), "ffhip_jpeg_recon_items")
 
 
+def jpeg_scaled_block(coef, quant, denom):
+    """ffhip_jpeg_scaled_block: the N x N samples (N = 8 / denom, denom 2, 4 or 8) of one block from its 64 coefficients and 64 quantisers
+    (natural order), by the reduced-size rule the kernel runs.  Needs no device."""
+    coef = np.ascontiguousarray(coef, np.int16).reshape(64)
+    quant = np.ascontiguousarray(quant, np.uint16).reshape(64)
+    n = 8 // denom if denom in (1, 2, 4, 8) else 1
+    out = np.zeros((n, n), np.int16)
+    capi.check(capi.lib().ffhip_jpeg_scaled_block(_vp(coef), _vp(quant), denom, _vp(out)), "ffhip_jpeg_scaled_block")
+    return out
+
+
+def jpeg_scaled_size(width, height, denom):
+    """ffhip_jpeg_scaled_size: (width, height) a width x height picture displays at 1 / denom."""
+    w, h = C.c_int(), C.c_int()
+    capi.check(capi.lib().ffhip_jpeg_scaled_size(width, height, denom, C.byref(w), C.byref(h)), "ffhip_jpeg_scaled_size")
+    return w.value, h.value
+
+
+def jpeg_scaled_rect(width, height, denom, roi):
+    """ffhip_jpeg_scaled_rect: the rectangle (x0, y0, w, h) of the full-size width x height display picture mapped onto the picture at 1 / denom."""
+    r, out = capi.Rect(*[int(v) for v in roi]), capi.Rect()
+    capi.check(capi.lib().ffhip_jpeg_scaled_rect(width, height, denom, C.byref(r), C.byref(out)), "ffhip_jpeg_scaled_rect")
+    return out.x0, out.y0, out.width, out.height
+
+
+def jpeg_scale_choose(rect_w, rect_h, out_w, out_h):
+    """ffhip_jpeg_scale_choose: the largest denominator in 8, 4, 2, 1 at which a rect_w x rect_h rectangle still covers out_w x out_h."""
+    d = capi.lib().ffhip_jpeg_scale_choose(rect_w, rect_h, out_w, out_h)
+    capi.check(min(d, 0), "ffhip_jpeg_scale_choose")
+    return d
+
+
+def jpeg_recon_items_scaled(items, denom, stream=None):
+    """ffhip_jpeg_recon_items_scaled: `items` a list of capi.JpegItem whose d_bgra / pitch describe the picture at 1 / denom[i]; one launch
+    per denominator present, denominator 1 through ffhip_jpeg_recon_items.  Only enqueues on `stream`."""
+    L = capi.lib()
+    n = len(items)
+    arr = (capi.JpegItem * max(n, 1))(*items)
+    den = (C.c_int * max(n, 1))(*[int(d) for d in denom])
+    capi.check(L.ffhip_jpeg_recon_items_scaled(arr, den, n, stream), "ffhip_jpeg_recon_items_scaled")
+
+
+def jpeg_decode_files_mixed_device_scaled(files, denom, n_threads=8, stream=None, strict=True):
+    """ffhip_jpeg_decode_files_mixed_device_scaled: as jpeg_decode_files_mixed_device with file i at 1 / denom[i] of its size.  Returns (geoms,
+    [host BGRA [h][w][4] at the SCALED CODED size], device buffer); with strict=False a failing file's entry is None and the per-file status
+    codes follow."""
+    L = capi.require_device()
+    n = len(files)
+    offs, pitches, rows_of, total = [], [], [], 0
+    for f, d in zip(files, denom):
+        try:
+            g, _, _ = jpeg_probe(f)
+            pitch, rows = (g.width // d * 4 + 15) & ~15, g.height // d
+        except capi.FfhipError:
+            pitch = rows = 0
+        offs.append(total)
+        pitches.append(pitch)
+        rows_of.append(rows)
+        total += (pitch * rows + 15) & ~15
+    dout = DeviceBuffer(nbytes=max(total, 16))
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
+    pitch_arr = (C.c_int64 * n)(*pitches)
+    den = (C.c_int * n)(*[int(d) for d in denom])
+    geoms = (capi.JpegGeom * n)()
+    status = (C.c_int * n)()
+    rc = L.ffhip_jpeg_decode_files_mixed_device_scaled(ptrs, lens, n, n_threads, outs, pitch_arr, den, geoms, status, stream)
+    if strict or rc not in (0, capi.FFHIP_EINVAL):
+        capi.check(rc, "ffhip_jpeg_decode_files_mixed_device_scaled")
+    flat = dout.to_host((max(total, 16),), np.uint8)
+    images = []
+    for i in range(n):
+        if status[i] or not pitches[i]:
+            images.append(None)
+            continue
+        pic = flat[offs[i]:offs[i] + pitches[i] * rows_of[i]].reshape(rows_of[i], pitches[i] // 4, 4)
+        images.append(pic[:, :geoms[i].width // denom[i]].copy())
+    if strict:
+        return list(geoms), images, dout
+    return list(geoms), images, dout, list(status)
+
+
+def tensor_last_parts():
+    """ffhip_debug_tensor_last_parts: the parts the calling thread's last files-to-tensors call cut its batch into."""
+    return capi.lib().ffhip_debug_tensor_last_parts()
+
+
 def vp8_decode_items(items, stream=None):
     """ffhip_vp8_decode_items: `items` a list of capi.Vp8Item; key frames of any size, quantisers and loop filter in one call
     (one launch per filter type and residual-map form).  Only enqueues on `stream`."""

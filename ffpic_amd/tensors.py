@@ -117,9 +117,22 @@ def _sizes(size, n):
     return size
 
 
-def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size=None, antialias=True):
+def _reduce(reduce, size):
+    """reduce=1 | 2 | 4 | 8 | 'auto' -> the denominator for every file, 0 for 'auto' (the library chooses per file; needs size)"""
+    if reduce == "auto":
+        if size is None:
+            raise ValueError("reduce='auto' needs size=: the denominator is chosen so that the picture still covers it")
+        return 0
+    if isinstance(reduce, bool) or reduce not in (1, 2, 4, 8):
+        raise ValueError(f"reduce {reduce!r}: 1, 2, 4, 8 or 'auto'")
+    return int(reduce)
+
+
+def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size=None, antialias=True,
+                       reduce=1, return_reduce=False):
     fmt = tensor_format(dtype, layout, order, mean, std)
     targets = _sizes(size, len(files))                            # argument errors come before any device use
+    den = _reduce(reduce, size)
     import torch
     tdtype = getattr(torch, _dtype_name(dtype))
     dev = torch.cuda.current_device()
@@ -135,7 +148,16 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
                 raise
             sizes.append(None)
             continue
-        sizes.append(targets[i] if targets else (rois[i][3], rois[i][2]) if rois else (h, w))
+        if targets or den == 1:
+            sizes.append(targets[i] if targets else (rois[i][3], rois[i][2]) if rois else (h, w))
+            continue
+        try:                                                      # without a target the tensor has the mapped rectangle's size
+            _, _, mw, mh = ops.jpeg_scaled_rect(w, h, den, rois[i] if rois else (0, 0, w, h))
+        except capi.FfhipError:
+            if strict or stack:
+                raise
+            mw, mh = rois[i][2], rois[i][3]                       # a rectangle the library refuses: its code comes from the call
+        sizes.append((mh, mw))
     shape = (lambda h, w: (3, h, w)) if layout == "CHW" else (lambda h, w: (h, w, 3))
     device = torch.device("cuda", dev)
     if stack:
@@ -152,8 +174,13 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
     lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
     status = (C.c_int * max(n, 1))()
     stream = torch.cuda.current_stream().cuda_stream
-    if targets:
-        out_size = (capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets])
+    used = (C.c_int * max(n, 1))(*([1] * max(n, 1)))
+    out_size = (capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets]) if targets else None
+    if den != 1:
+        what = "ffhip_jpeg_decode_files_tensor_scaled"
+        rc = L.ffhip_jpeg_decode_files_tensor_scaled(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias),
+                                                     (C.c_int * max(n, 1))(*([den] * max(n, 1))), used, None, status, stream)
+    elif targets:
         rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias), None, status, stream)
     else:
         rc = call(L)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, None, status, stream)
@@ -161,9 +188,11 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
     if strict or stack or (rc != 0 and rc not in status):         # a file's code, or the call's own failure
         capi.check(rc, what)
     if stack:
-        return batch
-    tensors = [None if status[i] else tensors[i] for i in range(n)]
-    return tensors if strict else (tensors, status)
+        result = batch
+    else:
+        tensors = [None if status[i] else tensors[i] for i in range(n)]
+        result = tensors if strict else (tensors, status)
+    return (result, list(used)[:n]) if return_reduce else result
 
 
 def _jpeg_size(f):
@@ -177,7 +206,7 @@ def _webp_size(f):
 
 
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                           strict=True, size=None, antialias=True):
+                           strict=True, size=None, antialias=True, reduce=1, return_reduce=False):
     """ffhip_jpeg_decode_files_tensor: baseline JPEG files (list of bytes) of any geometry in one call -> torch tensors on the current
     device, written on torch's current stream (the call synchronises it).
       dtype    torch.uint8 (None), torch.float16 or torch.float32;  layout 'CHW' / 'HWC';  order 'RGB' / 'BGR'
@@ -189,10 +218,17 @@ def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
                roi) is resized on the device to that size (ffhip_jpeg_decode_files_tensor_resized; the library's integer rule), so
                that stack=True takes files of different sizes
       antialias  with size: True widens the filter with the shrink factor (as PIL, torch antialias=True); False: two taps per axis
+      reduce   1: the pictures are reconstructed at full size.  2, 4, 8: at 1/2, 1/4, 1/8 size straight from the coefficients
+               (ffhip_jpeg_decode_files_tensor_scaled; as libjpeg's scale_num / 8, PIL's draft()): roi stays in full-size coordinates and
+               is mapped (ops.jpeg_scaled_rect: its edges may move out by up to reduce - 1 source pixels); without size the tensor has
+               the mapped rectangle's size.  'auto' (needs size): per file the largest of 8, 4, 2, 1 at which its rectangle still
+               covers size (ops.jpeg_scale_choose), the resize doing the rest
+      return_reduce  also return the denominator each file was decoded at
     Returns the list of tensors; with strict=False a failing file does not raise: its entry is None, and the per-file status codes
-    follow as a second element."""
+    follow as a second element.  With return_reduce: (that, [denominators])."""
     return _decode_to_tensors(lambda L: L.ffhip_jpeg_decode_files_tensor, "ffhip_jpeg_decode_files_tensor" + ("_resized" if size is not None else ""),
-                              _jpeg_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias)
+                              _jpeg_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias, reduce,
+                              return_reduce)
 
 
 def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,

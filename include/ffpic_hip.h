@@ -888,6 +888,68 @@ int ffhip_webp_decode_files_tensor_resized(const uint8_t *const *files, const si
                                            const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                            ffhip_webp_info *info_out, int *status, void *stream);
 
+/* ---- JPEG pictures at 1/2, 1/4 and 1/8 size straight from the coefficients (ffhip_jpeg_scaled.hip) ----
+ * A loader that shrinks camera pictures to a few hundred pixels does not need them at full size first.  With the denominator d in 1, 2, 4, 8
+ * and N = 8 / d, a block of a component becomes N x N samples by the steps of the full-size path (format/jpg.c:247-253, utils/idct.c:512-534)
+ * with an N-point matrix in place of the 8-point one (what libjpeg's scale_num / 8 and PIL's draft() do):
+ *   1. F[v][u] = (int16)(coef[8 v + u] * quant[8 v + u])                          for u, v < N (natural order)
+ *   2. c[y][u] = (int16)((sum_v T_N[y][v] F[v][u] + 1024) >> 11)
+ *   3. s[y][x] = max(0, (sum_u T_N[x][u] c[y][u] + (257 << 17)) >> 18)
+ * all sums int32; T_N[x][u] = round(8192 sqrt(2) alpha(u) cos((2 x + 1) u pi / 2 N)): T_1 = [[8192]], T_2 = [[8192, 8192], [8192, -8192]],
+ * T_4 = [[8192, 10703, 8192, 4433], [8192, 4433, -8192, -10703], [8192, -4433, -8192, 10703], [8192, -10703, 8192, -4433]].  No sum can leave
+ * int32 (the largest row of |T_4| is 31 520, the inputs are int16) and a sample is at most 4068: the full-size path's upper clamp cannot bind.
+ * A DC-only block gives, at every N, the value the full-size path gives each of its 64 pixels.
+ * The picture at denominator d: coded size (N h mcu_cols) x (N v mcu_rows), display size ceil(W / d) x ceil(H / d); pixel (x, y) of an MCU takes
+ * sample (y % N, x % N) of luma block (y / N) h + x / N and sample (y / v, x / h) of the MCU's one chroma block (the replication of
+ * utils/colorspace.c:148-150); B, G, R, 0xFF by the full-size path's conversion, grey files with its U = V = 0.
+ * d = 1 is the full-size path itself, byte for byte: it is routed to the full-size kernels. */
+/* Host only, no device needed: the block rule.  out receives the N x N samples row-major, N = 8 / denom, denom 2, 4 or 8 (FFHIP_EINVAL for 1:
+ * the 8 x 8 rule is the full-size kernels' and ffhip_get_dct_ops's).  The kernel runs the same function (ffhip_jpeg_scaled_body.h). */
+int ffhip_jpeg_scaled_block(const int16_t *coef /* [64] */, const uint16_t *quant /* [64] */, int denom, int16_t *out /* [N][N] */);
+/* Host only.  *w = ceil(width / denom), *h = ceil(height / denom): the display size at that denominator. */
+int ffhip_jpeg_scaled_size(int width, int height, int denom, int *w, int *h);
+/* Host only.  A rectangle of the FULL-SIZE display picture (inside width x height, not empty) mapped onto the picture at `denom`:
+ * x0' = x0 / d, x1' = min(ceil(W / d), ceil((x0 + w) / d)), likewise y.  Its edges may lie up to d - 1 source pixels outside the request. */
+int ffhip_jpeg_scaled_rect(int width, int height, int denom, const ffhip_rect *roi, ffhip_rect *out);
+/* Host only.  The largest d in 8, 4, 2, 1 at which a rect_w x rect_h rectangle at the origin, mapped as above (ceil(rect_w / d) x
+ * ceil(rect_h / d); a rectangle elsewhere maps to at least that), is still at least out_w x out_h; 1 when none is (a target larger than
+ * the rectangle).  FFHIP_EINVAL for a side below 1. */
+int ffhip_jpeg_scale_choose(int rect_w, int rect_h, int out_w, int out_h);
+/* Luma blocks side by side that one workgroup of the reduced kernel covers (a wave is that wide; its four waves take four rows) */
+#define FFHIP_JPEG_SCALED_WG_BLOCKS 64
+int ffhip_jpeg_scaled_wg_blocks(void);
+/* ffhip_jpeg_recon_items with a denominator per item: item i is written at 1 / denom[i] of its size.  Per item as there, except
+ *   d_bgra, pitch   the SCALED coded picture, (8 / d) h mcu_cols x (8 / d) v mcu_rows: 16-byte aligned, pitch >= 4 x that width and a
+ *                   multiple of 16.  Nothing beyond 4 x the scaled coded width of a row is written
+ * One launch per denominator present (2, 4, 8: one kernel, generic over the seven fused layout classes; the two-pass layouts stay
+ * refused), and the items of denominator 1 through ffhip_jpeg_recon_items.  `items` and `denom` are HOST arrays; every check is made
+ * before anything is enqueued (FFHIP_EINVAL -- a denominator other than 1, 2, 4, 8 included --, on a machine without a device too;
+ * FFHIP_ENODEV there for good arguments).  Only enqueues on `stream`. */
+int ffhip_jpeg_recon_items_scaled(const ffhip_jpeg_item *items, const int *denom, int n, void *stream);
+/* ffhip_jpeg_decode_files_mixed_device with a denominator per file: picture i at d_bgra[i] at its SCALED coded size (pitch[i] as for
+ * ffhip_jpeg_recon_items_scaled).  Probe, entropy decode and write pass are the unscaled call's; the denominators travel to the
+ * reconstruction behind the device entropy decoder's parts and to the one behind the host threads' upload.  FFHIP_EINVAL for NULL denom
+ * and for a denominator other than 1, 2, 4, 8, before anything else. */
+int ffhip_jpeg_decode_files_mixed_device_scaled(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
+                                                uint8_t *const *d_bgra, const int64_t *pitch, const int *denom,
+                                                ffhip_jpeg_geom *geom_out, int *status, void *stream);
+/* ffhip_jpeg_decode_files_tensor_resized with a denominator per file.
+ *   denom[i]     1, 2, 4, 8, or 0: "choose" -- ffhip_jpeg_scale_choose of the file's rectangle and out_size[i] (needs out_size: FFHIP_EINVAL
+ *                without).  denom_out[i] (may be NULL) receives the denominator used, 0 for a file the probe refused
+ *   roi          stays in FULL-SIZE display coordinates (NULL: the whole picture), is checked there, and is mapped as
+ *                ffhip_jpeg_scaled_rect says: the resize (or, without one, the tensor stage) reads the mapped rectangle, whose edges may lie
+ *                up to d - 1 source pixels outside the request
+ *   out_size     may be NULL: the tensor then has the mapped rectangle's size, outs[i] is laid out for it, `filter` is still checked
+ * The parts of the batch are sized by the SCALED coded pictures (pitch 4 x the scaled coded width rounded up to 16 bytes).  All 1: the
+ * bytes of the unscaled calls. */
+int ffhip_jpeg_decode_files_tensor_scaled(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                          const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                          const int *denom, int *denom_out, ffhip_jpeg_geom *geom_out, int *status, void *stream);
+/* Diagnostics: the parts the calling thread's last ffhip_*_decode_files_tensor* call cut its batch into, counted from the moment the call has
+ * probed its files: 0 where it then returned before its first part (a missing device, a failed allocation).  A call refused for its
+ * arguments before that, or one of no files, leaves the count as it was. */
+int ffhip_debug_tensor_last_parts(void);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
