@@ -32,6 +32,9 @@ EXPORTS = [
     "ffhip_jpeg_scaled_block", "ffhip_jpeg_scaled_size", "ffhip_jpeg_scaled_rect", "ffhip_jpeg_scale_choose", "ffhip_jpeg_scaled_wg_blocks",
     "ffhip_jpeg_recon_items_scaled", "ffhip_jpeg_decode_files_mixed_device_scaled", "ffhip_jpeg_decode_files_tensor_scaled",
     "ffhip_debug_tensor_last_parts",
+    "ffhip_jpeg_exif_orientation", "ffhip_webp_exif_orientation", "ffhip_orient_size", "ffhip_orient_rect", "ffhip_orient_inverse",
+    "ffhip_bgra_orient_items", "ffhip_jpeg_decode_files_tensor_oriented", "ffhip_webp_decode_files_tensor_oriented",
+    "ffhip_debug_orient_last_items",
 ]
 
 
@@ -161,6 +164,12 @@ class ResizeItem(C.Structure):
 class Size(C.Structure):
     """ffhip_size"""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32)]
+
+
+class OrientItem(C.Structure):
+    """ffhip_orient_item: one picture of an ffhip_bgra_orient_items call (device pointers; pitches in bytes; the STORED rectangle)"""
+    _fields_ = [("d_src", C.c_void_p), ("src_pitch", C.c_int64), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int64), ("orientation", C.c_int32)]
 
 
 def jpeg_geom(mcu_cols, mcu_rows, ncomp=3, h=2, v=2, qt_id=(0, 1, 1)):
@@ -318,6 +327,17 @@ def lib():
     L.ffhip_jpeg_decode_files_mixed_device_scaled.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(ci), C.POINTER(JpegGeom), vp, vp]
     L.ffhip_jpeg_decode_files_tensor_scaled.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
                                                         C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_jpeg_exif_orientation.argtypes = [vp, sz, C.POINTER(ci)]
+    L.ffhip_webp_exif_orientation.argtypes = [vp, sz, C.POINTER(ci)]
+    L.ffhip_orient_size.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]
+    L.ffhip_orient_rect.argtypes = [ci, ci, ci, C.POINTER(Rect), C.POINTER(Rect)]
+    L.ffhip_orient_inverse.argtypes = [ci]
+    L.ffhip_bgra_orient_items.argtypes = [C.POINTER(OrientItem), ci, vp]
+    L.ffhip_jpeg_decode_files_tensor_oriented.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                          C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
+                                                          C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_webp_decode_files_tensor_oriented.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                          C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(WebpInfo), vp, vp]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

@@ -116,7 +116,9 @@ enum FfhipScratchKind {
     SCRATCH_TENSOR_BGRA = 71,      /* ffhip_*_decode_files_tensor: a part's BGRA pictures */
     SCRATCH_RESIZE_ITEMS = 72,     /* ffhip_bgra_resize_items' records, per-workgroup table and tap tables, pinned records */
     SCRATCH_RESIZE_BGRA = 73,      /* ffhip_*_decode_files_tensor_resized: a part's resized BGRA pictures */
-    SCRATCH_JPEG_SCALED = 80,      /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_scaled's records and per-workgroup table, pinned records */
+    SCRATCH_ORIENT_ITEMS = 74,     /* ffhip_bgra_orient_items' records and per-workgroup table, pinned records */
+    SCRATCH_ORIENT_BGRA = 75,      /* ffhip_*_decode_files_tensor_oriented: a part's upright BGRA pictures */
+    SCRATCH_JPEG_SCALED = 80,     /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_scaled's records and per-workgroup table, pinned records */
 };
 
 /* ffhip_vp8_decode_items (ffhip_vp8_frame.hip): its levels items' residual stage (ffhip_vp8.hip) and its device mode check

@@ -541,6 +541,49 @@ def tensor_last_parts():
     return capi.lib().ffhip_debug_tensor_last_parts()
 
 
+def orient_last_items():
+    """ffhip_debug_orient_last_items: the pictures the calling thread's last ffhip_*_decode_files_tensor* call turned upright"""
+    return capi.lib().ffhip_debug_orient_last_items()
+
+
+def _exif_orientation(call, data):
+    buf = np.frombuffer(data, dtype=np.uint8)
+    o = C.c_int(0)
+    capi.check(call(buf.ctypes.data if buf.size else None, buf.size, C.byref(o)), "ffhip_*_exif_orientation")
+    return o.value
+
+
+def jpeg_exif_orientation(data):
+    """ffhip_jpeg_exif_orientation: the EXIF orientation (1..8) of a JPEG file's bytes; 1 where the file has no usable tag.  No device."""
+    return _exif_orientation(capi.lib().ffhip_jpeg_exif_orientation, data)
+
+
+def webp_exif_orientation(data):
+    """ffhip_webp_exif_orientation: the same from a WebP file's EXIF chunk"""
+    return _exif_orientation(capi.lib().ffhip_webp_exif_orientation, data)
+
+
+def orient_size(width, height, orientation):
+    """ffhip_orient_size: (width, height) of the upright picture of a stored width x height one"""
+    w, h = C.c_int(), C.c_int()
+    capi.check(capi.lib().ffhip_orient_size(width, height, orientation, C.byref(w), C.byref(h)), "ffhip_orient_size")
+    return w.value, h.value
+
+
+def orient_rect(width, height, orientation, roi):
+    """ffhip_orient_rect: the rectangle (x0, y0, w, h) of the upright picture as a rectangle of the stored width x height picture"""
+    out = capi.Rect()
+    capi.check(capi.lib().ffhip_orient_rect(width, height, orientation, C.byref(capi.Rect(*roi)), C.byref(out)), "ffhip_orient_rect")
+    return out.x0, out.y0, out.width, out.height
+
+
+def orient_inverse(orientation):
+    """ffhip_orient_inverse: the orientation that undoes `orientation`"""
+    o = capi.lib().ffhip_orient_inverse(orientation)
+    capi.check(min(o, 0), "ffhip_orient_inverse")
+    return o
+
+
 def vp8_decode_items(items, stream=None):
     """ffhip_vp8_decode_items: `items` a list of capi.Vp8Item; key frames of any size, quantisers and loop filter in one call
     (one launch per filter type and residual-map form).  Only enqueues on `stream`."""

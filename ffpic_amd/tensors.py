@@ -60,6 +60,16 @@ def resize_bgra(items, antialias=True, stream=None):
     capi.check(L.ffhip_bgra_resize_items(arr, n, _filter(antialias), stream), "ffhip_bgra_resize_items")
 
 
+def orient_bgra(items, stream=None):
+    """ffhip_bgra_orient_items: `items` a list of capi.OrientItem (device pointers, pitches in bytes, the STORED rectangle and its EXIF
+    orientation 1..8), BGRA rectangles of any sizes turned upright, one launch for the whole batch.  Only enqueues on `stream` (a
+    hipStream_t handle; None: the default stream)."""
+    L = capi.lib()
+    n = len(items)
+    arr = (capi.OrientItem * max(n, 1))(*items)
+    capi.check(L.ffhip_bgra_orient_items(arr, n, stream), "ffhip_bgra_orient_items")
+
+
 def _filter(antialias):
     return capi.FFHIP_RESIZE_ANTIALIAS if antialias else capi.FFHIP_RESIZE_BILINEAR
 
@@ -128,11 +138,26 @@ def _reduce(reduce, size):
     return int(reduce)
 
 
+def _orientations(orientation, n):
+    """orientation=None | 1..8 | one per file -> [1..8] * n, None for None"""
+    if orientation is None:
+        return None
+    imposed = [orientation] * n if not hasattr(orientation, "__len__") else list(orientation)
+    if len(imposed) != n:
+        raise ValueError("orientation: one value 1..8, or one per file")
+    for o in imposed:
+        if isinstance(o, bool) or o not in (1, 2, 3, 4, 5, 6, 7, 8):
+            raise ValueError(f"orientation {o!r}: an EXIF orientation, 1..8")
+    return [int(o) for o in imposed]
+
+
 def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size=None, antialias=True,
-                       reduce=1, return_reduce=False):
+                       reduce=1, return_reduce=False, tag=None, apply_exif_orientation=False, orientation=None, return_orientation=False):
     fmt = tensor_format(dtype, layout, order, mean, std)
     targets = _sizes(size, len(files))                            # argument errors come before any device use
     den = _reduce(reduce, size)
+    imposed = _orientations(orientation, len(files))
+    oriented = bool(apply_exif_orientation) or imposed is not None
     import torch
     tdtype = getattr(torch, _dtype_name(dtype))
     dev = torch.cuda.current_device()
@@ -140,6 +165,7 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
     n = len(files)
     rois = _rois(roi, n)
     sizes = []                                                    # (height, width) of each file's tensor; None: the probe refused it
+    turns = [1] * n                                               # the orientation of each file's tensor; 0: the probe refused it
     for i, f in enumerate(files):
         try:
             w, h = probe(f)
@@ -147,17 +173,22 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
             if strict or stack:
                 raise
             sizes.append(None)
+            turns[i] = 0
             continue
+        if oriented:                                              # sizes and rectangles are the upright picture's
+            turns[i] = imposed[i] if imposed else tag(f)
+        swap = turns[i] >= 5
         if targets or den == 1:
-            sizes.append(targets[i] if targets else (rois[i][3], rois[i][2]) if rois else (h, w))
+            sizes.append(targets[i] if targets else (rois[i][3], rois[i][2]) if rois else (w, h) if swap else (h, w))
             continue
         try:                                                      # without a target the tensor has the mapped rectangle's size
-            _, _, mw, mh = ops.jpeg_scaled_rect(w, h, den, rois[i] if rois else (0, 0, w, h))
+            stored = (0, 0, w, h) if not rois else ops.orient_rect(w, h, turns[i], rois[i]) if oriented else rois[i]
+            _, _, mw, mh = ops.jpeg_scaled_rect(w, h, den, stored)
         except capi.FfhipError:
             if strict or stack:
                 raise
-            mw, mh = rois[i][2], rois[i][3]                       # a rectangle the library refuses: its code comes from the call
-        sizes.append((mh, mw))
+            mw, mh, swap = rois[i][2], rois[i][3], False          # a rectangle the library refuses: its code comes from the call
+        sizes.append((mw, mh) if swap else (mh, mw))
     shape = (lambda h, w: (3, h, w)) if layout == "CHW" else (lambda h, w: (h, w, 3))
     device = torch.device("cuda", dev)
     if stack:
@@ -176,7 +207,19 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
     stream = torch.cuda.current_stream().cuda_stream
     used = (C.c_int * max(n, 1))(*([1] * max(n, 1)))
     out_size = (capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets]) if targets else None
-    if den != 1:
+    if oriented:
+        what = what.split("_decode_")[0] + "_decode_files_tensor_oriented"
+        turn = (C.c_int * max(n, 1))(*[max(t, 1) if imposed else 0 for t in turns])
+        used_turn = (C.c_int * max(n, 1))()
+        if "jpeg" in what:
+            denoms = (C.c_int * max(n, 1))(*([den] * max(n, 1)))
+            rc = L.ffhip_jpeg_decode_files_tensor_oriented(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias),
+                                                           denoms, used, turn, used_turn, None, status, stream)
+        else:
+            rc = L.ffhip_webp_decode_files_tensor_oriented(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias),
+                                                           turn, used_turn, None, status, stream)
+        turns = list(used_turn)[:n]
+    elif den != 1:
         what = "ffhip_jpeg_decode_files_tensor_scaled"
         rc = L.ffhip_jpeg_decode_files_tensor_scaled(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias),
                                                      (C.c_int * max(n, 1))(*([den] * max(n, 1))), used, None, status, stream)
@@ -192,7 +235,8 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
     else:
         tensors = [None if status[i] else tensors[i] for i in range(n)]
         result = tensors if strict else (tensors, status)
-    return (result, list(used)[:n]) if return_reduce else result
+    extras = ([list(used)[:n]] if return_reduce else []) + ([turns] if return_orientation else [])
+    return (result, *extras) if extras else result
 
 
 def _jpeg_size(f):
@@ -206,7 +250,8 @@ def _webp_size(f):
 
 
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                           strict=True, size=None, antialias=True, reduce=1, return_reduce=False):
+                           strict=True, size=None, antialias=True, reduce=1, return_reduce=False, apply_exif_orientation=False, orientation=None,
+                           return_orientation=False):
     """ffhip_jpeg_decode_files_tensor: baseline JPEG files (list of bytes) of any geometry in one call -> torch tensors on the current
     device, written on torch's current stream (the call synchronises it).
       dtype    torch.uint8 (None), torch.float16 or torch.float32;  layout 'CHW' / 'HWC';  order 'RGB' / 'BGR'
@@ -224,17 +269,27 @@ def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
                the mapped rectangle's size.  'auto' (needs size): per file the largest of 8, 4, 2, 1 at which its rectangle still
                covers size (ops.jpeg_scale_choose), the resize doing the rest
       return_reduce  also return the denominator each file was decoded at
+      apply_exif_orientation  True: every picture is delivered UPRIGHT, as its EXIF orientation tag says (ops.jpeg_exif_orientation; what
+               torchvision's argument of this name and PIL's ImageOps.exif_transpose do), by ffhip_jpeg_decode_files_tensor_oriented: the
+               tensors have the upright shape (a stored 4000 x 3000 of orientation 6 or 8 is 3000 wide and 4000 high), roi and size are
+               in upright coordinates, and stack=True with size takes landscape and portrait files together.  False: the stored picture
+      orientation  None, or an EXIF orientation 1..8 for all files or a list of one per file: applied whatever the files say (and
+               whatever apply_exif_orientation says)
+      return_orientation  also return the orientation each file was delivered at (0: the probe refused the file)
     Returns the list of tensors; with strict=False a failing file does not raise: its entry is None, and the per-file status codes
-    follow as a second element.  With return_reduce: (that, [denominators])."""
+    follow as a second element.  With return_reduce and / or return_orientation: (that, [denominators], [orientations])."""
     return _decode_to_tensors(lambda L: L.ffhip_jpeg_decode_files_tensor, "ffhip_jpeg_decode_files_tensor" + ("_resized" if size is not None else ""),
                               _jpeg_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias, reduce,
-                              return_reduce)
+                              return_reduce, ops.jpeg_exif_orientation, apply_exif_orientation, orientation, return_orientation)
 
 
 def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                           strict=True, size=None, antialias=True):
-    """ffhip_webp_decode_files_tensor (with size: ffhip_webp_decode_files_tensor_resized): lossy WebP files; arguments and result as
+                           strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False):
+    """ffhip_webp_decode_files_tensor (with size: ffhip_webp_decode_files_tensor_resized; with apply_exif_orientation or orientation:
+    ffhip_webp_decode_files_tensor_oriented, the tag read from the file's EXIF chunk): lossy WebP files; arguments and result as
     decode_jpeg_to_tensors.  A file's display size is the
     probe's width x height as far as the decoded picture holds it."""
     return _decode_to_tensors(lambda L: L.ffhip_webp_decode_files_tensor, "ffhip_webp_decode_files_tensor" + ("_resized" if size is not None else ""),
-                              _webp_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias)
+                              _webp_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias,
+                              tag=ops.webp_exif_orientation, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
+                              return_orientation=return_orientation)

@@ -950,6 +950,84 @@ int ffhip_jpeg_decode_files_tensor_scaled(const uint8_t *const *files, const siz
  * arguments before that, or one of no files, leaves the count as it was. */
 int ffhip_debug_tensor_last_parts(void);
 
+/* ---- EXIF orientation: decoded pictures upright (ffhip_exif.c, ffhip_orient.hip) ----
+ * A camera stores the sensor's picture and says in the EXIF orientation tag (0x0112, 1..8) how to hold it; the decoders above deliver the
+ * STORED picture S, Ws x Hs, as the reference does (it skips APP1, format/jpg.c:836-840).  The UPRIGHT picture U of orientation o:
+ *   o   U size    U[y][x] =                  o   U size    U[y][x] =
+ *   1   Ws x Hs   S[y][x]                    5   Hs x Ws   S[x][y]
+ *   2   Ws x Hs   S[y][Ws-1-x]               6   Hs x Ws   S[Hs-1-x][y]
+ *   3   Ws x Hs   S[Hs-1-y][Ws-1-x]          7   Hs x Ws   S[Hs-1-x][Ws-1-y]
+ *   4   Ws x Hs   S[Hs-1-y][x]               8   Hs x Ws   S[x][Ws-1-y]
+ * (what PIL.ImageOps.exif_transpose and torchvision's apply_exif_orientation deliver).  Pure pixel movement: no byte changes its value. */
+/* Host only, no device needed.  The orientation tag of a JPEG file: the marker segments behind SOI are walked up to the first SOS or EOI,
+ * the first APP1 whose payload begins "Exif\0\0" decides; in it the TIFF header ("II*\0" or "MM\0*"), IFD0 and its 12-byte entries, of
+ * which the first with tag 0x0112 counts: type SHORT or LONG, count 1, a value in 1..8, read in the file's byte order.  No other IFD is
+ * followed.  FFHIP_EINVAL only for a NULL argument; otherwise FFHIP_OK, with *orientation = 1 for no tag, a malformed one or a value outside
+ * 1..8: a bad tag never fails a decode.  Nothing outside file[0 .. len) is read, whatever the lengths and offsets in the file say. */
+int ffhip_jpeg_exif_orientation(const uint8_t *file, size_t len, int *orientation);
+/* The same for a WebP file: the RIFF chunks are walked by their sizes (with the format's padding byte behind an odd one), past the `VP8 `
+ * chunk, to the first `EXIF` chunk, whose payload is that TIFF structure, with or without "Exif\0\0" in front. */
+int ffhip_webp_exif_orientation(const uint8_t *file, size_t len, int *orientation);
+/* Host only.  *uw x *uh = the upright size of a stored w x h picture.  FFHIP_EINVAL for o outside 1..8, a side below 1, a NULL result. */
+int ffhip_orient_size(int w, int h, int o, int *uw, int *uh);
+/* Host only.  A rectangle of the UPRIGHT picture mapped onto the stored ws x hs picture: the rectangle of S that holds its pixels (under
+ * o = 6, (x0, y0, w, h) becomes (y0, hs - x0 - w, h, w)).  Orienting that stored rectangle on its own gives the upright rectangle:
+ * orient(S)[upright] == orient(S[stored]).  FFHIP_EINVAL for o outside 1..8, a side of the picture below 1 and for a rectangle that is
+ * empty or leaves the upright picture. */
+int ffhip_orient_rect(int ws, int hs, int o, const ffhip_rect *upright, ffhip_rect *stored);
+/* Host only.  The orientation that undoes o: 1..5 and 7 are their own inverse, 6 and 8 each other's.  FFHIP_EINVAL outside 1..8. */
+int ffhip_orient_inverse(int o);
+/* One picture of a batch.  All pointers are DEVICE pointers.
+ *   d_src, src_pitch   a BGRA picture as the decode calls write it: 4-byte aligned, pitch a multiple of 4
+ *   x0, y0, width,     the STORED rectangle to turn (width, height >= 1, x0, y0 >= 0); the caller keeps it inside the picture, the call
+ *   height             checks what ffhip_tensor_item's line says: 4 (x0 + width) <= src_pitch, and (y0 + height) src_pitch < 2^31
+ *   d_dst, dst_pitch   the upright picture (height x width pixels for orientation 5..8): 4-byte aligned, dst_pitch a multiple of 4,
+ *                      >= 4 x the upright width and <= 2^32
+ *   orientation        1..8; 1 is a plain copy of the rectangle
+ * Only the upright width x height pixels are written (one dword store each): the row padding of the destination stays untouched.
+ * Source and destination must not overlap. */
+typedef struct ffhip_orient_item {
+    const uint8_t *d_src;
+    int64_t src_pitch;
+    int32_t x0, y0, width, height;
+    uint8_t *d_dst;
+    int64_t dst_pitch;
+    int32_t orientation;
+} ffhip_orient_item;
+/* The whole batch, rectangles of any sizes and orientations, in ONE launch behind the small launch that writes the per-workgroup table.  A
+ * workgroup moves one 64 x 64 tile of a stored rectangle: straight (1..4: mirrored reads, row stores) or through an LDS tile (5..8: rows
+ * in, columns out, both sides of memory in runs of 64 dwords).  `items` is a HOST array; every check is made before
+ * anything is enqueued (FFHIP_EINVAL -- n < 0, NULL items with n > 0, an item outside what its fields' lines above say --, on a machine
+ * without a device too; FFHIP_ENODEV there for good arguments).  n == 0 is FFHIP_OK.  Only enqueues on `stream`; the records and the
+ * per-workgroup table are library scratch of the stream. */
+int ffhip_bgra_orient_items(const ffhip_orient_item *items, int n, void *stream);
+/* Files in, UPRIGHT tensors out: supersets of ffhip_jpeg_decode_files_tensor_scaled and ffhip_webp_decode_files_tensor_resized.
+ *   orient[i]    1..8: the orientation to apply, whatever the file says; 0: the file's tag (the functions above).  orient == NULL: every
+ *                file's tag.  Any other value: FFHIP_EINVAL for the whole call.  orient_out[i] (may be NULL) receives the value used, 0
+ *                for a file the probe refused
+ *   roi, out_size, outs   in UPRIGHT coordinates: roi[i] a rectangle of the upright picture (NULL: all of it), out_size[i] the upright
+ *                size to resize it to (out_size may be NULL: no resize; `filter` is still checked), outs[i] laid out for the upright result
+ *   denom, denom_out (JPEG)   as ffhip_jpeg_decode_files_tensor_scaled; denom may be NULL: every file at full size
+ * Decode, reduced decode and resize run in the STORED axes exactly as in the calls above: the rectangle is mapped by ffhip_orient_rect,
+ * out_size[i] is swapped for 5..8, ffhip_jpeg_scale_choose and ffhip_jpeg_scaled_rect see those.  Then ffhip_bgra_orient_items moves whole
+ * pixels once -- the resized picture where there is a resize, the (mapped) rectangle otherwise -- into part scratch at pitch 4 x upright
+ * width, which counts towards the part budget, and the tensor stage reads that.  So the result is, byte for byte, the table above applied
+ * to what the calls above deliver for the mapped rectangle and size, and the expensive stages see no more pixels than there.  (The resize
+ * rule's tie-break, "the lowest k on a tie", is not mirror-symmetric: resizing the upright picture could differ in a rare last bit.  The
+ * result is DEFINED in the stored axes.)  Files of orientation 1 take the way of the calls above; a batch of nothing else issues their
+ * launches and gives their bytes.  status[i] = FFHIP_EINVAL also for a rectangle that leaves the UPRIGHT picture and for an output laid
+ * out for the un-swapped size where the tensor stage refuses it; that file alone is affected. */
+int ffhip_jpeg_decode_files_tensor_oriented(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                            const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                            const int *denom, int *denom_out, const int *orient, int *orient_out, ffhip_jpeg_geom *geom_out,
+                                            int *status, void *stream);
+int ffhip_webp_decode_files_tensor_oriented(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                            const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                            const int *orient, int *orient_out, ffhip_webp_info *info_out, int *status, void *stream);
+/* Diagnostics: the items the calling thread's last ffhip_*_decode_files_tensor* call sent through ffhip_bgra_orient_items, all its parts
+ * together: 0 for a batch of orientation 1 only and for the calls without orientation.  Reset where ffhip_debug_tensor_last_parts is. */
+int ffhip_debug_orient_last_items(void);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
