@@ -35,10 +35,13 @@ EXPORTS = [
     "ffhip_jpeg_exif_orientation", "ffhip_webp_exif_orientation", "ffhip_orient_size", "ffhip_orient_rect", "ffhip_orient_inverse",
     "ffhip_bgra_orient_items", "ffhip_jpeg_decode_files_tensor_oriented", "ffhip_webp_decode_files_tensor_oriented",
     "ffhip_debug_orient_last_items",
+    "ffhip_jpeg_probe_any", "ffhip_jpeg_progressive_decode", "ffhip_jpeg_progressive_batch_gpu", "ffhip_jpeg_decode_files_mixed_device_ex",
+    "ffhip_debug_progressive_last", "ffhip_jpeg_decode_files_tensor_ex",
 ]
 
 
 FFHIP_EINVAL, FFHIP_ENOMEM, FFHIP_ENODEV, FFHIP_EIO = -22, -12, -19, -5     # include/ffpic_hip.h:34-37
+FFHIP_JPEG_ACCEPT_PROGRESSIVE, FFHIP_JPEG_MAX_SCANS = 1, 128
 FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1002, -1003
 
 
@@ -338,6 +341,14 @@ def lib():
                                                           C.POINTER(JpegGeom), vp, vp]
     L.ffhip_webp_decode_files_tensor_oriented.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
                                                           C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(WebpInfo), vp, vp]
+    L.ffhip_jpeg_probe_any.argtypes = [vp, sz, C.POINTER(JpegGeom), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.ffhip_jpeg_progressive_decode.argtypes = [vp, sz, C.POINTER(JpegGeom), vp, vp, vp, vp, ci]
+    L.ffhip_jpeg_progressive_batch_gpu.argtypes = [vp, vp, ci, ci, C.POINTER(JpegGeom), vp, vp, vp, vp, ci, vp, vp]
+    L.ffhip_jpeg_decode_files_mixed_device_ex.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(ci), C.c_uint, C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_debug_progressive_last.argtypes = [C.POINTER(ci)]
+    L.ffhip_jpeg_decode_files_tensor_ex.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                    C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.c_uint,
+                                                    C.POINTER(JpegGeom), vp, vp]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

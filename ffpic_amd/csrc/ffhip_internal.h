@@ -119,6 +119,7 @@ enum FfhipScratchKind {
     SCRATCH_ORIENT_ITEMS = 74,     /* ffhip_bgra_orient_items' records and per-workgroup table, pinned records */
     SCRATCH_ORIENT_BGRA = 75,      /* ffhip_*_decode_files_tensor_oriented: a part's upright BGRA pictures */
     SCRATCH_JPEG_SCALED = 80,     /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_scaled's records and per-workgroup table, pinned records */
+    SCRATCH_HUFF_PROG = 90,       /* ffhip_jpeg_progressive_batch_gpu: staged scans, tables, records and work lists (and their pinned copy) */
 };
 
 /* ffhip_vp8_decode_items (ffhip_vp8_frame.hip): its levels items' residual stage (ffhip_vp8.hip) and its device mode check
@@ -178,6 +179,12 @@ struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_j
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
                                 const ffhip_jpeg_geom *geoms, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant,
                                 int *status, void *stream, const FfhipHuffThen *then);
+/* ffhip_jpeg_progressive_batch_gpu (ffhip_huff_prog_gpu.hip) with per-picture geometries of one layout class, a k_max per picture (k_maxes, or NULL:
+ * k_max for all) and the hand-off (items form only).  counts[4] += progressive files, scans decoded, scans skipped, levels launched.  FFHIP_OK when the
+ * batch ran, whatever the files' own verdicts in status[]; FFHIP_EINVAL when the call refuses the batch as a whole */
+int jpeg_progressive_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
+                                    const ffhip_jpeg_geom *geoms, int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant,
+                                    int k_max, const int *k_maxes, int *status, void *stream, const FfhipHuffThen *then, int counts[4]);
 /* The layout classes of the fused JPEG kernels (ffhip_jpeg.hip: 4:2:0, 4:4:4, 4:2:2, 4:4:0, h4v1, h1v4, grey) and what one call chooses for its
  * kernels, read from the FFHIP_JPEG_* switches once, up front */
 #define JPEG_CLASSES 7

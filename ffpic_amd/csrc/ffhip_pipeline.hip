@@ -12,10 +12,12 @@
 #include "ffhip_internal.h"
 #include "ffhip_entropy_internal.h"
 #include "ffhip_jpeg_scaled_body.h"
+#include "ffhip_jpeg_prog_internal.h"
 
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <mutex>
 #include <thread> /* copy_out */
 #include <vector>
@@ -316,10 +318,14 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
 /* denom == NULL: every picture at full size, the call as it was.  Otherwise picture i at 1 / denom[i] of its size (ffhip_jpeg_recon_items_scaled):
  * its output is checked against the SCALED coded width, and the denominators travel with the items to both reconstruction sites -- behind
  * the device entropy decoder's parts, and behind the host threads' upload */
+/* flags (ffhip_jpeg_decode_files_mixed_device_ex): 0, the call as it was.  FFHIP_JPEG_ACCEPT_PROGRESSIVE: the probe is ffhip_jpeg_probe_any, and a
+ * class's progressive files take a turn of their own behind its baseline files: the same planes, items and reconstruction, another front end --
+ * jpeg_progressive_batch_gpu_impl or ffhip_jpeg_progressive_decode on host threads (FFHIP_JPEG_PROGRESSIVE_GPU; unset: host threads, DESIGN.md
+ * 4.14), with k_max = 0 / 4 / 24 for a file at 1/8, 1/4, 1/2 size: the reconstruction reads no coefficient behind those */
 static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
-                                   const int *denom, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+                                   const int *denom, unsigned flags, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
+    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status)) || (flags & ~FFHIP_JPEG_ACCEPT_PROGRESSIVE)) return FFHIP_EINVAL;
     for (int i = 0; denom && i < n; i++)
         if (!jpeg_denom_ok(denom[i])) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
@@ -329,12 +335,15 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
      * or pitch ffhip_jpeg_recon_items refuses) has its code now and takes no further part ---- */
     std::vector<ffhip_jpeg_geom> geoms((size_t)n);
     std::vector<int> cls((size_t)n, -1);
+    std::vector<int> prog((size_t)n, 0); /* 1: a progressive file (never with flags = 0) */
+    int prog_last[5] = {0, 0, 0, 0, 0};
     const JpegChoices ch = jpeg_choices();
     ffhip_parallel_for(n, n_threads, [&](int i) {
         int w = 0, h = 0;
         ffhip_jpeg_geom &g = geoms[(size_t)i];
         memset(&g, 0, sizeof(g));
-        status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
+        if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) status[i] = files[i] && lens[i] ? ffhip_jpeg_probe_any(files[i], lens[i], &g, &w, &h, &prog[(size_t)i]) : FFHIP_EINVAL;
+        else status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
         if (geom_out) geom_out[i] = g;
         if (status[i]) return;
         if (denom && denom[i] > 1) /* the output holds the scaled picture: rows of 8 / denom x h x mcu_cols pixels */
@@ -346,10 +355,12 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
     int rc = FFHIP_OK;
-    for (int c = 0; c < JPEG_CLASSES && rc == FFHIP_OK; c++) {
+    const int turns = (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) ? 2 : 1;
+    for (int turn = 0; turn < JPEG_CLASSES * turns && rc == FFHIP_OK; turn++) {
+        const int c = turn / turns, pg = turn % turns; /* a class's baseline files, then its progressive files */
         std::vector<int> idx;
         for (int i = 0; i < n; i++)
-            if (cls[(size_t)i] == c) idx.push_back(i);
+            if (cls[(size_t)i] == c && prog[(size_t)i] == pg) idx.push_back(i);
         const int nc = (int)idx.size();
         if (!nc) continue;
         std::vector<const uint8_t *> cf((size_t)nc);
@@ -374,7 +385,21 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
         if (!dev) { rc = FFHIP_ENOMEM; break; }
         const Planes d = blk.at(dev);
         bool done = false;
-        if (jpeg_entropy_on_device(cf[0], cl[0], nc)) {
+        std::vector<int> kmax((size_t)nc, 63); /* progressive files: the last coefficient the reconstruction reads */
+        for (int k = 0; pg && k < nc; k++) kmax[(size_t)k] = cd[(size_t)k] == 8 ? 0 : cd[(size_t)k] == 4 ? 4 : cd[(size_t)k] == 2 ? 24 : 63;
+        const char *pgpu = pg ? FFHIP_ENV("FFHIP_JPEG_PROGRESSIVE_GPU") : nullptr;
+        if (pg && pgpu && pgpu[0] == '1') {
+            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom ? cd.data() : nullptr};
+            int counts[4] = {0, 0, 0, 0};
+            const int grc = jpeg_progressive_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, 63, kmax.data(), cs.data(),
+                                                            stream, &then, counts);
+            if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
+            done = grc == FFHIP_OK;
+            if (done) {
+                for (int q = 0; q < 4; q++) prog_last[q] += counts[q];
+                prog_last[4] = 1;
+            }
+        } else if (!pg && jpeg_entropy_on_device(cf[0], cl[0], nc)) {
             const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom ? cd.data() : nullptr};
             const int grc = jpeg_entropy_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, cs.data(), stream, &then);
             if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
@@ -386,12 +411,26 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
             uint8_t *pin = ffhip_pinned_scratch(SCRATCH_FILES_MIXED, stream, blk.bytes);
             if (!pin) { rc = FFHIP_ENOMEM; break; }
             const Planes h = blk.at(pin);
+            std::vector<std::array<int, 3>> pcounts(pg ? (size_t)nc : 0);
             ffhip_parallel_for(nc, n_threads, [&](int k) {
                 const ffhip_jpeg_geom &g = cg[(size_t)k];
                 const size_t b = base[(size_t)k];
+                if (pg) {
+                    pcounts[(size_t)k] = {0, 0, 0};
+                    cs[(size_t)k] = ffhip_prog_decode_host(cf[(size_t)k], cl[(size_t)k], &g, h.y + b * g.h * g.v * 64, h.u ? h.u + b * 64 : nullptr,
+                                                           h.v ? h.v + b * 64 : nullptr, h.q + (size_t)k * 256, kmax[(size_t)k], pcounts[(size_t)k].data());
+                    return;
+                }
                 cs[(size_t)k] = ffhip_jpeg_entropy_decode(cf[(size_t)k], cl[(size_t)k], &g, h.y + b * g.h * g.v * 64, h.u ? h.u + b * 64 : nullptr,
                                                           h.v ? h.v + b * 64 : nullptr, h.q + (size_t)k * 256);
             });
+            if (pg) {
+                for (int k = 0; k < nc; k++) {
+                    prog_last[0] += pcounts[(size_t)k][0] + pcounts[(size_t)k][1] > 0; /* files that parsed, as the device front end counts them */
+                    for (int q = 0; q < 3; q++) prog_last[1 + q] += pcounts[(size_t)k][(size_t)q];
+                }
+                prog_last[4] = 0;
+            }
             if (hipMemcpyAsync(dev, pin, blk.bytes, hipMemcpyHostToDevice, st) != hipSuccess) { rc = FFHIP_EIO; break; }
             std::vector<ffhip_jpeg_item> good;
             std::vector<int> good_d;
@@ -408,17 +447,25 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
         }
         for (int k = 0; k < nc; k++) status[idx[(size_t)k]] = cs[(size_t)k];
     }
+    if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) ffhip_prog_note_last(prog_last);
     if (rc) return rc;
     for (int i = 0; i < n; i++)
         if (status[i]) return status[i];
     return FFHIP_OK;
 }
 
+extern "C" int ffhip_jpeg_decode_files_mixed_device_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                                       const int64_t *pitch, const int *denom, unsigned flags, ffhip_jpeg_geom *geom_out,
+                                                       int *status, void *stream)
+{
+    return jpeg_decode_files_mixed(files, lens, n, n_threads, d_bgra, pitch, denom, flags, geom_out, status, stream);
+}
+
 extern "C" int ffhip_jpeg_decode_files_mixed_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
                                                     uint8_t *const *d_bgra, const int64_t *pitch, ffhip_jpeg_geom *geom_out,
                                                     int *status, void *stream)
 {
-    return jpeg_decode_files_mixed(files, lens, n, n_threads, d_bgra, pitch, nullptr, geom_out, status, stream);
+    return jpeg_decode_files_mixed(files, lens, n, n_threads, d_bgra, pitch, nullptr, 0u, geom_out, status, stream);
 }
 
 extern "C" int ffhip_jpeg_decode_files_mixed_device_scaled(const uint8_t *const *files, const size_t *lens, int n, int n_threads,
@@ -426,5 +473,5 @@ extern "C" int ffhip_jpeg_decode_files_mixed_device_scaled(const uint8_t *const 
                                                            ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
     if (n > 0 && !denom) return FFHIP_EINVAL;
-    return jpeg_decode_files_mixed(files, lens, n, n_threads, d_bgra, pitch, denom, geom_out, status, stream);
+    return jpeg_decode_files_mixed(files, lens, n, n_threads, d_bgra, pitch, denom, 0u, geom_out, status, stream);
 }

@@ -10,6 +10,7 @@
 #include "ffhip_jpeg_scaled_body.h"
 #include "ffhip_orient_body.h"
 #include "ffhip_tensor_body.h"
+#include "ffhip_jpeg_prog_internal.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -354,9 +355,9 @@ private:
  * -- coded and display size, a pitch rounded up to 16 bytes -- and the rectangle is the full-size one mapped onto it */
 int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
                       const ffhip_rect *roi, const TensorResize &rs, const int *denom, int *denom_out, const TensorOrient &to,
-                      ffhip_jpeg_geom *geom_out, int *status, void *stream)
+                      ffhip_jpeg_geom *geom_out, int *status, void *stream, unsigned flags = 0u)
 {
-    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status) || !orient_files_args_ok(n, to)) return FFHIP_EINVAL;
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status) || !orient_files_args_ok(n, to) || (flags & ~FFHIP_JPEG_ACCEPT_PROGRESSIVE)) return FFHIP_EINVAL;
     for (int i = 0; denom && i < n; i++)
         if (denom[i] != 0 ? !jpeg_denom_ok(denom[i]) : !rs.out_size) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
@@ -368,7 +369,8 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
         ffhip_jpeg_geom g;
         memset(&g, 0, sizeof(g));
         int w = 0, h = 0;
-        status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
+        if (flags) status[i] = files[i] && lens[i] ? ffhip_jpeg_probe_any(files[i], lens[i], &g, &w, &h, nullptr) : FFHIP_EINVAL;
+        else status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
         if (geom_out) geom_out[i] = g;
         pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h, 4LL * g.mcu_cols * 8 * g.h};
         if (to.on) {
@@ -394,14 +396,26 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
         pic[(size_t)i] = TensorPicture{cw, chh, jpeg_scaled_len(w, d), jpeg_scaled_len(h, d), (4LL * cw + 15) & ~15LL};
         if (roi && r_ok) mapped[(size_t)i] = jpeg_scaled_rect_of(w, h, d, r);
     });
-    return tensor_files_run(n, fmt, outs, denom && roi ? mapped.data() : stored.roi(), TensorResize{stored.out_size(), rs.filter}, pic, stored.orient(), status, stream,
+    int prog_total[5] = {0, 0, 0, 0, 0}; /* the parts' ffhip_debug_progressive_last, summed (the front end: the last part's) */
+    const int rc = tensor_files_run(n, fmt, outs, denom && roi ? mapped.data() : stored.roi(), TensorResize{stored.out_size(), rs.filter}, pic, stored.orient(), status, stream,
                             [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+        if (flags) { /* ffhip_jpeg_decode_files_tensor_ex: the parts go through the call that takes progressive files */
+            const int prc = ffhip_jpeg_decode_files_mixed_device_ex(files + first, lens + first, cnt, n_threads, d_bgra, pitch, denom ? den.data() + first : nullptr, flags,
+                                                                    geom_out ? geom_out + first : nullptr, status + first, stream);
+            int last[5];
+            ffhip_debug_progressive_last(last);
+            for (int q = 0; q < 4; q++) prog_total[q] += last[q];
+            prog_total[4] = last[4];
+            return prc;
+        }
         if (denom)
             return ffhip_jpeg_decode_files_mixed_device_scaled(files + first, lens + first, cnt, n_threads, d_bgra, pitch, den.data() + first,
                                                                geom_out ? geom_out + first : nullptr, status + first, stream);
         return ffhip_jpeg_decode_files_mixed_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, geom_out ? geom_out + first : nullptr,
                                                     status + first, stream);
     });
+    if (flags) ffhip_prog_note_last(prog_total);
+    return rc;
 }
 
 int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
@@ -475,6 +489,16 @@ extern "C" int ffhip_jpeg_decode_files_tensor_oriented(const uint8_t *const *fil
     if (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS) return FFHIP_EINVAL;
     return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, denom, denom_out, TensorOrient{true, orient, orient_out},
                              geom_out, status, stream);
+}
+
+extern "C" int ffhip_jpeg_decode_files_tensor_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                 const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                 const int *denom, int *denom_out, const int *orient, int *orient_out, unsigned flags,
+                                                 ffhip_jpeg_geom *geom_out, int *status, void *stream)
+{
+    if (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS) return FFHIP_EINVAL;
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, denom, denom_out, TensorOrient{true, orient, orient_out},
+                             geom_out, status, stream, flags);
 }
 
 extern "C" int ffhip_webp_decode_files_tensor_oriented(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,

@@ -306,6 +306,65 @@ def jpeg_probe(data):
     return g, w.value, h.value
 
 
+def jpeg_probe_any(data):
+    """ffhip_jpeg_probe_any: geometry of a baseline OR progressive JPEG file (bytes) -> (JpegGeom, width, height, progressive)."""
+    L = capi.lib()
+    g, w, h, pg = capi.JpegGeom(), C.c_int(), C.c_int(), C.c_int()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    capi.check(L.ffhip_jpeg_probe_any(buf.ctypes.data if buf.size else None, buf.size, C.byref(g), C.byref(w), C.byref(h), C.byref(pg)),
+               "ffhip_jpeg_probe_any")
+    return g, w.value, h.value, bool(pg.value)
+
+
+def jpeg_progressive_decode(data, k_max=63):
+    """ffhip_jpeg_progressive_decode: the host decoder of progressive files (T.81 Annex G).  Returns (geom, cy, cu, cv, quant[4][64]) in the
+    layout of jpeg_entropy_batch for one file; scans with Ss > k_max are skipped and their coefficients read as zero.  No device."""
+    L = capi.lib()
+    g, _, _, _ = jpeg_probe_any(data)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    cy = np.empty(g.y_blocks * 64, np.int16)
+    cu = np.empty(g.c_blocks * 64, np.int16) if g.ncomp == 3 else None
+    cv = np.empty(g.c_blocks * 64, np.int16) if g.ncomp == 3 else None
+    quant = np.empty((4, 64), np.uint16)
+    capi.check(L.ffhip_jpeg_progressive_decode(buf.ctypes.data, buf.size, C.byref(g), _vp(cy), _vp(cu), _vp(cv), _vp(quant), k_max),
+               "ffhip_jpeg_progressive_decode")
+    return g, cy, cu, cv, quant
+
+
+def jpeg_progressive_batch_gpu(files, k_max=63, n_threads=4, strict=True):
+    """ffhip_jpeg_progressive_batch_gpu on progressive files of one geometry; planes come back to the host for inspection.  Returns
+    (geom, cy, cu, cv, quant[n][4][64]) like jpeg_entropy_batch_gpu; with strict=False a failing file does not raise and the per-file
+    status codes follow."""
+    L = capi.require_device()
+    g, _, _, _ = jpeg_probe_any(files[0])
+    n = len(files)
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    dy = DeviceBuffer(nbytes=n * g.y_blocks * 128)
+    du = DeviceBuffer(nbytes=max(n * g.c_blocks * 128, 16)) if g.ncomp == 3 else None
+    dv = DeviceBuffer(nbytes=max(n * g.c_blocks * 128, 16)) if g.ncomp == 3 else None
+    dq = DeviceBuffer(nbytes=n * 512)
+    status = (C.c_int * n)()
+    rc = L.ffhip_jpeg_progressive_batch_gpu(ptrs, lens, n, n_threads, C.byref(g), dy.ptr, du.ptr if du else None, dv.ptr if dv else None, dq.ptr,
+                                            k_max, status, None)
+    if strict or rc not in (0, capi.FFHIP_EINVAL):
+        capi.check(rc, "ffhip_jpeg_progressive_batch_gpu")
+    cy = dy.to_host((n * g.y_blocks * 64,), np.int16)
+    cu = du.to_host((n * g.c_blocks * 64,), np.int16) if du else None
+    cv = dv.to_host((n * g.c_blocks * 64,), np.int16) if dv else None
+    out = (g, cy, cu, cv, dq.to_host((n, 4, 64), np.uint16))
+    return out if strict else out + (list(status),)
+
+
+def progressive_last():
+    """ffhip_debug_progressive_last: (progressive files, scans decoded, scans skipped, levels launched, front end: 0 host, 1 device) of the
+    calling thread's last progressive call."""
+    out = (C.c_int * 5)()
+    capi.check(capi.lib().ffhip_debug_progressive_last(out), "ffhip_debug_progressive_last")
+    return tuple(out)
+
+
 def jpeg_entropy_batch(files, n_threads=4):
     """Host-side Huffman decode of same-geometry JPEG files (list of bytes) into the planes the
     reconstruction reads (format/jpg.c:255-415, 588-655).  Returns (geom, cy, cu, cv, quant[n][4][64])."""
@@ -593,18 +652,20 @@ def vp8_decode_items(items, stream=None):
     capi.check(L.ffhip_vp8_decode_items(arr, n, stream), "ffhip_vp8_decode_items")
 
 
-def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True, crop=True):
+def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True, crop=True, progressive=False):
     """ffhip_jpeg_decode_files_mixed_device: baseline JPEG files of any geometry (list of bytes) in one call.  Every picture
     gets its place in ONE device allocation, at a 16-byte-aligned offset with the pitch 4 x its coded width.  Returns
     (geoms, [host BGRA [h][w][4] cropped to each file's display size (crop=False: the coded size)], device buffer); with
-    strict=False a failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows."""
+    strict=False a failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows.
+    progressive=True: ffhip_jpeg_decode_files_mixed_device_ex with FFHIP_JPEG_ACCEPT_PROGRESSIVE -- progressive files are probed
+    (jpeg_probe_any) and decoded too; False, the default, refuses them as ever."""
     L = capi.require_device()
     n = len(files)
     offs, pitches, total = [], [], 0
     sizes = []
     for f in files:
         try:
-            g, w, h = jpeg_probe(f)
+            g, w, h = jpeg_probe_any(f)[:3] if progressive else jpeg_probe(f)
             pitch, rows = g.width * 4, g.height
         except capi.FfhipError:
             w = h = pitch = rows = 0
@@ -620,7 +681,10 @@ def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True,
     pitch_arr = (C.c_int64 * n)(*pitches)
     geoms = (capi.JpegGeom * n)()
     status = (C.c_int * n)()
-    rc = L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n, n_threads, outs, pitch_arr, geoms, status, stream)
+    if progressive:
+        rc = L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n, n_threads, outs, pitch_arr, None, capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE, geoms, status, stream)
+    else:
+        rc = L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n, n_threads, outs, pitch_arr, geoms, status, stream)
     if strict:
         capi.check(rc, "ffhip_jpeg_decode_files_mixed_device")
     elif rc not in (0, capi.FFHIP_EINVAL):

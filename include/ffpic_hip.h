@@ -659,7 +659,8 @@ int ffhip_hevc_decode_tiles(const ffhip_hevc_tu *h_tus, const ffhip_hevc_tu *d_t
  * 771-855; coding/huffman.c:92-222): a baseline / extended-sequential Huffman scan becomes the
  * MCU-order coefficient planes and natural-order quant tables ffhip_jpeg_recon_batch reads.
  * Progressive, arithmetic, 12-bit, non-interleaved or chroma-subsampling-other-than-1x1 files
- * return FFHIP_EINVAL (keep the C path).  All pointers are HOST pointers. */
+ * return FFHIP_EINVAL from these calls (keep the C path); progressive files have entry points of their
+ * own further down ("progressive JPEG").  All pointers are HOST pointers. */
 int ffhip_jpeg_probe(const uint8_t *file, size_t len, ffhip_jpeg_geom *geom, int *width, int *height);
 int ffhip_jpeg_entropy_decode(const uint8_t *file, size_t len, const ffhip_jpeg_geom *expect,
                               int16_t *coef_y, int16_t *coef_u, int16_t *coef_v, uint16_t *quant /* [4][64] */);
@@ -1027,6 +1028,62 @@ int ffhip_webp_decode_files_tensor_oriented(const uint8_t *const *files, const s
 /* Diagnostics: the items the calling thread's last ffhip_*_decode_files_tensor* call sent through ffhip_bgra_orient_items, all its parts
  * together: 0 for a batch of orientation 1 only and for the calls without orientation.  Reset where ffhip_debug_tensor_last_parts is. */
 int ffhip_debug_orient_last_items(void);
+
+/* ---- progressive JPEG (ffhip_jpeg_progressive.c, ffhip_jpeg_prog_body.h, ffhip_huff_prog_gpu.hip) ----
+ * SOF2 files, decoded by ITU-T T.81 Annex G into the SAME coefficient planes a baseline file of the same quantised coefficients gives: the
+ * reconstruction behind the planes is the one above, and the tests hold every file against its baseline twin.  (The reference's progressive
+ * branches, format/jpg.c:255-415, 512-576, are nothing to be in parity with: DESIGN.md 2.)  Every call above keeps refusing such files; what
+ * follows is opt-in.
+ * Accepted: 8-bit, Huffman, 1 or 3 components in the layouts of ffhip_jpeg_probe; DC scans interleaved or not, AC scans of one component;
+ * DHT and DRI redefined between scans.  FFHIP_EINVAL at parse time, before anything is decoded: arithmetic, 12-bit and lossless files, an AC
+ * scan of several components, Ss = 0 with Se != 0, Se < Ss, Se > 63, a progression that breaks G.1.1.1.1 (a first scan with Ah != 0, a later
+ * one whose Ah is not the previous Al or whose Al is not Ah - 1), an AC scan of a component before its DC, a DQT behind the first SOS, more
+ * than FFHIP_JPEG_MAX_SCANS scans (a bound on hostile files, not on real ones), a table not yet defined, a missing EOI.  An incomplete
+ * progression that ends in EOI is valid: a band never sent stays zero, bits never refined stay as they are. */
+#define FFHIP_JPEG_MAX_SCANS 128
+/* Host only.  ffhip_jpeg_probe for baseline files (*progressive = 0); FFHIP_OK with *progressive = 1 for an accepted progressive file.
+ * progressive may be NULL. */
+int ffhip_jpeg_probe_any(const uint8_t *file, size_t len, ffhip_jpeg_geom *geom, int *width, int *height, int *progressive);
+/* Host only.  The outputs of ffhip_jpeg_entropy_decode in the same layout (MCU-order blocks, natural order inside a block, quant [4][64]
+ * de-zigzagged) from a progressive file.  k_max (0..63) = 63 decodes every scan; a scan with Ss > k_max is skipped whole and its
+ * coefficients read as zero, a scan with Ss <= k_max is decoded whole (and where such a scan is a refinement that reaches beyond k_max, the
+ * scans of its band are kept too: it needs their history).  FFHIP_EINVAL for a file the parse refuses and for a malformed scan: a code that
+ * matches no symbol, a DC category above 11, a refinement symbol with s other than 0 or 1, a run that carries k past Se, an EOBRUN larger
+ * than the blocks left in its restart interval, more bits consumed than an interval holds, fewer restart intervals than the scan needs.
+ * Nothing outside the planes is written whatever the file holds; the planes of a refused file are unspecified. */
+int ffhip_jpeg_progressive_decode(const uint8_t *file, size_t len, const ffhip_jpeg_geom *expect, int16_t *coef_y, int16_t *coef_u,
+                                  int16_t *coef_v, uint16_t *quant /* [4][64] */, int k_max);
+/* The same ON the device, with the plane layout and contract of ffhip_jpeg_entropy_batch_gpu: n progressive files of one geometry into
+ * DEVICE planes.  The host parses, unstuffs every kept scan into pinned memory and works out dependency levels (a scan waits for every
+ * earlier scan of its file that shares a component and a coefficient with it); the device runs k_jpeg_huff_prog once per level over the
+ * whole batch, one lane per (picture, scan, restart interval), behind one clear of the planes.  Verdicts are the host decoder's, file by
+ * file, in status[] (the body is shared).  Every argument check comes before anything is enqueued; FFHIP_ENODEV on a machine without a
+ * device for good arguments.  Synchronises `stream`. */
+int ffhip_jpeg_progressive_batch_gpu(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
+                                     int16_t *d_coef_y, int16_t *d_coef_u, int16_t *d_coef_v, uint16_t *d_quant, int k_max, int *status,
+                                     void *stream);
+/* ffhip_jpeg_decode_files_mixed_device (denom == NULL) / _scaled with flags.  flags = 0 is that call, byte for byte.
+ * FFHIP_JPEG_ACCEPT_PROGRESSIVE: files are probed with ffhip_jpeg_probe_any, each layout class is split into its baseline files (the path
+ * above, untouched) and its progressive files, and both are reconstructed by the same item kernels.  A file at 1/8, 1/4, 1/2 size is decoded
+ * with k_max = 0, 4, 24 (the largest zig-zag index of the leading 1x1, 2x2, 4x4 coefficients): whole AC scans are never read.
+ * FFHIP_JPEG_PROGRESSIVE_GPU=1 / =0 forces the device or the host-thread front end for the progressive files (host threads decode into
+ * pinned planes, one upload); unset: host threads (DESIGN.md 4.14 says why).  A class the device front end refuses goes to host threads.
+ * Any other flag bit: FFHIP_EINVAL. */
+#define FFHIP_JPEG_ACCEPT_PROGRESSIVE 1u
+int ffhip_jpeg_decode_files_mixed_device_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                            const int64_t *pitch, const int *denom /* may be NULL */, unsigned flags,
+                                            ffhip_jpeg_geom *geom_out, int *status, void *stream);
+/* ffhip_jpeg_decode_files_tensor_oriented with flags: 0 is that call; with FFHIP_JPEG_ACCEPT_PROGRESSIVE the files are probed with
+ * ffhip_jpeg_probe_any and the parts are decoded by ffhip_jpeg_decode_files_mixed_device_ex, so progressive files take part in every stage
+ * behind the decode (reduced size with its k_max, orientation, resize, tensor) exactly as their baseline twins do. */
+int ffhip_jpeg_decode_files_tensor_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                      const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                      const int *denom, int *denom_out, const int *orient, int *orient_out, unsigned flags,
+                                      ffhip_jpeg_geom *geom_out, int *status, void *stream);
+/* Diagnostics: the progressive files of the calling thread's last ffhip_jpeg_progressive_decode, ffhip_jpeg_progressive_batch_gpu,
+ * ffhip_jpeg_decode_files_mixed_device_ex or ffhip_jpeg_decode_files_tensor_ex call (all its parts together): out[0] progressive files, [1] scans decoded, [2] scans skipped (k_max), [3] levels launched
+ * (host front end: the deepest level of each file, summed), [4] the front end taken, 0 host, 1 device (the last class's). */
+int ffhip_debug_progressive_last(int out[5]);
 
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
