@@ -160,7 +160,9 @@ typedef struct ffhip_jpeg_geom {
  *                 layout an encoder writes -- 4:2:0, 4:4:4, 4:2:2, 4:4:0, 4:1:1 (h = 4), its
  *                 transpose (v = 4) and grey run fully fused -- and non-zero only for one component
  *                 with h*v > 1 blocks per MCU and for the three-block pairs (h or v = 3)
- *   stream        hipStream_t (NULL = default stream); the call only enqueues. */
+ *   stream        hipStream_t (NULL = default stream); the call only enqueues.  Every device operand is STREAM-ORDERED: the planes, d_quant
+ *                 and d_workspace are read, and d_bgra and d_workspace written, at the call's place in `stream` -- work the caller
+ *                 enqueued there in front of the call may produce them, work behind it may overwrite them. */
 int ffhip_jpeg_recon_batch(const ffhip_jpeg_geom *geom, int n_images, const int16_t *d_coef_y,
                            const int16_t *d_coef_u, const int16_t *d_coef_v,
                            const uint16_t *d_quant, int64_t quant_stride, uint8_t *d_bgra,
@@ -176,7 +178,11 @@ size_t ffhip_jpeg_workspace_bytes(const ffhip_jpeg_geom *geom, int n_images);
  *   d_bgra        its coded-size BGRA picture; pitch >= 4 x coded width, a multiple of 16, pitch x 16 < 2^31
  * Every device pointer 16-byte aligned.  `items` is a HOST array; every check is made before anything is enqueued
  * (FFHIP_EINVAL, on a machine without a device too; FFHIP_ENODEV there for good arguments).  Only enqueues on `stream`;
- * the records and the per-workgroup table are library scratch of the stream. */
+ * the records and the per-workgroup table are library scratch of the stream.  `items` is read before the call returns; what its
+ * device pointers name (planes, d_quant, d_bgra) is stream-ordered, as for ffhip_jpeg_recon_batch.  The records go up through pinned
+ * staging of the stream: a second call on a stream that has not reached the first one's upload waits on the host for that upload
+ * (not for the whole stream), and a call with more items than the stream's scratch holds synchronises the stream to grow it.  The same
+ * holds for every *_items call below. */
 typedef struct ffhip_jpeg_item {
     ffhip_jpeg_geom geom;
     const int16_t *d_coef_y, *d_coef_u, *d_coef_v;
@@ -213,7 +219,7 @@ const char *ffhip_jpeg_kernel_name(const ffhip_jpeg_geom *geom);
  *   ffhip_yuv420_to_bgra     == YUV420_to_BGRA32        (utils/colorspace.c:291-329; format/webp.c:1868)
  *   ffhip_yuv420_to_bgra_16  == YUV420_to_BGRA32_16bit  (utils/colorspace.c:628-669; coding/hevc.c:7260-7270)
  *   ffhip_yuv400_to_bgra_16  == YUV400_to_BGRA32_16bit  (utils/colorspace.c:715-742; coding/hevc.c:7271-7277)
- * Image i reads planes at +i*plane_stride_* and writes at d_bgra + i*image_stride. */
+ * Image i reads planes at +i*plane_stride_* and writes at d_bgra + i*image_stride.  Only enqueue; planes and d_bgra are stream-ordered. */
 int ffhip_yuv420_to_bgra(uint8_t *d_bgra, int pitch, const uint8_t *d_y, const uint8_t *d_u,
                          const uint8_t *d_v, int y_stride, int uv_stride, int mbrows, int mbcols,
                          int n_images, int64_t plane_stride_y, int64_t plane_stride_uv,
@@ -233,7 +239,8 @@ int ffhip_yuv400_to_bgra_16(uint8_t *d_bgra, int pitch, const int16_t *d_y, int 
  * ffhip_heif_grid_compose places rows*cols decoded BGRA tiles (tile j of the row-major `dimg`
  * list at d_tiles + j*tile_stride, tile_pitch bytes per row, all tile_w x tile_h) on the canvas
  * at (j % cols * tile_w, j / cols * tile_h), cropped to out_w x out_h.  NEW behaviour: the
- * reference decodes every tile into the same buffer (heif.c:305) and never places them. */
+ * reference decodes every tile into the same buffer (heif.c:305) and never places them.  Only enqueues; d_tiles and d_canvas are
+ * stream-ordered. */
 /* The picture buffer the reference's HEVC decoder allocates per slice and hands to the colour converter
  * (coding/hevc.c:7223-7236, 7258-7277): one int16 buffer of 2*size samples, Y at 0, Cb at `u_offset`, Cr at
  * `v_offset`; what ffhip_hevc_intra_recon / ffhip_yuv420_to_bgra_16 take as their plane pointers, strides and
@@ -284,7 +291,9 @@ int ffhip_vp8_residual_batch(long long n_mb, const int16_t *d_levels, const uint
  *   d_modes      the same [n_images][n_mb][20] records; [0] intra_y_mode, [18] segment_id
  *   d_filters    uint8 [4 segments][2 (i16x16, i4x4)][3] = sub_limit, inter_limit, hev_thresh
  *                (struct vp8_filter as calculate_filter_control_parameter leaves it,
- *                webp.c:1756-1803, format/webp.h:289-293) */
+ *                webp.c:1756-1803, format/webp.h:289-293)
+ * Only enqueues (the row form; FFHIP_VP8_LF_MODE=levels synchronises).  d_modes, d_filters and the planes, which are filtered in place,
+ * are all stream-ordered: there is no host copy of the modes here, nothing of them is looked at when the call is made. */
 /* The frame-header fields calculate_filter_control_parameter (format/webp.c:1756-1803) reads, as the reference's
  * header parser leaves them (format/webp.h:160-230), and the derivation itself on the host: the per-segment
  * {sub_limit, inter_limit, hev_thresh} triples ffhip_vp8_loopfilter takes as d_filters, and the filter_type
@@ -347,7 +356,8 @@ int ffhip_vp8_predict_loopfilter(int mbcols, int mbrows, int n_images, const uin
  *              scaling_list_enabled_flag == 0 (m = 16)
  *   bitdepth   BitDepthY or BitDepthC of the component the TUs belong to; epp =
  *              extended_precision_processing_flag
- *   d_residual int16 [n_tu][nTbS*nTbS]  r[] as construct_pic_pior_to_filtering consumes it */
+ *   d_residual int16 [n_tu][nTbS*nTbS]  r[] as construct_pic_pior_to_filtering consumes it
+ * Only enqueues; d_level, d_tuinfo, d_scaling and d_residual are stream-ordered. */
 int ffhip_hevc_residual_batch(int nTbS, long long n_tu, const int16_t *d_level, const uint8_t *d_tuinfo,
                               const uint8_t *d_scaling, int bitdepth, int epp, int16_t *d_residual,
                               void *stream);
@@ -378,7 +388,11 @@ int ffhip_hevc_residual_batch(int nTbS, long long n_tu, const int16_t *d_level, 
  * frames of a batch run side by side, so throughput grows with the batch up to a few hundred frames; should a wave's bounded wait ever run out, the next
  * ffhip_stream_sync on any stream returns FFHIP_EIO.  FFHIP_VP8_PRED_MODE=levels selects the older
  * one-launch-per-wavefront-level form.  Scratch is kept per stream: calls on different streams (or
- * host threads with their own streams) may be in flight together; calls on one stream are ordered. */
+ * host threads with their own streams) may be in flight together; calls on one stream are ordered.
+ * Operands: d_modes, d_residual, d_resmap and the planes (their former contents included) are STREAM-ORDERED -- the kernel reads them at
+ * the call's place in `stream`, so work enqueued there in front of the call may produce them.  h_modes is read when the call is made
+ * (the check above; nothing is scheduled from it in the row form) and must hold the records d_modes holds once `stream` reaches the call.
+ * The same holds for ffhip_vp8_predict_loopfilter and ffhip_vp8_decode_frames (there also d_filters, stream-ordered). */
 int ffhip_vp8_predict_recon(int mbcols, int mbrows, int n_images, const uint8_t *h_modes,
                             const uint8_t *d_modes, const int16_t *d_residual, int64_t residual_stride,
                             const int32_t *d_resmap, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v,
@@ -399,7 +413,10 @@ int ffhip_vp8_predict_recon(int mbcols, int mbrows, int n_images, const uint8_t 
  * Batches of at least half as many frames as the device has CUs run as ONE kernel in which a workgroup owns a frame, its
  * waves the frame's macroblock rows, and a wave predicts, filters and converts its macroblock before anything is stored
  * (every pixel is written once, as BGRA); smaller batches run the three stages (row kernels, then the colour
- * kernel: a single frame's critical path is shorter there).  FFHIP_VP8_FRAMES=fused|rows forces either. */
+ * kernel: a single frame's critical path is shorter there).  FFHIP_VP8_FRAMES=fused|rows forces either.
+ * Stream order: as ffhip_vp8_predict_recon.  The row form is a side-by-side call and has ffhip_vp8_predict_loopfilter's contract (inputs
+ * and planes unchanged until ffhip_stream_sync has returned, FFHIP_RETRIED); the frame kernel is never repeated, and work enqueued behind
+ * it may overwrite its inputs.  A caller that does not know the form (ffhip_vp8_decode_frames_form) keeps to the row form's rule. */
 /* which form ffhip_vp8_decode_frames takes for a batch of n_images on the current device: 1 the frame kernel, 0 the row kernels + colour kernel
  * (half the device's compute units and more take the frame kernel; FFHIP_VP8_FRAMES / FFHIP_VP8_FRAMES_MIN move that) */
 int ffhip_vp8_decode_frames_form(int n_images);
@@ -427,7 +444,8 @@ int ffhip_vp8_decode_frames(int mbcols, int mbrows, int n_images, const uint8_t 
  * frame form of ffhip_vp8_decode_frames (one launch per filter type and residual-map form present, frames dealt to workgroups
  * largest first): there is no row form and no FFHIP_RETRIED, so one or two frames decode with the frame kernel's latency, not
  * the row kernels'.  BGRA only (no planes).  Residual scratch, descriptor tables and line slots are library scratch of the
- * stream. */
+ * stream.  `items` (with h_modes, quant and filters) is read before the call returns; d_modes, d_levels, d_mbinfo, d_residual, d_resmap
+ * and d_bgra are stream-ordered, an h_modes must hold what its d_modes holds once `stream` reaches the call. */
 typedef struct ffhip_vp8_item {
     int mbcols, mbrows;
     const uint8_t *h_modes;
@@ -608,7 +626,12 @@ typedef struct ffhip_hevc_tu {
  * planner's verdict itself: a list it refuses is decoded by one wave in decode order inside the same launch (slow,
  * exact).  A bounded wait that ever runs out surfaces as FFHIP_EIO from the next ffhip_stream_sync.
  * FFHIP_HEVC_INTRA_MODE=levels selects the older one-launch-per-dependency-level form and FFHIP_HEVC_PLAN=host the
- * host-side planner (both synchronise the stream).  Scratch is kept per stream, as for VP8. */
+ * host-side planner (both synchronise the stream).  Scratch is kept per stream, as for VP8.
+ * Operands: d_tus, d_residual and the planes are STREAM-ORDERED -- every kernel that reads the list (validation, planner, substitution
+ * table, per-pixel programs: some on a stream of the library's own, forked from `stream` behind the call's place and joined back) waits for
+ * what the caller enqueued on `stream` in front of the call, and `stream` does not pass the call before the last of them has read it.  h_tus
+ * is read when the call is made and must hold the records d_tus holds once `stream` reaches the call.  (ffhip_hevc_intra_recon_tiles
+ * below asks MORE of d_tus: there it must be complete when the call is made.) */
 /* Host only, no device needed: the group schedule ffhip_hevc_intra_recon builds for an already valid
  * list -- out_ticket[i] = ticket of the group of TU i, out_wait[i] = TUs of other groups it waits for
  * (either may be NULL), stats[4] = {groups, luma window log2 used, wait entries, TUs served from the
