@@ -40,7 +40,9 @@ FFB_FN void ffb_load(ffb_dec *d)
     d->count += 8;
 }
 
-/* bool_dec_init (booldec.c:46-56): the first byte is loaded at once */
+/* bool_dec_init (booldec.c:46-56) loads the first byte at once; here the first decode loads it (`count` is negative), which is the
+ * same arithmetic.  So a partition that nothing is decoded from -- more token partitions than macroblock rows, or rows of skipped
+ * macroblocks only -- may have any length, zero included: the reference decodes such a file (its init reads one byte it never uses). */
 FFB_FN void ffb_init(ffb_dec *d, const uint8_t *p, uint32_t len)
 {
     d->p = p;
@@ -50,7 +52,6 @@ FFB_FN void ffb_init(ffb_dec *d, const uint8_t *p, uint32_t len)
     d->range = 255;
     d->count = -8;
     d->err = 0;
-    ffb_load(d);
 }
 
 FFB_FN int ffb_bit(ffb_dec *d, int prob)

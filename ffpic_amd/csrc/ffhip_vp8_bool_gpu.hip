@@ -105,11 +105,10 @@ __global__ __launch_bounds__(64) void k_webp_tokens(const WebpDesc *descs, int n
     ffb_dec d;
     int err = 0;
     for (int k = nparts - 1; k >= 0; k--) { /* bool_dec_init of every partition (webp.c:1905-1911); partition 0 stays in registers */
-        ffb_init(&d, D.bytes + D.part_off[k], D.part_len[k]);
+        ffb_init(&d, D.bytes + D.part_off[k], D.part_len[k]); /* loads nothing: a partition no row reads may be empty */
         if (nparts > 1) {
             D.parked[4 * k] = d.value; D.parked[4 * k + 1] = d.range; D.parked[4 * k + 2] = (uint32_t)d.count; D.parked[4 * k + 3] = d.pos;
         }
-        err |= d.err;
     }
     int cur = 0;
     for (int y = 0; y < rows; y++) {

@@ -102,13 +102,19 @@ def pil_cases():
 UNPINNED = ("syn_parts8", "syn_h37", "pil_50x37_q30")
 
 
+def unpinned_synthetic():
+    """the writer's arguments of the unpinned files that are its own"""
+    return {"syn_parts8": dict(width=48, height=160, seed=150, log2_parts=3, y_ac_qi=33, level=14, segmentation=SEG0, token_bytes=3000),
+            "syn_h37": dict(width=50, height=37, seed=151, y_ac_qi=48, level=21, sharpness=2, segmentation=SEG0)}
+
+
 def unpinned_cases():
     """Files the reference cannot record: 8 token partitions overflow its p[4] / bt[4] arrays (format/webp.h:268, webp.c:437, 1904), a
     height that is not a multiple of 16 its BGRA buffer (see above).  They are committed WITHOUT reference data; the tests hold the host
     parser, the kernels and the oracle chain against each other on them."""
     from PIL import Image
-    open(os.path.join(HERE, "syn_parts8.webp"), "wb").write(W.keyframe(width=48, height=160, seed=150, log2_parts=3, y_ac_qi=33, level=14, segmentation=SEG0, token_bytes=3000))
-    open(os.path.join(HERE, "syn_h37.webp"), "wb").write(W.keyframe(width=50, height=37, seed=151, y_ac_qi=48, level=21, sharpness=2, segmentation=SEG0))
+    for name, kw in unpinned_synthetic().items():
+        open(os.path.join(HERE, name + ".webp"), "wb").write(W.keyframe(**kw))
     rng = np.random.default_rng(78)
     yy, xx = np.mgrid[0:37, 0:50]
     img = np.stack([127 + 110 * np.sin(xx / 9.0 + yy / 31.0), 127 + 100 * np.cos(xx / 13.0) * np.sin(yy / 5.0), (xx * 3 + yy * 5) % 256], axis=2)
