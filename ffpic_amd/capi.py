@@ -37,11 +37,13 @@ EXPORTS = [
     "ffhip_debug_orient_last_items",
     "ffhip_jpeg_probe_any", "ffhip_jpeg_progressive_decode", "ffhip_jpeg_progressive_batch_gpu", "ffhip_jpeg_decode_files_mixed_device_ex",
     "ffhip_debug_progressive_last", "ffhip_jpeg_decode_files_tensor_ex",
+    "ffhip_jpeg_libjpeg_block", "ffhip_jpeg_libjpeg_picture", "ffhip_jpeg_recon_items_libjpeg",
 ]
 
 
 FFHIP_EINVAL, FFHIP_ENOMEM, FFHIP_ENODEV, FFHIP_EIO = -22, -12, -19, -5     # include/ffpic_hip.h:34-37
 FFHIP_JPEG_ACCEPT_PROGRESSIVE, FFHIP_JPEG_MAX_SCANS = 1, 128
+FFHIP_JPEG_PIXELS_LIBJPEG = 0x10
 FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1002, -1003
 
 
@@ -349,6 +351,9 @@ def lib():
     L.ffhip_jpeg_decode_files_tensor_ex.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
                                                     C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.c_uint,
                                                     C.POINTER(JpegGeom), vp, vp]
+    L.ffhip_jpeg_libjpeg_block.argtypes = [vp, vp, vp]
+    L.ffhip_jpeg_libjpeg_picture.argtypes = [C.POINTER(JpegGeom), ci, ci, vp, vp, vp, vp, vp, C.c_int64]
+    L.ffhip_jpeg_recon_items_libjpeg.argtypes = [C.POINTER(JpegItem), C.POINTER(Size), ci, vp]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

@@ -621,6 +621,7 @@ int huff_reconstruct(HuffCall &c, int lo, int hi, void *on, int part)
     }
     c.then_items.assign(then->items + lo, then->items + hi);
     for (int i = lo; i < hi; i++) jpeg_item_planes(&c.then_items[(size_t)(i - lo)], c.d_coef_y, c.d_coef_u, c.d_coef_v, c.d_quant, c.mcu_base[(size_t)i], (size_t)i);
+    if (then->display) return jpeg_recon_items_libjpeg_impl(c.then_items.data(), then->display + lo, hi - lo, on, part);
     if (then->denom) return jpeg_recon_items_scaled_impl(c.then_items.data(), then->denom + lo, hi - lo, on, part);
     return jpeg_recon_items_impl(c.then_items.data(), hi - lo, on, part);
 }

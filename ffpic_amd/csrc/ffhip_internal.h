@@ -119,7 +119,8 @@ enum FfhipScratchKind {
     SCRATCH_ORIENT_ITEMS = 74,     /* ffhip_bgra_orient_items' records and per-workgroup table, pinned records */
     SCRATCH_ORIENT_BGRA = 75,      /* ffhip_*_decode_files_tensor_oriented: a part's upright BGRA pictures */
     SCRATCH_JPEG_SCALED = 80,     /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_scaled's records and per-workgroup table, pinned records */
-    SCRATCH_HUFF_PROG = 90,       /* ffhip_jpeg_progressive_batch_gpu: staged scans, tables, records and work lists (and their pinned copy) */
+    SCRATCH_JPEG_LIBJPEG = 100,   /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_libjpeg's records, per-workgroup tables and sample planes, pinned records */
+    SCRATCH_HUFF_PROG = 90,      /* ffhip_jpeg_progressive_batch_gpu: staged scans, tables, records and work lists (and their pinned copy) */
 };
 
 /* ffhip_vp8_decode_items (ffhip_vp8_frame.hip): its levels items' residual stage (ffhip_vp8.hip) and its device mode check
@@ -173,7 +174,8 @@ int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint
 /* items (mixed batches, ffhip_jpeg_decode_files_mixed_device): per picture its geometry, output and pitch; the call fills in the plane and
  * quantiser pointers and reconstructs with ffhip_jpeg_recon_items instead (bgra, pitch and image_stride unused) */
 /* denom (with items only; NULL: every picture at full size): per picture its denominator 1, 2, 4 or 8 -- ffhip_jpeg_recon_items_scaled */
-struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_jpeg_item *items; const int *denom; };
+/* display (with items only, never with denom; NULL: the reference's pixels): per picture its display size -- ffhip_jpeg_recon_items_libjpeg */
+struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_jpeg_item *items; const int *denom; const ffhip_size *display; };
 /* geoms: NULL = every picture has *geom; else picture i has geoms[i], all of *geom's layout class (ncomp, h, v): the planes hold the
  * pictures one behind the other, picture i at the sum of the MCUs of the pictures before it */
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
@@ -204,6 +206,10 @@ int jpeg_geom_class(const ffhip_jpeg_geom *g); /* the layout class 0..6 of a geo
 int jpeg_scaled_item_class(const ffhip_jpeg_geom *g, int denom, const uint8_t *d_bgra, int64_t pitch);
 /* ffhip_jpeg_recon_items_scaled (ffhip_jpeg_scaled.hip) with that scratch slot: item i at 1 / denom[i] of its size, denominator 1 through jpeg_recon_items_impl */
 int jpeg_recon_items_scaled_impl(const ffhip_jpeg_item *items, const int *denom, int n, void *stream, int slot);
+/* ffhip_jpeg_recon_items_libjpeg (ffhip_jpeg_libjpeg.hip) with that scratch slot; jpeg_libjpeg_item_ok: what it asks of one picture's geometry,
+ * display size, output and pitch (the planes aside) */
+int jpeg_recon_items_libjpeg_impl(const ffhip_jpeg_item *items, const ffhip_size *display, int n, void *stream, int slot);
+bool jpeg_libjpeg_item_ok(const ffhip_jpeg_geom *g, int width, int height, const uint8_t *d_bgra, int64_t pitch);
 /* the plane and quantiser pointers of picture `index` of a call whose planes hold its pictures one behind the other: the picture's blocks start
  * at MCU `mcu_base` of y / u / v (u, v NULL for grey), its tables are the index-th 256 of q */
 inline void jpeg_item_planes(ffhip_jpeg_item *it, const int16_t *y, const int16_t *u, const int16_t *v, const uint16_t *q, size_t mcu_base, size_t index)

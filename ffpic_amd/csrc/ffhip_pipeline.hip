@@ -321,13 +321,16 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
 /* flags (ffhip_jpeg_decode_files_mixed_device_ex): 0, the call as it was.  FFHIP_JPEG_ACCEPT_PROGRESSIVE: the probe is ffhip_jpeg_probe_any, and a
  * class's progressive files take a turn of their own behind its baseline files: the same planes, items and reconstruction, another front end --
  * jpeg_progressive_batch_gpu_impl or ffhip_jpeg_progressive_decode on host threads (FFHIP_JPEG_PROGRESSIVE_GPU; unset: host threads, DESIGN.md
- * 4.14), with k_max = 0 / 4 / 24 for a file at 1/8, 1/4, 1/2 size: the reconstruction reads no coefficient behind those */
+ * 4.14), with k_max = 0 / 4 / 24 for a file at 1/8, 1/4, 1/2 size: the reconstruction reads no coefficient behind those.
+ * FFHIP_JPEG_PIXELS_LIBJPEG: the reconstruction at all three sites is ffhip_jpeg_recon_items_libjpeg with the probed display sizes (DESIGN.md
+ * 4.16); any denominator but 1 refuses the call */
 static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
                                    const int *denom, unsigned flags, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status)) || (flags & ~FFHIP_JPEG_ACCEPT_PROGRESSIVE)) return FFHIP_EINVAL;
+    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status)) || (flags & ~(FFHIP_JPEG_ACCEPT_PROGRESSIVE | FFHIP_JPEG_PIXELS_LIBJPEG))) return FFHIP_EINVAL;
+    const bool lj = (flags & FFHIP_JPEG_PIXELS_LIBJPEG) != 0; /* libjpeg's pixels: full size only */
     for (int i = 0; denom && i < n; i++)
-        if (!jpeg_denom_ok(denom[i])) return FFHIP_EINVAL;
+        if (!jpeg_denom_ok(denom[i]) || (lj && denom[i] != 1)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
     if (n_threads < 1) n_threads = 1;
     if (n_threads > 64) n_threads = 64;
@@ -336,6 +339,7 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
     std::vector<ffhip_jpeg_geom> geoms((size_t)n);
     std::vector<int> cls((size_t)n, -1);
     std::vector<int> prog((size_t)n, 0); /* 1: a progressive file (never with flags = 0) */
+    std::vector<ffhip_size> shown(lj ? (size_t)n : 0); /* the probed display sizes: ffhip_jpeg_recon_items_libjpeg's */
     int prog_last[5] = {0, 0, 0, 0, 0};
     const JpegChoices ch = jpeg_choices();
     ffhip_parallel_for(n, n_threads, [&](int i) {
@@ -346,7 +350,10 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
         else status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
         if (geom_out) geom_out[i] = g;
         if (status[i]) return;
-        if (denom && denom[i] > 1) /* the output holds the scaled picture: rows of 8 / denom x h x mcu_cols pixels */
+        if (lj) {
+            shown[(size_t)i] = ffhip_size{w, h};
+            cls[(size_t)i] = jpeg_libjpeg_item_ok(&g, w, h, d_bgra[i], pitch[i]) ? jpeg_geom_class(&g) : -1;
+        } else if (denom && denom[i] > 1) /* the output holds the scaled picture: rows of 8 / denom x h x mcu_cols pixels */
             cls[(size_t)i] = jpeg_scaled_item_class(&g, denom[i], d_bgra[i], pitch[i]);
         else
             cls[(size_t)i] = jpeg_item_class(ch, &g, d_bgra[i], pitch[i]);
@@ -368,10 +375,12 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
         std::vector<ffhip_jpeg_geom> cg((size_t)nc);
         std::vector<ffhip_jpeg_item> items((size_t)nc);
         std::vector<int> cs((size_t)nc, 0), cd((size_t)nc, 1); /* cd: the class's denominators */
+        std::vector<ffhip_size> cshown(lj ? (size_t)nc : 0);
         std::vector<size_t> base((size_t)nc + 1); /* MCUs of the class's pictures before picture k */
         for (int k = 0; k < nc; k++) {
             const int i = idx[(size_t)k];
             if (denom) cd[(size_t)k] = denom[i];
+            if (lj) cshown[(size_t)k] = shown[(size_t)i];
             cf[(size_t)k] = files[i]; cl[(size_t)k] = lens[i]; cg[(size_t)k] = geoms[(size_t)i];
             ffhip_jpeg_item &it = items[(size_t)k];
             memset(&it, 0, sizeof(it));
@@ -389,7 +398,7 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
         for (int k = 0; pg && k < nc; k++) kmax[(size_t)k] = cd[(size_t)k] == 8 ? 0 : cd[(size_t)k] == 4 ? 4 : cd[(size_t)k] == 2 ? 24 : 63;
         const char *pgpu = pg ? FFHIP_ENV("FFHIP_JPEG_PROGRESSIVE_GPU") : nullptr;
         if (pg && pgpu && pgpu[0] == '1') {
-            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom ? cd.data() : nullptr};
+            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom && !lj ? cd.data() : nullptr, lj ? cshown.data() : nullptr};
             int counts[4] = {0, 0, 0, 0};
             const int grc = jpeg_progressive_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, 63, kmax.data(), cs.data(),
                                                             stream, &then, counts);
@@ -400,7 +409,7 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
                 prog_last[4] = 1;
             }
         } else if (!pg && jpeg_entropy_on_device(cf[0], cl[0], nc)) {
-            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom ? cd.data() : nullptr};
+            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom && !lj ? cd.data() : nullptr, lj ? cshown.data() : nullptr};
             const int grc = jpeg_entropy_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, cs.data(), stream, &then);
             if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
             done = grc == FFHIP_OK;
@@ -434,15 +443,18 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
             if (hipMemcpyAsync(dev, pin, blk.bytes, hipMemcpyHostToDevice, st) != hipSuccess) { rc = FFHIP_EIO; break; }
             std::vector<ffhip_jpeg_item> good;
             std::vector<int> good_d;
+            std::vector<ffhip_size> good_s;
             for (int k = 0; k < nc; k++) {
                 if (cs[(size_t)k]) continue;
                 ffhip_jpeg_item it = items[(size_t)k];
                 jpeg_item_planes(&it, d.y, d.u, d.v, d.q, base[(size_t)k], (size_t)k);
                 good.push_back(it);
                 good_d.push_back(cd[(size_t)k]);
+                if (lj) good_s.push_back(cshown[(size_t)k]);
             }
-            rc = denom ? jpeg_recon_items_scaled_impl(good.data(), good_d.data(), (int)good.size(), stream, 0)
-                       : jpeg_recon_items_impl(good.data(), (int)good.size(), stream, 0);
+            rc = lj ? jpeg_recon_items_libjpeg_impl(good.data(), good_s.data(), (int)good.size(), stream, 0)
+                 : denom ? jpeg_recon_items_scaled_impl(good.data(), good_d.data(), (int)good.size(), stream, 0)
+                         : jpeg_recon_items_impl(good.data(), (int)good.size(), stream, 0);
             if (hipStreamSynchronize(st) != hipSuccess && rc == FFHIP_OK) rc = FFHIP_EIO;
         }
         for (int k = 0; k < nc; k++) status[idx[(size_t)k]] = cs[(size_t)k];

@@ -357,9 +357,11 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
                       const ffhip_rect *roi, const TensorResize &rs, const int *denom, int *denom_out, const TensorOrient &to,
                       ffhip_jpeg_geom *geom_out, int *status, void *stream, unsigned flags = 0u)
 {
-    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status) || !orient_files_args_ok(n, to) || (flags & ~FFHIP_JPEG_ACCEPT_PROGRESSIVE)) return FFHIP_EINVAL;
-    for (int i = 0; denom && i < n; i++)
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status) || !orient_files_args_ok(n, to) || (flags & ~(FFHIP_JPEG_ACCEPT_PROGRESSIVE | FFHIP_JPEG_PIXELS_LIBJPEG))) return FFHIP_EINVAL;
+    for (int i = 0; denom && i < n; i++) {
         if (denom[i] != 0 ? !jpeg_denom_ok(denom[i]) : !rs.out_size) return FFHIP_EINVAL;
+        if ((flags & FFHIP_JPEG_PIXELS_LIBJPEG) && denom[i] != 1) return FFHIP_EINVAL; /* libjpeg's pixels: full size only, "choose" included */
+    }
     if (n == 0) return FFHIP_OK;
     std::vector<TensorPicture> pic((size_t)n);
     std::vector<int> den(denom ? (size_t)n : 0, 1);
@@ -369,7 +371,7 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
         ffhip_jpeg_geom g;
         memset(&g, 0, sizeof(g));
         int w = 0, h = 0;
-        if (flags) status[i] = files[i] && lens[i] ? ffhip_jpeg_probe_any(files[i], lens[i], &g, &w, &h, nullptr) : FFHIP_EINVAL;
+        if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) status[i] = files[i] && lens[i] ? ffhip_jpeg_probe_any(files[i], lens[i], &g, &w, &h, nullptr) : FFHIP_EINVAL;
         else status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
         if (geom_out) geom_out[i] = g;
         pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h, 4LL * g.mcu_cols * 8 * g.h};

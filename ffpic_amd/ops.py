@@ -553,6 +553,40 @@ def jpeg_recon_items_scaled(items, denom, stream=None):
     capi.check(L.ffhip_jpeg_recon_items_scaled(arr, den, n, stream), "ffhip_jpeg_recon_items_scaled")
 
 
+def jpeg_libjpeg_block(coef, quant):
+    """ffhip_jpeg_libjpeg_block: the 8 x 8 samples (uint8) libjpeg makes of one block's 64 coefficients and 64 quantisers (natural order):
+    int32 dequantisation, the islow inverse DCT, + 128, clamped.  Needs no device."""
+    coef = np.ascontiguousarray(coef, np.int16).reshape(64)
+    quant = np.ascontiguousarray(quant, np.uint16).reshape(64)
+    out = np.zeros((8, 8), np.uint8)
+    capi.check(capi.lib().ffhip_jpeg_libjpeg_block(_vp(coef), _vp(quant), _vp(out)), "ffhip_jpeg_libjpeg_block")
+    return out
+
+
+def jpeg_libjpeg_picture(geom, width, height, coef_y, coef_u, coef_v, quant):
+    """ffhip_jpeg_libjpeg_picture: the width x height display picture libjpeg makes of host planes (layout of jpeg_recon_batch_host, one
+    picture; quant uint16 [4][64]) -> BGRA [height][width][4].  The CPU model of jpeg_recon_items_libjpeg.  Needs no device."""
+    cy = np.ascontiguousarray(coef_y, np.int16)
+    cu = None if coef_u is None else np.ascontiguousarray(coef_u, np.int16)
+    cv = None if coef_v is None else np.ascontiguousarray(coef_v, np.int16)
+    q = np.ascontiguousarray(quant, np.uint16)
+    out = np.zeros((max(int(height), 1), max(int(width), 1), 4), np.uint8)
+    capi.check(capi.lib().ffhip_jpeg_libjpeg_picture(C.byref(geom), width, height, _vp(cy), None if cu is None else _vp(cu),
+                                                     None if cv is None else _vp(cv), _vp(q), _vp(out), out.shape[1] * 4),
+               "ffhip_jpeg_libjpeg_picture")
+    return out
+
+
+def jpeg_recon_items_libjpeg(items, display, stream=None):
+    """ffhip_jpeg_recon_items_libjpeg: `items` a list of capi.JpegItem (device pointers), display[i] = (width, height) of item i's display
+    picture; libjpeg's pixels for pictures of any fused layout and size in one pair of launches.  Only enqueues on `stream`."""
+    L = capi.lib()
+    n = len(items)
+    arr = (capi.JpegItem * max(n, 1))(*items)
+    shown = (capi.Size * max(n, 1))(*[capi.Size(int(w), int(h)) for w, h in display])
+    capi.check(L.ffhip_jpeg_recon_items_libjpeg(arr, shown, n, stream), "ffhip_jpeg_recon_items_libjpeg")
+
+
 def jpeg_decode_files_mixed_device_scaled(files, denom, n_threads=8, stream=None, strict=True):
     """ffhip_jpeg_decode_files_mixed_device_scaled: as jpeg_decode_files_mixed_device with file i at 1 / denom[i] of its size.  Returns (geoms,
     [host BGRA [h][w][4] at the SCALED CODED size], device buffer); with strict=False a failing file's entry is None and the per-file status
@@ -652,13 +686,18 @@ def vp8_decode_items(items, stream=None):
     capi.check(L.ffhip_vp8_decode_items(arr, n, stream), "ffhip_vp8_decode_items")
 
 
-def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True, crop=True, progressive=False):
+def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True, crop=True, progressive=False, pixels="reference"):
     """ffhip_jpeg_decode_files_mixed_device: baseline JPEG files of any geometry (list of bytes) in one call.  Every picture
     gets its place in ONE device allocation, at a 16-byte-aligned offset with the pitch 4 x its coded width.  Returns
     (geoms, [host BGRA [h][w][4] cropped to each file's display size (crop=False: the coded size)], device buffer); with
     strict=False a failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows.
     progressive=True: ffhip_jpeg_decode_files_mixed_device_ex with FFHIP_JPEG_ACCEPT_PROGRESSIVE -- progressive files are probed
-    (jpeg_probe_any) and decoded too; False, the default, refuses them as ever."""
+    (jpeg_probe_any) and decoded too; False, the default, refuses them as ever.
+    pixels='libjpeg': the same call with FFHIP_JPEG_PIXELS_LIBJPEG -- libjpeg's pixels (PIL's, torchvision's) instead of the reference's;
+    any value but 'reference' and 'libjpeg' is a ValueError."""
+    if pixels not in ("reference", "libjpeg"):
+        raise ValueError(f"pixels {pixels!r}: 'reference' or 'libjpeg'")
+    flags = (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0) | (capi.FFHIP_JPEG_PIXELS_LIBJPEG if pixels == "libjpeg" else 0)
     L = capi.require_device()
     n = len(files)
     offs, pitches, total = [], [], 0
@@ -681,8 +720,8 @@ def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True,
     pitch_arr = (C.c_int64 * n)(*pitches)
     geoms = (capi.JpegGeom * n)()
     status = (C.c_int * n)()
-    if progressive:
-        rc = L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n, n_threads, outs, pitch_arr, None, capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE, geoms, status, stream)
+    if flags:
+        rc = L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n, n_threads, outs, pitch_arr, None, flags, geoms, status, stream)
     else:
         rc = L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n, n_threads, outs, pitch_arr, geoms, status, stream)
     if strict:

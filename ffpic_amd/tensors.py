@@ -153,7 +153,7 @@ def _orientations(orientation, n):
 
 def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size=None, antialias=True,
                        reduce=1, return_reduce=False, tag=None, apply_exif_orientation=False, orientation=None, return_orientation=False,
-                       progressive=False):
+                       progressive=False, flags=0):
     fmt = tensor_format(dtype, layout, order, mean, std)
     targets = _sizes(size, len(files))                            # argument errors come before any device use
     den = _reduce(reduce, size)
@@ -208,13 +208,13 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
     stream = torch.cuda.current_stream().cuda_stream
     used = (C.c_int * max(n, 1))(*([1] * max(n, 1)))
     out_size = (capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets]) if targets else None
-    if progressive:                                               # one entry point for every combination: orientation 1 where none is asked for
+    if progressive or flags:                                      # one entry point for every combination: orientation 1 where none is asked for
         what = "ffhip_jpeg_decode_files_tensor_ex"
         turn = (C.c_int * max(n, 1))(*[(max(t, 1) if imposed else 0) if oriented else 1 for t in turns])
         used_turn = (C.c_int * max(n, 1))()
         denoms = (C.c_int * max(n, 1))(*([den] * max(n, 1)))
         rc = L.ffhip_jpeg_decode_files_tensor_ex(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias), denoms, used,
-                                                 turn, used_turn, capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE, None, status, stream)
+                                                 turn, used_turn, flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0), None, status, stream)
         if oriented:
             turns = list(used_turn)[:n]
     elif oriented:
@@ -266,7 +266,7 @@ def _webp_size(f):
 
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
                            strict=True, size=None, antialias=True, reduce=1, return_reduce=False, apply_exif_orientation=False, orientation=None,
-                           return_orientation=False, progressive=False):
+                           return_orientation=False, progressive=False, pixels="reference"):
     """ffhip_jpeg_decode_files_tensor: baseline JPEG files (list of bytes) of any geometry in one call -> torch tensors on the current
     device, written on torch's current stream (the call synchronises it).
       dtype    torch.uint8 (None), torch.float16 or torch.float32;  layout 'CHW' / 'HWC';  order 'RGB' / 'BGR'
@@ -294,12 +294,19 @@ def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
       progressive  False: a progressive file is refused, as ever.  True: progressive files are decoded too
                (ffhip_jpeg_decode_files_tensor_ex with FFHIP_JPEG_ACCEPT_PROGRESSIVE; sizes from ops.jpeg_probe_any) and give what their
                baseline twins give; with reduce, the scans behind the coefficients the reduced picture reads are never decoded
+      pixels   'reference': the reference decoder's pixels, as ever.  'libjpeg': what libjpeg -- PIL, torchvision, DALI -- makes of the
+               same file, bit for bit (ffhip_jpeg_decode_files_tensor_ex with FFHIP_JPEG_PIXELS_LIBJPEG: islow inverse DCT, fancy
+               upsampling, the JFIF matrix); reduce must be 1.  Anything else: ValueError
     Returns the list of tensors; with strict=False a failing file does not raise: its entry is None, and the per-file status codes
     follow as a second element.  With return_reduce and / or return_orientation: (that, [denominators], [orientations])."""
+    if pixels not in ("reference", "libjpeg"):
+        raise ValueError(f"pixels {pixels!r}: 'reference' or 'libjpeg'")
+    if pixels == "libjpeg" and reduce != 1:
+        raise ValueError("pixels='libjpeg' needs reduce=1: libjpeg's reduced-size transforms are another rule")
     return _decode_to_tensors(lambda L: L.ffhip_jpeg_decode_files_tensor, "ffhip_jpeg_decode_files_tensor" + ("_resized" if size is not None else ""),
                               _jpeg_size_any if progressive else _jpeg_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict,
                               size, antialias, reduce, return_reduce, ops.jpeg_exif_orientation, apply_exif_orientation, orientation,
-                              return_orientation, progressive=bool(progressive))
+                              return_orientation, progressive=bool(progressive), flags=capi.FFHIP_JPEG_PIXELS_LIBJPEG if pixels == "libjpeg" else 0)
 
 
 def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,

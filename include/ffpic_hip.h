@@ -1091,7 +1091,7 @@ int ffhip_jpeg_progressive_batch_gpu(const uint8_t *const *files, const size_t *
  * with k_max = 0, 4, 24 (the largest zig-zag index of the leading 1x1, 2x2, 4x4 coefficients): whole AC scans are never read.
  * FFHIP_JPEG_PROGRESSIVE_GPU=1 / =0 forces the device or the host-thread front end for the progressive files (host threads decode into
  * pinned planes, one upload); unset: host threads (DESIGN.md 4.14 says why).  A class the device front end refuses goes to host threads.
- * Any other flag bit: FFHIP_EINVAL. */
+ * FFHIP_JPEG_PIXELS_LIBJPEG (below): libjpeg's pixels.  Any other flag bit: FFHIP_EINVAL. */
 #define FFHIP_JPEG_ACCEPT_PROGRESSIVE 1u
 int ffhip_jpeg_decode_files_mixed_device_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
                                             const int64_t *pitch, const int *denom /* may be NULL */, unsigned flags,
@@ -1103,6 +1103,42 @@ int ffhip_jpeg_decode_files_tensor_ex(const uint8_t *const *files, const size_t 
                                       const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                       const int *denom, int *denom_out, const int *orient, int *orient_out, unsigned flags,
                                       ffhip_jpeg_geom *geom_out, int *status, void *stream);
+/* ---- JPEG pictures with libjpeg's pixels (ffhip_jpeg_libjpeg.hip) ----
+ * A second, opt-in pixel rule beside the reference's: what libjpeg (and so PIL, torchvision, DALI) makes of the same coefficients, bit for
+ * bit -- dequantisation to int32, the "islow" inverse DCT (13-bit constants, pass 1 descaled by 11, pass 2 by 18, + 128, clamped to
+ * 0..255), "fancy" chroma upsampling (triangle filters for the ratios 2x1, 1x2 and 2x2 over the component's REAL sample grid
+ * ceil(W h_c / h_max) x ceil(H v_c / v_max), a neighbour outside it being the edge sample; replication for 4x1, 1x4 and for grids at
+ * most 2 samples wide) and the JFIF matrix in 16-bit fixed point (91881, 22554, 46802, 116130).  All arithmetic is 32-bit and wraps, so
+ * the rule is defined for ANY int16 coefficients and uint16 quantisers, and the device equals the host functions on all of them; equal
+ * to libjpeg it is for files whose coefficients come from 8-bit samples (beyond that libjpeg's own builds disagree with each other).
+ * Files libjpeg would not treat as YCbCr (Adobe APP14 transform 0, component ids R, G, B, four components) are out of scope.
+ * The upsampling reads neighbours across block and MCU borders and needs the display size, so these calls take it.
+ *
+ * Host only, no device needed:
+ *   ffhip_jpeg_libjpeg_block    one block: 64 samples, natural order
+ *   ffhip_jpeg_libjpeg_picture  a whole picture from HOST planes (layout of ffhip_jpeg_recon_batch, n = 1; quant uint16 [4][64]): writes the
+ *                               display rectangle width x height of `bgra` (B, G, R, 0xFF; rows `pitch` bytes apart, pitch >= 4 x width).
+ *                               FFHIP_EINVAL for a layout ffhip_jpeg_recon_items refuses, for a size that does not fit the geometry
+ *                               (width > 8 h mcu_cols or width <= 8 h (mcu_cols - 1); likewise the height) and for NULL arguments.
+ * On the device:
+ *   ffhip_jpeg_recon_items_libjpeg  the items of ffhip_jpeg_recon_items plus display[i], item i's display size (it must fit the geometry as
+ *                               above).  `items` and `display` are HOST arrays; every check is made before anything is enqueued (FFHIP_EINVAL,
+ *                               on a machine without a device too; FFHIP_ENODEV there for good arguments).  Only enqueues on `stream`: two
+ *                               launches for the whole batch (k_jpeg_idct_islow: blocks to uint8 sample planes; k_jpeg_upsample_color:
+ *                               planes to BGRA) behind the records' upload; records, table and sample planes are library scratch of the
+ *                               stream, the operands stream-ordered as for ffhip_jpeg_recon_items.  Inside the display rectangle the bytes
+ *                               are the rule's; inside the coded picture but outside it they are written but unspecified; nothing outside
+ *                               pitch x coded height is touched. */
+int ffhip_jpeg_libjpeg_block(const int16_t *coef, const uint16_t *quant, uint8_t *out);
+int ffhip_jpeg_libjpeg_picture(const ffhip_jpeg_geom *g, int width, int height, const int16_t *coef_y, const int16_t *coef_u, const int16_t *coef_v,
+                               const uint16_t *quant, uint8_t *bgra, int64_t pitch);
+int ffhip_jpeg_recon_items_libjpeg(const ffhip_jpeg_item *items, const ffhip_size *display, int n, void *stream);
+/* Flag of ffhip_jpeg_decode_files_mixed_device_ex and ffhip_jpeg_decode_files_tensor_ex: the reconstruction behind every part -- the device
+ * entropy decoder's, the host threads' upload, the progressive classes -- is ffhip_jpeg_recon_items_libjpeg with the probed display size.
+ * Everything in front of it and behind it is unchanged.  With a denominator other than 1 (0, "choose", included): FFHIP_EINVAL for the
+ * whole call, before anything is enqueued (libjpeg's reduced-size transforms are another rule). */
+#define FFHIP_JPEG_PIXELS_LIBJPEG 0x10u
+
 /* Diagnostics: the progressive files of the calling thread's last ffhip_jpeg_progressive_decode, ffhip_jpeg_progressive_batch_gpu,
  * ffhip_jpeg_decode_files_mixed_device_ex or ffhip_jpeg_decode_files_tensor_ex call (all its parts together): out[0] progressive files, [1] scans decoded, [2] scans skipped (k_max), [3] levels launched
  * (host front end: the deepest level of each file, summed), [4] the front end taken, 0 host, 1 device (the last class's). */
