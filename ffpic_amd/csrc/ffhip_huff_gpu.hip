@@ -608,7 +608,7 @@ int huff_tail_up(HuffCall &c)
     FFHIP_CHECK(hipMemcpyAsync(c.d_quant, c.dev + c.L.o_quant, (size_t)c.n * 512, hipMemcpyDeviceToDevice, c.st), FFHIP_EIO);
     return FFHIP_OK;
 }
-/* pictures [lo, hi) from their planes to then's BGRA on `on`: one geometry, one ffhip_jpeg_recon_batch; items, one ffhip_jpeg_recon_items (scratch
+/* pictures [lo, hi) from their planes to then's BGRA on `on`: one geometry, one ffhip_jpeg_recon_batch; items, the items call of then's rule (scratch
  * slot `part`: the parts' calls are in flight side by side) */
 int huff_reconstruct(HuffCall &c, int lo, int hi, void *on, int part)
 {
@@ -621,9 +621,7 @@ int huff_reconstruct(HuffCall &c, int lo, int hi, void *on, int part)
     }
     c.then_items.assign(then->items + lo, then->items + hi);
     for (int i = lo; i < hi; i++) jpeg_item_planes(&c.then_items[(size_t)(i - lo)], c.d_coef_y, c.d_coef_u, c.d_coef_v, c.d_quant, c.mcu_base[(size_t)i], (size_t)i);
-    if (then->display) return jpeg_recon_items_libjpeg_impl(c.then_items.data(), then->display + lo, hi - lo, on, part);
-    if (then->denom) return jpeg_recon_items_scaled_impl(c.then_items.data(), then->denom + lo, hi - lo, on, part);
-    return jpeg_recon_items_impl(c.then_items.data(), hi - lo, on, part);
+    return jpeg_recon_items_by_rule(c.then_items.data(), then->rule.at(lo), hi - lo, on, part);
 }
 /* The end of either decoder's enqueueing: the per-picture verdicts come back with the stream (tiny), the stream is drained -- the staging buffer is
  * free again after this sync --, and the call's times are kept (ffhip_debug_huff_times) and, on demand, printed */

@@ -250,8 +250,7 @@ int jpeg_progressive_batch_gpu_impl(const uint8_t *const *files, const size_t *l
     if (then) {
         std::vector<ffhip_jpeg_item> items(then->items, then->items + n);
         for (int i = 0; i < n; i++) jpeg_item_planes(&items[(size_t)i], d_coef_y, d_coef_u, d_coef_v, d_quant, mcu_base[(size_t)i], (size_t)i);
-        const int rrc = then->display ? jpeg_recon_items_libjpeg_impl(items.data(), then->display, n, stream, 0)
-                        : then->denom ? jpeg_recon_items_scaled_impl(items.data(), then->denom, n, stream, 0) : jpeg_recon_items_impl(items.data(), n, stream, 0);
+        const int rrc = jpeg_recon_items_by_rule(items.data(), then->rule, n, stream, 0);
         if (rrc) return rrc;
     }
     FFHIP_CHECK(hipMemcpyAsync(stage + L.o_status, dev + L.o_status, (size_t)n * 4, hipMemcpyDeviceToHost, st), FFHIP_EIO);

@@ -169,13 +169,19 @@ int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint
                                 int64_t residual_stride, const int32_t *d_resmap, int filter_type, const uint8_t *d_filters, uint8_t *d_y,
                                 uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const FfhipVp8Then *then);
 
+/* Which reconstruction a JPEG file call gives its pictures.  Both NULL: the reference's pixels at full size (ffhip_jpeg_recon_items).  denom:
+ * per picture its denominator 1, 2, 4 or 8 (ffhip_jpeg_recon_items_scaled).  display, never with denom: per picture its display size, libjpeg's
+ * pixels (ffhip_jpeg_recon_items_libjpeg) */
+struct JpegPixelRule {
+    const int *denom;
+    const ffhip_size *display;
+    JpegPixelRule at(int lo) const { return {denom ? denom + lo : nullptr, display ? display + lo : nullptr}; } /* the rule of the pictures from lo on */
+};
 /* ffhip_jpeg_decode_files_device -> ffhip_jpeg_entropy_batch_gpu: the reconstruction of the pictures, enqueued by the entropy call itself behind
  * each part of the batch it has decoded */
 /* items (mixed batches, ffhip_jpeg_decode_files_mixed_device): per picture its geometry, output and pitch; the call fills in the plane and
- * quantiser pointers and reconstructs with ffhip_jpeg_recon_items instead (bgra, pitch and image_stride unused) */
-/* denom (with items only; NULL: every picture at full size): per picture its denominator 1, 2, 4 or 8 -- ffhip_jpeg_recon_items_scaled */
-/* display (with items only, never with denom; NULL: the reference's pixels): per picture its display size -- ffhip_jpeg_recon_items_libjpeg */
-struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_jpeg_item *items; const int *denom; const ffhip_size *display; };
+ * quantiser pointers and reconstructs with jpeg_recon_items_by_rule under `rule` instead (bgra, pitch and image_stride unused) */
+struct FfhipHuffThen { uint8_t *bgra; int64_t pitch, image_stride; const ffhip_jpeg_item *items; JpegPixelRule rule; };
 /* geoms: NULL = every picture has *geom; else picture i has geoms[i], all of *geom's layout class (ncomp, h, v): the planes hold the
  * pictures one behind the other, picture i at the sum of the MCUs of the pictures before it */
 int jpeg_entropy_batch_gpu_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_jpeg_geom *geom,
@@ -199,17 +205,28 @@ struct JpegChoices {
 JpegChoices jpeg_choices(void);
 /* the layout class 0..6 of a picture ffhip_jpeg_recon_items takes with this output and pitch under these choices, -1 if it refuses it */
 int jpeg_item_class(const JpegChoices &ch, const ffhip_jpeg_geom *g, const uint8_t *d_bgra, int64_t pitch);
-int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot); /* ffhip_jpeg_recon_items with scratch slot 0..FFHIP_HUFF_PARTS-1 */
 int jpeg_geom_class(const ffhip_jpeg_geom *g); /* the layout class 0..6 of a geometry, -1 for a bad one and for the two-pass layouts */
 /* the layout class 0..6 of a picture ffhip_jpeg_recon_items_scaled takes at denominator 2, 4 or 8 with this output and pitch, -1 if it refuses
  * it: the one statement of what that call asks of geometry and output (ffhip_jpeg_scaled.hip) */
 int jpeg_scaled_item_class(const ffhip_jpeg_geom *g, int denom, const uint8_t *d_bgra, int64_t pitch);
-/* ffhip_jpeg_recon_items_scaled (ffhip_jpeg_scaled.hip) with that scratch slot: item i at 1 / denom[i] of its size, denominator 1 through jpeg_recon_items_impl */
-int jpeg_recon_items_scaled_impl(const ffhip_jpeg_item *items, const int *denom, int n, void *stream, int slot);
-/* ffhip_jpeg_recon_items_libjpeg (ffhip_jpeg_libjpeg.hip) with that scratch slot; jpeg_libjpeg_item_ok: what it asks of one picture's geometry,
- * display size, output and pitch (the planes aside) */
-int jpeg_recon_items_libjpeg_impl(const ffhip_jpeg_item *items, const ffhip_size *display, int n, void *stream, int slot);
+/* what ffhip_jpeg_recon_items_libjpeg asks of one picture's geometry, display size, output and pitch (the planes aside) */
 bool jpeg_libjpeg_item_ok(const ffhip_jpeg_geom *g, int width, int height, const uint8_t *d_bgra, int64_t pitch);
+/* The three items calls with scratch slot 0..FFHIP_HUFF_PARTS-1: ffhip_jpeg_recon_items; ffhip_jpeg_recon_items_scaled (item i at 1 / denom[i]
+ * of its size, denominator 1 through jpeg_recon_items_impl); ffhip_jpeg_recon_items_libjpeg.  The file calls reach them through the rule only */
+int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot);
+int jpeg_recon_items_scaled_impl(const ffhip_jpeg_item *items, const int *denom, int n, void *stream, int slot);
+int jpeg_recon_items_libjpeg_impl(const ffhip_jpeg_item *items, const ffhip_size *display, int n, void *stream, int slot);
+/* The two owners of "which pixels" (ffhip_jpeg.hip).  The items call of the rule over n items, the rule's arrays in the items' order; and the
+ * layout class 0..6 that call gives picture i of the rule (geometry *g, display size w x h) with this output and pitch, -1 if it refuses it */
+int jpeg_recon_items_by_rule(const ffhip_jpeg_item *items, const JpegPixelRule &rule, int n, void *stream, int slot);
+int jpeg_rule_item_class(const JpegChoices &ch, const JpegPixelRule &rule, int i, const ffhip_jpeg_geom *g, int w, int h, const uint8_t *d_bgra, int64_t pitch);
+/* A JPEG file's header for the file calls: ffhip_jpeg_probe, or with FFHIP_JPEG_ACCEPT_PROGRESSIVE in flags ffhip_jpeg_probe_any; a NULL or
+ * empty file is FFHIP_EINVAL.  Geometry, display size and the progressive bit are zero where the probe left them so */
+struct JpegProbed { ffhip_jpeg_geom geom; int width, height, progressive, status; };
+JpegProbed jpeg_probe_file(const uint8_t *file, size_t len, unsigned flags);
+/* ffhip_jpeg_decode_files_mixed_device_ex's body (ffhip_pipeline.hip): the three public mixed file calls and the tensor file calls' parts */
+int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
+                            const int *denom, unsigned flags, ffhip_jpeg_geom *geom_out, int *status, void *stream);
 /* the plane and quantiser pointers of picture `index` of a call whose planes hold its pictures one behind the other: the picture's blocks start
  * at MCU `mcu_base` of y / u / v (u, v NULL for grey), its tables are the index-th 256 of q */
 inline void jpeg_item_planes(ffhip_jpeg_item *it, const int16_t *y, const int16_t *u, const int16_t *v, const uint16_t *q, size_t mcu_base, size_t index)

@@ -35,6 +35,7 @@
  * This file must be compiled with -ffp-contract=off.
  */
 #include "ffhip_colorterms.h"
+#include "ffhip_items.h"
 
 #include <errno.h>
 #include <stdlib.h>
@@ -273,7 +274,7 @@ __device__ __forceinline__ u32 xcd_remap_wg(int mode)
 /* ------------------------------------------------------------------------
  * Mixed batches (ffhip_jpeg_recon_items): items of one layout class that differ in size, planes, quantiser tables, output
  * and pitch, in one launch.  The host lays the items' workgroups end to end (first_wg: a prefix sum of what each needs) and
- * k_jpeg_items_table writes every item's index over its range of a per-workgroup table; a workgroup of an items kernel
+ * k_items_table (ffhip_items.h) writes every item's index over its range of a per-workgroup table; a workgroup of an items kernel
  * then reads its item with one wave-uniform load after the XCD remap -- no search -- and the item's record with a few
  * more, builds the batch of one the uniform body runs on, and runs it.  Loads only: nothing per item is written back.
  * ---------------------------------------------------------------------- */
@@ -295,13 +296,6 @@ struct JpegItems {
     u32 wg_base;        /* this launch's first workgroup (a class's launches, split below 2^31 workgroups) */
     int xcd_remap;
 };
-
-/* one workgroup per item: the item's index over its range of the per-workgroup table */
-__global__ __launch_bounds__(256) void k_jpeg_items_table(const JpegItemDesc *desc, u32 *wg_item)
-{
-    const u32 item = blockIdx.x, first = desc[item].first_wg, n = desc[item].n_wgs;
-    for (u32 k = threadIdx.x; k < n; k += 256) wg_item[first + k] = item;
-}
 
 /* the batch of one the workgroup belongs to (img = 0, pointers the item's own); returns the workgroup's index inside it */
 __device__ __forceinline__ int jpeg_item_batch(const JpegItems &t, JpegBatch &p)
@@ -944,6 +938,20 @@ int jpeg_item_class(const JpegChoices &ch, const ffhip_jpeg_geom *g, const uint8
     return c >= 0 && picture_out_ok(g, d_bgra, pitch) && picture_limits_ok(g, ch.mps[c], pitch) ? c : -1;
 }
 
+int jpeg_rule_item_class(const JpegChoices &ch, const JpegPixelRule &rule, int i, const ffhip_jpeg_geom *g, int w, int h, const uint8_t *d_bgra, int64_t pitch)
+{
+    if (rule.display) return jpeg_libjpeg_item_ok(g, w, h, d_bgra, pitch) ? jpeg_geom_class(g) : -1;
+    if (rule.denom && rule.denom[i] > 1) return jpeg_scaled_item_class(g, rule.denom[i], d_bgra, pitch); /* the output holds the scaled picture */
+    return jpeg_item_class(ch, g, d_bgra, pitch);
+}
+
+int jpeg_recon_items_by_rule(const ffhip_jpeg_item *items, const JpegPixelRule &rule, int n, void *stream, int slot)
+{
+    if (rule.display) return jpeg_recon_items_libjpeg_impl(items, rule.display, n, stream, slot);
+    if (rule.denom) return jpeg_recon_items_scaled_impl(items, rule.denom, n, stream, slot);
+    return jpeg_recon_items_impl(items, n, stream, slot);
+}
+
 /* `slot` (0 .. FFHIP_HUFF_PARTS - 1) picks the scratch: the device entropy decoder enqueues one call per part of its batch, each with its own */
 int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int slot)
 {
@@ -986,27 +994,18 @@ int jpeg_recon_items_impl(const ffhip_jpeg_item *items, int n, void *stream, int
     wg_first[JPEG_CLASSES] = total;
     if (total > 0xffffffffULL) return FFHIP_EINVAL; /* the table's entries are 32-bit workgroup indices */
     /* device scratch: the records, then the per-workgroup table; pinned staging for the records.  Both per (stream, slot) */
-    const size_t desc_bytes = (size_t)n * sizeof(JpegItemDesc);
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_JPEG_ITEMS + slot, stream, desc_bytes / 4 + (size_t)total + 16);
-    if (!dev) return FFHIP_ENOMEM;
-    uint8_t *pin = ffhip_pinned_staging(SCRATCH_JPEG_ITEMS + slot, stream, desc_bytes);
-    if (!pin) return FFHIP_ENOMEM;
-    memcpy(pin, desc.data(), desc_bytes);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    if (ffhip_pinned_staged(SCRATCH_JPEG_ITEMS + slot, stream) != FFHIP_OK) return FFHIP_EIO;
-    const JpegItemDesc *d_desc = (const JpegItemDesc *)dev;
-    u32 *d_table = (u32 *)(dev + desc_bytes);
-    hipLaunchKernelGGL(k_jpeg_items_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_table);
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    for (int c = 0; c < JPEG_CLASSES; c++)
-        for (unsigned long long b = wg_first[c]; b < wg_first[c + 1]; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups; a class's total may not */
-            const unsigned long long left = wg_first[c + 1] - b;
-            const dim3 grid((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL), 1, 1);
+    const JpegItemDesc *d_desc = nullptr;
+    u32 *d_table = nullptr;
+    const int rc = ffhip_items_upload(SCRATCH_JPEG_ITEMS + slot, stream, desc, total, &d_desc, &d_table);
+    if (rc) return rc;
+    for (int c = 0; c < JPEG_CLASSES; c++) { /* a class's total may pass 2^31 workgroups */
+        const int lrc = ffhip_items_launch(wg_first[c], wg_first[c + 1], [&](unsigned grid_x, u32 wg_base) {
             JpegItems t;
-            t.desc = d_desc; t.wg_item = d_table; t.wg_base = (u32)b; t.xcd_remap = ch.remap;
-            launch_items(c, ch, grid, t, st);
-            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-        }
+            t.desc = d_desc; t.wg_item = d_table; t.wg_base = wg_base; t.xcd_remap = ch.remap;
+            launch_items(c, ch, dim3(grid_x, 1, 1), t, st);
+        });
+        if (lrc) return lrc;
+    }
     return FFHIP_OK;
 }
 extern "C" int ffhip_jpeg_recon_items(const ffhip_jpeg_item *items, int n, void *stream)

@@ -14,7 +14,7 @@
  * class is one code path and a mixed batch is one pair of launches (behind the records' upload and the per-workgroup tables' kernel, as in
  * ffhip_jpeg_recon_items).
  */
-#include "ffhip_internal.h"
+#include "ffhip_items.h"
 #include "ffhip_jpeg_libjpeg_body.h"
 
 #include <string.h>
@@ -319,36 +319,32 @@ int jpeg_recon_items_libjpeg_impl(const ffhip_jpeg_item *items, const ffhip_size
     hipStream_t st = (hipStream_t)stream;
     /* device scratch: the records, the two per-workgroup tables, the planes (256-byte aligned); pinned staging for the records.  Both per (stream, slot) */
     const size_t desc_bytes = (size_t)n * sizeof(JpegLibjpegDesc);
-    const size_t planes_off = (desc_bytes + ((size_t)total_idct + (size_t)total_color) * 4 + 255) & ~(size_t)255;
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_JPEG_LIBJPEG + slot, stream, (planes_off + plane_bytes) / 4 + 16);
-    if (!dev) return FFHIP_ENOMEM;
-    uint8_t *pin = ffhip_pinned_staging(SCRATCH_JPEG_LIBJPEG + slot, stream, desc_bytes);
-    if (!pin) return FFHIP_ENOMEM;
-    for (int i = 0; i < n; i++) {
-        JpegLibjpegDesc &d = desc[(size_t)i];
-        const size_t mcus = (size_t)d.mcu_cols * d.mcu_rows;
-        d.plane_y = dev + planes_off + plane_at[(size_t)i];
-        d.plane_u = d.ncomp == 3 ? d.plane_y + ((mcus * 64) << (d.h_log2 + d.v_log2)) : nullptr;
-        d.plane_v = d.ncomp == 3 ? d.plane_u + mcus * 64 : nullptr;
-    }
-    memcpy(pin, desc.data(), desc_bytes);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    if (ffhip_pinned_staged(SCRATCH_JPEG_LIBJPEG + slot, stream) != FFHIP_OK) return FFHIP_EIO;
+    const size_t table_words = (size_t)total_idct + (size_t)total_color;
+    const size_t planes_off = (desc_bytes + table_words * 4 + 255) & ~(size_t)255;
+    uint8_t *dev = nullptr;
+    const int rc = ffhip_items_stage(SCRATCH_JPEG_LIBJPEG + slot, stream, desc.data(), desc_bytes, table_words,
+                                     planes_off + plane_bytes - desc_bytes - table_words * 4, &dev, [&](uint8_t *base) {
+        for (int i = 0; i < n; i++) {
+            JpegLibjpegDesc &d = desc[(size_t)i];
+            const size_t mcus = (size_t)d.mcu_cols * d.mcu_rows;
+            d.plane_y = base + planes_off + plane_at[(size_t)i];
+            d.plane_u = d.ncomp == 3 ? d.plane_y + ((mcus * 64) << (d.h_log2 + d.v_log2)) : nullptr;
+            d.plane_v = d.ncomp == 3 ? d.plane_u + mcus * 64 : nullptr;
+        }
+    });
+    if (rc) return rc;
     const JpegLibjpegDesc *d_desc = (const JpegLibjpegDesc *)dev;
     u32 *d_idct = (u32 *)(dev + desc_bytes), *d_color = d_idct + total_idct;
     hipLaunchKernelGGL(k_jpeg_libjpeg_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_idct, d_color);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
     for (int pass = 0; pass < 2; pass++) {
-        const unsigned long long total = pass ? total_color : total_idct;
-        for (unsigned long long b = 0; b < total; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups */
-            const unsigned long long left = total - b;
-            const dim3 grid((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL), 1, 1);
+        const int lrc = ffhip_items_launch(0, pass ? total_color : total_idct, [&](unsigned grid_x, u32 wg_base) {
             JpegLibjpegArgs a;
-            a.desc = d_desc; a.wg_item = pass ? d_color : d_idct; a.wg_base = (u32)b;
-            if (pass) hipLaunchKernelGGL(k_jpeg_upsample_color, grid, dim3(LJ_WG_THREADS), 0, st, a);
-            else hipLaunchKernelGGL(k_jpeg_idct_islow, grid, dim3(LJ_WG_THREADS), 0, st, a);
-            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-        }
+            a.desc = d_desc; a.wg_item = pass ? d_color : d_idct; a.wg_base = wg_base;
+            if (pass) hipLaunchKernelGGL(k_jpeg_upsample_color, dim3(grid_x), dim3(LJ_WG_THREADS), 0, st, a);
+            else hipLaunchKernelGGL(k_jpeg_idct_islow, dim3(grid_x), dim3(LJ_WG_THREADS), 0, st, a);
+        });
+        if (lrc) return lrc;
     }
     return FFHIP_OK;
 }

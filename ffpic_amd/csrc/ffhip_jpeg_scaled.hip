@@ -18,6 +18,7 @@
  * This file must be compiled with -ffp-contract=off.
  */
 #include "ffhip_colorterms.h"
+#include "ffhip_items.h"
 #include "ffhip_jpeg_scaled_body.h"
 
 #include <string.h>
@@ -33,13 +34,6 @@ struct JpegScaledArgs {
     const u32 *wg_item; /* per workgroup of the call: its item */
     u32 wg_base;        /* the launch's first workgroup */
 };
-
-/* one workgroup per item: the item's index over its range of the per-workgroup table */
-__global__ __launch_bounds__(256) void k_jpeg_scaled_table(const JpegScaledDesc *desc, u32 *wg_item)
-{
-    const u32 item = blockIdx.x, first = desc[item].first_wg, n = desc[item].n_wgs;
-    for (u32 k = threadIdx.x; k < n; k += 256) wg_item[first + k] = item;
-}
 
 /* the N leading int16 of row v of a block, as one load of 2 N bytes */
 template <int N> __device__ __forceinline__ void load_corner_row(const int16_t *blk, int v, int16_t (&out)[N])
@@ -252,29 +246,20 @@ int jpeg_recon_items_scaled_impl(const ffhip_jpeg_item *items, const int *denom,
     if (!n_scaled) return FFHIP_OK;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
-    const size_t desc_bytes = n_scaled * sizeof(JpegScaledDesc);
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_JPEG_SCALED + slot, stream, desc_bytes / 4 + (size_t)total + 16);
-    if (!dev) return FFHIP_ENOMEM;
-    uint8_t *pin = ffhip_pinned_staging(SCRATCH_JPEG_SCALED + slot, stream, desc_bytes);
-    if (!pin) return FFHIP_ENOMEM;
-    memcpy(pin, desc.data(), desc_bytes);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    if (ffhip_pinned_staged(SCRATCH_JPEG_SCALED + slot, stream) != FFHIP_OK) return FFHIP_EIO;
-    const JpegScaledDesc *d_desc = (const JpegScaledDesc *)dev;
-    u32 *d_table = (u32 *)(dev + desc_bytes);
-    hipLaunchKernelGGL(k_jpeg_scaled_table, dim3((unsigned)n_scaled), dim3(256), 0, st, d_desc, d_table);
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    for (int c = 0; c < 3; c++)
-        for (unsigned long long b = wg_first[c]; b < wg_first[c + 1]; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups */
-            const unsigned long long left = wg_first[c + 1] - b;
-            const dim3 grid((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL), 1, 1);
+    const JpegScaledDesc *d_desc = nullptr;
+    u32 *d_table = nullptr;
+    const int rc = ffhip_items_upload(SCRATCH_JPEG_SCALED + slot, stream, desc, total, &d_desc, &d_table);
+    if (rc) return rc;
+    for (int c = 0; c < 3; c++) {
+        const int lrc = ffhip_items_launch(wg_first[c], wg_first[c + 1], [&](unsigned grid_x, u32 wg_base) {
             JpegScaledArgs a;
-            a.desc = d_desc; a.wg_item = d_table; a.wg_base = (u32)b;
-            if (c == 0) hipLaunchKernelGGL(k_jpeg_recon_scaled<4>, grid, dim3(SCALED_WG_THREADS), 0, st, a);
-            else if (c == 1) hipLaunchKernelGGL(k_jpeg_recon_scaled<2>, grid, dim3(SCALED_WG_THREADS), 0, st, a);
-            else hipLaunchKernelGGL(k_jpeg_recon_scaled<1>, grid, dim3(SCALED_WG_THREADS), 0, st, a);
-            FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-        }
+            a.desc = d_desc; a.wg_item = d_table; a.wg_base = wg_base;
+            if (c == 0) hipLaunchKernelGGL(k_jpeg_recon_scaled<4>, dim3(grid_x), dim3(SCALED_WG_THREADS), 0, st, a);
+            else if (c == 1) hipLaunchKernelGGL(k_jpeg_recon_scaled<2>, dim3(grid_x), dim3(SCALED_WG_THREADS), 0, st, a);
+            else hipLaunchKernelGGL(k_jpeg_recon_scaled<1>, dim3(grid_x), dim3(SCALED_WG_THREADS), 0, st, a);
+        });
+        if (lrc) return lrc;
+    }
     return FFHIP_OK;
 }
 

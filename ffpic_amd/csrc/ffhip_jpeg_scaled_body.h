@@ -78,6 +78,10 @@ template <int N> __host__ __device__ inline void jpeg_scaled_block_row(const int
     jpeg_scaled_row<N>(c, s);
 }
 
+/* the last coefficient, in zig-zag order, that the transform at denominator d reads: the largest index of the leading 1 x 1, 2 x 2, 4 x 4
+ * corner; a progressive file's scans that start behind it need not be decoded */
+inline int jpeg_scaled_k_max(int d) { return d == 8 ? 0 : d == 4 ? 4 : d == 2 ? 24 : 63; }
+
 /* the sizes of a picture at denominator d: ceil(W / d) x ceil(H / d) displayed; a rectangle of the full-size display picture mapped onto
  * it: x0' = x0 / d, x1' = min(ceil(W / d), ceil((x0 + w) / d)), likewise y -- its edges lie up to d - 1 source pixels outside the request */
 __host__ __device__ inline bool jpeg_denom_ok(int d) { return d == 1 || d == 2 || d == 4 || d == 8; }

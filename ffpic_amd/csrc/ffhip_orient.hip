@@ -3,13 +3,13 @@
  * include/ffpic_hip.h, "EXIF orientation").  Pure pixel movement, one dword per pixel.  The coordinate map, the layout of
  * the work and the LDS bank arithmetic are in ffhip_orient_body.h.
  *
- * Two launches per call: k_orient_items_table writes the per-workgroup item table, k_bgra_orient has one workgroup of 256 threads per
+ * Two launches per call: k_items_table (ffhip_items.h) writes the per-workgroup item table, k_bgra_orient has one workgroup of 256 threads per
  * 64 x 64 tile of an item's stored rectangle.  The orientation comes out of the item's record, so the branch on it is uniform over the
  * workgroup (the barrier of the transposing branch included), and so is the one on "the whole tile lies inside".  Every lane loads its 16
  * pixels before it stores the first: the loads of a wave are all in flight together, whatever the compiler may assume about source and
  * destination; in a whole tile no branch stands between the stores either.
  */
-#include "ffhip_internal.h"
+#include "ffhip_items.h"
 #include "ffhip_orient_body.h"
 
 #include <string.h>
@@ -21,13 +21,6 @@ struct OrientArgs {
     const u32 *wg_item; /* per workgroup of the call: its item */
     u32 wg_base;        /* the launch's first workgroup */
 };
-
-/* one workgroup per item: the item's index over its range of the per-workgroup table */
-__global__ __launch_bounds__(256) void k_orient_items_table(const OrientItemDesc *desc, u32 *wg_item)
-{
-    const u32 item = blockIdx.x, first = desc[item].first_wg, n = desc[item].n_wgs;
-    for (u32 k = threadIdx.x; k < n; k += 256) wg_item[first + k] = item;
-}
 
 /* One tile.  FULL: all 64 x 64 pixels of it lie inside the rectangle, and nothing is predicated: 16 loads, then 16 stores, no branch
  * between them.  Otherwise (the tiles along the right and the lower edge) every load and store has its lane's condition */
@@ -120,24 +113,13 @@ extern "C" int ffhip_bgra_orient_items(const ffhip_orient_item *items, int n, vo
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
     /* device scratch: the records, then the per-workgroup table; pinned staging for the records.  Both per stream */
-    const size_t desc_bytes = (size_t)n * sizeof(OrientItemDesc);
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_ORIENT_ITEMS, stream, desc_bytes / 4 + (size_t)total + 16);
-    if (!dev) return FFHIP_ENOMEM;
-    uint8_t *pin = ffhip_pinned_staging(SCRATCH_ORIENT_ITEMS, stream, desc_bytes);
-    if (!pin) return FFHIP_ENOMEM;
-    memcpy(pin, desc.data(), desc_bytes);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    if (ffhip_pinned_staged(SCRATCH_ORIENT_ITEMS, stream) != FFHIP_OK) return FFHIP_EIO;
-    const OrientItemDesc *d_desc = (const OrientItemDesc *)dev;
-    u32 *d_table = (u32 *)(dev + desc_bytes);
-    hipLaunchKernelGGL(k_orient_items_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_table);
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    for (unsigned long long b = 0; b < total; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups */
-        const unsigned long long left = total - b;
+    const OrientItemDesc *d_desc = nullptr;
+    u32 *d_table = nullptr;
+    const int rc = ffhip_items_upload(SCRATCH_ORIENT_ITEMS, stream, desc, total, &d_desc, &d_table);
+    if (rc) return rc;
+    return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
         OrientArgs a;
-        a.desc = d_desc; a.wg_item = d_table; a.wg_base = (u32)b;
-        hipLaunchKernelGGL(k_bgra_orient, dim3((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL)), dim3(FFHIP_ORIENT_WG_THREADS), 0, st, a);
-        FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    }
-    return FFHIP_OK;
+        a.desc = d_desc; a.wg_item = d_table; a.wg_base = wg_base;
+        hipLaunchKernelGGL(k_bgra_orient, dim3(grid_x), dim3(FFHIP_ORIENT_WG_THREADS), 0, st, a);
+    });
 }

@@ -310,9 +310,147 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
     return rc ? rc : result;
 }
 
+namespace {
+/* One picture of a class turn: a class's baseline files, or its progressive files */
+struct MixedPic {
+    int index;            /* the file's place in the call */
+    const uint8_t *file;
+    size_t len;
+    ffhip_jpeg_item item; /* geometry, output and pitch; the turn gives it its place in the class's planes */
+    int denom;            /* 1 where the call has none */
+    ffhip_size shown;     /* the probed display size (libjpeg's pixels only) */
+    size_t mcu_base;      /* MCUs of the turn's pictures in front of this one */
+    int k_max;            /* the last coefficient the reconstruction reads: what a progressive file is decoded up to */
+    int status;           /* the host threads' verdict */
+};
+
+/* the items of a turn's pictures (good_only: of those without a code) and the call's rule over them, in their order */
+struct TurnItems {
+    std::vector<ffhip_jpeg_item> items;
+    std::vector<int> denom;
+    std::vector<ffhip_size> display;
+    TurnItems(const std::vector<MixedPic> &pics, const JpegPixelRule &call, bool good_only)
+    {
+        items.reserve(pics.size());
+        if (call.denom) denom.reserve(pics.size());
+        if (call.display) display.reserve(pics.size());
+        for (const MixedPic &p : pics) {
+            if (good_only && p.status) continue;
+            items.push_back(p.item);
+            if (call.denom) denom.push_back(p.denom);
+            if (call.display) display.push_back(p.shown);
+        }
+    }
+    JpegPixelRule rule(const JpegPixelRule &call) const { return {call.denom ? denom.data() : nullptr, call.display ? display.data() : nullptr}; }
+};
+
+/* A turn through its device front end, the reconstruction behind it by the entropy call itself: jpeg_progressive_batch_gpu_impl (prog) or
+ * jpeg_entropy_batch_gpu_impl.  *done = false with FFHIP_OK: the front end refuses the class (FFHIP_EINVAL), host threads take it; any
+ * other error ends the call */
+int mixed_turn_device(std::vector<MixedPic> &pics, bool prog, const JpegPixelRule &call, const Planes &d, int n_threads, void *stream, int *status,
+                      int prog_last[5], bool *done)
+{
+    const size_t nc = pics.size();
+    std::vector<const uint8_t *> files(nc);
+    std::vector<size_t> lens(nc);
+    std::vector<ffhip_jpeg_geom> geoms(nc);
+    std::vector<int> k_maxes(nc), cs(nc, 0);
+    for (size_t k = 0; k < nc; k++) {
+        files[k] = pics[k].file; lens[k] = pics[k].len; geoms[k] = pics[k].item.geom; k_maxes[k] = pics[k].k_max;
+    }
+    const TurnItems t(pics, call, false);
+    const FfhipHuffThen then = {nullptr, 0, 0, t.items.data(), t.rule(call)};
+    int counts[4] = {0, 0, 0, 0};
+    const int grc = prog ? jpeg_progressive_batch_gpu_impl(files.data(), lens.data(), (int)nc, n_threads, &geoms[0], geoms.data(), d.y, d.u, d.v, d.q, 63, k_maxes.data(),
+                                                           cs.data(), stream, &then, counts)
+                         : jpeg_entropy_batch_gpu_impl(files.data(), lens.data(), (int)nc, n_threads, &geoms[0], geoms.data(), d.y, d.u, d.v, d.q, cs.data(), stream, &then);
+    *done = grc == FFHIP_OK;
+    if (!*done) return grc == FFHIP_EINVAL ? FFHIP_OK : grc;
+    if (prog) {
+        for (int q = 0; q < 4; q++) prog_last[q] += counts[q];
+        prog_last[4] = 1;
+    }
+    for (size_t k = 0; k < nc; k++) status[pics[k].index] = cs[k];
+    return FFHIP_OK;
+}
+
+/* A turn on host threads: each picture at its own offsets of the pinned planes, one upload, the good pictures reconstructed.  Everything
+ * has run when it returns */
+int mixed_turn_host(std::vector<MixedPic> &pics, bool prog, const JpegPixelRule &call, const PlaneBlock &blk, uint8_t *dev, int n_threads, void *stream,
+                    int *status, int prog_last[5])
+{
+    hipStream_t st = (hipStream_t)stream;
+    const int nc = (int)pics.size();
+    if (hipStreamSynchronize(st) != hipSuccess) return FFHIP_EIO; /* the scratch may still be read by what `stream` holds */
+    uint8_t *pin = ffhip_pinned_scratch(SCRATCH_FILES_MIXED, stream, blk.bytes);
+    if (!pin) return FFHIP_ENOMEM;
+    const Planes h = blk.at(pin);
+    std::vector<std::array<int, 3>> pcounts(prog ? (size_t)nc : 0);
+    ffhip_parallel_for(nc, n_threads, [&](int k) {
+        MixedPic &p = pics[(size_t)k];
+        const ffhip_jpeg_geom &g = p.item.geom;
+        const size_t b = p.mcu_base;
+        int16_t *y = h.y + b * g.h * g.v * 64, *u = h.u ? h.u + b * 64 : nullptr, *v = h.v ? h.v + b * 64 : nullptr;
+        uint16_t *q = h.q + (size_t)k * 256;
+        if (prog) {
+            pcounts[(size_t)k] = {0, 0, 0};
+            p.status = ffhip_prog_decode_host(p.file, p.len, &g, y, u, v, q, p.k_max, pcounts[(size_t)k].data());
+        } else
+            p.status = ffhip_jpeg_entropy_decode(p.file, p.len, &g, y, u, v, q);
+    });
+    if (prog) {
+        for (int k = 0; k < nc; k++) {
+            prog_last[0] += pcounts[(size_t)k][0] + pcounts[(size_t)k][1] > 0; /* files that parsed, as the device front end counts them */
+            for (int q = 0; q < 3; q++) prog_last[1 + q] += pcounts[(size_t)k][(size_t)q];
+        }
+        prog_last[4] = 0;
+    }
+    if (hipMemcpyAsync(dev, pin, blk.bytes, hipMemcpyHostToDevice, st) != hipSuccess) return FFHIP_EIO;
+    const TurnItems good(pics, call, true);
+    int rc = jpeg_recon_items_by_rule(good.items.data(), good.rule(call), (int)good.items.size(), stream, 0);
+    if (hipStreamSynchronize(st) != hipSuccess && rc == FFHIP_OK) rc = FFHIP_EIO;
+    for (const MixedPic &p : pics) status[p.index] = p.status;
+    return rc;
+}
+
+/* One turn: the class's planes in library scratch of the stream, every picture behind the MCUs of those before it; the device front end
+ * where the gate (baseline) or FFHIP_JPEG_PROGRESSIVE_GPU=1 (progressive) says so, host threads otherwise and for a class it refuses */
+int mixed_turn(std::vector<MixedPic> &pics, bool prog, const JpegPixelRule &call, int n_threads, void *stream, int *status, int prog_last[5])
+{
+    size_t mcus = 0;
+    for (MixedPic &p : pics) {
+        p.mcu_base = mcus;
+        mcus += (size_t)p.item.geom.mcu_cols * p.item.geom.mcu_rows;
+    }
+    const ffhip_jpeg_geom &g0 = pics[0].item.geom;
+    const PlaneBlock blk(mcus * g0.h * g0.v * 64, g0.ncomp == 3 ? mcus * 64 : 0, pics.size()); /* int16 elements of the class */
+    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_FILES_MIXED, stream, blk.bytes / 4 + 16);
+    if (!dev) return FFHIP_ENOMEM;
+    const Planes d = blk.at(dev);
+    for (size_t k = 0; k < pics.size(); k++) jpeg_item_planes(&pics[k].item, d.y, d.u, d.v, d.q, pics[k].mcu_base, k);
+    const char *pgpu = prog ? FFHIP_ENV("FFHIP_JPEG_PROGRESSIVE_GPU") : nullptr;
+    bool done = false;
+    if (prog ? (pgpu && pgpu[0] == '1') : jpeg_entropy_on_device(pics[0].file, pics[0].len, (int)pics.size())) {
+        const int rc = mixed_turn_device(pics, prog, call, d, n_threads, stream, status, prog_last, &done);
+        if (rc) return rc;
+    }
+    return done ? FFHIP_OK : mixed_turn_host(pics, prog, call, blk, dev, n_threads, stream, status, prog_last);
+}
+} // namespace
+
+JpegProbed jpeg_probe_file(const uint8_t *file, size_t len, unsigned flags)
+{
+    JpegProbed p;
+    memset(&p, 0, sizeof(p));
+    if (!file || !len) p.status = FFHIP_EINVAL;
+    else if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) p.status = ffhip_jpeg_probe_any(file, len, &p.geom, &p.width, &p.height, &p.progressive);
+    else p.status = ffhip_jpeg_probe(file, len, &p.geom, &p.width, &p.height);
+    return p;
+}
+
 /* Files of any baseline geometry, pixels on the device, one call: headers on host threads, the files grouped by layout class (the items
  * kernels take one class a launch, the device entropy decoder one MCU block record a call), and per class the device entropy decoder
- * over pictures of different sizes with one ffhip_jpeg_recon_items launch behind each part of its write pass; a class it refuses goes to
+ * over pictures of different sizes with one items launch (jpeg_recon_items_by_rule) behind each part of its write pass; a class it refuses goes to
  * host threads.  A class's planes are library scratch of the stream, reused by the next class: every class's work has run when its
  * turn ends (the entropy call synchronises the stream). */
 /* denom == NULL: every picture at full size, the call as it was.  Otherwise picture i at 1 / denom[i] of its size (ffhip_jpeg_recon_items_scaled):
@@ -321,11 +459,11 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
 /* flags (ffhip_jpeg_decode_files_mixed_device_ex): 0, the call as it was.  FFHIP_JPEG_ACCEPT_PROGRESSIVE: the probe is ffhip_jpeg_probe_any, and a
  * class's progressive files take a turn of their own behind its baseline files: the same planes, items and reconstruction, another front end --
  * jpeg_progressive_batch_gpu_impl or ffhip_jpeg_progressive_decode on host threads (FFHIP_JPEG_PROGRESSIVE_GPU; unset: host threads, DESIGN.md
- * 4.14), with k_max = 0 / 4 / 24 for a file at 1/8, 1/4, 1/2 size: the reconstruction reads no coefficient behind those.
+ * 4.14), with jpeg_scaled_k_max of the file's denominator: the reconstruction reads no coefficient behind it.
  * FFHIP_JPEG_PIXELS_LIBJPEG: the reconstruction at all three sites is ffhip_jpeg_recon_items_libjpeg with the probed display sizes (DESIGN.md
  * 4.16); any denominator but 1 refuses the call */
-static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
-                                   const int *denom, unsigned flags, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
+                            const int *denom, unsigned flags, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
     if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status)) || (flags & ~(FFHIP_JPEG_ACCEPT_PROGRESSIVE | FFHIP_JPEG_PIXELS_LIBJPEG))) return FFHIP_EINVAL;
     const bool lj = (flags & FFHIP_JPEG_PIXELS_LIBJPEG) != 0; /* libjpeg's pixels: full size only */
@@ -334,130 +472,46 @@ static int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *le
     if (n == 0) return FFHIP_OK;
     if (n_threads < 1) n_threads = 1;
     if (n_threads > 64) n_threads = 64;
-    /* ---- headers: each file's geometry and class; a file the mixed path cannot take (progressive, 12-bit, a two-pass layout, an output
-     * or pitch ffhip_jpeg_recon_items refuses) has its code now and takes no further part ---- */
-    std::vector<ffhip_jpeg_geom> geoms((size_t)n);
+    /* ---- headers: each file's geometry and class; a file the mixed path cannot take (progressive without the flag, 12-bit, a two-pass
+     * layout, an output or pitch the rule's items call refuses) has its code now and takes no further part ---- */
+    std::vector<JpegProbed> probed((size_t)n);
     std::vector<int> cls((size_t)n, -1);
-    std::vector<int> prog((size_t)n, 0); /* 1: a progressive file (never with flags = 0) */
-    std::vector<ffhip_size> shown(lj ? (size_t)n : 0); /* the probed display sizes: ffhip_jpeg_recon_items_libjpeg's */
-    int prog_last[5] = {0, 0, 0, 0, 0};
+    std::vector<ffhip_size> shown(lj ? (size_t)n : 0); /* the probed display sizes: the libjpeg rule's */
+    const JpegPixelRule rule = {lj ? nullptr : denom, lj ? shown.data() : nullptr};
     const JpegChoices ch = jpeg_choices();
     ffhip_parallel_for(n, n_threads, [&](int i) {
-        int w = 0, h = 0;
-        ffhip_jpeg_geom &g = geoms[(size_t)i];
-        memset(&g, 0, sizeof(g));
-        if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) status[i] = files[i] && lens[i] ? ffhip_jpeg_probe_any(files[i], lens[i], &g, &w, &h, &prog[(size_t)i]) : FFHIP_EINVAL;
-        else status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
-        if (geom_out) geom_out[i] = g;
+        JpegProbed &p = probed[(size_t)i];
+        p = jpeg_probe_file(files[i], lens[i], flags);
+        status[i] = p.status;
+        if (geom_out) geom_out[i] = p.geom;
         if (status[i]) return;
-        if (lj) {
-            shown[(size_t)i] = ffhip_size{w, h};
-            cls[(size_t)i] = jpeg_libjpeg_item_ok(&g, w, h, d_bgra[i], pitch[i]) ? jpeg_geom_class(&g) : -1;
-        } else if (denom && denom[i] > 1) /* the output holds the scaled picture: rows of 8 / denom x h x mcu_cols pixels */
-            cls[(size_t)i] = jpeg_scaled_item_class(&g, denom[i], d_bgra[i], pitch[i]);
-        else
-            cls[(size_t)i] = jpeg_item_class(ch, &g, d_bgra[i], pitch[i]);
+        if (lj) shown[(size_t)i] = ffhip_size{p.width, p.height};
+        cls[(size_t)i] = jpeg_rule_item_class(ch, rule, i, &p.geom, p.width, p.height, d_bgra[i], pitch[i]);
         if (cls[(size_t)i] < 0) status[i] = FFHIP_EINVAL;
     });
     if (!ffhip_have_device()) return FFHIP_ENODEV;
-    hipStream_t st = (hipStream_t)stream;
     int rc = FFHIP_OK;
+    int prog_last[5] = {0, 0, 0, 0, 0};
     const int turns = (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) ? 2 : 1;
+    int count[JPEG_CLASSES * 2] = {}; /* pictures of every turn */
+    for (int i = 0; i < n; i++)
+        if (cls[(size_t)i] >= 0) count[cls[(size_t)i] * turns + probed[(size_t)i].progressive]++;
     for (int turn = 0; turn < JPEG_CLASSES * turns && rc == FFHIP_OK; turn++) {
         const int c = turn / turns, pg = turn % turns; /* a class's baseline files, then its progressive files */
-        std::vector<int> idx;
-        for (int i = 0; i < n; i++)
-            if (cls[(size_t)i] == c && prog[(size_t)i] == pg) idx.push_back(i);
-        const int nc = (int)idx.size();
-        if (!nc) continue;
-        std::vector<const uint8_t *> cf((size_t)nc);
-        std::vector<size_t> cl((size_t)nc);
-        std::vector<ffhip_jpeg_geom> cg((size_t)nc);
-        std::vector<ffhip_jpeg_item> items((size_t)nc);
-        std::vector<int> cs((size_t)nc, 0), cd((size_t)nc, 1); /* cd: the class's denominators */
-        std::vector<ffhip_size> cshown(lj ? (size_t)nc : 0);
-        std::vector<size_t> base((size_t)nc + 1); /* MCUs of the class's pictures before picture k */
-        for (int k = 0; k < nc; k++) {
-            const int i = idx[(size_t)k];
-            if (denom) cd[(size_t)k] = denom[i];
-            if (lj) cshown[(size_t)k] = shown[(size_t)i];
-            cf[(size_t)k] = files[i]; cl[(size_t)k] = lens[i]; cg[(size_t)k] = geoms[(size_t)i];
-            ffhip_jpeg_item &it = items[(size_t)k];
-            memset(&it, 0, sizeof(it));
-            it.geom = geoms[(size_t)i]; it.d_bgra = d_bgra[i]; it.pitch = pitch[i];
-            base[(size_t)k + 1] = base[(size_t)k] + (size_t)it.geom.mcu_cols * it.geom.mcu_rows;
+        std::vector<MixedPic> pics;
+        pics.reserve((size_t)count[turn]);
+        for (int i = 0; i < n; i++) {
+            if (cls[(size_t)i] != c || probed[(size_t)i].progressive != pg) continue;
+            MixedPic p;
+            memset(&p, 0, sizeof(p));
+            p.index = i; p.file = files[i]; p.len = lens[i];
+            p.item.geom = probed[(size_t)i].geom; p.item.d_bgra = d_bgra[i]; p.item.pitch = pitch[i];
+            p.denom = denom ? denom[i] : 1;
+            if (lj) p.shown = shown[(size_t)i];
+            p.k_max = pg ? jpeg_scaled_k_max(p.denom) : 63;
+            pics.push_back(p);
         }
-        const ffhip_jpeg_geom &g0 = cg[0];
-        const size_t mcus = base[(size_t)nc], yb = mcus * g0.h * g0.v * 64, cb = g0.ncomp == 3 ? mcus * 64 : 0; /* int16 elements of the class */
-        const PlaneBlock blk(yb, cb, (size_t)nc);
-        uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_FILES_MIXED, stream, blk.bytes / 4 + 16);
-        if (!dev) { rc = FFHIP_ENOMEM; break; }
-        const Planes d = blk.at(dev);
-        bool done = false;
-        std::vector<int> kmax((size_t)nc, 63); /* progressive files: the last coefficient the reconstruction reads */
-        for (int k = 0; pg && k < nc; k++) kmax[(size_t)k] = cd[(size_t)k] == 8 ? 0 : cd[(size_t)k] == 4 ? 4 : cd[(size_t)k] == 2 ? 24 : 63;
-        const char *pgpu = pg ? FFHIP_ENV("FFHIP_JPEG_PROGRESSIVE_GPU") : nullptr;
-        if (pg && pgpu && pgpu[0] == '1') {
-            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom && !lj ? cd.data() : nullptr, lj ? cshown.data() : nullptr};
-            int counts[4] = {0, 0, 0, 0};
-            const int grc = jpeg_progressive_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, 63, kmax.data(), cs.data(),
-                                                            stream, &then, counts);
-            if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
-            done = grc == FFHIP_OK;
-            if (done) {
-                for (int q = 0; q < 4; q++) prog_last[q] += counts[q];
-                prog_last[4] = 1;
-            }
-        } else if (!pg && jpeg_entropy_on_device(cf[0], cl[0], nc)) {
-            const FfhipHuffThen then = {nullptr, 0, 0, items.data(), denom && !lj ? cd.data() : nullptr, lj ? cshown.data() : nullptr};
-            const int grc = jpeg_entropy_batch_gpu_impl(cf.data(), cl.data(), nc, n_threads, &g0, cg.data(), d.y, d.u, d.v, d.q, cs.data(), stream, &then);
-            if (grc != FFHIP_OK && grc != FFHIP_EINVAL) { rc = grc; break; }
-            done = grc == FFHIP_OK;
-        }
-        if (!done) {
-            /* host threads: each picture at its own offsets of the pinned planes, one upload, the good pictures reconstructed */
-            if (hipStreamSynchronize(st) != hipSuccess) { rc = FFHIP_EIO; break; } /* the scratch may still be read by what `stream` holds */
-            uint8_t *pin = ffhip_pinned_scratch(SCRATCH_FILES_MIXED, stream, blk.bytes);
-            if (!pin) { rc = FFHIP_ENOMEM; break; }
-            const Planes h = blk.at(pin);
-            std::vector<std::array<int, 3>> pcounts(pg ? (size_t)nc : 0);
-            ffhip_parallel_for(nc, n_threads, [&](int k) {
-                const ffhip_jpeg_geom &g = cg[(size_t)k];
-                const size_t b = base[(size_t)k];
-                if (pg) {
-                    pcounts[(size_t)k] = {0, 0, 0};
-                    cs[(size_t)k] = ffhip_prog_decode_host(cf[(size_t)k], cl[(size_t)k], &g, h.y + b * g.h * g.v * 64, h.u ? h.u + b * 64 : nullptr,
-                                                           h.v ? h.v + b * 64 : nullptr, h.q + (size_t)k * 256, kmax[(size_t)k], pcounts[(size_t)k].data());
-                    return;
-                }
-                cs[(size_t)k] = ffhip_jpeg_entropy_decode(cf[(size_t)k], cl[(size_t)k], &g, h.y + b * g.h * g.v * 64, h.u ? h.u + b * 64 : nullptr,
-                                                          h.v ? h.v + b * 64 : nullptr, h.q + (size_t)k * 256);
-            });
-            if (pg) {
-                for (int k = 0; k < nc; k++) {
-                    prog_last[0] += pcounts[(size_t)k][0] + pcounts[(size_t)k][1] > 0; /* files that parsed, as the device front end counts them */
-                    for (int q = 0; q < 3; q++) prog_last[1 + q] += pcounts[(size_t)k][(size_t)q];
-                }
-                prog_last[4] = 0;
-            }
-            if (hipMemcpyAsync(dev, pin, blk.bytes, hipMemcpyHostToDevice, st) != hipSuccess) { rc = FFHIP_EIO; break; }
-            std::vector<ffhip_jpeg_item> good;
-            std::vector<int> good_d;
-            std::vector<ffhip_size> good_s;
-            for (int k = 0; k < nc; k++) {
-                if (cs[(size_t)k]) continue;
-                ffhip_jpeg_item it = items[(size_t)k];
-                jpeg_item_planes(&it, d.y, d.u, d.v, d.q, base[(size_t)k], (size_t)k);
-                good.push_back(it);
-                good_d.push_back(cd[(size_t)k]);
-                if (lj) good_s.push_back(cshown[(size_t)k]);
-            }
-            rc = lj ? jpeg_recon_items_libjpeg_impl(good.data(), good_s.data(), (int)good.size(), stream, 0)
-                 : denom ? jpeg_recon_items_scaled_impl(good.data(), good_d.data(), (int)good.size(), stream, 0)
-                         : jpeg_recon_items_impl(good.data(), (int)good.size(), stream, 0);
-            if (hipStreamSynchronize(st) != hipSuccess && rc == FFHIP_OK) rc = FFHIP_EIO;
-        }
-        for (int k = 0; k < nc; k++) status[idx[(size_t)k]] = cs[(size_t)k];
+        if (!pics.empty()) rc = mixed_turn(pics, pg != 0, rule, n_threads, stream, status, prog_last);
     }
     if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) ffhip_prog_note_last(prog_last);
     if (rc) return rc;

@@ -10,7 +10,7 @@
  * sum goes into the lane's four accumulators times the row's weight: sum_y qy (sum_x qx v) is the rule's double sum exactly, below 2^32.
  * No intermediate picture goes to memory; a source row is read once per output row whose run holds it (about twice when shrinking).
  */
-#include "ffhip_internal.h"
+#include "ffhip_items.h"
 #include "ffhip_resize_body.h"
 
 #include <string.h>
@@ -156,23 +156,16 @@ extern "C" int ffhip_bgra_resize_items(const ffhip_resize_item *items, int n, in
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
     /* device scratch: the records, the per-workgroup table, the tap tables; pinned staging for the records.  Both per stream */
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_RESIZE_ITEMS, stream, at / 4 + 16);
-    if (!dev) return FFHIP_ENOMEM;
-    uint8_t *pin = ffhip_pinned_staging(SCRATCH_RESIZE_ITEMS, stream, desc_bytes);
-    if (!pin) return FFHIP_ENOMEM;
-    memcpy(pin, desc.data(), desc_bytes);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    if (ffhip_pinned_staged(SCRATCH_RESIZE_ITEMS, stream) != FFHIP_OK) return FFHIP_EIO;
+    uint8_t *dev = nullptr;
+    const int rc = ffhip_items_stage(SCRATCH_RESIZE_ITEMS, stream, desc.data(), desc_bytes, (size_t)total, at - desc_bytes - 4 * (size_t)total, &dev);
+    if (rc) return rc;
     const ResizeItemDesc *d_desc = (const ResizeItemDesc *)dev;
     u32 *d_table = (u32 *)(dev + desc_bytes);
     hipLaunchKernelGGL(k_resize_tables, dim3(2u * (unsigned)n), dim3(256), 0, st, d_desc, dev, d_table, filter);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    for (unsigned long long b = 0; b < total; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups */
-        const unsigned long long left = total - b;
+    return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
         ResizeArgs a;
-        a.desc = d_desc; a.tables = dev; a.wg_item = d_table; a.wg_base = (u32)b;
-        hipLaunchKernelGGL(k_bgra_resize, dim3((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL)), dim3(FFHIP_RESIZE_WG_THREADS), 0, st, a);
-        FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    }
-    return FFHIP_OK;
+        a.desc = d_desc; a.tables = dev; a.wg_item = d_table; a.wg_base = wg_base;
+        hipLaunchKernelGGL(k_bgra_resize, dim3(grid_x), dim3(FFHIP_RESIZE_WG_THREADS), 0, st, a);
+    });
 }

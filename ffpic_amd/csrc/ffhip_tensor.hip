@@ -6,7 +6,7 @@
  * ffhip_bgra_orient_items in front of this stage).
  * The layout of the work is described in ffhip_tensor_body.h.
  */
-#include "ffhip_internal.h"
+#include "ffhip_items.h"
 #include "ffhip_jpeg_scaled_body.h"
 #include "ffhip_orient_body.h"
 #include "ffhip_tensor_body.h"
@@ -24,13 +24,6 @@ struct TensorArgs {
     u32 wg_base;        /* the launch's first workgroup */
     TensorScale s;
 };
-
-/* one workgroup per item: the item's index over its range of the per-workgroup table */
-__global__ __launch_bounds__(256) void k_tensor_items_table(const TensorItemDesc *desc, u32 *wg_item)
-{
-    const u32 item = blockIdx.x, first = desc[item].first_wg, n = desc[item].n_wgs;
-    for (u32 k = threadIdx.x; k < n; k += 256) wg_item[first + k] = item;
-}
 
 /* A workgroup takes FFHIP_TENSOR_WG_UNITS consecutive units of one item, lane l the units l, l + 256, ...: a wave's 64 lanes store 64
  * consecutive 16-byte blocks of a run (or of the runs that follow each other in a narrow picture). */
@@ -126,28 +119,17 @@ extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n,
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     hipStream_t st = (hipStream_t)stream;
     /* device scratch: the records, then the per-workgroup table; pinned staging for the records.  Both per stream */
-    const size_t desc_bytes = (size_t)n * sizeof(TensorItemDesc);
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_TENSOR_ITEMS, stream, desc_bytes / 4 + (size_t)total + 16);
-    if (!dev) return FFHIP_ENOMEM;
-    uint8_t *pin = ffhip_pinned_staging(SCRATCH_TENSOR_ITEMS, stream, desc_bytes);
-    if (!pin) return FFHIP_ENOMEM;
-    memcpy(pin, desc.data(), desc_bytes);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, desc_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    if (ffhip_pinned_staged(SCRATCH_TENSOR_ITEMS, stream) != FFHIP_OK) return FFHIP_EIO;
-    const TensorItemDesc *d_desc = (const TensorItemDesc *)dev;
-    u32 *d_table = (u32 *)(dev + desc_bytes);
-    hipLaunchKernelGGL(k_tensor_items_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_table);
-    FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    const TensorItemDesc *d_desc = nullptr;
+    u32 *d_table = nullptr;
+    const int rc = ffhip_items_upload(SCRATCH_TENSOR_ITEMS, stream, desc, total, &d_desc, &d_table);
+    if (rc) return rc;
     const TensorKernel kernel = tensor_kernel(fmt);
-    for (unsigned long long b = 0; b < total; b += 0x7fffffffULL) { /* a launch stays below 2^31 workgroups */
-        const unsigned long long left = total - b;
+    return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
         TensorArgs a;
-        a.desc = d_desc; a.wg_item = d_table; a.wg_base = (u32)b;
+        a.desc = d_desc; a.wg_item = d_table; a.wg_base = wg_base;
         for (int c = 0; c < 3; c++) { a.s.scale[c] = fmt->scale[c]; a.s.bias[c] = fmt->bias[c]; }
-        hipLaunchKernelGGL(kernel, dim3((unsigned)(left < 0x7fffffffULL ? left : 0x7fffffffULL)), dim3(FFHIP_TENSOR_WG_THREADS), 0, st, a);
-        FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    }
-    return FFHIP_OK;
+        hipLaunchKernelGGL(kernel, dim3(grid_x), dim3(FFHIP_TENSOR_WG_THREADS), 0, st, a);
+    });
 }
 
 /* ---- files in, tensors out ---- */
@@ -368,11 +350,10 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
     std::vector<ffhip_rect> mapped(denom && roi ? (size_t)n : 0);
     TensorStored stored(n, to.on, roi, rs.out_size); /* rectangles and sizes in the stored axes, where the call turns pictures */
     ffhip_parallel_for(n, n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads), [&](int i) {
-        ffhip_jpeg_geom g;
-        memset(&g, 0, sizeof(g));
-        int w = 0, h = 0;
-        if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) status[i] = files[i] && lens[i] ? ffhip_jpeg_probe_any(files[i], lens[i], &g, &w, &h, nullptr) : FFHIP_EINVAL;
-        else status[i] = files[i] && lens[i] ? ffhip_jpeg_probe(files[i], lens[i], &g, &w, &h) : FFHIP_EINVAL;
+        const JpegProbed probed = jpeg_probe_file(files[i], lens[i], flags);
+        const ffhip_jpeg_geom &g = probed.geom;
+        const int w = probed.width, h = probed.height;
+        status[i] = probed.status;
         if (geom_out) geom_out[i] = g;
         pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h, 4LL * g.mcu_cols * 8 * g.h};
         if (to.on) {
@@ -401,22 +382,17 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
     int prog_total[5] = {0, 0, 0, 0, 0}; /* the parts' ffhip_debug_progressive_last, summed (the front end: the last part's) */
     const int rc = tensor_files_run(n, fmt, outs, denom && roi ? mapped.data() : stored.roi(), TensorResize{stored.out_size(), rs.filter}, pic, stored.orient(), status, stream,
                             [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
-        if (flags) { /* ffhip_jpeg_decode_files_tensor_ex: the parts go through the call that takes progressive files */
-            const int prc = ffhip_jpeg_decode_files_mixed_device_ex(files + first, lens + first, cnt, n_threads, d_bgra, pitch, denom ? den.data() + first : nullptr, flags,
-                                                                    geom_out ? geom_out + first : nullptr, status + first, stream);
+        const int prc = jpeg_decode_files_mixed(files + first, lens + first, cnt, n_threads, d_bgra, pitch, denom ? den.data() + first : nullptr, flags,
+                                                geom_out ? geom_out + first : nullptr, status + first, stream);
+        if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) { /* only then has the part written the thread's record */
             int last[5];
             ffhip_debug_progressive_last(last);
             for (int q = 0; q < 4; q++) prog_total[q] += last[q];
             prog_total[4] = last[4];
-            return prc;
         }
-        if (denom)
-            return ffhip_jpeg_decode_files_mixed_device_scaled(files + first, lens + first, cnt, n_threads, d_bgra, pitch, den.data() + first,
-                                                               geom_out ? geom_out + first : nullptr, status + first, stream);
-        return ffhip_jpeg_decode_files_mixed_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, geom_out ? geom_out + first : nullptr,
-                                                    status + first, stream);
+        return prc;
     });
-    if (flags) ffhip_prog_note_last(prog_total);
+    if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) ffhip_prog_note_last(prog_total);
     return rc;
 }
 

@@ -1139,8 +1139,9 @@ int ffhip_jpeg_recon_items_libjpeg(const ffhip_jpeg_item *items, const ffhip_siz
  * whole call, before anything is enqueued (libjpeg's reduced-size transforms are another rule). */
 #define FFHIP_JPEG_PIXELS_LIBJPEG 0x10u
 
-/* Diagnostics: the progressive files of the calling thread's last ffhip_jpeg_progressive_decode, ffhip_jpeg_progressive_batch_gpu,
- * ffhip_jpeg_decode_files_mixed_device_ex or ffhip_jpeg_decode_files_tensor_ex call (all its parts together): out[0] progressive files, [1] scans decoded, [2] scans skipped (k_max), [3] levels launched
+/* Diagnostics: the progressive files of the calling thread's last ffhip_jpeg_progressive_decode or ffhip_jpeg_progressive_batch_gpu call, or
+ * its last ffhip_jpeg_decode_files_mixed_device_ex or ffhip_jpeg_decode_files_tensor_ex call (all its parts together) that passed
+ * FFHIP_JPEG_ACCEPT_PROGRESSIVE -- a call of those two without the flag leaves the record as it was: out[0] progressive files, [1] scans decoded, [2] scans skipped (k_max), [3] levels launched
  * (host front end: the deepest level of each file, summed), [4] the front end taken, 0 host, 1 device (the last class's). */
 int ffhip_debug_progressive_last(int out[5]);
 

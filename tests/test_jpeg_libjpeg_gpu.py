@@ -172,6 +172,26 @@ def test_flag_with_a_denominator_is_refused_and_no_flag_is_the_old_call(files):
         tensors.decode_jpeg_to_tensors(base, pixels="libjpeg", reduce=2)
 
 
+def test_a_tensor_call_without_the_progressive_flag_leaves_the_progressive_record(files):
+    """ffhip_debug_progressive_last is the record of the thread's last call that took progressive files.  A tensor call with
+    FFHIP_JPEG_PIXELS_LIBJPEG alone writes nothing into it, however many parts it takes: here each of two baseline files is a part of its
+    own, and the record a progressive call left before is returned exactly as it was"""
+    prog = [d for n, d, _ in files if "progressive" in n]
+    base = [d for n, d, _ in files if "progressive" not in n][:2]
+    ops.jpeg_decode_files_mixed_device(prog, n_threads=2, progressive=True)
+    before = ops.progressive_last()
+    assert before[0] == len(prog) and before[1] > 0, before
+    capi.setenv("FFHIP_TENSOR_PART_BYTES", 1)
+    try:
+        got = tensors.decode_jpeg_to_tensors(base, layout="HWC", pixels="libjpeg")
+        assert ops.tensor_last_parts() == 2
+    finally:
+        capi.setenv("FFHIP_TENSOR_PART_BYTES", None)
+    assert ops.progressive_last() == before
+    for t, d in zip(got, base):
+        assert np.array_equal(t.cpu().numpy(), LC.pil_rgb(d))
+
+
 # ---------------------------------------------------------------------------------------------------- stream order (DESIGN.md 4.15)
 K = 128         # copies of one stall, as test_stream_order_gpu.py holds them to its rule
 

@@ -299,3 +299,93 @@ def test_two_threads_on_two_streams():
         L.ffhip_stream_destroy(s)
     assert not errors, errors
     assert results == [True, True]
+
+
+# ---------------------------------------------------------------------------------------------------- 8. one file call per pixel rule
+RULE_SIZES = [(16, 16), (72, 40), (33, 17), (50, 24), (24, 40), (61, 35), (17, 16), (40, 39), (72, 16), (19, 23), (64, 40), (45, 31)]
+RULE_LAYOUTS = ["420", "444", "grey"]
+RULES = ["full", "scaled", "libjpeg"]
+
+
+@pytest.fixture(scope="module")
+def rule_files():
+    """twelve small files of three layouts (restart markers on some) with a truncated file in the middle -> (files, index of the bad one);
+    the bad file's header is whole: it is probed, classified and takes its place in its class, and only its scan fails"""
+    rng = np.random.default_rng(41)
+    files = [_writer_file(rng, w, h, RULE_LAYOUTS[k % 3], restart=(k % 4) * 2)[0] for k, (w, h) in enumerate(RULE_SIZES)]
+    whole = _writer_file(rng, 64, 40, "420")[0]
+    sos = whole.rfind(b"\xff\xda")
+    files.insert(6, whole[:sos + (len(whole) - sos) // 3])
+    return files, 6
+
+
+def _rule_items_call(rule, geom, w, h, denom, planes, quant, pitch, rows):
+    """the public items call of the rule on one file's own coefficients -> its output, rows x pitch bytes over 0xA5"""
+    L = capi.lib()
+    keep = [_upload(p) if p is not None else None for p in planes] + [_upload(quant)]
+    out = _upload(np.full(rows * pitch, 0xA5, np.uint8))
+    it = capi.JpegItem()
+    it.geom = geom
+    it.d_coef_y, it.d_coef_u, it.d_coef_v = [b.ptr if b is not None else None for b in keep[:3]]
+    it.d_quant, it.d_bgra, it.pitch = keep[3].ptr, out.ptr, pitch
+    if rule == "full":
+        ops.jpeg_recon_items([it])
+    elif rule == "scaled":
+        ops.jpeg_recon_items_scaled([it], [denom])
+    else:
+        ops.jpeg_recon_items_libjpeg([it], [(w, h)])
+    capi.check(L.ffhip_stream_sync(None))
+    return out.to_host((rows, pitch), np.uint8)
+
+
+@pytest.mark.parametrize("device_entropy", ["0", "1"])
+@pytest.mark.parametrize("rule", RULES)
+def test_each_pixel_rule_in_a_file_call_equals_its_items_call(rule_files, entropy_env, rule, device_entropy):
+    """ffhip_jpeg_decode_files_mixed_device_ex under each rule -- denominators all 1, denominators 1, 2, 4, 8 in turn, libjpeg's pixels -- over
+    the same files: every good file's picture is what the rule's public items call makes of that file's own coefficients
+    (ffhip_jpeg_entropy_decode, upload, ffhip_jpeg_recon_items / _scaled / _libjpeg), so a denominator or display size that reached the
+    reconstruction from another file's place -- a part's offset, or the host threads' list of good files, which is shorter than the class --
+    shows.  The bad file has its code, the call returns it, and the guard bytes behind every row and every output keep their 0xA5."""
+    L = capi.require_device()
+    entropy_env(device_entropy)
+    files, bad = rule_files
+    n = len(files)
+    denom = [1] * n if rule != "scaled" else [(1, 2, 4, 8)[i % 4] for i in range(n)]
+    probed = [ops.jpeg_probe(f) for f in files]
+    sizes, offs, pitches, total = [], [], [], 32
+    for i, ((g, w, h), d) in enumerate(zip(probed, denom)):
+        cw, chh = g.width // d, g.height // d                                       # the coded picture at 1 / d
+        pitch = (4 * cw + 15) // 16 * 16 + 16 * (i % 2)                            # a guard behind every row of every other file
+        sizes.append((cw, chh))
+        offs.append(total)
+        pitches.append(pitch)
+        total += pitch * chh + 16 * (1 + i % 3)
+    dout = _upload(np.full(total, 0xA5, np.uint8))
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
+    geoms, status = (capi.JpegGeom * n)(), (C.c_int * n)()
+    rc = L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n, 4, outs, (C.c_int64 * n)(*pitches), None if rule == "libjpeg" else (C.c_int * n)(*denom),
+                                                   capi.FFHIP_JPEG_PIXELS_LIBJPEG if rule == "libjpeg" else 0, geoms, status, None)
+    capi.check(L.ffhip_stream_sync(None))
+    status = list(status)
+    assert status[bad] != 0 and rc == status[bad], (rc, status)
+    assert all(s == 0 for i, s in enumerate(status) if i != bad), status
+    got = dout.to_host((total,), np.uint8)
+    written = np.zeros(total, bool)
+    for i, ((g, w, h), d, (cw, chh), off, pitch) in enumerate(zip(probed, denom, sizes, offs, pitches)):
+        rows = np.lib.stride_tricks.as_strided(got[off:], (chh, 4 * cw), (pitch, 1))
+        np.lib.stride_tricks.as_strided(written[off:], (chh, 4 * cw), (pitch, 1))[...] = True
+        if i == bad:
+            continue
+        cy = np.empty(g.y_blocks * 64, np.int16)
+        cu, cv = (np.empty(g.c_blocks * 64, np.int16), np.empty(g.c_blocks * 64, np.int16)) if g.ncomp == 3 else (None, None)
+        quant = np.empty((4, 64), np.uint16)
+        capi.check(L.ffhip_jpeg_entropy_decode(bufs[i].ctypes.data, bufs[i].size, C.byref(g), cy.ctypes.data, cu.ctypes.data if cu is not None else None,
+                                               cv.ctypes.data if cv is not None else None, quant.ctypes.data), "ffhip_jpeg_entropy_decode")
+        want = _rule_items_call(rule, g, w, h, d, (cy, cu, cv), quant, pitch, chh)[:, :4 * cw]
+        if rule == "libjpeg":                                                       # outside the display rectangle the bytes are unspecified
+            rows, want = rows[:h, :4 * w], want[:h, :4 * w]
+        assert np.array_equal(rows, want), (i, rule, d, int((rows != want).sum()))
+    assert (got[~written] == 0xA5).all(), np.flatnonzero((got != 0xA5) & ~written)[:8]

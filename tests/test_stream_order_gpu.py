@@ -197,6 +197,44 @@ def jpeg_items_case(name, specs, denom=None, seed=0, many=False):
     return Case(name, call, operands, [out], expect)
 
 
+def jpeg_items_libjpeg_case(name, specs, seed=0):
+    """ffhip_jpeg_recon_items_libjpeg on the pictures of `specs`, every display size short of the coded one in both directions (the chroma
+    grid ends inside the last MCU: its edge replication is live); stream-ordered: every coefficient plane and the quantiser tables.  The
+    expected bytes are the host function's (ffhip_jpeg_libjpeg_picture) inside the display rectangles; what the call writes of a coded
+    picture outside its display rectangle is unspecified and is taken from the consumer's copy"""
+    L = capi.lib()
+    q, qd = synth.quant_tables(), synth.quant_tables(quality=50)
+    items, places, total = small_items(specs)
+    shown = [(geom.width - 1 - 2 * (k % 2), geom.height - 3) for k, (geom, _, _, _) in enumerate(places)]
+    dq, out = Operand(q, qd), Output(total)
+    operands, shared, pictures = [dq], {}, {}
+    for k, (it, (geom, off, pitch, true)) in enumerate(zip(items, places)):
+        if specs[k] not in shared:
+            decoy = synth.coef_batch(1, geom.mcu_cols, geom.mcu_rows, geom.ncomp, geom.h, geom.v, first=1000 + k + seed)
+            devs = [Operand(t, d) if t is not None else None for t, d in zip(true, decoy)]
+            operands += [d for d in devs if d is not None]
+            shared[specs[k]] = (true, decoy, devs)
+        it.d_coef_y, it.d_coef_u, it.d_coef_v = [d.ptr if d is not None else None for d in shared[specs[k]][2]]
+        it.d_quant, it.d_bgra, it.pitch = dq.ptr, out.ptr + off, pitch
+    arr = (capi.JpegItem * len(items))(*items)
+    sizes = (capi.Size * len(items))(*[capi.Size(w, h) for w, h in shown])
+
+    def call(s):
+        capi.check(L.ffhip_jpeg_recon_items_libjpeg(arr, sizes, len(items), s), "ffhip_jpeg_recon_items_libjpeg")
+
+    def expect(which):
+        buf, got = np.full(total, FILL, np.uint8), out.copied()
+        for k, ((geom, off, pitch, _), (w, h)) in enumerate(zip(places, shown)):
+            key = (which, specs[k], w, h)                          # pictures of one spec and display size are one host picture
+            if key not in pictures:
+                pictures[key] = ops.jpeg_libjpeg_picture(geom, w, h, *shared[specs[k]][which == "decoy"], pick(which, q, qd))
+            coded = np.lib.stride_tricks.as_strided(got[off:], (geom.height, geom.width, 4), (pitch, 4, 1)).copy()
+            coded[:h, :w] = pictures[key]
+            place(buf, off, coded.shape, pitch, coded)
+        return [buf]
+    return Case(name, call, operands, [out], expect)
+
+
 def jpeg_batch_case(h=2, v=2, mc=5, mr=4, n=2):
     """ffhip_jpeg_recon_batch; stream-ordered: planes, quantiser tables and (two-pass layouts) the caller's workspace"""
     L = capi.lib()
@@ -757,6 +795,7 @@ def test_heif_grid_compose(stall, stream):
 ITEMS_ENTRIES = {
     "jpeg_recon_items": lambda count, seed: jpeg_items_case(f"jpeg_recon_items n{count}", [JPEG_SMALL[(k + seed) % 4] for k in range(count)], None, seed, many=True),
     "jpeg_recon_items_scaled": lambda count, seed: jpeg_items_case(f"jpeg_recon_items_scaled n{count}", [JPEG_SMALL[(k + seed) % 4] for k in range(count)], 4, seed, many=True),
+    "jpeg_recon_items_libjpeg": lambda count, seed: jpeg_items_libjpeg_case(f"jpeg_recon_items_libjpeg n{count}", [JPEG_SMALL[(k + seed) % 4] for k in range(count)], seed),
     "bgra_resize_items": lambda count, seed: resize_case(AA, count, seed),
     "bgra_orient_items": lambda count, seed: orient_case(count, seed),
     "bgra_to_tensor_items": lambda count, seed: tensor_case(F16, 1, count, seed),
