@@ -67,12 +67,13 @@ bool tensor_format_ok(const ffhip_tensor_format *f)
     return true;
 }
 
-/* an item the call takes under format f; fills its record (first_wg aside) */
-bool tensor_item_desc(const ffhip_tensor_item &it, const ffhip_tensor_format *f, TensorItemDesc *out)
+/* an item the call takes under format f, its picture's address aside (the file calls plan their items before their pictures have one);
+ * fills its record (src and first_wg aside) */
+bool tensor_item_layout(const ffhip_tensor_item &it, const ffhip_tensor_format *f, TensorItemDesc *out)
 {
     const int es = tensor_elem_size(f->dtype);
     if (it.width < 1 || it.height < 1 || it.x0 < 0 || it.y0 < 0) return false;
-    if (!it.d_bgra || ((uintptr_t)it.d_bgra & 3) || it.pitch < 4 || (it.pitch & 3)) return false;
+    if (it.pitch < 4 || (it.pitch & 3)) return false;
     /* source offsets stay within 31 bits, as the decode calls' own pictures do (pitch x rows < 2^31), and the rectangle within the pitch */
     if (4LL * ((long long)it.x0 + it.width) > it.pitch || ((long long)it.y0 + it.height) * it.pitch > 0x7fffffffLL) return false;
     if (!it.d_out || ((uintptr_t)it.d_out & (uintptr_t)(es - 1))) return false;
@@ -88,7 +89,6 @@ bool tensor_item_desc(const ffhip_tensor_item &it, const ffhip_tensor_format *f,
     const long long units = (run_len * es + 15) / 16 + 1;
     if (runs * units > 0xffffffffLL) return false; /* a unit's index is 32-bit */
     memset(out, 0, sizeof(*out));
-    out->src = it.d_bgra + (long long)it.y0 * it.pitch + 4LL * it.x0;
     out->dst = (uint8_t *)it.d_out;
     out->pitch = it.pitch;
     out->row_stride = it.row_stride;
@@ -98,6 +98,14 @@ bool tensor_item_desc(const ffhip_tensor_item &it, const ffhip_tensor_format *f,
     out->units = (u32)units;
     out->total = (u32)(runs * units);
     out->n_wgs = (u32)((runs * units + FFHIP_TENSOR_WG_UNITS - 1) / FFHIP_TENSOR_WG_UNITS);
+    return true;
+}
+
+/* an item the call takes under format f; fills its record (first_wg aside) */
+bool tensor_item_desc(const ffhip_tensor_item &it, const ffhip_tensor_format *f, TensorItemDesc *out)
+{
+    if (!it.d_bgra || ((uintptr_t)it.d_bgra & 3) || !tensor_item_layout(it, f, out)) return false;
+    out->src = it.d_bgra + (long long)it.y0 * it.pitch + 4LL * it.x0;
     return true;
 }
 
@@ -136,6 +144,8 @@ extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n,
 namespace {
 
 struct TensorPicture { int coded_w, coded_h, width, height; int64_t pitch; }; /* what a decode call writes; what the file displays (inside it); its row bytes */
+struct TensorProbe { int code; TensorPicture pic; };                          /* a codec's word on a file: pic (at full size) is valid where code == 0 */
+typedef int (*TensorTag)(const uint8_t *file, size_t len, int *orientation);   /* a codec's reader of the EXIF orientation */
 thread_local int g_tensor_last_parts = 0; /* ffhip_debug_tensor_last_parts */
 thread_local int g_orient_last_items = 0; /* ffhip_debug_orient_last_items */
 /* decodes files [first, first + cnt) into d_bgra[k] with pitch[k]: the call underneath, its per-file codes into status + first */
@@ -148,241 +158,264 @@ size_t tensor_part_budget()
     return b > 0 ? (size_t)b : (size_t)1 << 30;
 }
 
-struct TensorResize { const ffhip_size *out_size; int filter; }; /* out_size == NULL: every file keeps its rectangle's size */
+/* What an entry point was asked for behind the files, the format and the outputs.  roi and out_size are the caller's: UPRIGHT axes, full
+ * size.  out_size == NULL: every file keeps its rectangle's size.  denom == NULL: every file at full size; otherwise file i at
+ * 1 / denom[i], 0 for the largest denominator at which its rectangle still covers out_size[i].  oriented: the calls that turn pictures
+ * upright, orient[i] 1..8 or 0 ("the file's tag"), orient == NULL: every file's tag */
+struct TensorOptions {
+    explicit TensorOptions(const ffhip_rect *r) : roi(r) {}
+    TensorOptions &resize(const ffhip_size *s, int f) { out_size = s; filter = f; return *this; }
+    TensorOptions &scale(const int *d, int *d_out) { denom = d; denom_out = d_out; return *this; }
+    TensorOptions &turn(const int *o, int *o_out) { oriented = true; orient = o; orient_out = o_out; return *this; }
+    TensorOptions &with(unsigned f) { flags = f; return *this; }
+    const ffhip_rect *roi;
+    const ffhip_size *out_size = nullptr;
+    int filter = FFHIP_RESIZE_BILINEAR;
+    const int *denom = nullptr, *orient = nullptr;
+    int *denom_out = nullptr, *orient_out = nullptr;
+    bool oriented = false;
+    unsigned flags = 0u;
+};
 
-/* pic[i] is valid where status[i] == 0 (the probe's verdict).  orient == NULL: the calls without orientation.  Otherwise orient[i] in 1..8
- * where status[i] == 0, and roi and rs.out_size are the STORED ones (mapped and swapped by the caller): decode and resize run as without,
- * and a file of another orientation than 1 goes through ffhip_bgra_orient_items -- its resized picture, or its rectangle -- into part
- * scratch at pitch 4 x upright width, which the sink then reads whole; outs[i] is laid out for the upright size */
-int tensor_files_run(int n, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs, const ffhip_rect *roi, const TensorResize &rs,
-                     const std::vector<TensorPicture> &pic, const int *orient, int *status, void *stream, const TensorDecode &decode)
+/* One file of a call, planned once (tensor_file_plan) and only read afterwards */
+struct TensorFile {
+    int code = FFHIP_OK;         /* the probe's, or this call's own FFHIP_EINVAL; 0: the file takes part */
+    bool refused_here = false;   /* code is this call's: the decoder still gets the file, and its code comes first */
+    TensorPicture pic = {};      /* what the decoder writes: the SCALED picture where there is a denominator */
+    ffhip_rect rect = {};        /* the rectangle of that picture to deliver: stored axes, mapped by the denominator */
+    ffhip_size resized = {0, 0}; /* {0, 0}: no resize; stored axes */
+    int orient = 1, denom = 1;   /* 1..8; 1, 2, 4, 8 */
+    ffhip_tensor_item sink = {}; /* everything but d_bgra */
+    size_t decoded_bytes = 0, resized_bytes = 0, upright_bytes = 0; /* the pictures' places in part scratch, 0 where the stage is not taken */
+};
+
+size_t tensor_place(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+/* a BGRA rectangle on its way through a file's stages */
+struct TensorView { uint8_t *ptr; int64_t pitch; int x0, y0, width, height; };
+TensorView tensor_whole(uint8_t *ptr, int width, int height) { return TensorView{ptr, 4LL * width, 0, 0, width, height}; }
+
+/* File f's stages, from its picture at `decoded` to what the sink reads: the rectangle; where f is resized, *s takes the rectangle to the
+ * whole picture at `small`; where f is turned, *t takes that to the whole upright picture at `upright`.  The planner runs it without
+ * addresses, the part loop with the part's */
+TensorView tensor_chain(const TensorFile &f, uint8_t *decoded, uint8_t *small, uint8_t *upright, ffhip_resize_item *s, ffhip_orient_item *t)
 {
-    const ffhip_size *out_size = rs.out_size;
+    TensorView v{decoded, f.pic.pitch, f.rect.x0, f.rect.y0, f.rect.width, f.rect.height};
+    if (f.resized.width) {
+        const TensorView to = tensor_whole(small, f.resized.width, f.resized.height);
+        *s = ffhip_resize_item{v.ptr, v.pitch, v.x0, v.y0, v.width, v.height, to.ptr, to.pitch, to.width, to.height};
+        v = to;
+    }
+    if (f.orient != 1) {
+        const bool swap = FFHIP_ORIENT_TRANSPOSE(f.orient);
+        const TensorView to = tensor_whole(upright, swap ? v.height : v.width, swap ? v.width : v.height);
+        *t = ffhip_orient_item{v.ptr, v.pitch, v.x0, v.y0, v.width, v.height, to.ptr, to.pitch, f.orient};
+        v = to;
+    }
+    return v;
+}
+
+/* File i's record, from the probe's word p and the orientation o it is delivered at (1 where the call turns nothing).  Everything a call
+ * decides about a file's rectangle, sizes and output is decided here, without the device; what it writes besides the record is
+ * denom_out[i] and orient_out[i] (0 for a file the probe refused) */
+TensorFile tensor_file_plan(const TensorProbe &p, int o, int i, const TensorOptions &opts, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs)
+{
+    TensorFile f;
+    f.code = p.code;
+    f.pic = p.pic;
+    if (opts.oriented && opts.orient_out) opts.orient_out[i] = p.code ? 0 : o;
+    if (opts.denom && opts.denom_out) opts.denom_out[i] = 0;
+    if (p.code) return f;
+    const bool swap = FFHIP_ORIENT_TRANSPOSE(o);
+    const int w = p.pic.width, h = p.pic.height, uw = swap ? h : w, uh = swap ? w : h; /* full size: stored, upright */
+    const ffhip_rect asked = opts.roi ? opts.roi[i] : ffhip_rect{0, 0, uw, uh};
+    bool ok = asked.x0 >= 0 && asked.y0 >= 0 && asked.width >= 1 && asked.height >= 1 && (long long)asked.x0 + asked.width <= uw &&
+              (long long)asked.y0 + asked.height <= uh;
+    ffhip_rect r = asked; /* in the stored axes */
+    if (ok && o != 1) ok = ffhip_orient_rect(w, h, o, &asked, &r) == FFHIP_OK;
+    const ffhip_size to = !opts.out_size ? ffhip_size{0, 0} : swap ? ffhip_size{opts.out_size[i].height, opts.out_size[i].width} : opts.out_size[i];
+    if (opts.denom) { /* the decoder's picture is the scaled one: sizes rounded up, a pitch rounded up to 16 bytes */
+        int d = opts.denom[i];
+        if (d == 0) d = ok && to.width >= 1 && to.height >= 1 ? ffhip_jpeg_scale_choose(r.width, r.height, to.width, to.height) : 1;
+        if (opts.denom_out) opts.denom_out[i] = d;
+        const int cw = p.pic.coded_w / d;
+        f.denom = d;
+        f.pic = TensorPicture{cw, p.pic.coded_h / d, jpeg_scaled_len(w, d), jpeg_scaled_len(h, d), (4LL * cw + 15) & ~15LL};
+        if (ok) r = jpeg_scaled_rect_of(w, h, d, r);
+    }
+    f.decoded_bytes = tensor_place((size_t)f.pic.pitch * f.pic.coded_h);
+    if (ok && opts.out_size) /* the rectangle is the resize's source */
+        ok = r.width <= FFHIP_RESIZE_MAX_SIDE && r.height <= FFHIP_RESIZE_MAX_SIDE && to.width >= 1 && to.width <= FFHIP_RESIZE_MAX_SIDE &&
+             to.height >= 1 && to.height <= FFHIP_RESIZE_MAX_SIDE;
+    if (ok) {
+        f.rect = r;
+        f.resized = to;
+        f.orient = o;
+        ffhip_resize_item s;
+        ffhip_orient_item t;
+        const TensorView v = tensor_chain(f, nullptr, nullptr, nullptr, &s, &t);
+        /* what the sink checks of its source, the orient stage checks of its own */
+        if (o != 1) ok = ((long long)t.y0 + t.height) * t.src_pitch <= 0x7fffffffLL;
+        f.sink = ffhip_tensor_item{nullptr, v.pitch, v.x0, v.y0, v.width, v.height, outs[i].d_out, outs[i].row_stride, outs[i].plane_stride};
+        TensorItemDesc d;
+        ok = ok && tensor_item_layout(f.sink, fmt, &d);
+        f.resized_bytes = to.width ? tensor_place((size_t)4 * to.width * to.height) : 0;
+        f.upright_bytes = o != 1 ? tensor_place((size_t)4 * v.width * v.height) : 0;
+    }
+    if (!ok) { /* the file still goes to the decoder, which may have a code of its own for it; no stage behind it takes it */
+        f.code = FFHIP_EINVAL;
+        f.refused_here = true;
+        f.resized_bytes = f.upright_bytes = 0;
+    }
+    return f;
+}
+
+/* a part: files while their pictures fit the budget; a picture larger than the budget is a part of its own */
+struct TensorPart { int first, cnt; size_t decoded, resized, upright; };
+
+TensorPart tensor_part_extent(const std::vector<TensorFile> &plan, int first, size_t budget)
+{
+    TensorPart p{first, 0, 0, 0, 0};
+    for (; (size_t)(first + p.cnt) < plan.size(); p.cnt++) {
+        const TensorFile &f = plan[(size_t)(first + p.cnt)];
+        if (p.cnt && p.decoded + p.resized + p.upright + f.decoded_bytes + f.resized_bytes + f.upright_bytes > budget) break;
+        p.decoded += f.decoded_bytes;
+        p.resized += f.resized_bytes;
+        p.upright += f.upright_bytes;
+    }
+    return p;
+}
+
+/* the part's pictures, one behind the other from *base on, each at its record's pitch.  Returns what ends the call: a decoder return that
+ * is none of the part's file codes */
+int tensor_part_decode(const std::vector<TensorFile> &plan, const TensorPart &p, const int *status, void *stream, const TensorDecode &decode, uint8_t **base)
+{
+    *base = (uint8_t *)ffhip_scratch(SCRATCH_TENSOR_BGRA, stream, p.decoded / 4 + 64);
+    if (!*base) return FFHIP_ENOMEM;
+    std::vector<uint8_t *> d_bgra((size_t)p.cnt);
+    std::vector<int64_t> pitch((size_t)p.cnt);
+    size_t at = 0;
+    for (int k = 0; k < p.cnt; k++) { /* (a file the probe refused: the decoder refuses it again before it looks at its output) */
+        const TensorFile &f = plan[(size_t)(p.first + k)];
+        d_bgra[(size_t)k] = *base + at;
+        pitch[(size_t)k] = f.code && !f.refused_here ? 0 : f.pic.pitch;
+        at += f.decoded_bytes;
+    }
+    g_tensor_last_parts++;
+    const int rc = decode(p.first, p.cnt, d_bgra.data(), pitch.data());
+    for (int k = 0; rc && k < p.cnt; k++)
+        if (status[p.first + k] == rc) return FFHIP_OK; /* a file's code */
+    return rc;
+}
+
+/* behind the decoder: every file it delivered through its stages, at most one call per stage with the items in file order; a file this
+ * call refuses gets its code here */
+int tensor_part_enqueue(const std::vector<TensorFile> &plan, const TensorPart &p, uint8_t *base, const TensorOptions &opts, const ffhip_tensor_format *fmt,
+                        int *status, void *stream)
+{
+    uint8_t *small = nullptr; /* the part's resized pictures, pitch 4 x out width */
+    if (opts.out_size && !(small = (uint8_t *)ffhip_scratch(SCRATCH_RESIZE_BGRA, stream, p.resized / 4 + 64))) return FFHIP_ENOMEM;
+    uint8_t *upright = nullptr; /* the part's upright pictures, pitch 4 x upright width */
+    if (p.upright && !(upright = (uint8_t *)ffhip_scratch(SCRATCH_ORIENT_BGRA, stream, p.upright / 4 + 64))) return FFHIP_ENOMEM;
+    std::vector<ffhip_resize_item> shrink;
+    std::vector<ffhip_orient_item> turn;
+    std::vector<ffhip_tensor_item> good;
+    good.reserve((size_t)p.cnt);
+    for (int k = 0; k < p.cnt; k++) {
+        const int i = p.first + k;
+        const TensorFile &f = plan[(size_t)i];
+        uint8_t *decoded = base;
+        base += f.decoded_bytes;
+        if (status[i]) continue;
+        if (f.refused_here) { status[i] = f.code; continue; }
+        ffhip_resize_item s;
+        ffhip_orient_item t;
+        ffhip_tensor_item sink = f.sink;
+        sink.d_bgra = tensor_chain(f, decoded, small, upright, &s, &t).ptr;
+        if (f.resized_bytes) { shrink.push_back(s); small += f.resized_bytes; }
+        if (f.upright_bytes) { turn.push_back(t); upright += f.upright_bytes; }
+        good.push_back(sink);
+    }
+    if (opts.out_size) {
+        const int rc = ffhip_bgra_resize_items(shrink.data(), (int)shrink.size(), opts.filter, stream);
+        if (rc) return rc;
+    }
+    if (!turn.empty()) {
+        const int rc = ffhip_bgra_orient_items(turn.data(), (int)turn.size(), stream);
+        if (rc) return rc;
+        g_orient_last_items += (int)turn.size();
+    }
+    return ffhip_bgra_to_tensor_items(good.data(), (int)good.size(), fmt, stream);
+}
+
+/* The driver: the planned files part by part -- decode, the stages behind it, one synchronisation (the next part decodes into the same
+ * scratch).  status[i] holds the probe's code on entry; behind it the decoder's, then this call's own.  Returns the first file's code */
+int tensor_files_run(const std::vector<TensorFile> &plan, const TensorOptions &opts, const ffhip_tensor_format *fmt, int *status, void *stream,
+                     const TensorDecode &decode)
+{
     g_tensor_last_parts = 0; /* a call that returns before its first part has taken none */
     g_orient_last_items = 0;
-    auto turned = [&](int i) { return orient && !status[i] && orient[i] != 1; };
-    /* the items, with a stand-in for the picture's address: everything about rectangle and output is checked before anything is enqueued */
-    std::vector<ffhip_tensor_item> item((size_t)n);
-    std::vector<int> mine((size_t)n, FFHIP_OK); /* the code this call gives a file the decoder takes */
-    for (int i = 0; i < n; i++) {
-        if (status[i]) continue;
-        const TensorPicture &p = pic[(size_t)i];
-        const ffhip_rect r = roi ? roi[i] : ffhip_rect{0, 0, p.width, p.height};
-        ffhip_tensor_item &it = item[(size_t)i];
-        it.d_bgra = (const uint8_t *)(uintptr_t)256; it.pitch = p.pitch;
-        it.x0 = r.x0; it.y0 = r.y0; it.width = r.width; it.height = r.height;
-        it.d_out = outs[i].d_out; it.row_stride = outs[i].row_stride; it.plane_stride = outs[i].plane_stride;
-        TensorItemDesc d;
-        bool ok = r.x0 >= 0 && r.y0 >= 0 && r.width >= 1 && r.height >= 1 && (long long)r.x0 + r.width <= p.width && (long long)r.y0 + r.height <= p.height;
-        if (ok && out_size) { /* the rectangle is the resize's source; the sink takes the whole resized picture */
-            const ffhip_size &o = out_size[i];
-            ok = r.width <= FFHIP_RESIZE_MAX_SIDE && r.height <= FFHIP_RESIZE_MAX_SIDE && o.width >= 1 && o.width <= FFHIP_RESIZE_MAX_SIDE &&
-                 o.height >= 1 && o.height <= FFHIP_RESIZE_MAX_SIDE;
-            it.pitch = 4LL * o.width; it.x0 = 0; it.y0 = 0; it.width = o.width; it.height = o.height;
-        }
-        if (ok && turned(i)) { /* the sink takes the whole upright picture; what it checked of the source, the stage checks of its own */
-            const bool swap = FFHIP_ORIENT_TRANSPOSE(orient[i]);
-            ok = ((long long)it.y0 + it.height) * it.pitch <= 0x7fffffffLL;
-            const int uw = swap ? it.height : it.width, uh = swap ? it.width : it.height;
-            it.pitch = 4LL * uw; it.x0 = 0; it.y0 = 0; it.width = uw; it.height = uh;
-        }
-        if (!ok || !tensor_item_desc(it, fmt, &d)) mine[(size_t)i] = FFHIP_EINVAL;
-    }
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t budget = tensor_part_budget();
-    auto bytes_of = [&](int i) { return status[i] ? (size_t)0 : ((size_t)pic[(size_t)i].pitch * pic[(size_t)i].coded_h + 255) & ~(size_t)255; };
-    /* the resized picture of a file that gets one */
-    auto resized_of = [&](int i) { return !out_size || status[i] || mine[(size_t)i] ? (size_t)0 : ((size_t)4 * out_size[i].width * out_size[i].height + 255) & ~(size_t)255; };
-    /* the upright picture of a file that gets one */
-    auto upright_of = [&](int i) { return !turned(i) || mine[(size_t)i] ? (size_t)0 : ((size_t)4 * item[(size_t)i].width * item[(size_t)i].height + 255) & ~(size_t)255; };
-    for (int first = 0; first < n;) {
-        /* a part: files while their pictures fit the budget; a picture larger than the budget is a part of its own */
-        int cnt = 0;
-        size_t bytes = 0, resized = 0, upright = 0;
-        while (first + cnt < n && (cnt == 0 || bytes + resized + upright + bytes_of(first + cnt) + resized_of(first + cnt) + upright_of(first + cnt) <= budget)) {
-            resized += resized_of(first + cnt);
-            upright += upright_of(first + cnt);
-            bytes += bytes_of(first + cnt++);
-        }
-        uint8_t *base = (uint8_t *)ffhip_scratch(SCRATCH_TENSOR_BGRA, stream, bytes / 4 + 64);
-        if (!base) return FFHIP_ENOMEM;
-        std::vector<uint8_t *> d_bgra((size_t)cnt);
-        std::vector<int64_t> pitch((size_t)cnt);
-        size_t at = 0;
-        for (int k = 0; k < cnt; k++) { /* (a file the probe refused: the decoder refuses it again before it looks at its output) */
-            d_bgra[(size_t)k] = base + at;
-            pitch[(size_t)k] = status[first + k] ? 0 : pic[(size_t)(first + k)].pitch;
-            at += bytes_of(first + k);
-        }
-        g_tensor_last_parts++;
-        const int rc = decode(first, cnt, d_bgra.data(), pitch.data());
-        if (rc) { /* a file's code, or the call's own failure */
-            bool a_files = false;
-            for (int k = 0; k < cnt; k++) a_files = a_files || status[first + k] == rc;
-            if (!a_files) return rc;
-        }
-        uint8_t *small = nullptr; /* the part's resized pictures, pitch 4 x out width */
-        if (out_size && !(small = (uint8_t *)ffhip_scratch(SCRATCH_RESIZE_BGRA, stream, resized / 4 + 64))) return FFHIP_ENOMEM;
-        uint8_t *turn_to = nullptr; /* the part's upright pictures, pitch 4 x upright width */
-        if (upright && !(turn_to = (uint8_t *)ffhip_scratch(SCRATCH_ORIENT_BGRA, stream, upright / 4 + 64))) return FFHIP_ENOMEM;
-        std::vector<ffhip_tensor_item> good;
-        std::vector<ffhip_resize_item> shrink;
-        std::vector<ffhip_orient_item> turn;
-        size_t small_at = 0, turn_at = 0;
-        for (int k = 0; k < cnt; k++) {
-            const int i = first + k;
-            if (status[i]) continue;
-            if (mine[(size_t)i]) { status[i] = mine[(size_t)i]; continue; }
-            item[(size_t)i].d_bgra = d_bgra[(size_t)k];
-            const ffhip_rect r = roi ? roi[i] : ffhip_rect{0, 0, pic[(size_t)i].width, pic[(size_t)i].height};
-            ffhip_orient_item t; /* what the stage turns where there is no resize: the rectangle of the decoded picture */
-            t.d_src = d_bgra[(size_t)k]; t.src_pitch = pitch[(size_t)k];
-            t.x0 = r.x0; t.y0 = r.y0; t.width = r.width; t.height = r.height;
-            if (out_size) {
-                ffhip_resize_item s;
-                s.d_src = d_bgra[(size_t)k]; s.src_pitch = pitch[(size_t)k];
-                s.x0 = r.x0; s.y0 = r.y0; s.width = r.width; s.height = r.height;
-                s.d_dst = small + small_at; s.dst_pitch = 4LL * out_size[i].width;
-                s.out_width = out_size[i].width; s.out_height = out_size[i].height;
-                shrink.push_back(s);
-                item[(size_t)i].d_bgra = s.d_dst;
-                small_at += resized_of(i);
-                t.d_src = s.d_dst; t.src_pitch = s.dst_pitch;
-                t.x0 = 0; t.y0 = 0; t.width = s.out_width; t.height = s.out_height;
-            }
-            if (turned(i)) {
-                t.d_dst = turn_to + turn_at; t.dst_pitch = item[(size_t)i].pitch;
-                t.orientation = orient[i];
-                turn.push_back(t);
-                item[(size_t)i].d_bgra = t.d_dst;
-                turn_at += upright_of(i);
-            }
-            good.push_back(item[(size_t)i]);
-        }
-        if (out_size) {
-            const int rrc = ffhip_bgra_resize_items(shrink.data(), (int)shrink.size(), rs.filter, stream);
-            if (rrc) return rrc;
-        }
-        if (!turn.empty()) {
-            const int trc = ffhip_bgra_orient_items(turn.data(), (int)turn.size(), stream);
-            if (trc) return trc;
-            g_orient_last_items += (int)turn.size();
-        }
-        const int src = ffhip_bgra_to_tensor_items(good.data(), (int)good.size(), fmt, stream);
-        if (src) return src;
-        FFHIP_CHECK(hipStreamSynchronize((hipStream_t)stream), FFHIP_EIO); /* the next part decodes into the same scratch */
-        first += cnt;
+    for (int first = 0; (size_t)first < plan.size();) {
+        const TensorPart p = tensor_part_extent(plan, first, budget);
+        uint8_t *base = nullptr;
+        int rc = tensor_part_decode(plan, p, status, stream, decode, &base);
+        if (!rc) rc = tensor_part_enqueue(plan, p, base, opts, fmt, status, stream);
+        if (rc) return rc;
+        FFHIP_CHECK(hipStreamSynchronize((hipStream_t)stream), FFHIP_EIO);
+        first += p.cnt;
     }
-    for (int i = 0; i < n; i++)
+    for (size_t i = 0; i < plan.size(); i++)
         if (status[i]) return status[i];
     return FFHIP_OK;
 }
 
-bool tensor_files_args_ok(const uint8_t *const *files, const size_t *lens, int n, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs, const int *status)
+/* what every entry refuses before it looks at a file */
+bool tensor_files_args_ok(const uint8_t *const *files, const size_t *lens, int n, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs, const int *status,
+                          const TensorOptions &opts)
 {
-    return n >= 0 && tensor_format_ok(fmt) && (n == 0 || (files && lens && outs && status));
-}
-
-bool resize_files_args_ok(int n, const ffhip_size *out_size, int filter)
-{
-    return (filter == FFHIP_RESIZE_BILINEAR || filter == FFHIP_RESIZE_ANTIALIAS) && (n <= 0 || out_size);
-}
-
-/* on: the _oriented calls.  orient[i] 1..8 or 0 ("the file's tag"); orient == NULL: every file's tag */
-struct TensorOrient { bool on; const int *orient; int *orient_out; };
-
-bool orient_files_args_ok(int n, const TensorOrient &to)
-{
-    for (int i = 0; to.on && to.orient && i < n; i++)
-        if (to.orient[i] < 0 || to.orient[i] > 8) return false;
+    if (n < 0 || !tensor_format_ok(fmt) || (n > 0 && !(files && lens && outs && status))) return false;
+    if (opts.filter != FFHIP_RESIZE_BILINEAR && opts.filter != FFHIP_RESIZE_ANTIALIAS) return false;
+    for (int i = 0; opts.oriented && opts.orient && i < n; i++)
+        if (opts.orient[i] < 0 || opts.orient[i] > 8) return false;
     return true;
 }
 
-/* What the run sees of the caller's upright rectangles and sizes.  Off: the caller's own arrays, nothing else.  On: per file the
- * orientation used, the rectangle mapped by ffhip_orient_rect (an empty one where it leaves the upright picture: the run refuses the
- * file) and the size swapped for 5..8 */
-class TensorStored {
-public:
-    TensorStored(int n, bool on, const ffhip_rect *roi, const ffhip_size *out_size)
-        : on_(on), caller_roi_(roi), caller_size_(out_size), o_(on ? (size_t)n : 0, 1), roi_(on && roi ? (size_t)n : 0, ffhip_rect{0, 0, 0, 0}),
-          size_(on && out_size ? (size_t)n : 0, ffhip_size{0, 0}) {}
-    /* file i: orientation o (0: the probe refused the file), its stored display size w x h */
-    void set(int i, int o, int w, int h, int *orient_out)
-    {
-        if (orient_out) orient_out[i] = o;
-        o_[(size_t)i] = o ? o : 1;
-        if (!o) return;
-        if (caller_roi_ && ffhip_orient_rect(w, h, o, &caller_roi_[i], &roi_[(size_t)i]) != FFHIP_OK) roi_[(size_t)i] = ffhip_rect{0, 0, 0, 0};
-        if (caller_size_) {
-            const ffhip_size s = caller_size_[i];
-            size_[(size_t)i] = FFHIP_ORIENT_TRANSPOSE(o) ? ffhip_size{s.height, s.width} : s;
-        }
-    }
-    const ffhip_rect *roi() const { return on_ && caller_roi_ ? roi_.data() : caller_roi_; }
-    const ffhip_size *out_size() const { return on_ && caller_size_ ? size_.data() : caller_size_; }
-    const int *orient() const { return on_ ? o_.data() : nullptr; }
-
-private:
-    bool on_;
-    const ffhip_rect *caller_roi_;
-    const ffhip_size *caller_size_;
-    std::vector<int> o_;
-    std::vector<ffhip_rect> roi_;
-    std::vector<ffhip_size> size_;
-};
-
-/* the two families' common bodies: rs.out_size == NULL is the call without a resize */
-/* denom == NULL: every file at full size, the calls as they were.  Otherwise file i is decoded at 1 / denom[i] of its size (0: the largest
- * denominator at which its rectangle still covers out_size[i], ffhip_jpeg_scale_choose): the picture the run below sees is the SCALED one
- * -- coded and display size, a pitch rounded up to 16 bytes -- and the rectangle is the full-size one mapped onto it */
-int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
-                      const ffhip_rect *roi, const TensorResize &rs, const int *denom, int *denom_out, const TensorOrient &to,
-                      ffhip_jpeg_geom *geom_out, int *status, void *stream, unsigned flags = 0u)
+/* the orientation file i is delivered at: the caller's, or the file's tag */
+int tensor_orientation(const TensorOptions &opts, int i, const TensorProbe &p, TensorTag tag, const uint8_t *file, size_t len)
 {
-    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status) || !orient_files_args_ok(n, to) || (flags & ~(FFHIP_JPEG_ACCEPT_PROGRESSIVE | FFHIP_JPEG_PIXELS_LIBJPEG))) return FFHIP_EINVAL;
-    for (int i = 0; denom && i < n; i++) {
-        if (denom[i] != 0 ? !jpeg_denom_ok(denom[i]) : !rs.out_size) return FFHIP_EINVAL;
-        if ((flags & FFHIP_JPEG_PIXELS_LIBJPEG) && denom[i] != 1) return FFHIP_EINVAL; /* libjpeg's pixels: full size only, "choose" included */
+    if (!opts.oriented) return 1;
+    int o = opts.orient ? opts.orient[i] : 0;
+    if (!p.code && o == 0) tag(file, len, &o);
+    return o;
+}
+
+/* The two codecs: they differ in their probe and in the call underneath */
+int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
+                      const TensorOptions &opts, ffhip_jpeg_geom *geom_out, int *status, void *stream)
+{
+    const unsigned flags = opts.flags;
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts) || (flags & ~(FFHIP_JPEG_ACCEPT_PROGRESSIVE | FFHIP_JPEG_PIXELS_LIBJPEG))) return FFHIP_EINVAL;
+    for (int i = 0; opts.denom && i < n; i++) {
+        if (opts.denom[i] != 0 ? !jpeg_denom_ok(opts.denom[i]) : !opts.out_size) return FFHIP_EINVAL;
+        if ((flags & FFHIP_JPEG_PIXELS_LIBJPEG) && opts.denom[i] != 1) return FFHIP_EINVAL; /* libjpeg's pixels: full size only, "choose" included */
     }
     if (n == 0) return FFHIP_OK;
-    std::vector<TensorPicture> pic((size_t)n);
-    std::vector<int> den(denom ? (size_t)n : 0, 1);
-    std::vector<ffhip_rect> mapped(denom && roi ? (size_t)n : 0);
-    TensorStored stored(n, to.on, roi, rs.out_size); /* rectangles and sizes in the stored axes, where the call turns pictures */
+    std::vector<TensorFile> plan((size_t)n);
     ffhip_parallel_for(n, n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads), [&](int i) {
         const JpegProbed probed = jpeg_probe_file(files[i], lens[i], flags);
         const ffhip_jpeg_geom &g = probed.geom;
-        const int w = probed.width, h = probed.height;
         status[i] = probed.status;
         if (geom_out) geom_out[i] = g;
-        pic[(size_t)i] = TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, w, h, 4LL * g.mcu_cols * 8 * g.h};
-        if (to.on) {
-            int o = to.orient ? to.orient[i] : 0;
-            if (!status[i] && o == 0) ffhip_jpeg_exif_orientation(files[i], lens[i], &o);
-            stored.set(i, status[i] ? 0 : o, w, h, to.orient_out);
-        }
-        if (!denom) return;
-        if (denom_out) denom_out[i] = 0;
-        if (roi) mapped[(size_t)i] = ffhip_rect{0, 0, 0, 0}; /* an empty rectangle: the run refuses the file */
-        if (status[i]) return;
-        const ffhip_rect r = roi ? stored.roi()[i] : ffhip_rect{0, 0, w, h};
-        const bool r_ok = r.x0 >= 0 && r.y0 >= 0 && r.width >= 1 && r.height >= 1 && (long long)r.x0 + r.width <= w && (long long)r.y0 + r.height <= h;
-        int d = denom[i];
-        if (d == 0) {
-            const ffhip_size &o = stored.out_size()[i];
-            d = r_ok && o.width >= 1 && o.height >= 1 ? ffhip_jpeg_scale_choose(r.width, r.height, o.width, o.height) : 1;
-        }
-        den[(size_t)i] = d;
-        if (denom_out) denom_out[i] = d;
-        const int N = 8 / d;
-        const int cw = N * g.h * g.mcu_cols, chh = N * g.v * g.mcu_rows;
-        pic[(size_t)i] = TensorPicture{cw, chh, jpeg_scaled_len(w, d), jpeg_scaled_len(h, d), (4LL * cw + 15) & ~15LL};
-        if (roi && r_ok) mapped[(size_t)i] = jpeg_scaled_rect_of(w, h, d, r);
+        const TensorProbe p{probed.status, TensorPicture{g.mcu_cols * 8 * g.h, g.mcu_rows * 8 * g.v, probed.width, probed.height, 4LL * g.mcu_cols * 8 * g.h}};
+        plan[(size_t)i] = tensor_file_plan(p, tensor_orientation(opts, i, p, ffhip_jpeg_exif_orientation, files[i], lens[i]), i, opts, fmt, outs);
     });
     int prog_total[5] = {0, 0, 0, 0, 0}; /* the parts' ffhip_debug_progressive_last, summed (the front end: the last part's) */
-    const int rc = tensor_files_run(n, fmt, outs, denom && roi ? mapped.data() : stored.roi(), TensorResize{stored.out_size(), rs.filter}, pic, stored.orient(), status, stream,
-                            [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
-        const int prc = jpeg_decode_files_mixed(files + first, lens + first, cnt, n_threads, d_bgra, pitch, denom ? den.data() + first : nullptr, flags,
+    const int rc = tensor_files_run(plan, opts, fmt, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+        std::vector<int> den(opts.denom ? (size_t)cnt : 0); /* the part's denominators, as the call underneath reads them */
+        for (size_t k = 0; k < den.size(); k++) den[k] = plan[(size_t)first + k].denom;
+        const int prc = jpeg_decode_files_mixed(files + first, lens + first, cnt, n_threads, d_bgra, pitch, opts.denom ? den.data() : nullptr, flags,
                                                 geom_out ? geom_out + first : nullptr, status + first, stream);
         if (flags & FFHIP_JPEG_ACCEPT_PROGRESSIVE) { /* only then has the part written the thread's record */
             int last[5];
@@ -397,24 +430,19 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
 }
 
 int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
-                      const ffhip_rect *roi, const TensorResize &rs, const TensorOrient &to, ffhip_webp_info *info_out, int *status, void *stream)
+                      const TensorOptions &opts, ffhip_webp_info *info_out, int *status, void *stream)
 {
-    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status) || !orient_files_args_ok(n, to)) return FFHIP_EINVAL;
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    std::vector<TensorPicture> pic((size_t)n);
-    TensorStored stored(n, to.on, roi, rs.out_size);
+    std::vector<TensorFile> plan((size_t)n);
     for (int i = 0; i < n; i++) {
         int w = 0, h = 0, c = 0, r = 0;
         status[i] = files[i] && lens[i] ? ffhip_webp_probe(files[i], lens[i], &w, &h, &c, &r) : FFHIP_EINVAL;
         /* the loader's size is the container's word (ffhip_webp_info): what of it the decoded picture holds */
-        pic[(size_t)i] = TensorPicture{16 * c, 16 * r, w < 16 * c ? w : 16 * c, h < 16 * r ? h : 16 * r, 64LL * c};
-        if (to.on) {
-            int o = to.orient ? to.orient[i] : 0;
-            if (!status[i] && o == 0) ffhip_webp_exif_orientation(files[i], lens[i], &o);
-            stored.set(i, status[i] ? 0 : o, pic[(size_t)i].width, pic[(size_t)i].height, to.orient_out);
-        }
+        const TensorProbe p{status[i], TensorPicture{16 * c, 16 * r, w < 16 * c ? w : 16 * c, h < 16 * r ? h : 16 * r, 64LL * c}};
+        plan[(size_t)i] = tensor_file_plan(p, tensor_orientation(opts, i, p, ffhip_webp_exif_orientation, files[i], lens[i]), i, opts, fmt, outs);
     }
-    return tensor_files_run(n, fmt, outs, stored.roi(), TensorResize{stored.out_size(), rs.filter}, pic, stored.orient(), status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+    return tensor_files_run(plan, opts, fmt, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
         return ffhip_webp_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
                                               status + first, stream);
     });
@@ -425,38 +453,37 @@ int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
 extern "C" int ffhip_jpeg_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                               const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{nullptr, 0}, nullptr, nullptr, TensorOrient{false, nullptr, nullptr}, geom_out, status, stream);
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi), geom_out, status, stream);
 }
 
 extern "C" int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                               const ffhip_tensor_out *outs, const ffhip_rect *roi, ffhip_webp_info *info_out, int *status, void *stream)
 {
-    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{nullptr, 0}, TensorOrient{false, nullptr, nullptr}, info_out, status, stream);
+    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi), info_out, status, stream);
 }
 
 extern "C" int ffhip_jpeg_decode_files_tensor_resized(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                                       const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                                       ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    if (!resize_files_args_ok(n, out_size, filter)) return FFHIP_EINVAL;
-    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, nullptr, nullptr, TensorOrient{false, nullptr, nullptr}, geom_out, status, stream);
+    if (n > 0 && !out_size) return FFHIP_EINVAL;
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter), geom_out, status, stream);
 }
 
 extern "C" int ffhip_webp_decode_files_tensor_resized(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                                       const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                                       ffhip_webp_info *info_out, int *status, void *stream)
 {
-    if (!resize_files_args_ok(n, out_size, filter)) return FFHIP_EINVAL;
-    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, TensorOrient{false, nullptr, nullptr}, info_out, status, stream);
+    if (n > 0 && !out_size) return FFHIP_EINVAL;
+    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter), info_out, status, stream);
 }
 
 extern "C" int ffhip_jpeg_decode_files_tensor_scaled(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                                      const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                                      const int *denom, int *denom_out, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    if (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS) return FFHIP_EINVAL;
     if (n > 0 && !denom) return FFHIP_EINVAL;
-    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, denom, denom_out, TensorOrient{false, nullptr, nullptr}, geom_out, status, stream);
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).scale(denom, denom_out), geom_out, status, stream);
 }
 
 extern "C" int ffhip_jpeg_decode_files_tensor_oriented(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
@@ -464,8 +491,7 @@ extern "C" int ffhip_jpeg_decode_files_tensor_oriented(const uint8_t *const *fil
                                                        const int *denom, int *denom_out, const int *orient, int *orient_out,
                                                        ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    if (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS) return FFHIP_EINVAL;
-    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, denom, denom_out, TensorOrient{true, orient, orient_out},
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).scale(denom, denom_out).turn(orient, orient_out),
                              geom_out, status, stream);
 }
 
@@ -474,17 +500,15 @@ extern "C" int ffhip_jpeg_decode_files_tensor_ex(const uint8_t *const *files, co
                                                  const int *denom, int *denom_out, const int *orient, int *orient_out, unsigned flags,
                                                  ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
-    if (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS) return FFHIP_EINVAL;
-    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, denom, denom_out, TensorOrient{true, orient, orient_out},
-                             geom_out, status, stream, flags);
+    return jpeg_files_tensor(files, lens, n, n_threads, fmt, outs,
+                             TensorOptions(roi).resize(out_size, filter).scale(denom, denom_out).turn(orient, orient_out).with(flags), geom_out, status, stream);
 }
 
 extern "C" int ffhip_webp_decode_files_tensor_oriented(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                                        const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                                        const int *orient, int *orient_out, ffhip_webp_info *info_out, int *status, void *stream)
 {
-    if (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS) return FFHIP_EINVAL;
-    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, roi, TensorResize{out_size, filter}, TensorOrient{true, orient, orient_out}, info_out, status, stream);
+    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out), info_out, status, stream);
 }
 
 extern "C" int ffhip_debug_tensor_last_parts(void) { return g_tensor_last_parts; }

@@ -297,6 +297,48 @@ def hevc_intra_recon(tus, residual, width, height, chroma=True, bd_y=8, bd_c=8, 
     return dy.to_host((height, width), np.int16), None, None
 
 
+def file_args(files):
+    """files (a list of bytes) as the batch calls take them: (the arrays that keep the bytes in place, const uint8_t *const *files,
+    const size_t *lens)"""
+    n = max(len(files), 1)
+    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    return bufs, (C.c_void_p * n)(*[b.ctypes.data for b in bufs]), (C.c_size_t * n)(*[b.size for b in bufs])
+
+
+def _files_to_pictures(files, probe, call, what, strict, own_failure=lambda rc: rc not in (0, capi.FFHIP_EINVAL)):
+    """Pictures of any sizes into ONE device allocation, each at a 16-byte-aligned offset, and back to the host.
+      probe(i, f) -> (pitch, rows, crop_w, crop_h) of file i's picture; capi.FfhipError for a file without one
+      call(L, ptrs, lens, n, outs, pitches, status) -> the batch call's return
+      strict: any failure raises; otherwise only one that own_failure(rc) says is the call's and no file's
+    Returns ([host BGRA [crop_h][crop_w][4], None for a failing file], device buffer, per-file status codes)."""
+    L = capi.require_device()
+    n = len(files)
+    places, offs, total = [], [], 0
+    for i, f in enumerate(files):
+        try:
+            place = probe(i, f)
+        except capi.FfhipError:
+            place = (0, 0, 0, 0)
+        places.append(place)
+        offs.append(total)
+        total += (place[0] * place[1] + 15) & ~15
+    dout = DeviceBuffer(nbytes=max(total, 16))
+    bufs, ptrs, lens = file_args(files)
+    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
+    status = (C.c_int * n)()
+    rc = call(L, ptrs, lens, n, outs, (C.c_int64 * n)(*[p[0] for p in places]), status)
+    if strict or own_failure(rc):
+        capi.check(rc, what)
+    flat = dout.to_host((max(total, 16),), np.uint8)
+    images = []
+    for (pitch, rows, w, h), off, code in zip(places, offs, status):
+        if code or not pitch:
+            images.append(None)
+            continue
+        images.append(flat[off:off + pitch * rows].reshape(rows, pitch // 4, 4)[:h, :w].copy())
+    return images, dout, list(status)
+
+
 def jpeg_probe(data):
     """Geometry of a baseline JPEG file (bytes) -> (JpegGeom, width, height)."""
     L = capi.lib()
@@ -338,9 +380,7 @@ def jpeg_progressive_batch_gpu(files, k_max=63, n_threads=4, strict=True):
     L = capi.require_device()
     g, _, _, _ = jpeg_probe_any(files[0])
     n = len(files)
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    bufs, ptrs, lens = file_args(files)
     dy = DeviceBuffer(nbytes=n * g.y_blocks * 128)
     du = DeviceBuffer(nbytes=max(n * g.c_blocks * 128, 16)) if g.ncomp == 3 else None
     dv = DeviceBuffer(nbytes=max(n * g.c_blocks * 128, 16)) if g.ncomp == 3 else None
@@ -371,9 +411,7 @@ def jpeg_entropy_batch(files, n_threads=4):
     L = capi.lib()
     g, _, _ = jpeg_probe(files[0])
     n = len(files)
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    bufs, ptrs, lens = file_args(files)
     cy = np.empty(n * g.y_blocks * 64, np.int16)
     cu = np.empty(n * g.c_blocks * 64, np.int16) if g.ncomp == 3 else None
     cv = np.empty(n * g.c_blocks * 64, np.int16) if g.ncomp == 3 else None
@@ -450,9 +488,7 @@ def jpeg_decode_files(files, n_threads=8, chunk=0, out=None):
     L = capi.require_device()
     g, _, _ = jpeg_probe(files[0])
     n = len(files)
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    bufs, ptrs, lens = file_args(files)
     if out is None:
         out = np.empty((n, g.height, g.width, 4), np.uint8)
     assert out.shape == (n, g.height, g.width, 4) and out.dtype == np.uint8 and out.flags.c_contiguous
@@ -469,9 +505,7 @@ def jpeg_entropy_batch_gpu(files, n_threads=4):
     L = capi.require_device()
     g, _, _ = jpeg_probe(files[0])
     n = len(files)
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    bufs, ptrs, lens = file_args(files)
     dy = DeviceBuffer(nbytes=n * g.y_blocks * 128)
     du = DeviceBuffer(nbytes=max(n * g.c_blocks * 128, 16)) if g.ncomp == 3 else None
     dv = DeviceBuffer(nbytes=max(n * g.c_blocks * 128, 16)) if g.ncomp == 3 else None
@@ -491,9 +525,7 @@ def jpeg_decode_files_device(files, n_threads=8):
     L = capi.require_device()
     g, _, _ = jpeg_probe(files[0])
     n = len(files)
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    bufs, ptrs, lens = file_args(files)
     dout = DeviceBuffer(nbytes=n * g.width * g.height * 4)
     status = (C.c_int * n)()
     g2 = capi.JpegGeom()
@@ -591,42 +623,16 @@ def jpeg_decode_files_mixed_device_scaled(files, denom, n_threads=8, stream=None
     """ffhip_jpeg_decode_files_mixed_device_scaled: as jpeg_decode_files_mixed_device with file i at 1 / denom[i] of its size.  Returns (geoms,
     [host BGRA [h][w][4] at the SCALED CODED size], device buffer); with strict=False a failing file's entry is None and the per-file status
     codes follow."""
-    L = capi.require_device()
-    n = len(files)
-    offs, pitches, rows_of, total = [], [], [], 0
-    for f, d in zip(files, denom):
-        try:
-            g, _, _ = jpeg_probe(f)
-            pitch, rows = (g.width // d * 4 + 15) & ~15, g.height // d
-        except capi.FfhipError:
-            pitch = rows = 0
-        offs.append(total)
-        pitches.append(pitch)
-        rows_of.append(rows)
-        total += (pitch * rows + 15) & ~15
-    dout = DeviceBuffer(nbytes=max(total, 16))
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
-    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
-    pitch_arr = (C.c_int64 * n)(*pitches)
-    den = (C.c_int * n)(*[int(d) for d in denom])
-    geoms = (capi.JpegGeom * n)()
-    status = (C.c_int * n)()
-    rc = L.ffhip_jpeg_decode_files_mixed_device_scaled(ptrs, lens, n, n_threads, outs, pitch_arr, den, geoms, status, stream)
-    if strict or rc not in (0, capi.FFHIP_EINVAL):
-        capi.check(rc, "ffhip_jpeg_decode_files_mixed_device_scaled")
-    flat = dout.to_host((max(total, 16),), np.uint8)
-    images = []
-    for i in range(n):
-        if status[i] or not pitches[i]:
-            images.append(None)
-            continue
-        pic = flat[offs[i]:offs[i] + pitches[i] * rows_of[i]].reshape(rows_of[i], pitches[i] // 4, 4)
-        images.append(pic[:, :geoms[i].width // denom[i]].copy())
-    if strict:
-        return list(geoms), images, dout
-    return list(geoms), images, dout, list(status)
+    def probe(i, f):
+        g, _, _ = jpeg_probe(f)
+        return (g.width // denom[i] * 4 + 15) & ~15, g.height // denom[i], g.width // denom[i], g.height // denom[i]
+
+    geoms = (capi.JpegGeom * len(files))()
+    den = (C.c_int * len(files))(*[int(d) for d in denom])
+    images, dout, status = _files_to_pictures(
+        files, probe, lambda L, ptrs, lens, n, outs, pitches, status: L.ffhip_jpeg_decode_files_mixed_device_scaled(
+            ptrs, lens, n, n_threads, outs, pitches, den, geoms, status, stream), "ffhip_jpeg_decode_files_mixed_device_scaled", strict)
+    return (list(geoms), images, dout) if strict else (list(geoms), images, dout, status)
 
 
 def tensor_last_parts():
@@ -698,49 +704,19 @@ def jpeg_decode_files_mixed_device(files, n_threads=8, stream=None, strict=True,
     if pixels not in ("reference", "libjpeg"):
         raise ValueError(f"pixels {pixels!r}: 'reference' or 'libjpeg'")
     flags = (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0) | (capi.FFHIP_JPEG_PIXELS_LIBJPEG if pixels == "libjpeg" else 0)
-    L = capi.require_device()
-    n = len(files)
-    offs, pitches, total = [], [], 0
-    sizes = []
-    for f in files:
-        try:
-            g, w, h = jpeg_probe_any(f)[:3] if progressive else jpeg_probe(f)
-            pitch, rows = g.width * 4, g.height
-        except capi.FfhipError:
-            w = h = pitch = rows = 0
-        offs.append(total)
-        pitches.append(pitch)
-        sizes.append((w, h, rows))
-        total += (pitch * rows + 15) & ~15
-    dout = DeviceBuffer(nbytes=max(total, 16))
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
-    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
-    pitch_arr = (C.c_int64 * n)(*pitches)
-    geoms = (capi.JpegGeom * n)()
-    status = (C.c_int * n)()
-    if flags:
-        rc = L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n, n_threads, outs, pitch_arr, None, flags, geoms, status, stream)
-    else:
-        rc = L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n, n_threads, outs, pitch_arr, geoms, status, stream)
-    if strict:
-        capi.check(rc, "ffhip_jpeg_decode_files_mixed_device")
-    elif rc not in (0, capi.FFHIP_EINVAL):
-        capi.check(rc, "ffhip_jpeg_decode_files_mixed_device")
-    flat = dout.to_host((max(total, 16),), np.uint8)
-    images = []
-    for i in range(n):
-        w, h, rows = sizes[i]
-        if status[i] or not pitches[i]:
-            images.append(None)
-            continue
-        pic = flat[offs[i]:offs[i] + pitches[i] * rows].reshape(rows, pitches[i] // 4, 4)
-        images.append(pic[:h, :w].copy() if crop else pic.copy())
-    geoms = list(geoms)
-    if strict:
-        return geoms, images, dout
-    return geoms, images, dout, list(status)
+    def probe(i, f):
+        g, w, h = jpeg_probe_any(f)[:3] if progressive else jpeg_probe(f)
+        return (g.width * 4, g.height, w, h) if crop else (g.width * 4, g.height, g.width, g.height)
+
+    geoms = (capi.JpegGeom * len(files))()
+
+    def call(L, ptrs, lens, n, outs, pitches, status):
+        if flags:
+            return L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n, n_threads, outs, pitches, None, flags, geoms, status, stream)
+        return L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n, n_threads, outs, pitches, geoms, status, stream)
+
+    images, dout, status = _files_to_pictures(files, probe, call, "ffhip_jpeg_decode_files_mixed_device", strict)
+    return (list(geoms), images, dout) if strict else (list(geoms), images, dout, status)
 
 
 def vp8_dequant_factors(y_ac_qi, deltas=(0, 0, 0, 0, 0), segmentation_enabled=0, update_mb_segmentation_map=1, updates=(0, 0, 0, 0)):
@@ -795,17 +771,9 @@ def webp_parse(data):
     return _webp_result(p, arrs)
 
 
-def _webp_batch_args(files):
-    n = len(files)
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
-    return bufs, ptrs, lens
-
-
 def _webp_parse_many(files, call):
     n = len(files)
-    bufs, ptrs, lens = _webp_batch_args(files)
+    bufs, ptrs, lens = file_args(files)
     outs = (capi.WebpParsed * n)()
     keep = []
     for i, f in enumerate(files):
@@ -840,40 +808,16 @@ def webp_decode_files_device(files, n_threads=8, stream=None, strict=True, crop=
     device allocation, at a 16-byte-aligned offset with the pitch 64 x its macroblock columns.  Returns (infos, [host BGRA [h][w][4]
     cropped to the probe's width x height (crop=False: the decoded 16*mbrows x 16*mbcols)], device buffer); with strict=False a
     failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows."""
-    L = capi.require_device()
-    n = len(files)
-    offs, pitches, sizes, total = [], [], [], 0
-    for f in files:
-        try:
-            w, h, c, r = webp_probe(f)
-            pitch, rows = 64 * c, 16 * r
-        except capi.FfhipError:
-            w = h = pitch = rows = 0
-        offs.append(total)
-        pitches.append(pitch)
-        sizes.append((w, h, rows))
-        total += (pitch * rows + 15) & ~15
-    dout = DeviceBuffer(nbytes=max(total, 16))
-    bufs, ptrs, lens = _webp_batch_args(files)
-    outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
-    pitch_arr = (C.c_int64 * n)(*pitches)
-    infos = (capi.WebpInfo * n)()
-    status = (C.c_int * n)()
-    rc = L.ffhip_webp_decode_files_device(ptrs, lens, n, n_threads, outs, pitch_arr, infos, status, stream)
-    if strict or (rc not in (0, capi.FFHIP_EINVAL) and rc > -1000):
-        capi.check(rc, "ffhip_webp_decode_files_device")
-    flat = dout.to_host((max(total, 16),), np.uint8)
-    images = []
-    for i in range(n):
-        w, h, rows = sizes[i]
-        if status[i] or not pitches[i]:
-            images.append(None)
-            continue
-        pic = flat[offs[i]:offs[i] + pitches[i] * rows].reshape(rows, pitches[i] // 4, 4)
-        images.append(pic[:h, :w].copy() if crop else pic.copy())
-    if strict:
-        return list(infos), images, dout
-    return list(infos), images, dout, list(status)
+    def probe(i, f):
+        w, h, c, r = webp_probe(f)
+        return (64 * c, 16 * r, w, h) if crop else (64 * c, 16 * r, 16 * c, 16 * r)
+
+    infos = (capi.WebpInfo * len(files))()
+    images, dout, status = _files_to_pictures(
+        files, probe, lambda L, ptrs, lens, n, outs, pitches, status: L.ffhip_webp_decode_files_device(
+            ptrs, lens, n, n_threads, outs, pitches, infos, status, stream), "ffhip_webp_decode_files_device", strict,
+        own_failure=lambda rc: rc not in (0, capi.FFHIP_EINVAL) and rc > -1000)
+    return (list(infos), images, dout) if strict else (list(infos), images, dout, status)
 
 
 def webp_last_parts():

@@ -2,6 +2,7 @@
 CHW / HWC, uint8 / float16 / float32 tensors out, nothing but the compressed bytes crossing PCIe.  torch is imported when a
 function here is called, not with the package: ffpic_amd.ops stays torch-free."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -151,14 +152,40 @@ def _orientations(orientation, n):
     return [int(o) for o in imposed]
 
 
-def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size=None, antialias=True,
-                       reduce=1, return_reduce=False, tag=None, apply_exif_orientation=False, orientation=None, return_orientation=False,
-                       progressive=False, flags=0):
+def entry_point(codec, oriented=False, den=1, targets=False, progressive=False, flags=0):
+    """The C entry a files-to-tensors call goes through: codec 'jpeg' or 'webp' and what was asked for -- pictures turned upright, the
+    denominator (0: chosen per file), target sizes, progressive files accepted, FFHIP_JPEG_* flags -> the symbol's name.  Needs neither
+    torch nor the library."""
+    if codec not in ("jpeg", "webp") or (codec == "webp" and (den != 1 or progressive or flags)):
+        raise ValueError(f"{codec!r}: 'jpeg', or 'webp' without denominator, progressive files and flags")
+    if progressive or flags:                                      # one entry point for every combination
+        return "ffhip_jpeg_decode_files_tensor_ex"
+    if oriented:
+        return f"ffhip_{codec}_decode_files_tensor_oriented"
+    if den != 1:
+        return "ffhip_jpeg_decode_files_tensor_scaled"
+    return f"ffhip_{codec}_decode_files_tensor" + ("_resized" if targets else "")
+
+
+# what each entry takes between the rectangles and its last three arguments (geom_out / info_out, status, stream)
+_ENTRY_TAILS = {
+    "ffhip_jpeg_decode_files_tensor": (), "ffhip_webp_decode_files_tensor": (),
+    "ffhip_jpeg_decode_files_tensor_resized": ("resize",), "ffhip_webp_decode_files_tensor_resized": ("resize",),
+    "ffhip_jpeg_decode_files_tensor_scaled": ("resize", "denom"),
+    "ffhip_jpeg_decode_files_tensor_oriented": ("resize", "denom", "orient"), "ffhip_webp_decode_files_tensor_oriented": ("resize", "orient"),
+    "ffhip_jpeg_decode_files_tensor_ex": ("resize", "denom", "orient", "flags"),
+}
+
+
+def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias, apply_exif_orientation,
+                       orientation, return_orientation, reduce=1, return_reduce=False, progressive=False, flags=0):
     fmt = tensor_format(dtype, layout, order, mean, std)
     targets = _sizes(size, len(files))                            # argument errors come before any device use
     den = _reduce(reduce, size)
     imposed = _orientations(orientation, len(files))
     oriented = bool(apply_exif_orientation) or imposed is not None
+    what = entry_point(codec.name, oriented, den, bool(targets), progressive, flags)
+    probe = codec.probe_progressive if progressive else codec.probe
     import torch
     tdtype = getattr(torch, _dtype_name(dtype))
     dev = torch.cuda.current_device()
@@ -177,7 +204,7 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
             turns[i] = 0
             continue
         if oriented:                                              # sizes and rectangles are the upright picture's
-            turns[i] = imposed[i] if imposed else tag(f)
+            turns[i] = imposed[i] if imposed else codec.tag(f)
         swap = turns[i] >= 5
         if targets or den == 1:
             sizes.append(targets[i] if targets else (rois[i][3], rois[i][2]) if rois else (w, h) if swap else (h, w))
@@ -199,44 +226,21 @@ def _decode_to_tensors(call, what, probe, files, dtype, layout, order, mean, std
         tensors = [batch[i] for i in range(n)]
     else:
         tensors = [None if s is None or min(s) < 1 else torch.empty(shape(*s), dtype=tdtype, device=device) for s in sizes]
+    ints = C.c_int * max(n, 1)
     outs = (capi.TensorOut * max(n, 1))(*[capi.TensorOut() if t is None else tensor_out(t, layout) for t in tensors])
     rects = (capi.Rect * max(n, 1))(*[capi.Rect(*r) for r in rois]) if rois else None
-    bufs = [np.frombuffer(f, dtype=np.uint8) for f in files]
-    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
-    status = (C.c_int * max(n, 1))()
-    stream = torch.cuda.current_stream().cuda_stream
-    used = (C.c_int * max(n, 1))(*([1] * max(n, 1)))
-    out_size = (capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets]) if targets else None
-    if progressive or flags:                                      # one entry point for every combination: orientation 1 where none is asked for
-        what = "ffhip_jpeg_decode_files_tensor_ex"
-        turn = (C.c_int * max(n, 1))(*[(max(t, 1) if imposed else 0) if oriented else 1 for t in turns])
-        used_turn = (C.c_int * max(n, 1))()
-        denoms = (C.c_int * max(n, 1))(*([den] * max(n, 1)))
-        rc = L.ffhip_jpeg_decode_files_tensor_ex(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias), denoms, used,
-                                                 turn, used_turn, flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0), None, status, stream)
-        if oriented:
-            turns = list(used_turn)[:n]
-    elif oriented:
-        what = what.split("_decode_")[0] + "_decode_files_tensor_oriented"
-        turn = (C.c_int * max(n, 1))(*[max(t, 1) if imposed else 0 for t in turns])
-        used_turn = (C.c_int * max(n, 1))()
-        if "jpeg" in what:
-            denoms = (C.c_int * max(n, 1))(*([den] * max(n, 1)))
-            rc = L.ffhip_jpeg_decode_files_tensor_oriented(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias),
-                                                           denoms, used, turn, used_turn, None, status, stream)
-        else:
-            rc = L.ffhip_webp_decode_files_tensor_oriented(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias),
-                                                           turn, used_turn, None, status, stream)
+    bufs, ptrs, lens = ops.file_args(files)
+    status, used, used_turn = ints(), ints(*([1] * max(n, 1))), ints()
+    tails = {                                                     # orientation 1 where none is asked for
+        "resize": ((capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets]) if targets else None, _filter(antialias)),
+        "denom": (ints(*([den] * max(n, 1))), used),
+        "orient": (ints(*[(max(t, 1) if imposed else 0) if oriented else 1 for t in turns]), used_turn),
+        "flags": (flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0),),
+    }
+    tail = sum((tails[part] for part in _ENTRY_TAILS[what]), ())
+    rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, *tail, None, status, torch.cuda.current_stream().cuda_stream)
+    if oriented:
         turns = list(used_turn)[:n]
-    elif den != 1:
-        what = "ffhip_jpeg_decode_files_tensor_scaled"
-        rc = L.ffhip_jpeg_decode_files_tensor_scaled(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias),
-                                                     (C.c_int * max(n, 1))(*([den] * max(n, 1))), used, None, status, stream)
-    elif targets:
-        rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, out_size, _filter(antialias), None, status, stream)
-    else:
-        rc = call(L)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, None, status, stream)
     status = list(status)[:n]
     if strict or stack or (rc != 0 and rc not in status):         # a file's code, or the call's own failure
         capi.check(rc, what)
@@ -262,6 +266,13 @@ def _jpeg_size_any(f):
 def _webp_size(f):
     w, h, c, r = ops.webp_probe(f)
     return min(w, 16 * c), min(h, 16 * r)
+
+
+# a codec as _decode_to_tensors sees it: its name in the entry points, file -> (width, height) of the display picture, the same for a
+# call that accepts progressive files (None: the codec has none), file -> its EXIF orientation
+_Codec = namedtuple("_Codec", "name probe probe_progressive tag")
+_JPEG = _Codec("jpeg", _jpeg_size, _jpeg_size_any, ops.jpeg_exif_orientation)
+_WEBP = _Codec("webp", _webp_size, None, ops.webp_exif_orientation)
 
 
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
@@ -303,10 +314,10 @@ def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
         raise ValueError(f"pixels {pixels!r}: 'reference' or 'libjpeg'")
     if pixels == "libjpeg" and reduce != 1:
         raise ValueError("pixels='libjpeg' needs reduce=1: libjpeg's reduced-size transforms are another rule")
-    return _decode_to_tensors(lambda L: L.ffhip_jpeg_decode_files_tensor, "ffhip_jpeg_decode_files_tensor" + ("_resized" if size is not None else ""),
-                              _jpeg_size_any if progressive else _jpeg_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict,
-                              size, antialias, reduce, return_reduce, ops.jpeg_exif_orientation, apply_exif_orientation, orientation,
-                              return_orientation, progressive=bool(progressive), flags=capi.FFHIP_JPEG_PIXELS_LIBJPEG if pixels == "libjpeg" else 0)
+    return _decode_to_tensors(_JPEG, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+                              strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
+                              return_orientation=return_orientation, reduce=reduce, return_reduce=return_reduce, progressive=bool(progressive),
+                              flags=capi.FFHIP_JPEG_PIXELS_LIBJPEG if pixels == "libjpeg" else 0)
 
 
 def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
@@ -315,7 +326,6 @@ def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
     ffhip_webp_decode_files_tensor_oriented, the tag read from the file's EXIF chunk): lossy WebP files; arguments and result as
     decode_jpeg_to_tensors.  A file's display size is the
     probe's width x height as far as the decoded picture holds it."""
-    return _decode_to_tensors(lambda L: L.ffhip_webp_decode_files_tensor, "ffhip_webp_decode_files_tensor" + ("_resized" if size is not None else ""),
-                              _webp_size, files, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias,
-                              tag=ops.webp_exif_orientation, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
+    return _decode_to_tensors(_WEBP, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+                              strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)

@@ -183,3 +183,40 @@ def test_python_format_rounds_once():
         tensors.tensor_format("uint8", mean=mean, std=std)
     with pytest.raises(ValueError):
         tensors.tensor_format("int32")
+
+
+def _entry_cases():
+    """every call the two public functions can make: WebP has neither a denominator nor progressive files nor flags"""
+    import itertools
+    for codec, oriented, den, targets, progressive, flags in itertools.product(("jpeg", "webp"), (False, True), (1, 2, 0), (False, True), (False, True),
+                                                                               (0, capi.FFHIP_JPEG_PIXELS_LIBJPEG)):
+        if codec == "jpeg" or (den == 1 and not progressive and not flags):
+            yield codec, oriented, den, targets, progressive, flags
+
+
+@pytest.mark.parametrize("codec,oriented,den,targets,progressive,flags", list(_entry_cases()))
+def test_entry_point_table(codec, oriented, den, targets, progressive, flags):
+    from ffpic_amd import tensors
+    if progressive or flags:
+        want = "ffhip_jpeg_decode_files_tensor_ex"
+    elif oriented:
+        want = {"jpeg": "ffhip_jpeg_decode_files_tensor_oriented", "webp": "ffhip_webp_decode_files_tensor_oriented"}[codec]
+    elif den != 1:
+        want = "ffhip_jpeg_decode_files_tensor_scaled"
+    elif targets:
+        want = {"jpeg": "ffhip_jpeg_decode_files_tensor_resized", "webp": "ffhip_webp_decode_files_tensor_resized"}[codec]
+    else:
+        want = {"jpeg": "ffhip_jpeg_decode_files_tensor", "webp": "ffhip_webp_decode_files_tensor"}[codec]
+    assert tensors.entry_point(codec, oriented, den, targets, progressive, flags) == want
+    assert want in capi.EXPORTS
+
+
+def test_entry_point_reaches_all_eight_entries_and_refuses_what_webp_lacks():
+    from ffpic_amd import tensors
+    reached = {tensors.entry_point(*case) for case in _entry_cases()}
+    assert reached == set(tensors._ENTRY_TAILS) and len(reached) == 8
+    for kw in (dict(den=2), dict(den=0), dict(progressive=True), dict(flags=capi.FFHIP_JPEG_PIXELS_LIBJPEG)):
+        with pytest.raises(ValueError):
+            tensors.entry_point("webp", **kw)
+    with pytest.raises(ValueError):
+        tensors.entry_point("heic")

@@ -76,6 +76,12 @@ class Outputs:
     def read(self):
         return self.dev.to_host((self.total * self.es,), np.uint8)
 
+    def view(self, k, flat):
+        """output k inside `flat`, the allocation's bytes (read(), or exp): [3][h][w] or [h][w][3]"""
+        at, rs, ps, h, w = self.places[k]
+        typed, es = flat.view(NP_DTYPE[self.f.dtype]), self.es
+        return np.lib.stride_tricks.as_strided(typed[at:], (3, h, w) if self.f.planar else (h, w, 3), (ps * es, rs * es, es) if self.f.planar else (rs * es, 3 * es, es))
+
 
 def run_items(f, src, rects, offs, extras, stream=None, one_by_one=False):
     """rectangles (x0, y0, w, h) of the host picture `src` [H][W][4] through ffhip_bgra_to_tensor_items -> (device bytes, expected bytes)"""
@@ -299,6 +305,44 @@ def test_many_parts_give_the_bytes_of_one_part(jpeg_batch, webp_batch, codec):
         check_files(entry, files, images, sizes, 2, f)
     capi.setenv("FFHIP_TENSOR_PART_BYTES", None)
     check_files(entry, files, images, sizes, 2, f)
+
+
+@pytest.mark.parametrize("codec", ["jpeg", "webp"])
+def test_a_damaged_file_with_a_bad_rectangle_keeps_the_decoders_code(webp_batch, codec):
+    """Whose code a file gets: the decoder's comes before this call's own.  File 1 is truncated inside its scan AND has a rectangle that
+    leaves its picture; file 2 is intact with such a rectangle; files 0 and 3 are delivered as in a call of their own.  One part, and a
+    part per file"""
+    if codec == "jpeg":
+        rng = np.random.default_rng(11)
+        files = [_writer_file(rng, w, h, layout)[0] for w, h, layout in ((37, 23, "420"), (100, 75, "444"), (100, 75, "420"), (37, 23, "444"))]
+        files[1] = files[1][:len(files[1]) * 2 // 3]
+        sizes = [(h, w) for _, w, h in (ops.jpeg_probe(d) for d in files)]
+    else:
+        all_files, _, all_sizes, bad = webp_batch
+        pick = [k for k in range(len(all_files)) if k != bad][:3]
+        pick.insert(1, bad)
+        files, sizes = [all_files[k] for k in pick], [all_sizes[k] for k in pick]
+    entry, f = f"ffhip_{codec}_decode_files_tensor", make_format(F16, 1, 0)
+    good = inner_rois(sizes)
+    rois = list(good)
+    rois[1] = (1, 0, sizes[1][1], sizes[1][0])                                  # one column too far
+    rois[2] = (0, sizes[2][0] - 1, 4, 2)                                        # one row too far
+    shapes = [(r[3], r[2]) for r in rois]
+    ref_status, _, ref_rc = files_to_tensors(entry, files, [(r[3], r[2]) for r in good], f, good)
+    assert ref_status[1] != 0 and ref_rc == ref_status[1] and not any(ref_status[k] for k in (0, 2, 3))
+    alone = {}
+    for k in (0, 3):
+        status, outs, rc = files_to_tensors(entry, [files[k]], [shapes[k]], f, [rois[k]])
+        assert rc == 0 and status == [0]
+        alone[k] = outs.view(0, outs.read()).copy()
+    for budget, parts in ((None, 1), (1, 4)):
+        capi.setenv("FFHIP_TENSOR_PART_BYTES", budget)
+        status, outs, rc = files_to_tensors(entry, files, shapes, f, rois)
+        assert ops.tensor_last_parts() == parts
+        assert status == [0, ref_status[1], capi.FFHIP_EINVAL, 0] and rc == status[1]
+        for k in (0, 3):
+            outs.view(k, outs.exp)[...] = alone[k]
+        assert np.array_equal(outs.read(), outs.exp)                           # outputs 1 and 2 and every byte around still hold 0xA5
 
 
 # ---------------------------------------------------------------------------------------------------- 7. torch

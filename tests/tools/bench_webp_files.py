@@ -33,7 +33,7 @@ def timed_call(L, files, n_threads, reps):
         offs.append(total)
         total += 64 * c * 16 * r
     dout = ops.DeviceBuffer(nbytes=total)
-    bufs, ptrs, lens = ops._webp_batch_args(files)
+    bufs, ptrs, lens = ops.file_args(files)
     outs = (C.c_void_p * n)(*[dout.ptr + o for o in offs])
     pitch = (C.c_int64 * n)(*[64 * p[2] for p in probes])
     status = (C.c_int * n)()
