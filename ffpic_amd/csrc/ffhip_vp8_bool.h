@@ -7,7 +7,9 @@
  *   - the 11 extra bits of a cat6 token are summed in a uint8_t (DCTextra, webp.c:965-971), so they wrap modulo 256;
  *   - a block's token count is n - first at the end-of-block token and 16 when the loop runs out (webp.c:1039, 1063).
  * A decoder that wants a byte beyond its partition sets `err` and reads zeros from then on (every loop here is bounded); the
- * reference reads one byte of heap there and then exits (utils/bitstream.c:115-120). */
+ * reference reads one byte of heap there and then exits (utils/bitstream.c:115-120).  libwebp has the same rule (a load past the
+ * end sets its eof flag), yet decodes files this rule refuses: what runs those files off their first partition is the segment id
+ * that ffb_mb_header reads with probabilities 0 while segmentation is off, a zero bit of which costs seven shifts. */
 #ifndef FFHIP_VP8_BOOL_H
 #define FFHIP_VP8_BOOL_H
 

@@ -2,7 +2,8 @@
  * frame tag and key-frame header of WEBP_read_frame (:1872-1926), read_vp8_ctl_partition (:897-935) with read_dequantization
  * (:458-548) as ffhip_vp8_dequant_factors, and the two per-macroblock parsers of ffhip_vp8_bool.h looped as vp8_decode loops them
  * (:1833-1851).  What comes out is what ffhip_vp8_decode_items takes: mode records, levels, token counts, the residual map of the
- * skipped macroblocks, quantisers and filter parameters.  The contract is the reference's decoder bit for bit, not RFC 6386. */
+ * skipped macroblocks, quantisers and filter parameters.  The contract is the reference's decoder bit for bit, not RFC 6386: every
+ * departure from RFC 6386 and libwebp is a named flag of tests/vp8_spec.py, the refusal of some valid files among them. */
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>

@@ -524,6 +524,9 @@ int ffhip_webp_probe(const uint8_t *file, size_t len, int *width, int *height, i
  * across rows, `left` starts at zero in every row; a skipped macroblock clears contexts 1-8 always and context 0 only when it is
  * not B_PRED (webp.c:1213-1221).  A partition that is asked for a byte beyond its length is FFHIP_EINVAL ("truncated": the
  * reference reads one byte of heap there and then exits, utils/bitstream.c:115-120), and no read goes outside [file, file + len).
+ * That verdict also meets files libwebp decodes: with segmentation off the reference still reads a segment id per macroblock, with
+ * probabilities 0 (webp.c:393, 1291-1294), and in a first partition that ends right behind the last macroblock header -- flat and
+ * tiny pictures -- those reads use up bits the encoder never wrote.  It is the reference's rule, kept and named.
  * The last partition ends with the FILE in the reference (webp.c:452-454); here it ends with the `VP8 ` chunk where that is
  * shorter, so bytes of a chunk behind the frame are never taken for tokens. */
 typedef struct ffhip_webp_parsed {

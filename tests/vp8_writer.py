@@ -7,6 +7,8 @@ entry points:
                    libwebp for: 2 / 4 / 8 token partitions, the simple filter, segmentation with absolute and delta quantisers
                    (negative sums included), mb_no_skip_coeff with many skips, coefficient probabilities that make cat6 tokens with
                    large extra bits common, quantiser index sweeps, a VP8X chunk.
+  Both write what the REFERENCE reads (ffhip_webp.c): a segment id in every macroblock header also without segmentation, no RIFF padding
+  byte.  valid=True writes what RFC 6386 and RIFF prescribe instead, so that libwebp takes the file (tests/golden/make_golden_libwebp.py).
   keyframe_from()  the WHOLE frame written from known data: per macroblock the y mode, the sixteen 4x4 modes, the uv mode, the
                    segment id, mb_skip_coeff and the 25 x 16 levels.  The macroblock headers follow the frame header in the SAME
                    encoder (the first partition is one stream); the tokens of row y go to partition y & (nparts - 1).  A decoder
@@ -111,12 +113,13 @@ def kf_bmode_probs():
 
 
 def _frame_header(e, *, y_ac_qi=40, deltas=(0, 0, 0, 0, 0), log2_parts=0, filter_type=0, level=0, sharpness=0, segmentation=None, lf_adj=None,
-                  coeff_probs=None, prob_skip=None):
+                  coeff_probs=None, prob_skip=None, valid=False):
     """the frame header into `e`; returns what it leaves for the macroblocks: the 1056 coefficient probabilities in force, whether a
-    segment id is coded in every macroblock header and with which probabilities, prob_skip_false or None"""
+    segment id is coded in every macroblock header and with which probabilities, prob_skip_false or None.  valid: what RFC 6386 has
+    where the reference departs from it: no segment ids without segmentation, 255 for a segment probability that is not set"""
     e.put(0)  # color_space
     e.put(0)  # clamp
-    seg_probs, ids_coded = (0, 0, 0), True   # segmentation off: an id is read all the same, with probabilities 0 (ffhip_vp8_bool.h)
+    seg_probs, ids_coded = (0, 0, 0), not valid   # segmentation off: an id is read all the same, with probabilities 0 (ffhip_vp8_bool.h)
     if segmentation is None:
         e.put(0)
     else:
@@ -137,7 +140,7 @@ def _frame_header(e, *, y_ac_qi=40, deltas=(0, 0, 0, 0, 0), log2_parts=0, filter
                 e.put(0 if p is None else 1)
                 if p is not None:
                     e.bits(p, 8)
-            seg_probs = tuple(0 if p is None else p for p in (s.get("probs") or (None, None, None)))   # unset: 0, not 255 (the reference)
+            seg_probs = tuple((255 if valid else 0) if p is None else p for p in (s.get("probs") or (None, None, None)))   # unset: 0, not 255 (the reference)
     e.put(filter_type)
     e.bits(level, 6)
     e.bits(sharpness, 3)
@@ -170,7 +173,9 @@ def _frame_header(e, *, y_ac_qi=40, deltas=(0, 0, 0, 0, 0), log2_parts=0, filter
     return probs, ids_coded, seg_probs, prob_skip
 
 
-def _container(width, height, p0, parts, vp8x=None, trailing_chunk=None):
+def _container(width, height, p0, parts, vp8x=None, trailing_chunk=None, leading_chunk=None, riff_pad=False):
+    """riff_pad: an odd-sized VP8 chunk gets the padding byte RIFF prescribes (the reference walks chunks without it, and so do the
+    files written without this option: libwebp's demuxer refuses those)"""
     assert len(p0) < (1 << 19)
     tag = (len(p0) << 5) | (1 << 4)  # key frame, version 0, show_frame
     frame = struct.pack("<I", tag)[:3] + b"\x9d\x01\x2a" + struct.pack("<HH", width, height) + p0
@@ -179,14 +184,18 @@ def _container(width, height, p0, parts, vp8x=None, trailing_chunk=None):
     frame += b"".join(parts)
     body = b"WEBP"
     if vp8x is not None:
-        body += b"VP8X" + struct.pack("<I", 10) + bytes(4) + struct.pack("<I", vp8x[0])[:3] + struct.pack("<I", vp8x[1])[:3]
+        body += b"VP8X" + struct.pack("<I", 10) + bytes([vp8x[2] if len(vp8x) > 2 else 0, 0, 0, 0]) + struct.pack("<I", vp8x[0])[:3] + struct.pack("<I", vp8x[1])[:3]
+    if leading_chunk:
+        body += leading_chunk
     body += b"VP8 " + struct.pack("<I", len(frame)) + frame
+    if riff_pad and len(frame) & 1:
+        body += b"\x00"
     if trailing_chunk:
         body += trailing_chunk
     return b"RIFF" + struct.pack("<I", len(body)) + body
 
 
-def keyframe(width, height, seed, *, p0_tail=600, token_bytes=6000, vp8x=None, trailing_chunk=None, **header):
+def keyframe(width, height, seed, *, p0_tail=600, token_bytes=6000, vp8x=None, trailing_chunk=None, valid=False, **header):
     """One lossy WebP file (bytes): the frame header, random bytes behind it.  `header`:
     y_ac_qi, deltas (5), log2_parts, filter_type, level, sharpness
     segmentation: None, or dict(update_map=0/1, feature_mode=0/1, quant=(4 ints)|None, lf=(4 ints)|None, probs=(3 ints or None)|None)
@@ -195,15 +204,16 @@ def keyframe(width, height, seed, *, p0_tail=600, token_bytes=6000, vp8x=None, t
     coeff_probs:  None (no updates), or {flat index: probability} / a 1056-list of probabilities to set (None = keep)
     prob_skip:    None (mb_no_skip_coeff = 0) or prob_skip_false
     p0_tail / token_bytes: random bytes behind the header in the first partition / in EACH token partition
-    vp8x:         None or (canvas_width_field, canvas_height_field) as stored
-    trailing_chunk: bytes of a whole chunk appended behind the VP8 chunk"""
+    vp8x:         None or (canvas_width_field, canvas_height_field) as stored, a third entry being the flags byte
+    trailing_chunk: bytes of a whole chunk appended behind the VP8 chunk
+    valid:        the file as RFC 6386 and RIFF have it where the reference departs from them (_frame_header, _container)"""
     rng = np.random.default_rng(seed)
     e = BoolEncoder()
-    _frame_header(e, **header)
+    _frame_header(e, valid=valid, **header)
     p0 = e.flush() + rng.integers(0, 256, p0_tail, dtype=np.uint8).tobytes()
     nparts = 1 << header.get("log2_parts", 0)
     parts = [rng.integers(0, 256, token_bytes, dtype=np.uint8).tobytes() for _ in range(nparts)]
-    return _container(width, height, p0, parts, vp8x, trailing_chunk)
+    return _container(width, height, p0, parts, vp8x, trailing_chunk, riff_pad=valid)
 
 
 # ---------------------------------------------------------------------------------------------------- the whole frame from known data
@@ -323,7 +333,7 @@ def new_facts():
 
 
 def keyframe_from(width, height, mbs, *, zeros16=None, tight=False, short=None, empty_parts=(), pad=8, facts=None, vp8x=None, trailing_chunk=None,
-                  **header):
+                  leading_chunk=None, valid=False, **header):
     """One lossy WebP file (bytes) written from known macroblock data.  mbs: dict of arrays over the macroblocks in raster order,
       ymode [n] (0 DC, 1 TM, 2 V, 3 H, 4 B_PRED), bmodes [n][16] (read for B_PRED only), uvmode [n], seg [n], skip [n],
       levels [n][25][16] at their raster positions inside a block, blocks in the library's order (16 Y, 4 U, 4 V, Y2).
@@ -331,10 +341,11 @@ def keyframe_from(width, height, mbs, *, zeros16=None, tight=False, short=None, 
     position 15.  With all levels zero that gives count 16 and nothing non-zero: legal, though no encoder of pictures writes it.
     tight: every partition, the first included, ends on the last byte decode() loads;  short: "p0" or a token partition's number:
     that partition loses its last byte;  empty_parts: token partitions written with length 0;  pad: zero bytes behind every flushed
-    partition otherwise.  `header` as for keyframe().  facts (a new_facts() dict) receives what the stream visits, the token counts
+    partition otherwise.  `header` and `valid` as for keyframe(); leading_chunk: a whole chunk in front of the VP8 chunk.  facts (a new_facts() dict) receives what the stream visits, the token counts
     [n][25] (`counts`), the levels and the residual map a decoder must return (`levels`, `resmap`) and the bytes of every partition
     (`part_bytes`, the first partition first)."""
     facts = new_facts() if facts is None else facts
+    assert not (tight and valid), "decode() below models the reference's reading, which is how `tight` finds the last byte"
     cols, rows = (((width + 3) & ~3) + 15) >> 4, (((height + 3) & ~3) + 15) >> 4
     n_mb = cols * rows
     nparts = 1 << header.get("log2_parts", 0)
@@ -343,7 +354,7 @@ def keyframe_from(width, height, mbs, *, zeros16=None, tight=False, short=None, 
     z16 = np.zeros((n_mb, 25), bool) if zeros16 is None else np.asarray(zeros16, bool)
     bprobs = kf_bmode_probs()
     e = BoolEncoder()
-    probs, ids_coded, seg_probs, prob_skip = _frame_header(e, **header)
+    probs, ids_coded, seg_probs, prob_skip = _frame_header(e, valid=valid, **header)
     assert ids_coded or not seg.any(), "the map is kept: no ids are coded, every macroblock is segment 0"
     assert prob_skip is not None or not skip.any(), "mb_no_skip_coeff = 0: no macroblock can be skipped"
     te = [BoolEncoder() for _ in range(nparts)]
@@ -409,7 +420,7 @@ def keyframe_from(width, height, mbs, *, zeros16=None, tight=False, short=None, 
     facts["levels"] = np.vectorize(decoded_level, otypes=[np.int16])(levels)
     facts["resmap"] = resmap
     facts["part_bytes"] = [len(p0)] + [len(p) for p in parts]
-    return _container(width, height, p0, parts, vp8x, trailing_chunk)
+    return _container(width, height, p0, parts, vp8x, trailing_chunk, leading_chunk, riff_pad=valid)
 
 
 # ---------------------------------------------------------------------------------------------------- the model decoder
