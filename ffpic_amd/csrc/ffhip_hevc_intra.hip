@@ -16,11 +16,12 @@
  * (FFHIP_HEVC_INTRA_MODE=levels): the host gives each TU a wavefront level (1 + the highest
  * level among the 4x4 blocks its available neighbours lie in) and launches k_hevc_intra once
  * per level, a wave per TU.
- * Two TU bodies with the same arithmetic, intra_tu (levels form) and intra_tu_g (grouped form):
- * the 4n+1 neighbours live in LDS in
- * scan order (left column bottom-up, corner, top row left-to-right): in that order the
+ * ONE TU body, intra_tu_g, under every kernel (grouped, serial, levels): the 4n+1 neighbours are
+ * taken in scan order (left column bottom-up, corner, top row left-to-right): in that order the
  * reference's substitution is "nearest available sample at or before me, else the first
- * available one", and its [1 2 1] smoothing is a 3-tap filter with untouched ends.
+ * available one", and its [1 2 1] smoothing is a 3-tap filter with untouched ends.  The kernels
+ * differ in the loop around the body, in where the substitution comes from (a table written
+ * beforehand; in the levels form the TU record) and in the plane resource they hand it.
  * This file: the kernels and the call (validation, the three paths, the tile entry points);
  * ffhip_hevc_plan.h has what the three files share.
  */
@@ -176,18 +177,6 @@ struct ResPrefetch {
     u32x4 v[2];
     bool wide; /* wave-uniform: v[] holds the block */
 };
-__device__ __forceinline__ void fetch_residual(const HevcIntraArgs &a, const ffhip_hevc_tu &t, const int lane, ResPrefetch &rp)
-{
-    rp.wide = false;
-    if (!(t.flags & 2)) return;
-    const int nn = 1 << (2 * t.log2_size);
-    const int16_t *src = a.residual + t.res_offset;
-    if (((uintptr_t)src & 15) != 0) return;
-    rp.wide = true;
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-        if (8 * lane + 512 * j < nn) rp.v[j] = *(const u32x4 *)(src + 8 * lane + 512 * j);
-}
 
 /* rdpcm accumulation of 8.6.5 on the wave's residual block in LDS.  Out of line on purpose: inlined four times (once
  * per TU size) its unrolled chunk arrays took the kernel to 314 VGPRs and a thousand register moves, and the scalar
@@ -228,205 +217,15 @@ __device__ __attribute__((noinline)) void rdpcm_accumulate(short *R, const int l
     }
 }
 
-/* One TU by one wave, the levels form's body: steps 5-10 of decode_intra_block.  s, s2: NB_MAX ints each;
- * refbase: 140 ints; R: 32*32 shorts -- all private to the wave (LDS).  Picture samples are read and written
- * with plain accesses: a level's TUs only read what earlier launches wrote. */
-template <int LG> /* LG = log2 of the TU size: every loop below has a compile-time trip count */
-__device__ __forceinline__ void intra_tu(const HevcIntraArgs &a, const ffhip_hevc_tu &t, const int lane, int *s, int *s2,
-                                         int *refbase, short *R, const ResPrefetch &rp)
-{
-    constexpr int n = 1 << LG, lg = LG;
-    const int cidx = t.cidx, mode = t.pred_mode, flags = t.flags;
-    const int bd = cidx == 0 ? a.bitdepth_y : a.bitdepth_c;
-    /* selects, not a.plane[cidx]: indexing the kernel-argument arrays with a run-time index is two scalar memory
-     * loads (and their latency) in front of every TU's gather */
-    int16_t *plane = cidx == 0 ? a.plane[0] : (cidx == 1 ? a.plane[1] : a.plane[2]);
-    const int stride = cidx == 0 ? a.stride[0] : (cidx == 1 ? a.stride[1] : a.stride[2]);
-    const int x0 = t.x, y0 = t.y;
-    constexpr int cnt = 4 * n + 1;
-    int *ref = refbase + 34;
-
-    /* availability in scan order: i < 2n -> left[2n-1-i]; i == 2n -> corner; i > 2n -> top[i-2n-1] */
-    const unsigned long long rl = __brevll(t.avail_left) >> (64 - 2 * n); /* bit i = left[2n-1-i] */
-    unsigned long long m0, m1;
-    unsigned m2;
-    {
-        const unsigned long long c = (flags & 1) ? 1ull : 0ull;
-        const unsigned long long tp = n == 32 ? t.avail_top : (t.avail_top & ((1ull << (2 * n)) - 1));
-        if (n == 32) { /* left 0..63, corner 64, top 65..128 */
-            m0 = rl; m1 = c | (tp << 1); m2 = (unsigned)(tp >> 63);
-        } else {
-            m0 = rl | (c << (2 * n)) | (tp << (2 * n + 1));
-            m1 = (2 * n + 1) ? (tp >> (63 - 2 * n)) : 0; /* bits that spill past 64 (n = 16: 4n+1 = 65) */
-            m2 = 0;
-        }
-    }
-    const int n_avail = __popcll(m0) + __popcll(m1) + (int)m2;
-
-    /* ---- 1. gather + 2. substitute, in one pass: in scan order the substitution of 8.4.4.2.2 is
-     * "the nearest available sample at or before me, else the first available one", so each
-     * lane works out WHICH sample it wants from the masks alone and fetches that one ---- */
-#pragma unroll
-    for (int pass = 0; pass < LANE_PASSES(cnt); pass++) {
-        const int i = lane + 64 * pass;
-        if (i >= cnt) break;
-        int j = i;
-        if (n_avail < cnt && n_avail > 0) {
-            j = -1;
-            if (n == 32 && i >= 128 && m2) j = 128;
-            if (n >= 16 && j < 0 && i >= 64) {
-                const unsigned long long mm = i >= 127 ? m1 : (m1 & ((2ull << (i - 64)) - 1));
-                if (mm) j = 127 - __clzll(mm);
-            }
-            if (j < 0) {
-                const unsigned long long mm = i >= 63 ? m0 : (m0 & ((2ull << i) - 1));
-                if (mm) j = 63 - __clzll(mm);
-            }
-            if (j < 0) j = m0 ? __ffsll((long long)m0) - 1 : (m1 ? 64 + __ffsll((long long)m1) - 1 : 128);
-        }
-        int px, py;
-        if (j < 2 * n) { px = x0 - 1; py = y0 + (2 * n - 1 - j); }
-        else if (j == 2 * n) { px = x0 - 1; py = y0 - 1; }
-        else { px = x0 + (j - 2 * n - 1); py = y0 - 1; }
-        int v = 1 << (bd - 1);
-        if (n_avail > 0) {
-            const int16_t *sp = plane + (long long)py * stride + px;
-            v = (int)*sp;
-        }
-        s[i] = v;
-    }
-    wave_sync();
-    /* handy accessors into the scan-order array */
-#define LEFT(y) s[2 * n - 1 - (y)]
-#define TOP(x) s[2 * n + 1 + (x)] /* TOP(-1) is the corner */
-
-    /* ---- 3. neighbour smoothing (8.4.4.2.3) ---- */
-    if ((flags & 4) && mode != 1 && n != 4) {
-        const int d26 = iabs(mode - 26), d10 = iabs(mode - 10);
-        const int thr = n == 8 ? 7 : (n == 16 ? 1 : 0);
-        if ((d26 < d10 ? d26 : d10) > thr) {
-            const bool bi = (flags & 8) && cidx == 0 && n == 32 &&
-                            iabs(TOP(-1) + TOP(2 * n - 1) - 2 * TOP(n - 1)) < (1 << (a.bitdepth_y - 5)) &&
-                            iabs(TOP(-1) + LEFT(2 * n - 1) - 2 * LEFT(n - 1)) < (1 << (a.bitdepth_y - 5));
-            const int corner = TOP(-1), l63 = bi ? LEFT(63) : 0, t63 = bi ? TOP(63) : 0;
-#pragma unroll
-            for (int pass = 0; pass < LANE_PASSES(cnt); pass++) {
-                const int i = lane + 64 * pass;
-                if (i >= cnt) break;
-                int v;
-                if (bi) {
-                    if (i < 2 * n) { const int y = 2 * n - 1 - i; v = y == 63 ? l63 : (corner * (63 - y) + (y + 1) * l63 + 32) >> 6; }
-                    else if (i == 2 * n) v = corner;
-                    else { const int x = i - 2 * n - 1; v = x == 63 ? t63 : (corner * (63 - x) + (x + 1) * t63 + 32) >> 6; }
-                    v = (int)(short)v;
-                } else {
-                    v = (i == 0 || i == cnt - 1) ? s[i] : (int)(short)((s[i - 1] + 2 * s[i] + s[i + 1] + 2) >> 2);
-                }
-                s2[i] = v;
-            }
-            wave_sync();
-            int *tmp = s; s = s2; s2 = tmp;
-        }
-    }
-
-    /* ---- residual (with the optional rdpcm accumulation of 8.6.5) ---- */
-    const bool has_res = (flags & 2) != 0;
-    if (has_res) {
-        if (rp.wide) {
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-                if (512 * j < n * n && 8 * lane + 512 * j < n * n) *(u32x4 *)(R + 8 * lane + 512 * j) = rp.v[j];
-        } else {
-            const int16_t *src = a.residual + t.res_offset;
-            for (int i = lane; i < n * n; i += 64) R[i] = src[i];
-        }
-        wave_sync();
-        if (flags & 0x40) {
-            rdpcm_accumulate<LG>(R, lane, mode); /* rare (range extensions): kept out of line, see there */
-            wave_sync();
-        }
-        if (flags & 0x80) { /* 8.6.6 with rY aliased to r, as at hevc.c:4753-4755; products wrap like -fwrapv */
-            const int bdc = a.bitdepth_c, bdy = a.bitdepth_y;
-#pragma unroll 4
-            for (int i = lane; i < n * n; i += 64) {
-                const int up = (int)((unsigned)(int)R[i] << bdc) >> bdy;
-                R[i] = (short)(R[i] + ((int)((unsigned)t.res_scale * (unsigned)up) >> 3));
-            }
-            wave_sync();
-        }
-    }
-
-    /* ---- 4. prediction (the reference reads the neighbours as uint16_t) ---- */
-#define U16(v) ((int)((unsigned)(v) & 0xffffu))
-    int dc = 0;
-    int angle = 0;
-    if (mode == 1) {
-        unsigned sum = 0;
-        for (int i = 0; i < n; i++) sum += (unsigned)U16(LEFT(i)) + (unsigned)U16(TOP(i)); /* independent LDS reads: they pipeline (a wave
-                                                                                              butterfly of dependent bpermutes measured slower) */
-        dc = (int)((sum + (1u << lg)) >> (lg + 1));
-    } else if (mode >= 2) {
-        angle = intra_angle(mode);
-        /* ref[] of 8.4.4.2.6: main = top for modes >= 18, left otherwise; both start at the corner */
-#pragma unroll
-        for (int pass = 0; pass < LANE_PASSES(2 * n + 1); pass++) {
-            const int xx = lane + 64 * pass;
-            if (xx > 2 * n) break;
-            if (xx == 0) ref[0] = U16(TOP(-1));
-            else if (xx <= n || angle >= 0) ref[xx] = mode >= 18 ? U16(TOP(xx - 1)) : U16(LEFT(xx - 1));
-        }
-        if (angle < 0 && ((n * angle) >> 5) < -1) {
-            const int lo = (angle * n) >> 5, inv = intra_inv_angle(mode);
-            const int xx = -1 - lane; /* lo >= -n >= -32: one pass */
-            if (xx >= lo) {
-                const int k = (xx * inv + 128) >> 8;
-                ref[xx] = k == 0 ? U16(TOP(-1)) : (mode >= 18 ? U16(LEFT(k - 1)) : U16(TOP(k - 1)));
-            }
-        }
-        wave_sync();
-    }
-    const bool edge_ok = cidx == 0 && n < 32;
-    constexpr int pred_unroll = n * n <= 256 ? LANE_PASSES(n * n) : 4; /* 32x32: four of the sixteen passes in flight, so that their LDS reads overlap */
-#pragma unroll pred_unroll
-    for (int p = lane; p < n * n; p += 64) {
-        const int x = p & (n - 1), y = p >> lg;
-        int v;
-        if (mode == 0) {
-            v = ((n - 1 - x) * U16(LEFT(y)) + (x + 1) * U16(TOP(n)) + (n - 1 - y) * U16(TOP(x)) + (y + 1) * U16(LEFT(n)) + n) >> (lg + 1);
-        } else if (mode == 1) {
-            v = dc;
-            if (edge_ok && !(flags & 0x20)) {
-                if (x == 0 && y == 0) v = (U16(LEFT(0)) + 2 * dc + U16(TOP(0)) + 2) >> 2;
-                else if (y == 0) v = (U16(TOP(x)) + 3 * dc + 2) >> 2;
-                else if (x == 0) v = (U16(LEFT(y)) + 3 * dc + 2) >> 2;
-            }
-        } else {
-            const int al = mode >= 18 ? y : x, ac = mode >= 18 ? x : y; /* along / across the direction */
-            const int idx = ((al + 1) * angle) >> 5, fact = ((al + 1) * angle) & 31;
-            v = fact ? ((32 - fact) * ref[ac + idx + 1] + fact * ref[ac + idx + 2] + 16) >> 5 : ref[ac + idx + 1];
-            if (edge_ok && !(flags & 0x10)) {
-                if (mode == 26 && x == 0) v = clip3i(0, (1 << a.bitdepth_y) - 1, U16(TOP(0)) + ((U16(LEFT(y)) - U16(TOP(-1))) >> 1));
-                if (mode == 10 && y == 0) v = clip3i(0, (1 << a.bitdepth_y) - 1, U16(LEFT(0)) + ((U16(TOP(x)) - U16(TOP(-1))) >> 1));
-            }
-        }
-        /* ---- 5. reconstruct: pred is stored as int16 by the reference before the add ---- */
-        const int pr = (int)(short)(v & 0xffff);
-        const int rs = has_res ? (int)R[p] : 0;
-        int16_t *dp = plane + (long long)(y0 + y) * stride + x0 + x;
-        const short rec = (short)clip3i(0, (1 << bd) - 1, pr + rs);
-        *dp = rec;
-    }
-#undef LEFT
-#undef TOP
-#undef U16
-}
-
-/* ---- the grouped form's TU body -------------------------------------------------------------------------------
- * Same arithmetic as intra_tu above, with everything that does not depend on SAMPLES taken off the wave's
- * instruction stream -- a lone wave pays ~6-9 cycles per instruction, and the critical path of a picture is ~10 000
- * TUs walked one after the other (tests/tools/diag_intra_trace.py):
- *   - which sample a scan position takes (availability masks, substitution) comes from a table a parallel kernel
- *     wrote beforehand (k_hevc_intra_jtable), fetched one TU ahead like the residual;
+/* ---- the TU body ----------------------------------------------------------------------------------------------
+ * One TU by one wave, steps 5-10 of decode_intra_block: the ONE statement of 8.4.4.2 on the device, called by the
+ * grouped, the serial and the levels kernel.  s: NB_MAX ints, R: 32*32 shorts, private to the wave (LDS).  Everything
+ * that does not depend on SAMPLES is off the wave's instruction stream -- a lone wave pays ~6-9 cycles per
+ * instruction, and the critical path of a picture is ~10 000 TUs walked one after the other
+ * (tests/tools/diag_intra_trace.py):
+ *   - which sample a scan position takes (availability masks, substitution) comes with the call, in a JPrefetch: from
+ *     a table a parallel kernel wrote beforehand (k_hevc_intra_jtable), fetched one TU ahead like the residual, or,
+ *     in the levels form, from the TU record (substitution_inline);
  *   - the angular predictor reads the scan-order array directly: ref[k] of 8.4.4.2.6 is s[2n + k] (k >= 0) or
  *     s[2n - ((k * invAngle + 128) >> 8)] (k < 0) for the vertical modes and the mirror image for the horizontal
  *     ones, so no ref[] array is built (that was an LDS write, a barrier and a dependent read per TU). */
@@ -475,7 +274,8 @@ __device__ __forceinline__ void fetch_residual_g(const HotArgs &a, const IntraSl
         if (8 * lane + 512 * j < nn) rp.v[j] = *(const __attribute__((address_space(1))) u32x4 *)(src + 8 * lane + 512 * j);
 }
 
-template <int LG, class MID>
+/* TILE: the wave keeps a window copy in LDS (tile); without it tile is never touched and every neighbour comes from the plane */
+template <int LG, bool TILE, class MID>
 __device__ __forceinline__ void intra_tu_g(const HotArgs &a, const GroupCtx &g, const IntraSlot &t, const int lane, int *__restrict__ s, int *__restrict__ s2, short *__restrict__ R,
                                            const ResPrefetch &rp, const JPrefetch &jp, short *__restrict__ tile, const short *__restrict__ zero_block, MID &&mid)
 {
@@ -483,7 +283,7 @@ __device__ __forceinline__ void intra_tu_g(const HotArgs &a, const GroupCtx &g, 
     const int x0 = (int)t.x, y0 = (int)t.y;
     const int wx0 = g.wx0, wy0 = g.wy0, wsz = 1 << g.wl;
     const int cidx = g.cidx, mode = (int)t.mode, flags = (int)t.flags;
-    const bool tile_ok = t.tile_ok != 0;
+    const bool tile_ok = TILE && t.tile_ok != 0;
     const int bd = cidx == 0 ? a.bitdepth_y : a.bitdepth_c;
     const int stride = g.stride;
     const __amdgpu_buffer_rsrc_t prs = g.plane_rs;
@@ -611,7 +411,7 @@ __device__ __forceinline__ void intra_tu_g(const HotArgs &a, const GroupCtx &g, 
             Rr += rstep; \
             __builtin_amdgcn_raw_buffer_store_b16(rec_, prs, goff, 0, FFHIP_AUX_SC1); \
             goff += gstep; \
-            cellp[(pass_) * rows * TILE_STRIDE] = rec_; \
+            if (TILE) cellp[(pass_) * rows * TILE_STRIDE] = rec_; \
         } while (0)
         if (n >= 8 || lane < 16) {
             if (mode == 0) {
@@ -1031,22 +831,23 @@ __global__ __launch_bounds__(256) void k_hevc_intra_program(ProgArgs a)
     }
 }
 
-template <class MID>
+template <bool TILE = true, class MID>
 __device__ __forceinline__ void intra_tu_g_any(const HotArgs &a, const GroupCtx &g, const IntraSlot &t, const int lane, int *s, int *s2, short *R,
                                                const ResPrefetch &rp, const JPrefetch &jp, short *tile, const short *zero_block, MID &&mid)
 {
     switch (t.lg) {
-    case 2: intra_tu_g<2>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
-    case 3: intra_tu_g<3>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
-    case 4: intra_tu_g<4>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
-    default: intra_tu_g<5>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
+    case 2: intra_tu_g<2, TILE>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
+    case 3: intra_tu_g<3, TILE>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
+    case 4: intra_tu_g<4, TILE>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
+    default: intra_tu_g<5, TILE>(a, g, t, lane, s, s2, R, rp, jp, tile, zero_block, mid); break;
     }
 }
 
 /* The substitution table: for every TU and every scan position i (left column bottom-up, corner, top row) the scan
  * position j whose sample position i takes -- "the nearest available one at or before me, else the first available
  * one" (8.4.4.2.2 in scan order) -- or 255 when nothing around the TU is available.  A pure function of the TU record:
- * one wave per TU, fully parallel, in front of the dependency-bound kernel. */
+ * one wave per TU, fully parallel, in front of the dependency-bound kernel.  (substitution_inline, of the levels form,
+ * states the same rule per scan position: a change to one is a change to both.) */
 struct JTabArgs {
     const ffhip_hevc_tu *tus;
     uint32_t n;
@@ -1097,31 +898,6 @@ __global__ __launch_bounds__(256) void k_hevc_intra_jtable(JTabArgs a)
     }
 }
 
-__device__ __forceinline__ void intra_tu_any(const HevcIntraArgs &a, const ffhip_hevc_tu &t, const int lane, int *s, int *s2,
-                                             int *refbase, short *R, const ResPrefetch &rp)
-{
-    switch (t.log2_size) {
-    case 2: intra_tu<2>(a, t, lane, s, s2, refbase, R, rp); break;
-    case 3: intra_tu<3>(a, t, lane, s, s2, refbase, R, rp); break;
-    case 4: intra_tu<4>(a, t, lane, s, s2, refbase, R, rp); break;
-    default: intra_tu<5>(a, t, lane, s, s2, refbase, R, rp); break;
-    }
-}
-
-/* level-synchronous form: one launch per dependency level, one wave per TU */
-__global__ __launch_bounds__(256) void k_hevc_intra(HevcIntraArgs a)
-{
-    __shared__ int nbA[4][NB_MAX], nbB[4][NB_MAX], refs[4][140];
-    __shared__ __attribute__((aligned(16))) short resl[4][32 * 32];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int item = blockIdx.x * 4 + w;
-    if (item >= a.count) return;
-    const ffhip_hevc_tu t = a.tus[a.work[item]];
-    ResPrefetch rp;
-    fetch_residual(a, t, lane, rp);
-    intra_tu_any(a, t, lane, nbA[w], nbB[w], refs[w], resl[w], rp);
-}
-
 /* Grouped form: ONE launch per picture.  The host cuts the TU list into groups -- the TUs whose
  * top-left corner falls into one window x window tile of one plane, contiguous in decode order
  * for any window no larger than the CTB -- and a wave takes groups by ticket and walks each in
@@ -1152,6 +928,84 @@ __device__ __forceinline__ IntraSlot decode_slot(const u32x4 q0, const u32x4 q2)
     sl.wait_begin = d8; sl.wait_count = d9 & 0xff; sl.signal = (d9 >> 8) & 1; sl.tile_ok = (d9 >> 9) & 1;
     sl.tu_index = d10; sl.jt_off = d11;
     return sl;
+}
+
+/* The levels form's substitution: j[pass] for scan position lane + 64 * pass, from the availability masks of the TU
+ * record alone -- the nearest available position at or before mine, else the first available one, 255 when nothing is
+ * available.  The same rule as k_hevc_intra_jtable's, stated per position instead of as a running scan (a change to
+ * one is a change to both): where the levels form is the only path, the planes are too large for a table. */
+__device__ __forceinline__ void substitution_inline(const int n, const unsigned flags, const unsigned long long avail_top, const unsigned long long avail_left,
+                                                    const int lane, JPrefetch &jp)
+{
+    /* availability by scan position as a 129-bit number: left column bottom-up (bit i = left[2n - 1 - i]), corner (bit 2n), top row */
+    const unsigned long long rl = __brevll(avail_left) >> (64 - 2 * n);
+    const unsigned long long c = (flags & 1) ? 1ull : 0ull;
+    const unsigned long long tp = n == 32 ? avail_top : (avail_top & ((1ull << (2 * n)) - 1));
+    unsigned long long m0, m1;
+    unsigned m2 = 0;
+    if (n == 32) { /* left 0..63, corner 64, top 65..128 */
+        m0 = rl; m1 = c | (tp << 1); m2 = (unsigned)(tp >> 63);
+    } else {
+        m0 = rl | (c << (2 * n)) | (tp << (2 * n + 1));
+        m1 = tp >> (63 - 2 * n); /* bits that spill past 64 (n = 16: 4n + 1 = 65) */
+    }
+    const int first = m0 ? __builtin_ctzll(m0) : (m1 ? 64 + __builtin_ctzll(m1) : (m2 ? 128 : 255));
+#pragma unroll
+    for (int pass = 0; pass < 3; pass++) {
+        const int i = lane + 64 * pass;
+        int j = -1;
+        if (i >= 128 && m2) j = 128;
+        if (j < 0 && i >= 64) {
+            const unsigned long long mm = i >= 127 ? m1 : (m1 & ((2ull << (i - 64)) - 1));
+            if (mm) j = 127 - __clzll(mm);
+        }
+        if (j < 0) {
+            const unsigned long long mm = i >= 63 ? m0 : (m0 & ((2ull << i) - 1));
+            if (mm) j = 63 - __clzll(mm);
+        }
+        jp.j[pass] = (unsigned)(j < 0 ? first : j);
+    }
+}
+
+/* Level-synchronous form: one launch per dependency level, a one-wave workgroup per TU (four waves to a workgroup
+ * measured no faster: DESIGN.md 4.20), no wave waits for another.  Per TU what k_hevc_intra_serial does -- a slot
+ * without waits or flag, a throw-away GroupCtx -- with three differences: the body is the instance without a window
+ * copy (nothing would read it: 9 KB of LDS per wave for dead stores), the substitution comes from the record
+ * (substitution_inline; hot.jt stays null), and the plane resource is made per TU.  This is the form for planes too
+ * large for 32-bit byte offsets (offsets_fit in intra_recon_impl), and the body forms its offsets in 32 bits: so the
+ * resource starts, in 64-bit arithmetic, at the first row the TU can touch (y0 - 1, or 0) and the body sees y relative
+ * to that row.  Its largest offset is then 2n rows of one stride (recon_levels checks that this fits). */
+__global__ __launch_bounds__(64) void k_hevc_intra(HevcIntraArgs a)
+{
+    __shared__ int nb[NB_MAX];
+    __shared__ __attribute__((aligned(16))) short resl[32 * 32];
+    __shared__ __attribute__((aligned(16))) short resz[64]; /* zeros: the residual of a TU without one */
+    const int lane = threadIdx.x;
+    resz[lane] = 0;
+    wave_sync();
+    const uint32_t index = SGPR(a.work[blockIdx.x]);
+    const u32x4 *rec = (const u32x4 *)(a.tus + index);
+    const u32x4 r1 = rec[1];
+    IntraSlot cur = decode_slot(rec[0], u32x4{0u, 0u, index, 0u}); /* no waits, no flag, no tile, no table */
+    const unsigned long long avail_top = (unsigned long long)SGPR(r1.x) | ((unsigned long long)SGPR(r1.y) << 32);
+    const unsigned long long avail_left = (unsigned long long)SGPR(r1.z) | ((unsigned long long)SGPR(r1.w) << 32);
+    HotArgs hot;
+    hot.residual = (const __attribute__((address_space(1))) int16_t *)(unsigned long long)a.residual;
+    hot.jt = nullptr;
+    hot.wait_idx = nullptr;
+    hot.bitdepth_y = a.bitdepth_y; hot.bitdepth_c = a.bitdepth_c;
+    ResPrefetch rp;
+    JPrefetch jp;
+    fetch_residual_g(hot, cur, lane, rp);
+    substitution_inline(1 << cur.lg, cur.flags, avail_top, avail_left, lane, jp);
+    const int row0 = cur.y ? (int)cur.y - 1 : 0;
+    GroupCtx sg = {};
+    sg.cidx = (int)cur.cidx; /* no window: the body is instantiated without the tile */
+    /* selects, not a.plane[cidx]: indexing the kernel-argument arrays with a run-time index is two scalar memory loads in front of the TU's gather */
+    sg.stride = sg.cidx == 0 ? a.stride[0] : (sg.cidx == 1 ? a.stride[1] : a.stride[2]);
+    sg.plane_rs = ffhip_rsrc((sg.cidx == 0 ? a.plane[0] : (sg.cidx == 1 ? a.plane[1] : a.plane[2])) + (long long)row0 * sg.stride, 0xffffffffu);
+    cur.y -= (unsigned)row0;
+    intra_tu_g_any<false>(hot, sg, cur, lane, nb, nullptr, resl, rp, jp, nullptr, resz, [] {}); /* (the body has no use for its second scratch array) */
 }
 
 /* A list the device planner refuses (groups that are not contiguous runs of the decode order for this window, more
@@ -1854,6 +1708,10 @@ static int recon_host_planned(IntraCall &c, const int want_wl, bool by_plane)
 /* The level-synchronous form: wavefront levels at 4x4-block granularity, per plane, one launch per level */
 static int recon_levels(IntraCall &c)
 {
+    /* k_hevc_intra's per-TU resource: a TU touches at most 2n + 1 <= 65 rows (fewer in a lower plane: no availability bit points outside it), and the
+     * byte offset of the last of them, formed in an int, must not overflow.  Rows of 16 M samples and more in a plane of more than 64 rows do. */
+    for (int k = 0; k < (c.chroma ? 3 : 1); k++)
+        if ((long long)(std::min(65, c.ph[k]) - 1) * c.a.stride[k] + c.pw[k] > (1LL << 30)) return FFHIP_EINVAL;
     std::vector<std::vector<uint32_t>> lists = intra_levels(c.h_tus, c.n_tus, c.pw, c.ph, c.chroma);
     std::vector<uint32_t> flat;
     flat.reserve((size_t)c.n_tus);
@@ -1866,7 +1724,7 @@ static int recon_levels(IntraCall &c)
     for (auto &l : lists) {
         c.a.work = g_work + off;
         c.a.count = (int)l.size();
-        hipLaunchKernelGGL(k_hevc_intra, dim3((unsigned)((c.a.count + 3) / 4)), dim3(256), 0, c.st, c.a);
+        hipLaunchKernelGGL(k_hevc_intra, dim3((unsigned)c.a.count), dim3(64), 0, c.st, c.a);
         off += l.size();
     }
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);

@@ -32,8 +32,11 @@ def test_golden_tu_lists(golden):
         assert np.array_equal(u, g[f"{tag}_u"]) and np.array_equal(v, g[f"{tag}_v"]), tag
 
 
-@pytest.mark.parametrize("w,h,seed,adv,bd", [(64, 64, 1, False, 8), (192, 128, 2, True, 8), (256, 256, 3, False, 10),
-                                             (320, 192, 4, True, 12), (512, 256, 5, False, 8)])
+TU_LIST_CASES = [(64, 64, 1, False, 8), (192, 128, 2, True, 8), (256, 256, 3, False, 10), (320, 192, 4, True, 12), (512, 256, 5, False, 8)]
+CCP_444_CASES = [(128, 128, 1, 8, 8), (256, 192, 2, 10, 12), (192, 64, 3, 12, 8)]
+
+
+@pytest.mark.parametrize("w,h,seed,adv,bd", TU_LIST_CASES)
 def test_tu_lists_vs_oracle(w, h, seed, adv, bd):
     tus, res = synth.hevc_intra_tus(w, h, seed + 100, adversarial_masks=adv)
     if bd > 8:
@@ -44,7 +47,7 @@ def test_tu_lists_vs_oracle(w, h, seed, adv, bd):
         assert np.array_equal(gp, e), name
 
 
-@pytest.mark.parametrize("w,h,seed,bd,bdc", [(128, 128, 1, 8, 8), (256, 192, 2, 10, 12), (192, 64, 3, 12, 8)])
+@pytest.mark.parametrize("w,h,seed,bd,bdc", CCP_444_CASES)
 def test_cross_component_444_vs_oracle(w, h, seed, bd, bdc):
     """8.6.6 after rdpcm on 4:4:4 TU lists, with extreme residuals so the shift/multiply wraps"""
     tus, res = synth.hevc_intra_tus(w, h, seed + 300, adversarial_masks=True, ccp=True, chroma_444=True)
@@ -81,6 +84,59 @@ def test_every_mode_and_size_isolated():
             got = ops.hevc_intra_recon(tus[i:i + 1], res, w, h, False)[0]
             exp = O.oracle_hevc_intra(tus[i:i + 1], res, w, h, False)[0]
             assert np.array_equal(got, exp), (lg, i)
+
+
+# The same lists through the level-synchronous launches (k_hevc_intra), which call the one TU body with a substitution and a plane
+# resource of their own: between them these reach every branch of the body -- all four sizes, smoothing with and without the bi-linear
+# 32x32 case, the edge filters, substitution from every side, rdpcm and the cross-component step, and "nothing available".
+@pytest.fixture
+def levels_form(monkeypatch):
+    monkeypatch.setenv("FFHIP_HEVC_INTRA_MODE", "levels"); capi.reload_env()
+
+
+def test_golden_tu_lists_levels_form(golden, levels_form):
+    test_golden_tu_lists(golden)
+
+
+@pytest.mark.parametrize("w,h,seed,adv,bd", TU_LIST_CASES)
+def test_tu_lists_vs_oracle_levels_form(w, h, seed, adv, bd, levels_form):
+    test_tu_lists_vs_oracle(w, h, seed, adv, bd)
+
+
+@pytest.mark.parametrize("w,h,seed,bd,bdc", CCP_444_CASES)
+def test_cross_component_444_vs_oracle_levels_form(w, h, seed, bd, bdc, levels_form):
+    test_cross_component_444_vs_oracle(w, h, seed, bd, bdc)
+
+
+def test_every_mode_and_size_isolated_levels_form(levels_form):
+    test_every_mode_and_size_isolated()
+
+
+def test_planes_too_large_for_32_bit_offsets():
+    """rows 32 MiB (luma) and 64 MiB (chroma) apart: the planes are too large for the 32-bit byte offsets of the grouped and the serial
+    form, so the call takes the levels form without being asked to, and that form has to address every row from a base of the TU's own"""
+    L = capi.require_device()
+    w = h = 64
+    ys, cs = 1 << 24, 1 << 25
+    tus, res = synth.hevc_intra_tus(w, h, 202, adversarial_masks=True)
+    assert set(tus["log2_size"][tus["cidx"] == 0].tolist()) == {2, 3, 4, 5} and 5 in set(tus["log2_size"][tus["cidx"] > 0].tolist())
+    exp = O.oracle_hevc_intra(tus, res, w, h, True, 8, 8)
+    tus = np.ascontiguousarray(tus)
+    dt, dr = ops.DeviceBuffer(tus.view(np.uint8)), ops.DeviceBuffer(np.ascontiguousarray(res))
+    geo = [(w, h, ys), (w // 2, h // 2, cs), (w // 2, h // 2, cs)]      # (width, rows, stride in samples) per plane
+    planes = [ops.DeviceBuffer(nbytes=((ph - 1) * st + pw) * 2) for (pw, ph, st) in geo]     # ~2 GiB each, touched in the picture's rows only
+    for d, (pw, ph, st) in zip(planes, geo):
+        for r in range(ph):
+            capi.check(L.ffhip_memset(d.ptr + r * st * 2, 0, pw * 2, None))
+    capi.check(L.ffhip_hevc_intra_recon(tus.ctypes.data, dt.ptr, len(tus), dr.ptr, planes[0].ptr, planes[1].ptr, planes[2].ptr,
+                                        w, h, ys, w // 2, h // 2, cs, 8, 8, None), "ffhip_hevc_intra_recon")
+    capi.check(L.ffhip_stream_sync(None))
+    for d, (pw, ph, st), e, name in zip(planes, geo, exp, "YUV"):
+        got = np.empty((ph, pw), np.int16)
+        for r in range(ph):
+            capi.check(L.ffhip_memcpy_d2h(got[r].ctypes.data, d.ptr + r * st * 2, pw * 2, None), "d2h")
+        capi.check(L.ffhip_stream_sync(None))
+        assert np.array_equal(got, e), name
 
 
 @pytest.mark.parametrize("env", [{"FFHIP_HEVC_INTRA_MODE": "levels"}, {"FFHIP_HEVC_PLAN": "host"}, {"FFHIP_HEVC_PLAN": "host", "FFHIP_HEVC_INTRA_WINDOW": "4"},
