@@ -27,6 +27,8 @@ EXPORTS = [
     "ffhip_bgra_checksum", "ffhip_vp8_filter_params", "ffhip_vp8_predict_loopfilter", "ffhip_reload_env", "ffhip_env_value_test", "ffhip_vp8_decode_frames", "ffhip_bgra_layout",
     "ffhip_jpeg_recon_items", "ffhip_jpeg_decode_files_mixed_device", "ffhip_vp8_decode_items",
     "ffhip_vp8_dequant_factors", "ffhip_webp_probe", "ffhip_webp_parse", "ffhip_webp_parse_batch", "ffhip_webp_parse_device", "ffhip_webp_decode_files_device", "ffhip_debug_webp_last_parts",
+    "ffhip_webp_probe_ex", "ffhip_webp_parse_ex", "ffhip_webp_parse_device_ex", "ffhip_webp_decode_files_device_ex", "ffhip_webp_decode_files_tensor_ex",
+    "ffhip_vp8_libwebp_residual_mb", "ffhip_webp_libwebp_color", "ffhip_debug_vp8_decode_items_libwebp", "ffhip_debug_vp8_upsample_color",
     "ffhip_bgra_to_tensor_items", "ffhip_jpeg_decode_files_tensor", "ffhip_webp_decode_files_tensor",
     "ffhip_resize_axis_taps", "ffhip_bgra_resize_items", "ffhip_jpeg_decode_files_tensor_resized", "ffhip_webp_decode_files_tensor_resized",
     "ffhip_jpeg_scaled_block", "ffhip_jpeg_scaled_size", "ffhip_jpeg_scaled_rect", "ffhip_jpeg_scale_choose", "ffhip_jpeg_scaled_wg_blocks",
@@ -44,6 +46,7 @@ EXPORTS = [
 FFHIP_EINVAL, FFHIP_ENOMEM, FFHIP_ENODEV, FFHIP_EIO = -22, -12, -19, -5     # include/ffpic_hip.h:34-37
 FFHIP_JPEG_ACCEPT_PROGRESSIVE, FFHIP_JPEG_MAX_SCANS = 1, 128
 FFHIP_JPEG_PIXELS_LIBJPEG = 0x10
+FFHIP_WEBP_PIXELS_LIBWEBP = 0x10
 FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1002, -1003
 
 
@@ -289,6 +292,14 @@ def lib():
     L.ffhip_webp_parse_device.argtypes = [vp, vp, ci, C.POINTER(WebpParsed), vp, vp]
     L.ffhip_debug_webp_last_parts.argtypes = [vp]
     L.ffhip_webp_decode_files_device.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(WebpInfo), vp, vp]
+    L.ffhip_webp_probe_ex.argtypes = [vp, sz, C.c_uint, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.ffhip_webp_parse_ex.argtypes = [vp, sz, C.c_uint, C.POINTER(WebpParsed)]
+    L.ffhip_webp_parse_device_ex.argtypes = [vp, vp, ci, C.c_uint, C.POINTER(WebpParsed), vp, vp]
+    L.ffhip_webp_decode_files_device_ex.argtypes = [vp, vp, ci, ci, vp, vp, vp, C.c_uint, C.POINTER(WebpInfo), vp, vp]
+    L.ffhip_vp8_libwebp_residual_mb.argtypes = [vp, ci, vp, vp, C.POINTER(ci)]
+    L.ffhip_webp_libwebp_color.argtypes = [vp, i64, vp, vp, i64, ci, ci, vp, i64]
+    L.ffhip_debug_vp8_decode_items_libwebp.argtypes = [C.POINTER(Vp8Item), ci, C.POINTER(Size), vp]
+    L.ffhip_debug_vp8_upsample_color.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, i64, i64, vp, i64, i64, vp]
     L.ffhip_hevc_picture_layout.argtypes = [ci, ci, ci, C.POINTER(HevcLayout)]
     L.ffhip_heif_grid_parse.argtypes = [vp, sz, C.POINTER(HeifGrid)]
     L.ffhip_heif_grid_compose.argtypes = [vp, i64, ci, ci, vp, i64, i64, ci, ci, ci, ci, vp]
@@ -343,6 +354,8 @@ def lib():
                                                           C.POINTER(JpegGeom), vp, vp]
     L.ffhip_webp_decode_files_tensor_oriented.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
                                                           C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(WebpInfo), vp, vp]
+    L.ffhip_webp_decode_files_tensor_ex.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                    C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.c_uint, C.POINTER(WebpInfo), vp, vp]
     L.ffhip_jpeg_probe_any.argtypes = [vp, sz, C.POINTER(JpegGeom), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.ffhip_jpeg_progressive_decode.argtypes = [vp, sz, C.POINTER(JpegGeom), vp, vp, vp, vp, ci]
     L.ffhip_jpeg_progressive_batch_gpu.argtypes = [vp, vp, ci, ci, C.POINTER(JpegGeom), vp, vp, vp, vp, ci, vp, vp]

@@ -111,6 +111,7 @@ enum FfhipScratchKind {
     SCRATCH_FILES_MIXED = 7,       /* ffhip_jpeg_decode_files_mixed_device: a class's planes and quantiser tables, the host decoder's pinned planes */
     SCRATCH_JPEG_ITEMS = 40,       /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items' records and per-workgroup table, pinned records */
     SCRATCH_WEBP = 60,             /* .. + 1: ffhip_webp_decode_files_device: a part's arrays, descriptors and file bytes (and their pinned copy); the host threads' pinned arrays */
+    SCRATCH_VP8_LIBWEBP = 55,      /* .. + 1: the libwebp rule of ffhip_vp8_decode_items: the colour items' records and table (pinned records); the filtered planes */
     SCRATCH_VP8_ITEMS = 50,        /* .. + 2: ffhip_vp8_decode_items' tables (and their pinned copy), the levels items' residual, the line slots */
     SCRATCH_TENSOR_ITEMS = 70,     /* ffhip_bgra_to_tensor_items' records and per-workgroup table, pinned records */
     SCRATCH_TENSOR_BGRA = 71,      /* ffhip_*_decode_files_tensor: a part's BGRA pictures */
@@ -135,6 +136,26 @@ struct Vp8ResItem {
 struct Vp8CheckItem { const uint8_t *modes; long long first; /* its first record among the items checked on the device */ };
 int vp8_residual_items_enqueue(const Vp8ResItem *d_items, int n, long long n_mb, uint32_t *d_wg_item, void *stream);
 int vp8_check_modes_items_enqueue(const Vp8CheckItem *d_items, int n, long long n_records, uint32_t *ctrl, int *async_err, void *stream);
+
+/* ---- WEBP_RULE_LIBWEBP behind the front end (ffhip_vp8_bool.h has the rule's value) ----
+ * the residual stage's items (ffhip_vp8_libwebp.hip): as Vp8ResItem, with the item's mode records, byte [19] of which receives "some block of
+ * the macroblock has a non-zero dequantised coefficient"; the table ends in a sentinel whose `first` is the total */
+struct Vp8LwResItem : Vp8ResItem {
+    uint8_t *modes; /* [n_mb][20], the call's own copy */
+};
+int vp8_libwebp_residual_items_enqueue(const Vp8LwResItem *d_items, int n, long long n_mb, void *stream);
+/* planes to BGRA over the display rectangle, a HOST array of items, one launch (k_vp8_upsample_color): planes 4-byte aligned, strides multiples
+ * of 4 with ys >= width rounded up to 4; bgra 16-byte aligned, pitch a multiple of 16.  Only enqueues */
+struct Vp8LwColorItem {
+    const uint8_t *y, *u, *v;
+    int ys, uvs, width, height;
+    uint8_t *bgra;
+    long long pitch;
+};
+int vp8_libwebp_color_items(const Vp8LwColorItem *items, int n, void *stream);
+/* ffhip_vp8_decode_items under a rule.  WEBP_RULE_LIBWEBP: levels items without a residual map only; display[i] = the picture's width and height
+ * (within its macroblock grid); planes: NULL or per item a triple y, u, v that receives the filtered planes as well */
+int vp8_decode_items_rule(const ffhip_vp8_item *items, int n, int rule, const ffhip_size *display, uint8_t *const *planes, void *stream);
 
 /* ffhip_vp8_decode_frames (row form) -> ffhip_vp8_predict_loopfilter: the colour conversion the caller enqueues behind the call belongs to
  * it -- a retry has to run it again, behind the filter */

@@ -432,19 +432,20 @@ int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
 int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
                       const TensorOptions &opts, ffhip_webp_info *info_out, int *status, void *stream)
 {
-    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts)) return FFHIP_EINVAL;
+    const unsigned flags = opts.flags; /* FFHIP_WEBP_PIXELS_LIBWEBP: probe and decode under that rule; the planner and the chain do not know */
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts) || (flags & ~FFHIP_WEBP_PIXELS_LIBWEBP)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
     std::vector<TensorFile> plan((size_t)n);
     for (int i = 0; i < n; i++) {
         int w = 0, h = 0, c = 0, r = 0;
-        status[i] = files[i] && lens[i] ? ffhip_webp_probe(files[i], lens[i], &w, &h, &c, &r) : FFHIP_EINVAL;
+        status[i] = files[i] && lens[i] ? ffhip_webp_probe_ex(files[i], lens[i], flags, &w, &h, &c, &r) : FFHIP_EINVAL;
         /* the loader's size is the container's word (ffhip_webp_info): what of it the decoded picture holds */
         const TensorProbe p{status[i], TensorPicture{16 * c, 16 * r, w < 16 * c ? w : 16 * c, h < 16 * r ? h : 16 * r, 64LL * c}};
         plan[(size_t)i] = tensor_file_plan(p, tensor_orientation(opts, i, p, ffhip_webp_exif_orientation, files[i], lens[i]), i, opts, fmt, outs);
     }
     return tensor_files_run(plan, opts, fmt, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
-        return ffhip_webp_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
-                                              status + first, stream);
+        return ffhip_webp_decode_files_device_ex(files + first, lens + first, cnt, n_threads, d_bgra, pitch, nullptr, flags,
+                                                 info_out ? info_out + first : nullptr, status + first, stream);
     });
 }
 
@@ -513,3 +514,11 @@ extern "C" int ffhip_webp_decode_files_tensor_oriented(const uint8_t *const *fil
 
 extern "C" int ffhip_debug_tensor_last_parts(void) { return g_tensor_last_parts; }
 extern "C" int ffhip_debug_orient_last_items(void) { return g_orient_last_items; }
+
+extern "C" int ffhip_webp_decode_files_tensor_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                 const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                 const int *orient, int *orient_out, unsigned flags, ffhip_webp_info *info_out, int *status, void *stream)
+{
+    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags), info_out,
+                             status, stream);
+}

@@ -1,7 +1,7 @@
 /* ffhip_vp8_bool.h -- the VP8 bool decoder and the two per-macroblock parsers behind it, written once for the host front end
  * (ffhip_webp.c, plain C) and the device front end (ffhip_vp8_bool_gpu.hip): the arithmetic of coding/booldec.c:95-119,
  * vp8_decode_mb_header (format/webp.c:1277-1450) and vp8_get_coefficients / vp8_decode_residual_block's parse order
- * (webp.c:992-1064, 1147-1196), restated as they ARE, not as RFC 6386 has them:
+ * (webp.c:992-1064, 1147-1196), restated as they ARE, not as RFC 6386 has them (under WEBP_RULE_LIBWEBP, below, as RFC 6386 has them):
  *   - `range` is kept as the range itself; a decode works on range - 1, takes split = ((range - 1) * prob) >> 8 and
  *     renormalises by 7 ^ floor(log2(range)); a byte is loaded only when `count` is negative (booldec.c:98-117);
  *   - the 11 extra bits of a cat6 token are summed in a uint8_t (DCTextra, webp.c:965-971), so they wrap modulo 256;
@@ -24,6 +24,17 @@
 #define FFB_FN static inline
 #define FFB_TBL static const
 #endif
+
+/* WebpPixelRule: which pixels a lossy WebP call gives, ONE compile-time value wherever it reaches generated code.  Plain host code takes it as a
+ * `const int rule` that its callers pass as a literal.  Text that kernels compile is included once per rule with the rule as a macro
+ * (ffhip_vp8_bool_tokens.inc, ffhip_vp8_bool_kernels.inc, ffhip_vp8_frame_items.inc, ffhip_vp8_frame_row.inc): as a function argument or a template parameter it changed
+ * the names of static tables and the address arithmetic of the reference's instances, which are held to their code instruction by instruction
+ * (tests/tools/isa_diff.py).
+ *   WEBP_RULE_REFERENCE  the reference's WEBP_load bit for bit, with its named deviations from RFC 6386: the default
+ *   WEBP_RULE_LIBWEBP    RFC 6386 as libwebp decodes it: tests/vp8_spec.py with rules=SPEC is its witness */
+typedef int WebpPixelRule;
+#define WEBP_RULE_REFERENCE 0
+#define WEBP_RULE_LIBWEBP 1
 
 typedef struct ffb_dec {
     const uint8_t *p; /* the partition */
@@ -91,8 +102,9 @@ FFB_FN int ffb_sbits(ffb_dec *d, int n) /* bool_dec_signed_bits: magnitude, then
 /* What the frame header leaves for the macroblock headers (webp.c:1291-1300). */
 typedef struct ffb_mbhdr_probs {
     uint8_t update_map;  /* update_mb_segmentation_map: 1 also when segmentation is OFF (webp.c:393), so a segment id is then read
-                            from every macroblock header with the zero probabilities of the calloc'ed decoder */
-    uint8_t seg_prob[3]; /* 0 unless the header set them: the reference has no 255 default */
+                            from every macroblock header with the zero probabilities of the calloc'ed decoder.  WEBP_RULE_LIBWEBP: the
+                            header reader leaves 1 here only when segmentation AND the map update are on */
+    uint8_t seg_prob[3]; /* 0 unless the header set them: the reference has no 255 default (WEBP_RULE_LIBWEBP: 255) */
     uint8_t no_skip;     /* mb_no_skip_coeff */
     uint8_t prob_skip;   /* prob_skip_false */
 } ffb_mbhdr_probs;
@@ -164,95 +176,22 @@ FFB_FN uint32_t ffb_rec_bottom4(const uint8_t *rec)
     return (uint32_t)rec[14] | (uint32_t)rec[15] << 8 | (uint32_t)rec[16] << 16 | (uint32_t)rec[17] << 24;
 }
 
-/* vp8_get_coefficients (webp.c:992-1064) without its dequantising multiply: the LEVELS at their raster position in out[16].
- * probs: the 8 bands x 3 contexts x 11 probabilities of the block's type. */
-FFB_FN int ffb_coefficients(ffb_dec *d, const uint8_t *probs, int first, int ctx, int16_t *out)
-{
-    FFB_TBL uint8_t pcat[4][12] = {{173, 148, 140, 0}, {176, 155, 140, 135, 0}, {180, 157, 141, 134, 130, 0},
-                                   {254, 254, 243, 230, 196, 177, 153, 140, 133, 130, 129, 0}};
-    const uint64_t bands = 0x7666666665463210ull;  /* coeff_bands[16], a nibble each (webp.c:1129) */
-    const uint64_t zigzag = 0xfeb7adc963258410ull; /* kZigzag[16] (webp.c:1013) */
-    int prev_zero = 0;
-    for (int n = first; n < 16; ++n) {
-        const uint8_t *p = probs + (int)((bands >> (4 * n)) & 15) * 33 + ctx * 11;
-        int v;
-        if (!prev_zero && !ffb_bit(d, p[0])) return n - first; /* dct_eob; not coded behind a zero */
-        if (!ffb_bit(d, p[1])) {
-            prev_zero = 1;
-            ctx = 0;
-            continue; /* out[] was cleared by the caller */
-        }
-        prev_zero = 0;
-        if (!ffb_bit(d, p[2])) {
-            v = 1;
-        } else if (!ffb_bit(d, p[3])) {
-            if (!ffb_bit(d, p[4])) v = 2;
-            else v = 3 + ffb_bit(d, p[5]);
-        } else if (!ffb_bit(d, p[6])) {
-            if (!ffb_bit(d, p[7])) {
-                v = 5 + ffb_bit(d, 159); /* cat1 */
-            } else {
-                v = 7 + 2 * ffb_bit(d, 165); /* cat2 */
-                v += ffb_bit(d, 145);
-            }
-        } else {
-            const int b1 = ffb_bit(d, p[8]);
-            const int cat = 2 * b1 + ffb_bit(d, p[9 + b1]); /* 0..3 = cat3..cat6 */
-            uint32_t extra = 0;
-            for (const uint8_t *q = pcat[cat]; *q; ++q) extra = (2 * extra + (uint32_t)ffb_bit(d, *q)) & 255u; /* a uint8_t in the reference */
-            v = (int)extra + (cat == 0 ? 11 : cat == 1 ? 19 : cat == 2 ? 35 : 67);
-        }
-        ctx = v == 1 ? 1 : 2;
-        if (ffb_bit(d, 128)) v = -v;
-        out[(zigzag >> (4 * n)) & 15] = (int16_t)v;
-    }
-    return 16;
-}
-
-/* The token parse of one coded macroblock (webp.c:1147-1196).  probs [4][8][3][11]; *top9 / *left9: the nine "had tokens" flags
- * of the column above / of the row so far, bit 0 the Y2 block, 1-4 luma, 5-6 U, 7-8 V; levels [25][16] must be ZERO on entry
- * (only non-zero levels are stored), counts [25] receives every block's token count. */
-FFB_FN void ffb_mb_tokens(ffb_dec *d, const uint8_t *probs, int has_y2, uint32_t *top9, uint32_t *left9, int16_t *levels, uint8_t *counts)
-{
-    uint32_t top = *top9, left = *left9;
-    int first = 0;
-    const uint8_t *yp = probs + 3 * 264;
-    if (has_y2) {
-        const int nz = ffb_coefficients(d, probs + 264, 0, (int)(top & 1) + (int)(left & 1), levels + 24 * 16);
-        counts[24] = (uint8_t)nz;
-        top = (top & ~1u) | (nz > 0);
-        left = (left & ~1u) | (nz > 0);
-        first = 1;
-        yp = probs;
-    } else {
-        counts[24] = 0;
-    }
-    for (int y = 0; y < 4; ++y) {
-        uint32_t l = (left >> (y + 1)) & 1;
-        for (int x = 0; x < 4; ++x) {
-            const int nz = ffb_coefficients(d, yp, first, (int)((top >> (x + 1)) & 1) + (int)l, levels + (y * 4 + x) * 16);
-            counts[y * 4 + x] = (uint8_t)nz;
-            l = nz > 0;
-            top = (top & ~(2u << x)) | (l << (x + 1));
-        }
-        left = (left & ~(2u << y)) | (l << (y + 1));
-    }
-    int blk = 16;
-    for (int ch = 5; ch <= 7; ch += 2)
-        for (int y = 0; y < 2; ++y) {
-            uint32_t l = (left >> (y + ch)) & 1;
-            for (int x = 0; x < 2; ++x, ++blk) {
-                const int nz = ffb_coefficients(d, probs + 2 * 264, 0, (int)l + (int)((top >> (x + ch)) & 1), levels + blk * 16);
-                counts[blk] = (uint8_t)nz;
-                l = nz > 0;
-                top = (top & ~(1u << (x + ch))) | (l << (x + ch));
-            }
-            left = (left & ~(1u << (y + ch))) | (l << (y + ch));
-        }
-    *top9 = top;
-    *left9 = left;
-}
-
+/* the token parsers, an instance per rule (ffhip_vp8_bool_tokens.inc): ffb_coefficients + ffb_mb_tokens (the reference's) and ffb_coefficients_libwebp +
+ * ffb_mb_tokens_libwebp (cat6 extra bits not wrapped) */
+#define FFB_COEF_NAME ffb_coefficients
+#define FFB_TOKENS_NAME ffb_mb_tokens
+#define FFB_COEF_RULE WEBP_RULE_REFERENCE
+#include "ffhip_vp8_bool_tokens.inc"
+#undef FFB_COEF_NAME
+#undef FFB_TOKENS_NAME
+#undef FFB_COEF_RULE
+#define FFB_COEF_NAME ffb_coefficients_libwebp
+#define FFB_TOKENS_NAME ffb_mb_tokens_libwebp
+#define FFB_COEF_RULE WEBP_RULE_LIBWEBP
+#include "ffhip_vp8_bool_tokens.inc"
+#undef FFB_COEF_NAME
+#undef FFB_TOKENS_NAME
+#undef FFB_COEF_RULE
 /* a skipped macroblock's contexts (webp.c:1213-1221): 1-8 cleared always, 0 only when it has a Y2 block */
 FFB_FN uint32_t ffb_skip_ctx(uint32_t ctx9, int has_y2) { return has_y2 ? 0u : ctx9 & 1u; }
 

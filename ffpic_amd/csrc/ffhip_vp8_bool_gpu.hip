@@ -49,98 +49,25 @@ struct WebpDesc {
     uint8_t probs[1056];
 };
 
-/* kernel A: one lane = the first partition of one frame */
-__global__ __launch_bounds__(64) void k_webp_mb_headers(const WebpDesc *descs, int n, int pack, int32_t *verdict)
-{
-    const int lane = threadIdx.x, i = blockIdx.x * pack + lane;
-    if (lane >= pack || i >= n) return;
-    const WebpDesc &D = descs[i];
-    ffb_dec d;
-    d.p = D.bytes;
-    d.pos = D.pos;
-    d.len = D.p0_len;
-    d.value = D.value;
-    d.range = D.range;
-    d.count = D.count;
-    d.err = 0;
-    const ffb_mbhdr_probs fp = D.mb;
-    const int cols = D.mbcols, rows = D.mbrows;
-    int32_t last_coded = -1;
-    for (int y = 0; y < rows; y++) {
-        uint32_t left4 = 0;
-        for (int x = 0; x < cols; x++) {
-            const int32_t mb = y * cols + x;
-            uint8_t *rec = D.modes + (size_t)mb * 20;
-            const uint32_t above4 = y > 0 ? ffb_rec_bottom4(rec - (size_t)cols * 20) : 0;
-            uint8_t r[20];
-            const int skip = ffb_mb_header(&d, &fp, above4, &left4, r);
-            uint32_t *rw = (uint32_t *)rec; /* records are 4-byte aligned */
-#pragma unroll
-            for (int k = 0; k < 5; k++) rw[k] = (uint32_t)r[4 * k] | (uint32_t)r[4 * k + 1] << 8 | (uint32_t)r[4 * k + 2] << 16 | (uint32_t)r[4 * k + 3] << 24;
-            D.skip[mb] = (uint8_t)skip;
-            if (!skip) last_coded = mb;
-            D.resmap[mb] = skip && last_coded >= 0 ? last_coded : mb;
-        }
-    }
-    verdict[2 * i] = d.err;
-}
-
-/* kernel B: one lane = the token partitions of one frame */
-__global__ __launch_bounds__(64) void k_webp_tokens(const WebpDesc *descs, int n, int pack, int32_t *verdict)
-{
-    extern __shared__ uint32_t s_probs[]; /* [pack][264] */
-    for (int s = 0; s < pack; s++) {
-        const int f = blockIdx.x * pack + s;
-        if (f < n) {
-            const uint32_t *src = (const uint32_t *)descs[f].probs;
-            for (int k = threadIdx.x; k < 264; k += 64) s_probs[s * 264 + k] = src[k];
-        }
-    }
-    __syncthreads();
-    const int lane = threadIdx.x, i = blockIdx.x * pack + lane;
-    if (lane >= pack || i >= n) return;
-    const WebpDesc &D = descs[i];
-    const uint8_t *probs = (const uint8_t *)(s_probs + lane * 264);
-    const int cols = D.mbcols, rows = D.mbrows, nparts = D.nparts;
-    ffb_dec d;
-    int err = 0;
-    for (int k = nparts - 1; k >= 0; k--) { /* bool_dec_init of every partition (webp.c:1905-1911); partition 0 stays in registers */
-        ffb_init(&d, D.bytes + D.part_off[k], D.part_len[k]); /* loads nothing: a partition no row reads may be empty */
-        if (nparts > 1) {
-            D.parked[4 * k] = d.value; D.parked[4 * k + 1] = d.range; D.parked[4 * k + 2] = (uint32_t)d.count; D.parked[4 * k + 3] = d.pos;
-        }
-    }
-    int cur = 0;
-    for (int y = 0; y < rows; y++) {
-        const int want = y & (nparts - 1);
-        if (want != cur) { /* park the row's decoder, take the next row's */
-            D.parked[4 * cur] = d.value; D.parked[4 * cur + 1] = d.range; D.parked[4 * cur + 2] = (uint32_t)d.count; D.parked[4 * cur + 3] = d.pos;
-            err |= d.err;
-            d.p = D.bytes + D.part_off[want];
-            d.len = D.part_len[want];
-            d.value = D.parked[4 * want]; d.range = D.parked[4 * want + 1]; d.count = (int32_t)D.parked[4 * want + 2]; d.pos = D.parked[4 * want + 3];
-            d.err = 0;
-            cur = want;
-        }
-        uint32_t left9 = 0;
-        for (int x = 0; x < cols; x++) {
-            const size_t mb = (size_t)y * cols + x;
-            const int has_y2 = D.modes[mb * 20] != 4;
-            uint8_t *info = D.mbinfo + mb * 32;
-            uint32_t top9 = D.top[x];
-            if (!D.skip[mb]) {
-                ffb_mb_tokens(&d, probs, has_y2, &top9, &left9, D.levels + mb * 400, info);
-            } else {
-                top9 = ffb_skip_ctx(top9, has_y2);
-                left9 = ffb_skip_ctx(left9, has_y2);
-            }
-            D.top[x] = (uint16_t)top9;
-            info[25] = (uint8_t)has_y2;
-            info[26] = D.modes[mb * 20 + 18];
-        }
-    }
-    verdict[2 * i + 1] = err | d.err;
-}
+/* the two kernels, once per rule */
+#define WEBP_K_HEADERS k_webp_mb_headers
+#define WEBP_K_TOKENS k_webp_tokens
+#define WEBP_K_RULE WEBP_RULE_REFERENCE
+#define WEBP_K_MB_TOKENS ffb_mb_tokens
+#include "ffhip_vp8_bool_kernels.inc"
+#undef WEBP_K_HEADERS
+#undef WEBP_K_TOKENS
+#undef WEBP_K_RULE
+#undef WEBP_K_MB_TOKENS
+#define WEBP_K_HEADERS k_webp_mb_headers_libwebp
+#define WEBP_K_TOKENS k_webp_tokens_libwebp
+#define WEBP_K_RULE WEBP_RULE_LIBWEBP
+#define WEBP_K_MB_TOKENS ffb_mb_tokens_libwebp
+#include "ffhip_vp8_bool_kernels.inc"
+#undef WEBP_K_HEADERS
+#undef WEBP_K_TOKENS
+#undef WEBP_K_RULE
+#undef WEBP_K_MB_TOKENS
 
 namespace {
 
@@ -179,8 +106,9 @@ int env_int(const char *v, int dflt) { return v && *v ? atoi(v) : dflt; }
  * `outs` is given the arrays are copied back to the host instead of being decoded (ffhip_webp_parse_device). */
 int run_part(const std::vector<PartFile> &pf, const std::vector<ffhip_webp_frame> &frames, const uint8_t *const *files, const size_t *lens,
              size_t n_mb, size_t cols_sum, size_t file_bytes, bool on_device, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
-             ffhip_webp_parsed *outs, int *status, void *stream)
+             ffhip_webp_parsed *outs, int *status, void *stream, int rule, uint8_t *const *planes)
 {
+    const bool lw = rule == WEBP_RULE_LIBWEBP;
     hipStream_t st = (hipStream_t)stream;
     const int nf = (int)pf.size();
     const PartLayout L(n_mb, cols_sum, (size_t)nf, on_device ? file_bytes : 0);
@@ -225,15 +153,20 @@ int run_part(const std::vector<PartFile> &pf, const std::vector<ffhip_webp_frame
         });
         FFHIP_CHECK(hipMemcpyAsync(dev + L.descs, pin, pin_bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
         FFHIP_CHECK(hipMemsetAsync(dev + L.levels, 0, L.modes - L.levels, st), FFHIP_EIO);
-        int slots = ffhip_resident_waves((const void *)k_webp_tokens, 64);
+        int slots = ffhip_resident_waves(lw ? (const void *)k_webp_tokens_libwebp : (const void *)k_webp_tokens, 64);
         if (slots < 1) slots = 1024;
         int pack = nf <= slots ? 1 : std::min(WEBP_PACK_MAX, (nf + slots - 1) / slots);
         pack = std::max(1, std::min(WEBP_PACK_MAX, env_int(FFHIP_ENV("FFHIP_WEBP_PACK"), pack))); /* tests: several frames to a wave in a small batch */
         const int grid = (nf + pack - 1) / pack;
         const WebpDesc *dd = (const WebpDesc *)(dev + L.descs);
         int32_t *dv = (int32_t *)(dev + L.verdict);
-        hipLaunchKernelGGL(k_webp_mb_headers, dim3(grid), dim3(64), 0, st, dd, nf, pack, dv);
-        hipLaunchKernelGGL(k_webp_tokens, dim3(grid), dim3(64), (size_t)pack * 1056, st, dd, nf, pack, dv);
+        if (lw) {
+            hipLaunchKernelGGL(k_webp_mb_headers_libwebp, dim3(grid), dim3(64), 0, st, dd, nf, pack, dv);
+            hipLaunchKernelGGL(k_webp_tokens_libwebp, dim3(grid), dim3(64), (size_t)pack * 1056, st, dd, nf, pack, dv);
+        } else {
+            hipLaunchKernelGGL(k_webp_mb_headers, dim3(grid), dim3(64), 0, st, dd, nf, pack, dv);
+            hipLaunchKernelGGL(k_webp_tokens, dim3(grid), dim3(64), (size_t)pack * 1056, st, dd, nf, pack, dv);
+        }
         FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
         std::vector<int32_t> verdict((size_t)nf * 2);
         FFHIP_CHECK(hipMemcpyAsync(verdict.data(), dv, (size_t)nf * 8, hipMemcpyDeviceToHost, st), FFHIP_EIO);
@@ -249,7 +182,7 @@ int run_part(const std::vector<PartFile> &pf, const std::vector<ffhip_webp_frame
         if (!pin) return FFHIP_ENOMEM;
         ffhip_parallel_for(nf, n_threads, [&](int k) {
             const PartFile &p = pf[(size_t)k];
-            status[p.idx] = ffhip_webp_parse_frame(files[p.idx], &frames[(size_t)p.idx], pin + L.modes + p.first_mb * 20,
+            status[p.idx] = (lw ? ffhip_webp_parse_frame_libwebp : ffhip_webp_parse_frame)(files[p.idx], &frames[(size_t)p.idx], pin + L.modes + p.first_mb * 20,
                                                    (int16_t *)(pin + L.levels) + p.first_mb * 400, pin + L.mbinfo + p.first_mb * 32,
                                                    (int32_t *)(pin + L.resmap) + p.first_mb);
         });
@@ -270,6 +203,8 @@ int run_part(const std::vector<PartFile> &pf, const std::vector<ffhip_webp_frame
         return FFHIP_OK;
     }
     std::vector<ffhip_vp8_item> items;
+    std::vector<ffhip_size> display;
+    std::vector<uint8_t *> item_planes;
     for (int k = 0; k < nf; k++) {
         const PartFile &p = pf[(size_t)k];
         if (status[p.idx]) continue;
@@ -282,28 +217,33 @@ int run_part(const std::vector<PartFile> &pf, const std::vector<ffhip_webp_frame
         it.d_levels = (const int16_t *)(dev + L.levels) + p.first_mb * 400;
         it.d_mbinfo = dev + L.mbinfo + p.first_mb * 32;
         memcpy(it.quant, f.info.quant, sizeof(it.quant));
-        it.d_resmap = (const int32_t *)(dev + L.resmap) + p.first_mb;
+        it.d_resmap = lw ? nullptr : (const int32_t *)(dev + L.resmap) + p.first_mb; /* the libwebp rule's map is the identity */
         it.filter_type = f.info.filter_type;
         memcpy(it.filters, f.info.filters, sizeof(it.filters));
         it.d_bgra = d_bgra[p.idx];
         it.pitch = pitch[p.idx];
         items.push_back(it);
+        display.push_back({f.info.width, f.info.height});
+        if (planes)
+            for (int q = 0; q < 3; q++) item_planes.push_back(planes[3 * p.idx + q]);
     }
-    int rc = ffhip_vp8_decode_items(items.data(), (int)items.size(), stream);
+    /* (the mode records are this part's scratch: the libwebp rule's residual stage writes their byte [19]) */
+    int rc = vp8_decode_items_rule(items.data(), (int)items.size(), rule, lw ? display.data() : nullptr, planes ? item_planes.data() : nullptr, stream);
     const int src = ffhip_stream_sync(stream); /* the next part reuses the scratch */
     if (rc == FFHIP_OK && src < 0) rc = src;
     return rc;
 }
 
 int webp_files_impl(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch,
-                    ffhip_webp_info *info_out, ffhip_webp_parsed *outs, int *status, void *stream)
+                    ffhip_webp_info *info_out, ffhip_webp_parsed *outs, int *status, void *stream, int rule, uint8_t *const *planes)
 {
+    const bool lw = rule == WEBP_RULE_LIBWEBP;
     if (n_threads < 1) n_threads = 1;
     if (n_threads > 64) n_threads = 64;
     std::vector<ffhip_webp_frame> frames((size_t)n);
     ffhip_parallel_for(n, n_threads, [&](int i) {
         ffhip_webp_frame &f = frames[(size_t)i];
-        status[i] = files[i] && lens[i] ? ffhip_webp_read_header(files[i], lens[i], &f) : FFHIP_EINVAL;
+        status[i] = files[i] && lens[i] ? (lw ? ffhip_webp_read_header_libwebp : ffhip_webp_read_header)(files[i], lens[i], &f) : FFHIP_EINVAL;
         if (info_out) info_out[i] = f.info;
         if (status[i]) return;
         const int64_t n_mb = (int64_t)f.info.mbcols * f.info.mbrows;
@@ -313,6 +253,9 @@ int webp_files_impl(const uint8_t *const *files, const size_t *lens, int n, int 
             else o.info = f.info;
         } else if (!d_bgra[i] || ((uintptr_t)d_bgra[i] & 15) || pitch[i] < 64LL * f.info.mbcols || pitch[i] > 0x7fffffffLL ||
                    (pitch[i] & 15) || pitch[i] * 16 * f.info.mbrows > 0x7fffffffLL) { /* what ffhip_vp8_decode_items asks of an output */
+            status[i] = FFHIP_EINVAL;
+        } else if (planes && (!planes[3 * i] || !planes[3 * i + 1] || !planes[3 * i + 2] ||
+                              (((uintptr_t)planes[3 * i] | (uintptr_t)planes[3 * i + 1] | (uintptr_t)planes[3 * i + 2]) & 3))) {
             status[i] = FFHIP_EINVAL;
         }
     });
@@ -353,7 +296,7 @@ int webp_files_impl(const uint8_t *const *files, const size_t *lens, int n, int 
         if (pf.empty()) break;
         i = next;
         t_last_parts[on_device ? 0 : 1]++;
-        rc = run_part(pf, frames, files, lens, n_mb, cols_sum, file_bytes, on_device, n_threads, d_bgra, pitch, outs, status, stream);
+        rc = run_part(pf, frames, files, lens, n_mb, cols_sum, file_bytes, on_device, n_threads, d_bgra, pitch, outs, status, stream, rule, planes);
     }
     if (rc) return rc;
     for (int k = 0; k < n; k++)
@@ -368,14 +311,36 @@ extern "C" int ffhip_webp_decode_files_device(const uint8_t *const *files, const
 {
     if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    return webp_files_impl(files, lens, n, n_threads, d_bgra, pitch, info_out, nullptr, status, stream);
+    return webp_files_impl(files, lens, n, n_threads, d_bgra, pitch, info_out, nullptr, status, stream, WEBP_RULE_REFERENCE, nullptr);
+}
+
+extern "C" int ffhip_webp_decode_files_device_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                                 const int64_t *pitch, uint8_t *const *planes, unsigned flags, ffhip_webp_info *info_out, int *status,
+                                                 void *stream)
+{
+    if (flags & ~FFHIP_WEBP_PIXELS_LIBWEBP) return FFHIP_EINVAL;
+    const int rule = (flags & FFHIP_WEBP_PIXELS_LIBWEBP) ? WEBP_RULE_LIBWEBP : WEBP_RULE_REFERENCE;
+    if (planes && rule != WEBP_RULE_LIBWEBP) return FFHIP_EINVAL; /* the default rule's file call writes no planes */
+    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    return webp_files_impl(files, lens, n, n_threads, d_bgra, pitch, info_out, nullptr, status, stream, rule, planes);
 }
 
 extern "C" int ffhip_webp_parse_device(const uint8_t *const *files, const size_t *lens, int n, ffhip_webp_parsed *outs, int *status, void *stream)
 {
     if (n < 0 || (n > 0 && (!files || !lens || !outs || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    return webp_files_impl(files, lens, n, 1, nullptr, nullptr, nullptr, outs, status, stream);
+    return webp_files_impl(files, lens, n, 1, nullptr, nullptr, nullptr, outs, status, stream, WEBP_RULE_REFERENCE, nullptr);
+}
+
+extern "C" int ffhip_webp_parse_device_ex(const uint8_t *const *files, const size_t *lens, int n, unsigned flags, ffhip_webp_parsed *outs, int *status,
+                                          void *stream)
+{
+    if (flags & ~FFHIP_WEBP_PIXELS_LIBWEBP) return FFHIP_EINVAL;
+    if (n < 0 || (n > 0 && (!files || !lens || !outs || !status))) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    return webp_files_impl(files, lens, n, 1, nullptr, nullptr, nullptr, outs, status, stream,
+                           (flags & FFHIP_WEBP_PIXELS_LIBWEBP) ? WEBP_RULE_LIBWEBP : WEBP_RULE_REFERENCE, nullptr);
 }
 
 extern "C" int ffhip_debug_webp_last_parts(int out[2])

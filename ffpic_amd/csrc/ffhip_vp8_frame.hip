@@ -37,6 +37,7 @@
  */
 #include "ffhip_colorterms.h"
 #include "ffhip_vp8_filters.h"
+#include "ffhip_vp8_bool.h"
 
 #include <algorithm>
 #include <queue>
@@ -76,6 +77,7 @@ struct Vp8FrameArgs {
 #define SH_BYTES 768
 #define FR_OUT ((int)0x80000000u) /* a buffer offset outside everything: loads return 0, stores are dropped */
 
+#define FR_SPEC 0 /* the row text under the reference's rule; k_vp8_frames_items_libwebp includes it once more with 1 */
 #define FR_AUX_SC0 1 /* workgroup-scope loads of the lines (they hit the CU's L1 like plain loads: the producer is on this CU) */
 /* a B_PRED sub-block mode as the row reads it: k_vp8_frames takes it as it is (the host's check or k_vp8_check_modes refused the call
  * in front of it); k_vp8_frames_items clamps it (an item's host copy is checked, not its device copy: TT is never indexed beyond mode 9).
@@ -195,66 +197,25 @@ template <int TYPE, bool MAP>
 __global__ __launch_bounds__(1024) void k_vp8_frames_items(Vp8ItemsArgs ia)
 {
     constexpr bool PLANES = false;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    u32 *const TT = (u32 *)(smem + SH_TT);
-    u32 *const PROG = (u32 *)(smem + SH_PROG);
-    u32 *const ABORT = (u32 *)(smem + SH_ABORT);
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), NW = (int)(blockDim.x >> 6);
-    uint8_t *const AR = smem + SH_BYTES + w * AR_BYTES;
-    uint8_t *const FT = smem + SH_BYTES + NW * AR_BYTES + 32 * w; /* the wave's frame's filter parameters */
-    uint8_t *const BT = AR + AR_BT, *const T = BT, *const C0 = BT + BT_C0, *const C1 = BT + BT_C1;
-    short *const R = (short *)(AR + AR_R);
-    uint8_t *const TL = AR + AR_TL;
-    typedef __attribute__((address_space(3))) uint8_t lds_u8;
-    const unsigned bt = (unsigned)(unsigned long long)(lds_u8 *)BT, tl = (unsigned)(unsigned long long)(lds_u8 *)TL,
-                   tc0 = (unsigned)(unsigned long long)(lds_u8 *)(AR + AR_TC0), tc1 = (unsigned)(unsigned long long)(lds_u8 *)(AR + AR_TC1),
-                   dump = (unsigned)(unsigned long long)(lds_u8 *)(AR + AR_DUMP) + 4u * (unsigned)lane;
+#include "ffhip_vp8_frame_items.inc"
+}
 
-    if (w == 0) {
-        if (lane < 16) {
-            auto off = [](int k) { return k < 4 ? (3 - k) * PRS - 1 : (k == 4 ? -PRS - 1 : -PRS + (k - 5)); };
-#pragma unroll
-            for (int m = 0; m < 8; m++) {
-                const unsigned t = kVp8Taps[m][lane];
-                TT[(m + 2) * 16 + lane] = (u32)(off((int)(t & 15)) + 64) | ((u32)(off((int)((t >> 4) & 15)) + 64) << 8) | ((u32)(off((int)(t >> 8)) + 64) << 16);
-            }
-            const int r = lane >> 2, c = lane & 3;
-            TT[16 + lane] = (u32)(r * PRS - 1 + 64) | ((u32)(-PRS + c + 64) << 8) | ((u32)(-PRS - 1 + 64) << 16);
-            TT[lane] = 64u | (64u << 8) | (64u << 16);
-            PROG[lane] = 0u;
-        }
-        if (lane == 0) *ABORT = ia.ctrl[1];
-    }
-    if (lane < 12) T[(4 + 4 * (lane >> 2)) * PRS + 20 + (lane & 3)] = 127;
-    __syncthreads();
-    if (__hip_atomic_load(ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return;
-
-    const __amdgpu_buffer_rsrc_t rL = ffhip_rsrc(ia.lines + (long long)blockIdx.x * (long long)(ia.nslot + 1) * (long long)ia.slot_bytes,
-                                                 (unsigned)ia.nslot * ia.slot_bytes);
-    fr_cslot *const S = (fr_cslot *)ia.sched + ((fr_cu32 *)ia.wg_first)[blockIdx.x];
-    int e = 0;
-    for (int g = w;; g += NW) {
-        while (S[e].frame >= 0 && g >= S[e + 1].row0) e++;
-        const int fi = S[e].frame;
-        if (fi < 0) break;
-        fr_cdesc *const fd = (fr_cdesc *)ia.frames + fi;
-        Vp8FrameArgs a = {};
-        a.modes = fd->modes; a.residual = fd->residual; a.resmap = fd->resmap; a.bgra = fd->bgra;
-        a.lines = ia.lines; a.ctrl = ia.ctrl; a.async_err = ia.async_err;
-        a.res_stride = fd->res_stride; a.pitch = fd->pitch; a.mbcols = fd->mbcols; a.mbrows = fd->mbrows; a.n_images = 1;
-        a.nslot = ia.nslot; a.slot_bytes = ia.slot_bytes;
-        const long long img = 0;
-        const int y = g - S[e].row0;
-        const int ys = 16 * a.mbcols, us = 8 * a.mbcols, n_mb = a.mbcols * a.mbrows;
-        const int off_fu = 6 * ys, off_fv = 6 * ys + 4 * us, off_ul = 6 * ys + 8 * us, off_uu = off_ul + ys, off_uv = off_uu + us;
-        if (TYPE != 0 && lane < 24) FT[lane] = fd->filters[lane];
-#include "ffhip_vp8_frame_lanes.inc"
-        const bool real_row = y < a.mbrows;
-        const int wp = (w + NW - 1) % NW;
-        const u32 my_base = S[e].base0 + (u32)y * (u32)(a.mbcols + 2), up_base = y > 0 ? my_base - (u32)(a.mbcols + 2) : 0u;
-#include "ffhip_vp8_frame_row.inc"
-    }
+/* ---- WEBP_RULE_LIBWEBP: k_vp8_frames_items' text (ffhip_vp8_frame_items.inc) once more with FR_SPEC set.  Prediction by RFC 6386 (the 127 / 129 borders for
+ * 16x16 V_PRED and H_PRED too, so no row waits for the whole row above; the macroblock's above-right samples for sub-blocks 7, 11 and 15; the
+ * last sample above, four times, right of the last macroblock), the loop filter's inner edges by B_PRED or the record's byte [19], and the
+ * filtered PLANES as the only output: libwebp's upsampler reads the chroma row below a pixel row, which is final only after the next macroblock
+ * row has been filtered, so the colour step is k_vp8_upsample_color behind this kernel.  The planes of a frame lie behind each other at the
+ * descriptor's `bgra`: Y (256 B per macroblock), U, V (64 each).  Never a residual map.  The hand-counted wait in the row text counts, behind the
+ * fetch and the lines, three stores (luma, U | V) where the BGRA instances count one and k_vp8_frames' PLANES instances four. */
+template <int TYPE>
+__global__ __launch_bounds__(1024) void k_vp8_frames_items_libwebp(Vp8ItemsArgs ia)
+{
+    constexpr bool PLANES = true, MAP = false;
+#undef FR_SPEC
+#define FR_SPEC 1
+#include "ffhip_vp8_frame_items.inc"
+#undef FR_SPEC
+#define FR_SPEC 0
 }
 #undef FR_SUBMODE
 
@@ -416,8 +377,10 @@ extern "C" int ffhip_vp8_decode_frames(int mbcols, int mbrows, int n_images, con
 
 /* ---- ffhip_vp8_decode_items ---- */
 
-static const void *items_kernel(int ft, bool map)
+static const void *items_kernel(int ft, bool map, int rule)
 {
+    if (rule == WEBP_RULE_LIBWEBP)
+        return ft == 0 ? (const void *)k_vp8_frames_items_libwebp<0> : ft == 1 ? (const void *)k_vp8_frames_items_libwebp<1> : (const void *)k_vp8_frames_items_libwebp<2>;
 #define FRI_PICK(T, M) if (ft == T && map == M) return (const void *)k_vp8_frames_items<T, M>
     FRI_PICK(0, false); FRI_PICK(1, false); FRI_PICK(2, false); FRI_PICK(0, true); FRI_PICK(1, true); FRI_PICK(2, true);
 #undef FRI_PICK
@@ -428,7 +391,18 @@ static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *stream)
 {
-    if (n < 0 || (n > 0 && !items)) return FFHIP_EINVAL;
+    return vp8_decode_items_rule(items, n, WEBP_RULE_REFERENCE, nullptr, nullptr, stream);
+}
+
+extern "C" int ffhip_debug_vp8_decode_items_libwebp(const ffhip_vp8_item *items, int n, const ffhip_size *display, void *stream)
+{
+    return vp8_decode_items_rule(items, n, WEBP_RULE_LIBWEBP, display, nullptr, stream);
+}
+
+int vp8_decode_items_rule(const ffhip_vp8_item *items, int n, int rule, const ffhip_size *display, uint8_t *const *planes, void *stream)
+{
+    const bool lw = rule == WEBP_RULE_LIBWEBP;
+    if (n < 0 || (n > 0 && !items) || (lw && n > 0 && !display)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
     /* every item checked as ffhip_vp8_residual_batch + ffhip_vp8_decode_frames check a batch of one */
     long long total_mb = 0, lv_mb = 0, chk_recs = 0, bases = 0;
@@ -444,6 +418,13 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
         if (lv == (it.d_residual != nullptr)) return FFHIP_EINVAL; /* exactly one form of the residual */
         if (lv ? (!it.d_mbinfo || ((uintptr_t)it.d_levels & 15) || ((uintptr_t)it.d_mbinfo & 3)) : ((uintptr_t)it.d_residual & 3) != 0) return FFHIP_EINVAL;
         if ((uintptr_t)it.d_resmap & 3) return FFHIP_EINVAL;
+        if (lw) { /* levels only, no residual map, the picture inside its macroblock grid; delivered planes 4-byte aligned */
+            if (!lv || it.d_resmap || display[i].width < 1 || display[i].height < 1 || display[i].width > 16 * it.mbcols || display[i].height > 16 * it.mbrows)
+                return FFHIP_EINVAL;
+            if (planes && (!planes[3 * i] || !planes[3 * i + 1] || !planes[3 * i + 2] ||
+                           (((uintptr_t)planes[3 * i] | (uintptr_t)planes[3 * i + 1] | (uintptr_t)planes[3 * i + 2]) & 3)))
+                return FFHIP_EINVAL;
+        }
         total_mb += n_mb;
         bases += (long long)(it.mbrows + 1) * (it.mbcols + 2); /* the progress bases of a workgroup's share stay below this */
         if (total_mb > 0x3fffffffLL || bases > 0x7fff0000LL) return FFHIP_EINVAL;
@@ -485,7 +466,7 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
             L.nw = nw;
             L.lds = SH_BYTES + (size_t)nw * (AR_BYTES + 32);
             int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, items_kernel(ft, L.map), nw * 64, L.lds) != hipSuccess || per_cu < 1) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, items_kernel(ft, L.map, rule), nw * 64, L.lds) != hipSuccess || per_cu < 1) {
                 (void)hipGetLastError();
                 per_cu = 1;
             }
@@ -527,7 +508,7 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
     const size_t off_frames = at;
     at = align16(at + (size_t)n * sizeof(Vp8FrameDesc));
     const size_t off_res = at;
-    at = align16(at + (size_t)(n_lv + 1) * sizeof(Vp8ResItem));
+    at = align16(at + (size_t)(n_lv + 1) * (lw ? sizeof(Vp8LwResItem) : sizeof(Vp8ResItem)));
     const size_t off_chk = at;
     at = align16(at + (size_t)(n_chk + 1) * sizeof(Vp8CheckItem));
     for (Launch &L : launches) {
@@ -546,12 +527,19 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
     }
     uint8_t *dev_lines = (uint8_t *)ffhip_scratch(SCRATCH_VP8_ITEMS + 2, stream, lines_bytes / 4 + 4);
     if (!dev_lines) return FFHIP_ENOMEM;
+    uint8_t *dev_planes = nullptr; /* the libwebp rule: every frame's filtered planes, 384 B per macroblock, in stream scratch */
+    if (lw) {
+        dev_planes = (uint8_t *)ffhip_scratch(SCRATCH_VP8_LIBWEBP + 1, stream, (size_t)total_mb * 96 + 4);
+        if (!dev_planes) return FFHIP_ENOMEM;
+    }
+    std::vector<Vp8LwColorItem> colour;
     uint8_t *pin = ffhip_pinned_staging(SCRATCH_VP8_ITEMS, stream, blob);
     if (!pin) return FFHIP_ENOMEM;
     memset(pin, 0, blob);
     {
         Vp8FrameDesc *fd = (Vp8FrameDesc *)(pin + off_frames);
         Vp8ResItem *ri = (Vp8ResItem *)(pin + off_res);
+        Vp8LwResItem *rl = (Vp8LwResItem *)(pin + off_res);
         Vp8CheckItem *ci = (Vp8CheckItem *)(pin + off_chk);
         long long lv_at = 0, chk_at = 0;
         int k_lv = 0, k_chk = 0;
@@ -562,7 +550,17 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
             d.modes = it.d_modes; d.resmap = it.d_resmap; d.bgra = it.d_bgra;
             d.res_stride = n_mb * 384; d.pitch = (int)it.pitch; d.mbcols = it.mbcols; d.mbrows = it.mbrows;
             memcpy(d.filters, it.filters, 24);
-            if (it.d_levels) {
+            if (lw) {
+                Vp8LwResItem &r = rl[k_lv++];
+                r.levels = it.d_levels; r.info = it.d_mbinfo; r.out = dev_res + lv_at * 384; r.first = lv_at;
+                r.modes = const_cast<uint8_t *>(it.d_modes); /* byte [19] of every record is this call's to write */
+                memcpy(r.quant, it.quant, sizeof(r.quant));
+                d.residual = r.out;
+                uint8_t *pl = dev_planes + lv_at * 384;
+                d.bgra = pl; d.pitch = 0; /* the libwebp instances' planes stand where the BGRA instances have their picture */
+                colour.push_back({pl, pl + 256 * n_mb, pl + 320 * n_mb, 16 * it.mbcols, 8 * it.mbcols, display[i].width, display[i].height, it.d_bgra, (long long)it.pitch});
+                lv_at += n_mb;
+            } else if (it.d_levels) {
                 Vp8ResItem &r = ri[k_lv++];
                 r.levels = it.d_levels; r.info = it.d_mbinfo; r.out = dev_res + lv_at * 384; r.first = lv_at;
                 memcpy(r.quant, it.quant, sizeof(r.quant));
@@ -577,7 +575,8 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
                 chk_at += n_mb;
             }
         }
-        ri[n_lv].first = lv_mb;
+        if (lw) rl[n_lv].first = lv_mb;
+        else ri[n_lv].first = lv_mb;
         ci[n_chk].first = chk_recs;
         for (const Launch &L : launches) {
             memcpy(pin + L.wg_first_off, L.wg_first.data(), L.wg_first.size() * sizeof(u32));
@@ -591,7 +590,10 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
         const int rc = vp8_check_modes_items_enqueue((const Vp8CheckItem *)(dev_tab + off_chk), n_chk, chk_recs, ctrl, async_err, stream);
         if (rc) return rc;
     }
-    if (n_lv) {
+    if (lw) {
+        const int rc = vp8_libwebp_residual_items_enqueue((const Vp8LwResItem *)(dev_tab + off_res), n_lv, lv_mb, stream);
+        if (rc) return rc;
+    } else if (n_lv) {
         const int rc = vp8_residual_items_enqueue((const Vp8ResItem *)(dev_tab + off_res), n_lv, lv_mb, (uint32_t *)(dev_tab + blob), stream);
         if (rc) return rc;
     }
@@ -605,8 +607,20 @@ extern "C" int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *
         a.wg_first = (const u32 *)(dev_tab + L.wg_first_off);
         a.lines = dev_lines; a.ctrl = ctrl; a.async_err = async_err; a.nslot = L.nslot; a.slot_bytes = L.slot_bytes;
         void *kargs[] = {(void *)&a};
-        FFHIP_CHECK(hipLaunchKernel(items_kernel(L.ft, L.map), dim3((unsigned)L.grid), dim3((unsigned)L.nw * 64), kargs, L.lds, st), FFHIP_EIO);
+        FFHIP_CHECK(hipLaunchKernel(items_kernel(L.ft, L.map, rule), dim3((unsigned)L.grid), dim3((unsigned)L.nw * 64), kargs, L.lds, st), FFHIP_EIO);
         FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
+    }
+    if (lw) {
+        const int rc = vp8_libwebp_color_items(colour.data(), (int)colour.size(), stream);
+        if (rc) return rc;
+        if (planes)
+            for (int i = 0; i < n; i++) {
+                const size_t n_mb = (size_t)items[i].mbcols * items[i].mbrows;
+                const uint8_t *pl = colour[(size_t)i].y;
+                FFHIP_CHECK(hipMemcpyAsync(planes[3 * i], pl, 256 * n_mb, hipMemcpyDeviceToDevice, st), FFHIP_EIO);
+                FFHIP_CHECK(hipMemcpyAsync(planes[3 * i + 1], pl + 256 * n_mb, 64 * n_mb, hipMemcpyDeviceToDevice, st), FFHIP_EIO);
+                FFHIP_CHECK(hipMemcpyAsync(planes[3 * i + 2], pl + 320 * n_mb, 64 * n_mb, hipMemcpyDeviceToDevice, st), FFHIP_EIO);
+            }
     }
     return FFHIP_OK;
 }

@@ -55,7 +55,11 @@
                 f.mo = (u32)__builtin_amdgcn_raw_buffer_load_b32(rMo, (lane < 5 ? lane : 4) * 4, x1 * 20, 0);
                 /* the row above's last pixel for the raw H_PRED read at x = 0; the rest of that column is not reconstructed yet and reads 0 */
                 const int pbo = pb_off + x1 * pb_step;
+#if FR_SPEC /* WEBP_RULE_LIBWEBP: no raw read; instead the right-most macroblock's four above-right lanes take the last sample above it */
+                f.pb = (int)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(rL, lane >= 17 && lane <= 20 && x1 == a.mbcols - 1 ? off_ul + ys - 1 : pbo, up_off, FR_AUX_SC0);
+#else
                 f.pb = (int)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(rL, lane == 48 && x1 == 0 ? off_ul + ys - 1 : pbo, up_off, FR_AUX_SC0);
+#endif
             }
             f.lt = (u32)__builtin_amdgcn_raw_buffer_load_b32(rL, lt_off + x1 * lt_step, up_off, FR_AUX_SC0);
         };
@@ -86,11 +90,16 @@
 #pragma unroll
                 for (int i = 0; i < 5; i++) mo[i] = (u32)__builtin_amdgcn_readlane((int)f.mo, i);
                 const int ymode = (int)(mo[0] & 0xff);
+#if FR_SPEC
+                const bool raw = false; /* V_PRED and H_PRED take the 127 / 129 borders like the other modes */
+                (void)ymode;
+#else
                 const bool raw = ymode == 2 || ymode == 3;
+#endif
                 const int carry = (int)BT[carry_src]; /* the previous macroblock's right column (unfiltered: the filter works on its own tile) */
                 const unsigned long long none = 0ull;
                 *(u32x3 *)((char *)R + lane * 12) = u32x3{f.res[0], f.res[1], f.res[2]};
-                const unsigned long long m127 = (y == 0 ? (M_UTOP | M_VTOP | (raw ? none : M_LUMATOP)) : none) | ((!raw && x == a.mbcols - 1) ? M_TOPRIGHT : none);
+                const unsigned long long m127 = (y == 0 ? (M_UTOP | M_VTOP | (raw ? none : M_LUMATOP)) : none) | ((!FR_SPEC && !raw && x == a.mbcols - 1) ? M_TOPRIGHT : none); /* (FR_SPEC: below row 0 the fetch brought the last sample above) */
                 const unsigned long long m129 = (x == 0 ? (M_FIRST_CHROMA | (raw ? none : (M_FIRST_LUMA | M_LEFT))) : none) & ~m127;
                 int v = f.pb;
                 v = lane_select_smask(x != 0 ? M_LEFT : none, v, carry);
@@ -101,15 +110,21 @@
             }
             FLDS32(lt_dst) = f.lt;
             wave_sync();
+#if FR_SPEC /* above-right of sub-blocks 7, 11 and 15: the four samples above-right of the MACROBLOCK, where sub-block 3 gets them */
+            if (lane < 12) T[(4 + 4 * (lane >> 2)) * PRS + 20 + (lane & 3)] = T[20 + (lane & 3)];
+            wave_sync();
+#endif
         };
         const int ymode0 = real_row ? __builtin_amdgcn_readfirstlane((int)mrow[0]) : 0;
-        fetch(0, real_row ? res_row(0) : 0, (real_row && y > 0 && ymode0 == 3) ? (u32)a.mbcols : need_of(0));
+        fetch(0, real_row ? res_row(0) : 0, (!FR_SPEC && real_row && y > 0 && ymode0 == 3) ? (u32)a.mbcols : need_of(0));
         consume(0);
         {   /* the loop's state at its head, from here as from its own end: one fetch in flight, the stores of a macroblock behind it (these go nowhere) */
             const int x1 = 1 < a.mbcols ? 1 : a.mbcols - 1;
             fetch(x1, real_row ? res_row(x1) : 0, need_of(x1));
             __builtin_amdgcn_raw_buffer_store_b32(0u, rL, FR_OUT, me_off, 0);
+#if !FR_SPEC
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, rOut, FR_OUT, 0, 0);
+#endif
             if (PLANES) {
                 __builtin_amdgcn_raw_buffer_store_b32(0u, rY, FR_OUT, 0, 0);
                 if (lane < 16) __builtin_amdgcn_raw_buffer_store_b32(0u, rU, FR_OUT, 0, 0);
@@ -246,7 +261,13 @@
                     const uint8_t *fp = FT + ((((mo[4] >> 16) & 3) * 2) + (bpred ? 1 : 0)) * 3;
                     sub = __builtin_amdgcn_readfirstlane((int)fp[0]); inter = __builtin_amdgcn_readfirstlane((int)fp[1]);
                     hevt = __builtin_amdgcn_readfirstlane((int)fp[2]);
+                    /* FR_SPEC, both filter types: B_PRED, or some block has a non-zero dequantised coefficient (byte [19] of the record, left there
+                     * by the residual stage; mo[4] is fetched for the segment id anyway) */
+#if FR_SPEC
+                    inner = bpred || ((mo[4] >> 24) & 1u) != 0u;
+#else
                     inner = TYPE == 1 ? bpred : !bpred;
+#endif
                     if (sub) {
                         filter_phase<1, TYPE == 1 ? 1 : 2>(f_vbase, f_active, f_lum, x > 0, inner, sub, inter, hevt);
                         wave_sync();
@@ -263,14 +284,22 @@
             /* colour (utils/colorspace.c:291-329) in the packed form of the fused JPEG kernels: the three chroma terms of the lane's two
              * chroma samples at once (one fma + one add each, exact on 8-bit samples: tests/tools/check_color_fma.c), per pixel PAIR three
              * 16-bit adds, three saturating packs, three byte permutes; fp64 only where 215 uu + 381 vv is a non-zero multiple of 1000 */
+#if FR_SPEC /* planes only: the colour step is a kernel of its own */
+            (void)eu; (void)ev; (void)rOut; (void)em_dst;
+#else
             const u32x4 px = ff_packed420_row(ff_packed420_terms(eu, ev), el);
+#endif
             /* ---- the lines of macroblock x - 1 are complete, and the fetch of x + 1 has arrived, once all but this wave's NEWEST memory operations
              * have completed (they complete in issue order): the end of the previous iteration issued the fetch of x + 1 FIRST, then the lines of
              * x - 1, then -- last -- the block of x - 1 (and its planes).  Those last stores are a kilobyte on its way to HBM; nothing waits for them
              * here (as s_waitcnt vmcnt(0), with the fetch issued at the top of the iteration behind them, this wait was for their completion:
              * 41 % of the waves' cycles were waiting, profiles/r4_vp8_frames256_pmc.txt) ---- */
+#if FR_SPEC /* no block: behind the fetch and the lines come luma, U | V (two instructions), so all but the newest THREE */
+            asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+#else
             if (PLANES) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); /* block, luma, U | V (two instructions) */
             else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");        /* block */
+#endif
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0 && real_row) __hip_atomic_store(&PROG[w], my_base + (u32)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             /* ---- the tiles move on: their right ends become the left border, the fetched macroblock goes in ---- */
@@ -295,8 +324,10 @@
             }
             {
                 const unsigned long long em_ok = em_rows & (x == 0 ? cols_first : (x < a.mbcols ? ~0ull : ~cols_first));
+#if !FR_SPEC
                 const int dst = lane_select_smask(em_ok, FR_OUT, em_dst + y * 16 * a.pitch + x * 64);
                 __builtin_amdgcn_raw_buffer_store_b128(px, rOut, dst, 0, 0);
+#endif
                 if (PLANES) {
                     const int dsty = lane_select_smask(em_ok, FR_OUT, em_dsty + y * 16 * ys + x * 16);
                     __builtin_amdgcn_raw_buffer_store_b32(el, rY, dsty, 0, 0);

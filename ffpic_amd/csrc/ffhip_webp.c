@@ -16,21 +16,22 @@ static int is4(const uint8_t *p, const char *tag) { return memcmp(p, tag, 4) == 
 
 static int clamp127(int v) { return v < 0 ? 0 : v > 127 ? 127 : v; }
 
+/* RFC 6386 section 14.1 */
+static const uint16_t dc_q[128] = {
+    4,   5,   6,   7,   8,   9,   10,  10,  11,  12,  13,  14,  15,  16,  17,  17,  18,  19,  20,  20,  21,  21,  22,  22,  23,  23,
+    24,  25,  25,  26,  27,  28,  29,  30,  31,  32,  33,  34,  35,  36,  37,  37,  38,  39,  40,  41,  42,  43,  44,  45,  46,  46,
+    47,  48,  49,  50,  51,  52,  53,  54,  55,  56,  57,  58,  59,  60,  61,  62,  63,  64,  65,  66,  67,  68,  69,  70,  71,  72,
+    73,  74,  75,  76,  76,  77,  78,  79,  80,  81,  82,  83,  84,  85,  86,  87,  88,  89,  91,  93,  95,  96,  98,  100, 101, 102,
+    104, 106, 108, 110, 112, 114, 116, 118, 122, 124, 126, 128, 130, 132, 134, 136, 138, 140, 143, 145, 148, 151, 154, 157};
+static const uint16_t ac_q[128] = {
+    4,   5,   6,   7,   8,   9,   10,  11,  12,  13,  14,  15,  16,  17,  18,  19,  20,  21,  22,  23,  24,  25,  26,  27,  28,  29,
+    30,  31,  32,  33,  34,  35,  36,  37,  38,  39,  40,  41,  42,  43,  44,  45,  46,  47,  48,  49,  50,  51,  52,  53,  54,  55,
+    56,  57,  58,  60,  62,  64,  66,  68,  70,  72,  74,  76,  78,  80,  82,  84,  86,  88,  90,  92,  94,  96,  98,  100, 102, 104,
+    106, 108, 110, 112, 114, 116, 119, 122, 125, 128, 131, 134, 137, 140, 143, 146, 149, 152, 155, 158, 161, 164, 167, 170, 173, 177,
+    181, 185, 189, 193, 197, 201, 205, 209, 213, 217, 221, 225, 229, 234, 239, 245, 249, 254, 259, 264, 269, 274, 279, 284};
+
 int ffhip_vp8_dequant_factors(const ffhip_vp8_quant_header *h, uint16_t *out /* [4][8] */)
 {
-    /* RFC 6386 section 14.1 */
-    static const uint16_t dc_q[128] = {
-        4,   5,   6,   7,   8,   9,   10,  10,  11,  12,  13,  14,  15,  16,  17,  17,  18,  19,  20,  20,  21,  21,  22,  22,  23,  23,
-        24,  25,  25,  26,  27,  28,  29,  30,  31,  32,  33,  34,  35,  36,  37,  37,  38,  39,  40,  41,  42,  43,  44,  45,  46,  46,
-        47,  48,  49,  50,  51,  52,  53,  54,  55,  56,  57,  58,  59,  60,  61,  62,  63,  64,  65,  66,  67,  68,  69,  70,  71,  72,
-        73,  74,  75,  76,  76,  77,  78,  79,  80,  81,  82,  83,  84,  85,  86,  87,  88,  89,  91,  93,  95,  96,  98,  100, 101, 102,
-        104, 106, 108, 110, 112, 114, 116, 118, 122, 124, 126, 128, 130, 132, 134, 136, 138, 140, 143, 145, 148, 151, 154, 157};
-    static const uint16_t ac_q[128] = {
-        4,   5,   6,   7,   8,   9,   10,  11,  12,  13,  14,  15,  16,  17,  18,  19,  20,  21,  22,  23,  24,  25,  26,  27,  28,  29,
-        30,  31,  32,  33,  34,  35,  36,  37,  38,  39,  40,  41,  42,  43,  44,  45,  46,  47,  48,  49,  50,  51,  52,  53,  54,  55,
-        56,  57,  58,  60,  62,  64,  66,  68,  70,  72,  74,  76,  78,  80,  82,  84,  86,  88,  90,  92,  94,  96,  98,  100, 102, 104,
-        106, 108, 110, 112, 114, 116, 119, 122, 125, 128, 131, 134, 137, 140, 143, 146, 149, 152, 155, 158, 161, 164, 167, 170, 173, 177,
-        181, 185, 189, 193, 197, 201, 205, 209, 213, 217, 221, 225, 229, 234, 239, 245, 249, 254, 259, 264, 269, 274, 279, 284};
     if (!h || !out || h->y_ac_qi > 127) return FFHIP_EINVAL;
     memset(out, 0, 32 * sizeof(uint16_t));
     const int nseg = h->segmentation_enabled ? 4 : 1; /* webp.c:515: the other segments keep the zeros of the calloc'ed decoder */
@@ -53,9 +54,57 @@ int ffhip_vp8_dequant_factors(const ffhip_vp8_quant_header *h, uint16_t *out /* 
     return FFHIP_OK;
 }
 
+/* WEBP_RULE_LIBWEBP: RFC 6386 section 9.6 / 14.1 as libwebp derives the factors (`_quant` of tests/vp8_spec.py): segment_feature_mode says
+ * absolute or delta, every index and sum clamps to 0..127 as an int, all four segments are derived (without segmentation all from y_ac_qi),
+ * and the cap of 132 sits on the chroma DC factor. */
+static void quant_factors_libwebp(const ffhip_vp8_quant_header *h, int feature_mode, uint16_t *out /* [4][8] */)
+{
+    memset(out, 0, 32 * sizeof(uint16_t));
+    for (int i = 0; i < 4; i++) {
+        int q = h->y_ac_qi;
+        if (h->segmentation_enabled) q = feature_mode ? h->quantizer_update_value[i] : q + h->quantizer_update_value[i];
+        uint16_t *o = out + 8 * i;
+        o[0] = dc_q[clamp127(q + h->y_dc_delta)];
+        o[1] = ac_q[clamp127(q)];
+        o[2] = (uint16_t)(dc_q[clamp127(q + h->y2_dc_delta)] * 2);
+        o[3] = (uint16_t)(ac_q[clamp127(q + h->y2_ac_delta)] * 155 / 100);
+        o[4] = dc_q[clamp127(q + h->uv_dc_delta)];
+        o[5] = ac_q[clamp127(q + h->uv_ac_delta)];
+        if (o[3] < 8) o[3] = 8;
+        if (o[4] > 132) o[4] = 132;
+    }
+}
+
+/* WEBP_RULE_LIBWEBP: section 9.6 / 15.2 (`_filters` of tests/vp8_spec.py): all four segments, and ONE clamp, behind the deltas. */
+static void filter_params_libwebp(const ffhip_vp8_filter_header *h, uint8_t *filters /* [4][2][3] */, int *filter_type)
+{
+    const int ft = h->loop_filter_level == 0 ? 0 : (h->filter_type ? 1 : 2);
+    *filter_type = ft;
+    memset(filters, 0, 24);
+    if (!ft) return;
+    for (int s = 0; s < 4; s++)
+        for (int b = 0; b < 2; b++) {
+            int level = h->loop_filter_level;
+            if (h->segmentation_enabled) level = h->segment_feature_mode ? h->lf_update_value[s] : level + h->lf_update_value[s];
+            if (h->loop_filter_adj_enable) level += h->mode_ref_lf_delta0 + (b ? h->mb_mode_delta0 : 0);
+            level = level < 0 ? 0 : level > 63 ? 63 : level;
+            if (!level) continue;
+            int il = level;
+            if (h->sharpness_level) {
+                il >>= h->sharpness_level > 4 ? 2 : 1;
+                if (il > 9 - h->sharpness_level) il = 9 - h->sharpness_level;
+            }
+            if (il < 1) il = 1;
+            uint8_t *f = filters + (s * 2 + b) * 3;
+            f[0] = (uint8_t)(2 * level + il);
+            f[1] = (uint8_t)il;
+            f[2] = level >= 40 ? 2 : (level >= 15 ? 1 : 0);
+        }
+}
+
 /* The chunk walk.  *vp8 = offset of the `VP8 ` chunk header, canvas[2] = the VP8X canvas fields as the reference reads them
  * (READ_UINT24 of the stored bytes, without the format's "+ 1"), 0 when there is no VP8X chunk. */
-static int walk_chunks(const uint8_t *file, size_t len, size_t *vp8, uint32_t canvas[2])
+static inline int walk_chunks(const uint8_t *file, size_t len, size_t *vp8, uint32_t canvas[2], const int rule)
 {
     if (len < 12 || !is4(file, "RIFF") || !is4(file + 8, "WEBP")) return FFHIP_EINVAL;
     size_t pos = 12;
@@ -68,7 +117,7 @@ static int walk_chunks(const uint8_t *file, size_t len, size_t *vp8, uint32_t ca
             canvas[0] = rd24(c + 12);
             canvas[1] = rd24(c + 15);
             pos += 18;
-        } else if (is4(c, "ALPH")) { /* struct webp_alpha: 9 bytes, size field 1 (webp.c:2031-2039) */
+        } else if (rule != WEBP_RULE_LIBWEBP && is4(c, "ALPH")) { /* struct webp_alpha: 9 bytes, size field 1 (webp.c:2031-2039) */
             if (pos + 9 > len || rd32(c + 4) != 1) return FFHIP_EINVAL;
             pos += 9;
         } else if (is4(c, "VP8 ")) {
@@ -84,6 +133,7 @@ static int walk_chunks(const uint8_t *file, size_t len, size_t *vp8, uint32_t ca
             const uint32_t size = rd32(c + 4);
             if (size > len - pos - 8) return FFHIP_EINVAL;
             pos += 8 + (size_t)size;
+            if (rule == WEBP_RULE_LIBWEBP) pos += size & 1; /* the format's padding byte; an ALPH chunk of any size is walked over like this too */
         }
     }
     return FFHIP_EINVAL; /* no VP8 chunk */
@@ -103,8 +153,15 @@ static int read_frame_tag(const uint8_t *file, size_t len, size_t vp8, uint32_t 
     return FFHIP_OK;
 }
 
-static void fill_dims(ffhip_webp_info *info, int fw, int fh, const uint32_t canvas[2])
+static inline void fill_dims(ffhip_webp_info *info, int fw, int fh, const uint32_t canvas[2], const int rule)
 {
+    if (rule == WEBP_RULE_LIBWEBP) { /* the frame tag's sizes are the picture */
+        info->mbcols = (fw + 15) >> 4;
+        info->mbrows = (fh + 15) >> 4;
+        info->width = fw;
+        info->height = fh;
+        return;
+    }
     const int w4 = ((fw + 3) >> 2) << 2, h4 = ((fh + 3) >> 2) << 2; /* webp.c:1810-1813 */
     info->mbcols = (w4 + 15) >> 4;
     info->mbrows = (h4 + 15) >> 4;
@@ -112,18 +169,18 @@ static void fill_dims(ffhip_webp_info *info, int fw, int fh, const uint32_t canv
     info->height = canvas[1] ? (int)canvas[1] : h4;
 }
 
-int ffhip_webp_probe(const uint8_t *file, size_t len, int *width, int *height, int *mbcols, int *mbrows)
+static inline int webp_probe_rule(const uint8_t *file, size_t len, int *width, int *height, int *mbcols, int *mbrows, const int rule)
 {
     if (!file) return FFHIP_EINVAL;
     size_t vp8 = 0;
     uint32_t canvas[2], p0;
     int fw, fh;
-    int rc = walk_chunks(file, len, &vp8, canvas);
+    int rc = walk_chunks(file, len, &vp8, canvas, rule);
     if (rc) return rc;
     rc = read_frame_tag(file, len, vp8, &p0, &fw, &fh);
     if (rc) return rc;
     ffhip_webp_info info;
-    fill_dims(&info, fw, fh, canvas);
+    fill_dims(&info, fw, fh, canvas, rule);
     if (width) *width = info.width;
     if (height) *height = info.height;
     if (mbcols) *mbcols = info.mbcols;
@@ -131,7 +188,19 @@ int ffhip_webp_probe(const uint8_t *file, size_t len, int *width, int *height, i
     return FFHIP_OK;
 }
 
-int ffhip_webp_read_header(const uint8_t *file, size_t len, ffhip_webp_frame *f)
+int ffhip_webp_probe(const uint8_t *file, size_t len, int *width, int *height, int *mbcols, int *mbrows)
+{
+    return webp_probe_rule(file, len, width, height, mbcols, mbrows, WEBP_RULE_REFERENCE);
+}
+
+int ffhip_webp_probe_ex(const uint8_t *file, size_t len, unsigned flags, int *width, int *height, int *mbcols, int *mbrows)
+{
+    if (flags & ~FFHIP_WEBP_PIXELS_LIBWEBP) return FFHIP_EINVAL;
+    if (flags & FFHIP_WEBP_PIXELS_LIBWEBP) return webp_probe_rule(file, len, width, height, mbcols, mbrows, WEBP_RULE_LIBWEBP);
+    return webp_probe_rule(file, len, width, height, mbcols, mbrows, WEBP_RULE_REFERENCE);
+}
+
+static inline int webp_read_header_rule(const uint8_t *file, size_t len, ffhip_webp_frame *f, const int rule)
 {
     static const uint8_t update_probs[1056] = FFB_COEFF_UPDATE_PROBS;
     static const uint8_t default_probs[1056] = FFB_DEFAULT_COEFF_PROBS;
@@ -141,11 +210,11 @@ int ffhip_webp_read_header(const uint8_t *file, size_t len, ffhip_webp_frame *f)
     size_t vp8 = 0;
     uint32_t canvas[2], p0_size;
     int fw, fh;
-    int rc = walk_chunks(file, len, &vp8, canvas);
+    int rc = walk_chunks(file, len, &vp8, canvas, rule);
     if (rc) return rc;
     rc = read_frame_tag(file, len, vp8, &p0_size, &fw, &fh);
     if (rc) return rc;
-    fill_dims(&f->info, fw, fh, canvas);
+    fill_dims(&f->info, fw, fh, canvas, rule);
     const size_t p0_off = vp8 + 18;
     f->p0_off = (uint32_t)p0_off;
     f->p0_len = (uint32_t)(p0_size <= len - p0_off ? p0_size : len - p0_off);
@@ -160,7 +229,8 @@ int ffhip_webp_read_header(const uint8_t *file, size_t len, ffhip_webp_frame *f)
     memset(&qh, 0, sizeof qh);
     memset(&lh, 0, sizeof lh);
     const int seg_on = ffb_bit(&d, 128);
-    int update_map = 1; /* also when segmentation is off (webp.c:393) */
+    int update_map = rule == WEBP_RULE_LIBWEBP ? 0 : 1; /* the reference: also when segmentation is off (webp.c:393) */
+    if (rule == WEBP_RULE_LIBWEBP) f->mb.seg_prob[0] = f->mb.seg_prob[1] = f->mb.seg_prob[2] = 255; /* a tree probability the header does not set */
     if (seg_on) {
         update_map = ffb_bit(&d, 128);
         if (ffb_bit(&d, 128)) { /* update_segment_feature_data */
@@ -228,16 +298,26 @@ int ffhip_webp_read_header(const uint8_t *file, size_t len, ffhip_webp_frame *f)
     f->pos = d.pos;
     f->info.quant_header = qh;
     f->info.filter_header = lh;
+    int ftype = 0;
+    if (rule == WEBP_RULE_LIBWEBP) { /* segment_feature_mode travels in the filter header; the public structs stay as they are */
+        quant_factors_libwebp(&qh, lh.segment_feature_mode, &f->info.quant[0][0]);
+        filter_params_libwebp(&lh, &f->info.filters[0][0][0], &ftype);
+        f->info.filter_type = ftype;
+        return FFHIP_OK;
+    }
     rc = ffhip_vp8_dequant_factors(&qh, &f->info.quant[0][0]);
     if (rc) return rc;
-    int ftype = 0;
     rc = ffhip_vp8_filter_params(&lh, &f->info.filters[0][0][0], &ftype);
     if (rc) return rc;
     f->info.filter_type = ftype;
     return FFHIP_OK;
 }
 
-int ffhip_webp_parse_frame(const uint8_t *file, const ffhip_webp_frame *f, uint8_t *modes, int16_t *levels, uint8_t *mbinfo, int32_t *resmap)
+int ffhip_webp_read_header(const uint8_t *file, size_t len, ffhip_webp_frame *f) { return webp_read_header_rule(file, len, f, WEBP_RULE_REFERENCE); }
+int ffhip_webp_read_header_libwebp(const uint8_t *file, size_t len, ffhip_webp_frame *f) { return webp_read_header_rule(file, len, f, WEBP_RULE_LIBWEBP); }
+
+static inline int webp_parse_frame_rule(const uint8_t *file, const ffhip_webp_frame *f, uint8_t *modes, int16_t *levels, uint8_t *mbinfo, int32_t *resmap,
+                                        const int rule)
 {
     const int cols = f->info.mbcols, rows = f->info.mbrows, nparts = f->info.nbr_partitions;
     const size_t n_mb = (size_t)cols * rows;
@@ -266,13 +346,15 @@ int ffhip_webp_parse_frame(const uint8_t *file, const ffhip_webp_frame *f, uint8
             const int has_y2 = rec[0] != 4;
             uint32_t top9 = top[x];
             if (!skip) {
-                ffb_mb_tokens(bt, f->probs, has_y2, &top9, &left9, levels + mb * 400, info);
+                if (rule == WEBP_RULE_LIBWEBP) ffb_mb_tokens_libwebp(bt, f->probs, has_y2, &top9, &left9, levels + mb * 400, info);
+                else ffb_mb_tokens(bt, f->probs, has_y2, &top9, &left9, levels + mb * 400, info);
                 last_coded = (int32_t)mb;
                 resmap[mb] = (int32_t)mb;
             } else {
                 top9 = ffb_skip_ctx(top9, has_y2);
                 left9 = ffb_skip_ctx(left9, has_y2);
-                resmap[mb] = last_coded >= 0 ? last_coded : (int32_t)mb; /* none yet: its own row, all zeros (the reference reads an uninitialised array) */
+                /* WEBP_RULE_LIBWEBP: a skipped macroblock has a zero residual: its own row, which nothing was written to */
+                resmap[mb] = rule != WEBP_RULE_LIBWEBP && last_coded >= 0 ? last_coded : (int32_t)mb; /* none yet: its own row, all zeros (the reference reads an uninitialised array) */
             }
             top[x] = (uint16_t)top9;
             info[25] = (uint8_t)has_y2;
@@ -285,16 +367,30 @@ int ffhip_webp_parse_frame(const uint8_t *file, const ffhip_webp_frame *f, uint8
     return err ? FFHIP_EINVAL : FFHIP_OK; /* truncated: a partition was asked for a byte beyond its length */
 }
 
-int ffhip_webp_parse(const uint8_t *file, size_t len, ffhip_webp_parsed *out)
+int ffhip_webp_parse_frame(const uint8_t *file, const ffhip_webp_frame *f, uint8_t *modes, int16_t *levels, uint8_t *mbinfo, int32_t *resmap)
 {
+    return webp_parse_frame_rule(file, f, modes, levels, mbinfo, resmap, WEBP_RULE_REFERENCE);
+}
+int ffhip_webp_parse_frame_libwebp(const uint8_t *file, const ffhip_webp_frame *f, uint8_t *modes, int16_t *levels, uint8_t *mbinfo, int32_t *resmap)
+{
+    return webp_parse_frame_rule(file, f, modes, levels, mbinfo, resmap, WEBP_RULE_LIBWEBP);
+}
+
+int ffhip_webp_parse_ex(const uint8_t *file, size_t len, unsigned flags, ffhip_webp_parsed *out)
+{
+    if (flags & ~FFHIP_WEBP_PIXELS_LIBWEBP) return FFHIP_EINVAL;
     if (!file || !out || !out->modes || !out->levels || !out->mbinfo || !out->resmap) return FFHIP_EINVAL;
+    const int libwebp = (flags & FFHIP_WEBP_PIXELS_LIBWEBP) != 0;
     ffhip_webp_frame f;
-    const int rc = ffhip_webp_read_header(file, len, &f);
+    const int rc = libwebp ? ffhip_webp_read_header_libwebp(file, len, &f) : ffhip_webp_read_header(file, len, &f);
     if (rc) return rc;
     if (out->n_mb_cap < (int64_t)f.info.mbcols * f.info.mbrows) return FFHIP_EINVAL;
     out->info = f.info;
-    return ffhip_webp_parse_frame(file, &f, out->modes, out->levels, out->mbinfo, out->resmap);
+    return libwebp ? ffhip_webp_parse_frame_libwebp(file, &f, out->modes, out->levels, out->mbinfo, out->resmap)
+                   : ffhip_webp_parse_frame(file, &f, out->modes, out->levels, out->mbinfo, out->resmap);
 }
+
+int ffhip_webp_parse(const uint8_t *file, size_t len, ffhip_webp_parsed *out) { return ffhip_webp_parse_ex(file, len, 0u, out); }
 
 struct webp_job {
     const uint8_t *const *files;

@@ -24,6 +24,10 @@ extern "C" {
 int ffhip_webp_read_header(const uint8_t *file, size_t len, ffhip_webp_frame *out);
 /* the two macroblock loops on the host, behind ffhip_webp_read_header */
 int ffhip_webp_parse_frame(const uint8_t *file, const ffhip_webp_frame *f, uint8_t *modes, int16_t *levels, uint8_t *mbinfo, int32_t *resmap);
+/* the same two under WEBP_RULE_LIBWEBP (ffhip_vp8_bool.h): the frame tag's sizes, the padded chunk walk, segment ids only where they are coded,
+ * quantisers and filter parameters by RFC 6386, the identity residual map; info.quant / .filters hold the spec-derived values */
+int ffhip_webp_read_header_libwebp(const uint8_t *file, size_t len, ffhip_webp_frame *out);
+int ffhip_webp_parse_frame_libwebp(const uint8_t *file, const ffhip_webp_frame *f, uint8_t *modes, int16_t *levels, uint8_t *mbinfo, int32_t *resmap);
 #ifdef __cplusplus
 }
 #endif

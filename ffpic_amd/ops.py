@@ -733,13 +733,25 @@ def vp8_dequant_factors(y_ac_qi, deltas=(0, 0, 0, 0, 0), segmentation_enabled=0,
     return out
 
 
-def webp_probe(data):
+def webp_pixel_flags(pixels):
+    """pixels 'reference' | 'libwebp' -> the flags of the ffhip_webp_*_ex calls; anything else is a ValueError"""
+    if pixels not in ("reference", "libwebp"):
+        raise ValueError(f"pixels {pixels!r}: 'reference' or 'libwebp'")
+    return capi.FFHIP_WEBP_PIXELS_LIBWEBP if pixels == "libwebp" else 0
+
+
+def webp_probe(data, pixels="reference"):
     """ffhip_webp_probe: (width, height, mbcols, mbrows) of a lossy WebP file (bytes); the picture ffhip_webp_decode_files_device
-    writes is 16*mbcols x 16*mbrows, width x height of it is what the reference's loader reports."""
+    writes is 16*mbcols x 16*mbrows, width x height of it is what the reference's loader reports.
+    pixels='libwebp' (ffhip_webp_probe_ex with FFHIP_WEBP_PIXELS_LIBWEBP): the frame tag's width and height, and the macroblock grid of those."""
+    flags = webp_pixel_flags(pixels)
     L = capi.lib()
     v = [C.c_int() for _ in range(4)]
     buf = np.frombuffer(data, dtype=np.uint8)
-    capi.check(L.ffhip_webp_probe(buf.ctypes.data, buf.size, *[C.byref(x) for x in v]), "ffhip_webp_probe")
+    if flags:
+        capi.check(L.ffhip_webp_probe_ex(buf.ctypes.data, buf.size, flags, *[C.byref(x) for x in v]), "ffhip_webp_probe_ex")
+    else:
+        capi.check(L.ffhip_webp_probe(buf.ctypes.data, buf.size, *[C.byref(x) for x in v]), "ffhip_webp_probe")
     return tuple(x.value for x in v)
 
 
@@ -760,25 +772,30 @@ def _webp_result(p, arrs):
     return arrs
 
 
-def webp_parse(data):
+def webp_parse(data, pixels="reference"):
     """ffhip_webp_parse on the host: dict of modes [n_mb][20], levels [n_mb][25][16], mbinfo [n_mb][32], resmap [n_mb], quant [4][8],
-    filters [4][2][3], filter_type, the sizes and the header (`info`, a capi.WebpInfo)."""
+    filters [4][2][3], filter_type, the sizes and the header (`info`, a capi.WebpInfo).  pixels='libwebp': ffhip_webp_parse_ex under that
+    rule (RFC 6386 as libwebp parses it: tests/vp8_spec.py is the witness)."""
+    flags = webp_pixel_flags(pixels)
     L = capi.lib()
-    _, _, c, r = webp_probe(data)
+    _, _, c, r = webp_probe(data, pixels)
     p, arrs = _webp_parsed(c * r)
     buf = np.frombuffer(data, dtype=np.uint8)
-    capi.check(L.ffhip_webp_parse(buf.ctypes.data, buf.size, C.byref(p)), "ffhip_webp_parse")
+    if flags:
+        capi.check(L.ffhip_webp_parse_ex(buf.ctypes.data, buf.size, flags, C.byref(p)), "ffhip_webp_parse_ex")
+    else:
+        capi.check(L.ffhip_webp_parse(buf.ctypes.data, buf.size, C.byref(p)), "ffhip_webp_parse")
     return _webp_result(p, arrs)
 
 
-def _webp_parse_many(files, call):
+def _webp_parse_many(files, call, pixels="reference"):
     n = len(files)
     bufs, ptrs, lens = file_args(files)
     outs = (capi.WebpParsed * n)()
     keep = []
     for i, f in enumerate(files):
         try:
-            _, _, c, r = webp_probe(f)
+            _, _, c, r = webp_probe(f, pixels)
         except capi.FfhipError:
             c = r = 0
         p, arrs = _webp_parsed(max(c * r, 1))
@@ -797,27 +814,101 @@ def webp_parse_batch(files, n_threads=4):
     return _webp_parse_many(files, lambda ptrs, lens, n, outs, status: L.ffhip_webp_parse_batch(ptrs, lens, n, n_threads, outs, status))
 
 
-def webp_parse_device(files, stream=None):
-    """ffhip_webp_parse_device: the same arrays from the two device kernels (no host fall-back), for comparing the halves."""
+def webp_parse_device(files, stream=None, pixels="reference"):
+    """ffhip_webp_parse_device: the same arrays from the two device kernels (no host fall-back), for comparing the halves.
+    pixels='libwebp': ffhip_webp_parse_device_ex, the kernels' instances under that rule."""
+    flags = webp_pixel_flags(pixels)
     L = capi.require_device()
+    if flags:
+        return _webp_parse_many(files, lambda ptrs, lens, n, outs, status: L.ffhip_webp_parse_device_ex(ptrs, lens, n, flags, outs, status, stream), pixels)
     return _webp_parse_many(files, lambda ptrs, lens, n, outs, status: L.ffhip_webp_parse_device(ptrs, lens, n, outs, status, stream))
 
 
-def webp_decode_files_device(files, n_threads=8, stream=None, strict=True, crop=True):
+def webp_decode_files_device(files, n_threads=8, stream=None, strict=True, crop=True, pixels="reference", planes=False):
     """ffhip_webp_decode_files_device: lossy WebP files of any sizes (list of bytes) in one call.  Every picture gets its place in ONE
     device allocation, at a 16-byte-aligned offset with the pitch 64 x its macroblock columns.  Returns (infos, [host BGRA [h][w][4]
     cropped to the probe's width x height (crop=False: the decoded 16*mbrows x 16*mbcols)], device buffer); with strict=False a
-    failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows."""
+    failing file does not raise: its entry is None and a fourth element, the per-file status codes, follows.
+    pixels='libwebp': ffhip_webp_decode_files_device_ex with FFHIP_WEBP_PIXELS_LIBWEBP -- libwebp's pixels (PIL's, a browser's) instead of
+    the reference's; only the probe's width x height are written, so crop=False shows unwritten bytes beyond them.
+    planes=True (needs pixels='libwebp'): a last element follows, per file (y, u, v) -- the loop-filtered planes of its macroblock grid --
+    or None for a failing file."""
+    flags = webp_pixel_flags(pixels)
+    if planes and not flags:
+        raise ValueError("planes=True needs pixels='libwebp'")
+
+    grids = []
+
     def probe(i, f):
-        w, h, c, r = webp_probe(f)
+        try:
+            w, h, c, r = webp_probe(f, pixels)
+        except capi.FfhipError:
+            grids.append((0, 0))
+            raise
+        grids.append((c, r))
         return (64 * c, 16 * r, w, h) if crop else (64 * c, 16 * r, 16 * c, 16 * r)
 
     infos = (capi.WebpInfo * len(files))()
-    images, dout, status = _files_to_pictures(
-        files, probe, lambda L, ptrs, lens, n, outs, pitches, status: L.ffhip_webp_decode_files_device(
-            ptrs, lens, n, n_threads, outs, pitches, infos, status, stream), "ffhip_webp_decode_files_device", strict,
-        own_failure=lambda rc: rc not in (0, capi.FFHIP_EINVAL) and rc > -1000)
-    return (list(infos), images, dout) if strict else (list(infos), images, dout, status)
+    pl = {}
+
+    def call(L, ptrs, lens, n, outs, pitches, status):
+        if not flags:
+            return L.ffhip_webp_decode_files_device(ptrs, lens, n, n_threads, outs, pitches, infos, status, stream)
+        triples = None
+        if planes:
+            offs, total = [], 0
+            for c, r in grids:
+                offs.append(total)
+                total += 384 * c * r
+            pl["buf"], pl["offs"] = DeviceBuffer(nbytes=max(total, 16)), offs
+            triples = (C.c_void_p * (3 * max(n, 1)))()
+            for i, (c, r) in enumerate(grids):
+                base = pl["buf"].ptr + offs[i]
+                triples[3 * i], triples[3 * i + 1], triples[3 * i + 2] = base, base + 256 * c * r, base + 320 * c * r
+        return L.ffhip_webp_decode_files_device_ex(ptrs, lens, n, n_threads, outs, pitches, triples, flags, infos, status, stream)
+
+    images, dout, status = _files_to_pictures(files, probe, call, "ffhip_webp_decode_files_device" + ("_ex" if flags else ""), strict,
+                                              own_failure=lambda rc: rc not in (0, capi.FFHIP_EINVAL) and rc > -1000)
+    out = (list(infos), images, dout) if strict else (list(infos), images, dout, status)
+    if planes:
+        flat = pl["buf"].to_host((pl["buf"].nbytes,), np.uint8) if "buf" in pl else None
+        res = []
+        for i, (c, r) in enumerate(grids):
+            if status[i] or not c:
+                res.append(None)
+                continue
+            o = pl["offs"][i]
+            res.append((flat[o:o + 256 * c * r].reshape(16 * r, 16 * c).copy(), flat[o + 256 * c * r:o + 320 * c * r].reshape(8 * r, 8 * c).copy(),
+                        flat[o + 320 * c * r:o + 384 * c * r].reshape(8 * r, 8 * c).copy()))
+        out = out + (res,)
+    return out
+
+
+def vp8_libwebp_residual_mb(levels, has_y2, factors):
+    """ffhip_vp8_libwebp_residual_mb (host, no device): one macroblock's levels [25][16], has_y2 and its six factors y1_dc, y1_ac, y2_dc,
+    y2_ac, uv_dc, uv_ac -> (residual int16 [24][16], whether some block has a non-zero dequantised coefficient): the residual stage of
+    pixels='libwebp' as the kernel compiles it."""
+    lv = np.ascontiguousarray(levels, np.int16).reshape(25, 16)
+    q = np.ascontiguousarray(np.asarray(factors).reshape(-1)[:6], np.uint16)
+    res = np.zeros((24, 16), np.int16)
+    nz = C.c_int()
+    capi.check(capi.lib().ffhip_vp8_libwebp_residual_mb(lv.ctypes.data, int(bool(has_y2)), q.ctypes.data, res.ctypes.data, C.byref(nz)),
+               "ffhip_vp8_libwebp_residual_mb")
+    return res, bool(nz.value)
+
+
+def webp_libwebp_color(y, u, v, pitch=None):
+    """ffhip_webp_libwebp_color (host, no device): planes y [h][w], u / v [(h + 1) / 2][(w + 1) / 2] -> BGRA [h][w][4] by libwebp's fancy
+    upsampler and colour step, as k_vp8_upsample_color compiles them."""
+    y, u, v = (np.ascontiguousarray(p, np.uint8) for p in (y, u, v))
+    h, w = y.shape
+    if u.shape != ((h + 1) // 2, (w + 1) // 2) or v.shape != u.shape:
+        raise ValueError(f"chroma planes {u.shape}, {v.shape} for a {w} x {h} picture")
+    pitch = 4 * w if pitch is None else pitch
+    out = np.zeros((h, pitch), np.uint8)
+    capi.check(capi.lib().ffhip_webp_libwebp_color(y.ctypes.data, w, u.ctypes.data, v.ctypes.data, u.shape[1], w, h, out.ctypes.data, pitch),
+               "ffhip_webp_libwebp_color")
+    return out[:, :4 * w].reshape(h, w, 4)
 
 
 def webp_last_parts():

@@ -167,6 +167,15 @@ def entry_point(codec, oriented=False, den=1, targets=False, progressive=False, 
     return f"ffhip_{codec}_decode_files_tensor" + ("_resized" if targets else "")
 
 
+def webp_entry_point(pixels="reference", oriented=False, targets=False):
+    """The C entry a WebP files-to-tensors call goes through under a pixel rule: 'reference' is entry_point('webp', ...); 'libwebp' has ONE
+    entry for every combination, ffhip_webp_decode_files_tensor_ex (its tail: _WEBP_EX_TAIL).  Anything else is a ValueError."""
+    return "ffhip_webp_decode_files_tensor_ex" if ops.webp_pixel_flags(pixels) else entry_point("webp", oriented, 1, targets)
+
+
+_WEBP_EX_TAIL = ("resize", "orient", "flags")                    # of ffhip_webp_decode_files_tensor_ex: beside the table, not in it
+
+
 # what each entry takes between the rectangles and its last three arguments (geom_out / info_out, status, stream)
 _ENTRY_TAILS = {
     "ffhip_jpeg_decode_files_tensor": (), "ffhip_webp_decode_files_tensor": (),
@@ -178,13 +187,14 @@ _ENTRY_TAILS = {
 
 
 def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias, apply_exif_orientation,
-                       orientation, return_orientation, reduce=1, return_reduce=False, progressive=False, flags=0):
+                       orientation, return_orientation, reduce=1, return_reduce=False, progressive=False, flags=0, pixels="reference"):
     fmt = tensor_format(dtype, layout, order, mean, std)
     targets = _sizes(size, len(files))                            # argument errors come before any device use
     den = _reduce(reduce, size)
     imposed = _orientations(orientation, len(files))
     oriented = bool(apply_exif_orientation) or imposed is not None
-    what = entry_point(codec.name, oriented, den, bool(targets), progressive, flags)
+    webp_ex = codec.name == "webp" and pixels == "libwebp"        # the ninth entry: flags = FFHIP_WEBP_PIXELS_LIBWEBP
+    what = webp_entry_point(pixels, oriented, bool(targets)) if webp_ex else entry_point(codec.name, oriented, den, bool(targets), progressive, flags)
     probe = codec.probe_progressive if progressive else codec.probe
     import torch
     tdtype = getattr(torch, _dtype_name(dtype))
@@ -235,9 +245,9 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
         "resize": ((capi.Size * max(n, 1))(*[capi.Size(w, h) for h, w in targets]) if targets else None, _filter(antialias)),
         "denom": (ints(*([den] * max(n, 1))), used),
         "orient": (ints(*[(max(t, 1) if imposed else 0) if oriented else 1 for t in turns]), used_turn),
-        "flags": (flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0),),
+        "flags": (capi.FFHIP_WEBP_PIXELS_LIBWEBP if webp_ex else flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0),),
     }
-    tail = sum((tails[part] for part in _ENTRY_TAILS[what]), ())
+    tail = sum((tails[part] for part in (_WEBP_EX_TAIL if webp_ex else _ENTRY_TAILS[what])), ())
     rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, *tail, None, status, torch.cuda.current_stream().cuda_stream)
     if oriented:
         turns = list(used_turn)[:n]
@@ -273,6 +283,7 @@ def _webp_size(f):
 _Codec = namedtuple("_Codec", "name probe probe_progressive tag")
 _JPEG = _Codec("jpeg", _jpeg_size, _jpeg_size_any, ops.jpeg_exif_orientation)
 _WEBP = _Codec("webp", _webp_size, None, ops.webp_exif_orientation)
+_WEBP_LIBWEBP = _Codec("webp", lambda f: ops.webp_probe(f, "libwebp")[:2], None, ops.webp_exif_orientation)
 
 
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
@@ -321,11 +332,16 @@ def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
 
 
 def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                           strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False):
+                           strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False,
+                           pixels="reference"):
     """ffhip_webp_decode_files_tensor (with size: ffhip_webp_decode_files_tensor_resized; with apply_exif_orientation or orientation:
     ffhip_webp_decode_files_tensor_oriented, the tag read from the file's EXIF chunk): lossy WebP files; arguments and result as
     decode_jpeg_to_tensors.  A file's display size is the
-    probe's width x height as far as the decoded picture holds it."""
-    return _decode_to_tensors(_WEBP, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+    probe's width x height as far as the decoded picture holds it.
+      pixels   'reference': the reference decoder's pixels, as ever.  'libwebp': what libwebp -- PIL, torchvision, a browser -- makes of the
+               same file, sample for sample (ffhip_webp_decode_files_tensor_ex with FFHIP_WEBP_PIXELS_LIBWEBP): the picture is the frame
+               tag's width x height, and roi, size and orientation act on it.  Anything else: ValueError"""
+    ops.webp_pixel_flags(pixels)
+    return _decode_to_tensors(_WEBP_LIBWEBP if pixels == "libwebp" else _WEBP, files, pixels=pixels, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)

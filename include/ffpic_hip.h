@@ -581,6 +581,67 @@ int ffhip_webp_decode_files_device(const uint8_t *const *files, const size_t *le
  * kernels (out[0]) and to the host threads (out[1]). */
 int ffhip_debug_webp_last_parts(int out[2]);
 
+/* ---- lossy WebP, the second pixel rule: the pixels libwebp gives (opt-in) ----
+ * The calls above give the reference's WEBP_load bit for bit, which is not what libwebp, PIL, torchvision or a browser show (DESIGN.md
+ * 4.19: twenty named deviations from RFC 6386, one in five valid files refused).  With FFHIP_WEBP_PIXELS_LIBWEBP in `flags` the _ex calls
+ * below decode RFC 6386 as libwebp does, sample for sample, and finish with libwebp's fancy upsampler and colour step:
+ *   - RIFF chunks are walked with the padding byte of an odd-sized one; the picture is the frame tag's 14-bit width x height, and
+ *     mbcols = (width + 15) >> 4, mbrows likewise: 50 x 37 stays 50 x 37 (the default rule says 52 x 40);
+ *   - a segment id is read only when segmentation and the map update are on, an unset tree probability is 255, cat6 extra bits are not
+ *     wrapped, a skipped macroblock has a zero residual (resmap is the identity);
+ *   - quantisers: segment_feature_mode says absolute or delta, a negative index clamps to 0, the cap of 132 sits on the chroma DC factor;
+ *     filter parameters: all four segments, one clamp behind the deltas.  ffhip_webp_info.quant and .filters hold these values; the two
+ *     header structs are filled as ever (update_mb_segmentation_map is the bit of the stream, 0 without segmentation);
+ *   - residual: the int16 store of level x quantiser and of the Y2-derived DC stay (libwebp has them too), the first IDCT pass is plain
+ *     int, every block with a non-zero coefficient goes through the IDCT;
+ *   - prediction: 16x16 V_PRED / H_PRED take the 127 / 129 borders like every other mode; B_PRED sub-blocks 7, 11 and 15 take the four
+ *     samples above-right of the MACROBLOCK; the right-most macroblock takes the last sample above it four times (127 in row 0);
+ *   - loop filter, both types: inner edges for B_PRED macroblocks and for those with a non-zero dequantised coefficient;
+ *   - colour: libwebp's fancy upsampler (9-3-3-1 on the chroma samples around a pixel) and its 14-bit fixed-point YUV -> RGB, with the
+ *     edges taken at the DISPLAY width and height; the alpha byte is 255, as the default rule writes it.
+ * Where the first IDCT pass leaves 16 bits there is no single libwebp picture: its C transform keeps int, its SIMD transforms saturate or
+ * wrap at 16 bits.  The rule follows the witness, tests/vp8_spec.py with rules=SPEC, i.e. the C transform; no encoder
+ * writes such a stream.  A file with an `ALPH` chunk decodes its colour; the alpha plane is ignored.
+ * The verdicts stay: FFHIP_EWEBP_LOSSLESS / _ANIMATION / _INTER_FRAME, and FFHIP_EINVAL for a partition asked for a byte beyond its length
+ * (under the rule no valid file of the libwebp corpus, tests/golden/webp_libwebp.npz, gets it).
+ * flags == 0 is the plain call, bit for bit; any other bit is FFHIP_EINVAL.  Argument errors come before FFHIP_ENODEV, both before the first
+ * allocation; FFHIP_WEBP_GPU_ENTROPY, FFHIP_WEBP_PACK, FFHIP_WEBP_PART_MB and FFHIP_WEBP_GPU_MIN_FILES act as in the plain calls. */
+#define FFHIP_WEBP_PIXELS_LIBWEBP 0x10u
+/* host only */
+int ffhip_webp_probe_ex(const uint8_t *file, size_t len, unsigned flags, int *width, int *height, int *mbcols, int *mbrows);
+int ffhip_webp_parse_ex(const uint8_t *file, size_t len, unsigned flags, ffhip_webp_parsed *out);
+/* the device twin of ffhip_webp_parse_ex (as ffhip_webp_parse_device is ffhip_webp_parse's) */
+int ffhip_webp_parse_device_ex(const uint8_t *const *files, const size_t *lens, int n, unsigned flags, ffhip_webp_parsed *outs, int *status,
+                               void *stream);
+/* ffhip_webp_decode_files_device under `flags`.  Buffers as there, with the _ex probe's mbcols and mbrows (pitch >= 64*mbcols, room for
+ * 16*mbrows rows), so a caller switches rules without new arithmetic; under the rule only `height` rows of `width` pixels are written.
+ * planes: NULL, or [n] triples of device pointers y, u, v (16*mbcols x 16*mbrows and 8*mbcols x 8*mbrows samples, strides 16*mbcols and
+ * 8*mbcols, 4-byte aligned): the loop-filtered planes of each file's macroblock grid are delivered too, which lets a caller name the plane and
+ * macroblock at which a decode differs.  planes with flags == 0 is FFHIP_EINVAL.  Under the rule the back half is three launches per part and
+ * filter type: the residual instance (which also leaves, in byte [19] of each mode record of the call's scratch, whether the macroblock has a
+ * non-zero dequantised coefficient), k_vp8_frames_items' libwebp instances, which write planes and no pixels, and k_vp8_upsample_color:
+ * libwebp's upsampler reads the chroma row BELOW a pixel row, which is final only once the next macroblock row has been filtered. */
+int ffhip_webp_decode_files_device_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                      const int64_t *pitch, uint8_t *const *planes, unsigned flags, ffhip_webp_info *info_out, int *status,
+                                      void *stream);
+/* Host only, no device needed: the arithmetic the kernels compile (ffhip_vp8_libwebp_body.h).
+ * ffhip_vp8_libwebp_residual_mb: one macroblock's levels [25][16] (raster positions; 16 Y, 4 U, 4 V, Y2), has_y2, and its six factors
+ * y1_dc, y1_ac, y2_dc, y2_ac, uv_dc, uv_ac -> residual [24][16] and *any_nz: some block has a non-zero dequantised coefficient.
+ * ffhip_webp_libwebp_color: planes y (stride ys) and u, v (stride uvs; (width + 1) / 2 x (height + 1) / 2 samples) -> width x height BGRA
+ * pixels, `pitch` bytes a row, alpha 255. */
+int ffhip_vp8_libwebp_residual_mb(const int16_t *levels, int has_y2, const uint16_t *factors, int16_t *residual, int *any_nz);
+int ffhip_webp_libwebp_color(const uint8_t *y, int64_t ys, const uint8_t *u, const uint8_t *v, int64_t uvs, int width, int height,
+                             uint8_t *bgra, int64_t pitch);
+/* Diagnostics (tests/tools/bench_webp_pixels.py measures the rule's back half and its colour kernel alone with them; both only enqueue):
+ * ffhip_vp8_decode_items under the libwebp rule -- levels items without a residual map, display[i] the picture's size inside its macroblock
+ * grid; the call WRITES byte [19] of every record of d_modes -- and k_vp8_upsample_color on planes laid out as ffhip_yuv420_to_bgra takes
+ * them (4-byte aligned, strides multiples of 4). */
+struct ffhip_size; /* (defined with the resize calls below) */
+int ffhip_debug_vp8_decode_items_libwebp(const ffhip_vp8_item *items, int n, const struct ffhip_size *display, void *stream);
+int ffhip_debug_vp8_upsample_color(const uint8_t *d_y, const uint8_t *d_u, const uint8_t *d_v, int ys, int uvs, int width, int height,
+                                   int n_images, int64_t plane_stride_y, int64_t plane_stride_uv, uint8_t *d_bgra, int64_t pitch,
+                                   int64_t image_stride, void *stream);
+
 /* ---- HEVC intra prediction + reconstruction for a list of transform units ----
  * decode_intra_block steps 5-10 (coding/hevc.c:4730-4790) for every TU of a picture:
  * intra_sample_prediction (hevc.c:4542-4662: neighbour gathering, reference_sample_substitution
@@ -1048,6 +1109,12 @@ int ffhip_jpeg_decode_files_tensor_oriented(const uint8_t *const *files, const s
                                             const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                             const int *denom, int *denom_out, const int *orient, int *orient_out, ffhip_jpeg_geom *geom_out,
                                             int *status, void *stream);
+/* ffhip_webp_decode_files_tensor_oriented with `flags` (0, or FFHIP_WEBP_PIXELS_LIBWEBP: any other bit is FFHIP_EINVAL): the files are probed and
+ * decoded under that rule, and the region, resize and orientation stages act on the picture it gives -- under the libwebp rule the frame tag's
+ * width x height.  flags == 0 gives the bytes of ffhip_webp_decode_files_tensor_oriented. */
+int ffhip_webp_decode_files_tensor_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                      const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                      const int *orient, int *orient_out, unsigned flags, ffhip_webp_info *info_out, int *status, void *stream);
 int ffhip_webp_decode_files_tensor_oriented(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                             const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                             const int *orient, int *orient_out, ffhip_webp_info *info_out, int *status, void *stream);
