@@ -40,6 +40,8 @@ EXPORTS = [
     "ffhip_jpeg_probe_any", "ffhip_jpeg_progressive_decode", "ffhip_jpeg_progressive_batch_gpu", "ffhip_jpeg_decode_files_mixed_device_ex",
     "ffhip_debug_progressive_last", "ffhip_jpeg_decode_files_tensor_ex",
     "ffhip_jpeg_libjpeg_block", "ffhip_jpeg_libjpeg_picture", "ffhip_jpeg_recon_items_libjpeg",
+    "ffhip_inflate", "ffhip_png_probe", "ffhip_png_picture", "ffhip_png_exif_orientation", "ffhip_png_decode_files_device",
+    "ffhip_png_decode_files_tensor", "ffhip_debug_png_last", "ffhip_debug_png_times",
 ]
 
 
@@ -91,6 +93,13 @@ class WebpInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("mbcols", C.c_int32), ("mbrows", C.c_int32), ("filter_type", C.c_int32),
                 ("nbr_partitions", C.c_int32), ("quant", (C.c_uint16 * 8) * 4), ("filters", C.c_uint8 * 24),
                 ("quant_header", Vp8QuantHeader), ("filter_header", Vp8FilterHeader)]
+
+
+class PngInfo(C.Structure):
+    """ffhip_png_info"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32), ("color_type", C.c_int32), ("interlace", C.c_int32),
+                ("has_trns", C.c_int32), ("palette_size", C.c_int32), ("n_passes", C.c_int32), ("filtered_bytes", C.c_uint64),
+                ("pass_rows", C.c_int32 * 7), ("pass_row_bytes", C.c_int32 * 7)]
 
 
 class WebpParsed(C.Structure):
@@ -367,6 +376,15 @@ def lib():
     L.ffhip_jpeg_libjpeg_block.argtypes = [vp, vp, vp]
     L.ffhip_jpeg_libjpeg_picture.argtypes = [C.POINTER(JpegGeom), ci, ci, vp, vp, vp, vp, vp, C.c_int64]
     L.ffhip_jpeg_recon_items_libjpeg.argtypes = [C.POINTER(JpegItem), C.POINTER(Size), ci, vp]
+    L.ffhip_inflate.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
+    L.ffhip_png_probe.argtypes = [vp, sz, C.POINTER(PngInfo)]
+    L.ffhip_png_picture.argtypes = [vp, sz, vp, i64]
+    L.ffhip_png_exif_orientation.argtypes = [vp, sz, C.POINTER(ci)]
+    L.ffhip_png_decode_files_device.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(PngInfo), vp, vp]
+    L.ffhip_png_decode_files_tensor.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.c_uint, C.POINTER(PngInfo), vp, vp]
+    L.ffhip_debug_png_last.argtypes = [C.POINTER(ci)]
+    L.ffhip_debug_png_times.argtypes = [C.POINTER(C.c_double)]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

@@ -1,5 +1,5 @@
 /*
- * ffhip_exif.c -- the EXIF orientation tag of a JPEG or WebP file, and the host side of the eight orientations: sizes, rectangles,
+ * ffhip_exif.c -- the EXIF orientation tag of a JPEG, WebP or PNG file, and the host side of the eight orientations: sizes, rectangles,
  * inverses (include/ffpic_hip.h, "EXIF orientation").  Plain C11, no HIP.
  *
  * The reference skips APP1 (format/jpg.c:836-840) and does not look at the WebP `EXIF` chunk, and so do the decoders here: these
@@ -7,6 +7,7 @@
  * layout:
  *   JPEG   SOI, marker segments; APP1 (FFE1) with payload "Exif\0\0" + TIFF
  *   WebP   "RIFF" size "WEBP", chunks (tag, 32-bit little-endian size, payload, a padding byte behind an odd size); `EXIF` = TIFF
+ *   PNG    the signature, chunks (32-bit big-endian length, type, payload, CRC); the first `eXIf` = TIFF
  *   TIFF   "II*\0" (little-endian) or "MM\0*" (big-endian), the 32-bit offset of IFD0 from the header's first byte; IFD0 = a 16-bit entry
  *          count and that many 12-byte entries: tag (16), type (16), count (32), value or offset (32, a value shorter than that left-aligned)
  * Every read is checked against the end of its segment or chunk, which is checked against the end of the file; every loop moves forward
@@ -90,6 +91,24 @@ int ffhip_webp_exif_orientation(const uint8_t *file, size_t len, int *orientatio
         const size_t step = 8 + size + (size & 1);
         if (step > len - p) return FFHIP_OK; /* the padding byte is missing: the last chunk */
         p += step;
+    }
+    return FFHIP_OK;
+}
+
+int ffhip_png_exif_orientation(const uint8_t *file, size_t len, int *orientation)
+{
+    if (!file || !orientation) return FFHIP_EINVAL;
+    *orientation = 1;
+    if (len < 8 || memcmp(file, "\x89PNG\r\n\x1a\n", 8) != 0) return FFHIP_OK;
+    size_t p = 8;
+    while (len - p >= 12) { /* length, type, payload, CRC: walked by the lengths; eXIf may stand behind the picture */
+        const size_t size = tiff32(file + p, 1);
+        if (size > len - p - 12) return FFHIP_OK;
+        if (memcmp(file + p + 4, "eXIf", 4) == 0) {
+            *orientation = tiff_orientation(file + p + 8, size);
+            return FFHIP_OK;
+        }
+        p += size + 12;
     }
     return FFHIP_OK;
 }

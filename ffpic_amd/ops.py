@@ -916,3 +916,71 @@ def webp_last_parts():
     out = (C.c_int * 2)()
     capi.check(capi.lib().ffhip_debug_webp_last_parts(out), "ffhip_debug_webp_last_parts")
     return out[0], out[1]
+
+
+def inflate(data, cap):
+    """ffhip_inflate (host, no device): a zlib-wrapped deflate stream (bytes) into at most cap bytes -> bytes.  Everything the library
+    refuses -- a bad header or check value, a stream that ends early, code lengths no tree has, output beyond cap -- is FfhipError (FFHIP_EINVAL)."""
+    src = np.frombuffer(data, dtype=np.uint8)
+    dst = np.zeros(max(int(cap), 1), np.uint8)
+    got = C.c_size_t()
+    capi.check(capi.lib().ffhip_inflate(src.ctypes.data if src.size else None, src.size, dst.ctypes.data, int(cap), C.byref(got)), "ffhip_inflate")
+    return dst[:got.value].tobytes()
+
+
+def png_probe(data):
+    """ffhip_png_probe (host, no device): a PNG file (bytes) -> capi.PngInfo: width, height, bit_depth, color_type, interlace, has_trns,
+    palette_size, n_passes, filtered_bytes, pass_rows[7], pass_row_bytes[7]"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    info = capi.PngInfo()
+    capi.check(capi.lib().ffhip_png_probe(buf.ctypes.data if buf.size else None, buf.size, C.byref(info)), "ffhip_png_probe")
+    return info
+
+
+def png_picture(data, pitch=None):
+    """ffhip_png_picture (host, no device): the whole decode of a PNG file (bytes) by the functions the kernels compile -> BGRA [h][w][4]"""
+    info = png_probe(data)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    pitch = 4 * info.width if pitch is None else pitch
+    out = np.zeros((info.height, pitch), np.uint8)
+    capi.check(capi.lib().ffhip_png_picture(buf.ctypes.data, buf.size, out.ctypes.data, pitch), "ffhip_png_picture")
+    return out[:, :4 * info.width].reshape(info.height, info.width, 4)
+
+
+def png_exif_orientation(data):
+    """ffhip_png_exif_orientation: the same from a PNG file's eXIf chunk"""
+    return _exif_orientation(capi.lib().ffhip_png_exif_orientation, data)
+
+
+def png_decode_files_device(files, n_threads=8, stream=None, strict=True):
+    """ffhip_png_decode_files_device: PNG files of any sizes and kinds (list of bytes) in one call.  Every picture gets its place in ONE
+    device allocation, at a 16-byte-aligned offset with the pitch 4 x its width rounded up to 16 bytes.  Returns (infos, [host BGRA
+    [h][w][4], alpha included], device buffer); with strict=False a failing file does not raise: its entry is None and a fourth element,
+    the per-file status codes, follows."""
+    def probe(i, f):
+        info = png_probe(f)
+        return ((4 * info.width + 15) & ~15, info.height, info.width, info.height)
+
+    infos = (capi.PngInfo * max(len(files), 1))()
+
+    def call(L, ptrs, lens, n, outs, pitches, status):
+        return L.ffhip_png_decode_files_device(ptrs, lens, n, n_threads, outs, pitches, infos, status, stream)
+
+    images, dout, status = _files_to_pictures(files, probe, call, "ffhip_png_decode_files_device", strict)
+    infos = list(infos)[:len(files)]
+    return (infos, images, dout) if strict else (infos, images, dout, status)
+
+
+def png_last():
+    """ffhip_debug_png_last: (parts, launches of k_png_unfilter) of this thread's last ffhip_png_decode_files_device"""
+    out = (C.c_int * 2)()
+    capi.check(capi.lib().ffhip_debug_png_last(out), "ffhip_debug_png_last")
+    return out[0], out[1]
+
+
+def png_times():
+    """ffhip_debug_png_times: milliseconds of this thread's last ffhip_png_decode_files_device -- (host chunk walk and inflate, upload,
+    k_png_unfilter over its levels, k_png_expand); the last three only while FFHIP_PNG_TIMES is set"""
+    out = (C.c_double * 4)()
+    capi.check(capi.lib().ffhip_debug_png_times(out), "ffhip_debug_png_times")
+    return tuple(out)

@@ -194,7 +194,9 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
     imposed = _orientations(orientation, len(files))
     oriented = bool(apply_exif_orientation) or imposed is not None
     webp_ex = codec.name == "webp" and pixels == "libwebp"        # the ninth entry: flags = FFHIP_WEBP_PIXELS_LIBWEBP
-    what = webp_entry_point(pixels, oriented, bool(targets)) if webp_ex else entry_point(codec.name, oriented, den, bool(targets), progressive, flags)
+    one_entry = webp_ex or codec.name == "png"                    # PNG has ONE entry, with the ninth's tail and flags = 0
+    what = ("ffhip_png_decode_files_tensor" if codec.name == "png" else webp_entry_point(pixels, oriented, bool(targets)) if webp_ex
+            else entry_point(codec.name, oriented, den, bool(targets), progressive, flags))
     probe = codec.probe_progressive if progressive else codec.probe
     import torch
     tdtype = getattr(torch, _dtype_name(dtype))
@@ -247,7 +249,7 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
         "orient": (ints(*[(max(t, 1) if imposed else 0) if oriented else 1 for t in turns]), used_turn),
         "flags": (capi.FFHIP_WEBP_PIXELS_LIBWEBP if webp_ex else flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0),),
     }
-    tail = sum((tails[part] for part in (_WEBP_EX_TAIL if webp_ex else _ENTRY_TAILS[what])), ())
+    tail = sum((tails[part] for part in (_WEBP_EX_TAIL if one_entry else _ENTRY_TAILS[what])), ())
     rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, *tail, None, status, torch.cuda.current_stream().cuda_stream)
     if oriented:
         turns = list(used_turn)[:n]
@@ -284,6 +286,14 @@ _Codec = namedtuple("_Codec", "name probe probe_progressive tag")
 _JPEG = _Codec("jpeg", _jpeg_size, _jpeg_size_any, ops.jpeg_exif_orientation)
 _WEBP = _Codec("webp", _webp_size, None, ops.webp_exif_orientation)
 _WEBP_LIBWEBP = _Codec("webp", lambda f: ops.webp_probe(f, "libwebp")[:2], None, ops.webp_exif_orientation)
+
+
+def _png_size(f):
+    info = ops.png_probe(f)
+    return info.width, info.height
+
+
+_PNG = _Codec("png", _png_size, None, ops.png_exif_orientation)
 
 
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
@@ -343,5 +353,15 @@ def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
                tag's width x height, and roi, size and orientation act on it.  Anything else: ValueError"""
     ops.webp_pixel_flags(pixels)
     return _decode_to_tensors(_WEBP_LIBWEBP if pixels == "libwebp" else _WEBP, files, pixels=pixels, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+                              strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
+                              return_orientation=return_orientation)
+
+
+def decode_png_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
+                          strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False):
+    """ffhip_png_decode_files_tensor: PNG files of every colour type and bit depth, interlaced or not; arguments and result as
+    decode_webp_to_tensors (the orientation tag is read from the file's eXIf chunk).  A file's display size is its width x height.  The
+    tensors have three channels: alpha is dropped, as PIL's convert("RGB") drops it -- ops.png_decode_files_device delivers BGRA with it."""
+    return _decode_to_tensors(_PNG, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)

@@ -1215,6 +1215,57 @@ int ffhip_jpeg_recon_items_libjpeg(const ffhip_jpeg_item *items, const ffhip_siz
  * (host front end: the deepest level of each file, summed), [4] the front end taken, 0 host, 1 device (the last class's). */
 int ffhip_debug_progressive_last(int out[5]);
 
+/* ---- PNG (ffhip_inflate.c, ffhip_png.c, ffhip_png_body.h, ffhip_png_gpu.hip) ----
+ * The pixel rule is the PNG specification (ISO/IEC 15948) as libpng applies it for an 8-bit RGBA output:
+ *   - the picture is BGRA at width x height with the file's alpha, 255 where the file has none;
+ *   - 16-bit samples become their high byte; grey at 1, 2 and 4 bits is scaled by 255, 85 and 17;
+ *   - palette files take their PLTE entries, alpha from tRNS and 255 beyond its length;
+ *   - tRNS on grey and RGB: the sample or the triple is compared at the file's own bit depth, alpha 0 on equality, 255 otherwise;
+ *   - Adam7 files are de-interlaced, no pixel dropped; gAMA, sRGB, iCCP, bKGD and the APNG chunks are ignored (ancillary chunks are
+ *     skipped by their length, without a CRC check); bytes the zlib stream holds beyond the filtered picture are ignored.
+ * FFHIP_EINVAL for a file with: a CRC failure on IHDR, PLTE, tRNS, IDAT or IEND; a bad Adler-32; a zlib stream that ends short of the
+ * filtered picture; a filter byte above 4; a bit depth its colour type does not have; compression, filter or interlace method bytes out
+ * of range; a side of 0 or above 65535; a palette index beyond PLTE; no IEND; a critical chunk other than the four. */
+/* Host only.  A zlib-wrapped deflate stream (CM 8, window up to 32 KiB, no preset dictionary; stored, fixed and dynamic blocks) into
+ * dst[0 .. cap); *out_len receives the bytes written.  FFHIP_EINVAL for everything it refuses: a bad header or check value, a stream
+ * that ends early, over-subscribed code lengths (an incomplete set only as the one-code distance tree zlib accepts), a distance beyond
+ * the start of the output, symbols deflate does not have, output beyond cap.  Reads nothing outside src[0 .. len). */
+int ffhip_inflate(const uint8_t *src, size_t len, uint8_t *dst, size_t cap, size_t *out_len);
+typedef struct ffhip_png_info {
+    int32_t width, height, bit_depth, color_type, interlace;
+    int32_t has_trns;        /* a tRNS chunk that counts: in front of IDAT, of the colour type's length */
+    int32_t palette_size;    /* PLTE entries of a colour type 3 file, else 0 */
+    int32_t n_passes;        /* sub-images with pixels: 1, or up to 7 of an Adam7 file */
+    uint64_t filtered_bytes; /* what the zlib stream has to hold: every pass's rows x (1 + row bytes) */
+    int32_t pass_rows[7], pass_row_bytes[7]; /* by Adam7 pass ([0] alone: not interlaced); 0 rows for a pass without pixels */
+} ffhip_png_info;
+/* Host only, cheap: the header (its CRC checked) and the chunks up to the first IDAT walked by their lengths (no CRC). */
+int ffhip_png_probe(const uint8_t *file, size_t len, ffhip_png_info *info);
+/* Host only, no device needed: the whole decode into bgra (pitch >= 4 x width), by the functions the kernels compile. */
+int ffhip_png_picture(const uint8_t *file, size_t len, uint8_t *bgra, int64_t pitch);
+/* As ffhip_jpeg_exif_orientation, from the file's eXIf chunk (the TIFF structure, without "Exif\0\0"). */
+int ffhip_png_exif_orientation(const uint8_t *file, size_t len, int *orientation);
+/* PNG files of any sizes and kinds in one call: shape and per-file contract of ffhip_webp_decode_files_device.  d_bgra[i] (16-byte aligned,
+ * pitch[i] >= 4 x width, a multiple of 16) receives file i's width x height BGRA pixels and nothing else.  Host threads walk the chunks,
+ * check the CRCs and inflate straight into pinned staging; k_png_unfilter undoes the row filters (one launch per level of 64 rows) and
+ * k_png_expand writes the pictures.  The batch goes in PARTS of at most 1 GiB of filtered bytes (FFHIP_PNG_PART_BYTES replaces the figure),
+ * a larger file a part of its own.  status[i] receives each file's code; a refused file writes nothing and every other file is delivered;
+ * returns the first failure.  Argument checks come before anything is enqueued: FFHIP_EINVAL for NULL arrays, then FFHIP_ENODEV.
+ * Synchronises `stream`. */
+int ffhip_png_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                  const int64_t *pitch, ffhip_png_info *info_out, int *status, void *stream);
+/* Files to tensors, as ffhip_webp_decode_files_tensor_ex: the display picture is width x height, alpha is dropped by the three-channel
+ * sink; out_size == NULL: no resize; orient[i] 1..8, or 0 for the file's eXIf tag, orient == NULL: every file's tag; flags must be 0. */
+int ffhip_png_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                  const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                  const int *orient, int *orient_out, unsigned flags, ffhip_png_info *info_out, int *status, void *stream);
+/* Diagnostics: parts and unfilter levels (launches of k_png_unfilter) of the calling thread's last ffhip_png_decode_files_device. */
+int ffhip_debug_png_last(int out[2]);
+/* Diagnostics (tests/tools/bench_png.py): milliseconds of that call's stages, all its parts together -- [0] the host threads' chunk walk
+ * and inflate (wall clock), and, measured by events only while FFHIP_PNG_TIMES is set (0 otherwise), [1] the upload, [2] k_png_unfilter
+ * over all its levels, [3] k_png_expand. */
+int ffhip_debug_png_times(double out[4]);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
