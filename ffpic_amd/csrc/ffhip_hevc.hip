@@ -106,7 +106,10 @@ struct InvDct<4> {
     }
 };
 
-/* DST-VII 4-point (idct.c:11-16): in[0] = (x0, x2), in[1] = (x1, x3) */
+/* DST-VII 4-point (idct.c:11-16): in[0] = (x0, x2), in[1] = (x1, x3).
+ * rnd is the REFERENCE's rounding term, not H.265's: its callers pass `shift - 1` (6, and bdShift - 1) where 8.6.4.2 and 8.6.2 have
+ * 1 << (shift - 1) (64, and 1 << (bdShift - 1)), and the second pass is clipped like the first.  The spec witness names these
+ * rules dst_round_is_shift_minus_1 and dst_clips_second_pass (tests/hevc_spec.py). */
 __device__ __forceinline__ void inv_dst4(const u32 *in, int *out, int rnd)
 {
     out[0] = dot2(in[0], PK16(29, 84), dot2(in[1], PK16(74, 55), rnd));
@@ -126,7 +129,9 @@ struct HevcResArgs {
 };
 
 #define TU_DST 1u    /* trType 1: luma intra 4x4 -> idct_4x4_hevc                     */
-#define TU_TSKIP 2u  /* transform_skip_flag: r = d << (5 + log2 N)                    */
+#define TU_TSKIP 2u  /* transform_skip_flag: r = d << (5 + log2 N) -- the reference's rule, not H.265's: the
+                        (r + (1 << (bdShift - 1))) >> bdShift of 8.6.2 is never applied to such a block (flags
+                        ts_without_bdshift and ts_shift_int16 of tests/hevc_spec.py) */
 #define TU_BYPASS 4u /* cu_transquant_bypass_flag: r = level                          */
 #define TU_ROTATE 8u /* rotateCoeffs (4x4 intra with transform_skip_rotation_enabled) */
 

@@ -186,7 +186,9 @@ __device__ __attribute__((noinline)) void rdpcm_accumulate(short *R, const int l
 {
     constexpr int n = 1 << LG;
     if (mode / 26 == 0) {
-        /* running sum over the flattened block from index n (hevc.c:3963-3968):
+        /* running sum over the flattened block from index n (hevc.c:3963-3968).  The reference's rule, not H.265's: 8.6.5
+         * accumulates along every row and never across a row end (flag rdpcm_horizontal_runs_on of tests/hevc_spec.py,
+         * DESIGN.md 4.23):
          * R[i] = sum of R[n-1 .. i] mod 2^16 -- a prefix sum: per-lane chunks, then a wave scan of the chunk totals */
         constexpr int nn = n * n, chunk = nn >= 64 ? nn >> 6 : 1, active = nn / chunk;
         int loc[16], sum = 0;
@@ -372,7 +374,8 @@ __device__ __forceinline__ void intra_tu_g(const HotArgs &a, const GroupCtx &g, 
             rdpcm_accumulate<LG>(R, lane, mode);
             wave_sync();
         }
-        if (flags & 0x80) {
+        if (flags & 0x80) { /* 8.6.6 as the reference calls it, not as H.265 has it: rY is this chroma block, not the luma residual
+                             * (flag ccp_reads_chroma of tests/hevc_spec.py) */
             const int bdc = a.bitdepth_c, bdy = a.bitdepth_y;
 #pragma unroll 4
             for (int i = lane; i < n * n; i += 64) {

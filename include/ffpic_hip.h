@@ -357,6 +357,10 @@ int ffhip_vp8_predict_loopfilter(int mbcols, int mbrows, int n_images, const uin
  *   bitdepth   BitDepthY or BitDepthC of the component the TUs belong to; epp =
  *              extended_precision_processing_flag
  *   d_residual int16 [n_tu][nTbS*nTbS]  r[] as construct_pic_pior_to_filtering consumes it
+ * Two rules here are the reference's and not H.265's, on conformant streams too (tests/hevc_spec.py names them, DESIGN.md 4.23
+ * measures them): the 4x4 DST rounds with `shift - 1` in both passes where the standard has 1 << (shift - 1)
+ * (dst_round_is_shift_minus_1), and a transform-skipped block is d << tsShift without the bdShift step of 8.6.2
+ * (ts_without_bdshift).
  * Only enqueues; d_level, d_tuinfo, d_scaling and d_residual are stream-ordered. */
 int ffhip_hevc_residual_batch(int nTbS, long long n_tu, const int16_t *d_level, const uint8_t *d_tuinfo,
                               const uint8_t *d_scaling, int bitdepth, int epp, int16_t *d_residual,
@@ -674,10 +678,14 @@ typedef struct ffhip_hevc_tu {
 #define FFHIP_TU_STRONG 0x08   /* sps strong_intra_smoothing_enabled_flag                    */
 #define FFHIP_TU_NO_BF 0x10    /* disableIntraBoundaryFilter (hevc.c:4642-4648)              */
 #define FFHIP_TU_NO_DC_BF 0x20 /* intra_boundary_filtering_disabled_flag (DC edge filter)    */
-#define FFHIP_TU_RDPCM 0x40    /* residualDpcm == 1: 8.6.5 on the residual before the add    */
+#define FFHIP_TU_RDPCM 0x40    /* residualDpcm == 1: 8.6.5 on the residual before the add.  Horizontally the
+                                  reference's rule, not H.265's: a running sum over the flattened block from index
+                                  nTbS on (flag rdpcm_horizontal_runs_on of tests/hevc_spec.py) */
 #define FFHIP_TU_CCP 0x80      /* 8.6.6 cross-component prediction after 8.6.5, exactly as the reference
                                   calls it (hevc.c:4750-4756): the "luma" residual it passes is the chroma
-                                  block itself, so r += (res_scale * ((r << BitDepthC) >> BitDepthY)) >> 3 */
+                                  block itself, so r += (res_scale * ((r << BitDepthC) >> BitDepthY)) >> 3.
+                                  The reference's rule, not H.265's, where rY is the luma residual (flag
+                                  ccp_reads_chroma of tests/hevc_spec.py) */
 /* h_tus / d_tus: the SAME n_tus records on the host (dependency scheduling) and on the device.
  * d_residual: int16 residual blocks (row-major n*n each) as ffhip_hevc_residual_batch writes
  * them.  Planes: int16, strides in samples; d_cb/d_cr may be NULL for 4:0:0.  ONLY ENQUEUES: h_tus is validated on
