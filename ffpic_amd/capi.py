@@ -42,6 +42,8 @@ EXPORTS = [
     "ffhip_jpeg_libjpeg_block", "ffhip_jpeg_libjpeg_picture", "ffhip_jpeg_recon_items_libjpeg",
     "ffhip_inflate", "ffhip_png_probe", "ffhip_png_picture", "ffhip_png_exif_orientation", "ffhip_png_decode_files_device",
     "ffhip_png_decode_files_tensor", "ffhip_debug_png_last", "ffhip_debug_png_times",
+    "ffhip_vp8l_probe", "ffhip_vp8l_read_info", "ffhip_vp8l_picture", "ffhip_vp8l_decode_files_device", "ffhip_vp8l_decode_files_tensor",
+    "ffhip_debug_vp8l_last", "ffhip_debug_vp8l_times",
 ]
 
 
@@ -100,6 +102,13 @@ class PngInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32), ("color_type", C.c_int32), ("interlace", C.c_int32),
                 ("has_trns", C.c_int32), ("palette_size", C.c_int32), ("n_passes", C.c_int32), ("filtered_bytes", C.c_uint64),
                 ("pass_rows", C.c_int32 * 7), ("pass_row_bytes", C.c_int32 * 7)]
+
+
+class Vp8lInfo(C.Structure):
+    """ffhip_vp8l_info"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("has_alpha", C.c_int32), ("n_transforms", C.c_int32), ("transforms", C.c_int32 * 4),
+                ("predictor_bits", C.c_int32), ("cross_bits", C.c_int32), ("palette_size", C.c_int32), ("pixels_per_word", C.c_int32),
+                ("cache_bits", C.c_int32), ("has_meta", C.c_int32), ("residual_width", C.c_int32)]
 
 
 class WebpParsed(C.Structure):
@@ -385,6 +394,14 @@ def lib():
                                                 C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.c_uint, C.POINTER(PngInfo), vp, vp]
     L.ffhip_debug_png_last.argtypes = [C.POINTER(ci)]
     L.ffhip_debug_png_times.argtypes = [C.POINTER(C.c_double)]
+    L.ffhip_vp8l_probe.argtypes = [vp, sz, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.ffhip_vp8l_read_info.argtypes = [vp, sz, C.POINTER(Vp8lInfo)]
+    L.ffhip_vp8l_picture.argtypes = [vp, sz, vp, i64]
+    L.ffhip_vp8l_decode_files_device.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(Vp8lInfo), vp, vp]
+    L.ffhip_vp8l_decode_files_tensor.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect),
+                                                 C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.c_uint, C.POINTER(Vp8lInfo), vp, vp]
+    L.ffhip_debug_vp8l_last.argtypes = [C.POINTER(ci)]
+    L.ffhip_debug_vp8l_times.argtypes = [C.POINTER(C.c_double)]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

@@ -122,6 +122,7 @@ enum FfhipScratchKind {
     SCRATCH_JPEG_SCALED = 80,     /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_scaled's records and per-workgroup table, pinned records */
     SCRATCH_JPEG_LIBJPEG = 100,   /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_libjpeg's records, per-workgroup tables and sample planes, pinned records */
     SCRATCH_PNG = 110,           /* .. + 2: ffhip_png_decode_files_device: a part's filtered pictures and palettes (and their pinned copy); k_png_unfilter's records; k_png_expand's records and per-workgroup table (pinned records) */
+    SCRATCH_VP8L = 113,          /* .. + 2: ffhip_vp8l_decode_files_device: a part's residual images, block images and palettes (and their pinned copy); k_vp8l_predict's records; k_vp8l_finish's records and per-workgroup table (pinned records) */
     SCRATCH_HUFF_PROG = 90,      /* ffhip_jpeg_progressive_batch_gpu: staged scans, tables, records and work lists (and their pinned copy) */
 };
 

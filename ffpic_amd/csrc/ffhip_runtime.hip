@@ -162,7 +162,7 @@ extern "C" const char *ffhip_strerror(int code)
     case FFHIP_ENOMEM: return "out of memory";
     case FFHIP_ENODEV: return g_last_error[0] ? g_last_error : "no usable gfx950 device";
     case FFHIP_EIO: return g_last_error[0] ? g_last_error : "HIP launch or copy failed";
-    case FFHIP_EWEBP_LOSSLESS: return "lossless WebP (VP8L) is not decoded";
+    case FFHIP_EWEBP_LOSSLESS: return "lossless WebP (VP8L) is not decoded by this call (the ffhip_vp8l_* calls decode it)";
     case FFHIP_EWEBP_ANIMATION: return "animated WebP is not decoded";
     case FFHIP_EWEBP_INTER_FRAME: return "the VP8 frame is not a key frame";
     default: return "unknown error";

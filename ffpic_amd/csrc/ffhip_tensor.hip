@@ -1,7 +1,7 @@
 /*
  * ffhip_tensor.hip -- the last stage between the decoders and a program that reads tensors: BGRA pictures as the decode calls leave
  * them -> RGB / BGR, CHW / HWC, uint8 / float16 / float32, cropped to a rectangle, in one launch for a whole mixed batch
- * (ffhip_bgra_to_tensor_items), and the file calls built on it (ffhip_jpeg_decode_files_tensor, ffhip_webp_decode_files_tensor, ffhip_png_decode_files_tensor, and
+ * (ffhip_bgra_to_tensor_items), and the file calls built on it (ffhip_jpeg_decode_files_tensor, ffhip_webp_decode_files_tensor, ffhip_png_decode_files_tensor, ffhip_vp8l_decode_files_tensor, and
  * their _resized forms with ffhip_bgra_resize_items between the decoder and this stage, their _oriented forms with
  * ffhip_bgra_orient_items in front of this stage).
  * The layout of the work is described in ffhip_tensor_body.h.
@@ -391,7 +391,7 @@ int tensor_orientation(const TensorOptions &opts, int i, const TensorProbe &p, T
     return o;
 }
 
-/* The three codecs: they differ in their probe and in the call underneath */
+/* The codecs: they differ in their probe and in the call underneath */
 int jpeg_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
                       const TensorOptions &opts, ffhip_jpeg_geom *geom_out, int *status, void *stream)
 {
@@ -465,6 +465,25 @@ int png_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int
     return tensor_files_run(plan, opts, fmt, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
         return ffhip_png_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
                                              status + first, stream);
+    });
+}
+
+int vp8l_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
+                      const TensorOptions &opts, ffhip_vp8l_info *info_out, int *status, void *stream)
+{
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts) || opts.flags) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    std::vector<TensorFile> plan((size_t)n);
+    for (int i = 0; i < n; i++) {
+        int w = 0, h = 0, alpha = 0;
+        status[i] = files[i] && lens[i] ? ffhip_vp8l_probe(files[i], lens[i], &w, &h, &alpha) : FFHIP_EINVAL;
+        const int cw = (w + 3) & ~3; /* the file call's pictures: rows of whole 16-byte groups */
+        const TensorProbe p{status[i], TensorPicture{cw, h, w, h, 4LL * cw}};
+        plan[(size_t)i] = tensor_file_plan(p, tensor_orientation(opts, i, p, ffhip_webp_exif_orientation, files[i], lens[i]), i, opts, fmt, outs);
+    }
+    return tensor_files_run(plan, opts, fmt, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
+        return ffhip_vp8l_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
+                                              status + first, stream);
     });
 }
 
@@ -548,4 +567,12 @@ extern "C" int ffhip_png_decode_files_tensor(const uint8_t *const *files, const 
 {
     return png_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags), info_out,
                             status, stream);
+}
+
+extern "C" int ffhip_vp8l_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                              const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                              const int *orient, int *orient_out, unsigned flags, ffhip_vp8l_info *info_out, int *status, void *stream)
+{
+    return vp8l_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags), info_out,
+                             status, stream);
 }

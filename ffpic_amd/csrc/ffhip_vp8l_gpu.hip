@@ -1,0 +1,435 @@
+/* ffhip_vp8l_gpu.hip -- lossless WebP files to BGRA pictures on the device (include/ffpic_hip.h, "lossless WebP").  Host
+ * threads decode the prefix codes, copies and colour cache (ffhip_vp8l.c) straight into a part's pinned staging: a file's RESIDUAL image,
+ * its predictor and cross-colour block images and its palette; one upload; k_vp8l_predict undoes the predictor in place, k_vp8l_finish
+ * undoes what is left and writes the pictures.  Both kernels compile the functions of ffhip_vp8l_body.h, as ffhip_vp8l_picture does on the
+ * host, and neither has an error path: what a file can be refused for is seen on the host.
+ *
+ * k_vp8l_predict, in the form of k_png_unfilter.  An item is a file, cut into bands of 64 rows; a wave takes one band, lane r its row r.
+ * A row is walked in CHUNKS of four pixels (16 bytes), and the lanes are skewed by TWO chunks: at step t lane r reconstructs chunk t - 2r.
+ * A chunk's last pixel has the first pixel of the NEXT chunk above as its TR, so the lane above must have finished chunk q + 1 when this
+ * lane starts chunk q.  A lane keeps its last two chunks and hands them down by DPP wave_shr:1 -- the older one whole (T of the four
+ * pixels), of the newer one the first pixel (TR of the last): five moves per step; TL of the first pixel is the older chunk's last pixel
+ * of the step before, kept in a register.  The first pixel of the lane's own row is kept too: it is the TR of the row's last pixel.  Lane 0
+ * reads the row above from memory, where the launch before has written it: bands depend on each other top to bottom, and level l of
+ * every file is one launch.  No spin-waits, no counters.
+ *   The mode is constant over a chunk and differs between lanes.  Chosen by instruction count: ONE switch per chunk
+ * (ffhip_vp8l_predict_chunk), the lanes of a wave walking the arms their modes name one after the other.  The kernel is 1 784
+ * instructions, about 1 500 of them the thirteen arms of four pixels each (mode 13's clamps and Select's two v_sad_u8 a pixel the longest);
+ * the select form -- every mode computed, the lane's own picked -- would issue all of them at every step of every wave, where the switch
+ * issues the arms of the modes PRESENT among the 64 lanes and two branch instructions an arm, so it is never more and mostly far less:
+ * encoded pictures hold runs of one mode down a column of blocks.  Families by whether the mode reads L would save nothing, since the four
+ * pixels of a chunk hang on each other through L in ten of the thirteen arms, and it is that chain, not the issue rate, that an arm costs.
+ *   The pointwise transforms undone BEFORE the predictor (cross-colour, in the order libwebp's encoder writes) are applied to the residual
+ * as it is loaded.
+ *
+ * k_vp8l_finish.  The gather form of k_png_expand: a lane owns four consecutive output pixels of a row, applies the pointwise transforms
+ * behind the predictor in the file's order, looks a colour-indexed file's pixels up in the palette (2, 4 or 8 to a word), applies the
+ * alpha rule and makes one 16-byte store.  A picture's last partial group of four is stored pixel by pixel. */
+#include "ffhip_items.h"
+#include "ffhip_vp8l_internal.h"
+
+#include <algorithm>
+#include <chrono>
+#include <stdlib.h>
+
+namespace {
+
+constexpr int VP8L_BAND = 64;
+constexpr int VP8L_SKEW = 2; /* chunks between a lane and the lane above it */
+constexpr int VP8L_FINISH_THREADS = 256;
+
+/* one file's residual image, to be predicted in place */
+struct Vp8lPredDesc {
+    u32 *res;            /* rows x width words */
+    const u32 *modes;    /* the predictor's block image */
+    const u32 *cross;    /* the cross-colour block image, where a step before the predictor reads it */
+    u32 width, rows, n_bands;
+    ffhip_vp8l_steps steps;
+};
+struct Vp8lPredArgs {
+    const Vp8lPredDesc *desc; /* sorted by n_bands, largest first: the items with a band `level` are the first of them */
+    u32 level, wg_base;
+};
+
+/* one file's picture */
+struct Vp8lFinDesc {
+    const u32 *res;      /* the residual image with the predictor undone: rows of res_width words */
+    uint8_t *dst;
+    int64_t pitch;
+    const u32 *cross, *palette;
+    u32 width, height, res_width, groups_x;
+    u32 first_wg, n_wgs;
+    ffhip_vp8l_steps steps;
+};
+struct Vp8lFinArgs {
+    const Vp8lFinDesc *desc;
+    const u32 *wg_item;
+    u32 wg_base;
+};
+
+struct __attribute__((packed, aligned(4))) Vp8lQuad { u32 w[4]; }; /* four words at any word address */
+
+__device__ __forceinline__ u32 vp8l_shr1(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); } /* wave_shr:1 -- lane r - 1; lane 0: 0 */
+
+/* n <= 4 words at p -> w, zero behind them */
+__device__ __forceinline__ void vp8l_load(const u32 *p, int n, u32 (&w)[4])
+{
+    if (n == 4) {
+        const Vp8lQuad v = *(const Vp8lQuad *)p;
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = v.w[k];
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) w[k] = k < n ? p[k] : 0u;
+}
+
+/* One band.  Every lane runs every step, whatever its row: the cross-lane moves want the whole wave */
+__global__ __launch_bounds__(VP8L_BAND) void k_vp8l_predict(Vp8lPredArgs a)
+{
+    const Vp8lPredDesc d = a.desc[a.wg_base + blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    const u32 band = a.level, width = d.width;
+    const u32 row = band * VP8L_BAND + (u32)lane;
+    const bool live = row < d.rows;
+    u32 *cur = d.res + (unsigned long long)(live ? row : 0) * width;
+    const u32 *above = band ? d.res + ((unsigned long long)band * VP8L_BAND - 1) * width : nullptr; /* lane 0's row above */
+    const u32 n_chunks = (width + 3) / 4;
+    const int pbits = d.steps.predictor_bits, cbits = d.steps.cross_bits;
+    const u32 *mode_row = d.modes + (unsigned long long)(row >> pbits) * d.steps.predictor_bx;
+    const u32 *cross_row = d.cross ? d.cross + (unsigned long long)(row >> cbits) * d.steps.cross_bx : nullptr;
+    u32 older[4] = {0, 0, 0, 0}, newer[4] = {0, 0, 0, 0}; /* the lane's last two chunks */
+    u32 corner = 0, first = 0;                            /* above left of the next chunk; the row's first pixel */
+    const u32 start = (u32)(VP8L_SKEW * lane);
+    for (u32 t = 0; t < n_chunks + VP8L_SKEW * (VP8L_BAND - 1); t++) {
+        u32 up[6];
+#pragma unroll
+        for (int k = 0; k < 4; k++) up[1 + k] = vp8l_shr1(older[k]);
+        up[5] = vp8l_shr1(newer[0]);
+        if (t < start) continue;
+        const u32 q = t - start;
+#pragma unroll
+        for (int k = 0; k < 4; k++) older[k] = newer[k]; /* a finished lane goes on shifting: the lane below still reads its last chunks */
+        if (!live || q >= n_chunks) continue;
+        const u32 x0 = 4 * q;
+        const int n = (int)min(4u, width - x0);
+        if (lane == 0 && above) {
+            u32 w4[4];
+            vp8l_load(above + x0, n, w4);
+#pragma unroll
+            for (int k = 0; k < 4; k++) up[1 + k] = w4[k];
+            up[5] = x0 + 4 < width ? above[x0 + 4] : 0u;
+        }
+        up[0] = corner;
+        corner = up[4];
+        u32 res[4], out[4] = {0, 0, 0, 0};
+        vp8l_load(cur + x0, n, res);
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            if (s >= (int)d.steps.n_pre) break;
+            const int type = d.steps.pre[s];
+            const u32 m = type == FFHIP_VP8L_CROSS_COLOR ? cross_row[x0 >> cbits] : 0u;
+#pragma unroll
+            for (int j = 0; j < 4; j++) res[j] = type == FFHIP_VP8L_CROSS_COLOR ? ffhip_vp8l_cross(res[j], m) : ffhip_vp8l_add_green(res[j]);
+        }
+        const bool last = q + 1 == n_chunks;
+        if (last && q) { /* the row's last pixel: its TR is the row's own first pixel.  A row of one chunk: tr_own */
+#pragma unroll
+            for (int k = 2; k < 6; k++)
+                if (k == n + 1) up[k] = first;
+        }
+        const int block = row ? ffhip_vp8l_mode_of(mode_row[x0 >> pbits]) : 1;
+        ffhip_vp8l_predict_chunk(q ? block : row ? 2 : 0, block, n, n_chunks == 1 ? n - 1 : 0, res, newer[3], up, out);
+        if (q == 0) first = out[0];
+#pragma unroll
+        for (int k = 0; k < 4; k++) newer[k] = out[k];
+        if (n == 4) {
+            Vp8lQuad v;
+#pragma unroll
+            for (int k = 0; k < 4; k++) v.w[k] = out[k];
+            *(Vp8lQuad *)(cur + x0) = v;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                if (k < n) cur[x0 + (u32)k] = out[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(VP8L_FINISH_THREADS) void k_vp8l_finish(Vp8lFinArgs a)
+{
+    const u32 wg = a.wg_base + blockIdx.x;
+    const u32 item = __builtin_amdgcn_readfirstlane(a.wg_item[wg]);
+    const Vp8lFinDesc *d = a.desc + item;
+    const u32 width = d->width, gx = d->groups_x, rw = d->res_width;
+    const u32 g = (wg - d->first_wg) * VP8L_FINISH_THREADS + threadIdx.x; /* groups_x x height < 2^28 */
+    if (g >= gx * d->height) return;
+    const u32 y = g / gx, x0 = 4 * (g - y * gx);
+    const int n = (int)min(4u, width - x0);
+    const ffhip_vp8l_steps steps = d->steps;
+    const u32 *row = d->res + (unsigned long long)y * rw;
+    const u32 opaque = steps.has_alpha ? 0u : 0xff000000u;
+    u32 v[4] = {0, 0, 0, 0};
+    if (!steps.has_index) {
+        vp8l_load(row + x0, n, v);
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            if (s >= (int)steps.n_post) break;
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = ffhip_vp8l_pointwise(steps.post[s], v[j], min(x0 + (u32)j, width - 1), y, &steps, d->cross);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const u32 x = min(x0 + (u32)j, width - 1), xp = x >> steps.index_bits;
+            u32 word = row[xp];
+#pragma unroll
+            for (int s = 0; s < 2; s++)
+                if (s < (int)steps.n_post) word = ffhip_vp8l_pointwise(steps.post[s], word, xp, y, &steps, d->cross);
+            v[j] = ffhip_vp8l_index(word, x, steps.index_bits, d->palette);
+        }
+    }
+    uint8_t *out = d->dst + (long long)y * d->pitch + 4ll * x0;
+    if (n == 4) {
+        *(u32x4 *)out = u32x4{v[0] | opaque, v[1] | opaque, v[2] | opaque, v[3] | opaque};
+    } else {
+        for (int j = 0; j < n; j++) ((u32 *)out)[j] = v[j] | opaque;
+    }
+}
+
+thread_local int t_vp8l_last[3];     /* ffhip_debug_vp8l_last */
+thread_local double t_vp8l_times[4]; /* ffhip_debug_vp8l_times */
+
+/* FFHIP_VP8L_TIMES: events around a part's upload, predict launches and finish launch; off, nothing is recorded */
+struct Vp8lClock {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool on = false;
+    Vp8lClock()
+    {
+        const char *v = FFHIP_ENV("FFHIP_VP8L_TIMES");
+        on = v && v[0] && v[0] != '0';
+        for (int k = 0; on && k < 4; k++)
+            if (hipEventCreate(&ev[k]) != hipSuccess) on = false;
+    }
+    ~Vp8lClock()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void mark(int k, hipStream_t st) { if (on) (void)hipEventRecord(ev[k], st); }
+    void add() /* behind the part's synchronisation */
+    {
+        for (int k = 0; on && k < 3; k++) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) t_vp8l_times[k + 1] += ms;
+        }
+    }
+};
+
+size_t vp8l_place(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+size_t vp8l_part_budget()
+{
+    const char *v = FFHIP_ENV("FFHIP_VP8L_PART_BYTES");
+    const long long b = v ? atoll(v) : 0;
+    return b > 0 ? (size_t)b : (size_t)1 << 30;
+}
+
+/* a file's place in its part's staging: the residual image (a host-form file: its finished pixels), then what the kernels read beside it */
+struct Vp8lPartFile { int idx; size_t res_off, modes_off, cross_off, palette_off; };
+
+size_t vp8l_res_bytes(const ffhip_vp8l_file &f)
+{
+    return 4 * (size_t)(f.device_form ? f.info.residual_width : f.info.width) * (size_t)f.info.height;
+}
+size_t vp8l_side_bytes(const ffhip_vp8l_file &f)
+{
+    if (!f.device_form) return 0;
+    return vp8l_place(4 * (size_t)f.predictor_words) + vp8l_place(4 * (size_t)f.cross_words) + (f.steps.has_index ? 1024 : 0);
+}
+
+/* One part: files pf[] of the call, `bytes` of staging */
+int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std::vector<ffhip_vp8l_file> &pf, int n_threads, uint8_t *const *d_bgra,
+                  const int64_t *pitch, int *status, void *stream, Vp8lClock &clock)
+{
+    hipStream_t st = (hipStream_t)stream;
+    for (int k = 0; k < 4; k++) clock.mark(k, st); /* a part that launches nothing has empty intervals */
+    uint8_t *pin = ffhip_pinned_scratch(SCRATCH_VP8L, stream, bytes + 64);
+    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_VP8L, stream, bytes / 4 + 16);
+    if (!pin || !dev) return FFHIP_ENOMEM;
+    const auto t0 = std::chrono::steady_clock::now();
+    ffhip_parallel_for((int)part.size(), n_threads, [&](int k) {
+        const Vp8lPartFile &p = part[(size_t)k];
+        const ffhip_vp8l_file &f = pf[(size_t)p.idx];
+        if (f.device_form) {
+            status[p.idx] = ffhip_vp8l_read_residual(&f, (uint32_t *)(pin + p.res_off));
+            if (f.predictor_words) memcpy(pin + p.modes_off, f.predictor_image, 4 * (size_t)f.predictor_words);
+            if (f.cross_words) memcpy(pin + p.cross_off, f.cross_image, 4 * (size_t)f.cross_words);
+            if (f.steps.has_index) memcpy(pin + p.palette_off, f.palette, 1024);
+            return;
+        }
+        /* colour indexing behind another transform: every step on the host, the pixels uploaded */
+        uint32_t *res = (uint32_t *)malloc(4 * (size_t)f.info.residual_width * (size_t)f.info.height);
+        status[p.idx] = res ? ffhip_vp8l_read_residual(&f, res) : FFHIP_ENOMEM;
+        if (!status[p.idx]) status[p.idx] = ffhip_vp8l_invert_host(&f, res, (uint32_t *)(pin + p.res_off));
+        free(res);
+    });
+    t_vp8l_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    clock.mark(0, st);
+    FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
+    for (int k = 1; k < 4; k++) clock.mark(k, st);
+    std::vector<Vp8lPredDesc> pred;
+    std::vector<Vp8lFinDesc> fin;
+    unsigned long long total = 0;
+    for (const Vp8lPartFile &p : part) {
+        if (status[p.idx]) continue;
+        const ffhip_vp8l_file &f = pf[(size_t)p.idx];
+        Vp8lFinDesc e;
+        memset(&e, 0, sizeof(e));
+        e.res = (const u32 *)(dev + p.res_off);
+        e.dst = d_bgra[p.idx];
+        e.pitch = pitch[p.idx];
+        e.width = (u32)f.info.width;
+        e.height = (u32)f.info.height;
+        e.groups_x = (e.width + 3) / 4;
+        e.res_width = e.width;
+        e.steps.has_alpha = (uint8_t)f.info.has_alpha;
+        if (f.device_form) {
+            e.res_width = (u32)f.info.residual_width;
+            e.steps = f.steps;
+            e.cross = f.cross_words ? (const u32 *)(dev + p.cross_off) : nullptr;
+            e.palette = f.steps.has_index ? (const u32 *)(dev + p.palette_off) : nullptr;
+            if (f.steps.has_predictor) {
+                Vp8lPredDesc u;
+                memset(&u, 0, sizeof(u));
+                u.res = (u32 *)(dev + p.res_off);
+                u.modes = (const u32 *)(dev + p.modes_off);
+                u.cross = e.cross;
+                u.width = e.res_width;
+                u.rows = e.height;
+                u.n_bands = (u.rows + VP8L_BAND - 1) / VP8L_BAND;
+                u.steps = f.steps;
+                pred.push_back(u);
+            }
+        } else {
+            t_vp8l_last[2]++;
+        }
+        e.first_wg = (u32)total;
+        e.n_wgs = (u32)(((unsigned long long)e.groups_x * e.height + VP8L_FINISH_THREADS - 1) / VP8L_FINISH_THREADS); /* < 2^20: both sides at most 2^14 */
+        total += e.n_wgs;
+        fin.push_back(e);
+    }
+    if (fin.empty()) return FFHIP_OK;
+    if (total > 0xffffffffULL) return FFHIP_EINVAL;
+    int rc = FFHIP_OK;
+    if (!pred.empty()) {
+        /* the files with the most bands first: the items that have a band l are then the first cnt(l) records, and level l is the
+         * workgroups [0, cnt(l)) of the records themselves */
+        std::stable_sort(pred.begin(), pred.end(), [](const Vp8lPredDesc &x, const Vp8lPredDesc &y) { return x.n_bands > y.n_bands; });
+        uint8_t *d_pred = nullptr;
+        rc = ffhip_items_stage(SCRATCH_VP8L + 1, stream, pred.data(), pred.size() * sizeof(Vp8lPredDesc), 0, 0, &d_pred);
+        if (rc) return rc;
+        size_t cnt = pred.size();
+        for (u32 level = 0; level < pred[0].n_bands; level++) {
+            while (pred[cnt - 1].n_bands <= level) cnt--;
+            rc = ffhip_items_launch(0, cnt, [&](unsigned grid_x, u32 wg_base) {
+                Vp8lPredArgs a;
+                a.desc = (const Vp8lPredDesc *)d_pred; a.level = level; a.wg_base = wg_base;
+                hipLaunchKernelGGL(k_vp8l_predict, dim3(grid_x), dim3(VP8L_BAND), 0, st, a);
+            });
+            if (rc) return rc;
+            t_vp8l_last[1]++;
+        }
+    }
+    for (int k = 2; k < 4; k++) clock.mark(k, st);
+    const Vp8lFinDesc *d_fin = nullptr;
+    u32 *d_table = nullptr;
+    rc = ffhip_items_upload(SCRATCH_VP8L + 2, stream, fin, total, &d_fin, &d_table);
+    if (rc) return rc;
+    rc = ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
+        Vp8lFinArgs a;
+        a.desc = d_fin; a.wg_item = d_table; a.wg_base = wg_base;
+        hipLaunchKernelGGL(k_vp8l_finish, dim3(grid_x), dim3(VP8L_FINISH_THREADS), 0, st, a);
+    });
+    clock.mark(3, st);
+    return rc;
+}
+
+} // namespace
+
+extern "C" int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                              const int64_t *pitch, ffhip_vp8l_info *info_out, int *status, void *stream)
+{
+    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
+    if (n == 0) return FFHIP_OK;
+    if (n_threads < 1) n_threads = 1;
+    if (n_threads > 64) n_threads = 64;
+    std::vector<ffhip_vp8l_file> pf((size_t)n);
+    struct Closer { /* the block images are the files' own heap */
+        std::vector<ffhip_vp8l_file> &v;
+        ~Closer() { for (ffhip_vp8l_file &f : v) ffhip_vp8l_close(&f); }
+    } closer{pf};
+    const auto t_open = std::chrono::steady_clock::now();
+    ffhip_parallel_for(n, n_threads, [&](int i) {
+        ffhip_vp8l_file &f = pf[(size_t)i];
+        memset(&f, 0, sizeof(f));
+        status[i] = files[i] && lens[i] ? ffhip_vp8l_open(files[i], lens[i], &f) : FFHIP_EINVAL;
+        if (info_out) info_out[i] = f.info;
+        if (status[i]) return;
+        /* what k_vp8l_finish asks of an output: whole 16-byte stores */
+        if (!d_bgra[i] || ((uintptr_t)d_bgra[i] & 15) || pitch[i] < 4LL * f.info.width || (pitch[i] & 15) || pitch[i] > 0x7fffffffLL) status[i] = FFHIP_EINVAL;
+    });
+    const double open_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_open).count();
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    t_vp8l_last[0] = t_vp8l_last[1] = t_vp8l_last[2] = 0;
+    for (double &t : t_vp8l_times) t = 0;
+    t_vp8l_times[0] = open_ms; /* the headers, transform lists and their sub-images */
+    Vp8lClock clock;
+    const size_t budget = vp8l_part_budget();
+    int rc = FFHIP_OK;
+    for (int i = 0; i < n && rc == FFHIP_OK;) {
+        std::vector<Vp8lPartFile> part;
+        size_t res = 0, side = 0;
+        for (; i < n; i++) {
+            if (status[i]) continue;
+            const ffhip_vp8l_file &f = pf[(size_t)i];
+            const size_t need = vp8l_place(vp8l_res_bytes(f));
+            if (!part.empty() && res + need > budget) break;
+            Vp8lPartFile p{i, res, side, 0, 0};
+            p.cross_off = p.modes_off + (f.device_form ? vp8l_place(4 * (size_t)f.predictor_words) : 0);
+            p.palette_off = p.cross_off + (f.device_form ? vp8l_place(4 * (size_t)f.cross_words) : 0);
+            part.push_back(p);
+            res += need;
+            side += vp8l_side_bytes(f);
+        }
+        if (part.empty()) break;
+        for (Vp8lPartFile &p : part) { p.modes_off += res; p.cross_off += res; p.palette_off += res; }
+        t_vp8l_last[0]++;
+        rc = vp8l_run_part(part, res + side, pf, n_threads, d_bgra, pitch, status, stream, clock);
+        const hipError_t e = hipStreamSynchronize((hipStream_t)stream); /* the next part, and the next call, refill the staging */
+        if (e != hipSuccess) {
+            ffhip_note_hip_error((int)e, "hipStreamSynchronize");
+            if (rc == FFHIP_OK) rc = FFHIP_EIO;
+        } else {
+            clock.add();
+        }
+    }
+    if (rc) return rc;
+    for (int k = 0; k < n; k++)
+        if (status[k]) return status[k];
+    return FFHIP_OK;
+}
+
+extern "C" int ffhip_debug_vp8l_last(int out[3])
+{
+    if (!out) return FFHIP_EINVAL;
+    for (int k = 0; k < 3; k++) out[k] = t_vp8l_last[k];
+    return FFHIP_OK;
+}
+
+extern "C" int ffhip_debug_vp8l_times(double out[4])
+{
+    if (!out) return FFHIP_EINVAL;
+    for (int k = 0; k < 4; k++) out[k] = t_vp8l_times[k];
+    return FFHIP_OK;
+}

@@ -984,3 +984,64 @@ def png_times():
     out = (C.c_double * 4)()
     capi.check(capi.lib().ffhip_debug_png_times(out), "ffhip_debug_png_times")
     return tuple(out)
+
+
+def vp8l_probe(data):
+    """ffhip_vp8l_probe (host, no device, cheap): a lossless WebP file (bytes) -> (width, height, has_alpha) of its VP8L header"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    w, h, a = C.c_int(), C.c_int(), C.c_int()
+    capi.check(capi.lib().ffhip_vp8l_probe(buf.ctypes.data if buf.size else None, buf.size, C.byref(w), C.byref(h), C.byref(a)), "ffhip_vp8l_probe")
+    return w.value, h.value, a.value
+
+
+def vp8l_info(data):
+    """ffhip_vp8l_read_info (host, no device): -> capi.Vp8lInfo: width, height, has_alpha, the transform types in the file's order, block
+    bits, palette size and pixels per word, colour-cache bits, has_meta, residual_width"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    info = capi.Vp8lInfo()
+    capi.check(capi.lib().ffhip_vp8l_read_info(buf.ctypes.data if buf.size else None, buf.size, C.byref(info)), "ffhip_vp8l_read_info")
+    return info
+
+
+def vp8l_picture(data, pitch=None):
+    """ffhip_vp8l_picture (host, no device): the whole decode of a lossless WebP file (bytes), the transforms undone by the functions the
+    kernels compile -> BGRA [h][w][4]"""
+    w, h, _ = vp8l_probe(data)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    pitch = 4 * w if pitch is None else pitch
+    out = np.zeros((h, pitch), np.uint8)
+    capi.check(capi.lib().ffhip_vp8l_picture(buf.ctypes.data, buf.size, out.ctypes.data, pitch), "ffhip_vp8l_picture")
+    return out[:, :4 * w].reshape(h, w, 4)
+
+
+def vp8l_decode_files_device(files, n_threads=8, stream=None, strict=True):
+    """ffhip_vp8l_decode_files_device: lossless WebP files of any sizes (list of bytes) in one call; shape and result of
+    png_decode_files_device: (infos, [host BGRA [h][w][4], alpha included], device buffer), with strict=False the status codes fourth."""
+    def probe(i, f):
+        w, h, _ = vp8l_probe(f)
+        return ((4 * w + 15) & ~15, h, w, h)
+
+    infos = (capi.Vp8lInfo * max(len(files), 1))()
+
+    def call(L, ptrs, lens, n, outs, pitches, status):
+        return L.ffhip_vp8l_decode_files_device(ptrs, lens, n, n_threads, outs, pitches, infos, status, stream)
+
+    images, dout, status = _files_to_pictures(files, probe, call, "ffhip_vp8l_decode_files_device", strict)
+    infos = list(infos)[:len(files)]
+    return (infos, images, dout) if strict else (infos, images, dout, status)
+
+
+def vp8l_last():
+    """ffhip_debug_vp8l_last: (parts, launches of k_vp8l_predict, files inverted on the host) of this thread's last
+    ffhip_vp8l_decode_files_device"""
+    out = (C.c_int * 3)()
+    capi.check(capi.lib().ffhip_debug_vp8l_last(out), "ffhip_debug_vp8l_last")
+    return out[0], out[1], out[2]
+
+
+def vp8l_times():
+    """ffhip_debug_vp8l_times: milliseconds of this thread's last ffhip_vp8l_decode_files_device -- (host stream decode, upload,
+    k_vp8l_predict over its levels, k_vp8l_finish); the last three only while FFHIP_VP8L_TIMES is set"""
+    out = (C.c_double * 4)()
+    capi.check(capi.lib().ffhip_debug_vp8l_times(out), "ffhip_debug_vp8l_times")
+    return tuple(out)

@@ -194,8 +194,8 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
     imposed = _orientations(orientation, len(files))
     oriented = bool(apply_exif_orientation) or imposed is not None
     webp_ex = codec.name == "webp" and pixels == "libwebp"        # the ninth entry: flags = FFHIP_WEBP_PIXELS_LIBWEBP
-    one_entry = webp_ex or codec.name == "png"                    # PNG has ONE entry, with the ninth's tail and flags = 0
-    what = ("ffhip_png_decode_files_tensor" if codec.name == "png" else webp_entry_point(pixels, oriented, bool(targets)) if webp_ex
+    one_entry = webp_ex or codec.name in ("png", "vp8l")          # PNG and lossless WebP have ONE entry each, with the ninth's tail and flags = 0
+    what = (f"ffhip_{codec.name}_decode_files_tensor" if codec.name in ("png", "vp8l") else webp_entry_point(pixels, oriented, bool(targets)) if webp_ex
             else entry_point(codec.name, oriented, den, bool(targets), progressive, flags))
     probe = codec.probe_progressive if progressive else codec.probe
     import torch
@@ -296,6 +296,9 @@ def _png_size(f):
 _PNG = _Codec("png", _png_size, None, ops.png_exif_orientation)
 
 
+_VP8L = _Codec("vp8l", lambda f: ops.vp8l_probe(f)[:2], None, ops.webp_exif_orientation)
+
+
 def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
                            strict=True, size=None, antialias=True, reduce=1, return_reduce=False, apply_exif_orientation=False, orientation=None,
                            return_orientation=False, progressive=False, pixels="reference"):
@@ -363,5 +366,15 @@ def decode_png_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=Non
     decode_webp_to_tensors (the orientation tag is read from the file's eXIf chunk).  A file's display size is its width x height.  The
     tensors have three channels: alpha is dropped, as PIL's convert("RGB") drops it -- ops.png_decode_files_device delivers BGRA with it."""
     return _decode_to_tensors(_PNG, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+                              strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
+                              return_orientation=return_orientation)
+
+
+def decode_webp_lossless_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
+                                    strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False):
+    """ffhip_vp8l_decode_files_tensor: lossless WebP (VP8L) files, the pixels libwebp gives; arguments and result as decode_png_to_tensors
+    (the orientation tag is read from the file's EXIF chunk).  A file's display size is its header's width x height.  The tensors have
+    three channels: alpha is dropped -- ops.vp8l_decode_files_device delivers BGRA with it."""
+    return _decode_to_tensors(_VP8L, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)

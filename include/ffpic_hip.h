@@ -470,7 +470,7 @@ int ffhip_vp8_decode_items(const ffhip_vp8_item *items, int n, void *stream);
  * The contract is the reference's WEBP_load (format/webp.c:2002 on; WEBP_read_frame :1872-1926, read_vp8_ctl_partition :897-935,
  * vp8_decode_mb_header :1277-1450, vp8_get_coefficients :992-1064, vp8_decode_residual_block / _data :1125-1225,
  * coding/booldec.c), bit for bit on the BGRA it produces -- not RFC 6386; ffhip_vp8_bool.h lists where the two differ. */
-#define FFHIP_EWEBP_LOSSLESS (-1001)    /* a VP8L chunk: lossless WebP is not decoded (the reference has a stub)      */
+#define FFHIP_EWEBP_LOSSLESS (-1001)    /* a VP8L chunk: these calls do not decode lossless WebP (the reference has a stub); the "lossless WebP" calls below do */
 #define FFHIP_EWEBP_ANIMATION (-1002)   /* the VP8X animation flag, or an ANIM / ANMF chunk in front of the frame      */
 #define FFHIP_EWEBP_INTER_FRAME (-1003) /* the frame tag says "not a key frame" (webp.c:1877-1880)                     */
 
@@ -1273,6 +1273,79 @@ int ffhip_debug_png_last(int out[2]);
  * and inflate (wall clock), and, measured by events only while FFHIP_PNG_TIMES is set (0 otherwise), [1] the upload, [2] k_png_unfilter
  * over all its levels, [3] k_png_expand. */
 int ffhip_debug_png_times(double out[4]);
+
+/* ---- lossless WebP (ffhip_vp8l.c, ffhip_vp8l_body.h, ffhip_vp8l_gpu.hip) ----
+ * The reference has a stub here, so the pixel rule is libwebp's: the BGRA picture is width x height of the VP8L header, sample for sample
+ * what PIL's Image.open(f).convert("RGBA") gives (libwebp 1.6.0).  Every line below was held against it (tests/test_vp8l_spec.py):
+ *   - container: RIFF/WEBP, chunks padded to even sizes, walked up to the first VP8L; a VP8X chunk in front is accepted when its canvas
+ *     equals the VP8L header's size and refused otherwise; bytes behind the RIFF size, and bytes of the chunk behind the stream's last bit,
+ *     are not looked at; a RIFF size beyond the file is refused;
+ *   - header: 0x2f, 14 bits width - 1, 14 bits height - 1, alpha_is_used, a 3-bit version that must be 0;
+ *   - alpha is the file's where alpha_is_used is set and 255 otherwise, whatever the stream's samples and whatever the VP8X alpha flag;
+ *     colour under alpha 0 is kept as stored;
+ *   - transforms: at most one of each type, in any order, undone last to first; each works at the width left by the colour-indexing
+ *     transforms in front of it (2, 4 or 8 pixels to a word for palettes of up to 16, 4 and 2 entries); a type given twice is refused;
+ *   - predictor: the mode of a block is green & 15 of its pixel, 14 and 15 act as 0 (0xff000000); the 14 modes of the format text; Select
+ *     returns L when sum|T - TL| < sum|L - TL| over the four channels, else T; mode 13's half difference truncates toward zero; pixel
+ *     (0,0) is predicted by 0xff000000, the rest of row 0 by L, column 0 by T; the TR of a row's last pixel is the first pixel of the
+ *     current row;
+ *   - cross-colour: the block's pixel holds green_to_red, green_to_blue, red_to_blue in bits 0..7, 8..15, 16..23, signed; a delta is
+ *     (multiplier x colour) >> 5; blue takes the red already corrected;
+ *   - colour indexing: the palette is stored as differences, per byte, to the entry before; an index beyond the palette gives 0x00000000;
+ *   - prefix codes: canonical, written MSB first into the LSB-first stream; code-length code order 17,18,0,1,..5,16,6,..15; repeat symbols
+ *     16 (the last non-zero length, 8 at the start, 3..6 times), 17 (zeros, 3..10), 18 (zeros, 11..138), a repeat beyond the alphabet
+ *     refused; max_symbol counts the code-length tokens read and is refused beyond the alphabet; a code of ONE symbol, in the simple form
+ *     or not, reads no bits; any other code must be complete; a simple code's symbol beyond its alphabet is dropped, which leaves a code
+ *     of no symbols: refused;
+ *   - five codes a group (green + length prefixes + cache, red, blue, alpha, distance), read green, red, blue, alpha; the meta prefix
+ *     image (the picture itself only) gives a block's group in bits 8..23 of its pixel, and a pixel's group is that of its own position,
+ *     behind a copy too;
+ *   - a length or distance prefix below 4 is value - 1; else extra = (p - 2) >> 1, value = ((2 + (p & 1)) << extra) + bits(extra) + 1;
+ *     distance codes 1..120 are libwebp's (dx, dy) table with dist = max(dx + dy x xsize, 1), code k > 120 is k - 120; copies may overlap
+ *     their own output; a distance beyond the pixels decoded, or a length beyond the image's end, is refused;
+ *   - colour cache: 1..11 bits (0 and 12..15 refused), key (0x1e35a7bd x argb) >> (32 - bits), every pixel -- literal, copied or a cache
+ *     hit -- enters it in order;
+ *   - a stream that has been asked for a bit behind its chunk's end is refused.
+ * FFHIP_EINVAL for everything refused above, for a file that is not RIFF/WEBP or has no VP8L chunk, and for a lossy file (`VP8 `);
+ * FFHIP_EWEBP_ANIMATION for the VP8X animation flag or an ANIM / ANMF chunk in front.  No read goes outside file[0 .. len). */
+typedef struct ffhip_vp8l_info {
+    int32_t width, height, has_alpha;
+    int32_t n_transforms, transforms[4]; /* the types in the file's order: 0 predictor, 1 cross-colour, 2 add-green, 3 colour indexing */
+    int32_t predictor_bits, cross_bits;  /* block size bits 2..9; 0 without the transform */
+    int32_t palette_size, pixels_per_word; /* 0 and 1 without colour indexing */
+    int32_t cache_bits, has_meta;        /* of the residual image: its colour cache (0: none), whether it has a meta prefix image */
+    int32_t residual_width;              /* the width the entropy-coded image has: width, or the packed width */
+} ffhip_vp8l_info;
+/* Host only, cheap: the container and the 5-byte header.  has_alpha: the alpha_is_used bit. */
+int ffhip_vp8l_probe(const uint8_t *file, size_t len, int *width, int *height, int *has_alpha);
+/* Host only, no device needed: the whole decode into bgra (pitch >= 4 x width), the transforms undone by the functions the kernels
+ * compile. */
+int ffhip_vp8l_picture(const uint8_t *file, size_t len, uint8_t *bgra, int64_t pitch);
+/* Host only: the header and the transform list read (their sub-images decoded), and the residual image's first two fields. */
+int ffhip_vp8l_read_info(const uint8_t *file, size_t len, ffhip_vp8l_info *info);
+/* Lossless WebP files of any sizes in one call: shape and per-file contract of ffhip_png_decode_files_device.  d_bgra[i] (16-byte aligned,
+ * pitch[i] >= 4 x width, a multiple of 16) receives file i's width x height BGRA pixels and nothing else.  Host threads decode the prefix
+ * codes, copies and colour cache straight into pinned staging -- a file's RESIDUAL image and the block images beside it; k_vp8l_predict
+ * undoes the predictor in place (one launch per level of 64 rows), k_vp8l_finish undoes the pointwise transforms behind it, expands a
+ * palette and writes the pictures.  A file whose colour indexing is not its first transform is inverted by the host threads and uploaded
+ * as pixels.  The batch goes in PARTS of at most 1 GiB of residual bytes (FFHIP_VP8L_PART_BYTES replaces the figure), a larger file a part
+ * of its own.  status[i] receives each file's code; a refused file writes nothing and every other file is delivered; returns the first
+ * failure.  Argument checks come before anything is enqueued: FFHIP_EINVAL for NULL arrays, then FFHIP_ENODEV.  Synchronises `stream`. */
+int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                   const int64_t *pitch, ffhip_vp8l_info *info_out, int *status, void *stream);
+/* Files to tensors, as ffhip_png_decode_files_tensor: the display picture is width x height, alpha is dropped by the three-channel sink;
+ * out_size == NULL: no resize; orient[i] 1..8, or 0 for the file's EXIF chunk (ffhip_webp_exif_orientation), orient == NULL: every file's
+ * tag; flags must be 0. */
+int ffhip_vp8l_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                   const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                   const int *orient, int *orient_out, unsigned flags, ffhip_vp8l_info *info_out, int *status, void *stream);
+/* Diagnostics: parts, launches of k_vp8l_predict, and files inverted on the host, of the calling thread's last
+ * ffhip_vp8l_decode_files_device. */
+int ffhip_debug_vp8l_last(int out[3]);
+/* Diagnostics (tests/tools/bench_vp8l.py): milliseconds of that call's stages, all its parts together -- [0] the host threads' stream
+ * decode (wall clock), and, measured by events only while FFHIP_VP8L_TIMES is set (0 otherwise), [1] the upload, [2] k_vp8l_predict over
+ * all its levels, [3] k_vp8l_finish. */
+int ffhip_debug_vp8l_times(double out[4]);
 
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
