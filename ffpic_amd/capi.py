@@ -44,6 +44,7 @@ EXPORTS = [
     "ffhip_png_decode_files_tensor", "ffhip_debug_png_last", "ffhip_debug_png_times",
     "ffhip_vp8l_probe", "ffhip_vp8l_read_info", "ffhip_vp8l_picture", "ffhip_vp8l_decode_files_device", "ffhip_vp8l_decode_files_tensor",
     "ffhip_debug_vp8l_last", "ffhip_debug_vp8l_times",
+    "ffhip_webp_alpha_probe", "ffhip_webp_alpha_plane", "ffhip_debug_webp_alpha_last", "ffhip_debug_webp_alpha_times",
 ]
 
 
@@ -51,6 +52,7 @@ FFHIP_EINVAL, FFHIP_ENOMEM, FFHIP_ENODEV, FFHIP_EIO = -22, -12, -19, -5     # in
 FFHIP_JPEG_ACCEPT_PROGRESSIVE, FFHIP_JPEG_MAX_SCANS = 1, 128
 FFHIP_JPEG_PIXELS_LIBJPEG = 0x10
 FFHIP_WEBP_PIXELS_LIBWEBP = 0x10
+FFHIP_WEBP_ALPHA = 0x20
 FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1002, -1003
 
 
@@ -402,6 +404,10 @@ def lib():
                                                  C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci), C.c_uint, C.POINTER(Vp8lInfo), vp, vp]
     L.ffhip_debug_vp8l_last.argtypes = [C.POINTER(ci)]
     L.ffhip_debug_vp8l_times.argtypes = [C.POINTER(C.c_double)]
+    L.ffhip_webp_alpha_probe.argtypes = [vp, sz, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.ffhip_webp_alpha_plane.argtypes = [vp, sz, vp, i64]
+    L.ffhip_debug_webp_alpha_last.argtypes = [C.POINTER(ci)]
+    L.ffhip_debug_webp_alpha_times.argtypes = [C.POINTER(C.c_double)]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

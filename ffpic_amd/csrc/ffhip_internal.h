@@ -123,6 +123,7 @@ enum FfhipScratchKind {
     SCRATCH_JPEG_LIBJPEG = 100,   /* .. + FFHIP_HUFF_PARTS - 1: ffhip_jpeg_recon_items_libjpeg's records, per-workgroup tables and sample planes, pinned records */
     SCRATCH_PNG = 110,           /* .. + 2: ffhip_png_decode_files_device: a part's filtered pictures and palettes (and their pinned copy); k_png_unfilter's records; k_png_expand's records and per-workgroup table (pinned records) */
     SCRATCH_VP8L = 113,          /* .. + 2: ffhip_vp8l_decode_files_device: a part's residual images, block images and palettes (and their pinned copy); k_vp8l_predict's records; k_vp8l_finish's records and per-workgroup table (pinned records) */
+    SCRATCH_WEBP_ALPHA = 116,    /* .. + 5: FFHIP_WEBP_ALPHA: a part's raw planes and lossless planes' residual images (and their pinned copy); k_vp8l_predict's records; k_vp8l_finish's records and table; the scratch pictures and unfiltered planes; k_webp_alpha_unfilter's records; k_webp_alpha_merge's records and table (pinned records) */
     SCRATCH_HUFF_PROG = 90,      /* ffhip_jpeg_progressive_batch_gpu: staged scans, tables, records and work lists (and their pinned copy) */
 };
 
@@ -158,6 +159,11 @@ int vp8_libwebp_color_items(const Vp8LwColorItem *items, int n, void *stream);
 /* ffhip_vp8_decode_items under a rule.  WEBP_RULE_LIBWEBP: levels items without a residual map only; display[i] = the picture's width and height
  * (within its macroblock grid); planes: NULL or per item a triple y, u, v that receives the filtered planes as well */
 int vp8_decode_items_rule(const ffhip_vp8_item *items, int n, int rule, const ffhip_size *display, uint8_t *const *planes, void *stream);
+
+/* FFHIP_WEBP_ALPHA behind the colour of ffhip_webp_decode_files_device_ex (ffhip_webp_alpha_gpu.hip): the files with status[i] == 0 that have an
+ * alpha plane get it in byte 3 of their width x height pixels; a refused plane sets status[i].  Synchronises the stream part by part */
+int webp_alpha_stage(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, int *status,
+                     void *stream);
 
 /* ffhip_vp8_decode_frames (row form) -> ffhip_vp8_predict_loopfilter: the colour conversion the caller enqueues behind the call belongs to
  * it -- a retry has to run it again, behind the filter */

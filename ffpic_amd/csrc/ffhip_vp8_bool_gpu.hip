@@ -318,12 +318,23 @@ extern "C" int ffhip_webp_decode_files_device_ex(const uint8_t *const *files, co
                                                  const int64_t *pitch, uint8_t *const *planes, unsigned flags, ffhip_webp_info *info_out, int *status,
                                                  void *stream)
 {
-    if (flags & ~FFHIP_WEBP_PIXELS_LIBWEBP) return FFHIP_EINVAL;
+    if (flags & ~(FFHIP_WEBP_PIXELS_LIBWEBP | FFHIP_WEBP_ALPHA)) return FFHIP_EINVAL;
     const int rule = (flags & FFHIP_WEBP_PIXELS_LIBWEBP) ? WEBP_RULE_LIBWEBP : WEBP_RULE_REFERENCE;
+    if ((flags & FFHIP_WEBP_ALPHA) && rule != WEBP_RULE_LIBWEBP) return FFHIP_EINVAL; /* the alpha plane goes with libwebp's pixels only */
     if (planes && rule != WEBP_RULE_LIBWEBP) return FFHIP_EINVAL; /* the default rule's file call writes no planes */
     if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    return webp_files_impl(files, lens, n, n_threads, d_bgra, pitch, info_out, nullptr, status, stream, rule, planes);
+    int rc = webp_files_impl(files, lens, n, n_threads, d_bgra, pitch, info_out, nullptr, status, stream, rule, planes);
+    if (!(flags & FFHIP_WEBP_ALPHA)) return rc;
+    /* the colour is what the unflagged call gives; a failure that is no file's own ends the call */
+    int first = FFHIP_OK;
+    for (int k = 0; k < n && !first; k++) first = status[k];
+    if (rc != first) return rc;
+    rc = webp_alpha_stage(files, lens, n, n_threads, d_bgra, pitch, status, stream);
+    if (rc) return rc;
+    for (int k = 0; k < n; k++)
+        if (status[k]) return status[k];
+    return FFHIP_OK;
 }
 
 extern "C" int ffhip_webp_parse_device(const uint8_t *const *files, const size_t *lens, int n, ffhip_webp_parsed *outs, int *status, void *stream)

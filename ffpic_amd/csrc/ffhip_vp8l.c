@@ -9,6 +9,8 @@
  *   image    [colour cache: 1, 4 bits] [meta prefix image: 1, 3 bits, an image -- the picture only] 5 codes a group, then the pixels
  *   code     simple: 1 or 2 symbols of 1 or 8 bits; normal: 4..19 code-length code lengths of 3 bits, [max_symbol], the lengths
  * Every bit read is checked against the end of the chunk: bits behind it read as 0 and the image they were asked for is refused.
+ * ffhip_vp8l_open_stream is the way in for a stream without container, signature and header: the ALPH chunk of a lossy file
+ * (ffhip_webp_alpha.c), whose one exception to the line above is `lenient_end` (ffhip_vp8l_internal.h).
  */
 #include "ffhip_vp8l_internal.h"
 
@@ -298,6 +300,48 @@ static inline uint32_t prefix_value(bits *b, uint32_t p)
     return ((2 + (p & 1)) << extra) + bits_read(b, extra) + 1;
 }
 
+/* ---- the last token of a `lenient` image that ran over the chunk's end, read again as libwebp's reader reads there ----
+ * That reader keeps the chunk's last 8 bytes in a 64-bit window and a position in it; at the end the position is 64.  A fetch takes the
+ * window from (position mod 64) on, zeros above it: a symbol that straddles the end gets zeros, one that begins AT the end gets the last
+ * 8 bytes again.  A read of extra bits, or a refill at position >= 32, that finds the position beyond 64 sets it to 0 and marks the end;
+ * from then on extra bits read as 0 and every refill sets the position to 0 again. */
+typedef struct tail {
+    uint64_t win;
+    unsigned pos;
+    int eos;
+} tail;
+
+static void tail_fill(tail *t)
+{
+    if (t->pos >= 32 && (t->eos || t->pos > 64)) { t->eos = 1; t->pos = 0; }
+}
+static uint32_t tail_bits(tail *t, int n)
+{
+    if (t->eos) { t->pos = 0; return 0; }
+    const uint32_t v = (uint32_t)((t->win >> (t->pos & 63)) & ((1ull << n) - 1));
+    t->pos += (unsigned)n;
+    if (t->pos > 64) { t->eos = 1; t->pos = 0; }
+    return v;
+}
+static uint32_t tail_symbol(tail *t, const code *c, const entry *e)
+{
+    if (c->single >= 0) return (uint32_t)c->single;
+    const entry *root = e + c->root;
+    entry x = root[(t->win >> (t->pos & 63)) & ((1u << ROOT_BITS) - 1)];
+    if (x.bits > 15) {
+        t->pos += ROOT_BITS;
+        x = root[x.value + ((t->win >> (t->pos & 63)) & ((1u << (x.bits - 16)) - 1))];
+    }
+    t->pos += x.bits;
+    return x.value;
+}
+static uint32_t tail_prefix_value(tail *t, uint32_t p)
+{
+    if (p < 4) return p + 1;
+    const int extra = (int)(p - 2) >> 1;
+    return ((2 + (p & 1)) << extra) + tail_bits(t, extra) + 1;
+}
+
 /* the image header's two fields; *meta_bits 0 without a meta prefix image */
 static int image_front(bits *b, int top, int *cache_bits, int *has_meta)
 {
@@ -311,8 +355,9 @@ static int image_front(bits *b, int top, int *cache_bits, int *has_meta)
     return FFHIP_OK;
 }
 
-/* w x h ARGB words into out.  top: the picture's own image, which may have a meta prefix image */
-static int image_read(bits *b, uint32_t w, uint32_t h, int top, uint32_t *out)
+/* w x h ARGB words into out.  top: the picture's own image, which may have a meta prefix image.  lenient: an image without a colour
+ * cache whose red, blue and alpha codes all have one symbol may take the bits of its LAST token from behind the chunk's end */
+static int image_read(bits *b, uint32_t w, uint32_t h, int top, int lenient, uint32_t *out)
 {
     int cache_bits, has_meta, meta_bits = 0;
     int rc = image_front(b, top, &cache_bits, &has_meta);
@@ -328,7 +373,7 @@ static int image_read(bits *b, uint32_t w, uint32_t h, int top, uint32_t *out)
         const uint32_t meta_h = subsample(h, meta_bits);
         meta = (uint32_t *)malloc((size_t)meta_w * meta_h * 4);
         if (!meta) return FFHIP_ENOMEM;
-        rc = image_read(b, meta_w, meta_h, 0, meta);
+        rc = image_read(b, meta_w, meta_h, 0, 0, meta);
         for (size_t k = 0; !rc && k < (size_t)meta_w * meta_h; k++) {
             meta[k] = (meta[k] >> 8) & 0xffffu;
             if (meta[k] >= n_groups) n_groups = meta[k] + 1;
@@ -340,7 +385,12 @@ static int image_read(bits *b, uint32_t w, uint32_t h, int top, uint32_t *out)
     const int alphabet[5] = {256 + 24 + (cache_bits ? 1 << cache_bits : 0), 256, 256, 256, 40};
     for (uint32_t g = 0; !rc && g < n_groups; g++)
         for (int a = 0; !rc && a < 5; a++) rc = code_parse(b, alphabet[a], lengths, &t, &codes[5 * g + a]);
+    if (cache_bits) lenient = 0;
+    for (size_t k = 0; !rc && lenient && k < (size_t)n_groups; k++)
+        if (codes[5 * k + 1].single < 0 || codes[5 * k + 2].single < 0 || codes[5 * k + 3].single < 0) lenient = 0;
     const uint64_t n = (uint64_t)w * h;
+    uint64_t token_at = b->pos, token_i = 0; /* where the last token read began: in the stream, in the image */
+    const code *token_grp = codes;
     const int cache_shift = 32 - cache_bits;
     const uint32_t meta_mask = has_meta ? (1u << meta_bits) - 1 : ~0u;
     const code *grp = codes;
@@ -351,6 +401,9 @@ static int image_read(bits *b, uint32_t w, uint32_t h, int top, uint32_t *out)
         /* up to the end of the group's block, or of the row */
         uint32_t run_end = has_meta ? ((x | meta_mask) + 1 < w ? (x | meta_mask) + 1 : w) : w;
         while (x < run_end) {
+            token_at = b->pos;
+            token_i = i;
+            token_grp = grp;
             const uint32_t s = code_read(&grp[0], t.e, b);
             if (s < 256) {
                 const uint32_t r = code_read(&grp[1], t.e, b), bl = code_read(&grp[2], t.e, b), al = code_read(&grp[3], t.e, b);
@@ -385,9 +438,32 @@ static int image_read(bits *b, uint32_t w, uint32_t h, int top, uint32_t *out)
             }
         }
         if (x == w) { x = 0; y++; }
-        if (bits_over(b)) rc = FFHIP_EINVAL; /* once a row or block: a cut stream is given up early */
+        if (bits_over(b) && i < n) rc = FFHIP_EINVAL; /* once a row or block: a cut stream is given up early */
     }
-    if (!rc && bits_over(b)) rc = FFHIP_EINVAL;
+    if (!rc && bits_over(b) && !(lenient && token_at <= 8ull * b->len)) rc = FFHIP_EINVAL;
+    if (!rc && bits_over(b) && b->len >= 8) { /* a shorter stream: zeros, as read above */
+        tail r = {0, 64 - (unsigned)(8ull * b->len - token_at), 0};
+        memcpy(&r.win, b->p + b->len - 8, 8);
+        tail_fill(&r);
+        const uint32_t s = tail_symbol(&r, &token_grp[0], t.e);
+        if (s < 256) {
+            if (token_i + 1 != n) rc = FFHIP_EINVAL; /* the end is marked now: pixels still to come are refused */
+            out[token_i] = (uint32_t)token_grp[3].single << 24 | (uint32_t)token_grp[1].single << 16 | s << 8 | (uint32_t)token_grp[2].single;
+        } else { /* a copy: the alphabet of an image without a cache ends with the length prefixes */
+            const uint32_t length = tail_prefix_value(&r, s - 256);
+            const uint32_t dsym = tail_symbol(&r, &token_grp[4], t.e);
+            tail_fill(&r);
+            uint32_t d = tail_prefix_value(&r, dsym);
+            if (d > 120) {
+                d -= 120;
+            } else {
+                const int64_t off = (int64_t)short_codes[d - 1][0] + (int64_t)short_codes[d - 1][1] * (int64_t)w;
+                d = off < 1 ? 1u : (uint32_t)off;
+            }
+            if ((uint64_t)d > token_i || (uint64_t)length != n - token_i) rc = FFHIP_EINVAL;
+            for (uint64_t k = token_i; !rc && k < token_i + length; k++) out[k] = out[k - d];
+        }
+    }
     free(meta);
     free(cache);
     free(codes);
@@ -414,12 +490,25 @@ int ffhip_vp8l_open(const uint8_t *file, size_t len, ffhip_vp8l_file *pf)
     memset(pf, 0, sizeof(*pf));
     const uint8_t *body;
     size_t body_len;
+    ffhip_vp8l_info head;
+    memset(&head, 0, sizeof(head));
+    const int rc = vp8l_header(file, len, &body, &body_len, &head);
+    if (rc) return rc;
+    return ffhip_vp8l_open_stream(body + 5, body_len - 5, head.width, head.height, head.has_alpha, 0, pf);
+}
+
+int ffhip_vp8l_open_stream(const uint8_t *stream, size_t len, int32_t width, int32_t height, int32_t has_alpha, int alpha_plane, ffhip_vp8l_file *pf)
+{
+    if (!stream || !pf || width < 1 || height < 1 || width > 16384 || height > 16384) return FFHIP_EINVAL;
+    memset(pf, 0, sizeof(*pf));
     ffhip_vp8l_info *info = &pf->info;
-    int rc = vp8l_header(file, len, &body, &body_len, info);
-    if (rc) { memset(info, 0, sizeof(*info)); return rc; }
-    pf->stream = body + 1;
-    pf->stream_len = body_len - 1;
-    bits b = {pf->stream, pf->stream_len, 32};
+    info->width = width;
+    info->height = height;
+    info->has_alpha = has_alpha;
+    int rc = FFHIP_OK;
+    pf->stream = stream;
+    pf->stream_len = len;
+    bits b = {pf->stream, pf->stream_len, 0};
     const uint32_t h = (uint32_t)info->height;
     uint32_t xs = (uint32_t)info->width;
     unsigned seen = 0;
@@ -443,11 +532,11 @@ int ffhip_vp8l_open(const uint8_t *file, size_t len, ffhip_vp8l_file *pf)
                 pf->cross_image = img; pf->cross_words = bx * by; info->cross_bits = bb;
                 pf->steps.cross_bits = (uint8_t)bb; pf->steps.cross_bx = bx;
             }
-            rc = image_read(&b, bx, by, 0, img);
+            rc = image_read(&b, bx, by, 0, 0, img);
         } else if (type == FFHIP_VP8L_COLOR_INDEXING) {
             const int colours = (int)bits_read(&b, 8) + 1;
             const int bb = vp8l_bundle_bits(colours);
-            rc = image_read(&b, (uint32_t)colours, 1, 0, pf->palette);
+            rc = image_read(&b, (uint32_t)colours, 1, 0, 0, pf->palette);
             for (int c = 1; !rc && c < colours; c++) pf->palette[c] = ffhip_vp8l_add(pf->palette[c], pf->palette[c - 1]);
             info->palette_size = colours;
             info->pixels_per_word = 1 << bb;
@@ -468,6 +557,7 @@ int ffhip_vp8l_open(const uint8_t *file, size_t len, ffhip_vp8l_file *pf)
         memset(info, 0, sizeof(*info));
         return rc;
     }
+    pf->lenient_end = alpha_plane && info->n_transforms == 1 && info->transforms[0] == FFHIP_VP8L_COLOR_INDEXING;
     /* the device form: the steps in the order they are undone, last transform first, colour indexing behind them all */
     ffhip_vp8l_steps *s = &pf->steps;
     s->has_alpha = (uint8_t)info->has_alpha;
@@ -502,7 +592,7 @@ int ffhip_vp8l_read_info(const uint8_t *file, size_t len, ffhip_vp8l_info *info)
 int ffhip_vp8l_read_residual(const ffhip_vp8l_file *pf, uint32_t *residual)
 {
     bits b = {pf->stream, pf->stream_len, pf->image_bit};
-    return image_read(&b, (uint32_t)pf->info.residual_width, (uint32_t)pf->info.height, 1, residual);
+    return image_read(&b, (uint32_t)pf->info.residual_width, (uint32_t)pf->info.height, 1, pf->lenient_end, residual);
 }
 
 int ffhip_vp8l_invert_host(const ffhip_vp8l_file *pf, uint32_t *residual, uint32_t *argb)

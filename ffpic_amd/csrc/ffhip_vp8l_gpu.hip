@@ -226,8 +226,6 @@ struct Vp8lClock {
     }
 };
 
-size_t vp8l_place(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
 size_t vp8l_part_budget()
 {
     const char *v = FFHIP_ENV("FFHIP_VP8L_PART_BYTES");
@@ -235,55 +233,63 @@ size_t vp8l_part_budget()
     return b > 0 ? (size_t)b : (size_t)1 << 30;
 }
 
-/* a file's place in its part's staging: the residual image (a host-form file: its finished pixels), then what the kernels read beside it */
-struct Vp8lPartFile { int idx; size_t res_off, modes_off, cross_off, palette_off; };
+} // namespace
 
-size_t vp8l_res_bytes(const ffhip_vp8l_file &f)
+static size_t vp8l_place(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+static size_t vp8l_res_bytes(const ffhip_vp8l_file &f)
 {
     return 4 * (size_t)(f.device_form ? f.info.residual_width : f.info.width) * (size_t)f.info.height;
 }
-size_t vp8l_side_bytes(const ffhip_vp8l_file &f)
+static size_t vp8l_side_bytes(const ffhip_vp8l_file &f)
 {
     if (!f.device_form) return 0;
     return vp8l_place(4 * (size_t)f.predictor_words) + vp8l_place(4 * (size_t)f.cross_words) + (f.steps.has_index ? 1024 : 0);
 }
 
-/* One part: files pf[] of the call, `bytes` of staging */
-int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std::vector<ffhip_vp8l_file> &pf, int n_threads, uint8_t *const *d_bgra,
-                  const int64_t *pitch, int *status, void *stream, Vp8lClock &clock)
+size_t vp8l_part_add(std::vector<Vp8lPartFile> &part, const ffhip_vp8l_file &f, int idx, size_t *res, size_t *side)
+{
+    Vp8lPartFile p{idx, *res, *side, 0, 0};
+    p.cross_off = p.modes_off + (f.device_form ? vp8l_place(4 * (size_t)f.predictor_words) : 0);
+    p.palette_off = p.cross_off + (f.device_form ? vp8l_place(4 * (size_t)f.cross_words) : 0);
+    part.push_back(p);
+    *res += vp8l_place(vp8l_res_bytes(f));
+    *side += vp8l_side_bytes(f);
+    return *res + *side;
+}
+
+void vp8l_part_seal(std::vector<Vp8lPartFile> &part, size_t res)
+{
+    for (Vp8lPartFile &p : part) { p.modes_off += res; p.cross_off += res; p.palette_off += res; }
+}
+
+int vp8l_stage_file(const ffhip_vp8l_file &f, const Vp8lPartFile &p, uint8_t *pin)
+{
+    if (f.device_form) {
+        const int rc = ffhip_vp8l_read_residual(&f, (uint32_t *)(pin + p.res_off));
+        if (f.predictor_words) memcpy(pin + p.modes_off, f.predictor_image, 4 * (size_t)f.predictor_words);
+        if (f.cross_words) memcpy(pin + p.cross_off, f.cross_image, 4 * (size_t)f.cross_words);
+        if (f.steps.has_index) memcpy(pin + p.palette_off, f.palette, 1024);
+        return rc;
+    }
+    /* colour indexing behind another transform: every step on the host, the pixels uploaded */
+    uint32_t *res = (uint32_t *)malloc(4 * (size_t)f.info.residual_width * (size_t)f.info.height);
+    int rc = res ? ffhip_vp8l_read_residual(&f, res) : FFHIP_ENOMEM;
+    if (!rc) rc = ffhip_vp8l_invert_host(&f, res, (uint32_t *)(pin + p.res_off));
+    free(res);
+    return rc;
+}
+
+int vp8l_enqueue_part(const std::vector<Vp8lPartFile> &part, uint8_t *dev, const ffhip_vp8l_file *pf, uint8_t *const *d_bgra, const int64_t *pitch,
+                      const int *status, void *stream, int kind, int counts[2], const std::function<void(int)> &mark)
 {
     hipStream_t st = (hipStream_t)stream;
-    for (int k = 0; k < 4; k++) clock.mark(k, st); /* a part that launches nothing has empty intervals */
-    uint8_t *pin = ffhip_pinned_scratch(SCRATCH_VP8L, stream, bytes + 64);
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_VP8L, stream, bytes / 4 + 16);
-    if (!pin || !dev) return FFHIP_ENOMEM;
-    const auto t0 = std::chrono::steady_clock::now();
-    ffhip_parallel_for((int)part.size(), n_threads, [&](int k) {
-        const Vp8lPartFile &p = part[(size_t)k];
-        const ffhip_vp8l_file &f = pf[(size_t)p.idx];
-        if (f.device_form) {
-            status[p.idx] = ffhip_vp8l_read_residual(&f, (uint32_t *)(pin + p.res_off));
-            if (f.predictor_words) memcpy(pin + p.modes_off, f.predictor_image, 4 * (size_t)f.predictor_words);
-            if (f.cross_words) memcpy(pin + p.cross_off, f.cross_image, 4 * (size_t)f.cross_words);
-            if (f.steps.has_index) memcpy(pin + p.palette_off, f.palette, 1024);
-            return;
-        }
-        /* colour indexing behind another transform: every step on the host, the pixels uploaded */
-        uint32_t *res = (uint32_t *)malloc(4 * (size_t)f.info.residual_width * (size_t)f.info.height);
-        status[p.idx] = res ? ffhip_vp8l_read_residual(&f, res) : FFHIP_ENOMEM;
-        if (!status[p.idx]) status[p.idx] = ffhip_vp8l_invert_host(&f, res, (uint32_t *)(pin + p.res_off));
-        free(res);
-    });
-    t_vp8l_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    clock.mark(0, st);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    for (int k = 1; k < 4; k++) clock.mark(k, st);
     std::vector<Vp8lPredDesc> pred;
     std::vector<Vp8lFinDesc> fin;
     unsigned long long total = 0;
     for (const Vp8lPartFile &p : part) {
         if (status[p.idx]) continue;
-        const ffhip_vp8l_file &f = pf[(size_t)p.idx];
+        const ffhip_vp8l_file &f = pf[p.idx];
         Vp8lFinDesc e;
         memset(&e, 0, sizeof(e));
         e.res = (const u32 *)(dev + p.res_off);
@@ -312,7 +318,7 @@ int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std
                 pred.push_back(u);
             }
         } else {
-            t_vp8l_last[2]++;
+            counts[1]++;
         }
         e.first_wg = (u32)total;
         e.n_wgs = (u32)(((unsigned long long)e.groups_x * e.height + VP8L_FINISH_THREADS - 1) / VP8L_FINISH_THREADS); /* < 2^20: both sides at most 2^14 */
@@ -327,7 +333,7 @@ int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std
          * workgroups [0, cnt(l)) of the records themselves */
         std::stable_sort(pred.begin(), pred.end(), [](const Vp8lPredDesc &x, const Vp8lPredDesc &y) { return x.n_bands > y.n_bands; });
         uint8_t *d_pred = nullptr;
-        rc = ffhip_items_stage(SCRATCH_VP8L + 1, stream, pred.data(), pred.size() * sizeof(Vp8lPredDesc), 0, 0, &d_pred);
+        rc = ffhip_items_stage(kind + 1, stream, pred.data(), pred.size() * sizeof(Vp8lPredDesc), 0, 0, &d_pred);
         if (rc) return rc;
         size_t cnt = pred.size();
         for (u32 level = 0; level < pred[0].n_bands; level++) {
@@ -338,20 +344,46 @@ int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std
                 hipLaunchKernelGGL(k_vp8l_predict, dim3(grid_x), dim3(VP8L_BAND), 0, st, a);
             });
             if (rc) return rc;
-            t_vp8l_last[1]++;
+            counts[0]++;
         }
     }
-    for (int k = 2; k < 4; k++) clock.mark(k, st);
+    mark(2);
     const Vp8lFinDesc *d_fin = nullptr;
     u32 *d_table = nullptr;
-    rc = ffhip_items_upload(SCRATCH_VP8L + 2, stream, fin, total, &d_fin, &d_table);
+    rc = ffhip_items_upload(kind + 2, stream, fin, total, &d_fin, &d_table);
     if (rc) return rc;
     rc = ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
         Vp8lFinArgs a;
         a.desc = d_fin; a.wg_item = d_table; a.wg_base = wg_base;
         hipLaunchKernelGGL(k_vp8l_finish, dim3(grid_x), dim3(VP8L_FINISH_THREADS), 0, st, a);
     });
-    clock.mark(3, st);
+    mark(3);
+    return rc;
+}
+
+namespace {
+
+/* One part: files pf[] of the call, `bytes` of staging */
+int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std::vector<ffhip_vp8l_file> &pf, int n_threads, uint8_t *const *d_bgra,
+                  const int64_t *pitch, int *status, void *stream, Vp8lClock &clock)
+{
+    hipStream_t st = (hipStream_t)stream;
+    for (int k = 0; k < 4; k++) clock.mark(k, st); /* a part that launches nothing has empty intervals */
+    uint8_t *pin = ffhip_pinned_scratch(SCRATCH_VP8L, stream, bytes + 64);
+    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_VP8L, stream, bytes / 4 + 16);
+    if (!pin || !dev) return FFHIP_ENOMEM;
+    const auto t0 = std::chrono::steady_clock::now();
+    ffhip_parallel_for((int)part.size(), n_threads, [&](int k) { status[part[(size_t)k].idx] = vp8l_stage_file(pf[(size_t)part[(size_t)k].idx], part[(size_t)k], pin); });
+    t_vp8l_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    clock.mark(0, st);
+    FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
+    for (int k = 1; k < 4; k++) clock.mark(k, st);
+    int counts[2] = {0, 0};
+    const int rc = vp8l_enqueue_part(part, dev, pf.data(), d_bgra, pitch, status, stream, SCRATCH_VP8L, counts, [&](int k) {
+        for (int j = k; j < 4; j++) clock.mark(j, st);
+    });
+    t_vp8l_last[1] += counts[0];
+    t_vp8l_last[2] += counts[1];
     return rc;
 }
 
@@ -393,17 +425,11 @@ extern "C" int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const
         for (; i < n; i++) {
             if (status[i]) continue;
             const ffhip_vp8l_file &f = pf[(size_t)i];
-            const size_t need = vp8l_place(vp8l_res_bytes(f));
-            if (!part.empty() && res + need > budget) break;
-            Vp8lPartFile p{i, res, side, 0, 0};
-            p.cross_off = p.modes_off + (f.device_form ? vp8l_place(4 * (size_t)f.predictor_words) : 0);
-            p.palette_off = p.cross_off + (f.device_form ? vp8l_place(4 * (size_t)f.cross_words) : 0);
-            part.push_back(p);
-            res += need;
-            side += vp8l_side_bytes(f);
+            if (!part.empty() && res + vp8l_place(vp8l_res_bytes(f)) > budget) break;
+            vp8l_part_add(part, f, i, &res, &side);
         }
         if (part.empty()) break;
-        for (Vp8lPartFile &p : part) { p.modes_off += res; p.cross_off += res; p.palette_off += res; }
+        vp8l_part_seal(part, res);
         t_vp8l_last[0]++;
         rc = vp8l_run_part(part, res + side, pf, n_threads, d_bgra, pitch, status, stream, clock);
         const hipError_t e = hipStreamSynchronize((hipStream_t)stream); /* the next part, and the next call, refill the staging */

@@ -824,7 +824,7 @@ def webp_parse_device(files, stream=None, pixels="reference"):
     return _webp_parse_many(files, lambda ptrs, lens, n, outs, status: L.ffhip_webp_parse_device(ptrs, lens, n, outs, status, stream))
 
 
-def webp_decode_files_device(files, n_threads=8, stream=None, strict=True, crop=True, pixels="reference", planes=False):
+def webp_decode_files_device(files, n_threads=8, stream=None, strict=True, crop=True, pixels="reference", planes=False, alpha=False):
     """ffhip_webp_decode_files_device: lossy WebP files of any sizes (list of bytes) in one call.  Every picture gets its place in ONE
     device allocation, at a 16-byte-aligned offset with the pitch 64 x its macroblock columns.  Returns (infos, [host BGRA [h][w][4]
     cropped to the probe's width x height (crop=False: the decoded 16*mbrows x 16*mbcols)], device buffer); with strict=False a
@@ -832,10 +832,15 @@ def webp_decode_files_device(files, n_threads=8, stream=None, strict=True, crop=
     pixels='libwebp': ffhip_webp_decode_files_device_ex with FFHIP_WEBP_PIXELS_LIBWEBP -- libwebp's pixels (PIL's, a browser's) instead of
     the reference's; only the probe's width x height are written, so crop=False shows unwritten bytes beyond them.
     planes=True (needs pixels='libwebp'): a last element follows, per file (y, u, v) -- the loop-filtered planes of its macroblock grid --
-    or None for a failing file."""
+    or None for a failing file.
+    alpha=True (needs pixels='libwebp'): FFHIP_WEBP_ALPHA -- a file with an alpha plane gets it in byte 3 of its pixels."""
     flags = webp_pixel_flags(pixels)
     if planes and not flags:
         raise ValueError("planes=True needs pixels='libwebp'")
+    if alpha and not flags:
+        raise ValueError("alpha=True needs pixels='libwebp'")
+    if alpha:
+        flags |= capi.FFHIP_WEBP_ALPHA
 
     grids = []
 
@@ -909,6 +914,42 @@ def webp_libwebp_color(y, u, v, pitch=None):
     capi.check(capi.lib().ffhip_webp_libwebp_color(y.ctypes.data, w, u.ctypes.data, v.ctypes.data, u.shape[1], w, h, out.ctypes.data, pitch),
                "ffhip_webp_libwebp_color")
     return out[:, :4 * w].reshape(h, w, 4)
+
+
+def webp_alpha_probe(data):
+    """ffhip_webp_alpha_probe (host, no device, cheap): a lossy WebP file (bytes) -> (has_alpha, compression, filter, pre_processing) of
+    the ALPH chunk FFHIP_WEBP_ALPHA would decode; has_alpha 0 for a file the flag leaves opaque"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    v = [C.c_int() for _ in range(4)]
+    capi.check(capi.lib().ffhip_webp_alpha_probe(buf.ctypes.data if buf.size else None, buf.size, *[C.byref(x) for x in v]), "ffhip_webp_alpha_probe")
+    return tuple(x.value for x in v)
+
+
+def webp_alpha_plane(data, pitch=None):
+    """ffhip_webp_alpha_plane (host, no device): the whole alpha decode of a lossy WebP file (bytes), the filter undone by the function
+    k_webp_alpha_unfilter compiles -> uint8 [h][w]"""
+    w, h, _, _ = webp_probe(data, "libwebp")
+    buf = np.frombuffer(data, dtype=np.uint8)
+    pitch = w if pitch is None else pitch
+    out = np.zeros((h, pitch), np.uint8)
+    capi.check(capi.lib().ffhip_webp_alpha_plane(buf.ctypes.data, buf.size, out.ctypes.data, pitch), "ffhip_webp_alpha_plane")
+    return out[:, :w]
+
+
+def webp_alpha_last():
+    """ffhip_debug_webp_alpha_last: (files with a plane, lossless ones among them, launches of k_webp_alpha_unfilter, parts) of this
+    thread's last webp_decode_files_device(..., alpha=True)"""
+    out = (C.c_int * 4)()
+    capi.check(capi.lib().ffhip_debug_webp_alpha_last(out), "ffhip_debug_webp_alpha_last")
+    return tuple(out)
+
+
+def webp_alpha_times():
+    """ffhip_debug_webp_alpha_times: milliseconds of that call's alpha stage -- (host walk, copies and stream decode; upload and the lossless
+    planes' two kernels; k_webp_alpha_unfilter over its levels; k_webp_alpha_merge); the last three only while FFHIP_WEBP_ALPHA_TIMES is set"""
+    out = (C.c_double * 4)()
+    capi.check(capi.lib().ffhip_debug_webp_alpha_times(out), "ffhip_debug_webp_alpha_times")
+    return tuple(out)
 
 
 def webp_last_parts():

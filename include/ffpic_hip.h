@@ -605,7 +605,8 @@ int ffhip_debug_webp_last_parts(int out[2]);
  *     edges taken at the DISPLAY width and height; the alpha byte is 255, as the default rule writes it.
  * Where the first IDCT pass leaves 16 bits there is no single libwebp picture: its C transform keeps int, its SIMD transforms saturate or
  * wrap at 16 bits.  The rule follows the witness, tests/vp8_spec.py with rules=SPEC, i.e. the C transform; no encoder
- * writes such a stream.  A file with an `ALPH` chunk decodes its colour; the alpha plane is ignored.
+ * writes such a stream.  A file with an `ALPH` chunk decodes its colour; the alpha plane is ignored unless FFHIP_WEBP_ALPHA asks for it
+ * ("lossy WebP, the alpha plane" below).
  * The verdicts stay: FFHIP_EWEBP_LOSSLESS / _ANIMATION / _INTER_FRAME, and FFHIP_EINVAL for a partition asked for a byte beyond its length
  * (under the rule no valid file of the libwebp corpus, tests/golden/webp_libwebp.npz, gets it).
  * flags == 0 is the plain call, bit for bit; any other bit is FFHIP_EINVAL.  Argument errors come before FFHIP_ENODEV, both before the first
@@ -617,7 +618,7 @@ int ffhip_webp_parse_ex(const uint8_t *file, size_t len, unsigned flags, ffhip_w
 /* the device twin of ffhip_webp_parse_ex (as ffhip_webp_parse_device is ffhip_webp_parse's) */
 int ffhip_webp_parse_device_ex(const uint8_t *const *files, const size_t *lens, int n, unsigned flags, ffhip_webp_parsed *outs, int *status,
                                void *stream);
-/* ffhip_webp_decode_files_device under `flags`.  Buffers as there, with the _ex probe's mbcols and mbrows (pitch >= 64*mbcols, room for
+/* ffhip_webp_decode_files_device under `flags` (FFHIP_WEBP_PIXELS_LIBWEBP, with it FFHIP_WEBP_ALPHA).  Buffers as there, with the _ex probe's mbcols and mbrows (pitch >= 64*mbcols, room for
  * 16*mbrows rows), so a caller switches rules without new arithmetic; under the rule only `height` rows of `width` pixels are written.
  * planes: NULL, or [n] triples of device pointers y, u, v (16*mbcols x 16*mbrows and 8*mbcols x 8*mbrows samples, strides 16*mbcols and
  * 8*mbcols, 4-byte aligned): the loop-filtered planes of each file's macroblock grid are delivered too, which lets a caller name the plane and
@@ -645,6 +646,53 @@ int ffhip_debug_vp8_decode_items_libwebp(const ffhip_vp8_item *items, int n, con
 int ffhip_debug_vp8_upsample_color(const uint8_t *d_y, const uint8_t *d_u, const uint8_t *d_v, int ys, int uvs, int width, int height,
                                    int n_images, int64_t plane_stride_y, int64_t plane_stride_uv, uint8_t *d_bgra, int64_t pitch,
                                    int64_t image_stride, void *stream);
+
+/* ---- lossy WebP, the alpha plane (opt-in; ffhip_webp_alpha.c, ffhip_webp_alpha_body.h, ffhip_webp_alpha_gpu.hip) ----
+ * FFHIP_WEBP_ALPHA is accepted together with FFHIP_WEBP_PIXELS_LIBWEBP by ffhip_webp_decode_files_device_ex and by no other call: without
+ * the libwebp bit, and on the probe, parse, parse_device and tensor calls (whose three-channel sink would drop alpha), it is FFHIP_EINVAL
+ * as any unknown bit is.  Without the bit every call keeps its bytes and its verdicts.  With it, a file that has a VP8X chunk with the
+ * alpha flag (0x10) set and an ALPH chunk between it and the `VP8 ` chunk gets that plane in byte 3 of its width x height pixels, sample
+ * for sample what PIL's Image.open(f).convert("RGBA") gives (libwebp 1.6.0); the colour bytes are those of the unflagged call (no
+ * premultiplication).  Every other file is exactly what the unflagged call gives: alpha 255, the same status.  The rule, each line held
+ * against PIL (tests/test_webp_alpha_spec.py):
+ *   - the chunk walk is the libwebp rule's, padding byte included; the frame tag's width x height is the plane's size;
+ *   - ALPH payload byte 0: reserved (2 bits) | pre-processing (2) | filter (2) | compression (2), bits 7..0.  Compression 2 or 3,
+ *     pre-processing 2 or 3 and a reserved bit set are refused, an empty payload too; pre-processing 1 changes nothing in the decode;
+ *   - compression 0: width x height bytes behind the header byte; fewer are refused, more are ignored;
+ *   - compression 1: a VP8L stream without signature and header that starts at the first transform bit ("lossless WebP" below, every
+ *     line of it), width and height the picture's; the stored sample is the green byte of each decoded ARGB word;
+ *   - filters, sums modulo 256 on the FINISHED plane: 0 none; row 0, or filter 1, the sample to the left, for x = 0 the one above and 0
+ *     at (0, 0); filter 2 the sample above; filter 3 clip255(left + above - above left); under 2 and 3 column 0 takes the sample above;
+ *   - a stream that asks for bits behind its chunk's end (they read as 0) is refused, as a VP8L file's is -- settled on truncated copies
+ *     with ONE exception: libwebp decodes a stream whose only transform is colour indexing, without a colour cache and with one-symbol
+ *     red, blue and alpha codes in every group, by a loop of its own, and that loop accepts the image when the LAST token (literal or
+ *     copy) is the one that ran over the end.  Such a stream is accepted here too, and the token is what libwebp's reader makes of it:
+ *     that reader keeps the chunk's last 8 bytes in a 64-bit window, so a symbol that straddles the end gets zeros and a token that
+ *     begins exactly at the end reads those 8 bytes again (ffhip_vp8l.c, tail_*); a stream of fewer than 8 bytes reads zeros.
+ * Named deviations, beside the one that the VP8X canvas is not compared with the frame tag: PIL refuses an ALPH chunk in a file without
+ * VP8X, an ALPH chunk behind the `VP8 ` chunk, and a second ALPH chunk; here the first two files stay opaque and of several ALPH chunks
+ * the first counts -- the flag never makes a container check stricter.  With the VP8X alpha flag clear PIL, too, ignores the chunk.
+ * A file whose ALPH chunk is refused gets FFHIP_EINVAL in status[i] and no promised bytes; every other file is delivered; the call returns
+ * the first failure.  The stage runs behind the colour, in parts of its own (1 GiB of staging and scratch; FFHIP_WEBP_ALPHA_PART_BYTES
+ * replaces the figure): host threads copy raw planes and decode lossless planes' prefix codes into pinned staging, k_vp8l_predict and
+ * k_vp8l_finish write the lossless planes into scratch pictures, k_webp_alpha_unfilter (one launch per level of 64 rows; none for
+ * filter 0) undoes the filter and k_webp_alpha_merge writes byte 3.  Synchronises `stream`, as the unflagged call does. */
+#define FFHIP_WEBP_ALPHA 0x20u
+/* Host only, cheap: the chunk walk and the header byte.  *has_alpha 0 with FFHIP_OK for a file the flag would leave opaque (the other
+ * three are 0 then); the libwebp rule's probe verdicts for a file it refuses, FFHIP_EINVAL for a refused header byte or a short raw plane. */
+int ffhip_webp_alpha_probe(const uint8_t *file, size_t len, int *has_alpha, int *compression, int *filter, int *pre_processing);
+/* Host only, no device needed: the whole alpha decode into width x height bytes at `alpha` (pitch >= width; the libwebp rule's probe
+ * gives the size), the filter undone by the function the kernel compiles.  It is to FFHIP_WEBP_ALPHA what ffhip_vp8l_picture is to the
+ * lossless file call.  FFHIP_EINVAL for everything refused above and for a file without a plane.  No read goes outside file[0 .. len). */
+int ffhip_webp_alpha_plane(const uint8_t *file, size_t len, uint8_t *alpha, int64_t pitch);
+/* Diagnostics, of the calling thread's last call with FFHIP_WEBP_ALPHA: files with a plane, how many of those were lossless, launches of
+ * k_webp_alpha_unfilter, parts. */
+int ffhip_debug_webp_alpha_last(int out[4]);
+/* Diagnostics (tests/tools/bench_webp_alpha.py): milliseconds of that call's alpha stage, all its parts together -- [0] the host threads'
+ * walk, copies and stream decode (wall clock), and, measured by events only while FFHIP_WEBP_ALPHA_TIMES is set (0 otherwise), [1] the
+ * upload with the lossless planes' k_vp8l_predict and k_vp8l_finish, [2] k_webp_alpha_unfilter over all its levels, [3]
+ * k_webp_alpha_merge. */
+int ffhip_debug_webp_alpha_times(double out[4]);
 
 /* ---- HEVC intra prediction + reconstruction for a list of transform units ----
  * decode_intra_block steps 5-10 (coding/hevc.c:4730-4790) for every TU of a picture:
