@@ -45,6 +45,7 @@ EXPORTS = [
     "ffhip_vp8l_probe", "ffhip_vp8l_read_info", "ffhip_vp8l_picture", "ffhip_vp8l_decode_files_device", "ffhip_vp8l_decode_files_tensor",
     "ffhip_debug_vp8l_last", "ffhip_debug_vp8l_times",
     "ffhip_webp_alpha_probe", "ffhip_webp_alpha_plane", "ffhip_debug_webp_alpha_last", "ffhip_debug_webp_alpha_times",
+    "ffhip_debug_scratch_fill",
 ]
 
 
@@ -408,6 +409,7 @@ def lib():
     L.ffhip_webp_alpha_plane.argtypes = [vp, sz, vp, i64]
     L.ffhip_debug_webp_alpha_last.argtypes = [C.POINTER(ci)]
     L.ffhip_debug_webp_alpha_times.argtypes = [C.POINTER(C.c_double)]
+    L.ffhip_debug_scratch_fill.argtypes = [vp, ci, C.POINTER(C.c_uint64), C.POINTER(ci), ci]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long
     _lib = L

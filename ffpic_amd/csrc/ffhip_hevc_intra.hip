@@ -1435,6 +1435,12 @@ extern "C" int ffhip_debug_hevc_plan_result(uint32_t out[8])
     FFHIP_CHECK(hipMemcpy(out, g_last_plan_result, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost), FFHIP_EIO);
     return FFHIP_OK;
 }
+/* for ffhip_debug_scratch_fill: the words above lie in the scratch of `stream`, which is about to be overwritten -- the calling thread's
+ * record of them goes, and ffhip_debug_hevc_plan_result says FFHIP_EINVAL until the thread's next device-planned call */
+void ffhip_hevc_plan_result_forget(void *stream)
+{
+    if (g_last_plan_result && g_last_plan_stream == (hipStream_t)stream) g_last_plan_result = nullptr;
+}
 
 /* One call of ffhip_hevc_intra_recon -- or the early pre-pass of ffhip_hevc_intra_recon_tiles --: what its validation and its three paths
  * share.  `st` takes everything in front of the grouped kernel: the caller's stream, or a stream of the library's own, behind which the

@@ -96,7 +96,8 @@ __device__ __forceinline__ int ffhip_load_s16_sc1(__amdgpu_buffer_rsrc_t r, int 
 }
 #endif
 
-/* Kinds of ffhip_scratch / ffhip_pinned_scratch: a (kind, device, stream) owns its buffer.  ".. + n": the kind's sub-slots go up to kind + n. */
+/* Kinds of ffhip_scratch / ffhip_pinned_scratch: a (kind, device, stream) owns its buffer.  ".. + n": the kind's sub-slots go up to kind + n.
+ * (tests/test_scratch_fill_gpu.py reads this enum, ranges included: a kind added here needs a case there that runs on its buffer behind a fill.) */
 enum FfhipScratchKind {
     SCRATCH_VP8_PRED = 1,
     SCRATCH_VP8_LF = 2,
@@ -305,6 +306,8 @@ extern std::mutex g_ffhip_state_mu;
 FfhipStreamState *ffhip_stream_state(void *stream, bool make = true);
 void ffhip_state_release(void); /* no call of any thread in flight: empties both registries and the pipeline's slots */
 void ffhip_pipeline_release(void); /* ffhip_pipeline.hip: its two slots of pinned + device buffers */
+int ffhip_pipeline_fill(int value, uint64_t bytes[2]); /* ffhip_pipeline.hip, for ffhip_debug_scratch_fill: every byte of both slots' buffers */
+void ffhip_hevc_plan_result_forget(void *stream); /* ffhip_hevc_intra.hip, for ffhip_debug_scratch_fill: the calling thread's pointer to its last plan's verdict in `stream`'s scratch */
 int ffhip_vp8_side_by_side_retry(void *stream); /* ffhip_vp8_lf.hip, for ffhip_stream_sync: 0 nothing reported by a side-by-side call of this
                                                    stream, FFHIP_RETRIED repeated, FFHIP_EIO */
 struct jpeg_hdr *ffhip_huff_hdr_records(size_t n); /* the calling thread's header records, room for at least n, kept between calls; NULL: no memory */

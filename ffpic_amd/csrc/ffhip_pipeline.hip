@@ -147,6 +147,27 @@ void ffhip_pipeline_release(void)
     }
 }
 
+/* ffhip_debug_scratch_fill's share of the slots: every byte of every buffer of both, each slot after its own stream has drained;
+ * bytes[0] += device bytes, bytes[1] += pinned bytes.  The streams themselves and first / count are state, not scratch */
+int ffhip_pipeline_fill(int value, uint64_t bytes[2])
+{
+    std::lock_guard<std::mutex> lock(g_pipe_mu);
+    for (int s = 0; s < 2; s++) {
+        Slot &sl = g_slot[s];
+        if (!sl.st) continue; /* never prepared: it holds nothing */
+        FFHIP_CHECK(hipStreamSynchronize(sl.st), FFHIP_EIO);
+        const struct { void *h, *d; size_t cap; } pairs[] = {{sl.h_y, sl.d_y, sl.cap_y}, {sl.h_u, sl.d_u, sl.cap_c}, {sl.h_v, sl.d_v, sl.cap_c},
+                                                              {sl.h_q, sl.d_q, sl.cap_q}, {nullptr, sl.d_out, sl.cap_out}, {sl.h_out, nullptr, sl.cap_hout}};
+        for (const auto &p : pairs) {
+            if (!p.cap) continue;
+            if (p.d) { FFHIP_CHECK(hipMemsetAsync(p.d, value, p.cap, sl.st), FFHIP_EIO); bytes[0] += p.cap; }
+            if (p.h) { memset(p.h, value, p.cap); bytes[1] += p.cap; }
+        }
+        FFHIP_CHECK(hipStreamSynchronize(sl.st), FFHIP_EIO);
+    }
+    return FFHIP_OK;
+}
+
 extern "C" void *ffhip_host_malloc(size_t bytes)
 {
     void *p = nullptr;

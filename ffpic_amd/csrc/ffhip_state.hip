@@ -3,12 +3,13 @@
  *   per (device, stream): device scratch and pinned staging per kind, the VP8 retry record, the HEVC tile guard;
  *   per (thread, device): the side stream and the other streams and events of the calls that fork work off the caller's stream,
  *   and per thread the Huffman decoder's header records.
- * One path (ffhip_state_release) empties both, with the pipeline's slots.
+ * One path (ffhip_state_release) empties both, with the pipeline's slots; one test hook (ffhip_debug_scratch_fill) overwrites what they hold.
  */
 #include "ffhip_internal.h"
 #include "ffhip_entropy_internal.h"
 
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <memory>
@@ -214,6 +215,69 @@ struct jpeg_hdr *ffhip_huff_hdr_records(size_t n)
         t.hdr_cap = t.hdr ? n + n / 4 : 0;
     }
     return t.hdr.get();
+}
+
+/* ---- diagnostics: the contents of what is kept, set by a test (include/ffpic_hip.h) ----
+ * Scratch is (current device, stream)'s device and pinned buffers over their whole capacity, the pipeline's slots and the calling thread's
+ * header records.  State is left alone: the retry record's pinned word, the async error word, events, streams, the tile guard.  Two kinds keep
+ * content a later call needs, and the host-side mark that says it is valid is dropped with it: SCRATCH_VP8_RETRY, the luma column
+ * ffhip_stream_sync puts back when it repeats a side-by-side call (`armed`; a report that is still waiting to be collected refuses the fill),
+ * and the device planner's verdict in the HEVC scratch that ffhip_debug_hevc_plan_result reads (the calling thread's pointer to it). */
+extern "C" int ffhip_debug_scratch_fill(void *stream, int value, uint64_t bytes[2], int *kinds, int cap)
+{
+    if (!bytes || cap < 0 || (cap > 0 && !kinds)) return FFHIP_EINVAL;
+    bytes[0] = bytes[1] = 0;
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    hipStream_t st = (hipStream_t)stream;
+    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
+    std::vector<hipEvent_t> staged;
+    {
+        std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
+        if (FfhipStreamState *e = ffhip_stream_state(stream, false))
+            for (auto &s : e->staged)
+                if (s.second) staged.push_back(s.second);
+    }
+    for (hipEvent_t ev : staged) FFHIP_CHECK(hipEventSynchronize(ev), FFHIP_EIO); /* (outside the lock, as ffhip_pinned_staging waits) */
+    int count = 0;
+    {
+        std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
+        if (FfhipStreamState *e = ffhip_stream_state(stream, false)) {
+            if (e->retry.armed && e->retry.err && *(volatile int *)e->retry.err) return FFHIP_EIO; /* ffhip_stream_sync first: the repeat needs the column */
+            e->retry.armed = false;
+            ffhip_hevc_plan_result_forget(stream);
+            std::vector<int> seen;
+            for (auto &b : e->scratch) {
+                if (!b.second.p) continue;
+                FFHIP_CHECK(hipMemsetAsync(b.second.p, value, b.second.cap * sizeof(uint32_t), st), FFHIP_EIO);
+                bytes[0] += b.second.cap * sizeof(uint32_t);
+                seen.push_back(b.first);
+            }
+            for (auto &b : e->pinned) {
+                if (!b.second.p) continue;
+                memset(b.second.p, value, b.second.cap);
+                bytes[1] += b.second.cap;
+                seen.push_back(b.first);
+            }
+            std::sort(seen.begin(), seen.end());
+            seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
+            for (int k : seen) {
+                if (count < cap) kinds[count] = k;
+                count++;
+            }
+        }
+    }
+    const int prc = ffhip_pipeline_fill(value, bytes);
+    if (prc) return prc;
+    {
+        ThreadState &t = this_thread();
+        std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
+        if (t.hdr) {
+            memset((void *)t.hdr.get(), value, t.hdr_cap * sizeof(struct jpeg_hdr));
+            bytes[1] += t.hdr_cap * sizeof(struct jpeg_hdr);
+        }
+    }
+    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
+    return count;
 }
 
 /* No call of ANY thread may be in flight, host part included: every thread's streams, events and header records go too. */

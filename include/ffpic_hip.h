@@ -55,6 +55,26 @@ void ffhip_reload_env(void);
 /* Test hook (no device needed): what the library holds for the switch `name` -- copied into dst[0..cap), full length returned,
  * -1 when unset.  Values are kept whole whatever their length (FFHIP_RCCL_LIB is a path). */
 long ffhip_env_value_test(const char *name, char *dst, size_t cap);
+/* Diagnostics, a test hook: sets every byte of what the library keeps between calls for (current device, `stream`) to the low byte of `value`,
+ * so that a test can show that no call's output depends on what an earlier call left there.  With no call of the library in flight on `stream`
+ * (and, for the slots and records below, none at all): waits for `stream` and for the events behind the last copies out of its pinned staging,
+ * then fills, over their WHOLE capacity (the headroom behind what the last call used included),
+ *   - every device scratch buffer and every pinned buffer of (current device, stream);
+ *   - the two slots of ffhip_jpeg_decode_files (pinned and device planes, tables, pixels), each after its own stream has drained;
+ *   - the calling thread's header records of ffhip_jpeg_entropy_batch_gpu;
+ * and waits again.  bytes[0], bytes[1]: device and host bytes written.  kinds[0..cap): the scratch kinds (the library's internal numbering,
+ * ascending) that had a device or a pinned buffer; the return value is their count, whatever cap is.
+ * NOT touched, being state and not scratch: the pinned word of the stream's VP8 retry record, the process-wide async error word, every event
+ * and stream, the HEVC tile guard (its parity and events).
+ * One kind keeps content a later call needs: the luma column ffhip_vp8_predict_loopfilter saves for the repeat by ffhip_stream_sync.  The hook
+ * fills it like the others and drops the host-side mark that says it is valid (the record is disarmed: there is nothing left to repeat once
+ * the stream has drained clean); while a report of that call is still waiting to be collected it fills nothing and returns FFHIP_EIO --
+ * call ffhip_stream_sync first.
+ * And one diagnostic reads scratch of an earlier call: ffhip_debug_hevc_plan_result, the device planner's verdict of the calling thread's last
+ * ffhip_hevc_intra_recon.  Where that verdict lies in `stream`'s scratch the hook drops the thread's record of it: the diagnostic answers
+ * FFHIP_EINVAL, as before the first call, until the thread's next device-planned call.
+ * FFHIP_EINVAL: bytes NULL, cap < 0, or kinds NULL with cap > 0 (checked first); FFHIP_ENODEV: no device. */
+int ffhip_debug_scratch_fill(void *stream, int value, uint64_t bytes[2], int *kinds, int cap);
 /* "gfx950" etc. of the bound device, "" if none. */
 const char *ffhip_arch_name(void);
 

@@ -164,6 +164,21 @@ def test_uniform_jpeg_call_reaches_the_device_check_first(L, why):
     assert _recon(L, g, **kw) == capi.FFHIP_ENODEV, why
 
 
+def test_scratch_fill_hook_checks_its_arguments_in_front_of_the_device_check(L):
+    """ffhip_debug_scratch_fill: NULL bytes, a negative cap and kinds NULL with room asked for are FFHIP_EINVAL with or without a device; a
+    well-formed call without a device is FFHIP_ENODEV, has written nothing to kinds and has zeroed bytes"""
+    nbytes, kinds = (C.c_uint64 * 2)(7, 7), (C.c_int * 4)(-3, -3, -3, -3)
+    assert L.ffhip_debug_scratch_fill(None, 0xFF, None, kinds, 4) == capi.FFHIP_EINVAL
+    assert L.ffhip_debug_scratch_fill(None, 0xFF, nbytes, kinds, -1) == capi.FFHIP_EINVAL
+    assert L.ffhip_debug_scratch_fill(None, 0xFF, nbytes, None, 4) == capi.FFHIP_EINVAL
+    assert list(nbytes) == [7, 7] and list(kinds) == [-3] * 4
+    if L.ffhip_device_count() > 0:
+        return                                  # with a device: tests/test_scratch_fill_gpu.py
+    assert L.ffhip_debug_scratch_fill(None, 0xFF, nbytes, kinds, 4) == capi.FFHIP_ENODEV
+    assert L.ffhip_debug_scratch_fill(None, 0xFF, nbytes, None, 0) == capi.FFHIP_ENODEV
+    assert list(nbytes) == [0, 0] and list(kinds) == [-3] * 4
+
+
 def test_product_never_touches_the_oracle():
     """The product tree must not import, link or reference the CPU checker."""
     pkg = os.path.join(ROOT, "ffpic_amd")
