@@ -196,6 +196,12 @@ size_t ffhip_jpeg_workspace_bytes(const ffhip_jpeg_geom *geom, int n_images);
  *   d_coef_*      its MCU-order planes (layout as ffhip_jpeg_recon_batch, n = 1; d_coef_u / _v NULL for grey)
  *   d_quant       uint16 [4][64] natural order
  *   d_bgra        its coded-size BGRA picture; pitch >= 4 x coded width, a multiple of 16, pitch x 16 < 2^31
+ *   size          the kernels index a picture by UNITS of its layout class: at most 4096 units in a picture row and 2^20 in a picture
+ *                 (the exact range of their reciprocal-multiply division).  A unit is 4 MCUs of 4:2:0, h4v1 and h1v4, 8 MCUs of
+ *                 4:2:2, 4:4:0 and grey, 16 MCUs of 4:4:4, a last partial unit of a row counting as one.  In MCUs:
+ *                   mcu_cols <= 16384 (4:2:0, h4v1, h1v4), 32768 (4:2:2, 4:4:0, grey), 65536 (4:4:4)
+ *                   ceil(mcu_cols / MCUs per unit) x mcu_rows <= 2^20: 256 MCU rows at the widest picture, 2^20 at one unit per row
+ *                 (FFHIP_JPEG_STRIPS=1 halves the unit of 4:4:4, 4:2:2 and 4:4:0 and with it their mcu_cols; =2 doubles grey's)
  * Every device pointer 16-byte aligned.  `items` is a HOST array; every check is made before anything is enqueued
  * (FFHIP_EINVAL, on a machine without a device too; FFHIP_ENODEV there for good arguments).  Only enqueues on `stream`;
  * the records and the per-workgroup table are library scratch of the stream.  `items` is read before the call returns; what its
@@ -1014,7 +1020,7 @@ int ffhip_resize_axis_taps(int n_in, int n_out, int filter, int o, int *first, u
  *   d_src, src_pitch   a BGRA picture as the decode calls write it: 4-byte aligned, pitch a multiple of 4
  *   x0, y0, width,     the source rectangle (x0, y0 >= 0; width, height in 1..16384); the caller keeps it inside the picture, the call
  *   height             checks what it can: 4 (x0 + width) <= src_pitch, and (y0 + height) src_pitch < 2^31
- *   d_dst, dst_pitch   the output picture: 4-byte aligned, dst_pitch a multiple of 4 and >= 4 out_width
+ *   d_dst, dst_pitch   the output picture: 4-byte aligned, dst_pitch a multiple of 4, >= 4 out_width and <= 2^40
  *   out_width,         in 1..16384
  *   out_height
  * Only the out_width x out_height pixels are written (one dword store each): the row padding of the destination stays untouched.
