@@ -22,6 +22,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
+
 /* ------------------------------------------------------------ device code */
 
 __device__ static const int kEven[4][4] = {
@@ -143,10 +145,15 @@ __global__ void k_mcu_color(const short *Y, const short *U, const short *V, int 
 
 /* -------------------------------------------------------------- host side */
 
-static void *g_stage = nullptr; /* 8 KiB device staging buffer */
+/* The one 8 KiB device staging buffer of every entry of this file.  g_stage_mu owns it: whoever allocates, frees or uses it holds the lock,
+ * a block operation from its first copy in to its last copy out (copy, launch and copy back are one unit: another thread's block between
+ * them would be transformed twice and handed to the wrong caller).  Calls from several host threads are serialised by it. */
+static std::mutex g_stage_mu;
+static void *g_stage = nullptr;
 #define STAGE_BYTES 8192
 
-static int stage_ready(void)
+/* with g_stage_mu held */
+static int stage_ready_locked(void)
 {
     if (!ffhip_have_device()) return 0;
     if (!g_stage && hipMalloc(&g_stage, STAGE_BYTES) != hipSuccess) {
@@ -154,6 +161,11 @@ static int stage_ready(void)
         return 0;
     }
     return 1;
+}
+static int stage_ready(void)
+{
+    std::lock_guard<std::mutex> lock(g_stage_mu);
+    return stage_ready_locked();
 }
 
 static void fail(const char *what)
@@ -166,7 +178,8 @@ static void fail(const char *what)
 
 static void run_inplace(int16_t *in, size_t bytes, int which)
 {
-    if (!stage_ready()) { fail("device init"); return; }
+    std::lock_guard<std::mutex> lock(g_stage_mu);
+    if (!stage_ready_locked()) { fail("device init"); return; }
     if (hipMemcpy(g_stage, in, bytes, hipMemcpyHostToDevice) != hipSuccess) { fail("h2d"); return; }
     if (which == 8) hipLaunchKernelGGL(k_block_idct8x8, dim3(1), dim3(64), 0, 0, (short *)g_stage, 1);
     else hipLaunchKernelGGL(k_block_vp8_idct4x4, dim3(1), dim3(64), 0, 0, (short *)g_stage, 1);
@@ -181,7 +194,8 @@ static void hip_idct_8x8_v(void *in, int bitdepth) { hip_idct_8x8((int16_t *)in,
 
 extern "C" void ffhip_idct_4x4_hevc(const int16_t *in, int16_t *out, int bitdepth, bool epp)
 {
-    if (!stage_ready()) { fail("device init"); return; }
+    std::lock_guard<std::mutex> lock(g_stage_mu);
+    if (!stage_ready_locked()) { fail("device init"); return; }
     short *d = (short *)g_stage;
     if (hipMemcpy(d, in, 32, hipMemcpyHostToDevice) != hipSuccess) { fail("h2d"); return; }
     hipLaunchKernelGGL(k_block_hevc_dst4x4, dim3(1), dim3(64), 0, 0, d, d + 16, 1, bitdepth, epp ? 1 : 0);
@@ -194,7 +208,10 @@ static void hip_yuv_to_bgra32(uint8_t *dst, int pitch, void *Y, void *U, void *V
     /* any pair the reference's caller can pass: its MCU scratch holds h*v <= 4 luma blocks (jpg.c:501); a pair beyond
      * that would make the reference itself read past Y[], so there is no behaviour to match */
     if (v < 1 || h < 1 || h * v > 4) { fail("sampling factor (h*v > 4)"); return; }
-    if (!stage_ready()) { fail("device init"); return; }
+    uint8_t tmp[1024];
+    {
+    std::lock_guard<std::mutex> lock(g_stage_mu);
+    if (!stage_ready_locked()) { fail("device init"); return; }
     /* staging layout: Y (h*v*128 B) | U 128 | V 128 | out (8v*8h*4 B <= 1024) */
     char *d = (char *)g_stage;
     const size_t yb = (size_t)h * v * 128;
@@ -204,8 +221,8 @@ static void hip_yuv_to_bgra32(uint8_t *dst, int pitch, void *Y, void *U, void *V
     hipLaunchKernelGGL(k_mcu_color, dim3(1), dim3(256), 0, 0, (const short *)d, (const short *)(d + 512),
                        (const short *)(d + 640), v, h, (u32 *)(d + 1024));
     if (hipGetLastError() != hipSuccess) { fail("launch"); return; }
-    uint8_t tmp[1024];
     if (hipMemcpy(tmp, d + 1024, (size_t)64 * v * h * 4, hipMemcpyDeviceToHost) != hipSuccess) { fail("d2h"); return; }
+    }
     for (int i = 0; i < 8 * v; i++) memcpy(dst + (size_t)i * pitch, tmp + (size_t)i * 8 * h * 4, (size_t)8 * h * 4);
 }
 
@@ -233,6 +250,7 @@ extern "C" void hip_accl_uninit(void)
     /* like opcl_amd_uninit / vulkan_uninit (arch/accl.c:54-62): releases device
      * resources; the registry never unlinks entries, so the ops struct stays valid
      * (static storage) and re-acquires the staging buffer on its next call */
+    std::lock_guard<std::mutex> lock(g_stage_mu);
     if (g_stage) {
         (void)hipFree(g_stage);
         g_stage = nullptr;

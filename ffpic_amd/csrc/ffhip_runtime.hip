@@ -8,10 +8,26 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <stdarg.h>
+
+#include <mutex>
+
+/* Process-wide, under g_init_mu: the bound device and its name are written by ffhip_init (any thread's first compute call gets there through
+ * ffhip_have_device), the text of the last error by whichever thread failed last.  g_ready is read without the lock (an atomic load): it is
+ * set last, when the name is whole.  ffhip_strerror hands out g_last_error itself: a text another thread may be replacing. */
+static std::mutex g_init_mu;
 static int g_device = -1;
 static int g_ready = 0;
 static char g_arch[64] = "";
 static char g_last_error[256] = "";
+static void set_last_error(const char *fmt, ...)
+{
+    std::lock_guard<std::mutex> lock(g_init_mu);
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_last_error, sizeof g_last_error, fmt, ap);
+    va_end(ap);
+}
 
 /* FFHIP_* switches: read once per call site and process, re-read after ffhip_reload_env() */
 #include <atomic>
@@ -63,8 +79,8 @@ extern "C" long ffhip_env_value_test(const char *name, char *dst, size_t cap)
 
 extern "C" void ffhip_note_hip_error(int hip_error, const char *what)
 {
-    snprintf(g_last_error, sizeof g_last_error, "%s: %s", what, hipGetErrorString((hipError_t)hip_error));
-    if (FFHIP_ENV("FFHIP_VERBOSE")) fprintf(stderr, "ffpic_hip: %s\n", g_last_error);
+    set_last_error("%s: %s", what, hipGetErrorString((hipError_t)hip_error));
+    if (FFHIP_ENV("FFHIP_VERBOSE")) fprintf(stderr, "ffpic_hip: %s: %s\n", what, hipGetErrorString((hipError_t)hip_error));
 }
 
 /* How many single-wave workgroups of `kernel` the device holds at once: what a kernel whose waves WAIT for each other
@@ -91,8 +107,14 @@ extern "C" int ffhip_resident_waves(const void *kernel, int block_threads)
 
 extern "C" int ffhip_have_device(void)
 {
-    if (!g_ready) ffhip_init(g_device < 0 ? 0 : g_device);
-    return g_ready;
+    if (__atomic_load_n(&g_ready, __ATOMIC_ACQUIRE)) return 1;
+    int dev;
+    {
+        std::lock_guard<std::mutex> lock(g_init_mu);
+        dev = g_device < 0 ? 0 : g_device;
+    }
+    ffhip_init(dev);
+    return __atomic_load_n(&g_ready, __ATOMIC_ACQUIRE);
 }
 
 extern "C" int ffhip_device_count(void)
@@ -109,16 +131,19 @@ extern "C" int ffhip_init(int device)
     FFHIP_CHECK(hipSetDevice(device), FFHIP_ENODEV);
     hipDeviceProp_t prop;
     FFHIP_CHECK(hipGetDeviceProperties(&prop, device), FFHIP_ENODEV);
-    strncpy(g_arch, prop.gcnArchName, sizeof g_arch - 1);
-    char *colon = strchr(g_arch, ':');
+    char arch[sizeof g_arch] = "";
+    strncpy(arch, prop.gcnArchName, sizeof arch - 1);
+    char *colon = strchr(arch, ':');
     if (colon) *colon = 0;
     /* the code object only holds gfx950 ISA: refuse anything else up front */
-    if (strcmp(g_arch, "gfx950") != 0) {
-        snprintf(g_last_error, sizeof g_last_error, "device %d is %s, this library is built for gfx950 only", device, g_arch);
+    if (strcmp(arch, "gfx950") != 0) {
+        set_last_error("device %d is %s, this library is built for gfx950 only", device, arch);
         return FFHIP_ENODEV;
     }
+    std::lock_guard<std::mutex> lock(g_init_mu);
+    memcpy(g_arch, arch, sizeof g_arch); /* (whole before g_ready says so: another thread's first call may be reading it) */
     g_device = device;
-    g_ready = 1;
+    __atomic_store_n(&g_ready, 1, __ATOMIC_RELEASE);
     return FFHIP_OK;
 }
 
@@ -126,23 +151,34 @@ extern "C" int ffhip_init(int device)
  * the device again. */
 extern "C" void ffhip_shutdown(void)
 {
-    if (g_ready) {
+    if (__atomic_load_n(&g_ready, __ATOMIC_ACQUIRE)) {
         (void)hipDeviceSynchronize();
         ffhip_release_caches();
     }
-    g_ready = 0;
+    __atomic_store_n(&g_ready, 0, __ATOMIC_RELEASE);
 }
 
 /* One pinned, device-visible word that a kernel with an in-launch dependency wait writes when it
  * gives up (its bounded spin ran out); checked and cleared by ffhip_stream_sync. */
+/* Process-wide.  g_async_mu owns its making and its freeing: two first calls at once make ONE word (with two, a kernel would report into one
+ * and the sync read the other).  It is read without the lock, by atomic loads: once made it stays until ffhip_release_caches, which needs
+ * every thread quiet. */
+static std::mutex g_async_mu;
 static int *g_async_err = nullptr;
+static int *async_err_peek(void) { return __atomic_load_n(&g_async_err, __ATOMIC_ACQUIRE); }
 extern "C" int *ffhip_async_err_word(void)
 {
-    if (!g_async_err && ffhip_have_device()) {
-        if (hipHostMalloc((void **)&g_async_err, 64, hipHostMallocMapped) != hipSuccess) g_async_err = nullptr;
-        else *g_async_err = 0;
+    int *w = async_err_peek();
+    if (w) return w;
+    if (!ffhip_have_device()) return nullptr;
+    std::lock_guard<std::mutex> lock(g_async_mu);
+    w = g_async_err;
+    if (!w) {
+        if (hipHostMalloc((void **)&w, 64, hipHostMallocMapped) != hipSuccess) return nullptr;
+        *w = 0;
+        __atomic_store_n(&g_async_err, w, __ATOMIC_RELEASE);
     }
-    return g_async_err;
+    return w;
 }
 
 extern "C" const char *ffhip_arch_name(void) { return g_arch; }
@@ -150,7 +186,12 @@ extern "C" const char *ffhip_arch_name(void) { return g_arch; }
 extern "C" void ffhip_release_caches(void)
 {
     ffhip_state_release();
-    if (g_async_err) { (void)hipHostFree(g_async_err); g_async_err = nullptr; }
+    std::lock_guard<std::mutex> lock(g_async_mu);
+    if (g_async_err) {
+        int *w = g_async_err;
+        __atomic_store_n(&g_async_err, (int *)nullptr, __ATOMIC_RELEASE);
+        (void)hipHostFree(w);
+    }
 }
 
 extern "C" const char *ffhip_strerror(int code)
@@ -208,16 +249,16 @@ extern "C" int ffhip_stream_sync(void *s)
      * of the planes' former contents it reads is kept (the last luma column), so the library repeats the stages ONE AFTER THE OTHER here and
      * says so: FFHIP_RETRIED, not FFHIP_OK -- what the caller had enqueued behind the call has consumed the aborted run's planes. */
     const int retried = ffhip_vp8_side_by_side_retry(s);
+    int *const word = async_err_peek();
     if (retried < 0) {
-        snprintf(g_last_error, sizeof g_last_error, "a side-by-side VP8 call aborted and could not be repeated");
-        if (g_async_err) *(volatile int *)g_async_err = 0;
+        set_last_error("a side-by-side VP8 call aborted and could not be repeated");
+        if (word) __atomic_store_n(word, 0, __ATOMIC_RELAXED);
         return FFHIP_EIO;
     }
-    if (g_async_err && *(volatile int *)g_async_err) {
-        const int code = *(volatile int *)g_async_err;
-        snprintf(g_last_error, sizeof g_last_error, code == FFHIP_ASYNC_BAD_INPUT ? "a dependency-scheduled kernel refused its input (code %d)"
-                                                                                   : "a dependency-scheduled kernel aborted (code %d)", code);
-        *(volatile int *)g_async_err = 0;
+    /* (taken with an exchange: the word is process-wide, and of two threads that sync at once ONE collects a give-up) */
+    if (const int code = word ? __atomic_exchange_n(word, 0, __ATOMIC_ACQ_REL) : 0) {
+        set_last_error(code == FFHIP_ASYNC_BAD_INPUT ? "a dependency-scheduled kernel refused its input (code %d)"
+                                                     : "a dependency-scheduled kernel aborted (code %d)", code);
         return code == FFHIP_ASYNC_BAD_INPUT ? FFHIP_EINVAL : FFHIP_EIO;
     }
     {

@@ -15,6 +15,25 @@
  * (FFHIP_E*).  (1) and (2) return void like the reference; a back-end that
  * cannot run does not register (arch/opencl/opcl.c:112-114), callers fall back
  * to C when the lookup returns NULL (format/webp.c:1173, coding/hevc.c:3913-3919).
+ *
+ * THREADS AND STREAMS (held by tests/test_concurrent_gpu.py; the state behind it is listed in DESIGN.md 4.27):
+ *  - In flight together: calls of different host threads, each on a stream of ITS OWN, and calls of one thread on different streams.  What
+ *    the library keeps between calls is per (device, stream) -- scratch, pinned staging, the VP8 retry record, the HEVC tile guard -- or per
+ *    (thread, device) -- the side, pipe and Huffman streams it forks work to -- and the ffhip_debug_*_last* records are per thread: a
+ *    thread reads the record of its own last call whatever other threads do meanwhile.  A thread binds its device with ffhip_init first
+ *    (hipSetDevice is per thread).
+ *  - Calls on ONE stream, the NULL stream included, are ordered by the caller: no two threads may have a call on the same stream in
+ *    flight, and the entries without a stream argument, other than those of the next point, use the NULL stream.
+ *  - Entries that serialise themselves, because each has ONE staging allocation (the NULL stream's): ffhip_jpeg_recon_batch_host, the block
+ *    operations (every function of ffhip_accl_ops_get, ffhip_get_dct_ops and ffhip_get_cs_ops, and ffhip_idct_4x4_hevc) and the two slots
+ *    of ffhip_jpeg_decode_files.  Any number of threads may call them at once; they take turns, a whole call at a time.
+ *  - ffhip_shutdown and hip_accl_uninit free what calls in flight use: every thread must be quiet,
+ *    host parts of calls included.  ffhip_stream_destroy needs only its own stream's caller quiet.  ffhip_reload_env may be called at any
+ *    time, but a call in flight may have read a switch before it.
+ *  - The async error word, through which a dependency-scheduled kernel (VP8 prediction and loop filter, HEVC intra) reports a bounded wait
+ *    that ran out, is ONE per process: the next ffhip_stream_sync of ANY thread on ANY stream collects it and returns FFHIP_EIO, once.  (The
+ *    side-by-side VP8 call reports into a word of its stream's own: its FFHIP_RETRIED goes to the sync of that stream.)  The text behind
+ *    ffhip_strerror(FFHIP_EIO / FFHIP_ENODEV) is the process's last one and may be another thread's.
  */
 #ifndef FFPIC_HIP_H
 #define FFPIC_HIP_H
@@ -146,7 +165,9 @@ const struct ffhip_dct_ops *ffhip_get_dct_ops(int component_bits);
 const struct ffhip_cs_ops *ffhip_get_cs_ops(int component_bits);
 /* HEVC DST-VII 4x4, same signature and rounding as idct_4x4_hevc (utils/idct.h:25,
  * utils/idct.c:36-55).  Kept as its own entry: the reference back-ends overloaded
- * accl_ops.idct_4x4 with three different transforms. */
+ * accl_ops.idct_4x4 with three different transforms.
+ * Every block operation of (1) and (2) and this one -- copy in, one launch, copy out, synchronous -- goes through ONE small device staging
+ * buffer: calls from several host threads are serialised inside the library, a whole operation at a time ("Threads and streams" above). */
 void ffhip_idct_4x4_hevc(const int16_t *in, int16_t *out, int bitdepth, bool epp);
 
 /* ------------------------------------------ (3) batched device-resident API */
@@ -228,7 +249,7 @@ int ffhip_bgra_layout(const ffhip_jpeg_geom *geom, int64_t *pitch, int64_t *imag
 /* Same computation from HOST buffers (copies in, runs, copies out, synchronises): what a patched
  * format/jpg.c would call per picture.  The device staging is library scratch kept between calls
  * (grown on demand, released by ffhip_shutdown); calls from several host threads are serialised
- * inside the library (one picture at a time, like the reference's decode loop) -- a host that wants
+ * inside the library (one picture at a time, like the reference's decode loop; "Threads and streams" above) -- a host that wants
  * pictures in flight side by side uses the device-pointer entry above with its own buffers and streams. */
 int ffhip_jpeg_recon_batch_host(const ffhip_jpeg_geom *geom, int n_images, const int16_t *coef_y,
                                 const int16_t *coef_u, const int16_t *coef_v,
@@ -418,7 +439,7 @@ int ffhip_hevc_residual_batch(int nTbS, long long n_tu, const int16_t *d_level, 
  * frames of a batch run side by side, so throughput grows with the batch up to a few hundred frames; should a wave's bounded wait ever run out, the next
  * ffhip_stream_sync on any stream returns FFHIP_EIO.  FFHIP_VP8_PRED_MODE=levels selects the older
  * one-launch-per-wavefront-level form.  Scratch is kept per stream: calls on different streams (or
- * host threads with their own streams) may be in flight together; calls on one stream are ordered.
+ * host threads with their own streams) may be in flight together; calls on one stream are ordered ("Threads and streams" above).
  * Operands: d_modes, d_residual, d_resmap and the planes (their former contents included) are STREAM-ORDERED -- the kernel reads them at
  * the call's place in `stream`, so work enqueued there in front of the call may produce them.  h_modes is read when the call is made
  * (the check above; nothing is scheduled from it in the row form) and must hold the records d_modes holds once `stream` reaches the call.

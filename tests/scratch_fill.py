@@ -21,6 +21,16 @@ INTERNAL_H = os.path.join(capi.CSRC, "ffhip_internal.h")
 COVERED = {}            # scratch kind -> the families whose fill reported it in front of a checked run
 
 
+class StreamBox:
+    """a stream that is made later: a runner built on one thread for a stream that the thread that runs it creates (tests/concurrency.py)"""
+    handle = None
+
+
+def h(s):
+    """the stream handle a runner was given: itself, or what its StreamBox holds by now"""
+    return s.handle if isinstance(s, StreamBox) else s
+
+
 def lib():
     L = capi.require_device(0)
     L.ffhip_scratch.argtypes = [C.c_int, C.c_void_p, C.c_size_t]          # exported, not public: ffhip_internal.h
@@ -161,9 +171,10 @@ def files_call(call, files, places, keys, statuses=None):
     return rc, status
 
 
-def tensor_files_call(call, files, fmt, shapes, keys):
+def tensor_files_call(call, files, fmt, shapes, keys, stream=None):
     """One files-to-tensors call into test_resize_gpu.Outputs (one 0xA5 allocation, ragged offsets and strides).  call(ptrs, lens, n, fmt, outs,
-    status) -> rc; shapes[i] = (h, w) of file i's tensor; keys[i]: the BGRA picture [h][w][4] the tensor is made of, None: the file must fail"""
+    status) -> rc; shapes[i] = (h, w) of file i's tensor; keys[i]: the BGRA picture [h][w][4] the tensor is made of, None: the file must fail.
+    stream: the one `call` runs on (it is waited for before the tensors are read)"""
     from test_resize_gpu import Outputs
     n = len(files)
     outs = Outputs(fmt, shapes)
@@ -178,6 +189,8 @@ def tensor_files_call(call, files, fmt, shapes, keys):
     assert [bool(s) for s in status] == [key is None for key in keys], status
     firsts = [s for s in status if s]
     assert rc == (firsts[0] if firsts else 0), (rc, status)
+    if stream is not None:
+        capi.sync(stream)
     got = outs.read()
     assert np.array_equal(got, outs.exp), np.flatnonzero(got != outs.exp)[:8].tolist()
     return status

@@ -135,11 +135,12 @@ class Output:
     def ptr(self):
         return self.dev.ptr
 
-    def refill(self):
+    def refill(self, s=None):
+        """0xA5 back into the buffers, by a blocking copy on `s` (the NULL stream unless a thread with a stream of its own gives that)"""
         L = capi.lib()
         for b in ([self.copy] if self.of is not None else [self.dev, self.copy]):
-            capi.check(L.ffhip_memcpy_h2d(b.ptr, self.fill.ctypes.data, self.fill.nbytes, None))
-        capi.check(L.ffhip_stream_sync(None))
+            capi.check(L.ffhip_memcpy_h2d(b.ptr, self.fill.ctypes.data, self.fill.nbytes, s))
+        capi.check(L.ffhip_stream_sync(s))
 
     def copied(self):
         return self.copy.to_host((self.nbytes,), np.uint8)

@@ -227,9 +227,9 @@ class Outputs:
         return self.dev.to_host((self.total * self.es,), np.uint8)
 
 
-def check_files(entry, batch, f, filt, sizes, rois=None, expect_bad=()):
+def check_files(entry, batch, f, filt, sizes, rois=None, expect_bad=(), stream=None, n_threads=4):
     """the resized C file call: sizes[i] = (h, w) of file i's output.  Every delivered tensor equals decode -> numpy rule -> formatting,
-    a refused file's output still holds its 0xA5"""
+    a refused file's output still holds its 0xA5.  stream: the stream of the call (NULL unless given; one that is given is waited for)"""
     files, images, bad = batch
     L, n = capi.lib(), len(files)
     outs = Outputs(f, sizes)
@@ -240,7 +240,9 @@ def check_files(entry, batch, f, filt, sizes, rois=None, expect_bad=()):
     rects = (capi.Rect * n)(*[capi.Rect(*r) for r in rois]) if rois else None
     out_size = (capi.Size * n)(*[capi.Size(w, h) for h, w in sizes])
     status = (C.c_int * n)()
-    rc = getattr(L, entry)(ptrs, lens, n, 4, C.byref(f), o, rects, out_size, filt, None, status, None)
+    rc = getattr(L, entry)(ptrs, lens, n, n_threads, C.byref(f), o, rects, out_size, filt, None, status, stream)
+    if stream is not None:
+        capi.sync(stream)
     status = list(status)
     for k, img in enumerate(images):
         if k == bad or k in expect_bad:

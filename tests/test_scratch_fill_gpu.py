@@ -67,7 +67,9 @@ _EXPECT = {}
 
 def plain(case, s, retry_ok=False, memo=True):
     """a Case of test_stream_order_gpu.py as a checked run without a stall: the real inputs into the operands, the call, the consumer's
-    copies, the sync, the outputs against the oracle's.  A side-by-side VP8 call the sync had to repeat is handled as it is there."""
+    copies, the sync, the outputs against the oracle's.  A side-by-side VP8 call the sync had to repeat is handled as it is there.
+    `s` may be a scratch_fill.StreamBox (tests/concurrency.py): the buffers are then refilled on that stream too, not on the NULL stream, and
+    run.prime() computes the answer key ahead of the first run.  run() -> the status of its sync (0, or FFHIP_RETRIED with retry_ok)"""
     def expect(which):
         if not memo:
             return case.expect(which)
@@ -77,10 +79,12 @@ def plain(case, s, retry_ok=False, memo=True):
 
     checked = TSO.Case(case.name, case.call, case.operands, case.outputs, expect)
 
-    def run():
+    def run(s=s):
         L = capi.lib()
+        own = isinstance(s, SF.StreamBox)
+        s = SF.h(s)
         for o in case.outputs:
-            o.refill()
+            o.refill(s if own else None)
         for ptr, value, nbytes in case.memsets:
             capi.check(L.ffhip_memset(ptr, value, nbytes, s), "ffhip_memset")
         for op in case.operands:
@@ -89,13 +93,15 @@ def plain(case, s, retry_ok=False, memo=True):
         for o in case.outputs:
             SO.copy(o.copy.ptr, o.dev.ptr, o.nbytes, s)
         rc = capi.sync(s)
-        assert rc == 0 or (retry_ok and rc == capi.FFHIP_RETRIED), rc
+        assert rc == 0 or (retry_ok and rc == capi.FFHIP_RETRIED), (case.name, rc)
         if rc == capi.FFHIP_RETRIED:
             TSO.assert_outputs(checked, "true", read="written")
             for o in case.outputs:
                 SO.copy(o.copy.ptr, o.dev.ptr, o.nbytes, s)
             assert capi.sync(s) == 0
         TSO.assert_outputs(checked, "true")
+        return rc
+    run.prime = lambda: expect("true")
     return run
 
 
@@ -196,10 +202,9 @@ def written_file(rng, w, h, layout, restart=0):
     return JpegFile(data, coef, w, h, layout, q)
 
 
-@pytest.fixture(scope="module")
-def jpeg_batch():
+def jpeg_batch_files(seed=6):
     """the files of test_resize_gpu.jpeg_batch's list with the truncated one in the middle -> ([JpegFile, None at the bad place], files, bad)"""
-    rng = np.random.default_rng(6)
+    rng = np.random.default_rng(seed)
     known = [written_file(rng, *spec) for spec in JPEG_BATCH]
     bad = len(known) // 2
     cut = known[4].data[:len(known[4].data) * 2 // 3]
@@ -208,7 +213,12 @@ def jpeg_batch():
     return known, files, bad
 
 
-def mixed_runner(known, files, s, rule="full", denoms=None, flags=0, bad_code=EINVAL):
+@pytest.fixture(scope="module")
+def jpeg_batch():
+    return jpeg_batch_files()
+
+
+def mixed_runner(known, files, s, rule="full", denoms=None, flags=0, bad_code=EINVAL, n_threads=4):
     """ffhip_jpeg_decode_files_mixed_device / _scaled / _ex over framed outputs.  A bad file's place is as large as the file it was cut from"""
     L = capi.lib()
     n = len(files)
@@ -221,18 +231,18 @@ def mixed_runner(known, files, s, rule="full", denoms=None, flags=0, bad_code=EI
 
     def call(ptrs, lens, n_, outs, pitches, status):
         if flags:
-            return L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n_, 4, outs, pitches, den if rule == "scaled" else None, flags, geoms, status, s)
+            return L.ffhip_jpeg_decode_files_mixed_device_ex(ptrs, lens, n_, n_threads, outs, pitches, den if rule == "scaled" else None, flags, geoms, status, SF.h(s))
         if rule == "scaled":
-            return L.ffhip_jpeg_decode_files_mixed_device_scaled(ptrs, lens, n_, 4, outs, pitches, den, geoms, status, s)
-        return L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n_, 4, outs, pitches, geoms, status, s)
+            return L.ffhip_jpeg_decode_files_mixed_device_scaled(ptrs, lens, n_, n_threads, outs, pitches, den, geoms, status, SF.h(s))
+        return L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n_, n_threads, outs, pitches, geoms, status, SF.h(s))
 
     def run():
         SF.files_call(call, files, places, keys, {i: bad_code for i, k in enumerate(known) if k is None})
-        capi.sync(s)
+        return capi.sync(SF.h(s))
     return run
 
 
-def uniform_runner(known, s, host_out=False, chunk=0):
+def uniform_runner(known, s, host_out=False, chunk=0, n_threads=3):
     """ffhip_jpeg_decode_files_device (pictures of one geometry into one device allocation) / ffhip_jpeg_decode_files (into pageable host
     memory through the pipeline's slots): a guard behind every row and behind every picture"""
     L = capi.lib()
@@ -249,11 +259,11 @@ def uniform_runner(known, s, host_out=False, chunk=0):
         status, geom = (C.c_int * n)(), capi.JpegGeom()
         if host_out:
             got = np.full(want.size, SF.FILL, np.uint8)
-            rc = L.ffhip_jpeg_decode_files(ptrs, lens, n, 3, chunk, C.byref(geom), got.ctypes.data, pitch, stride, status)
+            rc = L.ffhip_jpeg_decode_files(ptrs, lens, n, n_threads, chunk, C.byref(geom), got.ctypes.data, pitch, stride, status)
         else:
             dev = ops.DeviceBuffer(host=np.full(want.size, SF.FILL, np.uint8))
-            rc = L.ffhip_jpeg_decode_files_device(ptrs, lens, n, 3, C.byref(geom), dev.ptr, pitch, stride, status, s)
-            capi.sync(s)
+            rc = L.ffhip_jpeg_decode_files_device(ptrs, lens, n, n_threads, C.byref(geom), dev.ptr, pitch, stride, status, SF.h(s))
+            capi.sync(SF.h(s))
             got = dev.to_host((want.size,), np.uint8)
         assert rc == 0 and not any(status), (rc, list(status))
         assert (geom.mcu_cols, geom.mcu_rows) == (known[0].mc, known[0].mr)
@@ -261,13 +271,17 @@ def uniform_runner(known, s, host_out=False, chunk=0):
     return run
 
 
-@pytest.fixture(scope="module")
-def uniform_files():
-    rng = np.random.default_rng(16)
+def uniform_file_sets(seed=16):
+    rng = np.random.default_rng(seed)
     small = [written_file(rng, 67, 35, "420", r) for r in (0, 3, 0, 7, 0)]
     larger = [written_file(rng, 301, 47, "420", 0) for _ in range(7)]         # no restart markers: the subsequence decoder's batch
     marked = [written_file(rng, 301, 47, "420", 2) for _ in range(4)]         # an interval every two MCUs: the interval kernel's
     return small, larger, marked
+
+
+@pytest.fixture(scope="module")
+def uniform_files():
+    return uniform_file_sets()
 
 
 @pytest.mark.parametrize("entropy", [None, "0"], ids=["device_huffman", "host_threads"])
@@ -326,23 +340,24 @@ def test_jpeg_progressive_files(stream, gpu):
                     [mixed_runner(known, [k.data for k in known], stream, flags=flags)], ["SCRATCH_HUFF_PROG"] if gpu else ["SCRATCH_FILES_MIXED"])
 
 
-def test_jpeg_files_to_tensors(jpeg_batch):
-    """ffhip_jpeg_decode_files_tensor, _tensor_resized (test_resize_gpu.check_files on the oracle's pictures) and _tensor_oriented: the NULL
-    stream's"""
+def jpeg_tensor_runs(batch, stream=None, n_threads=4):
+    """ffhip_jpeg_decode_files_tensor, _tensor_resized (test_resize_gpu.check_files on the oracle's pictures) and _tensor_oriented on the
+    files of jpeg_batch_files -> (plain_tensors, resized, oriented); on the NULL stream unless one is given"""
     L = capi.lib()
-    known, files, bad = jpeg_batch
+    known, files, bad = batch
     n = len(files)
     images = [None if k is None else k.shown() for k in known]
     f16, u8 = make_format(F16, 1, 0), make_format(U8, 0, 1)
 
     def plain_tensors():
         shapes = [(1, 1) if im is None else im.shape[:2] for im in images]
-        SF.tensor_files_call(lambda ptrs, lens, n_, fmt, outs, status: L.ffhip_jpeg_decode_files_tensor(ptrs, lens, n_, 4, fmt, outs, None, None, status, None),
-                             files, f16, shapes, images)
+        SF.tensor_files_call(lambda ptrs, lens, n_, fmt, outs, status: L.ffhip_jpeg_decode_files_tensor(ptrs, lens, n_, n_threads, fmt, outs, None, None, status,
+                                                                                                        SF.h(stream)), files, f16, shapes, images, SF.h(stream))
 
     def resized():
-        check_files("ffhip_jpeg_decode_files_tensor_resized", (files, images, bad), u8, AA, per_file_sizes(n), inner_rois(images, bad))
-        check_files("ffhip_jpeg_decode_files_tensor_resized", (files, images, bad), f16, BIL, [(32, 32)] * n)
+        check_files("ffhip_jpeg_decode_files_tensor_resized", (files, images, bad), u8, AA, per_file_sizes(n), inner_rois(images, bad), stream=SF.h(stream),
+                    n_threads=n_threads)
+        check_files("ffhip_jpeg_decode_files_tensor_resized", (files, images, bad), f16, BIL, [(32, 32)] * n, stream=SF.h(stream), n_threads=n_threads)
 
     def oriented():
         for o, size in ((6, None), (5, (24, 40)), (3, (17, 9))):
@@ -361,7 +376,14 @@ def test_jpeg_files_to_tensors(jpeg_batch):
                 shapes.append(keys[-1].shape[:2])
             sizes = (capi.Size * n)(*[capi.Size(size[1], size[0]) for _ in range(n)]) if size else None
             SF.tensor_files_call(lambda ptrs, lens, n_, fmt, outs, status: L.ffhip_jpeg_decode_files_tensor_oriented(
-                ptrs, lens, n_, 4, fmt, outs, None, sizes, AA, None, None, orient, None, None, status, None), files, f16, shapes, keys)
+                ptrs, lens, n_, n_threads, fmt, outs, None, sizes, AA, None, None, orient, None, None, status, SF.h(stream)), files, f16, shapes, keys,
+                SF.h(stream))
+    return plain_tensors, resized, oriented
+
+
+def test_jpeg_files_to_tensors(jpeg_batch):
+    """ffhip_jpeg_decode_files_tensor, _tensor_resized and _tensor_oriented: the NULL stream's"""
+    plain_tensors, resized, oriented = jpeg_tensor_runs(jpeg_batch)
 
     def larger():
         capi.setenv("FFHIP_TENSOR_PART_BYTES", None)
@@ -425,7 +447,7 @@ def opaque(bgr, alpha=None):
     return np.ascontiguousarray(np.concatenate([bgr, a], axis=2))
 
 
-def webp_runner(files, keys, s, flags=0, statuses=None):
+def webp_runner(files, keys, s, flags=0, statuses=None, n_threads=4):
     """ffhip_webp_decode_files_device[_ex] over framed outputs: the reference rule writes the macroblock grid, the libwebp rule width x height
     of it (the frame is the grid's either way: the call asks for a pitch of 64 bytes a macroblock column)"""
     L = capi.lib()
@@ -440,12 +462,12 @@ def webp_runner(files, keys, s, flags=0, statuses=None):
 
     def call(ptrs, lens, n, outs, pitches, status):
         if flags:
-            return L.ffhip_webp_decode_files_device_ex(ptrs, lens, n, 4, outs, pitches, None, flags, None, status, s)
-        return L.ffhip_webp_decode_files_device(ptrs, lens, n, 4, outs, pitches, None, status, s)
+            return L.ffhip_webp_decode_files_device_ex(ptrs, lens, n, n_threads, outs, pitches, None, flags, None, status, SF.h(s))
+        return L.ffhip_webp_decode_files_device(ptrs, lens, n, n_threads, outs, pitches, None, status, SF.h(s))
 
     def run():
         SF.files_call(call, files, places, keys, statuses)
-        capi.sync(s)
+        return capi.sync(SF.h(s))
     return run
 
 
@@ -505,9 +527,10 @@ def test_webp_alpha_planes(stream):
     SF.run_protocol("webp alpha", stream, [everything], [everything, damaged, in_parts], ["SCRATCH_WEBP_ALPHA"])
 
 
-def test_webp_files_to_tensors():
+def webp_tensor_runs(stream=None, n_threads=4):
     """ffhip_webp_decode_files_tensor, _tensor_resized, _tensor_oriented (the reference rule, the reference's recorded pixels) and
-    ffhip_webp_decode_files_tensor_ex under the libwebp rule (PIL's recorded RGB): the NULL stream's"""
+    ffhip_webp_decode_files_tensor_ex under the libwebp rule (PIL's recorded RGB) -> [plain_tensors, resized, oriented, libwebp_rule]; on the
+    NULL stream unless one is given"""
     L = capi.lib()
     files, images = [file_bytes(n) for n in NAMES], [front_key(n) for n in NAMES]
     bad = len(files) // 2
@@ -521,25 +544,32 @@ def test_webp_files_to_tensors():
         return [(1, 1) if im is None else im.shape[:2] for im in ims]
 
     def plain_tensors():
-        SF.tensor_files_call(lambda ptrs, lens, n_, fmt, outs, status: L.ffhip_webp_decode_files_tensor(ptrs, lens, n_, 4, fmt, outs, None, None, status, None),
-                             files, u8, shapes_of(images), images)
+        SF.tensor_files_call(lambda ptrs, lens, n_, fmt, outs, status: L.ffhip_webp_decode_files_tensor(ptrs, lens, n_, n_threads, fmt, outs, None, None, status,
+                                                                                                        SF.h(stream)), files, u8, shapes_of(images), images, SF.h(stream))
 
     def resized():
-        check_files("ffhip_webp_decode_files_tensor_resized", (files, images, bad), u8, AA, per_file_sizes(n), inner_rois(images, bad))
+        check_files("ffhip_webp_decode_files_tensor_resized", (files, images, bad), u8, AA, per_file_sizes(n), inner_rois(images, bad), stream=SF.h(stream),
+                    n_threads=n_threads)
 
     def oriented():
         orient = (C.c_int * n)(*([8] * n))
         keys = [None if im is None else X.orient(im, 8) for im in images]
         SF.tensor_files_call(lambda ptrs, lens, n_, fmt, outs, status: L.ffhip_webp_decode_files_tensor_oriented(
-            ptrs, lens, n_, 4, fmt, outs, None, None, AA, orient, None, None, status, None), files, u8, shapes_of(keys), keys)
+            ptrs, lens, n_, n_threads, fmt, outs, None, None, AA, orient, None, None, status, SF.h(stream)), files, u8, shapes_of(keys), keys, SF.h(stream))
 
     def libwebp_rule():
         m = len(lw_files)
         orient = (C.c_int * m)(*([6] * m))
         keys = [X.orient(im, 6) for im in lw_images]
         SF.tensor_files_call(lambda ptrs, lens, n_, fmt, outs, status: L.ffhip_webp_decode_files_tensor_ex(
-            ptrs, lens, n_, 4, fmt, outs, None, None, AA, orient, None, capi.FFHIP_WEBP_PIXELS_LIBWEBP, None, status, None), lw_files, u8, shapes_of(keys), keys)
-    small = [plain_tensors, resized, oriented, libwebp_rule]
+            ptrs, lens, n_, n_threads, fmt, outs, None, None, AA, orient, None, capi.FFHIP_WEBP_PIXELS_LIBWEBP, None, status, SF.h(stream)), lw_files, u8, shapes_of(keys),
+            keys, SF.h(stream))
+    return [plain_tensors, resized, oriented, libwebp_rule]
+
+
+def test_webp_files_to_tensors():
+    """the four WebP files-to-tensors entries: the NULL stream's"""
+    small = webp_tensor_runs()
     SF.run_protocol("webp files to tensors", None, small, small, ["SCRATCH_TENSOR_BGRA", "SCRATCH_RESIZE_BGRA", "SCRATCH_ORIENT_BGRA"])
 
 
@@ -557,16 +587,22 @@ def test_hevc_residual_and_intra(stream):
 @pytest.mark.parametrize("decode", [False, True], ids=["recon_tiles", "decode_tiles"])
 def test_hevc_tile_calls_back_to_back(stream, decode):
     """three calls on one list back to back: both one-chunk scratches and their guard events are crossed behind every fill"""
-    s = stream
-    calls = 3
+    run = tiles_runner(decode, stream)
+    SF.run_protocol(f"hevc tiles {decode}", stream, [run], [run], ["SCRATCH_HEVC_TILES_ONE"])
+
+
+def tiles_runner(decode, s, calls=3):
+    """`calls` ffhip_hevc_intra_recon_tiles / ffhip_hevc_decode_tiles calls on one list back to back on `s`, every plane against the oracle's"""
     one, drs, sets, outputs_of, expect_of, keep = TSO.hevc_tiles_case(decode, calls)
     want = [[np.array(SO.as_bytes(e)) for e in expect_of(i, "true")] for i in range(calls)]
 
-    def run():
+    def run(s=s):
         L = capi.lib()
+        own = isinstance(s, SF.StreamBox)
+        s = SF.h(s)
         for i in range(calls):
             for o in outputs_of(i):
-                o.refill()
+                o.refill(s if own else None)
         for op in drs:
             SO.copy(op.dev.ptr, op.true.ptr, op.nbytes, s)
         for i in range(calls):
@@ -578,17 +614,19 @@ def test_hevc_tile_calls_back_to_back(stream, decode):
             for k, (o, e) in enumerate(zip(outputs_of(i), want[i])):
                 got = o.written()
                 assert np.array_equal(got, e), (i, k, np.flatnonzero(got != e)[:4].tolist())
-    SF.run_protocol(f"hevc tiles {decode}", s, [run], [run], ["SCRATCH_HEVC_TILES_ONE"])
+    run.keep = keep
+    return run
 
 
 # ---------------------------------------------------------------------------------------------------- PNG and lossless WebP
-def lossless_runner(entry, files, keys, sizes, s, statuses=None):
+def lossless_runner(entry, files, keys, sizes, s, statuses=None, n_threads=4):
     L = capi.lib()
     places = [(4 * w, h) for w, h in sizes]
 
     def run():
-        SF.files_call(lambda ptrs, lens, n, outs, pitches, status: getattr(L, entry)(ptrs, lens, n, 4, outs, pitches, None, status, s), files, places, keys, statuses)
-        capi.sync(s)
+        SF.files_call(lambda ptrs, lens, n, outs, pitches, status: getattr(L, entry)(ptrs, lens, n, n_threads, outs, pitches, None, status, SF.h(s)),
+                      files, places, keys, statuses)
+        return capi.sync(SF.h(s))
     return run
 
 
@@ -606,9 +644,9 @@ def sizes_of(keys, default=(8, 8)):
     return [default if k is None else (k.shape[1], k.shape[0]) for k in keys]
 
 
-def tensor_runs(entry, files, images):
+def tensor_runs(entry, files, images, stream=None, n_threads=4):
     """the tensor entry of PNG / lossless WebP with a rectangle, both resize filters and an imposed orientation: the numpy rules on the
-    witness's pictures"""
+    witness's pictures; on the NULL stream unless one is given"""
     L = capi.lib()
     n = len(files)
     u8 = make_format(U8, 1, 0)
@@ -617,21 +655,22 @@ def tensor_runs(entry, files, images):
         rects = (capi.Rect * n)(*[capi.Rect(*r) for r in roi]) if roi else None
         out_size = (capi.Size * n)(*[capi.Size(w, h) for h, w in sizes]) if sizes else None
         turn = (C.c_int * n)(*(orient or [1] * n))                         # (NULL would be every file's own tag: one case has an EXIF chunk)
-        return lambda ptrs, lens, n_, fmt, outs, status: getattr(L, entry)(ptrs, lens, n_, 4, fmt, outs, rects, out_size, filt, turn, None, 0, None, status, None)
+        return lambda ptrs, lens, n_, fmt, outs, status: getattr(L, entry)(ptrs, lens, n_, n_threads, fmt, outs, rects, out_size, filt, turn, None, 0, None, status,
+                                                                           SF.h(stream))
 
     def roi():
         rois = [(w // 3, h // 4, w - w // 3 - w // 5, h - h // 4 - h // 6) for h, w in (im.shape[:2] for im in images)]
         keys = [im[y0:y0 + rh, x0:x0 + rw] for im, (x0, y0, rw, rh) in zip(images, rois)]
-        SF.tensor_files_call(call(rois, None, AA, None), files, u8, [k.shape[:2] for k in keys], keys)
+        SF.tensor_files_call(call(rois, None, AA, None), files, u8, [k.shape[:2] for k in keys], keys, SF.h(stream))
 
     def resized():
         for filt in (AA, BIL):
             keys = [resize_rule(im, 32, 32, filt) for im in images]
-            SF.tensor_files_call(call(None, [(32, 32)] * n, filt, None), files, u8, [(32, 32)] * n, keys)
+            SF.tensor_files_call(call(None, [(32, 32)] * n, filt, None), files, u8, [(32, 32)] * n, keys, SF.h(stream))
 
     def turned():
         keys = [X.orient(im, 6) for im in images]
-        SF.tensor_files_call(call(None, None, AA, [6] * n), files, u8, [k.shape[:2] for k in keys], keys)
+        SF.tensor_files_call(call(None, None, AA, [6] * n), files, u8, [k.shape[:2] for k in keys], keys, SF.h(stream))
     return [roi, resized, turned]
 
 
