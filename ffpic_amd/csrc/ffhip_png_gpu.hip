@@ -1,7 +1,8 @@
 /* ffhip_png_gpu.hip -- PNG files to BGRA pictures on the device (include/ffpic_hip.h, "PNG").  Host threads walk the chunks,
  * check the CRCs and inflate (ffhip_png.c, ffhip_inflate.c) straight into a part's pinned staging; one upload; k_png_unfilter undoes the
  * row filters in place, k_png_expand writes the pictures.  Both kernels compile the functions of ffhip_png_body.h, as ffhip_png_picture
- * does on the host, and neither has an error path: what a file can be refused for is seen on the host.
+ * does on the host, and neither has an error path: what a file can be refused for is seen on the host.  How a part is driven -- the
+ * launch per band level, the gather launch, the end of a part, the stage clock -- is ffhip_staged.h's; the cut into parts is here.
  *
  * k_png_unfilter.  An item is one (file, pass) sub-image, cut into bands of 64 rows; a wave takes one band, lane r its row r.  A row is
  * walked in CHUNKS of four filter units (4 x bpp bytes = bpp dwords), and the lanes are skewed by one chunk: at step t lane r
@@ -18,17 +19,15 @@
  * k_png_expand.  The gather form: a lane owns four consecutive output pixels of a row and makes one 16-byte store.  Of an Adam7 file the
  * lane finds each pixel's pass and index by the map, so stores stay full rows whatever the interlace.  A picture's last partial group of
  * four is stored pixel by pixel. */
-#include "ffhip_items.h"
+#include "ffhip_staged.h"
 #include "ffhip_png_internal.h"
 
-#include <algorithm>
 #include <chrono>
-#include <stdlib.h>
 
 namespace {
 
 constexpr int PNG_BAND = 64;
-constexpr int PNG_EXPAND_THREADS = 256;
+constexpr int PNG_EXPAND_THREADS = FFHIP_GATHER_THREADS;
 
 /* one (file, pass) sub-image: `rows` rows of 1 + row_bytes bytes at `sub` */
 struct PngUnfDesc {
@@ -60,9 +59,6 @@ struct PngExpArgs {
 
 template <int N> struct __attribute__((packed)) PngRun { u32 w[N]; }; /* N dwords at any byte address */
 
-/* byte i (static) of a run of dwords */
-template <int N> __device__ __forceinline__ int png_byte(const u32 (&w)[N], int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); }
-
 /* nb <= 4 * N bytes at p -> w, zero behind them; nb == 4 * N is one unaligned load */
 template <int N> __device__ __forceinline__ void png_load_run(const uint8_t *p, u32 nb, u32 (&w)[N])
 {
@@ -90,7 +86,7 @@ template <int N> __device__ __forceinline__ void png_store_run(uint8_t *p, u32 n
     }
 #pragma unroll
     for (int i = 0; i < 4 * N; i++)
-        if ((u32)i < nb) p[i] = (uint8_t)png_byte(w, i);
+        if ((u32)i < nb) p[i] = (uint8_t)byte_of(w, i);
 }
 
 /* One band.  Every lane runs every step, whatever its row: the cross-lane move wants the whole wave */
@@ -110,7 +106,7 @@ template <int BPP> __device__ __forceinline__ void png_unfilter_band(const PngUn
     for (u32 t = 0; t < n_chunks + PNG_BAND - 1; t++) {
         u32 up[BPP];
 #pragma unroll
-        for (int k = 0; k < BPP; k++) up[k] = (u32)__builtin_amdgcn_update_dpp(0, (int)out[k], 0x138, 0xf, 0xf, false); /* wave_shr:1 -- lane r - 1; lane 0: 0 */
+        for (int k = 0; k < BPP; k++) up[k] = wave_shr1(out[k]); /* lane r - 1's; lane 0: 0 */
         const u32 q = t - (u32)lane;
         if (!live || t < (u32)lane || q >= n_chunks) continue;
         const u32 nb = min((u32)CB, d.row_bytes - q * CB);
@@ -120,9 +116,9 @@ template <int BPP> __device__ __forceinline__ void png_unfilter_band(const PngUn
         int o[CB];
 #pragma unroll
         for (int i = 0; i < CB; i++) {
-            const int a = i >= BPP ? o[i - BPP] : png_byte(out, 3 * BPP + i);
-            const int c = i >= BPP ? png_byte(up, i - BPP) : png_byte(corner, 3 * BPP + i);
-            o[i] = ffhip_png_unfilter_byte(ft, png_byte(raw, i), a, png_byte(up, i), c);
+            const int a = i >= BPP ? o[i - BPP] : byte_of(out, 3 * BPP + i);
+            const int c = i >= BPP ? byte_of(up, i - BPP) : byte_of(corner, 3 * BPP + i);
+            o[i] = ffhip_png_unfilter_byte(ft, byte_of(raw, i), a, byte_of(up, i), c);
         }
 #pragma unroll
         for (int k = 0; k < BPP; k++) {
@@ -172,7 +168,7 @@ __global__ __launch_bounds__(PNG_EXPAND_THREADS) void k_png_expand(PngExpArgs a)
             u32 w[3];
             png_load_run(row + 3ull * x0, 12, w);
 #pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = ffhip_png_bgra((u32)png_byte(w, 3 * j + 2), (u32)png_byte(w, 3 * j + 1), (u32)png_byte(w, 3 * j), 255u);
+            for (int j = 0; j < 4; j++) v[j] = ffhip_png_bgra((u32)byte_of(w, 3 * j + 2), (u32)byte_of(w, 3 * j + 1), (u32)byte_of(w, 3 * j), 255u);
         }
     } else {
 #pragma unroll
@@ -194,49 +190,15 @@ __global__ __launch_bounds__(PNG_EXPAND_THREADS) void k_png_expand(PngExpArgs a)
 thread_local int t_png_last[2];     /* ffhip_debug_png_last */
 thread_local double t_png_times[4]; /* ffhip_debug_png_times */
 
-/* FFHIP_PNG_TIMES: events around a part's upload, unfilter launches and expand launch; off, nothing is recorded */
-struct PngClock {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool on = false;
-    PngClock()
-    {
-        const char *v = FFHIP_ENV("FFHIP_PNG_TIMES");
-        on = v && v[0] && v[0] != '0';
-        for (int k = 0; on && k < 4; k++)
-            if (hipEventCreate(&ev[k]) != hipSuccess) on = false;
-    }
-    ~PngClock()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int k, hipStream_t st) { if (on) (void)hipEventRecord(ev[k], st); }
-    void add() /* behind the part's synchronisation */
-    {
-        for (int k = 0; on && k < 3; k++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) t_png_times[k + 1] += ms;
-        }
-    }
-};
-
-size_t png_place(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-size_t png_part_budget()
-{
-    const char *v = FFHIP_ENV("FFHIP_PNG_PART_BYTES");
-    const long long b = v ? atoll(v) : 0;
-    return b > 0 ? (size_t)b : (size_t)1 << 30;
-}
-
 struct PngPartFile { int idx; size_t rows_off, palette_off; };
 
-/* One part: files pf[] of the call, `bytes` of staging (their filtered pictures, then the palettes) */
+/* One part: files pf[] of the call, `bytes` of staging (their filtered pictures, then the palettes).  The clock (FFHIP_PNG_TIMES) stands
+ * around the upload, the unfilter launches and the expand launch */
 int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::vector<ffhip_png_file> &pf, const uint8_t *const *files, const size_t *lens,
-                 int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, int *status, void *stream, PngClock &clock)
+                 int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, int *status, void *stream, StageClock &clock)
 {
     hipStream_t st = (hipStream_t)stream;
-    for (int k = 0; k < 4; k++) clock.mark(k, st); /* a part that launches nothing has empty intervals */
+    clock.mark_from(0, st);
     uint8_t *pin = ffhip_pinned_scratch(SCRATCH_PNG, stream, bytes + 64);
     uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_PNG, stream, bytes / 4 + 16);
     if (!pin || !dev) return FFHIP_ENOMEM;
@@ -248,9 +210,9 @@ int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::
         if (f.info.color_type == 3) memcpy(pin + p.palette_off, f.palette, 1024);
     });
     t_png_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    clock.mark(0, st);
+    clock.mark_from(0, st);
     FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    for (int k = 1; k < 4; k++) clock.mark(k, st);
+    clock.mark_from(1, st);
     std::vector<PngUnfDesc> unf;
     std::vector<PngExpDesc> exp;
     unsigned long long total = 0;
@@ -266,7 +228,6 @@ int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::
         e.palette = info.color_type == 3 ? (const u32 *)(dev + p.palette_off) : nullptr;
         e.width = (u32)info.width;
         e.height = (u32)info.height;
-        e.groups_x = (e.width + 3) / 4;
         e.rule = f.rule;
         unsigned long long at = 0;
         for (int q = 0; q < 7; q++) {
@@ -282,41 +243,23 @@ int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::
             unf.push_back(u);
             at += (unsigned long long)e.pass_pitch[q] * u.rows;
         }
-        e.first_wg = (u32)total;
-        e.n_wgs = (u32)(((unsigned long long)e.groups_x * e.height + PNG_EXPAND_THREADS - 1) / PNG_EXPAND_THREADS); /* < 2^22: both sides below 2^16 */
-        total += e.n_wgs;
+        ffhip_gather_place(e, &total); /* n_wgs < 2^22: both sides below 2^16 */
         exp.push_back(e);
     }
     if (exp.empty()) return FFHIP_OK;
-    if (total > 0xffffffffULL) return FFHIP_EINVAL;
-    /* the sub-images with the most bands first: the items that have a band l are then the first cnt(l) records, and level l is the
-     * workgroups [0, cnt(l)) of the records themselves -- a workgroup's item is its index, so this table needs no second one */
-    std::stable_sort(unf.begin(), unf.end(), [](const PngUnfDesc &x, const PngUnfDesc &y) { return x.n_bands > y.n_bands; });
-    uint8_t *d_unf = nullptr;
-    int rc = ffhip_items_stage(SCRATCH_PNG + 1, stream, unf.data(), unf.size() * sizeof(PngUnfDesc), 0, 0, &d_unf);
+    int rc = ffhip_banded_launches(SCRATCH_PNG + 1, stream, unf, &t_png_last[1], [&](u32 level, const PngUnfDesc *d_unf, unsigned grid_x, u32 wg_base) {
+        PngUnfArgs a;
+        a.desc = d_unf; a.level = level; a.wg_base = wg_base;
+        hipLaunchKernelGGL(k_png_unfilter, dim3(grid_x), dim3(PNG_BAND), 0, st, a);
+    });
     if (rc) return rc;
-    size_t cnt = unf.size();
-    for (u32 level = 0; level < unf[0].n_bands; level++) {
-        while (unf[cnt - 1].n_bands <= level) cnt--;
-        rc = ffhip_items_launch(0, cnt, [&](unsigned grid_x, u32 wg_base) {
-            PngUnfArgs a;
-            a.desc = (const PngUnfDesc *)d_unf; a.level = level; a.wg_base = wg_base;
-            hipLaunchKernelGGL(k_png_unfilter, dim3(grid_x), dim3(PNG_BAND), 0, st, a);
-        });
-        if (rc) return rc;
-        t_png_last[1]++;
-    }
-    for (int k = 2; k < 4; k++) clock.mark(k, st);
-    const PngExpDesc *d_exp = nullptr;
-    u32 *d_table = nullptr;
-    rc = ffhip_items_upload(SCRATCH_PNG + 2, stream, exp, total, &d_exp, &d_table);
-    if (rc) return rc;
-    rc = ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
+    clock.mark_from(2, st);
+    rc = ffhip_gather_launch(SCRATCH_PNG + 2, stream, exp, total, [&](const PngExpDesc *d_exp, const u32 *d_table, unsigned grid_x, u32 wg_base) {
         PngExpArgs a;
         a.desc = d_exp; a.wg_item = d_table; a.wg_base = wg_base;
         hipLaunchKernelGGL(k_png_expand, dim3(grid_x), dim3(PNG_EXPAND_THREADS), 0, st, a);
     });
-    clock.mark(3, st);
+    clock.mark_from(3, st);
     return rc;
 }
 
@@ -327,8 +270,7 @@ extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const 
 {
     if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    if (n_threads < 1) n_threads = 1;
-    if (n_threads > 64) n_threads = 64;
+    n_threads = ffhip_host_threads(n_threads);
     std::vector<ffhip_png_file> pf((size_t)n);
     ffhip_parallel_for(n, n_threads, [&](int i) {
         ffhip_png_file &f = pf[(size_t)i];
@@ -336,21 +278,20 @@ extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const 
         if (status[i]) memset(&f.info, 0, sizeof(f.info));
         if (info_out) info_out[i] = f.info;
         if (status[i]) return;
-        /* what k_png_expand asks of an output: whole 16-byte stores */
-        if (!d_bgra[i] || ((uintptr_t)d_bgra[i] & 15) || pitch[i] < 4LL * f.info.width || (pitch[i] & 15) || pitch[i] > 0x7fffffffLL) status[i] = FFHIP_EINVAL;
+        if (!ffhip_bgra_takes_stores16(d_bgra[i], pitch[i], f.info.width)) status[i] = FFHIP_EINVAL; /* k_png_expand's */
     });
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     t_png_last[0] = t_png_last[1] = 0;
     for (double &t : t_png_times) t = 0;
-    PngClock clock;
-    const size_t budget = png_part_budget();
+    StageClock clock(FFHIP_ENV("FFHIP_PNG_TIMES"), t_png_times);
+    const size_t budget = ffhip_part_budget(FFHIP_ENV("FFHIP_PNG_PART_BYTES"));
     int rc = FFHIP_OK;
     for (int i = 0; i < n && rc == FFHIP_OK;) {
         std::vector<PngPartFile> part;
         size_t rows = 0, palettes = 0;
         for (; i < n; i++) {
             if (status[i]) continue;
-            const size_t need = png_place((size_t)pf[(size_t)i].info.filtered_bytes);
+            const size_t need = ffhip_up16((size_t)pf[(size_t)i].info.filtered_bytes);
             if (!part.empty() && rows + need > budget) break;
             part.push_back({i, rows, palettes});
             rows += need;
@@ -359,14 +300,7 @@ extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const 
         if (part.empty()) break;
         for (PngPartFile &p : part) p.palette_off += rows;
         t_png_last[0]++;
-        rc = png_run_part(part, rows + palettes, pf, files, lens, n_threads, d_bgra, pitch, status, stream, clock);
-        const hipError_t e = hipStreamSynchronize((hipStream_t)stream); /* the next part, and the next call, refill the staging */
-        if (e != hipSuccess) {
-            ffhip_note_hip_error((int)e, "hipStreamSynchronize");
-            if (rc == FFHIP_OK) rc = FFHIP_EIO;
-        } else {
-            clock.add();
-        }
+        rc = ffhip_part_end(png_run_part(part, rows + palettes, pf, files, lens, n_threads, d_bgra, pitch, status, stream, clock), stream, clock);
     }
     if (rc) return rc;
     for (int k = 0; k < n; k++)
@@ -374,17 +308,6 @@ extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const 
     return FFHIP_OK;
 }
 
-extern "C" int ffhip_debug_png_last(int out[2])
-{
-    if (!out) return FFHIP_EINVAL;
-    out[0] = t_png_last[0];
-    out[1] = t_png_last[1];
-    return FFHIP_OK;
-}
+extern "C" int ffhip_debug_png_last(int out[2]) { return ffhip_copy_out(out, t_png_last); }
 
-extern "C" int ffhip_debug_png_times(double out[4])
-{
-    if (!out) return FFHIP_EINVAL;
-    for (int k = 0; k < 4; k++) out[k] = t_png_times[k];
-    return FFHIP_OK;
-}
+extern "C" int ffhip_debug_png_times(double out[4]) { return ffhip_copy_out(out, t_png_times); }

@@ -6,7 +6,7 @@
  * ffhip_bgra_orient_items in front of this stage).
  * The layout of the work is described in ffhip_tensor_body.h.
  */
-#include "ffhip_items.h"
+#include "ffhip_staged.h" /* ffhip_part_budget */
 #include "ffhip_jpeg_scaled_body.h"
 #include "ffhip_orient_body.h"
 #include "ffhip_tensor_body.h"
@@ -150,13 +150,6 @@ thread_local int g_tensor_last_parts = 0; /* ffhip_debug_tensor_last_parts */
 thread_local int g_orient_last_items = 0; /* ffhip_debug_orient_last_items */
 /* decodes files [first, first + cnt) into d_bgra[k] with pitch[k]: the call underneath, its per-file codes into status + first */
 typedef std::function<int(int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch)> TensorDecode;
-
-size_t tensor_part_budget()
-{
-    const char *v = FFHIP_ENV("FFHIP_TENSOR_PART_BYTES");
-    const long long b = v ? atoll(v) : 0;
-    return b > 0 ? (size_t)b : (size_t)1 << 30;
-}
 
 /* What an entry point was asked for behind the files, the format and the outputs.  roi and out_size are the caller's: UPRIGHT axes, full
  * size.  out_size == NULL: every file keeps its rectangle's size.  denom == NULL: every file at full size; otherwise file i at
@@ -356,7 +349,7 @@ int tensor_files_run(const std::vector<TensorFile> &plan, const TensorOptions &o
     g_tensor_last_parts = 0; /* a call that returns before its first part has taken none */
     g_orient_last_items = 0;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
-    const size_t budget = tensor_part_budget();
+    const size_t budget = ffhip_part_budget(FFHIP_ENV("FFHIP_TENSOR_PART_BYTES"));
     for (int first = 0; (size_t)first < plan.size();) {
         const TensorPart p = tensor_part_extent(plan, first, budget);
         uint8_t *base = nullptr;

@@ -2,7 +2,9 @@
  * threads decode the prefix codes, copies and colour cache (ffhip_vp8l.c) straight into a part's pinned staging: a file's RESIDUAL image,
  * its predictor and cross-colour block images and its palette; one upload; k_vp8l_predict undoes the predictor in place, k_vp8l_finish
  * undoes what is left and writes the pictures.  Both kernels compile the functions of ffhip_vp8l_body.h, as ffhip_vp8l_picture does on the
- * host, and neither has an error path: what a file can be refused for is seen on the host.
+ * host, and neither has an error path: what a file can be refused for is seen on the host.  How a part is driven -- the launch per band
+ * level, the gather launch, the end of a part, the stage clock -- is ffhip_staged.h's; the cut into parts is here, and so is the block of
+ * functions that ffhip_webp_alpha_gpu.hip borrows (ffhip_vp8l_internal.h).
  *
  * k_vp8l_predict, in the form of k_png_unfilter.  An item is a file, cut into bands of 64 rows; a wave takes one band, lane r its row r.
  * A row is walked in CHUNKS of four pixels (16 bytes), and the lanes are skewed by TWO chunks: at step t lane r reconstructs chunk t - 2r.
@@ -25,10 +27,9 @@
  * k_vp8l_finish.  The gather form of k_png_expand: a lane owns four consecutive output pixels of a row, applies the pointwise transforms
  * behind the predictor in the file's order, looks a colour-indexed file's pixels up in the palette (2, 4 or 8 to a word), applies the
  * alpha rule and makes one 16-byte store.  A picture's last partial group of four is stored pixel by pixel. */
-#include "ffhip_items.h"
+#include "ffhip_staged.h"
 #include "ffhip_vp8l_internal.h"
 
-#include <algorithm>
 #include <chrono>
 #include <stdlib.h>
 
@@ -36,7 +37,7 @@ namespace {
 
 constexpr int VP8L_BAND = 64;
 constexpr int VP8L_SKEW = 2; /* chunks between a lane and the lane above it */
-constexpr int VP8L_FINISH_THREADS = 256;
+constexpr int VP8L_FINISH_THREADS = FFHIP_GATHER_THREADS;
 
 /* one file's residual image, to be predicted in place */
 struct Vp8lPredDesc {
@@ -68,8 +69,6 @@ struct Vp8lFinArgs {
 };
 
 struct __attribute__((packed, aligned(4))) Vp8lQuad { u32 w[4]; }; /* four words at any word address */
-
-__device__ __forceinline__ u32 vp8l_shr1(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); } /* wave_shr:1 -- lane r - 1; lane 0: 0 */
 
 /* n <= 4 words at p -> w, zero behind them */
 __device__ __forceinline__ void vp8l_load(const u32 *p, int n, u32 (&w)[4])
@@ -104,8 +103,8 @@ __global__ __launch_bounds__(VP8L_BAND) void k_vp8l_predict(Vp8lPredArgs a)
     for (u32 t = 0; t < n_chunks + VP8L_SKEW * (VP8L_BAND - 1); t++) {
         u32 up[6];
 #pragma unroll
-        for (int k = 0; k < 4; k++) up[1 + k] = vp8l_shr1(older[k]);
-        up[5] = vp8l_shr1(newer[0]);
+        for (int k = 0; k < 4; k++) up[1 + k] = wave_shr1(older[k]);
+        up[5] = wave_shr1(newer[0]);
         if (t < start) continue;
         const u32 q = t - start;
 #pragma unroll
@@ -200,60 +199,46 @@ __global__ __launch_bounds__(VP8L_FINISH_THREADS) void k_vp8l_finish(Vp8lFinArgs
 thread_local int t_vp8l_last[3];     /* ffhip_debug_vp8l_last */
 thread_local double t_vp8l_times[4]; /* ffhip_debug_vp8l_times */
 
-/* FFHIP_VP8L_TIMES: events around a part's upload, predict launches and finish launch; off, nothing is recorded */
-struct Vp8lClock {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool on = false;
-    Vp8lClock()
-    {
-        const char *v = FFHIP_ENV("FFHIP_VP8L_TIMES");
-        on = v && v[0] && v[0] != '0';
-        for (int k = 0; on && k < 4; k++)
-            if (hipEventCreate(&ev[k]) != hipSuccess) on = false;
-    }
-    ~Vp8lClock()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int k, hipStream_t st) { if (on) (void)hipEventRecord(ev[k], st); }
-    void add() /* behind the part's synchronisation */
-    {
-        for (int k = 0; on && k < 3; k++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) t_vp8l_times[k + 1] += ms;
-        }
-    }
-};
-
-size_t vp8l_part_budget()
+size_t vp8l_res_bytes(const ffhip_vp8l_file &f)
 {
-    const char *v = FFHIP_ENV("FFHIP_VP8L_PART_BYTES");
-    const long long b = v ? atoll(v) : 0;
-    return b > 0 ? (size_t)b : (size_t)1 << 30;
+    return 4 * (size_t)(f.device_form ? f.info.residual_width : f.info.width) * (size_t)f.info.height;
+}
+size_t vp8l_side_bytes(const ffhip_vp8l_file &f)
+{
+    if (!f.device_form) return 0;
+    return ffhip_up16(4 * (size_t)f.predictor_words) + ffhip_up16(4 * (size_t)f.cross_words) + (f.steps.has_index ? 1024 : 0);
+}
+
+/* One part: files pf[] of the call, `bytes` of staging.  The clock (FFHIP_VP8L_TIMES) stands around the upload, the predict launches and
+ * the finish launch */
+int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std::vector<ffhip_vp8l_file> &pf, int n_threads, uint8_t *const *d_bgra,
+                  const int64_t *pitch, int *status, void *stream, StageClock &clock)
+{
+    hipStream_t st = (hipStream_t)stream;
+    clock.mark_from(0, st);
+    uint8_t *pin = ffhip_pinned_scratch(SCRATCH_VP8L, stream, bytes + 64);
+    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_VP8L, stream, bytes / 4 + 16);
+    if (!pin || !dev) return FFHIP_ENOMEM;
+    const auto t0 = std::chrono::steady_clock::now();
+    ffhip_parallel_for((int)part.size(), n_threads, [&](int k) { status[part[(size_t)k].idx] = vp8l_stage_file(pf[(size_t)part[(size_t)k].idx], part[(size_t)k], pin); });
+    t_vp8l_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    clock.mark_from(0, st);
+    FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
+    clock.mark_from(1, st);
+    return vp8l_enqueue_part(part, dev, pf.data(), d_bgra, pitch, status, stream, SCRATCH_VP8L, t_vp8l_last + 1, &clock);
 }
 
 } // namespace
 
-static size_t vp8l_place(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-static size_t vp8l_res_bytes(const ffhip_vp8l_file &f)
-{
-    return 4 * (size_t)(f.device_form ? f.info.residual_width : f.info.width) * (size_t)f.info.height;
-}
-static size_t vp8l_side_bytes(const ffhip_vp8l_file &f)
-{
-    if (!f.device_form) return 0;
-    return vp8l_place(4 * (size_t)f.predictor_words) + vp8l_place(4 * (size_t)f.cross_words) + (f.steps.has_index ? 1024 : 0);
-}
+/* ---- lent to ffhip_webp_alpha_gpu.hip, as ffhip_vp8l_internal.h describes: from here to the mark below ---- */
 
 size_t vp8l_part_add(std::vector<Vp8lPartFile> &part, const ffhip_vp8l_file &f, int idx, size_t *res, size_t *side)
 {
     Vp8lPartFile p{idx, *res, *side, 0, 0};
-    p.cross_off = p.modes_off + (f.device_form ? vp8l_place(4 * (size_t)f.predictor_words) : 0);
-    p.palette_off = p.cross_off + (f.device_form ? vp8l_place(4 * (size_t)f.cross_words) : 0);
+    p.cross_off = p.modes_off + (f.device_form ? ffhip_up16(4 * (size_t)f.predictor_words) : 0);
+    p.palette_off = p.cross_off + (f.device_form ? ffhip_up16(4 * (size_t)f.cross_words) : 0);
     part.push_back(p);
-    *res += vp8l_place(vp8l_res_bytes(f));
+    *res += ffhip_up16(vp8l_res_bytes(f));
     *side += vp8l_side_bytes(f);
     return *res + *side;
 }
@@ -281,7 +266,7 @@ int vp8l_stage_file(const ffhip_vp8l_file &f, const Vp8lPartFile &p, uint8_t *pi
 }
 
 int vp8l_enqueue_part(const std::vector<Vp8lPartFile> &part, uint8_t *dev, const ffhip_vp8l_file *pf, uint8_t *const *d_bgra, const int64_t *pitch,
-                      const int *status, void *stream, int kind, int counts[2], const std::function<void(int)> &mark)
+                      const int *status, void *stream, int kind, int counts[2], StageClock *clock)
 {
     hipStream_t st = (hipStream_t)stream;
     std::vector<Vp8lPredDesc> pred;
@@ -297,7 +282,6 @@ int vp8l_enqueue_part(const std::vector<Vp8lPartFile> &part, uint8_t *dev, const
         e.pitch = pitch[p.idx];
         e.width = (u32)f.info.width;
         e.height = (u32)f.info.height;
-        e.groups_x = (e.width + 3) / 4;
         e.res_width = e.width;
         e.steps.has_alpha = (uint8_t)f.info.has_alpha;
         if (f.device_form) {
@@ -320,87 +304,36 @@ int vp8l_enqueue_part(const std::vector<Vp8lPartFile> &part, uint8_t *dev, const
         } else {
             counts[1]++;
         }
-        e.first_wg = (u32)total;
-        e.n_wgs = (u32)(((unsigned long long)e.groups_x * e.height + VP8L_FINISH_THREADS - 1) / VP8L_FINISH_THREADS); /* < 2^20: both sides at most 2^14 */
-        total += e.n_wgs;
+        ffhip_gather_place(e, &total); /* n_wgs < 2^20: both sides at most 2^14 */
         fin.push_back(e);
     }
     if (fin.empty()) return FFHIP_OK;
-    if (total > 0xffffffffULL) return FFHIP_EINVAL;
-    int rc = FFHIP_OK;
-    if (!pred.empty()) {
-        /* the files with the most bands first: the items that have a band l are then the first cnt(l) records, and level l is the
-         * workgroups [0, cnt(l)) of the records themselves */
-        std::stable_sort(pred.begin(), pred.end(), [](const Vp8lPredDesc &x, const Vp8lPredDesc &y) { return x.n_bands > y.n_bands; });
-        uint8_t *d_pred = nullptr;
-        rc = ffhip_items_stage(kind + 1, stream, pred.data(), pred.size() * sizeof(Vp8lPredDesc), 0, 0, &d_pred);
-        if (rc) return rc;
-        size_t cnt = pred.size();
-        for (u32 level = 0; level < pred[0].n_bands; level++) {
-            while (pred[cnt - 1].n_bands <= level) cnt--;
-            rc = ffhip_items_launch(0, cnt, [&](unsigned grid_x, u32 wg_base) {
-                Vp8lPredArgs a;
-                a.desc = (const Vp8lPredDesc *)d_pred; a.level = level; a.wg_base = wg_base;
-                hipLaunchKernelGGL(k_vp8l_predict, dim3(grid_x), dim3(VP8L_BAND), 0, st, a);
-            });
-            if (rc) return rc;
-            counts[0]++;
-        }
-    }
-    mark(2);
-    const Vp8lFinDesc *d_fin = nullptr;
-    u32 *d_table = nullptr;
-    rc = ffhip_items_upload(kind + 2, stream, fin, total, &d_fin, &d_table);
+    int rc = ffhip_banded_launches(kind + 1, stream, pred, &counts[0], [&](u32 level, const Vp8lPredDesc *d_pred, unsigned grid_x, u32 wg_base) {
+        Vp8lPredArgs a;
+        a.desc = d_pred; a.level = level; a.wg_base = wg_base;
+        hipLaunchKernelGGL(k_vp8l_predict, dim3(grid_x), dim3(VP8L_BAND), 0, st, a);
+    });
     if (rc) return rc;
-    rc = ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
+    if (clock) clock->mark_from(2, st);
+    rc = ffhip_gather_launch(kind + 2, stream, fin, total, [&](const Vp8lFinDesc *d_fin, const u32 *d_table, unsigned grid_x, u32 wg_base) {
         Vp8lFinArgs a;
         a.desc = d_fin; a.wg_item = d_table; a.wg_base = wg_base;
         hipLaunchKernelGGL(k_vp8l_finish, dim3(grid_x), dim3(VP8L_FINISH_THREADS), 0, st, a);
     });
-    mark(3);
+    if (clock) clock->mark_from(3, st);
     return rc;
 }
 
-namespace {
-
-/* One part: files pf[] of the call, `bytes` of staging */
-int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std::vector<ffhip_vp8l_file> &pf, int n_threads, uint8_t *const *d_bgra,
-                  const int64_t *pitch, int *status, void *stream, Vp8lClock &clock)
-{
-    hipStream_t st = (hipStream_t)stream;
-    for (int k = 0; k < 4; k++) clock.mark(k, st); /* a part that launches nothing has empty intervals */
-    uint8_t *pin = ffhip_pinned_scratch(SCRATCH_VP8L, stream, bytes + 64);
-    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_VP8L, stream, bytes / 4 + 16);
-    if (!pin || !dev) return FFHIP_ENOMEM;
-    const auto t0 = std::chrono::steady_clock::now();
-    ffhip_parallel_for((int)part.size(), n_threads, [&](int k) { status[part[(size_t)k].idx] = vp8l_stage_file(pf[(size_t)part[(size_t)k].idx], part[(size_t)k], pin); });
-    t_vp8l_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    clock.mark(0, st);
-    FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    for (int k = 1; k < 4; k++) clock.mark(k, st);
-    int counts[2] = {0, 0};
-    const int rc = vp8l_enqueue_part(part, dev, pf.data(), d_bgra, pitch, status, stream, SCRATCH_VP8L, counts, [&](int k) {
-        for (int j = k; j < 4; j++) clock.mark(j, st);
-    });
-    t_vp8l_last[1] += counts[0];
-    t_vp8l_last[2] += counts[1];
-    return rc;
-}
-
-} // namespace
+/* ---- the end of what is lent ---- */
 
 extern "C" int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
                                               const int64_t *pitch, ffhip_vp8l_info *info_out, int *status, void *stream)
 {
     if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    if (n_threads < 1) n_threads = 1;
-    if (n_threads > 64) n_threads = 64;
-    std::vector<ffhip_vp8l_file> pf((size_t)n);
-    struct Closer { /* the block images are the files' own heap */
-        std::vector<ffhip_vp8l_file> &v;
-        ~Closer() { for (ffhip_vp8l_file &f : v) ffhip_vp8l_close(&f); }
-    } closer{pf};
+    n_threads = ffhip_host_threads(n_threads);
+    Vp8lFiles opened((size_t)n);
+    std::vector<ffhip_vp8l_file> &pf = opened.v;
     const auto t_open = std::chrono::steady_clock::now();
     ffhip_parallel_for(n, n_threads, [&](int i) {
         ffhip_vp8l_file &f = pf[(size_t)i];
@@ -408,16 +341,15 @@ extern "C" int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const
         status[i] = files[i] && lens[i] ? ffhip_vp8l_open(files[i], lens[i], &f) : FFHIP_EINVAL;
         if (info_out) info_out[i] = f.info;
         if (status[i]) return;
-        /* what k_vp8l_finish asks of an output: whole 16-byte stores */
-        if (!d_bgra[i] || ((uintptr_t)d_bgra[i] & 15) || pitch[i] < 4LL * f.info.width || (pitch[i] & 15) || pitch[i] > 0x7fffffffLL) status[i] = FFHIP_EINVAL;
+        if (!ffhip_bgra_takes_stores16(d_bgra[i], pitch[i], f.info.width)) status[i] = FFHIP_EINVAL; /* k_vp8l_finish's */
     });
     const double open_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_open).count();
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     t_vp8l_last[0] = t_vp8l_last[1] = t_vp8l_last[2] = 0;
     for (double &t : t_vp8l_times) t = 0;
     t_vp8l_times[0] = open_ms; /* the headers, transform lists and their sub-images */
-    Vp8lClock clock;
-    const size_t budget = vp8l_part_budget();
+    StageClock clock(FFHIP_ENV("FFHIP_VP8L_TIMES"), t_vp8l_times);
+    const size_t budget = ffhip_part_budget(FFHIP_ENV("FFHIP_VP8L_PART_BYTES"));
     int rc = FFHIP_OK;
     for (int i = 0; i < n && rc == FFHIP_OK;) {
         std::vector<Vp8lPartFile> part;
@@ -425,20 +357,13 @@ extern "C" int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const
         for (; i < n; i++) {
             if (status[i]) continue;
             const ffhip_vp8l_file &f = pf[(size_t)i];
-            if (!part.empty() && res + vp8l_place(vp8l_res_bytes(f)) > budget) break;
+            if (!part.empty() && res + ffhip_up16(vp8l_res_bytes(f)) > budget) break;
             vp8l_part_add(part, f, i, &res, &side);
         }
         if (part.empty()) break;
         vp8l_part_seal(part, res);
         t_vp8l_last[0]++;
-        rc = vp8l_run_part(part, res + side, pf, n_threads, d_bgra, pitch, status, stream, clock);
-        const hipError_t e = hipStreamSynchronize((hipStream_t)stream); /* the next part, and the next call, refill the staging */
-        if (e != hipSuccess) {
-            ffhip_note_hip_error((int)e, "hipStreamSynchronize");
-            if (rc == FFHIP_OK) rc = FFHIP_EIO;
-        } else {
-            clock.add();
-        }
+        rc = ffhip_part_end(vp8l_run_part(part, res + side, pf, n_threads, d_bgra, pitch, status, stream, clock), stream, clock);
     }
     if (rc) return rc;
     for (int k = 0; k < n; k++)
@@ -446,16 +371,6 @@ extern "C" int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const
     return FFHIP_OK;
 }
 
-extern "C" int ffhip_debug_vp8l_last(int out[3])
-{
-    if (!out) return FFHIP_EINVAL;
-    for (int k = 0; k < 3; k++) out[k] = t_vp8l_last[k];
-    return FFHIP_OK;
-}
+extern "C" int ffhip_debug_vp8l_last(int out[3]) { return ffhip_copy_out(out, t_vp8l_last); }
 
-extern "C" int ffhip_debug_vp8l_times(double out[4])
-{
-    if (!out) return FFHIP_EINVAL;
-    for (int k = 0; k < 4; k++) out[k] = t_vp8l_times[k];
-    return FFHIP_OK;
-}
+extern "C" int ffhip_debug_vp8l_times(double out[4]) { return ffhip_copy_out(out, t_vp8l_times); }

@@ -44,10 +44,20 @@ int ffhip_vp8l_invert_host(const ffhip_vp8l_file *pf, uint32_t *residual, uint32
 #ifdef __cplusplus
 }
 
-#include <functional>
 #include <vector>
 
-/* ---- what ffhip_vp8l_gpu.hip lends ffhip_webp_alpha_gpu.hip: its part layout, its host stage and its two kernels' launches ----
+/* opened files and their owner: the block images are the files' own heap */
+struct Vp8lFiles {
+    std::vector<ffhip_vp8l_file> v;
+    explicit Vp8lFiles(size_t n) : v(n) {}
+    Vp8lFiles(const Vp8lFiles &) = delete;
+    ~Vp8lFiles() { for (ffhip_vp8l_file &f : v) ffhip_vp8l_close(&f); }
+};
+
+struct StageClock; /* ffhip_staged.h */
+
+/* ---- what ffhip_vp8l_gpu.hip lends ffhip_webp_alpha_gpu.hip, the block marked so there: its part layout, its host stage and its two
+ * kernels' launches ----
  * a file's place in its part's staging: the residual image (a host-form file: its finished pixels), then what the kernels read beside it */
 struct Vp8lPartFile { int idx; size_t res_off, modes_off, cross_off, palette_off; };
 /* file `idx` behind *res bytes of residual images and *side bytes beside them; both grow; -> the part's bytes so far */
@@ -58,9 +68,10 @@ void vp8l_part_seal(std::vector<Vp8lPartFile> &part, size_t res);
 int vp8l_stage_file(const ffhip_vp8l_file &f, const Vp8lPartFile &p, uint8_t *pin);
 /* k_vp8l_predict's levels and k_vp8l_finish over the part's files with status[idx] == 0, the staging uploaded to `dev`; pf, d_bgra, pitch
  * and status are indexed by Vp8lPartFile::idx; the records go through scratch kinds kind + 1 and kind + 2.  counts[0] += launches of
- * k_vp8l_predict, counts[1] += files the host inverted; mark(2) runs behind the predict launches, mark(3) behind the finish launch */
+ * k_vp8l_predict, counts[1] += files the host inverted; a clock is marked from 2 behind the predict launches and from 3 behind the finish
+ * launch, NULL is not */
 int vp8l_enqueue_part(const std::vector<Vp8lPartFile> &part, uint8_t *dev, const ffhip_vp8l_file *pf, uint8_t *const *d_bgra, const int64_t *pitch,
-                      const int *status, void *stream, int kind, int counts[2], const std::function<void(int)> &mark);
+                      const int *status, void *stream, int kind, int counts[2], StageClock *clock);
 #endif
 
 #endif

@@ -1,6 +1,6 @@
 /* ffhip_webp_alpha_gpu.hip -- the alpha plane of lossy WebP files into byte 3 of their pictures (include/ffpic_hip.h, "lossy WebP, the alpha
  * plane").  The stage runs behind the libwebp rule's back half of ffhip_webp_decode_files_device_ex, over the files with an
- * OK status and a plane, in parts of its own in the shape of vp8l_run_part: host threads copy a raw plane, or decode a lossless plane's
+ * OK status and a plane, in parts of its own, driven through ffhip_staged.h: host threads copy a raw plane, or decode a lossless plane's
  * prefix codes (ffhip_vp8l.c), into pinned staging; one upload; the lossless planes go through k_vp8l_predict and k_vp8l_finish, unchanged,
  * into scratch BGRA pictures, where alpha is byte 1 of a pixel; k_webp_alpha_unfilter undoes the filter into a byte plane;
  * k_webp_alpha_merge writes byte 3 of the pictures.  Neither kernel has an error path: what a file is refused for is seen on the host.
@@ -26,18 +26,16 @@
  * k_webp_alpha_merge.  Streaming: a lane owns four pixels of a row, loads their 16 bytes of BGRA and their four alpha samples -- from the
  * unfiltered plane, or for filter 0 straight from the source by the same pointer, pitch and step -- replaces byte 3 of each and makes one
  * 16-byte store.  A row's last partial group stores its alpha bytes one by one; nothing beside the width x height pixels is written. */
-#include "ffhip_items.h"
+#include "ffhip_staged.h"
 #include "ffhip_webp_alpha_internal.h"
 
-#include <algorithm>
 #include <chrono>
-#include <stdlib.h>
 
 namespace {
 
 constexpr int ALPHA_BAND = 64;
 constexpr int ALPHA_CHUNK = 16;
-constexpr int ALPHA_MERGE_THREADS = 256;
+constexpr int ALPHA_MERGE_THREADS = FFHIP_GATHER_THREADS;
 
 /* one file's stored plane: sample (x, y) is src[y * src_pitch + x * src_step] */
 struct AlphaUnfDesc {
@@ -63,10 +61,6 @@ struct AlphaMergeArgs {
     const u32 *wg_item;
     u32 wg_base;
 };
-
-__device__ __forceinline__ u32 alpha_shr1(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); } /* wave_shr:1 -- lane r - 1; lane 0: 0 */
-
-__device__ __forceinline__ int alpha_byte(const u32 (&w)[4], int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); }
 
 /* four samples at p, one a byte: step 1 a dword of a byte plane (p 4-byte aligned), step 4 one byte of each of four words (the words 16-byte aligned) */
 __device__ __forceinline__ u32 alpha_load4(const uint8_t *p, u32 step)
@@ -96,8 +90,8 @@ template <int MODE> __device__ __forceinline__ void alpha_chunk(const u32 (&raw)
     int o[ALPHA_CHUNK];
 #pragma unroll
     for (int i = 0; i < ALPHA_CHUNK; i++) {
-        const int b = alpha_byte(up, i);
-        o[i] = ffhip_webp_alpha_sample(MODE, alpha_byte(raw, i), a, b, c);
+        const int b = byte_of(up, i);
+        o[i] = ffhip_webp_alpha_sample(MODE, byte_of(raw, i), a, b, c);
         a = o[i];
         c = b;
     }
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(ALPHA_BAND) void k_webp_alpha_unfilter(AlphaUnfArgs
     for (u32 t = 0; t < n_chunks + ALPHA_BAND - 1; t++) {
         u32 up[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) up[k] = alpha_shr1(out[k]);
+        for (int k = 0; k < 4; k++) up[k] = wave_shr1(out[k]);
         const u32 q = t - (u32)lane;
         if (!live || t < (u32)lane || q >= n_chunks) continue;
         if (lane == 0 && above) alpha_load16(above + (unsigned long long)q * ALPHA_CHUNK, 1, up);
@@ -164,45 +158,6 @@ __global__ __launch_bounds__(ALPHA_MERGE_THREADS) void k_webp_alpha_merge(AlphaM
 thread_local int t_alpha_last[4];     /* ffhip_debug_webp_alpha_last */
 thread_local double t_alpha_times[4]; /* ffhip_debug_webp_alpha_times */
 
-/* FFHIP_WEBP_ALPHA_TIMES: events around a part's upload (with the lossless planes' two kernels), unfilter launches and merge launch; off,
- * nothing is recorded */
-struct AlphaClock {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool on = false;
-    AlphaClock()
-    {
-        const char *v = FFHIP_ENV("FFHIP_WEBP_ALPHA_TIMES");
-        on = v && v[0] && v[0] != '0';
-        for (int k = 0; on && k < 4; k++)
-            if (hipEventCreate(&ev[k]) != hipSuccess) on = false;
-    }
-    ~AlphaClock()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void mark(int from, hipStream_t st) /* the marks from `from` on: a part that launches nothing more has empty intervals */
-    {
-        for (int k = from; on && k < 4; k++) (void)hipEventRecord(ev[k], st);
-    }
-    void add() /* behind the part's synchronisation */
-    {
-        for (int k = 0; on && k < 3; k++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) t_alpha_times[k + 1] += ms;
-        }
-    }
-};
-
-size_t alpha_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
-
-size_t alpha_part_budget()
-{
-    const char *v = FFHIP_ENV("FFHIP_WEBP_ALPHA_PART_BYTES");
-    const long long b = v ? atoll(v) : 0;
-    return b > 0 ? (size_t)b : (size_t)1 << 30;
-}
-
 /* a file of the call with a plane */
 struct AlphaFile {
     int i; /* its index in the call */
@@ -212,17 +167,19 @@ struct AlphaFile {
  * in the part's work area its scratch picture (lossless) and its unfiltered plane (a filter) */
 struct AlphaPartFile { int j, v; size_t raw_off, pic_off, out_off; };
 
+size_t alpha_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
 size_t alpha_plane_pitch(const ffhip_webp_alpha_head &h) { return alpha_up(h.width, ALPHA_CHUNK); }
 size_t alpha_picture_pitch(const ffhip_webp_alpha_head &h) { return 4 * alpha_up(h.width, ALPHA_CHUNK); } /* a chunk of its samples is 64 bytes */
 
-/* One part: `vbytes` of VP8L staging, the raw planes behind them, `work_bytes` of pictures and planes that stay on the device */
+/* One part: `vbytes` of VP8L staging, the raw planes behind them, `work_bytes` of pictures and planes that stay on the device.  The clock
+ * (FFHIP_WEBP_ALPHA_TIMES) stands around the upload with the lossless planes' two kernels, the unfilter launches and the merge launch */
 int alpha_run_part(const std::vector<AlphaPartFile> &part, const std::vector<Vp8lPartFile> &vpart, size_t vbytes, size_t raw_bytes, size_t work_bytes,
                    const std::vector<AlphaFile> &af, const std::vector<ffhip_vp8l_file> &pf, std::vector<int> &st_a, std::vector<uint8_t *> &d_pic,
-                   std::vector<int64_t> &pic_pitch, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, void *stream, AlphaClock &clock)
+                   std::vector<int64_t> &pic_pitch, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, void *stream, StageClock &clock)
 {
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = vbytes + raw_bytes;
-    clock.mark(0, st);
+    clock.mark_from(0, st);
     uint8_t *pin = ffhip_pinned_scratch(SCRATCH_WEBP_ALPHA, stream, bytes + 64);
     uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_WEBP_ALPHA, stream, bytes / 4 + 16);
     uint8_t *work = (uint8_t *)ffhip_scratch(SCRATCH_WEBP_ALPHA + 3, stream, work_bytes / 4 + 16);
@@ -240,9 +197,9 @@ int alpha_run_part(const std::vector<AlphaPartFile> &part, const std::vector<Vp8
         for (u32 y = 0; y < h.height; y++) memcpy(to + y * pp, h.data + (size_t)y * h.width, h.width);
     });
     t_alpha_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    clock.mark(0, st);
+    clock.mark_from(0, st);
     FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
-    clock.mark(1, st);
+    clock.mark_from(1, st);
     int rc = FFHIP_OK;
     if (!vpart.empty()) {
         for (const AlphaPartFile &p : part) {
@@ -250,10 +207,10 @@ int alpha_run_part(const std::vector<AlphaPartFile> &part, const std::vector<Vp8
             d_pic[(size_t)p.j] = work + p.pic_off;
             pic_pitch[(size_t)p.j] = (int64_t)alpha_picture_pitch(af[(size_t)p.j].head);
         }
-        int counts[2] = {0, 0};
-        rc = vp8l_enqueue_part(vpart, dev, pf.data(), d_pic.data(), pic_pitch.data(), st_a.data(), stream, SCRATCH_WEBP_ALPHA, counts, [](int) {});
+        int counts[2] = {0, 0}; /* not reported: t_alpha_last[1] counts the lossless planes */
+        rc = vp8l_enqueue_part(vpart, dev, pf.data(), d_pic.data(), pic_pitch.data(), st_a.data(), stream, SCRATCH_WEBP_ALPHA, counts, nullptr);
         if (rc) return rc;
-        clock.mark(1, st);
+        clock.mark_from(1, st);
     }
     std::vector<AlphaUnfDesc> unf;
     std::vector<AlphaMergeDesc> mer;
@@ -288,43 +245,23 @@ int alpha_run_part(const std::vector<AlphaPartFile> &part, const std::vector<Vp8
         m.pitch = pitch[f.i];
         m.width = h.width;
         m.height = h.height;
-        m.groups_x = (m.width + 3) / 4;
-        m.first_wg = (u32)total;
-        m.n_wgs = (u32)(((unsigned long long)m.groups_x * m.height + ALPHA_MERGE_THREADS - 1) / ALPHA_MERGE_THREADS); /* < 2^20: both sides below 2^14 */
-        total += m.n_wgs;
+        ffhip_gather_place(m, &total); /* n_wgs < 2^20: both sides below 2^14 */
         mer.push_back(m);
     }
     if (mer.empty()) return FFHIP_OK;
-    if (total > 0xffffffffULL) return FFHIP_EINVAL;
-    if (!unf.empty()) {
-        /* the files with the most bands first: the items that have a band l are then the first cnt(l) records */
-        std::stable_sort(unf.begin(), unf.end(), [](const AlphaUnfDesc &x, const AlphaUnfDesc &y) { return x.n_bands > y.n_bands; });
-        uint8_t *d_unf = nullptr;
-        rc = ffhip_items_stage(SCRATCH_WEBP_ALPHA + 4, stream, unf.data(), unf.size() * sizeof(AlphaUnfDesc), 0, 0, &d_unf);
-        if (rc) return rc;
-        size_t cnt = unf.size();
-        for (u32 level = 0; level < unf[0].n_bands; level++) {
-            while (unf[cnt - 1].n_bands <= level) cnt--;
-            rc = ffhip_items_launch(0, cnt, [&](unsigned grid_x, u32 wg_base) {
-                AlphaUnfArgs a;
-                a.desc = (const AlphaUnfDesc *)d_unf; a.level = level; a.wg_base = wg_base;
-                hipLaunchKernelGGL(k_webp_alpha_unfilter, dim3(grid_x), dim3(ALPHA_BAND), 0, st, a);
-            });
-            if (rc) return rc;
-            t_alpha_last[2]++;
-        }
-    }
-    clock.mark(2, st);
-    const AlphaMergeDesc *d_mer = nullptr;
-    u32 *d_table = nullptr;
-    rc = ffhip_items_upload(SCRATCH_WEBP_ALPHA + 5, stream, mer, total, &d_mer, &d_table);
+    rc = ffhip_banded_launches(SCRATCH_WEBP_ALPHA + 4, stream, unf, &t_alpha_last[2], [&](u32 level, const AlphaUnfDesc *d_unf, unsigned grid_x, u32 wg_base) {
+        AlphaUnfArgs a;
+        a.desc = d_unf; a.level = level; a.wg_base = wg_base;
+        hipLaunchKernelGGL(k_webp_alpha_unfilter, dim3(grid_x), dim3(ALPHA_BAND), 0, st, a);
+    });
     if (rc) return rc;
-    rc = ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
+    clock.mark_from(2, st);
+    rc = ffhip_gather_launch(SCRATCH_WEBP_ALPHA + 5, stream, mer, total, [&](const AlphaMergeDesc *d_mer, const u32 *d_table, unsigned grid_x, u32 wg_base) {
         AlphaMergeArgs a;
         a.desc = d_mer; a.wg_item = d_table; a.wg_base = wg_base;
         hipLaunchKernelGGL(k_webp_alpha_merge, dim3(grid_x), dim3(ALPHA_MERGE_THREADS), 0, st, a);
     });
-    clock.mark(3, st);
+    clock.mark_from(3, st);
     return rc;
 }
 
@@ -333,8 +270,7 @@ int alpha_run_part(const std::vector<AlphaPartFile> &part, const std::vector<Vp8
 int webp_alpha_stage(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, int *status,
                      void *stream)
 {
-    if (n_threads < 1) n_threads = 1;
-    if (n_threads > 64) n_threads = 64;
+    n_threads = ffhip_host_threads(n_threads);
     for (int &v : t_alpha_last) v = 0;
     for (double &t : t_alpha_times) t = 0;
     const auto t_open = std::chrono::steady_clock::now();
@@ -351,11 +287,8 @@ int webp_alpha_stage(const uint8_t *const *files, const size_t *lens, int n, int
         if (heads[(size_t)i].has_alpha) af.push_back({i, heads[(size_t)i]});
     if (af.empty()) return FFHIP_OK;
     const size_t m = af.size();
-    std::vector<ffhip_vp8l_file> pf(m);
-    struct Closer { /* the block images are the files' own heap */
-        std::vector<ffhip_vp8l_file> &v;
-        ~Closer() { for (ffhip_vp8l_file &f : v) ffhip_vp8l_close(&f); }
-    } closer{pf};
+    Vp8lFiles opened(m);
+    std::vector<ffhip_vp8l_file> &pf = opened.v;
     std::vector<int> st_a(m, 0);
     ffhip_parallel_for((int)m, n_threads, [&](int j) {
         const ffhip_webp_alpha_head &h = af[(size_t)j].head;
@@ -365,8 +298,8 @@ int webp_alpha_stage(const uint8_t *const *files, const size_t *lens, int n, int
     t_alpha_times[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_open).count();
     std::vector<uint8_t *> d_pic(m, nullptr);
     std::vector<int64_t> pic_pitch(m, 0);
-    AlphaClock clock;
-    const size_t budget = alpha_part_budget();
+    StageClock clock(FFHIP_ENV("FFHIP_WEBP_ALPHA_TIMES"), t_alpha_times);
+    const size_t budget = ffhip_part_budget(FFHIP_ENV("FFHIP_WEBP_ALPHA_PART_BYTES"));
     int rc = FFHIP_OK;
     for (size_t j = 0; j < m && rc == FFHIP_OK;) {
         std::vector<AlphaPartFile> part;
@@ -390,14 +323,7 @@ int webp_alpha_stage(const uint8_t *const *files, const size_t *lens, int n, int
         if (part.empty()) break;
         vp8l_part_seal(vpart, res);
         t_alpha_last[3]++;
-        rc = alpha_run_part(part, vpart, res + side, raw, work, af, pf, st_a, d_pic, pic_pitch, n_threads, d_bgra, pitch, stream, clock);
-        const hipError_t e = hipStreamSynchronize((hipStream_t)stream); /* the next part, and the next call, refill the staging */
-        if (e != hipSuccess) {
-            ffhip_note_hip_error((int)e, "hipStreamSynchronize");
-            if (rc == FFHIP_OK) rc = FFHIP_EIO;
-        } else {
-            clock.add();
-        }
+        rc = ffhip_part_end(alpha_run_part(part, vpart, res + side, raw, work, af, pf, st_a, d_pic, pic_pitch, n_threads, d_bgra, pitch, stream, clock), stream, clock);
     }
     for (size_t j = 0; j < m; j++) {
         if (st_a[j]) status[af[j].i] = st_a[j] == FFHIP_ENOMEM ? FFHIP_ENOMEM : FFHIP_EINVAL;
@@ -407,16 +333,6 @@ int webp_alpha_stage(const uint8_t *const *files, const size_t *lens, int n, int
     return rc;
 }
 
-extern "C" int ffhip_debug_webp_alpha_last(int out[4])
-{
-    if (!out) return FFHIP_EINVAL;
-    for (int k = 0; k < 4; k++) out[k] = t_alpha_last[k];
-    return FFHIP_OK;
-}
+extern "C" int ffhip_debug_webp_alpha_last(int out[4]) { return ffhip_copy_out(out, t_alpha_last); }
 
-extern "C" int ffhip_debug_webp_alpha_times(double out[4])
-{
-    if (!out) return FFHIP_EINVAL;
-    for (int k = 0; k < 4; k++) out[k] = t_alpha_times[k];
-    return FFHIP_OK;
-}
+extern "C" int ffhip_debug_webp_alpha_times(double out[4]) { return ffhip_copy_out(out, t_alpha_times); }
