@@ -107,7 +107,11 @@ static int planar_args(PlanarArgs &a, const void *y, const void *u, const void *
 {
     if (!y || !bgra || (chroma && (!u || !v)) || rows <= 0 || cols <= 0 || n_images < 0) return FFHIP_EINVAL;
     if (unit < 2 || (unit & 1)) return FFHIP_EINVAL;
-    a.width = cols * unit; a.height = rows * unit;
+    /* the picture's sides in 64 bits before they become the kernels' ints: 4 x width has to fit `pitch`, and a launch has at most 65535
+     * workgroups in y, each of 4 row pairs (4:2:0) or 4 rows (4:0:0) */
+    const long long width = (long long)cols * unit, height = (long long)rows * unit;
+    if (width * 4 > 0x7fffffffLL || height > (chroma ? 8LL : 4LL) * 65535) return FFHIP_EINVAL;
+    a.width = (int)width; a.height = (int)height;
     if ((a.width & 3) || y_stride < a.width || (chroma && uv_stride < a.width / 2)) return FFHIP_EINVAL;
     if (pitch < a.width * 4 || (pitch & 15) || ((uintptr_t)bgra & 15) || (image_stride & 15)) return FFHIP_EINVAL;
     if (n_images > 65535) return FFHIP_EINVAL;

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_grid_compose(GridArgs a)
     const int x = (blockIdx.x * 256 + threadIdx.x) * VEC;
     if (x >= a.out_w) return;
     const int tr = y / a.tile_h, tc = x / a.tile_w; /* tile_h uniform per block row: scalar division */
-    const uint8_t *src = a.tiles + (long long)(tr * a.cols + tc) * a.tile_stride + (long long)(y - tr * a.tile_h) * a.tile_pitch +
+    const uint8_t *src = a.tiles + ((long long)tr * a.cols + tc) * a.tile_stride + (long long)(y - tr * a.tile_h) * a.tile_pitch +
                          (long long)(x - tc * a.tile_w) * 4;
     uint8_t *dst = a.canvas + (long long)y * a.canvas_pitch + (long long)x * 4;
     if (VEC == 4) {

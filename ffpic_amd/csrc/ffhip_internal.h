@@ -187,6 +187,8 @@ int vp8_predict_recon_impl(int mbcols, int mbrows, int n_images, const uint8_t *
                            int64_t plane_stride_uv, void *stream, Vp8SideBySide *sbs);
 int vp8_loopfilter_impl(int mbcols, int mbrows, int n_images, int filter_type, const uint8_t *d_modes, const uint8_t *d_filters, uint8_t *d_y,
                         uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y, int64_t plane_stride_uv, void *stream, const Vp8SideBySide *sbs);
+int vp8_predict_args_check(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
+                           int64_t residual_stride, const uint8_t *d_y, const uint8_t *d_u, const uint8_t *d_v);
 /* shared by the two stages' host entries (ffhip_vp8_pred.hip).  The row forms' switches: FFHIP_VP8_PROGRESS_SHIFT, FFHIP_VP8_SLACK, and where the
  * kernel reports a wait that ran out -- the process-wide pinned word, the side-by-side call's own, or NULL: no row form (`mode` is "levels") */
 struct Vp8RowSwitches { int pshift, slack; int *async_err; };

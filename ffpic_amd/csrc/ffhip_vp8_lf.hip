@@ -545,6 +545,9 @@ int vp8_predict_loopfilter_impl(int mbcols, int mbrows, int n_images, const uint
 {
     if (filter_type < 0 || filter_type > 2) return FFHIP_EINVAL;
     if (filter_type != 0 && !d_filters) return FFHIP_EINVAL;
+    /* the prediction's check here too: what follows enqueues a kernel on d_y before the prediction is called */
+    const int bad = vp8_predict_args_check(mbcols, mbrows, n_images, h_modes, d_modes, d_residual, residual_stride, d_y, d_u, d_v);
+    if (bad) return bad;
     const char *off = FFHIP_ENV("FFHIP_VP8_FUSE"); /* =0: one after the other on `stream` (A/B knob) */
     const bool fuse = filter_type != 0 && n_images > 0 && !(off && off[0] == '0') && ffhip_have_device();
     Vp8SideBySide sbs = {};

@@ -876,17 +876,27 @@ static int pred_levels_enqueue(Vp8PredArgs a, int n_images, const uint8_t *h_mod
     });
 }
 
-/* sbs: next to the loop filter of the same call (ffhip_vp8_predict_loopfilter), which starts behind the counter reset */
-int vp8_predict_recon_impl(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
-                           int64_t residual_stride, const int32_t *d_resmap, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y,
-                           int64_t plane_stride_uv, void *stream, Vp8SideBySide *sbs)
+/* the prediction's argument check, made before the device is asked for and before anything is enqueued (ffhip_vp8_predict_loopfilter makes it
+ * in front of the kernel that saves the last luma column).  n_images 0 passes whatever the pointers are: nothing to do */
+int vp8_predict_args_check(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
+                           int64_t residual_stride, const uint8_t *d_y, const uint8_t *d_u, const uint8_t *d_v)
 {
     if (mbcols <= 0 || mbrows <= 0 || n_images < 0) return FFHIP_EINVAL;
     if (n_images == 0) return FFHIP_OK;
     if (!h_modes || !d_modes || !d_residual || !d_y || !d_u || !d_v) return FFHIP_EINVAL;
     if (((uintptr_t)d_residual & 3) || ((uintptr_t)d_y & 3) || (residual_stride & 1)) return FFHIP_EINVAL;
+    if ((long long)mbcols * mbrows * n_images > 0x3fffffffLL) return FFHIP_EINVAL;
+    return FFHIP_OK;
+}
+
+/* sbs: next to the loop filter of the same call (ffhip_vp8_predict_loopfilter), which starts behind the counter reset */
+int vp8_predict_recon_impl(int mbcols, int mbrows, int n_images, const uint8_t *h_modes, const uint8_t *d_modes, const int16_t *d_residual,
+                           int64_t residual_stride, const int32_t *d_resmap, uint8_t *d_y, uint8_t *d_u, uint8_t *d_v, int64_t plane_stride_y,
+                           int64_t plane_stride_uv, void *stream, Vp8SideBySide *sbs)
+{
+    const int bad = vp8_predict_args_check(mbcols, mbrows, n_images, h_modes, d_modes, d_residual, residual_stride, d_y, d_u, d_v);
+    if (bad || n_images == 0) return bad;
     const long long n_mb = (long long)mbcols * mbrows;
-    if (n_mb * n_images > 0x3fffffffLL) return FFHIP_EINVAL;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     { /* (the self-healing record of a side-by-side call is good while that call is the stream's last: ffhip_vp8_lf.hip) */
         std::lock_guard<std::mutex> l(g_ffhip_state_mu);

@@ -266,7 +266,11 @@ const char *ffhip_jpeg_kernel_name(const ffhip_jpeg_geom *geom);
  *   ffhip_yuv420_to_bgra     == YUV420_to_BGRA32        (utils/colorspace.c:291-329; format/webp.c:1868)
  *   ffhip_yuv420_to_bgra_16  == YUV420_to_BGRA32_16bit  (utils/colorspace.c:628-669; coding/hevc.c:7260-7270)
  *   ffhip_yuv400_to_bgra_16  == YUV400_to_BGRA32_16bit  (utils/colorspace.c:715-742; coding/hevc.c:7271-7277)
- * Image i reads planes at +i*plane_stride_* and writes at d_bgra + i*image_stride.  Only enqueue; planes and d_bgra are stream-ordered. */
+ * Image i reads planes at +i*plane_stride_* and writes at d_bgra + i*image_stride.  Only enqueue; planes and d_bgra are stream-ordered.
+ * Limits (FFHIP_EINVAL beyond them, checked before the device is): the block size even and >= 2; width = cols x block a multiple of 4
+ * with 4 x width <= 2^31 - 1 (it has to fit `pitch`); height = rows x block <= 524280 (4:2:0) or 262140 (4:0:0), the 65535 workgroups a
+ * launch has in y; y_stride >= width, uv_stride >= width / 2; pitch >= 4 x width; d_bgra, pitch and image_stride multiples of 16;
+ * n_images <= 65535.  Plane strides are free: 0 converts one set of planes n_images times. */
 int ffhip_yuv420_to_bgra(uint8_t *d_bgra, int pitch, const uint8_t *d_y, const uint8_t *d_u,
                          const uint8_t *d_v, int y_stride, int uv_stride, int mbrows, int mbcols,
                          int n_images, int64_t plane_stride_y, int64_t plane_stride_uv,

@@ -206,3 +206,157 @@ def float_key_holds(key, what):
     if what == "-zero":
         return bool(np.any((body == 0) & (sign == 1)))
     raise ValueError(what)
+
+
+# ---------------------------------------------------------------------------------------------------- the batch entry points' layouts
+# What test_batch_limits_gpu.py runs and test_batch_limits.py asks the argument checks about: a layout is the strides, offsets and sizes
+# of one call; `place` lays its operands out (in an arena or at made-up addresses) and `call` passes them to the library
+class Planar:
+    """one call of ffhip_yuv420_to_bgra (bits 8), ffhip_yuv420_to_bgra_16 (bits 16) or ffhip_yuv400_to_bgra_16 (bits 16, chroma False).
+    Strides in samples, offsets in bytes added to the 256-aligned start of a region; None is the tightest value, pitch and image_stride
+    None are 4 W + 16 and H pitch + 48"""
+
+    def __init__(self, bits, rows, cols, unit, n, chroma=True, y_off=0, u_off=0, v_off=0, y_stride=None, uv_stride=None, plane_y=None,
+                 plane_uv=None, pitch=None, image_stride=None):
+        self.bits, self.es, self.chroma, self.rows, self.cols, self.unit, self.n = bits, bits // 8, chroma, rows, cols, unit, n
+        self.W, self.H = cols * unit, rows * unit
+        self.y_off, self.u_off, self.v_off = y_off, u_off, v_off
+        self.y_stride = self.W if y_stride is None else y_stride
+        self.uv_stride = self.W // 2 if uv_stride is None else uv_stride
+        self.plane_y = self.H * self.y_stride if plane_y is None else plane_y
+        self.plane_uv = self.H // 2 * self.uv_stride if plane_uv is None else plane_uv
+        self.pitch = 4 * self.W + 16 if pitch is None else pitch
+        self.image_stride = self.H * self.pitch + 48 if image_stride is None else image_stride
+
+    def spans(self):
+        """bytes of the regions y, u, v, bgra"""
+        n1, es = self.n - 1, self.es
+        y = self.y_off + (n1 * self.plane_y + (self.H - 1) * self.y_stride + self.W) * es
+        c = (n1 * self.plane_uv + (self.H // 2 - 1) * self.uv_stride + self.W // 2) * es
+        return y, self.u_off + c, self.v_off + c, n1 * self.image_stride + (self.H - 1) * self.pitch + 4 * self.W
+
+    def place(self, add):
+        """add(nbytes) -> offset of a region; -> offsets of y, u, v, bgra (u and v None without chroma)"""
+        y, u, v, o = self.spans()
+        return (add(y) + self.y_off, add(u) + self.u_off if self.chroma else None, add(v) + self.v_off if self.chroma else None, add(o))
+
+    def call(self, L, base, at):
+        y, u, v, o = [None if a is None else base + a for a in at]
+        if self.bits == 8:
+            return L.ffhip_yuv420_to_bgra(o, self.pitch, y, u, v, self.y_stride, self.uv_stride, self.rows, self.cols, self.n, self.plane_y,
+                                          self.plane_uv, self.image_stride, None)
+        if self.chroma:
+            return L.ffhip_yuv420_to_bgra_16(o, self.pitch, y, u, v, self.y_stride, self.uv_stride, self.rows, self.cols, self.unit, self.n,
+                                             self.plane_y, self.plane_uv, self.image_stride, None)
+        return L.ffhip_yuv400_to_bgra_16(o, self.pitch, y, self.y_stride, self.rows, self.cols, self.unit, self.n, self.plane_y,
+                                         self.image_stride, None)
+
+    def packed(self):
+        """the 8-bit call's alignment predicate, restated: does it take the packed kernel"""
+        return not (self.y_off & 3 or self.y_stride & 3 or self.plane_y & 3 or self.u_off & 1 or self.v_off & 1 or self.uv_stride & 1
+                    or self.plane_uv & 1)
+
+
+def planar_product(y_off, y_stride_extra):
+    """A1's product for one d_y offset and one y_stride: the other settings, at 3 x 2 macroblocks and three images"""
+    W, H = 48, 32
+    out = []
+    for u_off in (0, 1):
+        for v_off in (0, 1):
+            for uv_extra in (0, 1):
+                for odd in (1, 0):                           # plane strides larger than a plane, odd or even
+                    ys, uvs = W + y_stride_extra, W // 2 + uv_extra
+                    out.append(Planar(8, 2, 3, 16, 3, y_off=y_off, u_off=u_off, v_off=v_off, y_stride=ys, uv_stride=uvs,
+                                      plane_y=H * ys + (5 if odd else 8), plane_uv=H // 2 * uvs + (3 if odd else 6)))
+    return out
+
+
+PLANAR_Y_OFFS, PLANAR_Y_EXTRAS = (0, 1, 2), (0, 1, 2, 4)
+# ctbsize, rows, cols: height / 2 % 4 != 0, height % 4 != 0 and width / 4 % 64 != 0, two workgroups in x and three or more in y
+PLANAR_CTBS = [(2, 11, 134), (6, 3, 46), (10, 3, 26)]
+PLANAR_DOMAINS = [(0, 256), (0, 1024), (0, 8192), (-32768, 32768)]          # test_hevc_planes_domains_and_ctb_sizes'
+
+
+def planar_16(chroma, ctb, rows, cols, **kw):
+    W = cols * ctb
+    return Planar(16, rows, cols, ctb, 2, chroma=chroma, y_stride=W + 3, uv_stride=W // 2 + 1, **kw)
+
+
+def planar_far(bits, chroma, y_off=0):
+    """B1: two pictures of 3 x 2 macroblocks (or CTBs of 16), the second one's planes past 2^31 bytes, its pixels past 2^32"""
+    far = (1 << 31) + 4 if bits == 8 else (1 << 30) + 2
+    return Planar(bits, 2, 3, 16, 2, chroma=chroma, y_off=y_off, y_stride=52, uv_stride=26, plane_y=far, plane_uv=far - 2,
+                  image_stride=(1 << 32) + 16)
+
+
+class Grid:
+    """one call of ffhip_heif_grid_compose; offsets in bytes added to the 256-aligned start of a region"""
+
+    def __init__(self, rows, cols, tw, th, ow, oh, canvas_pitch=None, tile_pitch=None, tile_stride=None, canvas_off=0, tiles_off=0):
+        self.rows, self.cols, self.tw, self.th, self.ow, self.oh = rows, cols, tw, th, ow, oh
+        self.canvas_pitch = 4 * ow if canvas_pitch is None else canvas_pitch
+        self.tile_pitch = 4 * tw if tile_pitch is None else tile_pitch
+        self.tile_stride = self.tile_pitch * th if tile_stride is None else tile_stride
+        self.canvas_off, self.tiles_off = canvas_off, tiles_off
+
+    def spans(self):
+        tiles = (self.rows * self.cols - 1) * self.tile_stride + (self.th - 1) * self.tile_pitch + 4 * self.tw
+        return self.tiles_off + tiles, self.canvas_off + (self.oh - 1) * self.canvas_pitch + 4 * self.ow
+
+    def place(self, add):
+        t, c = self.spans()
+        return add(t) + self.tiles_off, add(c) + self.canvas_off
+
+    def call(self, L, base, at):
+        return L.ffhip_heif_grid_compose(base + at[1], self.canvas_pitch, self.ow, self.oh, base + at[0], self.tile_pitch, self.tile_stride,
+                                         self.tw, self.th, self.rows, self.cols, None)
+
+    def vector(self):
+        """the entry's choice, restated: the four-pixel kernel"""
+        return not (self.tw & 3 or (self.canvas_off | self.tiles_off | self.canvas_pitch | self.tile_pitch | self.tile_stride) & 15)
+
+
+def up16(v):
+    return (v + 15) // 16 * 16
+
+
+# the vector tail: tiles of 64 x 8, three across and two down, the last row and the last column overhanging
+GRID_TAIL = {ow: Grid(2, 3, 64, 8, ow, 13, canvas_pitch=up16(4 * ow) + 16) for ow in (177, 178, 179)}
+# the per-pixel kernel by each alignment input in turn, on the layout of the tail case
+_G = dict(rows=2, cols=3, tw=64, th=8, ow=178, oh=13)
+GRID_UNALIGNED = {"canvas": Grid(**_G, canvas_pitch=736, canvas_off=4), "tiles": Grid(**_G, canvas_pitch=736, tiles_off=4),
+                  "canvas_pitch": Grid(**_G, canvas_pitch=740), "tile_pitch": Grid(**_G, canvas_pitch=736, tile_pitch=260),
+                  "tile_stride": Grid(**_G, canvas_pitch=736, tile_stride=256 * 8 + 4)}
+# the stride gaps, tiles of a width the vector kernel could take and of one it could not
+GRID_GAPS = {tw: Grid(3, 2, tw, 18, 2 * tw - 13, 40, canvas_pitch=4 * (2 * tw - 13) + 20, tile_pitch=4 * tw + 32,
+                      tile_stride=(4 * tw + 32) * 18 + 64) for tw in (64, 30)}
+# B1: the third tile past 2^32, the third canvas row past 2^32
+GRID_FAR = {"tile_stride": Grid(1, 3, 64, 8, 178, 5, canvas_pitch=736, tile_stride=(1 << 31) + 16),
+            "canvas_pitch": Grid(1, 3, 64, 8, 178, 3, canvas_pitch=(1 << 31) + 16)}
+
+
+class Fake:
+    """made-up addresses for a layout's regions, 256-aligned like an arena's: what the argument checks see without a device"""
+
+    def __init__(self):
+        self.lay = Layout()
+        self.base = 1 << 40
+
+    def add(self, nbytes):
+        return self.lay.add(nbytes)
+
+
+# the two-pass geometries of ffhip_jpeg_recon_batch, one of each kind: grey with 2 x 2 blocks per MCU, a three-block pair
+JPEG_TWO_PASS = {"grey2x2": (1, 2, 2), "h3": (3, 3, 1)}
+
+
+def jpeg_batch_sizes(name):
+    """(mcu_cols, mcu_rows): 5 x 3, and one whole unit and three MCUs of the next in a row"""
+    return [(5, 3), (JPEG_CLASSES[name][3] + 3 if name in JPEG_CLASSES else 9, 2)]
+
+
+# B2: counts whose byte offsets pass 2^31 and 2^32.  The smallest n_mb whose levels (800 bytes a macroblock) pass 2^31 bytes, plus 9;
+# (nTbS, n_tu) of the HEVC residual stage: 2^31 bytes of levels and a few units more
+VP8_RESIDUAL_FAR = -(-(1 << 31) // 800) + 9
+HEVC_RESIDUAL_FAR = [(32, (1 << 20) + 8), (4, (1 << 26) + 300)]
+FAR_ENDS = 64                                     # units at either end that come from the host; zeros in between
