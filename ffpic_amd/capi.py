@@ -46,6 +46,8 @@ EXPORTS = [
     "ffhip_debug_vp8l_last", "ffhip_debug_vp8l_times",
     "ffhip_webp_alpha_probe", "ffhip_webp_alpha_plane", "ffhip_debug_webp_alpha_last", "ffhip_debug_webp_alpha_times",
     "ffhip_debug_scratch_fill",
+    "ffhip_bgra_to_tensor_items_alpha", "ffhip_bgra_resize_items_premultiplied",
+    "ffhip_png_decode_files_tensor_alpha", "ffhip_vp8l_decode_files_tensor_alpha", "ffhip_webp_decode_files_tensor_alpha",
 ]
 
 
@@ -162,6 +164,15 @@ FFHIP_TENSOR_U8, FFHIP_TENSOR_F16, FFHIP_TENSOR_F32 = 0, 1, 2
 class TensorFormat(C.Structure):
     """ffhip_tensor_format"""
     _fields_ = [("dtype", C.c_int32), ("bgr", C.c_int32), ("planar", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+FFHIP_ALPHA_DROP, FFHIP_ALPHA_STRAIGHT, FFHIP_ALPHA_PREMULTIPLIED, FFHIP_ALPHA_OVER = 0, 1, 2, 3
+
+
+class TensorAlpha(C.Structure):
+    """ffhip_tensor_alpha: what the sink and the chain make of the alpha byte (background: B,G,R,unused)"""
+    _fields_ = [("mode", C.c_int32), ("source_premultiplied", C.c_int32), ("background", C.c_uint8 * 4), ("alpha_scale", C.c_float),
+                ("alpha_bias", C.c_float)]
 
 
 class TensorItem(C.Structure):
@@ -409,6 +420,12 @@ def lib():
     L.ffhip_webp_alpha_plane.argtypes = [vp, sz, vp, i64]
     L.ffhip_debug_webp_alpha_last.argtypes = [C.POINTER(ci)]
     L.ffhip_debug_webp_alpha_times.argtypes = [C.POINTER(C.c_double)]
+    L.ffhip_bgra_to_tensor_items_alpha.argtypes = [C.POINTER(TensorItem), ci, C.POINTER(TensorFormat), C.POINTER(TensorAlpha), vp]
+    L.ffhip_bgra_resize_items_premultiplied.argtypes = [C.POINTER(ResizeItem), ci, ci, vp]
+    for name, info in (("png", PngInfo), ("vp8l", Vp8lInfo), ("webp", WebpInfo)):
+        getattr(L, f"ffhip_{name}_decode_files_tensor_alpha").argtypes = [
+            vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect), C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci),
+            C.c_uint, C.POINTER(TensorAlpha), C.POINTER(info), vp, vp]
     L.ffhip_debug_scratch_fill.argtypes = [vp, ci, C.POINTER(C.c_uint64), C.POINTER(ci), ci]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long

@@ -11,6 +11,7 @@
  * No intermediate picture goes to memory; a source row is read once per output row whose run holds it (about twice when shrinking).
  */
 #include "ffhip_items.h"
+#include "ffhip_alpha_body.h"
 #include "ffhip_resize_body.h"
 
 #include <string.h>
@@ -46,7 +47,9 @@ __global__ __launch_bounds__(256) void k_resize_tables(const ResizeItemDesc *des
         for (u32 k = threadIdx.x; k < d.n_wgs; k += 256) wg_item[d.first_wg + k] = item;
 }
 
-__global__ __launch_bounds__(FFHIP_RESIZE_WG_THREADS) void k_bgra_resize(ResizeArgs a)
+/* PREMUL: every pixel is premultiplied as it is staged (once per staged pixel, not per tap): the filter runs over premultiplied bytes and
+ * the output is premultiplied BGRA (ffhip_bgra_resize_items_premultiplied) */
+template <bool PREMUL> __device__ __forceinline__ void bgra_resize_wg(ResizeArgs a)
 {
     __shared__ u32 row[FFHIP_RESIZE_LDS_PIXELS];
     const u32 wg = a.wg_base + blockIdx.x;
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(FFHIP_RESIZE_WG_THREADS) void k_bgra_resize(ResizeA
         u32 h0 = 0, h1 = 0, h2 = 0, h3 = 0;
         for (u32 c0 = seg0; c0 < seg1; c0 += FFHIP_RESIZE_LDS_PIXELS) {
             const u32 len = seg1 - c0 < FFHIP_RESIZE_LDS_PIXELS ? seg1 - c0 : FFHIP_RESIZE_LDS_PIXELS;
-            for (u32 i = threadIdx.x; i < len; i += FFHIP_RESIZE_WG_THREADS) row[i] = src[c0 + i];
+            for (u32 i = threadIdx.x; i < len; i += FFHIP_RESIZE_WG_THREADS) row[i] = resize_staged<PREMUL>(src[c0 + i]);
             __syncthreads();
             /* the lane's taps that lie in this chunk: pixels max(fx, c0) .. min(fx + cx, c0 + len) - 1 */
             const u32 j_lo = c0 > fx ? c0 - fx : 0u;
@@ -93,6 +96,16 @@ __global__ __launch_bounds__(FFHIP_RESIZE_WG_THREADS) void k_bgra_resize(ResizeA
         const u32 px = ((acc0 + (1u << 23)) >> 24) | ((acc1 + (1u << 23)) >> 24) << 8 | ((acc2 + (1u << 23)) >> 24) << 16 | ((acc3 + (1u << 23)) >> 24) << 24;
         *(RESIZE_GLOBAL u32 *)(d.dst + (long long)oy * d.dst_pitch + 4ll * ox) = px;
     }
+}
+
+__global__ __launch_bounds__(FFHIP_RESIZE_WG_THREADS) void k_bgra_resize(ResizeArgs a)
+{
+    bgra_resize_wg<false>(a);
+}
+
+__global__ __launch_bounds__(FFHIP_RESIZE_WG_THREADS) void k_bgra_resize_premultiplied(ResizeArgs a)
+{
+    bgra_resize_wg<true>(a);
 }
 
 bool side_ok(long long v) { return v >= 1 && v <= FFHIP_RESIZE_MAX_SIDE; }
@@ -130,7 +143,9 @@ extern "C" int ffhip_resize_axis_taps(int n_in, int n_out, int filter, int o, in
     return (int)t.count;
 }
 
-extern "C" int ffhip_bgra_resize_items(const ffhip_resize_item *items, int n, int filter, void *stream)
+namespace {
+
+int resize_items(const ffhip_resize_item *items, int n, int filter, bool premultiply, void *stream)
 {
     if (n < 0 || n > 0x3fffffff || (n > 0 && !items) || (filter != FFHIP_RESIZE_BILINEAR && filter != FFHIP_RESIZE_ANTIALIAS)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
@@ -166,6 +181,18 @@ extern "C" int ffhip_bgra_resize_items(const ffhip_resize_item *items, int n, in
     return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
         ResizeArgs a;
         a.desc = d_desc; a.tables = dev; a.wg_item = d_table; a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_bgra_resize, dim3(grid_x), dim3(FFHIP_RESIZE_WG_THREADS), 0, st, a);
+        hipLaunchKernelGGL(premultiply ? k_bgra_resize_premultiplied : k_bgra_resize, dim3(grid_x), dim3(FFHIP_RESIZE_WG_THREADS), 0, st, a);
     });
+}
+
+} // namespace
+
+extern "C" int ffhip_bgra_resize_items(const ffhip_resize_item *items, int n, int filter, void *stream)
+{
+    return resize_items(items, n, filter, false, stream);
+}
+
+extern "C" int ffhip_bgra_resize_items_premultiplied(const ffhip_resize_item *items, int n, int filter, void *stream)
+{
+    return resize_items(items, n, filter, true, stream);
 }

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "ffpic_hip.h"
+#include "ffhip_alpha_body.h"
 
 #ifndef __HIPCC__
 #define __host__
@@ -92,6 +93,9 @@ template <class Store> __host__ __device__ inline void resize_axis_weights(const
         owed -= take;
     }
 }
+
+/* A source pixel as the resize kernel stages it into its row: as it is, or premultiplied (ffhip_bgra_resize_items_premultiplied) */
+template <bool PREMUL> __host__ __device__ inline uint32_t resize_staged(uint32_t px) { return PREMUL ? alpha_premultiply_pixel(px) : px; }
 
 /* One item of a call, as the kernels read it.  The tap tables of an axis: fc[o] = first | count << 16 (first <= 16383, count <= 16384), and the
  * weights TAP-MAJOR, q[j * n_out + o] for tap j of output o, so that the lanes of a

@@ -1,7 +1,8 @@
 /*
  * ffhip_tensor.hip -- the last stage between the decoders and a program that reads tensors: BGRA pictures as the decode calls leave
  * them -> RGB / BGR, CHW / HWC, uint8 / float16 / float32, cropped to a rectangle, in one launch for a whole mixed batch
- * (ffhip_bgra_to_tensor_items), and the file calls built on it (ffhip_jpeg_decode_files_tensor, ffhip_webp_decode_files_tensor, ffhip_png_decode_files_tensor, ffhip_vp8l_decode_files_tensor, and
+ * (ffhip_bgra_to_tensor_items), and the file calls built on it (ffhip_jpeg_decode_files_tensor, ffhip_webp_decode_files_tensor, ffhip_png_decode_files_tensor, ffhip_vp8l_decode_files_tensor, their
+ * _alpha forms that carry the alpha byte through the chain, and
  * their _resized forms with ffhip_bgra_resize_items between the decoder and this stage, their _oriented forms with
  * ffhip_bgra_orient_items in front of this stage).
  * The layout of the work is described in ffhip_tensor_body.h.
@@ -55,6 +56,72 @@ TensorKernel tensor_kernel(const ffhip_tensor_format *f)
                                         : tensor_kernel_of<FFHIP_TENSOR_F32>(planar, bgr);
 }
 
+/* The forms with alpha: the same deal of units, NC channels under policy AP.  A kernel of their own, so that the twelve
+ * instances above keep their argument block and their instructions */
+struct TensorAlphaArgs {
+    const TensorItemDesc *desc;
+    const u32 *wg_item;
+    u32 wg_base;
+    TensorScale s;
+    TensorAlpha al;
+};
+template <int DT, bool PLANAR, bool BGR, int NC, int AP> __global__ __launch_bounds__(FFHIP_TENSOR_WG_THREADS) void k_bgra_to_tensor_alpha(TensorAlphaArgs a)
+{
+    const u32 wg = a.wg_base + blockIdx.x;
+    const u32 item = __builtin_amdgcn_readfirstlane(a.wg_item[wg]);
+    const TensorItemDesc d = a.desc[item];
+    const u32 base = (wg - d.first_wg) * FFHIP_TENSOR_WG_UNITS + threadIdx.x;
+#pragma unroll 2
+    for (int i = 0; i < FFHIP_TENSOR_UNITS_PER_LANE; i++) {
+        const u32 t = base + (u32)i * FFHIP_TENSOR_WG_THREADS;
+        if (t >= d.total) break;
+        tensor_unit<DT, PLANAR, BGR, NC, AP>(d, a.s, t, a.al);
+    }
+}
+
+typedef void (*TensorAlphaKernel)(TensorAlphaArgs);
+template <int DT, bool PLANAR, bool BGR> TensorAlphaKernel tensor_alpha_kernel_as(int policy)
+{
+    switch (policy) {
+    case TENSOR_ALPHA_KEEP: return k_bgra_to_tensor_alpha<DT, PLANAR, BGR, 4, TENSOR_ALPHA_KEEP>;
+    case TENSOR_ALPHA_PREMUL: return k_bgra_to_tensor_alpha<DT, PLANAR, BGR, 4, TENSOR_ALPHA_PREMUL>;
+    case TENSOR_ALPHA_UNPREMUL: return k_bgra_to_tensor_alpha<DT, PLANAR, BGR, 4, TENSOR_ALPHA_UNPREMUL>;
+    case TENSOR_ALPHA_OVER_S: return k_bgra_to_tensor_alpha<DT, PLANAR, BGR, 3, TENSOR_ALPHA_OVER_S>;
+    default: return k_bgra_to_tensor_alpha<DT, PLANAR, BGR, 3, TENSOR_ALPHA_OVER_P>;
+    }
+}
+template <int DT> TensorAlphaKernel tensor_alpha_kernel_of(bool planar, bool bgr, int policy)
+{
+    return planar ? (bgr ? tensor_alpha_kernel_as<DT, true, true>(policy) : tensor_alpha_kernel_as<DT, true, false>(policy))
+                  : (bgr ? tensor_alpha_kernel_as<DT, false, true>(policy) : tensor_alpha_kernel_as<DT, false, false>(policy));
+}
+TensorAlphaKernel tensor_alpha_kernel(const ffhip_tensor_format *f, int policy)
+{
+    const bool planar = f->planar != 0, bgr = f->bgr != 0;
+    return f->dtype == FFHIP_TENSOR_U8 ? tensor_alpha_kernel_of<FFHIP_TENSOR_U8>(planar, bgr, policy)
+         : f->dtype == FFHIP_TENSOR_F16 ? tensor_alpha_kernel_of<FFHIP_TENSOR_F16>(planar, bgr, policy)
+                                        : tensor_alpha_kernel_of<FFHIP_TENSOR_F32>(planar, bgr, policy);
+}
+
+/* a record with a mode other than DROP: does anything of it take part */
+bool tensor_alpha_on(const ffhip_tensor_alpha *a) { return a && a->mode != FFHIP_ALPHA_DROP; }
+int tensor_channels(const ffhip_tensor_alpha *a) { return tensor_alpha_on(a) && a->mode != FFHIP_ALPHA_OVER ? 4 : 3; }
+/* the policy a mode comes to with a straight or a premultiplied source */
+int tensor_alpha_policy(const ffhip_tensor_alpha *a)
+{
+    const bool pre = a->source_premultiplied != 0;
+    if (a->mode == FFHIP_ALPHA_STRAIGHT) return pre ? TENSOR_ALPHA_UNPREMUL : TENSOR_ALPHA_KEEP;
+    if (a->mode == FFHIP_ALPHA_PREMULTIPLIED) return pre ? TENSOR_ALPHA_KEEP : TENSOR_ALPHA_PREMUL;
+    return pre ? TENSOR_ALPHA_OVER_P : TENSOR_ALPHA_OVER_S;
+}
+bool tensor_alpha_ok(const ffhip_tensor_alpha *a, const ffhip_tensor_format *f)
+{
+    if (!tensor_alpha_on(a)) return true; /* the rest of the record is not read */
+    if (a->mode < FFHIP_ALPHA_DROP || a->mode > FFHIP_ALPHA_OVER || (a->source_premultiplied != 0 && a->source_premultiplied != 1)) return false;
+    if (!isfinite(a->alpha_scale) || !isfinite(a->alpha_bias)) return false;
+    return !(f->dtype == FFHIP_TENSOR_U8 && (a->alpha_scale != 1.0f || a->alpha_bias != 0.0f));
+}
+
 int tensor_elem_size(int dtype) { return dtype == FFHIP_TENSOR_U8 ? 1 : (dtype == FFHIP_TENSOR_F16 ? 2 : 4); }
 
 bool tensor_format_ok(const ffhip_tensor_format *f)
@@ -69,7 +136,7 @@ bool tensor_format_ok(const ffhip_tensor_format *f)
 
 /* an item the call takes under format f, its picture's address aside (the file calls plan their items before their pictures have one);
  * fills its record (src and first_wg aside) */
-bool tensor_item_layout(const ffhip_tensor_item &it, const ffhip_tensor_format *f, TensorItemDesc *out)
+bool tensor_item_layout(const ffhip_tensor_item &it, const ffhip_tensor_format *f, int nc, TensorItemDesc *out)
 {
     const int es = tensor_elem_size(f->dtype);
     if (it.width < 1 || it.height < 1 || it.x0 < 0 || it.y0 < 0) return false;
@@ -77,15 +144,15 @@ bool tensor_item_layout(const ffhip_tensor_item &it, const ffhip_tensor_format *
     /* source offsets stay within 31 bits, as the decode calls' own pictures do (pitch x rows < 2^31), and the rectangle within the pitch */
     if (4LL * ((long long)it.x0 + it.width) > it.pitch || ((long long)it.y0 + it.height) * it.pitch > 0x7fffffffLL) return false;
     if (!it.d_out || ((uintptr_t)it.d_out & (uintptr_t)(es - 1))) return false;
-    const long long run_len = f->planar ? it.width : 3LL * it.width;
+    const long long run_len = f->planar ? it.width : (long long)nc * it.width;
     if (it.row_stride < run_len) return false;
     __int128 span = (__int128)it.row_stride * (it.height - 1) + run_len; /* elements from the first to behind the last of a plane (HWC: of the tensor) */
     if (f->planar) {
         if ((__int128)it.plane_stride < span) return false;
-        span += (__int128)it.plane_stride * 2;
+        span += (__int128)it.plane_stride * (nc - 1);
     }
     if (span * es > ((__int128)1 << 62)) return false; /* element offsets are 64-bit in the kernel */
-    const long long runs = (f->planar ? 3LL : 1LL) * it.height;
+    const long long runs = (f->planar ? (long long)nc : 1LL) * it.height;
     const long long units = (run_len * es + 15) / 16 + 1;
     if (runs * units > 0xffffffffLL) return false; /* a unit's index is 32-bit */
     memset(out, 0, sizeof(*out));
@@ -102,24 +169,24 @@ bool tensor_item_layout(const ffhip_tensor_item &it, const ffhip_tensor_format *
 }
 
 /* an item the call takes under format f; fills its record (first_wg aside) */
-bool tensor_item_desc(const ffhip_tensor_item &it, const ffhip_tensor_format *f, TensorItemDesc *out)
+bool tensor_item_desc(const ffhip_tensor_item &it, const ffhip_tensor_format *f, int nc, TensorItemDesc *out)
 {
-    if (!it.d_bgra || ((uintptr_t)it.d_bgra & 3) || !tensor_item_layout(it, f, out)) return false;
+    if (!it.d_bgra || ((uintptr_t)it.d_bgra & 3) || !tensor_item_layout(it, f, nc, out)) return false;
     out->src = it.d_bgra + (long long)it.y0 * it.pitch + 4LL * it.x0;
     return true;
 }
 
-} // namespace
-
-extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, void *stream)
+/* both items calls: alpha NULL or of mode DROP is the three-channel call */
+int tensor_items(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, const ffhip_tensor_alpha *alpha, void *stream)
 {
-    if (n < 0 || (n > 0 && !items) || !tensor_format_ok(fmt)) return FFHIP_EINVAL;
+    if (n < 0 || (n > 0 && !items) || !tensor_format_ok(fmt) || !tensor_alpha_ok(alpha, fmt)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
+    const int nc = tensor_channels(alpha);
     /* the records, every item's workgroups behind those of the items before it */
     std::vector<TensorItemDesc> desc((size_t)n);
     unsigned long long total = 0;
     for (int i = 0; i < n; i++) {
-        if (!tensor_item_desc(items[i], fmt, &desc[(size_t)i])) return FFHIP_EINVAL;
+        if (!tensor_item_desc(items[i], fmt, nc, &desc[(size_t)i])) return FFHIP_EINVAL;
         desc[(size_t)i].first_wg = (u32)total;
         total += desc[(size_t)i].n_wgs;
     }
@@ -131,6 +198,17 @@ extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n,
     u32 *d_table = nullptr;
     const int rc = ffhip_items_upload(SCRATCH_TENSOR_ITEMS, stream, desc, total, &d_desc, &d_table);
     if (rc) return rc;
+    if (tensor_alpha_on(alpha)) {
+        const TensorAlphaKernel kernel = tensor_alpha_kernel(fmt, tensor_alpha_policy(alpha));
+        return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
+            TensorAlphaArgs a;
+            a.desc = d_desc; a.wg_item = d_table; a.wg_base = wg_base;
+            for (int c = 0; c < 3; c++) { a.s.scale[c] = fmt->scale[c]; a.s.bias[c] = fmt->bias[c]; }
+            a.al.background = (u32)alpha->background[0] | (u32)alpha->background[1] << 8 | (u32)alpha->background[2] << 16;
+            a.al.alpha_scale = alpha->alpha_scale; a.al.alpha_bias = alpha->alpha_bias;
+            hipLaunchKernelGGL(kernel, dim3(grid_x), dim3(FFHIP_TENSOR_WG_THREADS), 0, st, a);
+        });
+    }
     const TensorKernel kernel = tensor_kernel(fmt);
     return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
         TensorArgs a;
@@ -138,6 +216,19 @@ extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n,
         for (int c = 0; c < 3; c++) { a.s.scale[c] = fmt->scale[c]; a.s.bias[c] = fmt->bias[c]; }
         hipLaunchKernelGGL(kernel, dim3(grid_x), dim3(FFHIP_TENSOR_WG_THREADS), 0, st, a);
     });
+}
+
+} // namespace
+
+extern "C" int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, void *stream)
+{
+    return tensor_items(items, n, fmt, nullptr, stream);
+}
+
+extern "C" int ffhip_bgra_to_tensor_items_alpha(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, const ffhip_tensor_alpha *alpha,
+                                                void *stream)
+{
+    return tensor_items(items, n, fmt, alpha, stream);
 }
 
 /* ---- files in, tensors out ---- */
@@ -161,6 +252,7 @@ struct TensorOptions {
     TensorOptions &scale(const int *d, int *d_out) { denom = d; denom_out = d_out; return *this; }
     TensorOptions &turn(const int *o, int *o_out) { oriented = true; orient = o; orient_out = o_out; return *this; }
     TensorOptions &with(unsigned f) { flags = f; return *this; }
+    TensorOptions &keep(const ffhip_tensor_alpha *a) { alpha = a; return *this; }
     const ffhip_rect *roi;
     const ffhip_size *out_size = nullptr;
     int filter = FFHIP_RESIZE_BILINEAR;
@@ -168,6 +260,8 @@ struct TensorOptions {
     int *denom_out = nullptr, *orient_out = nullptr;
     bool oriented = false;
     unsigned flags = 0u;
+    const ffhip_tensor_alpha *alpha = nullptr; /* NULL or mode DROP: three channels, the alpha byte ignored.  Otherwise the resize is the
+                                                * premultiplying one and the sink is told so */
 };
 
 /* One file of a call, planned once (tensor_file_plan) and only read afterwards */
@@ -251,7 +345,7 @@ TensorFile tensor_file_plan(const TensorProbe &p, int o, int i, const TensorOpti
         if (o != 1) ok = ((long long)t.y0 + t.height) * t.src_pitch <= 0x7fffffffLL;
         f.sink = ffhip_tensor_item{nullptr, v.pitch, v.x0, v.y0, v.width, v.height, outs[i].d_out, outs[i].row_stride, outs[i].plane_stride};
         TensorItemDesc d;
-        ok = ok && tensor_item_layout(f.sink, fmt, &d);
+        ok = ok && tensor_item_layout(f.sink, fmt, tensor_channels(opts.alpha), &d);
         f.resized_bytes = to.width ? tensor_place((size_t)4 * to.width * to.height) : 0;
         f.upright_bytes = o != 1 ? tensor_place((size_t)4 * v.width * v.height) : 0;
     }
@@ -329,8 +423,10 @@ int tensor_part_enqueue(const std::vector<TensorFile> &plan, const TensorPart &p
         if (f.upright_bytes) { turn.push_back(t); upright += f.upright_bytes; }
         good.push_back(sink);
     }
+    const bool with_alpha = tensor_alpha_on(opts.alpha);
     if (opts.out_size) {
-        const int rc = ffhip_bgra_resize_items(shrink.data(), (int)shrink.size(), opts.filter, stream);
+        const int rc = with_alpha ? ffhip_bgra_resize_items_premultiplied(shrink.data(), (int)shrink.size(), opts.filter, stream)
+                                  : ffhip_bgra_resize_items(shrink.data(), (int)shrink.size(), opts.filter, stream);
         if (rc) return rc;
     }
     if (!turn.empty()) {
@@ -338,7 +434,10 @@ int tensor_part_enqueue(const std::vector<TensorFile> &plan, const TensorPart &p
         if (rc) return rc;
         g_orient_last_items += (int)turn.size();
     }
-    return ffhip_bgra_to_tensor_items(good.data(), (int)good.size(), fmt, stream);
+    if (!with_alpha) return ffhip_bgra_to_tensor_items(good.data(), (int)good.size(), fmt, stream);
+    ffhip_tensor_alpha sink_alpha = *opts.alpha;
+    sink_alpha.source_premultiplied = opts.out_size ? 1 : 0; /* every file of a call with targets went through the resize */
+    return ffhip_bgra_to_tensor_items_alpha(good.data(), (int)good.size(), fmt, &sink_alpha, stream);
 }
 
 /* The driver: the planned files part by part -- decode, the stages behind it, one synchronisation (the next part decodes into the same
@@ -369,6 +468,7 @@ bool tensor_files_args_ok(const uint8_t *const *files, const size_t *lens, int n
                           const TensorOptions &opts)
 {
     if (n < 0 || !tensor_format_ok(fmt) || (n > 0 && !(files && lens && outs && status))) return false;
+    if (!tensor_alpha_ok(opts.alpha, fmt) || (tensor_alpha_on(opts.alpha) && opts.alpha->source_premultiplied)) return false;
     if (opts.filter != FFHIP_RESIZE_BILINEAR && opts.filter != FFHIP_RESIZE_ANTIALIAS) return false;
     for (int i = 0; opts.oriented && opts.orient && i < n; i++)
         if (opts.orient[i] < 0 || opts.orient[i] > 8) return false;
@@ -427,6 +527,9 @@ int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
 {
     const unsigned flags = opts.flags; /* FFHIP_WEBP_PIXELS_LIBWEBP: probe and decode under that rule; the planner and the chain do not know */
     if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts) || (flags & ~FFHIP_WEBP_PIXELS_LIBWEBP)) return FFHIP_EINVAL;
+    const bool with_alpha = tensor_alpha_on(opts.alpha);
+    if (with_alpha && !(flags & FFHIP_WEBP_PIXELS_LIBWEBP)) return FFHIP_EINVAL; /* the reference rule has no alpha */
+    const unsigned decode_flags = flags | (with_alpha ? FFHIP_WEBP_ALPHA : 0u);  /* the probe knows no alpha bit */
     if (n == 0) return FFHIP_OK;
     std::vector<TensorFile> plan((size_t)n);
     for (int i = 0; i < n; i++) {
@@ -437,7 +540,7 @@ int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
         plan[(size_t)i] = tensor_file_plan(p, tensor_orientation(opts, i, p, ffhip_webp_exif_orientation, files[i], lens[i]), i, opts, fmt, outs);
     }
     return tensor_files_run(plan, opts, fmt, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
-        return ffhip_webp_decode_files_device_ex(files + first, lens + first, cnt, n_threads, d_bgra, pitch, nullptr, flags,
+        return ffhip_webp_decode_files_device_ex(files + first, lens + first, cnt, n_threads, d_bgra, pitch, nullptr, decode_flags,
                                                  info_out ? info_out + first : nullptr, status + first, stream);
     });
 }
@@ -568,4 +671,32 @@ extern "C" int ffhip_vp8l_decode_files_tensor(const uint8_t *const *files, const
 {
     return vp8l_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags), info_out,
                              status, stream);
+}
+
+/* the calls with the alpha record: the same code, the existing entries being alpha == NULL */
+extern "C" int ffhip_webp_decode_files_tensor_alpha(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                    const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                    const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                                    ffhip_webp_info *info_out, int *status, void *stream)
+{
+    return webp_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags).keep(alpha),
+                             info_out, status, stream);
+}
+
+extern "C" int ffhip_png_decode_files_tensor_alpha(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                   const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                   const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                                   ffhip_png_info *info_out, int *status, void *stream)
+{
+    return png_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags).keep(alpha),
+                            info_out, status, stream);
+}
+
+extern "C" int ffhip_vp8l_decode_files_tensor_alpha(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                    const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                    const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                                    ffhip_vp8l_info *info_out, int *status, void *stream)
+{
+    return vp8l_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags).keep(alpha),
+                             info_out, status, stream);
 }

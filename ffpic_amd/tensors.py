@@ -42,23 +42,80 @@ def tensor_format(dtype=None, layout="CHW", order="RGB", mean=None, std=None):
     return f
 
 
-def bgra_to_tensors(items, fmt, stream=None):
+_ALPHA_MODES = {"drop": capi.FFHIP_ALPHA_DROP, "straight": capi.FFHIP_ALPHA_STRAIGHT, "premultiplied": capi.FFHIP_ALPHA_PREMULTIPLIED,
+                "over": capi.FFHIP_ALPHA_OVER}
+
+
+def _alpha_arg(alpha):
+    """alpha='drop' | 'straight' | 'premultiplied' | ('over', (r, g, b)) -> (mode name, (r, g, b) or None); anything else: ValueError"""
+    if isinstance(alpha, str) and alpha in ("drop", "straight", "premultiplied"):
+        return alpha, None
+    if isinstance(alpha, (tuple, list)) and len(alpha) == 2 and alpha[0] == "over":
+        try:
+            rgb = tuple(alpha[1])
+        except TypeError:
+            rgb = ()
+        if len(rgb) == 3 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v <= 255 for v in rgb):
+            return "over", tuple(int(v) for v in rgb)
+    raise ValueError(f"alpha {alpha!r}: 'drop', 'straight', 'premultiplied' or ('over', (r, g, b)) with bytes r, g, b")
+
+
+def tensor_alpha(alpha="drop", normalised=False, source_premultiplied=False):
+    """capi.TensorAlpha for alpha='drop' | 'straight' | 'premultiplied' | ('over', (r, g, b)).  normalised: the alpha channel of a float
+    output is alpha * float32(1 / 255), as the colours are on a 0..1 scale under mean / std; otherwise the byte value.
+    source_premultiplied: the pictures the sink reads are premultiplied BGRA (what resize_bgra(..., premultiplied=True) leaves)."""
+    mode, rgb = _alpha_arg(alpha)
+    a = capi.TensorAlpha()
+    a.mode, a.source_premultiplied = _ALPHA_MODES[mode], int(bool(source_premultiplied))
+    if rgb:
+        a.background[0], a.background[1], a.background[2] = rgb[2], rgb[1], rgb[0]
+    a.alpha_scale, a.alpha_bias = (1.0 / 255.0 if normalised else 1.0), 0.0      # ctypes rounds the double to float32, once
+    return a
+
+
+def alpha_channels(alpha="drop"):
+    """the channel count of the tensors under alpha=: 4 for 'straight' and 'premultiplied', 3 otherwise"""
+    return 4 if _alpha_arg(alpha)[0] in ("straight", "premultiplied") else 3
+
+
+def alpha_entry_point(codec, alpha="drop", pixels="reference", oriented=False, targets=False):
+    """The C entry a files-to-tensors call of codec 'png', 'vp8l' or 'webp' goes through under alpha=: 'drop' is the entry the call took
+    before there was the argument; every other value is the codec's _alpha entry, which WebP has under pixels='libwebp' only (the
+    reference rule has no alpha: ValueError).  Needs neither torch nor the library."""
+    if codec not in ("png", "vp8l", "webp"):
+        raise ValueError(f"{codec!r}: 'png', 'vp8l' or 'webp' -- the codecs whose files can have alpha")
+    flags = ops.webp_pixel_flags(pixels) if codec == "webp" else 0
+    if _alpha_arg(alpha)[0] == "drop":
+        return f"ffhip_{codec}_decode_files_tensor" if codec != "webp" else webp_entry_point(pixels, oriented, targets)
+    if codec == "webp" and not flags:
+        raise ValueError("alpha needs pixels='libwebp': the reference rule decodes no alpha plane")
+    return f"ffhip_{codec}_decode_files_tensor_alpha"
+
+
+def bgra_to_tensors(items, fmt, stream=None, alpha=None):
     """ffhip_bgra_to_tensor_items: `items` a list of capi.TensorItem (device pointers, strides in elements), `fmt` a capi.TensorFormat;
-    one launch for the whole batch.  Only enqueues on `stream` (a hipStream_t handle; None: the default stream)."""
+    one launch for the whole batch.  alpha: None, or a capi.TensorAlpha (tensor_alpha) -- ffhip_bgra_to_tensor_items_alpha: four
+    channels, or three composited over a background.  Only enqueues on `stream` (a hipStream_t handle; None: the default stream)."""
     L = capi.lib()
     n = len(items)
     arr = (capi.TensorItem * max(n, 1))(*items)
-    capi.check(L.ffhip_bgra_to_tensor_items(arr, n, C.byref(fmt), stream), "ffhip_bgra_to_tensor_items")
+    if alpha is None:
+        capi.check(L.ffhip_bgra_to_tensor_items(arr, n, C.byref(fmt), stream), "ffhip_bgra_to_tensor_items")
+    else:
+        capi.check(L.ffhip_bgra_to_tensor_items_alpha(arr, n, C.byref(fmt), C.byref(alpha), stream), "ffhip_bgra_to_tensor_items_alpha")
 
 
-def resize_bgra(items, antialias=True, stream=None):
+def resize_bgra(items, antialias=True, stream=None, premultiplied=False):
     """ffhip_bgra_resize_items: `items` a list of capi.ResizeItem (device pointers, pitches in bytes), BGRA rectangles of any sizes to BGRA
     pictures of any sizes by the library's integer rule (antialias: the triangle widens with the shrink factor; otherwise two taps), one
-    resize launch for the whole batch.  Only enqueues on `stream` (a hipStream_t handle; None: the default stream)."""
+    resize launch for the whole batch.  premultiplied=True: ffhip_bgra_resize_items_premultiplied -- straight BGRA in, every pixel
+    premultiplied before it is filtered, premultiplied BGRA out: the colour under transparent pixels does not bleed into the edges.
+    Only enqueues on `stream` (a hipStream_t handle; None: the default stream)."""
     L = capi.lib()
     n = len(items)
     arr = (capi.ResizeItem * max(n, 1))(*items)
-    capi.check(L.ffhip_bgra_resize_items(arr, n, _filter(antialias), stream), "ffhip_bgra_resize_items")
+    what = "ffhip_bgra_resize_items_premultiplied" if premultiplied else "ffhip_bgra_resize_items"
+    capi.check(getattr(L, what)(arr, n, _filter(antialias), stream), what)
 
 
 def orient_bgra(items, stream=None):
@@ -91,13 +148,13 @@ def axis_taps(n_in, n_out, antialias=True):
     return first, taps
 
 
-def tensor_out(t, layout):
+def tensor_out(t, layout, channels=3):
     """capi.TensorOut of a torch tensor [3][H][W] (layout 'CHW') or [H][W][3] ('HWC') whose innermost dimension(s) are dense: a slice of a
-    batch tensor, a view with padded rows"""
+    batch tensor, a view with padded rows.  channels=4: the tensors of the four-channel alpha modes"""
     if layout == "CHW":
-        ok, rs, ps = t.dim() == 3 and t.shape[0] == 3 and t.stride(2) == 1, t.stride(1), t.stride(0)
+        ok, rs, ps = t.dim() == 3 and t.shape[0] == channels and t.stride(2) == 1, t.stride(1), t.stride(0)
     else:
-        ok, rs, ps = t.dim() == 3 and t.shape[2] == 3 and t.stride(2) == 1 and t.stride(1) == 3, t.stride(0), 0
+        ok, rs, ps = t.dim() == 3 and t.shape[2] == channels and t.stride(2) == 1 and t.stride(1) == channels, t.stride(0), 0
     if not ok:
         raise ValueError(f"a {layout} tensor with dense pixels is needed, got shape {tuple(t.shape)} strides {t.stride()}")
     return capi.TensorOut(t.data_ptr(), rs, ps)
@@ -187,8 +244,12 @@ _ENTRY_TAILS = {
 
 
 def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias, apply_exif_orientation,
-                       orientation, return_orientation, reduce=1, return_reduce=False, progressive=False, flags=0, pixels="reference"):
+                       orientation, return_orientation, reduce=1, return_reduce=False, progressive=False, flags=0, pixels="reference", alpha="drop"):
     fmt = tensor_format(dtype, layout, order, mean, std)
+    with_alpha = _alpha_arg(alpha)[0] != "drop"                   # 'drop' goes through the entries the call took before there was the argument
+    alpha_what = alpha_entry_point(codec.name, alpha, pixels) if with_alpha else None
+    record = tensor_alpha(alpha, normalised=mean is not None or std is not None) if with_alpha else None
+    channels = alpha_channels(alpha)
     targets = _sizes(size, len(files))                            # argument errors come before any device use
     den = _reduce(reduce, size)
     imposed = _orientations(orientation, len(files))
@@ -197,6 +258,7 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
     one_entry = webp_ex or codec.name in ("png", "vp8l")          # PNG and lossless WebP have ONE entry each, with the ninth's tail and flags = 0
     what = (f"ffhip_{codec.name}_decode_files_tensor" if codec.name in ("png", "vp8l") else webp_entry_point(pixels, oriented, bool(targets)) if webp_ex
             else entry_point(codec.name, oriented, den, bool(targets), progressive, flags))
+    what = alpha_what or what
     probe = codec.probe_progressive if progressive else codec.probe
     import torch
     tdtype = getattr(torch, _dtype_name(dtype))
@@ -229,7 +291,7 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
                 raise
             mw, mh, swap = rois[i][2], rois[i][3], False          # a rectangle the library refuses: its code comes from the call
         sizes.append((mw, mh) if swap else (mh, mw))
-    shape = (lambda h, w: (3, h, w)) if layout == "CHW" else (lambda h, w: (h, w, 3))
+    shape = (lambda h, w: (channels, h, w)) if layout == "CHW" else (lambda h, w: (h, w, channels))
     device = torch.device("cuda", dev)
     if stack:
         if len(set(sizes)) > 1:
@@ -239,7 +301,7 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
     else:
         tensors = [None if s is None or min(s) < 1 else torch.empty(shape(*s), dtype=tdtype, device=device) for s in sizes]
     ints = C.c_int * max(n, 1)
-    outs = (capi.TensorOut * max(n, 1))(*[capi.TensorOut() if t is None else tensor_out(t, layout) for t in tensors])
+    outs = (capi.TensorOut * max(n, 1))(*[capi.TensorOut() if t is None else tensor_out(t, layout, channels) for t in tensors])
     rects = (capi.Rect * max(n, 1))(*[capi.Rect(*r) for r in rois]) if rois else None
     bufs, ptrs, lens = ops.file_args(files)
     status, used, used_turn = ints(), ints(*([1] * max(n, 1))), ints()
@@ -249,7 +311,9 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
         "orient": (ints(*[(max(t, 1) if imposed else 0) if oriented else 1 for t in turns]), used_turn),
         "flags": (capi.FFHIP_WEBP_PIXELS_LIBWEBP if webp_ex else flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0),),
     }
-    tail = sum((tails[part] for part in (_WEBP_EX_TAIL if one_entry else _ENTRY_TAILS[what])), ())
+    tail = sum((tails[part] for part in (_WEBP_EX_TAIL if one_entry or with_alpha else _ENTRY_TAILS[what])), ())
+    if with_alpha:                                                # the _alpha entries: the ninth's tail, then the record
+        tail += (C.byref(record),)
     rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, *tail, None, status, torch.cuda.current_stream().cuda_stream)
     if oriented:
         turns = list(used_turn)[:n]
@@ -346,35 +410,46 @@ def decode_jpeg_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
 
 def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
                            strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False,
-                           pixels="reference"):
+                           pixels="reference", alpha="drop"):
     """ffhip_webp_decode_files_tensor (with size: ffhip_webp_decode_files_tensor_resized; with apply_exif_orientation or orientation:
     ffhip_webp_decode_files_tensor_oriented, the tag read from the file's EXIF chunk): lossy WebP files; arguments and result as
     decode_jpeg_to_tensors.  A file's display size is the
     probe's width x height as far as the decoded picture holds it.
       pixels   'reference': the reference decoder's pixels, as ever.  'libwebp': what libwebp -- PIL, torchvision, a browser -- makes of the
                same file, sample for sample (ffhip_webp_decode_files_tensor_ex with FFHIP_WEBP_PIXELS_LIBWEBP): the picture is the frame
-               tag's width x height, and roi, size and orientation act on it.  Anything else: ValueError"""
+               tag's width x height, and roi, size and orientation act on it.  Anything else: ValueError
+      alpha    as decode_png_to_tensors: the ALPH plane of a file that has one (ffhip_webp_decode_files_tensor_alpha, FFHIP_WEBP_ALPHA
+               underneath), 255 for every other file.  Only with pixels='libwebp': the reference rule decodes no alpha (ValueError)"""
     ops.webp_pixel_flags(pixels)
+    alpha_entry_point("webp", alpha, pixels)
     return _decode_to_tensors(_WEBP_LIBWEBP if pixels == "libwebp" else _WEBP, files, pixels=pixels, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
-                              return_orientation=return_orientation)
+                              return_orientation=return_orientation, alpha=alpha)
 
 
 def decode_png_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                          strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False):
+                          strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False,
+                          alpha="drop"):
     """ffhip_png_decode_files_tensor: PNG files of every colour type and bit depth, interlaced or not; arguments and result as
-    decode_webp_to_tensors (the orientation tag is read from the file's eXIf chunk).  A file's display size is its width x height.  The
-    tensors have three channels: alpha is dropped, as PIL's convert("RGB") drops it -- ops.png_decode_files_device delivers BGRA with it."""
-    return _decode_to_tensors(_PNG, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+    decode_webp_to_tensors (the orientation tag is read from the file's eXIf chunk).  A file's display size is its width x height.
+      alpha    'drop': three channels, alpha is dropped as PIL's convert("RGB") drops it -- the colour stored under transparent pixels
+               shows.  'straight': four channels R,G,B,A ([N,4,H,W] with stack=True), the colour as stored.  'premultiplied': four
+               channels, the colour times alpha / 255 (PIL's convert("RGBa")).  ('over', (r, g, b)): three channels, the picture
+               composited over that background colour (Image.alpha_composite).  With size the resize filters premultiplied samples, so
+               the colour under transparent pixels never bleeds into the edges; 'straight' un-premultiplies behind it.  Integers only
+               (include/ffpic_hip.h, "alpha into the tensors").  The alpha channel of a float tensor is alpha * float32(1 / 255) when
+               mean or std is given, the byte value otherwise (ffhip_png_decode_files_tensor_alpha).  Anything else: ValueError"""
+    return _decode_to_tensors(_PNG, files, alpha=alpha, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)
 
 
 def decode_webp_lossless_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
-                                    strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False):
+                                    strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False,
+                                    alpha="drop"):
     """ffhip_vp8l_decode_files_tensor: lossless WebP (VP8L) files, the pixels libwebp gives; arguments and result as decode_png_to_tensors
-    (the orientation tag is read from the file's EXIF chunk).  A file's display size is its header's width x height.  The tensors have
-    three channels: alpha is dropped -- ops.vp8l_decode_files_device delivers BGRA with it."""
-    return _decode_to_tensors(_VP8L, files, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+    (the orientation tag is read from the file's EXIF chunk; alpha= through ffhip_vp8l_decode_files_tensor_alpha, a file whose
+    alpha_is_used bit is clear delivering alpha 255).  A file's display size is its header's width x height."""
+    return _decode_to_tensors(_VP8L, files, alpha=alpha, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)

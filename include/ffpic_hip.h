@@ -700,8 +700,8 @@ int ffhip_debug_vp8_upsample_color(const uint8_t *d_y, const uint8_t *d_u, const
 
 /* ---- lossy WebP, the alpha plane (opt-in; ffhip_webp_alpha.c, ffhip_webp_alpha_body.h, ffhip_webp_alpha_gpu.hip) ----
  * FFHIP_WEBP_ALPHA is accepted together with FFHIP_WEBP_PIXELS_LIBWEBP by ffhip_webp_decode_files_device_ex and by no other call: without
- * the libwebp bit, and on the probe, parse, parse_device and tensor calls (whose three-channel sink would drop alpha), it is FFHIP_EINVAL
- * as any unknown bit is.  Without the bit every call keeps its bytes and its verdicts.  With it, a file that has a VP8X chunk with the
+ * the libwebp bit, and on the probe, parse, parse_device and tensor calls, it is FFHIP_EINVAL as any unknown bit is (a tensor call that
+ * keeps alpha is ffhip_webp_decode_files_tensor_alpha, which sets the bit underneath itself).  Without the bit every call keeps its bytes and its verdicts.  With it, a file that has a VP8X chunk with the
  * alpha flag (0x10) set and an ALPH chunk between it and the `VP8 ` chunk gets that plane in byte 3 of its width x height pixels, sample
  * for sample what PIL's Image.open(f).convert("RGBA") gives (libwebp 1.6.0); the colour bytes are those of the unflagged call (no
  * premultiplication).  Every other file is exactly what the unflagged call gives: alpha 255, the same status.  The rule, each line held
@@ -980,7 +980,7 @@ typedef struct ffhip_tensor_format {
  *   row_stride,        in elements.  HWC: element (y, x, c) at y row_stride + 3 x + c, row_stride >= 3 width, plane_stride unused.
  *   plane_stride       CHW: element (c, y, x) at c plane_stride + y row_stride + x, row_stride >= width,
  *                      plane_stride >= row_stride (height - 1) + width
- * The alpha byte is ignored.  Only the width x height elements per channel are written: row padding, plane padding and the bytes around the
+ * The alpha byte is ignored (ffhip_bgra_to_tensor_items_alpha below keeps it).  Only the width x height elements per channel are written: row padding, plane padding and the bytes around the
  * output stay untouched, whatever the output's alignment (rows are cut along the DESTINATION's 16-byte blocks: whole blocks are stored as
  * one 16-byte store, the partial block at either end of a row element by element). */
 typedef struct ffhip_tensor_item {
@@ -996,6 +996,38 @@ typedef struct ffhip_tensor_item {
  * outside what its fields' lines above say --, on a machine without a device too; FFHIP_ENODEV there for good arguments).  n == 0 is
  * FFHIP_OK.  Only enqueues on `stream`; the records and the per-workgroup table are library scratch of the stream. */
 int ffhip_bgra_to_tensor_items(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, void *stream);
+
+/* ---- alpha into the tensors (ffhip_alpha_body.h, ffhip_tensor.hip) ----
+ * PNG, lossless WebP and lossy WebP with an ALPH chunk decode to BGRA with real alpha; the call above ignores that byte.  This record
+ * tells the sink -- and, through the _alpha file calls, the whole chain -- what to make of it.  Integers only, every step held against
+ * PIL (tests/test_tensor_alpha_capi.py); c, p, g, a are bytes, div255(t) = (t + 128 + ((t + 128) >> 8)) >> 8 = floor(t / 255 + 1/2):
+ *   premultiply         p = div255(c a)                                  (PIL convert("RGBa"))
+ *   un-premultiply      a == 0 ? 0 : floor(255 p / a)                    (PIL RGBa -> RGBA; exact for p <= a, at most 255)
+ *   over g, straight    div255(c a + g (255 - a))                        (PIL Image.alpha_composite onto an opaque background)
+ *   over g, premult.    p + div255(g (255 - a))                          (p <= a: at most 255)
+ * A source that claims to be premultiplied and is not (p > a) gives bytes saturated at 255, never anything outside its element.
+ *   FFHIP_ALPHA_DROP           three channels, the alpha byte ignored: ffhip_bgra_to_tensor_items
+ *   FFHIP_ALPHA_STRAIGHT       four channels R,G,B,A (bgr: B,G,R,A): the colour as stored, un-premultiplied where the source is premultiplied
+ *   FFHIP_ALPHA_PREMULTIPLIED  four channels, the colour p: premultiplied here where the source is straight
+ *   FFHIP_ALPHA_OVER           three channels, the colour composited over `background`
+ * Float outputs: the colour channels take fmt's scale and bias, applied to the byte the rule gives; the alpha channel takes alpha_scale
+ * and alpha_bias by the same two-rounding expression.  U8 needs alpha_scale 1 and alpha_bias 0; both finite. */
+#define FFHIP_ALPHA_DROP 0
+#define FFHIP_ALPHA_STRAIGHT 1
+#define FFHIP_ALPHA_PREMULTIPLIED 2
+#define FFHIP_ALPHA_OVER 3
+typedef struct ffhip_tensor_alpha {
+    int32_t mode;                 /* FFHIP_ALPHA_*                                                                       */
+    int32_t source_premultiplied; /* 0: the pictures are straight BGRA, as the decode calls leave them; 1: premultiplied */
+    uint8_t background[4];        /* B,G,R,unused: FFHIP_ALPHA_OVER                                                      */
+    float alpha_scale, alpha_bias;
+} ffhip_tensor_alpha;
+/* ffhip_bgra_to_tensor_items under *alpha.  alpha == NULL or mode FFHIP_ALPHA_DROP: that call, bit for bit (the rest of the record is not
+ * read).  Items as there; with four channels HWC element (y, x, c) is at y row_stride + 4 x + c, row_stride >= 4 width, and CHW has four
+ * planes, the alpha plane last.  FFHIP_EINVAL besides that call's: an unknown mode, source_premultiplied other than 0 or 1, an alpha
+ * scale or bias that is not finite, U8 with alpha_scale other than 1 or alpha_bias other than 0.  Every check is made before anything is
+ * enqueued (FFHIP_EINVAL in front of FFHIP_ENODEV).  Only enqueues on `stream`. */
+int ffhip_bgra_to_tensor_items_alpha(const ffhip_tensor_item *items, int n, const ffhip_tensor_format *fmt, const ffhip_tensor_alpha *alpha, void *stream);
 
 /* Files in, tensors out.  outs[i] is file i's output (fields as in ffhip_tensor_item); roi[i] the rectangle of its DISPLAY picture to
  * deliver, roi == NULL the whole of it: width x height as ffhip_jpeg_probe reports them, ffhip_webp_info.width x .height (what of it
@@ -1033,7 +1065,8 @@ int ffhip_webp_decode_files_tensor(const uint8_t *const *files, const size_t *le
  *   can pay for (ANTIALIAS 1080 -> 1: 41 too many, the largest weight 7), that tap becomes 0 and what is still owed is taken from the
  *   taps that follow in the same order -- falling r, the lowest k on a tie --, each down to 0 at most.  No run of up to 224 taps needs it.
  * A byte of output pixel (ox, oy) is (sum_y sum_x qy qx v[y][x] + 2^23) >> 24: one rounding, no clamp needed (at most 255 2^24 + 2^23).
- * All four bytes of a pixel are filtered alike: a constant alpha stays constant, equal sizes on both axes are a copy. */
+ * All four bytes of a pixel are filtered alike: a constant alpha stays constant, equal sizes on both axes are a copy.  For pictures with
+ * real alpha that is the wrong rule -- the colour stored under transparent pixels reaches the edges --: ffhip_bgra_resize_items_premultiplied. */
 #define FFHIP_RESIZE_BILINEAR 0
 #define FFHIP_RESIZE_ANTIALIAS 1
 #define FFHIP_RESIZE_MAX_SIDE 16384 /* of a source rectangle and of an output: (2 k + 1) n_out stays below 2^30 */
@@ -1064,6 +1097,12 @@ typedef struct ffhip_resize_item {
  * say --, on a machine without a device too; FFHIP_ENODEV there for good arguments).  n == 0 is FFHIP_OK.  Only enqueues on `stream`; the
  * records, the per-workgroup table and the tap tables are library scratch of the stream. */
 int ffhip_bgra_resize_items(const ffhip_resize_item *items, int n, int filter, void *stream);
+/* The same call for pictures with real alpha: the source is STRAIGHT BGRA, every pixel is premultiplied (p = div255(c a), "alpha into the
+ * tensors" above) as its row is staged, the rule above runs unchanged over the four premultiplied bytes, and the destination is
+ * PREMULTIPLIED BGRA (p <= a holds for every output pixel: the weights are non-negative and sum to 4096, and the rounding is monotone).
+ * The colour stored under transparent pixels therefore never reaches the output, which it does through the call above.  An opaque
+ * picture gives that call's bytes.  Items, checks and scratch as there. */
+int ffhip_bgra_resize_items_premultiplied(const ffhip_resize_item *items, int n, int filter, void *stream);
 
 /* Files in, tensors of chosen sizes out: ffhip_*_decode_files_tensor with the resize between the decoder and the tensor stage.  roi[i]
  * (roi == NULL: the whole display picture) is file i's SOURCE rectangle, out_size[i] the size it is resized to by `filter`, and outs[i]
@@ -1225,6 +1264,16 @@ int ffhip_webp_decode_files_tensor_ex(const uint8_t *const *files, const size_t 
 int ffhip_webp_decode_files_tensor_oriented(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                             const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                             const int *orient, int *orient_out, ffhip_webp_info *info_out, int *status, void *stream);
+/* ffhip_webp_decode_files_tensor_ex with the alpha record ("alpha into the tensors" above).  alpha == NULL or mode FFHIP_ALPHA_DROP: that
+ * call.  Otherwise `flags` must be FFHIP_WEBP_PIXELS_LIBWEBP (the reference rule has no alpha: FFHIP_EINVAL), the files are decoded with
+ * FFHIP_WEBP_ALPHA underneath -- a file without an ALPH plane is opaque, a refused plane is that file's FFHIP_EINVAL --, and the chain
+ * carries alpha: the resize is ffhip_bgra_resize_items_premultiplied, the sink ffhip_bgra_to_tensor_items_alpha, told that its source is
+ * premultiplied behind a resize.  alpha->source_premultiplied must be 0 (the chain sets it); outs[i] is laid out for the mode's
+ * channel count.  Every check is made before anything is enqueued. */
+int ffhip_webp_decode_files_tensor_alpha(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                         const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                         const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                         ffhip_webp_info *info_out, int *status, void *stream);
 /* Diagnostics: the items the calling thread's last ffhip_*_decode_files_tensor* call sent through ffhip_bgra_orient_items, all its parts
  * together: 0 for a batch of orientation 1 only and for the calls without orientation.  Reset where ffhip_debug_tensor_last_parts is. */
 int ffhip_debug_orient_last_items(void);
@@ -1362,10 +1411,18 @@ int ffhip_png_exif_orientation(const uint8_t *file, size_t len, int *orientation
 int ffhip_png_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
                                   const int64_t *pitch, ffhip_png_info *info_out, int *status, void *stream);
 /* Files to tensors, as ffhip_webp_decode_files_tensor_ex: the display picture is width x height, alpha is dropped by the three-channel
- * sink; out_size == NULL: no resize; orient[i] 1..8, or 0 for the file's eXIf tag, orient == NULL: every file's tag; flags must be 0. */
+ * sink (ffhip_png_decode_files_tensor_alpha keeps it); out_size == NULL: no resize; orient[i] 1..8, or 0 for the file's eXIf tag,
+ * orient == NULL: every file's tag; flags must be 0. */
 int ffhip_png_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                   const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                   const int *orient, int *orient_out, unsigned flags, ffhip_png_info *info_out, int *status, void *stream);
+/* The same with the alpha record ("alpha into the tensors"): alpha == NULL or mode FFHIP_ALPHA_DROP is the call above; otherwise tRNS and
+ * the alpha of colour types 4 and 6 reach the tensors as the mode says, through ffhip_bgra_resize_items_premultiplied where there is a
+ * resize.  alpha->source_premultiplied must be 0; outs[i] is laid out for the mode's channel count. */
+int ffhip_png_decode_files_tensor_alpha(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                        const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                        const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                        ffhip_png_info *info_out, int *status, void *stream);
 /* Diagnostics: parts and unfilter levels (launches of k_png_unfilter) of the calling thread's last ffhip_png_decode_files_device. */
 int ffhip_debug_png_last(int out[2]);
 /* Diagnostics (tests/tools/bench_png.py): milliseconds of that call's stages, all its parts together -- [0] the host threads' chunk walk
@@ -1432,12 +1489,17 @@ int ffhip_vp8l_read_info(const uint8_t *file, size_t len, ffhip_vp8l_info *info)
  * failure.  Argument checks come before anything is enqueued: FFHIP_EINVAL for NULL arrays, then FFHIP_ENODEV.  Synchronises `stream`. */
 int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
                                    const int64_t *pitch, ffhip_vp8l_info *info_out, int *status, void *stream);
-/* Files to tensors, as ffhip_png_decode_files_tensor: the display picture is width x height, alpha is dropped by the three-channel sink;
- * out_size == NULL: no resize; orient[i] 1..8, or 0 for the file's EXIF chunk (ffhip_webp_exif_orientation), orient == NULL: every file's
- * tag; flags must be 0. */
+/* Files to tensors, as ffhip_png_decode_files_tensor: the display picture is width x height, alpha is dropped by the three-channel sink
+ * (ffhip_vp8l_decode_files_tensor_alpha keeps it); out_size == NULL: no resize; orient[i] 1..8, or 0 for the file's EXIF chunk
+ * (ffhip_webp_exif_orientation), orient == NULL: every file's tag; flags must be 0. */
 int ffhip_vp8l_decode_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
                                    const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
                                    const int *orient, int *orient_out, unsigned flags, ffhip_vp8l_info *info_out, int *status, void *stream);
+/* The same with the alpha record, as ffhip_png_decode_files_tensor_alpha: a file whose alpha_is_used bit is clear delivers alpha 255. */
+int ffhip_vp8l_decode_files_tensor_alpha(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                         const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                         const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                         ffhip_vp8l_info *info_out, int *status, void *stream);
 /* Diagnostics: parts, launches of k_vp8l_predict, and files inverted on the host, of the calling thread's last
  * ffhip_vp8l_decode_files_device. */
 int ffhip_debug_vp8l_last(int out[3]);
