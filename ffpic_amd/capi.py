@@ -48,6 +48,7 @@ EXPORTS = [
     "ffhip_debug_scratch_fill",
     "ffhip_bgra_to_tensor_items_alpha", "ffhip_bgra_resize_items_premultiplied",
     "ffhip_png_decode_files_tensor_alpha", "ffhip_vp8l_decode_files_tensor_alpha", "ffhip_webp_decode_files_tensor_alpha",
+    "ffhip_inflate_streams_device", "ffhip_png_decode_files_device_ex", "ffhip_png_decode_files_tensor_ex", "ffhip_debug_png_inflate",
 ]
 
 
@@ -56,6 +57,7 @@ FFHIP_JPEG_ACCEPT_PROGRESSIVE, FFHIP_JPEG_MAX_SCANS = 1, 128
 FFHIP_JPEG_PIXELS_LIBJPEG = 0x10
 FFHIP_WEBP_PIXELS_LIBWEBP = 0x10
 FFHIP_WEBP_ALPHA = 0x20
+FFHIP_PNG_INFLATE_DEVICE = 0x1
 FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1002, -1003
 
 
@@ -426,6 +428,14 @@ def lib():
         getattr(L, f"ffhip_{name}_decode_files_tensor_alpha").argtypes = [
             vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect), C.POINTER(Size), ci, C.POINTER(ci), C.POINTER(ci),
             C.c_uint, C.POINTER(TensorAlpha), C.POINTER(info), vp, vp]
+    L.ffhip_inflate_streams_device.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
+    L.ffhip_png_decode_files_device_ex.argtypes = [vp, vp, ci, ci, vp, vp, C.POINTER(PngInfo), vp, C.c_uint, vp]
+    L.ffhip_png_decode_files_tensor_ex.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect), C.POINTER(Size), ci,
+                                                   C.POINTER(ci), C.POINTER(ci), C.c_uint, C.POINTER(TensorAlpha), C.c_uint, C.POINTER(PngInfo), vp, vp]
+    L.ffhip_debug_png_inflate.argtypes = [C.POINTER(C.c_double)]
+    for name in ("ffhip_inflate_upto", "ffhip_inflate_model"):    # exported, not in the public header (csrc/ffhip_png_internal.h)
+        getattr(L, name).argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci]
+    L.ffhip_inflate_model_mode.argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci, ci]
     L.ffhip_debug_scratch_fill.argtypes = [vp, ci, C.POINTER(C.c_uint64), C.POINTER(ci), ci]
     L.ffhip_env_value_test.argtypes = [C.c_char_p, vp, sz]
     L.ffhip_env_value_test.restype = C.c_long

@@ -173,26 +173,30 @@ int ffhip_png_open(const uint8_t *file, size_t len, ffhip_png_file *pf)
     }
 }
 
+void ffhip_png_join_idat(const uint8_t *file, const ffhip_png_file *pf, uint8_t *joined)
+{
+    uint32_t size = 0;
+    size_t at = pf->first_idat, got = 0;
+    for (int k = 0; k < pf->idat_chunks; at += (size_t)size + 12) { /* the walk ffhip_png_open has made: every chunk fits the file */
+        size = be32(file + at);
+        if (!chunk_is(file, at, "IDAT")) continue;
+        memcpy(joined + got, file + at + 8, size);
+        got += size;
+        k++;
+    }
+}
+
 int ffhip_png_read_filtered(const uint8_t *file, size_t len, const ffhip_png_file *pf, uint8_t *filtered)
 {
     const ffhip_png_info *info = &pf->info;
     const uint8_t *z = NULL;
     uint8_t *joined = NULL;
-    uint32_t size = 0;
-    size_t at = pf->first_idat;
     if (pf->idat_chunks == 1) { /* the stream lies in the file as it is */
-        z = file + at + 8;
+        z = file + pf->first_idat + 8;
     } else {
         joined = (uint8_t *)malloc(pf->idat_bytes ? pf->idat_bytes : 1);
         if (!joined) return FFHIP_ENOMEM;
-        size_t got = 0;
-        for (int k = 0; k < pf->idat_chunks; at += (size_t)size + 12) { /* the walk ffhip_png_open has made: every chunk fits the file */
-            size = be32(file + at);
-            if (!chunk_is(file, at, "IDAT")) continue;
-            memcpy(joined + got, file + at + 8, size);
-            got += size;
-            k++;
-        }
+        ffhip_png_join_idat(file, pf, joined);
         z = joined;
     }
     (void)len;
@@ -208,7 +212,7 @@ int ffhip_png_read_filtered(const uint8_t *file, size_t len, const ffhip_png_fil
             if (sub[y * pitch] > 4) return FFHIP_EINVAL;
         sub += pitch * (uint64_t)info->pass_rows[p];
     }
-    if (info->color_type != 3 || info->palette_size >= (1 << info->bit_depth)) return FFHIP_OK;
+    if (!ffhip_png_short_palette(info)) return FFHIP_OK;
     /* a palette shorter than its indices' range: the indices are known only once the rows are unfiltered, which is done on a copy -- the
      * caller's rows stay filtered, for the device or the host to unfilter as every other file's */
     uint8_t *copy = (uint8_t *)malloc((size_t)info->filtered_bytes);

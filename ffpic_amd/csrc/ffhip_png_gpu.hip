@@ -3,6 +3,8 @@
  * row filters in place, k_png_expand writes the pictures.  Both kernels compile the functions of ffhip_png_body.h, as ffhip_png_picture
  * does on the host, and neither has an error path: what a file can be refused for is seen on the host.  How a part is driven -- the
  * launch per band level, the gather launch, the end of a part, the stage clock -- is ffhip_staged.h's; the cut into parts is here.
+ * With FFHIP_PNG_INFLATE_DEVICE the host threads copy the streams instead and k_inflate (ffhip_inflate_gpu.hip)
+ * inflates them in front of the two kernels: png_front_device beside png_front_host.
  *
  * k_png_unfilter.  An item is one (file, pass) sub-image, cut into bands of 64 rows; a wave takes one band, lane r its row r.  A row is
  * walked in CHUNKS of four filter units (4 x bpp bytes = bpp dwords), and the lanes are skewed by one chunk: at step t lane r
@@ -20,6 +22,7 @@
  * lane finds each pixel's pass and index by the map, so stores stay full rows whatever the interlace.  A picture's last partial group of
  * four is stored pixel by pixel. */
 #include "ffhip_staged.h"
+#include "ffhip_inflate_gpu.h"
 #include "ffhip_png_internal.h"
 
 #include <chrono>
@@ -187,15 +190,41 @@ __global__ __launch_bounds__(PNG_EXPAND_THREADS) void k_png_expand(PngExpArgs a)
     }
 }
 
-thread_local int t_png_last[2];     /* ffhip_debug_png_last */
-thread_local double t_png_times[4]; /* ffhip_debug_png_times */
+thread_local int t_png_last[2];       /* ffhip_debug_png_last */
+thread_local double t_png_times[4];   /* ffhip_debug_png_times */
+thread_local double t_png_inflate[4]; /* ffhip_debug_png_inflate */
 
 struct PngPartFile { int idx; size_t rows_off, palette_off; };
+/* where the stages behind the front end find a part's file on the device */
+struct PngPartPlace { uint8_t *rows; const u32 *palette; };
 
-/* One part: files pf[] of the call, `bytes` of staging (their filtered pictures, then the palettes).  The clock (FFHIP_PNG_TIMES) stands
- * around the upload, the unfilter launches and the expand launch */
-int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::vector<ffhip_png_file> &pf, const uint8_t *const *files, const size_t *lens,
-                 int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, int *status, void *stream, StageClock &clock)
+/* three events of the device front end's own, made only under FFHIP_PNG_TIMES */
+struct PngInflateClock {
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    bool on;
+    explicit PngInflateClock(bool want) : on(want)
+    {
+        for (int k = 0; on && k < 3; k++)
+            if (hipEventCreate(&ev[k]) != hipSuccess) on = false;
+    }
+    PngInflateClock(const PngInflateClock &) = delete;
+    ~PngInflateClock()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void mark(int k, hipStream_t st) { if (on) (void)hipEventRecord(ev[k], st); }
+    double ms(int k) /* from mark k to mark k + 1, behind a synchronisation */
+    {
+        float v = 0;
+        return on && hipEventElapsedTime(&v, ev[k], ev[k + 1]) == hipSuccess ? v : 0.0;
+    }
+};
+
+/* A part's front end, the host way: the host threads inflate into the pinned staging (the filtered pictures, then the palettes), one
+ * upload */
+int png_front_host(const std::vector<PngPartFile> &part, size_t bytes, const std::vector<ffhip_png_file> &pf, const uint8_t *const *files, const size_t *lens,
+                   int n_threads, int *status, void *stream, StageClock &clock, std::vector<PngPartPlace> &place)
 {
     hipStream_t st = (hipStream_t)stream;
     clock.mark_from(0, st);
@@ -210,22 +239,123 @@ int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::
         if (f.info.color_type == 3) memcpy(pin + p.palette_off, f.palette, 1024);
     });
     t_png_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t_png_inflate[1] += (double)part.size();
     clock.mark_from(0, st);
     FFHIP_CHECK(hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, st), FFHIP_EIO);
     clock.mark_from(1, st);
+    for (size_t k = 0; k < part.size(); k++) place[k] = {dev + part[k].rows_off, (const u32 *)(dev + part[k].palette_off)};
+    return FFHIP_OK;
+}
+
+/* The same with FFHIP_PNG_INFLATE_DEVICE.  The device scratch holds the filtered pictures at their places of the host way (`rows_bytes`
+ * of them) and behind them the TAIL, which alone has a pinned copy and is the one upload: the palettes, the filtered bytes of the files
+ * the host threads inflate after all (a palette shorter than its depth's range: ffhip_png_read_filtered checks the indices on unfiltered
+ * rows), every other file's IDAT payloads joined, and k_inflate's records.  k_inflate writes the pictures and its verdicts, one copy
+ * brings the records back, one synchronisation.  The upload's time goes where the host way's goes; the launch and the copy back are
+ * ffhip_debug_png_inflate's alone: the part's clock starts again behind them */
+int png_front_device(const std::vector<PngPartFile> &part, size_t rows_bytes, const std::vector<ffhip_png_file> &pf, const uint8_t *const *files,
+                     const size_t *lens, int n_threads, int *status, void *stream, StageClock &clock, std::vector<PngPartPlace> &place)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = part.size();
+    std::vector<size_t> pal_off(n, 0), own_off(n, 0);
+    std::vector<char> host_way(n, 0);
+    size_t tail = 0, n_dev = 0, z_bytes = 0;
+    for (size_t k = 0; k < n; k++)
+        if (pf[(size_t)part[k].idx].info.color_type == 3) { pal_off[k] = tail; tail += 1024; }
+    for (size_t k = 0; k < n; k++) {
+        const ffhip_png_file &f = pf[(size_t)part[k].idx];
+        host_way[k] = (char)ffhip_png_short_palette(&f.info);
+        own_off[k] = tail; /* filtered bytes, or the stream */
+        tail += ffhip_up16(host_way[k] ? (size_t)f.info.filtered_bytes : f.idat_bytes);
+        if (!host_way[k]) { n_dev++; z_bytes += f.idat_bytes; }
+    }
+    const size_t rec_off = tail, rec_bytes = n_dev * sizeof(FfhipInflateRec);
+    tail += rec_bytes;
+    uint8_t *pin = ffhip_pinned_scratch(SCRATCH_PNG, stream, tail + 64);
+    uint8_t *dev = (uint8_t *)ffhip_scratch(SCRATCH_PNG, stream, (rows_bytes + tail) / 4 + 16);
+    if (!pin || !dev) return FFHIP_ENOMEM;
+    uint8_t *dev_tail = dev + rows_bytes;
+    const auto t0 = std::chrono::steady_clock::now();
+    ffhip_parallel_for((int)n, n_threads, [&](int k) {
+        const PngPartFile &p = part[(size_t)k];
+        const ffhip_png_file &f = pf[(size_t)p.idx];
+        if (host_way[(size_t)k]) status[p.idx] = ffhip_png_read_filtered(files[p.idx], lens[p.idx], &f, pin + own_off[(size_t)k]);
+        else ffhip_png_join_idat(files[p.idx], &f, pin + own_off[(size_t)k]);
+        if (f.info.color_type == 3) memcpy(pin + pal_off[(size_t)k], f.palette, 1024);
+    });
+    t_png_times[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<FfhipInflateRec> rec;
+    rec.reserve(n_dev);
+    for (size_t k = 0; k < n; k++) {
+        const ffhip_png_info &info = pf[(size_t)part[k].idx].info;
+        place[k] = {host_way[k] ? dev_tail + own_off[k] : dev + part[k].rows_off, (const u32 *)(dev_tail + pal_off[k])};
+        if (host_way[k]) continue;
+        FfhipInflateRec r;
+        memset(&r, 0, sizeof(r));
+        r.src = dev_tail + own_off[k];
+        r.dst = place[k].rows;
+        r.len = pf[(size_t)part[k].idx].idat_bytes;
+        r.cap = info.filtered_bytes;
+        r.partial = 1; /* PNG's "extra bytes are ignored" */
+        r.index = (u32)k;
+        r.png = 1;
+        for (int q = 0; q < 7; q++) {
+            r.rows[q] = (u32)info.pass_rows[q];
+            r.pitch[q] = (u32)info.pass_row_bytes[q] + 1;
+        }
+        rec.push_back(r);
+    }
+    ffhip_inflate_sort(rec);
+    if (rec_bytes) memcpy(pin + rec_off, rec.data(), rec_bytes);
+    t_png_inflate[0] += (double)n_dev;
+    t_png_inflate[1] += (double)(n - n_dev);
+    t_png_inflate[2] += (double)z_bytes;
+    PngInflateClock own(clock.on);
+    own.mark(0, st);
+    FFHIP_CHECK(hipMemcpyAsync(dev_tail, pin, tail, hipMemcpyHostToDevice, st), FFHIP_EIO);
+    own.mark(1, st);
+    if (n_dev) {
+        const int rc = ffhip_inflate_launch((FfhipInflateRec *)(dev_tail + rec_off), n_dev, stream);
+        if (rc) return rc;
+        FFHIP_CHECK(hipMemcpyAsync(pin + rec_off, dev_tail + rec_off, rec_bytes, hipMemcpyDeviceToHost, st), FFHIP_EIO);
+    }
+    own.mark(2, st);
+    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
+    t_png_times[1] += own.ms(0);
+    t_png_inflate[3] += own.ms(1);
+    const FfhipInflateRec *back = (const FfhipInflateRec *)(pin + rec_off);
+    for (size_t k = 0; k < n_dev; k++) status[part[back[k].index].idx] = back[k].status;
+    clock.mark_from(0, st);
+    return FFHIP_OK;
+}
+
+/* One part: files pf[] of the call, `rows_bytes` of filtered pictures and `palette_bytes` of palettes behind them.  The clock
+ * (FFHIP_PNG_TIMES) stands around the upload, the unfilter launches and the expand launch */
+int png_run_part(const std::vector<PngPartFile> &part, size_t rows_bytes, size_t palette_bytes, const std::vector<ffhip_png_file> &pf,
+                 const uint8_t *const *files, const size_t *lens, int n_threads, uint8_t *const *d_bgra, const int64_t *pitch, int *status,
+                 unsigned png_flags, void *stream, StageClock &clock)
+{
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<PngPartPlace> place(part.size());
+    int rc = png_flags & FFHIP_PNG_INFLATE_DEVICE
+                 ? png_front_device(part, rows_bytes, pf, files, lens, n_threads, status, stream, clock, place)
+                 : png_front_host(part, rows_bytes + palette_bytes, pf, files, lens, n_threads, status, stream, clock, place);
+    if (rc) return rc;
     std::vector<PngUnfDesc> unf;
     std::vector<PngExpDesc> exp;
     unsigned long long total = 0;
-    for (const PngPartFile &p : part) {
+    for (size_t k = 0; k < part.size(); k++) {
+        const PngPartFile &p = part[k];
         if (status[p.idx]) continue;
         const ffhip_png_file &f = pf[(size_t)p.idx];
         const ffhip_png_info &info = f.info;
         PngExpDesc e;
         memset(&e, 0, sizeof(e));
-        e.rows = dev + p.rows_off;
+        e.rows = place[k].rows;
         e.dst = d_bgra[p.idx];
         e.pitch = pitch[p.idx];
-        e.palette = info.color_type == 3 ? (const u32 *)(dev + p.palette_off) : nullptr;
+        e.palette = info.color_type == 3 ? place[k].palette : nullptr;
         e.width = (u32)info.width;
         e.height = (u32)info.height;
         e.rule = f.rule;
@@ -235,7 +365,7 @@ int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::
             e.pass_pitch[q] = (u32)info.pass_row_bytes[q] + 1;
             if (!info.pass_rows[q]) continue;
             PngUnfDesc u;
-            u.sub = dev + p.rows_off + at;
+            u.sub = place[k].rows + at;
             u.rows = (u32)info.pass_rows[q];
             u.row_bytes = (u32)info.pass_row_bytes[q];
             u.bpp = (u32)ffhip_png_bpp(info.color_type, info.bit_depth);
@@ -247,7 +377,7 @@ int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::
         exp.push_back(e);
     }
     if (exp.empty()) return FFHIP_OK;
-    int rc = ffhip_banded_launches(SCRATCH_PNG + 1, stream, unf, &t_png_last[1], [&](u32 level, const PngUnfDesc *d_unf, unsigned grid_x, u32 wg_base) {
+    rc = ffhip_banded_launches(SCRATCH_PNG + 1, stream, unf, &t_png_last[1], [&](u32 level, const PngUnfDesc *d_unf, unsigned grid_x, u32 wg_base) {
         PngUnfArgs a;
         a.desc = d_unf; a.level = level; a.wg_base = wg_base;
         hipLaunchKernelGGL(k_png_unfilter, dim3(grid_x), dim3(PNG_BAND), 0, st, a);
@@ -265,11 +395,13 @@ int png_run_part(const std::vector<PngPartFile> &part, size_t bytes, const std::
 
 } // namespace
 
-extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
-                                             const int64_t *pitch, ffhip_png_info *info_out, int *status, void *stream)
+extern "C" int ffhip_png_decode_files_device_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                                const int64_t *pitch, ffhip_png_info *info_out, int *status, unsigned png_flags, void *stream)
 {
-    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status))) return FFHIP_EINVAL;
+    if (n < 0 || (n > 0 && (!files || !lens || !d_bgra || !pitch || !status)) || (png_flags & ~FFHIP_PNG_INFLATE_DEVICE)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
+    const char *sw = FFHIP_ENV("FFHIP_PNG_INFLATE_GPU"); /* the unedited tools and suites over the device front end */
+    if (sw && sw[0] && sw[0] != '0') png_flags |= FFHIP_PNG_INFLATE_DEVICE;
     n_threads = ffhip_host_threads(n_threads);
     std::vector<ffhip_png_file> pf((size_t)n);
     ffhip_parallel_for(n, n_threads, [&](int i) {
@@ -283,6 +415,7 @@ extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const 
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     t_png_last[0] = t_png_last[1] = 0;
     for (double &t : t_png_times) t = 0;
+    for (double &t : t_png_inflate) t = 0;
     StageClock clock(FFHIP_ENV("FFHIP_PNG_TIMES"), t_png_times);
     const size_t budget = ffhip_part_budget(FFHIP_ENV("FFHIP_PNG_PART_BYTES"));
     int rc = FFHIP_OK;
@@ -300,13 +433,21 @@ extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const 
         if (part.empty()) break;
         for (PngPartFile &p : part) p.palette_off += rows;
         t_png_last[0]++;
-        rc = ffhip_part_end(png_run_part(part, rows + palettes, pf, files, lens, n_threads, d_bgra, pitch, status, stream, clock), stream, clock);
+        rc = ffhip_part_end(png_run_part(part, rows, palettes, pf, files, lens, n_threads, d_bgra, pitch, status, png_flags, stream, clock), stream, clock);
     }
     if (rc) return rc;
     for (int k = 0; k < n; k++)
         if (status[k]) return status[k];
     return FFHIP_OK;
 }
+
+extern "C" int ffhip_png_decode_files_device(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                             const int64_t *pitch, ffhip_png_info *info_out, int *status, void *stream)
+{
+    return ffhip_png_decode_files_device_ex(files, lens, n, n_threads, d_bgra, pitch, info_out, status, 0u, stream);
+}
+
+extern "C" int ffhip_debug_png_inflate(double out[4]) { return ffhip_copy_out(out, t_png_inflate); }
 
 extern "C" int ffhip_debug_png_last(int out[2]) { return ffhip_copy_out(out, t_png_last); }
 

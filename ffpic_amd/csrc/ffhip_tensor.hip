@@ -253,6 +253,7 @@ struct TensorOptions {
     TensorOptions &turn(const int *o, int *o_out) { oriented = true; orient = o; orient_out = o_out; return *this; }
     TensorOptions &with(unsigned f) { flags = f; return *this; }
     TensorOptions &keep(const ffhip_tensor_alpha *a) { alpha = a; return *this; }
+    TensorOptions &png(unsigned f) { png_flags = f; return *this; }
     const ffhip_rect *roi;
     const ffhip_size *out_size = nullptr;
     int filter = FFHIP_RESIZE_BILINEAR;
@@ -260,6 +261,7 @@ struct TensorOptions {
     int *denom_out = nullptr, *orient_out = nullptr;
     bool oriented = false;
     unsigned flags = 0u;
+    unsigned png_flags = 0u; /* the PNG calls': FFHIP_PNG_INFLATE_DEVICE */
     const ffhip_tensor_alpha *alpha = nullptr; /* NULL or mode DROP: three channels, the alpha byte ignored.  Otherwise the resize is the
                                                 * premultiplying one and the sink is told so */
 };
@@ -548,7 +550,7 @@ int webp_files_tensor(const uint8_t *const *files, const size_t *lens, int n, in
 int png_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt, const ffhip_tensor_out *outs,
                      const TensorOptions &opts, ffhip_png_info *info_out, int *status, void *stream)
 {
-    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts) || opts.flags) return FFHIP_EINVAL;
+    if (!tensor_files_args_ok(files, lens, n, fmt, outs, status, opts) || opts.flags || (opts.png_flags & ~FFHIP_PNG_INFLATE_DEVICE)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
     std::vector<TensorFile> plan((size_t)n);
     for (int i = 0; i < n; i++) {
@@ -559,8 +561,8 @@ int png_files_tensor(const uint8_t *const *files, const size_t *lens, int n, int
         plan[(size_t)i] = tensor_file_plan(p, tensor_orientation(opts, i, p, ffhip_png_exif_orientation, files[i], lens[i]), i, opts, fmt, outs);
     }
     return tensor_files_run(plan, opts, fmt, status, stream, [&](int first, int cnt, uint8_t *const *d_bgra, const int64_t *pitch) {
-        return ffhip_png_decode_files_device(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
-                                             status + first, stream);
+        return ffhip_png_decode_files_device_ex(files + first, lens + first, cnt, n_threads, d_bgra, pitch, info_out ? info_out + first : nullptr,
+                                                status + first, opts.png_flags, stream);
     });
 }
 
@@ -690,6 +692,15 @@ extern "C" int ffhip_png_decode_files_tensor_alpha(const uint8_t *const *files, 
 {
     return png_files_tensor(files, lens, n, n_threads, fmt, outs, TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags).keep(alpha),
                             info_out, status, stream);
+}
+
+extern "C" int ffhip_png_decode_files_tensor_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                                const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                                const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                                unsigned png_flags, ffhip_png_info *info_out, int *status, void *stream)
+{
+    return png_files_tensor(files, lens, n, n_threads, fmt, outs,
+                            TensorOptions(roi).resize(out_size, filter).turn(orient, orient_out).with(flags).keep(alpha).png(png_flags), info_out, status, stream);
 }
 
 extern "C" int ffhip_vp8l_decode_files_tensor_alpha(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,

@@ -969,6 +969,81 @@ def inflate(data, cap):
     return dst[:got.value].tobytes()
 
 
+def _inflate_host(entry, what, data, cap, *tail):
+    src = np.frombuffer(data, dtype=np.uint8)
+    dst = np.zeros(max(int(cap), 1), np.uint8)
+    got = C.c_size_t()
+    capi.check(entry(src.ctypes.data if src.size else dst.ctypes.data, src.size, dst.ctypes.data, int(cap), C.byref(got), *tail), what)
+    return dst[:got.value].tobytes()
+
+
+def inflate_upto(data, cap, partial=False):
+    """ffhip_inflate_upto (host; csrc/ffhip_png_internal.h): ffhip_inflate, and with partial=True a stream that holds more than cap
+    bytes is cut there and accepted, its check value not looked at"""
+    return _inflate_host(capi.lib().ffhip_inflate_upto, "ffhip_inflate_upto", data, cap, int(bool(partial)))
+
+
+def inflate_model(stream, cap, partial=False, mode=0):
+    """ffhip_inflate_model (host): the model of k_inflate -- the body the kernel compiles, the wave's lanes emulated, every step as all 64
+    loads, then all 64 stores.  Arguments, verdicts and bytes of inflate_upto.  mode: the emulation's variants for the test of the
+    emulation itself (csrc/ffhip_inflate_model.c); 0 is the kernel's."""
+    if mode:
+        return _inflate_host(capi.lib().ffhip_inflate_model_mode, "ffhip_inflate_model_mode", stream, cap, int(bool(partial)), int(mode))
+    return _inflate_host(capi.lib().ffhip_inflate_model, "ffhip_inflate_model", stream, cap, int(bool(partial)))
+
+
+def inflate_streams_device(streams, caps=None, strict=True, stream=None, guard=0, fill=0):
+    """ffhip_inflate_streams_device: zlib streams (list of bytes) inflated by k_inflate, a wave per stream, in one launch, each into its own
+    piece of ONE device allocation.  caps: the pieces' sizes (None: found by the host decoder; a stream it refuses gets 0).  Returns
+    (outputs, status): bytes per stream, None for a refused one, and the per-stream codes; strict: a refused stream raises.
+    guard, fill: `guard` bytes of `fill` between the pieces (and the pieces filled with it), for tests; a third element follows then, the
+    whole allocation as the call left it, with a fourth, the pieces' offsets."""
+    L = capi.require_device()
+    n = len(streams)
+    if caps is None:
+        caps = []
+        for z in streams:
+            try:
+                caps.append(len(inflate_upto(z, 1 << 30 if len(z) > (1 << 20) else 1032 * max(len(z), 1))))
+            except capi.FfhipError:
+                caps.append(0)
+    caps = [int(c) for c in caps]
+    offs, total = [], guard
+    for c in caps:
+        offs.append(total)
+        total += c + guard
+    dout = DeviceBuffer(host=np.full(max(total, 16), fill, np.uint8))
+    bufs = [np.frombuffer(z, dtype=np.uint8) for z in streams]
+    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+    outs = (C.c_void_p * max(n, 1))(*[dout.ptr + o if c else None for o, c in zip(offs, caps)])
+    cap_arr = (C.c_size_t * max(n, 1))(*caps)
+    got = (C.c_size_t * max(n, 1))()
+    status = (C.c_int * max(n, 1))()
+    rc = L.ffhip_inflate_streams_device(ptrs, lens, n, outs, cap_arr, got, status, stream)
+    status = list(status)[:n]
+    if strict or rc not in status:
+        capi.check(rc, "ffhip_inflate_streams_device")
+    flat = dout.to_host((max(total, 16),), np.uint8)
+    outputs = [None if status[i] else flat[offs[i]:offs[i] + got[i]].tobytes() for i in range(n)]
+    return (outputs, status, flat, offs) if guard else (outputs, status)
+
+
+def png_inflate_flags(inflate):
+    """inflate= of the PNG file calls -> their png_flags"""
+    if inflate not in ("host", "device"):
+        raise ValueError(f"inflate={inflate!r}: 'host' or 'device'")
+    return capi.FFHIP_PNG_INFLATE_DEVICE if inflate == "device" else 0
+
+
+def png_inflate_last():
+    """ffhip_debug_png_inflate: (files inflated on the device, files inflated on the host, compressed bytes uploaded, milliseconds of
+    k_inflate and its copy back -- only while FFHIP_PNG_TIMES is set) of this thread's last PNG file call, all its parts"""
+    out = (C.c_double * 4)()
+    capi.check(capi.lib().ffhip_debug_png_inflate(out), "ffhip_debug_png_inflate")
+    return tuple(out)
+
+
 def png_probe(data):
     """ffhip_png_probe (host, no device): a PNG file (bytes) -> capi.PngInfo: width, height, bit_depth, color_type, interlace, has_trns,
     palette_size, n_passes, filtered_bytes, pass_rows[7], pass_row_bytes[7]"""
@@ -993,11 +1068,14 @@ def png_exif_orientation(data):
     return _exif_orientation(capi.lib().ffhip_png_exif_orientation, data)
 
 
-def png_decode_files_device(files, n_threads=8, stream=None, strict=True):
+def png_decode_files_device(files, n_threads=8, stream=None, strict=True, inflate="host"):
     """ffhip_png_decode_files_device: PNG files of any sizes and kinds (list of bytes) in one call.  Every picture gets its place in ONE
     device allocation, at a 16-byte-aligned offset with the pitch 4 x its width rounded up to 16 bytes.  Returns (infos, [host BGRA
     [h][w][4], alpha included], device buffer); with strict=False a failing file does not raise: its entry is None and a fourth element,
-    the per-file status codes, follows."""
+    the per-file status codes, follows.  inflate: 'host', or 'device' -- ffhip_png_decode_files_device_ex with FFHIP_PNG_INFLATE_DEVICE:
+    k_inflate inflates, a wave per file; the same pictures and codes."""
+    png_flags = png_inflate_flags(inflate)
+
     def probe(i, f):
         info = png_probe(f)
         return ((4 * info.width + 15) & ~15, info.height, info.width, info.height)
@@ -1005,9 +1083,11 @@ def png_decode_files_device(files, n_threads=8, stream=None, strict=True):
     infos = (capi.PngInfo * max(len(files), 1))()
 
     def call(L, ptrs, lens, n, outs, pitches, status):
+        if png_flags:
+            return L.ffhip_png_decode_files_device_ex(ptrs, lens, n, n_threads, outs, pitches, infos, status, png_flags, stream)
         return L.ffhip_png_decode_files_device(ptrs, lens, n, n_threads, outs, pitches, infos, status, stream)
 
-    images, dout, status = _files_to_pictures(files, probe, call, "ffhip_png_decode_files_device", strict)
+    images, dout, status = _files_to_pictures(files, probe, call, "ffhip_png_decode_files_device" + ("_ex" if png_flags else ""), strict)
     infos = list(infos)[:len(files)]
     return (infos, images, dout) if strict else (infos, images, dout, status)
 

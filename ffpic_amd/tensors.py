@@ -244,8 +244,9 @@ _ENTRY_TAILS = {
 
 
 def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, stack, n_threads, strict, size, antialias, apply_exif_orientation,
-                       orientation, return_orientation, reduce=1, return_reduce=False, progressive=False, flags=0, pixels="reference", alpha="drop"):
+                       orientation, return_orientation, reduce=1, return_reduce=False, progressive=False, flags=0, pixels="reference", alpha="drop", inflate="host"):
     fmt = tensor_format(dtype, layout, order, mean, std)
+    png_flags = ops.png_inflate_flags(inflate)                    # 'device': the _ex entry, which takes the alpha record or NULL
     with_alpha = _alpha_arg(alpha)[0] != "drop"                   # 'drop' goes through the entries the call took before there was the argument
     alpha_what = alpha_entry_point(codec.name, alpha, pixels) if with_alpha else None
     record = tensor_alpha(alpha, normalised=mean is not None or std is not None) if with_alpha else None
@@ -258,7 +259,7 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
     one_entry = webp_ex or codec.name in ("png", "vp8l")          # PNG and lossless WebP have ONE entry each, with the ninth's tail and flags = 0
     what = (f"ffhip_{codec.name}_decode_files_tensor" if codec.name in ("png", "vp8l") else webp_entry_point(pixels, oriented, bool(targets)) if webp_ex
             else entry_point(codec.name, oriented, den, bool(targets), progressive, flags))
-    what = alpha_what or what
+    what = "ffhip_png_decode_files_tensor_ex" if png_flags else alpha_what or what
     probe = codec.probe_progressive if progressive else codec.probe
     import torch
     tdtype = getattr(torch, _dtype_name(dtype))
@@ -311,9 +312,11 @@ def _decode_to_tensors(codec, files, *, dtype, layout, order, mean, std, roi, st
         "orient": (ints(*[(max(t, 1) if imposed else 0) if oriented else 1 for t in turns]), used_turn),
         "flags": (capi.FFHIP_WEBP_PIXELS_LIBWEBP if webp_ex else flags | (capi.FFHIP_JPEG_ACCEPT_PROGRESSIVE if progressive else 0),),
     }
-    tail = sum((tails[part] for part in (_WEBP_EX_TAIL if one_entry or with_alpha else _ENTRY_TAILS[what])), ())
-    if with_alpha:                                                # the _alpha entries: the ninth's tail, then the record
-        tail += (C.byref(record),)
+    tail = sum((tails[part] for part in (_WEBP_EX_TAIL if one_entry or with_alpha or png_flags else _ENTRY_TAILS[what])), ())
+    if with_alpha or png_flags:                                   # the _alpha entries: the ninth's tail, then the record
+        tail += (C.byref(record) if with_alpha else None,)
+    if png_flags:
+        tail += (png_flags,)
     rc = getattr(L, what)(ptrs, lens, n, n_threads, C.byref(fmt), outs, rects, *tail, None, status, torch.cuda.current_stream().cuda_stream)
     if oriented:
         turns = list(used_turn)[:n]
@@ -429,7 +432,7 @@ def decode_webp_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=No
 
 def decode_png_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=None, std=None, roi=None, stack=False, n_threads=8,
                           strict=True, size=None, antialias=True, apply_exif_orientation=False, orientation=None, return_orientation=False,
-                          alpha="drop"):
+                          alpha="drop", inflate="host"):
     """ffhip_png_decode_files_tensor: PNG files of every colour type and bit depth, interlaced or not; arguments and result as
     decode_webp_to_tensors (the orientation tag is read from the file's eXIf chunk).  A file's display size is its width x height.
       alpha    'drop': three channels, alpha is dropped as PIL's convert("RGB") drops it -- the colour stored under transparent pixels
@@ -438,8 +441,10 @@ def decode_png_to_tensors(files, dtype=None, layout="CHW", order="RGB", mean=Non
                composited over that background colour (Image.alpha_composite).  With size the resize filters premultiplied samples, so
                the colour under transparent pixels never bleeds into the edges; 'straight' un-premultiplies behind it.  Integers only
                (include/ffpic_hip.h, "alpha into the tensors").  The alpha channel of a float tensor is alpha * float32(1 / 255) when
-               mean or std is given, the byte value otherwise (ffhip_png_decode_files_tensor_alpha).  Anything else: ValueError"""
-    return _decode_to_tensors(_PNG, files, alpha=alpha, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
+               mean or std is given, the byte value otherwise (ffhip_png_decode_files_tensor_alpha).  Anything else: ValueError
+      inflate  'host' (the default): the host threads inflate.  'device': k_inflate does, a wave per file
+               (ffhip_png_decode_files_tensor_ex with FFHIP_PNG_INFLATE_DEVICE); the tensors are the same bit for bit"""
+    return _decode_to_tensors(_PNG, files, alpha=alpha, inflate=inflate, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)
 

@@ -1430,6 +1430,40 @@ int ffhip_debug_png_last(int out[2]);
  * over all its levels, [3] k_png_expand. */
 int ffhip_debug_png_times(double out[4]);
 
+/* ---- PNG, inflate on the device (ffhip_inflate_body.h, ffhip_inflate_model.c, ffhip_inflate_gpu.hip) ----
+ * Opt-in: every default keeps its bytes, its stages and its timings.  k_inflate gives one wave to one zlib stream: the serial decode is
+ * wave-uniform, the wave stores a run of literals or 64 bytes of a match at a time, and the output itself is the window. */
+/* n zlib streams in host memory into n DEVICE buffers, in one launch: the rule, stream for stream, is ffhip_inflate's.  d_dst[i] takes
+ * cap[i] bytes (cap[i] == 0 with a NULL d_dst[i] is allowed); out_len[i] and status[i] receive what ffhip_inflate would have given, and
+ * the return value is the first non-zero status[i].  Nothing beyond out_len[i] bytes of a destination is written; the bytes of a
+ * refused stream's destination are unspecified inside cap[i] and untouched outside it.  FFHIP_EINVAL for n < 0, a NULL array, a NULL
+ * src[i] with len[i] > 0 or a NULL d_dst[i] with cap[i] > 0; then FFHIP_ENODEV; both before the first allocation.  n == 0 is FFHIP_OK.
+ * Uploads, launches, reads the verdicts back and synchronises `stream`; the staging is the PNG file call's (one call of either at a
+ * time per stream). */
+int ffhip_inflate_streams_device(const uint8_t *const *src, const size_t *len, int n, uint8_t *const *d_dst, const size_t *cap,
+                                 size_t *out_len, int *status, void *stream);
+/* png_flags of the two calls below.  FFHIP_PNG_INFLATE_DEVICE: the host threads walk the chunks and check the CRCs as ever, then copy
+ * every file's IDAT payloads, joined, into the pinned staging instead of inflating them; one upload carries streams, palettes and
+ * records; k_inflate writes the filtered pictures where the host path's upload would have put them and checks every row's filter byte;
+ * one copy back and one synchronisation bring the verdicts; k_png_unfilter and k_png_expand run on the files that are still clean.  A
+ * palette file whose palette is shorter than its depth's range is inflated by the host threads as ever (its indices are checked on
+ * unfiltered rows) and its filtered bytes go up with the rest.  Per-file codes, pictures, "a refused file writes nothing", the cut into
+ * parts (the budget sums filtered bytes) and ffhip_debug_png_last are those of the host path.  The switch FFHIP_PNG_INFLATE_GPU=1 sets
+ * the bit for every PNG file entry, the ones above included. */
+#define FFHIP_PNG_INFLATE_DEVICE 0x1u
+/* ffhip_png_decode_files_device with png_flags: 0 is that call byte for byte; unknown bits are FFHIP_EINVAL. */
+int ffhip_png_decode_files_device_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, uint8_t *const *d_bgra,
+                                     const int64_t *pitch, ffhip_png_info *info_out, int *status, unsigned png_flags, void *stream);
+/* ffhip_png_decode_files_tensor_alpha with png_flags (alpha == NULL: the three-channel call); flags must be 0 as there. */
+int ffhip_png_decode_files_tensor_ex(const uint8_t *const *files, const size_t *lens, int n, int n_threads, const ffhip_tensor_format *fmt,
+                                     const ffhip_tensor_out *outs, const ffhip_rect *roi, const ffhip_size *out_size, int filter,
+                                     const int *orient, int *orient_out, unsigned flags, const ffhip_tensor_alpha *alpha,
+                                     unsigned png_flags, ffhip_png_info *info_out, int *status, void *stream);
+/* Diagnostics, all parts of the calling thread's last PNG file call: [0] files inflated on the device, [1] files inflated on the
+ * host, [2] compressed bytes uploaded, [3] milliseconds of k_inflate plus the copy back, measured by events only while FFHIP_PNG_TIMES is
+ * set (0 otherwise) and not part of ffhip_debug_png_times' [1] .. [3]. */
+int ffhip_debug_png_inflate(double out[4]);
+
 /* ---- lossless WebP (ffhip_vp8l.c, ffhip_vp8l_body.h, ffhip_vp8l_gpu.hip) ----
  * The reference has a stub here, so the pixel rule is libwebp's: the BGRA picture is width x height of the VP8L header, sample for sample
  * what PIL's Image.open(f).convert("RGBA") gives (libwebp 1.6.0).  Every line below was held against it (tests/test_vp8l_spec.py):
