@@ -49,6 +49,8 @@ EXPORTS = [
     "ffhip_bgra_to_tensor_items_alpha", "ffhip_bgra_resize_items_premultiplied",
     "ffhip_png_decode_files_tensor_alpha", "ffhip_vp8l_decode_files_tensor_alpha", "ffhip_webp_decode_files_tensor_alpha",
     "ffhip_inflate_streams_device", "ffhip_png_decode_files_device_ex", "ffhip_png_decode_files_tensor_ex", "ffhip_debug_png_inflate",
+    "ffhip_jpeg_encode_tables", "ffhip_jpeg_encode_block", "ffhip_jpeg_encode_header", "ffhip_jpeg_encode_bound", "ffhip_jpeg_encode_picture",
+    "ffhip_jpeg_fdct_items", "ffhip_jpeg_huff_encode_items", "ffhip_jpeg_encode_items",
 ]
 
 
@@ -59,6 +61,9 @@ FFHIP_WEBP_PIXELS_LIBWEBP = 0x10
 FFHIP_WEBP_ALPHA = 0x20
 FFHIP_PNG_INFLATE_DEVICE = 0x1
 FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1002, -1003
+FFHIP_JPEG_ENC_444, FFHIP_JPEG_ENC_422, FFHIP_JPEG_ENC_420, FFHIP_JPEG_ENC_GREY = 0, 1, 2, 3
+FFHIP_EJPEG_NOSPACE, FFHIP_EJPEG_RANGE = -1101, -1102
+FFHIP_JPEG_ENC_HEADER_MAX = 640
 
 
 class FfhipError(RuntimeError):
@@ -212,6 +217,38 @@ class OrientItem(C.Structure):
     """ffhip_orient_item: one picture of an ffhip_bgra_orient_items call (device pointers; pitches in bytes; the STORED rectangle)"""
     _fields_ = [("d_src", C.c_void_p), ("src_pitch", C.c_int64), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32),
                 ("height", C.c_int32), ("d_dst", C.c_void_p), ("dst_pitch", C.c_int64), ("orientation", C.c_int32)]
+
+
+class JpegSource(C.Structure):
+    """ffhip_jpeg_source: a uint8 picture by byte strides (channels 3 or 1), or a BGRA picture (channels 4)"""
+    _fields_ = [("pixels", C.c_void_p), ("row_stride", C.c_int64), ("pixel_stride", C.c_int64), ("chan", C.c_int64 * 3),
+                ("channels", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32)]
+
+
+class JpegFdctItem(C.Structure):
+    """ffhip_jpeg_fdct_item (device pointers)"""
+    _fields_ = [("src", JpegSource), ("layout", C.c_int32), ("quality", C.c_int32), ("d_coef_y", C.c_void_p), ("d_coef_u", C.c_void_p),
+                ("d_coef_v", C.c_void_p)]
+
+
+class JpegHuffItem(C.Structure):
+    """ffhip_jpeg_huff_item (device pointers)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("layout", C.c_int32), ("quality", C.c_int32), ("restart", C.c_int32),
+                ("d_coef_y", C.c_void_p), ("d_coef_u", C.c_void_p), ("d_coef_v", C.c_void_p), ("d_out", C.c_void_p), ("cap", C.c_size_t)]
+
+
+class JpegEncodeItem(C.Structure):
+    """ffhip_jpeg_encode_item (device pointers)"""
+    _fields_ = [("src", JpegSource), ("layout", C.c_int32), ("quality", C.c_int32), ("restart", C.c_int32), ("reserved", C.c_int32),
+                ("d_out", C.c_void_p), ("cap", C.c_size_t)]
+
+
+def jpeg_source(pixels, width, height, row_stride, pixel_stride, chan=(0, 0, 0), channels=3):
+    s = JpegSource()
+    s.pixels, s.width, s.height, s.row_stride, s.pixel_stride, s.channels = pixels, width, height, row_stride, pixel_stride, channels
+    for k in range(3):
+        s.chan[k] = chan[k] if k < len(chan) else 0
+    return s
 
 
 def jpeg_geom(mcu_cols, mcu_rows, ncomp=3, h=2, v=2, qt_id=(0, 1, 1)):
@@ -433,6 +470,15 @@ def lib():
     L.ffhip_png_decode_files_tensor_ex.argtypes = [vp, vp, ci, ci, C.POINTER(TensorFormat), C.POINTER(TensorOut), C.POINTER(Rect), C.POINTER(Size), ci,
                                                    C.POINTER(ci), C.POINTER(ci), C.c_uint, C.POINTER(TensorAlpha), C.c_uint, C.POINTER(PngInfo), vp, vp]
     L.ffhip_debug_png_inflate.argtypes = [C.POINTER(C.c_double)]
+    L.ffhip_jpeg_encode_tables.argtypes = [ci, vp]
+    L.ffhip_jpeg_encode_block.argtypes = [vp, vp, vp]
+    L.ffhip_jpeg_encode_header.argtypes = [ci, ci, ci, ci, ci, vp, sz, C.POINTER(sz)]
+    L.ffhip_jpeg_encode_bound.argtypes = [ci, ci, ci, ci]
+    L.ffhip_jpeg_encode_bound.restype = sz
+    L.ffhip_jpeg_encode_picture.argtypes = [C.POINTER(JpegSource), ci, ci, ci, vp, sz, C.POINTER(sz)]
+    L.ffhip_jpeg_fdct_items.argtypes = [C.POINTER(JpegFdctItem), ci, vp]
+    L.ffhip_jpeg_huff_encode_items.argtypes = [C.POINTER(JpegHuffItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
+    L.ffhip_jpeg_encode_items.argtypes = [C.POINTER(JpegEncodeItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
     for name in ("ffhip_inflate_upto", "ffhip_inflate_model"):    # exported, not in the public header (csrc/ffhip_png_internal.h)
         getattr(L, name).argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci]
     L.ffhip_inflate_model_mode.argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci, ci]

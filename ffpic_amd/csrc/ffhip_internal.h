@@ -125,6 +125,7 @@ enum FfhipScratchKind {
     SCRATCH_PNG = 110,           /* .. + 2: ffhip_png_decode_files_device: a part's filtered pictures and palettes (and their pinned copy); k_png_unfilter's records; k_png_expand's records and per-workgroup table (pinned records).  With FFHIP_PNG_INFLATE_DEVICE slot + 0 holds, behind the filtered pictures, the palettes, the host-inflated files' filtered bytes, the zlib streams and k_inflate's records (their pinned copy: everything but the pictures); ffhip_inflate_streams_device: the streams and records in slot + 0 */
     SCRATCH_VP8L = 113,          /* .. + 2: ffhip_vp8l_decode_files_device: a part's residual images, block images and palettes (and their pinned copy); k_vp8l_predict's records; k_vp8l_finish's records and per-workgroup table (pinned records) */
     SCRATCH_WEBP_ALPHA = 116,    /* .. + 5: FFHIP_WEBP_ALPHA: a part's raw planes and lossless planes' residual images (and their pinned copy); k_vp8l_predict's records; k_vp8l_finish's records and table; the scratch pictures and unfiltered planes; k_webp_alpha_unfilter's records; k_webp_alpha_merge's records and table (pinned records) */
+    SCRATCH_JPEG_ENC = 130,      /* .. + 4: the JPEG encoder.  + 0 ffhip_jpeg_fdct_items' records, per-workgroup tables and sample planes (pinned records); + 1 ffhip_jpeg_huff_encode_items' records, code tables, per-workgroup table, positions and results (pinned records); + 2 its stream records, per-chunk table, FF counts, unstuffed streams and masks (pinned records); + 3 its results on the host (pinned only); + 4 ffhip_jpeg_encode_items: a part's coefficient planes */
     SCRATCH_HUFF_PROG = 90,      /* ffhip_jpeg_progressive_batch_gpu: staged scans, tables, records and work lists (and their pinned copy) */
 };
 

@@ -206,6 +206,8 @@ extern "C" const char *ffhip_strerror(int code)
     case FFHIP_EWEBP_LOSSLESS: return "lossless WebP (VP8L) is not decoded by this call (the ffhip_vp8l_* calls decode it)";
     case FFHIP_EWEBP_ANIMATION: return "animated WebP is not decoded";
     case FFHIP_EWEBP_INTER_FRAME: return "the VP8 frame is not a key frame";
+    case FFHIP_EJPEG_NOSPACE: return "the JPEG file does not fit the output's cap (the length is the size it needs)";
+    case FFHIP_EJPEG_RANGE: return "a coefficient Annex K's Huffman tables cannot code (AC magnitude over 1023 or DC difference beyond +-2047)";
     default: return "unknown error";
     }
 }

@@ -1166,3 +1166,101 @@ def vp8l_times():
     out = (C.c_double * 4)()
     capi.check(capi.lib().ffhip_debug_vp8l_times(out), "ffhip_debug_vp8l_times")
     return tuple(out)
+
+
+# ---- JPEG encoding (include/ffpic_hip.h "JPEG encoding") ----
+JPEG_ENC_LAYOUTS = {"4:4:4": capi.FFHIP_JPEG_ENC_444, "4:2:2": capi.FFHIP_JPEG_ENC_422, "4:2:0": capi.FFHIP_JPEG_ENC_420, "grey": capi.FFHIP_JPEG_ENC_GREY}
+
+
+def jpeg_encode_layout(layout):
+    """a layout's FFHIP_JPEG_ENC_* value from its name ('4:4:4', '4:2:2', '4:2:0', 'grey') or the value itself"""
+    if isinstance(layout, str):
+        if layout not in JPEG_ENC_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(JPEG_ENC_LAYOUTS)}, got {layout!r}")
+        return JPEG_ENC_LAYOUTS[layout]
+    return int(layout)
+
+
+def jpeg_encode_tables(quality):
+    """ffhip_jpeg_encode_tables: libjpeg's quantiser tables of a quality -> uint16 [2][64] natural order (luma, chroma).  Needs no device."""
+    out = np.zeros((2, 64), np.uint16)
+    capi.check(capi.lib().ffhip_jpeg_encode_tables(int(quality), _vp(out)), "ffhip_jpeg_encode_tables")
+    return out
+
+
+def jpeg_encode_block(samples, quant):
+    """ffhip_jpeg_encode_block: the quantised coefficients (int16 [64], natural order) of 64 samples: the islow forward DCT and libjpeg's
+    quantiser.  Needs no device."""
+    s = np.ascontiguousarray(samples, np.uint8).reshape(64)
+    q = np.ascontiguousarray(quant, np.uint16).reshape(64)
+    out = np.zeros(64, np.int16)
+    capi.check(capi.lib().ffhip_jpeg_encode_block(_vp(s), _vp(q), _vp(out)), "ffhip_jpeg_encode_block")
+    return out
+
+
+def jpeg_encode_header(width, height, layout, quality, restart=0):
+    """ffhip_jpeg_encode_header: the file's bytes in front of the scan data.  Needs no device."""
+    out = np.zeros(capi.FFHIP_JPEG_ENC_HEADER_MAX, np.uint8)
+    n = C.c_size_t()
+    capi.check(capi.lib().ffhip_jpeg_encode_header(width, height, jpeg_encode_layout(layout), quality, restart, _vp(out), out.size, C.byref(n)),
+               "ffhip_jpeg_encode_header")
+    return out[:n.value].tobytes()
+
+
+def jpeg_encode_bound(width, height, layout, restart=0):
+    """ffhip_jpeg_encode_bound: a certain bound on the file's size (0: bad arguments).  Needs no device."""
+    return int(capi.lib().ffhip_jpeg_encode_bound(width, height, jpeg_encode_layout(layout), restart))
+
+
+def jpeg_host_source(pixels):
+    """capi.JpegSource of a host array uint8 [H][W][3] (R, G, B) or [H][W] (grey), whatever its strides; keep the array alive"""
+    if pixels.dtype != np.uint8 or pixels.ndim not in (2, 3) or (pixels.ndim == 3 and pixels.shape[2] != 3):
+        raise ValueError("pixels must be uint8 [H][W][3] or [H][W]")
+    st = pixels.strides
+    chan = (0, st[2], 2 * st[2]) if pixels.ndim == 3 else (0,)
+    return capi.jpeg_source(pixels.ctypes.data, pixels.shape[1], pixels.shape[0], st[0], st[1], chan, len(chan))
+
+
+def jpeg_encode_picture(pixels, layout, quality=75, restart=0, cap=None):
+    """ffhip_jpeg_encode_picture: host pixels (uint8 [H][W][3] RGB, or [H][W] for 'grey') to the file's bytes, the CPU model of
+    jpeg_encode_items.  cap: the output's size (the bound when None); -> bytes, or with cap given (rc, length, the cap bytes)."""
+    src = jpeg_host_source(pixels)
+    size = jpeg_encode_bound(src.width, src.height, layout, restart) if cap is None else int(cap)
+    out = np.zeros(max(size, 1), np.uint8)
+    n = C.c_size_t()
+    rc = capi.lib().ffhip_jpeg_encode_picture(C.byref(src), jpeg_encode_layout(layout), quality, restart, _vp(out), size, C.byref(n))
+    if cap is not None:
+        return rc, n.value, out[:size].tobytes()
+    capi.check(rc, "ffhip_jpeg_encode_picture")
+    return out[:n.value].tobytes()
+
+
+def jpeg_fdct_items(items, stream=None):
+    """ffhip_jpeg_fdct_items: `items` a list of capi.JpegFdctItem (device pointers); pixels to quantised coefficient planes in MCU order, pictures
+    of any sizes, layouts and qualities in one pair of launches.  Only enqueues on `stream`."""
+    n = len(items)
+    arr = (capi.JpegFdctItem * max(n, 1))(*items)
+    capi.check(capi.lib().ffhip_jpeg_fdct_items(arr, n, stream), "ffhip_jpeg_fdct_items")
+
+
+def _lengths_call(entry, kind, items, stream, strict):
+    n = len(items)
+    arr = (kind * max(n, 1))(*items)
+    lens, status = (C.c_size_t * max(n, 1))(), (C.c_int * max(n, 1))()
+    rc = getattr(capi.lib(), entry)(arr, n, lens, status, stream)
+    status = list(status)[:n]
+    if strict or (rc != 0 and rc not in status):
+        capi.check(rc, entry)
+    return list(lens)[:n], status
+
+
+def jpeg_huff_encode_items(items, stream=None, strict=True):
+    """ffhip_jpeg_huff_encode_items: `items` a list of capi.JpegHuffItem (device coefficient planes in MCU order) -> ([file length], [status]);
+    the files are in the items' d_out.  Synchronises `stream` twice."""
+    return _lengths_call("ffhip_jpeg_huff_encode_items", capi.JpegHuffItem, items, stream, strict)
+
+
+def jpeg_encode_items(items, stream=None, strict=True):
+    """ffhip_jpeg_encode_items: `items` a list of capi.JpegEncodeItem (device pictures) -> ([file length], [status]); the files are in the
+    items' d_out.  With strict=False a file that does not fit its cap is its status (FFHIP_EJPEG_NOSPACE) and its length the size it needs."""
+    return _lengths_call("ffhip_jpeg_encode_items", capi.JpegEncodeItem, items, stream, strict)

@@ -458,3 +458,78 @@ def decode_webp_lossless_to_tensors(files, dtype=None, layout="CHW", order="RGB"
     return _decode_to_tensors(_VP8L, files, alpha=alpha, dtype=dtype, layout=layout, order=order, mean=mean, std=std, roi=roi, stack=stack, n_threads=n_threads,
                               strict=strict, size=size, antialias=antialias, apply_exif_orientation=apply_exif_orientation, orientation=orientation,
                               return_orientation=return_orientation)
+
+
+def jpeg_source_of(t):
+    """capi.JpegSource of a uint8 device tensor [3,H,W], [1,H,W] or [H,W,3], whatever its strides -> (source, grey).  A first dimension of 3
+    or 1 is ALWAYS read as channels first, as torchvision's encode_jpeg reads it: an [H,W,3] picture that is 1 or 3 rows high has to be passed
+    as t.permute(2, 0, 1)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 3:
+        raise ValueError("encode_jpeg takes uint8 device tensors [3,H,W], [1,H,W] or [H,W,3]")
+    if t.shape[0] in (1, 3):
+        c, (height, width), (plane, row, pixel) = t.shape[0], t.shape[1:], t.stride()
+    elif t.shape[2] == 3:
+        c, (height, width), (row, pixel, plane) = 3, t.shape[:2], t.stride()
+    else:
+        raise ValueError(f"encode_jpeg takes [3,H,W], [1,H,W] or [H,W,3], got {tuple(t.shape)}")
+    if width < 1 or height < 1:
+        raise ValueError(f"encode_jpeg: an empty picture {tuple(t.shape)}")
+    return capi.jpeg_source(t.data_ptr(), width, height, row, pixel, tuple(k * plane for k in range(c)), c), c == 1
+
+
+def encode_jpeg(pictures, quality=75, subsampling="4:2:0", restart_blocks=0, to_host=False):
+    """Device pictures to baseline JPEG files, byte for byte what libjpeg (PIL, torchvision) writes at this quality: a list of uint8 device
+    tensors [3,H,W] (R, G, B), [1,H,W] (grey) or [H,W,3] (a first dimension of 3 or 1 is always channels: pass an [H,W,3] picture 1 or 3 rows high as t.permute(2, 0, 1)), of any sizes and strides, in ONE ffhip_jpeg_encode_items call on the current stream
+    -> a list of 1-D uint8 device tensors (views of one allocation), or of bytes with to_host=True.  quality, subsampling ('4:4:4', '4:2:2',
+    '4:2:0'; a grey picture is written as one component) and restart_blocks (MCUs per restart interval, 0: none) are one value or one per
+    picture.  The outputs start at half the pixels' size; the files that need more (the call says how much) go through a second call."""
+    import torch
+    single = isinstance(pictures, torch.Tensor)
+    pictures = [pictures] if single else list(pictures)
+    n = len(pictures)
+
+    def each(value, name):
+        values = list(value) if isinstance(value, (list, tuple)) else [value] * n
+        if len(values) != n:
+            raise ValueError(f"{name}: {len(values)} values for {n} pictures")
+        return values
+    qualities, layouts, restarts = each(quality, "quality"), each(subsampling, "subsampling"), [int(r) for r in each(restart_blocks, "restart_blocks")]
+    sources = [jpeg_source_of(t) for t in pictures]                       # argument errors come before any device use
+    layouts = [capi.FFHIP_JPEG_ENC_GREY if grey else ops.jpeg_encode_layout(l) for (_, grey), l in zip(sources, layouts)]
+    for (_, grey), l in zip(sources, layouts):
+        if not grey and l == capi.FFHIP_JPEG_ENC_GREY:
+            raise ValueError("subsampling 'grey' needs a [1,H,W] picture")
+    if n == 0:
+        return []
+    dev = torch.cuda.current_device()
+    capi.require_device(dev)
+    device = torch.device("cuda", dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    files, todo = [None] * n, list(range(n))
+    caps = [((1024 + s.width * s.height * s.channels // 2) + 255) & ~255 for s, _ in sources]
+    for _ in range(2):
+        offs = np.concatenate([[0], np.cumsum([caps[i] for i in todo])]).astype(np.int64)
+        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
+        items = []
+        for k, i in enumerate(todo):
+            it = capi.JpegEncodeItem()
+            it.src, it.layout, it.quality, it.restart = sources[i][0], layouts[i], int(qualities[i]), restarts[i]
+            it.d_out, it.cap = buf.data_ptr() + int(offs[k]), caps[i]
+            items.append(it)
+        lens, status = ops.jpeg_encode_items(items, stream, strict=False)
+        again = []
+        for k, i in enumerate(todo):
+            if status[k] == 0:
+                files[i] = buf[int(offs[k]):int(offs[k]) + lens[k]]
+            elif status[k] == capi.FFHIP_EJPEG_NOSPACE:
+                caps[i] = (lens[k] + 255) & ~255
+                again.append(i)
+            else:
+                capi.check(status[k], "ffhip_jpeg_encode_items")
+        todo = again
+        if not todo:
+            break
+    if to_host:
+        files = [bytes(f.cpu().numpy()) for f in files]
+    return files[0] if single else files

@@ -1542,6 +1542,117 @@ int ffhip_debug_vp8l_last(int out[3]);
  * all its levels, [3] k_vp8l_finish. */
 int ffhip_debug_vp8l_times(double out[4]);
 
+/* ---- JPEG encoding (ffhip_jpeg_enc.c, ffhip_jpeg_enc_body.h, ffhip_jpeg_enc_gpu.hip) ----
+ * Device pictures to baseline JPEG files, byte for byte what libjpeg writes after jpeg_set_quality(q, force_baseline) with its defaults
+ * (islow forward DCT, Annex K Huffman tables, no optimisation) -- so PIL's Image.save and torchvision's encode_jpeg.  THE RULE, integers only:
+ *  1. Quantiser tables.  q clamped to 1..100; s = 5000 / q for q < 50, else 200 - 2 q; t = clamp((std s + 50) / 100, 1, 255) over Annex K's
+ *     luma and chroma tables (T.81 K.1, K.2).  Slot 0 is luma, slot 1 chroma.
+ *  2. Colour.  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16;
+ *     Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.  Grey sources skip this step.
+ *  3. Edges and chroma -- NOT symmetric.  Horizontally a full-resolution sample beyond the last column is the last column, out to the MCU
+ *     width, before downsampling.  Vertically full-resolution rows are replicated only up to a multiple of v; the plane is then downsampled,
+ *     and the chroma rows still missing up to the MCU height are copies of the last DOWNSAMPLED row.  h2v2: (a + b + c + d + bias) >> 2 with
+ *     bias 1, 2, 1, 2, .. along an output row, from 1 in every row; h2v1: (a + b + bias) >> 1 with bias 0, 1, 0, 1, ...
+ *  4. Luma blocks.  Blocks bx < ceil(W / 8), by < ceil(H / 8) are real, computed from the edge-replicated plane.  The other luma blocks of a
+ *     last MCU are dummy blocks: all AC coefficients 0, the DC the quantised DC of the previous block in the MCU's block order (after that
+ *     block's own substitution).  Chroma is padded as samples by step 3 and has no dummy blocks.
+ *  5. Forward DCT, jfdctint.c: samples minus 128; the row pass keeps PASS1_BITS = 2 (outputs 0 and 4 shifted left by 2, the others
+ *     DESCALE(.., 11)); the column pass gives outputs 0 and 4 as DESCALE(.., 2), the others DESCALE(.., 15); DESCALE(x, n) =
+ *     (x + (1 << (n - 1))) >> n; constants 2446, 3196, 4433, 6270, 7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172; 32-bit arithmetic.
+ *  6. Quantise: with d = 8 t, c = sign(x) ((|x| + (d >> 1)) / d).
+ *  7. Entropy coding, T.81 F.1.2 with Annex K's four tables: a DC prediction per component, reset at every restart interval; `restart`
+ *     counts MCUs (0: none); an interval's last byte is padded with ones; markers FFD0 + (k & 7); 00 stuffed behind every FF of entropy data.
+ *  8. File: SOI; APP0 "JFIF\0" 1.1, units 0, density 1 x 1, no thumbnail; one DQT segment per table; SOF0 with component ids 1, 2, 3; four
+ *     DHT segments DC0, AC0, DC1, AC1 (grey: one DQT, two DHT); DRI if restart != 0; SOS; the scan; EOI.
+ * Layouts: 4:4:4, 4:2:2 (h2v1), 4:2:0 (h2v2) and grey; sizes 1..65535; restart 0..65535.  Anything else is FFHIP_EINVAL.
+ *
+ * A source picture is uint8 samples addressed by byte strides: sample c of pixel (x, y) at pixels + y row_stride + x pixel_stride + chan[c],
+ * chan = the offsets of R, G, B (channels = 3: CHW, HWC, RGB and BGR tensors are all this one form) or of the one grey sample (channels =
+ * 1, the grey layout's only source, and that layout takes no other); or channels = 4: a BGRA picture as the decoders leave it (pixel_stride
+ * 4, row_stride the pitch, a multiple of 4, pixels 4-byte aligned, chan ignored), read a pixel a load.  Strides may be negative. */
+#define FFHIP_JPEG_ENC_444 0
+#define FFHIP_JPEG_ENC_422 1
+#define FFHIP_JPEG_ENC_420 2
+#define FFHIP_JPEG_ENC_GREY 3
+#define FFHIP_EJPEG_NOSPACE (-1101) /* the file does not fit cap: len is the size it needs, nothing at or beyond cap was written */
+#define FFHIP_EJPEG_RANGE (-1102)   /* a coefficient Annex K's tables cannot code: an AC magnitude over 1023 or a DC difference beyond +-2047 */
+typedef struct ffhip_jpeg_source {
+    const uint8_t *pixels;
+    int64_t row_stride, pixel_stride; /* bytes */
+    int64_t chan[3];
+    int32_t channels;                 /* 3, 1, or 4 (BGRA) */
+    int32_t width, height;
+    int32_t reserved;                 /* 0 */
+} ffhip_jpeg_source;
+/* Host only, no device needed; what the device calls are held to:
+ *   ffhip_jpeg_encode_tables   step 1: quant[2][64], natural order
+ *   ffhip_jpeg_encode_block    steps 5 and 6 on 64 samples, natural order in and out
+ *   ffhip_jpeg_encode_header   step 8 up to and including SOS: *len = its size (at most FFHIP_JPEG_ENC_HEADER_MAX), written if it fits cap
+ *                              (else FFHIP_EJPEG_NOSPACE and nothing written)
+ *   ffhip_jpeg_encode_bound    a CERTAIN bound on the file's size, 0 for bad arguments.  A block takes at most 1660 bits: a DC code of up
+ *                              to 11 bits (Annex K's longest, chroma's size 11) and 11 bits of magnitude, and 63 AC coefficients of a
+ *                              16-bit code and 10 bits of magnitude each (a ZRL only ever stands for coefficients that take nothing).  An
+ *                              interval of b blocks is at most ceil(1660 b / 8) bytes, padding included; stuffing at most doubles them (every
+ *                              byte FF); each interval ends in a two-byte marker (RSTn, or EOI).  So
+ *                                bound = header + sum over intervals (2 ceil(1660 b / 8) + 2)
+ *   ffhip_jpeg_encode_picture  a whole picture from HOST pixels to the file's bytes, through the same bodies as the kernels.  *len = the
+ *                              file's size; FFHIP_EJPEG_NOSPACE when it exceeds cap (no byte at or beyond out + cap is written; what lies
+ *                              below is unspecified then). */
+#define FFHIP_JPEG_ENC_HEADER_MAX 640
+int ffhip_jpeg_encode_tables(int quality, uint16_t *quant);
+int ffhip_jpeg_encode_block(const uint8_t *samples, const uint16_t *quant, int16_t *coef);
+int ffhip_jpeg_encode_header(int width, int height, int layout, int quality, int restart, uint8_t *out, size_t cap, size_t *len);
+size_t ffhip_jpeg_encode_bound(int width, int height, int layout, int restart);
+int ffhip_jpeg_encode_picture(const ffhip_jpeg_source *src, int layout, int quality, int restart, uint8_t *out, size_t cap, size_t *len);
+/* On the device, in three calls.  `items` are HOST arrays, read before the call returns; every check is made before anything is enqueued
+ * (FFHIP_EINVAL, on a machine without a device too; FFHIP_ENODEV there for good arguments); records, tables, sample planes and streams are
+ * library scratch of the stream.
+ *
+ * ffhip_jpeg_fdct_items: pixels to quantised coefficients (steps 1 to 6), the other direction of ffhip_jpeg_recon_items_libjpeg.  Only
+ *   enqueues: k_jpeg_color_downsample (a thread takes the 8 h x v pixels over 8 chroma samples of a row: the source to padded uint8 sample
+ *   planes), then k_jpeg_fdct_islow (a thread takes one block, dummy blocks included, both passes in registers).  d_coef_*: int16, 64 a block,
+ *   natural order, blocks in MCU order -- the plane layout ffhip_jpeg_recon_items reads, for the geometry mcu_cols = ceil(W / 8 h),
+ *   mcu_rows = ceil(H / 8 v); 16-byte aligned; d_coef_u and d_coef_v NULL for grey.  At most 2^31 - 1 blocks a picture.  The source is
+ *   stream-ordered, like the planes. */
+typedef struct ffhip_jpeg_fdct_item {
+    ffhip_jpeg_source src; /* pixels: device */
+    int32_t layout, quality;
+    int16_t *d_coef_y, *d_coef_u, *d_coef_v;
+} ffhip_jpeg_fdct_item;
+int ffhip_jpeg_fdct_items(const ffhip_jpeg_fdct_item *items, int n, void *stream);
+/* ffhip_jpeg_huff_encode_items: coefficient planes in that layout -- from the call above or from anywhere else -- to whole files (steps 7
+ *   and 8; quality only names the header's tables).  d_out[0, cap) receives the file; len_out[i] (host) its size; status[i] (host) FFHIP_OK,
+ *   FFHIP_EJPEG_RANGE (the file is unspecified, within cap) or FFHIP_EJPEG_NOSPACE (len_out[i] is the size the file needs; no byte at or
+ *   beyond cap is written).  An item's verdict leaves its neighbours alone.  Returns the first item's code that is not FFHIP_OK, else
+ *   FFHIP_OK.  Kernels: a thread per block counts its bits (its DC predecessor is read from the planes: nothing is carried); a workgroup per
+ *   picture turns the counts into positions with a prefix scan in a loop of its own; a thread per block writes its bits into the zeroed
+ *   unstuffed stream (first and last word by atomicOr, the words between by plain stores; an interval's last block adds the padding and the
+ *   marker); a workgroup per KiB of that stream counts the FF bytes to stuff; a workgroup per picture sums those; a last kernel copies
+ *   header and stuffed stream into d_out.  No kernel waits for another workgroup; every loop runs to a bound known at its entry.
+ *   LIMIT: a picture whose ffhip_jpeg_encode_bound reaches 2^32 bytes (some 10.3 M blocks: 220 Mpixel at 4:4:4, 440 at 4:2:0) is FFHIP_EINVAL
+ *   here and in ffhip_jpeg_encode_items, though its sizes lie in 1..65535: chunk indices and FF counts are held in 32 bits.
+ *   The host entries have no such limit.
+ *   The call SYNCHRONISES the stream twice: once behind the positions, to size the streams' scratch by the counted totals and not by the
+ *   bound, and once at its end, for len_out and status. */
+typedef struct ffhip_jpeg_huff_item {
+    int32_t width, height, layout, quality, restart;
+    const int16_t *d_coef_y, *d_coef_u, *d_coef_v;
+    uint8_t *d_out;
+    size_t cap;
+} ffhip_jpeg_huff_item;
+int ffhip_jpeg_huff_encode_items(const ffhip_jpeg_huff_item *items, int n, size_t *len_out, int *status, void *stream);
+/* ffhip_jpeg_encode_items: the file call -- pictures of any sizes, layouts, qualities and restart intervals in one batch.  The batch is cut
+ *   into parts by a byte budget over the coefficient planes (1 GiB; a picture beyond it is a part of its own); a part is one
+ *   ffhip_jpeg_fdct_items into library scratch and one ffhip_jpeg_huff_encode_items, so the call synchronises the stream twice a part.
+ *   len_out, status, the return value and the LIMIT on a picture's bound as above. */
+typedef struct ffhip_jpeg_encode_item {
+    ffhip_jpeg_source src; /* pixels: device */
+    int32_t layout, quality, restart, reserved;
+    uint8_t *d_out;
+    size_t cap;
+} ffhip_jpeg_encode_item;
+int ffhip_jpeg_encode_items(const ffhip_jpeg_encode_item *items, int n, size_t *len_out, int *status, void *stream);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
