@@ -3,7 +3,7 @@
  *  and the BMP sink behind it (row f2).  Plain C11, no HIP.
  *
  * Stands where these pieces of the reference stand (paths in the ffpic tree):
- *   marker loop, SOF/DQT/DHT/DRI/SOS parsing   format/jpg.c:78-105, 640-655, 771-855
+ *   SOS parsing (the marker loop and the other segments: ffhip_jpeg_front.c)   format/jpg.c:640-655
  *   read_compressed_scan (FF00 unstuffing, RSTn) format/jpg.c:588-637
  *   decode_data_unit (baseline branch)         format/jpg.c:255-415
  *   huffman_decode_symbol                      coding/huffman.c:92-222
@@ -28,42 +28,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-static const uint8_t k_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                                     12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                                     58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-static int huff_build(struct huff *h, const uint8_t counts[16], const uint8_t *vals, int nvals)
-{
-    memset(h, 0, sizeof *h);
-    int code = 0, k = 0;
-    memcpy(h->vals, vals, (size_t)nvals);
-    for (int len = 1; len <= 16; len++) {
-        h->valptr[len] = k;
-        h->mincode[len] = code;
-        for (int i = 0; i < counts[len - 1]; i++, k++, code++) {
-            if (k >= nvals) return -1;
-            if (code >= (1 << len)) return -1; /* over-subscribed DHT (Kraft sum > 1): the code does not fit its length */
-            if (len <= LOOK) {
-                int first = code << (LOOK - len), n = 1 << (LOOK - len);
-                for (int j = 0; j < n; j++) h->look[first + j] = (uint16_t)((len << 8) | vals[k]);
-            }
-        }
-        h->maxcode[len] = counts[len - 1] ? code - 1 : -1;
-        code <<= 1;
-    }
-    h->maxcode[17] = 0x7fffffff;
-    h->present = 1;
-    for (int i = 0; i < (1 << LOOK); i++) {
-        const unsigned e = h->look[i];
-        const int len = (int)(e >> 8), run = (int)((e >> 4) & 15), mag = (int)(e & 15);
-        if (!e || !mag || len + mag > LOOK) continue;
-        int k = ((i << len) & ((1 << LOOK) - 1)) >> (LOOK - mag);
-        if (k < (1 << (mag - 1))) k -= (1 << mag) - 1; /* EXTEND of T.81 F.2.2.1 */
-        if (k >= -128 && k <= 127) h->fast[i] = (int16_t)((k * 256) + (run * 16) + len + mag);
-    }
-    return 0;
-}
+static const uint8_t k_zigzag[64] = FFHIP_JPEG_ZIGZAG;
 
 struct bits {
     const uint8_t *p, *end;
@@ -127,99 +92,58 @@ static inline int huff_decode(struct bits *b, const struct huff *h)
 }
 static inline int extend(int v, int t) { return (t && v < (1 << (t - 1))) ? v - (1 << t) + 1 : v; }
 
-static int parse_headers(const uint8_t *f, size_t len, struct jpeg_hdr *j)
+/* the baseline parser, for ffhip_huff_gpu.hip too: the marker walk up to the first SOS; clears its record itself.  Its choices against ffhip_prog_parse's: DESIGN.md 4.32 */
+int ffhip_jpeg_parse(const uint8_t *f, size_t len, struct jpeg_hdr *j)
 {
     memset(j, 0, sizeof *j);
     for (int t = 0; t < 4; t++)
-        for (int i = 0; i < 64; i++) j->quant[t][i] = 1;
-    if (len < 4 || f[0] != 0xFF || f[1] != 0xD8) return FFHIP_EINVAL;
-    size_t p = 2;
+        for (int i = 0; i < 64; i++) j->fr.quant[t][i] = 1;
+    struct jpeg_walk w;
+    if (ffhip_jpeg_walk_open(&w, f, len)) return FFHIP_EINVAL;
     int have_sof = 0;
-    while (p + 4 <= len) {
-        if (f[p] != 0xFF) return FFHIP_EINVAL;
-        while (p < len && f[p] == 0xFF) p++; /* fill bytes */
-        if (p >= len) return FFHIP_EINVAL;
-        const int m = f[p++];
-        if (m == 0xD9) return FFHIP_EINVAL; /* EOI before SOS */
-        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-        if (p + 2 > len) return FFHIP_EINVAL;
-        const size_t L = ((size_t)f[p] << 8) | f[p + 1];
-        if (L < 2 || p + L > len) return FFHIP_EINVAL;
-        const uint8_t *s = f + p + 2;
-        const size_t sl = L - 2;
-        p += L;
-        if (m == 0xDB) { /* DQT: stored de-zigzagged like read_dqt (jpg.c:78-105) */
-            size_t i = 0;
-            while (i < sl) {
-                const int prec = s[i] >> 4, id = s[i] & 15;
-                i++;
-                if (id > 3 || i + (size_t)64 * (prec + 1) > sl) return FFHIP_EINVAL;
-                for (int k = 0; k < 64; k++, i += prec + 1)
-                    j->quant[id][k_zigzag[k]] = prec ? (uint16_t)((s[i] << 8) | s[i + 1]) : s[i];
-            }
-        } else if (m == 0xC4) { /* DHT */
-            size_t i = 0;
-            while (i + 17 <= sl) {
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                int n = 0;
-                for (int k = 0; k < 16; k++) n += s[i + 1 + k];
-                if (tc > 1 || th > 3 || n > 256 || i + 17 + (size_t)n > sl) return FFHIP_EINVAL;
-                if (huff_build(tc ? &j->ac[th] : &j->dc[th], s + i + 1, s + i + 17, n)) return FFHIP_EINVAL;
-                i += 17 + (size_t)n;
-            }
-        } else if (m == 0xC0 || m == 0xC1) { /* SOF0 / SOF1 */
-            if (sl < 6 || s[0] != 8) return FFHIP_EINVAL;
-            j->height = (s[1] << 8) | s[2];
-            j->width = (s[3] << 8) | s[4];
-            j->ncomp = s[5];
-            if ((j->ncomp != 1 && j->ncomp != 3) || sl < (size_t)(6 + 3 * j->ncomp)) return FFHIP_EINVAL;
-            if (j->width == 0 || j->height == 0) return FFHIP_EINVAL; /* height 0 = "see DNL": not this path */
-            for (int c = 0; c < j->ncomp; c++) {
-                j->cid[c] = s[6 + 3 * c];
-                j->h[c] = s[7 + 3 * c] >> 4;
-                j->v[c] = s[7 + 3 * c] & 15;
-                j->tq[c] = s[8 + 3 * c];
-                if (j->tq[c] > 3) return FFHIP_EINVAL;
-            }
+    while (!j->scan) {
+        const enum jpeg_event ev = ffhip_jpeg_walk_next(&w);
+        if (ev == JPEG_STANDALONE) continue;
+        if (ev != JPEG_SEGMENT) return FFHIP_EINVAL; /* EOI in front of SOS is refused, like a malformed file and one that ends */
+        const int m = w.marker;
+        const uint8_t *s = w.seg;
+        const size_t sl = w.seg_len;
+        if (m == 0xDB) {
+            if (ffhip_jpeg_read_dqt(s, sl, j->fr.quant, 15)) return FFHIP_EINVAL; /* any precision nibble: prec + 1 bytes an entry */
+        } else if (m == 0xC4) {
+            if (ffhip_jpeg_read_dht(s, sl, j->dc, j->ac, 1, NULL)) return FFHIP_EINVAL; /* with decode_mcus' one-look-up path: the DC tables carry it too */
+        } else if (m == 0xC0 || m == 0xC1) { /* SOF0 / SOF1; a later one replaces an earlier one, the layout rule waits for the last */
+            if (ffhip_jpeg_read_sof(s, sl, &j->fr)) return FFHIP_EINVAL;
             have_sof = 1;
         } else if (m == 0xC2 || (m >= 0xC5 && m <= 0xCF && m != 0xC8 && m != 0xCC)) {
-            return FFHIP_EINVAL; /* progressive / lossless / arithmetic: not this path */
+            return FFHIP_EINVAL; /* progressive / lossless / arithmetic: not this path (C3, C8 and CC are skipped like any segment) */
         } else if (m == 0xDD) {
-            if (sl < 2) return FFHIP_EINVAL;
-            j->restart = (s[0] << 8) | s[1];
+            if (ffhip_jpeg_read_dri(s, sl, &j->restart)) return FFHIP_EINVAL;
         } else if (m == 0xDA) { /* SOS */
-            if (!have_sof || sl < 1 || s[0] != j->ncomp || sl < (size_t)(4 + 2 * j->ncomp)) return FFHIP_EINVAL;
-            for (int k = 0; k < j->ncomp; k++) {
+            const int ncomp = j->fr.ncomp;
+            if (!have_sof || sl < 1 || s[0] != ncomp || sl < (size_t)(4 + 2 * ncomp)) return FFHIP_EINVAL;
+            for (int k = 0; k < ncomp; k++) {
                 int c;
-                for (c = 0; c < j->ncomp && j->cid[c] != s[1 + 2 * k]; c++) {}
-                if (c == j->ncomp) return FFHIP_EINVAL;
+                for (c = 0; c < ncomp && j->fr.cid[c] != s[1 + 2 * k]; c++) {}
+                if (c == ncomp) return FFHIP_EINVAL;
                 j->td[c] = s[2 + 2 * k] >> 4;
                 j->ta[c] = s[2 + 2 * k] & 15;
                 if (j->td[c] > 3 || j->ta[c] > 3 || !j->dc[j->td[c]].present || !j->ac[j->ta[c]].present) return FFHIP_EINVAL;
             }
-            const uint8_t *t = s + 1 + 2 * j->ncomp;
+            const uint8_t *t = s + 1 + 2 * ncomp;
             if (t[0] != 0 || t[1] != 63 || t[2] != 0) return FFHIP_EINVAL;
-            j->scan = f + p;
-            j->scan_len = len - p;
-            break;
+            j->scan = f + w.p; /* the first SOS ends the walk */
+            j->scan_len = len - w.p;
         }
     }
-    if (!j->scan) return FFHIP_EINVAL;
-    if (j->ncomp == 1) { j->h[0] = j->v[0] = 1; } /* single-component scans are never interleaved */
-    if (j->h[0] < 1 || j->v[0] < 1 || j->h[0] * j->v[0] > 4) return FFHIP_EINVAL; /* jpg.c:501: Y[3][64*4] */
-    for (int c = 1; c < j->ncomp; c++)
-        if (j->h[c] != 1 || j->v[c] != 1) return FFHIP_EINVAL; /* colorspace.c:149-150: chroma is one block per MCU */
-    return FFHIP_OK;
+    return ffhip_jpeg_frame_layout(&j->fr) ? FFHIP_EINVAL : FFHIP_OK;
 }
-
-/* for the other translation units of the library (ffhip_huff_gpu.hip) */
-int ffhip_jpeg_parse(const uint8_t *file, size_t len, struct jpeg_hdr *j) { return parse_headers(file, len, j); }
 /* the DRI value of a file this front end accepts (0 = none), -1 if it does not parse */
 int ffhip_jpeg_probe_restart(const uint8_t *file, size_t len)
 {
     struct jpeg_hdr *j = malloc(sizeof *j);
     if (!j) return -1;
-    const int r = parse_headers(file, len, j) ? -1 : j->restart;
+    const int r = ffhip_jpeg_parse(file, len, j) ? -1 : j->restart;
     free(j);
     return r;
 }
@@ -228,16 +152,11 @@ int ffhip_jpeg_probe(const uint8_t *file, size_t len, ffhip_jpeg_geom *geom, int
 {
     struct jpeg_hdr *j = malloc(sizeof *j);
     if (!j) return FFHIP_ENOMEM;
-    int rc = file && geom ? parse_headers(file, len, j) : FFHIP_EINVAL;
+    int rc = file && geom ? ffhip_jpeg_parse(file, len, j) : FFHIP_EINVAL;
     if (rc == FFHIP_OK) {
-        geom->ncomp = j->ncomp;
-        geom->h = j->h[0];
-        geom->v = j->v[0];
-        geom->mcu_cols = (j->width + 8 * j->h[0] - 1) / (8 * j->h[0]);
-        geom->mcu_rows = (j->height + 8 * j->v[0] - 1) / (8 * j->v[0]);
-        for (int c = 0; c < 3; c++) geom->qt_id[c] = c < j->ncomp ? j->tq[c] : 0;
-        if (width) *width = j->width;
-        if (height) *height = j->height;
+        ffhip_jpeg_frame_geom(&j->fr, geom);
+        if (width) *width = j->fr.width;
+        if (height) *height = j->fr.height;
     }
     free(j);
     return rc;
@@ -249,14 +168,14 @@ int ffhip_jpeg_probe(const uint8_t *file, size_t len, ffhip_jpeg_geom *geom, int
 static int decode_mcus(const struct jpeg_hdr *j, int16_t *const planes[3], struct bits *b, long mcu, long count)
 {
     int pred[3] = {0, 0, 0};
-    for (int c = 0; c < j->ncomp; c++) {
-        const size_t per = (size_t)j->h[c] * j->v[c] * 64;
+    for (int c = 0; c < j->fr.ncomp; c++) {
+        const size_t per = (size_t)j->fr.h[c] * j->fr.v[c] * 64;
         memset(planes[c] + (size_t)mcu * per, 0, (size_t)count * per * sizeof(int16_t));
     }
     for (const long end = mcu + count; mcu < end; mcu++) {
-        for (int c = 0; c < j->ncomp; c++) {
+        for (int c = 0; c < j->fr.ncomp; c++) {
             const struct huff *hd = &j->dc[j->td[c]], *ha = &j->ac[j->ta[c]];
-            const int nb = j->h[c] * j->v[c];
+            const int nb = j->fr.h[c] * j->fr.v[c];
             for (int k = 0; k < nb; k++) {
                 int16_t *blk = planes[c] + (mcu * nb + k) * 64;
                 const int t = huff_decode(b, hd);
@@ -324,14 +243,13 @@ int ffhip_jpeg_entropy_decode_mt(const uint8_t *file, size_t len, const ffhip_jp
 {
     struct jpeg_hdr *j = malloc(sizeof *j);
     if (!j) return FFHIP_ENOMEM;
-    int rc = file && coef_y && quant ? parse_headers(file, len, j) : FFHIP_EINVAL;
+    int rc = file && coef_y && quant ? ffhip_jpeg_parse(file, len, j) : FFHIP_EINVAL;
     if (rc) { free(j); return rc; }
-    const int mcu_cols = (j->width + 8 * j->h[0] - 1) / (8 * j->h[0]), mcu_rows = (j->height + 8 * j->v[0] - 1) / (8 * j->v[0]);
-    if (expect && (expect->mcu_cols != mcu_cols || expect->mcu_rows != mcu_rows || expect->ncomp != j->ncomp ||
-                   expect->h != j->h[0] || expect->v != j->v[0])) { free(j); return FFHIP_EINVAL; }
-    if (j->ncomp == 3 && (!coef_u || !coef_v)) { free(j); return FFHIP_EINVAL; }
-    memcpy(quant, j->quant, sizeof j->quant);
-    const long mcus = (long)mcu_cols * mcu_rows;
+    ffhip_jpeg_geom g;
+    ffhip_jpeg_frame_geom(&j->fr, &g);
+    if ((expect && !ffhip_jpeg_geom_same(expect, &g)) || (g.ncomp == 3 && (!coef_u || !coef_v))) { free(j); return FFHIP_EINVAL; }
+    memcpy(quant, j->fr.quant, sizeof j->fr.quant);
+    const long mcus = (long)g.mcu_cols * g.mcu_rows;
     struct interval_job base = {j, {coef_y, coef_u, coef_v}, NULL, 1, mcus, 0, 1, FFHIP_OK};
     if (!j->restart) { /* one segment, one thread */
         struct bits b = {j->scan, j->scan + j->scan_len, 0, 0, 0, 0};

@@ -15,6 +15,7 @@
  */
 #include "ffpic_hip.h"
 #include "ffhip_orient_body.h"
+#include "ffhip_jpeg_front.h"
 
 #include <string.h>
 
@@ -52,23 +53,16 @@ int ffhip_jpeg_exif_orientation(const uint8_t *file, size_t len, int *orientatio
 {
     if (!file || !orientation) return FFHIP_EINVAL;
     *orientation = 1;
-    if (len < 4 || file[0] != 0xFF || file[1] != 0xD8) return FFHIP_OK;
-    size_t p = 2;
-    while (p + 2 <= len) {
-        if (file[p] != 0xFF) return FFHIP_OK;
-        while (p < len && file[p] == 0xFF) p++; /* fill bytes */
-        if (p >= len) return FFHIP_OK;
-        const int m = file[p++];
-        if (m == 0xD9 || m == 0xDA) return FFHIP_OK;           /* EOI, SOS: no tag in front of the picture */
-        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;   /* markers without a segment */
-        if (len - p < 2) return FFHIP_OK;
-        const size_t seg = (size_t)file[p] << 8 | file[p + 1]; /* counts its own two bytes */
-        if (seg < 2 || seg > len - p) return FFHIP_OK;
-        if (m == 0xE1 && seg >= 8 && memcmp(file + p + 2, "Exif\0\0", 6) == 0) {
-            *orientation = tiff_orientation(file + p + 8, seg - 8);
-            return FFHIP_OK;
+    struct jpeg_walk w;
+    if (ffhip_jpeg_walk_open(&w, file, len)) return FFHIP_OK;
+    for (;;) {
+        const enum jpeg_event ev = ffhip_jpeg_walk_next(&w);
+        if (ev == JPEG_STANDALONE) continue;
+        if (ev != JPEG_SEGMENT || w.marker == 0xDA) break; /* EOI, SOS: no tag in front of the picture; a malformed file or its end fails nothing */
+        if (w.marker == 0xE1 && w.seg_len >= 6 && memcmp(w.seg, "Exif\0\0", 6) == 0) {
+            *orientation = tiff_orientation(w.seg + 6, w.seg_len - 6);
+            break;
         }
-        p += seg;
     }
     return FFHIP_OK;
 }

@@ -50,10 +50,7 @@ struct HuffArgs {
     uint32_t n_work;
 };
 
-__device__ static const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                                               12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                               35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                                               58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__device__ static const uint8_t kZigzag[64] = FFHIP_JPEG_ZIGZAG;
 
 /* The byte streams the kernel reads are UNSTUFFED (the host removes the 00 behind every FF while it stages the
  * bytes) and every restart interval starts 4-byte aligned and is followed by zero padding -- what the reference's
@@ -475,11 +472,10 @@ int huff_parse_headers(HuffCall &c)
         struct jpeg_hdr &j = c.hdr[(size_t)i];
         c.status[i] = ffhip_jpeg_parse(c.files[i], c.lens[i], &j);
         if (c.status[i]) return;
-        const int mc = (j.width + 8 * j.h[0] - 1) / (8 * j.h[0]), mr = (j.height + 8 * j.v[0] - 1) / (8 * j.v[0]);
-        const ffhip_jpeg_geom *gi = c.geoms ? &c.geoms[i] : c.geom;
+        ffhip_jpeg_geom g;
+        ffhip_jpeg_frame_geom(&j.fr, &g);
         const size_t mcus = c.pic_mcus[(size_t)i];
-        if (mc != gi->mcu_cols || mr != gi->mcu_rows || j.ncomp != gi->ncomp || j.h[0] != gi->h || j.v[0] != gi->v ||
-            j.scan_len > 0x7fffffffu) {
+        if (!ffhip_jpeg_geom_same(&g, c.geoms ? &c.geoms[i] : c.geom) || j.scan_len > 0x7fffffffu) {
             c.status[i] = FFHIP_EINVAL; /* another geometry */
             return;
         }
@@ -527,13 +523,13 @@ int huff_lay_out(HuffCall &c)
         im.restart = (uint32_t)j.restart;
         im.mcus = c.pic_mcus[(size_t)i];
         im.mcu_base = c.mcu_base[(size_t)i];
-        im.ncomp = (uint32_t)j.ncomp;
+        im.ncomp = (uint32_t)j.fr.ncomp;
         im.seg_base = (uint32_t)c.seg_total;
         im.n_seg = (uint32_t)c.segs[(size_t)i].size() - 1;
         for (int k = 0; k < 3; k++) {
-            im.nb[k] = k < j.ncomp ? (uint32_t)(j.h[k] * j.v[k]) : 0;
-            im.tab_dc[k] = huff_table_id(c.uniq, &j.dc[k < j.ncomp ? j.td[k] : j.td[0]]);
-            im.tab_ac[k] = huff_table_id(c.uniq, &j.ac[k < j.ncomp ? j.ta[k] : j.ta[0]]);
+            im.nb[k] = k < j.fr.ncomp ? (uint32_t)(j.fr.h[k] * j.fr.v[k]) : 0;
+            im.tab_dc[k] = huff_table_id(c.uniq, &j.dc[k < j.fr.ncomp ? j.td[k] : j.td[0]]);
+            im.tab_ac[k] = huff_table_id(c.uniq, &j.ac[k < j.fr.ncomp ? j.ta[k] : j.ta[0]]);
         }
         c.scan_total += (j.scan_len + 8 * (size_t)im.n_seg + 64 + 15) & ~(size_t)15; /* unstuffed, every interval aligned and padded, slack for the 16-byte stores */
         c.seg_total += im.n_seg;
@@ -585,7 +581,7 @@ void huff_stage_pictures(HuffCall &c, int lo, int hi, bool lists)
             wk[k].y = k;
         }
         sg[im.n_seg] = (uint32_t)off;
-        memcpy(c.stage + c.L.o_quant + (size_t)i * 512, j.quant, 512);
+        memcpy(c.stage + c.L.o_quant + (size_t)i * 512, j.fr.quant, 512);
     });
 }
 int huff_part_lo(const HuffCall &c, int n_parts, int part) { return (int)((long long)c.n * part / n_parts); }
@@ -739,7 +735,7 @@ int huff_decode_subsequences(HuffCall &c)
     SyncJob jobs[FFHIP_HUFF_PARTS];
     std::vector<SyncSeg> part_segs[FFHIP_HUFF_PARTS];
     uint32_t *h_cnt[FFHIP_HUFF_PARTS];
-    for (int i = 0; i < c.n; i++) memcpy(c.stage + c.L.o_quant + (size_t)i * 512, c.hdr[(size_t)i].quant, 512);
+    for (int i = 0; i < c.n; i++) memcpy(c.stage + c.L.o_quant + (size_t)i * 512, c.hdr[(size_t)i].fr.quant, 512);
     int rc = huff_tail_up(c);
     if (rc) return rc;
     (void)hipEventRecord(c.time_ev[0], c.st);

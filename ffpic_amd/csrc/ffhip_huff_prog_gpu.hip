@@ -106,9 +106,8 @@ int jpeg_progressive_batch_gpu_impl(const uint8_t *const *files, const size_t *l
         status[i] = files[i] && lens[i] ? ffhip_prog_parse(files[i], lens[i], &pf[(size_t)i]) : FFHIP_EINVAL;
         if (status[i]) { memset(&pf[(size_t)i], 0, sizeof(struct prog_file)); return; }
         ffhip_jpeg_geom g;
-        ffhip_prog_geom(&pf[(size_t)i], &g);
-        const ffhip_jpeg_geom *gi = geoms ? &geoms[i] : geom;
-        if (g.mcu_cols != gi->mcu_cols || g.mcu_rows != gi->mcu_rows || g.ncomp != gi->ncomp || g.h != gi->h || g.v != gi->v) {
+        ffhip_jpeg_frame_geom(&pf[(size_t)i].fr, &g);
+        if (!ffhip_jpeg_geom_same(&g, geoms ? &geoms[i] : geom)) {
             status[i] = FFHIP_EINVAL; /* another geometry */
             ffhip_prog_free(&pf[(size_t)i]);
             pf[(size_t)i].n_scans = 0;
@@ -199,7 +198,7 @@ int jpeg_progressive_batch_gpu_impl(const uint8_t *const *files, const size_t *l
     for (int i = 0; i < n; i++) {
         uint16_t *q = (uint16_t *)(stage + L.o_quant) + (size_t)i * 256;
         if (status[i]) for (int k = 0; k < 256; k++) q[k] = 1;
-        else memcpy(q, pf[(size_t)i].quant, 512);
+        else memcpy(q, pf[(size_t)i].fr.quant, 512);
     }
     /* the work lists, level by level: the lanes of a level are independent of each other */
     std::vector<uint32_t> level_first((size_t)max_level + 2, 0u);

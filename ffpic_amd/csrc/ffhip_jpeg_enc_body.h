@@ -11,6 +11,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include "ffhip_jpeg_front.h" /* the zig-zag order */
 
 #ifdef __HIPCC__
 #define JE_FN __host__ __device__ static inline __attribute__((always_inline))
@@ -109,9 +110,7 @@ JE_FN void je_fdct_quant(int32_t *d, const uint16_t *quant)
 }
 
 /* ---- step 7 ---- */
-JE_TABLE uint8_t je_zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+JE_TABLE uint8_t je_zz[64] = FFHIP_JPEG_ZIGZAG;
 
 /* The code tables as the walk reads them: per table set (0 luma, 1 chroma) JE_TAB_WORDS words, length << 16 | code: the AC code of symbol
  * (run << 4 | size) at [symbol], the DC code of size t at [256 + t]; 0: no such code */

@@ -69,9 +69,7 @@ struct prog_bits {
 #else
 #define PROG_TABLE static const
 #endif
-PROG_TABLE uint8_t prog_zz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                  41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+PROG_TABLE uint8_t prog_zz[64] = FFHIP_JPEG_ZIGZAG;
 PROG_HD int prog_zigzag(int k) { return prog_zz[k & 63]; }
 
 PROG_HD void prog_bits_open(struct prog_bits *b, const uint8_t *p, uint32_t pos, uint32_t end)

@@ -11,9 +11,7 @@ extern "C" {
 #endif
 
 struct prog_file {
-    int width, height, ncomp;
-    int h[3], v[3], tq[3], cid[3];
-    uint16_t quant[4][64];
+    struct jpeg_frame fr;
     int n_scans;
     struct prog_scan scan[FFHIP_JPEG_MAX_SCANS]; /* pic, data and seg_base are the decoder's to fill in; tab[] indexes `tabs` */
     const uint8_t *raw[FFHIP_JPEG_MAX_SCANS];    /* each scan's entropy-coded bytes in the file */
@@ -24,7 +22,6 @@ struct prog_file {
 
 int ffhip_prog_parse(const uint8_t *file, size_t len, struct prog_file *pf); /* 0, FFHIP_EINVAL or FFHIP_ENOMEM (nothing to free then) */
 void ffhip_prog_free(struct prog_file *pf);
-void ffhip_prog_geom(const struct prog_file *pf, ffhip_jpeg_geom *geom);
 int ffhip_prog_k_eff(const struct prog_file *pf, int k_max); /* scans with Ss above this are skipped */
 uint32_t ffhip_prog_stage_scan(uint8_t *dst, const uint8_t *src, size_t len, uint32_t *seg, uint32_t n_seg);
 int ffhip_prog_decode_host(const uint8_t *file, size_t len, const ffhip_jpeg_geom *expect, int16_t *coef_y, int16_t *coef_u, int16_t *coef_v,

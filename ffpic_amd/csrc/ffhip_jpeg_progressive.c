@@ -21,36 +21,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-static const uint8_t k_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                                     12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                                     58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-/* the table of a DHT segment: what huff_build of ffhip_entropy.c builds, without the one-look-up AC path (never read here) */
-static int prog_huff_build(struct huff *h, const uint8_t counts[16], const uint8_t *vals, int nvals)
-{
-    memset(h, 0, sizeof *h);
-    int code = 0, k = 0;
-    memcpy(h->vals, vals, (size_t)nvals);
-    for (int len = 1; len <= 16; len++) {
-        h->valptr[len] = k;
-        h->mincode[len] = code;
-        for (int i = 0; i < counts[len - 1]; i++, k++, code++) {
-            if (k >= nvals) return -1;
-            if (code >= (1 << len)) return -1; /* over-subscribed */
-            if (len <= LOOK) {
-                const int first = code << (LOOK - len), n = 1 << (LOOK - len);
-                for (int j = 0; j < n; j++) h->look[first + j] = (uint16_t)((len << 8) | vals[k]);
-            }
-        }
-        h->maxcode[len] = counts[len - 1] ? code - 1 : -1;
-        code <<= 1;
-    }
-    h->maxcode[17] = 0x7fffffff;
-    h->present = 1;
-    return 0;
-}
-
 void ffhip_prog_free(struct prog_file *pf)
 {
     free(pf->tabs);
@@ -74,84 +44,48 @@ static int prog_snapshot(struct prog_file *pf, const struct huff *cur, int *snap
     return snap[slot] = pf->n_tabs++;
 }
 
+/* the progressive parser: the marker walk over the whole file, every scan cut at the first marker that is no RSTn.  Its choices against ffhip_jpeg_parse's: DESIGN.md 4.32 */
 int ffhip_prog_parse(const uint8_t *f, size_t len, struct prog_file *pf)
 {
     memset(pf, 0, sizeof *pf);
     for (int t = 0; t < 4; t++)
-        for (int i = 0; i < 64; i++) pf->quant[t][i] = 1;
-    if (!f || len < 4 || f[0] != 0xFF || f[1] != 0xD8) return FFHIP_EINVAL;
+        for (int i = 0; i < 64; i++) pf->fr.quant[t][i] = 1;
+    struct jpeg_walk w;
+    if (!f || ffhip_jpeg_walk_open(&w, f, len)) return FFHIP_EINVAL;
     struct huff *cur = calloc(8, sizeof *cur); /* the tables as the marker loop has them now */
     if (!cur) return FFHIP_ENOMEM;
-    int snap[8], rc = FFHIP_EINVAL, have_sof = 0, restart = 0, eoi = 0;
+    int snap[8], rc = FFHIP_EINVAL, have_sof = 0, restart = 0;
     int8_t last_al[3][64]; /* per component and coefficient: the Al of its latest scan, -1 = none yet */
     memset(last_al, -1, sizeof last_al);
     for (int i = 0; i < 8; i++) snap[i] = -1;
-    size_t p = 2;
-    int hmax = 1, vmax = 1;
-    while (p + 2 <= len) {
-        if (f[p] != 0xFF) goto out;
-        while (p < len && f[p] == 0xFF) p++; /* fill bytes */
-        if (p >= len) goto out;
-        const int m = f[p++];
-        if (m == 0xD9) { eoi = 1; break; }
-        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-        if (p + 2 > len) goto out;
-        const size_t L = ((size_t)f[p] << 8) | f[p + 1];
-        if (L < 2 || p + L > len) goto out;
-        const uint8_t *s = f + p + 2;
-        const size_t sl = L - 2;
-        p += L;
+    for (;;) {
+        const enum jpeg_event ev = ffhip_jpeg_walk_next(&w);
+        if (ev == JPEG_EOI) break; /* ends the file, wherever it stands */
+        if (ev == JPEG_STANDALONE) continue;
+        if (ev != JPEG_SEGMENT) goto out; /* malformed, or the file ends without EOI */
+        const int m = w.marker;
+        const uint8_t *s = w.seg;
+        const size_t sl = w.seg_len;
         if (m == 0xDB) {
             if (pf->n_scans) goto out; /* a DQT behind the first SOS: the planes would need two quantisers */
-            size_t i = 0;
-            while (i < sl) {
-                const int prec = s[i] >> 4, id = s[i] & 15;
-                i++;
-                if (prec > 1 || id > 3 || i + (size_t)64 * (prec + 1) > sl) goto out;
-                for (int k = 0; k < 64; k++, i += prec + 1)
-                    pf->quant[id][k_zigzag[k]] = prec ? (uint16_t)((s[i] << 8) | s[i + 1]) : s[i];
-            }
+            if (ffhip_jpeg_read_dqt(s, sl, pf->fr.quant, 1)) goto out; /* 8 and 16 bit entries only */
         } else if (m == 0xC4) {
-            size_t i = 0;
-            while (i + 17 <= sl) {
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                int n = 0;
-                for (int k = 0; k < 16; k++) n += s[i + 1 + k];
-                if (tc > 1 || th > 3 || n > 256 || i + 17 + (size_t)n > sl) goto out;
-                if (prog_huff_build(&cur[tc * 4 + th], s + i + 1, s + i + 17, n)) goto out;
-                snap[tc * 4 + th] = -1;
-                i += 17 + (size_t)n;
-            }
-        } else if (m == 0xC2) {
-            if (have_sof || sl < 6 || s[0] != 8) goto out;
-            pf->height = (s[1] << 8) | s[2];
-            pf->width = (s[3] << 8) | s[4];
-            pf->ncomp = s[5];
-            if ((pf->ncomp != 1 && pf->ncomp != 3) || sl < (size_t)(6 + 3 * pf->ncomp)) goto out;
-            if (pf->width == 0 || pf->height == 0) goto out;
-            for (int c = 0; c < pf->ncomp; c++) {
-                pf->cid[c] = s[6 + 3 * c];
-                pf->h[c] = s[7 + 3 * c] >> 4;
-                pf->v[c] = s[7 + 3 * c] & 15;
-                pf->tq[c] = s[8 + 3 * c];
-                if (pf->tq[c] > 3) goto out;
-            }
-            if (pf->ncomp == 1) pf->h[0] = pf->v[0] = 1;
-            if (pf->h[0] < 1 || pf->v[0] < 1 || pf->h[0] * pf->v[0] > 4) goto out;
-            for (int c = 1; c < pf->ncomp; c++)
-                if (pf->h[c] != 1 || pf->v[c] != 1) goto out;
-            hmax = pf->h[0];
-            vmax = pf->v[0];
+            unsigned built = 0;
+            if (ffhip_jpeg_read_dht(s, sl, cur, cur + 4, 0, &built)) goto out; /* without the one-look-up path: never read here, fast[] stays zero */
+            for (int t = 0; t < 8; t++)
+                if (built >> t & 1) snap[t] = -1;
+        } else if (m == 0xC2) { /* SOF2, once, the layout rule at once */
+            if (have_sof || ffhip_jpeg_read_sof(s, sl, &pf->fr) || ffhip_jpeg_frame_layout(&pf->fr)) goto out;
             have_sof = 1;
         } else if (m >= 0xC0 && m <= 0xCF) {
-            goto out; /* another frame type (baseline, lossless, arithmetic), DAC: not this path */
+            goto out; /* another frame type (baseline, lossless, arithmetic), DAC, JPG: not this path */
         } else if (m == 0xDD) {
-            if (sl < 2) goto out;
-            restart = (s[0] << 8) | s[1];
+            if (ffhip_jpeg_read_dri(s, sl, &restart)) goto out;
         } else if (m == 0xDA) {
             if (!have_sof || sl < 1 || pf->n_scans == FFHIP_JPEG_MAX_SCANS) goto out;
             const int ns = s[0];
-            if (ns < 1 || ns > pf->ncomp || sl < (size_t)(4 + 2 * ns)) goto out;
+            const struct jpeg_frame *fr = &pf->fr;
+            if (ns < 1 || ns > fr->ncomp || sl < (size_t)(4 + 2 * ns)) goto out;
             struct prog_scan *sc = &pf->scan[pf->n_scans];
             memset(sc, 0, sizeof *sc);
             const uint8_t *t = s + 1 + 2 * ns;
@@ -160,8 +94,8 @@ int ffhip_prog_parse(const uint8_t *f, size_t len, struct prog_file *pf)
             sc->ncomp = (uint32_t)ns; sc->ss = (uint32_t)ss; sc->se = (uint32_t)se; sc->ah = (uint32_t)ah; sc->al = (uint32_t)al;
             for (int k = 0; k < ns; k++) {
                 int c;
-                for (c = 0; c < pf->ncomp && pf->cid[c] != s[1 + 2 * k]; c++) {}
-                if (c == pf->ncomp) goto out;
+                for (c = 0; c < fr->ncomp && fr->cid[c] != s[1 + 2 * k]; c++) {}
+                if (c == fr->ncomp) goto out;
                 for (int q = 0; q < k; q++)
                     if (sc->comp[q] == (uint32_t)c) goto out;
                 if (k && (uint32_t)c < sc->comp[k - 1]) goto out; /* B.2.3: in the frame's order */
@@ -180,21 +114,23 @@ int ffhip_prog_parse(const uint8_t *f, size_t len, struct prog_file *pf)
                 if (id < 0) goto out; /* a table not yet defined */
                 sc->tab[k] = (uint32_t)id;
             }
-            const uint32_t mcu_cols = (uint32_t)(pf->width + 8 * hmax - 1) / (uint32_t)(8 * hmax);
-            const uint32_t mcu_rows = (uint32_t)(pf->height + 8 * vmax - 1) / (uint32_t)(8 * vmax);
             if (ns > 1) {
-                sc->units = mcu_cols * mcu_rows;
-                sc->bw = mcu_cols;
-            } else { /* the component's own grid: ceil(ceil(W h_c / h_max) / 8) x ceil(ceil(H v_c / v_max) / 8) */
+                ffhip_jpeg_geom g;
+                ffhip_jpeg_frame_geom(fr, &g);
+                sc->units = (uint32_t)g.mcu_cols * (uint32_t)g.mcu_rows;
+                sc->bw = (uint32_t)g.mcu_cols;
+            } else { /* the component's own grid: ceil(ceil(W h_c / h_max) / 8) x ceil(ceil(H v_c / v_max) / 8); the first component's factors are the largest */
                 const int c = (int)sc->comp[0];
-                const uint32_t cw = ((uint32_t)pf->width * (uint32_t)pf->h[c] + (uint32_t)hmax - 1) / (uint32_t)hmax;
-                const uint32_t chh = ((uint32_t)pf->height * (uint32_t)pf->v[c] + (uint32_t)vmax - 1) / (uint32_t)vmax;
+                const uint32_t hmax = (uint32_t)fr->h[0], vmax = (uint32_t)fr->v[0];
+                const uint32_t cw = ((uint32_t)fr->width * (uint32_t)fr->h[c] + hmax - 1) / hmax;
+                const uint32_t chh = ((uint32_t)fr->height * (uint32_t)fr->v[c] + vmax - 1) / vmax;
                 sc->bw = (cw + 7) / 8;
                 sc->units = sc->bw * ((chh + 7) / 8);
             }
             sc->restart = restart ? (uint32_t)restart : sc->units;
             sc->n_seg = (sc->units + sc->restart - 1) / sc->restart;
             /* the entropy-coded bytes: up to the first marker that is no RSTn */
+            const size_t p = w.p;
             size_t q = p;
             while (q + 1 < len && !(f[q] == 0xFF && f[q + 1] != 0 && !(f[q + 1] >= 0xD0 && f[q + 1] <= 0xD7))) q++;
             if (q + 1 >= len) goto out; /* no marker behind the scan: the EOI is missing */
@@ -203,10 +139,10 @@ int ffhip_prog_parse(const uint8_t *f, size_t len, struct prog_file *pf)
             pf->raw[pf->n_scans] = f + p;
             pf->raw_len[pf->n_scans] = q - p;
             pf->n_scans++;
-            p = q;
+            w.p = q;
         }
     }
-    if (!eoi || !pf->n_scans) goto out;
+    if (!pf->n_scans) goto out;
     /* levels: a scan waits for every earlier scan that touches one of its (component, coefficient) pairs */
     for (int a = 0; a < pf->n_scans; a++) {
         struct prog_scan *sa = &pf->scan[a];
@@ -274,16 +210,6 @@ int ffhip_debug_progressive_last(int out[5])
     return FFHIP_OK;
 }
 
-void ffhip_prog_geom(const struct prog_file *pf, ffhip_jpeg_geom *geom)
-{
-    geom->ncomp = pf->ncomp;
-    geom->h = pf->h[0];
-    geom->v = pf->v[0];
-    geom->mcu_cols = (pf->width + 8 * pf->h[0] - 1) / (8 * pf->h[0]);
-    geom->mcu_rows = (pf->height + 8 * pf->v[0] - 1) / (8 * pf->v[0]);
-    for (int c = 0; c < 3; c++) geom->qt_id[c] = c < pf->ncomp ? pf->tq[c] : 0;
-}
-
 int ffhip_jpeg_probe_any(const uint8_t *file, size_t len, ffhip_jpeg_geom *geom, int *width, int *height, int *progressive)
 {
     if (!file || !geom) return FFHIP_EINVAL;
@@ -294,9 +220,9 @@ int ffhip_jpeg_probe_any(const uint8_t *file, size_t len, ffhip_jpeg_geom *geom,
     if (!pf) return FFHIP_ENOMEM;
     rc = ffhip_prog_parse(file, len, pf);
     if (rc == FFHIP_OK) {
-        ffhip_prog_geom(pf, geom);
-        if (width) *width = pf->width;
-        if (height) *height = pf->height;
+        ffhip_jpeg_frame_geom(&pf->fr, geom);
+        if (width) *width = pf->fr.width;
+        if (height) *height = pf->fr.height;
         if (progressive) *progressive = 1;
         ffhip_prog_free(pf);
     }
@@ -314,14 +240,13 @@ int ffhip_prog_decode_host(const uint8_t *file, size_t len, const ffhip_jpeg_geo
     int rc = ffhip_prog_parse(file, len, pf);
     if (rc) { free(pf); return rc; }
     ffhip_jpeg_geom g;
-    ffhip_prog_geom(pf, &g);
-    if ((expect && (expect->mcu_cols != g.mcu_cols || expect->mcu_rows != g.mcu_rows || expect->ncomp != g.ncomp || expect->h != g.h ||
-                    expect->v != g.v)) || (g.ncomp == 3 && (!coef_u || !coef_v))) {
+    ffhip_jpeg_frame_geom(&pf->fr, &g);
+    if ((expect && !ffhip_jpeg_geom_same(expect, &g)) || (g.ncomp == 3 && (!coef_u || !coef_v))) {
         ffhip_prog_free(pf);
         free(pf);
         return FFHIP_EINVAL;
     }
-    memcpy(quant, pf->quant, sizeof pf->quant);
+    memcpy(quant, pf->fr.quant, sizeof pf->fr.quant);
     const size_t mcus = (size_t)g.mcu_cols * g.mcu_rows;
     memset(coef_y, 0, mcus * g.h * g.v * 64 * sizeof(int16_t));
     if (g.ncomp == 3) {

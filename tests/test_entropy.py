@@ -160,7 +160,8 @@ def test_front_end_under_sanitizers(tmp_path):
     exe = str(tmp_path / "fuzz_entropy")
     subprocess.check_call(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I" + os.path.join(root, "include"), os.path.join(root, "tests", "tools", "fuzz_entropy.c"),
-                           os.path.join(root, "ffpic_amd", "csrc", "ffhip_entropy.c"), "-lpthread", "-o", exe])
+                           os.path.join(root, "ffpic_amd", "csrc", "ffhip_entropy.c"), os.path.join(root, "ffpic_amd", "csrc", "ffhip_jpeg_front.c"),
+                           "-lpthread", "-o", exe])
     files = [os.path.join(GOLDEN, f) for f in FILES.values()]
     out = subprocess.run([exe, "400"] + files, capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]

@@ -62,7 +62,8 @@ def test_shared_body_under_sanitizers(tmp_path):
     csrc = os.path.join(ROOT, "ffpic_amd", "csrc")
     subprocess.check_call(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(ROOT, "tests", "tools", "fuzz_progressive.c"),
-                           os.path.join(csrc, "ffhip_jpeg_progressive.c"), os.path.join(csrc, "ffhip_entropy.c"), "-lpthread", "-o", exe])
+                           os.path.join(csrc, "ffhip_jpeg_progressive.c"), os.path.join(csrc, "ffhip_entropy.c"), os.path.join(csrc, "ffhip_jpeg_front.c"),
+                           "-lpthread", "-o", exe])
     out = subprocess.run([exe, "4000", path], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert "decoded" in out.stdout and "unexpected" not in out.stdout

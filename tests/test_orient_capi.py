@@ -197,7 +197,8 @@ def _sanitizer_build(tmp_path, sources, out, compiler, flags=()):
 
 def test_sanitizer_program_over_truncated_and_mutated_files(tmp_path, jpeg, webp):
     """ffhip_exif.c and tests/tools/exif_fuzz_main.c as a program of their own under ASan + UBSan: exit 0, nothing on stderr"""
-    exe = _sanitizer_build(tmp_path, [os.path.join(ROOT, "ffpic_amd", "csrc", "ffhip_exif.c"), os.path.join(ROOT, "tests", "tools", "exif_fuzz_main.c")],
+    csrc = os.path.join(ROOT, "ffpic_amd", "csrc")
+    exe = _sanitizer_build(tmp_path, [os.path.join(csrc, "ffhip_exif.c"), os.path.join(csrc, "ffhip_jpeg_front.c"), os.path.join(ROOT, "tests", "tools", "exif_fuzz_main.c")],
                            "exif_fuzz", "cc", ["-std=c11"])
     files = {"le_short.jpg": X.tagged_jpeg(jpeg, 6), "be_long.jpg": X.tagged_jpeg(jpeg, 8, big_endian=True, kind=X.LONG),
              "behind_xmp.jpg": X.splice(jpeg, X.XMP_APP1, X.exif_app1(3)), "plain.jpg": jpeg,
