@@ -51,6 +51,8 @@ EXPORTS = [
     "ffhip_inflate_streams_device", "ffhip_png_decode_files_device_ex", "ffhip_png_decode_files_tensor_ex", "ffhip_debug_png_inflate",
     "ffhip_jpeg_encode_tables", "ffhip_jpeg_encode_block", "ffhip_jpeg_encode_header", "ffhip_jpeg_encode_bound", "ffhip_jpeg_encode_picture",
     "ffhip_jpeg_fdct_items", "ffhip_jpeg_huff_encode_items", "ffhip_jpeg_encode_items",
+    "ffhip_deflate", "ffhip_deflate_bound", "ffhip_deflate_code_lengths", "ffhip_png_filtered_size", "ffhip_png_filter_picture",
+    "ffhip_png_encode_bound", "ffhip_png_encode_picture", "ffhip_deflate_streams_device", "ffhip_png_encode_items",
 ]
 
 
@@ -64,6 +66,9 @@ FFHIP_EWEBP_LOSSLESS, FFHIP_EWEBP_ANIMATION, FFHIP_EWEBP_INTER_FRAME = -1001, -1
 FFHIP_JPEG_ENC_444, FFHIP_JPEG_ENC_422, FFHIP_JPEG_ENC_420, FFHIP_JPEG_ENC_GREY = 0, 1, 2, 3
 FFHIP_EJPEG_NOSPACE, FFHIP_EJPEG_RANGE = -1101, -1102
 FFHIP_JPEG_ENC_HEADER_MAX = 640
+FFHIP_DEFLATE_CHUNK = 16384
+FFHIP_PNG_FILTER_ADAPTIVE = 5
+FFHIP_EPNG_NOSPACE, FFHIP_EDEFLATE_NOSPACE = -1201, -1202
 
 
 class FfhipError(RuntimeError):
@@ -247,6 +252,26 @@ def jpeg_source(pixels, width, height, row_stride, pixel_stride, chan=(0, 0, 0),
     s = JpegSource()
     s.pixels, s.width, s.height, s.row_stride, s.pixel_stride, s.channels = pixels, width, height, row_stride, pixel_stride, channels
     for k in range(3):
+        s.chan[k] = chan[k] if k < len(chan) else 0
+    return s
+
+
+class PngSource(C.Structure):
+    """ffhip_png_source: a uint8 picture of 1..4 channels by byte strides, chan[] in file order (grey, A / R, G, B, A)"""
+    _fields_ = [("pixels", C.c_void_p), ("row_stride", C.c_int64), ("pixel_stride", C.c_int64), ("chan", C.c_int64 * 4),
+                ("channels", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PngEncodeItem(C.Structure):
+    """ffhip_png_encode_item (device pointers)"""
+    _fields_ = [("src", PngSource), ("filter", C.c_int32), ("reserved", C.c_int32), ("d_out", C.c_void_p), ("cap", C.c_size_t)]
+
+
+def png_source(pixels, width, height, row_stride, pixel_stride, chan, channels=None):
+    s = PngSource()
+    s.pixels, s.width, s.height, s.row_stride, s.pixel_stride = pixels, width, height, row_stride, pixel_stride
+    s.channels = len(chan) if channels is None else channels
+    for k in range(4):
         s.chan[k] = chan[k] if k < len(chan) else 0
     return s
 
@@ -479,6 +504,18 @@ def lib():
     L.ffhip_jpeg_fdct_items.argtypes = [C.POINTER(JpegFdctItem), ci, vp]
     L.ffhip_jpeg_huff_encode_items.argtypes = [C.POINTER(JpegHuffItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
     L.ffhip_jpeg_encode_items.argtypes = [C.POINTER(JpegEncodeItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
+    L.ffhip_deflate.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
+    L.ffhip_deflate_bound.argtypes = [sz]
+    L.ffhip_deflate_bound.restype = sz
+    L.ffhip_deflate_code_lengths.argtypes = [vp, ci, ci, vp]
+    L.ffhip_png_filtered_size.argtypes = [ci, ci, ci]
+    L.ffhip_png_filtered_size.restype = sz
+    L.ffhip_png_filter_picture.argtypes = [C.POINTER(PngSource), ci, vp, sz, C.POINTER(sz)]
+    L.ffhip_png_encode_bound.argtypes = [ci, ci, ci]
+    L.ffhip_png_encode_bound.restype = sz
+    L.ffhip_png_encode_picture.argtypes = [C.POINTER(PngSource), ci, vp, sz, C.POINTER(sz)]
+    L.ffhip_deflate_streams_device.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
+    L.ffhip_png_encode_items.argtypes = [C.POINTER(PngEncodeItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
     for name in ("ffhip_inflate_upto", "ffhip_inflate_model"):    # exported, not in the public header (csrc/ffhip_png_internal.h)
         getattr(L, name).argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci]
     L.ffhip_inflate_model_mode.argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci, ci]

@@ -1264,3 +1264,133 @@ def jpeg_encode_items(items, stream=None, strict=True):
     """ffhip_jpeg_encode_items: `items` a list of capi.JpegEncodeItem (device pictures) -> ([file length], [status]); the files are in the
     items' d_out.  With strict=False a file that does not fit its cap is its status (FFHIP_EJPEG_NOSPACE) and its length the size it needs."""
     return _lengths_call("ffhip_jpeg_encode_items", capi.JpegEncodeItem, items, stream, strict)
+
+
+def deflate_bound(length):
+    """ffhip_deflate_bound: a certain bound on the zlib stream of `length` bytes.  Needs no device."""
+    return int(capi.lib().ffhip_deflate_bound(int(length)))
+
+
+def deflate(data, cap=None):
+    """ffhip_deflate (host, no device): bytes to a zlib stream under the rule of include/ffpic_hip.h "PNG encoding", the CPU model of
+    deflate_streams_device.  cap: the output's size (the bound when None); -> bytes, or with cap given (rc, length, the cap bytes)."""
+    src = np.frombuffer(data, dtype=np.uint8)
+    size = deflate_bound(src.size) if cap is None else int(cap)
+    out = np.zeros(max(size, 1), np.uint8)
+    n = C.c_size_t()
+    rc = capi.lib().ffhip_deflate(src.ctypes.data if src.size else None, src.size, _vp(out), size, C.byref(n))
+    if cap is not None:
+        return rc, n.value, out[:size].tobytes()
+    capi.check(rc, "ffhip_deflate")
+    return out[:n.value].tobytes()
+
+
+def deflate_code_lengths(freq, limit):
+    """ffhip_deflate_code_lengths: the length rule alone -- frequencies (up to 288) -> uint8 code lengths of at most `limit` bits"""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    out = np.zeros(max(f.size, 1), np.uint8)
+    capi.check(capi.lib().ffhip_deflate_code_lengths(_vp(f), f.size, int(limit), _vp(out)), "ffhip_deflate_code_lengths")
+    return out[:f.size]
+
+
+def deflate_streams_device(buffers, caps=None, strict=True, stream=None, guard=0, fill=0):
+    """ffhip_deflate_streams_device: byte strings, uploaded into ONE device allocation, to zlib streams by k_deflate_chunks, each into its own
+    piece of another.  caps: the pieces' sizes (None: the bound).  Returns (streams, lengths, status): bytes per buffer (what lies below its
+    cap), the sizes the call names and the per-stream codes; strict: a stream that does not fit raises.  guard, fill: `guard` bytes of
+    `fill` between the pieces (and the pieces filled with it), for tests; a fourth element follows then, the whole allocation as the call
+    left it, with a fifth, the pieces' offsets."""
+    L = capi.require_device()
+    n = len(buffers)
+    bufs = [np.frombuffer(b, dtype=np.uint8) for b in buffers]
+    caps = [deflate_bound(b.size) if caps is None or caps[k] is None else int(caps[k]) for k, b in enumerate(bufs)]
+    in_offs, in_total = [], 0
+    for b in bufs:
+        in_offs.append(in_total)
+        in_total += (b.size + 255) & ~255
+    flat_in = np.zeros(max(in_total, 16), np.uint8)
+    for o, b in zip(in_offs, bufs):
+        flat_in[o:o + b.size] = b
+    din = DeviceBuffer(host=flat_in)
+    offs, total = [], guard
+    for c in caps:
+        offs.append(total)
+        total += c + guard
+    dout = DeviceBuffer(host=np.full(max(total, 16), fill, np.uint8))
+    srcs = (C.c_void_p * max(n, 1))(*[din.ptr + o if b.size else None for o, b in zip(in_offs, bufs)])
+    lens = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
+    outs = (C.c_void_p * max(n, 1))(*[dout.ptr + o if c else None for o, c in zip(offs, caps)])
+    cap_arr = (C.c_size_t * max(n, 1))(*caps)
+    got = (C.c_size_t * max(n, 1))()
+    status = (C.c_int * max(n, 1))()
+    rc = L.ffhip_deflate_streams_device(srcs, lens, n, outs, cap_arr, got, status, stream)
+    status = list(status)[:n]
+    if strict or (rc != 0 and rc not in status):
+        capi.check(rc, "ffhip_deflate_streams_device")
+    flat = dout.to_host((max(total, 16),), np.uint8)
+    streams = [flat[offs[i]:offs[i] + min(got[i], caps[i])].tobytes() for i in range(n)]
+    return (streams, list(got)[:n], status, flat, offs) if guard else (streams, list(got)[:n], status)
+
+
+def png_filter_id(filter):
+    """'adaptive', 'none', 'sub', 'up', 'average', 'paeth' or 0..5 -> the filter argument of the PNG encoder"""
+    names = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": capi.FFHIP_PNG_FILTER_ADAPTIVE}
+    if isinstance(filter, str):
+        if filter not in names:
+            raise ValueError(f"filter={filter!r}: one of {sorted(names)}")
+        return names[filter]
+    if isinstance(filter, bool) or not isinstance(filter, (int, np.integer)) or not 0 <= int(filter) <= capi.FFHIP_PNG_FILTER_ADAPTIVE:
+        raise ValueError(f"filter={filter!r}: 0..5 or a filter's name")
+    return int(filter)
+
+
+def png_host_source(pixels):
+    """capi.PngSource of a host array uint8 [H][W][C] (C in 1..4, file order) or [H][W] (grey), whatever its strides; keep the array alive"""
+    if pixels.dtype != np.uint8 or pixels.ndim not in (2, 3) or (pixels.ndim == 3 and not 1 <= pixels.shape[2] <= 4):
+        raise ValueError("pixels must be uint8 [H][W][C] with C in 1..4, or [H][W]")
+    st = pixels.strides
+    chan = tuple(k * st[2] for k in range(pixels.shape[2])) if pixels.ndim == 3 else (0,)
+    return capi.png_source(pixels.ctypes.data, pixels.shape[1], pixels.shape[0], st[0], st[1], chan)
+
+
+def _png_src(pixels):
+    return pixels if isinstance(pixels, capi.PngSource) else png_host_source(pixels)
+
+
+def png_filtered_size(width, height, channels):
+    return int(capi.lib().ffhip_png_filtered_size(width, height, channels))
+
+
+def png_encode_bound(width, height, channels):
+    """ffhip_png_encode_bound: a certain bound on the file's size (0: bad arguments).  Needs no device."""
+    return int(capi.lib().ffhip_png_encode_bound(width, height, channels))
+
+
+def png_filter_picture(pixels, filter="adaptive"):
+    """ffhip_png_filter_picture: host pixels (an array as png_host_source takes it, or a capi.PngSource of host memory) -> the filtered
+    picture's bytes: per row the filter type and width x channels bytes.  Needs no device."""
+    src = _png_src(pixels)
+    size = png_filtered_size(src.width, src.height, src.channels)
+    out = np.zeros(max(size, 1), np.uint8)
+    n = C.c_size_t()
+    capi.check(capi.lib().ffhip_png_filter_picture(C.byref(src), png_filter_id(filter), _vp(out), size, C.byref(n)), "ffhip_png_filter_picture")
+    return out[:n.value].tobytes()
+
+
+def png_encode_picture(pixels, filter="adaptive", cap=None):
+    """ffhip_png_encode_picture: host pixels (as png_filter_picture) to the PNG file's bytes, the CPU model of png_encode_items.  cap: the
+    output's size (the bound when None); -> bytes, or with cap given (rc, length, the cap bytes)."""
+    src = _png_src(pixels)
+    size = png_encode_bound(src.width, src.height, src.channels) if cap is None else int(cap)
+    out = np.zeros(max(size, 1), np.uint8)
+    n = C.c_size_t()
+    rc = capi.lib().ffhip_png_encode_picture(C.byref(src), png_filter_id(filter), _vp(out), size, C.byref(n))
+    if cap is not None:
+        return rc, n.value, out[:size].tobytes()
+    capi.check(rc, "ffhip_png_encode_picture")
+    return out[:n.value].tobytes()
+
+
+def png_encode_items(items, stream=None, strict=True):
+    """ffhip_png_encode_items: `items` a list of capi.PngEncodeItem (device pictures) -> ([file length], [status]); the files are in the
+    items' d_out.  With strict=False a file that does not fit its cap is its status (FFHIP_EPNG_NOSPACE) and its length the size it needs."""
+    return _lengths_call("ffhip_png_encode_items", capi.PngEncodeItem, items, stream, strict)

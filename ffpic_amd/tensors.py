@@ -533,3 +533,70 @@ def encode_jpeg(pictures, quality=75, subsampling="4:2:0", restart_blocks=0, to_
     if to_host:
         files = [bytes(f.cpu().numpy()) for f in files]
     return files[0] if single else files
+
+
+def png_source_of(t):
+    """capi.PngSource of a uint8 device tensor [C,H,W] or [H,W,C] with C in 1..4 (grey, grey + alpha, RGB, RGBA), whatever its strides.  A
+    first dimension of 1..4 is ALWAYS read as channels first, jpeg_source_of's convention: an [H,W,C] picture up to 4 rows high has to be
+    passed as t.permute(2, 0, 1)."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 3:
+        raise ValueError("encode_png takes uint8 device tensors [C,H,W] or [H,W,C] with C in 1..4")
+    if 1 <= t.shape[0] <= 4:
+        c, (height, width), (plane, row, pixel) = t.shape[0], t.shape[1:], t.stride()
+    elif 1 <= t.shape[2] <= 4:
+        c, (height, width), (row, pixel, plane) = t.shape[2], t.shape[:2], t.stride()
+    else:
+        raise ValueError(f"encode_png takes [C,H,W] or [H,W,C] with C in 1..4, got {tuple(t.shape)}")
+    if width < 1 or height < 1 or width > 65535 or height > 65535:
+        raise ValueError(f"encode_png: sides of 1..65535, got {tuple(t.shape)}")
+    return capi.png_source(t.data_ptr(), width, height, row, pixel, tuple(k * plane for k in range(c)))
+
+
+def encode_png(pictures, filter="adaptive", to_host=False):
+    """Device pictures to PNG files, lossless: a list of uint8 device tensors [C,H,W] or [H,W,C] with C in 1..4 (colour type grey, grey +
+    alpha, RGB, RGBA; a first dimension of 1..4 is always channels), of any sizes and strides, in ONE ffhip_png_encode_items call on the
+    current stream -> a list of 1-D uint8 device tensors (views of one allocation), or of bytes with to_host=True.  filter: 'adaptive' (per
+    row the type with the smallest sum of absolute values), 'none', 'sub', 'up', 'average', 'paeth' or 0..5, one value or one per picture.
+    The outputs start at half the bound; the files that need more (the call says how much) go through a second call."""
+    import torch
+    single = isinstance(pictures, torch.Tensor)
+    pictures = [pictures] if single else list(pictures)
+    n = len(pictures)
+    filters = list(filter) if isinstance(filter, (list, tuple)) else [filter] * n
+    if len(filters) != n:
+        raise ValueError(f"filter: {len(filters)} values for {n} pictures")
+    filters = [ops.png_filter_id(f) for f in filters]                     # argument errors come before any device use
+    sources = [png_source_of(t) for t in pictures]
+    if n == 0:
+        return []
+    dev = torch.cuda.current_device()
+    capi.require_device(dev)
+    device = torch.device("cuda", dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    files, todo = [None] * n, list(range(n))
+    caps = [(ops.png_encode_bound(s.width, s.height, s.channels) // 2 + 255) & ~255 for s in sources]
+    for _ in range(2):
+        offs = np.concatenate([[0], np.cumsum([caps[i] for i in todo])]).astype(np.int64)
+        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
+        items = []
+        for k, i in enumerate(todo):
+            it = capi.PngEncodeItem()
+            it.src, it.filter, it.d_out, it.cap = sources[i], filters[i], buf.data_ptr() + int(offs[k]), caps[i]
+            items.append(it)
+        lens, status = ops.png_encode_items(items, stream, strict=False)
+        again = []
+        for k, i in enumerate(todo):
+            if status[k] == 0:
+                files[i] = buf[int(offs[k]):int(offs[k]) + lens[k]]
+            elif status[k] == capi.FFHIP_EPNG_NOSPACE:
+                caps[i] = (lens[k] + 255) & ~255
+                again.append(i)
+            else:
+                capi.check(status[k], "ffhip_png_encode_items")
+        todo = again
+        if not todo:
+            break
+    if to_host:
+        files = [bytes(f.cpu().numpy()) for f in files]
+    return files[0] if single else files

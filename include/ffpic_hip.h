@@ -1653,6 +1653,92 @@ typedef struct ffhip_jpeg_encode_item {
 } ffhip_jpeg_encode_item;
 int ffhip_jpeg_encode_items(const ffhip_jpeg_encode_item *items, int n, size_t *len_out, int *status, void *stream);
 
+/* ---- PNG encoding (ffhip_png_enc.c, ffhip_png_enc_body.h, ffhip_png_enc_gpu.hip; ffhip_deflate.c, ffhip_deflate_body.h,
+ *      ffhip_deflate_gpu.hip) ----
+ * Pictures to complete PNG files, lossless: the filters and deflate as kernels, the same bodies as host functions.  THE RULE, which host and
+ * device share so that their files are equal byte for byte:
+ *   PICTURES  8 bits a sample; colour type 0, 4, 2, 6 for 1, 2, 3, 4 channels (grey, grey + alpha, RGB, RGBA); not interlaced; sides 1..65535.
+ *             The file: signature, IHDR, the IDAT chunks, IEND; no ancillary chunk.
+ *   FILTERS   filter 0..4: that type on every row.  FFHIP_PNG_FILTER_ADAPTIVE: per row the type whose filtered bytes, read as signed 8-bit,
+ *             have the smallest sum of absolute values, the lowest type at equal sums.  The row above row 0 and the bpp = channels bytes
+ *             left of a row are zeros.  A filtered row is the type byte and width x channels bytes; the filtered picture is the rows end to end.
+ *   ZLIB      header 78 01.  The filtered picture is cut into chunks of FFHIP_DEFLATE_CHUNK bytes (the last one shorter; an empty input is one
+ *             empty chunk).  A chunk becomes ONE deflate block: dynamic Huffman, or stored when the dynamic block is not shorter in bytes (an
+ *             empty chunk is stored).  A chunk starts at a byte boundary: every chunk but the last is followed by an empty stored block (three
+ *             zero header bits behind the block's last bit, zeros to the byte boundary, 00 00 FF FF); the last chunk's block has BFINAL and
+ *             is padded with zeros.  The Adler-32 of the input, big-endian, ends the stream.
+ *   PARSE     within a chunk, by steps of 64 positions.  Position p (its match may be min(258, bytes left in the chunk) long) tries, in this
+ *             order, distances 1, 2, 3, 4 (where the stream has that many bytes in front of p, earlier chunks included; a match of 3 or more
+ *             counts) and then, when 4 bytes are left, the LATEST position of an EARLIER step of this chunk whose 4 bytes have the same hash
+ *             ((little-endian word x 2654435761) >> 20; a match of 4 or more counts).  The longest wins, the first tried among equals;
+ *             a position a token of an earlier step covers tries nothing.  Then greedy: from the first uncovered position, a position
+ *             with a match emits it and skips its length, any other emits its byte.  Length 258 is symbol 285.
+ *   CODES     frequencies of the chunk's tokens, end-of-block once.  Lengths: Huffman's algorithm on the used symbols sorted by (frequency,
+ *             symbol), two queues, leaf before inner node at equal weight; while a length exceeds the limit (15, and 7 for the code-length
+ *             alphabet) every used frequency becomes (f + 1) / 2 and the tree is built again.  One used symbol gets one bit; a block without
+ *             a match has one distance code (symbol 0) of one bit.  HLIT, HDIST, HCLEN are the smallest the lengths allow.  The lengths of
+ *             both alphabets, as one sequence, are run-length coded run by run of equal values: a non-zero value once, then 16 for 6, ...,
+ *             3 of the rest, then singly; zeros by 18 for 138 .. 11, then 17 for 10 .. 3, then singly.  Codes are canonical.
+ *   CHUNKS    one IDAT per deflate chunk (the first holds the zlib header in front), then an IDAT of the four Adler bytes, then IEND.
+ * Every choice is a function of the input bytes alone. */
+#define FFHIP_DEFLATE_CHUNK 16384
+#define FFHIP_PNG_FILTER_ADAPTIVE 5
+#define FFHIP_EPNG_NOSPACE (-1201)     /* the file does not fit cap: len is the size it needs, nothing at or beyond cap was written */
+#define FFHIP_EDEFLATE_NOSPACE (-1202) /* the same for a zlib stream */
+/* A uint8 picture by byte strides, either of which may be negative: sample c of pixel (x, y) is pixels[y row_stride + x pixel_stride +
+ * chan[c]], c in file order (grey, A / R, G, B, A).  A BGRA picture as the decoders leave it: pixel_stride 4, chan {2, 1, 0, 3}; with
+ * channels 3 and chan {2, 1, 0} its alpha is dropped.  Strides and offsets lie within +-2^30; reserved 0. */
+typedef struct ffhip_png_source {
+    const uint8_t *pixels;
+    int64_t row_stride, pixel_stride;
+    int64_t chan[4];
+    int32_t channels, width, height, reserved;
+} ffhip_png_source;
+/* Host entries; they need no device.
+ *   ffhip_deflate              src[0, len) to a zlib stream under the rule: *out_len its size; FFHIP_EDEFLATE_NOSPACE when that exceeds cap (no
+ *                              byte at or beyond dst + cap is written)
+ *   ffhip_deflate_bound        a CERTAIN bound: 2 + len + 4, 5 bytes a chunk for the stored form, 5 for each empty stored block between chunks
+ *   ffhip_deflate_code_lengths the length rule alone: n <= 288 frequencies (their sum below 2^32), limit 1..15 with 2^limit >= n
+ *   ffhip_png_filtered_size    height x (1 + width x channels), 0 for bad arguments
+ *   ffhip_png_filter_picture   the filtered picture, ffhip_png_filtered_size bytes (*len; FFHIP_EPNG_NOSPACE and nothing written when that
+ *                              exceeds cap); filter 0..4 or FFHIP_PNG_FILTER_ADAPTIVE
+ *   ffhip_png_encode_bound     a CERTAIN bound on the file, 0 for bad arguments: 33 bytes of signature and IHDR, 12 an IDAT, the deflate bound
+ *                              of the filtered size, 12 for the IDAT around the Adler-32, 12 of IEND
+ *   ffhip_png_encode_picture   HOST pixels to the file; *len its size; FFHIP_EPNG_NOSPACE when that exceeds cap (no byte at or beyond out + cap
+ *                              is written) */
+int ffhip_deflate(const uint8_t *src, size_t len, uint8_t *dst, size_t cap, size_t *out_len);
+size_t ffhip_deflate_bound(size_t len);
+int ffhip_deflate_code_lengths(const uint32_t *freq, int n, int limit, uint8_t *lengths);
+size_t ffhip_png_filtered_size(int width, int height, int channels);
+int ffhip_png_filter_picture(const ffhip_png_source *src, int filter, uint8_t *out, size_t cap, size_t *len);
+size_t ffhip_png_encode_bound(int width, int height, int channels);
+int ffhip_png_encode_picture(const ffhip_png_source *src, int filter, uint8_t *out, size_t cap, size_t *len);
+/* On the device.  The arrays are HOST arrays, read before the call returns; every check is made before anything is enqueued (FFHIP_EINVAL, on
+ * a machine without a device too; FFHIP_ENODEV there for good arguments); n == 0 is FFHIP_OK.  Kernels: k_png_filter (a wave per row: the five
+ * sums by a wave reduction, the row above read from the source again, 16-byte stores inside the row), k_deflate_chunks (a workgroup of one
+ * wave per chunk: the body above, head table in LDS, tokens in scratch), a workgroup per picture or stream that scans the chunks' sizes,
+ * joins the Adler parts and writes the verdict, and a copy kernel with every store under cap.  No kernel waits for another workgroup.
+ * Sizes are held in 32 bits: an input whose bound reaches 2^32 bytes is FFHIP_EINVAL in both calls (the host entries have no such limit).
+ *
+ * ffhip_deflate_streams_device: n DEVICE buffers d_src[i][0, len[i]) to n zlib streams in d_dst[i][0, cap[i]), the twin of
+ *   ffhip_inflate_streams_device.  out_len[i], status[i] (FFHIP_OK or FFHIP_EDEFLATE_NOSPACE: out_len[i] is the size needed, no byte at or
+ *   beyond cap[i] is written) as ffhip_deflate gives them; a stream's verdict leaves its neighbours alone; returns the first code that is
+ *   not FFHIP_OK.  SYNCHRONISES the stream once a part (below), at the part's end. */
+int ffhip_deflate_streams_device(const uint8_t *const *d_src, const size_t *len, int n, uint8_t *const *d_dst, const size_t *cap,
+                                 size_t *out_len, int *status, void *stream);
+/* ffhip_png_encode_items: pictures of any sizes, channel counts and source forms in one batch, byte for byte ffhip_png_encode_picture's
+ *   files.  The batch is cut into parts by a byte budget over the filtered bytes (256 MiB -- a filtered byte takes six of scratch -- and at
+ *   most 4096 pictures; a picture beyond the budget is a part of its own); the call SYNCHRONISES the stream once a part.  len_out, status
+ *   (FFHIP_OK or FFHIP_EPNG_NOSPACE) and the return value as above.  ffhip_deflate_streams_device cuts its streams by the same budget and
+ *   synchronises once a part too. */
+typedef struct ffhip_png_encode_item {
+    ffhip_png_source src; /* pixels: device */
+    int32_t filter, reserved;
+    uint8_t *d_out;
+    size_t cap;
+} ffhip_png_encode_item;
+int ffhip_png_encode_items(const ffhip_png_encode_item *items, int n, size_t *len_out, int *status, void *stream);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
