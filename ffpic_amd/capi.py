@@ -53,6 +53,7 @@ EXPORTS = [
     "ffhip_jpeg_fdct_items", "ffhip_jpeg_huff_encode_items", "ffhip_jpeg_encode_items",
     "ffhip_deflate", "ffhip_deflate_bound", "ffhip_deflate_code_lengths", "ffhip_png_filtered_size", "ffhip_png_filter_picture",
     "ffhip_png_encode_bound", "ffhip_png_encode_picture", "ffhip_deflate_streams_device", "ffhip_png_encode_items",
+    "ffhip_vp8l_encode_bound", "ffhip_vp8l_encode_residual", "ffhip_vp8l_encode_picture", "ffhip_vp8l_encode_items",
 ]
 
 
@@ -69,6 +70,9 @@ FFHIP_JPEG_ENC_HEADER_MAX = 640
 FFHIP_DEFLATE_CHUNK = 16384
 FFHIP_PNG_FILTER_ADAPTIVE = 5
 FFHIP_EPNG_NOSPACE, FFHIP_EDEFLATE_NOSPACE = -1201, -1202
+FFHIP_VP8L_ENC_SUBTRACT_GREEN, FFHIP_VP8L_ENC_PREDICT = 1, 2
+FFHIP_VP8L_ENC_TILE_BITS, FFHIP_VP8L_ENC_CHUNK = 4, 4096
+FFHIP_EVP8L_NOSPACE = -1301
 
 
 class FfhipError(RuntimeError):
@@ -265,6 +269,11 @@ class PngSource(C.Structure):
 class PngEncodeItem(C.Structure):
     """ffhip_png_encode_item (device pointers)"""
     _fields_ = [("src", PngSource), ("filter", C.c_int32), ("reserved", C.c_int32), ("d_out", C.c_void_p), ("cap", C.c_size_t)]
+
+
+class Vp8lEncodeItem(C.Structure):
+    """ffhip_vp8l_encode_item (device pointers); its source is a PngSource"""
+    _fields_ = [("src", PngSource), ("flags", C.c_int32), ("reserved", C.c_int32), ("d_out", C.c_void_p), ("cap", C.c_size_t)]
 
 
 def png_source(pixels, width, height, row_stride, pixel_stride, chan, channels=None):
@@ -516,6 +525,11 @@ def lib():
     L.ffhip_png_encode_picture.argtypes = [C.POINTER(PngSource), ci, vp, sz, C.POINTER(sz)]
     L.ffhip_deflate_streams_device.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
     L.ffhip_png_encode_items.argtypes = [C.POINTER(PngEncodeItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
+    L.ffhip_vp8l_encode_bound.argtypes = [ci, ci]
+    L.ffhip_vp8l_encode_bound.restype = sz
+    L.ffhip_vp8l_encode_residual.argtypes = [C.POINTER(PngSource), ci, vp, vp]
+    L.ffhip_vp8l_encode_picture.argtypes = [C.POINTER(PngSource), ci, vp, sz, C.POINTER(sz)]
+    L.ffhip_vp8l_encode_items.argtypes = [C.POINTER(Vp8lEncodeItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
     for name in ("ffhip_inflate_upto", "ffhip_inflate_model"):    # exported, not in the public header (csrc/ffhip_png_internal.h)
         getattr(L, name).argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci]
     L.ffhip_inflate_model_mode.argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci, ci]

@@ -1394,3 +1394,45 @@ def png_encode_items(items, stream=None, strict=True):
     """ffhip_png_encode_items: `items` a list of capi.PngEncodeItem (device pictures) -> ([file length], [status]); the files are in the
     items' d_out.  With strict=False a file that does not fit its cap is its status (FFHIP_EPNG_NOSPACE) and its length the size it needs."""
     return _lengths_call("ffhip_png_encode_items", capi.PngEncodeItem, items, stream, strict)
+
+
+# ---- Lossless WebP encoding (include/ffpic_hip.h "Lossless WebP encoding"; DESIGN.md 4.34) ----
+def vp8l_encode_flags(predict=True, subtract_green=True):
+    return (capi.FFHIP_VP8L_ENC_PREDICT if predict else 0) | (capi.FFHIP_VP8L_ENC_SUBTRACT_GREEN if subtract_green else 0)
+
+
+def vp8l_encode_bound(width, height):
+    """ffhip_vp8l_encode_bound: a certain bound on the file's size (0: bad arguments).  Needs no device."""
+    return int(capi.lib().ffhip_vp8l_encode_bound(width, height))
+
+
+def vp8l_encode_residual(pixels, flags=3):
+    """ffhip_vp8l_encode_residual: host pixels (an array as png_host_source takes it, or a capi.PngSource of host memory) -> (the residual
+    ARGB words uint32 [H][W] as the file codes them, the tiles' modes uint8 [tile rows][tile columns] or None without
+    FFHIP_VP8L_ENC_PREDICT).  Needs no device."""
+    src = _png_src(pixels)
+    tile = 1 << capi.FFHIP_VP8L_ENC_TILE_BITS
+    res = np.zeros((src.height, src.width), np.uint32)
+    modes = np.zeros(((src.height + tile - 1) // tile, (src.width + tile - 1) // tile), np.uint8)
+    capi.check(capi.lib().ffhip_vp8l_encode_residual(C.byref(src), int(flags), _vp(res), _vp(modes)), "ffhip_vp8l_encode_residual")
+    return res, (modes if int(flags) & capi.FFHIP_VP8L_ENC_PREDICT else None)
+
+
+def vp8l_encode_picture(pixels, flags=3, cap=None):
+    """ffhip_vp8l_encode_picture: host pixels (as vp8l_encode_residual) to the lossless WebP file's bytes, the CPU model of
+    vp8l_encode_items.  cap: the output's size (the bound when None); -> bytes, or with cap given (rc, length, the cap bytes)."""
+    src = _png_src(pixels)
+    size = vp8l_encode_bound(src.width, src.height) if cap is None else int(cap)
+    out = np.zeros(max(size, 1), np.uint8)
+    n = C.c_size_t()
+    rc = capi.lib().ffhip_vp8l_encode_picture(C.byref(src), int(flags), _vp(out), size, C.byref(n))
+    if cap is not None:
+        return rc, n.value, out[:size].tobytes()
+    capi.check(rc, "ffhip_vp8l_encode_picture")
+    return out[:n.value].tobytes()
+
+
+def vp8l_encode_items(items, stream=None, strict=True):
+    """ffhip_vp8l_encode_items: `items` a list of capi.Vp8lEncodeItem (device pictures) -> ([file length], [status]); the files are in the
+    items' d_out.  With strict=False a file that does not fit its cap is its status (FFHIP_EVP8L_NOSPACE) and its length the size it needs."""
+    return _lengths_call("ffhip_vp8l_encode_items", capi.Vp8lEncodeItem, items, stream, strict)

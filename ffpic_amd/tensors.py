@@ -600,3 +600,58 @@ def encode_png(pictures, filter="adaptive", to_host=False):
     if to_host:
         files = [bytes(f.cpu().numpy()) for f in files]
     return files[0] if single else files
+
+
+def encode_webp_lossless(pictures, predict=True, subtract_green=True, to_host=False):
+    """Device pictures to lossless WebP files: a list of uint8 device tensors as encode_png takes them ([C,H,W] or [H,W,C] with C in 1..4:
+    grey, grey + alpha, RGB, RGBA; sides up to 16384), of any sizes and strides, in ONE ffhip_vp8l_encode_items call on the current stream
+    -> a list of 1-D uint8 device tensors (views of one allocation), or of bytes with to_host=True.  predict, subtract_green: the two
+    transforms, one value or one per picture.  The outputs start at half the bound; the files that need more (the call says how much) go
+    through a second call."""
+    import torch
+    single = isinstance(pictures, torch.Tensor)
+    pictures = [pictures] if single else list(pictures)
+    n = len(pictures)
+    flags = []
+    for name, value in (("predict", predict), ("subtract_green", subtract_green)):
+        values = list(value) if isinstance(value, (list, tuple)) else [value] * n
+        if len(values) != n or not all(isinstance(v, (bool, np.bool_)) for v in values):
+            raise ValueError(f"{name}: True or False, one value or one per picture")
+        flags.append(values)
+    flags = [ops.vp8l_encode_flags(p, g) for p, g in zip(*flags)]            # argument errors come before any device use
+    sources = [png_source_of(t) for t in pictures]
+    for s in sources:
+        if s.width > 16384 or s.height > 16384:
+            raise ValueError(f"encode_webp_lossless: sides of 1..16384, got {s.width} x {s.height}")
+    if n == 0:
+        return []
+    dev = torch.cuda.current_device()
+    capi.require_device(dev)
+    device = torch.device("cuda", dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    files, todo = [None] * n, list(range(n))
+    caps = [(ops.vp8l_encode_bound(s.width, s.height) // 2 + 255) & ~255 for s in sources]
+    for _ in range(2):
+        offs = np.concatenate([[0], np.cumsum([caps[i] for i in todo])]).astype(np.int64)
+        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
+        items = []
+        for k, i in enumerate(todo):
+            it = capi.Vp8lEncodeItem()
+            it.src, it.flags, it.d_out, it.cap = sources[i], flags[i], buf.data_ptr() + int(offs[k]), caps[i]
+            items.append(it)
+        lens, status = ops.vp8l_encode_items(items, stream, strict=False)
+        again = []
+        for k, i in enumerate(todo):
+            if status[k] == 0:
+                files[i] = buf[int(offs[k]):int(offs[k]) + lens[k]]
+            elif status[k] == capi.FFHIP_EVP8L_NOSPACE:
+                caps[i] = (lens[k] + 255) & ~255
+                again.append(i)
+            else:
+                capi.check(status[k], "ffhip_vp8l_encode_items")
+        todo = again
+        if not todo:
+            break
+    if to_host:
+        files = [bytes(f.cpu().numpy()) for f in files]
+    return files[0] if single else files

@@ -1739,6 +1739,75 @@ typedef struct ffhip_png_encode_item {
 } ffhip_png_encode_item;
 int ffhip_png_encode_items(const ffhip_png_encode_item *items, int n, size_t *len_out, int *status, void *stream);
 
+/* ---- Lossless WebP encoding (ffhip_vp8l_enc.c, ffhip_vp8l_enc_body.h, ffhip_vp8l_enc_gpu.hip) ----
+ * Pictures to complete lossless WebP files (RIFF / WEBP / VP8L): transforms, parse and prefix codes as kernels, the same body as host
+ * functions.  There is no byte-for-byte target outside the library: THE RULE is its own, a function of the input bytes alone, and host and
+ * device share it so that their files are equal byte for byte.
+ *   PICTURES    8 bits a sample, 1..4 channels (grey, grey + alpha, RGB, RGBA) by byte strides, sides 1..16384.  A pixel is the ARGB word
+ *               alpha << 24 | red << 16 | green << 8 | blue; grey is R = G = B, a missing alpha 255.  The header's alpha bit is set for 2
+ *               and 4 channels, its version is 0.  Colour under transparent pixels is kept.  The file: "RIFF", its size, "WEBP", "VP8L",
+ *               the chunk's size, the byte 2F, the bits; a zero byte behind an odd chunk, so the file's size is even.
+ *   TRANSFORMS  flags FFHIP_VP8L_ENC_SUBTRACT_GREEN and FFHIP_VP8L_ENC_PREDICT, either, both or none.  With both, green is subtracted from
+ *               red and blue first and prediction runs over that picture; the file lists them in this order.  With none the ARGB words are
+ *               coded as they are.  Prediction has square tiles of 1 << FFHIP_VP8L_ENC_TILE_BITS pixels.  A tile's mode 0..13 is the one with
+ *               the smallest sum, over the tile's pixels and their four channels, of the absolute values of the residual bytes (pixel less
+ *               prediction, modulo 256) read as signed; the lowest mode at equal sums.  What the format fixes counts the same for every mode:
+ *               the first pixel against FF000000, the top row from the left, the left column from above; the rightmost pixel's top-right
+ *               neighbour is its row's first pixel.  Neighbours are the (green-subtracted) source's own pixels.  The sub-image holds one
+ *               pixel a tile, FF000000 | mode << 8, coded as literals.
+ *   PARSE       the residual picture in scan order is cut into chunks of FFHIP_VP8L_ENC_CHUNK pixels, the last one shorter; a chunk is parsed
+ *               without another chunk's tokens, by steps of 64 positions.  A position tries distance 1, then distance width (the pixel above;
+ *               with width 1 the two are one candidate), where the picture has that many pixels in front of it, earlier chunks' included; a
+ *               match may run to the chunk's end and counts from 3 pixels on.  The longest wins, the first tried among equals; a position a
+ *               token of an earlier step covers tries nothing.  Then greedy: from the first uncovered position, a position with a match emits
+ *               it and skips its length, any other emits its word as a literal.  The distance codes are the smallest that decode to the
+ *               distance: 1 for the pixel above, 2 for the pixel to the left (any other distance would be distance + 120).  No colour cache.
+ *   CODES       one group of five prefix codes for the picture and one for the sub-image, no meta prefix image: green with the 24 length
+ *               prefixes (280 symbols), red, blue, alpha (256), distance (40); frequencies over all tokens of the image.  Lengths by the
+ *               rule of ffhip_deflate_code_lengths, limit 15.  An alphabet with no used symbol is written as the simple code of symbol 0, one
+ *               with one or two used symbols, all below 256, as the simple code of those (the lower first; a first symbol above 1 takes 8
+ *               bits).  Any other is a normal code: its lengths, all of them (no max_symbol), under the 19-symbol code (the same rule, limit 7,
+ *               as few of its lengths as the format's order allows, at least 4), run by run of equal values: zeros as 18 for 138 .. 11, then
+ *               17 for 10 .. 3, then singly; a value v once unless it is the last non-zero value written (8 at the start), then 16 for
+ *               6 .. 3 of the rest, then singly.  Codes are canonical.  A code with ONE used symbol has the empty word.
+ *   BOUND       4096 bytes for the head and the tables of both groups, 2 a tile, 60 bits a pixel, 2 bytes.  Bit positions are held in 64 bits.
+ * Every choice is a function of the input bytes alone. */
+#define FFHIP_VP8L_ENC_SUBTRACT_GREEN 0x1
+#define FFHIP_VP8L_ENC_PREDICT 0x2
+#define FFHIP_VP8L_ENC_TILE_BITS 4
+#define FFHIP_VP8L_ENC_CHUNK 4096
+#define FFHIP_EVP8L_NOSPACE (-1301) /* the file does not fit cap: len is the size it needs, nothing at or beyond cap was written */
+/* The source is the PNG encoder's record. */
+typedef ffhip_png_source ffhip_vp8l_source;
+/* Host entries; they need no device.
+ *   ffhip_vp8l_encode_bound     a CERTAIN bound on the file (BOUND above), 0 for bad arguments
+ *   ffhip_vp8l_encode_residual  the TRANSFORMS alone: residual[height][width] ARGB words as the file codes them, and with
+ *                               FFHIP_VP8L_ENC_PREDICT modes[tile rows][tile columns], a byte a tile (modes may be NULL without the flag)
+ *   ffhip_vp8l_encode_picture   HOST pixels to the file; *len its size; FFHIP_EVP8L_NOSPACE when that exceeds cap (no byte at or beyond
+ *                               out + cap is written) */
+size_t ffhip_vp8l_encode_bound(int width, int height);
+int ffhip_vp8l_encode_residual(const ffhip_vp8l_source *src, int flags, uint32_t *residual, uint8_t *modes);
+int ffhip_vp8l_encode_picture(const ffhip_vp8l_source *src, int flags, uint8_t *out, size_t cap, size_t *len);
+/* ffhip_vp8l_encode_items: pictures of any sizes, channel counts, source forms and flags in one batch, byte for byte
+ *   ffhip_vp8l_encode_picture's files.  The arrays are HOST arrays, read before the call returns; every check is made before anything is
+ *   enqueued (FFHIP_EINVAL, on a machine without a device too; FFHIP_ENODEV there for good arguments); n == 0 is FFHIP_OK.  len_out[i],
+ *   status[i] (FFHIP_OK or FFHIP_EVP8L_NOSPACE: len_out[i] is the size needed, no byte at or beyond cap is written); a picture's verdict leaves
+ *   its neighbours alone; returns the first code that is not FFHIP_OK.  The batch is cut into parts by a budget over the pixels (64 Mi pixels
+ *   -- a pixel takes sixteen bytes of scratch -- and at most 4096 pictures; a picture beyond the budget is a part of its own); the call
+ *   SYNCHRONISES the stream once a part.  Kernels: k_vp8l_enc_predict (a wave per tile: the 14 sums by a wave reduction, the residual words
+ *   16 bytes a store where the row allows), k_vp8l_enc_parse (a wave per chunk: candidates, the uniform greedy walk, the histogram in LDS,
+ *   then integer atomics into the picture's counters), k_vp8l_enc_codes (a wave per picture: lengths, codes, the file's head), k_vp8l_enc_count
+ *   and k_vp8l_enc_write (a wave per chunk: its tokens' bits counted, then written by atomicOr into zeroed words), k_vp8l_enc_scan (a workgroup
+ *   per picture: the chunks' bit positions, the sizes, the verdict) and a copy kernel with every store under cap.  No kernel waits for
+ *   another workgroup. */
+typedef struct ffhip_vp8l_encode_item {
+    ffhip_vp8l_source src; /* pixels: device */
+    int32_t flags, reserved;
+    uint8_t *d_out;
+    size_t cap;
+} ffhip_vp8l_encode_item;
+int ffhip_vp8l_encode_items(const ffhip_vp8l_encode_item *items, int n, size_t *len_out, int *status, void *stream);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
