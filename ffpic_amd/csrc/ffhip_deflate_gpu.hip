@@ -8,9 +8,11 @@
  *   k_deflate_scan    a workgroup per stream: the chunks' offsets (a prefix scan in a loop of its own), the Adler parts joined, the verdict
  *   k_deflate_copy    a workgroup per chunk: header, chunk and check value into the caller's buffer, every byte under cap
  * No kernel waits for another workgroup; every loop runs to a bound known at its entry.
+ * The host side is the encoders' common one: ffhip_parts_run, ffhip_items_run, ffhip_lengths_read; deflate_part's offsets are its own.
  */
 #include "ffhip_items.h"
-#include "ffhip_staged.h" /* ffhip_part_budget */
+#include "ffhip_parts.h"
+#include "ffhip_wave.h" /* wg_scan */
 #include "ffhip_deflate_internal.h"
 
 #include <string.h>
@@ -43,7 +45,7 @@ struct DefDst { /* per stream, behind the ffhip_def_stream records */
     u32 *chunk_off; /* per chunk: where its bytes start in the stream */
 };
 struct DefVerdict {
-    unsigned long long out_len;
+    unsigned long long file_len;
     int32_t status;
     u32 adler;
 };
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(DEF_WG) void k_deflate_scan(const ffhip_def_stream 
         const u32 c = turn * DEF_WG + threadIdx.x;
         const u32 v = c < s.n_wgs ? s.res[c].out_len : 0u;
         u32 total;
-        const u32 before = ffhip_def_wg_scan<DEF_WG>(v, wave_sum, &total);
+        const u32 before = wg_scan<DEF_WG>(v, wave_sum, &total);
         if (c < s.n_wgs) d.chunk_off[c] = (u32)carry + before;
         carry += total;
     }
@@ -70,8 +72,8 @@ __global__ __launch_bounds__(DEF_WG) void k_deflate_scan(const ffhip_def_stream 
             ffhip_def_adler_join(&a, &b, s.res[c].adler_a, s.res[c].adler_b, left < FFHIP_DEF_CHUNK ? left : FFHIP_DEF_CHUNK);
         }
         DefVerdict &r = verdict[blockIdx.x];
-        r.out_len = carry + 4;
-        r.status = r.out_len > d.cap ? FFHIP_EDEFLATE_NOSPACE : FFHIP_OK;
+        r.file_len = carry + 4;
+        r.status = r.file_len > d.cap ? FFHIP_EDEFLATE_NOSPACE : FFHIP_OK;
         r.adler = (b << 16) | a;
     }
 }
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(DEF_WG) void k_deflate_copy(DefChunkArgs a, const D
         if (at + k < d.cap) d.dst[at + k] = from[k];
     if (c == 0 && threadIdx.x < 2 && threadIdx.x < d.cap) d.dst[threadIdx.x] = threadIdx.x ? 0x01 : 0x78;
     if (c == s.n_wgs - 1 && threadIdx.x < 4) {
-        const unsigned long long o = verdict[item].out_len - 4 + threadIdx.x;
+        const unsigned long long o = verdict[item].file_len - 4 + threadIdx.x;
         if (o < d.cap) d.dst[o] = (uint8_t)(verdict[item].adler >> (24 - 8 * threadIdx.x));
     }
 }
@@ -107,15 +109,15 @@ int deflate_part(const uint8_t *const *d_src, const size_t *len, int n, uint8_t 
         s.src = d_src[i]; s.len = len[i];
         s.first_wg = (u32)total_chunks; s.n_wgs = (u32)ffhip_def_chunks(len[i]);
         total_chunks += s.n_wgs;
-        tok_words += (len[i] + 3) & ~(size_t)3;
+        tok_words += ffhip_up(len[i], 4);
         dst[(size_t)i].dst = d_dst[i]; dst[(size_t)i].cap = cap[i];
     }
     if (total_chunks > 0xffffffffULL) return FFHIP_EINVAL;
     /* the scratch: stream records and destinations (uploaded), the per-chunk table, offsets, results, verdicts, the output words (zeroed), tokens */
     const size_t rec_bytes = (size_t)n * sizeof(ffhip_def_stream), up_bytes = rec_bytes + (size_t)n * sizeof(DefDst);
     const size_t off_off = up_bytes + (size_t)total_chunks * 4, res_off = off_off + (size_t)total_chunks * 4;
-    const size_t ver_off = res_off + (size_t)total_chunks * sizeof(ffhip_def_result), ver_bytes = (size_t)n * sizeof(DefVerdict);
-    const size_t out_off = (ver_off + ver_bytes + 255) & ~(size_t)255, out_bytes = (size_t)total_chunks * FFHIP_DEF_OUT_BYTES;
+    const size_t ver_off = res_off + (size_t)total_chunks * sizeof(ffhip_def_result);
+    const size_t out_off = ffhip_up(ver_off + (size_t)n * sizeof(DefVerdict), 256), out_bytes = (size_t)total_chunks * FFHIP_DEF_OUT_BYTES;
     const size_t tok_off = out_off + out_bytes, end = tok_off + (size_t)tok_words * 4;
     std::vector<uint8_t> up(up_bytes);
     uint8_t *dev = nullptr;
@@ -128,7 +130,7 @@ int deflate_part(const uint8_t *const *d_src, const size_t *len, int n, uint8_t 
             s.out = (u32 *)(base + out_off + (size_t)s.first_wg * FFHIP_DEF_OUT_BYTES);
             s.res = (ffhip_def_result *)(base + res_off) + s.first_wg;
             dst[(size_t)i].chunk_off = (u32 *)(base + off_off) + s.first_wg;
-            tok_at += (len[i] + 3) & ~(size_t)3;
+            tok_at += ffhip_up(len[i], 4);
         }
         memcpy(up.data(), rec.data(), rec_bytes);
         memcpy(up.data() + rec_bytes, dst.data(), up_bytes - rec_bytes);
@@ -147,22 +149,9 @@ int deflate_part(const uint8_t *const *d_src, const size_t *len, int n, uint8_t 
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
     DefChunkArgs a;
     a.streams = d_rec; a.wg_item = d_table; a.wg_base = 0;
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_deflate_copy, dim3(grid_x), dim3(DEF_WG), 0, st, a, d_dsts, (const DefVerdict *)d_ver);
-    });
+    rc = ffhip_items_run(k_deflate_copy, total_chunks, DEF_WG, stream, a, d_dsts, (const DefVerdict *)d_ver);
     if (rc) return rc;
-    DefVerdict *h_ver = (DefVerdict *)ffhip_pinned_scratch(SCRATCH_PNG_ENC + 1, stream, ver_bytes);
-    if (!h_ver) return FFHIP_ENOMEM;
-    FFHIP_CHECK(hipMemcpyAsync(h_ver, d_ver, ver_bytes, hipMemcpyDeviceToHost, st), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-    int first = FFHIP_OK;
-    for (int i = 0; i < n; i++) {
-        out_len[i] = (size_t)h_ver[i].out_len;
-        status[i] = h_ver[i].status;
-        if (first == FFHIP_OK && status[i] != FFHIP_OK) first = status[i];
-    }
-    return first;
+    return ffhip_lengths_read(SCRATCH_PNG_ENC + 1, stream, d_ver, n, out_len, status);
 }
 
 } // namespace
@@ -171,10 +160,7 @@ int ffhip_deflate_chunks_enqueue(const ffhip_def_stream *d_streams, const uint32
 {
     DefChunkArgs a;
     a.streams = d_streams; a.wg_item = d_wg_item; a.wg_base = 0;
-    return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_deflate_chunks, dim3(grid_x), dim3(FFHIP_DEF_LANES), 0, (hipStream_t)stream, a);
-    });
+    return ffhip_items_run(k_deflate_chunks, total, FFHIP_DEF_LANES, stream, a);
 }
 
 extern "C" int ffhip_deflate_streams_device(const uint8_t *const *d_src, const size_t *len, int n, uint8_t *const *d_dst, const size_t *cap,
@@ -187,15 +173,7 @@ extern "C" int ffhip_deflate_streams_device(const uint8_t *const *d_src, const s
     }
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t budget = ffhip_part_budget(nullptr) / 4; /* a byte of input takes six of scratch */
-    int first_rc = FFHIP_OK;
-    for (int first = 0; first < n;) {
-        int cnt = 0;
-        size_t bytes = 0;
-        while (first + cnt < n && (cnt == 0 || bytes + len[first + cnt] <= budget)) bytes += len[first + cnt++];
-        const int rc = deflate_part(d_src + first, len + first, cnt, d_dst + first, cap + first, out_len + first, status + first, stream);
-        if (rc == FFHIP_EINVAL || rc == FFHIP_ENOMEM || rc == FFHIP_EIO || rc == FFHIP_ENODEV) return rc;
-        if (first_rc == FFHIP_OK) first_rc = rc;
-        first += cnt;
-    }
-    return first_rc;
+    return ffhip_parts_run(n, budget, FFHIP_PARTS_NO_CAP, [&](int i) { return len[i]; }, [&](int first, int cnt) {
+        return deflate_part(d_src + first, len + first, cnt, d_dst + first, cap + first, out_len + first, status + first, stream);
+    });
 }

@@ -26,32 +26,8 @@ typedef struct ffhip_def_stream {
     uint32_t first_wg, n_wgs; /* its chunks among the call's */
 } ffhip_def_stream;
 #ifdef __cplusplus
-/* k_deflate_chunks over `total` chunks of the device records; wg_item: the per-chunk table (k_items_table<ffhip_def_stream>'s).  Only enqueues */
+/* k_deflate_chunks over `total` chunks of the device records; wg_item: the per-chunk table (k_items_table<ffhip_def_stream>'s, or the chunk half of k_items_tables2's).  Only enqueues */
 int ffhip_deflate_chunks_enqueue(const ffhip_def_stream *d_streams, const uint32_t *d_wg_item, unsigned long long total, void *stream);
-#endif
-
-#ifdef __HIPCC__
-/* exclusive prefix sum of v over a workgroup of WG threads; *total: the sum; wave_sum: WG / 64 words of LDS */
-template <int WG> __device__ static inline uint32_t ffhip_def_wg_scan(uint32_t v, uint32_t *wave_sum, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int w = 0; w < WG / 64; w++) {
-        if (w < wave) before += wave_sum[w];
-        all += wave_sum[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
 #endif
 
 #endif

@@ -16,9 +16,12 @@
  *   k_jenc_ff_scan        a workgroup per picture: their prefix sums, the file's size, the item's verdict
  *   k_jenc_copy           a workgroup per KiB of stream: header and stuffed stream into the caller's buffer, every byte under cap
  * No kernel waits for another workgroup; every loop runs to a bound known at its entry.
+ * The host side is the encoders' common one: ffhip_parts_run cuts ffhip_jpeg_encode_items into parts, k_items_tables2 writes
+ * the colour and FDCT tables, ffhip_items_run launches, ffhip_records_fetch is the first synchronisation, ffhip_lengths_read the second.
  */
 #include "ffhip_items.h"
-#include "ffhip_staged.h" /* ffhip_part_budget */
+#include "ffhip_parts.h"
+#include "ffhip_wave.h" /* wg_scan */
 #include "ffhip_jpeg_enc_internal.h"
 
 #include <string.h>
@@ -47,14 +50,6 @@ struct JencArgs {
     const u32 *wg_item;
     u32 wg_base;
 };
-
-__global__ __launch_bounds__(256) void k_jenc_fdct_table(const JencDesc *desc, u32 *color_item, u32 *fdct_item)
-{
-    const u32 item = blockIdx.x;
-    const u32 f0 = desc[item].color_first_wg, n0 = desc[item].color_n_wgs, f1 = desc[item].fdct_first_wg, n1 = desc[item].fdct_n_wgs;
-    for (u32 k = threadIdx.x; k < n0; k += 256) color_item[f0 + k] = item;
-    for (u32 k = threadIdx.x; k < n1; k += 256) fdct_item[f1 + k] = item;
-}
 
 /* pixel (col, row) of the source, both inside the picture */
 __device__ __forceinline__ void load_rgb(const JencDesc &d, int col, int row, int &r, int &g, int &b)
@@ -223,10 +218,9 @@ int fdct_items_impl(const ffhip_jpeg_fdct_item *items, int n, void *stream, bool
     if (total_color > 0xffffffffULL || total_fdct > 0xffffffffULL) return FFHIP_EINVAL; /* the tables' entries are 32-bit workgroup indices */
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     if (n == 0) return FFHIP_OK;
-    hipStream_t st = (hipStream_t)stream;
     const size_t desc_bytes = (size_t)n * sizeof(JencDesc);
     const size_t table_words = (size_t)total_color + (size_t)total_fdct;
-    const size_t planes_off = (desc_bytes + table_words * 4 + 255) & ~(size_t)255;
+    const size_t planes_off = ffhip_up(desc_bytes + table_words * 4, 256);
     uint8_t *dev = nullptr;
     const int rc = ffhip_items_stage(SCRATCH_JPEG_ENC, stream, desc.data(), desc_bytes, table_words, planes_off + plane_bytes - desc_bytes - table_words * 4, &dev,
                                      [&](uint8_t *base) {
@@ -241,18 +235,15 @@ int fdct_items_impl(const ffhip_jpeg_fdct_item *items, int n, void *stream, bool
     if (rc) return rc;
     const JencDesc *d_desc = (const JencDesc *)dev;
     u32 *d_color = (u32 *)(dev + desc_bytes), *d_fdct = d_color + total_color;
-    hipLaunchKernelGGL(k_jenc_fdct_table, dim3((unsigned)n), dim3(256), 0, st, d_desc, d_color, d_fdct);
+    hipLaunchKernelGGL((k_items_tables2<JencDesc, JencDesc, &JencDesc::color_first_wg, &JencDesc::color_n_wgs, &JencDesc::fdct_first_wg, &JencDesc::fdct_n_wgs>),
+                       dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, d_desc, d_desc, d_color, d_fdct);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    for (int pass = 0; pass < 2; pass++) {
-        const int lrc = ffhip_items_launch(0, pass ? total_fdct : total_color, [&](unsigned grid_x, u32 wg_base) {
-            JencArgs a;
-            a.desc = d_desc; a.wg_item = pass ? d_fdct : d_color; a.wg_base = wg_base;
-            if (pass) hipLaunchKernelGGL(k_jpeg_fdct_islow, dim3(grid_x), dim3(JE_WG), 0, st, a);
-            else hipLaunchKernelGGL(k_jpeg_color_downsample, dim3(grid_x), dim3(JE_WG), 0, st, a);
-        });
-        if (lrc) return lrc;
-    }
-    return FFHIP_OK;
+    JencArgs a;
+    a.desc = d_desc; a.wg_item = d_color; a.wg_base = 0;
+    const int lrc = ffhip_items_run(k_jpeg_color_downsample, total_color, JE_WG, stream, a);
+    if (lrc) return lrc;
+    a.wg_item = d_fdct;
+    return ffhip_items_run(k_jpeg_fdct_islow, total_fdct, JE_WG, stream, a);
 }
 
 /* ------------------------------------------------------------------------------------------------ coefficients to files */
@@ -381,28 +372,6 @@ __device__ __forceinline__ u32 word_ff(const JhuffStream &s, unsigned long long 
     return ff;
 }
 
-/* exclusive prefix sum of v over the workgroup; *total: the sum */
-__device__ __forceinline__ u32 wg_scan(u32 v, u32 *wave_sum, u32 *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u32 o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    u32 before = 0, all = 0;
-    for (int w = 0; w < JE_WG / 64; w++) {
-        if (w < wave) before += wave_sum[w];
-        all += wave_sum[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(JE_WG) void k_jenc_ff_count(JhuffArgs a)
 {
     __shared__ u32 wave_sum[JE_WG / 64];
@@ -412,7 +381,7 @@ __global__ __launch_bounds__(JE_WG) void k_jenc_ff_count(JhuffArgs a)
     const u32 chunk = wg - s.first_wg;
     u32 w, total;
     const u32 ff = word_ff(s, (unsigned long long)chunk * JE_CHUNK + 4u * threadIdx.x, w);
-    wg_scan((u32)__builtin_popcount(ff), wave_sum, &total);
+    wg_scan<JE_WG>((u32)__builtin_popcount(ff), wave_sum, &total);
     if (threadIdx.x == 0) s.chunk_ff[chunk] = total;
 }
 
@@ -428,7 +397,7 @@ __global__ __launch_bounds__(JE_WG) void k_jenc_ff_scan(const JhuffDesc *desc, c
         const u32 c = turn * JE_WG + threadIdx.x;
         const u32 v = c < s.n_wgs ? s.chunk_ff[c] : 0u;
         u32 total;
-        const u32 before = wg_scan(v, wave_sum, &total);
+        const u32 before = wg_scan<JE_WG>(v, wave_sum, &total);
         if (c < s.n_wgs) s.chunk_ff[c] = (u32)carry + before;
         carry += total;
     }
@@ -454,7 +423,7 @@ __global__ __launch_bounds__(JE_WG) void k_jenc_copy(JhuffArgs a)
     const unsigned long long at = (unsigned long long)chunk * JE_CHUNK + 4u * threadIdx.x;
     u32 w, total;
     const u32 ff = word_ff(s, at, w);
-    const u32 before = wg_scan((u32)__builtin_popcount(ff), wave_sum, &total);
+    const u32 before = wg_scan<JE_WG>((u32)__builtin_popcount(ff), wave_sum, &total);
     unsigned long long o = d.header_len + at + s.chunk_ff[chunk] + before;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -506,7 +475,7 @@ int huff_items_impl(const ffhip_jpeg_huff_item *items, int n, size_t *len_out, i
     const size_t desc_bytes = (size_t)n * sizeof(JhuffDesc), tab_bytes = 2 * JE_TAB_WORDS * sizeof(u32);
     std::vector<uint8_t> rec(desc_bytes + tab_bytes);
     ffhip_jenc_code_tables((uint32_t *)(rec.data() + desc_bytes));
-    const size_t pos_off = (rec.size() + (size_t)total_wgs * 4 + 255) & ~(size_t)255;
+    const size_t pos_off = ffhip_up(rec.size() + (size_t)total_wgs * 4, 256);
     const size_t res_off = pos_off + (size_t)total_blocks * 8, res_bytes = (size_t)n * sizeof(JhuffResult);
     uint8_t *dev = nullptr;
     int rc = ffhip_items_stage(SCRATCH_JPEG_ENC + 1, stream, rec.data(), rec.size(), (size_t)total_wgs, res_off + res_bytes - rec.size() - (size_t)total_wgs * 4, &dev,
@@ -526,18 +495,14 @@ int huff_items_impl(const ffhip_jpeg_huff_item *items, int n, size_t *len_out, i
     FFHIP_CHECK(hipMemsetAsync(a.res, 0, res_bytes, st), FFHIP_EIO);
     hipLaunchKernelGGL(k_items_table<JhuffDesc>, dim3((unsigned)n), dim3(256), 0, st, a.desc, d_block_item);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    rc = ffhip_items_launch(0, total_wgs, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_jenc_blocks<false>, dim3(grid_x), dim3(JE_WG), 0, st, a);
-    });
+    rc = ffhip_items_run(k_jenc_blocks<false>, total_wgs, JE_WG, stream, a);
     if (rc) return rc;
     hipLaunchKernelGGL(k_jenc_positions, dim3((unsigned)n), dim3(JE_WG), 0, st, a.desc, a.res);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
     /* the streams' sizes: the first of the call's two synchronisations */
-    JhuffResult *h_res = (JhuffResult *)ffhip_pinned_scratch(SCRATCH_JPEG_ENC + 3, stream, res_bytes);
-    if (!h_res) return FFHIP_ENOMEM;
-    FFHIP_CHECK(hipMemcpyAsync(h_res, a.res, res_bytes, hipMemcpyDeviceToHost, st), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
+    const JhuffResult *h_res = nullptr;
+    rc = ffhip_records_fetch(SCRATCH_JPEG_ENC + 3, stream, a.res, n, &h_res);
+    if (rc) return rc;
 
     /* second scratch, sized by the counted totals: the stream records (uploaded), the per-chunk table, chunk_ff, then words and masks (zeroed) */
     std::vector<JhuffStream> str((size_t)n);
@@ -552,11 +517,11 @@ int huff_items_impl(const ffhip_jpeg_huff_item *items, int n, size_t *len_out, i
         words_at[(size_t)i] = zero_bytes;
         zero_bytes += (size_t)s.n_wgs * JE_CHUNK + 64; /* a block's closing word may lie in the four bytes behind the stream */
         mask_at[(size_t)i] = zero_bytes;
-        zero_bytes += (((size_t)s.n_wgs * JE_CHUNK / 8) + 64) & ~(size_t)63;
+        zero_bytes += ffhip_up((size_t)s.n_wgs * JE_CHUNK / 8 + 1, 64);
     }
     if (total_chunks > 0xffffffffULL) return FFHIP_EINVAL;
     const size_t str_bytes = (size_t)n * sizeof(JhuffStream);
-    const size_t ff_off = str_bytes + (size_t)total_chunks * 4, zero_off = (ff_off + (size_t)total_chunks * 4 + 255) & ~(size_t)255;
+    const size_t ff_off = str_bytes + (size_t)total_chunks * 4, zero_off = ffhip_up(ff_off + (size_t)total_chunks * 4, 256);
     uint8_t *dev2 = nullptr;
     rc = ffhip_items_stage(SCRATCH_JPEG_ENC + 2, stream, str.data(), str_bytes, (size_t)total_chunks, zero_off + zero_bytes - str_bytes - (size_t)total_chunks * 4, &dev2,
                            [&](uint8_t *base) {
@@ -573,34 +538,17 @@ int huff_items_impl(const ffhip_jpeg_huff_item *items, int n, size_t *len_out, i
     FFHIP_CHECK(hipMemsetAsync(dev2 + zero_off, 0, zero_bytes, st), FFHIP_EIO);
     hipLaunchKernelGGL(k_items_table<JhuffStream>, dim3((unsigned)n), dim3(256), 0, st, a.str, d_chunk_item);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    rc = ffhip_items_launch(0, total_wgs, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_jenc_blocks<true>, dim3(grid_x), dim3(JE_WG), 0, st, a);
-    });
+    rc = ffhip_items_run(k_jenc_blocks<true>, total_wgs, JE_WG, stream, a);
     if (rc) return rc;
     a.wg_item = d_chunk_item;
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_jenc_ff_count, dim3(grid_x), dim3(JE_WG), 0, st, a);
-    });
+    rc = ffhip_items_run(k_jenc_ff_count, total_chunks, JE_WG, stream, a);
     if (rc) return rc;
     hipLaunchKernelGGL(k_jenc_ff_scan, dim3((unsigned)n), dim3(JE_WG), 0, st, a.desc, a.str, a.res);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_jenc_copy, dim3(grid_x), dim3(JE_WG), 0, st, a);
-    });
+    rc = ffhip_items_run(k_jenc_copy, total_chunks, JE_WG, stream, a);
     if (rc) return rc;
     /* lengths and verdicts: the second synchronisation */
-    FFHIP_CHECK(hipMemcpyAsync(h_res, a.res, res_bytes, hipMemcpyDeviceToHost, st), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-    int first = FFHIP_OK;
-    for (int i = 0; i < n; i++) {
-        len_out[i] = (size_t)h_res[i].file_len;
-        status[i] = h_res[i].status;
-        if (first == FFHIP_OK && status[i] != FFHIP_OK) first = status[i];
-    }
-    return first;
+    return ffhip_lengths_read(SCRATCH_JPEG_ENC + 3, stream, (const JhuffResult *)a.res, n, len_out, status);
 }
 
 } // namespace
@@ -634,12 +582,10 @@ extern "C" int ffhip_jpeg_encode_items(const ffhip_jpeg_encode_item *items, int 
     }
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t budget = ffhip_part_budget(nullptr);
-    int first_rc = FFHIP_OK;
-    for (int first = 0; first < n;) {
-        /* a part: pictures while their coefficient planes fit the budget; a picture beyond it is a part of its own */
-        int cnt = 0;
+    /* a part: pictures while their coefficient planes fit the budget */
+    return ffhip_parts_run(n, budget, FFHIP_PARTS_NO_CAP, [&](int i) { return coef_bytes[(size_t)i]; }, [&](int first, int cnt) -> int {
         size_t bytes = 0;
-        while (first + cnt < n && (cnt == 0 || bytes + coef_bytes[(size_t)(first + cnt)] <= budget)) bytes += coef_bytes[(size_t)(first + cnt++)];
+        for (int i = first; i < first + cnt; i++) bytes += coef_bytes[(size_t)i];
         int16_t *planes = (int16_t *)ffhip_scratch(SCRATCH_JPEG_ENC + 4, stream, bytes / 4 + 16);
         if (!planes) return FFHIP_ENOMEM;
         size_t at = 0;
@@ -651,12 +597,8 @@ extern "C" int ffhip_jpeg_encode_items(const ffhip_jpeg_encode_item *items, int 
             hf[(size_t)i].d_coef_y = y; hf[(size_t)i].d_coef_u = u; hf[(size_t)i].d_coef_v = v;
             at += coef_bytes[(size_t)i] / 2;
         }
-        int rc = fdct_items_impl(fd.data() + first, cnt, stream, true);
-        if (rc) return rc;
-        rc = huff_items_impl(hf.data() + first, cnt, len_out + first, status + first, stream, true);
-        if (rc == FFHIP_EINVAL || rc == FFHIP_ENOMEM || rc == FFHIP_EIO || rc == FFHIP_ENODEV) return rc;
-        if (first_rc == FFHIP_OK) first_rc = rc;
-        first += cnt;
-    }
-    return first_rc;
+        const int rc = fdct_items_impl(fd.data() + first, cnt, stream, true);
+        if (rc) return rc; /* the call's own codes only: every one of them ends the call */
+        return huff_items_impl(hf.data() + first, cnt, len_out + first, status + first, stream, true);
+    });
 }

@@ -1,8 +1,9 @@
 /*
  * ffhip_png_enc_gpu.hip -- the PNG encoder on the device (include/ffpic_hip.h "PNG encoding").  The rule is
  * ffhip_png_enc_body.h's and ffhip_deflate_body.h's, shared with the host functions of ffhip_png_enc.c and ffhip_deflate.c.
- *   k_png_enc_tables  a workgroup per picture: its index over its rows and its chunks in the two per-workgroup tables
- *   k_png_filter      a wave per row: the five sums of the adaptive choice by a wave reduction (the row above is read from the source again),
+ *   k_items_tables2   (ffhip_items.h) a workgroup per picture: its index over its rows (PeDesc) and its chunks (ffhip_def_stream) in the two
+ *                     per-workgroup tables
+ *   k_png_filter     a wave per row: the five sums of the adaptive choice by a wave reduction (the row above is read from the source again),
  *                     then the filtered row into the scratch, 16 bytes a store between the row's first and last 16-byte boundary
  *   k_deflate_chunks  (ffhip_deflate_gpu.hip) a wave per chunk of the filtered picture
  *   k_png_enc_scan    a workgroup per picture: the chunks' offsets in the file, every IDAT's CRC-32 from its bytes' CRC-32, the Adler parts
@@ -10,9 +11,11 @@
  *   k_png_enc_copy    a workgroup per chunk: its IDAT into the caller's buffer -- the first with signature and IHDR in front, the last with
  *                     the Adler IDAT and IEND behind -- every byte under cap
  * No kernel waits for another workgroup; every loop runs to a bound known at its entry.
+ * The host side is the encoders' common one: ffhip_parts_run, ffhip_items_run, ffhip_lengths_read; encode_part's offsets are its own.
  */
 #include "ffhip_items.h"
-#include "ffhip_staged.h" /* ffhip_part_budget */
+#include "ffhip_parts.h"
+#include "ffhip_wave.h" /* wg_scan */
 #include "ffhip_png_enc_internal.h"
 
 #include <string.h>
@@ -46,14 +49,6 @@ struct PeArgs {
     PeVerdict *verdict;
     u32 wg_base;
 };
-
-__global__ __launch_bounds__(256) void k_png_enc_tables(const PeDesc *desc, const ffhip_def_stream *streams, u32 *row_item, u32 *chunk_item)
-{
-    const u32 item = blockIdx.x;
-    const u32 r0 = desc[item].row_first, rn = desc[item].row_n, c0 = streams[item].first_wg, cn = streams[item].n_wgs;
-    for (u32 k = threadIdx.x; k < rn; k += 256) row_item[r0 + k] = item;
-    for (u32 k = threadIdx.x; k < cn; k += 256) chunk_item[c0 + k] = item;
-}
 
 __global__ __launch_bounds__(64) void k_png_filter(PeArgs a)
 {
@@ -123,7 +118,7 @@ __global__ __launch_bounds__(PE_WG) void k_png_enc_scan(PeArgs a)
             s.res[c].crc = ffhip_pe_idat_crc(c == 0, n, s.res[c].crc); /* from the bytes' to the chunk's */
         }
         u32 total;
-        const u32 before = ffhip_def_wg_scan<PE_WG>(v, wave_sum, &total);
+        const u32 before = wg_scan<PE_WG>(v, wave_sum, &total);
         if (c < s.n_wgs) d.chunk_off[c] = (u32)carry + before;
         carry += total;
     }
@@ -193,7 +188,7 @@ int encode_part(const ffhip_png_encode_item *items, int n, size_t *len_out, int 
         s.first_wg = (u32)total_chunks; s.n_wgs = (u32)ffhip_def_chunks(d.flen);
         total_rows += d.row_n; total_chunks += s.n_wgs;
         filt_at[(size_t)i] = filt_bytes;
-        filt_bytes += ((size_t)d.flen + 15) & ~(size_t)15;
+        filt_bytes += ffhip_up((size_t)d.flen, 16);
     }
     if (total_rows > 0xffffffffULL || total_chunks > 0xffffffffULL) return FFHIP_EINVAL;
     /* the scratch: picture and stream records (uploaded), the two per-workgroup tables, offsets, results, verdicts, the chunks' output words
@@ -201,9 +196,9 @@ int encode_part(const ffhip_png_encode_item *items, int n, size_t *len_out, int 
     const size_t desc_bytes = (size_t)n * sizeof(PeDesc), up_bytes = desc_bytes + (size_t)n * sizeof(ffhip_def_stream);
     const size_t table_words = (size_t)total_rows + (size_t)total_chunks;
     const size_t off_off = up_bytes + table_words * 4, res_off = off_off + (size_t)total_chunks * 4;
-    const size_t ver_off = (res_off + (size_t)total_chunks * sizeof(ffhip_def_result) + 7) & ~(size_t)7, ver_bytes = (size_t)n * sizeof(PeVerdict);
-    const size_t out_off = (ver_off + ver_bytes + 255) & ~(size_t)255, out_bytes = (size_t)total_chunks * FFHIP_DEF_OUT_BYTES;
-    const size_t filt_off = (out_off + out_bytes + 255) & ~(size_t)255, tok_off = filt_off + filt_bytes, end = tok_off + filt_bytes * 4;
+    const size_t ver_off = ffhip_up(res_off + (size_t)total_chunks * sizeof(ffhip_def_result), 8);
+    const size_t out_off = ffhip_up(ver_off + (size_t)n * sizeof(PeVerdict), 256), out_bytes = (size_t)total_chunks * FFHIP_DEF_OUT_BYTES;
+    const size_t filt_off = ffhip_up(out_off + out_bytes, 256), tok_off = filt_off + filt_bytes, end = tok_off + filt_bytes * 4;
     std::vector<uint8_t> up(up_bytes);
     uint8_t *dev = nullptr;
     int rc = ffhip_items_stage(SCRATCH_PNG_ENC, stream, up.data(), up_bytes, table_words, end - up_bytes - table_words * 4, &dev, [&](uint8_t *base) {
@@ -225,35 +220,20 @@ int encode_part(const ffhip_png_encode_item *items, int n, size_t *len_out, int 
     a.desc = (const PeDesc *)dev; a.streams = (const ffhip_def_stream *)(dev + desc_bytes); a.verdict = (PeVerdict *)(dev + ver_off);
     u32 *d_row_item = (u32 *)(dev + up_bytes), *d_chunk_item = d_row_item + total_rows;
     FFHIP_CHECK(hipMemsetAsync(dev + out_off, 0, out_bytes, st), FFHIP_EIO);
-    hipLaunchKernelGGL(k_png_enc_tables, dim3((unsigned)n), dim3(256), 0, st, a.desc, a.streams, d_row_item, d_chunk_item);
+    hipLaunchKernelGGL((k_items_tables2<PeDesc, ffhip_def_stream, &PeDesc::row_first, &PeDesc::row_n, &ffhip_def_stream::first_wg, &ffhip_def_stream::n_wgs>),
+                       dim3((unsigned)n), dim3(256), 0, st, a.desc, a.streams, d_row_item, d_chunk_item);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
     a.wg_item = d_row_item;
-    rc = ffhip_items_launch(0, total_rows, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_png_filter, dim3(grid_x), dim3(64), 0, st, a);
-    });
+    rc = ffhip_items_run(k_png_filter, total_rows, 64, stream, a);
     if (rc) return rc;
     rc = ffhip_deflate_chunks_enqueue(a.streams, d_chunk_item, total_chunks, stream);
     if (rc) return rc;
     a.wg_item = d_chunk_item; a.wg_base = 0;
     hipLaunchKernelGGL(k_png_enc_scan, dim3((unsigned)n), dim3(PE_WG), 0, st, a);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_png_enc_copy, dim3(grid_x), dim3(PE_WG), 0, st, a);
-    });
+    rc = ffhip_items_run(k_png_enc_copy, total_chunks, PE_WG, stream, a);
     if (rc) return rc;
-    PeVerdict *h_ver = (PeVerdict *)ffhip_pinned_scratch(SCRATCH_PNG_ENC + 1, stream, ver_bytes);
-    if (!h_ver) return FFHIP_ENOMEM;
-    FFHIP_CHECK(hipMemcpyAsync(h_ver, a.verdict, ver_bytes, hipMemcpyDeviceToHost, st), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-    int first = FFHIP_OK;
-    for (int i = 0; i < n; i++) {
-        len_out[i] = (size_t)h_ver[i].file_len;
-        status[i] = h_ver[i].status;
-        if (first == FFHIP_OK && status[i] != FFHIP_OK) first = status[i];
-    }
-    return first;
+    return ffhip_lengths_read(SCRATCH_PNG_ENC + 1, stream, a.verdict, n, len_out, status);
 }
 
 } // namespace
@@ -265,21 +245,8 @@ extern "C" int ffhip_png_encode_items(const ffhip_png_encode_item *items, int n,
         if (!item_ok(items[i])) return FFHIP_EINVAL;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t budget = ffhip_part_budget(nullptr) / 4; /* a filtered byte takes six of scratch: itself, its token word, its chunk's output */
-    int first_rc = FFHIP_OK;
-    for (int first = 0; first < n;) {
-        /* a part: up to PE_PART_ITEMS pictures while their filtered bytes fit the budget; a picture beyond it is a part of its own */
-        int cnt = 0;
-        size_t bytes = 0;
-        while (first + cnt < n && cnt < PE_PART_ITEMS) {
-            const size_t flen = (size_t)ffhip_pe_filtered_len(items[first + cnt].src.width, items[first + cnt].src.height, items[first + cnt].src.channels);
-            if (cnt && bytes + flen > budget) break;
-            bytes += flen;
-            cnt++;
-        }
-        const int rc = encode_part(items + first, cnt, len_out + first, status + first, stream);
-        if (rc == FFHIP_EINVAL || rc == FFHIP_ENOMEM || rc == FFHIP_EIO || rc == FFHIP_ENODEV) return rc;
-        if (first_rc == FFHIP_OK) first_rc = rc;
-        first += cnt;
-    }
-    return first_rc;
+    /* a part: up to PE_PART_ITEMS pictures while their filtered bytes fit the budget */
+    return ffhip_parts_run(n, budget, PE_PART_ITEMS,
+                           [&](int i) { return (size_t)ffhip_pe_filtered_len(items[i].src.width, items[i].src.height, items[i].src.channels); },
+                           [&](int first, int cnt) { return encode_part(items + first, cnt, len_out + first, status + first, stream); });
 }

@@ -267,7 +267,7 @@ int png_front_device(const std::vector<PngPartFile> &part, size_t rows_bytes, co
         const ffhip_png_file &f = pf[(size_t)part[k].idx];
         host_way[k] = (char)ffhip_png_short_palette(&f.info);
         own_off[k] = tail; /* filtered bytes, or the stream */
-        tail += ffhip_up16(host_way[k] ? (size_t)f.info.filtered_bytes : f.idat_bytes);
+        tail += ffhip_up(host_way[k] ? (size_t)f.info.filtered_bytes : f.idat_bytes, 16);
         if (!host_way[k]) { n_dev++; z_bytes += f.idat_bytes; }
     }
     const size_t rec_off = tail, rec_bytes = n_dev * sizeof(FfhipInflateRec);
@@ -424,7 +424,7 @@ extern "C" int ffhip_png_decode_files_device_ex(const uint8_t *const *files, con
         size_t rows = 0, palettes = 0;
         for (; i < n; i++) {
             if (status[i]) continue;
-            const size_t need = ffhip_up16((size_t)pf[(size_t)i].info.filtered_bytes);
+            const size_t need = ffhip_up((size_t)pf[(size_t)i].info.filtered_bytes, 16);
             if (!part.empty() && rows + need > budget) break;
             part.push_back({i, rows, palettes});
             rows += need;

@@ -7,6 +7,7 @@
 #define FFHIP_STAGED_H
 
 #include "ffhip_items.h"
+#include "ffhip_parts.h" /* ffhip_part_budget */
 #include "ffhip_wave.h"
 
 #include <algorithm>
@@ -41,13 +42,6 @@ struct StageClock {
         }
     }
 };
-
-/* a *_PART_BYTES switch's value -> a part's budget */
-inline size_t ffhip_part_budget(const char *v)
-{
-    const long long b = v ? atoll(v) : 0;
-    return b > 0 ? (size_t)b : (size_t)1 << 30;
-}
 
 /* behind a part's last enqueue; rc is the part's so far -> the call's */
 inline int ffhip_part_end(int rc, void *stream, StageClock &clock)
@@ -106,8 +100,6 @@ template <class Desc, class Launch> int ffhip_gather_launch(int kind, void *stre
 }
 
 inline int ffhip_host_threads(int n_threads) { return n_threads < 1 ? 1 : n_threads > 64 ? 64 : n_threads; }
-
-inline size_t ffhip_up16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 /* what a gather kernel asks of a BGRA output: whole 16-byte stores */
 inline bool ffhip_bgra_takes_stores16(const uint8_t *p, int64_t pitch, int64_t width)

@@ -1,7 +1,7 @@
 /*
  * ffhip_vp8l_enc_gpu.hip -- the lossless WebP encoder on the device (include/ffpic_hip.h "Lossless WebP encoding").  The
  * rule is ffhip_vp8l_enc_body.h's, shared with the host functions of ffhip_vp8l_enc.c.
- *   k_vp8l_enc_tables   a workgroup per picture: its index over its tiles and its chunks in the two per-workgroup tables
+ *   k_items_tables2     (ffhip_items.h) a workgroup per picture: its index over its tiles and its chunks in the two per-workgroup tables
  *   k_vp8l_enc_predict  a wave per tile: the 14 sums of the choice by a wave reduction (neighbours are read from the source again), the mode
  *                       into the sub-image, the residual words into the scratch picture, 16 bytes a store where the row allows
  *   k_vp8l_enc_parse    a wave per chunk: candidates, the uniform greedy walk, a token word a position in scratch, the histogram in LDS and
@@ -12,9 +12,11 @@
  *   k_vp8l_enc_write    a wave per chunk: its tokens' bits by atomicOr at a wave prefix sum's positions into the file's zeroed words
  *   k_vp8l_enc_copy     a workgroup per chunk: its share of the file into the caller's buffer, every byte under cap
  * No kernel waits for another workgroup; every loop runs to a bound known at its entry.
+ * The host side is the encoders' common one: ffhip_parts_run, ffhip_items_run, ffhip_lengths_read; encode_part's offsets are its own.
  */
 #include "ffhip_items.h"
-#include "ffhip_staged.h" /* ffhip_part_budget */
+#include "ffhip_parts.h"
+#include "ffhip_wave.h" /* wg_scan */
 #include "ffhip_vp8l_enc_internal.h"
 
 #include <string.h>
@@ -48,14 +50,6 @@ struct VeArgs {
     VeVerdict *verdict;
     u32 wg_base;
 };
-
-__global__ __launch_bounds__(256) void k_vp8l_enc_tables(const VeDesc *desc, u32 *tile_item, u32 *chunk_item)
-{
-    const u32 item = blockIdx.x;
-    const u32 t0 = desc[item].tile_first, tn = desc[item].tile_n, c0 = desc[item].first_wg, cn = desc[item].n_wgs;
-    for (u32 k = threadIdx.x; k < tn; k += 256) tile_item[t0 + k] = item;
-    for (u32 k = threadIdx.x; k < cn; k += 256) chunk_item[c0 + k] = item;
-}
 
 __global__ __launch_bounds__(64) void k_vp8l_enc_predict(VeArgs a)
 {
@@ -147,7 +141,7 @@ __global__ __launch_bounds__(VE_WG) void k_vp8l_enc_scan(VeArgs a)
         const u32 c = turn * VE_WG + threadIdx.x;
         const u32 v = c < d.n_wgs ? d.chunk_bits[c] : 0u; /* a turn's sum: 256 x 4096 x 60 bits at most */
         u32 total;
-        const u32 before = ffhip_def_wg_scan<VE_WG>(v, wave_sum, &total);
+        const u32 before = wg_scan<VE_WG>(v, wave_sum, &total);
         if (c < d.n_wgs) d.chunk_pos[c] = carry + before;
         carry += total;
     }
@@ -196,8 +190,6 @@ bool item_ok(const ffhip_vp8l_encode_item &it)
     return it.reserved == 0 && ffhip_vp8lenc_source_ok(&it.src, it.flags) && !(it.cap && !it.d_out);
 }
 
-size_t up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
-
 /* the pictures of one part: one synchronisation */
 int encode_part(const ffhip_vp8l_encode_item *items, int n, size_t *len_out, int *status, void *stream)
 {
@@ -213,12 +205,12 @@ int encode_part(const ffhip_vp8l_encode_item *items, int n, size_t *len_out, int
         const u32 w = (u32)it.src.width, h = (u32)it.src.height;
         d.src = it.src; d.flags = it.flags; d.d_out = it.d_out; d.cap = it.cap;
         d.pixels = (unsigned long long)w * h;
-        d.words_bytes = up((size_t)ffhip_ve_bound(w, h) + 16, 16);
+        d.words_bytes = ffhip_up((size_t)ffhip_ve_bound(w, h) + 16, 16);
         d.tiles_x = ffhip_ve_sub_size(w);
         d.tile_first = (u32)total_tiles; d.tile_n = d.tiles_x * ffhip_ve_sub_size(h);
         d.first_wg = (u32)total_chunks; d.n_wgs = (u32)ffhip_ve_chunks(d.pixels);
         total_tiles += d.tile_n; total_chunks += d.n_wgs;
-        px_at[(size_t)i] = px_words; px_words += up((size_t)d.pixels, 4);
+        px_at[(size_t)i] = px_words; px_words += ffhip_up((size_t)d.pixels, 4);
         words_at[(size_t)i] = words_bytes; words_bytes += (size_t)d.words_bytes;
     }
     if (total_tiles > 0xffffffffULL || total_chunks > 0xffffffffULL) return FFHIP_EINVAL;
@@ -226,10 +218,10 @@ int encode_part(const ffhip_vp8l_encode_item *items, int n, size_t *len_out, int
      * the verdicts, the modes, then -- zeroed by the call -- the counters and the files' words, then the residual pictures and the tokens */
     const size_t up_bytes = (size_t)n * sizeof(VeDesc), table_words = (size_t)total_tiles + (size_t)total_chunks;
     const size_t bits_off = up_bytes + table_words * 4, code_off = bits_off + (size_t)total_chunks * 4;
-    const size_t pos_off = up(code_off + (size_t)n * FFHIP_VE_NSYM * 4, 8), ver_off = pos_off + (size_t)total_chunks * 8, ver_bytes = (size_t)n * sizeof(VeVerdict);
-    const size_t mode_off = ver_off + ver_bytes;
-    const size_t hist_off = up(mode_off + (size_t)total_tiles, 256), words_off = up(hist_off + (size_t)n * FFHIP_VE_NSYM * 4, 256);
-    const size_t res_off = up(words_off + words_bytes, 256), tok_off = res_off + px_words * 4, end = tok_off + px_words * 4;
+    const size_t pos_off = ffhip_up(code_off + (size_t)n * FFHIP_VE_NSYM * 4, 8), ver_off = pos_off + (size_t)total_chunks * 8;
+    const size_t mode_off = ver_off + (size_t)n * sizeof(VeVerdict);
+    const size_t hist_off = ffhip_up(mode_off + (size_t)total_tiles, 256), words_off = ffhip_up(hist_off + (size_t)n * FFHIP_VE_NSYM * 4, 256);
+    const size_t res_off = ffhip_up(words_off + words_bytes, 256), tok_off = res_off + px_words * 4, end = tok_off + px_words * 4;
     std::vector<uint8_t> upl(up_bytes);
     uint8_t *dev = nullptr;
     int rc = ffhip_items_stage(SCRATCH_VP8L_ENC, stream, upl.data(), up_bytes, table_words, end - up_bytes - table_words * 4, &dev, [&](uint8_t *base) {
@@ -251,52 +243,28 @@ int encode_part(const ffhip_vp8l_encode_item *items, int n, size_t *len_out, int
     a.desc = (const VeDesc *)dev; a.verdict = (VeVerdict *)(dev + ver_off);
     u32 *d_tile_item = (u32 *)(dev + up_bytes), *d_chunk_item = d_tile_item + total_tiles;
     FFHIP_CHECK(hipMemsetAsync(dev + hist_off, 0, res_off - hist_off, st), FFHIP_EIO);
-    hipLaunchKernelGGL(k_vp8l_enc_tables, dim3((unsigned)n), dim3(256), 0, st, a.desc, d_tile_item, d_chunk_item);
+    hipLaunchKernelGGL((k_items_tables2<VeDesc, VeDesc, &VeDesc::tile_first, &VeDesc::tile_n, &VeDesc::first_wg, &VeDesc::n_wgs>),
+                       dim3((unsigned)n), dim3(256), 0, st, a.desc, a.desc, d_tile_item, d_chunk_item);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
     a.wg_item = d_tile_item;
-    rc = ffhip_items_launch(0, total_tiles, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_vp8l_enc_predict, dim3(grid_x), dim3(64), 0, st, a);
-    });
+    rc = ffhip_items_run(k_vp8l_enc_predict, total_tiles, 64, stream, a);
     if (rc) return rc;
     a.wg_item = d_chunk_item;
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_vp8l_enc_parse, dim3(grid_x), dim3(FFHIP_DEF_LANES), 0, st, a);
-    });
+    rc = ffhip_items_run(k_vp8l_enc_parse, total_chunks, FFHIP_DEF_LANES, stream, a);
     if (rc) return rc;
     a.wg_base = 0;
     hipLaunchKernelGGL(k_vp8l_enc_codes, dim3((unsigned)n), dim3(FFHIP_DEF_LANES), 0, st, a);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_vp8l_enc_count, dim3(grid_x), dim3(FFHIP_DEF_LANES), 0, st, a);
-    });
+    rc = ffhip_items_run(k_vp8l_enc_count, total_chunks, FFHIP_DEF_LANES, stream, a);
     if (rc) return rc;
     a.wg_base = 0;
     hipLaunchKernelGGL(k_vp8l_enc_scan, dim3((unsigned)n), dim3(VE_WG), 0, st, a);
     FFHIP_CHECK(hipGetLastError(), FFHIP_EIO);
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_vp8l_enc_write, dim3(grid_x), dim3(FFHIP_DEF_LANES), 0, st, a);
-    });
+    rc = ffhip_items_run(k_vp8l_enc_write, total_chunks, FFHIP_DEF_LANES, stream, a);
     if (rc) return rc;
-    rc = ffhip_items_launch(0, total_chunks, [&](unsigned grid_x, u32 wg_base) {
-        a.wg_base = wg_base;
-        hipLaunchKernelGGL(k_vp8l_enc_copy, dim3(grid_x), dim3(VE_WG), 0, st, a);
-    });
+    rc = ffhip_items_run(k_vp8l_enc_copy, total_chunks, VE_WG, stream, a);
     if (rc) return rc;
-    VeVerdict *h_ver = (VeVerdict *)ffhip_pinned_scratch(SCRATCH_VP8L_ENC + 1, stream, ver_bytes);
-    if (!h_ver) return FFHIP_ENOMEM;
-    FFHIP_CHECK(hipMemcpyAsync(h_ver, a.verdict, ver_bytes, hipMemcpyDeviceToHost, st), FFHIP_EIO);
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
-    int first = FFHIP_OK;
-    for (int i = 0; i < n; i++) {
-        len_out[i] = (size_t)h_ver[i].file_len;
-        status[i] = h_ver[i].status;
-        if (first == FFHIP_OK && status[i] != FFHIP_OK) first = status[i];
-    }
-    return first;
+    return ffhip_lengths_read(SCRATCH_VP8L_ENC + 1, stream, a.verdict, n, len_out, status);
 }
 
 } // namespace
@@ -308,21 +276,7 @@ extern "C" int ffhip_vp8l_encode_items(const ffhip_vp8l_encode_item *items, int 
         if (!item_ok(items[i])) return FFHIP_EINVAL;
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t budget = ffhip_part_budget(nullptr) / 16; /* a pixel takes sixteen bytes of scratch: its residual word, its token word, 7.5 of the file */
-    int first_rc = FFHIP_OK;
-    for (int first = 0; first < n;) {
-        /* a part: up to VE_PART_ITEMS pictures while their pixels fit the budget; a picture beyond it is a part of its own */
-        int cnt = 0;
-        size_t pixels = 0;
-        while (first + cnt < n && cnt < VE_PART_ITEMS) {
-            const size_t px = (size_t)items[first + cnt].src.width * (size_t)items[first + cnt].src.height;
-            if (cnt && pixels + px > budget) break;
-            pixels += px;
-            cnt++;
-        }
-        const int rc = encode_part(items + first, cnt, len_out + first, status + first, stream);
-        if (rc == FFHIP_EINVAL || rc == FFHIP_ENOMEM || rc == FFHIP_EIO || rc == FFHIP_ENODEV) return rc;
-        if (first_rc == FFHIP_OK) first_rc = rc;
-        first += cnt;
-    }
-    return first_rc;
+    /* a part: up to VE_PART_ITEMS pictures while their pixels fit the budget */
+    return ffhip_parts_run(n, budget, VE_PART_ITEMS, [&](int i) { return (size_t)items[i].src.width * (size_t)items[i].src.height; },
+                           [&](int first, int cnt) { return encode_part(items + first, cnt, len_out + first, status + first, stream); });
 }

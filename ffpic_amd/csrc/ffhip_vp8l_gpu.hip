@@ -206,7 +206,7 @@ size_t vp8l_res_bytes(const ffhip_vp8l_file &f)
 size_t vp8l_side_bytes(const ffhip_vp8l_file &f)
 {
     if (!f.device_form) return 0;
-    return ffhip_up16(4 * (size_t)f.predictor_words) + ffhip_up16(4 * (size_t)f.cross_words) + (f.steps.has_index ? 1024 : 0);
+    return ffhip_up(4 * (size_t)f.predictor_words, 16) + ffhip_up(4 * (size_t)f.cross_words, 16) + (f.steps.has_index ? 1024 : 0);
 }
 
 /* One part: files pf[] of the call, `bytes` of staging.  The clock (FFHIP_VP8L_TIMES) stands around the upload, the predict launches and
@@ -235,10 +235,10 @@ int vp8l_run_part(const std::vector<Vp8lPartFile> &part, size_t bytes, const std
 size_t vp8l_part_add(std::vector<Vp8lPartFile> &part, const ffhip_vp8l_file &f, int idx, size_t *res, size_t *side)
 {
     Vp8lPartFile p{idx, *res, *side, 0, 0};
-    p.cross_off = p.modes_off + (f.device_form ? ffhip_up16(4 * (size_t)f.predictor_words) : 0);
-    p.palette_off = p.cross_off + (f.device_form ? ffhip_up16(4 * (size_t)f.cross_words) : 0);
+    p.cross_off = p.modes_off + (f.device_form ? ffhip_up(4 * (size_t)f.predictor_words, 16) : 0);
+    p.palette_off = p.cross_off + (f.device_form ? ffhip_up(4 * (size_t)f.cross_words, 16) : 0);
     part.push_back(p);
-    *res += ffhip_up16(vp8l_res_bytes(f));
+    *res += ffhip_up(vp8l_res_bytes(f), 16);
     *side += vp8l_side_bytes(f);
     return *res + *side;
 }
@@ -357,7 +357,7 @@ extern "C" int ffhip_vp8l_decode_files_device(const uint8_t *const *files, const
         for (; i < n; i++) {
             if (status[i]) continue;
             const ffhip_vp8l_file &f = pf[(size_t)i];
-            if (!part.empty() && res + ffhip_up16(vp8l_res_bytes(f)) > budget) break;
+            if (!part.empty() && res + ffhip_up(vp8l_res_bytes(f), 16) > budget) break;
             vp8l_part_add(part, f, i, &res, &side);
         }
         if (part.empty()) break;

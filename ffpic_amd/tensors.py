@@ -460,6 +460,56 @@ def decode_webp_lossless_to_tensors(files, dtype=None, layout="CHW", order="RGB"
                               return_orientation=return_orientation)
 
 
+def _per_picture(value, n, name, error=None):
+    """one value or one per picture -> the list of n"""
+    values = list(value) if isinstance(value, (list, tuple)) else [value] * n
+    if len(values) != n:
+        raise ValueError(error or f"{name}: {len(values)} values for {n} pictures")
+    return values
+
+
+def _picture_list(pictures):
+    """one tensor or several -> (single, the list)"""
+    import torch
+    single = isinstance(pictures, torch.Tensor)
+    return single, [pictures] if single else list(pictures)
+
+
+def _encode_files(single, caps, item_of, call, nospace, entry, to_host):
+    """What the encoders share behind their argument checks: picture i's file goes into caps[i] bytes of ONE buffer on the current device,
+    item_of(i, d_out, cap) is its item, call(items, stream, strict=False) -> (lens, status) the ops entry named `entry`.  The files whose
+    status is `nospace` go through a second call at the length the first one reported; any other status raises.  -> the files as views of
+    the buffers, or as bytes with to_host; with `single` the one file."""
+    import torch
+    n = len(caps)
+    if n == 0:
+        return []
+    dev = torch.cuda.current_device()
+    capi.require_device(dev)
+    device = torch.device("cuda", dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    files, todo, caps = [None] * n, list(range(n)), list(caps)
+    for _ in range(2):
+        offs = np.concatenate([[0], np.cumsum([caps[i] for i in todo])]).astype(np.int64)
+        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
+        lens, status = call([item_of(i, buf.data_ptr() + int(offs[k]), caps[i]) for k, i in enumerate(todo)], stream, strict=False)
+        again = []
+        for k, i in enumerate(todo):
+            if status[k] == 0:
+                files[i] = buf[int(offs[k]):int(offs[k]) + lens[k]]
+            elif status[k] == nospace:
+                caps[i] = (lens[k] + 255) & ~255
+                again.append(i)
+            else:
+                capi.check(status[k], entry)
+        todo = again
+        if not todo:
+            break
+    if to_host:
+        files = [bytes(f.cpu().numpy()) for f in files]
+    return files[0] if single else files
+
+
 def jpeg_source_of(t):
     """capi.JpegSource of a uint8 device tensor [3,H,W], [1,H,W] or [H,W,3], whatever its strides -> (source, grey).  A first dimension of 3
     or 1 is ALWAYS read as channels first, as torchvision's encode_jpeg reads it: an [H,W,3] picture that is 1 or 3 rows high has to be passed
@@ -484,55 +534,23 @@ def encode_jpeg(pictures, quality=75, subsampling="4:2:0", restart_blocks=0, to_
     -> a list of 1-D uint8 device tensors (views of one allocation), or of bytes with to_host=True.  quality, subsampling ('4:4:4', '4:2:2',
     '4:2:0'; a grey picture is written as one component) and restart_blocks (MCUs per restart interval, 0: none) are one value or one per
     picture.  The outputs start at half the pixels' size; the files that need more (the call says how much) go through a second call."""
-    import torch
-    single = isinstance(pictures, torch.Tensor)
-    pictures = [pictures] if single else list(pictures)
+    single, pictures = _picture_list(pictures)
     n = len(pictures)
-
-    def each(value, name):
-        values = list(value) if isinstance(value, (list, tuple)) else [value] * n
-        if len(values) != n:
-            raise ValueError(f"{name}: {len(values)} values for {n} pictures")
-        return values
-    qualities, layouts, restarts = each(quality, "quality"), each(subsampling, "subsampling"), [int(r) for r in each(restart_blocks, "restart_blocks")]
+    qualities, layouts = _per_picture(quality, n, "quality"), _per_picture(subsampling, n, "subsampling")
+    restarts = [int(r) for r in _per_picture(restart_blocks, n, "restart_blocks")]
     sources = [jpeg_source_of(t) for t in pictures]                       # argument errors come before any device use
     layouts = [capi.FFHIP_JPEG_ENC_GREY if grey else ops.jpeg_encode_layout(l) for (_, grey), l in zip(sources, layouts)]
     for (_, grey), l in zip(sources, layouts):
         if not grey and l == capi.FFHIP_JPEG_ENC_GREY:
             raise ValueError("subsampling 'grey' needs a [1,H,W] picture")
-    if n == 0:
-        return []
-    dev = torch.cuda.current_device()
-    capi.require_device(dev)
-    device = torch.device("cuda", dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    files, todo = [None] * n, list(range(n))
     caps = [((1024 + s.width * s.height * s.channels // 2) + 255) & ~255 for s, _ in sources]
-    for _ in range(2):
-        offs = np.concatenate([[0], np.cumsum([caps[i] for i in todo])]).astype(np.int64)
-        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
-        items = []
-        for k, i in enumerate(todo):
-            it = capi.JpegEncodeItem()
-            it.src, it.layout, it.quality, it.restart = sources[i][0], layouts[i], int(qualities[i]), restarts[i]
-            it.d_out, it.cap = buf.data_ptr() + int(offs[k]), caps[i]
-            items.append(it)
-        lens, status = ops.jpeg_encode_items(items, stream, strict=False)
-        again = []
-        for k, i in enumerate(todo):
-            if status[k] == 0:
-                files[i] = buf[int(offs[k]):int(offs[k]) + lens[k]]
-            elif status[k] == capi.FFHIP_EJPEG_NOSPACE:
-                caps[i] = (lens[k] + 255) & ~255
-                again.append(i)
-            else:
-                capi.check(status[k], "ffhip_jpeg_encode_items")
-        todo = again
-        if not todo:
-            break
-    if to_host:
-        files = [bytes(f.cpu().numpy()) for f in files]
-    return files[0] if single else files
+
+    def item_of(i, d_out, cap):
+        it = capi.JpegEncodeItem()
+        it.src, it.layout, it.quality, it.restart = sources[i][0], layouts[i], int(qualities[i]), restarts[i]
+        it.d_out, it.cap = d_out, cap
+        return it
+    return _encode_files(single, caps, item_of, ops.jpeg_encode_items, capi.FFHIP_EJPEG_NOSPACE, "ffhip_jpeg_encode_items", to_host)
 
 
 def png_source_of(t):
@@ -559,47 +577,16 @@ def encode_png(pictures, filter="adaptive", to_host=False):
     current stream -> a list of 1-D uint8 device tensors (views of one allocation), or of bytes with to_host=True.  filter: 'adaptive' (per
     row the type with the smallest sum of absolute values), 'none', 'sub', 'up', 'average', 'paeth' or 0..5, one value or one per picture.
     The outputs start at half the bound; the files that need more (the call says how much) go through a second call."""
-    import torch
-    single = isinstance(pictures, torch.Tensor)
-    pictures = [pictures] if single else list(pictures)
-    n = len(pictures)
-    filters = list(filter) if isinstance(filter, (list, tuple)) else [filter] * n
-    if len(filters) != n:
-        raise ValueError(f"filter: {len(filters)} values for {n} pictures")
-    filters = [ops.png_filter_id(f) for f in filters]                     # argument errors come before any device use
+    single, pictures = _picture_list(pictures)
+    filters = [ops.png_filter_id(f) for f in _per_picture(filter, len(pictures), "filter")]   # argument errors come before any device use
     sources = [png_source_of(t) for t in pictures]
-    if n == 0:
-        return []
-    dev = torch.cuda.current_device()
-    capi.require_device(dev)
-    device = torch.device("cuda", dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    files, todo = [None] * n, list(range(n))
     caps = [(ops.png_encode_bound(s.width, s.height, s.channels) // 2 + 255) & ~255 for s in sources]
-    for _ in range(2):
-        offs = np.concatenate([[0], np.cumsum([caps[i] for i in todo])]).astype(np.int64)
-        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
-        items = []
-        for k, i in enumerate(todo):
-            it = capi.PngEncodeItem()
-            it.src, it.filter, it.d_out, it.cap = sources[i], filters[i], buf.data_ptr() + int(offs[k]), caps[i]
-            items.append(it)
-        lens, status = ops.png_encode_items(items, stream, strict=False)
-        again = []
-        for k, i in enumerate(todo):
-            if status[k] == 0:
-                files[i] = buf[int(offs[k]):int(offs[k]) + lens[k]]
-            elif status[k] == capi.FFHIP_EPNG_NOSPACE:
-                caps[i] = (lens[k] + 255) & ~255
-                again.append(i)
-            else:
-                capi.check(status[k], "ffhip_png_encode_items")
-        todo = again
-        if not todo:
-            break
-    if to_host:
-        files = [bytes(f.cpu().numpy()) for f in files]
-    return files[0] if single else files
+
+    def item_of(i, d_out, cap):
+        it = capi.PngEncodeItem()
+        it.src, it.filter, it.d_out, it.cap = sources[i], filters[i], d_out, cap
+        return it
+    return _encode_files(single, caps, item_of, ops.png_encode_items, capi.FFHIP_EPNG_NOSPACE, "ffhip_png_encode_items", to_host)
 
 
 def encode_webp_lossless(pictures, predict=True, subtract_green=True, to_host=False):
@@ -608,50 +595,23 @@ def encode_webp_lossless(pictures, predict=True, subtract_green=True, to_host=Fa
     -> a list of 1-D uint8 device tensors (views of one allocation), or of bytes with to_host=True.  predict, subtract_green: the two
     transforms, one value or one per picture.  The outputs start at half the bound; the files that need more (the call says how much) go
     through a second call."""
-    import torch
-    single = isinstance(pictures, torch.Tensor)
-    pictures = [pictures] if single else list(pictures)
-    n = len(pictures)
+    single, pictures = _picture_list(pictures)
     flags = []
     for name, value in (("predict", predict), ("subtract_green", subtract_green)):
-        values = list(value) if isinstance(value, (list, tuple)) else [value] * n
-        if len(values) != n or not all(isinstance(v, (bool, np.bool_)) for v in values):
-            raise ValueError(f"{name}: True or False, one value or one per picture")
+        error = f"{name}: True or False, one value or one per picture"
+        values = _per_picture(value, len(pictures), name, error)
+        if not all(isinstance(v, (bool, np.bool_)) for v in values):
+            raise ValueError(error)
         flags.append(values)
     flags = [ops.vp8l_encode_flags(p, g) for p, g in zip(*flags)]            # argument errors come before any device use
     sources = [png_source_of(t) for t in pictures]
     for s in sources:
         if s.width > 16384 or s.height > 16384:
             raise ValueError(f"encode_webp_lossless: sides of 1..16384, got {s.width} x {s.height}")
-    if n == 0:
-        return []
-    dev = torch.cuda.current_device()
-    capi.require_device(dev)
-    device = torch.device("cuda", dev)
-    stream = torch.cuda.current_stream().cuda_stream
-    files, todo = [None] * n, list(range(n))
     caps = [(ops.vp8l_encode_bound(s.width, s.height) // 2 + 255) & ~255 for s in sources]
-    for _ in range(2):
-        offs = np.concatenate([[0], np.cumsum([caps[i] for i in todo])]).astype(np.int64)
-        buf = torch.empty(int(offs[-1]), dtype=torch.uint8, device=device)
-        items = []
-        for k, i in enumerate(todo):
-            it = capi.Vp8lEncodeItem()
-            it.src, it.flags, it.d_out, it.cap = sources[i], flags[i], buf.data_ptr() + int(offs[k]), caps[i]
-            items.append(it)
-        lens, status = ops.vp8l_encode_items(items, stream, strict=False)
-        again = []
-        for k, i in enumerate(todo):
-            if status[k] == 0:
-                files[i] = buf[int(offs[k]):int(offs[k]) + lens[k]]
-            elif status[k] == capi.FFHIP_EVP8L_NOSPACE:
-                caps[i] = (lens[k] + 255) & ~255
-                again.append(i)
-            else:
-                capi.check(status[k], "ffhip_vp8l_encode_items")
-        todo = again
-        if not todo:
-            break
-    if to_host:
-        files = [bytes(f.cpu().numpy()) for f in files]
-    return files[0] if single else files
+
+    def item_of(i, d_out, cap):
+        it = capi.Vp8lEncodeItem()
+        it.src, it.flags, it.d_out, it.cap = sources[i], flags[i], d_out, cap
+        return it
+    return _encode_files(single, caps, item_of, ops.vp8l_encode_items, capi.FFHIP_EVP8L_NOSPACE, "ffhip_vp8l_encode_items", to_host)

@@ -1,7 +1,7 @@
 """CPU: the host PNG encoder (ffhip_png_filter_picture, ffhip_png_encode_picture) against the numpy witness
 (tests/png_encode_spec.py), PIL, the PNG witness of the decoder (tests/png_spec.py) and the library's own host decoder: the filtered bytes
 through every source form, the files' pixels, chunks, CRCs and bounds, the argument checks, the size conditions, and both host encoders in a
-stand-alone program under the sanitizers."""
+stand-alone program under the sanitizers.  Also the part loop of the device entry points (ffhip_parts.h), in a stand-alone program."""
 import ctypes as C
 import io
 import os
@@ -160,3 +160,17 @@ def test_both_host_encoders_under_the_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     assert r.stdout.strip().startswith("ok: ") and r.stdout.strip().endswith("pictures")
+
+
+def test_the_part_loop_on_the_cpu_under_the_sanitizers(tmp_path):
+    """tests/tools/check_parts.cpp: ffhip_parts_run (ffhip_parts.h, the part loop of the four encoders' entry points) over
+    seeded lists of weights: the cut, the cap on a part's items, and what a part's return code does to the call's.  A stand-alone program
+    with the sanitizers' runtimes linked into it"""
+    gxx = shutil.which("g++") or "g++"
+    exe = str(tmp_path / "check_parts")
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "ffpic_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "tools", "check_parts.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert r.stdout.startswith("ok: 400 lists, "), r.stdout

@@ -1,6 +1,6 @@
 """GPU: the lossless WebP encoder on the device against the host entry ffhip_vp8l_encode_picture -- the same body compiled by
 gcc, held to the numpy witness, PIL and two more decoders by tests/test_vp8l_encode_capi.py -- file for file and byte for byte: every case
-in ONE mixed batch and one call per item, every source form, a BGRA picture straight from the decoder, the cap, two threads with a stream
+in ONE mixed batch and one call per item, every source form, a BGRA picture straight from the decoder, the cap, a batch of two parts, two threads with a stream
 each, the device decoder on the device's files, and tensors.encode_webp_lossless.  The scratch protocol is
 tests/test_lossless_webp_encode_scratch_gpu.py's."""
 import ctypes as C
@@ -17,6 +17,7 @@ from vp8l_encode_cases import CASES, LARGE, SMALL
 pytestmark = pytest.mark.gpu
 FILL = 0xA5
 NOSPACE = capi.FFHIP_EVP8L_NOSPACE
+PART_ITEMS = 4096            # ffhip_vp8l_encode_items: a part holds at most this many pictures (VE_PART_ITEMS)
 HOST = {}
 
 
@@ -155,6 +156,35 @@ def test_cap_exact_one_short_and_none():
     assert status == [NOSPACE, NOSPACE] and files == [wants[0][:13], wants[1][:29]] and lens == [len(wants[0]), len(wants[1])]
     with pytest.raises(capi.FfhipError):
         encode_call(cases[:2], caps=[13, None])
+
+
+def test_a_batch_of_several_parts():
+    """a part holds at most 4096 pictures (ffhip_parts_run with VE_PART_ITEMS): 4096 + 5 pictures of a few pixels are two parts, with a
+    picture that does not fit in the second; its status is the call's return code, and every other file is the host entry's"""
+    L = capi.require_device()
+    small = sorted(SMALL, key=lambda c: c.width * c.height)[:4]
+    assert all(c.width * c.height <= 70 for c in small)
+    cases = [small[k % len(small)] for k in range(PART_ITEMS + 5)]
+    caps = [None] * len(cases)
+    caps[PART_ITEMS + 2] = 30
+    files, lens, status = encode_call(cases, caps=caps, strict=False)
+    assert [k for k, s in enumerate(status) if s] == [PART_ITEMS + 2] and status[PART_ITEMS + 2] == NOSPACE
+    wants = [host_file(c) for c in small]
+    assert all(len(w) > 30 for w in wants)
+    for k, (f, n) in enumerate(zip(files, lens)):
+        w = wants[k % len(small)]
+        assert n == len(w) and f == (w[:30] if k == PART_ITEMS + 2 else w), k
+    # the call's return code: the status of the picture that did not fit, from the second part
+    c = cases[PART_ITEMS + 2]
+    src = ops.DeviceBuffer(host=np.ascontiguousarray(c.samples))
+    out = ops.DeviceBuffer(host=np.full(len(cases) * 256, FILL, np.uint8))
+    items = (capi.Vp8lEncodeItem * len(cases))()
+    for k, it in enumerate(items):
+        it.src = capi.png_source(src.ptr, c.width, c.height, c.width * c.channels, c.channels, tuple(range(c.channels)))
+        it.flags, it.d_out, it.cap = c.flags, out.ptr + 256 * k, 30 if k == PART_ITEMS + 2 else 256
+    n_out, st_out = (C.c_size_t * len(cases))(), (C.c_int * len(cases))()
+    assert L.ffhip_vp8l_encode_items(items, len(cases), n_out, st_out, None) == NOSPACE
+    assert list(st_out) == status and list(n_out) == [len(host_file(c))] * len(cases)
 
 
 def test_two_threads_a_stream_each():
