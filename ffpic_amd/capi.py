@@ -54,6 +54,8 @@ EXPORTS = [
     "ffhip_deflate", "ffhip_deflate_bound", "ffhip_deflate_code_lengths", "ffhip_png_filtered_size", "ffhip_png_filter_picture",
     "ffhip_png_encode_bound", "ffhip_png_encode_picture", "ffhip_deflate_streams_device", "ffhip_png_encode_items",
     "ffhip_vp8l_encode_bound", "ffhip_vp8l_encode_residual", "ffhip_vp8l_encode_picture", "ffhip_vp8l_encode_items",
+    "ffhip_vp8_encode_quality_index", "ffhip_vp8_encode_bound", "ffhip_vp8_encode_planes", "ffhip_vp8_encode_mbs", "ffhip_vp8_encode_picture",
+    "ffhip_vp8_encode_items",
 ]
 
 
@@ -73,6 +75,7 @@ FFHIP_EPNG_NOSPACE, FFHIP_EDEFLATE_NOSPACE = -1201, -1202
 FFHIP_VP8L_ENC_SUBTRACT_GREEN, FFHIP_VP8L_ENC_PREDICT = 1, 2
 FFHIP_VP8L_ENC_TILE_BITS, FFHIP_VP8L_ENC_CHUNK = 4, 4096
 FFHIP_EVP8L_NOSPACE = -1301
+FFHIP_EVP8_NOSPACE, FFHIP_EVP8_PARTITION = -1401, -1402
 
 
 class FfhipError(RuntimeError):
@@ -274,6 +277,11 @@ class PngEncodeItem(C.Structure):
 class Vp8lEncodeItem(C.Structure):
     """ffhip_vp8l_encode_item (device pointers); its source is a PngSource"""
     _fields_ = [("src", PngSource), ("flags", C.c_int32), ("reserved", C.c_int32), ("d_out", C.c_void_p), ("cap", C.c_size_t)]
+
+
+class Vp8EncodeItem(C.Structure):
+    """ffhip_vp8_encode_item (device pointers); its source is a JpegSource of 1 or 3 channels"""
+    _fields_ = [("src", JpegSource), ("quality", C.c_int32), ("filter", C.c_int32), ("d_out", C.c_void_p), ("cap", C.c_size_t)]
 
 
 def png_source(pixels, width, height, row_stride, pixel_stride, chan, channels=None):
@@ -530,6 +538,13 @@ def lib():
     L.ffhip_vp8l_encode_residual.argtypes = [C.POINTER(PngSource), ci, vp, vp]
     L.ffhip_vp8l_encode_picture.argtypes = [C.POINTER(PngSource), ci, vp, sz, C.POINTER(sz)]
     L.ffhip_vp8l_encode_items.argtypes = [C.POINTER(Vp8lEncodeItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
+    L.ffhip_vp8_encode_quality_index.argtypes = [ci]
+    L.ffhip_vp8_encode_bound.argtypes = [ci, ci]
+    L.ffhip_vp8_encode_bound.restype = sz
+    L.ffhip_vp8_encode_planes.argtypes = [C.POINTER(JpegSource), vp, vp, vp]
+    L.ffhip_vp8_encode_mbs.argtypes = [C.POINTER(JpegSource), ci, vp, vp, vp, vp, vp, vp]
+    L.ffhip_vp8_encode_picture.argtypes = [C.POINTER(JpegSource), ci, ci, vp, sz, C.POINTER(sz)]
+    L.ffhip_vp8_encode_items.argtypes = [C.POINTER(Vp8EncodeItem), ci, C.POINTER(sz), C.POINTER(ci), vp]
     for name in ("ffhip_inflate_upto", "ffhip_inflate_model"):    # exported, not in the public header (csrc/ffhip_png_internal.h)
         getattr(L, name).argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci]
     L.ffhip_inflate_model_mode.argtypes = [vp, sz, vp, sz, C.POINTER(sz), ci, ci]

@@ -128,6 +128,7 @@ enum FfhipScratchKind {
     SCRATCH_JPEG_ENC = 130,      /* .. + 4: the JPEG encoder.  + 0 ffhip_jpeg_fdct_items' records, per-workgroup tables and sample planes (pinned records); + 1 ffhip_jpeg_huff_encode_items' records, code tables, per-workgroup table, positions and results (pinned records); + 2 its stream records, per-chunk table, FF counts, unstuffed streams and masks (pinned records); + 3 its results on the host (pinned only); + 4 ffhip_jpeg_encode_items: a part's coefficient planes */
     SCRATCH_PNG_ENC = 140,       /* .. + 1: ffhip_png_encode_items and ffhip_deflate_streams_device (one call of either at a time per stream).  + 0 a part's picture and stream records (pinned records), per-workgroup tables, chunk offsets and results, verdicts, the chunks' zeroed output words, the filtered pictures, the token words; + 1 the verdicts on the host (pinned only) */
     SCRATCH_VP8L_ENC = 150,      /* .. + 1: ffhip_vp8l_encode_items.  + 0 a part's picture records (pinned records), per-workgroup tables, the chunks' bits and positions, the tables of codes, verdicts, the sub-images, the zeroed counters and files' words, the residual pictures, the token words; + 1 the verdicts on the host (pinned only) */
+    SCRATCH_VP8_ENC = 160,       /* .. + 1: ffhip_vp8_encode_items.  + 0 a part's picture records (pinned records), per-workgroup tables, the files' records, masks, levels, modes, source planes and reconstruction, the partitions; + 1 the files' records on the host (pinned only) */
     SCRATCH_HUFF_PROG = 90,      /* ffhip_jpeg_progressive_batch_gpu: staged scans, tables, records and work lists (and their pinned copy) */
 };
 

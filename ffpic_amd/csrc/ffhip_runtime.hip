@@ -209,6 +209,8 @@ extern "C" const char *ffhip_strerror(int code)
     case FFHIP_EJPEG_NOSPACE: return "the JPEG file does not fit the output's cap (the length is the size it needs)";
     case FFHIP_EJPEG_RANGE: return "a coefficient Annex K's Huffman tables cannot code (AC magnitude over 1023 or DC difference beyond +-2047)";
     case FFHIP_EVP8L_NOSPACE: return "the lossless WebP file does not fit the output's cap (the length is the size it needs)";
+    case FFHIP_EVP8_NOSPACE: return "the lossy WebP file does not fit the output's cap (the length is the size it needs)";
+    case FFHIP_EVP8_PARTITION: return "a partition of the lossy WebP file is longer than a VP8 frame can say";
     case FFHIP_EPNG_NOSPACE: return "the PNG file does not fit the output's cap (the length is the size it needs)";
     case FFHIP_EDEFLATE_NOSPACE: return "the zlib stream does not fit the output's cap (the length is the size it needs)";
     default: return "unknown error";

@@ -1436,3 +1436,64 @@ def vp8l_encode_items(items, stream=None, strict=True):
     """ffhip_vp8l_encode_items: `items` a list of capi.Vp8lEncodeItem (device pictures) -> ([file length], [status]); the files are in the
     items' d_out.  With strict=False a file that does not fit its cap is its status (FFHIP_EVP8L_NOSPACE) and its length the size it needs."""
     return _lengths_call("ffhip_vp8l_encode_items", capi.Vp8lEncodeItem, items, stream, strict)
+
+
+# ---- lossy WebP encoding (include/ffpic_hip.h "Lossy WebP encoding", DESIGN.md 4.36)
+def _vp8_src(pixels):
+    return pixels if isinstance(pixels, capi.JpegSource) else jpeg_host_source(pixels)
+
+
+def vp8_encode_quality_index(quality):
+    """ffhip_vp8_encode_quality_index: y_ac_qi of a quality 0..100.  Needs no device."""
+    qi = int(capi.lib().ffhip_vp8_encode_quality_index(int(quality)))
+    capi.check(min(qi, 0), "ffhip_vp8_encode_quality_index")
+    return qi
+
+
+def vp8_encode_bound(width, height):
+    """ffhip_vp8_encode_bound: a certain bound on the file's size (0: bad arguments).  Needs no device."""
+    return int(capi.lib().ffhip_vp8_encode_bound(width, height))
+
+
+def vp8_encode_planes(pixels):
+    """ffhip_vp8_encode_planes: host pixels (uint8 [H][W][3] RGB or [H][W] grey, or a capi.JpegSource of host memory) -> (y, u, v), the padded
+    planes of the macroblock grid.  Needs no device."""
+    src = _vp8_src(pixels)
+    cols, rows = (src.width + 15) >> 4, (src.height + 15) >> 4
+    y, u, v = np.zeros((16 * rows, 16 * cols), np.uint8), np.zeros((8 * rows, 8 * cols), np.uint8), np.zeros((8 * rows, 8 * cols), np.uint8)
+    capi.check(capi.lib().ffhip_vp8_encode_planes(C.byref(src), _vp(y), _vp(u), _vp(v)), "ffhip_vp8_encode_planes")
+    return y, u, v
+
+
+def vp8_encode_mbs(pixels, quality=75):
+    """ffhip_vp8_encode_mbs: host pixels (as vp8_encode_planes) -> dict(ymode [n], uvmode [n], levels [n][25][16], y, u, v): modes, levels
+    in tests/vp8_writer.keyframe_from's layout and the unfiltered reconstruction.  Needs no device."""
+    src = _vp8_src(pixels)
+    cols, rows = (src.width + 15) >> 4, (src.height + 15) >> 4
+    n = cols * rows
+    out = dict(ymode=np.zeros(n, np.uint8), uvmode=np.zeros(n, np.uint8), levels=np.zeros((n, 25, 16), np.int16),
+               y=np.zeros((16 * rows, 16 * cols), np.uint8), u=np.zeros((8 * rows, 8 * cols), np.uint8), v=np.zeros((8 * rows, 8 * cols), np.uint8))
+    capi.check(capi.lib().ffhip_vp8_encode_mbs(C.byref(src), int(quality), *[_vp(out[k]) for k in ("ymode", "uvmode", "levels", "y", "u", "v")]),
+               "ffhip_vp8_encode_mbs")
+    return out
+
+
+def vp8_encode_picture(pixels, quality=75, filter=-1, cap=None):
+    """ffhip_vp8_encode_picture: host pixels (as vp8_encode_planes) to the lossy WebP file's bytes, the CPU model of vp8_encode_items.
+    filter: the loop filter level 0..63, -1 for the rule's own.  cap: the output's size (the bound when None); -> bytes, or with cap
+    given (rc, length, the cap bytes)."""
+    src = _vp8_src(pixels)
+    size = vp8_encode_bound(src.width, src.height) if cap is None else int(cap)
+    out = np.zeros(max(size, 1), np.uint8)
+    n = C.c_size_t()
+    rc = capi.lib().ffhip_vp8_encode_picture(C.byref(src), int(quality), int(filter), _vp(out), size, C.byref(n))
+    if cap is not None:
+        return rc, n.value, out[:size].tobytes()
+    capi.check(rc, "ffhip_vp8_encode_picture")
+    return out[:n.value].tobytes()
+
+
+def vp8_encode_items(items, stream=None, strict=True):
+    """ffhip_vp8_encode_items: `items` a list of capi.Vp8EncodeItem (device pictures) -> ([file length], [status]); the files are in the
+    items' d_out.  With strict=False a file that does not fit its cap is its status (FFHIP_EVP8_NOSPACE) and its length the size it needs."""
+    return _lengths_call("ffhip_vp8_encode_items", capi.Vp8EncodeItem, items, stream, strict)

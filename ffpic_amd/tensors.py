@@ -615,3 +615,31 @@ def encode_webp_lossless(pictures, predict=True, subtract_green=True, to_host=Fa
         it.src, it.flags, it.d_out, it.cap = sources[i], flags[i], d_out, cap
         return it
     return _encode_files(single, caps, item_of, ops.vp8l_encode_items, capi.FFHIP_EVP8L_NOSPACE, "ffhip_vp8l_encode_items", to_host)
+
+
+def encode_webp(pictures, quality=75, filter=None, to_host=False):
+    """Device pictures to lossy WebP files (one VP8 key frame each, the rule of include/ffpic_hip.h "Lossy WebP encoding"): a list of uint8
+    device tensors as encode_jpeg takes them ([3,H,W], [1,H,W] or [H,W,3]; sides up to 16383), of any sizes and strides, in ONE
+    ffhip_vp8_encode_items call on the current stream -> a list of 1-D uint8 device tensors (views of one allocation), or of bytes with
+    to_host=True.  quality 0..100 and filter (the loop filter level 0..63, None for the rule's own) are one value or one per picture.  The
+    outputs start at half the pixels' bytes; the files that need more (the call says how much) go through a second call."""
+    single, pictures = _picture_list(pictures)
+    n = len(pictures)
+    qualities = _per_picture(quality, n, "quality")
+    filters = [-1 if f is None else f for f in _per_picture(filter, n, "filter")]
+    for q, f in zip(qualities, filters):                                   # argument errors come before any device use
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= q <= 100:
+            raise ValueError(f"quality: integers 0..100, got {q!r}")
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not -1 <= f <= 63:
+            raise ValueError(f"filter: None or integers 0..63, got {f!r}")
+    sources = [jpeg_source_of(t)[0] for t in pictures]
+    for s in sources:
+        if s.width > 16383 or s.height > 16383:
+            raise ValueError(f"encode_webp: sides of 1..16383, got {s.width} x {s.height}")
+    caps = [(s.width * s.height * s.channels // 2 + 255) & ~255 for s in sources]
+
+    def item_of(i, d_out, cap):
+        it = capi.Vp8EncodeItem()
+        it.src, it.quality, it.filter, it.d_out, it.cap = sources[i], int(qualities[i]), int(filters[i]), d_out, cap
+        return it
+    return _encode_files(single, caps, item_of, ops.vp8_encode_items, capi.FFHIP_EVP8_NOSPACE, "ffhip_vp8_encode_items", to_host)

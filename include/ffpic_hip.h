@@ -1808,6 +1808,91 @@ typedef struct ffhip_vp8l_encode_item {
 } ffhip_vp8l_encode_item;
 int ffhip_vp8l_encode_items(const ffhip_vp8l_encode_item *items, int n, size_t *len_out, int *status, void *stream);
 
+/* ---- Lossy WebP encoding (ffhip_vp8_enc.c, ffhip_vp8_enc_body.h, ffhip_vp8_enc_gpu.hip) ----
+ * Pictures to complete lossy WebP files (RIFF / WEBP / "VP8 ": one VP8 key frame, RFC 6386): colour, prediction, transforms, quantiser,
+ * tokens and the bool coder as kernels, the same body as host functions.  There is no byte-for-byte target outside the library -- libwebp's
+ * choices are rate-distortion searches -- so THE RULE is its own, a function of the input bytes alone, and host and device share it so that
+ * their files are equal byte for byte.  What the rule promises of the file: every decoder of RFC 6386 gives exactly the reconstruction below.
+ *   PICTURES    uint8 samples by byte strides in the JPEG encoder's source record, 1 or 3 channels (grey is R = G = B); four channels (alpha)
+ *               are FFHIP_EINVAL.  Sides 1..16383.  The file: "RIFF", its size, "WEBP", "VP8 ", the chunk's size, the frame: the 10-byte
+ *               key-frame head (scale 0), the first partition, the partition sizes, the token partitions; a zero byte behind an odd chunk.
+ *               No VP8X chunk.
+ *   COLOUR      libwebp's fixed-point matrix.  Y = (16839 R + 33059 G + 6420 B + (16 << 16) + (1 << 15)) >> 16 per pixel.  For chroma r, g, b
+ *               are the PLAIN sums over a 2 x 2 cell -- this is not libwebp's gamma-aware averaging -- with the last column and row
+ *               repeated beyond the right and bottom edge: U = (-9719 r - 19081 g + 28800 b + (128 << 18) + (1 << 17)) >> 18,
+ *               V = (28800 r - 24116 g - 4684 b + (128 << 18) + (1 << 17)) >> 18, both clamped to 0..255.  The planes are padded to whole
+ *               macroblocks by repeating their last column and row.
+ *   QUANTISER   quality 0..100 gives y_ac_qi by a table of 101 entries (ffhip_vp8_encode_quality_index: libwebp's 127 (1 - cbrt(l))
+ *               evaluated once); the five deltas are 0, there are no segments.  The six steps are RFC 6386's for that index as a decoder
+ *               derives them: Y2 DC twice the DC step, Y2 AC 155 / 100 of the AC step and 8 at least, chroma DC 132 at most (what
+ *               ffhip_vp8_dequant_factors gives up to index 69; above it that function has the reference's cap on Y2 DC, which no other
+ *               decoder has).  level = sign(c) min(2047, (|c| + bias) / step), the exact quotient; bias = step >> 1 for every DC and the
+ *               whole Y2 block, (3 step) >> 3 for AC.
+ *   TRANSFORMS  over source less prediction, libwebp's forward pair.  The 4 x 4 DCT, rows first, with a0 = d0 + d3, a1 = d1 + d2,
+ *               a2 = d1 - d2, a3 = d0 - d3: (a0 + a1) 8, (a2 2217 + a3 5352 + 1812) >> 9, (a0 - a1) 8, (a3 2217 - a2 5352 + 937) >> 9; then
+ *               columns, the same butterflies over t[i], t[4 + i], t[8 + i], t[12 + i]: (a0 + a1 + 7) >> 4,
+ *               ((a2 2217 + a3 5352 + 12000) >> 16) + (a3 != 0), (a0 - a1 + 7) >> 4, (a3 2217 - a2 5352 + 51000) >> 16.  The Y2 WHT over the
+ *               sixteen luma DCs before they are quantised: rows a0 = x0 + x2, a1 = x1 + x3, a2 = x1 - x3, a3 = x0 - x2 giving a0 + a1,
+ *               a3 + a2, a3 - a2, a0 - a1; columns a0 = t[i] + t[8 + i], a1 = t[4 + i] + t[12 + i], a2 = t[4 + i] - t[12 + i],
+ *               a3 = t[i] - t[8 + i] giving (a0 + a1) >> 1, (a3 + a2) >> 1, (a3 - a2) >> 1, (a0 - a1) >> 1 at i, 4 + i, 8 + i, 12 + i.
+ *   MODES       every macroblock is 16 x 16 with a Y2 block, never B_PRED.  The luma mode is the one of DC, TM, V, H (numbered 0, 1, 2, 3)
+ *               with the smallest sum of squared differences between source and prediction, the lowest number at equal sums; the chroma
+ *               mode the same over U and V together.  Predictions are RFC 6386's, with its rows of 127 and columns of 129 at the frame's
+ *               edges, and are built from the encoder's RECONSTRUCTION, never from the source.
+ *   RECONSTRUCTION  RFC 6386's dequantisation (16-bit products), inverse WHT and inverse DCT with clamping: the picture the next macroblock
+ *               predicts from, and what a decoder shows when filter is 0.
+ *   HEADER      colour space 0, clamp 0, no segmentation, the normal loop filter with sharpness 0 and no deltas; its level is `filter`
+ *               0..63, or for -1 min(63, (5 y_ac_qi) >> 4).  Token partitions: the largest power of two <= min(8, macroblock rows).  No
+ *               coefficient probability update.  mb_no_skip_coeff = 1 with prob_skip_false = clamp((256 coded + total / 2) / total, 1, 255);
+ *               a macroblock whose 25 blocks are all zero is skipped.
+ *   TOKENS      RFC 6386 section 13 under the default probabilities; contexts from the neighbours' non-zero flags; an end-of-block behind a
+ *               block's last non-zero level; row y goes to partition y & (partitions - 1).  The bool coder and its flush (four bytes) are
+ *               section 7.3's.
+ *   LIMITS      a first partition over 2^19 - 1 bytes or a token partition over 2^24 - 1 bytes is FFHIP_EVP8_PARTITION for that picture
+ *               (its length is 0, nothing is written).
+ *   BOUND       a coded bit moves the coder by 7 bits at most, whatever its probability (the range stays within 128..255 and a split is 1
+ *               at least), so no look at the default tables can ask more; a flush adds 4 bytes.  The frame header is 1094 coded bits, a
+ *               macroblock's header 7.  A coefficient is 19 coded bits at most: not end-of-block, six tree nodes down to cat6, cat6's eleven
+ *               extra bits (they hold a level up to 2047, the clamp), the sign.  A block is 16 x 19 + 1, a luma block behind Y2 15 x 19 + 1:
+ *               7321 a macroblock.  bound = 30 + ceil(7 (1094 + 7 n) / 8) + 4 + 3 (partitions - 1) + sum over partitions
+ *               (ceil(7 x 7321 n_p / 8) + 4) + 1, some 25 bytes a pixel.
+ * Every choice is a function of the input bytes alone. */
+#define FFHIP_EVP8_NOSPACE (-1401)   /* the file does not fit cap: len is the size it needs, nothing at or beyond cap was written */
+#define FFHIP_EVP8_PARTITION (-1402) /* a partition is longer than the frame can say (LIMITS) */
+/* Host entries; they need no device.  cols = ceil(width / 16), rows = ceil(height / 16), n = cols x rows.
+ *   ffhip_vp8_encode_quality_index  y_ac_qi of a quality, FFHIP_EINVAL beyond 0..100
+ *   ffhip_vp8_encode_bound          a CERTAIN bound on the file (BOUND above), 0 for bad arguments
+ *   ffhip_vp8_encode_planes         COLOUR alone: y[16 rows][16 cols], u and v [8 rows][8 cols], padding included
+ *   ffhip_vp8_encode_mbs            MODES, levels and RECONSTRUCTION: ymode[n], uvmode[n], levels[n][25][16] (raster positions inside a block;
+ *                                   16 Y, 4 U, 4 V, Y2: the decoders' layout), recon_y / _u / _v as the planes above, unfiltered
+ *   ffhip_vp8_encode_picture        HOST pixels to the file; *len its size; FFHIP_EVP8_NOSPACE when that exceeds cap (no byte at or beyond
+ *                                   out + cap is written; below it lie the file's first cap bytes) */
+int ffhip_vp8_encode_quality_index(int quality);
+size_t ffhip_vp8_encode_bound(int width, int height);
+int ffhip_vp8_encode_planes(const ffhip_jpeg_source *src, uint8_t *y, uint8_t *u, uint8_t *v);
+int ffhip_vp8_encode_mbs(const ffhip_jpeg_source *src, int quality, uint8_t *ymode, uint8_t *uvmode, int16_t *levels, uint8_t *recon_y, uint8_t *recon_u,
+                         uint8_t *recon_v);
+int ffhip_vp8_encode_picture(const ffhip_jpeg_source *src, int quality, int filter, uint8_t *out, size_t cap, size_t *len);
+/* ffhip_vp8_encode_items: pictures of any sizes, channel counts, source forms, qualities and filter levels in one batch, byte for byte
+ *   ffhip_vp8_encode_picture's files.  The arrays are HOST arrays, read before the call returns; every check is made before anything is
+ *   enqueued (FFHIP_EINVAL, on a machine without a device too; FFHIP_ENODEV there for good arguments); n == 0 is FFHIP_OK.  len_out[i],
+ *   status[i] (FFHIP_OK; FFHIP_EVP8_NOSPACE: len_out[i] is the size needed, no byte at or beyond cap is written; FFHIP_EVP8_PARTITION); a
+ *   picture's verdict leaves its neighbours alone; returns the first code that is not FFHIP_OK.  The batch is cut into parts by a budget over
+ *   the pixels of the macroblock grids (32 Mi pixels -- a pixel takes 32 bytes of scratch: 3 of planes, 3.2 of levels, modes and masks, 25.1 of
+ *   the partitions' bound -- and at most 4096 pictures; a picture beyond the budget is a part of its own); the call SYNCHRONISES the stream
+ *   once a part.  Kernels: k_vp8_enc_color (a thread per 2 x 2 cell: the padded planes), k_vp8_enc_mb (a wave per macroblock, ONE LAUNCH PER
+ *   ANTI-DIAGONAL of the part's largest grid, cols + rows - 1 of them: a macroblock reads the reconstruction of its left, upper and upper-left
+ *   neighbours only; the eight sums by a wave reduction, a block a lane for the transforms), k_vp8_enc_parts (a lane per partition of a
+ *   picture, the first partition included: it tokenises as it codes), k_vp8_enc_scan (a thread per picture: sizes, head, verdict) and
+ *   k_vp8_enc_copy with every store under cap.  No kernel waits for another workgroup. */
+typedef struct ffhip_vp8_encode_item {
+    ffhip_jpeg_source src; /* pixels: device */
+    int32_t quality, filter;
+    uint8_t *d_out;
+    size_t cap;
+} ffhip_vp8_encode_item;
+int ffhip_vp8_encode_items(const ffhip_vp8_encode_item *items, int n, size_t *len_out, int *status, void *stream);
+
 /* ---- batches over the GPUs of one node, from C (ffhip_shard.hip) ----
  * The reference decodes one image at a time on one thread (format/jpg.c:458-585) and has no collective of any kind
  * (SURVEY 2.1); images are independent, so a batch shards into contiguous image ranges -- one process and one GPU
