@@ -68,6 +68,7 @@ template <class F> void ffhip_parallel_for(int count, int n_threads, F f)
     part(0);
     for (auto &th : pool) th.join();
 }
+inline int ffhip_host_threads(int n_threads) { return n_threads < 1 ? 1 : n_threads > 64 ? 64 : n_threads; }
 
 typedef unsigned int u32;
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
@@ -107,6 +108,8 @@ enum FfhipScratchKind {
     SCRATCH_JPEG_HOST = 6,
     SCRATCH_VP8_RETRY = 8,
     SCRATCH_VP8_FRAMES = 9,        /* .. + 1 */
+    SCRATCH_FILES_PLANES = 11,     /* a slot stream of the JPEG file pipeline (ffhip_pipeline.hip): a chunk's planes and quantiser tables, and their pinned twin the host threads decode into */
+    SCRATCH_FILES_PIXELS = 12,     /* a slot stream of ffhip_jpeg_decode_files: a chunk's pictures at ffhip_bgra_layout's pitch; pinned, the tight staging of a pageable destination */
     SCRATCH_HEVC_TILES_ONE = 25,   /* .. + 1 */
     SCRATCH_HUFF_SYNC = 30,        /* .. + FFHIP_HUFF_PARTS - 1 */
     SCRATCH_FILES_MIXED = 7,       /* ffhip_jpeg_decode_files_mixed_device: a class's planes and quantiser tables, the host decoder's pinned planes */
@@ -310,9 +313,7 @@ struct FfhipStreamState {
 /* the entry of (current device, stream), made when missing unless !make; hold g_ffhip_state_mu while touching it (the tile guard's `turn` aside) */
 extern std::mutex g_ffhip_state_mu;
 FfhipStreamState *ffhip_stream_state(void *stream, bool make = true);
-void ffhip_state_release(void); /* no call of any thread in flight: empties both registries and the pipeline's slots */
-void ffhip_pipeline_release(void); /* ffhip_pipeline.hip: its two slots of pinned + device buffers */
-int ffhip_pipeline_fill(int value, uint64_t bytes[2]); /* ffhip_pipeline.hip, for ffhip_debug_scratch_fill: every byte of both slots' buffers */
+void ffhip_state_release(void); /* no call of any thread in flight: empties both registries */
 void ffhip_hevc_plan_result_forget(void *stream); /* ffhip_hevc_intra.hip, for ffhip_debug_scratch_fill: the calling thread's pointer to its last plan's verdict in `stream`'s scratch */
 int ffhip_vp8_side_by_side_retry(void *stream); /* ffhip_vp8_lf.hip, for ffhip_stream_sync: 0 nothing reported by a side-by-side call of this
                                                    stream, FFHIP_RETRIED repeated, FFHIP_EIO */
@@ -325,6 +326,10 @@ extern "C" int ffhip_side_stream_get(FfhipSide *out);
  * the event the caller's stream waits for in front of the grouped kernel; same owner and lifetime as the side stream */
 struct FfhipPipe { void *plan, *plan_done; };
 extern "C" int ffhip_pipe_streams_get(FfhipPipe *out);
+/* the calling thread's two slot streams of the JPEG file pipeline (ffhip_pipeline.hip); same owner and lifetime, and what the registry keeps
+ * under them (SCRATCH_FILES_PLANES, SCRATCH_FILES_PIXELS, the device front end's kinds) goes with them */
+struct FfhipSlotStreams { void *s[2]; };
+extern "C" int ffhip_slot_streams_get(FfhipSlotStreams *out);
 
 /* ... and the device Huffman decoder's (ffhip_jpeg_entropy_batch_gpu): the copy stream its parts' bytes go up on, the second kernel stream, the
  * parts' events, fork / join, two timing events; all made together (none is published unless all exist); same owner and lifetime */

@@ -13,87 +13,29 @@
 #include "ffhip_entropy_internal.h"
 #include "ffhip_jpeg_scaled_body.h"
 #include "ffhip_jpeg_prog_internal.h"
+#include "ffhip_planes.h"
 
 #include <stdlib.h>
 #include <string.h>
 
 #include <array>
-#include <mutex>
-#include <thread> /* copy_out */
 #include <vector>
 
 namespace {
-/* two slots of pinned + device buffers and a stream each, kept between calls (pinning hundreds of MB costs
- * more than decoding them) and grown on demand; one pipeline call at a time (mutex) */
-struct Slot {
-    int16_t *h_y = nullptr, *h_u = nullptr, *h_v = nullptr; /* pinned */
-    uint16_t *h_q = nullptr;
-    uint8_t *h_out = nullptr;                               /* pinned staging, unused when the caller's buffer is pinned */
-    int16_t *d_y = nullptr, *d_u = nullptr, *d_v = nullptr;
-    uint16_t *d_q = nullptr;
-    uint8_t *d_out = nullptr;
-    hipStream_t st = nullptr;
-    size_t cap_y = 0, cap_c = 0, cap_q = 0, cap_out = 0, cap_hout = 0; /* bytes */
-    int first = -1, count = 0; /* pictures in flight in this slot */
-};
-Slot g_slot[2];
-std::mutex g_pipe_mu;
-
-bool grow_pair(void **h, void **d, size_t *cap, size_t bytes)
-{
-    if (bytes <= *cap) return true;
-    if (*h) (void)hipHostFree(*h);
-    if (*d) (void)hipFree(*d);
-    *h = *d = nullptr;
-    *cap = 0;
-    if (hipHostMalloc(h, bytes, hipHostMallocDefault) != hipSuccess) { *h = nullptr; return false; }
-    if (hipMalloc(d, bytes) != hipSuccess) { *d = nullptr; return false; }
-    *cap = bytes;
-    return true;
-}
-bool prepare(Slot &s, size_t by, size_t bc, size_t bq, size_t bout, bool need_hout)
-{
-    if (!s.st && hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess) return false;
-    if (!grow_pair((void **)&s.h_y, (void **)&s.d_y, &s.cap_y, by)) return false;
-    if (bc > s.cap_c) {
-        size_t c1 = s.cap_c, c2 = s.cap_c;
-        if (!grow_pair((void **)&s.h_u, (void **)&s.d_u, &c1, bc) || !grow_pair((void **)&s.h_v, (void **)&s.d_v, &c2, bc)) { s.cap_c = 0; return false; }
-        s.cap_c = bc;
-    }
-    if (!grow_pair((void **)&s.h_q, (void **)&s.d_q, &s.cap_q, bq)) return false;
-    if (bout > s.cap_out) {
-        if (s.d_out) (void)hipFree(s.d_out);
-        s.d_out = nullptr; s.cap_out = 0;
-        if (hipMalloc((void **)&s.d_out, bout) != hipSuccess) { s.d_out = nullptr; return false; }
-        s.cap_out = bout;
-    }
-    if (need_hout && bout > s.cap_hout) {
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        s.h_out = nullptr; s.cap_hout = 0;
-        if (hipHostMalloc((void **)&s.h_out, bout, hipHostMallocDefault) != hipSuccess) { s.h_out = nullptr; return false; }
-        s.cap_hout = bout;
-    }
-    s.first = -1;
-    s.count = 0;
-    return true;
-}
-/* rows of `count` pictures from tight pinned staging to the caller's pageable buffer, over host threads */
-void copy_out(uint8_t *bgra, int64_t pitch, int64_t image_stride, const uint8_t *src, size_t dev_pitch, int64_t height, int first,
-              int count, int n_threads)
+/* rows of `count` pictures from tight pinned staging to the caller's pageable buffer, a contiguous range of them to each of 16 host threads
+ * at most; fewer than 64 rows are copied inline (ffhip_planes.h) */
+void copy_out(uint8_t *bgra, int64_t pitch, int64_t image_stride, const uint8_t *src, size_t row_b, int64_t height, int first, int count,
+              int n_threads)
 {
     const long long rows = (long long)count * height;
-    auto part = [&](int t, int nt) {
-        for (long long r = rows * t / nt, e = rows * (t + 1) / nt; r < e; r++) {
+    const int nt = ffhip_copy_threads(rows, n_threads);
+    ffhip_parallel_for(nt, nt, [&](int t) {
+        const FfhipRows mine = ffhip_copy_rows(rows, t, nt);
+        for (long long r = mine.lo; r < mine.hi; r++) {
             const long long i = r / height, y = r % height;
-            memcpy(bgra + (first + i) * image_stride + y * pitch, src + (size_t)r * dev_pitch, dev_pitch);
+            memcpy(bgra + (first + i) * image_stride + y * pitch, src + (size_t)r * row_b, row_b);
         }
-    };
-    const int nt = n_threads < 1 ? 1 : (n_threads > 16 ? 16 : n_threads);
-    if (nt == 1 || rows < 64) { part(0, 1); return; }
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; t++) pool.emplace_back(part, t, nt);
-    part(0, nt);
-    for (auto &th : pool) th.join();
+    });
 }
 
 /* Does the entropy decode of these files go to the device?  FFHIP_JPEG_GPU_ENTROPY=0 keeps it on the host threads and =1 forces it to the device.
@@ -108,65 +50,114 @@ bool jpeg_entropy_on_device(const uint8_t *file0, size_t len0, int n)
     return !(sy && sy[0] == '0') || ffhip_jpeg_probe_restart(file0, len0) > 0 || n >= 1024;
 }
 
-/* Y | U | V | quantiser tables of a batch in one block, device or pinned: yb and cb are the int16 elements of the luma plane and of each chroma
- * plane (cb 0: grey, no chroma planes), the n pictures' tables lie on a 16-byte boundary behind the planes */
-struct Planes { int16_t *y, *u, *v; uint16_t *q; };
-struct PlaneBlock {
-    size_t yb, cb, q_off, bytes;
-    PlaneBlock(size_t yb_, size_t cb_, size_t n) : yb(yb_), cb(cb_), q_off(((yb_ + 2 * cb_) * 2 + 15) & ~(size_t)15), bytes(q_off + n * 512) {}
-    Planes at(uint8_t *base) const { int16_t *y = (int16_t *)base; return {y, cb ? y + yb : nullptr, cb ? y + yb + cb : nullptr, (uint16_t *)(base + q_off)}; }
+/* One of the calling thread's two slots, as a call sees it: the slot's stream (kept per thread and device, ffhip_slot_streams_get) and what
+ * the registry keeps under it (pinning hundreds of MB costs more than decoding them): a chunk's planes and tables as one block on the
+ * device and its pinned twin, both laid out by PlaneBlock; for ffhip_jpeg_decode_files the chunk's pictures on the device and, for a
+ * pageable destination, their tight pinned staging */
+struct Slot {
+    hipStream_t st;
+    uint8_t *h_blk, *d_blk;
+    uint8_t *d_out, *h_out;
+    int first, count; /* pictures in flight in this slot */
 };
-
-/* Host threads Huffman-decode pictures [first, first + cnt) into the slot's pinned planes (yb, cb: int16 elements per picture), then four H2D
- * copies on the slot's stream.  The decoder's code goes to *result if that holds none yet: per-picture codes are in status[], bad pictures
- * still occupy their place. */
-int host_decode_chunk(Slot &sl, const uint8_t *const *files, const size_t *lens, int first, int cnt, int n_threads, const ffhip_jpeg_geom &g,
-                      size_t yb, size_t cb, int *status, int *result)
+/* both slots for chunks of blk_bytes of planes and tables and out_bytes of pictures (0: none), the staging where need_hout */
+int take_slots(Slot slot[2], size_t blk_bytes, size_t out_bytes, bool need_hout)
 {
-    const int erc = ffhip_jpeg_entropy_batch(files + first, lens + first, cnt, n_threads, &g, sl.h_y, cb ? sl.h_u : nullptr, cb ? sl.h_v : nullptr, sl.h_q,
-                                             status + first);
-    if (erc && !*result) *result = erc;
-    hipError_t e = hipMemcpyAsync(sl.d_y, sl.h_y, cnt * yb * 2, hipMemcpyHostToDevice, sl.st);
-    if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_u, sl.h_u, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
-    if (e == hipSuccess && cb) e = hipMemcpyAsync(sl.d_v, sl.h_v, cnt * cb * 2, hipMemcpyHostToDevice, sl.st);
-    if (e == hipSuccess) e = hipMemcpyAsync(sl.d_q, sl.h_q, (size_t)cnt * 512, hipMemcpyHostToDevice, sl.st);
-    return e == hipSuccess ? FFHIP_OK : FFHIP_EIO;
-}
-} // namespace
-
-void ffhip_pipeline_release(void)
-{
-    std::lock_guard<std::mutex> lock(g_pipe_mu);
+    FfhipSlotStreams ss;
+    const int rc = ffhip_slot_streams_get(&ss);
+    if (rc) return rc;
     for (int s = 0; s < 2; s++) {
-        Slot &sl = g_slot[s];
-        if (sl.st) (void)hipStreamSynchronize(sl.st);
-        (void)hipHostFree(sl.h_y); (void)hipHostFree(sl.h_u); (void)hipHostFree(sl.h_v); (void)hipHostFree(sl.h_q); (void)hipHostFree(sl.h_out);
-        (void)hipFree(sl.d_y); (void)hipFree(sl.d_u); (void)hipFree(sl.d_v); (void)hipFree(sl.d_q); (void)hipFree(sl.d_out);
-        if (sl.st) (void)hipStreamDestroy(sl.st);
-        sl = Slot();
-    }
-}
-
-/* ffhip_debug_scratch_fill's share of the slots: every byte of every buffer of both, each slot after its own stream has drained;
- * bytes[0] += device bytes, bytes[1] += pinned bytes.  The streams themselves and first / count are state, not scratch */
-int ffhip_pipeline_fill(int value, uint64_t bytes[2])
-{
-    std::lock_guard<std::mutex> lock(g_pipe_mu);
-    for (int s = 0; s < 2; s++) {
-        Slot &sl = g_slot[s];
-        if (!sl.st) continue; /* never prepared: it holds nothing */
-        FFHIP_CHECK(hipStreamSynchronize(sl.st), FFHIP_EIO);
-        const struct { void *h, *d; size_t cap; } pairs[] = {{sl.h_y, sl.d_y, sl.cap_y}, {sl.h_u, sl.d_u, sl.cap_c}, {sl.h_v, sl.d_v, sl.cap_c},
-                                                              {sl.h_q, sl.d_q, sl.cap_q}, {nullptr, sl.d_out, sl.cap_out}, {sl.h_out, nullptr, sl.cap_hout}};
-        for (const auto &p : pairs) {
-            if (!p.cap) continue;
-            if (p.d) { FFHIP_CHECK(hipMemsetAsync(p.d, value, p.cap, sl.st), FFHIP_EIO); bytes[0] += p.cap; }
-            if (p.h) { memset(p.h, value, p.cap); bytes[1] += p.cap; }
-        }
-        FFHIP_CHECK(hipStreamSynchronize(sl.st), FFHIP_EIO);
+        Slot &sl = slot[s];
+        sl = Slot{(hipStream_t)ss.s[s], nullptr, nullptr, nullptr, nullptr, -1, 0};
+        sl.d_blk = (uint8_t *)ffhip_scratch(SCRATCH_FILES_PLANES, sl.st, (blk_bytes + 3) / 4);
+        sl.h_blk = ffhip_pinned_scratch(SCRATCH_FILES_PLANES, sl.st, blk_bytes);
+        if (!sl.d_blk || !sl.h_blk) return FFHIP_ENOMEM;
+        if (out_bytes && !(sl.d_out = (uint8_t *)ffhip_scratch(SCRATCH_FILES_PIXELS, sl.st, (out_bytes + 3) / 4))) return FFHIP_ENOMEM;
+        if (out_bytes && need_hout && !(sl.h_out = ffhip_pinned_scratch(SCRATCH_FILES_PIXELS, sl.st, out_bytes))) return FFHIP_ENOMEM;
     }
     return FFHIP_OK;
 }
+
+/* where the chunk loop's pictures go: DEVICE, the reconstruction writes picture i at dst + i * image_stride itself; PINNED, it writes the
+ * slot's pictures and 2-D copies behind it take them to dst; PAGEABLE, one 2-D copy takes them to the slot's staging, and host threads from
+ * there to dst once the slot has been waited for */
+struct PixelsOut {
+    enum { DEVICE, PINNED, PAGEABLE } to;
+    uint8_t *dst;
+    int64_t pitch, image_stride;
+};
+
+/* Files [0, n) of geometry g in chunks over the calling thread's two slots: while the front end works on chunk k + 1, chunk k is on its
+ * slot's stream.  The front end is the device decoder where gpu_entropy says so and it takes the chunk (straight into the device planes: the
+ * host only parses headers and unstuffs the scan bytes), else host threads into the pinned block and one upload.  Everything has run when
+ * it returns.  The host decoder's first code is the call's if nothing worse happens: per-picture codes are in status[], bad pictures still
+ * occupy their place. */
+int chunk_loop(const uint8_t *const *files, const size_t *lens, int n, int n_threads, int chunk, const ffhip_jpeg_geom &g, bool gpu_entropy,
+               const PixelsOut &out, int *status)
+{
+    const size_t mcus = (size_t)g.mcu_cols * g.mcu_rows;
+    const size_t yb = mcus * g.h * g.v * 64, cb = g.ncomp == 3 ? mcus * 64 : 0; /* int16 elements per picture */
+    const int64_t width = (int64_t)g.mcu_cols * 8 * g.h, height = (int64_t)g.mcu_rows * 8 * g.v;
+    /* on the device the pictures have the pitch ffhip_bgra_layout recommends (the buffer is the library's; DESIGN.md 5); the pinned staging
+     * for a pageable destination is tight, and every copy off the device is a 2-D copy */
+    int64_t lp = 0, ls = 0;
+    if (out.to != PixelsOut::DEVICE && ffhip_bgra_layout(&g, &lp, &ls) != FFHIP_OK) return FFHIP_EINVAL;
+    const size_t dev_pitch = (size_t)lp, out_b = (size_t)ls, row_b = (size_t)width * 4;
+    Slot slot[2];
+    int rc = take_slots(slot, PlaneBlock(chunk * yb, chunk * cb, (size_t)chunk).bytes, chunk * out_b, out.to == PixelsOut::PAGEABLE);
+    if (rc) return rc;
+    int result = FFHIP_OK;
+    /* wait for what a slot's stream holds -- its chunk has left the pinned block -- and hand the pixels of a chunk that was enqueued whole to the caller */
+    auto drain = [&](Slot &sl) -> int {
+        if (hipStreamSynchronize(sl.st) != hipSuccess) return FFHIP_EIO;
+        if (sl.count && out.to == PixelsOut::PAGEABLE) copy_out(out.dst, out.pitch, out.image_stride, sl.h_out, row_b, height, sl.first, sl.count, n_threads);
+        sl.count = 0;
+        return FFHIP_OK;
+    };
+    int k = 0;
+    for (int first = 0; first < n; first += chunk, k++) {
+        Slot &sl = slot[k & 1];
+        const int cnt = n - first < chunk ? n - first : chunk;
+        rc = drain(sl); /* the slot's previous chunk (k - 2) */
+        if (rc) break;
+        const PlaneBlock blk(cnt * yb, cnt * cb, (size_t)cnt);
+        const Planes d = blk.at(sl.d_blk), h = blk.at(sl.h_blk);
+        bool on_device = false;
+        if (gpu_entropy) {
+            const int grc = ffhip_jpeg_entropy_batch_gpu(files + first, lens + first, cnt, n_threads, &g, d.y, d.u, d.v, d.q, status + first, sl.st);
+            on_device = grc == FFHIP_OK;
+            if (!on_device && grc != FFHIP_EINVAL) { rc = grc; break; }
+        }
+        if (!on_device) {
+            const int erc = ffhip_jpeg_entropy_batch(files + first, lens + first, cnt, n_threads, &g, h.y, h.u, h.v, h.q, status + first);
+            if (erc && !result) result = erc;
+            if (hipMemcpyAsync(sl.d_blk, sl.h_blk, blk.bytes, hipMemcpyHostToDevice, sl.st) != hipSuccess) { rc = FFHIP_EIO; break; }
+        }
+        if (out.to == PixelsOut::DEVICE)
+            rc = ffhip_jpeg_recon_batch(&g, cnt, d.y, d.u, d.v, d.q, 256, out.dst + (int64_t)first * out.image_stride, out.pitch, out.image_stride, nullptr, 0, sl.st);
+        else
+            rc = ffhip_jpeg_recon_batch(&g, cnt, d.y, d.u, d.v, d.q, 256, sl.d_out, (int64_t)dev_pitch, (int64_t)out_b, nullptr, 0, sl.st);
+        if (rc) break;
+        hipError_t e = hipSuccess;
+        if (out.to == PixelsOut::PAGEABLE)
+            e = hipMemcpy2DAsync(sl.h_out, row_b, sl.d_out, dev_pitch, row_b, (size_t)height * cnt, hipMemcpyDeviceToHost, sl.st);
+        else if (out.to == PixelsOut::PINNED && (cnt == 1 || out.image_stride == out.pitch * height)) /* the caller's pictures follow each other row after row: one copy for the chunk */
+            e = hipMemcpy2DAsync(out.dst + (int64_t)first * out.image_stride, (size_t)out.pitch, sl.d_out, dev_pitch, row_b, (size_t)height * cnt, hipMemcpyDeviceToHost, sl.st);
+        else if (out.to == PixelsOut::PINNED)
+            for (int i = 0; i < cnt && e == hipSuccess; i++)
+                e = hipMemcpy2DAsync(out.dst + (int64_t)(first + i) * out.image_stride, (size_t)out.pitch, sl.d_out + (size_t)i * out_b, dev_pitch, row_b, (size_t)height,
+                                     hipMemcpyDeviceToHost, sl.st);
+        if (e != hipSuccess) { rc = FFHIP_EIO; break; }
+        sl.first = first;
+        sl.count = cnt;
+    }
+    for (int s = 0; s < 2; s++) {
+        const int r2 = drain(slot[(k + s) & 1]); /* oldest first */
+        if (rc == FFHIP_OK) rc = r2;
+    }
+    return rc ? rc : result;
+}
+} // namespace
 
 extern "C" void *ffhip_host_malloc(size_t bytes)
 {
@@ -202,75 +193,11 @@ extern "C" int ffhip_jpeg_decode_files(const uint8_t *const *files, const size_t
         if (gpu_entropy && px > 0 && (256ll << 20) / px > chunk) chunk = (int)((256ll << 20) / px > 4096 ? 4096 : (256ll << 20) / px);
     }
     if (chunk > n) chunk = n;
-    const size_t mcus = (size_t)g.mcu_cols * g.mcu_rows;
-    const size_t yb = mcus * g.h * g.v * 64, cb = g.ncomp == 3 ? mcus * 64 : 0; /* int16 elements per picture */
-    /* on the device the pictures have the pitch ffhip_bgra_layout recommends (the buffer is the library's; DESIGN.md 5); the pinned staging
-     * for a pageable destination is tight, and every copy off the device is a 2-D copy */
-    int64_t lp = 0, ls = 0;
-    if (ffhip_bgra_layout(&g, &lp, &ls) != FFHIP_OK) return FFHIP_EINVAL;
-    const size_t dev_pitch = (size_t)lp, out_b = (size_t)ls, row_b = (size_t)width * 4;
     /* a pinned (hipHostMalloc'ed / registered) destination takes the D2H copy directly */
     hipPointerAttribute_t attr;
     const bool pinned_dst = hipPointerGetAttributes(&attr, bgra) == hipSuccess && attr.type == hipMemoryTypeHost;
     if (!pinned_dst) (void)hipGetLastError(); /* an unknown pointer leaves an error behind: not ours */
-
-    std::lock_guard<std::mutex> lock(g_pipe_mu);
-    Slot *slot = g_slot;
-    for (int s = 0; s < 2; s++)
-        if (!prepare(slot[s], chunk * yb * 2, chunk * cb * 2, (size_t)chunk * 512, chunk * out_b, !pinned_dst)) return FFHIP_ENOMEM;
-    int result = FFHIP_OK;
-    /* wait for a slot's chunk and hand its pixels to the caller */
-    auto drain = [&](Slot &sl) -> int {
-        if (sl.count == 0) return FFHIP_OK;
-        if (hipStreamSynchronize(sl.st) != hipSuccess) return FFHIP_EIO;
-        if (!pinned_dst) copy_out(bgra, pitch, image_stride, sl.h_out, row_b, height, sl.first, sl.count, n_threads);
-        sl.count = 0;
-        return FFHIP_OK;
-    };
-    rc = FFHIP_OK;
-    int k = 0;
-    for (int first = 0; first < n && rc == FFHIP_OK; first += chunk, k++) {
-        Slot &sl = slot[k & 1];
-        const int cnt = n - first < chunk ? n - first : chunk;
-        rc = drain(sl); /* the slot's previous chunk (k - 2) */
-        if (rc) break;
-        hipError_t e = hipSuccess;
-        /* entropy decode.  On the device, straight into the device planes (the host only parses headers and unstuffs the
-         * scan bytes), unless the gate keeps the files on the host or the device call refuses them: then host threads
-         * into pinned memory and H2D.  Either way chunk k - 1 is on the GPU meanwhile. */
-        bool on_device = false;
-        if (gpu_entropy) {
-            const int grc = ffhip_jpeg_entropy_batch_gpu(files + first, lens + first, cnt, n_threads, &g, sl.d_y, cb ? sl.d_u : nullptr,
-                                                         cb ? sl.d_v : nullptr, sl.d_q, status + first, sl.st);
-            on_device = grc == FFHIP_OK;
-            if (!on_device && grc != FFHIP_EINVAL) { rc = grc; break; }
-        }
-        if (!on_device) {
-            rc = host_decode_chunk(sl, files, lens, first, cnt, n_threads, g, yb, cb, status, &result);
-            if (rc) break;
-        }
-        rc = ffhip_jpeg_recon_batch(&g, cnt, sl.d_y, cb ? sl.d_u : nullptr, cb ? sl.d_v : nullptr, sl.d_q, 256, sl.d_out, (int64_t)dev_pitch,
-                                    (int64_t)out_b, nullptr, 0, sl.st);
-        if (rc) break;
-        if (pinned_dst) {
-            if (cnt == 1 || image_stride == pitch * height) /* the caller's pictures follow each other row after row: one copy for the chunk */
-                e = hipMemcpy2DAsync(bgra + (int64_t)first * image_stride, (size_t)pitch, sl.d_out, dev_pitch, row_b, (size_t)height * cnt, hipMemcpyDeviceToHost, sl.st);
-            else
-                for (int i = 0; i < cnt && e == hipSuccess; i++)
-                    e = hipMemcpy2DAsync(bgra + (int64_t)(first + i) * image_stride, (size_t)pitch, sl.d_out + (size_t)i * out_b, dev_pitch, row_b,
-                                         (size_t)height, hipMemcpyDeviceToHost, sl.st);
-        } else {
-            e = hipMemcpy2DAsync(sl.h_out, row_b, sl.d_out, dev_pitch, row_b, (size_t)height * cnt, hipMemcpyDeviceToHost, sl.st);
-        }
-        if (e != hipSuccess) { rc = FFHIP_EIO; break; }
-        sl.first = first;
-        sl.count = cnt;
-    }
-    for (int s = 0; s < 2; s++) {
-        const int r2 = drain(slot[(k + s) & 1]); /* oldest first */
-        if (rc == FFHIP_OK) rc = r2;
-    }
-    return rc ? rc : result;
+    return chunk_loop(files, lens, n, n_threads, chunk, g, gpu_entropy, {pinned_dst ? PixelsOut::PINNED : PixelsOut::PAGEABLE, bgra, pitch, image_stride}, status);
 }
 
 /* Files in, pixels out ON THE DEVICE: for consumers that live on the GPU (a resize, an inference pre-processing
@@ -290,7 +217,6 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
     if (!ffhip_have_device()) return FFHIP_ENODEV;
     const size_t mcus = (size_t)g.mcu_cols * g.mcu_rows;
     const size_t yb = mcus * g.h * g.v * 64, cb = g.ncomp == 3 ? mcus * 64 : 0; /* int16 elements per picture */
-    hipStream_t st = (hipStream_t)stream;
     if (jpeg_entropy_on_device(files[0], lens[0], n)) {
         /* entropy decode on the device, straight into planes in library scratch; the reconstruction is enqueued by the entropy call itself, behind
          * each part of the batch as it is decoded */
@@ -303,32 +229,14 @@ extern "C" int ffhip_jpeg_decode_files_device(const uint8_t *const *files, const
         if (rc == FFHIP_OK) return FFHIP_OK;
         if (rc != FFHIP_EINVAL) return rc;
     }
-    /* Host threads (the gate's answer, or the device call refused the files).  A pipeline of
-     * chunks over the two slots ffhip_jpeg_decode_files uses: while the host threads decode chunk k + 1 into pinned memory, chunk k is copied
-     * to the device and reconstructed on the slot's own stream, straight into the caller's d_bgra.  (Until round 5 this path decoded the whole
-     * batch into pageable vectors, then uploaded it: 1.84 s for 256 4K files, most of it page faults and a pageable copy of 9.5 GB.)  Everything
-     * has run when the call returns. */
+    /* Host threads (the gate's answer, or the device call refused the files).  The chunk loop of ffhip_jpeg_decode_files over the same two slots:
+     * while the host threads decode chunk k + 1 into pinned memory, chunk k is copied to the device and reconstructed on the slot's own stream,
+     * straight into the caller's d_bgra.  (Until round 5 this path decoded the whole batch into pageable vectors, then uploaded it: 1.84 s for
+     * 256 4K files, most of it page faults and a pageable copy of 9.5 GB.)  Everything has run when the call returns. */
     int chunk = n_threads < 8 ? 8 : (n_threads > 32 ? 32 : n_threads);
     if (chunk > n) chunk = n;
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO); /* d_bgra may still be read by what `stream` holds */
-    std::lock_guard<std::mutex> lock(g_pipe_mu);
-    Slot *slot = g_slot;
-    for (int s = 0; s < 2; s++)
-        if (!prepare(slot[s], chunk * yb * 2, chunk * cb * 2, (size_t)chunk * 512, 0, false)) return FFHIP_ENOMEM;
-    int result = FFHIP_OK, k = 0;
-    rc = FFHIP_OK;
-    for (int first = 0; first < n && rc == FFHIP_OK; first += chunk, k++) {
-        Slot &sl = slot[k & 1];
-        const int cnt = n - first < chunk ? n - first : chunk;
-        if (hipStreamSynchronize(sl.st) != hipSuccess) { rc = FFHIP_EIO; break; } /* the slot's previous chunk (k - 2) has left its pinned planes */
-        rc = host_decode_chunk(sl, files, lens, first, cnt, n_threads, g, yb, cb, status, &result);
-        if (rc) break;
-        rc = ffhip_jpeg_recon_batch(&g, cnt, sl.d_y, cb ? sl.d_u : nullptr, cb ? sl.d_v : nullptr, sl.d_q, 256, d_bgra + (int64_t)first * image_stride, pitch, image_stride,
-                                    nullptr, 0, sl.st);
-    }
-    for (int s = 0; s < 2; s++)
-        if (hipStreamSynchronize(slot[s].st) != hipSuccess && rc == FFHIP_OK) rc = FFHIP_EIO;
-    return rc ? rc : result;
+    FFHIP_CHECK(hipStreamSynchronize((hipStream_t)stream), FFHIP_EIO); /* d_bgra may still be read by what `stream` holds */
+    return chunk_loop(files, lens, n, n_threads, chunk, g, false, {PixelsOut::DEVICE, d_bgra, pitch, image_stride}, status);
 }
 
 namespace {
@@ -491,8 +399,7 @@ int jpeg_decode_files_mixed(const uint8_t *const *files, const size_t *lens, int
     for (int i = 0; denom && i < n; i++)
         if (!jpeg_denom_ok(denom[i]) || (lj && denom[i] != 1)) return FFHIP_EINVAL;
     if (n == 0) return FFHIP_OK;
-    if (n_threads < 1) n_threads = 1;
-    if (n_threads > 64) n_threads = 64;
+    n_threads = ffhip_host_threads(n_threads);
     /* ---- headers: each file's geometry and class; a file the mixed path cannot take (progressive without the flag, 12-bit, a two-pass
      * layout, an output or pitch the rule's items call refuses) has its code now and takes no further part ---- */
     std::vector<JpegProbed> probed((size_t)n);

@@ -99,8 +99,6 @@ template <class Desc, class Launch> int ffhip_gather_launch(int kind, void *stre
     return ffhip_items_launch(0, total, [&](unsigned grid_x, u32 wg_base) { launch(d_desc, d_table, grid_x, wg_base); });
 }
 
-inline int ffhip_host_threads(int n_threads) { return n_threads < 1 ? 1 : n_threads > 64 ? 64 : n_threads; }
-
 /* what a gather kernel asks of a BGRA output: whole 16-byte stores */
 inline bool ffhip_bgra_takes_stores16(const uint8_t *p, int64_t pitch, int64_t width)
 {

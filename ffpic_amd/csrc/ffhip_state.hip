@@ -1,9 +1,10 @@
 /*
  * ffhip_state.hip -- what libffpic_hip.so keeps between calls, in two registries with one lock:
  *   per (device, stream): device scratch and pinned staging per kind, the VP8 retry record, the HEVC tile guard;
- *   per (thread, device): the side stream and the other streams and events of the calls that fork work off the caller's stream,
+ *   per (thread, device): the side stream and the other streams and events of the calls that fork work off the caller's stream, the two
+ *   slot streams of the JPEG file pipeline (their buffers are entries of the first registry, like any stream's),
  *   and per thread the Huffman decoder's header records.
- * One path (ffhip_state_release) empties both, with the pipeline's slots; one test hook (ffhip_debug_scratch_fill) overwrites what they hold.
+ * One path (ffhip_state_release) empties both; one test hook (ffhip_debug_scratch_fill) overwrites what they hold.
  */
 #include "ffhip_internal.h"
 #include "ffhip_entropy_internal.h"
@@ -46,6 +47,22 @@ void release(FfhipStreamState &s)
     if (s.retry.err) (void)hipHostFree(s.retry.err);
     for (hipEvent_t e : s.tiles.ev)
         if (e) (void)hipEventDestroy(e);
+}
+/* With g_ffhip_state_mu held and nothing of `s` in flight: every entry of the handle `s` goes, whatever device was current when it was made,
+ * so that a stream made next with the same handle starts from nothing.  An abort a side-by-side VP8 call of `s` reported, and nobody
+ * collected, goes to the process-wide word: not lost. */
+void forget_stream(void *s)
+{
+    for (auto it = g_streams.begin(); it != g_streams.end();) {
+        if (it->first.second != s) { ++it; continue; }
+        const int *err = it->second.retry.err;
+        if (err && *(volatile const int *)err) {
+            int *g = ffhip_async_err_word();
+            if (g) *(volatile int *)g = *(volatile const int *)err;
+        }
+        release(it->second);
+        it = g_streams.erase(it);
+    }
 }
 } // namespace
 
@@ -91,25 +108,14 @@ extern "C" int ffhip_pinned_staged(int kind, void *stream)
     return hipEventRecord(ev, (hipStream_t)stream) == hipSuccess ? FFHIP_OK : FFHIP_EIO;
 }
 
-/* Waits for what `s` holds, then frees its entries with the stream: a stream made next with the same handle starts from nothing.  (A handle
- * other than NULL names one stream whatever device was current when an entry was made: all of its entries go.)  An abort a side-by-side
- * VP8 call of `s` reported, and nobody collected, goes to the process-wide word: not lost. */
+/* Waits for what `s` holds, then frees its entries with the stream (forget_stream) */
 extern "C" void ffhip_stream_destroy(void *s)
 {
     if (!s) return;
     (void)hipStreamSynchronize((hipStream_t)s);
     {
         std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
-        for (auto it = g_streams.begin(); it != g_streams.end();) {
-            if (it->first.second != s) { ++it; continue; }
-            const int *err = it->second.retry.err;
-            if (err && *(volatile const int *)err) {
-                int *g = ffhip_async_err_word();
-                if (g) *(volatile int *)g = *(volatile const int *)err;
-            }
-            release(it->second);
-            it = g_streams.erase(it);
-        }
+        forget_stream(s);
     }
     (void)hipStreamDestroy((hipStream_t)s);
 }
@@ -148,7 +154,17 @@ struct ThreadSet {
     Group<1, 3> side;
     Group<1, 1> pipe;                    /* plan; plan_done */
     Group<2, FFHIP_HUFF_PARTS + 4> huff; /* up, c2; the last two events time */
-    void release() { side.release(); pipe.release(); huff.release(); }
+    Group<2, 0> slots;                   /* the JPEG file pipeline's (ffhip_pipeline.hip): a chunk in flight on each */
+    /* with g_ffhip_state_mu held, no call of the thread in flight.  The slot streams own registry entries: those go with them */
+    void release()
+    {
+        for (hipStream_t s : slots.s) {
+            if (!s) continue;
+            (void)hipStreamSynchronize(s);
+            forget_stream(s);
+        }
+        side.release(); pipe.release(); huff.release(); slots.release();
+    }
 };
 struct ThreadState;
 std::vector<ThreadState *> g_threads;
@@ -186,6 +202,13 @@ extern "C" int ffhip_side_stream_get(FfhipSide *out)
     *out = {g->s[0], g->ev[0], g->ev[1], g->ev[2]};
     return FFHIP_OK;
 }
+extern "C" int ffhip_slot_streams_get(FfhipSlotStreams *out)
+{
+    const auto *g = thread_group(&ThreadSet::slots, false, 0);
+    if (!g) return FFHIP_EIO;
+    *out = {{g->s[0], g->s[1]}};
+    return FFHIP_OK;
+}
 extern "C" int ffhip_pipe_streams_get(FfhipPipe *out)
 {
     const auto *g = thread_group(&ThreadSet::pipe, false, 1);
@@ -218,18 +241,17 @@ struct jpeg_hdr *ffhip_huff_hdr_records(size_t n)
 }
 
 /* ---- diagnostics: the contents of what is kept, set by a test (include/ffpic_hip.h) ----
- * Scratch is (current device, stream)'s device and pinned buffers over their whole capacity, the pipeline's slots and the calling thread's
- * header records.  State is left alone: the retry record's pinned word, the async error word, events, streams, the tile guard.  Two kinds keep
- * content a later call needs, and the host-side mark that says it is valid is dropped with it: SCRATCH_VP8_RETRY, the luma column
- * ffhip_stream_sync puts back when it repeats a side-by-side call (`armed`; a report that is still waiting to be collected refuses the fill),
- * and the device planner's verdict in the HEVC scratch that ffhip_debug_hevc_plan_result reads (the calling thread's pointer to it). */
-extern "C" int ffhip_debug_scratch_fill(void *stream, int value, uint64_t bytes[2], int *kinds, int cap)
+ * Scratch is (current device, stream)'s device and pinned buffers over their whole capacity, the same of the calling thread's two slot streams
+ * of the current device, and the thread's header records.  State is left alone: the retry record's pinned word, the async error word, events,
+ * streams, the tile guard.  Two kinds keep content a later call needs, and the host-side mark that says it is valid is dropped with it:
+ * SCRATCH_VP8_RETRY, the luma column ffhip_stream_sync puts back when it repeats a side-by-side call (`armed`; a report that is still waiting
+ * to be collected refuses the fill), and the device planner's verdict in the HEVC scratch that ffhip_debug_hevc_plan_result reads (the calling
+ * thread's pointer to it). */
+namespace {
+/* waits for `stream` and for the events behind the last copies out of its pinned staging (outside the lock, as ffhip_pinned_staging waits) */
+int drain_for_fill(void *stream)
 {
-    if (!bytes || cap < 0 || (cap > 0 && !kinds)) return FFHIP_EINVAL;
-    bytes[0] = bytes[1] = 0;
-    if (!ffhip_have_device()) return FFHIP_ENODEV;
-    hipStream_t st = (hipStream_t)stream;
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
+    FFHIP_CHECK(hipStreamSynchronize((hipStream_t)stream), FFHIP_EIO);
     std::vector<hipEvent_t> staged;
     {
         std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
@@ -237,60 +259,89 @@ extern "C" int ffhip_debug_scratch_fill(void *stream, int value, uint64_t bytes[
             for (auto &s : e->staged)
                 if (s.second) staged.push_back(s.second);
     }
-    for (hipEvent_t ev : staged) FFHIP_CHECK(hipEventSynchronize(ev), FFHIP_EIO); /* (outside the lock, as ffhip_pinned_staging waits) */
-    int count = 0;
+    for (hipEvent_t ev : staged) FFHIP_CHECK(hipEventSynchronize(ev), FFHIP_EIO);
+    return FFHIP_OK;
+}
+/* with g_ffhip_state_mu held: every byte of every buffer of `e`, the device ones by memsets enqueued on `st`; bytes[0] += device bytes,
+ * bytes[1] += pinned bytes, the kinds behind `seen` */
+int fill_entry(FfhipStreamState &e, hipStream_t st, int value, uint64_t bytes[2], std::vector<int> &seen)
+{
+    for (auto &b : e.scratch) {
+        if (!b.second.p) continue;
+        FFHIP_CHECK(hipMemsetAsync(b.second.p, value, b.second.cap * sizeof(uint32_t), st), FFHIP_EIO);
+        bytes[0] += b.second.cap * sizeof(uint32_t);
+        seen.push_back(b.first);
+    }
+    for (auto &b : e.pinned) {
+        if (!b.second.p) continue;
+        memset(b.second.p, value, b.second.cap);
+        bytes[1] += b.second.cap;
+        seen.push_back(b.first);
+    }
+    return FFHIP_OK;
+}
+} // namespace
+
+extern "C" int ffhip_debug_scratch_fill(void *stream, int value, uint64_t bytes[2], int *kinds, int cap)
+{
+    if (!bytes || cap < 0 || (cap > 0 && !kinds)) return FFHIP_EINVAL;
+    bytes[0] = bytes[1] = 0;
+    if (!ffhip_have_device()) return FFHIP_ENODEV;
+    ThreadState &t = this_thread();
+    int dev = -1;
+    (void)hipGetDevice(&dev);
+    void *streams[3] = {stream, nullptr, nullptr}; /* the caller's, then the thread's slot streams of this device, where they exist */
+    int n_streams = 1;
     {
         std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
-        if (FfhipStreamState *e = ffhip_stream_state(stream, false)) {
+        auto set = t.sets.find(dev);
+        if (set != t.sets.end())
+            for (hipStream_t s : set->second.slots.s)
+                if (s) streams[n_streams++] = s;
+    }
+    std::vector<int> seen;
+    for (int k = 0; k < n_streams; k++) {
+        const int rc = drain_for_fill(streams[k]);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
+        FfhipStreamState *e = ffhip_stream_state(streams[k], false);
+        if (!e) continue;
+        if (k == 0) {
             if (e->retry.armed && e->retry.err && *(volatile int *)e->retry.err) return FFHIP_EIO; /* ffhip_stream_sync first: the repeat needs the column */
             e->retry.armed = false;
             ffhip_hevc_plan_result_forget(stream);
-            std::vector<int> seen;
-            for (auto &b : e->scratch) {
-                if (!b.second.p) continue;
-                FFHIP_CHECK(hipMemsetAsync(b.second.p, value, b.second.cap * sizeof(uint32_t), st), FFHIP_EIO);
-                bytes[0] += b.second.cap * sizeof(uint32_t);
-                seen.push_back(b.first);
-            }
-            for (auto &b : e->pinned) {
-                if (!b.second.p) continue;
-                memset(b.second.p, value, b.second.cap);
-                bytes[1] += b.second.cap;
-                seen.push_back(b.first);
-            }
-            std::sort(seen.begin(), seen.end());
-            seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
-            for (int k : seen) {
-                if (count < cap) kinds[count] = k;
-                count++;
-            }
         }
+        const int frc = fill_entry(*e, (hipStream_t)streams[k], value, bytes, seen);
+        if (frc) return frc;
     }
-    const int prc = ffhip_pipeline_fill(value, bytes);
-    if (prc) return prc;
+    std::sort(seen.begin(), seen.end());
+    seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
+    int count = 0;
+    for (int k : seen) {
+        if (count < cap) kinds[count] = k;
+        count++;
+    }
     {
-        ThreadState &t = this_thread();
         std::lock_guard<std::mutex> lock(g_ffhip_state_mu);
         if (t.hdr) {
             memset((void *)t.hdr.get(), value, t.hdr_cap * sizeof(struct jpeg_hdr));
             bytes[1] += t.hdr_cap * sizeof(struct jpeg_hdr);
         }
     }
-    FFHIP_CHECK(hipStreamSynchronize(st), FFHIP_EIO);
+    for (int k = n_streams - 1; k >= 0; k--) FFHIP_CHECK(hipStreamSynchronize((hipStream_t)streams[k]), FFHIP_EIO);
     return count;
 }
 
 /* No call of ANY thread may be in flight, host part included: every thread's streams, events and header records go too. */
 void ffhip_state_release(void)
 {
-    ffhip_pipeline_release();
     std::lock_guard<std::mutex> l(g_ffhip_state_mu);
-    for (auto &e : g_streams) release(e.second);
-    g_streams.clear();
     for (ThreadState *t : g_threads) {
         for (auto &e : t->sets) e.second.release();
         t->sets.clear();
         t->hdr.reset();
         t->hdr_cap = 0;
     }
+    for (auto &e : g_streams) release(e.second);
+    g_streams.clear();
 }

@@ -19,14 +19,17 @@
  * THREADS AND STREAMS (held by tests/test_concurrent_gpu.py; the state behind it is listed in DESIGN.md 4.27):
  *  - In flight together: calls of different host threads, each on a stream of ITS OWN, and calls of one thread on different streams.  What
  *    the library keeps between calls is per (device, stream) -- scratch, pinned staging, the VP8 retry record, the HEVC tile guard -- or per
- *    (thread, device) -- the side, pipe and Huffman streams it forks work to -- and the ffhip_debug_*_last* records are per thread: a
- *    thread reads the record of its own last call whatever other threads do meanwhile.  A thread binds its device with ffhip_init first
- *    (hipSetDevice is per thread).
+ *    (thread, device) -- the side, pipe and Huffman streams it forks work to, the two slot streams of the JPEG file pipeline -- and the
+ *    ffhip_debug_*_last* records are per thread: a thread reads the record of its own last call whatever other threads do meanwhile.  A
+ *    thread binds its device with ffhip_init first (hipSetDevice is per thread).
  *  - Calls on ONE stream, the NULL stream included, are ordered by the caller: no two threads may have a call on the same stream in
  *    flight, and the entries without a stream argument, other than those of the next point, use the NULL stream.
- *  - Entries that serialise themselves, because each has ONE staging allocation (the NULL stream's): ffhip_jpeg_recon_batch_host, the block
- *    operations (every function of ffhip_accl_ops_get, ffhip_get_dct_ops and ffhip_get_cs_ops, and ffhip_idct_4x4_hevc) and the two slots
- *    of ffhip_jpeg_decode_files.  Any number of threads may call them at once; they take turns, a whole call at a time.
+ *  - Entries that serialise themselves, because each has ONE staging allocation (the NULL stream's): ffhip_jpeg_recon_batch_host and the block
+ *    operations (every function of ffhip_accl_ops_get, ffhip_get_dct_ops and ffhip_get_cs_ops, and ffhip_idct_4x4_hevc).  Any number of
+ *    threads may call them at once; they take turns, a whole call at a time.
+ *  - ffhip_jpeg_decode_files (and the host-thread path of ffhip_jpeg_decode_files_device) shares nothing: each calling thread keeps two slots
+ *    per device -- a stream each, with pinned and device memory for a chunk of pictures -- and ffhip_shutdown / ffhip_release_caches or the
+ *    thread's end frees them.  Any number of threads may call at once, and none waits for another.
  *  - ffhip_shutdown and hip_accl_uninit free what calls in flight use: every thread must be quiet,
  *    host parts of calls included.  ffhip_stream_destroy needs only its own stream's caller quiet.  ffhip_reload_env may be called at any
  *    time, but a call in flight may have read a switch before it.
@@ -65,8 +68,8 @@ int ffhip_device_count(void);
 /* Bind the calling thread's library state to `device` (hipSetDevice) and create
  * the small internal staging buffers used by the per-block entry points. */
 int ffhip_init(int device);
-void ffhip_shutdown(void); /* with no call of any thread in flight: frees the scratch, staging and pipeline buffers the library keeps
-                              between calls; a later compute call binds the device again */
+void ffhip_shutdown(void); /* with no call of any thread in flight: frees the scratch and staging the library keeps between calls, with
+                              every thread's own streams (the file pipeline's slots among them); a later compute call binds the device again */
 const char *ffhip_strerror(int code);
 /* The FFHIP_* environment switches (A/B knobs of tests/tools, diagnostics; none is needed in production) are read ONCE per
  * process, at first use.  A host that changes one in a live process calls this to have them read again. */
@@ -76,10 +79,11 @@ void ffhip_reload_env(void);
 long ffhip_env_value_test(const char *name, char *dst, size_t cap);
 /* Diagnostics, a test hook: sets every byte of what the library keeps between calls for (current device, `stream`) to the low byte of `value`,
  * so that a test can show that no call's output depends on what an earlier call left there.  With no call of the library in flight on `stream`
- * (and, for the slots and records below, none at all): waits for `stream` and for the events behind the last copies out of its pinned staging,
- * then fills, over their WHOLE capacity (the headroom behind what the last call used included),
+ * (and, for the slots and records below, none of the calling thread's at all): waits for `stream` and for the events behind the last copies out
+ * of its pinned staging, then fills, over their WHOLE capacity (the headroom behind what the last call used included),
  *   - every device scratch buffer and every pinned buffer of (current device, stream);
- *   - the two slots of ffhip_jpeg_decode_files (pinned and device planes, tables, pixels), each after its own stream has drained;
+ *   - the calling thread's slots of the current device, every kind kept under their streams, the front end's included (pinned and device
+ *     planes and tables, pixels; the device Huffman decoder's staging and sync arrays), each after its own stream has drained;
  *   - the calling thread's header records of ffhip_jpeg_entropy_batch_gpu;
  * and waits again.  bytes[0], bytes[1]: device and host bytes written.  kinds[0..cap): the scratch kinds (the library's internal numbering,
  * ascending) that had a device or a pinned buffer; the return value is their count, whatever cap is.

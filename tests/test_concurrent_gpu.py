@@ -2,8 +2,9 @@
 
 a. every pair of families of entry points meets on two threads, by the schedule of tests/concurrency.py, under both front-end configurations;
 b. the kernels whose waves wait for each other run beside each other at the sizes of test_handoff_stress_gpu.py;
-c. the entries the library serialises itself -- ffhip_jpeg_recon_batch_host, ffhip_jpeg_decode_files, the block operations -- are called by four
-   threads at once, each with data of its own;
+c. the entries without a stream argument -- ffhip_jpeg_recon_batch_host and the block operations, which the library serialises itself, and
+   ffhip_jpeg_decode_files, whose two slots each calling thread keeps for itself -- are called by four threads at once, each with data of
+   its own; and threads that end give their slots back with their streams;
 d. the first calls of a process are made by four threads at once (a child process);
 e. the per-thread diagnostic records hold the calling thread's call while the other threads make theirs.
 Every comparison is exact, against answer keys made on the main thread before a thread starts; no switch changes while threads run; the
@@ -210,7 +211,7 @@ def test_kernels_that_wait_for_each_other_run_beside_each_other(handoff, threads
 
 # ---------------------------------------------------------------------------------------------------- c. entries that serialise themselves
 def test_host_entry_and_file_pipeline_from_four_threads():
-    """ffhip_jpeg_recon_batch_host (one lock around the call) and ffhip_jpeg_decode_files (the pipeline's two slots under theirs), four
+    """ffhip_jpeg_recon_batch_host (one lock around the call) and ffhip_jpeg_decode_files (each thread on two slots of its own, no lock), four
     threads at once, planes and files of each thread's own: the oracle's pictures"""
     q = synth.quant_tables()
     jobs = []
@@ -233,6 +234,73 @@ def test_host_entry_and_file_pipeline_from_four_threads():
     with K.Crew(4) as crew:
         for _ in range(3):
             crew.round(jobs, reps=4, labels=["host entry + files"] * 4)
+
+
+def test_file_pipeline_slots_end_with_their_thread():
+    """Six threads, one after another: each makes one ffhip_jpeg_decode_files call (two pictures a chunk; the device front end on the even
+    threads, host threads on the odd ones) and one ffhip_jpeg_decode_files_device call on the host path, and ends -- its slot streams are
+    destroyed, and what the library kept under them goes with them.  A slot stream made next may get a handle of theirs and must start
+    from nothing: two fresh threads in turn find nothing to fill before their first call and, behind a one-picture call, their own
+    slots' two kinds at the same byte counts and nothing an ended thread kept; the main thread then makes its own calls, sets every byte
+    the library keeps for it to 0x5A, and makes them again.  Every picture is the answer key's, with the 0xA5 around it intact."""
+    import threading
+    capi.require_device(0)
+    small, larger, _ = F.uniform_file_sets(50)
+    files, device = F.uniform_runner(small, None, True, 2), F.uniform_runner(small, None)
+    errors = []
+
+    def work(t):
+        try:
+            capi.setenv("FFHIP_JPEG_GPU_ENTROPY", "0" if t & 1 else None)      # (no other thread runs meanwhile)
+            files()
+            capi.setenv("FFHIP_JPEG_GPU_ENTROPY", "0")
+            device()
+        except BaseException as e:  # noqa: BLE001 -- reported below, on the main thread
+            errors.append((t, e))
+
+    for t in range(6):
+        th = threading.Thread(target=work, args=(t,))
+        th.start()
+        th.join()
+        assert not errors, errors
+
+    # no entry of an ended thread's is left for a later thread to find: a fresh thread with a fresh stream has nothing to fill before its
+    # first call; behind one host-threads call of ONE picture a fill finds its slots' two kinds and nothing else -- not the device front
+    # end's kinds the even threads kept under their slot streams, not their two-picture capacities -- twice over, the same bytes
+    one, seen = F.uniform_runner(small[:1], None, True, 1), []
+
+    def fresh(t):
+        try:
+            L = capi.require_device(0)
+            s = L.ffhip_stream_create()
+            assert s
+            before = SF.fill(s, 0x5A)
+            assert before == (0, 0, []), before
+            capi.setenv("FFHIP_JPEG_GPU_ENTROPY", "0")
+            one()
+            dev, host, kinds = SF.fill(s, 0x5A)
+            assert dev > 0 and host > 0 and {SF.base_of(k) for k in kinds} == {"SCRATCH_FILES_PLANES", "SCRATCH_FILES_PIXELS"}, (dev, host, kinds)
+            seen.append((dev, host, kinds))
+            one()
+            L.ffhip_stream_destroy(s)
+        except BaseException as e:  # noqa: BLE001
+            errors.append((t, e))
+
+    for t in (6, 7):
+        th = threading.Thread(target=fresh, args=(t,))
+        th.start()
+        th.join()
+        assert not errors, errors
+    assert seen[0] == seen[1], seen
+    own = [F.uniform_runner(larger, None, True, 2), files, device]
+    for entropy in (None, "0"):
+        capi.setenv("FFHIP_JPEG_GPU_ENTROPY", entropy)
+        for run in own:
+            run()
+        dev, host, kinds = SF.fill(None, 0x5A)
+        assert dev > 0 and host > 0 and {"SCRATCH_FILES_PLANES", "SCRATCH_FILES_PIXELS"} <= {SF.base_of(k) for k in kinds}, (dev, host, kinds)
+        for run in own:
+            run()
 
 
 def test_block_operations_from_four_threads():

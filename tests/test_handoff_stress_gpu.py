@@ -357,3 +357,33 @@ def test_null_stream_calls_alternating_between_two_devices():
     for k in calls:
         k.close()
     capi.require_device(0)
+
+
+def test_jpeg_file_calls_alternating_between_two_devices():
+    """One thread, ffhip_jpeg_decode_files (pageable destination, two pictures a chunk) and ffhip_jpeg_decode_files_device on device 0, then 1,
+    then 0 ...: the thread's two slots -- their streams, and the planes, pixels and front-end scratch the library keeps under them -- are per
+    device like the rest of its state.  Six rounds with the device front end and six with host threads; behind the third round every byte
+    of what the library keeps on either device is set to 0xFF.  Every picture is the answer key's, with the 0xA5 around it intact."""
+    import ctypes as C
+
+    import test_scratch_fill_gpu as F
+    L = capi.lib()
+    if L.ffhip_device_count() < 2:
+        pytest.skip("needs two devices")
+    small, larger, _ = F.uniform_file_sets()
+    runs = [[F.uniform_runner(larger, None, True, 2, device=d), F.uniform_runner(small, None, True, 2, device=d),
+             F.uniform_runner(larger, None, device=d), F.uniform_runner(small, None, device=d)] for d in (0, 1)]
+    try:
+        for entropy in (None, "0"):
+            capi.setenv("FFHIP_JPEG_GPU_ENTROPY", entropy)              # before the rounds start
+            for rnd in range(6):
+                for run in runs[rnd & 1]:
+                    run()
+                if rnd == 2:
+                    for d in (0, 1):
+                        capi.require_device(d)
+                        nbytes, kinds = (C.c_uint64 * 2)(), (C.c_int * 256)()
+                        assert L.ffhip_debug_scratch_fill(None, 0xFF, nbytes, kinds, 256) > 0 and nbytes[0] > 0 and nbytes[1] > 0, (entropy, d)
+    finally:
+        capi.setenv("FFHIP_JPEG_GPU_ENTROPY", None)
+        capi.require_device(0)

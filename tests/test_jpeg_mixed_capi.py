@@ -133,3 +133,19 @@ def test_file_entry_reports_geometries_then_no_device(no_gpu):
     pitch[1] = 640 * 4 - 16
     assert L.ffhip_jpeg_decode_files_mixed_device(ptrs, lens, n, 2, outs, pitch, geoms, status, None) == capi.FFHIP_ENODEV
     assert status[0] == 0 and status[1] == capi.FFHIP_EINVAL
+
+
+def test_the_slots_arithmetic_on_the_cpu_under_the_sanitizers(tmp_path):
+    """tests/tools/check_slots.cpp: ffhip_planes.h -- a chunk's planes and tables inside a slot's block for every chunk
+    size up to the slot's, and the split of copy_out's rows over host threads.  A stand-alone program with the sanitizers' runtimes
+    linked into it"""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "check_slots")
+    subprocess.check_call([shutil.which("g++") or "g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", "-I", os.path.join(root, "ffpic_amd", "csrc"),
+                           os.path.join(root, "tests", "tools", "check_slots.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert r.stdout.startswith("ok: 525 blocks, "), r.stdout

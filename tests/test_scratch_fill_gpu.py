@@ -1,7 +1,8 @@
 """GPU: no call's output depends on what the library's kept memory held before it.
 
-The library keeps, per (device, stream) and scratch kind, a device buffer and a pinned one that only grow (with a quarter of headroom),
-the two slots of ffhip_jpeg_decode_files and per thread the Huffman decoder's header records.  In the rest of the suite a call finds there
+The library keeps, per (device, stream) and scratch kind, a device buffer and a pinned one that only grow (with a quarter of headroom) --
+each thread's two slots of the JPEG file pipeline are such buffers, under slot streams the thread keeps per device: a fill reaches every
+kind kept under them, the front end's included -- and per thread the Huffman decoder's header records.  In the rest of the suite a call finds there
 either a fresh allocation or its own case's bytes from last time.  Here ffhip_debug_scratch_fill sets every byte of all of it -- 0xFF,
 0x5A, 0x00 in turn -- between the calls of every family of entry points, by the protocol of scratch_fill.run_protocol: the family's
 larger case first, then its small cases after each fill, then the larger case after a last fill of 0xFF.  Every output is compared, byte
@@ -242,9 +243,10 @@ def mixed_runner(known, files, s, rule="full", denoms=None, flags=0, bad_code=EI
     return run
 
 
-def uniform_runner(known, s, host_out=False, chunk=0, n_threads=3):
+def uniform_runner(known, s, host_out=False, chunk=0, n_threads=3, device=0):
     """ffhip_jpeg_decode_files_device (pictures of one geometry into one device allocation) / ffhip_jpeg_decode_files (into pageable host
-    memory through the pipeline's slots): a guard behind every row and behind every picture"""
+    memory through the calling thread's slots): a guard behind every row and behind every picture.  device: the one the run binds its
+    thread to first, and allocates on"""
     L = capi.lib()
     n = len(known)
     W, H = known[0].cw, known[0].ch
@@ -255,16 +257,24 @@ def uniform_runner(known, s, host_out=False, chunk=0, n_threads=3):
     files = [k.data for k in known]
 
     def run():
+        capi.require_device(device)
         bufs, ptrs, lens = ops.file_args(files)
         status, geom = (C.c_int * n)(), capi.JpegGeom()
+        got = np.full(want.size, SF.FILL, np.uint8)
         if host_out:
-            got = np.full(want.size, SF.FILL, np.uint8)
             rc = L.ffhip_jpeg_decode_files(ptrs, lens, n, n_threads, chunk, C.byref(geom), got.ctypes.data, pitch, stride, status)
         else:
-            dev = ops.DeviceBuffer(host=np.full(want.size, SF.FILL, np.uint8))
-            rc = L.ffhip_jpeg_decode_files_device(ptrs, lens, n, n_threads, C.byref(geom), dev.ptr, pitch, stride, status, SF.h(s))
-            capi.sync(SF.h(s))
-            got = dev.to_host((want.size,), np.uint8)
+            dev = L.ffhip_malloc(got.nbytes)                # (not ops.DeviceBuffer: that binds device 0)
+            assert dev
+            try:
+                capi.check(L.ffhip_memcpy_h2d(dev, got.ctypes.data, got.nbytes, None), "ffhip_memcpy_h2d")
+                capi.sync(None)
+                rc = L.ffhip_jpeg_decode_files_device(ptrs, lens, n, n_threads, C.byref(geom), dev, pitch, stride, status, SF.h(s))
+                capi.sync(SF.h(s))
+                capi.check(L.ffhip_memcpy_d2h(got.ctypes.data, dev, got.nbytes, None), "ffhip_memcpy_d2h")
+                capi.sync(None)
+            finally:
+                L.ffhip_free(dev)
         assert rc == 0 and not any(status), (rc, list(status))
         assert (geom.mcu_cols, geom.mcu_rows) == (known[0].mc, known[0].mr)
         assert np.array_equal(got, want), np.flatnonzero(got != want)[:8].tolist()
@@ -287,10 +297,11 @@ def uniform_files():
 @pytest.mark.parametrize("entropy", [None, "0"], ids=["device_huffman", "host_threads"])
 def test_jpeg_files_of_one_geometry(stream, uniform_files, entropy):
     """ffhip_jpeg_decode_files_device: the device Huffman decoder (the subsequence decoder's sync arrays, the header records, the planes in
-    SCRATCH_FILES_DEV), and with FFHIP_JPEG_GPU_ENTROPY=0 the host threads through the pipeline's slots"""
+    SCRATCH_FILES_DEV), and with FFHIP_JPEG_GPU_ENTROPY=0 the host threads through the calling thread's slots (their planes in
+    SCRATCH_FILES_PLANES of the slot streams, which a fill of any stream by this thread reaches)"""
     capi.setenv("FFHIP_JPEG_GPU_ENTROPY", entropy)
     small, larger, marked = uniform_files
-    kinds = ["SCRATCH_HUFF", "SCRATCH_HUFF_SYNC", "SCRATCH_FILES_DEV"] if entropy is None else []
+    kinds = ["SCRATCH_HUFF", "SCRATCH_HUFF_SYNC", "SCRATCH_FILES_DEV"] if entropy is None else ["SCRATCH_FILES_PLANES"]
     SF.run_protocol(f"jpeg files, one geometry, {entropy}", stream, [uniform_runner(larger, stream), uniform_runner(marked, stream)],
                     [uniform_runner(small, stream), uniform_runner(small[:1], stream), uniform_runner(marked[:2], stream)], kinds)
 
@@ -298,11 +309,13 @@ def test_jpeg_files_of_one_geometry(stream, uniform_files, entropy):
 @pytest.mark.parametrize("entropy", [None, "0"], ids=["device_huffman", "host_threads"])
 def test_jpeg_files_through_the_pipeline_slots(uniform_files, entropy):
     """ffhip_jpeg_decode_files: two pictures a chunk, so that both slots take turns (and the second one a last partial chunk); the slots'
-    pinned and device planes, tables and pixels are filled with the NULL stream's scratch"""
+    pinned and device planes, tables and pixels -- and, with the device front end, its staging and sync arrays, which are the slot streams'
+    too -- are filled with the NULL stream's scratch"""
     capi.setenv("FFHIP_JPEG_GPU_ENTROPY", entropy)
     small, larger, _ = uniform_files
+    kinds = ["SCRATCH_FILES_PLANES", "SCRATCH_FILES_PIXELS"] + (["SCRATCH_HUFF", "SCRATCH_HUFF_SYNC"] if entropy is None else [])
     SF.run_protocol(f"jpeg pipeline slots, {entropy}", None, [uniform_runner(larger, None, True, 3)],
-                    [uniform_runner(small, None, True, 2), uniform_runner(small[:1], None, True, 0)])
+                    [uniform_runner(small, None, True, 2), uniform_runner(small[:1], None, True, 0)], kinds)
 
 
 @pytest.mark.parametrize("entropy", [None, "0"], ids=["device_huffman", "host_threads"])
